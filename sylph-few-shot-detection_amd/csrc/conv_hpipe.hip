@@ -5,8 +5,10 @@
 // independent ph x pw patches (<= 128 positions each, shapes picked per pyramid level on the host: 10 x 12 on the
 // 100 x 168 / 50 x 84 maps), one per wave row:
 //
-//   * 8 waves = 2 (patch) x 4 (64-channel column); wave tile 128 x 64 = 4 x 2 MFMA 32x32x16 tiles (128 accumulator
-//     VGPRs): 12 ds_read_b128 per 16 MFMAs.
+//   * 8 waves = 2 (patch) x 4 (64-channel column); wave tile 128 x 64 = 8 x 4 MFMA 16x16x32 tiles (128 accumulator
+//     VGPRs): one k-step of 32 per tap, 12 ds_read_b128 (8 position + 4 weight fragments, 48 VGPRs) per 32 MFMAs.  This
+//     kernel's instruction mix on random data sustains 1.175x the FLOP/s in the 16x16x32 form (profiles/r7_mfma_shape_probe.txt);
+//     in the kernel the change measured as 6-11 % fewer cycles at an unchanged clock (profiles/r7_clock_counters.txt).
 //   * K order: 32-channel half-slice outer, the 9 taps inner.  A operand: the (ph+2) x (pw+2) input halo of each patch
 //     for one half-slice (64-byte rows) is fetched ONCE and all nine taps read shifted rows of it, so the only per-tap
 //     traffic is the weight tile (256 rows x 64 B = 16 KiB): L2->LDS bytes per flop are 0.58x those of a plain
@@ -16,9 +18,9 @@
 //     phase q+3 and (during taps 0..3) one quarter of the next half-slice's halo are issued by global_load_lds right after
 //     the fragment reads of phase q and waited for two phases later with a COUNTED s_waitcnt vmcnt(N): never a drain in
 //     the steady state.  The 9 taps are unrolled, so every N and every tap offset is an immediate.  The loads sit in the
-//     L (fragment read) segment, whose instruction stream has the slack; the M segment is 16 bare MFMAs.  Load addresses
+//     L (fragment read) segment, whose instruction stream has the slack; the M segment is 32 bare MFMAs.  Load addresses
 //     cost no VALU work: weights use a wave-uniform base + a constant per-lane offset, the halo running per-lane pointers.
-//   * The two wave rows (the two waves that share a SIMD) run staggered by one barrier: while one issues its 16
+//   * The two wave rows (the two waves that share a SIMD) run staggered by one barrier: while one issues its 32
 //     MFMAs (s_setprio 1) the other does its fragment reads and address arithmetic.  Raw s_barrier + explicit
 //     waitcnts only (a __syncthreads would drain the LDS-DMA queue).
 //
@@ -38,14 +40,21 @@
 // over all channels).  Blocks also start the K loop at different half-slices (rotation by tile index), which spreads the
 // 64-byte-per-512-byte halo rows of concurrently running blocks over the channels.
 //
-// LDS images (lane-linear global_load_lds, swizzle on the SOURCE side, same XOR on the fragment reads):
-//   weights [256 rows][64 B]: slot s of row r holds 16-byte chunk s ^ ((r >> 2) & 3) (applied by the re-pack);
-//   halo    [2 patches][256 rows][64 B], row h = hy * (pw + 4) + hx: slot s holds chunk s ^ ((k >> 2) & 3), k = hy * pw + hx.
-//           The reader of tap (kh, kw) at patch position m sits on k = m + kh * pw + kw; the 16 lanes of a ds_read_b128
-//           group ({0-3, 12-15, 20-27} + ...) hold 16 distinct k mod 16.  The 16-byte bank slot of a read is
-//           (h & 3) * 4 + slot, and with the pitch pw + 4 (two unused entries per halo row) h = k + 4 hy, so it depends on
-//           k mod 16 only: conflict-free for every patch shape.  (Pitch pw + 2 made it depend on the parity of hy: measured
-//           35 % of all LDS cycles were bank conflicts, SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE.)
+// LDS images (lane-linear global_load_lds, swizzle on the SOURCE side, same XOR on the fragment reads).  A 16x16x32 operand
+// read gives lane l row l & 15 and 16-byte chunk c = l >> 4; the 16 lanes of a ds_read_b128 group are rows {0-3, 12-15}
+// with chunk c0 and rows {4-11} with chunk c0 ^ 1 ({0-3, 12-15, 20-27}: c0 = 0, {4-11, 16-19, 28-31}: c0 = 1, + 32: c0 ^ 2).
+// With 64-byte rows the 16-byte bank slot of slot s in a row with key x is (x & 3) * 4 + s (below: the row index equals the
+// key mod 4), so the four lanes of one key residue, keys x, x + 12 (chunk c0) and x + 4, x + 8 (chunk c0 ^ 1) for some x,
+// need four distinct slots.  The swizzle
+//   slot = chunk ^ sw(key),  sw(key) = ((key >> 2) & 1) << 1
+// gives them c0 ^ {a, a ^ 2} and c0 ^ 1 ^ {a ^ 2, a}: distinct, for EVERY x, so a read stays conflict-free when all its
+// keys are shifted by the same amount.  (The 32x32x16 swizzle chunk ^ ((key >> 2) & 3) is 2-way on this read pattern.)
+//   weights [256 rows][64 B]: key = row r (applied by the re-pack);
+//   halo    [2 patches][256 rows][64 B], row h = hy * (pw + 4) + hx: key k = hy * pw + hx.  The reader of tap (kh, kw) at patch
+//           position m sits on k = m + kh * pw + kw, and with the pitch pw + 4 (two unused entries per halo row) h = k + 4 hy,
+//           so h & 3 = k & 3 and a read's slots depend on (m + kh * pw + kw) mod 16 only: conflict-free for every tap and
+//           every patch shape (tests/test_hpipe_mfma16_swizzle.py enumerates them).  (Pitch pw + 2 made the slot depend on
+//           the parity of hy: measured 35 % of all LDS cycles were bank conflicts, SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE.)
 //
 // Scope (launch_conv checks): bf16 in/out, 3x3 s1 p1, no residual, no per-segment Scale, ReLU on all channels or none,
 // Cout % 256 == 0, Cin % 32 == 0, padded scale/shift; optional fused GroupNorm partial statistics (one per patch).
@@ -123,7 +132,7 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
-  const int l31 = lane & 31, lh = lane >> 5;
+  const int l15 = lane & 15, lq = lane >> 4;  // MFMA 16x16x32 operand row / 16-byte k chunk of this lane
 
   int2 tl0 = a.tiles[2 * mt], tl1 = a.tiles[2 * mt + 1];
   const int rot_key = (int)((unsigned)tl0.x >> 20);  // index of this pair inside its image (api_conv.hip make_geom_patch)
@@ -158,7 +167,7 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
     const int hy = (int)(((unsigned)h * sd.inv_hw2) >> 16), hx = h - hy * HP;
     const int iy = (ty >> 16) - 1 + hy, ix = (ty & 0xffff) - 1 + hx;
     const bool ok = h < HR && hx < PW + 2 && (unsigned)iy < (unsigned)sd.in_H && (unsigned)ix < (unsigned)sd.in_W;
-    const int cs = s4 ^ (((hy * PW + hx) >> 2) & 3);
+    const int cs = s4 ^ ((((hy * PW + hx) >> 2) & 1) << 1);
     hcs |= (unsigned)cs << (2 * g);
     hptr[g] = ok ? reinterpret_cast<const char*>(in + ((size_t)(sd.in_row0 + iy * sd.in_W + ix) * a.in_ld + cs * 8 + goff + c0 * 32))
                  : reinterpret_cast<const char*>(zero + s4 * 8);
@@ -197,7 +206,9 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
   // bf16(relu(a * x + b)).  Lanes on the zero page (conv padding, halo pad entries) are skipped: the padding of the
   // NORMALISED tensor is zero.  Readers see the result after the next lgkmcnt(0) + barrier, phases before its first use.
   constexpr bool gn_in = GNIN;  // the plain instantiation carries none of this
-  const bool gn_relu = a.gn_relu != 0;
+  // ReLU (or none) on a bf16 pair as a packed signed 16-bit max with a wave-uniform floor: 0 clears negative values (sign bit set),
+  // -32768 passes every value.  Unconditional, so the transform carries no select between the two forms (fewer VALU per MFMA gap).
+  const short gn_floor = a.gn_relu != 0 ? (short)0 : (short)-32768;
   // The LDS accesses are inline asm: for a compiler-visible ds_read hipcc inserts s_waitcnt vmcnt(0) (it must assume the
   // LDS-DMA still in flight aliases the read), which would drain the whole load pipeline in 4 of 9 phases.  The data read
   // here was fetched by THIS lane and retired by this wave's counted vmcnt two phases ago; the lgkmcnt wait is tied to the
@@ -231,13 +242,9 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
       const f32x2v xv = {__uint_as_float(gx[e] << 16), __uint_as_float(gx[e] & 0xffff0000u)};
       const f32x2v av = {cs[e][0], cs[e][1]}, bv = {cs[e][2], cs[e][3]};
       const f32x2v r = __builtin_elementwise_fma(xv, av, bv);
-      bf16x2 pk;
-      pk[0] = (bf16_t)r[0]; pk[1] = (bf16_t)r[1];
-      unsigned u = __builtin_bit_cast(unsigned, pk);
-      if (gn_relu) {  // ReLU on the bf16 pair: packed signed max with 0
-        const s16x2v z = {0, 0};
-        u = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2v, u), z));
-      }
+      const bf16x2 pk = __builtin_convertvector(r, bf16x2);  // one v_cvt_pk_bf16_f32 (round to nearest even, as the casts)
+      const s16x2v fl = {gn_floor, gn_floor};
+      const unsigned u = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2v, pk), fl));
       y[e] = u & live;
     }
     asm volatile("ds_write_b128 %0, %1" ::"v"(gn_addr(g, cc_of_piece)), "v"(y) : "memory");
@@ -247,43 +254,42 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
   // ---- fragment addressing -----------------------------------------------------------------------------------------
   const SegDesc& sdm = wm ? sd1 : sd0;  // this wave row's patch
   const int PWm = sdm.pw, HW2m = sdm.hpitch;
-  int a0[4];
+  int a0[8];  // position fragment i: patch position m = 16 i + l15
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = i * 32 + l31;
+  for (int i = 0; i < 8; ++i) {
+    const int m = i * 16 + l15;
     const int my = (int)(((unsigned)m * sdm.inv_pw) >> 16);
     a0[i] = (wm * HPROWS + my * HW2m + (m - my * PWm)) * 64;
   }
-  int offB[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) offB[ks] = (wn * 64 + l31) * 64 + (((ks * 2 + lh) ^ ((l31 >> 2) & 3)) << 4);
+  // weight fragment j: output channel wn * 64 + 16 j + l15 (16 j keeps the row's swizzle key)
+  const int offB = (wn * 64 + l15) * 64 + ((lq ^ (((l15 >> 2) & 1) << 1)) << 4);
 
-  f32x16 acc[4][2];
+  f32x4 acc[8][4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  bf16x8 fa[2][4], fb[2][2];
+      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+  bf16x8 fa[8], fb[4];
 
   // L(cc, t): the 12 fragment reads of tap t of half-slice cc
   auto ldfrag = [&](int cc, int t) {
     const int kh = t / 3, kw = t - 3 * kh;
     const char* bs = smem + ((cc + t) & 3) * BSTAGE;  // phase q = 9 cc + t; q & 3 == (cc + t) & 3
     const char* hs = smem + HALO_OFF + (cc & 1) * HBUF + (kh * HW2m + kw) * 64;
-    const int f = ((l31 + kh * PWm + kw) >> 2) & 3;
+    // swizzle key k = 16 i + l15 + kh * pw + kw: bit 2 of it does not depend on i.  Recomputed per tap (three VALU): hoisted
+    // out of the K loop, the nine per-tap values cost nine VGPRs the kernel does not have (they were spilled to scratch).
+    int key = l15;
+    asm volatile("" : "+v"(key));
+    const int so = (lq ^ ((((key + kh * PWm + kw) >> 2) & 1) << 1)) << 4;
 #ifdef HP_NOLDS
     if (cc + t > 0) return;
 #endif
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int so = ((ks * 2 + lh) ^ f) << 4;
+    for (int j = 0; j < 4; ++j) fb[j] = *reinterpret_cast<const bf16x8*>(bs + offB + j * 1024);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) fb[ks][j] = *reinterpret_cast<const bf16x8*>(bs + offB[ks] + j * 2048);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fa[ks][i] = *reinterpret_cast<const bf16x8*>(hs + a0[i] + so);
-    }
+    for (int i = 0; i < 8; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(hs + a0[i] + so);
   };
 
   // The loads of phase q+3 = tap t+3 (weights into stage (q+3) & 3) and, on taps 0..2, piece t of the next half-slice's
@@ -298,36 +304,38 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
     issue_w(st3, 0, blk);
     issue_w(st3, 1, blk);
   };
-  // M(cc, t): 16 back-to-back MFMAs.  With a fused input GroupNorm, taps 3..6 also transform halo piece t - 3 of the next
+  // M(cc, t): 32 back-to-back MFMAs.  With a fused input GroupNorm, taps 3..6 also transform halo piece t - 3 of the next
   // half-slice (landed: its load was issued in L(cc, t - 3) and retired by this wave's counted wait two phases later); the
-  // ~40 VALU / LDS instructions are spread between the MFMAs (sched_group_barrier), where the wave has free issue slots.
+  // ~30 VALU / LDS instructions are spread between the MFMAs (sched_group_barrier), where the wave has free issue slots.  A
+  // 16x16x32 MFMA holds the SIMD's issue for 8 of its 16 cycles, which leaves room for about two 4-cycle VALU per gap (shared
+  // with the partner wave's L segment): the transform goes at most two per gap over MFMAs 8..23.  (Its 32x32x16 form had ~40
+  // VALU at four per gap; packed at three per gap here it cost the GroupNorm-in launches most of the shape's gain.  Spreading
+  // those 40 over more gaps made the compiler spill to scratch inside the K loop, whose reloads wait with vmcnt(0).)
   auto mma = [&](int cc, int t) {
     __builtin_amdgcn_s_setprio(1);
     // (unconditional on the last half-slice too: it then rewrites the re-read copy in the buffer nobody reads any more)
     const bool xf = gn_in && t >= 3 && t < 3 + NPIECE;
-    if (xf) {  // the five LDS reads go out first; their latency hides behind the first four MFMAs
+    if (xf) {  // the five LDS reads go out first; their latency hides behind the first eight MFMAs
       gn_read(t - 3, cc + 1);
       HP_SCHED_FENCE;
     }
     int n = 0;
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+    for (int i = 0; i < 8; ++i)
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[ks][j], fa[ks][i], acc[i][j], 0, 0, 0);  // D^T
-          if (xf && n == 3) {
-            HP_SCHED_FENCE;
-            gn_finish(t - 3, cc + 1);  // ~40 VALU + one LDS write, spread between the remaining MFMAs below
-          }
-          ++n;
+      for (int j = 0; j < 4; ++j) {
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);  // D^T
+        if (xf && n == 7) {
+          HP_SCHED_FENCE;
+          gn_finish(t - 3, cc + 1);  // ~30 VALU + one LDS write, spread between the following MFMAs
         }
+        ++n;
+      }
     if (xf) {
 #pragma unroll
-      for (int k = 0; k < 12; ++k) {
+      for (int k = 0; k < 16; ++k) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);  // up to four VALU
+        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);  // up to two VALU
       }
     }
     __builtin_amdgcn_s_setprio(0);
@@ -337,8 +345,8 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
   // of the L segment): otherwise it inserts its own s_waitcnt lgkmcnt(0) at the first MFMA of the M segment, behind the
   // GroupNorm transform's LDS reads issued there, and their latency is exposed again.
   auto frags_ready = [&]() {
-    asm volatile("" ::"v"(fa[0][0]), "v"(fa[0][1]), "v"(fa[0][2]), "v"(fa[0][3]), "v"(fa[1][0]), "v"(fa[1][1]), "v"(fa[1][2]),
-                 "v"(fa[1][3]), "v"(fb[0][0]), "v"(fb[0][1]), "v"(fb[1][0]), "v"(fb[1][1]));
+    asm volatile("" ::"v"(fa[0]), "v"(fa[1]), "v"(fa[2]), "v"(fa[3]), "v"(fa[4]), "v"(fa[5]), "v"(fa[6]), "v"(fa[7]), "v"(fb[0]),
+                 "v"(fb[1]), "v"(fb[2]), "v"(fb[3]));
   };
 
   // ---- prologue: halo of half-slice 0 and the weights of phases 0..2 ---------------------------------------------
@@ -445,17 +453,14 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
 #pragma unroll
     for (int hp = 0; hp < 2; ++hp) {  // 64-row half of the patch
       if (pp + hp > 0) lds_barrier();
-      if (wm == pp) {
+      if (wm == pp) {  // 16x16x32 accumulator layout: position 16 i + l15, channels 16 j + 4 lq .. + 3
 #pragma unroll
-        for (int ii = 0; ii < 2; ++ii)
+        for (int ii = 0; ii < 4; ++ii)
 #pragma unroll
-          for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const f32x16& c = acc[2 * hp + ii][j];
-              *reinterpret_cast<float4*>(sC + (ii * 32 + l31) * SCP + wn * 64 + j * 32 + 8 * g + 4 * lh) =
-                  make_float4(c[4 * g], c[4 * g + 1], c[4 * g + 2], c[4 * g + 3]);
-            }
+          for (int j = 0; j < 4; ++j) {
+            const f32x4& c = acc[4 * hp + ii][j];
+            *reinterpret_cast<float4*>(sC + (ii * 16 + l15) * SCP + wn * 64 + j * 16 + 4 * lq) = make_float4(c[0], c[1], c[2], c[3]);
+          }
       }
       lds_barrier();
 #pragma unroll
@@ -522,6 +527,7 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
 }
 
 // [Cout][3][3][Cin] bf16 (conv_igemm layout) -> [Cout / 256][Cin / 32][9][256 rows][4 slots][8] with the stage swizzle applied
+// (slot s of row r holds chunk s ^ sw(r), "LDS images" above)
 __global__ void hpipe_pack_weights_kernel(const bf16_t* __restrict__ w, bf16_t* __restrict__ out, int Cout, int Cin) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // one 16-byte chunk
   const size_t nchunks = (size_t)Cout * 9 * Cin / 8;
@@ -530,7 +536,7 @@ __global__ void hpipe_pack_weights_kernel(const bf16_t* __restrict__ w, bf16_t* 
   const int s = (int)(i & 3), r = (int)((i >> 2) & 255);
   const size_t blk = i >> 10;
   const int t = (int)(blk % 9), c = (int)((blk / 9) % ncc), nt = (int)(blk / (9 * (size_t)ncc));
-  const int chunk = s ^ ((r >> 2) & 3);
+  const int chunk = s ^ (((r >> 2) & 1) << 1);
   const uint4 v = *reinterpret_cast<const uint4*>(w + ((size_t)(nt * 256 + r) * 9 + t) * Cin + c * 32 + chunk * 8);
   *reinterpret_cast<uint4*>(out + i * 8) = v;
 }

@@ -1,6 +1,8 @@
 // MEASUREMENT PROBE, not part of the product (round-2 experiment "four-wave 128x128-wave-tile variant", git 054d86d, rebuilt against the
 // round-5 tree by tools/probes/build_hq.sh for profiles/r5_tower_four_wave.txt).
 // Four-wave variant of conv_hpipe.hip (same tile, same LDS images, same weight stage images, same geometry tables):
+// NOTE: it reads the 32x32x16-era images (slot s holds chunk s ^ ((key >> 2) & 3)); since conv_hpipe.hip moved to 16x16x32 MFMAs
+// (round 7) the product's re-pack writes chunk s ^ (((key >> 2) & 1) << 1), so a rebuild needs that swizzle here first.
 //
 // conv_hpipe_kernel's fragment-read segment is LDS-bandwidth bound: a 128 x 64 wave tile needs 12 ds_read_b128 per 16 MFMAs,
 // four waves are in that segment at a time (48 KiB) while the weight / halo DMA writes another ~20 KiB -- ~530 cycles of LDS
