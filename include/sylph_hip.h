@@ -74,6 +74,9 @@ typedef struct sylph_config {
   int cg_tower_gn_mask;    /* CODE_GENERATOR.TOWER_LAYERS[i][0] == "GN"   -> bit i (sylph_config_default: all ones = ["GN", "ReLU"] layers); */
   int cg_tower_relu_mask;  /* CODE_GENERATOR.TOWER_LAYERS[i][1] == "ReLU" -> bit i.  A layer without norm / activation has no such module
                               in support_set_shared_tower, whose nn.Sequential indices advance per EXISTING module (code_generator.py:648-688) */
+  int tower_deformable;    /* MODEL.FCOS.USE_DEFORMABLE: the LAST conv of the cls and of the bbox tower is a modulated deformable conv (adet
+                              DFConv2d, DCNv2): keys {k}.offset.weight / .bias [27,256,3,3] and {k}.conv.weight / .bias instead of {k}.weight
+                              / .bias (fcos.py:83-84).  Not with the paired-tower mode. */
 } sylph_config;
 
 /* Fill cfg with the defaults of the COCO Meta-FCOS finetune yaml. */

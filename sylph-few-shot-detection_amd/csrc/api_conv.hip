@@ -465,8 +465,15 @@ int add_conv_gn(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const 
                        OpFn* apply_out) {
   o.want_gn = 1;
   Geom g;
-  const int ld = L.Cout, ngroups = L.Cout / 8;
-  RET(add_conv(c, ops, L, in, in_ld, out, ld, segs, o, &g));
+  RET(add_conv(c, ops, L, in, in_ld, out, L.Cout, segs, o, &g));
+  return add_gn_from_partials(c, ops, out, L.Cout, segs, g, G, relu, coef_out, apply_out);
+}
+
+// the GroupNorm of a conv whose epilogue left per-M-tile partials in g.gn_partial (conv_igemm / conv_hpipe / conv_deform): finalize +
+// in-place apply, or (coef_out) the (a, b) table for the next consumer and optionally (apply_out) the stand-alone apply
+int add_gn_from_partials(sylph_ctx* c, std::vector<OpFn>& ops, void* out, int ld, const std::vector<SegDesc>& segs, const Geom& g, const GNLayer& G, int relu,
+                         const float2** coef_out, OpFn* apply_out) {
+  const int ngroups = ld / 8;
   const float* partial = g.gn_partial;
   std::vector<GnSeg> gs;
   int max_rows = 0;
@@ -497,6 +504,35 @@ int add_conv_gn(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const 
     return launch_gn_apply_partials(dt, out, ld, ngroups, gsd, nseg, max_rows, partial, stats_ws, ga, be, 1e-5f, relu, s);
   });
   return 0;
+}
+
+// Modulated deformable 3x3 conv (MODEL.FCOS.USE_DEFORMABLE tower layer): the offset conv (27 channels, fp32 output: offsets of a few
+// pixels must not be rounded to bf16) through add_conv, then conv_deform.hip with bias (+ ReLU) and, when G is given, the GroupNorm
+// partials of its epilogue followed by the same GroupNorm handling as add_conv_gn.  `in` is the layer input after its GroupNorm + ReLU.
+int add_conv_deform(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& off, const ConvLayer& L, const void* in, void* out,
+                    const std::vector<SegDesc>& segs, int segs_per_image, const GNLayer* G, int relu, const float2** coef_out, OpFn* apply_out) {
+  if (off.Cout != 27 || off.Cin != 256 || off.KH != 3 || L.Cin != 256 || L.Cout != 256 || L.KH != 3 || L.KW != 3)
+    return fail("internal: deformable tower layer shapes");
+  long rows = 0;
+  for (auto& s : segs) rows = std::max(rows, (long)s.out_row0 + (long)s.out_H * s.out_W);
+  float* om = nullptr;
+  RET(c->dalloc((void**)&om, (size_t)rows * off.Cout_pad * sizeof(float)));
+  ConvOpts oo; oo.pad = 1; oo.out_f32 = true; oo.segs_per_image = segs_per_image;
+  RET(add_conv(c, ops, off, in, 256, om, off.Cout_pad, segs, oo));
+  Geom g;
+  RET(make_geom(c, segs, 128, &g));
+  if (G) RET(c->dalloc((void**)&g.gn_partial, (size_t)(g.n_mtiles + 1) * 32 * 3 * sizeof(float)));
+  DeformArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = in; a.om = om; a.om_ld = off.Cout_pad; a.wt = L.w; a.bias = L.shift; a.out = out; a.zeros = c->zeros;
+  a.segs = g.segs; a.tiles = g.tiles; a.n_mtiles = g.n_mtiles; a.gn_partial = g.gn_partial; a.relu = relu && !G;
+  long real = 0;
+  for (auto& s : segs) real += (long)s.out_H * s.out_W;
+  const double flops = 2.0 * (double)real * 256.0 * 9.0 * 256.0;
+  const DType dt = c->dt;
+  ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_deform_kernel", flops, s, [=](hipStream_t st) { return launch_conv_deform(dt, a, st); }); });
+  if (!G) return 0;
+  return add_gn_from_partials(c, ops, out, 256, segs, g, *G, relu, coef_out, apply_out);
 }
 
 std::vector<SegDesc> image_segs(int B, int Hin, int Win, int Hout, int Wout, int resH, int resW) {

@@ -131,6 +131,7 @@ void sylph_config_default(sylph_config* cfg) {
   cfg->cg_has_weight = 0; cfg->cg_has_scale = 0;
   cfg->num_share_convs = 0; cfg->tower_norm = 0;
   cfg->cg_tower_gn_mask = 0x3fffffff; cfg->cg_tower_relu_mask = 0x3fffffff;  // every TOWER_LAYERS entry is ["GN", "ReLU"]
+  cfg->tower_deformable = 0;
 }
 
 const char* sylph_last_error(void) { return g_err.c_str(); }

@@ -64,15 +64,17 @@ int build_head(sylph_ctx* c, Plan* P) {
   auto& ops = P->head_ops;
   const bool tower_gn = c->cfg.tower_norm == 0;  // MODEL.FCOS.NORM "GN"; otherwise "none": conv + bias + ReLU layers
   const void* tower_in = P->F;                    // what the cls / bbox towers read: the pyramid, or the shared tower's output
+  // doff: MODEL.FCOS.USE_DEFORMABLE -- the offset conv of the tower's deformable last layer (nullptr: a plain tower)
   auto tower = [&](int which, const std::vector<ConvLayer>& convs, const std::vector<GNLayer>& gns, void* b0, void* b1,
-                   void** last, const float2** coef_last, OpFn* apply_last) -> int {
+                   void** last, const float2** coef_last, OpFn* apply_last, const ConvLayer* doff) -> int {
     const bool defer_last = coef_last != nullptr;
     const void* in = tower_in;
     void* out = b0;
     if (!tower_gn) {  // no norm layer: the ReLU is the conv epilogue's
       for (size_t i = 0; i < convs.size(); ++i) {
         ConvOpts o; o.pad = 1; o.segs_per_image = c->cfg.nlevels; o.relu_nch = 1 << 30;
-        RET(add_conv(c, ops, convs[i], in, 256, out, 256, segs, o));
+        if (doff && i + 1 == convs.size()) RET(add_conv_deform(c, ops, *doff, convs[i], in, out, segs, c->cfg.nlevels, nullptr, 1));
+        else RET(add_conv(c, ops, convs[i], in, 256, out, 256, segs, o));
         if (which < 2) { P->tap_out[which].push_back(out); P->tap_coef[which].push_back(nullptr); }
         in = out;
         out = (out == b0) ? b1 : b0;
@@ -84,6 +86,8 @@ int build_head(sylph_ctx* c, Plan* P) {
     // GroupNorm + ReLU of layers 0 .. n-2 are applied by the NEXT layer's conv to its input halo in LDS (conv_hpipe.hip):
     // no separate streaming pass over those tensors.  The last layer keeps its apply pass (its readers are the
     // prediction convs and the class-conditional 1x1 conv).
+    // A deformable last layer (doff) reads its input twice, through the offset conv and through the gather of conv_deform.hip: layer
+    // n - 2 keeps its own GroupNorm apply pass so that this input is materialised once.
     static const int gn_fuse_on = getenv("SYLPH_GN_FUSE") ? atoi(getenv("SYLPH_GN_FUSE")) : 1;
     ConvOpts probe; probe.pad = 1;
     const bool fuse = gn_fuse_on && convs.size() > 1 && convs[0].Cin <= 512 && use_hpipe(c, convs[1], segs, probe);
@@ -93,9 +97,13 @@ int build_head(sylph_ctx* c, Plan* P) {
       if (coef_prev) { o.gn_coef = coef_prev; o.gn_relu = 1; }
       const float2* coef = nullptr;
       const bool is_last = i + 1 == convs.size();
-      const bool defer = (fuse && !is_last) || (is_last && defer_last);
+      const bool feeds_deform = doff && i + 2 == convs.size();
+      const bool defer = (fuse && !is_last && !feeds_deform) || (is_last && defer_last);
       OpFn apply;
-      RET(add_conv_gn(c, ops, convs[i], in, 256, out, segs, o, gns[i], 1, defer ? &coef : nullptr, (is_last && defer_last) ? &apply : nullptr));
+      if (doff && is_last)
+        RET(add_conv_deform(c, ops, *doff, convs[i], in, out, segs, c->cfg.nlevels, &gns[i], 1, defer ? &coef : nullptr, defer_last ? &apply : nullptr));
+      else
+        RET(add_conv_gn(c, ops, convs[i], in, 256, out, segs, o, gns[i], 1, defer ? &coef : nullptr, (is_last && defer_last) ? &apply : nullptr));
       if (is_last && defer_last) { *coef_last = coef; *apply_last = apply; }
       coef_prev = coef;
       if (which < 2) { P->tap_out[which].push_back(out); P->tap_coef[which].push_back(coef); }
@@ -147,7 +155,7 @@ int build_head(sylph_ctx* c, Plan* P) {
       void *s0 = nullptr, *s1 = nullptr, *share_out = nullptr;
       RET(c->dalloc(&s0, rows * 256 * e));
       RET(c->dalloc(&s1, rows * 256 * e));
-      RET(tower(2, c->share_tower, c->share_gn, s0, s1, &share_out, nullptr, nullptr));
+      RET(tower(2, c->share_tower, c->share_gn, s0, s1, &share_out, nullptr, nullptr, nullptr));
       tower_in = share_out;
     }
     // Small batches (SylphPredictor and the reference's query loop run batch 1, meta_learn_evaluation.py:421-426, predictor.py:248-274):
@@ -168,14 +176,16 @@ int build_head(sylph_ctx* c, Plan* P) {
         if (hipEventRecord(c->ev_fork, s) != hipSuccess || hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) != hipSuccess) return -101;
         return 0;
       });
-    RET(tower(0, c->cls_tower, c->cls_gn, P->tA, P->tB, &cls_feat, (defer && !c->cls_tower.empty()) ? &P->cls_coef : nullptr, &cls_apply));
+    RET(tower(0, c->cls_tower, c->cls_gn, P->tA, P->tB, &cls_feat, (defer && !c->cls_tower.empty()) ? &P->cls_coef : nullptr, &cls_apply,
+              c->cls_off.Cout ? &c->cls_off : nullptr));
     P->cls_apply = cls_apply;
     box_defer = defer && c->pred_taps && !c->box_tower.empty();
     side_from = ops.size();
     // from here to the join the ops run on the side stream: a split-K conv among them (towers without GroupNorm, the prediction conv)
     // must take the side stream's partial-plane scratch, not the one the cls tower is using at the same time
     c->build_slot = two_streams ? 1 : 0;
-    RET(tower(1, c->box_tower, c->box_gn, P->tC, P->tD, &box_feat, box_defer ? &box_coef : nullptr, &box_apply));
+    RET(tower(1, c->box_tower, c->box_gn, P->tC, P->tD, &box_feat, box_defer ? &box_coef : nullptr, &box_apply,
+              c->box_off.Cout ? &c->box_off : nullptr));
   }
   P->cls_ld = feat_ld;
   Geom g32;  // 128-row pointwise tiles of the pyramid (class-conditional conv with N <= 32, fused GN + prediction pass)

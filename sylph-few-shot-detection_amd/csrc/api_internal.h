@@ -103,6 +103,7 @@ struct sylph_ctx {
   std::vector<ConvLayer> cls_tower, box_tower, share_tower;  // share_tower: MODEL.FCOS.NUM_SHARE_CONVS layers in front of both
   std::vector<GNLayer> share_gn;
   std::vector<GNLayer> cls_gn, box_gn;
+  ConvLayer cls_off, box_off;  // MODEL.FCOS.USE_DEFORMABLE: offset conv of the last cls / bbox tower layer (27 channels; Cout == 0: plain tower)
   std::vector<ConvLayer> pair_tower;  // cls|bbox towers stacked on Cout (layer 0 shares the input, then grouped)
   std::vector<GNLayer> pair_gn;
   bool paired = false;
@@ -323,6 +324,11 @@ int timed_op(sylph_ctx* c, const char* kern, double flops, hipStream_t s, const 
 bool use_hpipe(sylph_ctx* c, const ConvLayer& L, const std::vector<SegDesc>& segs, const ConvOpts& o);
 int add_conv(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, int in_ld, void* out, int out_ld, const std::vector<SegDesc>& segs, const ConvOpts& o, Geom* geom_out = nullptr);
 int add_conv_gn(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, int in_ld, void* out, const std::vector<SegDesc>& segs, ConvOpts o, const GNLayer& G, int relu, const float2** coef_out = nullptr, OpFn* apply_out = nullptr);
+int add_gn_from_partials(sylph_ctx* c, std::vector<OpFn>& ops, void* out, int ld, const std::vector<SegDesc>& segs, const Geom& g, const GNLayer& G, int relu,
+                         const float2** coef_out, OpFn* apply_out);
+int add_conv_deform(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& off, const ConvLayer& L, const void* in, void* out,
+                    const std::vector<SegDesc>& segs, int segs_per_image, const GNLayer* G, int relu, const float2** coef_out = nullptr,
+                    OpFn* apply_out = nullptr);
 std::vector<SegDesc> image_segs(int B, int Hin, int Win, int Hout, int Wout, int resH = 0, int resW = 0);
 // api_backbone.hip
 int ensure_pyramid(sylph_ctx* c, Plan* P);

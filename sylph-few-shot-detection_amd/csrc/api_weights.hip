@@ -268,12 +268,38 @@ int sylph_finalize_weights(sylph_ctx* c) {
     struct { const char* name; std::vector<ConvLayer>* convs; std::vector<GNLayer>* gns; int n; } towers[3] = {
         {".cls_tower.", &c->cls_tower, &c->cls_gn, c->cfg.num_cls_convs}, {".bbox_tower.", &c->box_tower, &c->box_gn, c->cfg.num_box_convs},
         {".share_tower.", &c->share_tower, &c->share_gn, c->cfg.num_share_convs}};
-    for (auto& t : towers)
+    ConvLayer* offs[3] = {&c->cls_off, &c->box_off, nullptr};
+    c->cls_off = ConvLayer(); c->box_off = ConvLayer();
+    for (int ti = 0; ti < 3; ++ti) {
+      auto& t = towers[ti];
       for (int i = 0; i < t.n; ++i) {
-        RET(make_conv_bias(c, {hp + t.name + std::to_string(step * i)}, &(*t.convs)[i]));
+        const std::string k = hp + t.name + std::to_string(step * i);
+        if (c->cfg.tower_deformable && offs[ti] && i + 1 == t.n) {
+          // MODEL.FCOS.USE_DEFORMABLE (fcos.py:83-84): the last conv is adet's DFConv2d -- offset conv (27 = 2 x 9 offsets + 9 mask
+          // logits) and the modulated deformable conv itself (conv_deform.hip)
+          for (const char* sfx : {".offset.weight", ".offset.bias", ".conv.weight", ".conv.bias"})
+            if (!find_w(c, k + sfx)) return fail("MODEL.FCOS.USE_DEFORMABLE: missing checkpoint key " + k + sfx);
+          const HostTensor *ow = find_w(c, k + ".offset.weight"), *cw = find_w(c, k + ".conv.weight");
+          if (ow->shape != std::vector<int64_t>{27, 256, 3, 3}) return fail(k + ".offset.weight must be [27, 256, 3, 3] (modulated, one deformable group)");
+          if (cw->shape != std::vector<int64_t>{256, 256, 3, 3}) return fail(k + ".conv.weight must be [256, 256, 3, 3]");
+          if (find_w(c, k + ".offset.bias")->data.size() != 27 || find_w(c, k + ".conv.bias")->data.size() != 256)
+            return fail(k + ".offset.bias / .conv.bias must have 27 / 256 elements");
+          RET(make_conv_bias(c, {k + ".offset"}, offs[ti]));
+          // split-bf16 parity mode: conv_deform.hip runs this layer with exact fp32 MFMAs on fp32-packed weights
+          const DType keep = c->dt;
+          if (keep == DT_F32S) c->dt = DT_F32;
+          const int rc = make_conv_bias(c, {k + ".conv"}, &(*t.convs)[i]);
+          c->dt = keep;
+          RET(rc);
+        } else {
+          RET(make_conv_bias(c, {k}, &(*t.convs)[i]));
+        }
         if (gn) RET(make_gn(c, hp + t.name + std::to_string(step * i + 1), &(*t.gns)[i]));
       }
+    }
     const int pair_on = SYLPH_AB_ENV("SYLPH_PAIR_TOWERS", 0);  // A/B knob (-DSYLPH_ABLATE builds only)
+    if (pair_on == 1 && c->cfg.tower_deformable)
+      return fail("the paired-tower mode (SYLPH_PAIR_TOWERS=1) cannot run deformable towers (MODEL.FCOS.USE_DEFORMABLE)");
     // Pairing (both towers as ONE grouped launch per layer) paid +2 % with the pre-halo kernel (the A tile was shared by
     // four N tiles); with halo tiles the separate towers are 1 % faster (1 666-1 672 vs 1 645-1 660 img/s), so it is opt-in.
     if (c->cfg.num_cls_convs == c->cfg.num_box_convs && c->cfg.num_cls_convs > 0 && pair_on == 1) {

@@ -105,6 +105,24 @@ int launch_export_nchw(DType dt, const void* src, float* dst, int C, int HW, int
 int launch_export_nchw_f32(const float* src, float* dst, int C, int HW, int row0, int ld, int ch0, hipStream_t s);
 int launch_pack_codes(DType dt, const float* w, int N, int C, int Npad, void* out, const float* bias, float* bias_pad, float* bias_scan, hipStream_t s);
 
+// conv_deform.hip: modulated deformable 3x3 conv (DCNv2, deformable FCOS tower layer), 256 -> 256 channels, stride 1, pad 1.
+// x: the layer input [rows][256] (storage dtype), om: its offset-conv output [rows][om_ld] fp32 (dy, dx of tap j in 2j, 2j + 1,
+// mask logits in 18 .. 26), wt: the conv_igemm weight layout [256][3][3][256] (fp32 in DT_F32 and DT_F32S), out: [rows][256];
+// tiles: 128-row tiles of the segments (make_geom), gn_partial: optional [n_mtiles][32][3] GroupNorm partials (n, mean, M2)
+struct DeformArgs {
+  const void* x;
+  const float* om;
+  const void* wt;
+  const float* bias;
+  void* out;
+  const void* zeros;  // >= 128 B of zeros
+  const SegDesc* segs;
+  const int2* tiles;
+  float* gn_partial;
+  int n_mtiles, om_ld, relu;
+};
+int launch_conv_deform(DType dt, const DeformArgs& a, hipStream_t s);
+
 // detect.hip
 // many-way class-conditional conv fused with the scan (detect.hip); x: raw cls-tower output, coef: its GroupNorm (a, b) per
 // (segment, channel), w: packed codes [>= 32 * ceil(N/32)][256] bf16, wf_ws: as many bytes of workspace (the codes in MFMA

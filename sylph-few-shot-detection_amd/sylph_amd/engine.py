@@ -35,8 +35,8 @@ def config_from_cfg(cfg) -> SylphConfig:
     sc.num_cls_convs = int(f.NUM_CLS_CONVS)
     sc.num_box_convs = int(f.NUM_BOX_CONVS)
     sc.num_share_convs = int(f.NUM_SHARE_CONVS)
-    if bool(f.USE_DEFORMABLE):
-        raise NotImplementedError("MODEL.FCOS.USE_DEFORMABLE is not supported")
+    # the last conv of the cls and of the bbox tower becomes adet's modulated deformable DFConv2d (fcos.py:83-84, 391-395)
+    sc.tower_deformable = int(bool(f.get("USE_DEFORMABLE", False)))
     # backbone branches the five target configs leave at their defaults: refuse them instead of silently building the default graph
     r = m.RESNETS
     if int(r.get("NUM_GROUPS", 1)) != 1 or int(r.get("WIDTH_PER_GROUP", 64)) != 64:

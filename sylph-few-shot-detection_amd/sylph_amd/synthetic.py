@@ -75,9 +75,11 @@ def backbone_state_dict(seed: int = 0, depth: int = 50) -> Dict[str, torch.Tenso
 
 def head_state_dict(seed: int = 1, num_classes: int = 60, c: int = 256, num_convs: int = 4,
                     levels: int = 5, num_share_convs: int = 0, norm: str = "GN", num_cls_convs: int = None,
-                    num_box_convs: int = None) -> Dict[str, torch.Tensor]:
+                    num_box_convs: int = None, deformable: bool = False) -> Dict[str, torch.Tensor]:
     """MetaFCOSHead weights under the reference's keys.  norm "GN": a tower is nn.Sequential(conv, GroupNorm, ReLU) x n (indices 3i,
-    3i + 1); norm "none": (conv, ReLU) x n (index 2i) -- fcos.py:72-122.  num_share_convs: the shared tower in front of both."""
+    3i + 1); norm "none": (conv, ReLU) x n (index 2i) -- fcos.py:72-122.  num_share_convs: the shared tower in front of both.
+    deformable (MODEL.FCOS.USE_DEFORMABLE): the last conv of the cls and of the bbox tower is adet's DFConv2d, keys
+    {k}.offset.weight [27,256,3,3], {k}.offset.bias, {k}.conv.weight, {k}.conv.bias instead of {k}.weight / {k}.bias."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
     p = "proposal_generator.fcos_head"
@@ -95,6 +97,23 @@ def head_state_dict(seed: int = 1, num_classes: int = 60, c: int = 256, num_conv
         sd[f"{p}.share_tower.{step * i}.bias"] = torch.randn(c, generator=g2) * 0.1
         if norm == "GN":
             _gn(g2, sd, f"{p}.share_tower.{step * i + 1}", c)
+    if deformable:
+        # a separate stream again: every other key stays bit-stable.  Offset rows are scaled so that on a GroupNorm + ReLU input (E x^2 ~ 0.5)
+        # the offsets have a std of ~2 px (fractional, many crossing a level border, some far off the map) and the mask logits ~1.5
+        # (sigmoid not saturated); zero offsets would hide every sampling bug.
+        g3 = torch.Generator().manual_seed(seed * 11 + 5)
+        fan = 9 * c * 0.5
+        for t, n in (("cls_tower", num_convs if num_cls_convs is None else num_cls_convs),
+                     ("bbox_tower", num_convs if num_box_convs is None else num_box_convs)):
+            if n == 0:
+                continue
+            k = step * (n - 1)
+            del sd[f"{p}.{t}.{k}.weight"], sd[f"{p}.{t}.{k}.bias"]
+            row_std = torch.cat([torch.full((18,), 2.0), torch.full((9,), 1.5)]) / math.sqrt(fan)
+            sd[f"{p}.{t}.{k}.offset.weight"] = torch.randn(27, c, 3, 3, generator=g3) * row_std.view(27, 1, 1, 1)
+            sd[f"{p}.{t}.{k}.offset.bias"] = torch.cat([torch.randn(18, generator=g3), 0.5 * torch.randn(9, generator=g3)])
+            sd[f"{p}.{t}.{k}.conv.weight"] = _conv(g3, c, c, 3, std=math.sqrt(2.0 / (9 * c)))
+            sd[f"{p}.{t}.{k}.conv.bias"] = torch.randn(c, generator=g3) * 0.1
     sd[f"{p}.cls_logits.weight"] = _conv(g, num_classes, c, 1, std=0.01)
     sd[f"{p}.cls_logits.bias"] = torch.full((num_classes,), -math.log(99.0))
     sd[f"{p}.bbox_pred.weight"] = _conv(g, 4, c, 3, std=0.02)
