@@ -151,7 +151,10 @@ int sylph_import_head(sylph_ctx* ctx, int N, int level, const float* logits_nchw
  * (sylph/modeling/meta_fcos/fcos_outputs.py:743-812,904-1028; meta_one_stage_detector.py:288-296).
  * out_heights/out_widths (host, may be NULL = image size): the "height"/"width" of each input dict.
  * Device outputs, row-major [B][max_out][...]; counts_dev[B]; status_dev[1] (bit0 candidate
- * overflow, bit1 output truncated).  cand_dev: (level, location, class) ordinal of each detection. */
+ * overflow, bit1 output truncated).  cand_dev: (level, location, class) ordinal of each detection.
+ * Decode reads the outputs of the most recent head call (sylph_fcos_head, sylph_fcos_head_pretrained or sylph_import_head) of the
+ * current batch; any order of stage calls on one context is valid (a head need not be followed by a decode, a decode may be repeated,
+ * and a decode that reported a status bit leaves nothing behind for the next one). */
 int sylph_decode_nms(sylph_ctx* ctx, const int* out_heights, const int* out_widths, int max_out, float* boxes_dev,
                      float* scores_dev, int* classes_dev, int* levels_dev, float* locations_dev, int* cand_dev,
                      int* counts_dev, int* status_dev);

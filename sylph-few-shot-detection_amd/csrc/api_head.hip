@@ -437,6 +437,10 @@ int sylph_fcos_head(sylph_ctx* c, const float* cls_conv, const float* cls_bias, 
     float* bias_scan = P->bias_pad + P->bias_pad_cap;  // written by the pack_codes launch above
     const Plan* PP = P;
     const int nseg = P->B * c->cfg.nlevels;
+    // the counters hold this scan's candidates from here on (set before the launch: a failed one may have counted too): whatever fills
+    // the logits next -- a plain head, the pretrained head, an import -- before a decode has run must not have its decode scan append to
+    // them (sylph_decode_nms clears a dirty table in front of a plain scan)
+    P->cand_dirty = true;
     KCHK(timed_op(c, "logits_scan_kernel", 2.0 * (double)rows * N * 256.0, c->stream, [=](hipStream_t st) {
            return launch_logits_scan(PP->cls_feat, 256, PP->cls_coef, PP->code_w, PP->code_wf, bias_scan, PP->head_segs, PP->head_tiles32,
                                      PP->head_mtiles32, PP->pred, 8, d, PP->dbuf, nseg, st);
@@ -521,8 +525,9 @@ int sylph_decode_nms(sylph_ctx* c, const int* oh, const int* ow, int max_out, fl
   }
   const DecodeCfg d = decode_cfg(c, P, max_out);
   const int L = c->cfg.nlevels;
-  // the candidate counters are left zero by every decode that ran its own scan; after a fused many-way step (whose launcher clears them
-  // itself and whose candidates stay valid for a repeated decode) the plain scan starts from a cleared table again
+  // the candidate counters are left zero by every decode that ran its own scan; after a fused many-way scan (whose launcher clears them
+  // itself and whose candidates stay valid for a repeated decode) -- decoded or not: sylph_fcos_head marks the table dirty -- the plain
+  // scan starts from a cleared table again.  A steady stream of fused or of plain steps never clears here (no extra launch)
   if (!P->scan_fused && P->cand_dirty) HIPCHK(hipMemsetAsync(P->dbuf.cand_count, 0, (size_t)P->B * L * 4, c->stream));
   P->cand_dirty = P->scan_fused;
   int nwb = (L * c->cfg.pre_nms_topk + 63) / 64;

@@ -557,7 +557,7 @@ def test_full_size_properties_bf16(full_sd):
         assert (iou[same] <= 0.75).all()
 
 
-@pytest.mark.parametrize("nb", [120, 144])
+@pytest.mark.parametrize("nb", [120, 144, 192])
 def test_full_size_batch120_far_end_of_the_tensors_bf16(full_sd, nb):
     """The default bench batch (120 images of 800x1333: activations of up to 4.13e9 bytes, just below 4 GiB, 1.9 x the signed 32-bit
     range) and 144 images (4.95e9 bytes: past the 32-bit range -- since round 6 bottleneck64[p] and conv_pw address their res2-sized
@@ -565,7 +565,10 @@ def test_full_size_batch120_far_end_of_the_tensors_bf16(full_sd, nb):
     images).  Four distinct images repeated nb / 4 times: every copy of an image must
     come out BIT FOR BIT the same wherever it sits in the batch (round 6: conv_hpipe pairs patches per image and keys its K-walk
     rotation on the pair's place inside the image, as conv_pw does since round 5: a served image's detections do not depend on its
-    neighbours), and equal its 4-image run (other tile shapes at B = 4) up to bf16 rounding."""
+    neighbours), and equal its 4-image run (other tile shapes at B = 4) up to bf16 rounding.
+    192 images (bench.py's batch: 6.6e9 bytes of res2 activations, images 145-191 on per-image 64-bit bases no smaller batch reaches):
+    also the decoder at the far end of the tensors -- the oracle decoder on the HIP head outputs of images 188-191 must give exactly
+    the HIP decode's candidate ordinals, scores within 1e-5."""
     from sylph_amd import synthetic as W
     base = W.synthetic_images(4, 800, 1333, seed=11)
     codes = W.synthetic_codes(5, seed=4, scale=3.0)
@@ -586,6 +589,16 @@ def test_full_size_batch120_far_end_of_the_tensors_bf16(full_sd, nb):
         assert a["scores"].numel() == b["scores"].numel() > 0
         assert torch.equal(a["cand_index"], b["cand_index"]) and torch.equal(a["scores"], b["scores"]) and torch.equal(a["pred_boxes"], b["pred_boxes"]), \
             f"image {i}: detections differ from its copy {i % 4}"
+    if nb == 192:
+        from oracle import decode as OD
+        far = slice(nb - 4, nb)
+        heads = [[t[far].cpu() for t in ts] for ts in eng.export_head()]
+        for j, w in enumerate(OD.predict_proposals(*heads), start=nb - 4):
+            w = OD.detector_postprocess(w, (800, 1333), 800, 1333)
+            assert w["scores"].numel() > 0
+            np.testing.assert_array_equal(det[j]["cand_index"].cpu().numpy(), _cand_ordinals(w, 800, 1344, 5), err_msg=f"image {j}")
+            np.testing.assert_allclose(det[j]["scores"].cpu().numpy(), w["scores"].numpy(), atol=1e-5, err_msg=f"image {j}")
+        del heads
     small = [p[0:4].clone() for p in pyr]
     del pyr
     eng4 = _engine("bf16", _cfg())
