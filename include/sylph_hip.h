@@ -76,7 +76,7 @@ typedef struct sylph_config {
                               in support_set_shared_tower, whose nn.Sequential indices advance per EXISTING module (code_generator.py:648-688) */
   int tower_deformable;    /* MODEL.FCOS.USE_DEFORMABLE: the LAST conv of the cls and of the bbox tower is a modulated deformable conv (adet
                               DFConv2d, DCNv2): keys {k}.offset.weight / .bias [27,256,3,3] and {k}.conv.weight / .bias instead of {k}.weight
-                              / .bias (fcos.py:83-84).  Not with the paired-tower mode. */
+                              / .bias (fcos.py:83-84). */
 } sylph_config;
 
 /* Fill cfg with the defaults of the COCO Meta-FCOS finetune yaml. */

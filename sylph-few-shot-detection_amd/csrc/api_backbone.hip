@@ -46,6 +46,20 @@ int ensure_pyramid(sylph_ctx* c, Plan* P) {
   return 0;
 }
 
+// Patch list of the bottleneck kernels (bottleneck.hip, conv_rw3.hip): ph x pw patches of B images of H x W positions
+static int upload_bk_tiles(sylph_ctx* c, int B, int H, int W, int ph, int pw, BottleneckArgs* ba) {
+  std::vector<BkTile> bt;
+  for (int b = 0; b < B; ++b)
+    for (int yy = 0; yy < H; yy += ph)
+      for (int xx = 0; xx < W; xx += pw)
+        bt.push_back(BkTile{b * H * W, H, W, (yy << 16) | xx, ph, pw, (65536u + pw - 1) / pw, (65536u + pw + 2 - 1) / (pw + 2)});
+  void* btd = nullptr;
+  RET(upload(c, &btd, bt.data(), bt.size() * sizeof(BkTile)));
+  ba->bk = (const BkTile*)btd;
+  ba->n_tiles = (int)bt.size();
+  return 0;
+}
+
 // One ResNet bottleneck block (detectron2 BottleneckBlock: 1x1 -> 3x3 -> 1x1, FrozenBN folded, residual / projection shortcut)
 // appended to `ops`: X [B][Hin*Win][Cin] -> Y [B][Ho*Wo][cout].  t1 / t2 / sc are scratch activations of the stage.
 // Shared by build_backbone and the single-block parity entry sylph_bottleneck, so both run the same kernels.
@@ -75,21 +89,12 @@ int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block&
     ba.zeros = c->zeros;
     if (!*scr.trash) RET(c->dalloc(scr.trash, (size_t)1024 * 256 * 128));  // per-thread trash slots (grid <= CU count <= 1024)
     ba.trash = *scr.trash;
-    std::vector<SegDesc> sg = image_segs(B, Hin, Win, Hin, Win);
-    std::vector<BkTile> bt;
     int ph, pw;
     // (A 64-position variant with a double-buffered halo was measured in round 3: 1.56 vs 1.31 ms per launch -- 2.2 x as many tiles pay
     // the per-tile fixed costs; it left the tree in round 5, see bottleneck.hip.)
     const int bk_small = 0;
     pick_patch(Hin, Win, 128, 184, 2, &ph, &pw);
-    for (size_t si2 = 0; si2 < sg.size(); ++si2)
-      for (int yy = 0; yy < Hin; yy += ph)
-        for (int xx = 0; xx < Win; xx += pw)
-          bt.push_back(BkTile{sg[si2].in_row0, Hin, Win, (yy << 16) | xx, ph, pw, (65536u + pw - 1) / pw, (65536u + pw + 2 - 1) / (pw + 2)});
-    void* btd = nullptr;
-    RET(upload(c, &btd, bt.data(), bt.size() * sizeof(BkTile)));
-    ba.bk = (const BkTile*)btd;
-    ba.n_tiles = (int)bt.size();
+    RET(upload_bk_tiles(c, B, Hin, Win, ph, pw, &ba));
     const double fl = 2.0 * (double)B * Hin * Win * (fuse_id ? (256.0 * 64 + 64.0 * 576 + 64.0 * 256) : (64.0 * 64 + 64.0 * 576 + 128.0 * 256));
     if (fuse_id) ops.push_back([=](hipStream_t s) { return timed_op(c, "bottleneck64_kernel", fl, s, [=](hipStream_t st) { return launch_bottleneck64(ba, bk_small, st); }); });
     else ops.push_back([=](hipStream_t s) { return timed_op(c, "bottleneck64p_kernel", fl, s, [=](hipStream_t st) { return launch_bottleneck64p(ba, st); }); });
@@ -109,16 +114,7 @@ int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block&
     memset(&ba, 0, sizeof(ba));
     ba.x = t1; ba.y = t2;
     ba.w2 = (const __bf16*)blk.c2.w; ba.s2 = blk.c2.scale; ba.b2 = blk.c2.shift;
-    std::vector<SegDesc> sg = image_segs(B, H1, W1, H1, W1);
-    std::vector<BkTile> bt;
-    for (size_t si2 = 0; si2 < sg.size(); ++si2)
-      for (int yy = 0; yy < H1; yy += ph)
-        for (int xx = 0; xx < W1; xx += pw)
-          bt.push_back(BkTile{sg[si2].in_row0, H1, W1, (yy << 16) | xx, ph, pw, (65536u + pw - 1) / pw, (65536u + pw + 2 - 1) / (pw + 2)});
-    void* btd = nullptr;
-    RET(upload(c, &btd, bt.data(), bt.size() * sizeof(BkTile)));
-    ba.bk = (const BkTile*)btd;
-    ba.n_tiles = (int)bt.size();
+    RET(upload_bk_tiles(c, B, H1, W1, ph, pw, &ba));
     const double fl = 2.0 * (double)B * H1 * W1 * 128.0 * 1152.0;
     ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_rw3_kernel", fl, s, [=](hipStream_t st) { return launch_conv_rw3(ba, st); }); });
   } else {

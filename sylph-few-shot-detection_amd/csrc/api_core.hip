@@ -147,7 +147,6 @@ int sylph_ctx_create(int device_id, int dtype, sylph_ctx** out) {
   c->device = device_id;
   c->dt = dtype == SYLPH_BF16 ? DT_BF16 : (dtype == SYLPH_F32S ? DT_F32S : DT_F32);
   sylph_config_default(&c->cfg);
-  conv_set_nbuf(SYLPH_AB_ENV("SYLPH_CONV_NBUF", 1));  // A/B knob (-DSYLPH_ABLATE builds): LDS stages of the conv kernel
   if (const char* mp = getenv("SYLPH_MAX_PLANS")) c->max_plans = atoi(mp) > 1 ? (size_t)atoi(mp) : 2;
   {
     size_t free_b = 0, total_b = 0;

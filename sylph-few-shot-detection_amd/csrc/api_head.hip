@@ -47,7 +47,7 @@ int build_head(sylph_ctx* c, Plan* P) {
   const size_t e = c->esz();
   const size_t rows = (size_t)P->B * P->Ltot;
   const int L = c->cfg.nlevels, nseg = P->B * L;
-  RET(c->dalloc(&P->tA, rows * 512 * e));  // paired towers: [rows][512]; unpaired: tA/tB = halves
+  RET(c->dalloc(&P->tA, rows * 512 * e));  // tA/tB, tC/tD: the ping-pong buffers of the cls / bbox towers
   RET(c->dalloc(&P->tC, rows * 512 * e));
   P->tB = (char*)P->tA + rows * 256 * e;
   P->tD = (char*)P->tC + rows * 256 * e;
@@ -90,7 +90,7 @@ int build_head(sylph_ctx* c, Plan* P) {
     // n - 2 keeps its own GroupNorm apply pass so that this input is materialised once.
     static const int gn_fuse_on = getenv("SYLPH_GN_FUSE") ? atoi(getenv("SYLPH_GN_FUSE")) : 1;
     ConvOpts probe; probe.pad = 1;
-    const bool fuse = gn_fuse_on && convs.size() > 1 && convs[0].Cin <= 512 && use_hpipe(c, convs[1], segs, probe);
+    const bool fuse = gn_fuse_on && convs.size() > 1 && convs[0].Cin <= 512 && pick_conv_route(c, convs[1], 256, segs, probe).kind == ConvKind::hpipe;
     const float2* coef_prev = nullptr;
     for (size_t i = 0; i < convs.size(); ++i) {
       ConvOpts o; o.pad = 1; o.segs_per_image = c->cfg.nlevels;
@@ -115,79 +115,49 @@ int build_head(sylph_ctx* c, Plan* P) {
     return 0;
   };
   void *cls_feat = nullptr, *box_feat = nullptr;
-  int feat_ld = 256;
   const float2* box_coef = nullptr;
   OpFn box_apply;
-  bool box_defer = false, two_streams = false;
-  size_t side_from = 0;  // two streams: ops[side_from ..] (bbox tower + prediction pass) go to the side stream
-  if (c->paired) {
-    // tA|tB and tC|tD are used as two [rows][512] ping-pong buffers.  The towers run image-chunk by
-    // image-chunk (depth first): a chunk's [rows][512] layer output (~23 MB per 800x1344 image) is
-    // normalised and consumed by the next layer while it is still resident in the 256 MiB Infinity Cache.
-    int chunk_imgs = P->B;
-    if (const char* cz = getenv("SYLPH_HEAD_CHUNK")) chunk_imgs = atoi(cz) > 0 ? atoi(cz) : P->B;
-    const void* in = nullptr;
-    for (int b0 = 0; b0 < P->B; b0 += chunk_imgs) {
-      const int b1 = b0 + chunk_imgs < P->B ? b0 + chunk_imgs : P->B;
-      const std::vector<SegDesc> csegs(segs.begin() + (size_t)b0 * L, segs.begin() + (size_t)b1 * L);
-      in = P->F;
-      int in_ld = 256;
-      void* out = P->tA;
-      for (size_t i = 0; i < c->pair_tower.size(); ++i) {
-        ConvOpts o; o.pad = 1; o.segs_per_image = c->cfg.nlevels;
-        if (i > 0) { o.group_cout = 256; o.group_in_off = 256; }
-        RET(add_conv_gn(c, ops, c->pair_tower[i], in, in_ld, out, csegs, o, c->pair_gn[i], 1));
-        in = out; in_ld = 512;
-        out = (out == P->tA) ? P->tC : P->tA;
-      }
-    }
-    cls_feat = const_cast<void*>(in);
-    box_feat = (char*)cls_feat + 256 * e;
-    feat_ld = 512;
-  } else {
-    // the cls tower's last GroupNorm is left to sylph_fcos_head (fused into the class-conditional conv when N <= 32)
-    static const int gn_logits_on = getenv("SYLPH_FUSE_GN_LOGITS") ? atoi(getenv("SYLPH_FUSE_GN_LOGITS")) : 1;
-    P->cls_coef = nullptr; P->cls_apply = nullptr;
-    const bool defer = gn_logits_on && c->dt == DT_BF16 && tower_gn;
-    OpFn cls_apply;
-    if (!c->share_tower.empty()) {
-      // MODEL.FCOS.NUM_SHARE_CONVS (fcos.py:397,626): a shared tower in front of both; its last norm is applied in place (two readers)
-      void *s0 = nullptr, *s1 = nullptr, *share_out = nullptr;
-      RET(c->dalloc(&s0, rows * 256 * e));
-      RET(c->dalloc(&s1, rows * 256 * e));
-      RET(tower(2, c->share_tower, c->share_gn, s0, s1, &share_out, nullptr, nullptr, nullptr));
-      tower_in = share_out;
-    }
-    // Small batches (SylphPredictor and the reference's query loop run batch 1, meta_learn_evaluation.py:421-426, predictor.py:248-274):
-    // a tower layer is a launch of a few hundred blocks whose K loop is latency-bound, and the two towers are independent chains of
-    // four such launches -> the bbox tower (+ its prediction pass) runs on a second stream between a fork and a join event, the cls
-    // tower stays on the caller's stream.  Large batches fill the chip for many rounds per launch: one stream (measured equal).
-    static const int two_on = getenv("SYLPH_HEAD_STREAMS") ? atoi(getenv("SYLPH_HEAD_STREAMS")) : 1;
-    // Round 6: up to 32 full-size images (was 8): the two towers' launches of one layer share the last partial round of blocks -- batch 12
-    // 1 737 -> 1 806 img/s, batch 16 / 24 / 32 +1 %, 48 ... 192 equal (profiles/r6_small_batch.md)
-    two_streams = two_on == 2 || (two_on == 1 && rows <= (size_t)32 * 22400);
-    if (two_streams && !c->side_stream) {
-      HIPCHK(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    }
-    if (two_streams)
-      ops.push_back([c](hipStream_t s) {
-        if (hipEventRecord(c->ev_fork, s) != hipSuccess || hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) != hipSuccess) return -101;
-        return 0;
-      });
-    RET(tower(0, c->cls_tower, c->cls_gn, P->tA, P->tB, &cls_feat, (defer && !c->cls_tower.empty()) ? &P->cls_coef : nullptr, &cls_apply,
-              c->cls_off.Cout ? &c->cls_off : nullptr));
-    P->cls_apply = cls_apply;
-    box_defer = defer && c->pred_taps && !c->box_tower.empty();
-    side_from = ops.size();
-    // from here to the join the ops run on the side stream: a split-K conv among them (towers without GroupNorm, the prediction conv)
-    // must take the side stream's partial-plane scratch, not the one the cls tower is using at the same time
-    c->build_slot = two_streams ? 1 : 0;
-    RET(tower(1, c->box_tower, c->box_gn, P->tC, P->tD, &box_feat, box_defer ? &box_coef : nullptr, &box_apply,
-              c->box_off.Cout ? &c->box_off : nullptr));
+  // the cls tower's last GroupNorm is left to sylph_fcos_head (fused into the class-conditional conv when N <= 32)
+  static const int gn_logits_on = getenv("SYLPH_FUSE_GN_LOGITS") ? atoi(getenv("SYLPH_FUSE_GN_LOGITS")) : 1;
+  P->cls_coef = nullptr; P->cls_apply = nullptr;
+  const bool defer = gn_logits_on && c->dt == DT_BF16 && tower_gn;
+  OpFn cls_apply;
+  if (!c->share_tower.empty()) {
+    // MODEL.FCOS.NUM_SHARE_CONVS (fcos.py:397,626): a shared tower in front of both; its last norm is applied in place (two readers)
+    void *s0 = nullptr, *s1 = nullptr, *share_out = nullptr;
+    RET(c->dalloc(&s0, rows * 256 * e));
+    RET(c->dalloc(&s1, rows * 256 * e));
+    RET(tower(2, c->share_tower, c->share_gn, s0, s1, &share_out, nullptr, nullptr, nullptr));
+    tower_in = share_out;
   }
-  P->cls_ld = feat_ld;
+  // Small batches (SylphPredictor and the reference's query loop run batch 1, meta_learn_evaluation.py:421-426, predictor.py:248-274):
+  // a tower layer is a launch of a few hundred blocks whose K loop is latency-bound, and the two towers are independent chains of
+  // four such launches -> the bbox tower (+ its prediction pass) runs on a second stream between a fork and a join event, the cls
+  // tower stays on the caller's stream.  Large batches fill the chip for many rounds per launch: one stream (measured equal).
+  static const int two_on = getenv("SYLPH_HEAD_STREAMS") ? atoi(getenv("SYLPH_HEAD_STREAMS")) : 1;
+  // Round 6: up to 32 full-size images (was 8): the two towers' launches of one layer share the last partial round of blocks -- batch 12
+  // 1 737 -> 1 806 img/s, batch 16 / 24 / 32 +1 %, 48 ... 192 equal (profiles/r6_small_batch.md)
+  const bool two_streams = two_on == 2 || (two_on == 1 && rows <= (size_t)32 * 22400);
+  if (two_streams && !c->side_stream) {
+    HIPCHK(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+  }
+  if (two_streams)
+    ops.push_back([c](hipStream_t s) {
+      if (hipEventRecord(c->ev_fork, s) != hipSuccess || hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) != hipSuccess) return -101;
+      return 0;
+    });
+  RET(tower(0, c->cls_tower, c->cls_gn, P->tA, P->tB, &cls_feat, (defer && !c->cls_tower.empty()) ? &P->cls_coef : nullptr, &cls_apply,
+            c->cls_off.Cout ? &c->cls_off : nullptr));
+  P->cls_apply = cls_apply;
+  const bool box_defer = defer && c->pred_taps && !c->box_tower.empty();
+  const size_t side_from = ops.size();  // two streams: ops[side_from ..] (bbox tower + prediction pass) go to the side stream
+  // from here to the join the ops run on the side stream: a split-K conv among them (towers without GroupNorm, the prediction conv)
+  // must take the side stream's partial-plane scratch, not the one the cls tower is using at the same time
+  c->build_slot = two_streams ? 1 : 0;
+  RET(tower(1, c->box_tower, c->box_gn, P->tC, P->tD, &box_feat, box_defer ? &box_coef : nullptr, &box_apply,
+            c->box_off.Cout ? &c->box_off : nullptr));
   Geom g32;  // 128-row pointwise tiles of the pyramid (class-conditional conv with N <= 32, fused GN + prediction pass)
   RET(make_geom(c, segs, 128, &g32));
   if (box_defer && box_coef) {
@@ -207,7 +177,7 @@ int build_head(sylph_ctx* c, Plan* P) {
     });
   } else {
     ConvOpts op; op.pad = 1; op.segs_per_image = c->cfg.nlevels; op.relu_nch = 4; op.mul_nch = 4; op.out_f32 = true;
-    RET(add_conv(c, ops, c->pred, box_feat, feat_ld, P->pred, 8, segs, op));
+    RET(add_conv(c, ops, c->pred, box_feat, 256, P->pred, 8, segs, op));
   }
   c->build_slot = 0;
   if (two_streams) {
@@ -338,7 +308,7 @@ int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow) {
   // row pitch of the logits: the padded class count, except for <= 8 classes on the fused GroupNorm + class-conditional conv path
   // (gn_logits_kernel stores any multiple of 4 columns): 8 floats per location instead of 32 -- the conv writes and the scan reads
   // a quarter of the bytes (a 5-way episode: 46 MB instead of 183 MB per 64 images)
-  const bool narrow = allow_narrow && N <= 8 && c->dt == DT_BF16 && P->head_built && P->cls_coef && P->cls_ld == 256;
+  const bool narrow = allow_narrow && N <= 8 && c->dt == DT_BF16 && P->head_built && P->cls_coef;
   P->logits_ld = narrow ? 8 : Npad;
   P->ncls = N;
   return 0;
@@ -352,7 +322,7 @@ int run_cond_logits(sylph_ctx* c, Plan* P) {
   const size_t rows = (size_t)P->B * P->Ltot;
   const float* bias = P->has_bias ? P->bias_pad : nullptr;
   if (P->cls_coef) {
-    if (bn == 32 && P->cls_ld == 256) {  // GroupNorm + ReLU + class-conditional conv in one HBM pass (head_fused.hip)
+    if (bn == 32) {  // GroupNorm + ReLU + class-conditional conv in one HBM pass (head_fused.hip)
       const Plan* PP = P;
       KCHK(timed_op(c, "gn_logits_kernel", 2.0 * (double)rows * N * 256.0, c->stream, [=](hipStream_t st) {
              return launch_gn_logits(PP->cls_feat, 256, PP->cls_coef, PP->code_w, bias, N, PP->logits, Npad, PP->head_segs, PP->head_tiles32,
@@ -373,8 +343,10 @@ int run_cond_logits(sylph_ctx* c, Plan* P) {
   else { a.tiles = P->head_tiles; a.n_mtiles = P->head_mtiles; }
   a.n_ntiles = Npad / bn;
   a.Cin = 256; a.Cout = N; a.KH = 1; a.KW = 1; a.stride = 1; a.pad = 0;
-  a.in_ld = P->cls_ld; a.out_ld = Npad;
-  KCHK(timed_conv(c, c->dt, true, a, BM, bn, 2.0 * (double)rows * N * 256.0, c->stream), "cond_cls_logits");
+  a.in_ld = 256; a.out_ld = Npad;
+  const DType dt = c->dt;
+  KCHK(timed_op(c, "conv_igemm_kernel", 2.0 * (double)rows * N * 256.0, c->stream, [=](hipStream_t st) { return launch_conv(dt, true, a, BM, bn, st); }),
+       "cond_cls_logits");
   return 0;
 }
 
@@ -430,7 +402,7 @@ int sylph_fcos_head(sylph_ctx* c, const float* cls_conv, const float* cls_bias, 
   P->scan_fused = false; P->logits_stale = false;
   // Many-way episodes (bf16): conv + scan in one pass, the logits never reach HBM (detect.hip: logits_scan_kernel)
   static const int fuse_scan_on = getenv("SYLPH_FUSE_SCAN") ? atoi(getenv("SYLPH_FUSE_SCAN")) : 1;
-  if (fuse_scan_on && c->dt == DT_BF16 && P->cls_coef && (bn != 32 || fuse_scan_on == 2) && P->cls_ld == 256 && N < 65536) {
+  if (fuse_scan_on && c->dt == DT_BF16 && P->cls_coef && (bn != 32 || fuse_scan_on == 2) && N < 65536) {
     BUILD(build_decode(c, P), P);
     RET(ensure_cand_cap(c, P));
     const DecodeCfg d = decode_cfg(c, P, 0);
@@ -463,7 +435,7 @@ int sylph_fcos_head_pretrained(sylph_ctx* c, int* num_classes) {
   if (P->cls_logits_dst != P->logits) {  // (re)build the conv launch for this plan's buffers
     P->cls_logits_ops.clear();
     ConvOpts o; o.pad = c->cls_logits.KH / 2; o.segs_per_image = c->cfg.nlevels; o.out_f32 = true;
-    RET(add_conv(c, P->cls_logits_ops, c->cls_logits, P->cls_feat, P->cls_ld, P->logits, P->logits_ld, pyramid_segs(c, P), o));
+    RET(add_conv(c, P->cls_logits_ops, c->cls_logits, P->cls_feat, 256, P->logits, P->logits_ld, pyramid_segs(c, P), o));
     P->cls_logits_dst = P->logits;
   }
   P->scan_fused = false; P->logits_stale = false;

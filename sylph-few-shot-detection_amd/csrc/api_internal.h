@@ -104,9 +104,6 @@ struct sylph_ctx {
   std::vector<GNLayer> share_gn;
   std::vector<GNLayer> cls_gn, box_gn;
   ConvLayer cls_off, box_off;  // MODEL.FCOS.USE_DEFORMABLE: offset conv of the last cls / bbox tower layer (27 channels; Cout == 0: plain tower)
-  std::vector<ConvLayer> pair_tower;  // cls|bbox towers stacked on Cout (layer 0 shares the input, then grouped)
-  std::vector<GNLayer> pair_gn;
-  bool paired = false;
   ConvLayer pred;  // bbox_pred(4) + ctrness(1) + iou_overlap(1)
   ConvLayer cls_logits;  // the base detector's own classifier (fcos.py:418-427), 1x1 or 3x3, when the checkpoint carries it
   bool has_cls_logits = false;
@@ -207,8 +204,7 @@ struct Plan {
   // head
   void *tA = nullptr, *tB = nullptr, *tC = nullptr, *tD = nullptr;
   void* cls_feat = nullptr;  // output of the cls tower (input of the class-conditional conv)
-  int cls_ld = 256;
-  // bf16, un-paired towers: the last cls-tower GroupNorm is NOT applied by the head ops; sylph_fcos_head either fuses it into the
+  // bf16: the last cls-tower GroupNorm is NOT applied by the head ops; sylph_fcos_head either fuses it into the
   // class-conditional conv (N <= 32: head_fused.hip) or runs cls_apply first
   const float2* cls_coef = nullptr;
   std::function<int(hipStream_t)> cls_apply;
@@ -277,7 +273,6 @@ struct ConvOpts {
   int res_ld = 0, res_mode = 0;
   bool out_f32 = false;
   int cout_override = -1;  // logical Cout (class-conditional conv)
-  int group_cout = 0, group_in_off = 0;  // grouped conv (paired FCOS towers)
   int stem = 0;            // ResNet stem loader
   int want_gn = 0;         // leave per-tile GroupNorm partials in the epilogue
   const void* in2 = nullptr;  // dual-source pointwise conv: second input, its row stride / channels / stride
@@ -287,6 +282,20 @@ struct ConvOpts {
   int gn_relu = 0;
   int segs_per_image = 1;  // consecutive segments that belong to one image (pyramid-wide launches: the FPN levels)
   int stream_slot = 0;     // 1: the op will run on the context's side stream (its split-K scratch must not be the main stream's)
+};
+
+// The kernel add_conv launches for one conv (pick_conv_route), with its tiles, LDS stages and K split:
+//   hpipe         conv_hpipe.hip: 256 x 256 tiles over PAIRS of 3x3 halo patches, weights re-packed into stage images
+//   igemm_halo    conv_igemm.hip on 128-position halo patches (3x3 s1 p1)
+//   pw, spw       conv_pw.hip / conv_spw.hip: persistent pointwise kernels (conv_pw weight table, one PwDesc per M tile)
+//   igemm_splitk  conv_igemm.hip split along K into fp32 partial planes + splitk_finish_kernel
+//   igemm         conv_igemm.hip on BM-row tiles
+enum class ConvKind { hpipe, igemm_halo, pw, spw, igemm_splitk, igemm };
+struct ConvRoute {
+  ConvKind kind = ConvKind::igemm;
+  int BM = 0, BN = 0;
+  int nbuf = 0;    // conv_igemm LDS stages of the 64-row tiles of small launches (ConvArgs::nbuf2): 0 = one, 2, 3
+  int ksplit = 1;  // igemm_splitk: K ranges
 };
 
 struct BkScratch { void *t1, *t2, *sc; void** trash; };
@@ -319,9 +328,8 @@ void pick_patch(int H, int W, int max_pos, int halo_rows, int xpad, int* ph_out,
 void set_patch(SegDesc* s, int ph, int pw, int xpad);
 int make_geom_patch(sylph_ctx* c, std::vector<SegDesc> segs, int max_pos, int halo_rows, int xpad, bool pair, Geom* g, int group = 1);
 long patch_count(const std::vector<SegDesc>& segs, int max_pos, int halo_rows, int xpad);
-int timed_conv(sylph_ctx* c, DType dt, bool of32, const ConvArgs& a, int BM, int BN, double flops, hipStream_t s);
 int timed_op(sylph_ctx* c, const char* kern, double flops, hipStream_t s, const std::function<int(hipStream_t)>& fn);
-bool use_hpipe(sylph_ctx* c, const ConvLayer& L, const std::vector<SegDesc>& segs, const ConvOpts& o);
+ConvRoute pick_conv_route(const sylph_ctx* c, const ConvLayer& L, int in_ld, const std::vector<SegDesc>& segs, const ConvOpts& o);  // pure: no allocation, no upload
 int add_conv(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, int in_ld, void* out, int out_ld, const std::vector<SegDesc>& segs, const ConvOpts& o, Geom* geom_out = nullptr);
 int add_conv_gn(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, int in_ld, void* out, const std::vector<SegDesc>& segs, ConvOpts o, const GNLayer& G, int relu, const float2** coef_out = nullptr, OpFn* apply_out = nullptr);
 int add_gn_from_partials(sylph_ctx* c, std::vector<OpFn>& ops, void* out, int ld, const std::vector<SegDesc>& segs, const Geom& g, const GNLayer& G, int relu,

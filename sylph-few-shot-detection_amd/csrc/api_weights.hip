@@ -297,31 +297,6 @@ int sylph_finalize_weights(sylph_ctx* c) {
         if (gn) RET(make_gn(c, hp + t.name + std::to_string(step * i + 1), &(*t.gns)[i]));
       }
     }
-    const int pair_on = SYLPH_AB_ENV("SYLPH_PAIR_TOWERS", 0);  // A/B knob (-DSYLPH_ABLATE builds only)
-    if (pair_on == 1 && c->cfg.tower_deformable)
-      return fail("the paired-tower mode (SYLPH_PAIR_TOWERS=1) cannot run deformable towers (MODEL.FCOS.USE_DEFORMABLE)");
-    // Pairing (both towers as ONE grouped launch per layer) paid +2 % with the pre-halo kernel (the A tile was shared by
-    // four N tiles); with halo tiles the separate towers are 1 % faster (1 666-1 672 vs 1 645-1 660 img/s), so it is opt-in.
-    if (c->cfg.num_cls_convs == c->cfg.num_box_convs && c->cfg.num_cls_convs > 0 && pair_on == 1) {
-      // run both towers as ONE launch per layer: outputs side by side ([rows][512] = cls | bbox)
-      const int n = c->cfg.num_cls_convs;
-      c->pair_tower.resize(n); c->pair_gn.resize(n);
-      for (int i = 0; i < n; ++i) {
-        RET(make_conv_bias(c, {hp + ".cls_tower." + std::to_string(3 * i), hp + ".bbox_tower." + std::to_string(3 * i)},
-                           &c->pair_tower[i]));
-        std::vector<float> ga, be;
-        for (const char* t : {".cls_tower.", ".bbox_tower."}) {
-          const HostTensor *g = find_w(c, hp + t + std::to_string(3 * i + 1) + ".weight"),
-                           *b = find_w(c, hp + t + std::to_string(3 * i + 1) + ".bias");
-          if (!g || !b || g->data.size() != 256) return fail("missing GroupNorm weights of the FCOS towers");
-          ga.insert(ga.end(), g->data.begin(), g->data.end());
-          be.insert(be.end(), b->data.begin(), b->data.end());
-        }
-        RET(upload_vec(c, &c->pair_gn[i].gamma, ga, 512));
-        RET(upload_vec(c, &c->pair_gn[i].beta, be, 512));
-      }
-      c->paired = true;
-    }
     RET(make_conv_bias(c, {hp + ".bbox_pred", hp + ".ctrness", hp + ".iou_overlap"}, &c->pred));
     if (find_w(c, hp + ".cls_logits.weight") && find_w(c, hp + ".cls_logits.bias")) {
       const HostTensor* w = find_w(c, hp + ".cls_logits.weight");

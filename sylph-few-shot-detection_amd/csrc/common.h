@@ -56,13 +56,11 @@ struct ConvArgs {
   int Cin, Cout, KH, KW, stride, pad;
   int in_ld, out_ld, res_ld;  // row strides in elements
   int Cin2, in2_ld, stride2;  // second input: channels, row stride, spatial stride
-  int group_cout, group_in_off;  // grouped conv: output channels per group, input-channel offset per group (0 = off)
   int relu_nch;               // ReLU on output channels < relu_nch
   int mul_nch;                // seg.mul on output channels < mul_nch
   int res_mode;               // 0 none, 1 same geometry, 2 nearest-neighbour 2x upsample of res
   float* gn_partial;          // optional [n_mtiles][Cout/8][3] per-tile GroupNorm partials (n, mean, M2)
-  int halo;                   // 3x3 s1 p1 halo-tile mode: tiles[].y = (patch row << 16) | patch col (seg.ph x seg.pw patches)
-  int res_lds;                // set by launch_conv: residual tile staged through LDS
+  int halo;                   // conv_igemm.hip 3x3 s1 p1 halo-tile mode: tiles[].y = (patch row << 16) | patch col (seg.ph x seg.pw patches)
   int ss_padded_host;         // as given by the caller (ss_padded is cleared for wide tiles)
   int ss_padded;              // scale/shift arrays are padded to a multiple of the N tile (vector prefetch allowed)
   int stem;                   // ResNet-stem A loader (see conv_igemm.hip)
@@ -177,8 +175,7 @@ int launch_conv(DType dt, bool out_f32, const ConvArgs& a, int BM, int BN, hipSt
 void conv_pick_tile(int rows_total, int cout, int ntaps, int* BM, int* BN);
 int launch_splitk_finish(const float* partial, int ksplit, size_t plane, int ld, int Cout, const SplitSeg* segs_dev, int nseg, int max_rows,
                          const float* scale, const float* shift, const void* res, int res_ld, int relu_nch, void* out, int out_ld, hipStream_t s);
-// conv_hpipe.hip: 256x256 deep-pipelined halo-operand 3x3 kernel (BM == BN == 256 selects it in launch_conv; the tile
-// table then holds PAIRS of patches and n_mtiles counts the pairs)
+// conv_hpipe.hip: 256x256 deep-pipelined halo-operand 3x3 kernel (the tile table holds PAIRS of patches and n_mtiles counts the pairs)
 bool conv_hpipe_ok(DType dt, bool out_f32, const ConvArgs& a);
 int launch_conv_hpipe(const ConvArgs& a, hipStream_t s);
 int launch_hpipe_pack_weights(const void* w_igemm, void* w_hpipe, int Cout, int Cin, hipStream_t s);  // a.wt of an hpipe launch
@@ -186,7 +183,6 @@ int launch_bottleneck64(const BottleneckArgs& a, int small, hipStream_t s);   //
 int launch_bottleneck64p(const BottleneckArgs& a, hipStream_t s);  // first block of res2: x [pos][64], w3 = [256][128] packed [W3 | Wsc], y = relu(acc + b3)
 int launch_conv_rw3(const BottleneckArgs& a, hipStream_t s);  // conv_rw3.hip: 3x3 s1 128 -> 128 + FrozenBN + ReLU, weights in registers (x, y, w2, s2, b2, bk, n_tiles)
 bool conv_rw3_patch_ok(int ph, int pw);
-void conv_set_nbuf(int n);  // 1: single LDS stage (max occupancy), 2: double-buffered
 // conv_pw.hip: persistent pipelined pointwise (1x1) conv, bf16; a.wt = the layer's stage-image weights (launch_pw_pack_weights),
 // a.tiles = BM-row tiles, a.pw_desc / a.pw_table as below; (BM, BN) from conv_pw_tile (false: not eligible)
 bool conv_pw_tile(int cout, int k_total, bool has_res, int* BM, int* BN);

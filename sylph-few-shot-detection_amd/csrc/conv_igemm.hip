@@ -165,7 +165,6 @@ __global__ __launch_bounds__(WGM * WGN * 64, (SPLIT ? (BM * BN == 128 * 128 ? 3 
   uint32_t hmask = 0;
   int hb[TM];
   if constexpr (HALO) {
-    const int goff_h = a.group_cout > 0 ? ((nt * BN) / a.group_cout) * a.group_in_off : 0;
 #pragma unroll
     for (int t = 0; t < HRND; ++t) {
       const int hrow = t * RS + r0;
@@ -176,7 +175,7 @@ __global__ __launch_bounds__(WGM * WGN * 64, (SPLIT ? (BM * BN == 128 * 128 ? 3 
       // so the 16 lanes of a ds_read_b128 group (16 consecutive m) see 16 distinct k mod 16, and k has the parity of the
       // halo row index (row - k = 2 * hy): (row & 1, (k >> 1) & 7) is a distinct 16-byte bank slot for every lane
       const int clh = c16 ^ (((hy * HPW + hx) >> 1) & 7);
-      hsrc[t] = (sd.in_row0 + iy * sd.in_W + ix) * a.in_ld + clh * EPC + goff_h;
+      hsrc[t] = (sd.in_row0 + iy * sd.in_W + ix) * a.in_ld + clh * EPC;
       hmask |= (ok ? 1u : 0u) << t;
     }
 #pragma unroll
@@ -185,11 +184,6 @@ __global__ __launch_bounds__(WGM * WGN * 64, (SPLIT ? (BM * BN == 128 * 128 ? 3 
       const int my = (int)(((unsigned)m * inv_pw) >> 16);
       hb[i] = my * HW2 + (m - my * HPW);
     }
-  }
-  if (a.group_cout > 0) {  // grouped conv: this N tile's group reads its own input-channel window
-    const int goff = ((nt * BN) / a.group_cout) * a.group_in_off;
-#pragma unroll
-    for (int i = 0; i < AR; ++i) abase[i] += goff;
   }
   size_t bbase[BR];
 #pragma unroll
@@ -240,42 +234,17 @@ __global__ __launch_bounds__(WGM * WGN * 64, (SPLIT ? (BM * BN == 128 * 128 ? 3 
     if (++cc == cpt && !second) { cc = 0; ++tap; if (++kw == KW) { kw = 0; ++kh; } }
   };
 
-  // Every HBM access of the block is issued up front so that the only exposed memory round trip is
-  // the first operand slice:
-  //  * residual tile via global_load_lds (narrow HBM-bound tiles): piece-major LDS image, piece q =
-  //    bytes [128q, 128q+128) of every row at 128-byte pitch, read back by the epilogue;
-  //  * per-channel scale/shift: one float4 per lane of the first BN/2 lanes, parked in LDS later.
+  // Per-channel scale/shift are fetched up front (one float4 per lane of the first BN/2 lanes) and parked in LDS later, so
+  // that their round trip hides under the first operand slice.
   constexpr int SCP = BN + 4;                 // fp32 pitch of the epilogue tile (+16 B: conflict-free b128 writes)
   constexpr int SC_BYTES = WTM * SCP * 4;
-  constexpr int RES_OFF = (NBUF * STAGE > SC_BYTES) ? NBUF * STAGE : SC_BYTES;
-  constexpr int RES_PIECES = BN * (int)sizeof(T) / 128;
   constexpr bool SS_IN_STAGE = NBUF * STAGE >= SC_BYTES + BN * 8;  // scale/shift fit behind the epilogue tile
-  const int ss_off = SS_IN_STAGE ? SC_BYTES : RES_OFF + (a.res_lds ? BM * BN * (int)sizeof(T) : 0);
+  constexpr int ss_off = SS_IN_STAGE ? SC_BYTES : ((NBUF * STAGE > SC_BYTES) ? NBUF * STAGE : SC_BYTES);  // else behind everything
   float4 ssv = make_float4(0.f, 0.f, 0.f, 0.f);
   if (BN <= 64 && a.ss_padded) {
     if (tid < BN / 4) ssv = a.scale ? reinterpret_cast<const float4*>(a.scale)[nt * (BN / 4) + tid] : make_float4(1.f, 1.f, 1.f, 1.f);
     else if (tid < BN / 2 && a.shift) ssv = reinterpret_cast<const float4*>(a.shift)[nt * (BN / 4) + tid - BN / 4];
   }
-  if (a.res_lds) {
-    const T* __restrict__ resg = reinterpret_cast<const T*>(a.res);
-#pragma unroll
-    for (int i = 0; i < AR; ++i) {
-      const int pos = tile.y + r0 + RS * i;
-      int rp = pos;
-      if (a.res_mode == 2) {
-        const int oy = pos / sd.out_W, ox = pos - oy * sd.out_W;
-        rp = (oy >> 1) * sd.res_W + (ox >> 1);
-      }
-      const T* rowp = resg + (size_t)(sd.res_row0 + rp) * a.res_ld + nt * BN + c16 * EPC;
-#pragma unroll
-      for (int q = 0; q < RES_PIECES; ++q) {
-        const T* src = pos < seg_rows ? rowp + q * (128 / (int)sizeof(T)) : zero + c16 * EPC;
-        __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)(smem + RES_OFF + q * BM * 128 + (wave * 8 + i * RS) * 128),
-                                         16, 0, 0);
-      }
-    }
-  }
-
   f32x16 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -543,13 +512,7 @@ __global__ __launch_bounds__(WGM * WGN * 64, (SPLIT ? (BM * BN == 128 * 128 ? 3 
           rp = (oy >> 1) * sd.res_W + (ox >> 1);
         }
         const T* rptr = res + (size_t)(sd.res_row0 + rp) * a.res_ld + n0;
-        if (a.res_lds) {
-          float rv[8];
-          const int row = p * WTM + rl, byte = c8 * 8 * (int)sizeof(T);
-          load8<T>(reinterpret_cast<const T*>(smem + RES_OFF + (byte >> 7) * BM * 128 + row * 128 + (byte & 127)), rv);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += rv[e];
-        } else if (vec) {
+        if (vec) {
           float rv[8];
           load8<T>(rptr, rv);
 #pragma unroll
@@ -597,7 +560,6 @@ static int launch_cfg(const ConvArgs& a, hipStream_t s) {
   const int grid = 8 * chunk * a.n_ntiles;
   const size_t stage = HALO ? (size_t)(BN + 184) * 128 : (size_t)NBUF * (BM + BN) * 128, epi = (size_t)(BM / WGM) * (BN + 4) * 4;
   size_t lds = stage > epi ? stage : epi;
-  if (a.res_lds) lds += (size_t)BM * BN * sizeof(T);
   if (!(stage >= epi + (size_t)BN * 8)) lds += (size_t)BN * 8;  // scale/shift parked behind everything else
   if (lds > 65536) (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<T, OutT, BM, BN, WGM, WGN, NBUF, FAST, HALO, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   auto kern = conv_igemm_kernel<T, OutT, BM, BN, WGM, WGN, NBUF, FAST, HALO, SPLIT>;
@@ -648,41 +610,31 @@ int launch_splitk_finish(const float* partial, int ksplit, size_t plane, int ld,
   return (int)hipGetLastError();
 }
 
-#ifdef SYLPH_ABLATE
-static int g_nbuf = 1;  // A/B knob: a second LDS stage (rejected)
-void conv_set_nbuf(int n) { g_nbuf = n == 2 ? 2 : 1; }
-#else
-static constexpr int g_nbuf = 1;
-void conv_set_nbuf(int) {}
-#endif
-
+// 64-row tiles also come with two and three LDS stages (a.nbuf2); the 128-row tiles run one
 template <typename T, typename OutT, int NBUF, bool FAST>
 static int launch_n(const ConvArgs& a, int BM, int BN, hipStream_t s) {
-#ifdef SYLPH_ABLATE  // reachable only through SYLPH_CONV_FORCE_BM / _BN
-  if (BM == 256 && BN == 128) return launch_cfg<T, OutT, 256, 128, 2, 2, NBUF, FAST>(a, s);
-  if (BM == 128 && BN == 256) return launch_cfg<T, OutT, 128, 256, 2, 2, NBUF, FAST>(a, s);
-#endif
-  if (BM == 128 && BN == 128) return launch_cfg<T, OutT, 128, 128, 2, 2, NBUF, FAST>(a, s);
-  if (BM == 128 && BN == 64) return launch_cfg<T, OutT, 128, 64, 2, 2, NBUF, FAST>(a, s);
-  if (BM == 128 && BN == 32) return launch_cfg<T, OutT, 128, 32, 4, 1, NBUF, FAST>(a, s);
+  if constexpr (NBUF == 1) {
+    if (BM == 128 && BN == 128) return launch_cfg<T, OutT, 128, 128, 2, 2, NBUF, FAST>(a, s);
+    if (BM == 128 && BN == 64) return launch_cfg<T, OutT, 128, 64, 2, 2, NBUF, FAST>(a, s);
+    if (BM == 128 && BN == 32) return launch_cfg<T, OutT, 128, 32, 4, 1, NBUF, FAST>(a, s);
+  }
   if (BM == 64 && BN == 128) return launch_cfg<T, OutT, 64, 128, 2, 2, NBUF, FAST>(a, s);
   if (BM == 64 && BN == 64) return launch_cfg<T, OutT, 64, 64, 2, 2, NBUF, FAST>(a, s);
   return -1;
 }
 
-// FAST epilogue: see the kernel.  Only the production dtype (bf16 in, bf16 out, single stage) gets it.
+// FAST epilogue: see the kernel.  Only the production dtype (bf16 in, bf16 out) gets it.
 static bool fast_ok(const ConvArgs& a, int BN) {
   static const int on = SYLPH_AB_ENV("SYLPH_CONV_FAST", 1);
   return on && a.ss_padded_host && (BN > 64 || a.ss_padded) && a.Cout % BN == 0 && (a.out_ld & 7) == 0 && (a.res_mode == 0 || (a.res_ld & 7) == 0) &&
          a.mul_nch == 0 && (a.relu_nch == 0 || a.relu_nch >= a.Cout);
 }
 
-template <typename T, typename OutT>
-static int launch_t(const ConvArgs& a, int BM, int BN, hipStream_t s) {
-#ifdef SYLPH_ABLATE
-  if (g_nbuf == 2) return launch_n<T, OutT, 2, false>(a, BM, BN, s);
-#endif
-  return launch_n<T, OutT, 1, false>(a, BM, BN, s);
+// bf16 operands on NBUF LDS stages: fp32 out, or bf16 out (FAST epilogue where it applies)
+template <int NBUF>
+static int launch_bf16(const ConvArgs& a, bool out_f32, int BM, int BN, hipStream_t s) {
+  if (out_f32) return launch_n<bf16_t, float, NBUF, false>(a, BM, BN, s);
+  return fast_ok(a, BN) ? launch_n<bf16_t, bf16_t, NBUF, true>(a, BM, BN, s) : launch_n<bf16_t, bf16_t, NBUF, false>(a, BM, BN, s);
 }
 
 // Tile choice: widest N tile the layer fills (MFMA-bound 3x3 convs); HBM-bound pointwise convs
@@ -692,12 +644,6 @@ void conv_pick_tile(int rows_total, int cout, int ntaps, int* BM, int* BN) {
   int bn = cout >= 128 ? 128 : (cout > 32 ? 64 : 32);
   // (pointwise convs used to prefer 128x64 for occupancy; since the per-tile instruction diet 128x128 is equal or
   // better on every bottleneck 1x1: less LDS-DMA traffic per flop)
-#ifdef SYLPH_ABLATE
-  if (const char* f = getenv("SYLPH_CONV_FORCE_BN")) {  // tuning knob
-    const int v = atoi(f);
-    if ((v == 64 || v == 128 || v == 256) && cout % v == 0) bn = v;
-  }
-#endif
   int bm = 128;
   if (bn != 32) {
     const long blocks128 = (long)((rows_total + 127) / 128) * ((cout + bn - 1) / bn);
@@ -707,36 +653,24 @@ void conv_pick_tile(int rows_total, int cout, int ntaps, int* BM, int* BN) {
     static const int bn64_max = getenv("SYLPH_CONV_BN64_MAX") ? atoi(getenv("SYLPH_CONV_BN64_MAX")) : 160;
     if (bm == 64 && bn == 128 && cout % 64 == 0 && (long)((rows_total + 63) / 64) * (cout / 128) <= bn64_max) bn = 64;
   }
-#ifdef SYLPH_ABLATE
-  if (const char* f = getenv("SYLPH_CONV_FORCE_BM")) {  // tuning knob
-    const int v = atoi(f);
-    if ((v == 64 || v == 128 || v == 256) && bn != 32) bm = v;
-  }
-#endif
-  if (bn == 256) bm = 128;
-  if (bm == 256 && bn != 128) bm = 128;
   *BM = bm;
   *BN = bn;
 }
 
 int launch_conv(DType dt, bool out_f32, const ConvArgs& a_in, int BM, int BN, hipStream_t s) {
   ConvArgs a = a_in;
-  // stage the residual through LDS on the narrow (HBM-bound) tiles; measured 1.4 % slower (LDS occupancy 5 -> 4 blocks), so off; SYLPH_CONV_RES_LDS=1 enables
-  static const int res_lds_on = SYLPH_AB_ENV("SYLPH_CONV_RES_LDS", 0);
   static const int ss_on = SYLPH_AB_ENV("SYLPH_CONV_SS_LDS", 1);
-  a.res_lds = (res_lds_on && a.res_mode != 0 && BN == 64 && a.Cout % 64 == 0 && (a.res_ld & 7) == 0) ? 1 : 0;
   a.ss_padded_host = a.ss_padded;
   if (!ss_on || BN > 64) a.ss_padded = 0;  // the wide tiles are MFMA-bound and have no VGPRs to spare for the prefetch
-  if (BM == 256 && BN == 256) return conv_hpipe_ok(dt, out_f32, a) ? launch_conv_hpipe(a, s) : -8;
   if (a.KH * a.KW > 31) return -3;
   const int bk = dt == DT_BF16 ? 64 : 32;
   if (a.Cin % bk != 0) return -4;
   if (a.in2 && (a.Cin2 % bk != 0 || a.KH * a.KW != 1)) return -6;
   if (!a.zeros) return -5;
-  if (a.ksplit > 1 && (a.halo || a.in2 || !out_f32 || a.stem || a.gn_partial || a.res_mode != 0 || g_nbuf != 1)) return -10;
+  if (a.ksplit > 1 && (a.halo || a.in2 || !out_f32 || a.stem || a.gn_partial || a.res_mode != 0)) return -10;
   if (dt == DT_BF16) {
     if (a.halo) {  // 3x3 s1 p1 with patch tiles (api_conv.hip builds the matching tile table)
-      if (g_nbuf != 1 || BM != 128 || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.stem || a.in2) return -9;
+      if (BM != 128 || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.stem || a.in2) return -9;
       if (BN == 32) {  // narrow prediction convs (bbox/ctrness, code-generator heads): fp32 or bf16 out
         return out_f32 ? launch_cfg<bf16_t, float, 128, 32, 4, 1, 1, false, true>(a, s)
                        : launch_cfg<bf16_t, bf16_t, 128, 32, 4, 1, 1, false, true>(a, s);
@@ -748,27 +682,10 @@ int launch_conv(DType dt, bool out_f32, const ConvArgs& a_in, int BM, int BN, hi
       return fast ? launch_cfg<bf16_t, bf16_t, 128, 64, 2, 2, 1, true, true>(a, s)
                   : launch_cfg<bf16_t, bf16_t, 128, 64, 2, 2, 1, false, true>(a, s);
     }
-#define SYLPH_IGEMM_RING(NB)                                                                                                                       \
-  do {                                                                                                                                             \
-    const bool fast = !out_f32 && fast_ok(a, BN);                                                                                                  \
-    if (BN == 128) return out_f32 ? launch_cfg<bf16_t, float, 64, 128, 2, 2, NB, false>(a, s)                                                      \
-                                  : (fast ? launch_cfg<bf16_t, bf16_t, 64, 128, 2, 2, NB, true>(a, s) : launch_cfg<bf16_t, bf16_t, 64, 128, 2, 2, NB, false>(a, s)); \
-    return out_f32 ? launch_cfg<bf16_t, float, 64, 64, 2, 2, NB, false>(a, s)                                                                      \
-                   : (fast ? launch_cfg<bf16_t, bf16_t, 64, 64, 2, 2, NB, true>(a, s) : launch_cfg<bf16_t, bf16_t, 64, 64, 2, 2, NB, false>(a, s)); \
-  } while (0)
-    if (a.nbuf2 == 3 && g_nbuf == 1 && BM == 64 && (BN == 128 || BN == 64)) SYLPH_IGEMM_RING(3);
-#undef SYLPH_IGEMM_RING
-    if (a.nbuf2 && g_nbuf == 1 && BM == 64 && (BN == 128 || BN == 64)) {
-      // small launches (fewer blocks than it takes to hide a slice's round trip by occupancy): two LDS stages, the next slice's loads
-      // in flight under the current slice's MFMAs
-      const bool fast = !out_f32 && fast_ok(a, BN);
-      if (BN == 128) return out_f32 ? launch_cfg<bf16_t, float, 64, 128, 2, 2, 2, false>(a, s)
-                                    : (fast ? launch_cfg<bf16_t, bf16_t, 64, 128, 2, 2, 2, true>(a, s) : launch_cfg<bf16_t, bf16_t, 64, 128, 2, 2, 2, false>(a, s));
-      return out_f32 ? launch_cfg<bf16_t, float, 64, 64, 2, 2, 2, false>(a, s)
-                     : (fast ? launch_cfg<bf16_t, bf16_t, 64, 64, 2, 2, 2, true>(a, s) : launch_cfg<bf16_t, bf16_t, 64, 64, 2, 2, 2, false>(a, s));
-    }
-    if (!out_f32 && g_nbuf == 1 && fast_ok(a, BN)) return launch_n<bf16_t, bf16_t, 1, true>(a, BM, BN, s);
-    return out_f32 ? launch_t<bf16_t, float>(a, BM, BN, s) : launch_t<bf16_t, bf16_t>(a, BM, BN, s);
+    // small launches (fewer blocks than it takes to hide a slice's round trip by occupancy): the next slices' loads in flight
+    // under the current slice's MFMAs
+    if (a.nbuf2 && BM == 64) return a.nbuf2 == 3 ? launch_bf16<3>(a, out_f32, BM, BN, s) : launch_bf16<2>(a, out_f32, BM, BN, s);
+    return launch_bf16<1>(a, out_f32, BM, BN, s);
   }
   if (dt == DT_F32S) {  // split-bf16 parity mode: fp32 storage, three bf16 MFMAs per product (MmaSplit)
     if (BM == 128 && BN == 128) return launch_cfg<float, float, 128, 128, 2, 2, 1, false, false, true>(a, s);
@@ -778,7 +695,7 @@ int launch_conv(DType dt, bool out_f32, const ConvArgs& a_in, int BM, int BN, hi
     if (BM == 64 && BN == 64) return launch_cfg<float, float, 64, 64, 2, 2, 1, false, false, true>(a, s);
     return -1;
   }
-  return launch_t<float, float>(a, BM, BN, s);
+  return launch_n<float, float, 1, false>(a, BM, BN, s);
 }
 
 }  // namespace sylph

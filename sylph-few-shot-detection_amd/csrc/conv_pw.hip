@@ -420,7 +420,7 @@ bool conv_pw_tile(int cout, int k_total, bool has_res, int* BM, int* BN) {
 }
 
 bool conv_pw_ok(DType dt, bool out_f32, const ConvArgs& a) {
-  return dt == DT_BF16 && !out_f32 && a.Cout % 128 == 0 && a.KH == 1 && a.KW == 1 && a.pad == 0 && !a.stem && !a.halo && a.group_cout == 0 &&
+  return dt == DT_BF16 && !out_f32 && a.Cout % 128 == 0 && a.KH == 1 && a.KW == 1 && a.pad == 0 && !a.stem && !a.halo &&
          a.mul_nch == 0 && (a.relu_nch == 0 || a.relu_nch >= a.Cout) && !a.gn_partial && !a.gn_coef && a.Cin % 32 == 0 &&
          (!a.in2 || a.Cin2 % 32 == 0) && (a.Cin + (a.in2 ? a.Cin2 : 0)) >= 128 && (a.out_ld & 7) == 0 && (a.in_ld & 7) == 0 &&
          (!a.in2 || (a.in2_ld & 7) == 0) && (a.res_mode == 0 || (a.res_ld & 3) == 0) && a.res_mode >= 0 && a.res_mode <= 2 &&

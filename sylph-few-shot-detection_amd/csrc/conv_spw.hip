@@ -367,7 +367,7 @@ __global__ __launch_bounds__(512, 1) void conv_spw_kernel(const ConvArgs a) {
 }
 
 bool conv_spw_ok(DType dt, bool out_f32, const ConvArgs& a) {
-  if (!(dt == DT_BF16 && !out_f32 && a.Cout % 256 == 0 && a.KH == 1 && a.KW == 1 && a.pad == 0 && !a.stem && !a.halo && a.group_cout == 0 && a.mul_nch == 0 &&
+  if (!(dt == DT_BF16 && !out_f32 && a.Cout % 256 == 0 && a.KH == 1 && a.KW == 1 && a.pad == 0 && !a.stem && !a.halo && a.mul_nch == 0 &&
         (a.relu_nch == 0 || a.relu_nch >= a.Cout) && !a.gn_partial && !a.gn_coef && a.n_ntiles <= 8 && (a.out_ld & 7) == 0 && (a.in_ld & 7) == 0 &&
         a.pw_desc != nullptr && a.pw_table != nullptr))
     return false;

@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(T* __restrict__ x, const 
 
 // Fused variant: the conv epilogue already left (n, mean, M2) per (M-tile, group); every block folds
 // the partials of its segment in tile order (deterministic, fp64) and applies the affine (+ReLU).
-// ngroups = C/8 (32 for one tower, 64 for the paired cls|bbox towers held side by side).
+// ngroups = C/8 (32 for a 256-channel layer).
 // Finalize: one block per segment folds the conv epilogue's per-tile (n, mean, M2) partials of every group in a
 // fixed order (fp64 Chan merges: 1024/ngroups interleaved chains per group, then the chains in index order) and
 // leaves (mean, rstd) per (segment, group).  Done once per layer: the fp64 chain (two divisions per tile) is far

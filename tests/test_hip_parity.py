@@ -187,8 +187,7 @@ def test_head_variants_match_reference_golden(g1, golden_dir, tag, share, norm, 
 @pytest.mark.parametrize("tag,nc,nb,share,norm", [("c2b3", 2, 3, 0, "GN"), ("c1b4_share1", 1, 4, 1, "GN"), ("c3b1_nonorm", 3, 1, 0, "none"),
                                                    ("c0b2", 0, 2, 0, "GN")])
 def test_unequal_tower_depths_match_reference_golden(g1, golden_dir, tag, nc, nb, share, norm, dtype):
-    """MODEL.FCOS.NUM_CLS_CONVS != NUM_BOX_CONVS (the HIP path stacks the two towers into one launch per layer only for equal depths:
-    unequal depths take the un-paired plan), with / without the shared tower and GroupNorm, a depth-0 cls tower -- against goldens
+    """MODEL.FCOS.NUM_CLS_CONVS != NUM_BOX_CONVS, with / without the shared tower and GroupNorm, a depth-0 cls tower -- against goldens
     generated from the reference (g1e).  fp32: head outputs <= 1e-3 and the reference's (level, location, class) set; bf16: head
     outputs to bf16 tolerance.  VERDICT r4 next #1 (re-audit of the round-4 branch additions)."""
     from oracle.decode import detector_postprocess

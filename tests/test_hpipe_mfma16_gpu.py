@@ -47,7 +47,7 @@ def _assert_ulps(got, want, what, max_ulp=1.0, max_frac=0.01):
     assert worst <= max_ulp and frac <= max_frac, f"{what}: {frac:.4f} of elements differ, worst {worst:.2f} ulp"
 
 
-# map, channels, batch: >= 90 blocks of two patches, so the launch rule of api_conv.hip use_hpipe picks conv_hpipe (the
+# map, channels, batch: >= 90 blocks of two patches, so api_conv.hip pick_conv_route picks conv_hpipe (the
 # single-conv entry builds its ops on a scratch context that the per-kernel profile does not see; the tower test below checks
 # the kernel names)
 CONVS = [((100, 168), 256, 2), ((50, 84), 256, 6), ((25, 42), 256, 24), ((13, 21), 256, 64), ((7, 11), 256, 192),

@@ -7,7 +7,8 @@ mkdir -p ../lib/variants
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DSYLPH_ABLATE -DSYLPH_HQ_PROBE"
 /opt/rocm/bin/hipcc $F -c conv_hpipe.hip -o /tmp/hq_conv_hpipe.o
 /opt/rocm/bin/hipcc $F -c ../../tools/probes/conv_hpipe4.hip -o /tmp/hq_conv_hpipe4.o
+make -s -j16
 OBJS=""
-for o in conv_igemm.o conv_pw.o collective.o bottleneck.o head_fused.o stem_conv.o elementwise.o detect.o codegen.o roi_encoder.o api_core.o api_weights.o api_conv.o api_backbone.o api_head.o api_codegen.o api_parity.o; do OBJS="$OBJS $o"; done
+for o in $(make -s --eval='print-objs: ; @echo $(OBJS)' print-objs); do [ "$o" == conv_hpipe.o ] || OBJS="$OBJS $o"; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS /tmp/hq_conv_hpipe.o /tmp/hq_conv_hpipe4.o -ldl -o ../lib/variants/libsylph_hq.so
 echo built ../lib/variants/libsylph_hq.so

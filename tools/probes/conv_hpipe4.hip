@@ -84,7 +84,6 @@ __global__ __launch_bounds__(PNT, 1) void conv_hq_kernel(const ConvArgs a) {
   const T* __restrict__ zero = reinterpret_cast<const T*>(a.zeros);
   const int Cin = a.Cin;
   const int ncc = Cin >> 5;
-  const int goff = a.group_cout > 0 ? ((nt * 256) / a.group_cout) * a.group_in_off : 0;
   const int c0 = (mt + nt) % ncc;
 
   // ---- loader state: lane (r4, s4) of a block-wide global_load_lds fetches 16-byte slot s4 of LDS row (piece * 64 + r4) ----
@@ -103,7 +102,7 @@ __global__ __launch_bounds__(PNT, 1) void conv_hq_kernel(const ConvArgs a) {
     const bool ok = h < HR && hx < PW + 2 && (unsigned)iy < (unsigned)sd.in_H && (unsigned)ix < (unsigned)sd.in_W;
     const int cs = s4 ^ (((hy * PW + hx) >> 2) & 3);
     hcs |= (unsigned)cs << (2 * g);
-    hptr[g] = ok ? reinterpret_cast<const char*>(in + ((size_t)(sd.in_row0 + iy * sd.in_W + ix) * a.in_ld + cs * 8 + goff + c0 * 32))
+    hptr[g] = ok ? reinterpret_cast<const char*>(in + ((size_t)(sd.in_row0 + iy * sd.in_W + ix) * a.in_ld + cs * 8 + c0 * 32))
                  : reinterpret_cast<const char*>(zero + s4 * 8);
     hmask |= (ok ? 1u : 0u) << g;
   }
@@ -265,7 +264,7 @@ __global__ __launch_bounds__(PNT, 1) void conv_hq_kernel(const ConvArgs a) {
     for (int idx = tid; idx < Cin; idx += PNT) {
       const int pch = idx >= Cin / 2 ? 1 : 0, ch = (idx - pch * (Cin / 2)) * 2;
       const int seg = pch ? tl1.x : tl0.x;
-      const float2 c0v = a.gn_coef[(size_t)seg * a.in_ld + goff + ch], c1v = a.gn_coef[(size_t)seg * a.in_ld + goff + ch + 1];
+      const float2 c0v = a.gn_coef[(size_t)seg * a.in_ld + ch], c1v = a.gn_coef[(size_t)seg * a.in_ld + ch + 1];
       *reinterpret_cast<float4*>(smem + COEF_OFF + (pch * Cin + ch) * 8) = make_float4(c0v.x, c1v.x, c0v.y, c1v.y);
     }
   }

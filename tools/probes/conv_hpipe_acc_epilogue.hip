@@ -143,7 +143,6 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
   const T* __restrict__ zero = reinterpret_cast<const T*>(a.zeros);
   const int Cin = a.Cin;
   const int ncc = Cin >> 5;  // 32-channel half-slices
-  const int goff = a.group_cout > 0 ? ((nt * 256) / a.group_cout) * a.group_in_off : 0;
   // K-loop rotation: this block walks the half-slices c0, c0+1, ... (mod ncc); keyed on the pair's place inside its own image, so the
   // summation order of an image's outputs does not depend on the batch around it
   const int c0 = (rot_key + nt) % ncc;
@@ -168,7 +167,7 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
     const bool ok = h < HR && hx < PW + 2 && (unsigned)iy < (unsigned)sd.in_H && (unsigned)ix < (unsigned)sd.in_W;
     const int cs = s4 ^ (((hy * PW + hx) >> 2) & 3);
     hcs |= (unsigned)cs << (2 * g);
-    hptr[g] = ok ? reinterpret_cast<const char*>(in + ((size_t)(sd.in_row0 + iy * sd.in_W + ix) * a.in_ld + cs * 8 + goff + c0 * 32))
+    hptr[g] = ok ? reinterpret_cast<const char*>(in + ((size_t)(sd.in_row0 + iy * sd.in_W + ix) * a.in_ld + cs * 8 + c0 * 32))
                  : reinterpret_cast<const char*>(zero + s4 * 8);
     hmask |= (ok ? 1u : 0u) << g;
   }
@@ -368,7 +367,7 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
     for (int idx = tid; idx < Cin; idx += PNT) {
       const int pch = idx >= Cin / 2 ? 1 : 0, ch = (idx - pch * (Cin / 2)) * 2;
       const int seg = pch ? tl1.x : tl0.x;
-      const float2 c0v = a.gn_coef[(size_t)seg * a.in_ld + goff + ch], c1v = a.gn_coef[(size_t)seg * a.in_ld + goff + ch + 1];
+      const float2 c0v = a.gn_coef[(size_t)seg * a.in_ld + ch], c1v = a.gn_coef[(size_t)seg * a.in_ld + ch + 1];
       *reinterpret_cast<float4*>(smem + COEF_OFF + (pch * Cin + ch) * 8) = make_float4(c0v.x, c1v.x, c0v.y, c1v.y);
     }
   }
@@ -574,10 +573,10 @@ int launch_hpipe_pack_weights(const void* w, void* out, int Cout, int Cin, hipSt
 }
 
 bool conv_hpipe_ok(DType dt, bool out_f32, const ConvArgs& a) {
-  if (a.gn_coef && (a.Cin > COEF_MAX_CIN || a.group_cout > 0)) return false;
+  if (a.gn_coef && a.Cin > COEF_MAX_CIN) return false;
   return dt == DT_BF16 && !out_f32 && !a.stem && !a.in2 && a.res_mode == 0 && a.mul_nch == 0 && a.KH == 3 && a.KW == 3 &&
          a.stride == 1 && a.pad == 1 && (a.relu_nch == 0 || a.relu_nch >= a.Cout) && a.Cout % 256 == 0 && a.Cin % 32 == 0 &&
-         a.Cin >= 32 && a.ss_padded_host && (a.out_ld & 7) == 0 && a.zeros != nullptr;
+         a.Cin >= 32 && a.ss_padded && (a.out_ld & 7) == 0 && a.zeros != nullptr;
 }
 
 #ifdef SYLPH_ABLATE
