@@ -77,6 +77,9 @@ typedef struct sylph_config {
   int tower_deformable;    /* MODEL.FCOS.USE_DEFORMABLE: the LAST conv of the cls and of the bbox tower is a modulated deformable conv (adet
                               DFConv2d, DCNv2): keys {k}.offset.weight / .bias [27,256,3,3] and {k}.conv.weight / .bias instead of {k}.weight
                               / .bias (fcos.py:83-84). */
+  int num_groups;          /* MODEL.RESNETS.NUM_GROUPS: groups of every bottleneck's 3x3 conv2 (1 = ResNet, > 1 = ResNeXt) */
+  int width_per_group;     /* MODEL.RESNETS.WIDTH_PER_GROUP: conv2 channels per group in res2 (doubling per stage); the bottleneck width of
+                              stage s (0 = res2) is num_groups * width_per_group << s (detectron2 build_resnet_backbone) */
 } sylph_config;
 
 /* Fill cfg with the defaults of the COCO Meta-FCOS finetune yaml. */
@@ -257,6 +260,17 @@ int sylph_bottleneck(sylph_ctx* ctx, const float* x_nchw_dev, int B, int Cin, in
  * device; w_host (256,C,1,1), bias_host (256); top (B,256,H/2,W/2) device or NULL (fpn_lateral5); y (B,256,H,W) fp32 NCHW device. */
 int sylph_fpn_lateral(sylph_ctx* ctx, const float* x_nchw_dev, int B, int C, int H, int W, const float* w_host, const float* bias_host,
                       const float* top_nchw_dev, float* y_nchw_dev);
+
+/* Kernel parity entry: ONE grouped 3x3 conv (pad 1) with FrozenBN scale / shift and optional ReLU, as a ResNeXt bottleneck's conv2
+ * launches it (conv_group.hip).  x (B,C,H,W) fp32 NCHW device; w_host (C, C / groups, 3, 3); scale / shift host (C); stride 1 or 2;
+ * y (B,C,Ho,Wo) fp32 NCHW device.  C a multiple of 64, C / groups a power of two in [4, 64]. */
+int sylph_group_conv(sylph_ctx* ctx, const float* x_nchw_dev, int B, int C, int H, int W, int groups, int stride, const float* w_host,
+                     const float* scale_host, const float* shift_host, int relu, float* y_nchw_dev);
+/* Kernel parity entry: ONE ResNeXt BottleneckBlock: sylph_bottleneck with a grouped conv2, w_host[1] (mid, mid / groups, 3, 3),
+ * through the launches sylph_backbone_fpn makes for such a block. */
+int sylph_bottleneck_grouped(sylph_ctx* ctx, const float* x_nchw_dev, int B, int Cin, int H, int W, int stride, int mid, int cout,
+                             int groups, const float* const* w_host, const float* const* scale_host, const float* const* shift_host,
+                             float* y_nchw_dev);
 
 /* Bytes of device memory currently held by the context (weights + workspace). */
 int64_t sylph_device_bytes(sylph_ctx* ctx);

@@ -71,13 +71,36 @@ int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block&
   const int H1 = (Hin - 1) / s1 + 1, W1 = (Win - 1) / s1 + 1;
   const int Ho = (Hin - 1) / stride + 1, Wo = (Win - 1) / stride + 1;
   void *t1 = scr.t1, *t2 = scr.t2, *sc = scr.sc;
+  if (blk.c2.groups > 1) {
+    // ResNeXt: the blocks are up to 8x wider than R-50's (X-101-32x8d res3.0: t1 = 512 channels at res2 resolution, 34 M elements per
+    // image), so at large batches whole-tensor offsets of the 1x1 kernels (conv_igemm's 31-bit element offsets, conv_pw's 32-bit residual
+    // byte offsets) would overflow.  Such a block is built as a sequence of image chunks, each small enough that every tensor of the chunk
+    // stays below 2^31 elements; every chunk runs the block's own launches on its slice of the (dense, image-major) buffers.
+    const long per_img = std::max({(long)Hin * Win * Cin, (long)H1 * W1 * mid, (long)Ho * Wo * mid, (long)Ho * Wo * cout});
+    const int nb = (int)std::min<long>(B, ((1L << 31) - 1) / per_img);
+    if (nb < 1) return fail("image too large for the ResNeXt block kernels: " + std::to_string(per_img) + " elements per image");
+    if (nb < B) {
+      const int nch = (B + nb - 1) / nb, cb = (B + nch - 1) / nch;
+      const size_t e = c->esz();
+      for (int b0 = 0; b0 < B; b0 += cb) {
+        const int n = std::min(cb, B - b0);
+        BkScratch sub{(char*)t1 + (size_t)b0 * H1 * W1 * mid * e, (char*)t2 + (size_t)b0 * Ho * Wo * mid * e,
+                      (char*)sc + (size_t)b0 * Ho * Wo * cout * e, scr.trash};
+        RET(add_bottleneck(c, ops, blk, n, (const char*)X + (size_t)b0 * Hin * Win * Cin * e, Cin, Hin, Win, stride, mid, cout,
+                           (char*)Y + (size_t)b0 * Ho * Wo * cout * e, sub));
+      }
+      return 0;
+    }
+  }
   // res2 identity blocks (C 256, mid 64, stride 1, no projection), bf16: ONE fused kernel (bottleneck.hip): the two
   // 64-channel intermediates and the second read of x never reach HBM (2 048 -> 1 024 B per position)
   static const int fuse_bn = getenv("SYLPH_FUSE_BOTTLENECK") ? atoi(getenv("SYLPH_FUSE_BOTTLENECK")) : 1;
-  const bool fuse_id = fuse_bn && dt == DT_BF16 && !blk.has_sc && stride == 1 && mid == 64 && Cin == 256 && cout == 256 &&
+  // (a grouped conv2 -- ResNeXt -- never takes the fused R-50 kernels nor conv_rw3: they compute a dense 3x3)
+  const bool dense2 = blk.c2.groups == 1;
+  const bool fuse_id = fuse_bn && dense2 && dt == DT_BF16 && !blk.has_sc && stride == 1 && mid == 64 && Cin == 256 && cout == 256 &&
                        blk.c1.Cout_pad == 64 && blk.c2.Cout_pad == 64 && blk.c3.Cout_pad == 256;
   // first block of res2 (64 -> 64 -> 64 -> 256, projection folded into conv3's GEMM, stride 1): one fused kernel too
-  const bool fuse_pr = fuse_bn && dt == DT_BF16 && blk.fused_sc && stride == 1 && mid == 64 && Cin == 64 && cout == 256 &&
+  const bool fuse_pr = fuse_bn && dense2 && dt == DT_BF16 && blk.fused_sc && stride == 1 && mid == 64 && Cin == 64 && cout == 256 &&
                        blk.c1.Cout_pad == 64 && blk.c2.Cout_pad == 64 && blk.c3sc.Cout_pad == 256 && blk.c3sc.Cin == 128 && !blk.c3sc.scale;
   if ((fuse_id || fuse_pr) && (size_t)Hin * Win * 512 < ((size_t)1 << 32) && (size_t)B * Hin * Win < ((size_t)1 << 31)) {  // 32-bit byte offsets inside ONE image (64-bit image base)
     BottleneckArgs ba;
@@ -104,12 +127,25 @@ int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block&
   RET(add_conv(c, ops, blk.c1, X, Cin, t1, mid, image_segs(B, Hin, Win, H1, W1), o1));
   // res3 conv2 (3x3, 128 -> 128, stride 1), bf16: weights in registers, LDS holds only the activation halo (conv_rw3.hip)
   static const int rw3_on = getenv("SYLPH_CONV_RW3") ? atoi(getenv("SYLPH_CONV_RW3")) : 1;
-  const bool rw3 = rw3_on && dt == DT_BF16 && mid == 128 && s3 == 1 && blk.c2.Cin == 128 && blk.c2.Cout_pad == 128 && blk.c2.KH == 3 && blk.c2.KW == 3 &&
+  const bool rw3 = rw3_on && dense2 && dt == DT_BF16 && mid == 128 && s3 == 1 && blk.c2.Cin == 128 && blk.c2.Cout_pad == 128 && blk.c2.KH == 3 && blk.c2.KW == 3 &&
                    blk.c2.scale && blk.c2.shift && (size_t)B * H1 * W1 * 256 < ((size_t)1 << 31) &&  // (2 GiB buffer descriptors)
                    (rw3_on == 2 || (size_t)B * H1 * W1 >= (size_t)256 * 120);
   int ph = 0, pw = 0;
   if (rw3) pick_patch(H1, W1, 128, 184, 2, &ph, &pw);  // 100 x 168 -> 10 x 12 patches (halo 12 x 14 = 168 rows)
-  if (rw3 && conv_rw3_patch_ok(ph, pw)) {
+  if (!dense2) {
+    // ResNeXt conv2: grouped 3x3 (stride s3) + FrozenBN + ReLU, conv_group.hip, on the dense images t1 [B][H1 * W1][mid] -> t2
+    const int cpg = mid / blk.c2.groups;
+    if (blk.c2.Cin != mid || blk.c2.Cout != mid || mid % 64 != 0 || cpg < 4 || cpg > 64 || (cpg & (cpg - 1)) != 0)
+      return fail("internal: grouped conv2 shape");
+    if ((long)H1 * W1 * mid >= (1L << 31))
+      return fail("image too large for conv_group: " + std::to_string((long)H1 * W1 * mid) + " elements per image exceed its 31-bit offsets");
+    GroupConvArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.x = t1; ga.y = t2; ga.wt = blk.c2.w; ga.scale = blk.c2.scale; ga.shift = blk.c2.shift;
+    ga.B = B; ga.C = mid; ga.cpg = cpg; ga.Hin = H1; ga.Win = W1; ga.Ho = Ho; ga.Wo = Wo; ga.stride = s3; ga.relu = 1;
+    const double fl = 2.0 * (double)B * Ho * Wo * mid * 9.0 * cpg;
+    ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_group_kernel", fl, s, [=](hipStream_t st) { return launch_conv_group(dt, ga, st); }); });
+  } else if (rw3 && conv_rw3_patch_ok(ph, pw)) {
     BottleneckArgs ba;
     memset(&ba, 0, sizeof(ba));
     ba.x = t1; ba.y = t2;
@@ -195,7 +231,7 @@ int build_backbone(sylph_ctx* c, Plan* P) {
   const void* stage_out[4] = {nullptr, nullptr, nullptr, nullptr};
   int stage_h[4], stage_w[4];
   for (int si = 0; si < 4; ++si) {
-    const int mid = 64 << si, cout = 256 << si;
+    const int mid = (c->cfg.num_groups * c->cfg.width_per_group) << si, cout = 256 << si;  // (ResNeXt: num_groups > 1)
     const int first_stride = si == 0 ? 1 : 2;
     const int Hs = (Hin - 1) / first_stride + 1, Ws = (Win - 1) / first_stride + 1;
     void *t1, *t2, *sc, *Ya, *Yb;

@@ -132,6 +132,7 @@ void sylph_config_default(sylph_config* cfg) {
   cfg->num_share_convs = 0; cfg->tower_norm = 0;
   cfg->cg_tower_gn_mask = 0x3fffffff; cfg->cg_tower_relu_mask = 0x3fffffff;  // every TOWER_LAYERS entry is ["GN", "ReLU"]
   cfg->tower_deformable = 0;
+  cfg->num_groups = 1; cfg->width_per_group = 64;
 }
 
 const char* sylph_last_error(void) { return g_err.c_str(); }
@@ -188,6 +189,15 @@ int sylph_set_config(sylph_ctx* c, const sylph_config* cfg) {
   if (cfg->nlevels != 5) return fail("only the 5-level FCOS pyramid (p3..p7) is supported");
   if (cfg->resnet_depth != 50 && cfg->resnet_depth != 101 && cfg->resnet_depth != 152)
     return fail("MODEL.RESNETS.DEPTH must be 50, 101 or 152");
+  if (cfg->num_groups != 1 || cfg->width_per_group != 64) {  // ResNeXt: what conv_group.hip covers (sylph_amd/engine.py config_from_cfg)
+    bool ok = cfg->num_groups >= 1 && cfg->width_per_group >= 1 && (cfg->num_groups * cfg->width_per_group) % 64 == 0;
+    for (int s = 0; s < 4 && ok; ++s) {
+      const int w = cfg->width_per_group << s;
+      ok = w >= 4 && w <= 64 && (w & (w - 1)) == 0;
+    }
+    if (!ok) return fail("MODEL.RESNETS.NUM_GROUPS / WIDTH_PER_GROUP: a per-group width that is a power of two in [4, 64] at every stage "
+                         "and NUM_GROUPS * WIDTH_PER_GROUP a multiple of 64 are required");
+  }
   c->cfg = *cfg;
   return 0;
 }

@@ -68,6 +68,7 @@ struct ConvLayer {
   float* scale = nullptr;  // device, Cout_pad (may be null)
   float* shift = nullptr;
   int Cin = 0, Cout = 0, Cout_pad = 0, KH = 1, KW = 1;
+  int groups = 1;          // > 1: grouped 3x3 conv (ResNeXt conv2), w in conv_group_pack's layout, scale / shift Cout floats
 };
 struct GNLayer {
   float* gamma = nullptr;
@@ -314,6 +315,8 @@ const HostTensor* find_w(sylph_ctx* c, const std::string& k);
 int pack_conv(sylph_ctx* c, const std::vector<const HostTensor*>& ws, ConvLayer* L);
 int upload_vec(sylph_ctx* c, float** dev, const std::vector<float>& v, int pad_to);
 int make_conv_bn(sylph_ctx* c, const std::string& name, ConvLayer* L);
+int pack_conv_grouped(sylph_ctx* c, const HostTensor& w, const std::string& key, int C, int groups, const float* scale, const float* shift,
+                      ConvLayer* L);
 int make_conv_bias(sylph_ctx* c, const std::vector<std::string>& names, ConvLayer* L);
 int make_c3sc(sylph_ctx* c, const HostTensor& w3, const float* s3, const float* h3, const HostTensor& ws, const float* ss, const float* hs, ConvLayer* L);
 int make_gn(sylph_ctx* c, const std::string& name, GNLayer* G);

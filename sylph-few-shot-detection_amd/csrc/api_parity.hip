@@ -78,8 +78,8 @@ int sylph_export_tower(sylph_ctx* c, int tower, int layer, int level, float* y, 
   return 0;
 }
 
-int sylph_bottleneck(sylph_ctx* c, const float* x, int B, int Cin, int H, int W, int stride, int mid, int cout, const float* const* w_host,
-                     const float* const* scale_host, const float* const* shift_host, float* y) {
+static int bottleneck_entry(sylph_ctx* c, const float* x, int B, int Cin, int H, int W, int stride, int mid, int cout, int groups,
+                            const float* const* w_host, const float* const* scale_host, const float* const* shift_host, float* y) {
   HIPCHK(hipSetDevice(c->device));
   const int bk = c->dt == DT_BF16 ? 64 : 32;
   if (Cin % bk != 0 || mid % bk != 0) return fail("sylph_bottleneck: channel counts must be multiples of " + std::to_string(bk));
@@ -94,8 +94,13 @@ int sylph_bottleneck(sylph_ctx* c, const float* x, int B, int Cin, int H, int W,
   ConvLayer* Ls[4] = {&blk.c1, &blk.c2, &blk.c3, &blk.sc};
   HostTensor hw[4];
   for (int i = 0; i < (has_sc ? 4 : 3); ++i) {
-    hw[i].shape = {couts[i], cins[i], ks[i], ks[i]};
-    hw[i].data.assign(w_host[i], w_host[i] + (size_t)couts[i] * cins[i] * ks[i] * ks[i]);
+    const int cin_w = i == 1 ? cins[i] / groups : cins[i];
+    hw[i].shape = {couts[i], cin_w, ks[i], ks[i]};
+    hw[i].data.assign(w_host[i], w_host[i] + (size_t)couts[i] * cin_w * ks[i] * ks[i]);
+    if (i == 1 && groups > 1) {  // ResNeXt conv2 (conv_group.hip)
+      RET(pack_conv_grouped(&tmp, hw[i], "conv2.weight", mid, groups, scale_host[i], shift_host[i], Ls[i]));
+      continue;
+    }
     RET(pack_conv(&tmp, {&hw[i]}, Ls[i]));
     RET(upload_vec(&tmp, &Ls[i]->scale, std::vector<float>(scale_host[i], scale_host[i] + couts[i]), Ls[i]->Cout_pad));
     RET(upload_vec(&tmp, &Ls[i]->shift, std::vector<float>(shift_host[i], shift_host[i] + couts[i]), Ls[i]->Cout_pad));
@@ -124,6 +129,51 @@ int sylph_bottleneck(sylph_ctx* c, const float* x, int B, int Cin, int H, int W,
   tmp.prof_recs.clear();
   for (int b = 0; b < B; ++b)
     KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * cout * Ho * Wo, cout, Ho * Wo, b * Ho * Wo, cout, c->stream), "export");
+  return 0;
+}
+
+int sylph_bottleneck(sylph_ctx* c, const float* x, int B, int Cin, int H, int W, int stride, int mid, int cout, const float* const* w_host,
+                     const float* const* scale_host, const float* const* shift_host, float* y) {
+  return bottleneck_entry(c, x, B, Cin, H, W, stride, mid, cout, 1, w_host, scale_host, shift_host, y);
+}
+
+int sylph_bottleneck_grouped(sylph_ctx* c, const float* x, int B, int Cin, int H, int W, int stride, int mid, int cout, int groups,
+                             const float* const* w_host, const float* const* scale_host, const float* const* shift_host, float* y) {
+  if (groups < 1 || mid % groups != 0) return fail("sylph_bottleneck_grouped: mid must be a multiple of groups");
+  return bottleneck_entry(c, x, B, Cin, H, W, stride, mid, cout, groups, w_host, scale_host, shift_host, y);
+}
+
+int sylph_group_conv(sylph_ctx* c, const float* x, int B, int C, int H, int W, int groups, int stride, const float* w_host,
+                     const float* scale_host, const float* shift_host, int relu, float* y) {
+  HIPCHK(hipSetDevice(c->device));
+  if (groups < 1 || C % groups != 0 || (stride != 1 && stride != 2) || B < 1) return fail("sylph_group_conv: bad arguments");
+  sylph_ctx tmp;  // scratch allocations freed on return
+  tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros; tmp.cfg = c->cfg;
+  tmp.prof = c->prof;
+  struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
+  HostTensor hw;
+  hw.shape = {C, C / groups, 3, 3};
+  hw.data.assign(w_host, w_host + (size_t)C * (C / groups) * 9);
+  ConvLayer L;
+  RET(pack_conv_grouped(&tmp, hw, "sylph_group_conv weight", C, groups, scale_host, shift_host, &L));
+  const size_t e = tmp.esz();
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  void *xin, *yout;
+  RET(tmp.dalloc(&xin, (size_t)B * H * W * C * e));
+  RET(tmp.dalloc(&yout, (size_t)B * Ho * Wo * C * e));
+  for (int b = 0; b < B; ++b)
+    KCHK(launch_import_nchw(c->dt, x + (size_t)b * C * H * W, xin, C, H * W, b * H * W, C, c->stream), "import");
+  GroupConvArgs ga;
+  memset(&ga, 0, sizeof(ga));
+  ga.x = xin; ga.y = yout; ga.wt = L.w; ga.scale = L.scale; ga.shift = L.shift;
+  ga.B = B; ga.C = C; ga.cpg = C / groups; ga.Hin = H; ga.Win = W; ga.Ho = Ho; ga.Wo = Wo; ga.stride = stride; ga.relu = relu ? 1 : 0;
+  const double fl = 2.0 * (double)B * Ho * Wo * C * 9.0 * (C / groups);
+  const DType dt = c->dt;
+  KCHK(timed_op(&tmp, "conv_group_kernel", fl, c->stream, [=](hipStream_t st) { return launch_conv_group(dt, ga, st); }), "conv_group");
+  for (auto& r : tmp.prof_recs) c->prof_recs.push_back(r);
+  tmp.prof_recs.clear();
+  for (int b = 0; b < B; ++b)
+    KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * C * Ho * Wo, C, Ho * Wo, b * Ho * Wo, C, c->stream), "export");
   return 0;
 }
 

@@ -12,6 +12,7 @@ const HostTensor* find_w(sylph_ctx* c, const std::string& k) {
 // pack (Cout,Cin,KH,KW) fp32 -> [Cout_pad][KH][KW][Cin] compute dtype; several tensors may be stacked on Cout
 int pack_conv(sylph_ctx* c, const std::vector<const HostTensor*>& ws, ConvLayer* L) {
   const HostTensor* w0 = ws[0];
+  if (L->groups != 1) return fail("internal: pack_conv builds dense layers only (a grouped conv is packed by pack_conv_grouped)");
   if (w0->shape.size() != 4) return fail("conv weight must be 4-D");
   const int Cin = (int)w0->shape[1], KH = (int)w0->shape[2], KW = (int)w0->shape[3];
   int Cout = 0;
@@ -82,6 +83,52 @@ int make_conv_bn(sylph_ctx* c, const std::string& name, ConvLayer* L) {
   RET(upload_vec(c, &L->scale, sc, L->Cout_pad));
   RET(upload_vec(c, &L->shift, sh, L->Cout_pad));
   return 0;
+}
+
+// grouped 3x3 conv (ResNeXt conv2, detectron2 Conv2d(C, C, 3, groups=G)): weight (C, C / G, 3, 3) in conv_group.hip's layout,
+// FrozenBN folded into scale / shift.  `key` names the weight in errors.
+int pack_conv_grouped(sylph_ctx* c, const HostTensor& w, const std::string& key, int C, int groups, const float* scale, const float* shift,
+                      ConvLayer* L) {
+  if (groups < 1 || C % groups != 0) return fail(key + ": bad group count");
+  const int cpg = C / groups;
+  if (w.shape.size() != 4 || w.shape[0] != C || w.shape[1] != cpg || w.shape[2] != 3 || w.shape[3] != 3) {
+    std::string got;
+    for (size_t i = 0; i < w.shape.size(); ++i) got += (i ? ", " : "") + std::to_string(w.shape[i]);
+    return fail(key + ": shape (" + got + ") where the config (MODEL.RESNETS.NUM_GROUPS " + std::to_string(groups) + ") needs (" +
+                std::to_string(C) + ", " + std::to_string(cpg) + ", 3, 3)");
+  }
+  if (C % 64 != 0 || cpg < 4 || cpg > 64 || (cpg & (cpg - 1)) != 0)
+    return fail(key + ": a grouped conv needs C % 64 == 0 and C / groups a power of two in [4, 64]");
+  std::vector<uint8_t> packed(conv_group_packed_bytes(c->dt, C, cpg));
+  conv_group_pack(c->dt, w.data.data(), C, cpg, packed.data());
+  L->Cin = C; L->Cout = C; L->Cout_pad = C; L->KH = 3; L->KW = 3; L->groups = groups;
+  RET(upload(c, &L->w, packed.data(), packed.size()));
+  RET(upload_vec(c, &L->scale, std::vector<float>(scale, scale + C), C));
+  RET(upload_vec(c, &L->shift, std::vector<float>(shift, shift + C), C));
+  return 0;
+}
+
+// a bottleneck's conv2 + FrozenBN: (mid, mid / groups, 3, 3) checked against the config, grouped or dense
+int make_conv2_bn(sylph_ctx* c, const std::string& name, int mid, int groups, ConvLayer* L) {
+  const HostTensor* w = find_w(c, name + ".weight");
+  if (w && (w->shape.size() != 4 || w->shape[0] != mid || w->shape[1] != mid / groups || w->shape[2] != 3 || w->shape[3] != 3)) {
+    std::string got;
+    for (size_t i = 0; i < w->shape.size(); ++i) got += (i ? ", " : "") + std::to_string(w->shape[i]);
+    return fail(name + ".weight: shape (" + got + ") where the config (MODEL.RESNETS.NUM_GROUPS " + std::to_string(groups) +
+                ", WIDTH_PER_GROUP " + std::to_string(c->cfg.width_per_group) + ") needs (" + std::to_string(mid) + ", " +
+                std::to_string(mid / groups) + ", 3, 3)");
+  }
+  if (groups == 1) return make_conv_bn(c, name, L);
+  const HostTensor *g = find_w(c, name + ".norm.weight"), *b = find_w(c, name + ".norm.bias");
+  const HostTensor *rm = find_w(c, name + ".norm.running_mean"), *rv = find_w(c, name + ".norm.running_var");
+  if (!w || !g || !b || !rm || !rv) return fail("missing weights for " + name);
+  std::vector<float> sc(mid), sh(mid);
+  for (int i = 0; i < mid; ++i) {
+    const float s = g->data[i] * (1.0f / sqrtf(rv->data[i] + 1e-5f));
+    sc[i] = s;
+    sh[i] = b->data[i] - rm->data[i] * s;
+  }
+  return pack_conv_grouped(c, *w, name + ".weight", mid, groups, sc.data(), sh.data(), L);
 }
 
 int make_conv_bias(sylph_ctx* c, const std::vector<std::string>& names, ConvLayer* L) {
@@ -224,7 +271,7 @@ int sylph_finalize_weights(sylph_ctx* c) {
         const std::string q = bu + ".res" + std::to_string(si + 2) + "." + std::to_string(bi);
         auto& blk = c->stages[si][bi];
         RET(make_conv_bn(c, q + ".conv1", &blk.c1));
-        RET(make_conv_bn(c, q + ".conv2", &blk.c2));
+        RET(make_conv2_bn(c, q + ".conv2", (c->cfg.num_groups * c->cfg.width_per_group) << si, c->cfg.num_groups, &blk.c2));
         RET(make_conv_bn(c, q + ".conv3", &blk.c3));
         blk.has_sc = bi == 0;
         if (blk.has_sc) RET(make_conv_bn(c, q + ".shortcut", &blk.sc));

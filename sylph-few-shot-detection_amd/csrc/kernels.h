@@ -123,6 +123,21 @@ struct DeformArgs {
 };
 int launch_conv_deform(DType dt, const DeformArgs& a, hipStream_t s);
 
+// conv_group.hip: grouped 3x3 conv (ResNeXt bottleneck conv2), pad 1, stride 1 / 2, FrozenBN scale / shift (+ ReLU) in the epilogue.
+// x [B][Hin * Win][C] -> y [B][Ho * Wo][C] (storage dtype, dense images); wt: conv_group_pack's layout (conv_group_packed_bytes);
+// scale / shift: C fp32.  C % 64 == 0, cpg = C / groups a power of two in [4, 64].
+struct GroupConvArgs {
+  const void* x;
+  void* y;
+  const void* wt;
+  const float* scale;
+  const float* shift;
+  int B, C, cpg, Hin, Win, Ho, Wo, stride, relu;
+};
+size_t conv_group_packed_bytes(DType dt, int C, int cpg);
+void conv_group_pack(DType dt, const float* w, int C, int cpg, void* out);
+int launch_conv_group(DType dt, const GroupConvArgs& a, hipStream_t s);
+
 // detect.hip
 // many-way class-conditional conv fused with the scan (detect.hip); x: raw cls-tower output, coef: its GroupNorm (a, b) per
 // (segment, channel), w: packed codes [>= 32 * ceil(N/32)][256] bf16, wf_ws: as many bytes of workspace (the codes in MFMA

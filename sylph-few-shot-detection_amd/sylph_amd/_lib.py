@@ -31,7 +31,7 @@ class SylphConfig(Structure):
         ("cg_type", c_int), ("tok_num_conv", c_int), ("tok_num_fc", c_int), ("enc_layers", c_int),
         ("head_num_fc", c_int), ("head_fc_dim", c_int), ("cg_meta_bias", c_int), ("cg_has_weight", c_int), ("cg_has_scale", c_int),
         ("num_share_convs", c_int), ("tower_norm", c_int), ("cg_tower_gn_mask", c_int), ("cg_tower_relu_mask", c_int),
-        ("tower_deformable", c_int),
+        ("tower_deformable", c_int), ("num_groups", c_int), ("width_per_group", c_int),
     ]
 
 
@@ -80,6 +80,9 @@ PROTOTYPES = {
     "sylph_comm_init_rank": (c_int, [c_void_p, ctypes.c_char_p, c_int, c_int, POINTER(c_void_p)]),
     "sylph_comm_destroy": (c_int, [c_void_p]),
     "sylph_fpn_lateral": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylph_group_conv": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "sylph_bottleneck_grouped": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                                                            c_void_p]),
     "sylph_device_bytes": (c_int64, [c_void_p]),
     "sylph_profile_enable": (c_int, [c_void_p, c_int]),
     "sylph_bench_conv": (c_int, [c_void_p] + [c_int] * 12 + [POINTER(c_float), POINTER(ctypes.c_double)]),

@@ -39,8 +39,18 @@ def config_from_cfg(cfg) -> SylphConfig:
     sc.tower_deformable = int(bool(f.get("USE_DEFORMABLE", False)))
     # backbone branches the five target configs leave at their defaults: refuse them instead of silently building the default graph
     r = m.RESNETS
-    if int(r.get("NUM_GROUPS", 1)) != 1 or int(r.get("WIDTH_PER_GROUP", 64)) != 64:
-        raise NotImplementedError("MODEL.RESNETS.NUM_GROUPS / WIDTH_PER_GROUP: only the plain ResNet bottleneck (1 group x 64) is supported (no ResNeXt)")
+    # ResNeXt (grouped 3x3 conv2, csrc/conv_group.hip): per-group width WIDTH_PER_GROUP << s a power of two in [4, 64] at every stage,
+    # NUM_GROUPS * WIDTH_PER_GROUP a multiple of 64; the plain ResNet bottleneck is 1 group x 64
+    ng, wpg = int(r.get("NUM_GROUPS", 1)), int(r.get("WIDTH_PER_GROUP", 64))
+    if ng != 1 or wpg != 64:
+        if sc.resnet_depth not in (50, 101, 152):
+            raise NotImplementedError(f"MODEL.RESNETS.DEPTH {sc.resnet_depth}: ResNeXt needs DEPTH 50, 101 or 152")
+        widths = [wpg << s for s in range(4)]
+        if ng < 1 or wpg < 1 or any(w < 4 or w > 64 or (w & (w - 1)) for w in widths) or (ng * wpg) % 64 != 0:
+            raise NotImplementedError(
+                f"MODEL.RESNETS.NUM_GROUPS {ng} / WIDTH_PER_GROUP {wpg}: the grouped conv needs a per-group width WIDTH_PER_GROUP << s "
+                f"that is a power of two in [4, 64] at every stage (here {widths}) and NUM_GROUPS * WIDTH_PER_GROUP a multiple of 64")
+    sc.num_groups, sc.width_per_group = ng, wpg
     if any(bool(v) for v in r.get("DEFORM_ON_PER_STAGE", [False] * 4)):
         raise NotImplementedError("MODEL.RESNETS.DEFORM_ON_PER_STAGE: deformable bottleneck convs are not supported")
     if int(r.get("RES5_DILATION", 1)) != 1:
@@ -620,6 +630,34 @@ class Engine:
         y = torch.empty(B, cout, Ho, Wo, device=self.device)
         check(self.L.sylph_bottleneck(self._ctx, _ptr(x), B, Cin, H, W, stride, mid, cout, arrs[0], arrs[1], arrs[2], _ptr(y)),
               "bottleneck")
+        return y
+
+    def bottleneck_grouped(self, x, ws, scales, shifts, stride=1, groups=32):
+        """One ResNeXt bottleneck block (conv2 grouped, weight (mid, mid / groups, 3, 3)) through the backbone's own launches."""
+        self._stream()
+        x = x.to(self.device, torch.float32).contiguous()
+        B, Cin, H, W = x.shape
+        mid, cout = ws[0].shape[0], ws[2].shape[0]
+        n = 4 if len(ws) > 3 and ws[3] is not None else 3
+        keep = [[t.detach().cpu().float().contiguous() for t in lst[:n]] for lst in (ws, scales, shifts)]
+        arrs = [(c_void_p * 4)(*([t.data_ptr() for t in lst] + [None] * (4 - n))) for lst in keep]
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        y = torch.empty(B, cout, Ho, Wo, device=self.device)
+        check(self.L.sylph_bottleneck_grouped(self._ctx, _ptr(x), B, Cin, H, W, stride, mid, cout, groups, arrs[0], arrs[1], arrs[2],
+                                              _ptr(y)), "bottleneck_grouped")
+        return y
+
+    def group_conv(self, x, w, scale, shift, groups, stride=1, relu=True):
+        """One grouped 3x3 conv (pad 1) + FrozenBN scale / shift (+ ReLU) through the ResNeXt conv2 kernel (conv_group.hip)."""
+        self._stream()
+        x = x.to(self.device, torch.float32).contiguous()
+        B, C, H, W = x.shape
+        wh = w.detach().cpu().float().contiguous()
+        sc, sh = scale.detach().cpu().float().contiguous(), shift.detach().cpu().float().contiguous()
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        y = torch.empty(B, C, Ho, Wo, device=self.device)
+        check(self.L.sylph_group_conv(self._ctx, _ptr(x), B, C, H, W, groups, stride, _ptr(wh), _ptr(sc), _ptr(sh), int(relu), _ptr(y)),
+              "group_conv")
         return y
 
     def fpn_lateral(self, x, w, bias, top=None):

@@ -38,8 +38,13 @@ def _gn(g, sd, prefix, c):
     sd[prefix + ".bias"] = 0.1 * torch.randn(c, generator=g)
 
 
-def backbone_state_dict(seed: int = 0, depth: int = 50) -> Dict[str, torch.Tensor]:
+def backbone_state_dict(seed: int = 0, depth: int = 50, num_groups: int = 1, width_per_group: int = 64) -> Dict[str, torch.Tensor]:
+    """num_groups / width_per_group (MODEL.RESNETS.*): a ResNeXt backbone (detectron2 build_resnet_backbone) with bottleneck width
+    num_groups * width_per_group << stage and conv2 weights (mid, mid / num_groups, 3, 3).  Its conv1 / conv2 / conv3 tensors come
+    from a generator of their own, so the default (1 x 64) dict is unchanged."""
     g = torch.Generator().manual_seed(seed)
+    grouped = (num_groups, width_per_group) != (1, 64)
+    gx = torch.Generator().manual_seed(seed + 7919) if grouped else g
     sd = {}
     p = "backbone.bottom_up"
     # inputs are O(100) (0..255 minus mean): scale the stem so activations are O(1)
@@ -48,19 +53,19 @@ def backbone_state_dict(seed: int = 0, depth: int = 50) -> Dict[str, torch.Tenso
     cin = 64
     for si, nb in enumerate(STAGE_BLOCKS[depth]):
         stage = si + 2
-        mid, cout = 64 * 2 ** si, 256 * 2 ** si
+        mid, cout = (num_groups * width_per_group) << si, 256 * 2 ** si
         for bi in range(nb):
             q = f"{p}.res{stage}.{bi}"
             if bi == 0:
                 sd[f"{q}.shortcut.weight"] = _conv(g, cout, cin, 1)
                 _bn(g, sd, f"{q}.shortcut.norm", cout)
-            sd[f"{q}.conv1.weight"] = _conv(g, mid, cin, 1)
-            _bn(g, sd, f"{q}.conv1.norm", mid)
-            sd[f"{q}.conv2.weight"] = _conv(g, mid, mid, 3)
-            _bn(g, sd, f"{q}.conv2.norm", mid)
+            sd[f"{q}.conv1.weight"] = _conv(gx, mid, cin, 1)
+            _bn(gx, sd, f"{q}.conv1.norm", mid)
+            sd[f"{q}.conv2.weight"] = _conv(gx, mid, mid // num_groups, 3)
+            _bn(gx, sd, f"{q}.conv2.norm", mid)
             # keep the residual branch small so activations stay O(1) through 16-33 blocks
-            sd[f"{q}.conv3.weight"] = _conv(g, cout, mid, 1) * 0.25
-            _bn(g, sd, f"{q}.conv3.norm", cout)
+            sd[f"{q}.conv3.weight"] = _conv(gx, cout, mid, 1) * 0.25
+            _bn(gx, sd, f"{q}.conv3.norm", cout)
             cin = cout
     for stage, c in ((3, 512), (4, 1024), (5, 2048)):
         sd[f"backbone.fpn_lateral{stage}.weight"] = _conv(g, 256, c, 1, std=math.sqrt(1.0 / c))
