@@ -30,14 +30,9 @@
 //
 // P1 recomputes conv1 on the (ph+2) x (pw+2) halo (+40 % of its flops); halo positions outside the image are forced to 0
 // (they are conv2's zero padding).  P2 reads shifted rows of the t1 halo exactly like conv_igemm.hip's HALO mode.
-#include "common.h"
-
-#include <stdlib.h>
+#include "gfx950.h"
 
 namespace sylph {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
 namespace {
 constexpr int MID = 64, C = 256;
@@ -47,50 +42,6 @@ constexpr int TP = 144;                        // t1 / t2 row pitch: 128 B of ch
 constexpr int T1_OFF = XB_BYTES;               // 27 648: t1 halo [192][64 ch]; t2 [128][64 ch] aliases it
 constexpr int BN_OFF = T1_OFF + XROWS * TP;    // s1 b1 s2 b2 (64 each) s3 b3 (256 each), fp32
 constexpr int LDS_BYTES = BN_OFF + (4 * MID + 2 * C) * 4;  // 129 024
-
-// MFMA with the weight fragment read straight from an AGPR and the accumulator in arch VGPRs.  Through the builtin hipcc keeps
-// weights and accumulators in AGPRs only as spill space and pays a v_accvgpr_read per use (~450 per tile, all on the one wave
-// that also has to issue the MFMAs).  Inline asm is invisible to the hazard recogniser: BK_MFMA_DRAIN* before the first VALU
-// read of an accumulator supplies the wait states (16-pass MFMA: 18) it would have inserted.
-#define BK_MFMA(acc, w, av) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(av))
-// first k-step of a chain: srcC = 0 (a VALU zero-fill followed by an MFMA reading it is a 2-wait-state hazard nobody would pad)
-#define BK_MFMA0(acc, w, av) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(acc) : "a"(w), "v"(av))
-// (the accumulators are operands of the drain: their VALU reads must not be scheduled above it)
-#define BK_MFMA_DRAIN2(a0, a1) asm volatile("s_nop 15\n\ts_nop 3" : "+v"(a0), "+v"(a1)::"memory")
-#define BK_MFMA_DRAIN3(a0, a1, a2) asm volatile("s_nop 15\n\ts_nop 3" : "+v"(a0), "+v"(a1), "+v"(a2)::"memory")
-
-// Ablation switches (measurement aids: BK_ONLY = run only phase 1 / 2 / 3 of every tile, BK_NOBAR, BK_NOP1, BK_NOP2, BK_NOX, BK_NOE3,
-// BK_NOSTORE) exist ONLY in builds made with -DSYLPH_ABLATE (tools/build_variant.sh -> lib/variants/): the product library is
-// compiled without it and every switch is forced off here.
-#ifndef SYLPH_ABLATE
-#undef BK_ONLY
-#undef BK_NOBAR
-#undef BK_NOP1
-#undef BK_NOP2
-#undef BK_NOX
-#undef BK_NOE3
-#undef BK_NOSTORE
-#undef BK_TIMING
-#endif
-// BK_TIMING (SYLPH_ABLATE builds): s_memtime stamps of the phases of patch 10, printed by block 8 (tools/bench_bottleneck.py shows them)
-#ifdef BK_TIMING
-#define BK_STAMP(i) do { if (it == 10) ts[i] = __builtin_readcyclecounter(); } while (0)
-#else
-#define BK_STAMP(i) do { } while (0)
-#endif
-#ifndef BK_ONLY
-#define BK_ONLY 0
-#endif
-#ifdef BK_NOBAR
-#define BK_BAR() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#else
-#define BK_BAR()                                       \
-  do {                                                 \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    __builtin_amdgcn_s_barrier();                      \
-    asm volatile("" ::: "memory");                     \
-  } while (0)
-#endif
 }  // namespace
 
 // NR1 / NR2 / NR3: 32-row MFMA tiles a wave processes in P1 (halo rows) / P2 / P3 (patch positions); XR = NR1 * 64 halo rows.
@@ -108,8 +59,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
   constexpr int TAB = STG + 4 * 4096;               // y byte offset of every patch position, [row tile][row & 7][(row >> 3) & 3] (512 B)
   constexpr int NST = NR3 * 4;                     // stores per lane and tile (16 bytes each: whole 128-byte lines per 8 lanes)
   typedef bf16_t T;
-  typedef int i32x8 __attribute__((ext_vector_type(8)));
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));  // ext_vector LDS accesses: hipcc adds no vmcnt(0) for them beside LDS-DMA
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -122,7 +71,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
   float* const bn = reinterpret_cast<float*>(smem + BNO);
   const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)smem;
   const unsigned stg = smem_lds + STG + wave * 4096;
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
   // ---- weights -> registers (plain loads, before any LDS-DMA exists) -------------------------------------------------------
   const int ct1 = wave >> 1;  // P1 / P2: this wave's 32 mid channels
@@ -157,7 +105,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
       s3r[j][gq] = *reinterpret_cast<const f32x4*>(a.s3 + 64 * wave + 32 * j + 8 * gq + 4 * lh);
       b3r[j][gq] = *reinterpret_cast<const f32x4*>(a.b3 + 64 * wave + 32 * j + 8 * gq + 4 * lh);
     }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
 
   // persistent tile walk: blocks of one XCD (blockIdx & 7) take neighbouring patches at the same time
   const int G = gridDim.x, xcd = blockIdx.x & 7, jb = blockIdx.x >> 3, gx = (G + 7) >> 3;
@@ -195,7 +143,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
   i32x8 td = load_tile(t < a.n_tiles ? t : 0);
   if (t < a.n_tiles) issue_x(td, xb);
   const int rb1 = (wave & 1) * NR1, rb2 = (wave & 1) * NR2;  // first row tile of this wave in P1 (3 tiles) / P2 (2 tiles)
-  typedef short s16x2 __attribute__((ext_vector_type(2)));
   // bf16 pair: ReLU as a packed signed-16-bit max with 0 (sign bit set <=> negative), then AND with a keep mask
   auto relu_pk = [](unsigned u, unsigned keep) {
     const s16x2 z = {0, 0};
@@ -203,21 +150,13 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
     return __builtin_bit_cast(unsigned, r) & keep;
   };
   auto pack2 = [](float lo, float hi) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
     bf16x2 v;
     v[0] = (bf16_t)lo;
     v[1] = (bf16_t)hi;
     return __builtin_bit_cast(unsigned, v);
   };
 
-#ifdef BK_TIMING
-  unsigned long long ts[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
   for (int it = 0; t < a.n_tiles; ++it) {
-#ifdef BK_TIMING
-    if (it == 11) ts[11] = __builtin_readcyclecounter();
-#endif
-    BK_STAMP(0);
     const int row0 = td[0], IH = td[1], IW = td[2], oy0 = td[3] >> 16, ox0 = td[3] & 0xffff;
     char* const yimg = reinterpret_cast<char*>(y) + (size_t)(unsigned)row0 * (size_t)(C * 2);  // this image's first output row (wave-uniform)
     const int PW = td[5], HW2 = PW + 2, HR = (td[4] + 2) * HW2, NPOS = td[4] * PW;
@@ -228,10 +167,9 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
     // this tile's halo has landed.  The counter retires in issue order and every lane issues exactly 32 stores per tile AFTER
     // the halo loads of the next one (lanes without a valid position write to a private trash slot instead of being masked
     // off), so vmcnt(32) leaves the previous tile's stores -- and their ~2 us of write acknowledgement -- in flight
-    if (it == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST) : "memory");
-    BK_BAR();  // ... for every wave; t1 / t2 of the previous tile are free
-    BK_STAMP(1);
+    if (it == 0) wait_vmcnt<0>();
+    else wait_vmcnt<NST>();
+    lds_barrier();  // ... for every wave; t1 / t2 of the previous tile are free
     // y byte offset of patch position m (0xffffffff: no such pixel -> the store goes to the trash slot), for the transposed stores of
     // P3: entry [m >> 5][m & 7][(m >> 3) & 3], so that a lane reads the four rows it stores of a row tile with one ds_read_b128.
     // (The previous patch's P3 is over for every wave -- barrier above; the next reader is this patch's P3, three barriers on.)
@@ -252,7 +190,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
     // ===== P1: t1 = relu(bn1(x_halo . W1^T)), row tiles rb1 .. rb1+2, channels ct1 ===========================================
     // (lz*: zero, opaque to the compiler and re-made per tile and phase: LDS addresses would otherwise be hoisted out of the tile
     //  loop as ~150 loop-invariant VGPRs, leaving no registers to pipeline the fragment reads)
-    if (BK_ONLY == 0 || BK_ONLY == 1) {
+    {
       int lz1;
       asm volatile("v_mov_b32 %0, 0" : "=v"(lz1));
       const int l31a = l31 + lz1;
@@ -270,13 +208,8 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
         for (int i = 0; i < NR1; ++i) af[ks][i] = *reinterpret_cast<const bf16x8*>(ap + i * 16384);
       }
       __builtin_amdgcn_sched_group_barrier(0x100, NR1 * (D1 - 1), 0);
-#ifdef BK_NOP1
-      constexpr int K1 = 4;
-#else
-      constexpr int K1 = 16;
-#endif
 #pragma unroll
-      for (int ks = 0; ks < K1; ++ks) {
+      for (int ks = 0; ks < 16; ++ks) {
         if (ks + D1 - 1 < 16) {
           const char* ap = abase + (((ks + D1 - 1) * 32) ^ akey);
 #pragma unroll
@@ -284,13 +217,12 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
         }
 #pragma unroll
         for (int i = 0; i < NR1; ++i) {
-          if (ks == 0) BK_MFMA0(acc1[i], W1f[ks], af[ks % D1][i]);
-          else BK_MFMA(acc1[i], W1f[ks], af[ks % D1][i]);
+          if (ks == 0) mfma_aw0(acc1[i], W1f[ks], af[ks % D1][i]);
+          else mfma_aw(acc1[i], W1f[ks], af[ks % D1][i]);
         }
       }
-      if constexpr (NR1 == 3) BK_MFMA_DRAIN3(acc1[0], acc1[1], acc1[2]);
-      else BK_MFMA_DRAIN2(acc1[0], acc1[1]);
-      BK_STAMP(2);
+      if constexpr (NR1 == 3) mfma_drain(acc1[0], acc1[1], acc1[2]);
+      else mfma_drain(acc1[0], acc1[1]);
       const float* sp = s1 + ct1 * 32 + 4 * lh;  // b1 = s1 + 64
 #pragma unroll
       for (int i = 0; i < NR1; ++i) {
@@ -309,7 +241,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
         }
       }
     }
-    BK_STAMP(3);
     // residual values of this lane's conv3 outputs (positions rt * 32 + l31, channels 64 wave + 32 j + 8 gq + 4 lh ..): halo -> registers
     u32x2 res[NR3 * 8];
     int lzr;
@@ -334,18 +265,13 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
       asm volatile(""
                    : "+v"(res[16]), "+v"(res[17]), "+v"(res[18]), "+v"(res[19]), "+v"(res[20]), "+v"(res[21]), "+v"(res[22]), "+v"(res[23]),
                      "+v"(res[24]), "+v"(res[25]), "+v"(res[26]), "+v"(res[27]), "+v"(res[28]), "+v"(res[29]), "+v"(res[30]), "+v"(res[31]));
-    BK_STAMP(4);
-    BK_BAR();  // t1 complete; every wave is done with the x halo
-    BK_STAMP(5);
-#ifndef BK_NOX
+    lds_barrier();  // t1 complete; every wave is done with the x halo
     if (!DB && t_next < a.n_tiles) issue_x(td_next, xb);
-#endif
-    BK_STAMP(6);
 
     // ===== P2: t2 = relu(bn2(conv3x3(t1))), row tiles rb2, rb2+1, channels ct1 ===============================================
     // t1 / t2 rows are PADDED to 144 B (they are written by ds_write, not by DMA): conflict-free without a swizzle, so the
     // k-step and tile offsets of every read are instruction immediates (one VALU add per tap and tile instead of per read)
-    if (BK_ONLY == 0 || BK_ONLY == 2) {
+    {
       int lz2;
       asm volatile("v_mov_b32 %0, 0" : "=v"(lz2));
       const int l31b = l31 + lz2;
@@ -375,13 +301,8 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
       };
 #pragma unroll
       for (int k = 0; k < D2 - 1; ++k) p2_read(k);
-#ifdef BK_NOP2
-      constexpr int K2 = 8;
-#else
-      constexpr int K2 = 36;
-#endif
 #pragma unroll
-      for (int k = 0; k < K2; ++k) {
+      for (int k = 0; k < 36; ++k) {
         if (k + D2 - 1 < 36) p2_read(k + D2 - 1);
         // reads issued after those of k-step k: NR2 per k-step still ahead
         const int ahead = (k + D2 - 1 < 36 ? D2 - 1 : 35 - k) * NR2;
@@ -398,15 +319,13 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
         }
 #pragma unroll
         for (int i = 0; i < NR2; ++i) {
-          if (k == 0) BK_MFMA0(acc2[i], W2f[k], af[k % D2][i]);
-          else BK_MFMA(acc2[i], W2f[k], af[k % D2][i]);
+          if (k == 0) mfma_aw0(acc2[i], W2f[k], af[k % D2][i]);
+          else mfma_aw(acc2[i], W2f[k], af[k % D2][i]);
         }
       }
-      if constexpr (NR2 == 2) BK_MFMA_DRAIN2(acc2[0], acc2[1]);
+      if constexpr (NR2 == 2) mfma_drain(acc2[0], acc2[1]);
       else asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc2[0])::"memory");
-      BK_STAMP(7);
-      BK_BAR();  // every wave has finished reading t1: t2 may overwrite it
-      BK_STAMP(8);
+      lds_barrier();  // every wave has finished reading t1: t2 may overwrite it
       const float* sp = s2 + ct1 * 32 + 4 * lh;  // b2 = s2 + 64
 #pragma unroll
       for (int i = 0; i < NR2; ++i) {
@@ -421,15 +340,13 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
         }
       }
     }
-    BK_STAMP(9);
-    BK_BAR();  // t2 complete
-    BK_STAMP(10);
+    lds_barrier();  // t2 complete
 
     // ===== P3: y = relu(bn3(t2 . W3^T) + x), all four row tiles, channels 64 wave .. 64 wave + 63 ==========================
     // Software pipelined over the row tiles: the 8 MFMAs of tile rt + 1 are issued one per epilogue chunk of tile rt (k-step
     // outer, channel tile inner, so the two dependent chains alternate).  Back to back they would stall the wave's in-order
     // issue for ~8 x 40 cycles per tile and then leave the matrix pipe idle during ~600 cycles of epilogue VALU work.
-    if (BK_ONLY == 0 || BK_ONLY == 3) {
+    {
       int lz3;
       asm volatile("v_mov_b32 %0, 0" : "=v"(lz3));
       const char* pbase = t1 + (l31 + lz3) * TP + 16 * lh;
@@ -443,13 +360,13 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
       for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          if (ks == 0) BK_MFMA0(acc3[0][j], W3f[j][0], av[0][0]);
-          else BK_MFMA(acc3[0][j], W3f[j][ks], av[0][ks]);
+          if (ks == 0) mfma_aw0(acc3[0][j], W3f[j][0], av[0][0]);
+          else mfma_aw(acc3[0][j], W3f[j][ks], av[0][ks]);
         }
 #pragma unroll
       for (int rt = 0; rt < NR3; ++rt) {
         const int cb = rt & 1, nb = cb ^ 1;
-        BK_MFMA_DRAIN2(acc3[cb][0], acc3[cb][1]);
+        mfma_drain(acc3[cb][0], acc3[cb][1]);
         if (rt + 2 < NR3) {  // fragments of tile rt + 2 into the buffer tile rt has just finished with
 #pragma unroll
           for (int ks = 0; ks < 4; ++ks) av[cb][ks] = *reinterpret_cast<const bf16x8*>(pbase + (rt + 2) * 32 * TP + ks * 32);
@@ -459,21 +376,16 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
           const int j = c >> 2, gq = c & 3;
           if (rt < NR3 - 1) {
             const int ks2 = c >> 1, j2 = c & 1;
-            if (ks2 == 0) BK_MFMA0(acc3[nb][j2], W3f[j2][0], av[nb][0]);
-            else BK_MFMA(acc3[nb][j2], W3f[j2][ks2], av[nb][ks2]);
+            if (ks2 == 0) mfma_aw0(acc3[nb][j2], W3f[j2][0], av[nb][0]);
+            else mfma_aw(acc3[nb][j2], W3f[j2][ks2], av[nb][ks2]);
           }
           const f32x4 sv = s3r[j][gq], bv = b3r[j][gq];
           const u32x2 rv = res[rt * 8 + j * 4 + gq];
           u32x2 o;
-#ifdef BK_NOE3
-          o[0] = pack2(acc3[cb][j][4 * gq] + sv[0] + bv[0] + __uint_as_float(rv[0]), acc3[cb][j][4 * gq + 1]);
-          o[1] = pack2(acc3[cb][j][4 * gq + 2], acc3[cb][j][4 * gq + 3] + __uint_as_float(rv[1]));
-#else
           o[0] = relu_pk(pack2(acc3[cb][j][4 * gq] * sv[0] + bv[0] + __uint_as_float(rv[0] << 16),
                                acc3[cb][j][4 * gq + 1] * sv[1] + bv[1] + __uint_as_float(rv[0] & 0xffff0000u)), 0xffffffffu);
           o[1] = relu_pk(pack2(acc3[cb][j][4 * gq + 2] * sv[2] + bv[2] + __uint_as_float(rv[1] << 16),
                                acc3[cb][j][4 * gq + 3] * sv[3] + bv[3] + __uint_as_float(rv[1] & 0xffff0000u)), 0xffffffffu);
-#endif
           // into the wave's staging tile: row l31, 16-byte piece p = 4 j + gq (this lane holds half lh of it)
           asm volatile("ds_write_b64 %0, %1" ::"v"(stg + l31 * 128 + (((c ^ (l31 & 7))) << 4) + lh * 8), "v"(o) : "memory");
         }
@@ -491,11 +403,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           char* dst = yo[q] != 0xffffffffu ? yimg + ((size_t)yo[q] + 128 * wave + (lane & 7) * 16) : trash;
-#ifdef BK_NOSTORE
-          if (ov[q][0] == 0x12345678u) *reinterpret_cast<u32x4*>(dst) = ov[q];
-#else
           *reinterpret_cast<u32x4*>(dst) = ov[q];
-#endif
         }
       }
     }
@@ -503,12 +411,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
     td = td_next;
     if (DB) xb = xb == smem ? smem + XBB : smem;
   }
-#ifdef BK_TIMING
-  if (blockIdx.x == 8 && lane == 0)
-    printf("wave %d: wait+bar %llu | P1 K %llu  epi %llu  res copy %llu  bar %llu | issue_x %llu  P2 K %llu  bar %llu  epi %llu  bar %llu | P3 %llu | total %llu\n", wave,
-           ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2], ts[4] - ts[3], ts[5] - ts[4], ts[6] - ts[5], ts[7] - ts[6], ts[8] - ts[7], ts[9] - ts[8],
-           ts[10] - ts[9], ts[11] - ts[10], ts[11] - ts[0]);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -529,9 +431,6 @@ constexpr int PLDS_BYTES = PTAB_OFF + 512;
 
 __global__ __launch_bounds__(256, 1) void bottleneck64p_kernel(const BottleneckArgs a) {
   typedef bf16_t T;
-  typedef int i32x8 __attribute__((ext_vector_type(8)));
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  typedef short s16x2 __attribute__((ext_vector_type(2)));
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -543,7 +442,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck64p_kernel(const BottleneckA
   float* const bn = reinterpret_cast<float*>(smem + PBN_OFF);
   const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)smem;
   const unsigned stg = smem_lds + PSTG_OFF + wave * 4096;
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
   const int ct1 = wave >> 1;
   bf16x8 W1f[4], W2f[36], W3f[2][8];
@@ -571,7 +469,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck64p_kernel(const BottleneckA
   for (int j = 0; j < 2; ++j)
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) b3r[j][gq] = *reinterpret_cast<const f32x4*>(a.b3 + 64 * wave + 32 * j + 8 * gq + 4 * lh);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
 
   const int G = gridDim.x, xcd = blockIdx.x & 7, jb = blockIdx.x >> 3, gx = (G + 7) >> 3;
   const int chunk = (a.n_tiles + 7) >> 3;
@@ -603,7 +501,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck64p_kernel(const BottleneckA
     return __builtin_bit_cast(unsigned, r) & keep;
   };
   auto pack2 = [](float lo, float hi) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
     bf16x2 v;
     v[0] = (bf16_t)lo;
     v[1] = (bf16_t)hi;
@@ -625,9 +522,9 @@ __global__ __launch_bounds__(256, 1) void bottleneck64p_kernel(const BottleneckA
     char* const xb = smem + (it & 1) * PX_BYTES;
 
     // this tile's halo (issued a whole tile ago, before the previous tile's 32 stores) has landed
-    if (it == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");  // (16 whole-line stores per lane and tile)
-    BK_BAR();  // ... for every wave; the other halo buffer and t1 / t2 of the previous tile are free
+    if (it == 0) wait_vmcnt<0>();
+    else wait_vmcnt<16>();  // (16 whole-line stores per lane and tile)
+    lds_barrier();  // ... for every wave; the other halo buffer and t1 / t2 of the previous tile are free
     if (t_next < a.n_tiles) issue_x(td_next, (it & 1) ^ 1);
     // y byte offset of patch position m (0xffffffff: no such pixel), entry [m >> 5][m & 7][(m >> 3) & 3] (see bottleneck64_kernel)
     if (tid < 128) {
@@ -657,10 +554,10 @@ __global__ __launch_bounds__(256, 1) void bottleneck64p_kernel(const BottleneckA
       for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-          if (ks == 0) BK_MFMA0(acc1[i], W1f[ks], af[ks][i]);
-          else BK_MFMA(acc1[i], W1f[ks], af[ks][i]);
+          if (ks == 0) mfma_aw0(acc1[i], W1f[ks], af[ks][i]);
+          else mfma_aw(acc1[i], W1f[ks], af[ks][i]);
         }
-      BK_MFMA_DRAIN3(acc1[0], acc1[1], acc1[2]);
+      mfma_drain(acc1[0], acc1[1], acc1[2]);
       const float* sp = s1 + ct1 * 32 + 4 * lh;
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
@@ -690,7 +587,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck64p_kernel(const BottleneckA
       const int hc = min((my + 1) * HW2 + mx + 1, XROWS - 1);
       xoff[rt] = hc * 128 + (((((hc >> 1) & 7)) ^ lh) << 4);  // chunk pair ks' of this row sits at xoff ^ (ks' * 32)
     }
-    BK_BAR();  // t1 complete
+    lds_barrier();  // t1 complete
 
     // ===== P2: t2 = relu(bn2(conv3x3(t1))) ==================================================================================
     {
@@ -723,13 +620,8 @@ __global__ __launch_bounds__(256, 1) void bottleneck64p_kernel(const BottleneckA
       };
 #pragma unroll
       for (int k = 0; k < D2 - 1; ++k) p2_read(k);
-#ifdef BK_NOP2
-      constexpr int K2 = 8;
-#else
-      constexpr int K2 = 36;
-#endif
 #pragma unroll
-      for (int k = 0; k < K2; ++k) {
+      for (int k = 0; k < 36; ++k) {
         if (k + D2 - 1 < 36) p2_read(k + D2 - 1);
         // reads issued after those of k-step k: two per k-step still ahead
         const int ahead = (k + D2 - 1 < 36 ? D2 - 1 : 35 - k) * 2;
@@ -739,12 +631,12 @@ __global__ __launch_bounds__(256, 1) void bottleneck64p_kernel(const BottleneckA
         else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[k % D2][0]), "+v"(af[k % D2][1]));
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-          if (k == 0) BK_MFMA0(acc2[i], W2f[k], af[k % D2][i]);
-          else BK_MFMA(acc2[i], W2f[k], af[k % D2][i]);
+          if (k == 0) mfma_aw0(acc2[i], W2f[k], af[k % D2][i]);
+          else mfma_aw(acc2[i], W2f[k], af[k % D2][i]);
         }
       }
-      BK_MFMA_DRAIN2(acc2[0], acc2[1]);
-      BK_BAR();  // every wave has finished reading t1: t2 may overwrite it
+      mfma_drain(acc2[0], acc2[1]);
+      lds_barrier();  // every wave has finished reading t1: t2 may overwrite it
       const float* sp = s2 + ct1 * 32 + 4 * lh;
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
@@ -759,7 +651,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck64p_kernel(const BottleneckA
         }
       }
     }
-    BK_BAR();  // t2 complete
+    lds_barrier();  // t2 complete
 
     // ===== P3: y = relu([t2 | x] . [W3 | Wsc]^T + shift), software pipelined over the row tiles like the identity block ======
     {
@@ -781,20 +673,20 @@ __global__ __launch_bounds__(256, 1) void bottleneck64p_kernel(const BottleneckA
       for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          if (ks == 0) BK_MFMA0(acc3[0][j], W3f[j][0], av[0][0]);
-          else BK_MFMA(acc3[0][j], W3f[j][ks], av[0][ks]);
+          if (ks == 0) mfma_aw0(acc3[0][j], W3f[j][0], av[0][0]);
+          else mfma_aw(acc3[0][j], W3f[j][ks], av[0][ks]);
         }
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt) {
         const int cb = rt & 1, nb = cb ^ 1;
-        BK_MFMA_DRAIN2(acc3[cb][0], acc3[cb][1]);
+        mfma_drain(acc3[cb][0], acc3[cb][1]);
         if (rt + 2 < 4) load_av(cb, rt + 2);
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
           const int j = c >> 2, gq = c & 3;
           if (rt < 3) {  // two of tile rt + 1's sixteen MFMAs per epilogue chunk: k-step c, both channel tiles
-            if (c == 0) { BK_MFMA0(acc3[nb][0], W3f[0][0], av[nb][0]); BK_MFMA0(acc3[nb][1], W3f[1][0], av[nb][0]); }
-            else { BK_MFMA(acc3[nb][0], W3f[0][c], av[nb][c]); BK_MFMA(acc3[nb][1], W3f[1][c], av[nb][c]); }
+            if (c == 0) { mfma_aw0(acc3[nb][0], W3f[0][0], av[nb][0]); mfma_aw0(acc3[nb][1], W3f[1][0], av[nb][0]); }
+            else { mfma_aw(acc3[nb][0], W3f[0][c], av[nb][c]); mfma_aw(acc3[nb][1], W3f[1][c], av[nb][c]); }
           }
           const f32x4 bv = b3r[j][gq];
           u32x2 o;

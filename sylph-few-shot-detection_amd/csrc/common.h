@@ -9,15 +9,6 @@
 
 #include <atomic>
 
-// A/B knobs of variants that were measured and rejected exist only in builds made with -DSYLPH_ABLATE
-// (tools/build_variant.sh): the product library reads no environment for them and carries no instantiation of them.
-#ifdef SYLPH_ABLATE
-#include <stdlib.h>
-#define SYLPH_AB_ENV(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))
-#else
-#define SYLPH_AB_ENV(name, dflt) (dflt)
-#endif
-
 namespace sylph {
 
 typedef __bf16 bf16_t;
@@ -132,14 +123,6 @@ template <> __device__ __forceinline__ void store8<bf16_t>(bf16_t* p, const floa
 #pragma unroll
   for (int i = 0; i < 8; ++i) o[i] = (bf16_t)v[i];
   *reinterpret_cast<bf16x8*>(p) = o;
-}
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt, i.e. waits for every global
-// store (and prefetch load) still in flight: ~1-2 us per barrier in an epilogue that has just issued its stores.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 // Per-device launch set-up of the persistent kernels (function-local statics took the CU count and the LDS attribute from

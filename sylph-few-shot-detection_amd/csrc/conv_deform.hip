@@ -29,7 +29,7 @@
 // slice k + 1 before the MFMAs of slice k (two LDS stages, 96 KiB, one barrier per slice), so the gather's L2 round trip runs
 // under the MFMAs.  The per-tap sample table (neighbour offsets, weights, mask) lives in registers; the next tap's three om
 // values per row are fetched one tap ahead.
-#include "common.h"
+#include "gfx950.h"
 #include "igemm_mma.h"
 #include "kernels.h"
 
@@ -37,8 +37,6 @@ namespace sylph {
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
 constexpr int DBM = 128, DBN = 256, DNT = 256;  // tile rows, output channels, threads
 constexpr int DSTAGE = (DBM + DBN) * 128;       // one LDS stage: A rows then weight rows, 128 B each
@@ -199,7 +197,7 @@ __global__ __launch_bounds__(DNT, 1) void conv_deform_kernel(const DeformArgs a)
   fetch_om(1);
   issue_w(0, 0);
   load_a(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   write_a(0);
   __syncthreads();
   for (int kt = 0; kt < NK; ++kt) {
@@ -215,7 +213,7 @@ __global__ __launch_bounds__(DNT, 1) void conv_deform_kernel(const DeformArgs a)
     }
     compute(buf);
     if (nk < NK) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       write_a(buf ^ 1);
     }
     __syncthreads();

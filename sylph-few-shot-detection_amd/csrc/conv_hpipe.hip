@@ -58,24 +58,9 @@
 //
 // Scope (launch_conv checks): bf16 in/out, 3x3 s1 p1, no residual, no per-segment Scale, ReLU on all channels or none,
 // Cout % 256 == 0, Cin % 32 == 0, padded scale/shift; optional fused GroupNorm partial statistics (one per patch).
-#include <stdlib.h>
-
-#include "common.h"
-
-// Ablation switches (measurement aids: HP_NOWAITV, HP_NOLDS, HP_NOLOAD, HP_NOEPI) exist ONLY in builds made with -DSYLPH_ABLATE
-// (tools/build_variant.sh -> lib/variants/): the product library is compiled without it and every switch is forced off here.
-#ifndef SYLPH_ABLATE
-#undef HP_NOWAITV
-#undef HP_NOLDS
-#undef HP_NOLOAD
-#undef HP_NOEPI
-#undef HP_TIMING
-#endif
+#include "gfx950.h"
 
 namespace sylph {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
 namespace {
 constexpr int PNT = 512;
@@ -94,21 +79,6 @@ static_assert(64 * SCP * 4 <= LDS_BYTES, "epilogue tile must fit");
 constexpr int NPIECE = 2 * HPROWS / 128;  // block-wide halo loads per half-slice (taps 0..3 carry one each)
 constexpr int nload(int t) { return ((t % 9 + 9) % 9) < NPIECE ? 3 : 2; }
 
-#define HP_SCHED_FENCE __builtin_amdgcn_sched_barrier(0)
-#define HP_BAR()                                   \
-  do {                                             \
-    asm volatile("" ::: "memory");                 \
-    HP_SCHED_FENCE;                                \
-    __builtin_amdgcn_s_barrier();                  \
-    HP_SCHED_FENCE;                                \
-    asm volatile("" ::: "memory");                 \
-  } while (0)
-#ifdef HP_NOWAITV
-#define HP_WAITV(N) asm volatile("" ::: "memory")
-#else
-#define HP_WAITV(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
-#endif
-#define HP_WAITL() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 }  // namespace
 
 template <bool GNIN>
@@ -124,10 +94,6 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
   const int nt = q0 - m_local * a.n_ntiles;
   const int mt = xcd * chunk + m_local;
   if (m_local >= chunk || mt >= a.n_mtiles) return;
-#ifdef HP_TIMING  // (SYLPH_ABLATE builds) s_memtime stamps of a block's prologue / K loop / epilogue, printed by 64 blocks of a launch
-  const unsigned long long hp_t0 = __builtin_readcyclecounter();
-  unsigned long long hp_t1 = 0, hp_t2 = 0;
-#endif
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -176,13 +142,9 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
   // bytes [tid * 16, +16) of each 8-KiB half: wave-uniform base (SALU) + a constant per-lane offset
   const char* const wtile = reinterpret_cast<const char*>(wt) + (size_t)nt * ncc * 9 * BSTAGE;
   const unsigned wvo = (unsigned)tid * 16u;
-  bool loads_on = true;  // ablation builds (HP_NOLOAD) switch the main-loop loads off after a prologue that fills every stage
   auto issue_halo = [&](int g, int buf) {  // piece g of the half-slice the running pointers stand on -> halo buffer buf
-    if (!loads_on) return;
-    {
     char* d = smem + HALO_OFF + buf * HBUF + g * 8192 + wave * 1024;  // wave-uniform; lane l lands at +16 l
     __builtin_amdgcn_global_load_lds((gbl_ptr_t)hptr[g], (lds_ptr_t)d, 16, 0, 0);
-    }
   };
   // step the halo pointers to the next half-slice of the rotated walk (wrap: back by Cin - 32 channels)
   auto advance_halo = [&](int cc_next) {
@@ -190,13 +152,14 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
 #pragma unroll
     for (int g = 0; g < NPIECE; ++g) hptr[g] += ((hmask >> g) & 1u) ? step : 0;
   };
+  // Always true.  The guard folds away, yet without it hipcc moves the weight loads' address arithmetic through the K loop
+  // from VALU to SALU: a schedule change to be measured on its own, not part of the refactor that removed its other uses.
+  bool w_loads = true;
   auto issue_w = [&](int stage, int j, int blk) {  // 8-KiB half j of weight block blk (= rotated half-slice * 9 + tap)
-    if (!loads_on) return;
-    {
+    if (!w_loads) return;
     char* d = smem + stage * BSTAGE + j * 8192 + wave * 1024;
     const char* src = wtile + (size_t)blk * BSTAGE + j * 8192 + wvo;
     __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)d, 16, 0, 0);
-    }
   };
   auto rot = [&](int cc) { const int c = c0 + cc; return c >= ncc ? c - ncc : c; };
 
@@ -212,11 +175,9 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
   // LDS-DMA still in flight aliases the read), which would drain the whole load pipeline in 4 of 9 phases.  The data read
   // here was fetched by THIS lane and retired by this wave's counted vmcnt two phases ago; the lgkmcnt wait is tied to the
   // loaded registers ("+v") so that no consumer can be scheduled above it.
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  typedef float f32x4v __attribute__((ext_vector_type(4)));
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
   u32x4 gx;
-  f32x4v gc0, gc1, gc2, gc3;  // (a, b) pairs of channels (0,1) (2,3) (4,5) (6,7)
+  f32x4 gc0, gc1, gc2, gc3;  // (a, b) pairs of channels (0,1) (2,3) (4,5) (6,7)
   auto gn_addr = [&](int g, int cc_of_piece) { return lds0 + HALO_OFF + (cc_of_piece & 1) * HBUF + g * 8192 + tid * 16; };
   auto gn_read = [&](int g, int cc_of_piece) {  // issue the five LDS reads of piece g (no wait)
     const unsigned d = gn_addr(g, cc_of_piece);
@@ -231,19 +192,16 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
   auto gn_finish = [&](int g, int cc_of_piece) {  // wait for them, transform, write back (branch-free: no cut in the MFMA stream)
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(gx), "+v"(gc0), "+v"(gc1), "+v"(gc2), "+v"(gc3));
     const unsigned live = ((hmask >> g) & 1u) ? 0xffffffffu : 0u;  // zero-page lanes (conv padding) keep their zeros
-    const f32x4v cs[4] = {gc0, gc1, gc2, gc3};                      // per channel pair: (a_lo, a_hi, b_lo, b_hi)
-    typedef float f32x2v __attribute__((ext_vector_type(2)));
-    typedef short s16x2v __attribute__((ext_vector_type(2)));
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+    const f32x4 cs[4] = {gc0, gc1, gc2, gc3};                      // per channel pair: (a_lo, a_hi, b_lo, b_hi)
     u32x4 y;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const f32x2v xv = {__uint_as_float(gx[e] << 16), __uint_as_float(gx[e] & 0xffff0000u)};
-      const f32x2v av = {cs[e][0], cs[e][1]}, bv = {cs[e][2], cs[e][3]};
-      const f32x2v r = __builtin_elementwise_fma(xv, av, bv);
+      const f32x2 xv = {__uint_as_float(gx[e] << 16), __uint_as_float(gx[e] & 0xffff0000u)};
+      const f32x2 av = {cs[e][0], cs[e][1]}, bv = {cs[e][2], cs[e][3]};
+      const f32x2 r = __builtin_elementwise_fma(xv, av, bv);
       const bf16x2 pk = __builtin_convertvector(r, bf16x2);  // one v_cvt_pk_bf16_f32 (round to nearest even, as the casts)
-      const s16x2v fl = {gn_floor, gn_floor};
-      const unsigned u = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2v, pk), fl));
+      const s16x2 fl = {gn_floor, gn_floor};
+      const unsigned u = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pk), fl));
       y[e] = u & live;
     }
     asm volatile("ds_write_b128 %0, %1" ::"v"(gn_addr(g, cc_of_piece)), "v"(y) : "memory");
@@ -282,9 +240,6 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
     int key = l15;
     asm volatile("" : "+v"(key));
     const int so = (lq ^ ((((key + kh * PWm + kw) >> 2) & 1) << 1)) << 4;
-#ifdef HP_NOLDS
-    if (cc + t > 0) return;
-#endif
 #pragma unroll
     for (int j = 0; j < 4; ++j) fb[j] = *reinterpret_cast<const bf16x8*>(bs + offB + j * 1024);
 #pragma unroll
@@ -316,7 +271,7 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
     const bool xf = gn_in && t >= 3 && t < 3 + NPIECE;
     if (xf) {  // the five LDS reads go out first; their latency hides behind the first eight MFMAs
       gn_read(t - 3, cc + 1);
-      HP_SCHED_FENCE;
+      sched_fence();
     }
     int n = 0;
 #pragma unroll
@@ -325,7 +280,7 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
       for (int j = 0; j < 4; ++j) {
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);  // D^T
         if (xf && n == 7) {
-          HP_SCHED_FENCE;
+          sched_fence();
           gn_finish(t - 3, cc + 1);  // ~30 VALU + one LDS write, spread between the following MFMAs
         }
         ++n;
@@ -356,12 +311,6 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
     issue_w(t, 0, c0 * 9 + t);
     issue_w(t, 1, c0 * 9 + t);
   }
-#ifdef HP_NOLOAD
-  issue_w(3, 0, c0 * 9 + 3); issue_w(3, 1, c0 * 9 + 3);
-  for (int g = 0; g < NPIECE; ++g) issue_halo(g, 1);
-  HP_WAITV(0);
-  loads_on = false;
-#endif
   if (gn_in) {  // (a, b) of both patches' segments -> LDS (plain loads: issued after the DMA queue, waited below)
     // stored per channel PAIR as (a0, a1, b0, b1): the transform is then one packed FMA per bf16 pair
     for (int idx = tid; idx < Cin; idx += PNT) {
@@ -371,58 +320,52 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
       *reinterpret_cast<float4*>(smem + COEF_OFF + (pch * Cin + ch) * 8) = make_float4(c0v.x, c1v.x, c0v.y, c1v.y);
     }
   }
-  HP_WAITV(4);  // halo + phase 0 landed (phases 1, 2 in flight)
+  wait_vmcnt<4>();  // halo + phase 0 landed (phases 1, 2 in flight)
   if (gn_in) {
-    HP_WAITL();
-    HP_BAR();   // the coefficient table is complete for every wave
+    wait_lgkmcnt0();
+    fenced_barrier();  // the coefficient table is complete for every wave
 #pragma unroll
     for (int g = 0; g < NPIECE; ++g) gn_piece(g, 0);
-    HP_WAITL();
+    wait_lgkmcnt0();
   }
-  HP_BAR();     // B_0
-#ifdef HP_TIMING
-  hp_t1 = __builtin_readcyclecounter();
-#endif
+  fenced_barrier();  // B_0
 
   // vmcnt immediates: a wave needs its loads of phase q+1 (issued in L(q-2)) landed before B_{2q+2}; the loads issued after
   // them are the groups of L(q-1) and L(q).  Row 0 waits at the end of M(q) (seg 2q+1), row 1 at the end of L(q) (seg 2q+1).
-#define HP_PHASE0(t)                      \
-  ldfrag(cc, t);                          \
-  HP_SCHED_FENCE;                         \
-  issue_next(cc, t);                      \
-  HP_WAITL();                             \
-  if (GNIN) frags_ready();                \
-  HP_BAR();                               \
-  mma(cc, t);                             \
-  HP_WAITV(nload((t) - 1) + nload(t));    \
-  HP_BAR();
-#define HP_PHASE1(t)                      \
-  ldfrag(cc, t);                          \
-  HP_SCHED_FENCE;                         \
-  issue_next(cc, t);                      \
-  HP_WAITV(nload((t) - 1) + nload(t));    \
-  HP_WAITL();                             \
-  if (GNIN) frags_ready();                \
-  HP_BAR();                               \
-  mma(cc, t);                             \
-  HP_BAR();
+#define HP_PHASE0(t)                       \
+  ldfrag(cc, t);                           \
+  sched_fence();                           \
+  issue_next(cc, t);                       \
+  wait_lgkmcnt0();                         \
+  if (GNIN) frags_ready();                 \
+  fenced_barrier();                        \
+  mma(cc, t);                              \
+  wait_vmcnt<nload((t) - 1) + nload(t)>(); \
+  fenced_barrier();
+#define HP_PHASE1(t)                       \
+  ldfrag(cc, t);                           \
+  sched_fence();                           \
+  issue_next(cc, t);                       \
+  wait_vmcnt<nload((t) - 1) + nload(t)>(); \
+  wait_lgkmcnt0();                         \
+  if (GNIN) frags_ready();                 \
+  fenced_barrier();                        \
+  mma(cc, t);                              \
+  fenced_barrier();
 
   if (wm == 0) {
     for (int cc = 0; cc < ncc; ++cc) {
       HP_PHASE0(0) HP_PHASE0(1) HP_PHASE0(2) HP_PHASE0(3) HP_PHASE0(4) HP_PHASE0(5) HP_PHASE0(6) HP_PHASE0(7) HP_PHASE0(8)
     }
-    HP_BAR();
+    fenced_barrier();
   } else {
-    HP_BAR();  // the stagger
+    fenced_barrier();  // the stagger
     for (int cc = 0; cc < ncc; ++cc) {
       HP_PHASE1(0) HP_PHASE1(1) HP_PHASE1(2) HP_PHASE1(3) HP_PHASE1(4) HP_PHASE1(5) HP_PHASE1(6) HP_PHASE1(7) HP_PHASE1(8)
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the zero-page tail loads must not land in the epilogue tile
+  wait_vmcnt<0>();  // the zero-page tail loads must not land in the epilogue tile
   __syncthreads();
-#ifdef HP_TIMING
-  hp_t2 = __builtin_readcyclecounter();
-#endif
 
   // ---- fused epilogue: per patch two 64-row passes through an fp32 LDS tile ---------------------------------------
   float* const sC = reinterpret_cast<float*>(smem);
@@ -484,11 +427,7 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
             for (int e = 0; e < 8; ++e) { const float d = v[e] - gn_pv; gn_s1 += d; gn_s2 = fmaf(d, d, gn_s2); }
             gn_n += 8.f;
           }
-#ifndef HP_NOEPI
           store8<bf16_t>(outn + (size_t)(oy * sp.out_W + ox) * a.out_ld, v);
-#else
-          if (v[0] == 1234.5f) store8<bf16_t>(outn + (size_t)(oy * sp.out_W + ox) * a.out_ld, v);
-#endif
         }
       }
     }
@@ -517,12 +456,6 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
       }
     }
   }
-#ifdef HP_TIMING
-  if (L >= 2048 && L < 2048 + 64 && (tid == 0 || tid == 256)) {
-    const unsigned long long t3 = __builtin_readcyclecounter();
-    printf("blk %d row %d: prologue %llu  K loop %llu  epilogue %llu cycles\n", L, tid >> 8, hp_t1 - hp_t0, hp_t2 - hp_t1, t3 - hp_t2);
-  }
-#endif
 }
 
 // [Cout][3][3][Cin] bf16 (conv_igemm layout) -> [Cout / 256][Cin / 32][9][256 rows][4 slots][8] with the stage swizzle applied
@@ -553,21 +486,13 @@ bool conv_hpipe_ok(DType dt, bool out_f32, const ConvArgs& a) {
          a.Cin >= 32 && a.ss_padded && (a.out_ld & 7) == 0 && a.zeros != nullptr;
 }
 
-#ifdef SYLPH_ABLATE
-int launch_conv_hq(const ConvArgs& a, hipStream_t s);  // tools/probes/conv_hpipe4.hip (linked by tools/probes/build_hq.sh only)
-#endif
-
 int launch_conv_hpipe(const ConvArgs& a, hipStream_t s) {
-#if defined(SYLPH_ABLATE) && defined(SYLPH_HQ_PROBE)
-  static const int hq = SYLPH_AB_ENV("SYLPH_CONV_HQ", 0);  // A/B: the four-wave probe kernel on the same tile table and stage images
-  if (hq) return launch_conv_hq(a, s);
-#endif
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)conv_hpipe_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return -7;
-    if (hipFuncSetAttribute((const void*)conv_hpipe_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return -7;
-    attr_set = true;
-  }
+  static PerDeviceOnce once;
+  if (!once.run(current_device(), [] {
+        return hipFuncSetAttribute((const void*)conv_hpipe_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess &&
+               hipFuncSetAttribute((const void*)conv_hpipe_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
+      }))
+    return -7;
   const int chunk = (a.n_mtiles + 7) / 8;
   const int grid = 8 * chunk * a.n_ntiles;
   if (a.gn_coef) hipLaunchKernelGGL(conv_hpipe_kernel<true>, dim3(grid), dim3(PNT), LDS_BYTES, s, a);

@@ -39,13 +39,10 @@
 // convs (code_generator.py:509-688).
 #include <stdlib.h>
 
-#include "common.h"
+#include "gfx950.h"
 #include "igemm_mma.h"
 
 namespace sylph {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
 template <typename T, typename OutT, int BM, int BN, int WGM, int WGN, int NBUF, bool FAST, bool HALO, bool SPLIT = false>
 __global__ __launch_bounds__(WGM * WGN * 64, (SPLIT ? (BM * BN == 128 * 128 ? 3 : (BM * BN == 128 * 64 && WGN == 2 ? 4 : 5)) : WGM * WGN == 8 ? 4 : (BM * BN <= 128 * 64 ? 5 : (BM * BN >= 256 * 128 ? 2 : (BM * BN == 128 * 128 ? 4 : 1))))) void conv_igemm_kernel(const ConvArgs a) {
@@ -296,20 +293,20 @@ __global__ __launch_bounds__(WGM * WGN * 64, (SPLIT ? (BM * BN == 128 * 128 ? 3 
     for (int kt = kt0; kt < kt1; ++kt) {
       const int hoff = ((kh * HW2 + kw) << 8) | ((kh * HPW + kw) & 15);  // halo row offset (and swizzle-key shift) of the tap about to be fetched
       issue(0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       __syncthreads();
       compute(0, hoff);
       __syncthreads();
     }
   } else if constexpr (NBUF == 2) {
     issue(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     for (int kt = kt0; kt < kt1; ++kt) {
       const int buf = (kt - kt0) & 1;
       if (kt + 1 < kt1) issue(buf ^ 1);
       compute(buf, 0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       __syncthreads();
     }
   } else {
@@ -326,9 +323,9 @@ __global__ __launch_bounds__(WGM * WGN * 64, (SPLIT ? (BM * BN == 128 * 128 ? 3 
     int cur = 0, nxt = NBUF - 1;
     for (int kt = kt0; kt < kt1; ++kt) {
       const int after = kt1 - 1 - kt;  // slices issued behind this one (capped at NBUF - 2)
-      if (after == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else if (after == 1 || NBUF == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W1) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W2) : "memory");
+      if (after == 0) wait_vmcnt<0>();
+      else if (after == 1 || NBUF == 3) wait_vmcnt<W1>();
+      else wait_vmcnt<W2>();
       lds_barrier();
       if (kt + NBUF - 1 < kt1) issue(nxt);
       compute(cur, 0);
@@ -561,8 +558,11 @@ static int launch_cfg(const ConvArgs& a, hipStream_t s) {
   const size_t stage = HALO ? (size_t)(BN + 184) * 128 : (size_t)NBUF * (BM + BN) * 128, epi = (size_t)(BM / WGM) * (BN + 4) * 4;
   size_t lds = stage > epi ? stage : epi;
   if (!(stage >= epi + (size_t)BN * 8)) lds += (size_t)BN * 8;  // scale/shift parked behind everything else
-  if (lds > 65536) (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<T, OutT, BM, BN, WGM, WGN, NBUF, FAST, HALO, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   auto kern = conv_igemm_kernel<T, OutT, BM, BN, WGM, WGN, NBUF, FAST, HALO, SPLIT>;
+  if (lds > 65536) {
+    static PerDeviceOnce once;
+    if (!once.run(current_device(), [&] { return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; })) return -7;
+  }
   hipLaunchKernelGGL(kern, dim3(grid, a.ksplit > 1 ? a.ksplit : 1), dim3(WGM * WGN * 64), lds, s, a);
   return (int)hipGetLastError();
 }
@@ -625,8 +625,7 @@ static int launch_n(const ConvArgs& a, int BM, int BN, hipStream_t s) {
 
 // FAST epilogue: see the kernel.  Only the production dtype (bf16 in, bf16 out) gets it.
 static bool fast_ok(const ConvArgs& a, int BN) {
-  static const int on = SYLPH_AB_ENV("SYLPH_CONV_FAST", 1);
-  return on && a.ss_padded_host && (BN > 64 || a.ss_padded) && a.Cout % BN == 0 && (a.out_ld & 7) == 0 && (a.res_mode == 0 || (a.res_ld & 7) == 0) &&
+  return a.ss_padded_host && (BN > 64 || a.ss_padded) && a.Cout % BN == 0 && (a.out_ld & 7) == 0 && (a.res_mode == 0 || (a.res_ld & 7) == 0) &&
          a.mul_nch == 0 && (a.relu_nch == 0 || a.relu_nch >= a.Cout);
 }
 
@@ -659,9 +658,8 @@ void conv_pick_tile(int rows_total, int cout, int ntaps, int* BM, int* BN) {
 
 int launch_conv(DType dt, bool out_f32, const ConvArgs& a_in, int BM, int BN, hipStream_t s) {
   ConvArgs a = a_in;
-  static const int ss_on = SYLPH_AB_ENV("SYLPH_CONV_SS_LDS", 1);
   a.ss_padded_host = a.ss_padded;
-  if (!ss_on || BN > 64) a.ss_padded = 0;  // the wide tiles are MFMA-bound and have no VGPRs to spare for the prefetch
+  if (BN > 64) a.ss_padded = 0;  // the wide tiles are MFMA-bound and have no VGPRs to spare for the prefetch
   if (a.KH * a.KW > 31) return -3;
   const int bk = dt == DT_BF16 ? 64 : 32;
   if (a.Cin % bk != 0) return -4;

@@ -36,46 +36,11 @@
 // as conv_igemm's epilogue (oracle/bf16.py conv_epilogue).
 // Reference ops replaced: the 1x1 convs of detectron2's BottleneckBlock and FPN at the call site
 // sylph/modeling/meta_arch/meta_one_stage_detector.py:181,273.
-#include <stdlib.h>
-
-#include "common.h"
+#include "gfx950.h"
 
 namespace sylph {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
 namespace {
-
-#define PW_FENCE __builtin_amdgcn_sched_barrier(0)
-#define PW_BAR()                        \
-  do {                                  \
-    asm volatile("" ::: "memory");      \
-    PW_FENCE;                           \
-    __builtin_amdgcn_s_barrier();       \
-    PW_FENCE;                           \
-    asm volatile("" ::: "memory");      \
-  } while (0)
-#define PW_WAITV(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
-
-// s_waitcnt vmcnt(n) for a wave-uniform run-time n (the instruction takes an immediate)
-__device__ __forceinline__ void pw_wait_vm(int n) {
-  switch (n) {
-#define PW_C(N) case N: PW_WAITV(N); break;
-    PW_C(0) PW_C(1) PW_C(2) PW_C(3) PW_C(4) PW_C(5) PW_C(6) PW_C(7) PW_C(8) PW_C(9) PW_C(10) PW_C(11) PW_C(12) PW_C(13) PW_C(14) PW_C(15)
-    PW_C(16) PW_C(17) PW_C(18) PW_C(19) PW_C(20) PW_C(21) PW_C(22) PW_C(23) PW_C(24) PW_C(25) PW_C(26) PW_C(27) PW_C(28) PW_C(29) PW_C(30) PW_C(31)
-    PW_C(32) PW_C(33) PW_C(34) PW_C(35) PW_C(36) PW_C(37) PW_C(38) PW_C(39) PW_C(40) PW_C(41) PW_C(42) PW_C(43) PW_C(44) PW_C(45) PW_C(46) PW_C(47)
-    PW_C(48) PW_C(49) PW_C(50) PW_C(51) PW_C(52) PW_C(53) PW_C(54) PW_C(55) PW_C(56) PW_C(57) PW_C(58) PW_C(59) PW_C(60) PW_C(61) PW_C(62)
-#undef PW_C
-    default: PW_WAITV(63); break;
-  }
-}
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 
 constexpr int pw_lds_bytes(int BM, int BN, int NST) { return NST * (BM + BN) * 64 + 2 * (2 * BN * 4); }
 }  // namespace
@@ -262,8 +227,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_pw_kernel(const
       int younger = oth[0];
 #pragma unroll
       for (int k = 1; k < NST - 1; ++k) younger += grp[k];
-      pw_wait_vm(younger < 63 ? younger : 63);
-      PW_BAR();  // everyone's part of stage `ring` has landed; everyone is done reading the stage refilled next
+      wait_vmcnt_upto<63>(younger < 63 ? younger : 63);
+      fenced_barrier();  // everyone's part of stage `ring` has landed; everyone is done reading the stage refilled next
       {
         int st2 = ring + NST - 1; st2 = st2 >= NST ? st2 - NST : st2;
 #pragma unroll
@@ -294,7 +259,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_pw_kernel(const
     const int last = ring == 0 ? NST - 1 : ring - 1;
     const unsigned stg = lds0 + last * STAGE + wave * 4096;  // 32 rows x 128 B, 16-byte chunk c of row r at slot c ^ (r & 7)
     const unsigned tab = lds0 + RING + cur_par * TAB;         // float scale[BN], shift[BN] (landed with the tile's phase 0)
-    PW_BAR();
+    fenced_barrier();
     u32x2 rchunk[8];
     if (RES && !HOIST) { load_res(0, rchunk); note_other(8); }
 #pragma unroll
@@ -305,7 +270,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_pw_kernel(const
       for (int jj = 0; jj < 2; ++jj) {
         const int j = jh * 2 + jj;
         // scale / shift of this lane's 16 channels of MFMA tile j: 8 table reads, one wait
-        f32x4v sc4[4], sh4[4];
+        f32x4 sc4[4], sh4[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int chw = wn * WTN + j * 32 + 8 * g + 4 * lh;  // channel inside the N tile
@@ -401,19 +366,14 @@ int launch_pw_pack_weights(const void* w, void* out, int Cout, int K, int BN, hi
 }
 
 // Tile shape of a pointwise layer (false: not eligible): 128 x 256 (256 x 128 when Cout % 256 != 0), 3 ring stages -- the operand
-// ratio of conv_hpipe (12 fragment reads per 16 MFMAs) and 6 LDS-DMA instructions per wave and phase.  The 128 x 128 / 4-stage
-// variant (whole residual tile prefetched at the tile start, three activation phases in flight) is kept for A/B runs
-// (SYLPH_PW_TILE=1, -DSYLPH_ABLATE builds only): measured 5-25 % slower on every layer of the R-50 graph -- per 32-channel phase a wave pays one barrier,
-// one counted wait and its LDS-DMA issue slots (~100 cycles each) for only 8 MFMAs.  SYLPH_PW_TILE=3: 256 x 256 tile, 8 lock-step
-// waves, one block per CU (A/B only: equal to the default within 3 %).
+// ratio of conv_hpipe (12 fragment reads per 16 MFMAs) and 6 LDS-DMA instructions per wave and phase.  Two variants were measured
+// and are in git history at ac4cfc5: 128 x 128 / 4 stages (whole residual tile prefetched at the tile start, three activation phases
+// in flight) was 5-25 % slower on every layer of the R-50 graph -- per 32-channel phase a wave pays one barrier, one counted wait
+// and its LDS-DMA issue slots (~100 cycles each) for only 8 MFMAs; 256 x 256 with 8 lock-step waves, one block per CU, was equal
+// to the default within 3 %.
 bool conv_pw_tile(int cout, int k_total, bool has_res, int* BM, int* BN) {
   if (cout % 128 != 0) return false;
   (void)k_total; (void)has_res;
-#ifdef SYLPH_ABLATE
-  static const int force = SYLPH_AB_ENV("SYLPH_PW_TILE", 0);
-  if (force == 3 && cout % 256 == 0) { *BM = 256; *BN = 256; return true; }  // experiment: 256 x 256 tile, 8 waves, one block per CU
-  if (force == 1) { *BM = 128; *BN = 128; return true; }
-#endif
   *BN = cout % 256 == 0 ? 256 : 128;
   *BM = 384 - *BN;
   return true;
@@ -427,34 +387,26 @@ bool conv_pw_ok(DType dt, bool out_f32, const ConvArgs& a) {
          a.trash != nullptr && a.pw_desc != nullptr && a.pw_table != nullptr;
 }
 
-template <int BM, int BN, int NST, int NW = 4>
-static int launch_pw_t(const ConvArgs& a, int grid, hipStream_t s) {
-  const bool relu = a.relu_nch > 0;
+template <int BM, int BN, int NST, int RES, bool RELU>
+static int launch_pw_k(const ConvArgs& a, int grid, int dev, hipStream_t s) {
   constexpr int lds = pw_lds_bytes(BM, BN, NST);
-#define PW_GO(R, L)                                                                                                                \
-  do {                                                                                                                             \
-    static bool attr = false;                                                                                                      \
-    if (!attr) {                                                                                                                   \
-      if (hipFuncSetAttribute((const void*)conv_pw_kernel<BM, BN, NW, NST, R, L>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -7; \
-      attr = true;                                                                                                                 \
-    }                                                                                                                              \
-    hipLaunchKernelGGL((conv_pw_kernel<BM, BN, NW, NST, R, L>), dim3(grid), dim3(NW * 64), lds, s, a);                                   \
-    return (int)hipGetLastError();                                                                                                 \
-  } while (0)
-  if (a.res_mode == 0) { if (relu) PW_GO(0, true); else PW_GO(0, false); }
-  if (a.res_mode == 1) { if (relu) PW_GO(1, true); else PW_GO(1, false); }
-  if (relu) PW_GO(2, true); else PW_GO(2, false);
-#undef PW_GO
+  static PerDeviceOnce once;
+  if (!once.run(dev, [] { return hipFuncSetAttribute((const void*)conv_pw_kernel<BM, BN, 4, NST, RES, RELU>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess; }))
+    return -7;
+  hipLaunchKernelGGL((conv_pw_kernel<BM, BN, 4, NST, RES, RELU>), dim3(grid), dim3(256), lds, s, a);
+  return (int)hipGetLastError();
+}
+
+template <int BM, int BN, int NST>
+static int launch_pw_t(const ConvArgs& a, int grid, int dev, hipStream_t s) {
+  const bool relu = a.relu_nch > 0;
+  if (a.res_mode == 0) return relu ? launch_pw_k<BM, BN, NST, 0, true>(a, grid, dev, s) : launch_pw_k<BM, BN, NST, 0, false>(a, grid, dev, s);
+  if (a.res_mode == 1) return relu ? launch_pw_k<BM, BN, NST, 1, true>(a, grid, dev, s) : launch_pw_k<BM, BN, NST, 1, false>(a, grid, dev, s);
+  return relu ? launch_pw_k<BM, BN, NST, 2, true>(a, grid, dev, s) : launch_pw_k<BM, BN, NST, 2, false>(a, grid, dev, s);
 }
 
 int launch_conv_pw(const ConvArgs& a_in, int BM, int BN, hipStream_t s) {
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return -7;
-    n_cu = p.multiProcessorCount;
-  }
+  const int dev = current_device(), n_cu = device_cu_count(dev);
   ConvArgs a = a_in;
   const int nk = (a.Cin + (a.in2 ? a.Cin2 : 0)) >> 5;
   int p2 = 1;
@@ -464,20 +416,8 @@ int launch_conv_pw(const ConvArgs& a_in, int BM, int BN, hipStream_t s) {
   int grid = (2 * n_cu + 7) & ~7;
   const long need = ((tiles + 7) / 8) * 8;
   if (need < grid) grid = (int)need;
-#ifdef SYLPH_ABLATE
-  static const int nst = SYLPH_AB_ENV("SYLPH_PW_NST", 4);  // tuning knob: ring depth of the small tile
-  if (BM == 128 && BN == 128) {
-    if (nst == 3) { grid = (int)((3L * n_cu + 7) & ~7L); if (need < grid) grid = (int)need; return launch_pw_t<128, 128, 3>(a, grid, s); }
-    return launch_pw_t<128, 128, 4>(a, grid, s);
-  }
-  if (BM == 256 && BN == 256) {  // 8 waves, one block per CU
-    grid = (n_cu + 7) & ~7;
-    if (need < grid) grid = (int)need;
-    return launch_pw_t<256, 256, 3, 8>(a, grid, s);
-  }
-#endif
-  if (BM == 128 && BN == 256) return launch_pw_t<128, 256, 3>(a, grid, s);
-  if (BM == 256 && BN == 128) return launch_pw_t<256, 128, 3>(a, grid, s);
+  if (BM == 128 && BN == 256) return launch_pw_t<128, 256, 3>(a, grid, dev, s);
+  if (BM == 256 && BN == 128) return launch_pw_t<256, 128, 3>(a, grid, dev, s);
   return -1;
 }
 

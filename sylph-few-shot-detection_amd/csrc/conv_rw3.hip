@@ -17,7 +17,7 @@
 //   * With one wave per SIMD nothing hides what is not an MFMA, and an in-order wave that waits for the matrix pipe at every MFMA has
 //     only the ~32 cycles of the MFMA just issued to hide anything in.  So the next patch's halo loads and LDS writes and the previous
 //     patch's stores are cut into pieces of a few instructions, one piece behind one MFMA of the K loop (hook() below, pinned with
-//     sched_barriers).  s_memtime stamps (-DRW_TIMING, SYLPH_ABLATE builds) priced every step of that at B = 64:
+//     sched_barriers).  s_memtime stamps (a measurement build, in git history at ac4cfc5) priced every step of that at B = 64:
 //         serial phases (load, K loop, epilogue, store)                                       304 us / launch
 //         + halo row pitch == pw (mod 16) pixels-of-16-bytes (2-way bank conflicts on every read before)     the reads alone 124 -> 70 us
 //         + the same work as three blocks of code inside the K loop                           300 us (a block extends its k-step by its length)
@@ -28,18 +28,10 @@
 //
 // Numerics: bf16 operands, fp32 accumulation over the taps in tap order, v = acc * scale + shift, ReLU, bf16: the rounding points of
 // conv_igemm's halo mode (oracle/bf16.py conv_epilogue).
-// Ablation switches (RW_NOSTORE, RW_NOHALO, RW_NOMFMA, RW_NOREAD: measurement aids) exist only in -DSYLPH_ABLATE builds (tools/build_variant.sh)
-#ifndef SYLPH_ABLATE
-#undef RW_NOSTORE
-#undef RW_NOHALO
-#undef RW_NOMFMA
-#undef RW_NOREAD
-#undef RW_TIMING
-#endif
 #include <type_traits>
 #include <utility>
 
-#include "common.h"
+#include "gfx950.h"
 
 namespace sylph {
 
@@ -71,23 +63,10 @@ __host__ __device__ inline int rw_row_pitch(int pw) {
   const int k0 = (pw + 2) * (RW_TP / 16);
   return (k0 + ((pw - k0) & 15)) * 16;
 }
-#define RW_MFMA_A(acc, w, av) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(av))
-#define RW_MFMA_A0(acc, w, av) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(acc) : "a"(w), "v"(av))
-#define RW_MFMA_V(acc, w, av) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(av))
-#define RW_BAR()                                       \
-  do {                                                 \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    __builtin_amdgcn_s_barrier();                      \
-    asm volatile("" ::: "memory");                     \
-  } while (0)
 }  // namespace
 
 __global__ __launch_bounds__(256, 1) void conv_rw3_kernel(const BottleneckArgs a) {
   typedef bf16_t T;
-  typedef int i32x8 __attribute__((ext_vector_type(8)));
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  typedef short s16x2 __attribute__((ext_vector_type(2)));
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -111,7 +90,7 @@ __global__ __launch_bounds__(256, 1) void conv_rw3_kernel(const BottleneckArgs a
     float* bn = reinterpret_cast<float*>(smem + RW_BN);
     bn[tid] = tid < RW_CH ? a.s2[tid] : a.b2[tid - RW_CH];
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
 
   // persistent tile walk: blocks of one XCD (blockIdx & 7) take neighbouring patches at the same time
   const int G = gridDim.x, xcd = blockIdx.x & 7, jb = blockIdx.x >> 3, gx = (G + 7) >> 3;
@@ -152,7 +131,6 @@ __global__ __launch_bounds__(256, 1) void conv_rw3_kernel(const BottleneckArgs a
     return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, u), z));
   };
   auto pack2 = [](float lo, float hi) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
     bf16x2 v;
     v[0] = (bf16_t)lo;
     v[1] = (bf16_t)hi;
@@ -177,34 +155,17 @@ __global__ __launch_bounds__(256, 1) void conv_rw3_kernel(const BottleneckArgs a
     for (int j = 0; j < 8; ++j) {
       const u32x4 v = *reinterpret_cast<const u32x4*>(smem + RW_STG + tid * 16 + j * 4096);
       const unsigned yo = *reinterpret_cast<const unsigned*>(smem + RW_TAB + (tid >> 4) * 4 + j * 64);
-#ifdef RW_NOSTORE
-      if (yo == 0xfffffff0u)
-#endif
       __builtin_amdgcn_raw_buffer_store_b128(v, yr, yo + st_sw, 0, 0);
     }
   };
 
-#ifdef RW_TIMING
-  unsigned long long ts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long rt0 = 0, rt1 = 0;
-#define RW_STAMP(i) do { if (it == 10) ts[i] = __builtin_readcyclecounter(); } while (0)
-#else
-#define RW_STAMP(i) do { } while (0)
-#endif
   for (int it = 0; t < a.n_tiles; ++it) {
-#ifdef RW_TIMING
-    if (it == 10) rt0 = wall_clock64();
-    if (it == 11) rt1 = wall_clock64();
-    if (it == 11) ts[8] = __builtin_readcyclecounter();
-#endif
-    RW_STAMP(0);
     const int row0 = td[0], IH = td[1], IW = td[2], oy0 = td[3] >> 16, ox0 = td[3] & 0xffff;
     const int PW = td[5], NPOS = td[4] * PW, PY = rw_row_pitch(PW);
     const unsigned inv_pw = (unsigned)td[6];
     int t_next = a.n_tiles;
     i32x8 td_next = td;
-    RW_BAR();  // this patch's halo is in buffer it & 1, the previous patch's staging tile and table are complete
-    RW_STAMP(1);
+    lds_barrier();  // this patch's halo is in buffer it & 1, the previous patch's staging tile and table are complete
 
     // ===== K loop: acc[i] = sum over taps and channels of halo(position 32 i + l31 shifted by the tap) x W ================================
     f32x16 acc[4];
@@ -228,11 +189,7 @@ __global__ __launch_bounds__(256, 1) void conv_rw3_kernel(const BottleneckArgs a
         for (int i = 0; i < 4; ++i) {
           const unsigned ad = hrow[i] + kh * PY + kw * RW_TP;
           bf16x8& dst = af[k % D][i];
-#ifdef RW_NOREAD
-          asm volatile("" : "=v"(dst) : "v"(ad));
-#else
           asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(ad), "n"(ks * 32));
-#endif
         }
       };
       // hook(k, i): the piece of non-K-loop work issued right after MFMA i of k-step k.  A wave issues in order and an MFMA waits for
@@ -255,7 +212,6 @@ __global__ __launch_bounds__(256, 1) void conv_rw3_kernel(const BottleneckArgs a
           asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=s"(td_next) : "s"(p));
         }
         if constexpr (k == 1 && i == 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(td_next));
-#ifndef RW_NOHALO
         if constexpr (k == 1 && i == 1) halo_cols((it + 1) & 1, td_next);
         if constexpr (k == 1 && i == 2) {  // bit j: halo row j of the next patch lies inside the image (none when there is no next patch)
           const int oy0n = td_next[3] >> 16, lo = max(0, 1 - oy0n), hi = min(td_next[4] + 2, td_next[1] - oy0n + 1);
@@ -275,12 +231,8 @@ __global__ __launch_bounds__(256, 1) void conv_rw3_kernel(const BottleneckArgs a
           const u32x4* hr = hreg;
           *reinterpret_cast<u32x4*>(smem + hlds + (k - 46) * PY) = hr[k - 46];  // (every patch of a launch has the same ph x pw)
         }
-#endif
         if constexpr (k >= 4 && k <= 39 && (k - 4) % 5 == 0 && i == 0) {
           asm volatile("" : "+v"(svr), "+v"(syor));
-#ifdef RW_NOSTORE
-          if (syor == 0xfffffff0u)
-#endif
           __builtin_amdgcn_raw_buffer_store_b128(svr, yr, syor + st_sw, 0, 0);
         }
       };
@@ -301,31 +253,20 @@ __global__ __launch_bounds__(256, 1) void conv_rw3_kernel(const BottleneckArgs a
         asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]) : "n"(ahead));
         static_for<0, 4>([&](auto ic) {
           constexpr int i = decltype(ic)::value;
-#ifdef RW_NOMFMA
-          if constexpr (k == 0 || k == 71)
-#endif
-          {
-            if constexpr (k == 0) RW_MFMA_A0(ac[i], wa[0], f[i]);
-            else if constexpr (k < 64) RW_MFMA_A(ac[i], wa[k], f[i]);
-            else RW_MFMA_V(ac[i], wv[k - 64], f[i]);
-          }
+          if constexpr (k == 0) mfma_aw0(ac[i], wa[0], f[i]);
+          else if constexpr (k < 64) mfma_aw(ac[i], wa[k], f[i]);
+          else mfma_vw(ac[i], wv[k - 64], f[i]);
           __builtin_amdgcn_sched_barrier(0);
           hook(kc, ic);
           __builtin_amdgcn_sched_barrier(0);
         });
-        if constexpr (k == 16) RW_STAMP(2);
-        if constexpr (k == 28) RW_STAMP(3);
-        if constexpr (k == 57) RW_STAMP(4);
       };
       rd(std::integral_constant<int, 0>{});
       rd(std::integral_constant<int, 1>{});
       static_for<0, 72>(step);
-      // inline-asm MFMAs are invisible to the hazard recogniser: the wait states it would insert before the first VALU read of an accumulator
-      asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3])::"memory");
+      mfma_drain(acc[0], acc[1], acc[2], acc[3]);
     }
-    RW_STAMP(5);
-    RW_BAR();  // every wave has stored the previous patch's staging tile (and is done reading this patch's halo)
-    RW_STAMP(6);
+    lds_barrier();  // every wave has stored the previous patch's staging tile (and is done reading this patch's halo)
 
     // ===== epilogue: FrozenBN + ReLU -> bf16 -> the staging tile (row m, piece 4 wave + g, half lh); y byte offsets of the positions ===
     if (tid < 128) {  // RW_OOB: no such pixel
@@ -355,17 +296,11 @@ __global__ __launch_bounds__(256, 1) void conv_rw3_kernel(const BottleneckArgs a
         }
       }
     }
-    RW_STAMP(7);
     t = t_next;
     td = td_next;
   }
-  RW_BAR();
+  lds_barrier();
   store_prev_all();
-#ifdef RW_TIMING
-  if (blockIdx.x == 8 && lane == 0)
-    printf("wave %d: top->barA %llu  ->k16 %llu  ->k28 %llu  ->k57 %llu  ->K end %llu  ->barB %llu  ->epi %llu  | whole iteration %llu cycles = %llu ns\n", wave,
-           ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2], ts[4] - ts[3], ts[5] - ts[4], ts[6] - ts[5], ts[7] - ts[6], ts[8] - ts[0], (rt1 - rt0) * 10);
-#endif
 }
 
 bool conv_rw3_patch_ok(int ph, int pw) {

@@ -31,49 +31,11 @@
 // addressed with a 64-bit base per image + 32-bit offsets inside it.
 //
 // Numerics: the rounding points of conv_pw / conv_igemm (fp32 accumulate, fma(acc, scale, shift) + residual, ReLU, bf16).
-#include <stdlib.h>
-
-#include "common.h"
+#include "gfx950.h"
 
 namespace sylph {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
 namespace {
-
-// Ablation switches (SPW_NOSTORE, SPW_NORES: measurement aids) exist only in -DSYLPH_ABLATE builds (tools/build_variant.sh)
-#ifndef SYLPH_ABLATE
-#undef SPW_NOSTORE
-#undef SPW_NORES
-#endif
-
-#define SP_FENCE __builtin_amdgcn_sched_barrier(0)
-#define SP_BAR()                        \
-  do {                                  \
-    asm volatile("" ::: "memory");      \
-    SP_FENCE;                           \
-    __builtin_amdgcn_s_barrier();       \
-    SP_FENCE;                           \
-    asm volatile("" ::: "memory");      \
-  } while (0)
-#define SP_WAITV(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
-
-__device__ __forceinline__ void sp_wait_vm(int n) {
-  switch (n) {
-#define SP_C(N) case N: SP_WAITV(N); break;
-    SP_C(0) SP_C(1) SP_C(2) SP_C(3) SP_C(4) SP_C(5) SP_C(6) SP_C(7) SP_C(8) SP_C(9) SP_C(10) SP_C(11) SP_C(12) SP_C(13) SP_C(14) SP_C(15)
-    SP_C(16) SP_C(17) SP_C(18) SP_C(19) SP_C(20) SP_C(21) SP_C(22) SP_C(23) SP_C(24) SP_C(25) SP_C(26) SP_C(27) SP_C(28) SP_C(29) SP_C(30) SP_C(31)
-#undef SP_C
-    default: SP_WAITV(32); break;
-  }
-}
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 
 constexpr int BM = 128, BN = 256, NST = 4;
 constexpr int STAGE = BM * 128, RING = NST * STAGE, TAB = 2 * BN * 4;   // a stage = A rows of one 64-channel phase: [128][128 B]
@@ -194,11 +156,7 @@ __global__ __launch_bounds__(512, 1) void conv_spw_kernel(const ConvArgs a) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int rc = c * 32 + 8 * k + r8, pos = p_row0 + rc;
-#ifdef SPW_NOSTORE
-        if (pos < p_seg_rows && o[k][0] == 0x12345678u)
-#else
         if (pos < p_seg_rows)
-#endif
           *reinterpret_cast<u32x4*>(outb + ((size_t)(p_out_row0 + pos) * a.out_ld + scol + ((s8 ^ (rc & 7)) << 3)) * 2) = o[k];
       }
     }
@@ -215,11 +173,7 @@ __global__ __launch_bounds__(512, 1) void conv_spw_kernel(const ConvArgs a) {
         pos = (oy >> 1) * res_W + (ox >> 1);
       }
       const char* src = resb + ((size_t)(res_row0 + pos) * a.res_ld + scol + ((s8 ^ (rc & 7)) << 3)) * 2;
-#ifdef SPW_NORES
-      if (src == nullptr) *reinterpret_cast<volatile int*>(region_p) = 0;
-#else
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)(region_p + k * 1024), 16, 0, 0);
-#endif
     }
   };
 
@@ -246,9 +200,9 @@ __global__ __launch_bounds__(512, 1) void conv_spw_kernel(const ConvArgs a) {
         int younger = 0;
 #pragma unroll
         for (int k = 1; k < NST - 1; ++k) younger += grp[k];
-        sp_wait_vm(younger);
+        wait_vmcnt_upto<32>(younger);
       }
-      SP_BAR();  // everyone's part of stage `ring` has landed; everyone is done reading the stage refilled next
+      fenced_barrier();  // everyone's part of stage `ring` has landed; everyone is done reading the stage refilled next
       if (loader) {
         int st2 = ring + NST - 1; st2 = st2 >= NST ? st2 - NST : st2;
 #pragma unroll
@@ -280,10 +234,10 @@ __global__ __launch_bounds__(512, 1) void conv_spw_kernel(const ConvArgs a) {
       }
       ring = ring + 1 == NST ? 0 : ring + 1;
     }
-    if (streamer) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this tile's residual has landed (and the previous tile is out)
-    SP_BAR();  // A: K loop done everywhere, residual in the buffer
+    if (streamer) wait_vmcnt<0>();  // this tile's residual has landed (and the previous tile is out)
+    fenced_barrier();  // A: K loop done everywhere, residual in the buffer
     if constexpr (K <= 384) {
-      f32x4v sc4[4], sh4[4];
+      f32x4 sc4[4], sh4[4];
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int chw = wave * 32 + 8 * g + 4 * lh;
@@ -334,7 +288,7 @@ __global__ __launch_bounds__(512, 1) void conv_spw_kernel(const ConvArgs a) {
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          f32x4v sc4, sh4;
+          f32x4 sc4, sh4;
           const int chw = wave * 32 + 8 * g + 4 * lh;
           asm volatile("ds_read_b128 %0, %1" : "=v"(sc4) : "v"(tab + chw * 4));
           asm volatile("ds_read_b128 %0, %1" : "=v"(sh4) : "v"(tab + (BN + chw) * 4));
@@ -358,7 +312,7 @@ __global__ __launch_bounds__(512, 1) void conv_spw_kernel(const ConvArgs a) {
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    SP_BAR();  // B: the buffer holds the finished tile
+    fenced_barrier();  // B: the buffer holds the finished tile
     if (streamer) { p_row0 = row0; p_seg_rows = seg_rows; p_out_row0 = out_row0; have_prev = true; }
     cur_m += m_step;
     if (!valid_at(cur_m)) break;

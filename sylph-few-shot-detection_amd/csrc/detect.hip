@@ -21,7 +21,7 @@
 //   sylph/modeling/meta_fcos/fcos_outputs.py:1010-1028 select_over_all_levels (ml_nms, kthvalue keep)
 //   sylph/modeling/meta_arch/meta_one_stage_detector.py:288-296 detector_postprocess
 //   sylph/modeling/meta_fcos/fcos.py:270-282 compute_locations
-#include "common.h"
+#include "gfx950.h"
 #include "kernels.h"
 
 namespace sylph {
@@ -456,10 +456,6 @@ __global__ __launch_bounds__(256, 2) void logits_scan_kernel(const bf16_t* __res
                                                              const SegDesc* __restrict__ segs, const int2* __restrict__ tiles,
                                                              int n_tiles, const float* __restrict__ pred, int pred_ld,
                                                              const DecodeCfg cfg, const DecodeBuffers buf) {
-  typedef float f32x2v __attribute__((ext_vector_type(2)));
-  typedef short s16x2v __attribute__((ext_vector_type(2)));
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
   __shared__ __attribute__((aligned(16))) float cf[4][512];  // per wave: (a0, a1, b0, b1) per channel pair of its current segment
   __shared__ unsigned q_x[4][LS_QCAP], q_id[4][LS_QCAP];      // hit queue: logit bits, (row of the group << 16) | class
   __shared__ unsigned c_key[4][LS_CCAP], c_idx[4][LS_CCAP];   // candidates of the wave's current segment
@@ -525,14 +521,14 @@ __global__ __launch_bounds__(256, 2) void logits_scan_kernel(const bf16_t* __res
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float4 c4 = *reinterpret_cast<const float4*>(cq + 4 * e);
-        const f32x2v xf = {__uint_as_float(yv[ks][e] << 16), __uint_as_float(yv[ks][e] & 0xffff0000u)};
-        const f32x2v av = {c4.x, c4.y}, bv = {c4.z, c4.w};
-        const f32x2v r = __builtin_elementwise_fma(xf, av, bv);
+        const f32x2 xf = {__uint_as_float(yv[ks][e] << 16), __uint_as_float(yv[ks][e] & 0xffff0000u)};
+        const f32x2 av = {c4.x, c4.y}, bv = {c4.z, c4.w};
+        const f32x2 r = __builtin_elementwise_fma(xf, av, bv);
         bf16x2 pk;
         pk[0] = (bf16_t)r[0];
         pk[1] = (bf16_t)r[1];
-        const s16x2v z = {0, 0};
-        yv[ks][e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2v, pk), z));  // ReLU on the bf16 pair
+        const s16x2 z = {0, 0};
+        yv[ks][e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pk), z));  // ReLU on the bf16 pair
       }
     }
     for (int ct = 0; ct < n_ct; ++ct) {

@@ -9,7 +9,7 @@
 // k-step, a row's 512 bytes over 16 k-steps), applies the same fused multiply-add + ReLU + bf16 rounding as the apply kernel
 // (bit-identical operand values), and multiplies by the 32 x 256 code matrix held in registers.  No LDS for data, no barriers:
 // the pass is HBM-bound (one read of the tower output, one write of the fp32 logits).
-#include "common.h"
+#include "gfx950.h"
 
 namespace sylph {
 
@@ -17,10 +17,6 @@ __global__ __launch_bounds__(256) void gn_logits_kernel(const bf16_t* __restrict
                                                         const bf16_t* __restrict__ w, const float* __restrict__ bias, int N,
                                                         float* __restrict__ out, int out_ld, const SegDesc* __restrict__ segs,
                                                         const int2* __restrict__ tiles, int n_tiles) {
-  typedef float f32x2v __attribute__((ext_vector_type(2)));
-  typedef short s16x2v __attribute__((ext_vector_type(2)));
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
   __shared__ __attribute__((aligned(16))) float cf[4][512];  // per wave: (a0, a1, b0, b1) per channel pair of its current segment
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
 
@@ -71,14 +67,14 @@ __global__ __launch_bounds__(256) void gn_logits_kernel(const bf16_t* __restrict
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float4 c4 = *reinterpret_cast<const float4*>(cq + 4 * e);
-        const f32x2v xf = {__uint_as_float(xv[ks][e] << 16), __uint_as_float(xv[ks][e] & 0xffff0000u)};
-        const f32x2v av = {c4.x, c4.y}, bv = {c4.z, c4.w};
-        const f32x2v r = __builtin_elementwise_fma(xf, av, bv);
+        const f32x2 xf = {__uint_as_float(xv[ks][e] << 16), __uint_as_float(xv[ks][e] & 0xffff0000u)};
+        const f32x2 av = {c4.x, c4.y}, bv = {c4.z, c4.w};
+        const f32x2 r = __builtin_elementwise_fma(xf, av, bv);
         bf16x2 pk;
         pk[0] = (bf16_t)r[0];
         pk[1] = (bf16_t)r[1];
-        const s16x2v z = {0, 0};
-        yv[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2v, pk), z));  // ReLU on the bf16 pair
+        const s16x2 z = {0, 0};
+        yv[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pk), z));  // ReLU on the bf16 pair
       }
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[ks], __builtin_bit_cast(bf16x8, yv), acc, 0, 0, 0);
     }
@@ -105,10 +101,6 @@ template <int NT>
 __global__ __launch_bounds__(256) void gn_taps_kernel(const bf16_t* __restrict__ x, int ld, const float2* __restrict__ coef,
                                                       const bf16_t* __restrict__ w, float* __restrict__ out, int sw, size_t plane_rows,
                                                       const SegDesc* __restrict__ segs, const int2* __restrict__ tiles, int n_tiles) {
-  typedef float f32x2v __attribute__((ext_vector_type(2)));
-  typedef short s16x2v __attribute__((ext_vector_type(2)));
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
   __shared__ __attribute__((aligned(16))) float cf[4][512];
   constexpr int TR_PITCH = NT * 32 + 4;  // floats per row of the transpose tile (+4: the 16-byte row pieces of 8 lanes fall on different banks)
   __shared__ __attribute__((aligned(16))) float tr[4][32 * TR_PITCH];
@@ -155,14 +147,14 @@ __global__ __launch_bounds__(256) void gn_taps_kernel(const bf16_t* __restrict__
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float4 c4 = *reinterpret_cast<const float4*>(cq + 4 * e);
-        const f32x2v xf = {__uint_as_float(xv[ks][e] << 16), __uint_as_float(xv[ks][e] & 0xffff0000u)};
-        const f32x2v av = {c4.x, c4.y}, bv = {c4.z, c4.w};
-        const f32x2v r = __builtin_elementwise_fma(xf, av, bv);
+        const f32x2 xf = {__uint_as_float(xv[ks][e] << 16), __uint_as_float(xv[ks][e] & 0xffff0000u)};
+        const f32x2 av = {c4.x, c4.y}, bv = {c4.z, c4.w};
+        const f32x2 r = __builtin_elementwise_fma(xf, av, bv);
         bf16x2 pk;
         pk[0] = (bf16_t)r[0];
         pk[1] = (bf16_t)r[1];
-        const s16x2v z = {0, 0};
-        yv[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2v, pk), z));
+        const s16x2 z = {0, 0};
+        yv[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pk), z));
       }
 #pragma unroll
       for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[t][ks], __builtin_bit_cast(bf16x8, yv), acc[t], 0, 0, 0);

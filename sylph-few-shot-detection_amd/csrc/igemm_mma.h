@@ -2,7 +2,7 @@
 // (conv_igemm.hip, conv_deform.hip).  Both kernels stage 128-byte K-slices per LDS row with the 16-byte chunk swizzle
 // slot = chunk ^ ((row >> 1) & 7), which is what the fragment readers below undo.
 #pragma once
-#include "common.h"
+#include "gfx950.h"
 
 namespace sylph {
 

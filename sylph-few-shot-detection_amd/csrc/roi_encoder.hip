@@ -181,13 +181,14 @@ __global__ __launch_bounds__(256) void mscam_kernel(const float* __restrict__ ct
 
 int launch_mscam(DType dt, const float* ctx, void* x, int S, const MsCamWeights& w, hipStream_t s) {
   const size_t lds = (size_t)(MP * MC * 2 + MP * MI + MC + 64) * sizeof(float);
-  if (dt == DT_BF16) {
-    (void)hipFuncSetAttribute((const void*)mscam_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(mscam_kernel<bf16_t>, dim3(S), dim3(256), lds, s, ctx, (bf16_t*)x, w);
-  } else {
-    (void)hipFuncSetAttribute((const void*)mscam_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(mscam_kernel<float>, dim3(S), dim3(256), lds, s, ctx, (float*)x, w);
-  }
+  static PerDeviceOnce once;
+  if (!once.run(current_device(), [&] {
+        return hipFuncSetAttribute((const void*)mscam_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
+               hipFuncSetAttribute((const void*)mscam_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+      }))
+    return -7;
+  if (dt == DT_BF16) hipLaunchKernelGGL(mscam_kernel<bf16_t>, dim3(S), dim3(256), lds, s, ctx, (bf16_t*)x, w);
+  else hipLaunchKernelGGL(mscam_kernel<float>, dim3(S), dim3(256), lds, s, ctx, (float*)x, w);
   return (int)hipGetLastError();
 }
 

@@ -14,7 +14,7 @@
 //   * D^T MFMA (weights as the A operand): a lane ends up with 4 consecutive channels of one position; the
 //     epilogue goes through an fp32 LDS tile like conv_igemm.hip (scale/shift, ReLU, 16-byte stores);
 //   * persistent blocks (grid-stride over tiles); the patches of the next two tiles are in flight in registers.
-#include "common.h"
+#include "gfx950.h"
 #include "kernels.h"
 
 namespace sylph {
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const bf16_t* __restr
   // moved) before its own park: the ~2 us HBM round trip is longer than one tile's work.
   const int g = gridDim.x;
   auto do_tile = [&](int tile, uint2 (&q)[NLOAD], uint32_t& qm) {
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    wait_vmcnt<4>();
     static_assert(NLOAD == 4, "the vmcnt immediate above is NLOAD");
     park(q, qm);
     lds_barrier();
@@ -205,8 +205,6 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const bf16_t* __restr
                                                            bf16_t* __restrict__ out, char* __restrict__ trash, int H, int W, int H2,
                                                            int W2, int H4, int W4, int tiles_y, int tiles_x, int ntiles) {
   constexpr int NV = RAW ? 3 * FNLOAD : FNLOAD;  // VMEM loads per thread and tile
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  typedef short s16x2 __attribute__((ext_vector_type(2)));
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* patch = smem;
   char* st = smem + FPATCH_BYTES;
@@ -297,7 +295,6 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const bf16_t* __restr
       uint2 t = make_uint2(0u, 0u);
       if ((okmask >> r) & 1u) {
         if (RAW) {
-          typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
           bf16x2 lo2;
           lo2[0] = (bf16_t)((__uint_as_float(v[3 * r]) - raw.m0) * raw.is0);
           lo2[1] = (bf16_t)((__uint_as_float(v[3 * r + 1]) - raw.m1) * raw.is1);
@@ -316,7 +313,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const bf16_t* __restr
   for (int ks = 0; ks < 14; ++ks)
 #pragma unroll
     for (int j = 0; j < 2; ++j) asm volatile("" : "+v"(wb[ks][j]));
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   if (RAW) __syncthreads();  // the image table is complete before the first fetch reads it
 
   const int g = gridDim.x;
@@ -325,9 +322,9 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const bf16_t* __restr
     // issued after this tile's patch loads (two tiles ago): 2 stores, the next tile's NV loads, 2 stores -- all may stay in flight
     // (the first two tiles have fewer operations behind their patch)
     static_assert(FNLOAD == 6, "the vmcnt immediates below are NV = 6 / 18 (+ 2 stores per finished tile)");
-    if (nth == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NV) : "memory");
-    else if (nth == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NV + 2) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NV + 4) : "memory");
+    if (nth == 0) wait_vmcnt<NV>();
+    else if (nth == 1) wait_vmcnt<NV + 2>();
+    else wait_vmcnt<NV + 4>();
     ++nth;
     park(q, qm);
     lds_barrier();
@@ -360,7 +357,6 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const bf16_t* __restr
           for (int q4 = 0; q4 < 4; ++q4) {
             const int n0 = 32 * j + 8 * q4 + 4 * lh;
             const f32x4 sv = *reinterpret_cast<const f32x4*>(ss + n0), bv = *reinterpret_cast<const f32x4*>(ss + 64 + n0);
-            typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
             u32x2 o;
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {

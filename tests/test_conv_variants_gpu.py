@@ -88,7 +88,7 @@ def test_parity_suite_with_pointwise_kernel_everywhere():
     """SYLPH_CONV_PW=2 routes EVERY eligible bf16 1x1 layer through conv_pw_kernel whatever the launch size -- also the layers the
     default policy leaves on conv_igemm (same-geometry residual: the RES = 1 instantiations; N = 128 identity conv1): conv2d vs
     torch, backbone / episode / full-size checks, and the ulp-level block tests.  (The rejected 128x128 / 256x256 tile variants
-    exist only in -DSYLPH_ABLATE builds, tools/build_variant.sh.)"""
+    are in git history at ac4cfc5.)"""
     env = {"SYLPH_CONV_PW": "2"}
     _rerun(env, "bf16 and (conv2d or backbone_fpn or c3_full_size or full_size_prop)")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_bf16_pinned_gpu.py"), "-m", "gpu", "-q", "-x", "-k",

@@ -2,7 +2,8 @@
 """Micro-benchmark of one identity bottleneck block at its production shape (default: res2, B x 200 x 336, C 256, mid 64: the fused
 bottleneck.hip kernel; stage 3 / 4 / 5: the three conv launches of a res3 / res4 / res5 identity block).
 HIP-event time of the kernel launch alone (sylph_profile), so the layout conversions of the parity entry are not in it.
-Usage (GPU box): [SYLPH_LIB_PATH=lib/variants/...so] python tools/bench_bottleneck.py [batch] [iters] [stage]"""
+Usage (GPU box): [SYLPH_LIB_PATH=<another build of the library>] python tools/bench_bottleneck.py [batch] [iters] [stage]
+(the ablation builds it was used with, tools/build_variant.sh, are in git history at ac4cfc5)"""
 import os
 import sys
 
