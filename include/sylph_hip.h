@@ -291,6 +291,10 @@ int sylph_profile_read(sylph_ctx* ctx, double* conv_ms, double* conv_flops, int6
  * kernel names in first-launch order), ms / flops / launches per kernel; *n_out kernels were written. */
 int sylph_profile_read_kernels(sylph_ctx* ctx, int max_kernels, char* names_out, double* ms_out, double* flops_out,
                                int64_t* launches_out, int* n_out);
+/* The conv route of every conv launch BUILT while profiling was enabled, in build order (consumes them): names_out = max_routes x 64
+ * bytes, NUL-terminated "<kind> <BM>x<BN>[ nbuf<n>][ ks<k>]" with kind one of hpipe, igemm_halo, pw, spw, igemm_splitk, igemm
+ * (e.g. "igemm_splitk 64x64 nbuf2 ks8"); *n_out routes were written.  A plan built once and replayed records its convs once. */
+int sylph_conv_routes_read(sylph_ctx* ctx, int max_routes, char* names_out, int* n_out);
 
 #ifdef __cplusplus
 }

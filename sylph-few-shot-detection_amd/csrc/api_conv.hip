@@ -274,6 +274,22 @@ ConvRoute pick_conv_route(const sylph_ctx* c, const ConvLayer& L, int in_ld, con
   return r;
 }
 
+// The route record of one add_conv (profiling on): kind, tile, LDS stages of the 64-row tiles, K ranges of a split launch
+std::string conv_route_name(const ConvRoute& r) {
+  static const char* kinds[] = {"hpipe", "igemm_halo", "pw", "spw", "igemm_splitk", "igemm"};
+  std::string s = std::string(kinds[(int)r.kind]) + " " + std::to_string(r.BM) + "x" + std::to_string(r.BN);
+  if (r.nbuf) s += " nbuf" + std::to_string(r.nbuf);
+  if (r.kind == ConvKind::igemm_splitk) s += " ks" + std::to_string(r.ksplit);
+  return s;
+}
+
+void adopt_records(sylph_ctx* c, sylph_ctx* tmp) {
+  for (auto& r : tmp->prof_recs) c->prof_recs.push_back(r);
+  tmp->prof_recs.clear();
+  for (auto& r : tmp->route_recs) c->route_recs.push_back(r);
+  tmp->route_recs.clear();
+}
+
 // Re-packed weight copies, made once per layer and owned by the context (they outlive the plan that first needed them), keyed by the
 // conv_igemm-layout pointer: conv_hpipe.hip's stage images; conv_pw.hip's stage images + scale/shift table.  conv_spw reads the
 // conv_igemm layout itself (weights in registers): it gets the table only (7 MB of dead memory), and the stage images are
@@ -451,6 +467,7 @@ int add_conv(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const voi
     };
   }
   ops.push_back([=](hipStream_t s) { return timed_op(c, kern, flops, s, launch); });
+  if (c->prof) c->route_recs.push_back(conv_route_name(r));
   return 0;
 }
 

@@ -251,4 +251,16 @@ int sylph_profile_read_kernels(sylph_ctx* c, int max_kernels, char* names, doubl
   return 0;
 }
 
+int sylph_conv_routes_read(sylph_ctx* c, int max_routes, char* names, int* n_out) {
+  int n = 0;
+  for (auto& r : c->route_recs) {
+    if (n >= max_routes) break;
+    snprintf(names + (size_t)n * 64, 64, "%s", r.c_str());
+    ++n;
+  }
+  c->route_recs.clear();
+  if (n_out) *n_out = n;
+  return 0;
+}
+
 }  // extern "C"

@@ -145,6 +145,7 @@ struct sylph_ctx {
   struct ProfRec { hipEvent_t a, b; double flops; const char* kern; };
   std::vector<ProfRec> prof_recs;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_free;
+  std::vector<std::string> route_recs;  // while prof: one line per add_conv naming the ConvRoute it took (sylph_conv_routes_read)
 
   // Plan cache policy: every allocation made while a plan is being built / grown is owned by that plan, and
   // plans are evicted least-recently-used first once their count or their bytes exceed the budget, so a stream of
@@ -333,6 +334,8 @@ int make_geom_patch(sylph_ctx* c, std::vector<SegDesc> segs, int max_pos, int ha
 long patch_count(const std::vector<SegDesc>& segs, int max_pos, int halo_rows, int xpad);
 int timed_op(sylph_ctx* c, const char* kern, double flops, hipStream_t s, const std::function<int(hipStream_t)>& fn);
 ConvRoute pick_conv_route(const sylph_ctx* c, const ConvLayer& L, int in_ld, const std::vector<SegDesc>& segs, const ConvOpts& o);  // pure: no allocation, no upload
+std::string conv_route_name(const ConvRoute& r);  // "igemm_splitk 64x64 nbuf2 ks8", "hpipe 256x256", "pw 128x256", ...
+void adopt_records(sylph_ctx* c, sylph_ctx* tmp);  // parity entries: move a scratch context's profile + route records to the caller's
 int add_conv(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, int in_ld, void* out, int out_ld, const std::vector<SegDesc>& segs, const ConvOpts& o, Geom* geom_out = nullptr);
 int add_conv_gn(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, int in_ld, void* out, const std::vector<SegDesc>& segs, ConvOpts o, const GNLayer& G, int relu, const float2** coef_out = nullptr, OpFn* apply_out = nullptr);
 int add_gn_from_partials(sylph_ctx* c, std::vector<OpFn>& ops, void* out, int ld, const std::vector<SegDesc>& segs, const Geom& g, const GNLayer& G, int relu,

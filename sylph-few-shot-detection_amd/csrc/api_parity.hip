@@ -13,6 +13,7 @@ int sylph_conv2d(sylph_ctx* c, const float* x, int B, int C, int H, int W, const
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
   sylph_ctx tmp;  // scratch allocations freed on return
   tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros;
+  tmp.prof = c->prof;  // profile + route records move to the caller's context below
   struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
   HostTensor hw;
   hw.shape = {Cout, C, KH, KW};
@@ -37,6 +38,7 @@ int sylph_conv2d(sylph_ctx* c, const float* x, int B, int C, int H, int W, const
   std::vector<OpFn> ops;
   RET(add_conv(&tmp, ops, L, xin, C, yout, Cout, image_segs(B, H, W, Ho, Wo), o));
   RET(run_ops(c, ops, "conv2d"));
+  adopt_records(c, &tmp);
   for (int b = 0; b < B; ++b)
     KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * Cout * Ho * Wo, Cout, Ho * Wo, b * Ho * Wo, Cout, c->stream),
          "export");
@@ -87,7 +89,7 @@ static int bottleneck_entry(sylph_ctx* c, const float* x, int B, int Cin, int H,
   if (!has_sc && (Cin != cout || stride != 1)) return fail("sylph_bottleneck: an identity block needs Cin == cout and stride 1");
   sylph_ctx tmp;  // scratch allocations freed on return
   tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros; tmp.cfg = c->cfg;
-  tmp.prof = c->prof;  // per-launch HIP-event timing (tools/bench_bottleneck.py): the records move to the caller's context below
+  tmp.prof = c->prof;  // per-launch HIP-event timing (tools/bench_bottleneck.py): the records (and route records) move to the caller's context below
   struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
   sylph_ctx::Block blk;
   const int cins[4] = {Cin, mid, mid, Cin}, couts[4] = {mid, mid, cout, cout}, ks[4] = {1, 3, 1, 1};
@@ -125,8 +127,7 @@ static int bottleneck_entry(sylph_ctx* c, const float* x, int B, int Cin, int H,
   BkScratch scr{t1, t2, sc, &trash};
   RET(add_bottleneck(&tmp, ops, blk, B, xin, Cin, H, W, stride, mid, cout, yout, scr));
   RET(run_ops(c, ops, "bottleneck"));
-  for (auto& r : tmp.prof_recs) c->prof_recs.push_back(r);
-  tmp.prof_recs.clear();
+  adopt_records(c, &tmp);
   for (int b = 0; b < B; ++b)
     KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * cout * Ho * Wo, cout, Ho * Wo, b * Ho * Wo, cout, c->stream), "export");
   return 0;
@@ -170,8 +171,7 @@ int sylph_group_conv(sylph_ctx* c, const float* x, int B, int C, int H, int W, i
   const double fl = 2.0 * (double)B * Ho * Wo * C * 9.0 * (C / groups);
   const DType dt = c->dt;
   KCHK(timed_op(&tmp, "conv_group_kernel", fl, c->stream, [=](hipStream_t st) { return launch_conv_group(dt, ga, st); }), "conv_group");
-  for (auto& r : tmp.prof_recs) c->prof_recs.push_back(r);
-  tmp.prof_recs.clear();
+  adopt_records(c, &tmp);
   for (int b = 0; b < B; ++b)
     KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * C * Ho * Wo, C, Ho * Wo, b * Ho * Wo, C, c->stream), "export");
   return 0;
@@ -185,6 +185,7 @@ int sylph_fpn_lateral(sylph_ctx* c, const float* x, int B, int C, int H, int W, 
   if (top && ((H & 1) || (W & 1))) return fail("sylph_fpn_lateral: the top-down input is half the size: H and W must be even");
   sylph_ctx tmp;  // scratch allocations freed on return
   tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros; tmp.cfg = c->cfg;
+  tmp.prof = c->prof;  // profile + route records move to the caller's context below
   struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
   HostTensor hw;
   hw.shape = {256, C, 1, 1};
@@ -211,6 +212,7 @@ int sylph_fpn_lateral(sylph_ctx* c, const float* x, int B, int C, int H, int W, 
   std::vector<OpFn> ops;
   RET(add_conv(&tmp, ops, L, xin, C, yout, 256, segs, o));
   RET(run_ops(c, ops, "fpn_lateral"));
+  adopt_records(c, &tmp);
   for (int b = 0; b < B; ++b)
     KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * 256 * H * W, 256, H * W, b * H * W, 256, c->stream), "export");
   return 0;

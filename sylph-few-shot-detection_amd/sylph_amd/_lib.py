@@ -89,6 +89,7 @@ PROTOTYPES = {
     "sylph_profile_read": (c_int, [c_void_p, POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(c_int64)]),
     "sylph_profile_read_kernels": (c_int, [c_void_p, c_int, ctypes.c_char_p, POINTER(ctypes.c_double), POINTER(ctypes.c_double),
                                            POINTER(c_int64), POINTER(c_int)]),
+    "sylph_conv_routes_read": (c_int, [c_void_p, c_int, ctypes.c_char_p, POINTER(c_int)]),
 }
 
 _LIB = None

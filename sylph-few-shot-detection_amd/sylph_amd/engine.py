@@ -697,3 +697,10 @@ class Engine:
             kern[names.raw[i * 64:(i + 1) * 64].split(b"\0", 1)[0].decode()] = {"ms": ms[i], "flops": fl[i], "launches": int(ln[i])}
         return {"conv_ms": sum(k["ms"] for k in kern.values()), "conv_flops": sum(k["flops"] for k in kern.values()),
                 "conv_launches": sum(k["launches"] for k in kern.values()), "kernels": kern}
+
+    def conv_routes(self, max_routes: int = 1024):
+        """The route of every conv launch built since the previous call while profiling was on, in build order (consumes them):
+        "<kind> <BM>x<BN>[ nbuf<n>][ ks<k>]", kind one of hpipe, igemm_halo, pw, spw, igemm_splitk, igemm."""
+        names, n = ctypes.create_string_buffer(max_routes * 64), c_int(0)
+        check(self.L.sylph_conv_routes_read(self._ctx, max_routes, names, ctypes.byref(n)), "conv_routes_read")
+        return [names.raw[i * 64:(i + 1) * 64].split(b"\0", 1)[0].decode() for i in range(n.value)]

@@ -30,6 +30,7 @@ import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+from bf16_ulps import assert_chain as _assert_chain, assert_ulps as _assert_ulps
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,33 +56,19 @@ def _cfg():
     return cfg
 
 
-def _ulps(got, want, floor="max"):
-    """(fraction of elements not bit-identical, worst difference in bf16 ulps).  The ulp of an element is taken at
-    max(|element|, floor) with floor = 1e-3 * max|want| ("max": single-conv kernels) or rms(want) ("rms": chains of convs
-    with bf16 intermediates; see the module docstring)."""
-    got, want = got.float().cpu(), want.float().cpu()
-    diff = (got - want).abs()
-    fl = 1e-3 * float(want.abs().max()) if floor == "max" else float(want.pow(2).mean().sqrt())
-    mag = torch.maximum(torch.maximum(got.abs(), want.abs()), torch.full_like(want, fl))
-    ulp = torch.exp2(torch.floor(torch.log2(mag)) - 7)
-    return float((diff > 0).float().mean()), float((diff / ulp).max())
+def _routing_overrides():
+    return sorted(k for k in os.environ if k.startswith(("SYLPH_CONV_", "SYLPH_SPLIT_", "SYLPH_FUSE_")))
 
 
-def _assert_ulps(got, want, what, max_ulp=1.0, max_frac=0.01, floor="max"):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    frac, worst = _ulps(got, want, floor)
-    print(f"{what}: {frac * 100:.3f} % of elements differ, worst {worst:.2f} bf16 ulp")
-    assert worst <= max_ulp and frac <= max_frac, f"{what}: {frac:.4f} of elements differ, worst {worst:.2f} ulp"
-
-
-def _assert_chain(got, want, what, max_ulp=16.0, max_rel_l2=2.0 ** -8):
-    """Chains of blocks (module docstring): error energy and worst element."""
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    frac, worst = _ulps(got, want, "rms")
-    g, w = got.float().cpu(), want.float().cpu()
-    rel = float((g - w).pow(2).sum().sqrt() / w.pow(2).sum().sqrt())
-    print(f"{what}: relative L2 error {rel:.2e}, {frac * 100:.1f} % of elements differ, worst {worst:.2f} bf16 ulp")
-    assert rel <= max_rel_l2 and worst <= max_ulp, f"{what}: relative L2 {rel:.3e}, worst {worst:.2f} ulp"
+def _assert_forms(eng, kernels, routes, what):
+    """The kernels that ran (profile records, in first-launch order) and the conv routes that were built (Engine.conv_routes(), in
+    build order) are the ones the case names.  Not asserted under the routing overrides of the forced-variant reruns
+    (tests/test_conv_variants_gpu.py), whose forms are the forced ones; the numbers are checked there all the same."""
+    got_k, got_r = list(eng.profile_read()["kernels"]), eng.conv_routes()
+    print(f"{what}: kernels {got_k}, conv routes {got_r}")
+    if _routing_overrides():
+        return
+    assert got_k == kernels and got_r == routes, f"{what}: expected kernels {kernels} / routes {routes}, ran {got_k} / {got_r}"
 
 
 def _assert_f32(got, want, what, rel=1e-4):
@@ -93,16 +80,28 @@ def _assert_f32(got, want, what, rel=1e-4):
 
 
 # ------------------------------------------------------------------------------------------------ towers + prediction passes
+TOWER_KERNELS = ["conv_hpipe_kernel<false>", "conv_hpipe_kernel<true>", "gn_taps_kernel+tap_gather_kernel", "gn_logits_kernel"]
+
+
 def test_tower_and_prediction_kernels_pinned_on_full_pyramid():
+    _tower_case(8)
+
+
+def test_tower_and_prediction_kernels_pinned_at_batch1():
+    _tower_case(1)
+
+
+def _tower_case(B):
     """conv_hpipe<false> (first tower layer, GroupNorm statistics in the epilogue), conv_hpipe<true> (layers 2-4: the previous
     layer's GroupNorm + ReLU applied to the input halo in LDS), gn_logits_kernel, gn_taps_kernel + tap_gather_kernel: ONE
     launch each over all five levels of eight 800x1344 pyramids (per-level patch shapes, the pair list, ragged last patches;
-    eight images so that the launch-size rule picks the same kernels as the B = 64 production step).
+    eight images so that the launch-size rule picks the same kernels as the B = 64 production step) -- and of ONE pyramid, the
+    batch-1 query (SylphPredictor): 94 blocks per tower layer, still on conv_hpipe (the >= 90-block rule).
     Every layer is checked on the operands the HIP graph itself produced (its stored input + its coefficient table)."""
     from oracle import bf16 as OB16
     from oracle.head import HEAD_PREFIX
     from sylph_amd import synthetic as Wt
-    B, N = 8, 5
+    N = 5
     sd = Wt.head_state_dict(seed=1, num_classes=60)
     g = torch.Generator().manual_seed(11)
     feats = [OB16.r(torch.randn(B, 256, h, w, generator=g)) for h, w in LEVELS]
@@ -110,8 +109,11 @@ def test_tower_and_prediction_kernels_pinned_on_full_pyramid():
     eng = _engine("bf16", _cfg())
     eng.load_state_dict(sd)
     eng.set_debug_taps(True)
+    eng.profile_enable(True)
     eng.import_pyramid(feats, (H, W))
     eng.head(codes["cls_conv"], codes["cls_bias"])
+    _assert_forms(eng, TOWER_KERNELS, ["hpipe 256x256"] * 8, f"towers at batch {B}")
+    eng.profile_enable(False)
     lo, rg, ct, io = eng.export_head()
     for t, name in ((0, "cls_tower"), (1, "bbox_tower")):
         x = feats
@@ -153,52 +155,89 @@ def _block_params(g, cin, mid, cout, shortcut):
     return ws, scales, shifts
 
 
+I64, I128, IH, HP = "igemm 64x128 nbuf2", "igemm 128x128", "igemm_halo 128x128", "hpipe 256x256"
+B1_64, B1_128, B1_128_2 = "igemm 64x64 nbuf3", "igemm 64x128 nbuf3", "igemm 64x128 nbuf2"
+PW, PW2, SPW = "pw 128x256", "pw 256x128", "spw 128x256"
+IG, RW3, SPWK, PWK = "conv_igemm_kernel", "conv_rw3_kernel", "conv_spw_kernel", "conv_pw_kernel"
+
 BLOCKS = [
-    # name, Cin, mid, cout, H, W, stride, shortcut, batch (large enough for the launch-size rules to pick the B = 64 kernels)
-    ("res2 identity (bottleneck64_kernel)", 256, 64, 256, 200, 336, 1, False, 2),
-    ("res2 first block (bottleneck64p_kernel)", 64, 64, 256, 200, 336, 1, True, 2),
-    ("res3 identity", 512, 128, 512, 100, 168, 1, False, 4),
-    ("res3 identity ragged map (conv_rw3 / conv_spw edge patches and partial tiles)", 512, 128, 512, 93, 157, 1, False, 4),
-    ("res3 first block (stride 2, conv3 + projection as one GEMM)", 256, 128, 512, 200, 336, 2, True, 4),
-    ("res4 identity (conv2 on conv_hpipe)", 1024, 256, 1024, 50, 84, 1, False, 32),
-    ("res5 first block", 1024, 512, 2048, 50, 84, 2, True, 16),
-    ("res5 identity", 2048, 512, 2048, 25, 42, 1, False, 32),
+    # name, Cin, mid, cout, H, W, stride, shortcut, batch (large enough for the launch-size rules to pick the B = 64 kernels),
+    # kernels that run (first-launch order), conv routes (conv1, conv2, conv3 [+ projection]; the fused / register-weight kernels
+    # build no conv route)
+    ("res2 identity (bottleneck64_kernel)", 256, 64, 256, 200, 336, 1, False, 2, ["bottleneck64_kernel"], []),
+    ("res2 first block (bottleneck64p_kernel)", 64, 64, 256, 200, 336, 1, True, 2, ["bottleneck64p_kernel"], []),
+    ("res3 identity", 512, 128, 512, 100, 168, 1, False, 4, [IG, RW3, SPWK], [I64, SPW]),
+    ("res3 identity ragged map (partial last tiles on conv_igemm: no conv_rw3 patch fits 93 x 157, 457 M tiles < conv_spw's 512;"
+     " the forced-variant reruns take it through both)", 512, 128, 512, 93, 157, 1, False, 4, [IG], [I64, I64, I128]),
+    ("res3 first block (stride 2, conv3 + projection as one GEMM)", 256, 128, 512, 200, 336, 2, True, 4, [PWK, RW3], [PW2, PW]),
+    ("res4 identity (conv2 on conv_hpipe)", 1024, 256, 1024, 50, 84, 1, False, 40, [PWK, "conv_hpipe_kernel<false>", SPWK], [PW, HP, SPW]),
+    ("res5 first block", 1024, 512, 2048, 50, 84, 2, True, 16, [PWK, "conv_hpipe_kernel<false>"], [PW, HP, PW]),
+    ("res5 identity", 2048, 512, 2048, 25, 42, 1, False, 32, [PWK, IG], [PW, IH, I128]),
 ]
+
+# The batch-1 query (SylphPredictor, the reference's per-image query loop) at the map sizes of one 800 x 1333 image: the small-launch
+# forms -- 64-row tiles, 64 x 64 tiles up to 160 64 x 128 tiles, three LDS stages up to 400 tiles.  (No block or lateral of one image
+# splits K: their launches have more than 64 tiles; tests/test_conv_routes_gpu.py pins split K with and without a residual.)
+BLOCKS_B1 = [
+    ("res3 identity", 512, 128, 512, 100, 168, 1, False, 1, [IG], [B1_128, B1_128, B1_128_2]),
+    ("res3 first block", 256, 128, 512, 200, 336, 2, True, 1, [IG, PWK], [B1_128, B1_128, PW]),
+    ("res4 first block", 512, 256, 1024, 100, 168, 2, True, 1, [IG], [B1_64, B1_64, B1_128_2]),
+    ("res4 identity", 1024, 256, 1024, 50, 84, 1, False, 1, [IG], [B1_64, B1_64, B1_128_2]),
+    ("res5 first block", 1024, 512, 2048, 50, 84, 2, True, 1, [IG], [B1_64, B1_64, B1_128]),
+    ("res5 identity", 2048, 512, 2048, 25, 42, 1, False, 1, [IG], [B1_64, B1_64, B1_128]),
+]
+
+
+def _run_block(case, what):
+    from oracle import bf16 as OB16
+    name, cin, mid, cout, h, w, stride, shortcut, B, kernels, routes = case
+    g = torch.Generator().manual_seed(cin + mid)
+    x = OB16.r(F.relu(torch.randn(B, cin, h, w, generator=g)))
+    ws, scales, shifts = _block_params(g, cin, mid, cout, shortcut)
+    eng = _engine("bf16")
+    eng.profile_enable(True)
+    y = eng.bottleneck(x, ws, scales, shifts, stride)
+    _assert_forms(eng, kernels, routes, what)
+    want = OB16.bottleneck(x, ws, scales, shifts, stride)
+    _assert_ulps(y, want, what, max_ulp=2.0, max_frac=0.03, floor="rms")
 
 
 @pytest.mark.parametrize("case", BLOCKS, ids=[c[0].split(" (")[0].replace(" ", "_") for c in BLOCKS])
 def test_bottleneck_blocks_pinned_at_production_shape(case):
     """One bottleneck block of every stage at its 800x1344 map size through the launches the backbone uses for it (the fused
     res2 kernels, the pointwise / halo / hpipe conv kernels) against the bf16-storage oracle on the same input."""
-    from oracle import bf16 as OB16
-    name, cin, mid, cout, h, w, stride, shortcut, B = case
-    g = torch.Generator().manual_seed(cin + mid)
-    x = OB16.r(F.relu(torch.randn(B, cin, h, w, generator=g)))
-    ws, scales, shifts = _block_params(g, cin, mid, cout, shortcut)
-    eng = _engine("bf16")
-    y = eng.bottleneck(x, ws, scales, shifts, stride)
-    want = OB16.bottleneck(x, ws, scales, shifts, stride)
-    _assert_ulps(y, want, name, max_ulp=2.0, max_frac=0.03, floor="rms")
+    _run_block(case, case[0])
 
 
-LATERALS = [("fpn_lateral5", 2048, 25, 42, False, 32), ("fpn_lateral4 (+ top-down)", 1024, 50, 84, True, 16),
-            ("fpn_lateral3 (+ top-down)", 512, 100, 168, True, 4)]
+@pytest.mark.parametrize("case", BLOCKS_B1, ids=[c[0].replace(" ", "_") for c in BLOCKS_B1])
+def test_bottleneck_blocks_pinned_at_batch1(case):
+    """The same blocks as one 800x1333 query image takes them (res3-res5), on the batch-1 conv forms; the bound of one block."""
+    _run_block(case, f"{case[0]} at batch 1")
 
 
-@pytest.mark.parametrize("case", LATERALS, ids=[c[0].split(" ")[0] for c in LATERALS])
+LATERALS = [("fpn_lateral5", 2048, 25, 42, False, 32, PWK, PW), ("fpn_lateral4 (+ top-down)", 1024, 50, 84, True, 16, PWK, PW),
+            ("fpn_lateral3 (+ top-down)", 512, 100, 168, True, 4, PWK, PW),
+            # batch 1 (one 800 x 1333 query image): conv_igemm's small-launch forms, the top-down add in its epilogue
+            ("fpn_lateral5 batch 1", 2048, 25, 42, False, 1, IG, B1_64), ("fpn_lateral4 batch 1 (+ top-down)", 1024, 50, 84, True, 1, IG, B1_64),
+            ("fpn_lateral3 batch 1 (+ top-down)", 512, 100, 168, True, 1, IG, B1_128_2)]
+
+
+@pytest.mark.parametrize("case", LATERALS, ids=[c[0].split(" (")[0].replace(" ", "_") for c in LATERALS])
 def test_fpn_laterals_pinned_at_production_shape(case):
     """conv_pw_kernel<128, 256, 3, RES, false> on the FPN laterals: RES = 0 (lateral5) and RES = 2 (lateral4 / 3: the nearest-2x
     upsampled level above added as a residual in the epilogue) at their 800x1344 map sizes, batches large enough for the production
-    kernel selection; one conv, no bf16 intermediate: <= 1 ulp."""
+    kernel selection -- and at batch 1 on conv_igemm's small-launch forms; one conv, no bf16 intermediate: <= 1 ulp."""
     from oracle import bf16 as OB16
-    name, cin, h, w, has_top, B = case
+    name, cin, h, w, has_top, B, kernel, route = case
     g = torch.Generator().manual_seed(cin)
     x = OB16.r(F.relu(torch.randn(B, cin, h, w, generator=g)))
     wt = torch.randn(256, cin, 1, 1, generator=g) * (1.0 / cin) ** 0.5
     bias = 0.2 * torch.randn(256, generator=g)
     top = OB16.r(torch.randn(B, 256, h // 2, w // 2, generator=g)) if has_top else None
     eng = _engine("bf16")
+    eng.profile_enable(True)
     y = eng.fpn_lateral(x, wt, bias, top)
+    _assert_forms(eng, [kernel], [route], name)
     res = F.interpolate(top, scale_factor=2.0, mode="nearest") if has_top else None
     _, want = OB16.conv_epilogue(x, wt, None, bias, res_bf=res)
     _assert_ulps(y, want, name)

@@ -78,14 +78,20 @@ def test_conv2d_matches_torch(dtype, case):
     eng = _engine(dtype)
     y = eng.conv2d(x, w, scale, shift, stride, pad, relu, res).cpu()
     if dtype == "bf16":
+        # bf16 operands are exact and the sums fp32: one output rounding is the only legitimate error.  Against float64 rounded once
+        # (RNE): <= 1 bf16 ulp, <= 1 % of elements not identical (tests/test_bf16_pinned_gpu.py) -- also in every forced-variant rerun
+        # of this test (tests/test_conv_variants_gpu.py), so each forced kernel form is held to it
+        from bf16_ulps import assert_ulps, bf16_rne, conv_epilogue_f64
         x, w = _bf16_round(x), _bf16_round(w)
         res = _bf16_round(res) if res is not None else None
+        assert_ulps(y, bf16_rne(conv_epilogue_f64(x, w, scale, shift, stride, pad, relu, res)), f"conv2d {case}")
+        return
     ref = F.conv2d(x, w, None, stride, pad) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
     if res is not None:
         ref = ref + res
     if relu:
         ref = F.relu(ref)
-    tol = _f32_tol(2e-5, 6e-5) if dtype == "f32" else 2e-2
+    tol = _f32_tol(2e-5, 6e-5)
     err = (y - ref).abs().max().item()
     assert err <= tol * max(1.0, ref.abs().max().item()), f"max err {err}"
 
