@@ -13,8 +13,12 @@ reported separately (it is amortised over all queries of an episode, SURVEY.md 8
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (the MFMA
-implicit-GEMM conv kernel, timed with HIP events on its launch stream inside the timed region) and
-`cpu_baseline` (the CPU oracle = fp32 torch restatement of the reference, timed on the host cores).
+implicit-GEMM conv kernel, timed with HIP events on its launch stream inside the timed region).  A plain
+run stops there: set-up, warm-up, timed steps, --dump-outputs, the line.  With --full the line also
+carries what takes runs of its own after the timed region: the backbone / head roofline split, the
+batch-size sweep and the other precisions, sizes and BASELINE configurations, `parity_bf16` against the
+CPU oracle, `roofline.traffic` from rocprofv3 --pmc child runs, and `cpu_baseline` (the CPU oracle =
+fp32 torch restatement of the reference, timed on the host cores).
 """
 import argparse
 import json
@@ -73,15 +77,19 @@ def main():
     ap.add_argument("--code-scale", type=float, default=3.0,
                     help="multiplier on the normalised class codes so the random-weight detector fires (SURVEY 8d)")
     ap.add_argument("--inflight", type=int, default=2, help="query steps enqueued before the oldest one's counts are read back")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every untimed extra leg (roofline split, sweeps, other precisions and "
+                         "configurations, oracle parity, live PMC traffic, CPU baseline); the --no-* options below skip single legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="do not bracket conv launches with HIP events (roofline fields become 0)")
     ap.add_argument("--cpu-images", type=int, default=3)
-    ap.add_argument("--no-sweep", action="store_true", help="skip the untimed batch-size sweep / fp32 legs")
-    ap.add_argument("--no-parity", action="store_true", help="skip the bf16-vs-oracle agreement leg")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: skip the untimed batch-size sweep / fp32 legs")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the bf16-vs-oracle agreement leg")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="do not collect roofline.traffic in this run (two rocprofv3 --pmc passes of a short child run of this script); "
-                         "the committed profiles/r6_pmc_hbm_traffic.json is used instead if its source fingerprint matches")
+                    help="with --full: do not collect roofline.traffic in this run (two rocprofv3 --pmc passes of a short child run of this "
+                         "script); the committed profiles/r6_pmc_hbm_traffic.json is used instead if its source fingerprint matches, "
+                         "as in every plain run")
     ap.add_argument("--dump-codes", default=None, help="rank 0 writes the gathered, normalised class codes (N x 257) to this .pt file (tests)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="rank 0 writes the detections of the last timed step to DIR/<field>.npy (see dump_outputs): with the same arguments "
@@ -207,9 +215,9 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(dets, args.dump_outputs, max_rows=eng.default_max_out())
     # Split of the conv time into backbone+FPN and head (BASELINE's second metric: "backbone MFMA %peak"): three
-    # extra UNTIMED, unpipelined steps with a sync between the two stages (the split needs a readback per stage).
+    # extra UNTIMED, unpipelined steps with a sync between the two stages (the split needs a readback per stage); --full only.
     split = {"backbone_ms": 0.0, "backbone_flops": 0.0, "head_ms": 0.0, "head_flops": 0.0}
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         for _ in range(3):
             eng.preprocess(queries)
             eng.backbone()
@@ -221,9 +229,10 @@ def main():
             split["backbone_ms"] += p1["conv_ms"]; split["backbone_flops"] += p1["conv_flops"]
             split["head_ms"] += p2["conv_ms"]; split["head_flops"] += p2["conv_flops"]
     eng.profile_enable(False)
-    # ---- untimed extra legs (rank 0, one GPU): batch-size sweep in the reference protocol, fp32 mode, bf16 agreement ----
+    # ---- untimed extra legs (--full; rank 0, one GPU): batch-size sweep in the reference protocol, fp32 mode, bf16 agreement ----
+    extras = args.full and rank == 0 and world == 1
     sweep, fp32_img_s, parity_mode_img_s, parity, host_u8_img_s, large_batch = None, None, None, None, None, None
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if extras and not args.no_sweep:
         sweep = {}
         for b in (1, 8, 16, 64, 96, 120):
             if b == B:
@@ -312,7 +321,7 @@ def main():
         fp32_img_s = mode_leg("f32", 64, 3)
         parity_mode_img_s = mode_leg("f32s", 64, 4)  # 64 per step: 522 / 560 / 571 / 580 / 585 img/s at 8 / 16 / 32 / 48 / 64 (one box)
     support_leg = None
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if extras and not args.no_sweep:
         # steady-state SUPPORT path: classes x shots support images of 800x1333 per batch through preprocess ->
         # ResNet-FPN -> ROIAlign -> code-generator tower -> per-class codes (sylph_codegen_classes), after one warm-up batch
         support_leg = {"unit": "support images/s", "image": [H, Wd], "note": "batched classes share the launches; codes per class as in the one-class-per-call path"}
@@ -342,7 +351,7 @@ def main():
         torch.cuda.synchronize()
         support_leg["S5_one_class_per_call"] = round(50 / (time.perf_counter() - ts), 1)
     many_way = None
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if extras and not args.no_sweep:
         # many-way episodes on the same backbone (BASELINE configs[2] / [3] head loads: 20 and 866 classes, 16 query images per step,
         # synchronous steps): the class-conditional conv + score scan are one kernel there (logits_scan_kernel), top-k by histogram
         many_way = {"unit": "images/s", "batch": 16, "code_scale": 1.5,
@@ -369,10 +378,10 @@ def main():
             many_way[f"N{nway}"] = round(16 * 8 / (time.perf_counter() - ts), 1)
         eng_m.close()
     config_legs = None
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if extras and not args.no_sweep:
         eng.close()  # the headline engine's plans (about 10 GB) are not needed any more
         config_legs = baseline_config_legs(args, device, local_rank)
-    if rank == 0 and world == 1 and not args.no_parity:
+    if extras and not args.no_parity:
         parity = parity_bf16(sd, queries[:2], cls_conv, cls_bias, dets[:2])
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -388,7 +397,7 @@ def main():
         images_timed = B * args.steps
         alg_flops = GFLOP_PER_IMAGE_MFMA_CONV * 1e9 * images_timed  # all conv launches of the region, this rank
         achieved = alg_flops / conv_s / 1e12 if conv_s > 0 else 0.0
-        if not args.no_live_pmc and world == 1 and args.dtype == "bf16":
+        if extras and not args.no_live_pmc and args.dtype == "bf16":
             collect_live_pmc(B)  # two short rocprofv3 --pmc passes of this command, after the timed region (N = 1 only)
         traffic, traffic_src = pmc_traffic_per_launch(B, launches // max(args.steps, 1))
         roofline = {
@@ -462,7 +471,7 @@ def main():
             out.update(config_legs)
         if parity is not None:
             out["parity_bf16"] = parity
-        if world == 1 and not args.no_cpu_baseline:
+        if extras and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd, queries, cls_conv, cls_bias, args.cpu_images)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -611,8 +620,7 @@ def collect_live_pmc(batch):
         return
     tmp = tempfile.mkdtemp(prefix="sylph_pmc_", dir="/tmp")
     env = dict(os.environ, SYLPH_BENCH_PMC_CHILD="1", TMPDIR="/tmp")
-    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(batch), "--steps", "2", "--warmup", "2", "--no-cpu-baseline",
-             "--no-kernel-events", "--no-sweep", "--no-parity", "--no-live-pmc"]
+    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(batch), "--steps", "2", "--warmup", "2", "--no-kernel-events"]
     try:
         for counter, tag in (("FETCH_SIZE", "f"), ("WRITE_SIZE", "w")):
             r = subprocess.run(["rocprofv3", "--pmc", counter, "--kernel-trace", "-d", os.path.join(tmp, tag), "-o", tag, "--"] + child,

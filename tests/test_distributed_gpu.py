@@ -246,6 +246,27 @@ def test_bench_dump_outputs_are_repeatable(tmp_path):
         assert (dirs[0] / nm).read_bytes() == (dirs[1] / nm).read_bytes(), f"{nm} differs between two identical runs"
 
 
+def test_bench_plain_run_is_headline_only_and_full_adds_the_legs():
+    """A plain bench.py run carries the headline and the timed region's roofline only; --full adds the untimed legs after it (here the
+    backbone / head roofline split, oracle parity and the CPU baseline: --no-sweep keeps the full-size sweep and configuration legs out)."""
+    import json
+    base = [sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "2", "--height", "128", "--width", "160", "--dtype", "f32"]
+    outs = []
+    for extra in ((), ("--full", "--no-sweep", "--cpu-images", "1")):
+        r = subprocess.run(base + list(extra), cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        outs.append(json.loads(lines[0]))
+    plain, full = outs
+    for out in outs:
+        assert out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 0 and out["roofline"]["launches"] > 0
+    assert not {"parity_bf16", "cpu_baseline", "sweep", "support_path", "many_way"} & set(plain)
+    assert "backbone_fpn" not in plain["roofline"] and "head" not in plain["roofline"]
+    assert full["parity_bf16"]["images"] == 2 and full["cpu_baseline"]["value"] > 0
+    assert full["roofline"]["backbone_fpn"]["achieved"] > 0 and full["roofline"]["head"]["achieved"] > 0
+
+
 _EPISODE_GATHER_SCRIPT = r"""
 import os, sys
 root = %(root)r
