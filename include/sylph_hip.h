@@ -246,6 +246,33 @@ int sylph_set_debug_taps(sylph_ctx* ctx, int on);
 int sylph_export_stage(sylph_ctx* ctx, int stage, float* out_nchw_dev);
 int sylph_export_tower(sylph_ctx* ctx, int tower, int layer, int level, float* y_nchw_dev, float* coef_dev);
 
+/* Support-path taps: the output of one stage of the last sylph_codegen / sylph_codegen_classes call on the current batch (S support
+ * images, 49 ROI positions).  ROI, CONV_OUT and CONTEXT, the GroupNorm coefficients and the class tokens are always kept; the other
+ * stages need sylph_set_debug_taps(1) before the first code-generator call of a batch shape, which copies each of them aside right
+ * after the launch that writes it (same kernels and launches).  `index` numbers the layers of a stage:
+ *   SYLPH_SUP_ROI          0: ROIAlign output, (S,256,7,7)
+ *   SYLPH_SUP_GN_Y         GroupNorm layer: the conv output stored BEFORE its GroupNorm, (S,256,7,7)
+ *   SYLPH_SUP_GN_COEF      GroupNorm layer: (a, b) per (image, channel) of its apply y = act(a * x + b), (S,256,2)
+ *   SYLPH_SUP_LAYER_OUT    layer output after its GroupNorm and activation, (S,256,7,7)
+ *   SYLPH_SUP_CONV_OUT     0: cls conv, (S,256,7,7); 1: the stacked 1-channel heads (bias, shot weight, class scale), (S,naux,7,7)
+ *   SYLPH_SUP_CONTEXT      0: ROIEncoder context, (S,256,7,7)
+ *   SYLPH_SUP_MSCAM        0: ROIEncoder box_pooler output after the MS-CAM gate, (S,256,7,7)
+ *   SYLPH_SUP_TOKENS       0: tokens after the tokenizer FC stack, 1 + l: after encoder layer l, (S,256)
+ *   SYLPH_SUP_CLS_TOKENS   0: class tokens (mean over the shots), (classes,256)
+ * Layers: the code generator's tower layer i is index i; the ROIEncoder's box_pooler conv is 0 and tokenizer conv k is 1 + k.
+ * All fp32 (maps NCHW).  sylph_support_tap_numel gives the element count of a tap; sylph_export_support writes it to out_dev. */
+#define SYLPH_SUP_ROI 0
+#define SYLPH_SUP_GN_Y 1
+#define SYLPH_SUP_GN_COEF 2
+#define SYLPH_SUP_LAYER_OUT 3
+#define SYLPH_SUP_CONV_OUT 4
+#define SYLPH_SUP_CONTEXT 5
+#define SYLPH_SUP_MSCAM 6
+#define SYLPH_SUP_TOKENS 7
+#define SYLPH_SUP_CLS_TOKENS 8
+int sylph_support_tap_numel(sylph_ctx* ctx, int stage, int index, int64_t* numel);
+int sylph_export_support(sylph_ctx* ctx, int stage, int index, float* out_dev);
+
 /* Kernel parity entry: ONE detectron2 BottleneckBlock (1x1 -> 3x3 -> 1x1, FrozenBN folded to scale/shift, identity or
  * projection shortcut, ReLU) through the same launches sylph_backbone_fpn uses for such a block (fused kernels included).
  * x (B,Cin,H,W) fp32 NCHW device; w_host[4] = conv1 (mid,Cin,1,1), conv2 (mid,mid,3,3), conv3 (cout,mid,1,1), shortcut

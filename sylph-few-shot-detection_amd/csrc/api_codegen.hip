@@ -4,6 +4,42 @@
 
 namespace sylph_host {
 
+// Parity taps of the support path (sylph_export_support).  A stage that no later op overwrites is recorded where it is; with debug taps
+// on, the others are copied aside by a device-to-device copy right after the op that writes them: the kernels and their launches are
+// the same with and without taps.  n = images (npos = 49: [n * 49][ld] maps) or rows (npos = 1); n = 0: the classes of the last call.
+static void tap_at(Plan* P, int stage, int index, const void* p, bool f32, int n, int npos, int C = 256, int ld = 256) {
+  Plan::SupTap t;
+  t.p = p; t.f32 = f32; t.n = n; t.npos = npos; t.C = C; t.ld = ld;
+  P->sup_taps[{stage, index}] = t;
+}
+
+static int tap_copy(sylph_ctx* c, Plan* P, std::vector<OpFn>& ops, int stage, int index, const void* src, bool f32, int n, int npos) {
+  if (!c->debug_taps) return 0;
+  const size_t bytes = (size_t)n * npos * 256 * (f32 ? 4 : c->esz());
+  void* dst = nullptr;
+  RET(c->dalloc(&dst, bytes));
+  ops.push_back([=](hipStream_t s) { return (int)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s); });
+  tap_at(P, stage, index, dst, f32, n, npos);
+  return 0;
+}
+
+// add_conv_gn of a support layer (7x7 maps, applied in place) with its taps: the stored pre-GroupNorm output, the statistics of the
+// apply, the applied output
+static int support_conv_gn(sylph_ctx* c, Plan* P, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, void* out,
+                           const std::vector<SegDesc>& segs, ConvOpts o, const GNLayer& G, int relu, int layer) {
+  const int S = P->B;
+  o.want_gn = 1;
+  Geom g;
+  RET(add_conv(c, ops, L, in, 256, out, L.Cout, segs, o, &g));
+  RET(tap_copy(c, P, ops, SYLPH_SUP_GN_Y, layer, out, false, S, 49));
+  const float2* stats = nullptr;
+  RET(add_gn_from_partials(c, ops, out, L.Cout, segs, g, G, relu, nullptr, nullptr, &stats));
+  Plan::SupTap t;
+  t.n = S; t.npos = 1; t.stats = stats; t.gamma = G.gamma; t.beta = G.beta;
+  P->sup_taps[{SYLPH_SUP_GN_COEF, layer}] = t;
+  return tap_copy(c, P, ops, SYLPH_SUP_LAYER_OUT, layer, out, false, S, 49);
+}
+
 int build_support(sylph_ctx* c, Plan* P) {
   if (P->support_built) return 0;
   if (!c->has_codegen) return fail("code generator weights were not loaded");
@@ -36,6 +72,7 @@ int build_support(sylph_ctx* c, Plan* P) {
     void* roi = P->roi;
     ops.push_back([=](hipStream_t s) { return launch_roi_align(dt, F, 256, lvd, L, PP->cur_boxes, S, 7, roi, s); });
   }
+  tap_at(P, SYLPH_SUP_ROI, 0, P->roi, false, S, npos);
   const void* in = P->roi;
   void* out = P->cgA;
   for (size_t i = 0; i < c->cg_tower.size(); ++i) {
@@ -43,10 +80,11 @@ int build_support(sylph_ctx* c, Plan* P) {
     const bool gn = (c->cfg.cg_tower_gn_mask >> i) & 1, relu = (c->cfg.cg_tower_relu_mask >> i) & 1;
     ConvOpts o; o.pad = 1;
     if (gn) {
-      RET(add_conv_gn(c, ops, c->cg_tower[i], in, 256, out, segs, o, c->cg_gn[i], relu ? 1 : 0));
+      RET(support_conv_gn(c, P, ops, c->cg_tower[i], in, out, segs, o, c->cg_gn[i], relu ? 1 : 0, (int)i));
     } else {
       if (relu) o.relu_nch = 1 << 30;
       RET(add_conv(c, ops, c->cg_tower[i], in, 256, out, 256, segs, o));
+      RET(tap_copy(c, P, ops, SYLPH_SUP_LAYER_OUT, (int)i, out, false, S, npos));
     }
     in = out;
     out = (out == P->cgA) ? P->cgB : P->cgA;
@@ -55,6 +93,8 @@ int build_support(sylph_ctx* c, Plan* P) {
   RET(add_conv(c, ops, c->cg_cls, in, 256, P->cg_conv_out, 256, segs, oc));
   const int naux = c->cg_naux;
   if (naux > 0) RET(add_conv(c, ops, c->cg_bias, in, 256, P->cg_bias_out, naux, segs, oc));
+  tap_at(P, SYLPH_SUP_CONV_OUT, 0, P->cg_conv_out, true, S, npos);
+  if (naux > 0) tap_at(P, SYLPH_SUP_CONV_OUT, 1, P->cg_bias_out, true, S, npos, naux, naux);
   {
     const float *co = P->cg_conv_out, *bo = P->cg_bias_out;
     const int l2 = c->cfg.cg_bias_l2_norm, ib = c->cg_ib, iw = c->cg_iw, is = c->cg_is;
@@ -108,18 +148,22 @@ int build_support_roienc(sylph_ctx* c, Plan* P) {
     ops.push_back([=](hipStream_t s) { return launch_roi_align(dt, F, 256, lvd, L, PP->cur_boxes, S, 7, roi, s); });
     ops.push_back([=](hipStream_t s) { return launch_adaptive_context(dt, F, 256, lvd, L, S, 7, ctx, s); });
   }
+  tap_at(P, SYLPH_SUP_ROI, 0, P->roi, false, S, npos);
+  tap_at(P, SYLPH_SUP_CONTEXT, 0, P->re_ctx, true, S, npos);
+  // GroupNorm layers: 0 = box_pooler, 1 + k = tokenizer conv k
   ConvOpts o; o.pad = 1;
-  RET(add_conv_gn(c, ops, R.pool_conv, P->roi, 256, P->cgA, segs, o, R.pool_gn, 1));
+  RET(support_conv_gn(c, P, ops, R.pool_conv, P->roi, P->cgA, segs, o, R.pool_gn, 1, 0));
   {
     const float* ctx = P->re_ctx;
     void* x = P->cgA;
     const MsCamWeights w = R.cam;
     ops.push_back([=](hipStream_t s) { return launch_mscam(dt, ctx, x, S, w, s); });
   }
+  RET(tap_copy(c, P, ops, SYLPH_SUP_MSCAM, 0, P->cgA, false, S, npos));
   void* cur = P->cgA;
   void* nxt = P->cgB;
   for (size_t k = 0; k < R.tok_conv.size(); ++k) {
-    RET(add_conv_gn(c, ops, R.tok_conv[k], cur, 256, nxt, segs, o, R.tok_gn[k], 1));
+    RET(support_conv_gn(c, P, ops, R.tok_conv[k], cur, nxt, segs, o, R.tok_gn[k], 1, 1 + (int)k));
     std::swap(cur, nxt);
   }
   // tokenizer FC stack: first FC reads the (position-major) activations directly
@@ -140,6 +184,8 @@ int build_support_roienc(sylph_ctx* c, Plan* P) {
     tok = a;
     tmp = b;
   }
+  RET(tap_copy(c, P, ops, SYLPH_SUP_TOKENS, 0, tok, true, S, 1));
+  int layer = 0;
   for (auto& l : R.layers) {
     const sylph_ctx::Lin at = l.attn, l1 = l.l1, l2 = l.l2;
     const GNLayer n1 = l.n1, n2 = l.n2;
@@ -149,7 +195,9 @@ int build_support_roienc(sylph_ctx* c, Plan* P) {
     ops.push_back([=](hipStream_t s) { return launch_linear(0, x, 256, S, l1.W, l1.b, l1.K, l1.O, hid, l1.O, 1, 0.f, s); });
     ops.push_back([=](hipStream_t s) { return launch_linear(0, hid, l1.O, S, l2.W, l2.b, l2.K, l2.O, t, 256, 0, 0.f, s); });
     ops.push_back([=](hipStream_t s) { return launch_add_layernorm(x, t, S, n2.gamma, n2.beta, s); });
+    RET(tap_copy(c, P, ops, SYLPH_SUP_TOKENS, ++layer, tok, true, S, 1));
   }
+  tap_at(P, SYLPH_SUP_CLS_TOKENS, 0, P->re_cls, true, 0, 1);
   {
     float* cls = P->re_cls;
     float* x = tok;
@@ -203,6 +251,60 @@ int sylph_roi_align(sylph_ctx* c, const float* boxes, float* out) {
   KCHK(launch_roi_align(c->dt, P->F, 256, lvd, L, boxes, S, 7, roi, c->stream), "roi_align");
   for (int s = 0; s < S; ++s)
     KCHK(launch_export_nchw(c->dt, roi, out + (size_t)s * 256 * 49, 256, 49, s * 49, 256, c->stream), "export roi");
+  return 0;
+}
+
+static int support_tap(sylph_ctx* c, int stage, int index, const Plan::SupTap** t, int* n) {
+  Plan* P = c->cur;
+  if (!P || !P->support_built) return fail("no code-generator pass on the current batch");
+  auto it = P->sup_taps.find({stage, index});
+  if (it == P->sup_taps.end())
+    return fail("support tap (" + std::to_string(stage) + ", " + std::to_string(index) + ") does not exist in this configuration" +
+                (c->debug_taps ? "" : " (intermediate stages need sylph_set_debug_taps(1) before the first code-generator call of a batch shape)"));
+  *t = &it->second;
+  *n = it->second.n > 0 ? it->second.n : P->B / (P->cur_shots > 0 ? P->cur_shots : P->B);
+  return 0;
+}
+
+int sylph_support_tap_numel(sylph_ctx* c, int stage, int index, int64_t* numel) {
+  const Plan::SupTap* t;
+  int n;
+  RET(support_tap(c, stage, index, &t, &n));
+  *numel = t->stats ? (int64_t)n * 512 : (int64_t)n * t->C * t->npos;
+  return 0;
+}
+
+int sylph_export_support(sylph_ctx* c, int stage, int index, float* out) {
+  const Plan::SupTap* t;
+  int n;
+  RET(support_tap(c, stage, index, &t, &n));
+  if (!out) return fail("NULL argument");
+  HIPCHK(hipSetDevice(c->device));
+  if (t->stats) {  // (a, b) = (rstd * gamma, fma(-mean, a, beta)) per (image, channel), as gn_apply_partials_kernel forms them (contracted)
+    std::vector<float2> st((size_t)n * 32);
+    std::vector<float> ga(256), be(256), ab((size_t)n * 512);
+    HIPCHK(hipMemcpyAsync(st.data(), t->stats, st.size() * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(ga.data(), t->gamma, 256 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(be.data(), t->beta, 256 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int s = 0; s < n; ++s)
+      for (int ch = 0; ch < 256; ++ch) {
+        const float2 v = st[(size_t)s * 32 + ch / 8];
+        const float a = v.y * ga[ch];
+        ab[((size_t)s * 256 + ch) * 2] = a;
+        ab[((size_t)s * 256 + ch) * 2 + 1] = fmaf(-v.x, a, be[ch]);
+      }
+    HIPCHK(hipMemcpyAsync(out, ab.data(), ab.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+  }
+  if (t->npos == 1) {  // fp32 rows
+    HIPCHK(hipMemcpy2DAsync(out, (size_t)t->C * 4, t->p, (size_t)t->ld * 4, (size_t)t->C * 4, n, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  }
+  const DType dt = t->f32 ? DT_F32 : c->dt;
+  for (int s = 0; s < n; ++s)
+    KCHK(launch_export_nchw(dt, t->p, out + (size_t)s * t->C * t->npos, t->C, t->npos, s * t->npos, t->ld, c->stream), "export support");
   return 0;
 }
 

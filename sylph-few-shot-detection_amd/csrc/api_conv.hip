@@ -485,8 +485,9 @@ int add_conv_gn(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const 
 
 // the GroupNorm of a conv whose epilogue left per-M-tile partials in g.gn_partial (conv_igemm / conv_hpipe / conv_deform): finalize +
 // in-place apply, or (coef_out) the (a, b) table for the next consumer and optionally (apply_out) the stand-alone apply
+// (stats_out: where the finalize leaves (mean, rstd) per (segment, group) -- the parity taps of the support path)
 int add_gn_from_partials(sylph_ctx* c, std::vector<OpFn>& ops, void* out, int ld, const std::vector<SegDesc>& segs, const Geom& g, const GNLayer& G, int relu,
-                         const float2** coef_out, OpFn* apply_out) {
+                         const float2** coef_out, OpFn* apply_out, const float2** stats_out) {
   const int ngroups = ld / 8;
   const float* partial = g.gn_partial;
   std::vector<GnSeg> gs;
@@ -503,6 +504,7 @@ int add_gn_from_partials(sylph_ctx* c, std::vector<OpFn>& ops, void* out, int ld
   const float *ga = G.gamma, *be = G.beta;
   float2* stats_ws = nullptr;
   RET(c->dalloc((void**)&stats_ws, (size_t)nseg * ngroups * sizeof(float2)));
+  if (stats_out) *stats_out = stats_ws;
   if (coef_out) {
     float2* coef = nullptr;
     RET(c->dalloc((void**)&coef, (size_t)nseg * ld * sizeof(float2)));

@@ -248,6 +248,16 @@ struct Plan {
   void *roi = nullptr, *cgA = nullptr, *cgB = nullptr;
   float *cg_conv_out = nullptr, *cg_bias_out = nullptr, *cg_wnorm = nullptr;  // cg_wnorm: cls_weight_norm per class of the last call
   float *re_ctx = nullptr, *re_tok = nullptr, *re_tmp = nullptr, *re_hid = nullptr, *re_cls = nullptr, *re_h = nullptr;
+  // support-path taps (sylph_export_support): (stage, index) -> where that stage's output of the last support pass lives; the stages
+  // whose buffer a later op overwrites are copied aside, only with debug taps on
+  struct SupTap {
+    const void* p = nullptr;
+    bool f32 = true;  // fp32 buffer (else the context's storage type)
+    int n = 0, npos = 49, C = 256, ld = 256;  // [n * npos][ld], first C channels (see api_codegen.hip tap_at)
+    const float2* stats = nullptr;  // GroupNorm (mean, rstd) per (image, group) of the in-place apply, with its gamma / beta
+    const float *gamma = nullptr, *beta = nullptr;
+  };
+  std::map<std::pair<int, int>, SupTap> sup_taps;
   const float* cur_boxes = nullptr;
   int cur_shots = 0;  // support images per class of the current sylph_codegen[_classes] call (B = classes x shots)
   float* cur_code_out = nullptr;
@@ -339,7 +349,7 @@ void adopt_records(sylph_ctx* c, sylph_ctx* tmp);  // parity entries: move a scr
 int add_conv(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, int in_ld, void* out, int out_ld, const std::vector<SegDesc>& segs, const ConvOpts& o, Geom* geom_out = nullptr);
 int add_conv_gn(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, int in_ld, void* out, const std::vector<SegDesc>& segs, ConvOpts o, const GNLayer& G, int relu, const float2** coef_out = nullptr, OpFn* apply_out = nullptr);
 int add_gn_from_partials(sylph_ctx* c, std::vector<OpFn>& ops, void* out, int ld, const std::vector<SegDesc>& segs, const Geom& g, const GNLayer& G, int relu,
-                         const float2** coef_out, OpFn* apply_out);
+                         const float2** coef_out, OpFn* apply_out, const float2** stats_out = nullptr);
 int add_conv_deform(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& off, const ConvLayer& L, const void* in, void* out,
                     const std::vector<SegDesc>& segs, int segs_per_image, const GNLayer* G, int relu, const float2** coef_out = nullptr,
                     OpFn* apply_out = nullptr);

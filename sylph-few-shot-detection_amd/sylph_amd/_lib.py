@@ -73,6 +73,8 @@ PROTOTYPES = {
     "sylph_set_debug_taps": (c_int, [c_void_p, c_int]),
     "sylph_export_stage": (c_int, [c_void_p, c_int, c_void_p]),
     "sylph_export_tower": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sylph_support_tap_numel": (c_int, [c_void_p, c_int, c_int, POINTER(c_int64)]),
+    "sylph_export_support": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "sylph_bottleneck": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p),
                                  POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
     "sylph_allgather_codes": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -616,6 +616,24 @@ class Engine:
             ys.append(y); cs.append(cf)
         return ys, cs
 
+    SUPPORT_STAGES = ("roi", "gn_y", "gn_coef", "layer_out", "conv_out", "context", "mscam", "tokens", "cls_tokens")
+
+    def export_support(self, stage: str, index: int = 0) -> torch.Tensor:
+        """One stage output of the last codegen / codegen_classes call (sylph_export_support; stage names as SUPPORT_STAGES, in the
+        order of the SYLPH_SUP_* constants): maps (S, C, 7, 7), GroupNorm coefficients (S, 256, 2), tokens (rows, 256), fp32."""
+        self._stream()
+        st = self.SUPPORT_STAGES.index(stage)
+        n = c_int64(0)
+        check(self.L.sylph_support_tap_numel(self._ctx, st, int(index), ctypes.byref(n)), "support_tap_numel")
+        out = torch.empty(n.value, device=self.device)
+        check(self.L.sylph_export_support(self._ctx, st, int(index), _ptr(out)), "export_support")
+        B = self._batch[0]
+        if stage == "gn_coef":
+            return out.view(B, 256, 2)
+        if stage in ("tokens", "cls_tokens"):
+            return out.view(-1, 256)
+        return out.view(B, -1, 7, 7)
+
     def bottleneck(self, x, ws, scales, shifts, stride=1):
         """One ResNet bottleneck block through the backbone's own launches.  ws / scales / shifts: conv1, conv2, conv3,
         shortcut (or None) weights and folded FrozenBN scale / shift."""

@@ -19,17 +19,20 @@ import torch
 
 
 # ------------------------------------------------------------------------------------------------ ROIAlignV2
-def _axis_weights(lo: float, length: float, size: int, out: int = 7) -> np.ndarray:
+def _axis_weights(lo: float, length: float, size: int, out: int = 7, f32_coords: bool = False) -> np.ndarray:
     """[out x size] float64: row p = average over the bin's sample points of the 1-D linear-interpolation weights.
-    `lo`, `length`: start and extent of the box on this axis in FEATURE coordinates (already scaled and shifted by -0.5)."""
-    bin_sz = length / out
+    `lo`, `length`: start and extent of the box on this axis in FEATURE coordinates (already scaled and shifted by -0.5).
+    f32_coords: the bin size and the sample coordinates are computed in fp32, operation by operation, as the operator does for fp32
+    inputs (torchvision roi_align with T = float: lo + p * bin + (i + 0.5) * bin / grid); the weights and sums stay float64."""
+    f = np.float32 if f32_coords else float
+    bin_sz = f(f(length) / f(out))
     grid = int(math.ceil(bin_sz))  # adaptive sampling ratio (sampling_ratio = 0)
     A = np.zeros((out, size), dtype=np.float64)
     if grid <= 0:
         return A  # no samples: the pooled value is 0 / max(count, 1) = 0
     for p in range(out):
         for i in range(grid):
-            c = lo + p * bin_sz + (i + 0.5) * bin_sz / grid
+            c = float(f(f(f(lo) + f(p) * bin_sz) + f(f(i) + f(0.5)) * bin_sz / f(grid)))
             if c < -1.0 or c > size:
                 continue  # the whole sample is zero
             c = max(c, 0.0)
@@ -52,18 +55,22 @@ def level_of_box(box, min_level=3, max_level=7, canonical_size=224.0, canonical_
     return int(min(max(lvl, min_level), max_level))
 
 
-def roi_pool_separable_f64(features, boxes, strides=(8, 16, 32, 64, 128), out: int = 7) -> np.ndarray:
-    """features[l]: (S, C, h_l, w_l) arrays; boxes (S, 4) xyxy image pixels, box i on image i -> (S, C, out, out) float64."""
+def roi_pool_separable_f64(features, boxes, strides=(8, 16, 32, 64, 128), out: int = 7, f32_coords: bool = False) -> np.ndarray:
+    """features[l]: (S, C, h_l, w_l) arrays; boxes (S, 4) xyxy image pixels, box i on image i -> (S, C, out, out) float64.
+    f32_coords: box and sample coordinates in fp32 as the operator computes them for fp32 inputs (_axis_weights): a sample coordinate
+    rounded to fp32 moves by up to 2^-24 of its size, i.e. by a few 1e-6 pixels on a large map, which shifts a sample whose
+    neighbours differ by O(1) by a few 1e-6 -- more than an ulp of a pooled value near the 1e-3-of-maximum floor (thin boxes)."""
     S = boxes.shape[0]
     min_level = int(round(math.log2(strides[0])))
+    t = np.float32 if f32_coords else float
     res = []
     for i in range(S):
         lvl = level_of_box(boxes[i], min_level, min_level + len(strides) - 1) - min_level
         f = np.asarray(features[lvl][i], dtype=np.float64)
-        sc = 1.0 / strides[lvl]
-        x1, y1, x2, y2 = (float(v) * sc - 0.5 for v in boxes[i])
-        Ay = _axis_weights(y1, y2 - y1, f.shape[1], out)
-        Ax = _axis_weights(x1, x2 - x1, f.shape[2], out)
+        sc = t(1.0 / strides[lvl])
+        x1, y1, x2, y2 = (t(t(v) * sc) - t(0.5) for v in boxes[i])
+        Ay = _axis_weights(y1, t(y2 - y1), f.shape[1], out, f32_coords)
+        Ax = _axis_weights(x1, t(x2 - x1), f.shape[2], out, f32_coords)
         res.append(np.einsum("ph,chw,qw->cpq", Ay, f, Ax))
     return np.stack(res)
 

@@ -1,6 +1,9 @@
 """CPU checks of oracle/bf16.py (the bf16-storage restatement used to pin the production kernels): it must be the fp32
 oracle up to bf16 rounding, its rounding helper must be round-to-nearest-even, and its fma a single rounding."""
+import os
+
 import numpy as np
+import pytest
 import torch
 
 
@@ -46,3 +49,74 @@ def test_gn_coef_matches_group_norm():
     y = v * cf[:, :, 0].reshape(2, 256, 1, 1) + cf[:, :, 1].reshape(2, 256, 1, 1)
     ref = torch.nn.functional.group_norm(v, 32, gamma, beta, eps=1e-5)
     assert float((y - ref).abs().max()) < 1e-5
+
+
+# ---- support path ------------------------------------------------------------------------------------------
+def _golden_feats(g, prefix):
+    return [torch.from_numpy(g[f"{prefix}{l}_q8"].astype(np.float32) / 32.0) for l in range(5)]  # bf16-representable
+
+
+def _assert_code_close(got, ref_conv, ref_bias, k, what):
+    """The bound of oracle/bf16.py's docstring: relative L2 <= k * 2^-9 after k bf16 stores; the bias likewise (scale max(1, |b|))."""
+    ref_conv = torch.as_tensor(ref_conv).reshape(-1).double()
+    rel = float((got[:256].double() - ref_conv).norm() / ref_conv.norm())
+    rb = float(np.asarray(ref_bias).reshape(-1)[0])
+    assert rel <= k * 2.0 ** -9, (what, rel)
+    assert abs(float(got[256]) - rb) <= k * 2.0 ** -9 * max(1.0, abs(rb)), (what, float(got[256]), rb)
+
+
+def test_bf16_support_oracle_tracks_fp32_oracle():
+    from oracle import bf16 as B, codegen as CG, roi_encoder as R
+    from sylph_amd import synthetic as W
+    g = torch.Generator().manual_seed(5)
+    feats = [B.r(torch.randn(6, 256, h, w, generator=g)) for h, w in ((16, 24), (8, 12), (4, 6), (2, 3), (1, 2))]
+    boxes = W.synthetic_boxes(6, 128, 192, seed=6)
+    sd = W.codegen_state_dict(seed=2)
+    out = B.codegen_support(feats, boxes, sd, 3)
+    for k in range(2):
+        ref = CG.code_generator([f[3 * k:3 * k + 3] for f in feats], boxes[3 * k:3 * k + 3], sd)
+        _assert_code_close(out["codes"][k], ref["cls_conv"], ref["cls_bias"], 5, f"code generator class {k}")
+    for v, y, cf, x in out["layers"]:
+        assert torch.equal(B.r(y), y) and torch.equal(B.r(x), x)  # everything the graph stores is bf16-representable
+    sd = W.roi_encoder_state_dict(seed=4)
+    out = B.roi_encoder_support(feats, boxes, sd, 3)
+    assert torch.equal(B.r(out["mscam"]), out["mscam"])
+    for k in range(2):  # one class per reference call: its encoder attends over the class axis
+        ref = R.roi_encoder([f[3 * k:3 * k + 3] for f in feats], boxes[3 * k:3 * k + 3], sd, num_shots=3)
+        _assert_code_close(out["codes"][k], ref["cls_conv"], ref["cls_bias"], 8, f"ROIEncoder class {k}")
+
+
+@pytest.mark.parametrize("S", [1, 2, 5])
+@pytest.mark.parametrize("lvis", [False, True])
+def test_bf16_code_generator_reproduces_reference_golden(golden_dir, S, lvis):
+    from oracle import bf16 as B
+    from sylph_amd import synthetic as W
+    g = np.load(os.path.join(golden_dir, "g3_codegen.npz"))
+    out = B.codegen_support(_golden_feats(g, f"s{S}_feat"), torch.from_numpy(g[f"s{S}_boxes"]), W.codegen_state_dict(seed=2), S,
+                            bias_l2_norm=lvis)
+    tag = f"{'lvis' if lvis else 'coco'}_s{S}"
+    _assert_code_close(out["codes"][0], g[f"{tag}_cls_conv"], g[f"{tag}_cls_bias"], 5, tag)
+
+
+@pytest.mark.parametrize("S", [2, 5])
+@pytest.mark.parametrize("tag,spec", [("mixed_tower", [["", "ReLU"], ["GN", ""], ["GN", "ReLU"]]), ("plain_tower", [["", ""]]),
+                                      ("no_tower", [])])
+def test_bf16_code_generator_variants_reproduce_reference_golden(golden_dir, tag, spec, S):
+    """k = one ROI store + one store per layer without GroupNorm, two per layer with it."""
+    from oracle import bf16 as B
+    from sylph_amd import synthetic as W
+    g3 = np.load(os.path.join(golden_dir, "g3_codegen.npz"))
+    g = np.load(os.path.join(golden_dir, "g3d_codegen_variants.npz"))
+    out = B.codegen_support(_golden_feats(g3, f"s{S}_feat"), torch.from_numpy(g3[f"s{S}_boxes"]),
+                            W.codegen_state_dict(seed=2, tower_spec=spec), S, spec=spec)
+    k = 1 + sum(2 if n == "GN" else 1 for n, _ in spec)
+    _assert_code_close(out["codes"][0], g[f"{tag}_s{S}_cls_conv"], g[f"{tag}_s{S}_cls_bias"], k, f"{tag} S={S}")
+
+
+@pytest.mark.parametrize("S", [2, 5])
+def test_bf16_roi_encoder_reproduces_reference_golden(golden_dir, S):
+    from oracle import bf16 as B
+    from sylph_amd import synthetic as W
+    g = np.load(os.path.join(golden_dir, "g7_roi_encoder.npz"))
+    out = B.roi_encoder_support(_golden_feats(g, f"s{S}_feat"), torch.from_numpy(g[f"s{S}_boxes"]), W.roi_encoder_state_dict(seed=4), S)
+    _assert_code_close(out["codes"][0], g[f"s{S}_cls_conv"], g[f"s{S}_cls_bias"], 8, f"ROIEncoder S={S}")
