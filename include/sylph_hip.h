@@ -30,7 +30,8 @@ enum { SYLPH_F32 = 0, SYLPH_BF16 = 1, SYLPH_F32S = 2 };
 /* Subset of the yacs config the path reads (sylph/runner/adet_configs.py:25-61,
  * sylph/runner/default_configs.py:43-167). */
 typedef struct sylph_config {
-  int resnet_depth;        /* MODEL.RESNETS.DEPTH: 50 | 101 | 152 */
+  int resnet_depth;        /* MODEL.RESNETS.DEPTH: 50 | 101 | 152 (bottleneck blocks, stage widths 256 << s), 18 | 34 (BasicBlock,
+                              stage widths 64 << s = RES2_OUT_CHANNELS 64; needs num_groups 1, width_per_group 64; stride_in_1x1 is ignored) */
   int stride_in_1x1;       /* MODEL.RESNETS.STRIDE_IN_1X1 */
   int num_cls_convs;       /* MODEL.FCOS.NUM_CLS_CONVS */
   int num_box_convs;       /* MODEL.FCOS.NUM_BOX_CONVS */
@@ -237,7 +238,7 @@ int sylph_stem_maxpool(sylph_ctx* ctx, const float* x_nchw_dev, int B, int H, in
  * sylph_set_debug_taps(1) before the first head call of a batch shape: every FCOS tower layer keeps its stored conv output in
  * its own buffer (same kernels and launches, other destination) instead of the two ping-pong buffers.
  * sylph_export_stage: output of ResNet stage `stage` (2..5 = res2..res5) of the last sylph_backbone_fpn as
- * (B, 256 << (stage - 2), h, w) fp32 NCHW (detectron2 ResNet.forward outputs; call site meta_one_stage_detector.py:181,273).
+ * (B, C << (stage - 2), h, w) fp32 NCHW, C = 256 (64 for the BasicBlock depths 18 / 34) (detectron2 ResNet.forward outputs; call site meta_one_stage_detector.py:181,273).
  * sylph_export_tower: conv output of layer `layer` of the cls (tower 0) / bbox (tower 1) tower on FPN level `level`
  * (sylph/modeling/meta_fcos/fcos.py:72-122,625-628) as (B,256,h_l,w_l) fp32 NCHW -- the value stored BEFORE GroupNorm when
  * the layer's GroupNorm is applied by its consumer -- and (coef_dev != NULL) that GroupNorm's per-(image, channel)
@@ -293,6 +294,18 @@ int sylph_fpn_lateral(sylph_ctx* ctx, const float* x_nchw_dev, int B, int C, int
  * y (B,C,Ho,Wo) fp32 NCHW device.  C a multiple of 64, C / groups a power of two in [4, 64]. */
 int sylph_group_conv(sylph_ctx* ctx, const float* x_nchw_dev, int B, int C, int H, int W, int groups, int stride, const float* w_host,
                      const float* scale_host, const float* shift_host, int relu, float* y_nchw_dev);
+/* Kernel parity entry: ONE 3x3 stride-1 pad-1 conv 64 -> 64 channels with FrozenBN scale / shift, optional same-shape residual and
+ * optional ReLU, as the res2 convs of a BasicBlock ResNet (R-18 / R-34) launch it: conv_rw64.hip in bf16 (SYLPH_CONV_RW64 = 0 off /
+ * 1 auto / 2 always), the generic conv route otherwise (detectron2 BasicBlock.conv1 / conv2; call site
+ * meta_one_stage_detector.py:181,273).  x, residual (or NULL), y (B,64,H,W) fp32 NCHW device; w_host (64,64,3,3); scale / shift host (64). */
+int sylph_conv3x3_c64(sylph_ctx* ctx, const float* x_nchw_dev, int B, int H, int W, const float* w_host, const float* scale_host,
+                      const float* shift_host, int relu, const float* residual_nchw_dev, float* y_nchw_dev);
+/* Kernel parity entry: ONE detectron2 BasicBlock through the launches sylph_backbone_fpn makes for it:
+ * t = relu(bn1(conv1 3x3 stride)(x)), y = relu(bn2(conv2 3x3)(t) + shortcut), shortcut = x or bn(conv 1x1 stride)(x).
+ * w_host / scale_host / shift_host: conv1 (cout,Cin,3,3), conv2 (cout,cout,3,3), shortcut (cout,Cin,1,1) or NULL (then Cin == cout,
+ * stride 1).  x (B,Cin,H,W), y (B,cout,Ho,Wo) fp32 NCHW device.  (Call site meta_one_stage_detector.py:181,273.) */
+int sylph_basic_block(sylph_ctx* ctx, const float* x_nchw_dev, int B, int Cin, int H, int W, int stride, int cout,
+                      const float* const* w_host, const float* const* scale_host, const float* const* shift_host, float* y_nchw_dev);
 /* Kernel parity entry: ONE ResNeXt BottleneckBlock: sylph_bottleneck with a grouped conv2, w_host[1] (mid, mid / groups, 3, 3),
  * through the launches sylph_backbone_fpn makes for such a block. */
 int sylph_bottleneck_grouped(sylph_ctx* ctx, const float* x_nchw_dev, int B, int Cin, int H, int W, int stride, int mid, int cout,

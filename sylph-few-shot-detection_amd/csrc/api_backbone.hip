@@ -177,6 +177,89 @@ int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block&
   return 0;
 }
 
+// Below this many patches a launch of conv_rw64 (one persistent block per CU, weights loaded into registers first) is left to the
+// generic route.  Measured at 200 x 336 (272 patches per image, profiles/resnet_basic_conv64.txt): 1 image a tie, 2 and 4 images
+// (544 / 1 088 patches: 3 and 5 rounds over the 256 CUs, the last one nearly empty) 4-28 % behind conv_igemm's 64-row tiles, 8 images
+// (2 176) 3-14 % ahead, 64 and 192 images 1.4-1.55 x.
+static const long RW64_MIN_PATCHES = 2048;
+
+// One 3x3 stride-1 pad-1 conv 64 -> 64 + FrozenBN [+ residual] [+ ReLU] on dense images x [B][H * W][64] -> y, appended to `ops`:
+// conv_rw64.hip in bf16 (SYLPH_CONV_RW64: 0 off, 1 auto = launches of at least RW64_MIN_PATCHES patches, 2 always; read per build so
+// that one process can build both), add_conv / pick_conv_route otherwise.  Shared by add_basic_block and the parity entry
+// sylph_conv3x3_c64.
+int add_conv3x3_c64(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, int B, int H, int W, const void* x, const void* res, void* y, int relu) {
+  const int rw64_on = getenv("SYLPH_CONV_RW64") ? atoi(getenv("SYLPH_CONV_RW64")) : 1;
+  const size_t bytes = (size_t)B * H * W * 128;
+  int ph = 0, pw = 0;
+  bool rw64 = rw64_on && c->dt == DT_BF16 && L.groups == 1 && L.Cin == 64 && L.Cout == 64 && L.Cout_pad == 64 && L.KH == 3 && L.KW == 3 &&
+              L.scale && L.shift && W < 65536 && bytes <= 0xff000000u;  // (32-bit byte offsets into descriptors of the tensor's real size)
+  if (rw64) {
+    pick_patch(H, W, 256, 352, 2, &ph, &pw);  // 200 x 336 -> 12 x 21 patches (halo 14 x 23 = 322 pixels)
+    const long n = (long)B * ((H + ph - 1) / ph) * ((W + pw - 1) / pw);
+    rw64 = conv_rw64_patch_ok(ph, pw) && (rw64_on == 2 || n >= RW64_MIN_PATCHES);
+  }
+  if (!rw64) {
+    ConvOpts o; o.pad = 1; o.relu_nch = relu ? (1 << 30) : 0;
+    if (res) { o.res = res; o.res_ld = 64; o.res_mode = 1; }
+    return add_conv(c, ops, L, x, 64, y, 64, image_segs(B, H, W, H, W), o);
+  }
+  BottleneckArgs ba;  // (the patch table of the bottleneck kernels)
+  memset(&ba, 0, sizeof(ba));
+  RET(upload_bk_tiles(c, B, H, W, ph, pw, &ba));
+  ConvRw64Args ra;
+  memset(&ra, 0, sizeof(ra));
+  ra.x = x; ra.y = y; ra.res = res; ra.w = (const __bf16*)L.w; ra.scale = L.scale; ra.shift = L.shift;
+  ra.bk = ba.bk; ra.n_tiles = ba.n_tiles; ra.bytes = (unsigned)bytes; ra.relu = relu ? 1 : 0;
+  const double fl = 2.0 * (double)B * H * W * 64.0 * 576.0;
+  ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_rw64_kernel", fl, s, [=](hipStream_t st) { return launch_conv_rw64(ra, st); }); });
+  return 0;
+}
+
+// One ResNet BasicBlock (detectron2 BasicBlock of R-18 / R-34: 3x3 (stride) -> 3x3, FrozenBN folded, identity or 1x1 projection
+// shortcut) appended to `ops`: X [B][Hin*Win][Cin] -> Y [B][Ho*Wo][cout]; scr.t1 (the block's intermediate) and scr.sc (the projected
+// shortcut) hold B * Ho * Wo * cout elements.  Shared by build_backbone and the parity entry sylph_basic_block.
+//   t = relu(bn1(conv1(x)))        res2: conv_rw64; res3 identity blocks: conv_rw3 (add_bottleneck's conditions); else add_conv
+//   sc = x | bn(shortcut(x))       a launch of its own (1x1, stride 2)
+//   y = relu(bn2(conv2(t)) + sc)   res2: conv_rw64 with the residual; else add_conv (conv_igemm halo tiles: the only 3x3 route with a residual)
+int add_basic_block(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win,
+                    int stride, int cout, void* Y, const BkScratch& scr) {
+  const DType dt = c->dt;
+  const int Ho = (Hin - 1) / stride + 1, Wo = (Win - 1) / stride + 1;
+  void *t = scr.t1, *sc = scr.sc;
+  if (!blk.has_sc && (Cin != cout || stride != 1)) return fail("internal: BasicBlock without a shortcut must keep its shape");
+  if (blk.c1.Cin != Cin || blk.c1.Cout != cout || blk.c2.Cin != cout || blk.c2.Cout != cout || blk.c1.KH != 3 || blk.c2.KH != 3)
+    return fail("internal: BasicBlock shape");
+  const bool c64 = Cin == 64 && cout == 64 && stride == 1;
+  static const int rw3_on = getenv("SYLPH_CONV_RW3") ? atoi(getenv("SYLPH_CONV_RW3")) : 1;
+  const bool rw3 = rw3_on && dt == DT_BF16 && stride == 1 && Cin == 128 && cout == 128 && blk.c1.Cout_pad == 128 && blk.c1.KW == 3 && blk.c1.scale &&
+                   blk.c1.shift && (size_t)B * Hin * Win * 256 < ((size_t)1 << 31) && (rw3_on == 2 || (size_t)B * Hin * Win >= (size_t)256 * 120);
+  int ph = 0, pw = 0;
+  if (rw3) pick_patch(Hin, Win, 128, 184, 2, &ph, &pw);
+  if (c64) {
+    RET(add_conv3x3_c64(c, ops, blk.c1, B, Hin, Win, X, nullptr, t, 1));
+  } else if (rw3 && conv_rw3_patch_ok(ph, pw)) {
+    BottleneckArgs ba;
+    memset(&ba, 0, sizeof(ba));
+    ba.x = X; ba.y = t;
+    ba.w2 = (const __bf16*)blk.c1.w; ba.s2 = blk.c1.scale; ba.b2 = blk.c1.shift;
+    RET(upload_bk_tiles(c, B, Hin, Win, ph, pw, &ba));
+    const double fl = 2.0 * (double)B * Hin * Win * 128.0 * 1152.0;
+    ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_rw3_kernel", fl, s, [=](hipStream_t st) { return launch_conv_rw3(ba, st); }); });
+  } else {
+    ConvOpts o1; o1.stride = stride; o1.pad = 1; o1.relu_nch = 1 << 30;
+    RET(add_conv(c, ops, blk.c1, X, Cin, t, cout, image_segs(B, Hin, Win, Ho, Wo), o1));
+  }
+  const void* resid = X;
+  if (blk.has_sc) {
+    ConvOpts os; os.stride = stride;
+    RET(add_conv(c, ops, blk.sc, X, Cin, sc, cout, image_segs(B, Hin, Win, Ho, Wo), os));
+    resid = sc;
+  }
+  if (c64) return add_conv3x3_c64(c, ops, blk.c2, B, Ho, Wo, t, resid, Y, 1);
+  ConvOpts o2; o2.pad = 1; o2.relu_nch = 1 << 30; o2.res = resid; o2.res_ld = cout; o2.res_mode = 1;
+  return add_conv(c, ops, blk.c2, t, cout, Y, cout, image_segs(B, Ho, Wo, Ho, Wo), o2);
+}
+
 int build_backbone(sylph_ctx* c, Plan* P) {
   if (P->backbone_built) return 0;
   if (!c->has_backbone) return fail("backbone weights were not loaded");
@@ -230,14 +313,16 @@ int build_backbone(sylph_ctx* c, Plan* P) {
   int Hin = H4, Win = W4, Cin = 64;
   const void* stage_out[4] = {nullptr, nullptr, nullptr, nullptr};
   int stage_h[4], stage_w[4];
+  const bool basic = !c->stages[0].empty() && c->stages[0][0].basic;  // R-18 / R-34: BasicBlocks, stage widths 64 << si
+  int stage_c[4];
   for (int si = 0; si < 4; ++si) {
-    const int mid = (c->cfg.num_groups * c->cfg.width_per_group) << si, cout = 256 << si;  // (ResNeXt: num_groups > 1)
+    const int mid = (c->cfg.num_groups * c->cfg.width_per_group) << si, cout = (basic ? 64 : 256) << si;  // (ResNeXt: num_groups > 1)
     const int first_stride = si == 0 ? 1 : 2;
     const int Hs = (Hin - 1) / first_stride + 1, Ws = (Win - 1) / first_stride + 1;
-    void *t1, *t2, *sc, *Ya, *Yb;
-    // t1 may still be at the input resolution when the stride sits on the 3x3
-    RET(c->dalloc(&t1, (size_t)B * Hin * Win * mid * e));
-    RET(c->dalloc(&t2, (size_t)B * Hs * Ws * mid * e));
+    void *t1, *t2 = nullptr, *sc, *Ya, *Yb;
+    // t1 may still be at the input resolution when the stride sits on the 3x3 (a BasicBlock's one intermediate is at the output's)
+    RET(c->dalloc(&t1, basic ? (size_t)B * Hs * Ws * cout * e : (size_t)B * Hin * Win * mid * e));
+    if (!basic) RET(c->dalloc(&t2, (size_t)B * Hs * Ws * mid * e));
     RET(c->dalloc(&sc, (size_t)B * Hs * Ws * cout * e));
     RET(c->dalloc(&Ya, (size_t)B * Hs * Ws * cout * e));
     RET(c->dalloc(&Yb, (size_t)B * Hs * Ws * cout * e));
@@ -247,11 +332,12 @@ int build_backbone(sylph_ctx* c, Plan* P) {
     for (size_t bi = 0; bi < blocks.size(); ++bi) {
       const int stride = bi == 0 ? first_stride : 1;
       Y = (Y == Ya) ? Yb : Ya;
-      RET(add_bottleneck(c, ops, blocks[bi], B, X, Cin, Hin, Win, stride, mid, cout, Y, scr));
+      if (basic) RET(add_basic_block(c, ops, blocks[bi], B, X, Cin, Hin, Win, stride, cout, Y, scr));
+      else RET(add_bottleneck(c, ops, blocks[bi], B, X, Cin, Hin, Win, stride, mid, cout, Y, scr));
       X = Y; Hin = (Hin - 1) / stride + 1; Win = (Win - 1) / stride + 1; Cin = cout;
     }
-    stage_out[si] = X; stage_h[si] = Hin; stage_w[si] = Win;
-    P->stage_out[si] = X; P->stage_h[si] = Hin; P->stage_w[si] = Win;
+    stage_out[si] = X; stage_h[si] = Hin; stage_w[si] = Win; stage_c[si] = cout;
+    P->stage_out[si] = X; P->stage_h[si] = Hin; P->stage_w[si] = Win; P->stage_c[si] = cout;
   }
   // FPN (res3..res5 -> p3..p5), top-down with nearest 2x upsample fused as a residual, then P6/P7
   // Small batches: after lateral5 the FPN is two independent chains of small launches -- {output5, P6, relu, P7} and {lateral4, output4,
@@ -267,7 +353,7 @@ int build_backbone(sylph_ctx* c, Plan* P) {
   std::vector<OpFn> side_ops;
   void* lat[3] = {nullptr, nullptr, nullptr};
   for (int k = 2; k >= 0; --k) {
-    const int si = k + 1, h = stage_h[si], w = stage_w[si], cin = 256 << si;
+    const int si = k + 1, h = stage_h[si], w = stage_w[si], cin = stage_c[si];
     if (h != P->hl[k] || w != P->wl[k]) return fail("internal: level geometry mismatch");
     RET(c->dalloc(&lat[k], (size_t)B * h * w * 256 * e));
     ConvOpts ol;

@@ -187,8 +187,11 @@ int sylph_set_stream(sylph_ctx* c, void* s) {
 int sylph_set_config(sylph_ctx* c, const sylph_config* cfg) {
   if (c->finalized) return fail("sylph_set_config must precede sylph_finalize_weights");
   if (cfg->nlevels != 5) return fail("only the 5-level FCOS pyramid (p3..p7) is supported");
-  if (cfg->resnet_depth != 50 && cfg->resnet_depth != 101 && cfg->resnet_depth != 152)
-    return fail("MODEL.RESNETS.DEPTH must be 50, 101 or 152");
+  const bool basic = cfg->resnet_depth == 18 || cfg->resnet_depth == 34;  // BasicBlock ResNets (stage widths 64 << s)
+  if (!basic && cfg->resnet_depth != 50 && cfg->resnet_depth != 101 && cfg->resnet_depth != 152)
+    return fail("MODEL.RESNETS.DEPTH must be 18, 34, 50, 101 or 152");
+  if (basic && (cfg->num_groups != 1 || cfg->width_per_group != 64))
+    return fail("MODEL.RESNETS.DEPTH 18 / 34 (BasicBlock) needs NUM_GROUPS 1 and WIDTH_PER_GROUP 64");
   if (cfg->num_groups != 1 || cfg->width_per_group != 64) {  // ResNeXt: what conv_group.hip covers (sylph_amd/engine.py config_from_cfg)
     bool ok = cfg->num_groups >= 1 && cfg->width_per_group >= 1 && (cfg->num_groups * cfg->width_per_group) % 64 == 0;
     for (int s = 0; s < 4 && ok; ++s) {

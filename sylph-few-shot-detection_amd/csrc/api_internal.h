@@ -98,7 +98,11 @@ struct sylph_ctx {
   // packed model
   ConvLayer stem;  // 7x7 s2 stem packed for the implicit-GEMM stem loader
   void* stem_wp = nullptr;  // bf16 [64][7][8][4] for the dedicated stem kernel (stem_conv.hip)
-  struct Block { ConvLayer c1, c2, c3, sc, c3sc; bool has_sc = false, fused_sc = false; };
+  struct Block {
+    ConvLayer c1, c2, c3, sc, c3sc;
+    bool has_sc = false, fused_sc = false;
+    bool basic = false;  // detectron2 BasicBlock (R-18 / R-34): c1, c2 are 3x3 convs, no c3, a shortcut only where the width changes
+  };
   std::vector<std::vector<Block>> stages;  // res2..res5
   ConvLayer fpn_lat[3], fpn_out[3], p6, p7;  // index 0..2 = stage 3..5
   std::vector<ConvLayer> cls_tower, box_tower, share_tower;  // share_tower: MODEL.FCOS.NUM_SHARE_CONVS layers in front of both
@@ -188,7 +192,7 @@ struct Plan {
   // parity taps (sylph_export_stage / sylph_export_tower): where the stage outputs res2..res5 and, with debug taps on, every
   // tower layer's stored conv output and GroupNorm coefficient table live
   const void* stage_out[4] = {nullptr, nullptr, nullptr, nullptr};
-  int stage_h[4] = {0, 0, 0, 0}, stage_w[4] = {0, 0, 0, 0};
+  int stage_h[4] = {0, 0, 0, 0}, stage_w[4] = {0, 0, 0, 0}, stage_c[4] = {0, 0, 0, 0};
   std::vector<const void*> tap_out[2];      // [cls | bbox][layer]: conv output [rows][256] (pre-GroupNorm when tap_coef is set)
   std::vector<const float2*> tap_coef[2];   // [cls | bbox][layer]: (a, b) per (segment, channel), nullptr if applied in place
   std::vector<OpFn> backbone_ops, head_ops, support_ops;
@@ -357,6 +361,8 @@ std::vector<SegDesc> image_segs(int B, int Hin, int Win, int Hout, int Wout, int
 // api_backbone.hip
 int ensure_pyramid(sylph_ctx* c, Plan* P);
 int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win, int stride, int mid, int cout, void* Y, const BkScratch& scr);
+int add_conv3x3_c64(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, int B, int H, int W, const void* x, const void* res, void* y, int relu);
+int add_basic_block(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win, int stride, int cout, void* Y, const BkScratch& scr);
 int build_backbone(sylph_ctx* c, Plan* P);
 // api_head.hip
 std::vector<SegDesc> pyramid_segs(sylph_ctx* c, Plan* P);

@@ -55,7 +55,7 @@ int sylph_export_stage(sylph_ctx* c, int stage, float* out) {
   if (!P || !P->backbone_built) return fail("no backbone pass on the current batch");
   if (stage < 2 || stage > 5 || !P->stage_out[stage - 2]) return fail("bad stage");
   HIPCHK(hipSetDevice(c->device));
-  const int si = stage - 2, C = 256 << si, hw = P->stage_h[si] * P->stage_w[si];
+  const int si = stage - 2, C = P->stage_c[si], hw = P->stage_h[si] * P->stage_w[si];
   for (int b = 0; b < P->B; ++b)
     KCHK(launch_export_nchw(c->dt, P->stage_out[si], out + (size_t)b * C * hw, C, hw, b * hw, C, c->stream), "export stage");
   return 0;
@@ -174,6 +174,82 @@ int sylph_group_conv(sylph_ctx* c, const float* x, int B, int C, int H, int W, i
   adopt_records(c, &tmp);
   for (int b = 0; b < B; ++b)
     KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * C * Ho * Wo, C, Ho * Wo, b * Ho * Wo, C, c->stream), "export");
+  return 0;
+}
+
+int sylph_conv3x3_c64(sylph_ctx* c, const float* x, int B, int H, int W, const float* w_host, const float* scale_host,
+                      const float* shift_host, int relu, const float* residual, float* y) {
+  HIPCHK(hipSetDevice(c->device));
+  if (B < 1 || H < 1 || W < 1 || !w_host || !scale_host || !shift_host) return fail("sylph_conv3x3_c64: bad arguments");
+  sylph_ctx tmp;  // scratch allocations freed on return
+  tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros; tmp.cfg = c->cfg;
+  tmp.prof = c->prof;  // profile + route records move to the caller's context below
+  struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
+  HostTensor hw;
+  hw.shape = {64, 64, 3, 3};
+  hw.data.assign(w_host, w_host + (size_t)64 * 64 * 9);
+  ConvLayer L;
+  RET(pack_conv(&tmp, {&hw}, &L));
+  RET(upload_vec(&tmp, &L.scale, std::vector<float>(scale_host, scale_host + 64), L.Cout_pad));
+  RET(upload_vec(&tmp, &L.shift, std::vector<float>(shift_host, shift_host + 64), L.Cout_pad));
+  const size_t n = (size_t)B * H * W * 64 * tmp.esz();
+  void *xin, *yout, *res = nullptr;
+  RET(tmp.dalloc(&xin, n));
+  RET(tmp.dalloc(&yout, n));
+  if (residual) RET(tmp.dalloc(&res, n));
+  for (int b = 0; b < B; ++b) {
+    KCHK(launch_import_nchw(c->dt, x + (size_t)b * 64 * H * W, xin, 64, H * W, b * H * W, 64, c->stream), "import");
+    if (residual) KCHK(launch_import_nchw(c->dt, residual + (size_t)b * 64 * H * W, res, 64, H * W, b * H * W, 64, c->stream), "import");
+  }
+  std::vector<OpFn> ops;
+  RET(add_conv3x3_c64(&tmp, ops, L, B, H, W, xin, res, yout, relu));
+  RET(run_ops(c, ops, "conv3x3_c64"));
+  adopt_records(c, &tmp);
+  for (int b = 0; b < B; ++b)
+    KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * 64 * H * W, 64, H * W, b * H * W, 64, c->stream), "export");
+  return 0;
+}
+
+int sylph_basic_block(sylph_ctx* c, const float* x, int B, int Cin, int H, int W, int stride, int cout, const float* const* w_host,
+                      const float* const* scale_host, const float* const* shift_host, float* y) {
+  HIPCHK(hipSetDevice(c->device));
+  const int bk = c->dt == DT_BF16 ? 64 : 32;
+  if (Cin % bk != 0 || cout % bk != 0) return fail("sylph_basic_block: channel counts must be multiples of " + std::to_string(bk));
+  if (stride != 1 && stride != 2) return fail("sylph_basic_block: stride must be 1 or 2");
+  const bool has_sc = w_host[2] != nullptr;
+  if (!has_sc && (Cin != cout || stride != 1)) return fail("sylph_basic_block: an identity block needs Cin == cout and stride 1");
+  sylph_ctx tmp;  // scratch allocations freed on return
+  tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros; tmp.cfg = c->cfg;
+  tmp.prof = c->prof;
+  struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
+  sylph_ctx::Block blk;
+  blk.basic = true; blk.has_sc = has_sc;
+  const int cins[3] = {Cin, cout, Cin}, ks[3] = {3, 3, 1};
+  ConvLayer* Ls[3] = {&blk.c1, &blk.c2, &blk.sc};
+  HostTensor hw[3];
+  for (int i = 0; i < (has_sc ? 3 : 2); ++i) {
+    hw[i].shape = {cout, cins[i], ks[i], ks[i]};
+    hw[i].data.assign(w_host[i], w_host[i] + (size_t)cout * cins[i] * ks[i] * ks[i]);
+    RET(pack_conv(&tmp, {&hw[i]}, Ls[i]));
+    RET(upload_vec(&tmp, &Ls[i]->scale, std::vector<float>(scale_host[i], scale_host[i] + cout), Ls[i]->Cout_pad));
+    RET(upload_vec(&tmp, &Ls[i]->shift, std::vector<float>(shift_host[i], shift_host[i] + cout), Ls[i]->Cout_pad));
+  }
+  const size_t e = tmp.esz();
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  void *xin, *yout, *t1, *sc, *trash = nullptr;
+  RET(tmp.dalloc(&xin, (size_t)B * H * W * Cin * e));
+  RET(tmp.dalloc(&yout, (size_t)B * Ho * Wo * cout * e));
+  RET(tmp.dalloc(&t1, (size_t)B * Ho * Wo * cout * e));
+  RET(tmp.dalloc(&sc, (size_t)B * Ho * Wo * cout * e));
+  for (int b = 0; b < B; ++b)
+    KCHK(launch_import_nchw(c->dt, x + (size_t)b * Cin * H * W, xin, Cin, H * W, b * H * W, Cin, c->stream), "import");
+  std::vector<OpFn> ops;
+  BkScratch scr{t1, nullptr, sc, &trash};
+  RET(add_basic_block(&tmp, ops, blk, B, xin, Cin, H, W, stride, cout, yout, scr));
+  RET(run_ops(c, ops, "basic_block"));
+  adopt_records(c, &tmp);
+  for (int b = 0; b < B; ++b)
+    KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * cout * Ho * Wo, cout, Ho * Wo, b * Ho * Wo, cout, c->stream), "export");
   return 0;
 }
 

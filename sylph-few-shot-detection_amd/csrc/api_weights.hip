@@ -131,6 +131,20 @@ int make_conv2_bn(sylph_ctx* c, const std::string& name, int mid, int groups, Co
   return pack_conv_grouped(c, *w, name + ".weight", mid, groups, sc.data(), sh.data(), L);
 }
 
+// a backbone conv whose shape follows from MODEL.RESNETS.DEPTH (bottleneck or BasicBlock layout): a checkpoint of the other block type
+// fails here, naming the key and the shape the config needs
+static int expect_conv_shape(sylph_ctx* c, const std::string& name, int cout, int cin, int k) {
+  const HostTensor* w = find_w(c, name + ".weight");
+  const std::string need = "(" + std::to_string(cout) + ", " + std::to_string(cin) + ", " + std::to_string(k) + ", " + std::to_string(k) + ")";
+  if (!w) return fail("missing weights for " + name + ".weight: MODEL.RESNETS.DEPTH " + std::to_string(c->cfg.resnet_depth) + " needs " + need);
+  if (w->shape.size() != 4 || w->shape[0] != cout || w->shape[1] != cin || w->shape[2] != k || w->shape[3] != k) {
+    std::string got;
+    for (size_t i = 0; i < w->shape.size(); ++i) got += (i ? ", " : "") + std::to_string(w->shape[i]);
+    return fail(name + ".weight: shape (" + got + ") where the config (MODEL.RESNETS.DEPTH " + std::to_string(c->cfg.resnet_depth) + ") needs " + need);
+  }
+  return 0;
+}
+
 int make_conv_bias(sylph_ctx* c, const std::vector<std::string>& names, ConvLayer* L) {
   std::vector<const HostTensor*> ws;
   std::vector<float> bias;
@@ -263,13 +277,35 @@ int sylph_finalize_weights(sylph_ctx* c) {
       }
     }
     const int nb50[4] = {3, 4, 6, 3}, nb101[4] = {3, 4, 23, 3}, nb152[4] = {3, 8, 36, 3};
-    const int* nb = c->cfg.resnet_depth == 50 ? nb50 : (c->cfg.resnet_depth == 101 ? nb101 : nb152);
+    const int nb18[4] = {2, 2, 2, 2}, nb34[4] = {3, 4, 6, 3};
+    const bool basic = c->cfg.resnet_depth == 18 || c->cfg.resnet_depth == 34;
+    const int* nb = c->cfg.resnet_depth == 18 ? nb18 : c->cfg.resnet_depth == 34 ? nb34 :
+                    c->cfg.resnet_depth == 50 ? nb50 : (c->cfg.resnet_depth == 101 ? nb101 : nb152);
     c->stages.resize(4);
     for (int si = 0; si < 4; ++si) {
       c->stages[si].resize(nb[si]);
       for (int bi = 0; bi < nb[si]; ++bi) {
         const std::string q = bu + ".res" + std::to_string(si + 2) + "." + std::to_string(bi);
         auto& blk = c->stages[si][bi];
+        if (basic) {
+          // detectron2 BasicBlock: conv1 3x3 (stride) -> conv2 3x3, stage width 64 << si, a projection shortcut only where the width changes
+          const int cout = 64 << si, cin = (bi == 0 && si > 0) ? cout / 2 : cout;
+          blk.basic = true;
+          RET(expect_conv_shape(c, q + ".conv1", cout, cin, 3));
+          RET(make_conv_bn(c, q + ".conv1", &blk.c1));
+          RET(expect_conv_shape(c, q + ".conv2", cout, cout, 3));
+          RET(make_conv_bn(c, q + ".conv2", &blk.c2));
+          blk.has_sc = cin != cout;
+          if (blk.has_sc) {
+            RET(expect_conv_shape(c, q + ".shortcut", cout, cin, 1));
+            RET(make_conv_bn(c, q + ".shortcut", &blk.sc));
+          }
+          continue;
+        }
+        if (const HostTensor* w1 = find_w(c, q + ".conv1.weight"))  // a BasicBlock checkpoint (3x3 conv1) under a bottleneck depth
+          if (w1->shape.size() == 4 && (w1->shape[2] != 1 || w1->shape[3] != 1))
+            return expect_conv_shape(c, q + ".conv1", (c->cfg.num_groups * c->cfg.width_per_group) << si,
+                                     bi > 0 ? 256 << si : (si == 0 ? 64 : 128 << si), 1);
         RET(make_conv_bn(c, q + ".conv1", &blk.c1));
         RET(make_conv2_bn(c, q + ".conv2", (c->cfg.num_groups * c->cfg.width_per_group) << si, c->cfg.num_groups, &blk.c2));
         RET(make_conv_bn(c, q + ".conv3", &blk.c3));
@@ -297,6 +333,12 @@ int sylph_finalize_weights(sylph_ctx* c) {
       }
     }
     for (int k = 0; k < 3; ++k) {
+      if (basic) {
+        const HostTensor* lw = find_w(c, "backbone.fpn_lateral" + std::to_string(k + 3) + ".weight");
+        if (lw && (lw->shape.size() != 4 || lw->shape[1] != (128 << k)))
+          return fail("backbone.fpn_lateral" + std::to_string(k + 3) + ".weight: MODEL.RESNETS.DEPTH " + std::to_string(c->cfg.resnet_depth) +
+                      " needs (256, " + std::to_string(128 << k) + ", 1, 1)");
+      }
       RET(make_conv_bias(c, {"backbone.fpn_lateral" + std::to_string(k + 3)}, &c->fpn_lat[k]));
       RET(make_conv_bias(c, {"backbone.fpn_output" + std::to_string(k + 3)}, &c->fpn_out[k]));
     }

@@ -87,6 +87,20 @@ struct BottleneckArgs {
   int n_tiles;
 };
 
+// conv_rw64.hip: 3x3 s1 p1 conv 64 -> 64 channels, bf16, weights in registers.  x, y (and res, the optional residual) are dense
+// [pos][64] tensors of `bytes` bytes each (< 4 GiB: buffer descriptors); w [64][3][3][64] (the conv_igemm layout); scale / shift fp32
+struct ConvRw64Args {
+  const void* x;
+  void* y;
+  const void* res;
+  const __bf16* w;
+  const float *scale, *shift;
+  const BkTile* bk;  // ph x pw patches, ph * pw <= 256 (conv_rw64_patch_ok), the same for every patch of a launch
+  int n_tiles;
+  unsigned bytes;
+  int relu;
+};
+
 template <typename T> struct Cvt;
 template <> struct Cvt<float> {
   static __device__ __forceinline__ float to_f(float v) { return v; }
@@ -166,6 +180,8 @@ int launch_bottleneck64(const BottleneckArgs& a, int small, hipStream_t s);   //
 int launch_bottleneck64p(const BottleneckArgs& a, hipStream_t s);  // first block of res2: x [pos][64], w3 = [256][128] packed [W3 | Wsc], y = relu(acc + b3)
 int launch_conv_rw3(const BottleneckArgs& a, hipStream_t s);  // conv_rw3.hip: 3x3 s1 128 -> 128 + FrozenBN + ReLU, weights in registers (x, y, w2, s2, b2, bk, n_tiles)
 bool conv_rw3_patch_ok(int ph, int pw);
+int launch_conv_rw64(const ConvRw64Args& a, hipStream_t s);  // conv_rw64.hip: 3x3 s1 64 -> 64 + FrozenBN [+ residual] [+ ReLU], weights in registers
+bool conv_rw64_patch_ok(int ph, int pw);
 // conv_pw.hip: persistent pipelined pointwise (1x1) conv, bf16; a.wt = the layer's stage-image weights (launch_pw_pack_weights),
 // a.tiles = BM-row tiles, a.pw_desc / a.pw_table as below; (BM, BN) from conv_pw_tile (false: not eligible)
 bool conv_pw_tile(int cout, int k_total, bool has_res, int* BM, int* BN);

@@ -85,6 +85,8 @@ PROTOTYPES = {
     "sylph_group_conv": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "sylph_bottleneck_grouped": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                                                             c_void_p]),
+    "sylph_conv3x3_c64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "sylph_basic_block": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
     "sylph_device_bytes": (c_int64, [c_void_p]),
     "sylph_profile_enable": (c_int, [c_void_p, c_int]),
     "sylph_bench_conv": (c_int, [c_void_p] + [c_int] * 12 + [POINTER(c_float), POINTER(ctypes.c_double)]),

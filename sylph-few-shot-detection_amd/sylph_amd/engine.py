@@ -42,6 +42,11 @@ def config_from_cfg(cfg) -> SylphConfig:
     # ResNeXt (grouped 3x3 conv2, csrc/conv_group.hip): per-group width WIDTH_PER_GROUP << s a power of two in [4, 64] at every stage,
     # NUM_GROUPS * WIDTH_PER_GROUP a multiple of 64; the plain ResNet bottleneck is 1 group x 64
     ng, wpg = int(r.get("NUM_GROUPS", 1)), int(r.get("WIDTH_PER_GROUP", 64))
+    # R-18 / R-34 (detectron2 BasicBlock, csrc/conv_rw64.hip): stage widths 64 << s, i.e. RES2_OUT_CHANNELS 64; STRIDE_IN_1X1 is ignored
+    # (the stride sits on conv1).  detectron2's own assertions for these depths: no groups, no deformable stages, no res5 dilation
+    basic = sc.resnet_depth in (18, 34)
+    if sc.resnet_depth not in (18, 34, 50, 101, 152):
+        raise NotImplementedError(f"MODEL.RESNETS.DEPTH {sc.resnet_depth}: 18, 34 (BasicBlock) and 50, 101, 152 (bottleneck) are supported")
     if ng != 1 or wpg != 64:
         if sc.resnet_depth not in (50, 101, 152):
             raise NotImplementedError(f"MODEL.RESNETS.DEPTH {sc.resnet_depth}: ResNeXt needs DEPTH 50, 101 or 152")
@@ -55,8 +60,13 @@ def config_from_cfg(cfg) -> SylphConfig:
         raise NotImplementedError("MODEL.RESNETS.DEFORM_ON_PER_STAGE: deformable bottleneck convs are not supported")
     if int(r.get("RES5_DILATION", 1)) != 1:
         raise NotImplementedError("MODEL.RESNETS.RES5_DILATION != 1 is not supported")
-    if int(r.get("RES2_OUT_CHANNELS", 256)) != 256 or int(r.get("STEM_OUT_CHANNELS", 64)) != 64:
-        raise NotImplementedError("MODEL.RESNETS.RES2_OUT_CHANNELS / STEM_OUT_CHANNELS: only 256 / 64 are supported")
+    res2_out = int(r.get("RES2_OUT_CHANNELS", 256))
+    if basic and res2_out != 64:
+        raise NotImplementedError(f"MODEL.RESNETS.RES2_OUT_CHANNELS {res2_out}: DEPTH {sc.resnet_depth} (BasicBlock) needs RES2_OUT_CHANNELS 64")
+    if not basic and res2_out == 64:
+        raise NotImplementedError(f"MODEL.RESNETS.RES2_OUT_CHANNELS 64 belongs to DEPTH 18 / 34 (BasicBlock); DEPTH {sc.resnet_depth} needs 256")
+    if res2_out != (64 if basic else 256) or int(r.get("STEM_OUT_CHANNELS", 64)) != 64:
+        raise NotImplementedError("MODEL.RESNETS.RES2_OUT_CHANNELS / STEM_OUT_CHANNELS: only 256 (64 for DEPTH 18 / 34) / 64 are supported")
     if str(r.get("NORM", "FrozenBN")) != "FrozenBN":
         raise NotImplementedError(f"MODEL.RESNETS.NORM {r.NORM!r}: only FrozenBN (inference) is supported")
     fpn = m.get("FPN", None)
@@ -594,13 +604,13 @@ class Engine:
         check(self.L.sylph_set_debug_taps(self._ctx, int(on)), "set_debug_taps")
 
     def export_stage(self, stage: int) -> torch.Tensor:
-        """res<stage> output of the last backbone pass, (B, C, h, w) fp32 NCHW."""
+        """res<stage> output of the last backbone pass, (B, C, h, w) fp32 NCHW; C = 256 << (stage - 2), 64 << (stage - 2) for R-18 / R-34."""
         self._stream()
         B, H, W, _ = self._batch
         h, w = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         for _ in range(stage - 1):
             h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-        out = torch.empty(B, 256 << (stage - 2), h, w, device=self.device)
+        out = torch.empty(B, (64 if self.sc.resnet_depth in (18, 34) else 256) << (stage - 2), h, w, device=self.device)
         check(self.L.sylph_export_stage(self._ctx, stage, _ptr(out)), "export_stage")
         return out
 
@@ -676,6 +686,36 @@ class Engine:
         y = torch.empty(B, C, Ho, Wo, device=self.device)
         check(self.L.sylph_group_conv(self._ctx, _ptr(x), B, C, H, W, groups, stride, _ptr(wh), _ptr(sc), _ptr(sh), int(relu), _ptr(y)),
               "group_conv")
+        return y
+
+    def conv3x3_c64(self, x, w, scale, shift, relu=True, residual=None):
+        """One 3x3 stride-1 pad-1 conv 64 -> 64 + FrozenBN scale / shift [+ residual] [+ ReLU] as the res2 convs of R-18 / R-34 launch it
+        (conv_rw64.hip in bf16 -- SYLPH_CONV_RW64 0 off / 1 auto / 2 always --, the generic conv route otherwise)."""
+        self._stream()
+        x = x.to(self.device, torch.float32).contiguous()
+        B, C, H, W = x.shape
+        assert C == 64 and tuple(w.shape) == (64, 64, 3, 3)
+        wh, sc, sh = [t.detach().cpu().float().contiguous() for t in (w, scale, shift)]
+        rs = residual.to(self.device, torch.float32).contiguous() if residual is not None else None
+        assert rs is None or rs.shape == x.shape
+        y = torch.empty_like(x)
+        check(self.L.sylph_conv3x3_c64(self._ctx, _ptr(x), B, H, W, _ptr(wh), _ptr(sc), _ptr(sh), int(relu), _ptr(rs), _ptr(y)),
+              "conv3x3_c64")
+        return y
+
+    def basic_block(self, x, ws, scales, shifts, stride=1):
+        """One ResNet BasicBlock (R-18 / R-34) through the backbone's own launches.  ws / scales / shifts: conv1 (cout, Cin, 3, 3),
+        conv2 (cout, cout, 3, 3), shortcut (cout, Cin, 1, 1) or None, with their folded FrozenBN scale / shift."""
+        self._stream()
+        x = x.to(self.device, torch.float32).contiguous()
+        B, Cin, H, W = x.shape
+        cout = ws[0].shape[0]
+        n = 3 if len(ws) > 2 and ws[2] is not None else 2
+        keep = [[t.detach().cpu().float().contiguous() for t in lst[:n]] for lst in (ws, scales, shifts)]
+        arrs = [(c_void_p * 3)(*([t.data_ptr() for t in lst] + [None] * (3 - n))) for lst in keep]
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        y = torch.empty(B, cout, Ho, Wo, device=self.device)
+        check(self.L.sylph_basic_block(self._ctx, _ptr(x), B, Cin, H, W, stride, cout, arrs[0], arrs[1], arrs[2], _ptr(y)), "basic_block")
         return y
 
     def fpn_lateral(self, x, w, bias, top=None):

@@ -17,7 +17,8 @@ from typing import Dict, List, Tuple
 
 import torch
 
-STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}  # detectron2 ResNet depths
+STAGE_BLOCKS = {18: (2, 2, 2, 2), 34: (3, 4, 6, 3), 50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}  # detectron2 ResNet depths
+BASIC_DEPTHS = (18, 34)  # detectron2 BasicBlock: two 3x3 convs per block, stage widths 64 << s (RES2_OUT_CHANNELS 64)
 
 
 def _conv(g, cout, cin, k, std=None):
@@ -41,7 +42,12 @@ def _gn(g, sd, prefix, c):
 def backbone_state_dict(seed: int = 0, depth: int = 50, num_groups: int = 1, width_per_group: int = 64) -> Dict[str, torch.Tensor]:
     """num_groups / width_per_group (MODEL.RESNETS.*): a ResNeXt backbone (detectron2 build_resnet_backbone) with bottleneck width
     num_groups * width_per_group << stage and conv2 weights (mid, mid / num_groups, 3, 3).  Its conv1 / conv2 / conv3 tensors come
-    from a generator of their own, so the default (1 x 64) dict is unchanged."""
+    from a generator of their own, so the default (1 x 64) dict is unchanged.
+    depth 18 / 34: BasicBlock backbones -- per block conv1 (cout, cin, 3, 3), conv2 (cout, cout, 3, 3, scaled x 0.25 as conv3 is), a
+    shortcut only where the width changes (res3.0, res4.0, res5.0), no conv3; FPN laterals read 128 / 256 / 512 channels."""
+    if depth in BASIC_DEPTHS:
+        assert (num_groups, width_per_group) == (1, 64), "BasicBlock backbones have no groups"
+        return _basic_backbone_state_dict(seed, depth)
     g = torch.Generator().manual_seed(seed)
     grouped = (num_groups, width_per_group) != (1, 64)
     gx = torch.Generator().manual_seed(seed + 7919) if grouped else g
@@ -68,6 +74,37 @@ def backbone_state_dict(seed: int = 0, depth: int = 50, num_groups: int = 1, wid
             _bn(gx, sd, f"{q}.conv3.norm", cout)
             cin = cout
     for stage, c in ((3, 512), (4, 1024), (5, 2048)):
+        sd[f"backbone.fpn_lateral{stage}.weight"] = _conv(g, 256, c, 1, std=math.sqrt(1.0 / c))
+        sd[f"backbone.fpn_lateral{stage}.bias"] = torch.randn(256, generator=g) * 0.1
+        sd[f"backbone.fpn_output{stage}.weight"] = _conv(g, 256, 256, 3, std=math.sqrt(1.0 / 2304))
+        sd[f"backbone.fpn_output{stage}.bias"] = torch.randn(256, generator=g) * 0.1
+    for n in ("p6", "p7"):
+        sd[f"backbone.top_block.{n}.weight"] = _conv(g, 256, 256, 3, std=math.sqrt(1.0 / 2304))
+        sd[f"backbone.top_block.{n}.bias"] = torch.randn(256, generator=g) * 0.1
+    return sd
+
+
+def _basic_backbone_state_dict(seed: int, depth: int) -> Dict[str, torch.Tensor]:
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    p = "backbone.bottom_up"
+    sd[f"{p}.stem.conv1.weight"] = _conv(g, 64, 3, 7) / 64.0
+    _bn(g, sd, f"{p}.stem.conv1.norm", 64)
+    cin = 64
+    for si, nb in enumerate(STAGE_BLOCKS[depth]):
+        cout = 64 << si
+        for bi in range(nb):
+            q = f"{p}.res{si + 2}.{bi}"
+            if cin != cout:
+                sd[f"{q}.shortcut.weight"] = _conv(g, cout, cin, 1)
+                _bn(g, sd, f"{q}.shortcut.norm", cout)
+            sd[f"{q}.conv1.weight"] = _conv(g, cout, cin, 3)
+            _bn(g, sd, f"{q}.conv1.norm", cout)
+            # keep the residual branch small so activations stay O(1) through the blocks
+            sd[f"{q}.conv2.weight"] = _conv(g, cout, cout, 3) * 0.25
+            _bn(g, sd, f"{q}.conv2.norm", cout)
+            cin = cout
+    for stage, c in ((3, 128), (4, 256), (5, 512)):
         sd[f"backbone.fpn_lateral{stage}.weight"] = _conv(g, 256, c, 1, std=math.sqrt(1.0 / c))
         sd[f"backbone.fpn_lateral{stage}.bias"] = torch.randn(256, generator=g) * 0.1
         sd[f"backbone.fpn_output{stage}.weight"] = _conv(g, 256, 256, 3, std=math.sqrt(1.0 / 2304))
