@@ -136,6 +136,19 @@ int sylph_export_pyramid(sylph_ctx* ctx, int level, float* out_nchw_dev);
  * CondConvBasic sylph/modeling/meta_fcos/head_utils.py:60-81).  cls_conv_dev: (N,256) fp32,
  * cls_bias_dev: (N) fp32 or NULL.  Results stay in the context (see sylph_export_head). */
 int sylph_fcos_head(sylph_ctx* ctx, const float* cls_conv_dev, const float* cls_bias_dev, int N);
+/* The same for a batch whose images belong to DIFFERENT episodes: image i is run with the codes of episode image_episode[i], and its head
+ * outputs (and the detections sylph_decode_nms then returns for it) are those of sylph_fcos_head with that episode's codes on the same
+ * batch -- bit for bit in bf16.  Everything in front of the class-conditional conv is class-agnostic (fcos.py:582-667,
+ * head_utils.py:60-81), so one large step can serve the queries of many episodes; it stands for that many turns of the reference's
+ * batch-1 query loop (sylph/evaluation/meta_learn_evaluation.py:421-426).
+ * cls_conv_dev: (sum_e N_e, 256) fp32, episode after episode; cls_bias_dev: (sum_e N_e) fp32 or NULL; n_classes: host, E entries,
+ * each >= 1; image_episode: host, B entries in [0, E).  An episode that no image uses is allowed.
+ * Afterwards sylph_decode_nms numbers classes within the image's own episode: classes_dev[i][k] < N_i, and the cand_dev ordinal is
+ * (loc_base + loc) * N_i + cls.  sylph_export_head writes logits (B, max_e N_e, h, w); entries [i, n >= N_i] are unspecified.
+ * bf16 with FCOS.NORM "GN" and every N_e <= 32 is one class-conditional launch for the whole batch; any other combination runs, per
+ * episode, the kernel sylph_fcos_head picks for that N over the episode's images. */
+int sylph_fcos_head_episodes(sylph_ctx* ctx, int E, const float* cls_conv_dev, const float* cls_bias_dev, const int* n_classes,
+                             const int* image_episode);
 /* MetaFCOSHead.forward with support_set_per_class_code = None -> forward_base_train (fcos.py:543-578): the towers and the checkpoint's
  * OWN classifier `cls_logits` (nn.Conv2d(256, NUM_CLASSES, CLS_LOGITS_KERNEL_SIZE 1 or 3, padding k // 2), fcos.py:418-427) -- the base
  * detector (run_type None) and evaluation with the pretrained codes.  *num_classes receives NUM_CLASSES. */
@@ -156,7 +169,7 @@ int sylph_import_head(sylph_ctx* ctx, int N, int level, const float* logits_nchw
  * out_heights/out_widths (host, may be NULL = image size): the "height"/"width" of each input dict.
  * Device outputs, row-major [B][max_out][...]; counts_dev[B]; status_dev[1] (bit0 candidate
  * overflow, bit1 output truncated).  cand_dev: (level, location, class) ordinal of each detection.
- * Decode reads the outputs of the most recent head call (sylph_fcos_head, sylph_fcos_head_pretrained or sylph_import_head) of the
+ * Decode reads the outputs of the most recent head call (sylph_fcos_head, sylph_fcos_head_episodes, sylph_fcos_head_pretrained or sylph_import_head) of the
  * current batch; any order of stage calls on one context is valid (a head need not be followed by a decode, a decode may be repeated,
  * and a decode that reported a status bit leaves nothing behind for the next one). */
 int sylph_decode_nms(sylph_ctx* ctx, const int* out_heights, const int* out_widths, int max_out, float* boxes_dev,

@@ -227,7 +227,7 @@ int build_decode(sylph_ctx* c, Plan* P) {
     for (int l = 0; l < L; ++l) {
       DecodeSeg d;
       d.row0 = b * P->Ltot + P->off[l]; d.nloc = P->hl[l] * P->wl[l]; d.W = P->wl[l];
-      d.stride = c->cfg.strides[l]; d.level = l; d.image = b; d.loc_base = lb; d.pad = 0;
+      d.stride = c->cfg.strides[l]; d.level = l; d.image = b; d.loc_base = lb; d.ncls = 0;
       lb += (unsigned)d.nloc;
       ds.push_back(d);
     }
@@ -314,6 +314,30 @@ int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow) {
   return 0;
 }
 
+// conv_igemm launch of an N-way class-conditional conv over a tile list (128-row tiles up to 32 classes, head_BM-row tiles above);
+// wt: packed codes [Npad][256], bias: Npad floats or nullptr; rows: what the tiles cover (profile FLOPs)
+static int cond_igemm(sylph_ctx* c, Plan* P, const void* wt, const float* bias, int N, size_t rows, const int2* tiles32, int n32,
+                      const int2* tilesBM, int nBM) {
+  const int bn = N >= 128 ? 128 : (N > 32 ? 64 : 32);
+  const int Npad = (N + bn - 1) / bn * bn;
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.in = P->cls_feat; a.wt = wt; a.out = P->logits;
+  a.shift = bias;
+  a.zeros = c->zeros; a.tap_dy = 1;
+  a.segs = P->head_segs;
+  int BM = P->head_BM;
+  if (bn == 32) { BM = 128; a.tiles = tiles32; a.n_mtiles = n32; }
+  else { a.tiles = tilesBM; a.n_mtiles = nBM; }
+  a.n_ntiles = Npad / bn;
+  a.Cin = 256; a.Cout = N; a.KH = 1; a.KW = 1; a.stride = 1; a.pad = 0;
+  a.in_ld = 256; a.out_ld = P->logits_ld;
+  const DType dt = c->dt;
+  KCHK(timed_op(c, "conv_igemm_kernel", 2.0 * (double)rows * N * 256.0, c->stream, [=](hipStream_t st) { return launch_conv(dt, true, a, BM, bn, st); }),
+       "cond_cls_logits");
+  return 0;
+}
+
 // the class-conditional conv as its own launch(es): logits[rows][Npad] fp32 from the cls tower output, the packed codes and
 // P->bias_pad (sylph_fcos_head; sylph_export_head after a fused many-way head)
 int run_cond_logits(sylph_ctx* c, Plan* P) {
@@ -332,21 +356,101 @@ int run_cond_logits(sylph_ctx* c, Plan* P) {
     }
     KCHK(P->cls_apply(c->stream), "gn_apply (cls tower, last layer)");
   }
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.in = P->cls_feat; a.wt = P->code_w; a.out = P->logits;
-  a.shift = bias;
-  a.zeros = c->zeros; a.tap_dy = 1;
-  a.segs = P->head_segs;
-  int BM = P->head_BM;
-  if (bn == 32) { BM = 128; a.tiles = P->head_tiles32; a.n_mtiles = P->head_mtiles32; }
-  else { a.tiles = P->head_tiles; a.n_mtiles = P->head_mtiles; }
-  a.n_ntiles = Npad / bn;
-  a.Cin = 256; a.Cout = N; a.KH = 1; a.KW = 1; a.stride = 1; a.pad = 0;
-  a.in_ld = 256; a.out_ld = Npad;
-  const DType dt = c->dt;
-  KCHK(timed_op(c, "conv_igemm_kernel", 2.0 * (double)rows * N * 256.0, c->stream, [=](hipStream_t st) { return launch_conv(dt, true, a, BM, bn, st); }),
-       "cond_cls_logits");
+  return cond_igemm(c, P, P->code_w, bias, N, rows, P->head_tiles32, P->head_mtiles32, P->head_tiles, P->head_mtiles);
+}
+
+// ---- mixed-episode head (sylph_fcos_head_episodes) ---------------------------------------------------------------------------------
+
+// the kernel sylph_fcos_head runs for an N-way episode: GroupNorm fused into the conv, conv fused with the scan, or plain conv_igemm
+enum class EpKind { gn_logits, scan, igemm };
+static EpKind ep_kind(const sylph_ctx* c, const Plan* P, int N) {
+  if (c->dt == DT_BF16 && P->cls_coef) return N <= 32 ? EpKind::gn_logits : EpKind::scan;
+  return EpKind::igemm;
+}
+
+// Host and device tables of a mixed batch: packed-row layout of the episodes' codes, segment -> code rows, the head's tiles regrouped
+// episode by episode, the decode's segment table with per-image class counts.  Rebuilt only when (n_classes, image_episode) differ
+// from the previous call's on this plan: a serving loop that keeps its assignment uploads nothing.
+static int ep_tables(sylph_ctx* c, Plan* P, int E, const int* n_classes, const int* image_episode) {
+  const int L = c->cfg.nlevels, B = P->B, nseg = B * L;
+  std::vector<int> en(n_classes, n_classes + E), ei(image_episode, image_episode + B);
+  if (P->dsegs_ep && en == P->ep_n && ei == P->ep_image) return 0;
+  P->ep_n.clear(); P->ep_image.clear();  // (a failure below leaves no key that would match half-written tables)
+  std::vector<int> row0(E), src_row;
+  int src = 0;
+  for (int e = 0; e < E; ++e) {
+    const int N = en[e], bn = N >= 128 ? 128 : (N > 32 ? 64 : 32), npad = (N + bn - 1) / bn * bn;
+    row0[e] = (int)src_row.size();
+    for (int r = 0; r < npad; ++r) src_row.push_back(r < N ? src + r : -1);
+    src += N;
+  }
+  const int rows = (int)src_row.size();
+  std::vector<std::vector<int>> members(E);
+  for (int b = 0; b < B; ++b) members[ei[b]].push_back(b);
+  std::vector<int2> tiles, t32(E), tBM(E);
+  for (int pass = 0; pass < 2; ++pass) {  // the tile order inside an image is make_geom's
+    const int BM = pass == 0 ? 128 : P->head_BM;
+    for (int e = 0; e < E; ++e) {
+      const int first = (int)tiles.size();
+      for (int b : members[e])
+        for (int l = 0; l < L; ++l)
+          for (int r = 0; r < P->hl[l] * P->wl[l]; r += BM) tiles.push_back(make_int2(b * L + l, r));
+      (pass == 0 ? t32 : tBM)[e] = make_int2(first, (int)tiles.size() - first);
+    }
+  }
+  if ((int)tiles.size() != P->head_mtiles32 + P->head_mtiles) return fail("internal: episode tile tables");
+  std::vector<int> seg_row0(nseg);
+  std::vector<DecodeSeg> ds;
+  for (int b = 0; b < B; ++b) {
+    const int N = en[ei[b]];
+    unsigned lb = 0;
+    for (int l = 0; l < L; ++l) {
+      seg_row0[b * L + l] = row0[ei[b]];
+      DecodeSeg d;
+      d.row0 = b * P->Ltot + P->off[l]; d.nloc = P->hl[l] * P->wl[l]; d.W = P->wl[l];
+      d.stride = c->cfg.strides[l]; d.level = l; d.image = b; d.loc_base = lb;
+      d.ncls = ep_kind(c, P, N) == EpKind::scan ? -N : N;
+      lb += (unsigned)d.nloc;
+      ds.push_back(d);
+    }
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));  // the previous step may still be reading the tables
+  if (rows > P->ep_rows_cap) {
+    c->dfree(P->ep_code_w); c->dfree(P->ep_bias); c->dfree(P->ep_src_row);
+    P->ep_code_w = nullptr; P->ep_bias = nullptr; P->ep_src_row = nullptr; P->ep_rows_cap = 0;
+    RET(c->dalloc(&P->ep_code_w, (size_t)rows * 256 * c->esz()));
+    RET(c->dalloc((void**)&P->ep_bias, (size_t)2 * rows * sizeof(float)));
+    RET(c->dalloc((void**)&P->ep_src_row, (size_t)rows * sizeof(int)));
+    P->ep_rows_cap = rows;
+  }
+  if (!P->ep_seg_row0) RET(c->dalloc((void**)&P->ep_seg_row0, (size_t)nseg * sizeof(int)));
+  if (!P->ep_tiles_dev) RET(c->dalloc((void**)&P->ep_tiles_dev, tiles.size() * sizeof(int2)));
+  if (!P->dsegs_ep) RET(c->dalloc((void**)&P->dsegs_ep, (size_t)nseg * sizeof(DecodeSeg)));
+  HIPCHK(hipMemcpy(P->ep_src_row, src_row.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(P->ep_seg_row0, seg_row0.data(), (size_t)nseg * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(P->ep_tiles_dev, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(P->dsegs_ep, ds.data(), ds.size() * sizeof(DecodeSeg), hipMemcpyHostToDevice));
+  P->ep_rows = rows; P->ep_row0 = row0; P->ep_tiles32 = t32; P->ep_tilesBM = tBM;
+  P->ep_n = en; P->ep_image = ei;
+  return 0;
+}
+
+// conv_igemm over the tiles of episode e (the unfused class-conditional conv of sylph_fcos_head on a sub-list of its tile table)
+static int ep_igemm(sylph_ctx* c, Plan* P, int e) {
+  const size_t r0 = (size_t)P->ep_row0[e];
+  const int2 a = P->ep_tiles32[e], b = P->ep_tilesBM[e];
+  if (a.y == 0) return 0;  // an episode no image uses
+  int n_img = 0;
+  for (int v : P->ep_image) n_img += v == e;
+  return cond_igemm(c, P, (const char*)P->ep_code_w + r0 * 256 * c->esz(), P->has_bias ? P->ep_bias + r0 : nullptr, P->ep_n[e],
+                    (size_t)n_img * P->Ltot, P->ep_tiles_dev + a.x, a.y, P->ep_tiles_dev + b.x, b.y);
+}
+
+// sylph_export_head after a mixed head some of whose episodes took the fused scan: their logits were never written
+int run_ep_stale_logits(sylph_ctx* c, Plan* P) {
+  KCHK(P->cls_apply(c->stream), "gn_apply (cls tower, last layer)");
+  for (size_t e = 0; e < P->ep_n.size(); ++e)
+    if (ep_kind(c, P, P->ep_n[e]) == EpKind::scan) RET(ep_igemm(c, P, (int)e));
   return 0;
 }
 
@@ -361,6 +465,7 @@ int sylph_import_head(sylph_ctx* c, int N, int level, const float* logits, const
   if (level < 0 || level >= c->cfg.nlevels) return fail("bad level");
   OwnerScope own(c, P);
   BUILD(build_head(c, P), P);
+  P->ep_on = false;
   if (!P->logits || N != P->ncls) RET(ensure_logits(c, P, N));
   P->scan_fused = false; P->logits_stale = false;
   const int hw = P->hl[level] * P->wl[level];
@@ -381,6 +486,7 @@ int sylph_fcos_head(sylph_ctx* c, const float* cls_conv, const float* cls_bias, 
   if (!cls_conv) return fail("cls_conv is NULL");
   OwnerScope own(c, P);
   BUILD(build_head(c, P), P);
+  P->ep_on = false;
   const size_t rows = (size_t)P->B * P->Ltot;
   const int bn = N >= 128 ? 128 : (N > 32 ? 64 : 32);
   const int Npad = (N + bn - 1) / bn * bn;
@@ -415,12 +521,91 @@ int sylph_fcos_head(sylph_ctx* c, const float* cls_conv, const float* cls_bias, 
     P->cand_dirty = true;
     KCHK(timed_op(c, "logits_scan_kernel", 2.0 * (double)rows * N * 256.0, c->stream, [=](hipStream_t st) {
            return launch_logits_scan(PP->cls_feat, 256, PP->cls_coef, PP->code_w, PP->code_wf, bias_scan, PP->head_segs, PP->head_tiles32,
-                                     PP->head_mtiles32, PP->pred, 8, d, PP->dbuf, nseg, st);
+                                     PP->head_mtiles32, PP->pred, 8, d, PP->dbuf, nseg, true, st);
          }), "logits_scan");
     P->scan_fused = true; P->logits_stale = true;
     return 0;
   }
   return run_cond_logits(c, P);
+}
+
+int sylph_fcos_head_episodes(sylph_ctx* c, int E, const float* cls_conv, const float* cls_bias, const int* n_classes, const int* image_episode) {
+  Plan* P = c->cur;
+  if (!P) return fail("no current batch");
+  if (E <= 0) return fail("no episodes (E <= 0)");
+  if (!cls_conv) return fail("cls_conv is NULL");
+  if (!n_classes || !image_episode) return fail("n_classes / image_episode is NULL");
+  int maxN = 0;
+  for (int e = 0; e < E; ++e) {
+    if (n_classes[e] <= 0) return fail("class_code is empty (episode " + std::to_string(e) + ")");
+    if (n_classes[e] > maxN) maxN = n_classes[e];
+  }
+  for (int b = 0; b < P->B; ++b)
+    if (image_episode[b] < 0 || image_episode[b] >= E)
+      return fail("image_episode[" + std::to_string(b) + "] = " + std::to_string(image_episode[b]) + " is not in [0, " + std::to_string(E) + ")");
+  OwnerScope own(c, P);
+  BUILD(build_head(c, P), P);
+  P->ep_on = false;
+  if (ep_kind(c, P, maxN) == EpKind::scan && maxN >= 65536) return fail("a mixed batch takes episodes of fewer than 65536 classes");
+  RET(ensure_logits(c, P, maxN, true));  // row pitch, candidate capacity and export width: those of the widest episode
+  RET(ep_tables(c, P, E, n_classes, image_episode));
+  P->has_bias = c->cfg.cond_use_bias && cls_bias;
+  // one launch packs every episode's codes and biases (in front of the towers, as in sylph_fcos_head)
+  KCHK(launch_pack_codes_episodes(c->dt, cls_conv, P->ep_src_row, P->ep_rows, 256, P->ep_code_w, P->has_bias ? cls_bias : nullptr, P->ep_bias,
+                                  P->ep_bias + P->ep_rows_cap, c->stream), "pack_codes_episodes");
+  RET(run_ops(c, P->head_ops, "fcos_head"));
+  P->scan_fused = false; P->logits_stale = false; P->ep_any_fused = false;
+  P->ep_on = true;
+  const float* bias = P->has_bias ? P->ep_bias : nullptr;
+  const Plan* PP = P;
+  if (ep_kind(c, P, maxN) == EpKind::gn_logits) {
+    // bf16, every episode <= 32 classes: ONE launch for the whole batch, whatever E is (head_fused.hip)
+    KCHK(timed_op(c, "gn_logits_episodes_kernel", 2.0 * (double)P->B * P->Ltot * maxN * 256.0, c->stream, [=](hipStream_t st) {
+           return launch_gn_logits_episodes(PP->cls_feat, 256, PP->cls_coef, PP->ep_code_w, bias, PP->ep_seg_row0, PP->logits, PP->logits_ld,
+                                            PP->head_segs, PP->head_tiles32, PP->head_mtiles32, st);
+         }), "gn_logits_episodes");
+    return 0;
+  }
+  // everything else: per episode, the kernel sylph_fcos_head picks for that N and dtype, over the episode's tiles
+  const int nseg = P->B * c->cfg.nlevels;
+  for (int e = 0; e < E; ++e) {
+    const int N = n_classes[e];
+    const int2 t32 = P->ep_tiles32[e];
+    if (t32.y == 0) continue;
+    const size_t r0 = (size_t)P->ep_row0[e];
+    const void* wt = (const char*)P->ep_code_w + r0 * 256 * c->esz();
+    const double fl = 2.0 * (double)(t32.y) * 128.0 * N * 256.0;
+    const int2* tl = P->ep_tiles_dev + t32.x;
+    switch (ep_kind(c, P, N)) {
+      case EpKind::gn_logits: {
+        const float* be = bias ? bias + r0 : nullptr;
+        KCHK(timed_op(c, "gn_logits_kernel", fl, c->stream, [=](hipStream_t st) {
+               return launch_gn_logits(PP->cls_feat, 256, PP->cls_coef, wt, be, N, PP->logits, PP->logits_ld, PP->head_segs, tl, t32.y, st);
+             }), "gn_logits");
+        break;
+      }
+      case EpKind::scan: {
+        if (!P->ep_any_fused) {  // first fused episode of the call: from here on the counters hold scan candidates (see sylph_fcos_head)
+          BUILD(build_decode(c, P), P);
+          RET(ensure_cand_cap(c, P));
+          P->cand_dirty = true; P->ep_any_fused = true; P->logits_stale = true;
+          HIPCHK(hipMemsetAsync(P->dbuf.cand_count, 0, (size_t)nseg * 4, c->stream));
+        }
+        DecodeCfg d = decode_cfg(c, P, 0);
+        d.num_classes = N;
+        const float* bias_scan = P->ep_bias + P->ep_rows_cap + r0;
+        KCHK(timed_op(c, "logits_scan_kernel", fl, c->stream, [=](hipStream_t st) {
+               return launch_logits_scan(PP->cls_feat, 256, PP->cls_coef, wt, PP->code_wf, bias_scan, PP->head_segs, tl, t32.y, PP->pred, 8, d,
+                                         PP->dbuf, nseg, false, st);
+             }), "logits_scan");
+        break;
+      }
+      case EpKind::igemm:
+        RET(ep_igemm(c, P, e));
+        break;
+    }
+  }
+  return 0;
 }
 
 int sylph_fcos_head_pretrained(sylph_ctx* c, int* num_classes) {
@@ -430,6 +615,7 @@ int sylph_fcos_head_pretrained(sylph_ctx* c, int* num_classes) {
   OwnerScope own(c, P);
   BUILD(build_head(c, P), P);
   const int N = c->cls_logits.Cout;
+  P->ep_on = false;
   RET(ensure_logits(c, P, N));
   if (c->cls_logits.Cout_pad != P->logits_ld) return fail("internal: cls_logits padding");
   if (P->cls_logits_dst != P->logits) {  // (re)build the conv launch for this plan's buffers
@@ -452,7 +638,8 @@ int sylph_export_head(sylph_ctx* c, int level, float* logits, float* reg, float*
   if (level < 0 || level >= c->cfg.nlevels) return fail("bad level");
   if (logits && P->logits_stale) {  // fused many-way head: the logits were never written
     OwnerScope own(c, P);
-    RET(run_cond_logits(c, P));
+    if (P->ep_on) RET(run_ep_stale_logits(c, P));
+    else RET(run_cond_logits(c, P));
     P->logits_stale = false;
   }
   const int hw = P->hl[level] * P->wl[level];
@@ -500,11 +687,14 @@ int sylph_decode_nms(sylph_ctx* c, const int* oh, const int* ow, int max_out, fl
   // the candidate counters are left zero by every decode that ran its own scan; after a fused many-way scan (whose launcher clears them
   // itself and whose candidates stay valid for a repeated decode) -- decoded or not: sylph_fcos_head marks the table dirty -- the plain
   // scan starts from a cleared table again.  A steady stream of fused or of plain steps never clears here (no extra launch)
-  if (!P->scan_fused && P->cand_dirty) HIPCHK(hipMemsetAsync(P->dbuf.cand_count, 0, (size_t)P->B * L * 4, c->stream));
-  P->cand_dirty = P->scan_fused;
+  // A mixed-episode head whose many-way episodes took the fused scan (ep_partial) is both at once, per image: the scan below skips the
+  // images whose candidates are there and nms_kernel keeps their counters; the table stays dirty for whatever plain head comes next.
+  const bool ep_partial = P->ep_on && P->ep_any_fused;
+  if (!P->scan_fused && !ep_partial && P->cand_dirty) HIPCHK(hipMemsetAsync(P->dbuf.cand_count, 0, (size_t)P->B * L * 4, c->stream));
+  P->cand_dirty = P->scan_fused || ep_partial;
   int nwb = (L * c->cfg.pre_nms_topk + 63) / 64;
   if (nwb > P->pool_cap / 64) nwb = P->pool_cap / 64;
-  KCHK(launch_decode(d, P->dsegs, P->B * L, P->hl[0] * P->wl[0], P->B, nwb, P->logits, P->pred, 8, P->dbuf,
+  KCHK(launch_decode(d, P->ep_on ? P->dsegs_ep : P->dsegs, P->B * L, P->hl[0] * P->wl[0], P->B, nwb, P->logits, P->pred, 8, P->dbuf,
                      P->img_out_dev, boxes, scores, classes, levels, locations, cand, counts, status, P->scan_fused, c->stream),
        "decode_nms");
   return 0;

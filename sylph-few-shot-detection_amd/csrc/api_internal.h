@@ -239,6 +239,21 @@ struct Plan {
   bool cand_dirty = false;    // the last decode left the candidate counters non-zero (fused scan: see sylph_decode_nms)
   bool scan_fused = false;    // the candidate buffers were filled by logits_scan_kernel (many-way head): decode skips its scan
   bool logits_stale = false;  // ... and the logits buffer was not written: sylph_export_head runs the unfused conv first
+  // Mixed-episode head (sylph_fcos_head_episodes): image i was run with the codes of episode ep_image[i].  ep_on says that the head outputs
+  // of the plan are such a head's; every other head entry (sylph_fcos_head, _pretrained, sylph_import_head) clears it, and with it every
+  // per-image fact below stops being read: the decode goes back to the plan's own segment table (DecodeSeg::ncls 0) and to scan_fused.
+  bool ep_on = false;
+  bool ep_any_fused = false;          // some episode has more than 32 classes (bf16): logits_scan_kernel left its images' candidates
+  std::vector<int> ep_n, ep_image;    // classes per episode, episode per image: what the device tables below were built for
+  std::vector<int> ep_row0;           // per episode: its first row in the packed code / bias tables (rows padded per episode as in sylph_fcos_head)
+  std::vector<int2> ep_tiles32, ep_tilesBM;  // per episode: {first, count} of its tiles in ep_tiles_dev (128-row tiles | head_BM-row tiles)
+  int ep_rows = 0, ep_rows_cap = 0;   // packed rows of all episodes; capacity of ep_code_w / ep_bias / ep_src_row
+  void* ep_code_w = nullptr;          // [ep_rows][256] compute dtype
+  float* ep_bias = nullptr;           // [2][ep_rows_cap]: zero-padded biases | the same with -inf in the padding rows (logits_scan_kernel)
+  int* ep_src_row = nullptr;          // [ep_rows]: row of the caller's (sum N, 256) table, -1 for a padding row
+  int* ep_seg_row0 = nullptr;         // [B * levels]: first packed row of the segment's episode
+  int2* ep_tiles_dev = nullptr;       // the tiles of the head's two tile tables regrouped episode by episode
+  DecodeSeg* dsegs_ep = nullptr;      // the decode's segment table with DecodeSeg::ncls set per image
   float* bias_pad = nullptr;  // fp32 class biases of the last sylph_fcos_head: [0, cap) zero-padded to the packed code rows; [cap, 2 cap) the
                               // same with -inf from class N on (logits_scan_kernel: padded classes never pass the threshold)
   int bias_pad_cap = 0;

@@ -35,6 +35,13 @@ __device__ __forceinline__ float quality_from(float ctr_logit, float iou_logit, 
   return sqrtf(sigmoid_f(iou_logit) * sigmoid_f(ctr_logit));
 }
 
+// Class count of a segment's image.  A uniform head leaves DecodeSeg::ncls 0 and the batch-wide cfg.num_classes holds; a mixed-episode
+// head (sylph_fcos_head_episodes) sets it to the N of the image's own episode -- negated where logits_scan_kernel has already left
+// that image's candidates (its scan is skipped, and nms_kernel keeps its counters for a repeated decode).
+__device__ __forceinline__ int seg_ncls(const DecodeCfg& cfg, const DecodeSeg& sg) {
+  return sg.ncls > 0 ? sg.ncls : (sg.ncls < 0 ? -sg.ncls : cfg.num_classes);
+}
+
 constexpr int SCAN_ROWS = 64;     // minimum locations per block
 constexpr int SCAN_UNROLL = 4;    // loads in flight per thread (16 B each on the vector path)
 constexpr int SCAN_STAGE = 2048;  // candidates a block collects in LDS before it reserves a range of the (image, level) buffer
@@ -55,10 +62,10 @@ __global__ __launch_bounds__(256) void decode_scan_kernel(const DecodeCfg cfg, c
   const int seg = blockIdx.y;
   const DecodeSeg sg = segs[seg];
   const int r_begin = blockIdx.x * rows_per_block;
-  if (r_begin >= sg.nloc) return;
+  if (r_begin >= sg.nloc || sg.ncls < 0) return;
   const int r_end = min(sg.nloc, r_begin + rows_per_block);
   constexpr int W = 4;  // classes per load
-  const int N = cfg.num_classes;
+  const int N = seg_ncls(cfg, sg);
   const int G = (N + W - 1) / W;  // W-wide class groups per location
   const int total = (r_end - r_begin) * G;
   __shared__ unsigned s_key[SCAN_STAGE], s_idx[SCAN_STAGE];
@@ -189,7 +196,7 @@ __device__ __forceinline__ unsigned sel_bin_of(unsigned kbits) { return min(kbit
 
 __device__ __forceinline__ unsigned long long pool_composite(const DecodeCfg& cfg, const DecodeSeg& sg, unsigned kbits, unsigned ix) {
   const float sq = sqrtf(__uint_as_float(kbits));
-  const unsigned ord = sg.loc_base * (unsigned)cfg.num_classes + ix;
+  const unsigned ord = sg.loc_base * (unsigned)seg_ncls(cfg, sg) + ix;
   return ((unsigned long long)__float_as_uint(sq) << 32) | (unsigned long long)(~ord);
 }
 
@@ -597,9 +604,9 @@ __global__ __launch_bounds__(256, 2) void logits_scan_kernel(const bf16_t* __res
 
 int launch_logits_scan(const void* x, int ld, const float2* coef, const void* w, void* wf_ws, const float* bias_scan,
                        const SegDesc* segs, const int2* tiles, int n_tiles, const float* pred, int pred_ld, const DecodeCfg& cfg,
-                       const DecodeBuffers& buf, int nseg, hipStream_t s) {
+                       const DecodeBuffers& buf, int nseg, bool clear_counts, hipStream_t s) {
   if (cfg.num_classes <= 0 || cfg.num_classes >= 65536 || n_tiles <= 0) return (int)hipErrorInvalidValue;
-  (void)hipMemsetAsync(buf.cand_count, 0, sizeof(unsigned) * nseg, s);
+  if (clear_counts) (void)hipMemsetAsync(buf.cand_count, 0, sizeof(unsigned) * nseg, s);
   const int n_frag = ((cfg.num_classes + 31) / 32) * 16;
   hipLaunchKernelGGL(pack_code_fragments_kernel, dim3((n_frag * 64 + 255) / 256), dim3(256), 0, s, (const bf16_t*)w, (bf16_t*)wf_ws,
                      n_frag);
@@ -663,8 +670,9 @@ __global__ __launch_bounds__(1024) void decode_sort_kernel(const DecodeCfg cfg, 
     chunk_pass(size, 4);
     __syncthreads();
   }
-  const int N = cfg.num_classes, L = cfg.nlevels;
+  const int L = cfg.nlevels;
   const DecodeSeg* isegs = segs + (size_t)img * L;
+  const int N = seg_ncls(cfg, isegs[0]);
   for (unsigned i = tid; i < n; i += 1024) {
     const unsigned long long kk = keys[i];
     const unsigned ord = ~(unsigned)(kk & 0xffffffffull);
@@ -719,7 +727,8 @@ __device__ __forceinline__ bool nms_overlap(float x1, float y1, float x2, float 
 //      writes the outputs; the walk stops as soon as the next chunk's best score is below the K-th kept score.
 // Only the chunks the walk visits cost anything (typically 3-10 of up to 79), and there is no B x pool x pool / 64 suppression
 // matrix in HBM: rounds 1-3 built that matrix for ALL chunk pairs in a separate launch (0.19 ms at the headline shape, 0.5 GB).
-__global__ __launch_bounds__(1024) void nms_kernel(const DecodeCfg cfg, const DecodeBuffers buf, const ImageOut* __restrict__ img_out,
+__global__ __launch_bounds__(1024) void nms_kernel(const DecodeCfg cfg, const DecodeSeg* __restrict__ segs, const DecodeBuffers buf,
+                                                   const ImageOut* __restrict__ img_out,
                                                    float* out_boxes, float* out_scores, int* out_classes, int* out_levels,
                                                    float* out_locations, int* out_cand, int* out_counts, int* status_out, int clear_cands) {
   extern __shared__ unsigned short kept_pos[];  // [pool_cap]: pool positions of the boxes kept so far
@@ -860,7 +869,8 @@ __global__ __launch_bounds__(1024) void nms_kernel(const DecodeCfg cfg, const De
   const int L = cfg.nlevels;
   __syncthreads();
   if (t == 0) buf.pool_count[img] = 0u;
-  if (clear_cands && t < L) buf.cand_count[(size_t)img * L + t] = 0u;  // (fused many-way scan: its launcher clears them itself)
+  // (fused many-way scan, batch-wide or of this image's episode: its launcher clears them itself)
+  if (clear_cands && t < L && segs[(size_t)img * L].ncls >= 0) buf.cand_count[(size_t)img * L + t] = 0u;
   unsigned* ws = buf.sel_ws + (size_t)img * L * SEL_WS;
   for (int i = t; i < L * SEL_WS; i += 1024) ws[i] = 0u;
   if (t == 0) {
@@ -908,7 +918,7 @@ int launch_decode(const DecodeCfg& cfg, const DecodeSeg* segs_dev, int nseg, int
   hipLaunchKernelGGL(decode_sort_kernel, dim3(B), dim3(1024), sizeof(unsigned long long) * cfg.pool_cap, s, cfg,
                      segs_dev, pred, pred_ld, buf);
   (void)nw_bound;
-  hipLaunchKernelGGL(nms_kernel, dim3(B), dim3(1024), sizeof(unsigned short) * cfg.pool_cap, s, cfg, buf, img_out_dev, out_boxes, out_scores,
+  hipLaunchKernelGGL(nms_kernel, dim3(B), dim3(1024), sizeof(unsigned short) * cfg.pool_cap, s, cfg, segs_dev, buf, img_out_dev, out_boxes, out_scores,
                      out_classes, out_levels, out_locations, out_cand, out_counts, status_out, candidates_ready ? 0 : 1);
   return (int)hipGetLastError();
 }

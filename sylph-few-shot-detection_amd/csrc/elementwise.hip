@@ -591,4 +591,42 @@ int launch_pack_codes(DType dt, const float* w, int N, int C, int Npad, void* ou
   return (int)hipGetLastError();
 }
 
+// launch_pack_codes for the episodes of a mixed batch (sylph_fcos_head_episodes): every episode's rows, zero-padded to its own tile
+// width, behind one another in ONE table -- the launch count of a mixed step does not grow with the number of episodes
+template <typename T, bool SPLIT>
+__global__ void pack_codes_episodes_kernel(const float* __restrict__ w, const int* __restrict__ src_row, int rows, int C, T* __restrict__ out,
+                                           const float* __restrict__ bias, float* __restrict__ bias_pad, float* __restrict__ bias_scan) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < rows) {
+    const int sr = src_row[i];
+    const float b = (bias && sr >= 0) ? bias[sr] : 0.f;
+    bias_pad[i] = b;
+    bias_scan[i] = sr >= 0 ? b : __uint_as_float(0xff800000u);
+  }
+  if (i >= rows * C) return;
+  const int r = i / C, sr = src_row[r];
+  const float v = sr >= 0 ? w[(size_t)sr * C + (i - r * C)] : 0.f;
+  if constexpr (SPLIT) {
+    const bf16_t hi = (bf16_t)v;
+    const size_t o = (size_t)(i >> 5) * 64 + (i & 31);
+    out[o] = hi;
+    out[o + 32] = (bf16_t)(v - (float)hi);
+  } else {
+    out[i] = Cvt<T>::from_f(v);
+  }
+}
+
+int launch_pack_codes_episodes(DType dt, const float* w, const int* src_row, int rows, int C, void* out, const float* bias, float* bias_pad,
+                               float* bias_scan, hipStream_t s) {
+  dim3 grid((rows * C + 255) / 256), block(256);
+  if (dt == DT_F32S) {
+    if (C % 32 != 0) return -1;
+    hipLaunchKernelGGL((pack_codes_episodes_kernel<bf16_t, true>), grid, block, 0, s, w, src_row, rows, C, (bf16_t*)out, bias, bias_pad, bias_scan);
+  } else if (dt == DT_BF16)
+    hipLaunchKernelGGL((pack_codes_episodes_kernel<bf16_t, false>), grid, block, 0, s, w, src_row, rows, C, (bf16_t*)out, bias, bias_pad, bias_scan);
+  else
+    hipLaunchKernelGGL((pack_codes_episodes_kernel<float, false>), grid, block, 0, s, w, src_row, rows, C, (float*)out, bias, bias_pad, bias_scan);
+  return (int)hipGetLastError();
+}
+
 }  // namespace sylph

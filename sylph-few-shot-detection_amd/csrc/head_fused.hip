@@ -9,32 +9,47 @@
 // k-step, a row's 512 bytes over 16 k-steps), applies the same fused multiply-add + ReLU + bf16 rounding as the apply kernel
 // (bit-identical operand values), and multiplies by the 32 x 256 code matrix held in registers.  No LDS for data, no barriers:
 // the pass is HBM-bound (one read of the tower output, one write of the fp32 logits).
+//
+// EPISODES (sylph_fcos_head_episodes; the loop the batch stands for: meta_learn_evaluation.py:421-426): the images of the batch belong
+// to different episodes.  w / bias hold every episode's block of 32 rows (zero rows and zero biases above its N), seg_row0[segment] is
+// the first row of the block of the segment's image: tile -> segment -> image -> episode -> code rows.  A wave reloads its B fragments
+// and biases only when the block of its next tile differs from the one it holds; everything else -- operand values, K order, rounding
+// points -- is the uniform kernel's, so an image's logits do not depend on which episodes its neighbours belong to.
 #include "gfx950.h"
 
 namespace sylph {
 
+template <bool EPISODES>
 __global__ __launch_bounds__(256) void gn_logits_kernel(const bf16_t* __restrict__ x, int ld, const float2* __restrict__ coef,
                                                         const bf16_t* __restrict__ w, const float* __restrict__ bias, int N,
-                                                        float* __restrict__ out, int out_ld, const SegDesc* __restrict__ segs,
-                                                        const int2* __restrict__ tiles, int n_tiles) {
+                                                        const int* __restrict__ seg_row0, float* __restrict__ out, int out_ld,
+                                                        const SegDesc* __restrict__ segs, const int2* __restrict__ tiles, int n_tiles) {
   __shared__ __attribute__((aligned(16))) float cf[4][512];  // per wave: (a0, a1, b0, b1) per channel pair of its current segment
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
 
   bf16x8 Wf[16];  // B operand: lane (n = l31, k half lh)
-#pragma unroll
-  for (int ks = 0; ks < 16; ++ks) Wf[ks] = *reinterpret_cast<const bf16x8*>(w + l31 * 256 + ks * 16 + lh * 8);
   float bs[16];   // D^T: register 4q + e of a lane is class 8q + 4lh + e of row l31
+  auto load_codes = [&](int row0) {  // the 32 x 256 block that starts at packed row row0
 #pragma unroll
-  for (int q = 0; q < 4; ++q)
+    for (int ks = 0; ks < 16; ++ks) Wf[ks] = *reinterpret_cast<const bf16x8*>(w + (size_t)(row0 + l31) * 256 + ks * 16 + lh * 8);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int n = 8 * q + 4 * lh + e;
-      bs[4 * q + e] = (bias && n < N) ? bias[n] : 0.f;
-    }
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int n = 8 * q + 4 * lh + e;
+        bs[4 * q + e] = (bias && n < N) ? bias[row0 + n] : 0.f;
+      }
+  };
+  int cur_row0 = EPISODES ? -1 : 0;
+  if constexpr (!EPISODES) load_codes(0);
 
   int cur_seg = -1;
-  const int n_groups = n_tiles * 4, stride = gridDim.x * 4;
-  for (int g = blockIdx.x * 4 + wave; g < n_groups; g += stride) {
+  // uniform: a block takes every gridDim.x-th tile.  EPISODES: a block takes a contiguous run of tiles -- its waves then stay inside one
+  // image (a few hundred tiles) for nearly all of it, and a code block is loaded once or twice per wave instead of once per tile
+  const int chunk = EPISODES ? (n_tiles + (int)gridDim.x - 1) / (int)gridDim.x : 1;
+  const int n_groups = EPISODES ? min(n_tiles, ((int)blockIdx.x + 1) * chunk) * 4 : n_tiles * 4;
+  const int stride = EPISODES ? 4 : gridDim.x * 4;
+  for (int g = blockIdx.x * chunk * 4 + wave; g < n_groups; g += stride) {
     const int2 tl = tiles[g >> 2];
     const int seg = tl.x, r0 = tl.y + (g & 3) * 32;
     const SegDesc& sd = segs[seg];
@@ -42,6 +57,10 @@ __global__ __launch_bounds__(256) void gn_logits_kernel(const bf16_t* __restrict
     if (r0 >= nrows) continue;  // wave-uniform
     if (seg != cur_seg) {       // wave-private coefficient table (same-wave LDS traffic is ordered: no barrier)
       cur_seg = seg;
+      if constexpr (EPISODES) {
+        const int row0 = seg_row0[seg];  // wave-uniform
+        if (row0 != cur_row0) { cur_row0 = row0; load_codes(row0); }
+      }
       const float2* cp = coef + (size_t)seg * 256;
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
@@ -274,8 +293,18 @@ int launch_gn_logits(const void* x, int ld, const float2* coef, const void* w, c
   if (N > 32 || out_ld < N || (out_ld & 3) != 0 || n_tiles <= 0) return -1;
   const int want = n_tiles;  // one block = 4 row groups = one 128-row tile per sweep
   const int grid = want < 2048 ? want : 2048;
-  hipLaunchKernelGGL(gn_logits_kernel, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, N, out, out_ld,
-                     segs, tiles, n_tiles);
+  hipLaunchKernelGGL(gn_logits_kernel<false>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, N, nullptr, out,
+                     out_ld, segs, tiles, n_tiles);
+  return (int)hipGetLastError();
+}
+
+// w: [32 * episodes][256] bf16, bias: as many fp32 (nullptr: no bias), both zero above each episode's N; seg_row0: [segments]
+int launch_gn_logits_episodes(const void* x, int ld, const float2* coef, const void* w, const float* bias, const int* seg_row0, float* out,
+                              int out_ld, const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s) {
+  if (!seg_row0 || (out_ld & 3) != 0 || out_ld <= 0 || n_tiles <= 0) return -1;
+  const int grid = n_tiles < 2048 ? n_tiles : 2048;
+  hipLaunchKernelGGL(gn_logits_kernel<true>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, 32, seg_row0, out,
+                     out_ld, segs, tiles, n_tiles);
   return (int)hipGetLastError();
 }
 

@@ -22,7 +22,7 @@ struct DecodeSeg {
   int level;       // FPN level index (0..)
   int image;       // batch index
   unsigned loc_base;  // sum_{l'<l} nloc_l'; global candidate ordinal = (loc_base + loc) * N + cls
-  int pad;
+  int ncls;        // 0: N = DecodeCfg::num_classes; mixed-episode head: N of the image's episode, negated where the fused scan has left its candidates
 };
 
 struct DecodeCfg {
@@ -83,6 +83,10 @@ int launch_stem_conv(const void* x, const void* wp, const float* scale, const fl
                      int W2, hipStream_t s);
 int launch_gn_logits(const void* x, int ld, const float2* coef, const void* w, const float* bias, int N, float* out, int out_ld,
                      const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s);  // head_fused.hip (bf16, N <= 32)
+// the same for a batch whose images belong to different episodes: w / bias hold every episode's 32 zero-padded rows, seg_row0[seg] the
+// first row of the block of the segment's image
+int launch_gn_logits_episodes(const void* x, int ld, const float2* coef, const void* w, const float* bias, const int* seg_row0, float* out,
+                              int out_ld, const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s);
 int launch_gn_pred_taps(const void* x, int ld, const float2* coef, const void* w_taps, int cp, const float* bias, int relu_nch, int mul_nch,
                         float* planes_ws, size_t plane_rows, float* out, int out_ld, const SegDesc* segs, const int2* tiles, int n_tiles,
                         hipStream_t s);  // head_fused.hip: last bbox-tower GroupNorm + 3x3 prediction convs (bf16)
@@ -104,6 +108,9 @@ int launch_import_nchw(DType dt, const float* src, void* dst, int C, int HW, int
 int launch_export_nchw(DType dt, const void* src, float* dst, int C, int HW, int row0, int ld, hipStream_t s);
 int launch_export_nchw_f32(const float* src, float* dst, int C, int HW, int row0, int ld, int ch0, hipStream_t s);
 int launch_pack_codes(DType dt, const float* w, int N, int C, int Npad, void* out, const float* bias, float* bias_pad, float* bias_scan, hipStream_t s);
+// several episodes' codes in one launch: packed row r takes row src_row[r] of w / bias, or zeros (bias_scan: -inf) where src_row[r] < 0
+int launch_pack_codes_episodes(DType dt, const float* w, const int* src_row, int rows, int C, void* out, const float* bias, float* bias_pad,
+                               float* bias_scan, hipStream_t s);
 
 // conv_deform.hip: modulated deformable 3x3 conv (DCNv2, deformable FCOS tower layer), 256 -> 256 channels, stride 1, pad 1.
 // x: the layer input [rows][256] (storage dtype), om: its offset-conv output [rows][om_ld] fp32 (dy, dx of tap j in 2j, 2j + 1,
@@ -142,9 +149,10 @@ int launch_conv_group(DType dt, const GroupConvArgs& a, hipStream_t s);
 // many-way class-conditional conv fused with the scan (detect.hip); x: raw cls-tower output, coef: its GroupNorm (a, b) per
 // (segment, channel), w: packed codes [>= 32 * ceil(N/32)][256] bf16, wf_ws: as many bytes of workspace (the codes in MFMA
 // fragment order), bias_scan: fp32 biases (zeros without a bias), -inf from class N up to the same row count
+// clear_counts: zero the nseg candidate counters first (the mixed-episode head clears once and scans one tile sub-list per episode)
 int launch_logits_scan(const void* x, int ld, const float2* coef, const void* w, void* wf_ws, const float* bias_scan,
                        const SegDesc* segs, const int2* tiles, int n_tiles, const float* pred, int pred_ld, const DecodeCfg& cfg,
-                       const DecodeBuffers& buf, int nseg, hipStream_t s);
+                       const DecodeBuffers& buf, int nseg, bool clear_counts, hipStream_t s);
 int launch_decode(const DecodeCfg& cfg, const DecodeSeg* segs_dev, int nseg, int max_nloc, int B, int nw_bound,
                   const float* logits, const float* pred, int pred_ld, const DecodeBuffers& buf,
                   const ImageOut* img_out_dev, float* out_boxes, float* out_scores, int* out_classes,

@@ -55,6 +55,7 @@ PROTOTYPES = {
                                      POINTER(c_void_p)]),
     "sylph_export_pyramid": (c_int, [c_void_p, c_int, c_void_p]),
     "sylph_fcos_head": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    "sylph_fcos_head_episodes": (c_int, [c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]),
     "sylph_fcos_head_pretrained": (c_int, [c_void_p, POINTER(c_int)]),
     "sylph_export_head": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylph_import_head": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -337,6 +337,32 @@ class Engine:
             out.append(t)
         return out
 
+    def _fold_codes(self, cls_conv: torch.Tensor, cls_bias: Optional[torch.Tensor], raw: bool = False):
+        """One episode's class codes -> ((N, 256) fp32, (N,) fp32 or None) on the device, the CondConvBlock of a ROIEncoder model folded in."""
+        k = cls_conv.size(1) // 256
+        assert cls_conv.size(1) == 256 * k and k >= 1, f"weight has wrong shape, {tuple(cls_conv.shape)}"
+        assert k == 1 or (self.is_roi_encoder and not raw), "feature.size(1) != weight.size(1)"  # CondConvBasic (head_utils.py:69)
+        w = cls_conv.to(self.device, torch.float32).reshape(cls_conv.size(0), 256 * k)
+        b = cls_bias.to(self.device, torch.float32).reshape(-1).contiguous() if cls_bias is not None else None
+        if self.is_roi_encoder and not raw:
+            # CondConvBlock (head_utils.py:140-162): sum over 256-channel chunks of scale_i * conv(feature, w_i, bias); the
+            # reference indexes the Scale of chunk i+1 with i (head_utils.py:157-161).  conv is linear in (w, bias), so
+            # the block is ONE class-conditional conv with w_eff = sum_i s_i' w_i and bias_eff = (sum_i s_i') bias.
+            if not self._cond_scales_loaded:
+                sc = [1.0 / k] * k  # Scale init of the reference (head_utils.py:131-136): no learned value in the checkpoint
+            else:
+                if len(self.cond_scales) < max(k - 1, 1):
+                    raise ValueError(f"the checkpoint has {len(self.cond_scales)} cond_cls_logits scales; a {256 * k}-channel class "
+                                     f"code needs {max(k - 1, 1)}")
+                sc = list(self.cond_scales)
+            per_chunk = [sc[0]] + [sc[i] for i in range(k - 1)]
+            w = sum(s_ * w[:, 256 * i:256 * (i + 1)] for i, s_ in enumerate(per_chunk))
+            b = b * float(sum(per_chunk)) if b is not None else None
+        w = w.contiguous()
+        if b is not None:
+            assert b.numel() == w.size(0)
+        return w, b
+
     def head(self, cls_conv: torch.Tensor, cls_bias: Optional[torch.Tensor], raw: bool = False):
         """raw=True: plain `conv(cls_tower, w, b)` even on a ROIEncoder model -- the checkpoint's own cls_logits run without the
         CondConvBlock Scale (forward_base_train, fcos.py:544-570,592-593)."""
@@ -362,34 +388,46 @@ class Engine:
                tuple(self.cond_scales), self._cond_scales_loaded, self._lib_writes)
         cached = getattr(self, "_codes_key", None) == key
         if not cached:
-            k = cls_conv.size(1) // 256
-            assert cls_conv.size(1) == 256 * k and k >= 1, f"weight has wrong shape, {tuple(cls_conv.shape)}"
-            assert k == 1 or (self.is_roi_encoder and not raw), "feature.size(1) != weight.size(1)"  # CondConvBasic (head_utils.py:69)
-            w = cls_conv.to(self.device, torch.float32).reshape(cls_conv.size(0), 256 * k)
-            b = cls_bias.to(self.device, torch.float32).reshape(-1).contiguous() if cls_bias is not None else None
-            if self.is_roi_encoder and not raw:
-                # CondConvBlock (head_utils.py:140-162): sum over 256-channel chunks of scale_i * conv(feature, w_i, bias); the
-                # reference indexes the Scale of chunk i+1 with i (head_utils.py:157-161).  conv is linear in (w, bias), so
-                # the block is ONE class-conditional conv with w_eff = sum_i s_i' w_i and bias_eff = (sum_i s_i') bias.
-                if not self._cond_scales_loaded:
-                    sc = [1.0 / k] * k  # Scale init of the reference (head_utils.py:131-136): no learned value in the checkpoint
-                else:
-                    if len(self.cond_scales) < max(k - 1, 1):
-                        raise ValueError(f"the checkpoint has {len(self.cond_scales)} cond_cls_logits scales; a {256 * k}-channel class "
-                                         f"code needs {max(k - 1, 1)}")
-                    sc = list(self.cond_scales)
-                per_chunk = [sc[0]] + [sc[i] for i in range(k - 1)]
-                w = sum(s_ * w[:, 256 * i:256 * (i + 1)] for i, s_ in enumerate(per_chunk))
-                b = b * float(sum(per_chunk)) if b is not None else None
-            w = w.contiguous()
-            if b is not None:
-                assert b.numel() == w.size(0)
-            self._codes = (w, b)
+            self._codes = self._fold_codes(cls_conv, cls_bias, raw)
             self._codes_src = (cls_conv, cls_bias)  # keeps the ids alive
             self._codes_key = key
         w, b = self._codes
         self._ncls = w.size(0)
         check(self.L.sylph_fcos_head(self._ctx, _ptr(w), _ptr(b), self._ncls), "fcos_head")
+
+    def head_episodes(self, codes, image_episode):
+        """The head for a batch whose images belong to different episodes (sylph_fcos_head_episodes): `codes` is a list of
+        (cls_conv (N_e, 256 k, 1, 1), cls_bias (N_e) or None), image i of the current batch is run with codes[image_episode[i]] and gets
+        what `head(*codes[image_episode[i]])` gives it on the same batch.  `decode` then numbers classes within the image's own episode."""
+        self._stream()
+        codes = [(w, b) for w, b in codes]
+        image_episode = [int(e) for e in image_episode]
+        if len(codes) == 0:
+            raise ValueError("head_episodes needs at least one episode")
+        if len(image_episode) != self._batch[0]:
+            raise ValueError(f"image_episode has {len(image_episode)} entries for a batch of {self._batch[0]} images")
+        if any(e < 0 or e >= len(codes) for e in image_episode):
+            raise ValueError(f"image_episode entries must be in [0, {len(codes)})")
+        for w, _ in codes:
+            assert w.dim() == 4, f"Weight has dimension: {w.dim()}"
+            assert w.size(2) == 1 and w.size(3) == 1
+        if self.owd:  # the codes are not read (one all-ones class, see head): the uniform call
+            return self.head(*codes[0])
+        if len({b is None for _, b in codes}) != 1:
+            raise ValueError("cls_bias must be given for every episode or for none")
+        # the packed (sum N, 256) table is kept like head's single code set: no cast / concat kernels in a steady serving loop
+        key = (tuple((id(w), w._version, id(b), None if b is None else b._version) for w, b in codes),
+               tuple(self.cond_scales), self._cond_scales_loaded, self._lib_writes)
+        if getattr(self, "_ep_codes_key", None) != key:
+            folded = [self._fold_codes(w, b) for w, b in codes]
+            W = torch.cat([w for w, _ in folded]).contiguous()
+            Bv = torch.cat([b for _, b in folded]).contiguous() if folded[0][1] is not None else None
+            self._ep_codes = (W, Bv, [int(w.size(0)) for w, _ in folded])
+            self._ep_codes_src = codes  # keeps the ids alive
+            self._ep_codes_key = key
+        W, Bv, n = self._ep_codes
+        self._ncls = max(n)
+        check(self.L.sylph_fcos_head_episodes(self._ctx, len(n), _ptr(W), _ptr(Bv), _iarr(n), _iarr(image_episode)), "fcos_head_episodes")
 
     def head_pretrained(self) -> int:
         """forward_base_train (fcos.py:543-578): towers + the checkpoint's own cls_logits conv (1x1 or 3x3) -> number of classes."""

@@ -116,6 +116,11 @@ class MetaFCOS(HipComponent):
         self.engine.head(cls_conv, cls_bias, raw=raw)
         return self.engine.decode(out_sizes)
 
+    def forward_episodes(self, codes, image_episode, out_sizes):
+        """Images of different episodes in one step: image i with codes[image_episode[i]] (Engine.head_episodes)."""
+        self.engine.head_episodes(codes, image_episode)
+        return self.engine.decode(out_sizes)
+
     def forward_pretrained(self, out_sizes):
         """support_set_per_class_code = None (fcos.py:543-578): the checkpoint's own cls_logits conv, any kernel size the library
         packed (1x1 / 3x3)."""
@@ -185,6 +190,23 @@ def build_code_generator(cfg, feature_channels, feature_levels, strides):
     return CODE_GENERATOR_REGISTRY.get(name)(cfg, feature_channels, feature_levels, strides)
 
 
+def group_episodes(class_code, num_inputs: int):
+    """A list / tuple of class-code dicts, one per input -> (the distinct dicts in order of first appearance, episode index per input).
+    Entries that are the SAME OBJECT form one episode: equal contents in two dicts are two episodes (nothing is compared)."""
+    if len(class_code) != num_inputs:
+        raise ValueError(f"class_code has {len(class_code)} entries for {num_inputs} inputs: one class-code dict per input")
+    index, dicts, image_episode = {}, [], []
+    for i, d in enumerate(class_code):
+        if d is None:
+            raise ValueError(f"class_code[{i}] is None: pass class_code=None as a whole for the pretrained codes")
+        e = index.get(id(d))
+        if e is None:
+            e = index[id(d)] = len(dicts)
+            dicts.append(d)
+        image_episode.append(e)
+    return dicts, image_episode
+
+
 @META_ARCH_REGISTRY.register()
 class MetaOneStageDetector(nn.Module):
     """Four inference forward types (meta_one_stage_detector.py:415-455):
@@ -193,6 +215,8 @@ class MetaOneStageDetector(nn.Module):
       "meta_learn_test_support"             -> forward_class_code
       "meta_learn_normalize_code"           -> normalize_class_code
       "meta_learn_test_instance"            -> forward_instances (class_code None: evaluation with the pretrained cls_logits)
+                                               class_code a list / tuple of dicts, one per input: images of different episodes
+                                               in one step (group_episodes; pred_classes index the image's own dict)
     Training is out of scope: calling the model in training mode raises NotImplementedError."""
 
     def __init__(self, cfg, dtype: Optional[str] = None, device_index: Optional[int] = None):
@@ -350,6 +374,16 @@ class MetaOneStageDetector(nn.Module):
 
     def _detect(self, batched_inputs: List[Dict[str, Any]], class_codes):
         assert not self.training, "Not for training"
+        if isinstance(class_codes, (list, tuple)):
+            # one class-code dict per input: the images of several episodes share one step (sylph_fcos_head_episodes); pred_classes
+            # index the image's own dict
+            dicts, image_episode = group_episodes(class_codes, len(batched_inputs))
+            codes = [(d["cls_conv"], d.get("cls_bias")) for d in dicts]
+            for w, _ in codes:
+                assert w.dim() == 4, f"Weight has dimension: {w.dim()}"
+                assert w.size(1) == 256
+            out_sizes = self._run_backbone(batched_inputs)
+            return self._to_results(self.proposal_generator.forward_episodes(codes, image_episode, out_sizes), out_sizes)
         pretrained = class_codes is None
         if class_codes is None:
             # MetaFCOSHead.forward with support_set_per_class_code=None -> forward_base_train (fcos.py:543-578):
@@ -368,6 +402,16 @@ class MetaOneStageDetector(nn.Module):
         assert w.dim() == 4, f"Weight has dimension: {w.dim()}"
         assert w.size(1) == 256
         conv3 = pretrained and tuple(w.shape[2:]) == (3, 3)  # a 3x3 cls_logits is a real conv, not a class-conditional 1x1
+        out_sizes = self._run_backbone(batched_inputs)
+        # the checkpoint's own cls_logits are a plain conv: no CondConvBlock Scale on a ROIEncoder model (ADVICE r2)
+        if conv3:
+            dets = self.proposal_generator.forward_pretrained(out_sizes)
+        else:
+            dets = self.proposal_generator(w, b, out_sizes, raw=True) if pretrained else self.proposal_generator(w, b, out_sizes)
+        return self._to_results(dets, out_sizes)
+
+    def _run_backbone(self, batched_inputs: List[Dict[str, Any]]):
+        """preprocess + backbone of the query batch -> the (height, width) each image's detections are scaled to"""
         if all("image_u8" in x for x in batched_inputs):
             # fused input pipeline (SURVEY.md 8f-3): the original uint8 HWC image + its ResizeShortestEdge target; resize,
             # BGR conversion, normalisation and padding run in one HIP kernel (sylph_preprocess_u8)
@@ -375,12 +419,10 @@ class MetaOneStageDetector(nn.Module):
                                   rgb_input=str(batched_inputs[0].get("input_format", "BGR")) == "RGB")
         else:
             sizes = self.backbone(images=[x["image"] for x in batched_inputs])
-        out_sizes = [(int(x.get("height", s[0])), int(x.get("width", s[1]))) for x, s in zip(batched_inputs, sizes)]
-        # the checkpoint's own cls_logits are a plain conv: no CondConvBlock Scale on a ROIEncoder model (ADVICE r2)
-        if conv3:
-            dets = self.proposal_generator.forward_pretrained(out_sizes)
-        else:
-            dets = self.proposal_generator(w, b, out_sizes, raw=True) if pretrained else self.proposal_generator(w, b, out_sizes)
+        return [(int(x.get("height", s[0])), int(x.get("width", s[1]))) for x, s in zip(batched_inputs, sizes)]
+
+    @staticmethod
+    def _to_results(dets, out_sizes):
         results = []
         for d, osz in zip(dets, out_sizes):
             r = Instances(osz)
