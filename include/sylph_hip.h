@@ -192,7 +192,21 @@ int sylph_codegen(sylph_ctx* ctx, const float* boxes_dev, float* code_out_dev);
  * the class axis of a (classes, shots, C) tensor and sees one class per call at inference (roi_encoder.py:184-186), so a class of the
  * batch never meets another class's tokens here either: the codes are those of one call per class. */
 int sylph_codegen_classes(sylph_ctx* ctx, const float* boxes_dev, int shots, float* codes_out_dev);
-/* With cg_has_scale: the "cls_weight_norm" outputs of the last sylph_codegen[_classes] call (one fp32 per class), the factor
+/* The same from a ROI LIST: R support instances over the current batch of B images, several per image if the image shows several.
+ * ROI r is box boxes_dev[r] (XYXY, network-input coordinates) on image roi_image[r] in [0, B), in any order; an image may carry no
+ * ROI or many.  The ROIs are cut into n_seg consecutive segments of seg_len[j] >= 1 ROIs (sum = R); row j of codes_out_dev
+ * (n_seg, 257) is what ONE reference call of CodeGeneratorHead.forward_roi_align (code_generator.py:924-1002) or, with cg_type 1, of
+ * ROIEncoder.forward (roi_encoder.py:146-204) gives for a support set of seg_len[j] shots whose shot i is the feature pyramid of the
+ * segment's i-th ROI's image with that ROI's box.  The backbone has run once per image, not once per instance; segments never see
+ * each other (shot softmax, compute_code, token mean and the length-1 attention stay inside a segment) and a segment may be longer
+ * than 64 shots.  roi_image and seg_len are HOST arrays; their device copies are kept per (batch shape, R) and uploaded again only
+ * when the values change.  Afterwards sylph_codegen_weight_norm gives n_seg values and the support taps R rows (per-shot stages;
+ * SYLPH_SUP_CONTEXT stays per image: B rows) or n_seg rows (class tokens). */
+int sylph_codegen_rois(sylph_ctx* ctx, int R, const float* boxes_dev, const int* roi_image, int n_seg, const int* seg_len,
+                       float* codes_out_dev);
+/* How many sylph_codegen_rois calls on this context had to upload their ROI tables (a repeated list uploads none). */
+int sylph_roi_table_uploads(sylph_ctx* ctx, int64_t* n_out);
+/* With cg_has_scale: the "cls_weight_norm" outputs of the last sylph_codegen[_classes | _rois] call (one fp32 per class / segment), the factor
  * forward_normalize_code multiplies into the L2-normalised code (code_generator.py:838-840,987-993) -> pass them to
  * sylph_normalize_codes as weight_norm_dev. */
 int sylph_codegen_weight_norm(sylph_ctx* ctx, float* weight_norm_out_dev);
@@ -201,6 +215,10 @@ int sylph_codegen_weight_norm(sylph_ctx* ctx, float* weight_norm_out_dev);
  * level assignment -> ROIAlignV2 aligned, adaptive sampling, 7x7).  The current batch holds S images, boxes_dev (S,4)
  * one XYXY box per image; out_nchw_dev (S,256,7,7) fp32. */
 int sylph_roi_align(sylph_ctx* ctx, const float* boxes_dev, float* out_nchw_dev);
+/* The same ROIPooler call (code_generator.py:341-348,928-930) over a ROI list: R boxes, box r on image roi_image[r] (host array)
+ * of the current batch; out_nchw_dev (R,256,7,7) fp32.  Row r equals sylph_roi_align's row on a batch whose image r is image
+ * roi_image[r]; a box wholly outside its level gives zeros. */
+int sylph_roi_align_rois(sylph_ctx* ctx, int R, const float* boxes_dev, const int* roi_image, float* out_nchw_dev);
 
 /* CodeGeneratorHead.forward_normalize_code (code_generator.py:832-897): codes_dev (n,257) in place.
  * weight_norm_dev: (n) cls_weight_norm factors applied after the L2 normalisation (code_generator.py:838-840), or NULL. */
@@ -260,8 +278,8 @@ int sylph_set_debug_taps(sylph_ctx* ctx, int on);
 int sylph_export_stage(sylph_ctx* ctx, int stage, float* out_nchw_dev);
 int sylph_export_tower(sylph_ctx* ctx, int tower, int layer, int level, float* y_nchw_dev, float* coef_dev);
 
-/* Support-path taps: the output of one stage of the last sylph_codegen / sylph_codegen_classes call on the current batch (S support
- * images, 49 ROI positions).  ROI, CONV_OUT and CONTEXT, the GroupNorm coefficients and the class tokens are always kept; the other
+/* Support-path taps: the output of one stage of the last sylph_codegen / sylph_codegen_classes / sylph_codegen_rois call on the
+ * current batch (S support images or, after a ROI-list call, S = R ROIs; 49 ROI positions).  ROI, CONV_OUT and CONTEXT, the GroupNorm coefficients and the class tokens are always kept; the other
  * stages need sylph_set_debug_taps(1) before the first code-generator call of a batch shape, which copies each of them aside right
  * after the launch that writes it (same kernels and launches).  `index` numbers the layers of a stage:
  *   SYLPH_SUP_ROI          0: ROIAlign output, (S,256,7,7)

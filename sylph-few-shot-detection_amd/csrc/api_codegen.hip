@@ -7,169 +7,188 @@ namespace sylph_host {
 // Parity taps of the support path (sylph_export_support).  A stage that no later op overwrites is recorded where it is; with debug taps
 // on, the others are copied aside by a device-to-device copy right after the op that writes them: the kernels and their launches are
 // the same with and without taps.  n = images (npos = 49: [n * 49][ld] maps) or rows (npos = 1); n = 0: the classes of the last call.
-static void tap_at(Plan* P, int stage, int index, const void* p, bool f32, int n, int npos, int C = 256, int ld = 256) {
-  Plan::SupTap t;
+static void tap_at(SupportPass* Q, int stage, int index, const void* p, bool f32, int n, int npos, int C = 256, int ld = 256) {
+  SupportPass::SupTap t;
   t.p = p; t.f32 = f32; t.n = n; t.npos = npos; t.C = C; t.ld = ld;
-  P->sup_taps[{stage, index}] = t;
+  Q->taps[{stage, index}] = t;
 }
 
-static int tap_copy(sylph_ctx* c, Plan* P, std::vector<OpFn>& ops, int stage, int index, const void* src, bool f32, int n, int npos) {
+static int tap_copy(sylph_ctx* c, SupportPass* Q, std::vector<OpFn>& ops, int stage, int index, const void* src, bool f32, int n, int npos) {
   if (!c->debug_taps) return 0;
   const size_t bytes = (size_t)n * npos * 256 * (f32 ? 4 : c->esz());
   void* dst = nullptr;
   RET(c->dalloc(&dst, bytes));
   ops.push_back([=](hipStream_t s) { return (int)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s); });
-  tap_at(P, stage, index, dst, f32, n, npos);
+  tap_at(Q, stage, index, dst, f32, n, npos);
+  return 0;
+}
+
+static std::vector<LevelDesc> level_table(sylph_ctx* c, Plan* P) {
+  std::vector<LevelDesc> lv;
+  for (int b = 0; b < P->B; ++b)
+    for (int l = 0; l < c->cfg.nlevels; ++l)
+      lv.push_back(LevelDesc{b * P->Ltot + P->off[l], P->hl[l], P->wl[l], 1.0f / (float)c->cfg.strides[l]});
+  return lv;
+}
+
+// the first op of a support pass: ROIAlign of the call's boxes into Q->roi
+static int add_roi_align(Plan* P, SupportPass* Q, DType dt, int L) {
+  const void* F = P->F;
+  const LevelDesc* lvd = P->lv_dev;
+  void* roi = Q->roi;
+  const int S = Q->S;
+  if (Q->rois) Q->ops.push_back([=](hipStream_t s) { return launch_roi_align_rois(dt, F, 256, lvd, L, Q->cur_boxes, Q->roi_image_dev, S, 7, roi, s); });
+  else Q->ops.push_back([=](hipStream_t s) { return launch_roi_align(dt, F, 256, lvd, L, Q->cur_boxes, S, 7, roi, s); });
   return 0;
 }
 
 // add_conv_gn of a support layer (7x7 maps, applied in place) with its taps: the stored pre-GroupNorm output, the statistics of the
 // apply, the applied output
-static int support_conv_gn(sylph_ctx* c, Plan* P, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, void* out,
+static int support_conv_gn(sylph_ctx* c, SupportPass* Q, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, void* out,
                            const std::vector<SegDesc>& segs, ConvOpts o, const GNLayer& G, int relu, int layer) {
-  const int S = P->B;
+  const int S = Q->S;
   o.want_gn = 1;
   Geom g;
   RET(add_conv(c, ops, L, in, 256, out, L.Cout, segs, o, &g));
-  RET(tap_copy(c, P, ops, SYLPH_SUP_GN_Y, layer, out, false, S, 49));
+  RET(tap_copy(c, Q, ops, SYLPH_SUP_GN_Y, layer, out, false, S, 49));
   const float2* stats = nullptr;
   RET(add_gn_from_partials(c, ops, out, L.Cout, segs, g, G, relu, nullptr, nullptr, &stats));
-  Plan::SupTap t;
+  SupportPass::SupTap t;
   t.n = S; t.npos = 1; t.stats = stats; t.gamma = G.gamma; t.beta = G.beta;
-  P->sup_taps[{SYLPH_SUP_GN_COEF, layer}] = t;
-  return tap_copy(c, P, ops, SYLPH_SUP_LAYER_OUT, layer, out, false, S, 49);
+  Q->taps[{SYLPH_SUP_GN_COEF, layer}] = t;
+  return tap_copy(c, Q, ops, SYLPH_SUP_LAYER_OUT, layer, out, false, S, 49);
 }
 
-int build_support(sylph_ctx* c, Plan* P) {
-  if (P->support_built) return 0;
+// the pyramid's (image, level) table: one per plan, whichever support pass comes first
+static int ensure_level_table(sylph_ctx* c, Plan* P) {
+  if (P->lv_dev) return 0;
+  std::vector<LevelDesc> lv = level_table(c, P);
+  return upload(c, (void**)&P->lv_dev, lv.data(), lv.size() * sizeof(LevelDesc));
+}
+
+// Q: the pass to build -- the plan's own (row s = image s, S = B) or a ROI-list pass (row r = ROI r, S = R).  The two differ in the
+// ROIAlign launch (which image a row reads) and in the tail (equal classes of cur_shots rows | the segment table); the convolutions
+// between them run on image_segs(S, 7, 7, 7, 7) either way, so their routes follow the row count.
+int build_support(sylph_ctx* c, Plan* P, SupportPass* Q) {
+  if (Q->built) return 0;
   if (!c->has_codegen) return fail("code generator weights were not loaded");
   RET(ensure_pyramid(c, P));
   const size_t e = c->esz();
-  const int S = P->B, L = c->cfg.nlevels, npos = 49;
-  std::vector<LevelDesc> lv;
-  for (int b = 0; b < S; ++b)
-    for (int l = 0; l < L; ++l)
-      lv.push_back(LevelDesc{b * P->Ltot + P->off[l], P->hl[l], P->wl[l], 1.0f / (float)c->cfg.strides[l]});
-  RET(upload(c, (void**)&P->lv_dev, lv.data(), lv.size() * sizeof(LevelDesc)));
-  RET(c->dalloc(&P->roi, (size_t)S * npos * 256 * e));
-  RET(c->dalloc(&P->cgA, (size_t)S * npos * 256 * e));
-  RET(c->dalloc(&P->cgB, (size_t)S * npos * 256 * e));
-  RET(c->dalloc((void**)&P->cg_conv_out, (size_t)S * npos * 256 * 4));
-  RET(c->dalloc((void**)&P->cg_bias_out, (size_t)S * npos * 4 * (c->cg_naux > 0 ? c->cg_naux : 1)));
-  RET(c->dalloc((void**)&P->cg_wnorm, (size_t)S * 4));
-  RET(ensure_gn_ws(c, P, S, P->hl[0] * P->wl[0]));
-  std::vector<RowSeg> rs;
-  for (int s = 0; s < S; ++s) rs.push_back(RowSeg{s * npos, npos});
-  RowSeg* rs_dev = nullptr;
-  RET(upload(c, (void**)&rs_dev, rs.data(), rs.size() * sizeof(RowSeg)));
+  const int S = Q->S, L = c->cfg.nlevels, npos = 49;
+  RET(ensure_level_table(c, P));
+  RET(c->dalloc(&Q->roi, (size_t)S * npos * 256 * e));
+  RET(c->dalloc(&Q->cgA, (size_t)S * npos * 256 * e));
+  RET(c->dalloc(&Q->cgB, (size_t)S * npos * 256 * e));
+  RET(c->dalloc((void**)&Q->cg_conv_out, (size_t)S * npos * 256 * 4));
+  RET(c->dalloc((void**)&Q->cg_bias_out, (size_t)S * npos * 4 * (c->cg_naux > 0 ? c->cg_naux : 1)));
+  RET(c->dalloc((void**)&Q->cg_wnorm, (size_t)S * 4));
   const std::vector<SegDesc> segs = image_segs(S, 7, 7, 7, 7);
-  auto& ops = P->support_ops;
+  auto& ops = Q->ops;
   const DType dt = c->dt;
-  Plan* PP = P;
-  {
-    const void* F = P->F;
-    const LevelDesc* lvd = P->lv_dev;
-    void* roi = P->roi;
-    ops.push_back([=](hipStream_t s) { return launch_roi_align(dt, F, 256, lvd, L, PP->cur_boxes, S, 7, roi, s); });
-  }
-  tap_at(P, SYLPH_SUP_ROI, 0, P->roi, false, S, npos);
-  const void* in = P->roi;
-  void* out = P->cgA;
+  SupportPass* QQ = Q;
+  RET(add_roi_align(P, Q, dt, L));
+  tap_at(Q, SYLPH_SUP_ROI, 0, Q->roi, false, S, npos);
+  const void* in = Q->roi;
+  void* out = Q->cgA;
   for (size_t i = 0; i < c->cg_tower.size(); ++i) {
     // CODE_GENERATOR.TOWER_LAYERS[i] = [norm, activation] (code_generator.py:648-688): conv3x3 + bias, GroupNorm(32) if "GN", ReLU if "ReLU"
     const bool gn = (c->cfg.cg_tower_gn_mask >> i) & 1, relu = (c->cfg.cg_tower_relu_mask >> i) & 1;
     ConvOpts o; o.pad = 1;
     if (gn) {
-      RET(support_conv_gn(c, P, ops, c->cg_tower[i], in, out, segs, o, c->cg_gn[i], relu ? 1 : 0, (int)i));
+      RET(support_conv_gn(c, Q, ops, c->cg_tower[i], in, out, segs, o, c->cg_gn[i], relu ? 1 : 0, (int)i));
     } else {
       if (relu) o.relu_nch = 1 << 30;
       RET(add_conv(c, ops, c->cg_tower[i], in, 256, out, 256, segs, o));
-      RET(tap_copy(c, P, ops, SYLPH_SUP_LAYER_OUT, (int)i, out, false, S, npos));
+      RET(tap_copy(c, Q, ops, SYLPH_SUP_LAYER_OUT, (int)i, out, false, S, npos));
     }
     in = out;
-    out = (out == P->cgA) ? P->cgB : P->cgA;
+    out = (out == Q->cgA) ? Q->cgB : Q->cgA;
   }
   ConvOpts oc; oc.pad = 1; oc.out_f32 = true;
-  RET(add_conv(c, ops, c->cg_cls, in, 256, P->cg_conv_out, 256, segs, oc));
+  RET(add_conv(c, ops, c->cg_cls, in, 256, Q->cg_conv_out, 256, segs, oc));
   const int naux = c->cg_naux;
-  if (naux > 0) RET(add_conv(c, ops, c->cg_bias, in, 256, P->cg_bias_out, naux, segs, oc));
-  tap_at(P, SYLPH_SUP_CONV_OUT, 0, P->cg_conv_out, true, S, npos);
-  if (naux > 0) tap_at(P, SYLPH_SUP_CONV_OUT, 1, P->cg_bias_out, true, S, npos, naux, naux);
+  if (naux > 0) RET(add_conv(c, ops, c->cg_bias, in, 256, Q->cg_bias_out, naux, segs, oc));
+  tap_at(Q, SYLPH_SUP_CONV_OUT, 0, Q->cg_conv_out, true, S, npos);
+  if (naux > 0) tap_at(Q, SYLPH_SUP_CONV_OUT, 1, Q->cg_bias_out, true, S, npos, naux, naux);
   {
-    const float *co = P->cg_conv_out, *bo = P->cg_bias_out;
+    const float *co = Q->cg_conv_out, *bo = Q->cg_bias_out;
     const int l2 = c->cfg.cg_bias_l2_norm, ib = c->cg_ib, iw = c->cg_iw, is = c->cg_is;
-    float* wn = P->cg_wnorm;
-    ops.push_back([=](hipStream_t s) {
-      const int shots = PP->cur_shots > 0 ? PP->cur_shots : S;
-      return launch_codegen_tail(co, 256, bo, naux > 0 ? naux : 1, ib, iw, is, S / shots, shots, npos, 256, l2, PP->cur_code_out, wn, s);
-    });
+    float* wn = Q->cg_wnorm;
+    if (Q->rois)
+      ops.push_back([=](hipStream_t s) {
+        return launch_codegen_tail_segs(co, 256, bo, naux > 0 ? naux : 1, ib, iw, is, QQ->seg_dev, QQ->n_seg, QQ->max_len, npos, 256, l2,
+                                        QQ->cur_code_out, wn, s);
+      });
+    else
+      ops.push_back([=](hipStream_t s) {
+        const int shots = QQ->cur_shots > 0 ? QQ->cur_shots : S;
+        return launch_codegen_tail(co, 256, bo, naux > 0 ? naux : 1, ib, iw, is, S / shots, shots, npos, 256, l2, QQ->cur_code_out, wn, s);
+      });
   }
-  P->support_built = true;
+  Q->built = true;
   return 0;
 }
 
-int build_support_roienc(sylph_ctx* c, Plan* P) {
-  if (P->support_built) return 0;
+int build_support_roienc(sylph_ctx* c, Plan* P, SupportPass* Q) {
+  if (Q->built) return 0;
   if (!c->has_roienc) return fail("ROIEncoder weights were not loaded");
   RET(ensure_pyramid(c, P));
   const size_t e = c->esz();
   // S support images = one or several classes of P->cur_shots images each (sylph_codegen_classes).  Everything up to the encoder
   // is per image; the reference's encoder attends over the CLASS axis of a (classes, shots, C) tensor (roi_encoder.py:184-186)
   // and always sees one class per call at inference, i.e. a length-1 sequence: here too a class never sees another one.
-  const int S = P->B, L = c->cfg.nlevels, npos = 49;
-  std::vector<LevelDesc> lv;
-  for (int b = 0; b < S; ++b)
-    for (int l = 0; l < L; ++l)
-      lv.push_back(LevelDesc{b * P->Ltot + P->off[l], P->hl[l], P->wl[l], 1.0f / (float)c->cfg.strides[l]});
-  RET(upload(c, (void**)&P->lv_dev, lv.data(), lv.size() * sizeof(LevelDesc)));
-  RET(c->dalloc(&P->roi, (size_t)S * npos * 256 * e));
-  RET(c->dalloc(&P->cgA, (size_t)S * npos * 256 * e));
-  RET(c->dalloc(&P->cgB, (size_t)S * npos * 256 * e));
-  RET(c->dalloc((void**)&P->re_ctx, (size_t)S * npos * 256 * 4));
-  RET(c->dalloc((void**)&P->re_tok, (size_t)S * 256 * 4));
-  RET(c->dalloc((void**)&P->re_tmp, (size_t)S * 256 * 4));
+  // A ROI-list pass has two row counts: S = R ROIs for everything per shot, B images for the context, which is a function of the
+  // image alone (utils.py:143-165) and is computed once per image; the MS-CAM gate of ROI r reads the context of image roi_image[r].
+  const int S = Q->S, B = P->B, L = c->cfg.nlevels, npos = 49;
+  RET(ensure_level_table(c, P));
+  RET(c->dalloc(&Q->roi, (size_t)S * npos * 256 * e));
+  RET(c->dalloc(&Q->cgA, (size_t)S * npos * 256 * e));
+  RET(c->dalloc(&Q->cgB, (size_t)S * npos * 256 * e));
+  RET(c->dalloc((void**)&Q->re_ctx, (size_t)B * npos * 256 * 4));
+  RET(c->dalloc((void**)&Q->re_tok, (size_t)S * 256 * 4));
+  RET(c->dalloc((void**)&Q->re_tmp, (size_t)S * 256 * 4));
   int maxhid = 1024;
   for (auto& l : c->re.layers) maxhid = l.l1.O > maxhid ? l.l1.O : maxhid;
-  RET(c->dalloc((void**)&P->re_hid, (size_t)S * maxhid * 4));
+  RET(c->dalloc((void**)&Q->re_hid, (size_t)S * maxhid * 4));
   const int hdim = c->cfg.head_fc_dim > 256 ? c->cfg.head_fc_dim : 256;
-  RET(c->dalloc((void**)&P->re_cls, (size_t)S * 256 * 4));
-  RET(c->dalloc((void**)&P->re_h, (size_t)2 * S * hdim * 4));
+  RET(c->dalloc((void**)&Q->re_cls, (size_t)S * 256 * 4));
+  RET(c->dalloc((void**)&Q->re_h, (size_t)2 * S * hdim * 4));
   const std::vector<SegDesc> segs = image_segs(S, 7, 7, 7, 7);
-  auto& ops = P->support_ops;
+  auto& ops = Q->ops;
   const DType dt = c->dt;
   const int xbf = dt == DT_BF16 ? 1 : 0;
-  Plan* PP = P;
+  SupportPass* QQ = Q;
   auto& R = c->re;
+  RET(add_roi_align(P, Q, dt, L));
   {
     const void* F = P->F;
     const LevelDesc* lvd = P->lv_dev;
-    void* roi = P->roi;
-    float* ctx = P->re_ctx;
-    ops.push_back([=](hipStream_t s) { return launch_roi_align(dt, F, 256, lvd, L, PP->cur_boxes, S, 7, roi, s); });
-    ops.push_back([=](hipStream_t s) { return launch_adaptive_context(dt, F, 256, lvd, L, S, 7, ctx, s); });
+    float* ctx = Q->re_ctx;
+    ops.push_back([=](hipStream_t s) { return launch_adaptive_context(dt, F, 256, lvd, L, B, 7, ctx, s); });
   }
-  tap_at(P, SYLPH_SUP_ROI, 0, P->roi, false, S, npos);
-  tap_at(P, SYLPH_SUP_CONTEXT, 0, P->re_ctx, true, S, npos);
+  tap_at(Q, SYLPH_SUP_ROI, 0, Q->roi, false, S, npos);
+  tap_at(Q, SYLPH_SUP_CONTEXT, 0, Q->re_ctx, true, B, npos);
   // GroupNorm layers: 0 = box_pooler, 1 + k = tokenizer conv k
   ConvOpts o; o.pad = 1;
-  RET(support_conv_gn(c, P, ops, R.pool_conv, P->roi, P->cgA, segs, o, R.pool_gn, 1, 0));
+  RET(support_conv_gn(c, Q, ops, R.pool_conv, Q->roi, Q->cgA, segs, o, R.pool_gn, 1, 0));
   {
-    const float* ctx = P->re_ctx;
-    void* x = P->cgA;
+    const float* ctx = Q->re_ctx;
+    void* x = Q->cgA;
     const MsCamWeights w = R.cam;
-    ops.push_back([=](hipStream_t s) { return launch_mscam(dt, ctx, x, S, w, s); });
+    if (Q->rois) ops.push_back([=](hipStream_t s) { return launch_mscam_rois(dt, ctx, QQ->roi_image_dev, x, S, w, s); });
+    else ops.push_back([=](hipStream_t s) { return launch_mscam(dt, ctx, x, S, w, s); });
   }
-  RET(tap_copy(c, P, ops, SYLPH_SUP_MSCAM, 0, P->cgA, false, S, npos));
-  void* cur = P->cgA;
-  void* nxt = P->cgB;
+  RET(tap_copy(c, Q, ops, SYLPH_SUP_MSCAM, 0, Q->cgA, false, S, npos));
+  void* cur = Q->cgA;
+  void* nxt = Q->cgB;
   for (size_t k = 0; k < R.tok_conv.size(); ++k) {
-    RET(support_conv_gn(c, P, ops, R.tok_conv[k], cur, nxt, segs, o, R.tok_gn[k], 1, 1 + (int)k));
+    RET(support_conv_gn(c, Q, ops, R.tok_conv[k], cur, nxt, segs, o, R.tok_gn[k], 1, 1 + (int)k));
     std::swap(cur, nxt);
   }
   // tokenizer FC stack: first FC reads the (position-major) activations directly
-  float* tok = P->re_tok;
-  float* tmp = P->re_tmp;
-  float* hid = P->re_hid;
+  float* tok = Q->re_tok;
+  float* tmp = Q->re_tmp;
+  float* hid = Q->re_hid;
   {
     const sylph_ctx::Lin f0 = R.tok_fc[0];
     const void* x = cur;
@@ -184,7 +203,7 @@ int build_support_roienc(sylph_ctx* c, Plan* P) {
     tok = a;
     tmp = b;
   }
-  RET(tap_copy(c, P, ops, SYLPH_SUP_TOKENS, 0, tok, true, S, 1));
+  RET(tap_copy(c, Q, ops, SYLPH_SUP_TOKENS, 0, tok, true, S, 1));
   int layer = 0;
   for (auto& l : R.layers) {
     const sylph_ctx::Lin at = l.attn, l1 = l.l1, l2 = l.l2;
@@ -195,18 +214,19 @@ int build_support_roienc(sylph_ctx* c, Plan* P) {
     ops.push_back([=](hipStream_t s) { return launch_linear(0, x, 256, S, l1.W, l1.b, l1.K, l1.O, hid, l1.O, 1, 0.f, s); });
     ops.push_back([=](hipStream_t s) { return launch_linear(0, hid, l1.O, S, l2.W, l2.b, l2.K, l2.O, t, 256, 0, 0.f, s); });
     ops.push_back([=](hipStream_t s) { return launch_add_layernorm(x, t, S, n2.gamma, n2.beta, s); });
-    RET(tap_copy(c, P, ops, SYLPH_SUP_TOKENS, ++layer, tok, true, S, 1));
+    RET(tap_copy(c, Q, ops, SYLPH_SUP_TOKENS, ++layer, tok, true, S, 1));
   }
-  tap_at(P, SYLPH_SUP_CLS_TOKENS, 0, P->re_cls, true, 0, 1);
+  tap_at(Q, SYLPH_SUP_CLS_TOKENS, 0, Q->re_cls, true, 0, 1);
   {
-    float* cls = P->re_cls;
+    float* cls = Q->re_cls;
     float* x = tok;
-    ops.push_back([=](hipStream_t s) { return launch_mean_tokens(x, S / PP->cur_shots, PP->cur_shots, cls, s); });
+    if (Q->rois) ops.push_back([=](hipStream_t s) { return launch_mean_tokens_segs(x, QQ->seg_dev, QQ->n_seg, cls, s); });
+    else ops.push_back([=](hipStream_t s) { return launch_mean_tokens(x, S / QQ->cur_shots, QQ->cur_shots, cls, s); });
     const float prior = -logf((1.f - 0.01f) / 0.01f);  // ROIEncoder hard-codes prior_prob = 0.01 (roi_encoder.py:139-140), whatever MODEL.FCOS.PRIOR_PROB says
     for (int head = 0; head < 2; ++head) {
       const std::vector<sylph_ctx::Lin>& fcs = head == 0 ? R.wh : R.bh;
       const float* in = cls;
-      float* h0 = P->re_h + (size_t)head * S * hdim;
+      float* h0 = Q->re_h + (size_t)head * S * hdim;
       for (size_t k = 0; k < fcs.size(); ++k) {
         const sylph_ctx::Lin f = fcs[k];
         const bool last = k + 1 == fcs.size();
@@ -214,18 +234,60 @@ int build_support_roienc(sylph_ctx* c, Plan* P) {
         const int off = head == 0 ? 0 : 256;
         if (last) {
           ops.push_back([=](hipStream_t s) {  // class k -> row k of the (classes, 257) output
-            return launch_linear(0, in, f.K, S / PP->cur_shots, f.W, f.b, f.K, f.O, PP->cur_code_out + off, 257, 0, add, s);
+            return launch_linear(0, in, f.K, QQ->n_seg, f.W, f.b, f.K, f.O, QQ->cur_code_out + off, 257, 0, add, s);
           });
         } else {
-          ops.push_back([=](hipStream_t s) { return launch_linear(0, in, f.K, S / PP->cur_shots, f.W, f.b, f.K, f.O, h0, f.O, 1, 0.f, s); });
+          ops.push_back([=](hipStream_t s) { return launch_linear(0, in, f.K, QQ->n_seg, f.W, f.b, f.K, f.O, h0, f.O, 1, 0.f, s); });
           in = h0;
         }
       }
     }
   }
-  P->support_built = true;
+  Q->built = true;
   return 0;
 }
+
+// the ROI list of a call against the batch: every failure names the offending index
+static int check_rois(const Plan* P, int R, const float* boxes, const int* roi_image) {
+  if (!P || !P->F) return fail("no current batch");
+  if (R < 1) return fail("ROI list: R = " + std::to_string(R) + " (at least one ROI is needed)");
+  if (!boxes || !roi_image) return fail("NULL argument");
+  for (int r = 0; r < R; ++r)
+    if (roi_image[r] < 0 || roi_image[r] >= P->B)
+      return fail("ROI list: roi_image[" + std::to_string(r) + "] = " + std::to_string(roi_image[r]) + " is outside the batch of " + std::to_string(P->B) + " images");
+  return 0;
+}
+
+// Host tables of a ROI-list call -> device, like the mixed-episode head's tables (api_head.hip ep_tables): uploaded when they differ
+// from what the pass holds, so a loop that repeats its list uploads nothing.
+static int roi_tables(sylph_ctx* c, SupportPass* Q, const int* roi_image, int n_seg, const int* seg_len) {
+  std::vector<int> ri(roi_image, roi_image + Q->S), sl(seg_len, seg_len + n_seg);
+  if (Q->roi_image_dev && ri == Q->roi_image && sl == Q->seg_len) return 0;
+  Q->roi_image.clear(); Q->seg_len.clear();  // (a failure below leaves no key that would match half-written tables)
+  std::vector<int2> sg;
+  int r0 = 0, mx = 0;
+  for (int j = 0; j < n_seg; ++j) {
+    sg.push_back(make_int2(r0, sl[j]));
+    r0 += sl[j];
+    mx = sl[j] > mx ? sl[j] : mx;
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));  // the previous call may still be reading the tables
+  if (!Q->roi_image_dev) RET(c->dalloc((void**)&Q->roi_image_dev, (size_t)Q->S * sizeof(int)));
+  if (!Q->seg_dev) RET(c->dalloc((void**)&Q->seg_dev, (size_t)Q->S * sizeof(int2)));
+  HIPCHK(hipMemcpy(Q->roi_image_dev, ri.data(), ri.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(Q->seg_dev, sg.data(), sg.size() * sizeof(int2), hipMemcpyHostToDevice));
+  Q->roi_image = ri; Q->seg_len = sl; Q->max_len = mx;
+  ++c->roi_table_uploads;
+  return 0;
+}
+
+// scratch context of the stand-alone ROIAlign entries: its allocations are freed on return
+struct RoiScratch {
+  sylph_ctx tmp;
+  hipStream_t s;
+  explicit RoiScratch(sylph_ctx* c) : s(c->stream) { tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros; }
+  ~RoiScratch() { (void)hipStreamSynchronize(s); for (void* p : tmp.allocs) (void)hipFree(p); }
+};
 
 }  // namespace sylph_host
 
@@ -237,37 +299,53 @@ int sylph_roi_align(sylph_ctx* c, const float* boxes, float* out) {
   if (!boxes || !out) return fail("NULL argument");
   HIPCHK(hipSetDevice(c->device));
   const int S = P->B, L = c->cfg.nlevels;
-  std::vector<LevelDesc> lv;
-  for (int b = 0; b < S; ++b)
-    for (int l = 0; l < L; ++l)
-      lv.push_back(LevelDesc{b * P->Ltot + P->off[l], P->hl[l], P->wl[l], 1.0f / (float)c->cfg.strides[l]});
-  sylph_ctx tmp;  // scratch allocations freed on return
-  tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros;
-  struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
+  const std::vector<LevelDesc> lv = level_table(c, P);
+  RoiScratch sc(c);
   LevelDesc* lvd = nullptr;
   void* roi = nullptr;
-  RET(upload(&tmp, (void**)&lvd, lv.data(), lv.size() * sizeof(LevelDesc)));
-  RET(tmp.dalloc(&roi, (size_t)S * 49 * 256 * c->esz()));
+  RET(upload(&sc.tmp, (void**)&lvd, lv.data(), lv.size() * sizeof(LevelDesc)));
+  RET(sc.tmp.dalloc(&roi, (size_t)S * 49 * 256 * c->esz()));
   KCHK(launch_roi_align(c->dt, P->F, 256, lvd, L, boxes, S, 7, roi, c->stream), "roi_align");
   for (int s = 0; s < S; ++s)
     KCHK(launch_export_nchw(c->dt, roi, out + (size_t)s * 256 * 49, 256, 49, s * 49, 256, c->stream), "export roi");
   return 0;
 }
 
-static int support_tap(sylph_ctx* c, int stage, int index, const Plan::SupTap** t, int* n) {
+int sylph_roi_align_rois(sylph_ctx* c, int R, const float* boxes, const int* roi_image, float* out) {
   Plan* P = c->cur;
-  if (!P || !P->support_built) return fail("no code-generator pass on the current batch");
-  auto it = P->sup_taps.find({stage, index});
-  if (it == P->sup_taps.end())
+  RET(check_rois(P, R, boxes, roi_image));
+  if (!out) return fail("NULL argument");
+  HIPCHK(hipSetDevice(c->device));
+  const int L = c->cfg.nlevels;
+  const std::vector<LevelDesc> lv = level_table(c, P);
+  RoiScratch sc(c);
+  LevelDesc* lvd = nullptr;
+  int* rid = nullptr;
+  void* roi = nullptr;
+  RET(upload(&sc.tmp, (void**)&lvd, lv.data(), lv.size() * sizeof(LevelDesc)));
+  RET(upload(&sc.tmp, (void**)&rid, roi_image, (size_t)R * sizeof(int)));
+  RET(sc.tmp.dalloc(&roi, (size_t)R * 49 * 256 * c->esz()));
+  KCHK(launch_roi_align_rois(c->dt, P->F, 256, lvd, L, boxes, rid, R, 7, roi, c->stream), "roi_align_rois");
+  for (int r = 0; r < R; ++r)
+    KCHK(launch_export_nchw(c->dt, roi, out + (size_t)r * 256 * 49, 256, 49, r * 49, 256, c->stream), "export roi");
+  return 0;
+}
+
+static int support_tap(sylph_ctx* c, int stage, int index, const SupportPass::SupTap** t, int* n) {
+  Plan* P = c->cur;
+  const SupportPass* Q = P ? P->sup_last : nullptr;
+  if (!Q || !Q->built) return fail("no code-generator pass on the current batch");
+  auto it = Q->taps.find({stage, index});
+  if (it == Q->taps.end())
     return fail("support tap (" + std::to_string(stage) + ", " + std::to_string(index) + ") does not exist in this configuration" +
                 (c->debug_taps ? "" : " (intermediate stages need sylph_set_debug_taps(1) before the first code-generator call of a batch shape)"));
   *t = &it->second;
-  *n = it->second.n > 0 ? it->second.n : P->B / (P->cur_shots > 0 ? P->cur_shots : P->B);
+  *n = it->second.n > 0 ? it->second.n : Q->n_seg;
   return 0;
 }
 
 int sylph_support_tap_numel(sylph_ctx* c, int stage, int index, int64_t* numel) {
-  const Plan::SupTap* t;
+  const SupportPass::SupTap* t;
   int n;
   RET(support_tap(c, stage, index, &t, &n));
   *numel = t->stats ? (int64_t)n * 512 : (int64_t)n * t->C * t->npos;
@@ -275,7 +353,7 @@ int sylph_support_tap_numel(sylph_ctx* c, int stage, int index, int64_t* numel) 
 }
 
 int sylph_export_support(sylph_ctx* c, int stage, int index, float* out) {
-  const Plan::SupTap* t;
+  const SupportPass::SupTap* t;
   int n;
   RET(support_tap(c, stage, index, &t, &n));
   if (!out) return fail("NULL argument");
@@ -315,20 +393,57 @@ int sylph_codegen_classes(sylph_ctx* c, const float* boxes, int shots, float* co
   if (shots < 1 || P->B % shots != 0) return fail("pooled_features.shape[0] " + std::to_string(P->B) + " Vs batch_size * num_shots: the batch is not a whole number of classes");
   if (shots > 64) return fail("codegen: " + std::to_string(shots) + " shots per class in one call; the shot reduction handles at most 64 (chunk the class and reduce the chunk codes, sylph_reduce_codes)");
   OwnerScope own(c, P);
-  if (c->cfg.cg_type == 1) BUILD(build_support_roienc(c, P), P);
-  else BUILD(build_support(c, P), P);
-  P->cur_boxes = boxes;
-  P->cur_code_out = codes_out;
-  P->cur_shots = shots;
-  return run_ops(c, P->support_ops, "codegen");
+  SupportPass* Q = &P->sup;
+  Q->S = P->B;
+  if (c->cfg.cg_type == 1) BUILD(build_support_roienc(c, P, Q), P);
+  else BUILD(build_support(c, P, Q), P);
+  Q->cur_boxes = boxes;
+  Q->cur_code_out = codes_out;
+  Q->cur_shots = shots;
+  Q->n_seg = P->B / shots;
+  P->sup_last = Q;
+  return run_ops(c, Q->ops, "codegen");
+}
+
+int sylph_codegen_rois(sylph_ctx* c, int R, const float* boxes, const int* roi_image, int n_seg, const int* seg_len, float* codes_out) {
+  Plan* P = c->cur;
+  RET(check_rois(P, R, boxes, roi_image));
+  if (!seg_len || !codes_out) return fail("NULL argument");
+  if (n_seg < 1) return fail("ROI list: n_seg = " + std::to_string(n_seg) + " (at least one segment is needed)");
+  long total = 0;
+  for (int j = 0; j < n_seg; ++j) {
+    if (seg_len[j] < 1) return fail("ROI list: seg_len[" + std::to_string(j) + "] = " + std::to_string(seg_len[j]) + " (a segment needs at least one ROI)");
+    total += seg_len[j];
+  }
+  if (total != R) return fail("ROI list: the segment lengths sum to " + std::to_string(total) + ", not to R = " + std::to_string(R));
+  if (R > 65535) return fail("ROI list: R = " + std::to_string(R) + " ROIs in one call; at most 65535");
+  HIPCHK(hipSetDevice(c->device));
+  OwnerScope own(c, P);
+  auto& slot = P->sup_rois[R];
+  if (!slot) { slot.reset(new SupportPass()); slot->S = R; slot->rois = true; }
+  SupportPass* Q = slot.get();
+  if (c->cfg.cg_type == 1) BUILD(build_support_roienc(c, P, Q), P);
+  else BUILD(build_support(c, P, Q), P);
+  RET(roi_tables(c, Q, roi_image, n_seg, seg_len));
+  Q->cur_boxes = boxes;
+  Q->cur_code_out = codes_out;
+  Q->n_seg = n_seg;
+  P->sup_last = Q;
+  return run_ops(c, Q->ops, "codegen_rois");
+}
+
+int sylph_roi_table_uploads(sylph_ctx* c, int64_t* n) {
+  if (!n) return fail("NULL argument");
+  *n = c->roi_table_uploads;
+  return 0;
 }
 
 int sylph_codegen_weight_norm(sylph_ctx* c, float* out) {
   Plan* P = c->cur;
-  if (!P || !P->support_built || !P->cg_wnorm) return fail("no code-generator pass on the current batch");
+  const SupportPass* Q = P ? P->sup_last : nullptr;
+  if (!Q || !Q->built || !Q->cg_wnorm) return fail("no code-generator pass on the current batch");
   if (!c->cfg.cg_has_scale) return fail("CODE_GENERATOR.SCALE_LAYER is empty: there is no cls_weight_norm");
-  const int ncls = P->B / (P->cur_shots > 0 ? P->cur_shots : P->B);
-  HIPCHK(hipMemcpyAsync(out, P->cg_wnorm, (size_t)ncls * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(out, Q->cg_wnorm, (size_t)Q->n_seg * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 

@@ -155,6 +155,7 @@ struct sylph_ctx {
   // plans are evicted least-recently-used first once their count or their bytes exceed the budget, so a stream of
   // distinct padded shapes (real COCO / LVIS episodes) cannot grow HBM without bound.
   Plan* alloc_owner = nullptr;
+  int64_t roi_table_uploads = 0;  // sylph_codegen_rois calls that had to upload their ROI tables (sylph_roi_table_uploads)
   bool debug_taps = false;  // sylph_set_debug_taps: tower layers keep their outputs in separate buffers (parity tests)
   uint64_t use_clock = 0;
   size_t max_plans = 32;
@@ -171,6 +172,39 @@ struct sylph_ctx {
   std::map<void*, size_t> alloc_bytes;
   void dfree(void* p);  // release one dalloc'ed buffer (the stream may still use it: drained first)
   size_t esz() const { return dt == DT_BF16 ? 2 : 4; }
+};
+
+// One support pass of a plan: the workspaces, launches and parity taps of the code generator for S rows (ROIs) of 49 positions.
+// The plan's own pass (Plan::sup) has row s = image s with its one box; a ROI-list pass (Plan::sup_rois[R]) has row r =
+// (roi_image[r], boxes[r]) and reduces ragged segments of consecutive rows, one code per segment.
+struct SupportPass {
+  int S = 0;           // rows: support images (one box each) or ROIs
+  bool rois = false;   // a ROI-list pass
+  bool built = false;
+  std::vector<OpFn> ops;
+  void *roi = nullptr, *cgA = nullptr, *cgB = nullptr;
+  float *cg_conv_out = nullptr, *cg_bias_out = nullptr, *cg_wnorm = nullptr;  // cg_wnorm: cls_weight_norm per class of the last call
+  float *re_ctx = nullptr, *re_tok = nullptr, *re_tmp = nullptr, *re_hid = nullptr, *re_cls = nullptr, *re_h = nullptr;
+  // support-path taps (sylph_export_support): (stage, index) -> where that stage's output of the last pass lives; the stages
+  // whose buffer a later op overwrites are copied aside, only with debug taps on
+  struct SupTap {
+    const void* p = nullptr;
+    bool f32 = true;  // fp32 buffer (else the context's storage type)
+    int n = 0, npos = 49, C = 256, ld = 256;  // [n * npos][ld], first C channels (see api_codegen.hip tap_at)
+    const float2* stats = nullptr;  // GroupNorm (mean, rstd) per (image, group) of the in-place apply, with its gamma / beta
+    const float *gamma = nullptr, *beta = nullptr;
+  };
+  std::map<std::pair<int, int>, SupTap> taps;
+  // the current call (read by the ops at launch time)
+  const float* cur_boxes = nullptr;
+  int cur_shots = 0;  // support images per class of the current sylph_codegen[_classes] call (S = classes x shots)
+  int n_seg = 0;      // codes of the current call: classes, or segments of the ROI list
+  float* cur_code_out = nullptr;
+  // ROI-list pass: the caller's host tables as last uploaded (an unchanged list uploads nothing) and their device copies
+  std::vector<int> roi_image, seg_len;
+  int max_len = 0;             // longest segment of seg_len
+  int* roi_image_dev = nullptr;  // [S]
+  int2* seg_dev = nullptr;       // [S] capacity: {first row, rows} per segment
 };
 
 struct Plan {
@@ -195,8 +229,8 @@ struct Plan {
   int stage_h[4] = {0, 0, 0, 0}, stage_w[4] = {0, 0, 0, 0}, stage_c[4] = {0, 0, 0, 0};
   std::vector<const void*> tap_out[2];      // [cls | bbox][layer]: conv output [rows][256] (pre-GroupNorm when tap_coef is set)
   std::vector<const float2*> tap_coef[2];   // [cls | bbox][layer]: (a, b) per (segment, channel), nullptr if applied in place
-  std::vector<OpFn> backbone_ops, head_ops, support_ops;
-  bool backbone_built = false, head_built = false, support_built = false;
+  std::vector<OpFn> backbone_ops, head_ops;
+  bool backbone_built = false, head_built = false;
   ImageDesc* img_desc_dev = nullptr;
   ImageDesc* img_desc_host = nullptr;
   std::vector<ImageDesc> img_desc_last;  // what img_desc_dev holds (sylph_preprocess skips the H2D copy of an unchanged table)
@@ -263,23 +297,11 @@ struct Plan {
   std::vector<ImageOut> img_out_last;  // what img_out_dev holds (the H2D copy is skipped when a call's scales equal it)
   hipEvent_t img_out_ev = nullptr;  // recorded after the H2D copy of img_out_host (guards its reuse without a stream sync)
   // support
-  LevelDesc* lv_dev = nullptr;
-  void *roi = nullptr, *cgA = nullptr, *cgB = nullptr;
-  float *cg_conv_out = nullptr, *cg_bias_out = nullptr, *cg_wnorm = nullptr;  // cg_wnorm: cls_weight_norm per class of the last call
-  float *re_ctx = nullptr, *re_tok = nullptr, *re_tmp = nullptr, *re_hid = nullptr, *re_cls = nullptr, *re_h = nullptr;
-  // support-path taps (sylph_export_support): (stage, index) -> where that stage's output of the last support pass lives; the stages
-  // whose buffer a later op overwrites are copied aside, only with debug taps on
-  struct SupTap {
-    const void* p = nullptr;
-    bool f32 = true;  // fp32 buffer (else the context's storage type)
-    int n = 0, npos = 49, C = 256, ld = 256;  // [n * npos][ld], first C channels (see api_codegen.hip tap_at)
-    const float2* stats = nullptr;  // GroupNorm (mean, rstd) per (image, group) of the in-place apply, with its gamma / beta
-    const float *gamma = nullptr, *beta = nullptr;
-  };
-  std::map<std::pair<int, int>, SupTap> sup_taps;
-  const float* cur_boxes = nullptr;
-  int cur_shots = 0;  // support images per class of the current sylph_codegen[_classes] call (B = classes x shots)
-  float* cur_code_out = nullptr;
+  LevelDesc* lv_dev = nullptr;  // per (image, level) of the batch: B x nlevels entries, shared by every support pass of the plan
+  SupportPass sup;              // sylph_codegen / sylph_codegen_classes: one box per image, S = B rows
+  // sylph_codegen_rois: one pass per ROI count R (workspaces and conv routes follow R as they follow B above)
+  std::map<int, std::unique_ptr<SupportPass>> sup_rois;
+  SupportPass* sup_last = nullptr;  // the pass of the last code-generator call on this plan (taps, cls_weight_norm)
 };
 
 // allocations made inside the scope belong to plan P (nullptr: to the context, e.g. re-packed weights)
@@ -391,7 +413,7 @@ DecodeCfg decode_cfg(const sylph_ctx* c, const Plan* P, int max_out);
 int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow = false);
 int run_cond_logits(sylph_ctx* c, Plan* P);
 // api_codegen.hip
-int build_support(sylph_ctx* c, Plan* P);
-int build_support_roienc(sylph_ctx* c, Plan* P);
+int build_support(sylph_ctx* c, Plan* P, SupportPass* Q);
+int build_support_roienc(sylph_ctx* c, Plan* P, SupportPass* Q);
 }  // namespace sylph_host
 using namespace sylph_host;

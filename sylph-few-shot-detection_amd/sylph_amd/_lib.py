@@ -60,10 +60,13 @@ PROTOTYPES = {
     "sylph_export_head": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylph_import_head": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylph_roi_align": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "sylph_roi_align_rois": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p]),
     "sylph_decode_nms": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylph_codegen": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sylph_codegen_classes": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "sylph_codegen_rois": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_int, POINTER(c_int), c_void_p]),
+    "sylph_roi_table_uploads": (c_int, [c_void_p, POINTER(c_int64)]),
     "sylph_codegen_weight_norm": (c_int, [c_void_p, c_void_p]),
     "sylph_normalize_codes": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "sylph_reduce_codes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int]),

@@ -473,6 +473,32 @@ class Engine:
         check(self.L.sylph_roi_align(self._ctx, _ptr(bx), _ptr(out)), "roi_align")
         return out
 
+    def _check_rois(self, boxes: torch.Tensor, roi_image) -> Tuple[torch.Tensor, List[int]]:
+        """The ROI list of a call against the current batch -> (boxes (R, 4) on the device, roi_image as ints)."""
+        if getattr(self, "_batch", None) is None:
+            raise ValueError("no current batch")
+        if boxes is None or roi_image is None:
+            raise ValueError("boxes and roi_image must be given")
+        B = self._batch[0]
+        ri = [int(i) for i in (roi_image.tolist() if torch.is_tensor(roi_image) else roi_image)]
+        R = len(ri)
+        if R < 1:
+            raise ValueError("the ROI list is empty (R < 1)")
+        if boxes.numel() != 4 * R:
+            raise ValueError(f"boxes has {boxes.numel()} values for {R} ROIs: (R, 4) expected")
+        for r, i in enumerate(ri):
+            if i < 0 or i >= B:
+                raise ValueError(f"roi_image[{r}] = {i} is outside the batch of {B} images")
+        return boxes.to(self.device, torch.float32).reshape(R, 4).contiguous(), ri
+
+    def roi_align_rois(self, boxes: torch.Tensor, roi_image) -> torch.Tensor:
+        """Test boundary: the ROIPooler call over a ROI list, box r on image roi_image[r] of the current batch -> (R,256,7,7)."""
+        self._stream()
+        bx, ri = self._check_rois(boxes, roi_image)
+        out = torch.empty(len(ri), 256, 7, 7, device=self.device)
+        check(self.L.sylph_roi_align_rois(self._ctx, len(ri), _ptr(bx), _iarr(ri), _ptr(out)), "roi_align_rois")
+        return out
+
     def decode(self, out_sizes: Optional[List[Tuple[int, int]]] = None, max_out: Optional[int] = None):
         """-> per image dict of device tensors (pred_boxes, scores, pred_classes, fpn_levels, locations,
         cand_index).  One device->host copy of the per-image counts (the only sync of a query step)."""
@@ -551,6 +577,7 @@ class Engine:
         out = torch.empty(257, device=self.device)
         self._keep_boxes = bx
         check(self.L.sylph_codegen(self._ctx, _ptr(bx), _ptr(out)), "codegen")
+        self._sup_rows = None
         return out
 
     def codegen_classes(self, boxes: torch.Tensor, shots: int) -> torch.Tensor:
@@ -566,10 +593,41 @@ class Engine:
         out = torch.empty(B // shots, 257, device=self.device)
         self._keep_boxes = bx
         check(self.L.sylph_codegen_classes(self._ctx, _ptr(bx), int(shots), _ptr(out)), "codegen_classes")
+        self._sup_rows = None
         return out
 
+    def codegen_rois(self, boxes: torch.Tensor, roi_image, seg_len) -> torch.Tensor:
+        """Class codes from a ROI list over the current batch (sylph_codegen_rois): ROI r is boxes[r] on image roi_image[r], any
+        number per image in any order; the ROIs are cut into consecutive segments of seg_len[j] >= 1 shots and row j of the
+        (n_seg, 257) result is the un-normalised code of segment j, as `codegen` gives it for a batch holding the segment's images
+        once per ROI.  No cap on a segment's length."""
+        self._stream()
+        bx, ri = self._check_rois(boxes, roi_image)
+        if seg_len is None:
+            raise ValueError("seg_len must be given")
+        sl = [int(n) for n in (seg_len.tolist() if torch.is_tensor(seg_len) else seg_len)]
+        if len(sl) < 1:
+            raise ValueError("the ROI list has no segment (n_seg < 1)")
+        for j, n in enumerate(sl):
+            if n < 1:
+                raise ValueError(f"seg_len[{j}] = {n}: a segment needs at least one ROI")
+        if sum(sl) != len(ri):
+            raise ValueError(f"the segment lengths sum to {sum(sl)}, not to R = {len(ri)}")
+        out = torch.empty(len(sl), 257, device=self.device)
+        self._keep_boxes = bx
+        check(self.L.sylph_codegen_rois(self._ctx, len(ri), _ptr(bx), _iarr(ri), len(sl), _iarr(sl), _ptr(out)), "codegen_rois")
+        self._sup_rows = len(ri)
+        return out
+
+    def roi_table_uploads(self) -> int:
+        """How many codegen_rois calls of this engine uploaded their ROI tables (a repeated identical list uploads none)."""
+        n = c_int64(0)
+        check(self.L.sylph_roi_table_uploads(self._ctx, ctypes.byref(n)), "roi_table_uploads")
+        return n.value
+
     def codegen_weight_norm(self, n_classes: int = 1) -> torch.Tensor:
-        """cls_weight_norm of the last codegen / codegen_classes call (CODE_GENERATOR.SCALE_LAYER), one value per class."""
+        """cls_weight_norm of the last codegen / codegen_classes / codegen_rois call (CODE_GENERATOR.SCALE_LAYER), one value per
+        class (per segment after codegen_rois)."""
         self._stream()
         out = torch.empty(n_classes, device=self.device)
         check(self.L.sylph_codegen_weight_norm(self._ctx, _ptr(out)), "codegen_weight_norm")
@@ -667,7 +725,7 @@ class Engine:
     SUPPORT_STAGES = ("roi", "gn_y", "gn_coef", "layer_out", "conv_out", "context", "mscam", "tokens", "cls_tokens")
 
     def export_support(self, stage: str, index: int = 0) -> torch.Tensor:
-        """One stage output of the last codegen / codegen_classes call (sylph_export_support; stage names as SUPPORT_STAGES, in the
+        """One stage output of the last codegen / codegen_classes / codegen_rois call (sylph_export_support; stage names as SUPPORT_STAGES, in the
         order of the SYLPH_SUP_* constants): maps (S, C, 7, 7), GroupNorm coefficients (S, 256, 2), tokens (rows, 256), fp32."""
         self._stream()
         st = self.SUPPORT_STAGES.index(stage)
@@ -676,6 +734,8 @@ class Engine:
         out = torch.empty(n.value, device=self.device)
         check(self.L.sylph_export_support(self._ctx, st, int(index), _ptr(out)), "export_support")
         B = self._batch[0]
+        if stage != "context":  # after codegen_rois the per-shot stages have one row per ROI; the context stays per image
+            B = getattr(self, "_sup_rows", None) or B
         if stage == "gn_coef":
             return out.view(B, 256, 2)
         if stage in ("tokens", "cls_tokens"):

@@ -187,6 +187,98 @@ def inference_on_support_set_dataset_base(model, data_loader, all_id_map=None, b
     return results
 
 
+def plan_roi_segments(records: List[Dict[str, Any]], chunk: int = 10):
+    """Annotated records -> the ROI list of ONE batch that holds each image once.  Every instance (instances.gt_boxes[i] with
+    instances.gt_classes[i]) is a support shot of its class; the shots of a class follow image order, then box order, and are cut
+    into segments of at most `chunk` shots (the chunking of the base-class path, meta_learn_evaluation.py:118-254); the segments
+    of a class are consecutive and the classes come in order of first appearance.  A record without boxes contributes nothing.
+    Returns (boxes (R, 4) fp32, roi_image [R], seg_len [n_seg], seg_class [n_seg]).  Pure host code, no random choice."""
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"chunk must be at least 1, got {chunk}")
+    shots: Dict[int, List[Any]] = {}  # class id -> [(image, box)], dicts keep first-appearance order
+    for b, rec in enumerate(records):
+        inst = rec.get("instances") if isinstance(rec, dict) else None
+        if inst is None or len(inst.gt_boxes.tensor) == 0:
+            continue
+        gt = inst.gt_boxes.tensor.detach().float().cpu().reshape(-1, 4)
+        cls = torch.as_tensor(inst.gt_classes).reshape(-1).tolist()
+        assert len(cls) == gt.shape[0], f"record {b}: {len(cls)} classes for {gt.shape[0]} boxes"
+        for i, cid in enumerate(cls):
+            shots.setdefault(int(cid), []).append((b, gt[i]))
+    boxes, roi_image, seg_len, seg_class = [], [], [], []
+    for cid, items in shots.items():
+        for k in range(0, len(items), chunk):
+            part = items[k:k + chunk]
+            boxes.extend(bx for _, bx in part)
+            roi_image.extend(b for b, _ in part)
+            seg_len.append(len(part))
+            seg_class.append(cid)
+    return (torch.stack(boxes) if boxes else torch.zeros(0, 4)), roi_image, seg_len, seg_class
+
+
+def inference_on_annotated_images(model, data_loader, chunk: int = 10, class_names=None, output_dir: str = None) -> List[Dict[str, Any]]:
+    """Base-class codes from annotated images at one backbone pass per image.  Each loader item is a list of annotated records
+    ("image", "instances" with gt_boxes / gt_classes); plan_roi_segments turns the item into one ROI list and
+    model.forward_class_codes_rois runs it as ONE batch.  Every segment code is weighted by its instance count and the rows of
+    the whole loader are reduced once on the device (Engine.reduce_codes, divide_by_acc): a class's code is the
+    instance-count-weighted mean of its chunk codes, the len / total_len weighting of inference_on_support_set_dataset_base.
+    Returns that function's records (first-appearance class order), so normalisation, the cross-rank gather and the .pth files
+    SylphPredictor reads work unchanged.  `class_names`: class id -> name (a dict or a sequence); default str(id)."""
+    from . import distributed as D
+    engine = getattr(model, "engine", None)
+    if output_dir is not None:
+        os.makedirs(output_dir, exist_ok=True)
+
+    def name_of(cid: int) -> str:
+        if class_names is None:
+            return str(cid)
+        return str(class_names[cid])
+
+    rows, names = [], {}
+    with ExitStack() as stack:
+        if isinstance(model, nn.Module):
+            stack.enter_context(inference_context(model))
+        stack.enter_context(torch.no_grad())
+        for records in data_loader:
+            boxes, roi_image, seg_len, seg_class = plan_roi_segments(records, chunk)
+            if not seg_len:
+                continue
+            segments, r0 = [], 0
+            for n in seg_len:
+                segments.append({"image_index": torch.tensor(roi_image[r0:r0 + n], dtype=torch.long), "boxes": boxes[r0:r0 + n]})
+                r0 += n
+            codes = model.forward_class_codes_rois(records, segments)  # device tensors; nothing is read back per item
+            for cid in seg_class:
+                names.setdefault(cid, name_of(cid))
+            w = torch.tensor(seg_len, dtype=torch.float32, device=codes[0]["cls_conv"].device)
+            conv = torch.cat([c["cls_conv"].reshape(1, 256) for c in codes]) * w[:, None]
+            bias = torch.cat([c["cls_bias"].reshape(1) for c in codes]) * w
+            wn = torch.cat([c["cls_weight_norm"].reshape(1) for c in codes]) * w if "cls_weight_norm" in codes[0] else None
+            rows.append(D.pack_codes(conv, bias, seg_class, seg_len, wn, [names[cid] for cid in seg_class]))
+    if not rows:
+        return []
+    packed = torch.cat(rows).contiguous()
+    ncls = max(names) + 1
+    if engine is not None and packed.is_cuda:
+        red = engine.reduce_codes(packed, ncls, divide_by_acc=True)
+    else:
+        red = D.scatter_by_class_id(D.reduce_packed_codes(packed, divide_by_acc=True), ncls)
+    red = red.cpu()  # the only read-back of the loop
+    results = []
+    for cid in names:  # first-appearance order
+        r = red[cid]
+        cc = {"cls_conv": r[:256].reshape(1, 256, 1, 1).clone(), "cls_bias": r[256:257].reshape(1, 1, 1, 1).clone(),
+              "acc_weight": float(r[D.F_ACC])}
+        if float(r[D.F_HAS_WNORM]) > 0:
+            cc["cls_weight_norm"] = r[D.F_WNORM:D.F_WNORM + 1].reshape(1, 1, 1, 1).clone()
+        result = {"support_set_target": cid, "class_name": names[cid], "class_code": cc}
+        if output_dir is not None:
+            torch.save(result, os.path.join(output_dir, f"{result['class_name']}.pth"))
+        results.append(result)
+    return results
+
+
 class _NoOpEvaluator:
     def reset(self):
         pass

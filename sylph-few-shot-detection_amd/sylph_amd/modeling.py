@@ -161,6 +161,18 @@ class CodeGenerator(HipComponent):
         return outs
 
 
+    def forward_rois(self, boxes: torch.Tensor, roi_image, seg_len):
+        """Classes from a ROI list over the current batch (Engine.codegen_rois): segment j of seg_len[j] (image, box) pairs -> one
+        code dict per segment, in forward_classes' shapes.  A segment's arithmetic is that of __call__ on its shots."""
+        codes = self.engine.codegen_rois(boxes, roi_image, seg_len)
+        outs = [{"cls_conv": c[:256].reshape(1, 256, 1, 1), "cls_bias": c[256:257].reshape(1, 1, 1, 1)} for c in codes]
+        if self.has_scale:
+            wn = self.engine.codegen_weight_norm(len(outs))
+            for o, w in zip(outs, wn):
+                o["cls_weight_norm"] = w.reshape(1, 1, 1, 1)
+        return outs
+
+
 @CODE_GENERATOR_REGISTRY.register()
 class ROIEncoder(HipComponent):
     """ROIEncoder.forward at inference (roi_encoder.py:146-204): one class of EVAL_SHOT support boxes -> its code."""
@@ -181,6 +193,15 @@ class ROIEncoder(HipComponent):
         sequence on its attention axis, roi_encoder.py:184-186), so the codes are those of __call__ per class."""
         assert shots == self.eval_shot, f"{shots} support images per class, EVAL_SHOT is {self.eval_shot}"
         codes = self.engine.codegen_classes(boxes, shots)
+        return [{"cls_conv": c[:256].reshape(1, 256, 1, 1), "cls_bias": c[256:257].reshape(1)} for c in codes]
+
+
+    def forward_rois(self, boxes: torch.Tensor, roi_image, seg_len):
+        """Classes from a ROI list over the current batch: every segment holds EVAL_SHOT (image, box) pairs -> one code dict per
+        segment.  As in forward_classes a segment's tokens never meet another segment's."""
+        for j, n in enumerate(seg_len):
+            assert int(n) == self.eval_shot, f"segment {j} has {int(n)} ROIs, EVAL_SHOT is {self.eval_shot}"
+        codes = self.engine.codegen_rois(boxes, roi_image, seg_len)
         return [{"cls_conv": c[:256].reshape(1, 256, 1, 1), "cls_bias": c[256:257].reshape(1)} for c in codes]
 
 
@@ -330,6 +351,33 @@ class MetaOneStageDetector(nn.Module):
         self.backbone(images=[rec["image"] for r in recs for rec in r])
         boxes = torch.cat([rec["instances"].gt_boxes.tensor.reshape(1, 4) for r in recs for rec in r], dim=0)
         return self.code_generator.forward_classes(boxes, shots)
+
+    def forward_class_codes_rois(self, records: List[Dict[str, Any]], segments: List[Dict[str, torch.Tensor]]) -> List[Dict[str, torch.Tensor]]:
+        """Class codes from annotated images at ONE backbone pass per image: `records` are the B images of the batch (dicts with
+        "image"), `segments` a list of {"image_index": LongTensor(n), "boxes": Tensor(n, 4)}: the n support instances of one class
+        (or one chunk of a class), instance i being box boxes[i] on records[image_index[i]], in network-input coordinates like
+        gt_boxes.  Returns one code dict per segment in forward_class_code's format; a segment's code is forward_class_code's on a
+        support set that repeats each image once per instance.  Every given instance counts: nothing is drawn at random."""
+        assert not self.training, "Not for training"
+        assert self.episodic_learning and hasattr(self.code_generator, "forward_rois")
+        boxes, roi_image, seg_len = [], [], []
+        for j, seg in enumerate(segments):
+            idx = torch.as_tensor(seg["image_index"]).reshape(-1).tolist()
+            bx = torch.as_tensor(seg["boxes"]).reshape(-1, 4)
+            if len(idx) == 0:
+                raise ValueError(f"segment {j} is empty: a class needs at least one support instance")
+            if len(idx) != bx.shape[0]:
+                raise ValueError(f"segment {j} has {len(idx)} image indices for {bx.shape[0]} boxes")
+            for i in idx:
+                if i < 0 or i >= len(records):
+                    raise ValueError(f"segment {j}: image_index {i} is outside the {len(records)} records")
+            boxes.append(bx.float().cpu())
+            roi_image.extend(int(i) for i in idx)
+            seg_len.append(len(idx))
+        if not segments:
+            raise ValueError("no segments")
+        self.backbone(images=[rec["image"] for rec in records])
+        return self.code_generator.forward_rois(torch.cat(boxes, dim=0), roi_image, seg_len)
 
     def normalize_class_code(self, codes: List[Dict]):
         """code_generator.py:877-897 via meta_one_stage_detector.py:256-259 (mutates the list)."""
