@@ -209,38 +209,41 @@ int build_head(sylph_ctx* c, Plan* P) {
 // buffer holds EVERY (location, class) score of the largest level (5-way: 84 000, 20-way: 262 144 of 336 000), i.e. it cannot
 // overflow for few-shot class counts; many-way episodes get 1/8 of the scores (LVIS 866-way: 1.8 M), at most 4 M
 // (HBM is plentiful: 8 bytes per slot).
-int want_cand_cap(const sylph_ctx* c, const Plan* P) {
+static int want_cand_cap(const sylph_ctx* c, const Plan* P, int ncls) {
   if (c->cfg.cand_cap > 0) return c->cfg.cand_cap;
-  const long all = (long)P->hl[0] * P->wl[0] * (long)(P->ncls > 0 ? P->ncls : 1);
+  const long all = (long)P->hl[0] * P->wl[0] * (long)(ncls > 0 ? ncls : 1);
   long w = all <= 262144 ? all : (all / 8 > 262144 ? all / 8 : 262144);
   if (w < 4096) w = 4096;
   if (w > (1L << 22)) w = 1L << 22;
   return (int)w;
 }
 
-int build_decode(sylph_ctx* c, Plan* P) {
-  if (P->decode_built) return 0;
-  const int L = c->cfg.nlevels, B = P->B, nseg = B * L;
+// the decode's segment table; img_ncls[b]: DecodeSeg::ncls of image b (nullptr: 0 everywhere, the plan's own table)
+static std::vector<DecodeSeg> decode_segs(const sylph_ctx* c, const Plan* P, const int* img_ncls) {
   std::vector<DecodeSeg> ds;
-  for (int b = 0; b < B; ++b) {
+  for (int b = 0; b < P->B; ++b) {
     unsigned lb = 0;
-    for (int l = 0; l < L; ++l) {
+    for (int l = 0; l < c->cfg.nlevels; ++l) {
       DecodeSeg d;
       d.row0 = b * P->Ltot + P->off[l]; d.nloc = P->hl[l] * P->wl[l]; d.W = P->wl[l];
-      d.stride = c->cfg.strides[l]; d.level = l; d.image = b; d.loc_base = lb; d.ncls = 0;
+      d.stride = c->cfg.strides[l]; d.level = l; d.image = b; d.loc_base = lb; d.ncls = img_ncls ? img_ncls[b] : 0;
       lb += (unsigned)d.nloc;
       ds.push_back(d);
     }
   }
+  return ds;
+}
+
+static int build_decode(sylph_ctx* c, Plan* P) {
+  if (P->decode_built) return 0;
+  const int L = c->cfg.nlevels, B = P->B, nseg = B * L;
+  const std::vector<DecodeSeg> ds = decode_segs(c, P, nullptr);
   RET(upload(c, (void**)&P->dsegs, ds.data(), ds.size() * sizeof(DecodeSeg)));
   int pool = 64;
   while (pool < L * c->cfg.pre_nms_topk) pool <<= 1;
   if (pool > 8192) return fail("levels * PRE_NMS_TOPK exceeds the 8192-entry on-chip sort capacity");
   P->pool_cap = pool;
-  P->cand_cap = want_cand_cap(c, P);
-  DecodeBuffers& d = P->dbuf;
-  RET(c->dalloc((void**)&d.cand_key, (size_t)nseg * P->cand_cap * 4));
-  RET(c->dalloc((void**)&d.cand_idx, (size_t)nseg * P->cand_cap * 4));
+  DecodeBuffers& d = P->dbuf;  // (cand_key, cand_idx: ensure_decode)
   RET(c->dalloc((void**)&d.cand_count, (size_t)nseg * 4));
   RET(c->dalloc((void**)&d.sel_ws, (size_t)nseg * SEL_WS * 4));
   RET(c->dalloc((void**)&d.sel_tie, (size_t)nseg * SEL_TIE * 8));
@@ -264,32 +267,53 @@ int build_decode(sylph_ctx* c, Plan* P) {
   return 0;
 }
 
-// more classes than when the decode buffers were built: grow the candidate buffers
-int ensure_cand_cap(sylph_ctx* c, Plan* P) {
-  if (want_cand_cap(c, P) <= P->cand_cap) return 0;
-  const int nseg = P->B * c->cfg.nlevels;
-  P->cand_cap = want_cand_cap(c, P);
+// the decode buffers of the plan, with candidate buffers for ncls classes (more than the last call's: they grow)
+static int ensure_decode(sylph_ctx* c, Plan* P, int ncls) {
+  BUILD(build_decode(c, P), P);
+  if (want_cand_cap(c, P, ncls) <= P->cand_cap) return 0;
+  const size_t bytes = (size_t)P->B * c->cfg.nlevels * want_cand_cap(c, P, ncls) * 4;
   c->dfree(P->dbuf.cand_key); c->dfree(P->dbuf.cand_idx);
-  P->dbuf.cand_key = nullptr; P->dbuf.cand_idx = nullptr;
-  RET(c->dalloc((void**)&P->dbuf.cand_key, (size_t)nseg * P->cand_cap * 4));
-  RET(c->dalloc((void**)&P->dbuf.cand_idx, (size_t)nseg * P->cand_cap * 4));
+  P->dbuf.cand_key = nullptr; P->dbuf.cand_idx = nullptr; P->cand_cap = 0;
+  RET(c->dalloc((void**)&P->dbuf.cand_key, bytes));
+  RET(c->dalloc((void**)&P->dbuf.cand_idx, bytes));
+  P->cand_cap = want_cand_cap(c, P, ncls);
   return 0;
 }
 
-DecodeCfg decode_cfg(const sylph_ctx* c, const Plan* P, int max_out) {
+static DecodeCfg decode_cfg(const sylph_ctx* c, const Plan* P, const HeadOut& o, int max_out) {
   DecodeCfg d;
-  d.num_classes = P->ncls; d.logits_ld = P->logits_ld; d.pre_nms_thresh = c->cfg.pre_nms_thresh;
+  d.num_classes = o.ncls; d.logits_ld = o.logits_ld; d.pre_nms_thresh = c->cfg.pre_nms_thresh;
   d.pre_nms_topk = c->cfg.pre_nms_topk; d.nms_thresh = c->cfg.nms_thresh; d.post_nms_topk = c->cfg.post_nms_topk;
   d.thresh_with_ctr = c->cfg.thresh_with_ctr; d.quality_mode = c->cfg.quality_mode; d.cand_cap = P->cand_cap;
   d.pool_cap = P->pool_cap; d.nlevels = c->cfg.nlevels; d.max_out = max_out;
   return d;
 }
 
-// logits / packed-code buffers of the current batch for N classes (grown on demand; the previous buffers are released)
-int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow) {
-  const size_t rows = (size_t)P->B * P->Ltot;
+// column tile of an N-way class-conditional conv and N padded to it: the rows of its packed codes and biases
+struct CondPad { int bn, Npad; };
+static CondPad cond_pad(int N) {
   const int bn = N >= 128 ? 128 : (N > 32 ? 64 : 32);
-  const int Npad = (N + bn - 1) / bn * bn;
+  return {bn, (N + bn - 1) / bn * bn};
+}
+
+// The kernel of an N-way class-conditional conv, for the uniform head and for every episode of a mixed one alike:
+//   gn_logits          last cls GroupNorm + ReLU + conv in one HBM pass (head_fused.hip): bf16, up to 32 classes
+//   scan               conv + score scan in one pass, the logits never reach HBM (detect.hip: logits_scan_kernel): bf16, many-way
+//   igemm_after_apply  conv_igemm once the last cls GroupNorm, which the head ops left out, has been applied in place
+//   igemm              conv_igemm (the head ops applied every GroupNorm: fp32 storage, FCOS.NORM "none", SYLPH_FUSE_GN_LOGITS=0)
+// allow_scan = false: the kernel that writes the logits a scan left out (sylph_export_head)
+enum class HeadKind { gn_logits, scan, igemm_after_apply, igemm };
+static HeadKind head_kind(const sylph_ctx* c, const Plan* P, int N, bool allow_scan = true) {
+  static const int fuse_scan_on = getenv("SYLPH_FUSE_SCAN") ? atoi(getenv("SYLPH_FUSE_SCAN")) : 1;  // 0: never, 2: for any class count
+  if (c->dt != DT_BF16 || !P->cls_coef) return HeadKind::igemm;
+  if (allow_scan && fuse_scan_on && (N > 32 || fuse_scan_on == 2) && N < 65536) return HeadKind::scan;
+  return N <= 32 ? HeadKind::gn_logits : HeadKind::igemm_after_apply;
+}
+
+// logits / packed-code buffers of the current batch for N classes (grown on demand; the previous buffers are released) -> o->ncls, o->logits_ld
+static int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow, HeadOut* o) {
+  const size_t rows = (size_t)P->B * P->Ltot;
+  const int Npad = cond_pad(N).Npad;
   if (Npad > P->logits_cap_ld) {
     if (P->logits) c->dfree(P->logits);
     P->logits = nullptr; P->logits_cap_ld = 0;
@@ -308,65 +332,12 @@ int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow) {
   // row pitch of the logits: the padded class count, except for <= 8 classes on the fused GroupNorm + class-conditional conv path
   // (gn_logits_kernel stores any multiple of 4 columns): 8 floats per location instead of 32 -- the conv writes and the scan reads
   // a quarter of the bytes (a 5-way episode: 46 MB instead of 183 MB per 64 images)
-  const bool narrow = allow_narrow && N <= 8 && c->dt == DT_BF16 && P->head_built && P->cls_coef;
-  P->logits_ld = narrow ? 8 : Npad;
-  P->ncls = N;
+  o->logits_ld = allow_narrow && N <= 8 && head_kind(c, P, N, false) == HeadKind::gn_logits ? 8 : Npad;
+  o->ncls = N;
   return 0;
 }
 
-// conv_igemm launch of an N-way class-conditional conv over a tile list (128-row tiles up to 32 classes, head_BM-row tiles above);
-// wt: packed codes [Npad][256], bias: Npad floats or nullptr; rows: what the tiles cover (profile FLOPs)
-static int cond_igemm(sylph_ctx* c, Plan* P, const void* wt, const float* bias, int N, size_t rows, const int2* tiles32, int n32,
-                      const int2* tilesBM, int nBM) {
-  const int bn = N >= 128 ? 128 : (N > 32 ? 64 : 32);
-  const int Npad = (N + bn - 1) / bn * bn;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.in = P->cls_feat; a.wt = wt; a.out = P->logits;
-  a.shift = bias;
-  a.zeros = c->zeros; a.tap_dy = 1;
-  a.segs = P->head_segs;
-  int BM = P->head_BM;
-  if (bn == 32) { BM = 128; a.tiles = tiles32; a.n_mtiles = n32; }
-  else { a.tiles = tilesBM; a.n_mtiles = nBM; }
-  a.n_ntiles = Npad / bn;
-  a.Cin = 256; a.Cout = N; a.KH = 1; a.KW = 1; a.stride = 1; a.pad = 0;
-  a.in_ld = 256; a.out_ld = P->logits_ld;
-  const DType dt = c->dt;
-  KCHK(timed_op(c, "conv_igemm_kernel", 2.0 * (double)rows * N * 256.0, c->stream, [=](hipStream_t st) { return launch_conv(dt, true, a, BM, bn, st); }),
-       "cond_cls_logits");
-  return 0;
-}
-
-// the class-conditional conv as its own launch(es): logits[rows][Npad] fp32 from the cls tower output, the packed codes and
-// P->bias_pad (sylph_fcos_head; sylph_export_head after a fused many-way head)
-int run_cond_logits(sylph_ctx* c, Plan* P) {
-  const int N = P->ncls, Npad = P->logits_ld;
-  const int bn = N >= 128 ? 128 : (N > 32 ? 64 : 32);
-  const size_t rows = (size_t)P->B * P->Ltot;
-  const float* bias = P->has_bias ? P->bias_pad : nullptr;
-  if (P->cls_coef) {
-    if (bn == 32) {  // GroupNorm + ReLU + class-conditional conv in one HBM pass (head_fused.hip)
-      const Plan* PP = P;
-      KCHK(timed_op(c, "gn_logits_kernel", 2.0 * (double)rows * N * 256.0, c->stream, [=](hipStream_t st) {
-             return launch_gn_logits(PP->cls_feat, 256, PP->cls_coef, PP->code_w, bias, N, PP->logits, Npad, PP->head_segs, PP->head_tiles32,
-                                     PP->head_mtiles32, st);
-           }), "gn_logits");
-      return 0;
-    }
-    KCHK(P->cls_apply(c->stream), "gn_apply (cls tower, last layer)");
-  }
-  return cond_igemm(c, P, P->code_w, bias, N, rows, P->head_tiles32, P->head_mtiles32, P->head_tiles, P->head_mtiles);
-}
-
-// ---- mixed-episode head (sylph_fcos_head_episodes) ---------------------------------------------------------------------------------
-
-// the kernel sylph_fcos_head runs for an N-way episode: GroupNorm fused into the conv, conv fused with the scan, or plain conv_igemm
-enum class EpKind { gn_logits, scan, igemm };
-static EpKind ep_kind(const sylph_ctx* c, const Plan* P, int N) {
-  if (c->dt == DT_BF16 && P->cls_coef) return N <= 32 ? EpKind::gn_logits : EpKind::scan;
-  return EpKind::igemm;
-}
+// ---- class-conditional conv: one launcher for the uniform head (sylph_fcos_head) and the episodes of a mixed one ------------------------
 
 // Host and device tables of a mixed batch: packed-row layout of the episodes' codes, segment -> code rows, the head's tiles regrouped
 // episode by episode, the decode's segment table with per-image class counts.  Rebuilt only when (n_classes, image_episode) differ
@@ -379,7 +350,7 @@ static int ep_tables(sylph_ctx* c, Plan* P, int E, const int* n_classes, const i
   std::vector<int> row0(E), src_row;
   int src = 0;
   for (int e = 0; e < E; ++e) {
-    const int N = en[e], bn = N >= 128 ? 128 : (N > 32 ? 64 : 32), npad = (N + bn - 1) / bn * bn;
+    const int N = en[e], npad = cond_pad(N).Npad;
     row0[e] = (int)src_row.size();
     for (int r = 0; r < npad; ++r) src_row.push_back(r < N ? src + r : -1);
     src += N;
@@ -399,21 +370,13 @@ static int ep_tables(sylph_ctx* c, Plan* P, int E, const int* n_classes, const i
     }
   }
   if ((int)tiles.size() != P->head_mtiles32 + P->head_mtiles) return fail("internal: episode tile tables");
-  std::vector<int> seg_row0(nseg);
-  std::vector<DecodeSeg> ds;
+  std::vector<int> seg_row0(nseg), img_ncls(B);
   for (int b = 0; b < B; ++b) {
     const int N = en[ei[b]];
-    unsigned lb = 0;
-    for (int l = 0; l < L; ++l) {
-      seg_row0[b * L + l] = row0[ei[b]];
-      DecodeSeg d;
-      d.row0 = b * P->Ltot + P->off[l]; d.nloc = P->hl[l] * P->wl[l]; d.W = P->wl[l];
-      d.stride = c->cfg.strides[l]; d.level = l; d.image = b; d.loc_base = lb;
-      d.ncls = ep_kind(c, P, N) == EpKind::scan ? -N : N;
-      lb += (unsigned)d.nloc;
-      ds.push_back(d);
-    }
+    for (int l = 0; l < L; ++l) seg_row0[b * L + l] = row0[ei[b]];
+    img_ncls[b] = head_kind(c, P, N) == HeadKind::scan ? -N : N;  // negative: the fused scan leaves this image's candidates
   }
+  const std::vector<DecodeSeg> ds = decode_segs(c, P, img_ncls.data());
   HIPCHK(hipStreamSynchronize(c->stream));  // the previous step may still be reading the tables
   if (rows > P->ep_rows_cap) {
     c->dfree(P->ep_code_w); c->dfree(P->ep_bias); c->dfree(P->ep_src_row);
@@ -435,22 +398,93 @@ static int ep_tables(sylph_ctx* c, Plan* P, int E, const int* n_classes, const i
   return 0;
 }
 
-// conv_igemm over the tiles of episode e (the unfused class-conditional conv of sylph_fcos_head on a sub-list of its tile table)
-static int ep_igemm(sylph_ctx* c, Plan* P, int e) {
+// Inputs of one class-conditional conv launch: the N-way codes wt [cond_pad(N).Npad][256], their biases (nullptr: none) and the copy with
+// -inf in the padding rows that the fused scan reads, the tiles to cover as a sub-list of the 128-row table (gn_logits, scan, conv_igemm
+// up to 32 classes) and of the head_BM-row table (conv_igemm above), the rows behind the profile FLOPs
+struct CondEp {
+  const void* wt; const float *bias, *bias_scan; int N;
+  const int2 *t32; int n32; const int2* tBM; int nBM;
+  double rows;
+};
+
+// episode e of the head that o describes, to be run by kernel k; the uniform head is ONE episode over the plan's whole tile tables
+static CondEp cond_ep(const sylph_ctx* c, const Plan* P, const HeadOut& o, int e, HeadKind k) {
+  if (o.src != HeadOut::episodes)
+    return {P->code_w, o.has_bias ? P->bias_pad : nullptr, P->bias_pad + P->bias_pad_cap, o.ncls,
+            P->head_tiles32, P->head_mtiles32, P->head_tiles, P->head_mtiles, (double)P->B * P->Ltot};
   const size_t r0 = (size_t)P->ep_row0[e];
   const int2 a = P->ep_tiles32[e], b = P->ep_tilesBM[e];
-  if (a.y == 0) return 0;  // an episode no image uses
   int n_img = 0;
   for (int v : P->ep_image) n_img += v == e;
-  return cond_igemm(c, P, (const char*)P->ep_code_w + r0 * 256 * c->esz(), P->has_bias ? P->ep_bias + r0 : nullptr, P->ep_n[e],
-                    (size_t)n_img * P->Ltot, P->ep_tiles_dev + a.x, a.y, P->ep_tiles_dev + b.x, b.y);
+  const bool fused = k == HeadKind::gn_logits || k == HeadKind::scan;  // (their FLOPs count whole 128-row tiles)
+  return {(const char*)P->ep_code_w + r0 * 256 * c->esz(), o.has_bias ? P->ep_bias + r0 : nullptr, P->ep_bias + P->ep_rows_cap + r0, P->ep_n[e],
+          P->ep_tiles_dev + a.x, a.y, P->ep_tiles_dev + b.x, b.y, fused ? a.y * 128.0 : (double)n_img * P->Ltot};
 }
 
-// sylph_export_head after a mixed head some of whose episodes took the fused scan: their logits were never written
-int run_ep_stale_logits(sylph_ctx* c, Plan* P) {
-  KCHK(P->cls_apply(c->stream), "gn_apply (cls tower, last layer)");
-  for (size_t e = 0; e < P->ep_n.size(); ++e)
-    if (ep_kind(c, P, P->ep_n[e]) == EpKind::scan) RET(ep_igemm(c, P, (int)e));
+// one launch of kind k into the logits (pitch o.logits_ld) or, scan, into the decode buffers; clear_counts: the first scan of a head
+static int launch_cond(sylph_ctx* c, Plan* P, const HeadOut& o, HeadKind k, const CondEp& v, bool clear_counts) {
+  const Plan* PP = P;
+  const int N = v.N, ld = o.logits_ld;
+  const double flops = 2.0 * v.rows * N * 256.0;
+  if (k == HeadKind::gn_logits) {
+    KCHK(timed_op(c, "gn_logits_kernel", flops, c->stream, [=](hipStream_t st) {
+           return launch_gn_logits(PP->cls_feat, 256, PP->cls_coef, v.wt, v.bias, N, PP->logits, ld, PP->head_segs, v.t32, v.n32, st);
+         }), "gn_logits");
+    return 0;
+  }
+  if (k == HeadKind::scan) {
+    RET(ensure_decode(c, P, o.ncls));
+    DecodeCfg d = decode_cfg(c, P, o, 0);
+    d.num_classes = N;
+    const int nseg = P->B * c->cfg.nlevels;
+    // the counters hold this scan's candidates from here on (set before the launch: a failed one may have counted too): whatever fills
+    // the logits next -- a plain head, the pretrained head, an import -- before a decode has run must not have its decode scan append to
+    // them (sylph_decode_nms clears a dirty table in front of a plain scan)
+    P->cand_dirty = true;
+    KCHK(timed_op(c, "logits_scan_kernel", flops, c->stream, [=](hipStream_t st) {
+           return launch_logits_scan(PP->cls_feat, 256, PP->cls_coef, v.wt, PP->code_wf, v.bias_scan, PP->head_segs, v.t32, v.n32, PP->pred, 8, d,
+                                     PP->dbuf, nseg, clear_counts, st);
+         }), "logits_scan");
+    return 0;
+  }
+  const int bn = cond_pad(N).bn;  // conv_igemm: 128-row tiles up to 32 classes, head_BM-row tiles above
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.in = P->cls_feat; a.wt = v.wt; a.out = P->logits;
+  a.shift = v.bias;
+  a.zeros = c->zeros; a.tap_dy = 1;
+  a.segs = P->head_segs;
+  int BM = P->head_BM;
+  if (bn == 32) { BM = 128; a.tiles = v.t32; a.n_mtiles = v.n32; }
+  else { a.tiles = v.tBM; a.n_mtiles = v.nBM; }
+  a.n_ntiles = cond_pad(N).Npad / bn;
+  a.Cin = 256; a.Cout = N; a.KH = 1; a.KW = 1; a.stride = 1; a.pad = 0;
+  a.in_ld = 256; a.out_ld = ld;
+  const DType dt = c->dt;
+  KCHK(timed_op(c, "conv_igemm_kernel", flops, c->stream, [=](hipStream_t st) { return launch_conv(dt, true, a, BM, bn, st); }), "cond_cls_logits");
+  return 0;
+}
+
+// The class-conditional convs of the head that o describes, one launch per episode with the kernel head_kind picks for its N (the uniform
+// head is the one-episode case) -> *scanned: some episode left candidates instead of logits.  missing_only: only the episodes whose
+// logits a scan left out, with the unfused kernel (sylph_export_head).  The last cls GroupNorm is applied in place, ONCE, and only after
+// every kernel that reads the un-normalised tower output (gn_logits, scan) has been launched: the conv_igemm episodes come last.
+static int run_cond(sylph_ctx* c, Plan* P, const HeadOut& o, bool missing_only, bool* scanned) {
+  const int E = o.src == HeadOut::episodes ? (int)P->ep_n.size() : 1;
+  bool applied = false, any_scan = false;
+  for (int pass = 0; pass < 2; ++pass)
+    for (int e = 0; e < E; ++e) {
+      const int N = o.src == HeadOut::episodes ? P->ep_n[e] : o.ncls;
+      if (missing_only && head_kind(c, P, N) != HeadKind::scan) continue;
+      const HeadKind k = head_kind(c, P, N, !missing_only);
+      if ((k == HeadKind::igemm_after_apply) != (pass == 1)) continue;
+      const CondEp v = cond_ep(c, P, o, e, k);
+      if (v.n32 == 0) continue;  // an episode no image uses
+      if (pass == 1 && !applied) { KCHK(P->cls_apply(c->stream), "gn_apply (cls tower, last layer)"); applied = true; }
+      RET(launch_cond(c, P, o, k, v, !any_scan));
+      any_scan = any_scan || k == HeadKind::scan;
+    }
+  if (scanned) *scanned = any_scan;
   return 0;
 }
 
@@ -458,24 +492,29 @@ int run_ep_stale_logits(sylph_ctx* c, Plan* P) {
 
 extern "C" {
 
+// every head entry: Plan::out = HeadOut() first, the work, then ONE assignment of the whole record as its last action (HeadOut)
 int sylph_import_head(sylph_ctx* c, int N, int level, const float* logits, const float* reg, const float* ctr, const float* iou) {
   Plan* P = c->cur;
   if (!P) return fail("no current batch");
   if (N <= 0) return fail("class_code is empty");
   if (level < 0 || level >= c->cfg.nlevels) return fail("bad level");
   OwnerScope own(c, P);
+  const HeadOut prev = P->out;
+  P->out = HeadOut();
   BUILD(build_head(c, P), P);
-  P->ep_on = false;
-  if (!P->logits || N != P->ncls) RET(ensure_logits(c, P, N));
-  P->scan_fused = false; P->logits_stale = false;
+  HeadOut o;
+  o.src = HeadOut::imported;
+  if (P->logits && N == prev.ncls) { o.ncls = N; o.logits_ld = prev.logits_ld; }  // level by level into the buffer as the last head laid it out
+  else RET(ensure_logits(c, P, N, false, &o));
   const int hw = P->hl[level] * P->wl[level];
   for (int b = 0; b < P->B; ++b) {
     const int row0 = b * P->Ltot + P->off[level];
-    if (logits) KCHK(launch_import_nchw(DT_F32, logits + (size_t)b * N * hw, P->logits, N, hw, row0, P->logits_ld, c->stream), "import logits");
+    if (logits) KCHK(launch_import_nchw(DT_F32, logits + (size_t)b * N * hw, P->logits, N, hw, row0, o.logits_ld, c->stream), "import logits");
     if (reg) KCHK(launch_import_nchw(DT_F32, reg + (size_t)b * 4 * hw, P->pred, 4, hw, row0, 8, c->stream), "import reg");
     if (ctr) KCHK(launch_import_nchw(DT_F32, ctr + (size_t)b * hw, P->pred + 4, 1, hw, row0, 8, c->stream), "import ctr");
     if (iou) KCHK(launch_import_nchw(DT_F32, iou + (size_t)b * hw, P->pred + 5, 1, hw, row0, 8, c->stream), "import iou");
   }
+  P->out = o;
   return 0;
 }
 
@@ -485,12 +524,13 @@ int sylph_fcos_head(sylph_ctx* c, const float* cls_conv, const float* cls_bias, 
   if (N <= 0) return fail("class_code is empty");
   if (!cls_conv) return fail("cls_conv is NULL");
   OwnerScope own(c, P);
+  P->out = HeadOut();
   BUILD(build_head(c, P), P);
-  P->ep_on = false;
-  const size_t rows = (size_t)P->B * P->Ltot;
-  const int bn = N >= 128 ? 128 : (N > 32 ? 64 : 32);
-  const int Npad = (N + bn - 1) / bn * bn;
-  RET(ensure_logits(c, P, N, true));
+  HeadOut o;
+  o.src = HeadOut::cond;
+  o.has_bias = c->cfg.cond_use_bias && cls_bias;
+  RET(ensure_logits(c, P, N, true, &o));
+  const int Npad = cond_pad(N).Npad;
   // the biases, zero-padded to the packed code rows (device copy: the caller's buffer need not outlive this call)
   if (Npad > P->bias_pad_cap) {
     if (P->bias_pad) c->dfree(P->bias_pad);
@@ -498,35 +538,18 @@ int sylph_fcos_head(sylph_ctx* c, const float* cls_conv, const float* cls_bias, 
     RET(c->dalloc((void**)&P->bias_pad, (size_t)2 * Npad * sizeof(float)));
     P->bias_pad_cap = Npad;
   }
-  P->has_bias = c->cfg.cond_use_bias && cls_bias;
   // one launch: packed codes + zero-padded biases + the -inf padded copy the fused scan reads
   // (in FRONT of the towers: it depends on the caller's codes only, and at small batches the main stream waits for the bbox tower on the
   // side stream at the end of the head ops anyway -- behind them it was 5 us of the step's serial tail)
-  KCHK(launch_pack_codes(c->dt, cls_conv, N, 256, Npad, P->code_w, P->has_bias ? cls_bias : nullptr, P->bias_pad, P->bias_pad + P->bias_pad_cap, c->stream),
+  KCHK(launch_pack_codes(c->dt, cls_conv, N, 256, Npad, P->code_w, o.has_bias ? cls_bias : nullptr, P->bias_pad, P->bias_pad + P->bias_pad_cap, c->stream),
        "pack_codes");
   RET(run_ops(c, P->head_ops, "fcos_head"));
-  P->scan_fused = false; P->logits_stale = false;
-  // Many-way episodes (bf16): conv + scan in one pass, the logits never reach HBM (detect.hip: logits_scan_kernel)
-  static const int fuse_scan_on = getenv("SYLPH_FUSE_SCAN") ? atoi(getenv("SYLPH_FUSE_SCAN")) : 1;
-  if (fuse_scan_on && c->dt == DT_BF16 && P->cls_coef && (bn != 32 || fuse_scan_on == 2) && N < 65536) {
-    BUILD(build_decode(c, P), P);
-    RET(ensure_cand_cap(c, P));
-    const DecodeCfg d = decode_cfg(c, P, 0);
-    float* bias_scan = P->bias_pad + P->bias_pad_cap;  // written by the pack_codes launch above
-    const Plan* PP = P;
-    const int nseg = P->B * c->cfg.nlevels;
-    // the counters hold this scan's candidates from here on (set before the launch: a failed one may have counted too): whatever fills
-    // the logits next -- a plain head, the pretrained head, an import -- before a decode has run must not have its decode scan append to
-    // them (sylph_decode_nms clears a dirty table in front of a plain scan)
-    P->cand_dirty = true;
-    KCHK(timed_op(c, "logits_scan_kernel", 2.0 * (double)rows * N * 256.0, c->stream, [=](hipStream_t st) {
-           return launch_logits_scan(PP->cls_feat, 256, PP->cls_coef, PP->code_w, PP->code_wf, bias_scan, PP->head_segs, PP->head_tiles32,
-                                     PP->head_mtiles32, PP->pred, 8, d, PP->dbuf, nseg, true, st);
-         }), "logits_scan");
-    P->scan_fused = true; P->logits_stale = true;
-    return 0;
-  }
-  return run_cond_logits(c, P);
+  bool scanned = false;
+  RET(run_cond(c, P, o, false, &scanned));
+  o.logits_missing = scanned;
+  o.cand = scanned ? HeadOut::cand_all : HeadOut::cand_none;
+  P->out = o;
+  return 0;
 }
 
 int sylph_fcos_head_episodes(sylph_ctx* c, int E, const float* cls_conv, const float* cls_bias, const int* n_classes, const int* image_episode) {
@@ -544,67 +567,33 @@ int sylph_fcos_head_episodes(sylph_ctx* c, int E, const float* cls_conv, const f
     if (image_episode[b] < 0 || image_episode[b] >= E)
       return fail("image_episode[" + std::to_string(b) + "] = " + std::to_string(image_episode[b]) + " is not in [0, " + std::to_string(E) + ")");
   OwnerScope own(c, P);
+  P->out = HeadOut();
   BUILD(build_head(c, P), P);
-  P->ep_on = false;
-  if (ep_kind(c, P, maxN) == EpKind::scan && maxN >= 65536) return fail("a mixed batch takes episodes of fewer than 65536 classes");
-  RET(ensure_logits(c, P, maxN, true));  // row pitch, candidate capacity and export width: those of the widest episode
+  HeadOut o;
+  o.src = HeadOut::episodes;
+  o.has_bias = c->cfg.cond_use_bias && cls_bias;
+  RET(ensure_logits(c, P, maxN, true, &o));  // row pitch, candidate capacity and export width: those of the widest episode
   RET(ep_tables(c, P, E, n_classes, image_episode));
-  P->has_bias = c->cfg.cond_use_bias && cls_bias;
   // one launch packs every episode's codes and biases (in front of the towers, as in sylph_fcos_head)
-  KCHK(launch_pack_codes_episodes(c->dt, cls_conv, P->ep_src_row, P->ep_rows, 256, P->ep_code_w, P->has_bias ? cls_bias : nullptr, P->ep_bias,
+  KCHK(launch_pack_codes_episodes(c->dt, cls_conv, P->ep_src_row, P->ep_rows, 256, P->ep_code_w, o.has_bias ? cls_bias : nullptr, P->ep_bias,
                                   P->ep_bias + P->ep_rows_cap, c->stream), "pack_codes_episodes");
   RET(run_ops(c, P->head_ops, "fcos_head"));
-  P->scan_fused = false; P->logits_stale = false; P->ep_any_fused = false;
-  P->ep_on = true;
-  const float* bias = P->has_bias ? P->ep_bias : nullptr;
-  const Plan* PP = P;
-  if (ep_kind(c, P, maxN) == EpKind::gn_logits) {
-    // bf16, every episode <= 32 classes: ONE launch for the whole batch, whatever E is (head_fused.hip)
+  bool scanned = false;
+  if (head_kind(c, P, maxN) == HeadKind::gn_logits) {
+    // every episode takes gn_logits: ONE launch for the whole batch, whatever E is (head_fused.hip)
+    const Plan* PP = P;
+    const float* bias = o.has_bias ? P->ep_bias : nullptr;
+    const int ld = o.logits_ld;
     KCHK(timed_op(c, "gn_logits_episodes_kernel", 2.0 * (double)P->B * P->Ltot * maxN * 256.0, c->stream, [=](hipStream_t st) {
-           return launch_gn_logits_episodes(PP->cls_feat, 256, PP->cls_coef, PP->ep_code_w, bias, PP->ep_seg_row0, PP->logits, PP->logits_ld,
+           return launch_gn_logits_episodes(PP->cls_feat, 256, PP->cls_coef, PP->ep_code_w, bias, PP->ep_seg_row0, PP->logits, ld,
                                             PP->head_segs, PP->head_tiles32, PP->head_mtiles32, st);
          }), "gn_logits_episodes");
-    return 0;
+  } else {
+    RET(run_cond(c, P, o, false, &scanned));
   }
-  // everything else: per episode, the kernel sylph_fcos_head picks for that N and dtype, over the episode's tiles
-  const int nseg = P->B * c->cfg.nlevels;
-  for (int e = 0; e < E; ++e) {
-    const int N = n_classes[e];
-    const int2 t32 = P->ep_tiles32[e];
-    if (t32.y == 0) continue;
-    const size_t r0 = (size_t)P->ep_row0[e];
-    const void* wt = (const char*)P->ep_code_w + r0 * 256 * c->esz();
-    const double fl = 2.0 * (double)(t32.y) * 128.0 * N * 256.0;
-    const int2* tl = P->ep_tiles_dev + t32.x;
-    switch (ep_kind(c, P, N)) {
-      case EpKind::gn_logits: {
-        const float* be = bias ? bias + r0 : nullptr;
-        KCHK(timed_op(c, "gn_logits_kernel", fl, c->stream, [=](hipStream_t st) {
-               return launch_gn_logits(PP->cls_feat, 256, PP->cls_coef, wt, be, N, PP->logits, PP->logits_ld, PP->head_segs, tl, t32.y, st);
-             }), "gn_logits");
-        break;
-      }
-      case EpKind::scan: {
-        if (!P->ep_any_fused) {  // first fused episode of the call: from here on the counters hold scan candidates (see sylph_fcos_head)
-          BUILD(build_decode(c, P), P);
-          RET(ensure_cand_cap(c, P));
-          P->cand_dirty = true; P->ep_any_fused = true; P->logits_stale = true;
-          HIPCHK(hipMemsetAsync(P->dbuf.cand_count, 0, (size_t)nseg * 4, c->stream));
-        }
-        DecodeCfg d = decode_cfg(c, P, 0);
-        d.num_classes = N;
-        const float* bias_scan = P->ep_bias + P->ep_rows_cap + r0;
-        KCHK(timed_op(c, "logits_scan_kernel", fl, c->stream, [=](hipStream_t st) {
-               return launch_logits_scan(PP->cls_feat, 256, PP->cls_coef, wt, PP->code_wf, bias_scan, PP->head_segs, tl, t32.y, PP->pred, 8, d,
-                                         PP->dbuf, nseg, false, st);
-             }), "logits_scan");
-        break;
-      }
-      case EpKind::igemm:
-        RET(ep_igemm(c, P, e));
-        break;
-    }
-  }
+  o.logits_missing = scanned;
+  o.cand = scanned ? HeadOut::cand_scanned : HeadOut::cand_none;
+  P->out = o;
   return 0;
 }
 
@@ -613,41 +602,45 @@ int sylph_fcos_head_pretrained(sylph_ctx* c, int* num_classes) {
   if (!P) return fail("no current batch");
   if (!c->has_cls_logits) return fail("the checkpoint has no proposal_generator.fcos_head.cls_logits (1x1 or 3x3, 256 input channels)");
   OwnerScope own(c, P);
+  P->out = HeadOut();
   BUILD(build_head(c, P), P);
   const int N = c->cls_logits.Cout;
-  P->ep_on = false;
-  RET(ensure_logits(c, P, N));
-  if (c->cls_logits.Cout_pad != P->logits_ld) return fail("internal: cls_logits padding");
+  HeadOut o;
+  o.src = HeadOut::pretrained;
+  RET(ensure_logits(c, P, N, false, &o));
+  if (c->cls_logits.Cout_pad != o.logits_ld) return fail("internal: cls_logits padding");
   if (P->cls_logits_dst != P->logits) {  // (re)build the conv launch for this plan's buffers
     P->cls_logits_ops.clear();
-    ConvOpts o; o.pad = c->cls_logits.KH / 2; o.segs_per_image = c->cfg.nlevels; o.out_f32 = true;
-    RET(add_conv(c, P->cls_logits_ops, c->cls_logits, P->cls_feat, 256, P->logits, P->logits_ld, pyramid_segs(c, P), o));
+    ConvOpts op; op.pad = c->cls_logits.KH / 2; op.segs_per_image = c->cfg.nlevels; op.out_f32 = true;
+    RET(add_conv(c, P->cls_logits_ops, c->cls_logits, P->cls_feat, 256, P->logits, o.logits_ld, pyramid_segs(c, P), op));
     P->cls_logits_dst = P->logits;
   }
-  P->scan_fused = false; P->logits_stale = false;
   RET(run_ops(c, P->head_ops, "fcos_head"));
   if (P->cls_coef) KCHK(P->cls_apply(c->stream), "gn_apply (cls tower, last layer)");
   RET(run_ops(c, P->cls_logits_ops, "cls_logits"));
   if (num_classes) *num_classes = N;
+  P->out = o;
   return 0;
 }
 
 int sylph_export_head(sylph_ctx* c, int level, float* logits, float* reg, float* ctr, float* iou) {
   Plan* P = c->cur;
-  if (!P || !P->head_built || !P->logits) return fail("sylph_fcos_head must be called first");
+  if (!P || P->out.src == HeadOut::none) return fail("sylph_fcos_head must be called first");
   if (level < 0 || level >= c->cfg.nlevels) return fail("bad level");
-  if (logits && P->logits_stale) {  // fused many-way head: the logits were never written
+  if (logits && P->out.logits_missing) {  // a fused scan left columns out: the unfused conv writes them now, and the record says so
     OwnerScope own(c, P);
-    if (P->ep_on) RET(run_ep_stale_logits(c, P));
-    else RET(run_cond_logits(c, P));
-    P->logits_stale = false;
+    HeadOut o = P->out;
+    P->out = HeadOut();
+    RET(run_cond(c, P, o, true, nullptr));
+    o.logits_missing = false;
+    P->out = o;
   }
+  const HeadOut& o = P->out;
   const int hw = P->hl[level] * P->wl[level];
   for (int b = 0; b < P->B; ++b) {
     const int row0 = b * P->Ltot + P->off[level];
     if (logits)
-      KCHK(launch_export_nchw_f32(P->logits, logits + (size_t)b * P->ncls * hw, P->ncls, hw, row0, P->logits_ld, 0,
-                                  c->stream), "export logits");
+      KCHK(launch_export_nchw_f32(P->logits, logits + (size_t)b * o.ncls * hw, o.ncls, hw, row0, o.logits_ld, 0, c->stream), "export logits");
     if (reg) KCHK(launch_export_nchw_f32(P->pred, reg + (size_t)b * 4 * hw, 4, hw, row0, 8, 0, c->stream), "export reg");
     if (ctr) KCHK(launch_export_nchw_f32(P->pred, ctr + (size_t)b * hw, 1, hw, row0, 8, 4, c->stream), "export ctr");
     if (iou) KCHK(launch_export_nchw_f32(P->pred, iou + (size_t)b * hw, 1, hw, row0, 8, 5, c->stream), "export iou");
@@ -658,11 +651,11 @@ int sylph_export_head(sylph_ctx* c, int level, float* logits, float* reg, float*
 int sylph_decode_nms(sylph_ctx* c, const int* oh, const int* ow, int max_out, float* boxes, float* scores,
                      int* classes, int* levels, float* locations, int* cand, int* counts, int* status) {
   Plan* P = c->cur;
-  if (!P || !P->head_built || !P->logits) return fail("sylph_fcos_head must be called first");
+  if (!P || P->out.src == HeadOut::none) return fail("sylph_fcos_head must be called first");
   if (max_out <= 0) return fail("max_out must be positive");
+  const HeadOut o = P->out;
   OwnerScope own(c, P);
-  BUILD(build_decode(c, P), P);
-  RET(ensure_cand_cap(c, P));
+  RET(ensure_decode(c, P, o.ncls));
   // postprocess scales of this call; the H2D copy is skipped when they equal what the device table already holds (every step of a
   // steady query stream).  Otherwise img_out_host is rewritten: wait only for the previous H2D copy of it, not for the stream
   std::vector<ImageOut> io((size_t)P->B);
@@ -682,20 +675,15 @@ int sylph_decode_nms(sylph_ctx* c, const int* oh, const int* ow, int max_out, fl
     HIPCHK(hipEventRecord(P->img_out_ev, c->stream));
     P->img_out_last = io;
   }
-  const DecodeCfg d = decode_cfg(c, P, max_out);
+  const DecodeCfg d = decode_cfg(c, P, o, max_out);
   const int L = c->cfg.nlevels;
-  // the candidate counters are left zero by every decode that ran its own scan; after a fused many-way scan (whose launcher clears them
-  // itself and whose candidates stay valid for a repeated decode) -- decoded or not: sylph_fcos_head marks the table dirty -- the plain
-  // scan starts from a cleared table again.  A steady stream of fused or of plain steps never clears here (no extra launch)
-  // A mixed-episode head whose many-way episodes took the fused scan (ep_partial) is both at once, per image: the scan below skips the
-  // images whose candidates are there and nms_kernel keeps their counters; the table stays dirty for whatever plain head comes next.
-  const bool ep_partial = P->ep_on && P->ep_any_fused;
-  if (!P->scan_fused && !ep_partial && P->cand_dirty) HIPCHK(hipMemsetAsync(P->dbuf.cand_count, 0, (size_t)P->B * L * 4, c->stream));
-  P->cand_dirty = P->scan_fused || ep_partial;
+  // the three states of HeadOut::cand: clear stale counters in front of a scan of every image, or keep the candidates that are there
+  if (o.cand == HeadOut::cand_none && P->cand_dirty) HIPCHK(hipMemsetAsync(P->dbuf.cand_count, 0, (size_t)P->B * L * 4, c->stream));
+  P->cand_dirty = o.cand != HeadOut::cand_none;
   int nwb = (L * c->cfg.pre_nms_topk + 63) / 64;
   if (nwb > P->pool_cap / 64) nwb = P->pool_cap / 64;
-  KCHK(launch_decode(d, P->ep_on ? P->dsegs_ep : P->dsegs, P->B * L, P->hl[0] * P->wl[0], P->B, nwb, P->logits, P->pred, 8, P->dbuf,
-                     P->img_out_dev, boxes, scores, classes, levels, locations, cand, counts, status, P->scan_fused, c->stream),
+  KCHK(launch_decode(d, o.src == HeadOut::episodes ? P->dsegs_ep : P->dsegs, P->B * L, P->hl[0] * P->wl[0], P->B, nwb, P->logits, P->pred, 8,
+                     P->dbuf, P->img_out_dev, boxes, scores, classes, levels, locations, cand, counts, status, o.cand == HeadOut::cand_all, c->stream),
        "decode_nms");
   return 0;
 }

@@ -207,6 +207,25 @@ struct SupportPass {
   int2* seg_dev = nullptr;       // [S] capacity: {first row, rows} per segment
 };
 
+// What the last head entry left on a plan: all that sylph_decode_nms and sylph_export_head know about it.  Every head entry (and the export,
+// where it writes missing logits) sets Plan::out to HeadOut() first and commits the whole record in ONE assignment as its last action: a
+// failure in between leaves src none, answered with "sylph_fcos_head must be called first".  Nothing assigns single fields of Plan::out.
+struct HeadOut {
+  enum Src { none, cond, episodes, pretrained, imported } src = none;  // sylph_fcos_head | _episodes | _pretrained | sylph_import_head
+  // Whose candidates logits_scan_kernel has already left in the decode buffers:
+  //   cand_none     nobody's: the decode scans every image, after clearing the counters if Plan::cand_dirty says that an earlier fused
+  //                 scan's candidates are still counted (a decode that ran its own scan leaves them zero: nms_kernel)
+  //   cand_all      every image's (many-way sylph_fcos_head; the scan launch clears the counters itself): the decode skips its scan
+  //   cand_scanned  those of the images whose episode takes the fused scan (mixed head; DecodeSeg::ncls < 0 in Plan::dsegs_ep):
+  //                 decode_scan_kernel skips these images
+  // In the last two nms_kernel keeps the counters, so a repeated decode finds the candidates again and the counters stay dirty.  A steady
+  // stream of steps of one kind never clears in the decode (no extra launch).
+  enum Cand { cand_none, cand_all, cand_scanned } cand = cand_none;
+  bool has_bias = false;        // the class-conditional conv adds biases
+  bool logits_missing = false;  // the logits columns of the scanned images were never written: sylph_export_head runs the unfused conv first
+  int ncls = 0, logits_ld = 0;  // classes (of the widest episode) and row pitch of Plan::logits
+};
+
 struct Plan {
   std::vector<void*> allocs;  // device buffers owned by this plan (freed on eviction)
   int64_t bytes = 0;
@@ -249,8 +268,9 @@ struct Plan {
   const float2* cls_coef = nullptr;
   std::function<int(hipStream_t)> cls_apply;
   float* pred = nullptr;    // [rows][8]
-  float* logits = nullptr;  // [rows][logits_ld]
-  int logits_ld = 0, logits_cap_ld = 0, ncls = 0;
+  float* logits = nullptr;  // [rows][out.logits_ld], capacity [rows][logits_cap_ld]
+  int logits_cap_ld = 0;
+  HeadOut out;              // what the last head entry left in logits / pred / the decode buffers
   void* code_w = nullptr;   // packed class codes [Npad][256]
   void* code_wf = nullptr;  // the same in MFMA fragment order (logits_scan_kernel), same capacity
   int code_w_cap = 0;
@@ -263,6 +283,7 @@ struct Plan {
   // decode
   DecodeSeg* dsegs = nullptr;
   DecodeBuffers dbuf;
+  bool cand_dirty = false;  // the candidate counters of dbuf are not zero: a fused scan filled them (a fact about the buffers: it survives heads)
   bool decode_built = false;
   std::vector<OpFn> cls_logits_ops;  // the checkpoint's cls_logits conv on this plan's cls tower output (sylph_fcos_head_pretrained)
   const float* cls_logits_dst = nullptr;  // the logits buffer those ops were built for
@@ -270,14 +291,8 @@ struct Plan {
   bool stem_takes_raw = false;  // this plan's first backbone op is the fused stem + pool kernel (bf16): it can read raw images
   bool raw_input = false;     // the batch came in through sylph_preprocess and its normalisation is fused into the stem kernel
                               // (launch_stem_pool_raw reads the caller's images through img_desc_dev): x0 has NOT been written
-  bool cand_dirty = false;    // the last decode left the candidate counters non-zero (fused scan: see sylph_decode_nms)
-  bool scan_fused = false;    // the candidate buffers were filled by logits_scan_kernel (many-way head): decode skips its scan
-  bool logits_stale = false;  // ... and the logits buffer was not written: sylph_export_head runs the unfused conv first
-  // Mixed-episode head (sylph_fcos_head_episodes): image i was run with the codes of episode ep_image[i].  ep_on says that the head outputs
-  // of the plan are such a head's; every other head entry (sylph_fcos_head, _pretrained, sylph_import_head) clears it, and with it every
-  // per-image fact below stops being read: the decode goes back to the plan's own segment table (DecodeSeg::ncls 0) and to scan_fused.
-  bool ep_on = false;
-  bool ep_any_fused = false;          // some episode has more than 32 classes (bf16): logits_scan_kernel left its images' candidates
+  // Mixed-episode head (sylph_fcos_head_episodes): image i was run with the codes of episode ep_image[i].  The tables below are read only
+  // while out.src says that the plan's head outputs are such a head's.
   std::vector<int> ep_n, ep_image;    // classes per episode, episode per image: what the device tables below were built for
   std::vector<int> ep_row0;           // per episode: its first row in the packed code / bias tables (rows padded per episode as in sylph_fcos_head)
   std::vector<int2> ep_tiles32, ep_tilesBM;  // per episode: {first, count} of its tiles in ep_tiles_dev (128-row tiles | head_BM-row tiles)
@@ -291,7 +306,6 @@ struct Plan {
   float* bias_pad = nullptr;  // fp32 class biases of the last sylph_fcos_head: [0, cap) zero-padded to the packed code rows; [cap, 2 cap) the
                               // same with -inf from class N on (logits_scan_kernel: padded classes never pass the threshold)
   int bias_pad_cap = 0;
-  bool has_bias = false;
   ImageOut* img_out_dev = nullptr;
   ImageOut* img_out_host = nullptr;
   std::vector<ImageOut> img_out_last;  // what img_out_dev holds (the H2D copy is skipped when a call's scales equal it)
@@ -406,12 +420,6 @@ std::vector<SegDesc> pyramid_segs(sylph_ctx* c, Plan* P);
 int add_gn(sylph_ctx* c, Plan* P, std::vector<OpFn>& ops, void* x, const RowSeg* segs_dev, int nseg, int max_rows, const GNLayer& G, int relu);
 int ensure_gn_ws(sylph_ctx* c, Plan* P, int nseg, int max_rows);
 int build_head(sylph_ctx* c, Plan* P);
-int want_cand_cap(const sylph_ctx* c, const Plan* P);
-int build_decode(sylph_ctx* c, Plan* P);
-int ensure_cand_cap(sylph_ctx* c, Plan* P);
-DecodeCfg decode_cfg(const sylph_ctx* c, const Plan* P, int max_out);
-int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow = false);
-int run_cond_logits(sylph_ctx* c, Plan* P);
 // api_codegen.hip
 int build_support(sylph_ctx* c, Plan* P, SupportPass* Q);
 int build_support_roienc(sylph_ctx* c, Plan* P, SupportPass* Q);

@@ -9,6 +9,10 @@ Codes: `synthetic_codes(n, seed, scale)` as listed in CODES; with the oracle (fc
 every one of them yields detections on every image, the 20- and 32-way sets detect classes >= 8 (beyond the 8-float narrow logits pitch)
 and the two 5-way sets differ.  The tests assert those conditions on what the uniform runs return, so none of them can pass vacuously;
 a decode that reports a status bit raises in `Engine.decode`."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -16,6 +20,7 @@ import torch
 from test_hip_parity import _cfg, _roienc_cfg
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 FULL, SMALL = (800, 1344), (128, 160)
 FIELDS = ("pred_boxes", "scores", "pred_classes", "fpn_levels", "locations", "cand_index")
@@ -212,6 +217,38 @@ def test_fallback_many_way_next_to_few_way_bf16():
     for i in range(4):
         _same(again[i], first[i], f"repeated decode: image {i}")
     eng.close()
+
+
+_FUSE_SCAN_OFF_CHILD = r"""
+import sys
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[2])
+import test_mixed_episodes_gpu as T
+codes, ie = [T._code("n60"), T._code("n5")], [0, 1, 1, 0]
+eng = T._new("bf16", T._pyramid(4, T.SMALL), T.SMALL)
+T._check_mixed(eng, codes, ie, what="SYLPH_FUSE_SCAN=0")  # (every image has detections: asserted on the uniform runs)
+few = T._kernels(eng, lambda: eng.head(codes[1]["cls_conv"], codes[1]["cls_bias"]))
+uni = T._kernels(eng, lambda: eng.head(codes[0]["cls_conv"], codes[0]["cls_bias"]))
+mix = T._kernels(eng, lambda: eng.head_episodes(T._pairs(codes), ie))
+print("uniform 5-way head:", few, "\nuniform 60-way head:", uni, "\nmixed head:", mix)
+assert "logits_scan_kernel" not in uni and "logits_scan_kernel" not in mix
+tower = few.get("conv_igemm_kernel", 0)  # the 5-way head's class-conditional conv is gn_logits_kernel: these are its tower layers
+assert few.get("gn_logits_kernel") == 1 and "logits_scan_kernel" not in few
+assert uni.get("conv_igemm_kernel") == tower + 1 and "gn_logits_kernel" not in uni
+assert mix.get("gn_logits_kernel") == 1 and mix.get("conv_igemm_kernel") == tower + 1
+eng.close()
+"""
+
+
+def test_mixed_head_follows_fuse_scan_switch():
+    """SYLPH_FUSE_SCAN=0 (one fresh child process): the 60-way episode of a mixed head runs what the uniform 60-way head runs then, the
+    GroupNorm apply + conv_igemm, behind the 5-way episode's gn_logits_kernel (which reads the tower output before that in-place apply);
+    no fused scan in either head, and the mixed step still equals the uniform runs bit for bit, exported logits included.  At this size
+    the tower layers run conv_igemm_kernel too (8 launches), so "the class-conditional conv_igemm ran once" is counted against the
+    uniform 5-way head, whose class-conditional conv is gn_logits_kernel.  The smallest batch with a few-way and a many-way episode
+    on more than one image each."""
+    r = subprocess.run([sys.executable, "-c", _FUSE_SCAN_OFF_CHILD, os.path.join(ROOT, "sylph-few-shot-detection_amd"), os.path.join(ROOT, "tests")],
+                       env=dict(os.environ, SYLPH_FUSE_SCAN="0"), cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 
 def test_fallback_norm_none_bf16():
