@@ -270,6 +270,10 @@ int sylph_stem_maxpool(sylph_ctx* ctx, const float* x_nchw_dev, int B, int H, in
  * its own buffer (same kernels and launches, other destination) instead of the two ping-pong buffers.
  * sylph_export_stage: output of ResNet stage `stage` (2..5 = res2..res5) of the last sylph_backbone_fpn as
  * (B, C << (stage - 2), h, w) fp32 NCHW, C = 256 (64 for the BasicBlock depths 18 / 34) (detectron2 ResNet.forward outputs; call site meta_one_stage_detector.py:181,273).
+ * res2 of a bf16 R-50 / R-101 step with STRIDE_IN_1X1 exists only at the even rows and columns res3 reads (SYLPH_BK_STRIDED_TAIL, default
+ * on): for stage 2 the tap then runs the dense launch of res2's last block from that block's input, which the step leaves intact, into a
+ * buffer of its own (allocated on the first such call) and exports that -- the same values, the dense shape.  It changes nothing a later
+ * tap, sylph_fcos_head or sylph_decode_nms reads and may be called any number of times, in any order with the other taps.
  * sylph_export_tower: conv output of layer `layer` of the cls (tower 0) / bbox (tower 1) tower on FPN level `level`
  * (sylph/modeling/meta_fcos/fcos.py:72-122,625-628) as (B,256,h_l,w_l) fp32 NCHW -- the value stored BEFORE GroupNorm when
  * the layer's GroupNorm is applied by its consumer -- and (coef_dev != NULL) that GroupNorm's per-(image, channel)
@@ -313,6 +317,12 @@ int sylph_export_support(sylph_ctx* ctx, int stage, int index, float* out_dev);
 int sylph_bottleneck(sylph_ctx* ctx, const float* x_nchw_dev, int B, int Cin, int H, int W, int stride, int mid, int cout,
                      const float* const* w_host, const float* const* scale_host, const float* const* shift_host,
                      float* y_nchw_dev);
+/* The same identity block (w_host[3] NULL) through the stride-2-output launch sylph_backbone_fpn uses for the last block of res2:
+ * y (B,cout,H/2,W/2) holds the block's output at the even rows and columns, bit for bit what sylph_bottleneck gives there.  Only the
+ * fused bf16 kernel's own shape (Cin = cout = 256, mid = 64) with even H and W; anything else is an error. */
+int sylph_bottleneck_even(sylph_ctx* ctx, const float* x_nchw_dev, int B, int Cin, int H, int W, int mid, int cout,
+                          const float* const* w_host, const float* const* scale_host, const float* const* shift_host,
+                          float* y_nchw_dev);
 
 /* Kernel parity entry: one FPN lateral as sylph_backbone_fpn launches it (detectron2 FPN.forward: lateral 1x1 conv + bias, plus
  * the nearest-2x upsampled level above, fused as a residual; call site meta_one_stage_detector.py:181,273).  x (B,C,H,W) fp32 NCHW

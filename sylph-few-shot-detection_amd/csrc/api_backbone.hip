@@ -47,12 +47,20 @@ int ensure_pyramid(sylph_ctx* c, Plan* P) {
 }
 
 // Patch list of the bottleneck kernels (bottleneck.hip, conv_rw3.hip): ph x pw patches of B images of H x W positions
-static int upload_bk_tiles(sylph_ctx* c, int B, int H, int W, int ph, int pw, BottleneckArgs* ba) {
+// even_rp != 0: the stride-2-output form (BkTile): ph x pw tiles of the H/2 x W/2 output map, t1 row pitch even_rp
+static int upload_bk_tiles(sylph_ctx* c, int B, int H, int W, int ph, int pw, BottleneckArgs* ba, int even_rp = 0) {
   std::vector<BkTile> bt;
-  for (int b = 0; b < B; ++b)
+  for (int b = 0; b < B; ++b) {
+    if (even_rp) {
+      for (int yy = 0; yy < H / 2; yy += ph)
+        for (int xx = 0; xx < W / 2; xx += pw)
+          bt.push_back(BkTile{b * H * W, H, W, (yy << 16) | xx, ph | (even_rp << 16), pw, (65536u + pw - 1) / pw, (65536u + 2 * pw) / (2 * pw + 1)});
+      continue;
+    }
     for (int yy = 0; yy < H; yy += ph)
       for (int xx = 0; xx < W; xx += pw)
         bt.push_back(BkTile{b * H * W, H, W, (yy << 16) | xx, ph, pw, (65536u + pw - 1) / pw, (65536u + pw + 2 - 1) / (pw + 2)});
+  }
   void* btd = nullptr;
   RET(upload(c, &btd, bt.data(), bt.size() * sizeof(BkTile)));
   ba->bk = (const BkTile*)btd;
@@ -64,9 +72,26 @@ static int upload_bk_tiles(sylph_ctx* c, int B, int H, int W, int ph, int pw, Bo
 // appended to `ops`: X [B][Hin*Win][Cin] -> Y [B][Ho*Wo][cout].  t1 / t2 / sc are scratch activations of the stage.
 // Shared by build_backbone and the single-block parity entry sylph_bottleneck, so both run the same kernels.
 
+static int fuse_bottleneck_knob() {
+  static const int v = getenv("SYLPH_FUSE_BOTTLENECK") ? atoi(getenv("SYLPH_FUSE_BOTTLENECK")) : 1;
+  return v;
+}
+
+// res2 identity blocks (C 256, mid 64, stride 1, no projection), bf16: the block add_bottleneck builds as ONE fused kernel
+bool bottleneck_takes_fuse_id(const sylph_ctx* c, const sylph_ctx::Block& blk, int B, int Cin, int Hin, int Win, int stride, int mid, int cout) {
+  return fuse_bottleneck_knob() && blk.c2.groups == 1 && c->dt == DT_BF16 && !blk.has_sc && stride == 1 && mid == 64 && Cin == 256 && cout == 256 &&
+         blk.c1.Cout_pad == 64 && blk.c2.Cout_pad == 64 && blk.c3.Cout_pad == 256 &&
+         (size_t)Hin * Win * 512 < ((size_t)1 << 32) && (size_t)B * Hin * Win < ((size_t)1 << 31);  // 32-bit byte offsets inside ONE image (64-bit image base)
+}
+
 int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win,
-                          int stride, int mid, int cout, void* Y, const BkScratch& scr) {
+                          int stride, int mid, int cout, void* Y, const BkScratch& scr, int flags) {
   const DType dt = c->dt;
+  const bool even_out = (flags & BK_EVEN_OUT) != 0;
+  // the producer already dropped the rows a stride-2 1x1 skips: stride is 1 here, the routes are chosen for the strided layer
+  const int route_stride = (flags & BK_IN_COMPACT) ? 2 : 0;
+  if (even_out && (!bottleneck_takes_fuse_id(c, blk, B, Cin, Hin, Win, stride, mid, cout) || (Hin & 1) || (Win & 1)))
+    return fail("the stride-2-output bottleneck is the fused bf16 identity block (C 256, mid 64) on a map of even height and width");
   const int s1 = c->cfg.stride_in_1x1 ? stride : 1, s3 = c->cfg.stride_in_1x1 ? 1 : stride;
   const int H1 = (Hin - 1) / s1 + 1, W1 = (Win - 1) / s1 + 1;
   const int Ho = (Hin - 1) / stride + 1, Wo = (Win - 1) / stride + 1;
@@ -87,22 +112,21 @@ int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block&
         BkScratch sub{(char*)t1 + (size_t)b0 * H1 * W1 * mid * e, (char*)t2 + (size_t)b0 * Ho * Wo * mid * e,
                       (char*)sc + (size_t)b0 * Ho * Wo * cout * e, scr.trash};
         RET(add_bottleneck(c, ops, blk, n, (const char*)X + (size_t)b0 * Hin * Win * Cin * e, Cin, Hin, Win, stride, mid, cout,
-                           (char*)Y + (size_t)b0 * Ho * Wo * cout * e, sub));
+                           (char*)Y + (size_t)b0 * Ho * Wo * cout * e, sub, flags));
       }
       return 0;
     }
   }
   // res2 identity blocks (C 256, mid 64, stride 1, no projection), bf16: ONE fused kernel (bottleneck.hip): the two
   // 64-channel intermediates and the second read of x never reach HBM (2 048 -> 1 024 B per position)
-  static const int fuse_bn = getenv("SYLPH_FUSE_BOTTLENECK") ? atoi(getenv("SYLPH_FUSE_BOTTLENECK")) : 1;
+  const int fuse_bn = fuse_bottleneck_knob();
   // (a grouped conv2 -- ResNeXt -- never takes the fused R-50 kernels nor conv_rw3: they compute a dense 3x3)
   const bool dense2 = blk.c2.groups == 1;
-  const bool fuse_id = fuse_bn && dense2 && dt == DT_BF16 && !blk.has_sc && stride == 1 && mid == 64 && Cin == 256 && cout == 256 &&
-                       blk.c1.Cout_pad == 64 && blk.c2.Cout_pad == 64 && blk.c3.Cout_pad == 256;
+  const bool fuse_id = bottleneck_takes_fuse_id(c, blk, B, Cin, Hin, Win, stride, mid, cout);
   // first block of res2 (64 -> 64 -> 64 -> 256, projection folded into conv3's GEMM, stride 1): one fused kernel too
   const bool fuse_pr = fuse_bn && dense2 && dt == DT_BF16 && blk.fused_sc && stride == 1 && mid == 64 && Cin == 64 && cout == 256 &&
                        blk.c1.Cout_pad == 64 && blk.c2.Cout_pad == 64 && blk.c3sc.Cout_pad == 256 && blk.c3sc.Cin == 128 && !blk.c3sc.scale;
-  if ((fuse_id || fuse_pr) && (size_t)Hin * Win * 512 < ((size_t)1 << 32) && (size_t)B * Hin * Win < ((size_t)1 << 31)) {  // 32-bit byte offsets inside ONE image (64-bit image base)
+  if (fuse_id || (fuse_pr && (size_t)Hin * Win * 512 < ((size_t)1 << 32) && (size_t)B * Hin * Win < ((size_t)1 << 31))) {  // 32-bit byte offsets inside ONE image (64-bit image base)
     BottleneckArgs ba;
     memset(&ba, 0, sizeof(ba));
     ba.x = X; ba.y = Y;
@@ -116,6 +140,15 @@ int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block&
     // (A 64-position variant with a double-buffered halo was measured in round 3: 1.56 vs 1.31 ms per launch -- 2.2 x as many tiles pay
     // the per-tile fixed costs; it left the tree in round 5, see bottleneck.hip.)
     const int bk_small = 0;
+    if (even_out) {
+      // outputs at (2 i, 2 j) only, compact: conv1 on every position (each one is in some output's 3x3 window), conv2 / conv3 on a quarter
+      int rp;
+      bottleneck64_even_patch(Hin, Win, &ph, &pw, &rp);
+      RET(upload_bk_tiles(c, B, Hin, Win, ph, pw, &ba, rp));
+      const double fl = 2.0 * (double)B * ((double)Hin * Win * 256.0 * 64 + (double)(Hin / 2) * (Win / 2) * (64.0 * 576 + 64.0 * 256));
+      ops.push_back([=](hipStream_t s) { return timed_op(c, "bottleneck64_kernel", fl, s, [=](hipStream_t st) { return launch_bottleneck64_even(ba, st); }); });
+      return 0;
+    }
     pick_patch(Hin, Win, 128, 184, 2, &ph, &pw);
     RET(upload_bk_tiles(c, B, Hin, Win, ph, pw, &ba));
     const double fl = 2.0 * (double)B * Hin * Win * (fuse_id ? (256.0 * 64 + 64.0 * 576 + 64.0 * 256) : (64.0 * 64 + 64.0 * 576 + 128.0 * 256));
@@ -123,7 +156,7 @@ int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block&
     else ops.push_back([=](hipStream_t s) { return timed_op(c, "bottleneck64p_kernel", fl, s, [=](hipStream_t st) { return launch_bottleneck64p(ba, st); }); });
     return 0;
   }
-  ConvOpts o1; o1.stride = s1; o1.relu_nch = 1 << 30;
+  ConvOpts o1; o1.stride = s1; o1.relu_nch = 1 << 30; o1.route_stride = route_stride;
   RET(add_conv(c, ops, blk.c1, X, Cin, t1, mid, image_segs(B, Hin, Win, H1, W1), o1));
   // res3 conv2 (3x3, 128 -> 128, stride 1), bf16: weights in registers, LDS holds only the activation halo (conv_rw3.hip)
   static const int rw3_on = getenv("SYLPH_CONV_RW3") ? atoi(getenv("SYLPH_CONV_RW3")) : 1;
@@ -162,12 +195,12 @@ int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block&
     // tensor is never written to / re-read from HBM
     std::vector<SegDesc> sg = image_segs(B, Ho, Wo, Ho, Wo);
     for (int b = 0; b < B; ++b) { sg[b].in2_row0 = b * Hin * Win; sg[b].in2_W = Win; }
-    ConvOpts o3; o3.relu_nch = 1 << 30; o3.in2 = X; o3.in2_ld = Cin; o3.Cin2 = Cin; o3.stride2 = stride;
+    ConvOpts o3; o3.relu_nch = 1 << 30; o3.in2 = X; o3.in2_ld = Cin; o3.Cin2 = Cin; o3.stride2 = stride;  // (no route depends on stride2)
     RET(add_conv(c, ops, blk.c3sc, t2, mid, Y, cout, sg, o3));
   } else {
     const void* resid = X;
     if (blk.has_sc) {
-      ConvOpts os; os.stride = stride;
+      ConvOpts os; os.stride = stride; os.route_stride = route_stride;
       RET(add_conv(c, ops, blk.sc, X, Cin, sc, cout, image_segs(B, Hin, Win, Ho, Wo), os));
       resid = sc;
     }
@@ -315,9 +348,15 @@ int build_backbone(sylph_ctx* c, Plan* P) {
   int stage_h[4], stage_w[4];
   const bool basic = !c->stages[0].empty() && c->stages[0][0].basic;  // R-18 / R-34: BasicBlocks, stage widths 64 << si
   int stage_c[4];
+  // The last block of a stage that no one reads but the next stage's strided 1x1 convs (res2 with STRIDE_IN_1X1: res3.0's conv1 and
+  // shortcut take every other row and column, and res2 is no FPN input) computes only those positions, into a compact tensor (bottleneck.hip,
+  // EVEN): a quarter of its conv2 / conv3 work and of its stores.  The next block then runs its own launches on that tensor with stride 1.
+  // SYLPH_BK_STRIDED_TAIL: 0 off, 1 (default) on.
+  static const int strided_tail = getenv("SYLPH_BK_STRIDED_TAIL") ? atoi(getenv("SYLPH_BK_STRIDED_TAIL")) : 1;
+  bool in_compact = false;  // X is such a compact tensor (Hin x Win its size)
   for (int si = 0; si < 4; ++si) {
     const int mid = (c->cfg.num_groups * c->cfg.width_per_group) << si, cout = (basic ? 64 : 256) << si;  // (ResNeXt: num_groups > 1)
-    const int first_stride = si == 0 ? 1 : 2;
+    const int first_stride = si == 0 ? 1 : in_compact ? 1 : 2;
     const int Hs = (Hin - 1) / first_stride + 1, Ws = (Win - 1) / first_stride + 1;
     void *t1, *t2 = nullptr, *sc, *Ya, *Yb;
     // t1 may still be at the input resolution when the stride sits on the 3x3 (a BasicBlock's one intermediate is at the output's)
@@ -332,11 +371,25 @@ int build_backbone(sylph_ctx* c, Plan* P) {
     for (size_t bi = 0; bi < blocks.size(); ++bi) {
       const int stride = bi == 0 ? first_stride : 1;
       Y = (Y == Ya) ? Yb : Ya;
+      const bool fpn_input = si >= 1;
+      const bool even_tail = strided_tail && !basic && bi > 0 && bi + 1 == blocks.size() && !fpn_input && si + 1 < 4 && c->cfg.stride_in_1x1 &&
+                             !c->stages[si + 1].empty() && !c->stages[si + 1][0].basic && (Hin & 1) == 0 && (Win & 1) == 0 &&
+                             bottleneck_takes_fuse_id(c, blocks[bi], B, Cin, Hin, Win, stride, mid, cout);
       if (basic) RET(add_basic_block(c, ops, blocks[bi], B, X, Cin, Hin, Win, stride, cout, Y, scr));
-      else RET(add_bottleneck(c, ops, blocks[bi], B, X, Cin, Hin, Win, stride, mid, cout, Y, scr));
+      else RET(add_bottleneck(c, ops, blocks[bi], B, X, Cin, Hin, Win, stride, mid, cout, Y, scr,
+                              even_tail ? BK_EVEN_OUT : (bi == 0 && in_compact) ? BK_IN_COMPACT : 0));
+      if (bi == 0) in_compact = false;
+      if (even_tail) {  // the dense output exists on demand only (sylph_export_stage)
+        P->tail_even = true; P->tail_x = X;
+        P->stage_h[si] = Hin; P->stage_w[si] = Win; P->stage_c[si] = cout;
+        in_compact = true;
+        X = Y; Hin /= 2; Win /= 2; Cin = cout;
+        continue;
+      }
       X = Y; Hin = (Hin - 1) / stride + 1; Win = (Win - 1) / stride + 1; Cin = cout;
     }
     stage_out[si] = X; stage_h[si] = Hin; stage_w[si] = Win; stage_c[si] = cout;
+    if (in_compact) continue;  // (P->stage_h / _w / _c hold the dense shape; P->stage_out[si] stays empty)
     P->stage_out[si] = X; P->stage_h[si] = Hin; P->stage_w[si] = Win; P->stage_c[si] = cout;
   }
   // FPN (res3..res5 -> p3..p5), top-down with nearest 2x upsample fused as a residual, then P6/P7

@@ -158,6 +158,7 @@ ConvRoute pick_conv_route(const sylph_ctx* c, const ConvLayer& L, int in_ld, con
   const bool bf16 = c->dt == DT_BF16;
   const bool k3s1 = L.KH == 3 && L.KW == 3 && o.stride == 1 && o.pad == 1 && !o.stem && !o.in2;
   const int cout_l = o.cout_override >= 0 ? o.cout_override : L.Cout;
+  const int pstride = o.route_stride ? o.route_stride : o.stride;  // (pointwise layers on an already subsampled input: ConvOpts)
   ConvRoute r;
   conv_pick_tile((int)rows, L.Cout_pad, o.stem ? 49 : L.KH * L.KW, &r.BM, &r.BN);
 
@@ -221,15 +222,15 @@ ConvRoute pick_conv_route(const sylph_ctx* c, const ConvLayer& L, int in_ld, con
     // images, 48 vs 40 at 16.)
     const long mtiles = (rows + bm - 1) / bm;
     const bool spw_shape = L.Cout % 256 == 0 && L.Cout <= 2048 && bm == 128 && bn == 256;
-    const bool spw_r1 = o.res_mode == 1 && o.res && (L.Cin == 128 || L.Cin == 256 || L.Cin == 512) && o.stride == 1 && !o.in2 && (o.res_ld & 7) == 0 &&
+    const bool spw_r1 = o.res_mode == 1 && o.res && (L.Cin == 128 || L.Cin == 256 || L.Cin == 512) && pstride == 1 && !o.in2 && (o.res_ld & 7) == 0 &&
                         (spw_on == 2 || mtiles >= 512);  // a block owns whole M tiles: at least two per CU
-    const bool spw_r2 = o.res_mode == 2 && o.res && L.Cin == 512 && o.stride == 1 && !o.in2 && o.relu_nch == 0 && (o.res_ld & 7) == 0 &&
+    const bool spw_r2 = o.res_mode == 2 && o.res && L.Cin == 512 && pstride == 1 && !o.in2 && o.relu_nch == 0 && (o.res_ld & 7) == 0 &&
                         (spw_on == 2 || mtiles >= 2048);
     const bool spw_r0 = o.res_mode == 0 && !o.res && o.relu_nch > 0 &&
-                        ((!o.in2 && L.Cin == 512 && o.stride == 2 && spw_on == 2) ||
-                         (o.in2 && L.Cin == 384 && o.Cin2 == 256 && o.stride == 1 && (o.in2_ld & 7) == 0 && (spw_on == 2 || mtiles >= 2048)));
+                        ((!o.in2 && L.Cin == 512 && pstride == 2 && spw_on == 2) ||
+                         (o.in2 && L.Cin == 384 && o.Cin2 == 256 && pstride == 1 && (o.in2_ld & 7) == 0 && (spw_on == 2 || mtiles >= 2048)));
     const bool spw = spw_on && spw_shape && (spw_r1 || spw_r2 || spw_r0);
-    const bool pays = (o.res_mode != 1 || spw) && (L.Cout % 256 == 0 || o.stride != 1);
+    const bool pays = (o.res_mode != 1 || spw) && (L.Cout % 256 == 0 || pstride != 1);
     if (fits && (pw_on == 2 || spw || (tiles >= 256 && pays))) {
       r.kind = spw ? ConvKind::spw : ConvKind::pw; r.BM = bm; r.BN = bn;
       return r;

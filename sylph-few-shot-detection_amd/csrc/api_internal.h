@@ -245,6 +245,12 @@ struct Plan {
   // parity taps (sylph_export_stage / sylph_export_tower): where the stage outputs res2..res5 and, with debug taps on, every
   // tower layer's stored conv output and GroupNorm coefficient table live
   const void* stage_out[4] = {nullptr, nullptr, nullptr, nullptr};
+  // res2 when its last block took the stride-2-output launch (build_backbone): stage_out[0] is then filled on demand -- the tap runs
+  // tail_dense_ops, the dense launch of that block from its intact input into tail_dense (allocated on first use)
+  bool tail_even = false;
+  const void* tail_x = nullptr;  // the last block's input: the stage's other ping-pong buffer
+  void* tail_dense = nullptr;
+  std::vector<OpFn> tail_dense_ops;
   int stage_h[4] = {0, 0, 0, 0}, stage_w[4] = {0, 0, 0, 0}, stage_c[4] = {0, 0, 0, 0};
   std::vector<const void*> tap_out[2];      // [cls | bbox][layer]: conv output [rows][256] (pre-GroupNorm when tap_coef is set)
   std::vector<const float2*> tap_coef[2];   // [cls | bbox][layer]: (a, b) per (segment, channel), nullptr if applied in place
@@ -349,6 +355,8 @@ struct ConvOpts {
   int gn_relu = 0;
   int segs_per_image = 1;  // consecutive segments that belong to one image (pyramid-wide launches: the FPN levels)
   int stream_slot = 0;     // 1: the op will run on the context's side stream (its split-K scratch must not be the main stream's)
+  int route_stride = 0;    // != 0: pick_conv_route decides as if `stride` were this (a strided 1x1 whose input was already subsampled by
+                           // its producer keeps the launch of the strided layer: same kernel, same tiles, same K order)
 };
 
 // The kernel add_conv launches for one conv (pick_conv_route), with its tiles, LDS stages and K split:
@@ -366,6 +374,12 @@ struct ConvRoute {
 };
 
 struct BkScratch { void *t1, *t2, *sc; void** trash; };
+// add_bottleneck flags
+//   BK_EVEN_OUT    the block's output only at even rows / columns, Y compact [B][Hin/2 * Win/2][cout]: the fused identity block of
+//                  res2 alone (bottleneck.hip, EVEN); anything else is refused
+//   BK_IN_COMPACT  X is the compact output of such a block and Hin x Win its size: the (first, stride-2, stride-in-1x1) block is
+//                  passed stride 1 and runs the strided block's launches on the rows it would have picked
+enum { BK_EVEN_OUT = 1, BK_IN_COMPACT = 2 };
 
 namespace sylph_host {
 std::shared_ptr<PilCoeffs> pil_bilinear_coeffs(int in_size, int out_size);
@@ -411,7 +425,8 @@ int add_conv_deform(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& off, 
 std::vector<SegDesc> image_segs(int B, int Hin, int Win, int Hout, int Wout, int resH = 0, int resW = 0);
 // api_backbone.hip
 int ensure_pyramid(sylph_ctx* c, Plan* P);
-int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win, int stride, int mid, int cout, void* Y, const BkScratch& scr);
+int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win, int stride, int mid, int cout, void* Y, const BkScratch& scr, int flags = 0);
+bool bottleneck_takes_fuse_id(const sylph_ctx* c, const sylph_ctx::Block& blk, int B, int Cin, int Hin, int Win, int stride, int mid, int cout);
 int add_conv3x3_c64(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, int B, int H, int W, const void* x, const void* res, void* y, int relu);
 int add_basic_block(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win, int stride, int cout, void* Y, const BkScratch& scr);
 int build_backbone(sylph_ctx* c, Plan* P);

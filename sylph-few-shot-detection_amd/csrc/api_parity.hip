@@ -53,11 +53,26 @@ int sylph_set_debug_taps(sylph_ctx* c, int on) {
 int sylph_export_stage(sylph_ctx* c, int stage, float* out) {
   Plan* P = c->cur;
   if (!P || !P->backbone_built) return fail("no backbone pass on the current batch");
-  if (stage < 2 || stage > 5 || !P->stage_out[stage - 2]) return fail("bad stage");
+  const bool on_demand = stage == 2 && P->tail_even;
+  if (stage < 2 || stage > 5 || (!P->stage_out[stage - 2] && !on_demand)) return fail("bad stage");
   HIPCHK(hipSetDevice(c->device));
   const int si = stage - 2, C = P->stage_c[si], hw = P->stage_h[si] * P->stage_w[si];
+  const void* src = P->stage_out[si];
+  if (on_demand) {
+    // the step computed res2 at the positions res3 reads only: run the last block's DENSE launch now, from its input (intact in the stage's
+    // other ping-pong buffer) into a buffer of the tap's own.  Nothing the step or a later head / decode reads is written.
+    if (!P->tail_dense) {
+      OwnerScope own(c, P);
+      RET(c->dalloc(&P->tail_dense, (size_t)P->B * hw * C * c->esz()));
+      BkScratch scr{nullptr, nullptr, nullptr, &P->bk_trash};
+      const int rc = add_bottleneck(c, P->tail_dense_ops, c->stages[0].back(), P->B, P->tail_x, C, P->stage_h[si], P->stage_w[si], 1, 64, C, P->tail_dense, scr);
+      if (rc != 0) { P->tail_dense_ops.clear(); return rc; }
+    }
+    RET(run_ops(c, P->tail_dense_ops, "res2 tap"));
+    src = P->tail_dense;
+  }
   for (int b = 0; b < P->B; ++b)
-    KCHK(launch_export_nchw(c->dt, P->stage_out[si], out + (size_t)b * C * hw, C, hw, b * hw, C, c->stream), "export stage");
+    KCHK(launch_export_nchw(c->dt, src, out + (size_t)b * C * hw, C, hw, b * hw, C, c->stream), "export stage");
   return 0;
 }
 
@@ -80,8 +95,9 @@ int sylph_export_tower(sylph_ctx* c, int tower, int layer, int level, float* y, 
   return 0;
 }
 
+// even_out: the stride-2-output launch of the fused identity block (BK_EVEN_OUT), y (B, cout, H/2, W/2)
 static int bottleneck_entry(sylph_ctx* c, const float* x, int B, int Cin, int H, int W, int stride, int mid, int cout, int groups,
-                            const float* const* w_host, const float* const* scale_host, const float* const* shift_host, float* y) {
+                            const float* const* w_host, const float* const* scale_host, const float* const* shift_host, float* y, bool even_out = false) {
   HIPCHK(hipSetDevice(c->device));
   const int bk = c->dt == DT_BF16 ? 64 : 32;
   if (Cin % bk != 0 || mid % bk != 0) return fail("sylph_bottleneck: channel counts must be multiples of " + std::to_string(bk));
@@ -114,7 +130,7 @@ static int bottleneck_entry(sylph_ctx* c, const float* x, int B, int Cin, int H,
     blk.fused_sc = true;
   }
   const size_t e = tmp.esz();
-  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  const int Ho = even_out ? H / 2 : (H - 1) / stride + 1, Wo = even_out ? W / 2 : (W - 1) / stride + 1;
   void *xin, *yout, *t1, *t2, *sc, *trash = nullptr;
   RET(tmp.dalloc(&xin, (size_t)B * H * W * Cin * e));
   RET(tmp.dalloc(&yout, (size_t)B * Ho * Wo * cout * e));
@@ -125,7 +141,7 @@ static int bottleneck_entry(sylph_ctx* c, const float* x, int B, int Cin, int H,
     KCHK(launch_import_nchw(c->dt, x + (size_t)b * Cin * H * W, xin, Cin, H * W, b * H * W, Cin, c->stream), "import");
   std::vector<OpFn> ops;
   BkScratch scr{t1, t2, sc, &trash};
-  RET(add_bottleneck(&tmp, ops, blk, B, xin, Cin, H, W, stride, mid, cout, yout, scr));
+  RET(add_bottleneck(&tmp, ops, blk, B, xin, Cin, H, W, stride, mid, cout, yout, scr, even_out ? BK_EVEN_OUT : 0));
   RET(run_ops(c, ops, "bottleneck"));
   adopt_records(c, &tmp);
   for (int b = 0; b < B; ++b)
@@ -136,6 +152,14 @@ static int bottleneck_entry(sylph_ctx* c, const float* x, int B, int Cin, int H,
 int sylph_bottleneck(sylph_ctx* c, const float* x, int B, int Cin, int H, int W, int stride, int mid, int cout, const float* const* w_host,
                      const float* const* scale_host, const float* const* shift_host, float* y) {
   return bottleneck_entry(c, x, B, Cin, H, W, stride, mid, cout, 1, w_host, scale_host, shift_host, y);
+}
+
+int sylph_bottleneck_even(sylph_ctx* c, const float* x, int B, int Cin, int H, int W, int mid, int cout, const float* const* w_host,
+                          const float* const* scale_host, const float* const* shift_host, float* y) {
+  if (B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return fail("sylph_bottleneck_even: H and W must be even");
+  if (Cin != 256 || mid != 64 || cout != 256 || c->dt != DT_BF16) return fail("sylph_bottleneck_even: the fused identity block is C 256, mid 64, bf16");
+  if (!w_host[0] || !w_host[1] || !w_host[2] || w_host[3]) return fail("sylph_bottleneck_even: an identity block has three convs and no shortcut");
+  return bottleneck_entry(c, x, B, Cin, H, W, 1, mid, cout, 1, w_host, scale_host, shift_host, y, true);
 }
 
 int sylph_bottleneck_grouped(sylph_ctx* c, const float* x, int B, int Cin, int H, int W, int stride, int mid, int cout, int groups,

@@ -42,6 +42,7 @@ constexpr int TP = 144;                        // t1 / t2 row pitch: 128 B of ch
 constexpr int T1_OFF = XB_BYTES;               // 27 648: t1 halo [192][64 ch]; t2 [128][64 ch] aliases it
 constexpr int BN_OFF = T1_OFF + XROWS * TP;    // s1 b1 s2 b2 (64 each) s3 b3 (256 each), fp32
 constexpr int LDS_BYTES = BN_OFF + (4 * MID + 2 * C) * 4;  // 129 024
+constexpr int EVEN_T1_ROWS = 224;              // t1 slots of the stride-2-output build (halo rows at a padded pitch, see EVEN below)
 }  // namespace
 
 // NR1 / NR2 / NR3: 32-row MFMA tiles a wave processes in P1 (halo rows) / P2 / P3 (patch positions); XR = NR1 * 64 halo rows.
@@ -49,12 +50,24 @@ constexpr int LDS_BYTES = BN_OFF + (4 * MID + 2 * C) * 4;  // 129 024
 //   <2, 1, 2, true>:  (round-3 experiment, no longer instantiated: patches of <= 64 positions, TWO 64-KiB halo buffers, the next
 //                     patch's halo issued a whole tile ahead.  The halo round trip was hidden, but 2.2 x as many tiles paid the
 //                     per-tile fixed costs: 1.56 ms vs 1.31 ms per launch at B = 64.  Its LDS no longer fits beside the store staging.)
-template <int NR1, int NR2, int NR3, bool DB>
+//
+// EVEN (<3, 1, 2, false, true>): the block's output only at even rows and even columns, written to a compact [B][H/2 * W/2][256]
+// tensor -- the last block of res2 when the next stage's first block strides in its 1x1 convs and reads nothing else.  A tile is
+// ph x pw OUTPUT positions (<= 64) at (2 i, 2 j); its halo is the (2 ph + 1) x (2 pw + 1) input positions conv2 reaches, every one of
+// which feeds some output: conv1 runs on all of them, conv2 / conv3 / the stores on the outputs alone.  The tile descriptor's yx is the
+// tile origin in OUTPUT coordinates, ph carries the t1 row pitch RP in its upper half.  Each stored value goes through exactly the
+// operations, in the order, of the dense build at that position.
+//   * t1 layout: halo position (hy, hx) sits in slot hy * RP + hx / 2 (+ pw + 1 for odd hx): de-interleaved by column parity, so the
+//     outputs mx, mx + 1, .. of a tile row read CONSECUTIVE 144-byte slots for each kw, as in the dense build (at the dense halo order
+//     they would be 288 B apart: ds_read_b128 lanes i and i + 8 on the same banks).  RP is chosen on the host so that the step to the
+//     next tile row (2 RP slots) continues that bank sequence: 2 RP = pw (mod 16), RP 20 for the 5 x 8 tiles of the 100 x 168 map.
+//   * the x halo keeps the dense order (it is what the LDS-DMA writes and conv1 reads); the residual copy reads its odd rows / columns.
+template <int NR1, int NR2, int NR3, bool DB, bool EVEN = false>
 __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckArgs a) {
   constexpr int XR = NR1 * 64;                     // halo rows of a buffer
   constexpr int XBB = XR * 512;                    // one halo buffer
   constexpr int T1O = (DB ? 2 : 1) * XBB;          // t1 halo [XR][64 ch] (pitch TP); t2 aliases it
-  constexpr int BNO = T1O + XR * TP;
+  constexpr int BNO = T1O + (EVEN ? EVEN_T1_ROWS : XR) * TP;
   constexpr int STG = BNO + (4 * MID + 2 * C) * 4;  // store staging: 4 KiB per wave (32 rows x 128 B, piece p of row r at slot p ^ (r & 7))
   constexpr int TAB = STG + 4 * 4096;               // y byte offset of every patch position, [row tile][row & 7][(row >> 3) & 3] (512 B)
   constexpr int NST = NR3 * 4;                     // stores per lane and tile (16 bytes each: whole 128-byte lines per 8 lanes)
@@ -124,13 +137,15 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
   // for those rows (they are conv2's zero padding) and the residual is only read at stored positions.
   const int xr = tid >> 5, xs = tid & 31;
   auto issue_x = [&](const i32x8 d, char* dstb) {
-    const int row0 = d[0], H = d[1], W = d[2], oy0 = d[3] >> 16, ox0 = d[3] & 0xffff, HW2 = d[5] + 2, HR = (d[4] + 2) * HW2;
+    const int row0 = d[0], H = d[1], W = d[2], oy0 = d[3] >> 16, ox0 = d[3] & 0xffff;
+    const int HW2 = EVEN ? 2 * d[5] + 1 : d[5] + 2, HR = (EVEN ? 2 * (d[4] & 0xffff) + 1 : d[4] + 2) * HW2;
+    const int hy0 = EVEN ? 2 * oy0 - 1 : oy0 - 1, hx0 = EVEN ? 2 * ox0 - 1 : ox0 - 1;  // image position of halo (0, 0)
     const int nr = (HR + 7) >> 3;  // rows >= HR are never read by P2
     int hy = 0, hx = xr;
     for (int r = 0; r < nr; ++r) {
       while (hx >= HW2) { hx -= HW2; ++hy; }  // (a single step for patches at least 6 wide; narrow maps may wrap twice)
       const int h = r * 8 + xr;
-      const int iy = min(max(oy0 - 1 + hy, 0), H - 1), ix = min(max(ox0 - 1 + hx, 0), W - 1);
+      const int iy = min(max(hy0 + hy, 0), H - 1), ix = min(max(hx0 + hx, 0), W - 1);
       // per-image 64-bit base (wave-uniform, from the tile descriptor) + a 32-bit offset INSIDE the image: no limit on the batch (rounds
       // 2-5 offset the whole tensor with 32 bits: the fused kernels fell away above 124 images of 800 x 1333)
       const unsigned off = ((unsigned)(iy * W + ix) << 9) + (unsigned)((xs ^ (h & 31)) << 4);
@@ -158,8 +173,13 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
 
   for (int it = 0; t < a.n_tiles; ++it) {
     const int row0 = td[0], IH = td[1], IW = td[2], oy0 = td[3] >> 16, ox0 = td[3] & 0xffff;
-    char* const yimg = reinterpret_cast<char*>(y) + (size_t)(unsigned)row0 * (size_t)(C * 2);  // this image's first output row (wave-uniform)
-    const int PW = td[5], HW2 = PW + 2, HR = (td[4] + 2) * HW2, NPOS = td[4] * PW;
+    // this image's first output row (wave-uniform; EVEN: the compact image has a quarter of the input's rows)
+    char* const yimg = reinterpret_cast<char*>(y) + (size_t)(unsigned)(EVEN ? row0 >> 2 : row0) * (size_t)(C * 2);
+    const int PH = EVEN ? td[4] & 0xffff : td[4], RP = EVEN ? td[4] >> 16 : 0, PW = td[5];
+    const int HW2 = EVEN ? 2 * PW + 1 : PW + 2, HR = (EVEN ? 2 * PH + 1 : PH + 2) * HW2, NPOS = PH * PW;
+    const int hy0 = EVEN ? 2 * oy0 - 1 : oy0 - 1, hx0 = EVEN ? 2 * ox0 - 1 : ox0 - 1;  // image position of halo (0, 0)
+    const int OH = EVEN ? IH >> 1 : IH, OW = EVEN ? IW >> 1 : IW;                      // the output map
+    (void)RP;
     const unsigned inv_pw = (unsigned)td[6], inv_hw2 = (unsigned)td[7];
     const int t_next = tile_of(it + 1);
     const i32x8 td_next = load_tile(t_next < a.n_tiles ? t_next : 0);
@@ -176,8 +196,8 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
     if (tid < NR3 * 32) {
       const int m = tid;
       const int my = (int)(((unsigned)m * inv_pw) >> 16), mx = m - my * PW;
-      const bool pv = m < NPOS && oy0 + my < IH && ox0 + mx < IW;
-      const unsigned off = pv ? (unsigned)((oy0 + my) * IW + ox0 + mx) * (unsigned)(C * 2) : 0xffffffffu;  // inside the image
+      const bool pv = m < NPOS && oy0 + my < OH && ox0 + mx < OW;
+      const unsigned off = pv ? (unsigned)((oy0 + my) * OW + ox0 + mx) * (unsigned)(C * 2) : 0xffffffffu;  // inside the image
       *reinterpret_cast<unsigned*>(smem + TAB + ((m >> 5) * 32 + (m & 7) * 4 + ((m >> 3) & 3)) * 4) = off;
     }
     if (DB) {
@@ -228,16 +248,20 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
       for (int i = 0; i < NR1; ++i) {
         const int h = (rb1 + i) * 32 + l31a;
         const int hy = (int)(((unsigned)h * inv_hw2) >> 16), hx = h - hy * HW2;
-        const bool in1 = h < HR && (unsigned)(oy0 - 1 + hy) < (unsigned)IH && (unsigned)(ox0 - 1 + hx) < (unsigned)IW;
+        const bool in1 = h < HR && (unsigned)(hy0 + hy) < (unsigned)IH && (unsigned)(hx0 + hx) < (unsigned)IW;
         const unsigned keep = in1 ? 0xffffffffu : 0u;
-        char* wp = t1 + h * TP + ct1 * 64 + 8 * lh;
+        // EVEN: slot de-interleaved by column parity, rows at pitch RP; rows >= HR have no slot (and no reader) and are not written
+        const int slot = EVEN ? hy * RP + (hx >> 1) + ((hx & 1) ? PW + 1 : 0) : h;
+        char* wp = t1 + slot * TP + ct1 * 64 + 8 * lh;
+        if (!EVEN || h < HR) {
 #pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-          const f32x4 sv = *reinterpret_cast<const f32x4*>(sp + 8 * gq), bv = *reinterpret_cast<const f32x4*>(sp + MID + 8 * gq);
-          u32x2 o;
-          o[0] = relu_pk(pack2(acc1[i][4 * gq] * sv[0] + bv[0], acc1[i][4 * gq + 1] * sv[1] + bv[1]), keep);
-          o[1] = relu_pk(pack2(acc1[i][4 * gq + 2] * sv[2] + bv[2], acc1[i][4 * gq + 3] * sv[3] + bv[3]), keep);
-          *reinterpret_cast<u32x2*>(wp + gq * 16) = o;
+          for (int gq = 0; gq < 4; ++gq) {
+            const f32x4 sv = *reinterpret_cast<const f32x4*>(sp + 8 * gq), bv = *reinterpret_cast<const f32x4*>(sp + MID + 8 * gq);
+            u32x2 o;
+            o[0] = relu_pk(pack2(acc1[i][4 * gq] * sv[0] + bv[0], acc1[i][4 * gq + 1] * sv[1] + bv[1]), keep);
+            o[1] = relu_pk(pack2(acc1[i][4 * gq + 2] * sv[2] + bv[2], acc1[i][4 * gq + 3] * sv[3] + bv[3]), keep);
+            *reinterpret_cast<u32x2*>(wp + gq * 16) = o;
+          }
         }
       }
     }
@@ -247,9 +271,10 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
     asm volatile("v_mov_b32 %0, 0" : "=v"(lzr));
 #pragma unroll
     for (int rt = 0; rt < NR3; ++rt) {
-      const int m = rt * 32 + l31 + lzr;
+      // (EVEN: pad positions m >= NPOS -- never stored -- take the last real one's rows: every LDS address stays inside the tile's)
+      const int m = EVEN ? min(rt * 32 + l31 + lzr, NPOS - 1) : rt * 32 + l31 + lzr;
       const int my = (int)(((unsigned)m * inv_pw) >> 16), mx = m - my * PW;
-      const int hc = (my + 1) * HW2 + mx + 1;
+      const int hc = EVEN ? (2 * my + 1) * HW2 + 2 * mx + 1 : (my + 1) * HW2 + mx + 1;
       const int rowoff = hc * 512 + ((hc & 31) << 4) + 8 * lh;  // chunk c of this row sits at rowoff ^ (c << 4)
 #pragma unroll
       for (int j = 0; j < 2; ++j)
@@ -279,9 +304,9 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
       const char* hrow[NR2];
 #pragma unroll
       for (int i = 0; i < NR2; ++i) {
-        const int m = (rb2 + i) * 32 + l31b;
+        const int m = EVEN ? min((rb2 + i) * 32 + l31b, NPOS - 1) : (rb2 + i) * 32 + l31b;
         const int my = (int)(((unsigned)m * inv_pw) >> 16);
-        hrow[i] = t1 + (my * HW2 + (m - my * PW)) * TP + 16 * lh;
+        hrow[i] = t1 + (EVEN ? 2 * my * RP + (m - my * PW) : my * HW2 + (m - my * PW)) * TP + 16 * lh;
       }
       // Fragment ring, D2 - 1 k-steps ahead of the MFMAs.  The reads are inline asm with COUNTED waits: the next patch's halo is
       // in flight (LDS-DMA) during this phase, and while one is pending hipcc treats the LGKM counter as out of order and turns
@@ -292,7 +317,9 @@ __global__ __launch_bounds__(256, 1) void bottleneck64_kernel(const BottleneckAr
         const int tap = k >> 2, ks = k & 3, kh = tap / 3, kw = tap - 3 * kh;
 #pragma unroll
         for (int i = 0; i < NR2; ++i) {
-          const unsigned ad = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)(hrow[i] + (kh * HW2 + kw) * TP);
+          // (EVEN: tap column kw of output mx is halo column 2 mx + kw = slot mx of the even block, mx of the odd block, mx + 1 of the even one)
+          const int tapoff = EVEN ? kh * RP + (kw == 1 ? PW + 1 : kw >> 1) : kh * HW2 + kw;
+          const unsigned ad = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)(hrow[i] + tapoff * TP);
           if (ks == 0) asm volatile("ds_read_b128 %0, %1" : "=v"(af[k % D2][i]) : "v"(ad));
           else if (ks == 1) asm volatile("ds_read_b128 %0, %1 offset:32" : "=v"(af[k % D2][i]) : "v"(ad));
           else if (ks == 2) asm volatile("ds_read_b128 %0, %1 offset:64" : "=v"(af[k % D2][i]) : "v"(ad));
@@ -728,6 +755,42 @@ int launch_bottleneck64(const BottleneckArgs& a, int small, hipStream_t s) {
   const int grid = want < ncu ? want : (ncu & ~7);
   if (small) return -1;  // the 64-position double-buffered variant (round 3, measured 1.56 vs 1.31 ms) no longer fits beside the store staging
   hipLaunchKernelGGL((bottleneck64_kernel<3, 2, 4, false>), dim3(grid), dim3(256), lds_big, s, a);
+  return (int)hipGetLastError();
+}
+
+// Tile of the stride-2-output build for an H x W INPUT map (both even): ph x pw outputs whose (2 ph + 1) x (2 pw + 1) halo fits the
+// 192-row halo buffer (at most 40 outputs: 5 x 8 or 4 x 10), fewest tiles first, then the smallest halo; 200 x 336 -> 5 x 8 (20 x 21
+// tiles).  rp: t1 row pitch in slots, >= 2 pw + 1, with 2 rp = pw (mod 16) where the slots allow it (see the kernel's header).
+void bottleneck64_even_patch(int H, int W, int* ph_out, int* pw_out, int* rp_out) {
+  const int Ho = H / 2, Wo = W / 2;
+  long best_n = -1;
+  int bh = 5, bw = 8, best_halo = 0;
+  for (int w = 4; w <= 32; ++w)
+    for (int h = 1; h * w <= 64; ++h) {
+      const int halo = (2 * h + 1) * (2 * w + 1);
+      if (halo > XROWS) continue;
+      const long n = (long)((Ho + h - 1) / h) * ((Wo + w - 1) / w);
+      if (best_n < 0 || n < best_n || (n == best_n && halo < best_halo)) { best_n = n; bh = h; bw = w; best_halo = halo; }
+    }
+  int rp = 2 * bw + 1;
+  if ((bw & 1) == 0) {
+    int r = rp;
+    while ((2 * r - bw) & 15) ++r;
+    if (2 * bh * r + 2 * bw + 1 <= EVEN_T1_ROWS) rp = r;  // highest slot written: row 2 ph, odd block's last column
+  }
+  *ph_out = bh; *pw_out = bw; *rp_out = rp;
+}
+
+// the stride-2-output build: the tile table is upload_bk_tiles' EVEN form (origins in output coordinates, ph | rp << 16)
+int launch_bottleneck64_even(const BottleneckArgs& a, hipStream_t s) {
+  constexpr int lds_even = 192 * 512 + EVEN_T1_ROWS * TP + (4 * MID + 2 * C) * 4 + 4 * 4096 + 512;
+  static_assert(lds_even <= 160 * 1024, "LDS budget");
+  static PerDeviceOnce once;
+  const int dev = current_device(), ncu = device_cu_count(dev);
+  if (!once.run(dev, [] { return hipFuncSetAttribute((const void*)bottleneck64_kernel<3, 1, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_even) == hipSuccess; })) return -7;
+  const int want = (a.n_tiles + 7) & ~7;
+  const int grid = want < ncu ? want : (ncu & ~7);
+  hipLaunchKernelGGL((bottleneck64_kernel<3, 1, 2, false, true>), dim3(grid), dim3(256), lds_even, s, a);
   return (int)hipGetLastError();
 }
 

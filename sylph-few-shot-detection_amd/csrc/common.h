@@ -75,6 +75,8 @@ struct PwDesc { int row0, seg_rows, out_W, out_row0, in_row0, in_W, in2_row0, in
 
 // fused identity bottleneck (bottleneck.hip): x, y [pos][256] bf16; w1 [64][256], w2 [64][3][3][64], w3 [256][64] bf16
 // (the conv_igemm weight layouts); FrozenBN scale / shift per conv (fp32)
+// (stride-2-output build of the identity block: H x W is the INPUT map, yx the tile origin in the H/2 x W/2 OUTPUT map, ph x pw output
+// positions, ph carries the t1 row pitch in bits 16.., inv_hw2 divides by the halo width 2 pw + 1)
 struct BkTile { int row0, H, W, yx, ph, pw; unsigned inv_pw, inv_hw2; };  // one 32-byte descriptor per patch (s_load_dwordx8)
 struct BottleneckArgs {
   const void* x;
@@ -177,6 +179,8 @@ bool conv_hpipe_ok(DType dt, bool out_f32, const ConvArgs& a);
 int launch_conv_hpipe(const ConvArgs& a, hipStream_t s);
 int launch_hpipe_pack_weights(const void* w_igemm, void* w_hpipe, int Cout, int Cin, hipStream_t s);  // a.wt of an hpipe launch
 int launch_bottleneck64(const BottleneckArgs& a, int small, hipStream_t s);   // bottleneck.hip: identity block, persistent, weights in registers; small: 64-position patches, double-buffered halo
+int launch_bottleneck64_even(const BottleneckArgs& a, hipStream_t s);  // the same block, outputs at even rows / columns only: y [B][H/2 * W/2][256]
+void bottleneck64_even_patch(int H, int W, int* ph_out, int* pw_out, int* rp_out);  // its tile (ph x pw outputs) and t1 row pitch for an H x W input
 int launch_bottleneck64p(const BottleneckArgs& a, hipStream_t s);  // first block of res2: x [pos][64], w3 = [256][128] packed [W3 | Wsc], y = relu(acc + b3)
 int launch_conv_rw3(const BottleneckArgs& a, hipStream_t s);  // conv_rw3.hip: 3x3 s1 128 -> 128 + FrozenBN + ReLU, weights in registers (x, y, w2, s2, b2, bk, n_tiles)
 bool conv_rw3_patch_ok(int ph, int pw);

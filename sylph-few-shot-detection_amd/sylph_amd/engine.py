@@ -758,6 +758,20 @@ class Engine:
               "bottleneck")
         return y
 
+    def bottleneck_even(self, x, ws, scales, shifts):
+        """The fused identity block (C 256, mid 64, bf16) through the stride-2-output launch of res2's last block: (B, 256, H/2, W/2), the
+        block's output at the even rows and columns.  H and W must be even."""
+        self._stream()
+        x = x.to(self.device, torch.float32).contiguous()
+        B, Cin, H, W = x.shape
+        mid, cout = ws[0].shape[0], ws[2].shape[0]
+        keep = [[t.detach().cpu().float().contiguous() for t in lst[:3]] for lst in (ws, scales, shifts)]
+        arrs = [(c_void_p * 4)(*([t.data_ptr() for t in lst] + [None])) for lst in keep]
+        y = torch.empty(B, cout, H // 2, W // 2, device=self.device)
+        check(self.L.sylph_bottleneck_even(self._ctx, _ptr(x), B, Cin, H, W, mid, cout, arrs[0], arrs[1], arrs[2], _ptr(y)),
+              "bottleneck_even")
+        return y
+
     def bottleneck_grouped(self, x, ws, scales, shifts, stride=1, groups=32):
         """One ResNeXt bottleneck block (conv2 grouped, weight (mid, mid / groups, 3, 3)) through the backbone's own launches."""
         self._stream()
