@@ -388,10 +388,13 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
     const int oy0 = ty >> 16, ox0 = ty & 0xffff;
     const int PW = sp.pw, NPOS = sp.ph * sp.pw;
     bf16_t* __restrict__ outn = out + (size_t)sp.out_row0 * a.out_ld + n0;
-    // GroupNorm partial sums of this patch about a pivot every lane of a group shares (the conv bias of the group's first
-    // channel: what makes |mean| >> sigma in practice), so that lanes and waves merge by plain additions
+    // GroupNorm partial sums of this patch about a pivot every lane of a group shares, so that lanes and waves merge by plain
+    // additions: the conv bias of the group's first channel (what makes |mean| >> sigma in practice) -- unless the patch's first
+    // position says the group sits far from it (a DC component the eight channels share): then the mean of that position's eight
+    // values.  The one-pass M2 = S2 - S1^2 / N loses (mean - pivot)^2 / sigma^2 of its fp32 precision: 1e-4 relative at 64 sigma.
+    // (The sampled position is one of the patch's 128: even an outlier there lies within sqrt(128) patch-sigma of the patch mean.)
     float gn_n = 0.f, gn_s1 = 0.f, gn_s2 = 0.f;
-    const float gn_pv = sh[0];
+    float gn_pv = sh[0];
 #pragma unroll
     for (int hp = 0; hp < 2; ++hp) {  // 64-row half of the patch
       if (pp + hp > 0) lds_barrier();
@@ -405,6 +408,20 @@ __global__ __launch_bounds__(PNT, 1) void conv_hpipe_kernel(const ConvArgs a) {
           }
       }
       lds_barrier();
+      if (hp == 0 && a.gn_partial) {  // row 0 of the patch, read by all sixteen row-lanes of the group (an LDS broadcast)
+        const float4 lo = *reinterpret_cast<const float4*>(sC + c8 * 8);
+        const float4 hi = *reinterpret_cast<const float4*>(sC + c8 * 8 + 4);
+        float v0[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        float vmin = 3.4e38f, vmax = -3.4e38f, vsum = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float t = v0[e] * sc[e] + sh[e];
+          if (relu) t = t > 0.f ? t : 0.f;
+          vmin = fminf(vmin, t); vmax = fmaxf(vmax, t); vsum += t;
+        }
+        const float m0 = vsum * 0.125f;
+        if (fabsf(m0 - gn_pv) > 4.f * (vmax - vmin)) gn_pv = m0;  // further off than four times the spread of the eight values
+      }
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int rl = rr + 16 * it;
