@@ -610,7 +610,7 @@ int launch_logits_scan(const void* x, int ld, const float2* coef, const void* w,
   const int n_frag = ((cfg.num_classes + 31) / 32) * 16;
   hipLaunchKernelGGL(pack_code_fragments_kernel, dim3((n_frag * 64 + 255) / 256), dim3(256), 0, s, (const bf16_t*)w, (bf16_t*)wf_ws,
                      n_frag);
-  const int grid = n_tiles < 2048 ? n_tiles : 2048;
+  const int grid = n_tiles < HEAD_STREAM_MAX_BLOCKS ? n_tiles : HEAD_STREAM_MAX_BLOCKS;
   hipLaunchKernelGGL(logits_scan_kernel, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)wf_ws, bias_scan,
                      segs, tiles, n_tiles, pred, pred_ld, cfg, buf);
   return (int)hipGetLastError();

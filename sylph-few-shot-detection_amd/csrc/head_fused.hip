@@ -16,6 +16,7 @@
 // and biases only when the block of its next tile differs from the one it holds; everything else -- operand values, K order, rounding
 // points -- is the uniform kernel's, so an image's logits do not depend on which episodes its neighbours belong to.
 #include "gfx950.h"
+#include "kernels.h"
 
 namespace sylph {
 
@@ -278,7 +279,7 @@ int launch_gn_pred_taps(const void* x, int ld, const float2* coef, const void* w
                         hipStream_t s) {
   const int sw = (3 * cp + 3) & ~3;
   if (cp < 1 || 3 * sw > 64 || n_tiles <= 0) return -1;
-  const int grid = n_tiles < 2048 ? n_tiles : 2048;
+  const int grid = n_tiles < HEAD_STREAM_MAX_BLOCKS ? n_tiles : HEAD_STREAM_MAX_BLOCKS;
   hipLaunchKernelGGL(gn_taps_kernel<2>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w_taps, planes_ws, sw, plane_rows,
                      segs, tiles, n_tiles);
   hipLaunchKernelGGL(tap_gather_kernel, dim3(n_tiles), dim3(128), 0, s, planes_ws, sw, plane_rows, cp, bias, relu_nch, mul_nch, out, out_ld, segs,
@@ -292,7 +293,7 @@ int launch_gn_logits(const void* x, int ld, const float2* coef, const void* w, c
                      const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s) {
   if (N > 32 || out_ld < N || (out_ld & 3) != 0 || n_tiles <= 0) return -1;
   const int want = n_tiles;  // one block = 4 row groups = one 128-row tile per sweep
-  const int grid = want < 2048 ? want : 2048;
+  const int grid = want < HEAD_STREAM_MAX_BLOCKS ? want : HEAD_STREAM_MAX_BLOCKS;
   hipLaunchKernelGGL(gn_logits_kernel<false>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, N, nullptr, out,
                      out_ld, segs, tiles, n_tiles);
   return (int)hipGetLastError();
@@ -302,7 +303,7 @@ int launch_gn_logits(const void* x, int ld, const float2* coef, const void* w, c
 int launch_gn_logits_episodes(const void* x, int ld, const float2* coef, const void* w, const float* bias, const int* seg_row0, float* out,
                               int out_ld, const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s) {
   if (!seg_row0 || (out_ld & 3) != 0 || out_ld <= 0 || n_tiles <= 0) return -1;
-  const int grid = n_tiles < 2048 ? n_tiles : 2048;
+  const int grid = n_tiles < HEAD_STREAM_MAX_BLOCKS ? n_tiles : HEAD_STREAM_MAX_BLOCKS;
   hipLaunchKernelGGL(gn_logits_kernel<true>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, 32, seg_row0, out,
                      out_ld, segs, tiles, n_tiles);
   return (int)hipGetLastError();

@@ -10,6 +10,11 @@ struct RowSeg { int row0, nrows; };                 // a run of rows (one GroupN
 struct ResizeDesc { const unsigned char* src; int h, w, new_h, new_w; int hb_off, hk_off, vb_off, vk_off, ksh, ksv; };
 
 constexpr int GN_ROWS_PER_CHUNK = 256;
+// Block cap of the head's persistent streaming kernels -- gn_logits_kernel<false / true> and gn_taps_kernel (head_fused.hip),
+// logits_scan_kernel (detect.hip): each launches min(n_tiles, HEAD_STREAM_MAX_BLOCKS) blocks over the 128-row tile table, so above the
+// cap a wave takes several row groups and carries its coefficient table, code fragments and candidate list from one to the next.
+// tests/test_head_sweeps_gpu.py pins that regime at small shapes and restates the value: change both together.
+constexpr int HEAD_STREAM_MAX_BLOCKS = 2048;
 // a GroupNorm sample (= conv segment) whose statistics were left by the conv epilogue as per-M-tile partials
 struct GnSeg { int row0, nrows, tile0, ntiles; };
 
