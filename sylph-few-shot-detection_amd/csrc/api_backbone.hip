@@ -46,9 +46,12 @@ int ensure_pyramid(sylph_ctx* c, Plan* P) {
   return 0;
 }
 
-// Patch list of the bottleneck kernels (bottleneck.hip, conv_rw3.hip): ph x pw patches of B images of H x W positions
+// One launch of a kernel that walks a patch table (bottleneck.hip, conv_rw3.hip, conv_rw64.hip), appended to `ops`: the table of the
+// ph x pw patches of B images of H x W positions is uploaded and handed to the kernel in a.bk / a.n_tiles
 // even_rp != 0: the stride-2-output form (BkTile): ph x pw tiles of the H/2 x W/2 output map, t1 row pitch even_rp
-static int upload_bk_tiles(sylph_ctx* c, int B, int H, int W, int ph, int pw, BottleneckArgs* ba, int even_rp = 0) {
+template <typename Args>
+static int add_patch_kernel(sylph_ctx* c, std::vector<OpFn>& ops, const char* kern, double flops, int (*launch)(const Args&, hipStream_t), Args a,
+                            int B, int H, int W, int ph, int pw, int even_rp = 0) {
   std::vector<BkTile> bt;
   for (int b = 0; b < B; ++b) {
     if (even_rp) {
@@ -63,134 +66,206 @@ static int upload_bk_tiles(sylph_ctx* c, int B, int H, int W, int ph, int pw, Bo
   }
   void* btd = nullptr;
   RET(upload(c, &btd, bt.data(), bt.size() * sizeof(BkTile)));
-  ba->bk = (const BkTile*)btd;
-  ba->n_tiles = (int)bt.size();
+  a.bk = (const BkTile*)btd;
+  a.n_tiles = (int)bt.size();
+  ops.push_back([=](hipStream_t s) { return timed_op(c, kern, flops, s, [=](hipStream_t st) { return launch(a, st); }); });
   return 0;
 }
 
-// One ResNet bottleneck block (detectron2 BottleneckBlock: 1x1 -> 3x3 -> 1x1, FrozenBN folded, residual / projection shortcut)
-// appended to `ops`: X [B][Hin*Win][Cin] -> Y [B][Ho*Wo][cout].  t1 / t2 / sc are scratch activations of the stage.
-// Shared by build_backbone and the single-block parity entry sylph_bottleneck, so both run the same kernels.
+// Below this many patches a launch of conv_rw64 (one persistent block per CU, weights loaded into registers first) is left to the
+// generic route.  Measured at 200 x 336 (272 patches per image, profiles/resnet_basic_conv64.txt): 1 image a tie, 2 and 4 images
+// (544 / 1 088 patches: 3 and 5 rounds over the 256 CUs, the last one nearly empty) 4-28 % behind conv_igemm's 64-row tiles, 8 images
+// (2 176) 3-14 % ahead, 64 and 192 images 1.4-1.55 x.
+static const long RW64_MIN_PATCHES = 2048;
 
-static int fuse_bottleneck_knob() {
-  static const int v = getenv("SYLPH_FUSE_BOTTLENECK") ? atoi(getenv("SYLPH_FUSE_BOTTLENECK")) : 1;
-  return v;
+// The kernel of one dense 3x3 pad-1 conv L + FrozenBN [+ residual] [+ ReLU] on B images of H x W (Conv3Route).  Both dedicated kernels
+// are bf16, stride 1, and need the layer's scale and shift:
+//   conv_rw3   128 -> 128, FrozenBN + ReLU without a residual (the callers ask for layers with that epilogue only): res3 conv2 of the bottleneck nets, conv1 of
+//              the res3 identity BasicBlocks.  Launches of at least 256 x 120 positions; 800 x 1344: 100 x 168 -> 10 x 12 patches (halo
+//              12 x 14 = 168 rows).  SYLPH_CONV_RW3: 0 off, 2 any launch.
+//   conv_rw64  64 -> 64: the res2 convs of R-18 / R-34.  Launches of at least RW64_MIN_PATCHES patches; 200 x 336 -> 12 x 21 patches (halo
+//              14 x 23 = 322 pixels).  SYLPH_CONV_RW64: 0 off, 2 any launch; read per pick so that one process can build both.
+Conv3Route pick_conv3_route(const sylph_ctx* c, const ConvLayer& L, int B, int H, int W, int stride) {
+  Conv3Route r;
+  if (c->dt != DT_BF16 || L.groups != 1 || L.KH != 3 || L.KW != 3 || stride != 1 || !L.scale || !L.shift) return r;
+  const size_t pos = (size_t)B * H * W;
+  int ph = 0, pw = 0;
+  if (const int on = knob::conv_rw3(); on && L.Cin == 128 && L.Cout == 128 && L.Cout_pad == 128 &&
+      pos * 256 < ((size_t)1 << 31) &&  // (2 GiB buffer descriptors)
+      (on == 2 || pos >= (size_t)256 * 120)) {
+    pick_patch(H, W, 128, 184, 2, &ph, &pw);
+    if (conv_rw3_patch_ok(ph, pw)) { r.kind = Conv3Kind::rw3; r.ph = ph; r.pw = pw; }
+    return r;
+  }
+  if (const int on = knob::conv_rw64(); on && L.Cin == 64 && L.Cout == 64 && L.Cout_pad == 64 && W < 65536 &&
+      pos * 128 <= 0xff000000u) {  // (32-bit byte offsets into descriptors of the tensor's real size)
+    pick_patch(H, W, 256, 352, 2, &ph, &pw);
+    const long n = (long)B * ((H + ph - 1) / ph) * ((W + pw - 1) / pw);
+    if (conv_rw64_patch_ok(ph, pw) && (on == 2 || n >= RW64_MIN_PATCHES)) { r.kind = Conv3Kind::rw64; r.ph = ph; r.pw = pw; }
+  }
+  return r;
 }
 
-// res2 identity blocks (C 256, mid 64, stride 1, no projection), bf16: the block add_bottleneck builds as ONE fused kernel
-bool bottleneck_takes_fuse_id(const sylph_ctx* c, const sylph_ctx::Block& blk, int B, int Cin, int Hin, int Win, int stride, int mid, int cout) {
-  return fuse_bottleneck_knob() && blk.c2.groups == 1 && c->dt == DT_BF16 && !blk.has_sc && stride == 1 && mid == 64 && Cin == 256 && cout == 256 &&
-         blk.c1.Cout_pad == 64 && blk.c2.Cout_pad == 64 && blk.c3.Cout_pad == 256 &&
-         (size_t)Hin * Win * 512 < ((size_t)1 << 32) && (size_t)B * Hin * Win < ((size_t)1 << 31);  // 32-bit byte offsets inside ONE image (64-bit image base)
+// One such conv appended to `ops` by its route: x [B][H * W][Cin] -> y [B][Ho * Wo][Cout] (res: same shape as y)
+static int add_conv3x3(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const Conv3Route& r, int B, int H, int W, int stride, const void* x,
+                       const void* res, void* y, int relu) {
+  switch (r.kind) {
+    case Conv3Kind::rw3: {
+      if (res || !relu) return fail("internal: conv_rw3 is conv + FrozenBN + ReLU");
+      BottleneckArgs ba;
+      memset(&ba, 0, sizeof(ba));
+      ba.x = x; ba.y = y;
+      ba.w2 = (const __bf16*)L.w; ba.s2 = L.scale; ba.b2 = L.shift;
+      return add_patch_kernel(c, ops, "conv_rw3_kernel", 2.0 * (double)B * H * W * 128.0 * 1152.0, launch_conv_rw3, ba, B, H, W, r.ph, r.pw);
+    }
+    case Conv3Kind::rw64: {
+      ConvRw64Args ra;
+      memset(&ra, 0, sizeof(ra));
+      ra.x = x; ra.y = y; ra.res = res; ra.w = (const __bf16*)L.w; ra.scale = L.scale; ra.shift = L.shift;
+      ra.bytes = (unsigned)((size_t)B * H * W * 128); ra.relu = relu ? 1 : 0;
+      return add_patch_kernel(c, ops, "conv_rw64_kernel", 2.0 * (double)B * H * W * 64.0 * 576.0, launch_conv_rw64, ra, B, H, W, r.ph, r.pw);
+    }
+    case Conv3Kind::generic: break;
+  }
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  ConvOpts o; o.stride = stride; o.pad = 1; o.relu_nch = relu ? (1 << 30) : 0;
+  if (res) { o.res = res; o.res_ld = L.Cout; o.res_mode = 1; }
+  return add_conv(c, ops, L, x, L.Cin, y, L.Cout, image_segs(B, H, W, Ho, Wo), o);
 }
 
-int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win,
-                          int stride, int mid, int cout, void* Y, const BkScratch& scr, int flags) {
-  const DType dt = c->dt;
-  const bool even_out = (flags & BK_EVEN_OUT) != 0;
-  // the producer already dropped the rows a stride-2 1x1 skips: stride is 1 here, the routes are chosen for the strided layer
-  const int route_stride = (flags & BK_IN_COMPACT) ? 2 : 0;
-  if (even_out && (!bottleneck_takes_fuse_id(c, blk, B, Cin, Hin, Win, stride, mid, cout) || (Hin & 1) || (Win & 1)))
-    return fail("the stride-2-output bottleneck is the fused bf16 identity block (C 256, mid 64) on a map of even height and width");
-  const int s1 = c->cfg.stride_in_1x1 ? stride : 1, s3 = c->cfg.stride_in_1x1 ? 1 : stride;
-  const int H1 = (Hin - 1) / s1 + 1, W1 = (Win - 1) / s1 + 1;
-  const int Ho = (Hin - 1) / stride + 1, Wo = (Win - 1) / stride + 1;
-  void *t1 = scr.t1, *t2 = scr.t2, *sc = scr.sc;
-  if (blk.c2.groups > 1) {
+// One 3x3 stride-1 pad-1 conv 64 -> 64 + FrozenBN [+ residual] [+ ReLU] on dense images x [B][H * W][64] -> y, appended to `ops`:
+// conv_rw64.hip or add_conv (pick_conv3_route).  The parity entry sylph_conv3x3_c64; add_basic_block builds its convs the same way.
+int add_conv3x3_c64(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, int B, int H, int W, const void* x, const void* res, void* y, int relu) {
+  return add_conv3x3(c, ops, L, pick_conv3_route(c, L, B, H, W, 1), B, H, W, 1, x, res, y, relu);
+}
+
+// How one bottleneck block is built (BlockRoute).  Hin x Win is X's map; with BK_IN_COMPACT `stride` is already 1.
+BlockRoute pick_block_route(const sylph_ctx* c, const sylph_ctx::Block& blk, int B, int Cin, int Hin, int Win, int stride, int mid, int cout, int flags) {
+  BlockRoute r;
+  r.chunk = B;
+  r.s1 = c->cfg.stride_in_1x1 ? stride : 1; r.s3 = c->cfg.stride_in_1x1 ? 1 : stride;
+  r.H1 = (Hin - 1) / r.s1 + 1; r.W1 = (Win - 1) / r.s1 + 1;
+  r.Ho = (Hin - 1) / stride + 1; r.Wo = (Win - 1) / stride + 1;
+  // (a grouped conv2 -- ResNeXt -- never takes the fused R-50 kernels nor conv_rw3: they compute a dense 3x3)
+  const bool dense2 = blk.c2.groups == 1;
+  // The two fused res2 kernels (bottleneck.hip), bf16: the two 64-channel intermediates and the second read of x never reach HBM
+  // (identity block: 2 048 -> 1 024 B per position).  32-bit byte offsets inside ONE image (64-bit image base).
+  const bool fused64 = knob::fuse_bottleneck() && dense2 && c->dt == DT_BF16 && stride == 1 && mid == 64 && cout == 256 && blk.c1.Cout_pad == 64 &&
+                       blk.c2.Cout_pad == 64 && (size_t)Hin * Win * 512 < ((size_t)1 << 32) && (size_t)B * Hin * Win < ((size_t)1 << 31);
+  const bool fuse_id = fused64 && !blk.has_sc && Cin == 256 && blk.c3.Cout_pad == 256;
+  const bool fuse_pr = fused64 && blk.fused_sc && Cin == 64 && blk.c3sc.Cout_pad == 256 && blk.c3sc.Cin == 128 && !blk.c3sc.scale;
+  r.tail_ok = fuse_id && (Hin & 1) == 0 && (Win & 1) == 0;
+  if ((flags & BK_EVEN_OUT) && !r.tail_ok) {
+    r.refuse = "the stride-2-output bottleneck is the fused bf16 identity block (C 256, mid 64) on a map of even height and width";
+    return r;
+  }
+  if (!dense2) {
     // ResNeXt: the blocks are up to 8x wider than R-50's (X-101-32x8d res3.0: t1 = 512 channels at res2 resolution, 34 M elements per
     // image), so at large batches whole-tensor offsets of the 1x1 kernels (conv_igemm's 31-bit element offsets, conv_pw's 32-bit residual
     // byte offsets) would overflow.  Such a block is built as a sequence of image chunks, each small enough that every tensor of the chunk
     // stays below 2^31 elements; every chunk runs the block's own launches on its slice of the (dense, image-major) buffers.
-    const long per_img = std::max({(long)Hin * Win * Cin, (long)H1 * W1 * mid, (long)Ho * Wo * mid, (long)Ho * Wo * cout});
+    const long per_img = std::max({(long)Hin * Win * Cin, (long)r.H1 * r.W1 * mid, (long)r.Ho * r.Wo * mid, (long)r.Ho * r.Wo * cout});
     const int nb = (int)std::min<long>(B, ((1L << 31) - 1) / per_img);
-    if (nb < 1) return fail("image too large for the ResNeXt block kernels: " + std::to_string(per_img) + " elements per image");
+    if (nb < 1) {
+      r.refuse = "image too large for the ResNeXt block kernels: " + std::to_string(per_img) + " elements per image";
+      return r;
+    }
     if (nb < B) {
-      const int nch = (B + nb - 1) / nb, cb = (B + nch - 1) / nch;
-      const size_t e = c->esz();
-      for (int b0 = 0; b0 < B; b0 += cb) {
-        const int n = std::min(cb, B - b0);
-        BkScratch sub{(char*)t1 + (size_t)b0 * H1 * W1 * mid * e, (char*)t2 + (size_t)b0 * Ho * Wo * mid * e,
-                      (char*)sc + (size_t)b0 * Ho * Wo * cout * e, scr.trash};
-        RET(add_bottleneck(c, ops, blk, n, (const char*)X + (size_t)b0 * Hin * Win * Cin * e, Cin, Hin, Win, stride, mid, cout,
-                           (char*)Y + (size_t)b0 * Ho * Wo * cout * e, sub, flags));
-      }
-      return 0;
+      const int nch = (B + nb - 1) / nb;
+      r.chunk = (B + nch - 1) / nch;
+      return r;
     }
   }
-  // res2 identity blocks (C 256, mid 64, stride 1, no projection), bf16: ONE fused kernel (bottleneck.hip): the two
-  // 64-channel intermediates and the second read of x never reach HBM (2 048 -> 1 024 B per position)
-  const int fuse_bn = fuse_bottleneck_knob();
-  // (a grouped conv2 -- ResNeXt -- never takes the fused R-50 kernels nor conv_rw3: they compute a dense 3x3)
-  const bool dense2 = blk.c2.groups == 1;
-  const bool fuse_id = bottleneck_takes_fuse_id(c, blk, B, Cin, Hin, Win, stride, mid, cout);
-  // first block of res2 (64 -> 64 -> 64 -> 256, projection folded into conv3's GEMM, stride 1): one fused kernel too
-  const bool fuse_pr = fuse_bn && dense2 && dt == DT_BF16 && blk.fused_sc && stride == 1 && mid == 64 && Cin == 64 && cout == 256 &&
-                       blk.c1.Cout_pad == 64 && blk.c2.Cout_pad == 64 && blk.c3sc.Cout_pad == 256 && blk.c3sc.Cin == 128 && !blk.c3sc.scale;
-  if (fuse_id || (fuse_pr && (size_t)Hin * Win * 512 < ((size_t)1 << 32) && (size_t)B * Hin * Win < ((size_t)1 << 31))) {  // 32-bit byte offsets inside ONE image (64-bit image base)
+  if (fuse_id || fuse_pr) {
+    r.form = fuse_pr ? BlockForm::fused_proj : (flags & BK_EVEN_OUT) ? BlockForm::fused_id_even : BlockForm::fused_id;
+    return r;
+  }
+  r.form = BlockForm::chain;
+  r.fused_sc = blk.fused_sc;
+  if (!dense2) {
+    // ResNeXt conv2: grouped 3x3 (stride s3) + FrozenBN + ReLU, conv_group.hip, on the dense images t1 [B][H1 * W1][mid] -> t2
+    const int cpg = mid / blk.c2.groups;
+    r.conv2 = Conv2Form::grouped;
+    if (blk.c2.Cin != mid || blk.c2.Cout != mid || mid % 64 != 0 || cpg < 4 || cpg > 64 || (cpg & (cpg - 1)) != 0)
+      r.refuse = "internal: grouped conv2 shape";
+    else if ((long)r.H1 * r.W1 * mid >= (1L << 31))
+      r.refuse = "image too large for conv_group: " + std::to_string((long)r.H1 * r.W1 * mid) + " elements per image exceed its 31-bit offsets";
+    return r;
+  }
+  // conv_rw3 where the layer picker gives it; a 64-channel conv2 (the res2 blocks with SYLPH_FUSE_BOTTLENECK=0) stays with add_conv:
+  // conv_rw64 is the BasicBlock nets' kernel
+  const Conv3Route r2 = pick_conv3_route(c, blk.c2, B, r.H1, r.W1, r.s3);
+  if (r2.kind == Conv3Kind::rw3) { r.conv2 = Conv2Form::rw3; r.ph = r2.ph; r.pw = r2.pw; }
+  return r;
+}
+
+// One ResNet bottleneck block (detectron2 BottleneckBlock: 1x1 -> 3x3 -> 1x1, FrozenBN folded, residual / projection shortcut)
+// appended to `ops` as pick_block_route says: X [B][Hin*Win][Cin] -> Y [B][Ho*Wo][cout].  t1 / t2 / sc are scratch activations of the stage.
+// Shared by build_backbone and the single-block parity entry sylph_bottleneck, so both run the same kernels.
+int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win,
+                          int stride, int mid, int cout, void* Y, const BkScratch& scr, int flags) {
+  const BlockRoute r = pick_block_route(c, blk, B, Cin, Hin, Win, stride, mid, cout, flags);
+  if (!r.refuse.empty()) return fail(r.refuse);
+  const DType dt = c->dt;
+  const int H1 = r.H1, W1 = r.W1, Ho = r.Ho, Wo = r.Wo;
+  void *t1 = scr.t1, *t2 = scr.t2, *sc = scr.sc;
+  if (r.chunk < B) {  // (ResNeXt at a large batch) slice by slice, each with its own route
+    const size_t e = c->esz();
+    for (int b0 = 0; b0 < B; b0 += r.chunk) {
+      const int n = std::min(r.chunk, B - b0);
+      BkScratch sub{(char*)t1 + (size_t)b0 * H1 * W1 * mid * e, (char*)t2 + (size_t)b0 * Ho * Wo * mid * e,
+                    (char*)sc + (size_t)b0 * Ho * Wo * cout * e, scr.trash};
+      RET(add_bottleneck(c, ops, blk, n, (const char*)X + (size_t)b0 * Hin * Win * Cin * e, Cin, Hin, Win, stride, mid, cout,
+                         (char*)Y + (size_t)b0 * Ho * Wo * cout * e, sub, flags));
+    }
+    return 0;
+  }
+  if (r.form != BlockForm::chain) {
+    const bool id = r.form != BlockForm::fused_proj;
     BottleneckArgs ba;
     memset(&ba, 0, sizeof(ba));
     ba.x = X; ba.y = Y;
-    ba.w1 = (const __bf16*)blk.c1.w; ba.w2 = (const __bf16*)blk.c2.w; ba.w3 = (const __bf16*)(fuse_id ? blk.c3.w : blk.c3sc.w);
+    ba.w1 = (const __bf16*)blk.c1.w; ba.w2 = (const __bf16*)blk.c2.w; ba.w3 = (const __bf16*)(id ? blk.c3.w : blk.c3sc.w);
     ba.s1 = blk.c1.scale; ba.b1 = blk.c1.shift; ba.s2 = blk.c2.scale; ba.b2 = blk.c2.shift;
-    ba.s3 = fuse_id ? blk.c3.scale : nullptr; ba.b3 = fuse_id ? blk.c3.shift : blk.c3sc.shift;
+    ba.s3 = id ? blk.c3.scale : nullptr; ba.b3 = id ? blk.c3.shift : blk.c3sc.shift;
     ba.zeros = c->zeros;
     if (!*scr.trash) RET(c->dalloc(scr.trash, (size_t)1024 * 256 * 128));  // per-thread trash slots (grid <= CU count <= 1024)
     ba.trash = *scr.trash;
     int ph, pw;
-    // (A 64-position variant with a double-buffered halo was measured in round 3: 1.56 vs 1.31 ms per launch -- 2.2 x as many tiles pay
-    // the per-tile fixed costs; it left the tree in round 5, see bottleneck.hip.)
-    const int bk_small = 0;
-    if (even_out) {
+    if (r.form == BlockForm::fused_id_even) {
       // outputs at (2 i, 2 j) only, compact: conv1 on every position (each one is in some output's 3x3 window), conv2 / conv3 on a quarter
       int rp;
       bottleneck64_even_patch(Hin, Win, &ph, &pw, &rp);
-      RET(upload_bk_tiles(c, B, Hin, Win, ph, pw, &ba, rp));
       const double fl = 2.0 * (double)B * ((double)Hin * Win * 256.0 * 64 + (double)(Hin / 2) * (Win / 2) * (64.0 * 576 + 64.0 * 256));
-      ops.push_back([=](hipStream_t s) { return timed_op(c, "bottleneck64_kernel", fl, s, [=](hipStream_t st) { return launch_bottleneck64_even(ba, st); }); });
-      return 0;
+      return add_patch_kernel(c, ops, "bottleneck64_kernel", fl, launch_bottleneck64_even, ba, B, Hin, Win, ph, pw, rp);
     }
     pick_patch(Hin, Win, 128, 184, 2, &ph, &pw);
-    RET(upload_bk_tiles(c, B, Hin, Win, ph, pw, &ba));
-    const double fl = 2.0 * (double)B * Hin * Win * (fuse_id ? (256.0 * 64 + 64.0 * 576 + 64.0 * 256) : (64.0 * 64 + 64.0 * 576 + 128.0 * 256));
-    if (fuse_id) ops.push_back([=](hipStream_t s) { return timed_op(c, "bottleneck64_kernel", fl, s, [=](hipStream_t st) { return launch_bottleneck64(ba, bk_small, st); }); });
-    else ops.push_back([=](hipStream_t s) { return timed_op(c, "bottleneck64p_kernel", fl, s, [=](hipStream_t st) { return launch_bottleneck64p(ba, st); }); });
-    return 0;
+    const double fl = 2.0 * (double)B * Hin * Win * (id ? (256.0 * 64 + 64.0 * 576 + 64.0 * 256) : (64.0 * 64 + 64.0 * 576 + 128.0 * 256));
+    if (id) return add_patch_kernel(c, ops, "bottleneck64_kernel", fl, launch_bottleneck64, ba, B, Hin, Win, ph, pw);
+    return add_patch_kernel(c, ops, "bottleneck64p_kernel", fl, launch_bottleneck64p, ba, B, Hin, Win, ph, pw);
   }
-  ConvOpts o1; o1.stride = s1; o1.relu_nch = 1 << 30; o1.route_stride = route_stride;
+  // the producer already dropped the rows a stride-2 1x1 skips: stride is 1 here, the routes are chosen for the strided layer
+  const int route_stride = (flags & BK_IN_COMPACT) ? 2 : 0;
+  ConvOpts o1; o1.stride = r.s1; o1.relu_nch = 1 << 30; o1.route_stride = route_stride;
   RET(add_conv(c, ops, blk.c1, X, Cin, t1, mid, image_segs(B, Hin, Win, H1, W1), o1));
-  // res3 conv2 (3x3, 128 -> 128, stride 1), bf16: weights in registers, LDS holds only the activation halo (conv_rw3.hip)
-  static const int rw3_on = getenv("SYLPH_CONV_RW3") ? atoi(getenv("SYLPH_CONV_RW3")) : 1;
-  const bool rw3 = rw3_on && dense2 && dt == DT_BF16 && mid == 128 && s3 == 1 && blk.c2.Cin == 128 && blk.c2.Cout_pad == 128 && blk.c2.KH == 3 && blk.c2.KW == 3 &&
-                   blk.c2.scale && blk.c2.shift && (size_t)B * H1 * W1 * 256 < ((size_t)1 << 31) &&  // (2 GiB buffer descriptors)
-                   (rw3_on == 2 || (size_t)B * H1 * W1 >= (size_t)256 * 120);
-  int ph = 0, pw = 0;
-  if (rw3) pick_patch(H1, W1, 128, 184, 2, &ph, &pw);  // 100 x 168 -> 10 x 12 patches (halo 12 x 14 = 168 rows)
-  if (!dense2) {
-    // ResNeXt conv2: grouped 3x3 (stride s3) + FrozenBN + ReLU, conv_group.hip, on the dense images t1 [B][H1 * W1][mid] -> t2
-    const int cpg = mid / blk.c2.groups;
-    if (blk.c2.Cin != mid || blk.c2.Cout != mid || mid % 64 != 0 || cpg < 4 || cpg > 64 || (cpg & (cpg - 1)) != 0)
-      return fail("internal: grouped conv2 shape");
-    if ((long)H1 * W1 * mid >= (1L << 31))
-      return fail("image too large for conv_group: " + std::to_string((long)H1 * W1 * mid) + " elements per image exceed its 31-bit offsets");
-    GroupConvArgs ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.x = t1; ga.y = t2; ga.wt = blk.c2.w; ga.scale = blk.c2.scale; ga.shift = blk.c2.shift;
-    ga.B = B; ga.C = mid; ga.cpg = cpg; ga.Hin = H1; ga.Win = W1; ga.Ho = Ho; ga.Wo = Wo; ga.stride = s3; ga.relu = 1;
-    const double fl = 2.0 * (double)B * Ho * Wo * mid * 9.0 * cpg;
-    ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_group_kernel", fl, s, [=](hipStream_t st) { return launch_conv_group(dt, ga, st); }); });
-  } else if (rw3 && conv_rw3_patch_ok(ph, pw)) {
-    BottleneckArgs ba;
-    memset(&ba, 0, sizeof(ba));
-    ba.x = t1; ba.y = t2;
-    ba.w2 = (const __bf16*)blk.c2.w; ba.s2 = blk.c2.scale; ba.b2 = blk.c2.shift;
-    RET(upload_bk_tiles(c, B, H1, W1, ph, pw, &ba));
-    const double fl = 2.0 * (double)B * H1 * W1 * 128.0 * 1152.0;
-    ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_rw3_kernel", fl, s, [=](hipStream_t st) { return launch_conv_rw3(ba, st); }); });
-  } else {
-    ConvOpts o2; o2.stride = s3; o2.pad = 1; o2.relu_nch = 1 << 30;
-    RET(add_conv(c, ops, blk.c2, t1, mid, t2, mid, image_segs(B, H1, W1, Ho, Wo), o2));
+  switch (r.conv2) {
+    case Conv2Form::grouped: {
+      GroupConvArgs ga;
+      memset(&ga, 0, sizeof(ga));
+      ga.x = t1; ga.y = t2; ga.wt = blk.c2.w; ga.scale = blk.c2.scale; ga.shift = blk.c2.shift;
+      ga.B = B; ga.C = mid; ga.cpg = mid / blk.c2.groups; ga.Hin = H1; ga.Win = W1; ga.Ho = Ho; ga.Wo = Wo; ga.stride = r.s3; ga.relu = 1;
+      const double fl = 2.0 * (double)B * Ho * Wo * mid * 9.0 * ga.cpg;
+      ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_group_kernel", fl, s, [=](hipStream_t st) { return launch_conv_group(dt, ga, st); }); });
+      break;
+    }
+    case Conv2Form::rw3:  // res3 conv2 (3x3, 128 -> 128, stride 1), bf16: weights in registers, LDS holds only the activation halo (conv_rw3.hip)
+      RET(add_conv3x3(c, ops, blk.c2, Conv3Route{Conv3Kind::rw3, r.ph, r.pw}, B, H1, W1, r.s3, t1, nullptr, t2, 1));
+      break;
+    case Conv2Form::generic:
+      RET(add_conv3x3(c, ops, blk.c2, Conv3Route{}, B, H1, W1, r.s3, t1, nullptr, t2, 1));
+      break;
   }
-  if (blk.fused_sc) {
+  if (r.fused_sc) {
     // conv3 + projection shortcut as ONE pointwise GEMM over K = [t2 | X(strided)]: the shortcut
     // tensor is never written to / re-read from HBM
     std::vector<SegDesc> sg = image_segs(B, Ho, Wo, Ho, Wo);
@@ -210,87 +285,34 @@ int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block&
   return 0;
 }
 
-// Below this many patches a launch of conv_rw64 (one persistent block per CU, weights loaded into registers first) is left to the
-// generic route.  Measured at 200 x 336 (272 patches per image, profiles/resnet_basic_conv64.txt): 1 image a tie, 2 and 4 images
-// (544 / 1 088 patches: 3 and 5 rounds over the 256 CUs, the last one nearly empty) 4-28 % behind conv_igemm's 64-row tiles, 8 images
-// (2 176) 3-14 % ahead, 64 and 192 images 1.4-1.55 x.
-static const long RW64_MIN_PATCHES = 2048;
-
-// One 3x3 stride-1 pad-1 conv 64 -> 64 + FrozenBN [+ residual] [+ ReLU] on dense images x [B][H * W][64] -> y, appended to `ops`:
-// conv_rw64.hip in bf16 (SYLPH_CONV_RW64: 0 off, 1 auto = launches of at least RW64_MIN_PATCHES patches, 2 always; read per build so
-// that one process can build both), add_conv / pick_conv_route otherwise.  Shared by add_basic_block and the parity entry
-// sylph_conv3x3_c64.
-int add_conv3x3_c64(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, int B, int H, int W, const void* x, const void* res, void* y, int relu) {
-  const int rw64_on = getenv("SYLPH_CONV_RW64") ? atoi(getenv("SYLPH_CONV_RW64")) : 1;
-  const size_t bytes = (size_t)B * H * W * 128;
-  int ph = 0, pw = 0;
-  bool rw64 = rw64_on && c->dt == DT_BF16 && L.groups == 1 && L.Cin == 64 && L.Cout == 64 && L.Cout_pad == 64 && L.KH == 3 && L.KW == 3 &&
-              L.scale && L.shift && W < 65536 && bytes <= 0xff000000u;  // (32-bit byte offsets into descriptors of the tensor's real size)
-  if (rw64) {
-    pick_patch(H, W, 256, 352, 2, &ph, &pw);  // 200 x 336 -> 12 x 21 patches (halo 14 x 23 = 322 pixels)
-    const long n = (long)B * ((H + ph - 1) / ph) * ((W + pw - 1) / pw);
-    rw64 = conv_rw64_patch_ok(ph, pw) && (rw64_on == 2 || n >= RW64_MIN_PATCHES);
-  }
-  if (!rw64) {
-    ConvOpts o; o.pad = 1; o.relu_nch = relu ? (1 << 30) : 0;
-    if (res) { o.res = res; o.res_ld = 64; o.res_mode = 1; }
-    return add_conv(c, ops, L, x, 64, y, 64, image_segs(B, H, W, H, W), o);
-  }
-  BottleneckArgs ba;  // (the patch table of the bottleneck kernels)
-  memset(&ba, 0, sizeof(ba));
-  RET(upload_bk_tiles(c, B, H, W, ph, pw, &ba));
-  ConvRw64Args ra;
-  memset(&ra, 0, sizeof(ra));
-  ra.x = x; ra.y = y; ra.res = res; ra.w = (const __bf16*)L.w; ra.scale = L.scale; ra.shift = L.shift;
-  ra.bk = ba.bk; ra.n_tiles = ba.n_tiles; ra.bytes = (unsigned)bytes; ra.relu = relu ? 1 : 0;
-  const double fl = 2.0 * (double)B * H * W * 64.0 * 576.0;
-  ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_rw64_kernel", fl, s, [=](hipStream_t st) { return launch_conv_rw64(ra, st); }); });
-  return 0;
-}
-
 // One ResNet BasicBlock (detectron2 BasicBlock of R-18 / R-34: 3x3 (stride) -> 3x3, FrozenBN folded, identity or 1x1 projection
 // shortcut) appended to `ops`: X [B][Hin*Win][Cin] -> Y [B][Ho*Wo][cout]; scr.t1 (the block's intermediate) and scr.sc (the projected
 // shortcut) hold B * Ho * Wo * cout elements.  Shared by build_backbone and the parity entry sylph_basic_block.
-//   t = relu(bn1(conv1(x)))        res2: conv_rw64; res3 identity blocks: conv_rw3 (add_bottleneck's conditions); else add_conv
+//   t = relu(bn1(conv1(x)))        res2: conv_rw64; res3 identity blocks: conv_rw3; else add_conv (pick_conv3_route)
 //   sc = x | bn(shortcut(x))       a launch of its own (1x1, stride 2)
 //   y = relu(bn2(conv2(t)) + sc)   res2: conv_rw64 with the residual; else add_conv (conv_igemm halo tiles: the only 3x3 route with a residual)
 int add_basic_block(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win,
                     int stride, int cout, void* Y, const BkScratch& scr) {
-  const DType dt = c->dt;
   const int Ho = (Hin - 1) / stride + 1, Wo = (Win - 1) / stride + 1;
   void *t = scr.t1, *sc = scr.sc;
   if (!blk.has_sc && (Cin != cout || stride != 1)) return fail("internal: BasicBlock without a shortcut must keep its shape");
   if (blk.c1.Cin != Cin || blk.c1.Cout != cout || blk.c2.Cin != cout || blk.c2.Cout != cout || blk.c1.KH != 3 || blk.c2.KH != 3)
     return fail("internal: BasicBlock shape");
-  const bool c64 = Cin == 64 && cout == 64 && stride == 1;
-  static const int rw3_on = getenv("SYLPH_CONV_RW3") ? atoi(getenv("SYLPH_CONV_RW3")) : 1;
-  const bool rw3 = rw3_on && dt == DT_BF16 && stride == 1 && Cin == 128 && cout == 128 && blk.c1.Cout_pad == 128 && blk.c1.KW == 3 && blk.c1.scale &&
-                   blk.c1.shift && (size_t)B * Hin * Win * 256 < ((size_t)1 << 31) && (rw3_on == 2 || (size_t)B * Hin * Win >= (size_t)256 * 120);
-  int ph = 0, pw = 0;
-  if (rw3) pick_patch(Hin, Win, 128, 184, 2, &ph, &pw);
-  if (c64) {
-    RET(add_conv3x3_c64(c, ops, blk.c1, B, Hin, Win, X, nullptr, t, 1));
-  } else if (rw3 && conv_rw3_patch_ok(ph, pw)) {
-    BottleneckArgs ba;
-    memset(&ba, 0, sizeof(ba));
-    ba.x = X; ba.y = t;
-    ba.w2 = (const __bf16*)blk.c1.w; ba.s2 = blk.c1.scale; ba.b2 = blk.c1.shift;
-    RET(upload_bk_tiles(c, B, Hin, Win, ph, pw, &ba));
-    const double fl = 2.0 * (double)B * Hin * Win * 128.0 * 1152.0;
-    ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_rw3_kernel", fl, s, [=](hipStream_t st) { return launch_conv_rw3(ba, st); }); });
-  } else {
-    ConvOpts o1; o1.stride = stride; o1.pad = 1; o1.relu_nch = 1 << 30;
-    RET(add_conv(c, ops, blk.c1, X, Cin, t, cout, image_segs(B, Hin, Win, Ho, Wo), o1));
-  }
+  RET(add_conv3x3(c, ops, blk.c1, pick_conv3_route(c, blk.c1, B, Hin, Win, stride), B, Hin, Win, stride, X, nullptr, t, 1));
   const void* resid = X;
   if (blk.has_sc) {
     ConvOpts os; os.stride = stride;
     RET(add_conv(c, ops, blk.sc, X, Cin, sc, cout, image_segs(B, Hin, Win, Ho, Wo), os));
     resid = sc;
   }
-  if (c64) return add_conv3x3_c64(c, ops, blk.c2, B, Ho, Wo, t, resid, Y, 1);
-  ConvOpts o2; o2.pad = 1; o2.relu_nch = 1 << 30; o2.res = resid; o2.res_ld = cout; o2.res_mode = 1;
-  return add_conv(c, ops, blk.c2, t, cout, Y, cout, image_segs(B, Ho, Wo, Ho, Wo), o2);
+  // conv2 adds the shortcut: conv_rw64 takes a residual (the res2 blocks: 64 -> 64, stride 1), conv_rw3 does not
+  const bool c64 = Cin == 64 && cout == 64 && stride == 1;
+  return add_conv3x3(c, ops, blk.c2, c64 ? pick_conv3_route(c, blk.c2, B, Ho, Wo, 1) : Conv3Route{}, B, Ho, Wo, 1, t, resid, Y, 1);
+}
+
+StemRoute pick_stem_route(const sylph_ctx* c) {
+  if (c->dt != DT_BF16 || !c->stem_wp || !knob::stem_kernel()) return StemRoute::igemm;
+  return knob::fuse_stem_pool() ? StemRoute::fused_pool : StemRoute::stem_conv;
 }
 
 int build_backbone(sylph_ctx* c, Plan* P) {
@@ -312,14 +334,11 @@ int build_backbone(sylph_ctx* c, Plan* P) {
     void *so = P->stem_out, *po = P->pool_out;
     ConvOpts os; os.stem = 1; os.relu_nch = 1 << 30;
     os.flops = 2.0 * (double)B * H2 * W2 * 64.0 * 147.0;
-    static const int stem_fast = getenv("SYLPH_STEM_KERNEL") ? atoi(getenv("SYLPH_STEM_KERNEL")) : 1;
-    if (dt == DT_BF16 && c->stem_wp && stem_fast) {
-      const void *x0 = P->x0, *wp = c->stem_wp;
-      const float *scl = c->stem.scale, *shf = c->stem.shift;
-      const double fl = os.flops;
-      // stem + max-pool in one kernel: the 64-channel stem output never reaches HBM (stem_conv.hip)
-      static const int fuse_pool = getenv("SYLPH_FUSE_STEM_POOL") ? atoi(getenv("SYLPH_FUSE_STEM_POOL")) : 1;
-      if (fuse_pool) {
+    const void *x0 = P->x0, *wp = c->stem_wp;
+    const float *scl = c->stem.scale, *shf = c->stem.shift;
+    const double fl = os.flops;
+    switch (pick_stem_route(c)) {
+      case StemRoute::fused_pool: {  // stem + max-pool in one kernel: the 64-channel stem output never reaches HBM (stem_conv.hip)
         void* trash = nullptr;
         RET(c->dalloc(&trash, (size_t)512 * 256 * 16));
         const Plan* PP = P;
@@ -331,15 +350,18 @@ int build_backbone(sylph_ctx* c, Plan* P) {
           });
         });
         P->stem_takes_raw = B <= STEM_RAW_MAX_BATCH;
-      } else {
+        break;
+      }
+      case StemRoute::stem_conv:
         ops.push_back([=](hipStream_t s) {
           return timed_op(c, "stem_conv_kernel", fl, s, [=](hipStream_t st) { return launch_stem_conv(x0, wp, scl, shf, so, B, H, W, H2, W2, st); });
         });
         ops.push_back([=](hipStream_t s) { return launch_maxpool(dt, so, po, B, H2, W2, 64, H4, W4, s); });
-      }
-    } else {
-      RET(add_conv(c, ops, c->stem, P->x0, 4, so, 64, image_segs(B, H, W, H2, W2), os));
-      ops.push_back([=](hipStream_t s) { return launch_maxpool(dt, so, po, B, H2, W2, 64, H4, W4, s); });
+        break;
+      case StemRoute::igemm:
+        RET(add_conv(c, ops, c->stem, P->x0, 4, so, 64, image_segs(B, H, W, H2, W2), os));
+        ops.push_back([=](hipStream_t s) { return launch_maxpool(dt, so, po, B, H2, W2, 64, H4, W4, s); });
+        break;
     }
   }
   const void* X = P->pool_out;
@@ -352,7 +374,6 @@ int build_backbone(sylph_ctx* c, Plan* P) {
   // shortcut take every other row and column, and res2 is no FPN input) computes only those positions, into a compact tensor (bottleneck.hip,
   // EVEN): a quarter of its conv2 / conv3 work and of its stores.  The next block then runs its own launches on that tensor with stride 1.
   // SYLPH_BK_STRIDED_TAIL: 0 off, 1 (default) on.
-  static const int strided_tail = getenv("SYLPH_BK_STRIDED_TAIL") ? atoi(getenv("SYLPH_BK_STRIDED_TAIL")) : 1;
   bool in_compact = false;  // X is such a compact tensor (Hin x Win its size)
   for (int si = 0; si < 4; ++si) {
     const int mid = (c->cfg.num_groups * c->cfg.width_per_group) << si, cout = (basic ? 64 : 256) << si;  // (ResNeXt: num_groups > 1)
@@ -372,9 +393,9 @@ int build_backbone(sylph_ctx* c, Plan* P) {
       const int stride = bi == 0 ? first_stride : 1;
       Y = (Y == Ya) ? Yb : Ya;
       const bool fpn_input = si >= 1;
-      const bool even_tail = strided_tail && !basic && bi > 0 && bi + 1 == blocks.size() && !fpn_input && si + 1 < 4 && c->cfg.stride_in_1x1 &&
-                             !c->stages[si + 1].empty() && !c->stages[si + 1][0].basic && (Hin & 1) == 0 && (Win & 1) == 0 &&
-                             bottleneck_takes_fuse_id(c, blocks[bi], B, Cin, Hin, Win, stride, mid, cout);
+      const bool even_tail = knob::bk_strided_tail() && !basic && bi > 0 && bi + 1 == blocks.size() && !fpn_input && si + 1 < 4 && c->cfg.stride_in_1x1 &&
+                             !c->stages[si + 1].empty() && !c->stages[si + 1][0].basic &&
+                             pick_block_route(c, blocks[bi], B, Cin, Hin, Win, stride, mid, cout, 0).tail_ok;
       if (basic) RET(add_basic_block(c, ops, blocks[bi], B, X, Cin, Hin, Win, stride, cout, Y, scr));
       else RET(add_bottleneck(c, ops, blocks[bi], B, X, Cin, Hin, Win, stride, mid, cout, Y, scr,
                               even_tail ? BK_EVEN_OUT : (bi == 0 && in_compact) ? BK_IN_COMPACT : 0));
@@ -396,13 +417,9 @@ int build_backbone(sylph_ctx* c, Plan* P) {
   // Small batches: after lateral5 the FPN is two independent chains of small launches -- {output5, P6, relu, P7} and {lateral4, output4,
   // lateral3, output3} -- so the first one runs on the context's side stream between a fork and a join (as the bbox tower does,
   // api_head.hip); large batches keep one stream.
-  static const int fpn_two_on = getenv("SYLPH_HEAD_STREAMS") ? atoi(getenv("SYLPH_HEAD_STREAMS")) : 1;
+  const int fpn_two_on = knob::head_streams();
   const bool fpn_two = fpn_two_on == 2 || (fpn_two_on == 1 && (size_t)B * P->Ltot <= (size_t)32 * 22400);  // (round 6: 32 images, as the head)
-  if (fpn_two && !c->side_stream) {
-    HIPCHK(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-  }
+  if (fpn_two) RET(ensure_side_stream(c));
   std::vector<OpFn> side_ops;
   void* lat[3] = {nullptr, nullptr, nullptr};
   for (int k = 2; k >= 0; --k) {
@@ -417,11 +434,7 @@ int build_backbone(sylph_ctx* c, Plan* P) {
       if (h != 2 * stage_h[si + 1] || w != 2 * stage_w[si + 1]) return fail("FPN needs exact 2x level sizes");
     }
     RET(add_conv(c, ops, c->fpn_lat[k], stage_out[si], cin, lat[k], 256, segs, ol));
-    if (k == 2 && fpn_two)  // fork right behind lateral5: the side stream continues from here
-      ops.push_back([c](hipStream_t s) {
-        if (hipEventRecord(c->ev_fork, s) != hipSuccess || hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) != hipSuccess) return -101;
-        return 0;
-      });
+    if (k == 2 && fpn_two) ops.push_back(side_fork_op(c));  // right behind lateral5: the side stream continues from here
     std::vector<SegDesc> so = image_segs(B, h, w, h, w);
     for (int b = 0; b < B; ++b) so[b].out_row0 = b * P->Ltot + P->off[k];
     ConvOpts oo; oo.pad = 1; oo.stream_slot = (k == 2 && fpn_two) ? 1 : 0;
@@ -454,11 +467,8 @@ int build_backbone(sylph_ctx* c, Plan* P) {
     RET(add_conv(c, top_ops, k == 3 ? c->p6 : c->p7, src, 256, P->F, 256, sg, op));
   }
   if (fpn_two) {
-    for (const OpFn& inner : side_ops) ops.push_back([c, inner](hipStream_t) { return inner(c->side_stream); });
-    ops.push_back([c](hipStream_t s) {
-      if (hipEventRecord(c->ev_join, c->side_stream) != hipSuccess || hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess) return -102;
-      return 0;
-    });
+    for (const OpFn& op : side_ops) ops.push_back(on_side_stream(c, op));
+    ops.push_back(side_join_op(c));
   }
   P->backbone_built = true;
   return 0;
@@ -497,8 +507,7 @@ int sylph_preprocess(sylph_ctx* c, int B, const float* const* images, const int*
     P->img_desc_last = tab;
     P->img_desc_kind = 1;
   }
-  const char* fp = getenv("SYLPH_FUSE_PREPROCESS");  // read per call (tests compare the two paths in one process)
-  P->raw_input = (!fp || atoi(fp) != 0) && P->stem_takes_raw;
+  P->raw_input = knob::fuse_preprocess() && P->stem_takes_raw;  // read per call (tests compare the two paths in one process)
   if (!P->raw_input)
     KCHK(launch_preprocess(c->dt, P->img_desc_dev, P->x0, B, mh, mw, c->cfg.pixel_mean, c->cfg.pixel_std, c->stream),
          "preprocess");

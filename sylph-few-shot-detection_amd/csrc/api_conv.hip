@@ -145,15 +145,9 @@ static long count_mtiles(const std::vector<SegDesc>& segs, int BM) {
 }
 
 ConvRoute pick_conv_route(const sylph_ctx* c, const ConvLayer& L, int in_ld, const std::vector<SegDesc>& segs, const ConvOpts& o) {
-  static const int hp_on = getenv("SYLPH_CONV_HPIPE") ? atoi(getenv("SYLPH_CONV_HPIPE")) : 1;
-  static const int halo_on = getenv("SYLPH_CONV_HALO") ? atoi(getenv("SYLPH_CONV_HALO")) : 1;
-  static const int pw_on = getenv("SYLPH_CONV_PW") ? atoi(getenv("SYLPH_CONV_PW")) : 1;
-  static const int spw_on = getenv("SYLPH_CONV_SPW") ? atoi(getenv("SYLPH_CONV_SPW")) : 1;
-  static const int nbuf2_on = getenv("SYLPH_CONV_NBUF2") ? atoi(getenv("SYLPH_CONV_NBUF2")) : 1;
-  static const int nbuf3_max = getenv("SYLPH_CONV_NBUF3_MAX") ? atoi(getenv("SYLPH_CONV_NBUF3_MAX")) : 400;
-  static const int split_on = getenv("SYLPH_SPLIT_K") ? atoi(getenv("SYLPH_SPLIT_K")) : 1;
-  static const int split_t1 = getenv("SYLPH_SPLIT_T1") ? atoi(getenv("SYLPH_SPLIT_T1")) : 64;
-  static const int split_t2 = getenv("SYLPH_SPLIT_T2") ? atoi(getenv("SYLPH_SPLIT_T2")) : 64;
+  const int hp_on = knob::conv_hpipe(), halo_on = knob::conv_halo(), pw_on = knob::conv_pw(), spw_on = knob::conv_spw();
+  const int nbuf2_on = knob::conv_nbuf2(), nbuf3_max = knob::conv_nbuf3_max();
+  const int split_on = knob::split_k(), split_t1 = knob::split_t1(), split_t2 = knob::split_t2();
   const long rows = total_rows(segs);
   const bool bf16 = c->dt == DT_BF16;
   const bool k3s1 = L.KH == 3 && L.KW == 3 && o.stride == 1 && o.pad == 1 && !o.stem && !o.in2;

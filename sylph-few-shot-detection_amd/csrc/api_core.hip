@@ -10,6 +10,11 @@ int fail(const std::string& m) {
   return 1;
 }
 
+long knob_env(const char* name, long dflt) {
+  const char* v = getenv(name);
+  return v ? atol(v) : dflt;
+}
+
 void free_plan(sylph_ctx* c, Plan* P) {
   (void)hipStreamSynchronize(c->stream);
   for (void* p : P->allocs) c->dfree_nosync(p);
@@ -72,7 +77,31 @@ int run_ops(sylph_ctx* c, const std::vector<OpFn>& ops, const char* what) {
   return 0;
 }
 
-// ================================================================================================
+int ensure_side_stream(sylph_ctx* c) {
+  if (c->side_stream) return 0;
+  HIPCHK(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
+  HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+  return 0;
+}
+
+OpFn side_fork_op(sylph_ctx* c) {
+  return [c](hipStream_t s) {
+    if (hipEventRecord(c->ev_fork, s) != hipSuccess || hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) != hipSuccess) return -101;
+    return 0;
+  };
+}
+
+OpFn side_join_op(sylph_ctx* c) {
+  return [c](hipStream_t s) {
+    if (hipEventRecord(c->ev_join, c->side_stream) != hipSuccess || hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess) return -102;
+    return 0;
+  };
+}
+
+OpFn on_side_stream(sylph_ctx* c, const OpFn& op) {
+  return [c, op](hipStream_t) { return op(c->side_stream); };
+}
 
 }  // namespace sylph_host
 
@@ -148,11 +177,11 @@ int sylph_ctx_create(int device_id, int dtype, sylph_ctx** out) {
   c->device = device_id;
   c->dt = dtype == SYLPH_BF16 ? DT_BF16 : (dtype == SYLPH_F32S ? DT_F32S : DT_F32);
   sylph_config_default(&c->cfg);
-  if (const char* mp = getenv("SYLPH_MAX_PLANS")) c->max_plans = atoi(mp) > 1 ? (size_t)atoi(mp) : 2;
+  c->max_plans = knob::max_plans() > 1 ? (size_t)knob::max_plans() : 2;
   {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) c->plan_byte_budget = (int64_t)(total_b / 10 * 6);  // 60 % of HBM for workspaces
-    if (const char* pb = getenv("SYLPH_PLAN_BYTES_MB")) c->plan_byte_budget = (int64_t)atol(pb) << 20;
+    if (knob::plan_bytes_mb() != LONG_MIN) c->plan_byte_budget = (int64_t)knob::plan_bytes_mb() << 20;
   }
   if (c->dalloc(&c->zeros, 256) != 0 || hipMemset(c->zeros, 0, 256) != hipSuccess) {
     delete c;

@@ -61,11 +61,11 @@ int build_head(sylph_ctx* c, Plan* P) {
   if (P->gn_partial) { P->gn_partial = nullptr; P->gn_stats = nullptr; }
   RET(ensure_gn_ws(c, P, nseg > P->B ? nseg : P->B, max_rows));
   const std::vector<SegDesc> segs = pyramid_segs(c, P);
-  auto& ops = P->head_ops;
+  auto& main_ops = P->head_ops;
   const bool tower_gn = c->cfg.tower_norm == 0;  // MODEL.FCOS.NORM "GN"; otherwise "none": conv + bias + ReLU layers
   const void* tower_in = P->F;                    // what the cls / bbox towers read: the pyramid, or the shared tower's output
   // doff: MODEL.FCOS.USE_DEFORMABLE -- the offset conv of the tower's deformable last layer (nullptr: a plain tower)
-  auto tower = [&](int which, const std::vector<ConvLayer>& convs, const std::vector<GNLayer>& gns, void* b0, void* b1,
+  auto tower = [&](std::vector<OpFn>& ops, int which, const std::vector<ConvLayer>& convs, const std::vector<GNLayer>& gns, void* b0, void* b1,
                    void** last, const float2** coef_last, OpFn* apply_last, const ConvLayer* doff) -> int {
     const bool defer_last = coef_last != nullptr;
     const void* in = tower_in;
@@ -88,9 +88,8 @@ int build_head(sylph_ctx* c, Plan* P) {
     // prediction convs and the class-conditional 1x1 conv).
     // A deformable last layer (doff) reads its input twice, through the offset conv and through the gather of conv_deform.hip: layer
     // n - 2 keeps its own GroupNorm apply pass so that this input is materialised once.
-    static const int gn_fuse_on = getenv("SYLPH_GN_FUSE") ? atoi(getenv("SYLPH_GN_FUSE")) : 1;
     ConvOpts probe; probe.pad = 1;
-    const bool fuse = gn_fuse_on && convs.size() > 1 && convs[0].Cin <= 512 && pick_conv_route(c, convs[1], 256, segs, probe).kind == ConvKind::hpipe;
+    const bool fuse = knob::gn_fuse() && convs.size() > 1 && convs[0].Cin <= 512 && pick_conv_route(c, convs[1], 256, segs, probe).kind == ConvKind::hpipe;
     const float2* coef_prev = nullptr;
     for (size_t i = 0; i < convs.size(); ++i) {
       ConvOpts o; o.pad = 1; o.segs_per_image = c->cfg.nlevels;
@@ -118,45 +117,39 @@ int build_head(sylph_ctx* c, Plan* P) {
   const float2* box_coef = nullptr;
   OpFn box_apply;
   // the cls tower's last GroupNorm is left to sylph_fcos_head (fused into the class-conditional conv when N <= 32)
-  static const int gn_logits_on = getenv("SYLPH_FUSE_GN_LOGITS") ? atoi(getenv("SYLPH_FUSE_GN_LOGITS")) : 1;
   P->cls_coef = nullptr; P->cls_apply = nullptr;
-  const bool defer = gn_logits_on && c->dt == DT_BF16 && tower_gn;
+  const bool defer = knob::fuse_gn_logits() && c->dt == DT_BF16 && tower_gn;
   OpFn cls_apply;
   if (!c->share_tower.empty()) {
     // MODEL.FCOS.NUM_SHARE_CONVS (fcos.py:397,626): a shared tower in front of both; its last norm is applied in place (two readers)
     void *s0 = nullptr, *s1 = nullptr, *share_out = nullptr;
     RET(c->dalloc(&s0, rows * 256 * e));
     RET(c->dalloc(&s1, rows * 256 * e));
-    RET(tower(2, c->share_tower, c->share_gn, s0, s1, &share_out, nullptr, nullptr, nullptr));
+    RET(tower(main_ops, 2, c->share_tower, c->share_gn, s0, s1, &share_out, nullptr, nullptr, nullptr));
     tower_in = share_out;
   }
   // Small batches (SylphPredictor and the reference's query loop run batch 1, meta_learn_evaluation.py:421-426, predictor.py:248-274):
   // a tower layer is a launch of a few hundred blocks whose K loop is latency-bound, and the two towers are independent chains of
   // four such launches -> the bbox tower (+ its prediction pass) runs on a second stream between a fork and a join event, the cls
   // tower stays on the caller's stream.  Large batches fill the chip for many rounds per launch: one stream (measured equal).
-  static const int two_on = getenv("SYLPH_HEAD_STREAMS") ? atoi(getenv("SYLPH_HEAD_STREAMS")) : 1;
+  const int two_on = knob::head_streams();
   // Round 6: up to 32 full-size images (was 8): the two towers' launches of one layer share the last partial round of blocks -- batch 12
   // 1 737 -> 1 806 img/s, batch 16 / 24 / 32 +1 %, 48 ... 192 equal (profiles/r6_small_batch.md)
   const bool two_streams = two_on == 2 || (two_on == 1 && rows <= (size_t)32 * 22400);
-  if (two_streams && !c->side_stream) {
-    HIPCHK(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+  if (two_streams) {
+    RET(ensure_side_stream(c));
+    main_ops.push_back(side_fork_op(c));
   }
-  if (two_streams)
-    ops.push_back([c](hipStream_t s) {
-      if (hipEventRecord(c->ev_fork, s) != hipSuccess || hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) != hipSuccess) return -101;
-      return 0;
-    });
-  RET(tower(0, c->cls_tower, c->cls_gn, P->tA, P->tB, &cls_feat, (defer && !c->cls_tower.empty()) ? &P->cls_coef : nullptr, &cls_apply,
+  RET(tower(main_ops, 0, c->cls_tower, c->cls_gn, P->tA, P->tB, &cls_feat, (defer && !c->cls_tower.empty()) ? &P->cls_coef : nullptr, &cls_apply,
             c->cls_off.Cout ? &c->cls_off : nullptr));
   P->cls_apply = cls_apply;
   const bool box_defer = defer && c->pred_taps && !c->box_tower.empty();
-  const size_t side_from = ops.size();  // two streams: ops[side_from ..] (bbox tower + prediction pass) go to the side stream
-  // from here to the join the ops run on the side stream: a split-K conv among them (towers without GroupNorm, the prediction conv)
-  // must take the side stream's partial-plane scratch, not the one the cls tower is using at the same time
+  // two streams: the bbox tower + prediction pass go to the side stream.  A split-K conv among them (towers without GroupNorm, the
+  // prediction conv) must take the side stream's partial-plane scratch, not the one the cls tower is using at the same time
+  std::vector<OpFn> side_ops;
+  std::vector<OpFn>& ops = two_streams ? side_ops : main_ops;
   c->build_slot = two_streams ? 1 : 0;
-  RET(tower(1, c->box_tower, c->box_gn, P->tC, P->tD, &box_feat, box_defer ? &box_coef : nullptr, &box_apply,
+  RET(tower(ops, 1, c->box_tower, c->box_gn, P->tC, P->tD, &box_feat, box_defer ? &box_coef : nullptr, &box_apply,
             c->box_off.Cout ? &c->box_off : nullptr));
   Geom g32;  // 128-row pointwise tiles of the pyramid (class-conditional conv with N <= 32, fused GN + prediction pass)
   RET(make_geom(c, segs, 128, &g32));
@@ -181,14 +174,8 @@ int build_head(sylph_ctx* c, Plan* P) {
   }
   c->build_slot = 0;
   if (two_streams) {
-    for (size_t k = side_from; k < ops.size(); ++k) {
-      const OpFn inner = ops[k];
-      ops[k] = [c, inner](hipStream_t) { return inner(c->side_stream); };
-    }
-    ops.push_back([c](hipStream_t s) {
-      if (hipEventRecord(c->ev_join, c->side_stream) != hipSuccess || hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess) return -102;
-      return 0;
-    });
+    for (const OpFn& op : side_ops) main_ops.push_back(on_side_stream(c, op));
+    main_ops.push_back(side_join_op(c));
   }
   // geometry for the class-conditional 1x1 conv (weights arrive per call)
   {
@@ -304,7 +291,7 @@ static CondPad cond_pad(int N) {
 // allow_scan = false: the kernel that writes the logits a scan left out (sylph_export_head)
 enum class HeadKind { gn_logits, scan, igemm_after_apply, igemm };
 static HeadKind head_kind(const sylph_ctx* c, const Plan* P, int N, bool allow_scan = true) {
-  static const int fuse_scan_on = getenv("SYLPH_FUSE_SCAN") ? atoi(getenv("SYLPH_FUSE_SCAN")) : 1;  // 0: never, 2: for any class count
+  const int fuse_scan_on = knob::fuse_scan();
   if (c->dt != DT_BF16 || !P->cls_coef) return HeadKind::igemm;
   if (allow_scan && fuse_scan_on && (N > 32 || fuse_scan_on == 2) && N < 65536) return HeadKind::scan;
   return N <= 32 ? HeadKind::gn_logits : HeadKind::igemm_after_apply;

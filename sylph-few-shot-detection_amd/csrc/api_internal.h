@@ -2,6 +2,7 @@
 // execution plan, the packed layer records, the plan-building helpers.  Not part of the C ABI (include/sylph_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -55,6 +56,48 @@ static inline uint16_t f2bf_host(float f) {
   u += 0x7fffu + ((u >> 16) & 1u);
   return (uint16_t)(u >> 16);
 }
+
+// The SYLPH_* environment overrides of the host units ("knobs"): every one is declared here and read through knob_env alone.  (Two more are
+// read inside kernel units, next to the launch they steer: SYLPH_CONV_BN64_MAX in conv_igemm.hip, SYLPH_SCAN_BLOCKS in detect.hip.)
+// Read time: ONCE = at first use, then fixed for the process; LIVE = at every call of the accessor, by the caller named in the row.
+namespace sylph_host {
+long knob_env(const char* name, long dflt);  // api_core.hip: the value of an integer environment variable, dflt when it is not set
+namespace knob {
+#define SYLPH_KNOB_ONCE(fn, name, dflt) inline int fn() { static const int v = (int)knob_env(name, dflt); return v; }
+#define SYLPH_KNOB_LIVE(fn, name, dflt) inline int fn() { return (int)knob_env(name, dflt); }
+// conv routes (pick_conv_route): 0 off, 1 where it pays, 2 wherever the kernel can run
+SYLPH_KNOB_ONCE(conv_hpipe, "SYLPH_CONV_HPIPE", 1)
+SYLPH_KNOB_ONCE(conv_halo, "SYLPH_CONV_HALO", 1)
+SYLPH_KNOB_ONCE(conv_pw, "SYLPH_CONV_PW", 1)
+SYLPH_KNOB_ONCE(conv_spw, "SYLPH_CONV_SPW", 1)
+SYLPH_KNOB_ONCE(conv_nbuf2, "SYLPH_CONV_NBUF2", 1)           // 0: one LDS stage in the 64-row tiles of conv_igemm
+SYLPH_KNOB_ONCE(conv_nbuf3_max, "SYLPH_CONV_NBUF3_MAX", 400)  // launches of at most this many tiles take three stages (0: two everywhere)
+SYLPH_KNOB_ONCE(split_k, "SYLPH_SPLIT_K", 1)                 // 0 off, 1 small launches of deep-K layers, 2 every layer of >= 8 K slices
+SYLPH_KNOB_ONCE(split_t1, "SYLPH_SPLIT_T1", 64)              // split K up to this many tiles (>= 32 K slices) ...
+SYLPH_KNOB_ONCE(split_t2, "SYLPH_SPLIT_T2", 64)              // ... and below this many (>= 64 K slices)
+// block routes (pick_conv3_route, pick_block_route, pick_stem_route)
+SYLPH_KNOB_ONCE(conv_rw3, "SYLPH_CONV_RW3", 1)               // 0 off, 1 launches of at least 256 x 120 positions, 2 any launch
+SYLPH_KNOB_LIVE(conv_rw64, "SYLPH_CONV_RW64", 1)             // 0 off, 1 launches of at least RW64_MIN_PATCHES patches, 2 any launch; per pick
+                                                             // (= per build: one process can build both)
+SYLPH_KNOB_ONCE(fuse_bottleneck, "SYLPH_FUSE_BOTTLENECK", 1)  // 0: the res2 blocks as conv chains
+SYLPH_KNOB_ONCE(bk_strided_tail, "SYLPH_BK_STRIDED_TAIL", 1)  // 0: the last res2 block computes every position
+SYLPH_KNOB_ONCE(stem_kernel, "SYLPH_STEM_KERNEL", 1)         // 0: the stem through conv_igemm
+SYLPH_KNOB_ONCE(fuse_stem_pool, "SYLPH_FUSE_STEM_POOL", 1)   // 0: stem_conv + maxpool as two launches
+// streams and fusions of the FPN / head
+SYLPH_KNOB_ONCE(head_streams, "SYLPH_HEAD_STREAMS", 1)       // 0 one stream, 1 two for small batches (FPN top and bbox tower on the side stream), 2 always two
+SYLPH_KNOB_ONCE(gn_fuse, "SYLPH_GN_FUSE", 1)                 // 0: every tower GroupNorm as its own apply pass
+SYLPH_KNOB_ONCE(fuse_gn_logits, "SYLPH_FUSE_GN_LOGITS", 1)   // 0: the head ops apply the last cls GroupNorm themselves
+SYLPH_KNOB_ONCE(fuse_scan, "SYLPH_FUSE_SCAN", 1)             // 0 never, 1 more than 32 classes, 2 any class count
+SYLPH_KNOB_LIVE(fuse_preprocess, "SYLPH_FUSE_PREPROCESS", 1)  // 0: a normalised copy of the batch; per sylph_preprocess call
+SYLPH_KNOB_LIVE(fuse_shortcut, "SYLPH_FUSE_SHORTCUT", 1)     // 0: conv3 and the projection shortcut as two convs; per sylph_finalize_weights /
+                                                             // per bottleneck parity entry call
+// plan cache, per sylph_ctx_create
+SYLPH_KNOB_LIVE(max_plans, "SYLPH_MAX_PLANS", 32)            // cached plans per context (at least 2)
+inline long plan_bytes_mb() { return knob_env("SYLPH_PLAN_BYTES_MB", LONG_MIN); }  // workspace budget in MiB; not set (LONG_MIN here): 60 % of the device
+#undef SYLPH_KNOB_ONCE
+#undef SYLPH_KNOB_LIVE
+}  // namespace knob
+}  // namespace sylph_host
 
 typedef std::function<int(hipStream_t)> OpFn;
 
@@ -373,6 +416,40 @@ struct ConvRoute {
   int ksplit = 1;  // igemm_splitk: K ranges
 };
 
+// The kernel of ONE dense 3x3 pad-1 conv + FrozenBN [+ residual] [+ ReLU] on whole images (pick_conv3_route):
+//   rw3      conv_rw3.hip: 128 -> 128, weights in registers, ph x pw patches (FrozenBN + ReLU only: no residual input)
+//   rw64     conv_rw64.hip: 64 -> 64, weights in registers, ph x pw patches
+//   generic  add_conv: pick_conv_route decides
+// The dedicated kernels push no route record (sylph_conv_routes_read lists add_conv's choices only).
+enum class Conv3Kind { rw3, rw64, generic };
+struct Conv3Route {
+  Conv3Kind kind = Conv3Kind::generic;
+  int ph = 0, pw = 0;
+};
+
+// How add_bottleneck builds one bottleneck block (pick_block_route):
+//   fused_id       bottleneck.hip, ONE kernel: the res2 identity blocks (C 256, mid 64, stride 1), bf16
+//   fused_id_even  the same kernel's stride-2-output launch (BK_EVEN_OUT)
+//   fused_proj     bottleneck.hip, ONE kernel: the first res2 block (64 -> 64 -> 64 -> 256, projection folded into conv3's GEMM)
+//   chain          conv1 (add_conv) -> conv2 (grouped: conv_group.hip | rw3: conv_rw3.hip | generic: add_conv) -> conv3 + shortcut (add_conv;
+//                  fused_sc: both as one GEMM over K = [t2 | X])
+enum class BlockForm { fused_id, fused_id_even, fused_proj, chain };
+enum class Conv2Form { grouped, rw3, generic };
+struct BlockRoute {
+  std::string refuse;  // not empty: the block cannot be built as asked; the text add_bottleneck fails with
+  int chunk = 0;       // images per build: B, or less for a ResNeXt block whose tensors would pass 2^31 elements -- such a block is built
+                       // chunk by chunk, every chunk with a pick of its own, and the fields below are not set
+  BlockForm form = BlockForm::chain;
+  Conv2Form conv2 = Conv2Form::generic;
+  int ph = 0, pw = 0;     // conv2 == rw3: its patch
+  bool fused_sc = false;  // chain: conv3 and the projection shortcut are one GEMM
+  bool tail_ok = false;   // the block can take BK_EVEN_OUT: a fused identity block on a map of even height and width
+  int s1 = 1, s3 = 1, H1 = 0, W1 = 0, Ho = 0, Wo = 0;  // strides of conv1 / conv2, conv1's output map, the block's output map
+};
+
+// The stem + max-pool launches of build_backbone (pick_stem_route): stem_pool_kernel | stem_conv_kernel + maxpool | add_conv's stem loader + maxpool
+enum class StemRoute { fused_pool, stem_conv, igemm };
+
 struct BkScratch { void *t1, *t2, *sc; void** trash; };
 // add_bottleneck flags
 //   BK_EVEN_OUT    the block's output only at even rows / columns, Y compact [B][Hin/2 * Win/2][cout]: the fused identity block of
@@ -390,6 +467,14 @@ void evict_plans(sylph_ctx* c, const Plan* keep);
 void drop_plan(sylph_ctx* c, Plan* P);
 Plan* get_plan(sylph_ctx* c, int B, int H, int W);
 int run_ops(sylph_ctx* c, const std::vector<OpFn>& ops, const char* what);
+// The context's side stream: a second chain of small launches runs on it between a fork and a join (the FPN's top levels in
+// build_backbone, the bbox tower in build_head).  The builder collects that chain's ops in a list of its own and appends them, each
+// through on_side_stream, in front of the join op.  A split-K conv of the chain takes the side stream's scratch (ConvOpts::stream_slot
+// or sylph_ctx::build_slot).
+int ensure_side_stream(sylph_ctx* c);  // the stream and its two events, created on first use
+OpFn side_fork_op(sylph_ctx* c);       // the side stream continues from here (fails with -101)
+OpFn side_join_op(sylph_ctx* c);       // the op's stream waits for what the side stream was given (fails with -102)
+OpFn on_side_stream(sylph_ctx* c, const OpFn& op);  // `op`, launched on the side stream whatever stream the op list runs on
 // api_weights.hip
 const HostTensor* find_w(sylph_ctx* c, const std::string& k);
 int pack_conv(sylph_ctx* c, const std::vector<const HostTensor*>& ws, ConvLayer* L);
@@ -425,8 +510,11 @@ int add_conv_deform(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& off, 
 std::vector<SegDesc> image_segs(int B, int Hin, int Win, int Hout, int Wout, int resH = 0, int resW = 0);
 // api_backbone.hip
 int ensure_pyramid(sylph_ctx* c, Plan* P);
+// the block-level pickers: pure (no allocation, no upload, no HIP call)
+Conv3Route pick_conv3_route(const sylph_ctx* c, const ConvLayer& L, int B, int H, int W, int stride);
+BlockRoute pick_block_route(const sylph_ctx* c, const sylph_ctx::Block& blk, int B, int Cin, int Hin, int Win, int stride, int mid, int cout, int flags);
+StemRoute pick_stem_route(const sylph_ctx* c);
 int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win, int stride, int mid, int cout, void* Y, const BkScratch& scr, int flags = 0);
-bool bottleneck_takes_fuse_id(const sylph_ctx* c, const sylph_ctx::Block& blk, int B, int Cin, int Hin, int Win, int stride, int mid, int cout);
 int add_conv3x3_c64(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, int B, int H, int W, const void* x, const void* res, void* y, int relu);
 int add_basic_block(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win, int stride, int cout, void* Y, const BkScratch& scr);
 int build_backbone(sylph_ctx* c, Plan* P);

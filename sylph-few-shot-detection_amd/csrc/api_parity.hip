@@ -2,6 +2,40 @@
 // No torch types, no CPU compute fallback: every stage is a HIP kernel from this directory.
 #include "api_internal.h"
 
+namespace {
+
+// B images between the caller's fp32 NCHW tensors and dense device images [B][hw][C] of the context's storage type
+int import_nchw(sylph_ctx* c, const float* src, void* dst, int B, int C, int hw, const char* what = "import") {
+  for (int b = 0; b < B; ++b) KCHK(launch_import_nchw(c->dt, src + (size_t)b * C * hw, dst, C, hw, b * hw, C, c->stream), what);
+  return 0;
+}
+int export_nchw(sylph_ctx* c, const void* src, float* dst, int B, int C, int hw, const char* what = "export") {
+  for (int b = 0; b < B; ++b) KCHK(launch_export_nchw(c->dt, src, dst + (size_t)b * C * hw, C, hw, b * hw, C, c->stream), what);
+  return 0;
+}
+
+// The scratch context of one parity entry: the builders allocate, upload and record into it as into any context, it works on the caller's
+// device, stream, storage type, zero page and configuration, and on return it drains the stream and frees what it allocated.
+//   Records::to_caller  profiling follows the caller's, and hand_records() moves the profile + route records of the entry's launches to the
+//                       caller's context (conv2d, bottleneck*, group_conv, conv3x3_c64, basic_block, fpn_lateral)
+//   Records::none       the entry's launches are never profiled (group_norm, stem_maxpool, bench_conv)
+enum class Records { to_caller, none };
+struct Scratch : sylph_ctx {
+  sylph_ctx* const caller;
+  Scratch(sylph_ctx* c, Records rec) : caller(c) {
+    device = c->device; dt = c->dt; stream = c->stream; zeros = c->zeros; cfg = c->cfg;
+    if (rec == Records::to_caller) prof = c->prof;
+  }
+  Scratch(const Scratch&) = delete;
+  ~Scratch() {
+    (void)hipStreamSynchronize(stream);
+    for (void* p : allocs) (void)hipFree(p);
+  }
+  void hand_records() { adopt_records(caller, this); }
+};
+
+}  // namespace
+
 extern "C" {
 
 int sylph_conv2d(sylph_ctx* c, const float* x, int B, int C, int H, int W, const float* w_host, int Cout, int KH, int KW,
@@ -11,10 +45,7 @@ int sylph_conv2d(sylph_ctx* c, const float* x, int B, int C, int H, int W, const
   const int bk = c->dt == DT_BF16 ? 64 : 32;
   if (C % bk != 0) return fail("sylph_conv2d: Cin must be a multiple of " + std::to_string(bk));
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-  sylph_ctx tmp;  // scratch allocations freed on return
-  tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros;
-  tmp.prof = c->prof;  // profile + route records move to the caller's context below
-  struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
+  Scratch tmp(c, Records::to_caller);
   HostTensor hw;
   hw.shape = {Cout, C, KH, KW};
   hw.data.assign(w_host, w_host + (size_t)Cout * C * KH * KW);
@@ -25,24 +56,18 @@ int sylph_conv2d(sylph_ctx* c, const float* x, int B, int C, int H, int W, const
   void *xin, *yout, *res = nullptr;
   RET(tmp.dalloc(&xin, (size_t)B * H * W * C * tmp.esz()));
   RET(tmp.dalloc(&yout, (size_t)B * Ho * Wo * Cout * tmp.esz()));
-  for (int b = 0; b < B; ++b)
-    KCHK(launch_import_nchw(c->dt, x + (size_t)b * C * H * W, xin, C, H * W, b * H * W, C, c->stream), "import");
+  RET(import_nchw(&tmp, x, xin, B, C, H * W));
   ConvOpts o; o.stride = stride; o.pad = pad; o.relu_nch = relu ? (1 << 30) : 0;
   if (residual) {
     RET(tmp.dalloc(&res, (size_t)B * Ho * Wo * Cout * tmp.esz()));
-    for (int b = 0; b < B; ++b)
-      KCHK(launch_import_nchw(c->dt, residual + (size_t)b * Cout * Ho * Wo, res, Cout, Ho * Wo, b * Ho * Wo, Cout,
-                              c->stream), "import");
+    RET(import_nchw(&tmp, residual, res, B, Cout, Ho * Wo));
     o.res = res; o.res_ld = Cout; o.res_mode = 1;
   }
   std::vector<OpFn> ops;
   RET(add_conv(&tmp, ops, L, xin, C, yout, Cout, image_segs(B, H, W, Ho, Wo), o));
   RET(run_ops(c, ops, "conv2d"));
-  adopt_records(c, &tmp);
-  for (int b = 0; b < B; ++b)
-    KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * Cout * Ho * Wo, Cout, Ho * Wo, b * Ho * Wo, Cout, c->stream),
-         "export");
-  return 0;
+  tmp.hand_records();
+  return export_nchw(&tmp, yout, y, B, Cout, Ho * Wo);
 }
 
 int sylph_set_debug_taps(sylph_ctx* c, int on) {
@@ -71,9 +96,7 @@ int sylph_export_stage(sylph_ctx* c, int stage, float* out) {
     RET(run_ops(c, P->tail_dense_ops, "res2 tap"));
     src = P->tail_dense;
   }
-  for (int b = 0; b < P->B; ++b)
-    KCHK(launch_export_nchw(c->dt, src, out + (size_t)b * C * hw, C, hw, b * hw, C, c->stream), "export stage");
-  return 0;
+  return export_nchw(c, src, out, P->B, C, hw, "export stage");
 }
 
 int sylph_export_tower(sylph_ctx* c, int tower, int layer, int level, float* y, float* coef) {
@@ -103,10 +126,7 @@ static int bottleneck_entry(sylph_ctx* c, const float* x, int B, int Cin, int H,
   if (Cin % bk != 0 || mid % bk != 0) return fail("sylph_bottleneck: channel counts must be multiples of " + std::to_string(bk));
   const bool has_sc = w_host[3] != nullptr;
   if (!has_sc && (Cin != cout || stride != 1)) return fail("sylph_bottleneck: an identity block needs Cin == cout and stride 1");
-  sylph_ctx tmp;  // scratch allocations freed on return
-  tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros; tmp.cfg = c->cfg;
-  tmp.prof = c->prof;  // per-launch HIP-event timing (tools/bench_bottleneck.py): the records (and route records) move to the caller's context below
-  struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
+  Scratch tmp(c, Records::to_caller);
   sylph_ctx::Block blk;
   const int cins[4] = {Cin, mid, mid, Cin}, couts[4] = {mid, mid, cout, cout}, ks[4] = {1, 3, 1, 1};
   ConvLayer* Ls[4] = {&blk.c1, &blk.c2, &blk.c3, &blk.sc};
@@ -124,8 +144,7 @@ static int bottleneck_entry(sylph_ctx* c, const float* x, int B, int Cin, int H,
     RET(upload_vec(&tmp, &Ls[i]->shift, std::vector<float>(shift_host[i], shift_host[i] + couts[i]), Ls[i]->Cout_pad));
   }
   blk.has_sc = has_sc;
-  const char* fz = getenv("SYLPH_FUSE_SHORTCUT");
-  if (has_sc && !(fz && atoi(fz) == 0)) {
+  if (has_sc && knob::fuse_shortcut()) {
     RET(make_c3sc(&tmp, hw[2], scale_host[2], shift_host[2], hw[3], scale_host[3], shift_host[3], &blk.c3sc));
     blk.fused_sc = true;
   }
@@ -137,16 +156,13 @@ static int bottleneck_entry(sylph_ctx* c, const float* x, int B, int Cin, int H,
   RET(tmp.dalloc(&t1, (size_t)B * H * W * mid * e));
   RET(tmp.dalloc(&t2, (size_t)B * Ho * Wo * mid * e));
   RET(tmp.dalloc(&sc, (size_t)B * Ho * Wo * cout * e));
-  for (int b = 0; b < B; ++b)
-    KCHK(launch_import_nchw(c->dt, x + (size_t)b * Cin * H * W, xin, Cin, H * W, b * H * W, Cin, c->stream), "import");
+  RET(import_nchw(&tmp, x, xin, B, Cin, H * W));
   std::vector<OpFn> ops;
   BkScratch scr{t1, t2, sc, &trash};
   RET(add_bottleneck(&tmp, ops, blk, B, xin, Cin, H, W, stride, mid, cout, yout, scr, even_out ? BK_EVEN_OUT : 0));
   RET(run_ops(c, ops, "bottleneck"));
-  adopt_records(c, &tmp);
-  for (int b = 0; b < B; ++b)
-    KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * cout * Ho * Wo, cout, Ho * Wo, b * Ho * Wo, cout, c->stream), "export");
-  return 0;
+  tmp.hand_records();
+  return export_nchw(&tmp, yout, y, B, cout, Ho * Wo);
 }
 
 int sylph_bottleneck(sylph_ctx* c, const float* x, int B, int Cin, int H, int W, int stride, int mid, int cout, const float* const* w_host,
@@ -172,10 +188,7 @@ int sylph_group_conv(sylph_ctx* c, const float* x, int B, int C, int H, int W, i
                      const float* scale_host, const float* shift_host, int relu, float* y) {
   HIPCHK(hipSetDevice(c->device));
   if (groups < 1 || C % groups != 0 || (stride != 1 && stride != 2) || B < 1) return fail("sylph_group_conv: bad arguments");
-  sylph_ctx tmp;  // scratch allocations freed on return
-  tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros; tmp.cfg = c->cfg;
-  tmp.prof = c->prof;
-  struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
+  Scratch tmp(c, Records::to_caller);
   HostTensor hw;
   hw.shape = {C, C / groups, 3, 3};
   hw.data.assign(w_host, w_host + (size_t)C * (C / groups) * 9);
@@ -186,8 +199,7 @@ int sylph_group_conv(sylph_ctx* c, const float* x, int B, int C, int H, int W, i
   void *xin, *yout;
   RET(tmp.dalloc(&xin, (size_t)B * H * W * C * e));
   RET(tmp.dalloc(&yout, (size_t)B * Ho * Wo * C * e));
-  for (int b = 0; b < B; ++b)
-    KCHK(launch_import_nchw(c->dt, x + (size_t)b * C * H * W, xin, C, H * W, b * H * W, C, c->stream), "import");
+  RET(import_nchw(&tmp, x, xin, B, C, H * W));
   GroupConvArgs ga;
   memset(&ga, 0, sizeof(ga));
   ga.x = xin; ga.y = yout; ga.wt = L.w; ga.scale = L.scale; ga.shift = L.shift;
@@ -195,20 +207,15 @@ int sylph_group_conv(sylph_ctx* c, const float* x, int B, int C, int H, int W, i
   const double fl = 2.0 * (double)B * Ho * Wo * C * 9.0 * (C / groups);
   const DType dt = c->dt;
   KCHK(timed_op(&tmp, "conv_group_kernel", fl, c->stream, [=](hipStream_t st) { return launch_conv_group(dt, ga, st); }), "conv_group");
-  adopt_records(c, &tmp);
-  for (int b = 0; b < B; ++b)
-    KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * C * Ho * Wo, C, Ho * Wo, b * Ho * Wo, C, c->stream), "export");
-  return 0;
+  tmp.hand_records();
+  return export_nchw(&tmp, yout, y, B, C, Ho * Wo);
 }
 
 int sylph_conv3x3_c64(sylph_ctx* c, const float* x, int B, int H, int W, const float* w_host, const float* scale_host,
                       const float* shift_host, int relu, const float* residual, float* y) {
   HIPCHK(hipSetDevice(c->device));
   if (B < 1 || H < 1 || W < 1 || !w_host || !scale_host || !shift_host) return fail("sylph_conv3x3_c64: bad arguments");
-  sylph_ctx tmp;  // scratch allocations freed on return
-  tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros; tmp.cfg = c->cfg;
-  tmp.prof = c->prof;  // profile + route records move to the caller's context below
-  struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
+  Scratch tmp(c, Records::to_caller);
   HostTensor hw;
   hw.shape = {64, 64, 3, 3};
   hw.data.assign(w_host, w_host + (size_t)64 * 64 * 9);
@@ -221,17 +228,13 @@ int sylph_conv3x3_c64(sylph_ctx* c, const float* x, int B, int H, int W, const f
   RET(tmp.dalloc(&xin, n));
   RET(tmp.dalloc(&yout, n));
   if (residual) RET(tmp.dalloc(&res, n));
-  for (int b = 0; b < B; ++b) {
-    KCHK(launch_import_nchw(c->dt, x + (size_t)b * 64 * H * W, xin, 64, H * W, b * H * W, 64, c->stream), "import");
-    if (residual) KCHK(launch_import_nchw(c->dt, residual + (size_t)b * 64 * H * W, res, 64, H * W, b * H * W, 64, c->stream), "import");
-  }
+  RET(import_nchw(&tmp, x, xin, B, 64, H * W));
+  if (residual) RET(import_nchw(&tmp, residual, res, B, 64, H * W));
   std::vector<OpFn> ops;
   RET(add_conv3x3_c64(&tmp, ops, L, B, H, W, xin, res, yout, relu));
   RET(run_ops(c, ops, "conv3x3_c64"));
-  adopt_records(c, &tmp);
-  for (int b = 0; b < B; ++b)
-    KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * 64 * H * W, 64, H * W, b * H * W, 64, c->stream), "export");
-  return 0;
+  tmp.hand_records();
+  return export_nchw(&tmp, yout, y, B, 64, H * W);
 }
 
 int sylph_basic_block(sylph_ctx* c, const float* x, int B, int Cin, int H, int W, int stride, int cout, const float* const* w_host,
@@ -242,10 +245,7 @@ int sylph_basic_block(sylph_ctx* c, const float* x, int B, int Cin, int H, int W
   if (stride != 1 && stride != 2) return fail("sylph_basic_block: stride must be 1 or 2");
   const bool has_sc = w_host[2] != nullptr;
   if (!has_sc && (Cin != cout || stride != 1)) return fail("sylph_basic_block: an identity block needs Cin == cout and stride 1");
-  sylph_ctx tmp;  // scratch allocations freed on return
-  tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros; tmp.cfg = c->cfg;
-  tmp.prof = c->prof;
-  struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
+  Scratch tmp(c, Records::to_caller);
   sylph_ctx::Block blk;
   blk.basic = true; blk.has_sc = has_sc;
   const int cins[3] = {Cin, cout, Cin}, ks[3] = {3, 3, 1};
@@ -265,16 +265,13 @@ int sylph_basic_block(sylph_ctx* c, const float* x, int B, int Cin, int H, int W
   RET(tmp.dalloc(&yout, (size_t)B * Ho * Wo * cout * e));
   RET(tmp.dalloc(&t1, (size_t)B * Ho * Wo * cout * e));
   RET(tmp.dalloc(&sc, (size_t)B * Ho * Wo * cout * e));
-  for (int b = 0; b < B; ++b)
-    KCHK(launch_import_nchw(c->dt, x + (size_t)b * Cin * H * W, xin, Cin, H * W, b * H * W, Cin, c->stream), "import");
+  RET(import_nchw(&tmp, x, xin, B, Cin, H * W));
   std::vector<OpFn> ops;
   BkScratch scr{t1, nullptr, sc, &trash};
   RET(add_basic_block(&tmp, ops, blk, B, xin, Cin, H, W, stride, cout, yout, scr));
   RET(run_ops(c, ops, "basic_block"));
-  adopt_records(c, &tmp);
-  for (int b = 0; b < B; ++b)
-    KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * cout * Ho * Wo, cout, Ho * Wo, b * Ho * Wo, cout, c->stream), "export");
-  return 0;
+  tmp.hand_records();
+  return export_nchw(&tmp, yout, y, B, cout, Ho * Wo);
 }
 
 int sylph_fpn_lateral(sylph_ctx* c, const float* x, int B, int C, int H, int W, const float* w_host, const float* bias_host, const float* top,
@@ -283,10 +280,7 @@ int sylph_fpn_lateral(sylph_ctx* c, const float* x, int B, int C, int H, int W, 
   const int bk = c->dt == DT_BF16 ? 64 : 32;
   if (C % bk != 0) return fail("sylph_fpn_lateral: Cin must be a multiple of " + std::to_string(bk));
   if (top && ((H & 1) || (W & 1))) return fail("sylph_fpn_lateral: the top-down input is half the size: H and W must be even");
-  sylph_ctx tmp;  // scratch allocations freed on return
-  tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros; tmp.cfg = c->cfg;
-  tmp.prof = c->prof;  // profile + route records move to the caller's context below
-  struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
+  Scratch tmp(c, Records::to_caller);
   HostTensor hw;
   hw.shape = {256, C, 1, 1};
   hw.data.assign(w_host, w_host + (size_t)256 * C);
@@ -297,38 +291,31 @@ int sylph_fpn_lateral(sylph_ctx* c, const float* x, int B, int C, int H, int W, 
   void *xin, *yout, *tp = nullptr;
   RET(tmp.dalloc(&xin, (size_t)B * H * W * C * e));
   RET(tmp.dalloc(&yout, (size_t)B * H * W * 256 * e));
-  for (int b = 0; b < B; ++b)
-    KCHK(launch_import_nchw(c->dt, x + (size_t)b * C * H * W, xin, C, H * W, b * H * W, C, c->stream), "import");
+  RET(import_nchw(&tmp, x, xin, B, C, H * W));
   ConvOpts o;
   std::vector<SegDesc> segs = image_segs(B, H, W, H, W);
   if (top) {  // exactly the launch build_backbone makes for fpn_lateral3 / 4: residual = nearest 2x upsample of the level above
     const int h2 = H / 2, w2 = W / 2;
     RET(tmp.dalloc(&tp, (size_t)B * h2 * w2 * 256 * e));
-    for (int b = 0; b < B; ++b)
-      KCHK(launch_import_nchw(c->dt, top + (size_t)b * 256 * h2 * w2, tp, 256, h2 * w2, b * h2 * w2, 256, c->stream), "import");
+    RET(import_nchw(&tmp, top, tp, B, 256, h2 * w2));
     o.res = tp; o.res_ld = 256; o.res_mode = 2;
     segs = image_segs(B, H, W, H, W, h2, w2);
   }
   std::vector<OpFn> ops;
   RET(add_conv(&tmp, ops, L, xin, C, yout, 256, segs, o));
   RET(run_ops(c, ops, "fpn_lateral"));
-  adopt_records(c, &tmp);
-  for (int b = 0; b < B; ++b)
-    KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * 256 * H * W, 256, H * W, b * H * W, 256, c->stream), "export");
-  return 0;
+  tmp.hand_records();
+  return export_nchw(&tmp, yout, y, B, 256, H * W);
 }
 
 int sylph_group_norm(sylph_ctx* c, const float* x, int B, int H, int W, const float* gamma_host, const float* beta_host,
                      int relu, float* y) {
   HIPCHK(hipSetDevice(c->device));
-  sylph_ctx tmp;
-  tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros;
-  struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
+  Scratch tmp(c, Records::none);
   const int HW = H * W;
   void* buf;
   RET(tmp.dalloc(&buf, (size_t)B * HW * 256 * tmp.esz()));
-  for (int b = 0; b < B; ++b)
-    KCHK(launch_import_nchw(c->dt, x + (size_t)b * 256 * HW, buf, 256, HW, b * HW, 256, c->stream), "import");
+  RET(import_nchw(&tmp, x, buf, B, 256, HW));
   std::vector<RowSeg> rs;
   for (int b = 0; b < B; ++b) rs.push_back(RowSeg{b * HW, HW});
   RowSeg* rsd;
@@ -341,18 +328,14 @@ int sylph_group_norm(sylph_ctx* c, const float* x, int B, int H, int W, const fl
   RET(tmp.dalloc((void**)&partial, (size_t)B * max_chunks * 32 * 3 * 4));
   RET(tmp.dalloc((void**)&stats, (size_t)B * 32 * sizeof(float2)));
   KCHK(launch_groupnorm(c->dt, buf, rsd, B, HW, 256, ga, be, 1e-5f, relu, partial, stats, c->stream), "group_norm");
-  for (int b = 0; b < B; ++b)
-    KCHK(launch_export_nchw(c->dt, buf, y + (size_t)b * 256 * HW, 256, HW, b * HW, 256, c->stream), "export");
-  return 0;
+  return export_nchw(&tmp, buf, y, B, 256, HW);
 }
 
 int sylph_stem_maxpool(sylph_ctx* c, const float* x, int B, int H, int W, const float* w_host, const float* scale_host,
                        const float* shift_host, float* stem_out, float* pool_out) {
   if (c->dt != DT_BF16) return fail("sylph_stem_maxpool: the dedicated stem kernels exist in bf16 mode only");
   HIPCHK(hipSetDevice(c->device));
-  sylph_ctx tmp;  // scratch allocations freed on return
-  tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros;
-  struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
+  Scratch tmp(c, Records::none);
   const int H2 = (H - 1) / 2 + 1, W2 = (W - 1) / 2 + 1, H4 = (H2 - 1) / 2 + 1, W4 = (W2 - 1) / 2 + 1;
   std::vector<bf16_t> wp((size_t)64 * 224);  // [n][kh][8 px][4 ch], kernel column 7 / channel 3 zero (as sylph_finalize_weights)
   for (int n = 0; n < 64; ++n)
@@ -375,18 +358,15 @@ int sylph_stem_maxpool(sylph_ctx* c, const float* x, int B, int H, int W, const 
   const float mean0[3] = {0.f, 0.f, 0.f}, std1[3] = {1.f, 1.f, 1.f};
   KCHK(launch_preprocess(c->dt, idd, x0, B, H, W, mean0, std1, c->stream), "preprocess");
   KCHK(launch_stem_conv(x0, wpd, scd, shd, so, B, H, W, H2, W2, c->stream), "stem_conv");
-  static const int fuse_pool = getenv("SYLPH_FUSE_STEM_POOL") ? atoi(getenv("SYLPH_FUSE_STEM_POOL")) : 1;
-  if (fuse_pool) {  // the product path: pool_out comes from the fused kernel, stem_out from the stand-alone stem kernel
+  if (knob::fuse_stem_pool()) {  // the product path: pool_out comes from the fused kernel, stem_out from the stand-alone stem kernel
     void* trash;
     RET(tmp.dalloc(&trash, (size_t)512 * 256 * 16));
     KCHK(launch_stem_pool(x0, wpd, scd, shd, po, trash, B, H, W, H2, W2, H4, W4, c->stream), "stem_pool");
   } else {
     KCHK(launch_maxpool(c->dt, so, po, B, H2, W2, 64, H4, W4, c->stream), "maxpool");
   }
-  for (int b = 0; b < B; ++b) {
-    if (stem_out) KCHK(launch_export_nchw(c->dt, so, stem_out + (size_t)b * 64 * H2 * W2, 64, H2 * W2, b * H2 * W2, 64, c->stream), "export");
-    if (pool_out) KCHK(launch_export_nchw(c->dt, po, pool_out + (size_t)b * 64 * H4 * W4, 64, H4 * W4, b * H4 * W4, 64, c->stream), "export");
-  }
+  if (stem_out) RET(export_nchw(&tmp, so, stem_out, B, 64, H2 * W2));
+  if (pool_out) RET(export_nchw(&tmp, po, pool_out, B, 64, H4 * W4));
   return 0;
 }
 
@@ -396,9 +376,7 @@ int sylph_bench_conv(sylph_ctx* c, int B, int H, int W, int Cin, int Cout, int K
   const int bk = c->dt == DT_BF16 ? 64 : 32;
   if (Cin % bk != 0) return fail("sylph_bench_conv: Cin must be a multiple of " + std::to_string(bk));
   const int Ho = (H + 2 * pad - K) / stride + 1, Wo = (W + 2 * pad - K) / stride + 1;
-  sylph_ctx tmp;
-  tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros;
-  struct Guard { sylph_ctx* t; hipStream_t s; ~Guard() { (void)hipStreamSynchronize(s); for (void* p : t->allocs) (void)hipFree(p); } } guard{&tmp, c->stream};
+  Scratch tmp(c, Records::none);
   HostTensor hw;
   hw.shape = {Cout, Cin, K, K};
   hw.data.resize((size_t)Cout * Cin * K * K);

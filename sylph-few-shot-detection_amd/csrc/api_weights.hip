@@ -311,8 +311,7 @@ int sylph_finalize_weights(sylph_ctx* c) {
         RET(make_conv_bn(c, q + ".conv3", &blk.c3));
         blk.has_sc = bi == 0;
         if (blk.has_sc) RET(make_conv_bn(c, q + ".shortcut", &blk.sc));
-        const char* fz = getenv("SYLPH_FUSE_SHORTCUT");
-        if (blk.has_sc && !(fz && atoi(fz) == 0)) {
+        if (blk.has_sc && knob::fuse_shortcut()) {
           // fold the two FrozenBN scales into the weights, sum the shifts (fp32 before the dtype cast)
           const HostTensor *w3 = find_w(c, q + ".conv3.weight"), *ws = find_w(c, q + ".shortcut.weight");
           const int co = (int)w3->shape[0];

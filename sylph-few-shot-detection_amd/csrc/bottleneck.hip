@@ -742,8 +742,9 @@ __global__ __launch_bounds__(256, 1) void bottleneck64p_kernel(const BottleneckA
   }
 }
 
-// small != 0: the double-buffered 64-position variant (the tile table must hold patches of <= 64 positions with <= 128 halo rows)
-int launch_bottleneck64(const BottleneckArgs& a, int small, hipStream_t s) {
+// (A double-buffered variant on 64-position patches was measured in round 3: 1.56 vs 1.31 ms per launch -- 2.2 x as many tiles pay the per-tile
+// fixed costs; it no longer fits beside the store staging and left the tree in round 5.)
+int launch_bottleneck64(const BottleneckArgs& a, hipStream_t s) {
   constexpr int lds_stage = 4 * 4096 + 512;  // store staging + position table
   constexpr int lds_big = 192 * 512 + 192 * TP + (4 * MID + 2 * C) * 4 + lds_stage;
   static_assert(lds_big == LDS_BYTES + lds_stage && lds_big <= 160 * 1024, "LDS budget");
@@ -753,7 +754,6 @@ int launch_bottleneck64(const BottleneckArgs& a, int small, hipStream_t s) {
   // the tile walk pairs blockIdx & 7 (XCD) with blockIdx >> 3: the grid must be a whole number of 8-block rounds
   const int want = (a.n_tiles + 7) & ~7;
   const int grid = want < ncu ? want : (ncu & ~7);
-  if (small) return -1;  // the 64-position double-buffered variant (round 3, measured 1.56 vs 1.31 ms) no longer fits beside the store staging
   hipLaunchKernelGGL((bottleneck64_kernel<3, 2, 4, false>), dim3(grid), dim3(256), lds_big, s, a);
   return (int)hipGetLastError();
 }

@@ -178,7 +178,7 @@ int launch_splitk_finish(const float* partial, int ksplit, size_t plane, int ld,
 bool conv_hpipe_ok(DType dt, bool out_f32, const ConvArgs& a);
 int launch_conv_hpipe(const ConvArgs& a, hipStream_t s);
 int launch_hpipe_pack_weights(const void* w_igemm, void* w_hpipe, int Cout, int Cin, hipStream_t s);  // a.wt of an hpipe launch
-int launch_bottleneck64(const BottleneckArgs& a, int small, hipStream_t s);   // bottleneck.hip: identity block, persistent, weights in registers; small: 64-position patches, double-buffered halo
+int launch_bottleneck64(const BottleneckArgs& a, hipStream_t s);   // bottleneck.hip: identity block, persistent, weights in registers
 int launch_bottleneck64_even(const BottleneckArgs& a, hipStream_t s);  // the same block, outputs at even rows / columns only: y [B][H/2 * W/2][256]
 void bottleneck64_even_patch(int H, int W, int* ph_out, int* pw_out, int* rp_out);  // its tile (ph x pw outputs) and t1 row pitch for an H x W input
 int launch_bottleneck64p(const BottleneckArgs& a, hipStream_t s);  // first block of res2: x [pos][64], w3 = [256][128] packed [W3 | Wsc], y = relu(acc + b3)
