@@ -81,6 +81,10 @@ typedef struct sylph_config {
   int num_groups;          /* MODEL.RESNETS.NUM_GROUPS: groups of every bottleneck's 3x3 conv2 (1 = ResNet, > 1 = ResNeXt) */
   int width_per_group;     /* MODEL.RESNETS.WIDTH_PER_GROUP: conv2 channels per group in res2 (doubling per stage); the bottleneck width of
                               stage s (0 = res2) is num_groups * width_per_group << s (detectron2 build_resnet_backbone) */
+  int cg_code_ksize;       /* CODE_GENERATOR.CLS_LAYER[2]: spatial size k of a class code, 1 or 3 (GlobalAdaptiveAvgPool2d(k_s = k),
+                              code_generator.py:519-540).  A code row is 256 k^2 + 1 floats: cls_conv.reshape(-1) in (c, ky, kx) order,
+                              then the bias; the query head runs it as a k x k conv with padding k / 2 (fcos.py:499-510,
+                              head_utils.py:60-81).  The ROIEncoder (cg_type 1) ignores it (fcos.py:524): its codes stay 1x1. */
 } sylph_config;
 
 /* Fill cfg with the defaults of the COCO Meta-FCOS finetune yaml. */
@@ -133,8 +137,9 @@ int sylph_import_pyramid(sylph_ctx* ctx, int B, int padded_h, int padded_w, cons
 int sylph_export_pyramid(sylph_ctx* ctx, int level, float* out_nchw_dev);
 
 /* MetaFCOSHead.forward with support_set_per_class_code (sylph/modeling/meta_fcos/fcos.py:582-667;
- * CondConvBasic sylph/modeling/meta_fcos/head_utils.py:60-81).  cls_conv_dev: (N,256) fp32,
- * cls_bias_dev: (N) fp32 or NULL.  Results stay in the context (see sylph_export_head). */
+ * CondConvBasic sylph/modeling/meta_fcos/head_utils.py:60-81).  cls_conv_dev: (N,256,k,k) fp32 with k = cg_code_ksize
+ * (1: (N,256); 3: a 3x3 cross-correlation with zero padding 1 of the NORMALISED tower output), cls_bias_dev: (N) fp32 or NULL.
+ * Results stay in the context (see sylph_export_head). */
 int sylph_fcos_head(sylph_ctx* ctx, const float* cls_conv_dev, const float* cls_bias_dev, int N);
 /* The same for a batch whose images belong to DIFFERENT episodes: image i is run with the codes of episode image_episode[i], and its head
  * outputs (and the detections sylph_decode_nms then returns for it) are those of sylph_fcos_head with that episode's codes on the same
@@ -146,7 +151,8 @@ int sylph_fcos_head(sylph_ctx* ctx, const float* cls_conv_dev, const float* cls_
  * Afterwards sylph_decode_nms numbers classes within the image's own episode: classes_dev[i][k] < N_i, and the cand_dev ordinal is
  * (loc_base + loc) * N_i + cls.  sylph_export_head writes logits (B, max_e N_e, h, w); entries [i, n >= N_i] are unspecified.
  * bf16 with FCOS.NORM "GN" and every N_e <= 32 is one class-conditional launch for the whole batch; any other combination runs, per
- * episode, the kernel sylph_fcos_head picks for that N over the episode's images. */
+ * episode, the kernel sylph_fcos_head picks for that N over the episode's images.
+ * 1x1 codes only: with cg_code_ksize 3 (CLS_LAYER kernel size 3) the call fails. */
 int sylph_fcos_head_episodes(sylph_ctx* ctx, int E, const float* cls_conv_dev, const float* cls_bias_dev, const int* n_classes,
                              const int* image_episode);
 /* MetaFCOSHead.forward with support_set_per_class_code = None -> forward_base_train (fcos.py:543-578): the towers and the checkpoint's
@@ -178,15 +184,15 @@ int sylph_decode_nms(sylph_ctx* ctx, const int* out_heights, const int* out_widt
 
 /* CodeGenerator.forward / CodeGeneratorHead.forward_roi_align, eval branch
  * (sylph/modeling/code_generator/code_generator.py:924-1002): the current batch is the S support
- * images of ONE class; boxes_dev (S,4) fp32 XYXY (one gt box per image).  code_out_dev: 257 fp32 =
- * un-normalised cls_conv[256] ++ cls_bias[1].
+ * images of ONE class; boxes_dev (S,4) fp32 XYXY (one gt box per image).  code_out_dev: 256 k^2 + 1 fp32 (k = cg_code_ksize;
+ * 257 for the 1x1 codes) = un-normalised cls_conv[256 k^2] in (c, ky, kx) order ++ cls_bias[1].
  * With cg_type 1 this is ROIEncoder.forward (sylph/modeling/code_generator/roi_encoder.py:146-204,
  * S = EVAL_SHOT shots of one class): cls_conv[256] ++ cls_bias[1] (prior already added, no
  * normalisation step exists for this variant). */
 int sylph_codegen(sylph_ctx* ctx, const float* boxes_dev, float* code_out_dev);
 /* The same for SEVERAL classes in one batch (support-path throughput: C4 runs 866 classes x 5 shots through the R-101 backbone):
  * the current batch holds n_classes x shots support images, class k = images [k * shots, (k + 1) * shots); boxes_dev
- * (n_classes * shots, 4); codes_out_dev (n_classes, 257).  The reference computes one class per call
+ * (n_classes * shots, 4); codes_out_dev (n_classes, 256 k^2 + 1).  The reference computes one class per call
  * (meta_one_stage_detector.py:229-254); per class the arithmetic here is the same (ROIAlign, tower, GroupNorm and the shot mean
  * are per image / per class), only the launches are shared.  ROIEncoder (cg_type 1): shots = EVAL_SHOT; its encoder attends over
  * the class axis of a (classes, shots, C) tensor and sees one class per call at inference (roi_encoder.py:184-186), so a class of the
@@ -195,7 +201,7 @@ int sylph_codegen_classes(sylph_ctx* ctx, const float* boxes_dev, int shots, flo
 /* The same from a ROI LIST: R support instances over the current batch of B images, several per image if the image shows several.
  * ROI r is box boxes_dev[r] (XYXY, network-input coordinates) on image roi_image[r] in [0, B), in any order; an image may carry no
  * ROI or many.  The ROIs are cut into n_seg consecutive segments of seg_len[j] >= 1 ROIs (sum = R); row j of codes_out_dev
- * (n_seg, 257) is what ONE reference call of CodeGeneratorHead.forward_roi_align (code_generator.py:924-1002) or, with cg_type 1, of
+ * (n_seg, 256 k^2 + 1) is what ONE reference call of CodeGeneratorHead.forward_roi_align (code_generator.py:924-1002) or, with cg_type 1, of
  * ROIEncoder.forward (roi_encoder.py:146-204) gives for a support set of seg_len[j] shots whose shot i is the feature pyramid of the
  * segment's i-th ROI's image with that ROI's box.  The backbone has run once per image, not once per instance; segments never see
  * each other (shot softmax, compute_code, token mean and the length-1 attention stay inside a segment) and a segment may be longer
@@ -220,7 +226,8 @@ int sylph_roi_align(sylph_ctx* ctx, const float* boxes_dev, float* out_nchw_dev)
  * roi_image[r]; a box wholly outside its level gives zeros. */
 int sylph_roi_align_rois(sylph_ctx* ctx, int R, const float* boxes_dev, const int* roi_image, float* out_nchw_dev);
 
-/* CodeGeneratorHead.forward_normalize_code (code_generator.py:832-897): codes_dev (n,257) in place.
+/* CodeGeneratorHead.forward_normalize_code (code_generator.py:832-897): codes_dev (n, 256 k^2 + 1) in place, k = cg_code_ksize.
+ * k = 3: GroupNorm(32, 256) on (1,256,3,3) -- a group is 8 channels x 9 taps -- then F.normalize(dim = 1) per tap over the channels.
  * weight_norm_dev: (n) cls_weight_norm factors applied after the L2 normalisation (code_generator.py:838-840), or NULL. */
 int sylph_normalize_codes(sylph_ctx* ctx, float* codes_dev, int n, const float* weight_norm_dev);
 
@@ -230,7 +237,8 @@ int sylph_normalize_codes(sylph_ctx* ctx, float* codes_dev, int n, const float* 
  * the rows of a class are summed in row order (acc_weight in double).  divide_by_acc != 0: the cross-rank reduce (sums
  * divided by the accumulated weight when |1 - acc| > 1e-6, acc_weight := 1); == 0: the per-rank accumulation of
  * len/total_len-weighted chunk codes (meta_learn_evaluation.py:176-188; acc_weight := accumulated weight).
- * out_dev (num_classes, row_ld): row c = class id c (valid = 0 when no chunk of that class exists). */
+ * out_dev (num_classes, row_ld): row c = class id c (valid = 0 when no chunk of that class exists).
+ * The row layout fixes the code at 256 floats: with cg_code_ksize 3 (CLS_LAYER kernel size 3) the call fails. */
 int sylph_reduce_codes(sylph_ctx* ctx, const float* rows_dev, int n, int row_ld, float* out_dev, int num_classes,
                        int divide_by_acc);
 
@@ -240,7 +248,8 @@ int sylph_reduce_codes(sylph_ctx* ctx, const float* rows_dev, int n, int row_ld,
  * rows zero (valid = 0).  ONE in-place ncclAllGather of equal-size blocks on the context's stream (RCCL over xGMI); capacity is the
  * statically known shard size ceil(n_classes / world), so there is no count exchange and no host read-back.  comm: an ncclComm_t --
  * from sylph_comm_init_rank below or the host's own RCCL communicator.  librccl is resolved at first use (dlopen): the library has
- * no link-time dependency on it.  The Python host side keeps torch.distributed (backend "nccl" = RCCL) as its default. */
+ * no link-time dependency on it.  The Python host side keeps torch.distributed (backend "nccl" = RCCL) as its default.
+ * Fails with cg_code_ksize 3 (CLS_LAYER kernel size 3), like sylph_reduce_codes. */
 int sylph_allgather_codes(sylph_ctx* ctx, void* comm, const float* local_dev, int n_local, int capacity, float* out_dev);
 /* Communicator helpers for hosts without their own RCCL binding: rank 0 makes the 128-byte id (ncclGetUniqueId), hands it to the
  * other ranks over any channel, every rank calls init_rank (ncclCommInitRank on the context's device). */

@@ -112,17 +112,17 @@ int build_support(sylph_ctx* c, Plan* P, SupportPass* Q) {
   if (naux > 0) tap_at(Q, SYLPH_SUP_CONV_OUT, 1, Q->cg_bias_out, true, S, npos, naux, naux);
   {
     const float *co = Q->cg_conv_out, *bo = Q->cg_bias_out;
-    const int l2 = c->cfg.cg_bias_l2_norm, ib = c->cg_ib, iw = c->cg_iw, is = c->cg_is;
+    const int l2 = c->cfg.cg_bias_l2_norm, ib = c->cg_ib, iw = c->cg_iw, is = c->cg_is, ks = c->cfg.cg_code_ksize;
     float* wn = Q->cg_wnorm;
     if (Q->rois)
       ops.push_back([=](hipStream_t s) {
-        return launch_codegen_tail_segs(co, 256, bo, naux > 0 ? naux : 1, ib, iw, is, QQ->seg_dev, QQ->n_seg, QQ->max_len, npos, 256, l2,
+        return launch_codegen_tail_segs(co, 256, bo, naux > 0 ? naux : 1, ib, iw, is, QQ->seg_dev, QQ->n_seg, QQ->max_len, npos, 256, ks, l2,
                                         QQ->cur_code_out, wn, s);
       });
     else
       ops.push_back([=](hipStream_t s) {
         const int shots = QQ->cur_shots > 0 ? QQ->cur_shots : S;
-        return launch_codegen_tail(co, 256, bo, naux > 0 ? naux : 1, ib, iw, is, S / shots, shots, npos, 256, l2, QQ->cur_code_out, wn, s);
+        return launch_codegen_tail(co, 256, bo, naux > 0 ? naux : 1, ib, iw, is, S / shots, shots, npos, 256, ks, l2, QQ->cur_code_out, wn, s);
       });
   }
   Q->built = true;
@@ -456,7 +456,7 @@ int sylph_normalize_codes(sylph_ctx* c, float* codes, int n, const float* weight
   if (!c->has_codegen) return fail("code generator weights were not loaded");
   if (n <= 0) return 0;
   const float prior = c->cg_bias_prior;
-  KCHK(launch_normalize_codes(codes, n, 256, c->cg_post.gamma, c->cg_post.beta, c->cfg.cg_post_norm,
+  KCHK(launch_normalize_codes(codes, n, 256, c->cfg.cg_code_ksize, c->cg_post.gamma, c->cg_post.beta, c->cfg.cg_post_norm,
                               c->cfg.cg_conv_l2_norm, c->cg_conv_scale, c->cg_bias_scale, prior, weight_norm, c->stream),
        "normalize_codes");
   return 0;
@@ -464,6 +464,8 @@ int sylph_normalize_codes(sylph_ctx* c, float* codes, int n, const float* weight
 
 int sylph_reduce_codes(sylph_ctx* c, const float* rows, int n, int row_ld, float* out, int num_classes, int divide_by_acc) {
   if (!rows || !out) return fail("NULL argument");
+  if (c->cfg.cg_code_ksize != 1)
+    return fail("sylph_reduce_codes: the packed rows hold 1x1 class codes only (CODE_GENERATOR.CLS_LAYER kernel size 3 is not supported here)");
   if (row_ld < 262) return fail("sylph_reduce_codes: rows must be at least 262 floats wide");
   if (num_classes <= 0 || n < 0) return fail("sylph_reduce_codes: bad sizes");
   HIPCHK(hipSetDevice(c->device));

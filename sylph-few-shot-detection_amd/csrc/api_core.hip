@@ -107,6 +107,8 @@ OpFn on_side_stream(sylph_ctx* c, const OpFn& op) {
 
 int sylph_internal_fail(const std::string& m) { return fail(m); }
 
+int sylph_internal_code_ksize(sylph_ctx* c) { return c->cfg.cg_code_ksize; }
+
 hipStream_t sylph_internal_stream(sylph_ctx* c) {
   (void)hipSetDevice(c->device);
   return c->stream;
@@ -162,6 +164,7 @@ void sylph_config_default(sylph_config* cfg) {
   cfg->cg_tower_gn_mask = 0x3fffffff; cfg->cg_tower_relu_mask = 0x3fffffff;  // every TOWER_LAYERS entry is ["GN", "ReLU"]
   cfg->tower_deformable = 0;
   cfg->num_groups = 1; cfg->width_per_group = 64;
+  cfg->cg_code_ksize = 1;
 }
 
 const char* sylph_last_error(void) { return g_err.c_str(); }
@@ -230,7 +233,10 @@ int sylph_set_config(sylph_ctx* c, const sylph_config* cfg) {
     if (!ok) return fail("MODEL.RESNETS.NUM_GROUPS / WIDTH_PER_GROUP: a per-group width that is a power of two in [4, 64] at every stage "
                          "and NUM_GROUPS * WIDTH_PER_GROUP a multiple of 64 are required");
   }
+  if (cfg->cg_code_ksize != 1 && cfg->cg_code_ksize != 3)
+    return fail("CODE_GENERATOR.CLS_LAYER kernel size " + std::to_string(cfg->cg_code_ksize) + ": class codes are 1x1 or 3x3 (cg_code_ksize 1 or 3)");
   c->cfg = *cfg;
+  if (c->cfg.cg_type == 1) c->cfg.cg_code_ksize = 1;  // the ROIEncoder ignores CLS_LAYER (fcos.py:524): its codes are 1x1
   return 0;
 }
 

@@ -289,7 +289,7 @@ static CondPad cond_pad(int N) {
 //   igemm_after_apply  conv_igemm once the last cls GroupNorm, which the head ops left out, has been applied in place
 //   igemm              conv_igemm (the head ops applied every GroupNorm: fp32 storage, FCOS.NORM "none", SYLPH_FUSE_GN_LOGITS=0)
 // allow_scan = false: the kernel that writes the logits a scan left out (sylph_export_head)
-enum class HeadKind { gn_logits, scan, igemm_after_apply, igemm };
+enum class HeadKind { gn_logits, scan, igemm_after_apply, igemm, gn_cond3x3 };  // gn_cond3x3: 3x3 codes only (head_kind3x3)
 static HeadKind head_kind(const sylph_ctx* c, const Plan* P, int N, bool allow_scan = true) {
   const int fuse_scan_on = knob::fuse_scan();
   if (c->dt != DT_BF16 || !P->cls_coef) return HeadKind::igemm;
@@ -298,7 +298,8 @@ static HeadKind head_kind(const sylph_ctx* c, const Plan* P, int N, bool allow_s
 }
 
 // logits / packed-code buffers of the current batch for N classes (grown on demand; the previous buffers are released) -> o->ncls, o->logits_ld
-static int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow, HeadOut* o) {
+// codes1x1 = false: the logits alone (3x3 codes have a table of their own)
+static int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow, HeadOut* o, bool codes1x1 = true) {
   const size_t rows = (size_t)P->B * P->Ltot;
   const int Npad = cond_pad(N).Npad;
   if (Npad > P->logits_cap_ld) {
@@ -307,7 +308,7 @@ static int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow, HeadOu
     RET(c->dalloc((void**)&P->logits, rows * Npad * sizeof(float)));
     P->logits_cap_ld = Npad;
   }
-  if (Npad > P->code_w_cap) {
+  if (codes1x1 && Npad > P->code_w_cap) {
     if (P->code_w) c->dfree(P->code_w);
     P->code_w = nullptr; P->code_w_cap = 0;
     RET(c->dalloc(&P->code_w, (size_t)Npad * 256 * c->esz()));
@@ -321,6 +322,96 @@ static int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow, HeadOu
   // a quarter of the bytes (a 5-way episode: 46 MB instead of 183 MB per 64 images)
   o->logits_ld = allow_narrow && N <= 8 && head_kind(c, P, N, false) == HeadKind::gn_logits ? 8 : Npad;
   o->ncls = N;
+  return 0;
+}
+
+// the biases of a uniform head, zero-padded to Npad packed code rows (device copy: the caller's buffer need not outlive the call), and
+// behind them the copy with -inf in the padding rows that the fused scan reads
+static int ensure_bias_pad(sylph_ctx* c, Plan* P, int Npad) {
+  if (Npad <= P->bias_pad_cap) return 0;
+  if (P->bias_pad) c->dfree(P->bias_pad);
+  P->bias_pad = nullptr; P->bias_pad_cap = 0;
+  RET(c->dalloc((void**)&P->bias_pad, (size_t)2 * Npad * sizeof(float)));
+  P->bias_pad_cap = Npad;
+  return 0;
+}
+
+// the deferred last cls GroupNorm, applied in place, with a profile record of its own
+static int apply_cls_gn(sylph_ctx* c, Plan* P) {
+  const Plan* PP = P;
+  KCHK(timed_op(c, "gn_apply_partials_kernel", 0.0, c->stream, [=](hipStream_t st) { return PP->cls_apply(st); }), "gn_apply (cls tower, last layer)");
+  return 0;
+}
+
+// ---- 3x3 class codes (CODE_GENERATOR.CLS_LAYER kernel size 3; sylph_fcos_head only) ---------------------------------------------------
+// The kernel of an N-way 3x3 class-conditional conv (padding 1 on the normalised tower output):
+//   gn_cond3x3         last cls GroupNorm + ReLU + 3x3 conv in one pass (head_fused.hip): bf16, up to 32 classes, only with SYLPH_GN_COND3X3=1 --
+//                      measured 0.73 / 0.80 ms (N = 5 / 32, 64 images) against 0.63 / 0.61 ms for the two launches below, so not the default
+//   igemm_after_apply  the deferred GroupNorm apply, then add_conv on the packed codes -- what sylph_fcos_head_pretrained builds for a 3x3
+//   igemm              cls_logits, with weights that arrive per call (fp32 storage, FCOS.NORM "none", SYLPH_FUSE_GN_LOGITS=0: no apply left)
+// The fused score scan never takes 3x3 codes.
+static HeadKind head_kind3x3(const sylph_ctx* c, const Plan* P, int N) {
+  if (c->dt != DT_BF16 || !P->cls_coef) return HeadKind::igemm;
+  return (N <= 32 && knob::gn_cond3x3()) ? HeadKind::gn_cond3x3 : HeadKind::igemm_after_apply;
+}
+
+// the conv launch of the generic route for o.ncls classes, built once per (N, bias) on the plan's current buffers
+static int cond3x3_conv_ops(sylph_ctx* c, Plan* P, const HeadOut& o, const std::vector<OpFn>** ops_out) {
+  if (P->cond3_for[0] != P->code_w3 || P->cond3_for[1] != P->logits || P->cond3_for[2] != P->bias_pad) {
+    P->cond3_ops.clear();
+    P->cond3_for[0] = P->code_w3; P->cond3_for[1] = P->logits; P->cond3_for[2] = P->bias_pad;
+  }
+  const std::pair<int, int> key(o.ncls, o.has_bias ? 1 : 0);
+  auto it = P->cond3_ops.find(key);
+  if (it == P->cond3_ops.end()) {
+    ConvLayer L;
+    L.w = P->code_w3; L.shift = o.has_bias ? P->bias_pad : nullptr;
+    L.Cin = 256; L.Cout = o.ncls; L.Cout_pad = cond_pad(o.ncls).Npad; L.KH = 3; L.KW = 3;
+    ConvOpts op; op.pad = 1; op.segs_per_image = c->cfg.nlevels; op.out_f32 = true;
+    std::vector<OpFn> ops;
+    RET(add_conv(c, ops, L, P->cls_feat, 256, P->logits, o.logits_ld, pyramid_segs(c, P), op));
+    it = P->cond3_ops.emplace(key, std::move(ops)).first;
+  }
+  *ops_out = &it->second;
+  return 0;
+}
+
+// sylph_fcos_head with cg_code_ksize 3, after the checks and build_head: cls_conv is (N, 256, 3, 3)
+static int fcos_head_3x3(sylph_ctx* c, Plan* P, const float* cls_conv, const float* cls_bias, int N) {
+  HeadOut o;
+  o.src = HeadOut::cond;
+  o.has_bias = c->cfg.cond_use_bias && cls_bias;
+  RET(ensure_logits(c, P, N, false, &o, false));
+  const HeadKind k = head_kind3x3(c, P, N);
+  const int Npad = cond_pad(N).Npad;
+  if (k == HeadKind::gn_cond3x3 && N <= 8) o.logits_ld = 8;  // as gn_logits: the fused kernel stores any multiple of 4 columns
+  if (Npad > P->code_w3_cap) {
+    if (P->code_w3) c->dfree(P->code_w3);
+    P->code_w3 = nullptr; P->code_w3_cap = 0;
+    RET(c->dalloc(&P->code_w3, (size_t)Npad * 9 * 256 * c->esz()));
+    P->code_w3_cap = Npad;
+  }
+  RET(ensure_bias_pad(c, P, Npad));
+  // one launch in front of the towers, as for the 1x1 codes
+  KCHK(launch_pack_codes3x3(c->dt, cls_conv, N, 256, Npad, P->code_w3, o.has_bias ? cls_bias : nullptr, P->bias_pad, P->bias_pad + P->bias_pad_cap,
+                            c->stream), "pack_codes3x3");
+  RET(run_ops(c, P->head_ops, "fcos_head"));
+  if (k == HeadKind::gn_cond3x3) {
+    const Plan* PP = P;
+    const float* bias = o.has_bias ? P->bias_pad : nullptr;
+    const int ld = o.logits_ld;
+    KCHK(timed_op(c, "gn_cond3x3_kernel", 2.0 * (double)P->B * P->Ltot * N * 2304.0, c->stream, [=](hipStream_t st) {
+           return launch_gn_cond3x3(PP->cls_feat, 256, PP->cls_coef, PP->code_w3, bias, N, PP->logits, ld, PP->head_segs, PP->head_tiles32,
+                                    PP->head_mtiles32, st);
+         }), "gn_cond3x3");
+  } else {
+    if (k == HeadKind::igemm_after_apply) RET(apply_cls_gn(c, P));
+    const std::vector<OpFn>* ops = nullptr;
+    RET(cond3x3_conv_ops(c, P, o, &ops));
+    RET(run_ops(c, *ops, "cond_cls_logits 3x3"));
+  }
+  o.cand = HeadOut::cand_none;
+  P->out = o;
   return 0;
 }
 
@@ -513,18 +604,14 @@ int sylph_fcos_head(sylph_ctx* c, const float* cls_conv, const float* cls_bias, 
   OwnerScope own(c, P);
   P->out = HeadOut();
   BUILD(build_head(c, P), P);
+  if (c->cfg.cg_code_ksize == 3) return fcos_head_3x3(c, P, cls_conv, cls_bias, N);
   HeadOut o;
   o.src = HeadOut::cond;
   o.has_bias = c->cfg.cond_use_bias && cls_bias;
   RET(ensure_logits(c, P, N, true, &o));
   const int Npad = cond_pad(N).Npad;
   // the biases, zero-padded to the packed code rows (device copy: the caller's buffer need not outlive this call)
-  if (Npad > P->bias_pad_cap) {
-    if (P->bias_pad) c->dfree(P->bias_pad);
-    P->bias_pad = nullptr; P->bias_pad_cap = 0;
-    RET(c->dalloc((void**)&P->bias_pad, (size_t)2 * Npad * sizeof(float)));
-    P->bias_pad_cap = Npad;
-  }
+  RET(ensure_bias_pad(c, P, Npad));
   // one launch: packed codes + zero-padded biases + the -inf padded copy the fused scan reads
   // (in FRONT of the towers: it depends on the caller's codes only, and at small batches the main stream waits for the bbox tower on the
   // side stream at the end of the head ops anyway -- behind them it was 5 us of the step's serial tail)
@@ -542,6 +629,9 @@ int sylph_fcos_head(sylph_ctx* c, const float* cls_conv, const float* cls_bias, 
 int sylph_fcos_head_episodes(sylph_ctx* c, int E, const float* cls_conv, const float* cls_bias, const int* n_classes, const int* image_episode) {
   Plan* P = c->cur;
   if (!P) return fail("no current batch");
+  if (c->cfg.cg_code_ksize != 1)
+    return fail("sylph_fcos_head_episodes runs 1x1 class codes only (CODE_GENERATOR.CLS_LAYER kernel size " + std::to_string(c->cfg.cg_code_ksize) +
+                " is not supported here; use sylph_fcos_head per episode)");
   if (E <= 0) return fail("no episodes (E <= 0)");
   if (!cls_conv) return fail("cls_conv is NULL");
   if (!n_classes || !image_episode) return fail("n_classes / image_episode is NULL");
@@ -603,7 +693,7 @@ int sylph_fcos_head_pretrained(sylph_ctx* c, int* num_classes) {
     P->cls_logits_dst = P->logits;
   }
   RET(run_ops(c, P->head_ops, "fcos_head"));
-  if (P->cls_coef) KCHK(P->cls_apply(c->stream), "gn_apply (cls tower, last layer)");
+  if (P->cls_coef) RET(apply_cls_gn(c, P));
   RET(run_ops(c, P->cls_logits_ops, "cls_logits"));
   if (num_classes) *num_classes = N;
   P->out = o;

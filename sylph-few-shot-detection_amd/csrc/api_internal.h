@@ -27,6 +27,7 @@ using sylph_host::fail;
 // collective.hip
 hipStream_t sylph_internal_stream(sylph_ctx* c);
 int sylph_internal_fail(const std::string& m);
+int sylph_internal_code_ksize(sylph_ctx* c);
 #define HIPCHK(x)                                                                                  \
   do {                                                                                             \
     hipError_t e_ = (x);                                                                           \
@@ -87,6 +88,7 @@ SYLPH_KNOB_ONCE(fuse_stem_pool, "SYLPH_FUSE_STEM_POOL", 1)   // 0: stem_conv + m
 SYLPH_KNOB_ONCE(head_streams, "SYLPH_HEAD_STREAMS", 1)       // 0 one stream, 1 two for small batches (FPN top and bbox tower on the side stream), 2 always two
 SYLPH_KNOB_ONCE(gn_fuse, "SYLPH_GN_FUSE", 1)                 // 0: every tower GroupNorm as its own apply pass
 SYLPH_KNOB_ONCE(fuse_gn_logits, "SYLPH_FUSE_GN_LOGITS", 1)   // 0: the head ops apply the last cls GroupNorm themselves
+SYLPH_KNOB_LIVE(gn_cond3x3, "SYLPH_GN_COND3X3", 0)          // 1: 3x3 class codes, bf16, N <= 32 through gn_cond3x3_kernel (off: it does not beat apply + conv_igemm yet); per head call
 SYLPH_KNOB_ONCE(fuse_scan, "SYLPH_FUSE_SCAN", 1)             // 0 never, 1 more than 32 classes, 2 any class count
 SYLPH_KNOB_LIVE(fuse_preprocess, "SYLPH_FUSE_PREPROCESS", 1)  // 0: a normalised copy of the batch; per sylph_preprocess call
 SYLPH_KNOB_LIVE(fuse_shortcut, "SYLPH_FUSE_SHORTCUT", 1)     // 0: conv3 and the projection shortcut as two convs; per sylph_finalize_weights /
@@ -323,6 +325,12 @@ struct Plan {
   void* code_w = nullptr;   // packed class codes [Npad][256]
   void* code_wf = nullptr;  // the same in MFMA fragment order (logits_scan_kernel), same capacity
   int code_w_cap = 0;
+  // 3x3 class codes (cg_code_ksize 3): packed [Npad][3][3][256] (pack_conv's layout) and, per (N, bias or not), the conv launch add_conv
+  // built on them -- valid while the buffers it captured are the plan's (cond3_for)
+  void* code_w3 = nullptr;
+  int code_w3_cap = 0;
+  std::map<std::pair<int, int>, std::vector<OpFn>> cond3_ops;
+  const void* cond3_for[3] = {nullptr, nullptr, nullptr};  // code_w3, logits, bias_pad the ops read
   const SegDesc* head_segs = nullptr;
   const int2 *head_tiles = nullptr, *head_tiles32 = nullptr;
   int head_mtiles = 0, head_BM = 128, head_mtiles32 = 0;

@@ -102,20 +102,39 @@ int launch_roi_align_rois(DType dt, const void* feats, int ld, const LevelDesc* 
   return (int)hipGetLastError();
 }
 
-// The S shots of one class (conv_out / aux_out at its first row) combined with the shot weights wsh[S] (LDS, complete): code_out[0, C)
+// The S shots of one class (conv_out / aux_out at its first row) combined with the shot weights wsh[S] (LDS, complete): code_out[0, C k^2)
 // by all threads, the bias and class-scale heads by the first wave.  Shared by the equal-classes and the ragged-segments kernel: a
 // class's arithmetic is the same whichever way its rows were found.
+// ksize 3 (CLS_LAYER kernel size 3): F.adaptive_avg_pool2d(., (3, 3)) of the 7 x 7 map instead of the global mean -- bin i of an axis is
+// [floor(7 i / 3), ceil(7 (i + 1) / 3)) = [0,3), [2,5), [4,7): nine positions per bin, neighbours overlap in one row / column -- into
+// code_out[(c * 3 + ky) * 3 + kx], torch's (c, ky, kx) order; every value of a shot gets the shot's one weight (compute_code,
+// code_generator.py:778-829).  The bias, shot-weight and class-scale heads stay globally pooled.
 __device__ __forceinline__ void codegen_tail_shots(const float* __restrict__ conv_out, int conv_ld, const float* __restrict__ aux_out,
-                                                   int aux_ld, int ib, int is, int S, int npos, int C, int bias_l2_norm,
+                                                   int aux_ld, int ib, int is, int S, int npos, int C, int ksize, int bias_l2_norm,
                                                    const float* wsh, float* __restrict__ code_out, float* __restrict__ wnorm_out) {
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    float code = 0.f;
-    for (int s = 0; s < S; ++s) {
-      float sum = 0.f;
-      for (int p = 0; p < npos; ++p) sum += conv_out[((size_t)s * npos + p) * conv_ld + c];
-      code += wsh[s] * (sum / (float)npos);
+  if (ksize == 3) {
+    for (int i = threadIdx.x; i < C * 9; i += blockDim.x) {  // npos == 49
+      const int c = i / 9, t = i - c * 9, ky = t / 3, kx = t - ky * 3;
+      const int y0 = (ky * 7) / 3, x0 = (kx * 7) / 3;  // three positions from there on either axis
+      float code = 0.f;
+      for (int s = 0; s < S; ++s) {
+        float sum = 0.f;
+        for (int dy = 0; dy < 3; ++dy)
+          for (int dx = 0; dx < 3; ++dx) sum += conv_out[((size_t)s * npos + (y0 + dy) * 7 + x0 + dx) * conv_ld + c];
+        code += wsh[s] * (sum / 9.f);
+      }
+      code_out[i] = code;
     }
-    code_out[c] = code;
+  } else {
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+      float code = 0.f;
+      for (int s = 0; s < S; ++s) {
+        float sum = 0.f;
+        for (int p = 0; p < npos; ++p) sum += conv_out[((size_t)s * npos + p) * conv_ld + c];
+        code += wsh[s] * (sum / (float)npos);
+      }
+      code_out[c] = code;
+    }
   }
   if (threadIdx.x < 64) {  // one wave: bias and class-scale heads
     const int lane = threadIdx.x;
@@ -140,24 +159,24 @@ __device__ __forceinline__ void codegen_tail_shots(const float* __restrict__ con
       }
     }
     if (lane == 0) {
-      code_out[C] = bias;
+      code_out[C * ksize * ksize] = bias;
       if (wnorm_out) wnorm_out[blockIdx.x] = wn;
     }
   }
 }
 
 // conv_out [ncls*S*npos][conv_ld] fp32, aux_out [ncls*S*npos][aux_ld] fp32 (channel ib: bias head, iw: shot-weight head, is: class-scale
-// head; -1 = absent) -> code_out[ncls][C+1] (+ wnorm_out[ncls] with a scale head); one block per class (its S consecutive support
+// head; -1 = absent) -> code_out[ncls][C * ksize^2 + 1] (+ wnorm_out[ncls] with a scale head); one block per class (its S consecutive support
 // images: the arithmetic of a class does not depend on how many classes share the batch).
 // code_generator.py:766-829: per shot the heads are global-average-pooled, the shots are combined with uniform weights 1/S or, with a
 // WEIGHT_LAYER, with softmax(pooled shot-weight logits) over the shots of the class.
 __global__ __launch_bounds__(256) void codegen_tail_kernel(const float* __restrict__ conv_out, int conv_ld,
                                                            const float* __restrict__ aux_out, int aux_ld, int ib, int iw, int is, int S,
-                                                           int npos, int C, int bias_l2_norm, float* __restrict__ code_out,
+                                                           int npos, int C, int ksize, int bias_l2_norm, float* __restrict__ code_out,
                                                            float* __restrict__ wnorm_out) {
   conv_out += (size_t)blockIdx.x * S * npos * conv_ld;
   aux_out += (size_t)blockIdx.x * S * npos * aux_ld;
-  code_out += (size_t)blockIdx.x * (C + 1);
+  code_out += (size_t)blockIdx.x * (C * ksize * ksize + 1);
   __shared__ float wsh[64];  // per-shot weights (S <= 64)
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
@@ -179,14 +198,14 @@ __global__ __launch_bounds__(256) void codegen_tail_kernel(const float* __restri
     }
   }
   __syncthreads();
-  codegen_tail_shots(conv_out, conv_ld, aux_out, aux_ld, ib, is, S, npos, C, bias_l2_norm, wsh, code_out, wnorm_out);
+  codegen_tail_shots(conv_out, conv_ld, aux_out, aux_ld, ib, is, S, npos, C, ksize, bias_l2_norm, wsh, code_out, wnorm_out);
 }
 
 int launch_codegen_tail(const float* conv_out, int conv_ld, const float* aux_out, int aux_ld, int ib, int iw, int is, int ncls, int S, int npos,
-                        int C, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s) {
-  if (npos > 64 || ncls < 1 || S > 64) return -1;
-  hipLaunchKernelGGL(codegen_tail_kernel, dim3(ncls), dim3(256), 0, s, conv_out, conv_ld, aux_out, aux_ld, ib, iw, is, S, npos, C, bias_l2_norm,
-                     code_out, is >= 0 ? wnorm_out : nullptr);
+                        int C, int ksize, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s) {
+  if (npos > 64 || ncls < 1 || S > 64 || (ksize != 1 && !(ksize == 3 && npos == 49))) return -1;
+  hipLaunchKernelGGL(codegen_tail_kernel, dim3(ncls), dim3(256), 0, s, conv_out, conv_ld, aux_out, aux_ld, ib, iw, is, S, npos, C, ksize,
+                     bias_l2_norm, code_out, is >= 0 ? wnorm_out : nullptr);
   return (int)hipGetLastError();
 }
 
@@ -197,13 +216,13 @@ int launch_codegen_tail(const float* conv_out, int conv_ld, const float* aux_out
 // lane, i.e. the plain kernel's reduction bit for bit.
 __global__ __launch_bounds__(256) void codegen_tail_segs_kernel(const float* __restrict__ conv_out, int conv_ld,
                                                                 const float* __restrict__ aux_out, int aux_ld, int ib, int iw, int is,
-                                                                const int2* __restrict__ seg, int npos, int C, int bias_l2_norm,
+                                                                const int2* __restrict__ seg, int npos, int C, int ksize, int bias_l2_norm,
                                                                 float* __restrict__ code_out, float* __restrict__ wnorm_out) {
   extern __shared__ float wsh[];  // per-shot weights: max(64, longest segment) floats
   const int S = seg[blockIdx.x].y;
   conv_out += (size_t)seg[blockIdx.x].x * npos * conv_ld;
   aux_out += (size_t)seg[blockIdx.x].x * npos * aux_ld;
-  code_out += (size_t)blockIdx.x * (C + 1);
+  code_out += (size_t)blockIdx.x * (C * ksize * ksize + 1);
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
     if (iw >= 0) {  // softmax over the shots of the pooled logits (torch.nn.Softmax(dim=1), fp32)
@@ -229,21 +248,21 @@ __global__ __launch_bounds__(256) void codegen_tail_segs_kernel(const float* __r
     }
   }
   __syncthreads();
-  codegen_tail_shots(conv_out, conv_ld, aux_out, aux_ld, ib, is, S, npos, C, bias_l2_norm, wsh, code_out, wnorm_out);
+  codegen_tail_shots(conv_out, conv_ld, aux_out, aux_ld, ib, is, S, npos, C, ksize, bias_l2_norm, wsh, code_out, wnorm_out);
 }
 
 constexpr int TAIL_SEGS_MAX_LEN = 16384;  // 64 KiB of shot weights in LDS
 
 int launch_codegen_tail_segs(const float* conv_out, int conv_ld, const float* aux_out, int aux_ld, int ib, int iw, int is, const int2* seg_dev,
-                             int n_seg, int max_len, int npos, int C, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s) {
-  if (npos > 64 || n_seg < 1 || max_len < 1 || max_len > TAIL_SEGS_MAX_LEN) return -1;
+                             int n_seg, int max_len, int npos, int C, int ksize, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s) {
+  if (npos > 64 || n_seg < 1 || max_len < 1 || max_len > TAIL_SEGS_MAX_LEN || (ksize != 1 && !(ksize == 3 && npos == 49))) return -1;
   const size_t lds = (size_t)(max_len > 64 ? max_len : 64) * sizeof(float);
   hipLaunchKernelGGL(codegen_tail_segs_kernel, dim3(n_seg), dim3(256), lds, s, conv_out, conv_ld, aux_out, aux_ld, ib, iw, is, seg_dev, npos, C,
-                     bias_l2_norm, code_out, is >= 0 ? wnorm_out : nullptr);
+                     ksize, bias_l2_norm, code_out, is >= 0 ? wnorm_out : nullptr);
   return (int)hipGetLastError();
 }
 
-// codes [ncodes][C+1] in place; one block of 256 threads per code, C == 256 (8 channels / group)
+// 1x1 codes [ncodes][C+1] in place; one block of 256 threads per code, C == 256 (8 channels / group)
 __global__ __launch_bounds__(256) void normalize_codes_kernel(float* __restrict__ codes, int C,
                                                               const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, int post_norm,
@@ -278,10 +297,63 @@ __global__ __launch_bounds__(256) void normalize_codes_kernel(float* __restrict_
   if (c == 0) code[C] = code[C] * bias_scale + bias_prior;
 }
 
-int launch_normalize_codes(float* codes, int ncodes, int C, const float* gn_gamma, const float* gn_beta,
+// The same for 3x3 codes [ncodes][C * 9 + 1], value (c, ky, kx) at (c * 3 + ky) * 3 + kx (normalize_code on a (1, C, 3, 3) tensor,
+// code_generator.py:832-843): thread c holds the nine taps of channel c.  GroupNorm(32, C): a group is 8 channels x 9 taps = 72 values
+// (biased variance, eps 1e-5, per-channel affine); F.normalize(p = 2, dim = 1): per TAP over the C channels.
+__global__ __launch_bounds__(256) void normalize_codes3_kernel(float* __restrict__ codes, int C, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, int post_norm, int l2_norm, float conv_scale,
+                                                               float bias_scale, float bias_prior, const float* __restrict__ weight_norm) {
+  float* code = codes + (size_t)blockIdx.x * (C * 9 + 1);
+  const int c = threadIdx.x;
+  float v[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) v[t] = code[c * 9 + t];
+  if (post_norm) {
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) s += v[t];
+    for (int o = 4; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float mean = s / 72.f;
+    float q = 0.f;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) { v[t] -= mean; q += v[t] * v[t]; }
+    for (int o = 4; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    const float rstd = 1.0f / sqrtf(q / 72.f + 1e-5f);
+    const float ga = gamma[c], be = beta[c];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) v[t] = v[t] * rstd * ga + be;
+  }
+  if (l2_norm) {
+    __shared__ float part[4][9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      float sq = v[t] * v[t];
+      for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+      if ((c & 63) == 0) part[c >> 6][t] = sq;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < 9; ++t) v[t] = v[t] / fmaxf(sqrtf(part[0][t] + part[1][t] + part[2][t] + part[3][t]), 1e-12f);
+  }
+  const float wn = weight_norm ? weight_norm[blockIdx.x] : 1.f;
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    float r = v[t];
+    if (weight_norm) r = r * wn;  // x cls_weight_norm (code_generator.py:838-840)
+    code[c * 9 + t] = r * conv_scale;
+  }
+  if (c == 0) code[C * 9] = code[C * 9] * bias_scale + bias_prior;
+}
+
+int launch_normalize_codes(float* codes, int ncodes, int C, int ksize, const float* gn_gamma, const float* gn_beta,
                            int post_norm, int l2_norm, float conv_scale, float bias_scale, float bias_prior,
                            const float* weight_norm, hipStream_t s) {
-  if (C != 256) return -1;
+  if (C != 256 || (ksize != 1 && ksize != 3)) return -1;
+  if (ksize == 3) {
+    hipLaunchKernelGGL(normalize_codes3_kernel, dim3(ncodes), dim3(256), 0, s, codes, C, gn_gamma, gn_beta, post_norm, l2_norm, conv_scale,
+                       bias_scale, bias_prior, weight_norm);
+    return (int)hipGetLastError();
+  }
   hipLaunchKernelGGL(normalize_codes_kernel, dim3(ncodes), dim3(256), 0, s, codes, C, gn_gamma, gn_beta, post_norm,
                      l2_norm, conv_scale, bias_scale, bias_prior, weight_norm);
   return (int)hipGetLastError();

@@ -16,6 +16,7 @@
 
 hipStream_t sylph_internal_stream(sylph_ctx* c);  // api_core.hip
 int sylph_internal_fail(const std::string& m);     // sets sylph_last_error(), returns 1
+int sylph_internal_code_ksize(sylph_ctx* c);       // sylph_config::cg_code_ksize of the context
 
 namespace {
 
@@ -119,6 +120,8 @@ int sylph_comm_destroy(void* comm) {
 }
 
 int sylph_allgather_codes(sylph_ctx* c, void* comm, const float* local_dev, int n_local, int capacity, float* out_dev) {
+  if (c && sylph_internal_code_ksize(c) != 1)
+    return sylph_internal_fail("sylph_allgather_codes: the packed 280-float rows hold 1x1 class codes only (CODE_GENERATOR.CLS_LAYER kernel size 3 is not supported here)");
   Rccl* R = rccl();
   if (!R->h) return sylph_internal_fail(R->err);
   if (!c || !comm || !out_dev || (n_local > 0 && !local_dev)) return sylph_internal_fail("sylph_allgather_codes: NULL argument");

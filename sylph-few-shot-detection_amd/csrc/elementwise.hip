@@ -591,6 +591,44 @@ int launch_pack_codes(DType dt, const float* w, int N, int C, int Npad, void* ou
   return (int)hipGetLastError();
 }
 
+// 3x3 class codes (N,C,3,3) fp32, torch's (n, c, ky, kx) order -> [Npad][3][3][C]: the weight layout of pack_conv (api_weights.hip), so that
+// add_conv runs them like a checkpoint's 3x3 classifier.  One thread per OUTPUT element (coalesced stores; a code set is a few hundred
+// KiB).  Biases as in pack_codes_kernel.  SPLIT: every 32-element K-slice as [32 bf16 hi | 32 bf16 lo].
+template <typename T, bool SPLIT>
+__global__ void pack_codes3x3_kernel(const float* __restrict__ w, int N, int C, int Npad, T* __restrict__ out, const float* __restrict__ bias,
+                                     float* __restrict__ bias_pad, float* __restrict__ bias_scan) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < Npad) {
+    const float b = (bias && i < N) ? bias[i] : 0.f;
+    if (bias_pad) bias_pad[i] = b;
+    if (bias_scan) bias_scan[i] = i < N ? b : __uint_as_float(0xff800000u);
+  }
+  if (i >= Npad * 9 * C) return;
+  const int n = i / (9 * C), r = i - n * 9 * C, t = r / C, c = r - t * C;
+  const float v = n < N ? w[((size_t)n * C + c) * 9 + t] : 0.f;
+  if constexpr (SPLIT) {
+    const bf16_t hi = (bf16_t)v;
+    const size_t o = (size_t)(i >> 5) * 64 + (i & 31);  // C % 32 == 0: slices do not straddle taps
+    out[o] = hi;
+    out[o + 32] = (bf16_t)(v - (float)hi);
+  } else {
+    out[i] = Cvt<T>::from_f(v);
+  }
+}
+
+int launch_pack_codes3x3(DType dt, const float* w, int N, int C, int Npad, void* out, const float* bias, float* bias_pad, float* bias_scan,
+                         hipStream_t s) {
+  if (C % 32 != 0 || N < 1 || Npad < N) return -1;
+  dim3 grid((Npad * 9 * C + 255) / 256), block(256);
+  if (dt == DT_F32S)
+    hipLaunchKernelGGL((pack_codes3x3_kernel<bf16_t, true>), grid, block, 0, s, w, N, C, Npad, (bf16_t*)out, bias, bias_pad, bias_scan);
+  else if (dt == DT_BF16)
+    hipLaunchKernelGGL((pack_codes3x3_kernel<bf16_t, false>), grid, block, 0, s, w, N, C, Npad, (bf16_t*)out, bias, bias_pad, bias_scan);
+  else
+    hipLaunchKernelGGL((pack_codes3x3_kernel<float, false>), grid, block, 0, s, w, N, C, Npad, (float*)out, bias, bias_pad, bias_scan);
+  return (int)hipGetLastError();
+}
+
 // launch_pack_codes for the episodes of a mixed batch (sylph_fcos_head_episodes): every episode's rows, zero-padded to its own tile
 // width, behind one another in ONE table -- the launch count of a mixed step does not grow with the number of episodes
 template <typename T, bool SPLIT>

@@ -287,6 +287,160 @@ int launch_gn_pred_taps(const void* x, int ld, const float2* coef, const void* w
   return (int)hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Last GroupNorm + ReLU of the cls tower fused into a 3x3 class-conditional conv (CODE_GENERATOR.CLS_LAYER kernel size 3, N <= 32), bf16:
+//
+//   logits[p][n] = sum_(ky, kx) sum_c xn[p + (ky - 1) W + (kx - 1)][c] * W[n][ky][kx][c] + bias[n],   xn = bf16(relu(a x + b))
+//
+// `F.conv2d(cls_tower, W, bias, padding = 1)` of CondConvBasic (head_utils.py:60-81, fcos.py:499-510): a cross-correlation whose zero
+// padding applies to the NORMALISED tensor -- a tap whose source lies outside the (image, level) map contributes zero, not relu(b).
+// The operand values are gn_logits_kernel's (same fma, same rounding point); xn is never written to HBM.  The nine taps' B fragments are
+// 9 x 64 VGPRs, more than one wave has: a block is THREE waves, wave ky holds the three taps of kernel row ky (192 VGPRs) and walks the
+// same 32-position groups as its siblings.  For a group at map-relative rows [r0, r0 + 32) the taps of kernel row ky read the 34
+// CONTIGUOUS rows [r0 + (ky - 1) W - 1, r0 + (ky - 1) W + 33): the wave loads that strip once (coalesced 16-byte pieces: a lane keeps one
+// 8-channel column of the strip, so its 16 GroupNorm coefficients live in registers), normalises it once and leaves it in wave-private
+// LDS; tap kx of output row j is strip row j + kx (row pitch 528 bytes: the 16-byte operand reads of 32 consecutive rows fall on
+// different banks).  A strip row outside the map is clamped to a valid row: every output that would read it is masked.  Each tap has
+// its own accumulator; in the D^T layout a lane holds ONE position's 16 classes, so the zero padding is a per-lane select of whole
+// accumulators (tap row outside the map: all three; column -1 / W: the kx = 0 / 2 one).  The next group's strip is loaded while the
+// MFMAs of the current one run.  The three kernel rows' 32 x 32 partials are summed in the fixed order ky = 0, 1, 2 through LDS (two
+// buffers, one barrier per group) and wave 0 writes the logits once.
+constexpr int C3_PITCH = 528;  // bytes per strip row in LDS
+__global__ __launch_bounds__(192) void gn_cond3x3_kernel(const bf16_t* __restrict__ x, int ld, const float2* __restrict__ coef,
+                                                         const bf16_t* __restrict__ w, const float* __restrict__ bias, int N,
+                                                         float* __restrict__ out, int out_ld, const SegDesc* __restrict__ segs,
+                                                         const int2* __restrict__ tiles, int n_tiles) {
+  __shared__ __attribute__((aligned(16))) unsigned char strip[3][34 * C3_PITCH];  // per wave: the normalised strip of its current group
+  __shared__ __attribute__((aligned(16))) float red[2][2][1024];                   // [group parity][wave 1 | 2]: register r of lane l at r * 64 + l
+  const int tid = threadIdx.x, lane = tid & 63, ky = tid >> 6, l31 = lane & 31, lh = lane >> 5;
+  bf16x8 Wf[3][16];  // B operands of taps (ky, 0..2): lane (n = l31, k half lh)
+#pragma unroll
+  for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks)
+      Wf[kx][ks] = *reinterpret_cast<const bf16x8*>(w + ((size_t)l31 * 9 + ky * 3 + kx) * 256 + ks * 16 + lh * 8);
+  float bs[16];  // D^T: register 4q + e of a lane is class 8q + 4lh + e of row l31
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int n = 8 * q + 4 * lh + e;
+      bs[4 * q + e] = (bias && n < N) ? bias[n] : 0.f;
+    }
+  const int end = n_tiles * 4;
+  // the groups of a block: the four of a tile, then the tile one grid stride on; groups past the end of a short level are skipped
+  // (block-uniform: the three waves walk the same groups)
+  auto group_r0 = [&](int g) { return tiles[g >> 2].y + (g & 3) * 32; };
+  auto group_rows = [&](int g) { const SegDesc& sd = segs[tiles[g >> 2].x]; return sd.out_H * sd.out_W; };
+  auto next_group = [&](int g) {
+    do g = (g & 3) == 3 ? g - 3 + (int)gridDim.x * 4 : g + 1;
+    while (g < end && group_r0(g) >= group_rows(g));
+    return g;
+  };
+  // a lane's pieces of a strip: piece it * 64 + lane = (strip row 2 it + lh, 8-channel column l31), 17 pieces = 34 rows
+  u32x4 xv[17];
+  auto load_strip = [&](int g) {
+    const SegDesc& sd = segs[tiles[g >> 2].x];
+    const int nrows = sd.out_H * sd.out_W, first = group_r0(g) + (ky - 1) * sd.out_W - 1;
+    const bf16_t* base = x + (size_t)sd.out_row0 * ld + l31 * 8;
+#pragma unroll
+    for (int it = 0; it < 17; ++it) {
+      const int r = min(max(first + 2 * it + lh, 0), nrows - 1);
+      xv[it] = *reinterpret_cast<const u32x4*>(base + (size_t)r * ld);
+    }
+  };
+  f32x2 ca[4], cb[4];  // (a, b) of the lane's 8 channels, as pairs
+  int cur_seg = -1, par = 0;
+  int g = blockIdx.x * 4;  // (the first group of a tile is never empty)
+  if (g < end) load_strip(g);
+  while (g < end) {
+    const int seg = tiles[g >> 2].x, r0 = group_r0(g);
+    const SegDesc& sd = segs[seg];
+    const int Hm = sd.out_H, Wm = sd.out_W, nrows = Hm * Wm;
+    if (seg != cur_seg) {
+      cur_seg = seg;
+      const float2* cp = coef + (size_t)seg * 256 + l31 * 8;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float2 c0 = cp[2 * e], c1 = cp[2 * e + 1];
+        ca[e] = f32x2{c0.x, c1.x};
+        cb[e] = f32x2{c0.y, c1.y};
+      }
+    }
+    // normalise the strip once: bf16(relu(fma(a, x, b))) -> LDS
+#pragma unroll
+    for (int it = 0; it < 17; ++it) {
+      u32x4 yv;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const f32x2 xf = {__uint_as_float(xv[it][e] << 16), __uint_as_float(xv[it][e] & 0xffff0000u)};
+        const f32x2 r = __builtin_elementwise_fma(xf, ca[e], cb[e]);
+        bf16x2 pk;
+        pk[0] = (bf16_t)r[0];
+        pk[1] = (bf16_t)r[1];
+        const s16x2 z = {0, 0};
+        yv[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pk), z));  // ReLU on the bf16 pair
+      }
+      *reinterpret_cast<u32x4*>(&strip[ky][(2 * it + lh) * C3_PITCH + l31 * 16]) = yv;
+    }
+    const int gn = next_group(g);
+    if (gn < end) load_strip(gn);  // in flight under the MFMAs below
+    f32x16 acc[3];
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[kx][r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const bf16x8 yv = *reinterpret_cast<const bf16x8*>(&strip[ky][(l31 + kx) * C3_PITCH + ks * 32 + lh * 16]);
+        acc[kx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[kx][ks], yv, acc[kx], 0, 0, 0);
+      }
+    // zero padding of the normalised tensor, per position = per lane
+    const int row = r0 + l31;
+    const bool valid = row < nrows;
+    const int own = valid ? row : nrows - 1;
+    const int py = own / Wm, px = own - py * Wm;
+    const bool mrow = valid && (unsigned)(py + ky - 1) < (unsigned)Hm;
+    const bool m0 = mrow && px > 0, m2 = mrow && px < Wm - 1;
+    f32x16 sum;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sum[r] = ((m0 ? acc[0][r] : 0.f) + (mrow ? acc[1][r] : 0.f)) + (m2 ? acc[2][r] : 0.f);
+    if (ky != 0) {
+      float* rp = &red[par][ky - 1][lane];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) rp[r * 64] = sum[r];
+    }
+    __syncthreads();
+    if (ky == 0 && valid) {
+      const float *r1 = &red[par][0][lane], *r2 = &red[par][1][lane];
+      float* op = out + (size_t)(sd.out_row0 + row) * out_ld + 4 * lh;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (8 * q + 4 * lh < out_ld) {  // out_ld: any multiple of 4 >= N (8 for <= 8 classes)
+          float v[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = (sum[4 * q + e] + r1[(4 * q + e) * 64]) + r2[(4 * q + e) * 64] + bs[4 * q + e];
+          *reinterpret_cast<float4*>(op + 8 * q) = make_float4(v[0], v[1], v[2], v[3]);
+        }
+    }
+    par ^= 1;  // the next group's partials go to the other buffer: wave 0 may still be reading this one
+    g = gn;
+  }
+}
+
+// x: raw (un-normalised) tower output [rows][ld] bf16; coef: [segments][256] (a, b); w: [32][3][3][256] bf16 (rows >= N zero);
+// out: fp32 [rows][out_ld], out_ld a multiple of 4 >= N; segs / tiles: the 128-row pointwise tile table of the head
+int launch_gn_cond3x3(const void* x, int ld, const float2* coef, const void* w, const float* bias, int N, float* out, int out_ld,
+                      const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s) {
+  if (N > 32 || out_ld < N || (out_ld & 3) != 0 || n_tiles <= 0) return -1;
+  const int grid = n_tiles < HEAD_STREAM_MAX_BLOCKS ? n_tiles : HEAD_STREAM_MAX_BLOCKS;  // one block = one 128-row tile per sweep
+  hipLaunchKernelGGL(gn_cond3x3_kernel, dim3(grid), dim3(192), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, N, out, out_ld, segs,
+                     tiles, n_tiles);
+  return (int)hipGetLastError();
+}
+
 // x: raw (un-normalised) tower output [rows][ld] bf16; coef: [segments][256] (a, b); w: [32][256] bf16 (rows >= N zero);
 // out: fp32 [rows][out_ld], out_ld a multiple of 4 >= N; segs / tiles: the 128-row pointwise tile table of the head
 int launch_gn_logits(const void* x, int ld, const float2* coef, const void* w, const float* bias, int N, float* out, int out_ld,

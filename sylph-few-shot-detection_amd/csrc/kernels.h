@@ -90,6 +90,9 @@ int launch_gn_logits(const void* x, int ld, const float2* coef, const void* w, c
                      const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s);  // head_fused.hip (bf16, N <= 32)
 // the same for a batch whose images belong to different episodes: w / bias hold every episode's 32 zero-padded rows, seg_row0[seg] the
 // first row of the block of the segment's image
+// the 3x3 sibling (CLS_LAYER kernel size 3): w [32][3][3][256] bf16 (launch_pack_codes3x3), zero padding of the normalised tensor
+int launch_gn_cond3x3(const void* x, int ld, const float2* coef, const void* w, const float* bias, int N, float* out, int out_ld,
+                      const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s);
 int launch_gn_logits_episodes(const void* x, int ld, const float2* coef, const void* w, const float* bias, const int* seg_row0, float* out,
                               int out_ld, const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s);
 int launch_gn_pred_taps(const void* x, int ld, const float2* coef, const void* w_taps, int cp, const float* bias, int relu_nch, int mul_nch,
@@ -113,6 +116,10 @@ int launch_import_nchw(DType dt, const float* src, void* dst, int C, int HW, int
 int launch_export_nchw(DType dt, const void* src, float* dst, int C, int HW, int row0, int ld, hipStream_t s);
 int launch_export_nchw_f32(const float* src, float* dst, int C, int HW, int row0, int ld, int ch0, hipStream_t s);
 int launch_pack_codes(DType dt, const float* w, int N, int C, int Npad, void* out, const float* bias, float* bias_pad, float* bias_scan, hipStream_t s);
+// 3x3 class codes (N,C,3,3) fp32 -> [Npad][3][3][C] in the compute dtype (pack_conv's layout, DT_F32S: its split hi / lo form), zero
+// padding rows; biases as launch_pack_codes pads them
+int launch_pack_codes3x3(DType dt, const float* w, int N, int C, int Npad, void* out, const float* bias, float* bias_pad, float* bias_scan,
+                         hipStream_t s);
 // several episodes' codes in one launch: packed row r takes row src_row[r] of w / bias, or zeros (bias_scan: -inf) where src_row[r] < 0
 int launch_pack_codes_episodes(DType dt, const float* w, const int* src_row, int rows, int C, void* out, const float* bias, float* bias_pad,
                                float* bias_scan, hipStream_t s);
@@ -170,11 +177,11 @@ int launch_roi_align(DType dt, const void* feats, int ld, const LevelDesc* lv_de
 int launch_roi_align_rois(DType dt, const void* feats, int ld, const LevelDesc* lv_dev, int nlevels, const float* boxes_dev,
                           const int* roi_image_dev, int R, int out_size, void* out, hipStream_t s);  // row r: box r on image roi_image[r]
 int launch_codegen_tail(const float* conv_out, int conv_ld, const float* aux_out, int aux_ld, int ib, int iw, int is, int ncls, int S, int npos,
-                        int C, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s);
+                        int C, int ksize, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s);
 // ragged segments of a ROI list: seg_dev[j] = {first row, rows}; max_len = the longest segment (sizes the LDS weight table)
 int launch_codegen_tail_segs(const float* conv_out, int conv_ld, const float* aux_out, int aux_ld, int ib, int iw, int is, const int2* seg_dev,
-                             int n_seg, int max_len, int npos, int C, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s);
-int launch_normalize_codes(float* codes, int ncodes, int C, const float* gn_gamma, const float* gn_beta, int post_norm,
+                             int n_seg, int max_len, int npos, int C, int ksize, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s);
+int launch_normalize_codes(float* codes, int ncodes, int C, int ksize, const float* gn_gamma, const float* gn_beta, int post_norm,
                            int l2_norm, float conv_scale, float bias_scale, float bias_prior, const float* weight_norm,
                            hipStream_t s);
 int launch_reduce_codes(const float* rows, int n, int ld, float* out, int num_classes, int divide_by_acc, hipStream_t s);

@@ -32,6 +32,7 @@ class SylphConfig(Structure):
         ("head_num_fc", c_int), ("head_fc_dim", c_int), ("cg_meta_bias", c_int), ("cg_has_weight", c_int), ("cg_has_scale", c_int),
         ("num_share_convs", c_int), ("tower_norm", c_int), ("cg_tower_gn_mask", c_int), ("cg_tower_relu_mask", c_int),
         ("tower_deformable", c_int), ("num_groups", c_int), ("width_per_group", c_int),
+        ("cg_code_ksize", c_int),
     ]
 
 

@@ -76,6 +76,17 @@ def _name_floats(names: Optional[Sequence[Optional[str]]], n: int) -> torch.Tens
     return torch.from_numpy(vals)
 
 
+def require_1x1_codes(cls_conv: torch.Tensor, what: str):
+    """The packed row fixes a class code at CODE_DIM floats: a 3x3 code (CODE_GENERATOR.CLS_LAYER kernel size 3: 2 304 floats) does not
+    fit it and must not be reshaped into several rows."""
+    n = int(cls_conv.shape[0]) if cls_conv.dim() > 0 else 0
+    if n and cls_conv.numel() != n * CODE_DIM:
+        raise NotImplementedError(
+            f"{what}: the packed {ROW}-float class-code rows hold 1x1 codes ({CODE_DIM} floats) only; a cls_conv of shape "
+            f"{tuple(cls_conv.shape)} (CODE_GENERATOR.CLS_LAYER kernel size {int(cls_conv.shape[-1]) if cls_conv.dim() == 4 else '?'}) "
+            "is not supported on this path")
+
+
 def pack_codes(cls_conv: torch.Tensor, cls_bias: torch.Tensor, class_ids, acc_weight=None, weight_norm=None,
                names: Optional[Sequence[Optional[str]]] = None, has_acc=None) -> torch.Tensor:
     """(n,256[,1,1]), (n,), ids -> (n, ROW) fp32 rows (layout above) on the device of cls_conv."""
@@ -84,6 +95,7 @@ def pack_codes(cls_conv: torch.Tensor, cls_bias: torch.Tensor, class_ids, acc_we
     out = torch.zeros(n, ROW, dtype=torch.float32, device=dev)
     if n == 0:
         return out
+    require_1x1_codes(cls_conv, "distributed.pack_codes")
     out[:, :CODE_DIM] = cls_conv.reshape(n, CODE_DIM)
     out[:, F_BIAS] = cls_bias.reshape(n)
     out[:, F_ACC] = 1.0 if acc_weight is None else torch.as_tensor(acc_weight, dtype=torch.float32, device=dev)

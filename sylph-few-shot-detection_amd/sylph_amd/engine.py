@@ -173,9 +173,13 @@ def config_from_cfg(cfg) -> SylphConfig:
             raise NotImplementedError(f"CODE_GENERATOR.TOWER_LAYERS entry {layer}: activation must be 'ReLU' or ''")
     if len(tl) > 30:
         raise NotImplementedError("more than 30 CODE_GENERATOR.TOWER_LAYERS")
+    # CLS_LAYER = [norm, activation, k]: k is the spatial size of the class code (GlobalAdaptiveAvgPool2d(k_s = k), code_generator.py:
+    # 519-540), run by the query head as a k x k conv with padding k // 2 (fcos.py:499-510).  2 cannot run in the reference (padding 1
+    # with an even kernel grows the map); larger sizes are not implemented
     cl = list(cg.CLS_LAYER)
-    if len(cl) != 3 or cl[0] not in ("", "none") or cl[1] != "" or int(cl[2]) != 1:
-        raise NotImplementedError(f"CODE_GENERATOR.CLS_LAYER {cl} (only ['', '', 1])")
+    if len(cl) != 3 or cl[0] not in ("", "none") or cl[1] != "" or int(cl[2]) not in (1, 3):
+        raise NotImplementedError(f"CODE_GENERATOR.CLS_LAYER {cl} (only ['', '', 1] and ['', '', 3]: no norm, no activation, a 1x1 or 3x3 class code)")
+    sc.cg_code_ksize = int(cl[2])
     bl = list(cg.BIAS_LAYER)
     sc.cg_has_bias = int(len(bl) != 0)
     if len(bl) and (len(bl) != 3 or bl[0] not in ("", "none") or bl[1] != "" or int(bl[2]) != 1):
@@ -217,6 +221,9 @@ class Engine:
         check(self.L.sylph_set_config(self._ctx, ctypes.byref(self.sc)), "set_config")
         self.nlevels = self.sc.nlevels
         self.is_roi_encoder = int(self.sc.cg_type) == 1
+        # CODE_GENERATOR.CLS_LAYER kernel size: a class code is (256, k, k), a packed code row 256 k^2 + 1 floats (the ROIEncoder's stay 1x1)
+        self.code_ksize = 1 if self.is_roi_encoder else max(1, int(self.sc.cg_code_ksize))  # (0: a library build that predates the field, tools/ab_bench.sh)
+        self.code_len = 256 * self.code_ksize ** 2 + 1
         self.cond_scale = 1.0  # CondConvBlock Scale of the first chunk (ROIEncoder head), read from the checkpoint
         self.cond_scales = [1.0]  # all CondConvBlock Scales (one per 256-channel chunk of the class code)
         self._cond_scales_loaded = False  # did the checkpoint carry cond_cls_logits.scales.*?
@@ -342,7 +349,8 @@ class Engine:
         k = cls_conv.size(1) // 256
         assert cls_conv.size(1) == 256 * k and k >= 1, f"weight has wrong shape, {tuple(cls_conv.shape)}"
         assert k == 1 or (self.is_roi_encoder and not raw), "feature.size(1) != weight.size(1)"  # CondConvBasic (head_utils.py:69)
-        w = cls_conv.to(self.device, torch.float32).reshape(cls_conv.size(0), 256 * k)
+        # (a 3x3 code keeps torch's (c, ky, kx) order per row: 256 * 9 floats; the library packs it tap-major)
+        w = cls_conv.to(self.device, torch.float32).reshape(cls_conv.size(0), -1)
         b = cls_bias.to(self.device, torch.float32).reshape(-1).contiguous() if cls_bias is not None else None
         if self.is_roi_encoder and not raw:
             # CondConvBlock (head_utils.py:140-162): sum over 256-channel chunks of scale_i * conv(feature, w_i, bias); the
@@ -368,14 +376,17 @@ class Engine:
         CondConvBlock Scale (forward_base_train, fcos.py:544-570,592-593)."""
         self._stream()
         assert cls_conv.dim() == 4, f"Weight has dimension: {cls_conv.dim()}"
-        assert cls_conv.size(2) == 1 and cls_conv.size(3) == 1
+        k = self.code_ksize
+        if cls_conv.size(2) != k or cls_conv.size(3) != k:
+            raise ValueError(f"class code of spatial size {cls_conv.size(2)}x{cls_conv.size(3)} on an engine configured for {k}x{k} codes "
+                             f"(CODE_GENERATOR.CLS_LAYER kernel size {k}): cls_conv must be (N, 256, {k}, {k})")
         if self.owd:
             # `logits_pred = ones_like(logits_pred)[:, :, [0]]` after the sigmoid: one class whose probability is exactly 1 -- a zero
             # code with bias 40 (sigmoid(40) rounds to 1.0f) through the same class-conditional conv; the towers / box heads are unchanged.
             # The decode then runs with thresh_with_ctr = 1 (config_from_cfg): 1.0f * quality == quality exactly, so the candidates
             # are the locations whose quality alone clears the threshold, as in the reference (fcos_outputs.py:937)
             if getattr(self, "_owd_codes", None) is None:
-                self._owd_codes = (torch.zeros(1, 256, device=self.device), torch.full((1,), 40.0, device=self.device))
+                self._owd_codes = (torch.zeros(1, 256 * k * k, device=self.device), torch.full((1,), 40.0, device=self.device))
             w1, b1 = self._owd_codes
             self._ncls = 1
             check(self.L.sylph_fcos_head(self._ctx, _ptr(w1), _ptr(b1), 1), "fcos_head (OWD)")
@@ -400,6 +411,9 @@ class Engine:
         (cls_conv (N_e, 256 k, 1, 1), cls_bias (N_e) or None), image i of the current batch is run with codes[image_episode[i]] and gets
         what `head(*codes[image_episode[i]])` gives it on the same batch.  `decode` then numbers classes within the image's own episode."""
         self._stream()
+        if self.code_ksize != 1:
+            raise NotImplementedError(f"head_episodes runs 1x1 class codes only: CODE_GENERATOR.CLS_LAYER kernel size {self.code_ksize} is not "
+                                      "supported here (call head once per episode)")
         codes = [(w, b) for w, b in codes]
         image_episode = [int(e) for e in image_episode]
         if len(codes) == 0:
@@ -574,7 +588,7 @@ class Engine:
         if B > 64:
             raise ValueError(f"{B} support images of one class in one call: the code generator's shot reduction handles at most 64 "
                              "(split the class into chunks and reduce them, as the base-class path does)")
-        out = torch.empty(257, device=self.device)
+        out = torch.empty(self.code_len, device=self.device)
         self._keep_boxes = bx
         check(self.L.sylph_codegen(self._ctx, _ptr(bx), _ptr(out)), "codegen")
         self._sup_rows = None
@@ -582,7 +596,7 @@ class Engine:
 
     def codegen_classes(self, boxes: torch.Tensor, shots: int) -> torch.Tensor:
         """Several classes in ONE batch: the current batch holds n_classes * shots support images (class k = images
-        [k * shots, (k + 1) * shots)), boxes (n_classes * shots, 4) -> (n_classes, 257) un-normalised codes."""
+        [k * shots, (k + 1) * shots)), boxes (n_classes * shots, 4) -> (n_classes, 256 k^2 + 1) un-normalised codes (k = code_ksize)."""
         self._stream()
         B = self._batch[0]
         bx = boxes.to(self.device, torch.float32).reshape(-1, 4).contiguous()
@@ -590,7 +604,7 @@ class Engine:
         if shots > 64:
             raise ValueError(f"{shots} shots per class in one call: the code generator's shot reduction handles at most 64 (split the "
                              "class into chunks and reduce them, as the base-class path does)")
-        out = torch.empty(B // shots, 257, device=self.device)
+        out = torch.empty(B // shots, self.code_len, device=self.device)
         self._keep_boxes = bx
         check(self.L.sylph_codegen_classes(self._ctx, _ptr(bx), int(shots), _ptr(out)), "codegen_classes")
         self._sup_rows = None
@@ -599,7 +613,7 @@ class Engine:
     def codegen_rois(self, boxes: torch.Tensor, roi_image, seg_len) -> torch.Tensor:
         """Class codes from a ROI list over the current batch (sylph_codegen_rois): ROI r is boxes[r] on image roi_image[r], any
         number per image in any order; the ROIs are cut into consecutive segments of seg_len[j] >= 1 shots and row j of the
-        (n_seg, 257) result is the un-normalised code of segment j, as `codegen` gives it for a batch holding the segment's images
+        (n_seg, 256 k^2 + 1) result is the un-normalised code of segment j, as `codegen` gives it for a batch holding the segment's images
         once per ROI.  No cap on a segment's length."""
         self._stream()
         bx, ri = self._check_rois(boxes, roi_image)
@@ -613,7 +627,7 @@ class Engine:
                 raise ValueError(f"seg_len[{j}] = {n}: a segment needs at least one ROI")
         if sum(sl) != len(ri):
             raise ValueError(f"the segment lengths sum to {sum(sl)}, not to R = {len(ri)}")
-        out = torch.empty(len(sl), 257, device=self.device)
+        out = torch.empty(len(sl), self.code_len, device=self.device)
         self._keep_boxes = bx
         check(self.L.sylph_codegen_rois(self._ctx, len(ri), _ptr(bx), _iarr(ri), len(sl), _iarr(sl), _ptr(out)), "codegen_rois")
         self._sup_rows = len(ri)
@@ -635,7 +649,10 @@ class Engine:
 
     def normalize_codes(self, codes: torch.Tensor, weight_norm: Optional[torch.Tensor] = None) -> torch.Tensor:
         self._stream()
-        assert codes.is_cuda and codes.dtype == torch.float32 and codes.is_contiguous() and codes.shape[-1] == 257
+        assert codes.is_cuda and codes.dtype == torch.float32 and codes.is_contiguous()
+        if codes.shape[-1] != self.code_len:
+            raise ValueError(f"normalize_codes: rows of {codes.shape[-1]} floats on an engine whose codes are {self.code_ksize}x{self.code_ksize} "
+                             f"({self.code_len} floats per row; CODE_GENERATOR.CLS_LAYER kernel size {self.code_ksize})")
         wn = None
         if weight_norm is not None:
             wn = weight_norm.to(self.device, torch.float32).reshape(-1).contiguous()
@@ -644,7 +661,7 @@ class Engine:
         self._lib_writes += 1  # `codes` changed in place without a torch version bump
         return codes
 
-    def reduce_codes(self, rows: torch.Tensor, num_classes: int, divide_by_acc: bool = True) -> torch.Tensor:
+    def reduce_codes(self, rows: torch.Tensor, num_classes: int, divide_by_acc: bool = True) -> torch.Tensor:  # (1x1 codes only: the C entry refuses cg_code_ksize 3)
         """Device-side reduce_class_code on packed rows (sylph_amd.distributed row layout) -> (num_classes, ROW), row c = class c.
         divide_by_acc False: plain per-class accumulation (the per-rank step of the base-class path)."""
         self._stream()

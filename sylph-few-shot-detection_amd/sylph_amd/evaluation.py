@@ -163,6 +163,7 @@ def inference_on_support_set_dataset_base(model, data_loader, all_id_map=None, b
             names[cid] = inputs[0]["class_name"]
             weight = float(inputs[0]["len"]) / inputs[0]["total_len"]
             wn = code["cls_weight_norm"].reshape(1) * weight if "cls_weight_norm" in code else None
+            D.require_1x1_codes(code["cls_conv"], "inference_on_support_set_dataset_base (chunk accumulation)")
             rows.append(D.pack_codes(code["cls_conv"].reshape(1, 256) * weight, code["cls_bias"].reshape(1) * weight, [cid],
                                      [weight], wn, [names[cid]]))
     if not rows:
@@ -252,6 +253,7 @@ def inference_on_annotated_images(model, data_loader, chunk: int = 10, class_nam
             for cid in seg_class:
                 names.setdefault(cid, name_of(cid))
             w = torch.tensor(seg_len, dtype=torch.float32, device=codes[0]["cls_conv"].device)
+            D.require_1x1_codes(codes[0]["cls_conv"], "inference_on_annotated_images (chunk accumulation)")
             conv = torch.cat([c["cls_conv"].reshape(1, 256) for c in codes]) * w[:, None]
             bias = torch.cat([c["cls_bias"].reshape(1) for c in codes]) * w
             wn = torch.cat([c["cls_weight_norm"].reshape(1) for c in codes]) * w if "cls_weight_norm" in codes[0] else None

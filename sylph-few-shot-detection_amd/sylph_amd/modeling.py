@@ -128,6 +128,12 @@ class MetaFCOS(HipComponent):
         return self.engine.decode(out_sizes)
 
 
+def _split_code(code: torch.Tensor, k: int = 1, bias_shape=(1, 1, 1, 1)) -> Dict[str, torch.Tensor]:
+    """One packed code row (256 k^2 + 1 floats: cls_conv in torch's (c, ky, kx) order, then the bias) -> the reference's dict."""
+    n = 256 * k * k
+    return {"cls_conv": code[:n].reshape(1, 256, k, k), "cls_bias": code[n:n + 1].reshape(*bias_shape)}
+
+
 @CODE_GENERATOR_REGISTRY.register()
 class CodeGenerator(HipComponent):
     """CodeGeneratorHead: forward_roi_align on the current support pyramid (code_generator.py:924-1002) and, with cls_norm=True,
@@ -143,8 +149,7 @@ class CodeGenerator(HipComponent):
     def __call__(self, boxes: Optional[torch.Tensor] = None, cls_norm: bool = False, class_codes=None, weight_norm=None):
         if cls_norm:
             return self.engine.normalize_codes(class_codes, weight_norm)
-        code = self.engine.codegen(boxes)
-        out = {"cls_conv": code[:256].reshape(1, 256, 1, 1), "cls_bias": code[256:257].reshape(1, 1, 1, 1)}
+        out = _split_code(self.engine.codegen(boxes), self.engine.code_ksize)  # (1, 256, k, k) with CLS_LAYER kernel size k
         if self.has_scale:  # code_generator.py:987-999
             out["cls_weight_norm"] = self.engine.codegen_weight_norm(1).reshape(1, 1, 1, 1)
         return out
@@ -153,7 +158,7 @@ class CodeGenerator(HipComponent):
         """Several classes of `shots` support boxes each in the current batch -> one code dict per class (the launches are
         shared, the per-class arithmetic is that of __call__)."""
         codes = self.engine.codegen_classes(boxes, shots)
-        outs = [{"cls_conv": c[:256].reshape(1, 256, 1, 1), "cls_bias": c[256:257].reshape(1, 1, 1, 1)} for c in codes]
+        outs = [_split_code(c, self.engine.code_ksize) for c in codes]
         if self.has_scale:
             wn = self.engine.codegen_weight_norm(len(outs))
             for o, w in zip(outs, wn):
@@ -165,7 +170,7 @@ class CodeGenerator(HipComponent):
         """Classes from a ROI list over the current batch (Engine.codegen_rois): segment j of seg_len[j] (image, box) pairs -> one
         code dict per segment, in forward_classes' shapes.  A segment's arithmetic is that of __call__ on its shots."""
         codes = self.engine.codegen_rois(boxes, roi_image, seg_len)
-        outs = [{"cls_conv": c[:256].reshape(1, 256, 1, 1), "cls_bias": c[256:257].reshape(1, 1, 1, 1)} for c in codes]
+        outs = [_split_code(c, self.engine.code_ksize) for c in codes]
         if self.has_scale:
             wn = self.engine.codegen_weight_norm(len(outs))
             for o, w in zip(outs, wn):
@@ -396,6 +401,10 @@ class MetaOneStageDetector(nn.Module):
             assert "cls_conv" in code["class_code"], "class_conv is not in class_code"
             cc = code["class_code"]
             assert cc["cls_conv"].ndim == 4
+            k = self.engine.code_ksize
+            if tuple(cc["cls_conv"].shape[1:]) != (256, k, k):
+                raise ValueError(f"class code of shape {tuple(cc['cls_conv'].shape)}: this model normalises {k}x{k} codes "
+                                 f"(1, 256, {k}, {k}) (CODE_GENERATOR.CLS_LAYER kernel size {k})")
             assert cc["cls_bias"].numel() == 1, "predicted bias should only have batch size 1"
             rows.append(torch.cat([cc["cls_conv"].reshape(-1).float(), cc["cls_bias"].reshape(-1).float()]))
             if "cls_weight_norm" in cc:  # x cls_weight_norm after the L2 normalisation (code_generator.py:838-840)
@@ -404,8 +413,7 @@ class MetaOneStageDetector(nn.Module):
         packed = torch.stack(rows).to(self.device).contiguous()
         out = self.code_generator(cls_norm=True, class_codes=packed, weight_norm=torch.cat(wns) if wns else None)
         for i, code in enumerate(codes):
-            code["class_code"]["cls_conv"] = out[i, :256].reshape(1, 256, 1, 1)
-            code["class_code"]["cls_bias"] = out[i, 256:257].reshape(1)
+            code["class_code"].update(_split_code(out[i], self.engine.code_ksize, bias_shape=(1,)))
         return codes
 
     # ---- query path ----------------------------------------------------------------------------------

@@ -43,6 +43,8 @@ def _rows_from_codes(codes: List[Dict[str, Any]], device) -> torch.Tensor:
     """list of {"support_set_target", "class_name", "class_code": {...}} -> packed rows (sylph_amd.distributed layout)."""
     if not codes:
         return torch.zeros(0, D.ROW, device=device)
+    for c in codes:
+        D.require_1x1_codes(c["class_code"]["cls_conv"], "_rows_from_codes")
     conv = torch.cat([c["class_code"]["cls_conv"].reshape(1, 256).float() for c in codes]).to(device)
     bias = torch.cat([c["class_code"]["cls_bias"].reshape(1).float() for c in codes]).to(device)
     acc = [float(c["class_code"].get("acc_weight", 1.0)) for c in codes]
