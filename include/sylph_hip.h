@@ -155,6 +155,18 @@ int sylph_fcos_head(sylph_ctx* ctx, const float* cls_conv_dev, const float* cls_
  * 1x1 codes only: with cg_code_ksize 3 (CLS_LAYER kernel size 3) the call fails. */
 int sylph_fcos_head_episodes(sylph_ctx* ctx, int E, const float* cls_conv_dev, const float* cls_bias_dev, const int* n_classes,
                              const int* image_episode);
+/* The dual case: EVERY image of the batch is scored against G code sets in one step.  The result for (image i, set g) -- head outputs,
+ * and the detections sylph_decode_nms_codesets then returns for it -- is that of sylph_fcos_head with set g's codes on the same batch, bit
+ * for bit.  Only the class-conditional conv reads the codes (fcos.py:582-667, head_utils.py:60-81): the towers, the box / centerness / IoU
+ * heads and the cls GroupNorm statistics run ONCE per call, not once per set.  It stands for the G query passes of the reference's
+ * TEST.REPEAT_TEST protocol, one per support seed over the same query set (sylph/runner/meta_fcos_runner.py:451-672, each pass the batch-1
+ * loop of sylph/evaluation/meta_learn_evaluation.py:421-426), or for one served frame scored for G tenants' class sets.
+ * cls_conv_dev: (sum_g N_g, 256) fp32, set after set; cls_bias_dev: (sum_g N_g) fp32 or NULL; n_classes: host, G entries, each >= 1.
+ * bf16 with FCOS.NORM "GN": the sets of up to 32 classes share one streaming pass over the tower output per 128 packed classes; any
+ * other set runs the kernel sylph_fcos_head picks for its N, on the tower output normalised once.
+ * sylph_export_head then writes logits (B, sum_g N_g, h, w), set after set.  The detections come from sylph_decode_nms_codesets;
+ * sylph_decode_nms fails after this call.  1x1 codes only: with cg_code_ksize 3 (CLS_LAYER kernel size 3) the call fails. */
+int sylph_fcos_head_codesets(sylph_ctx* ctx, int G, const float* cls_conv_dev, const float* cls_bias_dev, const int* n_classes);
 /* MetaFCOSHead.forward with support_set_per_class_code = None -> forward_base_train (fcos.py:543-578): the towers and the checkpoint's
  * OWN classifier `cls_logits` (nn.Conv2d(256, NUM_CLASSES, CLS_LOGITS_KERNEL_SIZE 1 or 3, padding k // 2), fcos.py:418-427) -- the base
  * detector (run_type None) and evaluation with the pretrained codes.  *num_classes receives NUM_CLASSES. */
@@ -177,10 +189,22 @@ int sylph_import_head(sylph_ctx* ctx, int N, int level, const float* logits_nchw
  * overflow, bit1 output truncated).  cand_dev: (level, location, class) ordinal of each detection.
  * Decode reads the outputs of the most recent head call (sylph_fcos_head, sylph_fcos_head_episodes, sylph_fcos_head_pretrained or sylph_import_head) of the
  * current batch; any order of stage calls on one context is valid (a head need not be followed by a decode, a decode may be repeated,
- * and a decode that reported a status bit leaves nothing behind for the next one). */
+ * and a decode that reported a status bit leaves nothing behind for the next one).  After sylph_fcos_head_codesets the call fails:
+ * that head's G * B results go through sylph_decode_nms_codesets. */
 int sylph_decode_nms(sylph_ctx* ctx, const int* out_heights, const int* out_widths, int max_out, float* boxes_dev,
                      float* scores_dev, int* classes_dev, int* levels_dev, float* locations_dev, int* cand_dev,
                      int* counts_dev, int* status_dev);
+/* The decode of a sylph_fcos_head_codesets call: predict_proposals + select_over_all_levels + detector_postprocess
+ * (fcos_outputs.py:743-812,904-1028; meta_one_stage_detector.py:288-296) once per (set, image), as the G query passes of
+ * meta_fcos_runner.py:451-672 run them.  The threshold, PRE_NMS_TOPK per (image, level), the per-class NMS and POST_NMS_TOPK per image act
+ * inside one set; classes are numbered within their own set (classes_dev < N_g) and the cand_dev ordinal is (loc_base + loc) * N_g + cls.
+ * Device outputs as for sylph_decode_nms, row-major [G][B][max_out][...]; counts_dev[G * B]; ONE status_dev.  G must equal the last
+ * head call's; after any other head entry the call fails (use sylph_decode_nms), as sylph_decode_nms fails after a code-sets head: a
+ * caller's B-sized buffers are never overrun.  The ordering rules of sylph_decode_nms hold: the decode may be repeated, the head need not
+ * be decoded, and a decode that reported a status bit leaves nothing behind for the next one. */
+int sylph_decode_nms_codesets(sylph_ctx* ctx, int G, const int* out_heights, const int* out_widths, int max_out, float* boxes_dev,
+                              float* scores_dev, int* classes_dev, int* levels_dev, float* locations_dev, int* cand_dev,
+                              int* counts_dev, int* status_dev);
 
 /* CodeGenerator.forward / CodeGeneratorHead.forward_roi_align, eval branch
  * (sylph/modeling/code_generator/code_generator.py:924-1002): the current batch is the S support

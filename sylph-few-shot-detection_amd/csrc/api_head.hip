@@ -214,6 +214,7 @@ static std::vector<DecodeSeg> decode_segs(const sylph_ctx* c, const Plan* P, con
       DecodeSeg d;
       d.row0 = b * P->Ltot + P->off[l]; d.nloc = P->hl[l] * P->wl[l]; d.W = P->wl[l];
       d.stride = c->cfg.strides[l]; d.level = l; d.image = b; d.loc_base = lb; d.ncls = img_ncls ? img_ncls[b] : 0;
+      d.cls0 = 0; d.slot = b;
       lb += (unsigned)d.nloc;
       ds.push_back(d);
     }
@@ -483,6 +484,7 @@ struct CondEp {
   const void* wt; const float *bias, *bias_scan; int N;
   const int2 *t32; int n32; const int2* tBM; int nBM;
   double rows;
+  float* out = nullptr;  // conv_igemm only: where column 0 of the launch goes (nullptr: Plan::logits; a code set: its first column)
 };
 
 // episode e of the head that o describes, to be run by kernel k; the uniform head is ONE episode over the plan's whole tile tables
@@ -528,7 +530,7 @@ static int launch_cond(sylph_ctx* c, Plan* P, const HeadOut& o, HeadKind k, cons
   const int bn = cond_pad(N).bn;  // conv_igemm: 128-row tiles up to 32 classes, head_BM-row tiles above
   ConvArgs a;
   memset(&a, 0, sizeof(a));
-  a.in = P->cls_feat; a.wt = v.wt; a.out = P->logits;
+  a.in = P->cls_feat; a.wt = v.wt; a.out = v.out ? v.out : P->logits;
   a.shift = v.bias;
   a.zeros = c->zeros; a.tap_dy = 1;
   a.segs = P->head_segs;
@@ -566,6 +568,129 @@ static int run_cond(sylph_ctx* c, Plan* P, const HeadOut& o, bool missing_only, 
   return 0;
 }
 
+// ---- several code sets over the same images (sylph_fcos_head_codesets / sylph_decode_nms_codesets) ------------------------------------
+
+// does set size N take the fused GroupNorm + conv kernel (gn_logits_sets_kernel)?  Exactly where sylph_fcos_head writes its logits with
+// gn_logits_kernel; every other set runs conv_igemm as there (after the deferred GroupNorm apply where the head ops left it out).  The
+// fused conv + score scan is not used per set: its detections equal the logits route's (tests/test_head_sweeps_gpu.py).
+static bool set_is_hot(const sylph_ctx* c, const Plan* P, int N) { return head_kind(c, P, N, false) == HeadKind::gn_logits; }
+
+// Host and device tables of a code-sets head: column layout (Plan::cs_col0), packed-row -> source-row table, the decode's segment table
+// of G * B slots.  Rebuilt only when n_classes differs from the previous call's on this plan.
+static int cs_tables(sylph_ctx* c, Plan* P, int G, const int* n_classes) {
+  const int L = c->cfg.nlevels, B = P->B;
+  std::vector<int> n(n_classes, n_classes + G);
+  if (P->dsegs_cs && n == P->cs_n) return 0;
+  P->cs_n.clear();  // (a failure below leaves no key that would match half-written tables)
+  std::vector<int> col0(G, 0), src0(G, 0);
+  int col = 0, src = 0;
+  for (int g = 0; g < G; ++g) { src0[g] = src; src += n[g]; }
+  bool any_cold = false;
+  for (int g = 0; g < G; ++g) {
+    if (!set_is_hot(c, P, n[g])) { any_cold = true; continue; }
+    col0[g] = col;
+    col += (n[g] + 3) & ~3;
+  }
+  const int hot_blocks = (col + 31) / 32, hot_width = col > 0 && col < 8 ? 8 : col;
+  int rows = hot_blocks * 32;
+  for (int g = 0; g < G; ++g) {
+    if (set_is_hot(c, P, n[g])) continue;
+    col0[g] = rows;
+    rows += cond_pad(n[g]).Npad;
+  }
+  const int ld = any_cold ? rows : hot_width;
+  std::vector<int> src_row((size_t)rows, -1);
+  for (int g = 0; g < G; ++g)
+    for (int r = 0; r < n[g]; ++r) src_row[(size_t)col0[g] + r] = src0[g] + r;
+  const std::vector<DecodeSeg> base = decode_segs(c, P, nullptr);
+  std::vector<DecodeSeg> ds;
+  ds.reserve((size_t)G * base.size());
+  for (int g = 0; g < G; ++g)
+    for (DecodeSeg d : base) {
+      d.ncls = n[g]; d.cls0 = col0[g]; d.slot = g * B + d.image;
+      ds.push_back(d);
+    }
+  HIPCHK(hipStreamSynchronize(c->stream));  // the previous step may still be reading the tables
+  if (rows > P->cs_rows_cap) {
+    c->dfree(P->cs_code_w); c->dfree(P->cs_bias); c->dfree(P->cs_src_row);
+    P->cs_code_w = nullptr; P->cs_bias = nullptr; P->cs_src_row = nullptr; P->cs_rows_cap = 0;
+    RET(c->dalloc(&P->cs_code_w, (size_t)rows * 256 * c->esz()));
+    RET(c->dalloc((void**)&P->cs_bias, (size_t)2 * rows * sizeof(float)));
+    RET(c->dalloc((void**)&P->cs_src_row, (size_t)rows * sizeof(int)));
+    P->cs_rows_cap = rows;
+  }
+  if (G * B * L > P->dsegs_cs_cap) {
+    c->dfree(P->dsegs_cs);
+    P->dsegs_cs = nullptr; P->dsegs_cs_cap = 0;
+    RET(c->dalloc((void**)&P->dsegs_cs, ds.size() * sizeof(DecodeSeg)));
+    P->dsegs_cs_cap = G * B * L;
+  }
+  HIPCHK(hipMemcpy(P->cs_src_row, src_row.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(P->dsegs_cs, ds.data(), ds.size() * sizeof(DecodeSeg), hipMemcpyHostToDevice));
+  P->cs_col0 = col0; P->cs_hot_blocks = hot_blocks; P->cs_hot_width = hot_width; P->cs_ld = ld; P->cs_rows = rows;
+  P->cs_n = n;
+  return 0;
+}
+
+// the decode buffers of G * B slots with candidate buffers for ncls classes per (slot, level): they grow, and are zeroed when they do
+// (every decode leaves them zero again: nms_kernel)
+static int ensure_decode_sets(sylph_ctx* c, Plan* P, int G, int ncls) {
+  BUILD(build_decode(c, P), P);
+  const int L = c->cfg.nlevels, slots = G * P->B, cap = want_cand_cap(c, P, ncls);
+  DecodeBuffers& d = P->dbuf_cs;
+  if (slots <= P->cs_slots_cap && cap <= P->cs_cand_cap) return 0;
+  const int ns = slots > P->cs_slots_cap ? slots : P->cs_slots_cap, nc = cap > P->cs_cand_cap ? cap : P->cs_cand_cap;
+  void* old[] = {d.cand_key, d.cand_idx, d.cand_count, d.sel_ws, d.sel_tie, d.pool_key, d.pool_count, d.s_box, d.s_score, d.s_cls, d.s_level,
+                 d.s_loc, d.s_ord, d.status};
+  for (void* p : old) c->dfree(p);
+  d = DecodeBuffers{};
+  P->cs_slots_cap = 0; P->cs_cand_cap = 0;
+  const size_t nseg = (size_t)ns * L, pool = (size_t)P->pool_cap;
+  RET(c->dalloc((void**)&d.cand_key, nseg * nc * 4));
+  RET(c->dalloc((void**)&d.cand_idx, nseg * nc * 4));
+  RET(c->dalloc((void**)&d.cand_count, nseg * 4));
+  RET(c->dalloc((void**)&d.sel_ws, nseg * SEL_WS * 4));
+  RET(c->dalloc((void**)&d.sel_tie, nseg * SEL_TIE * 8));
+  RET(c->dalloc((void**)&d.pool_key, ns * pool * 8));
+  RET(c->dalloc((void**)&d.pool_count, (size_t)ns * 4));
+  RET(c->dalloc((void**)&d.s_box, ns * pool * 16));
+  RET(c->dalloc((void**)&d.s_score, ns * pool * 4));
+  RET(c->dalloc((void**)&d.s_cls, ns * pool * 4));
+  RET(c->dalloc((void**)&d.s_level, ns * pool * 4));
+  RET(c->dalloc((void**)&d.s_loc, ns * pool * 8));
+  RET(c->dalloc((void**)&d.s_ord, ns * pool * 4));
+  RET(c->dalloc((void**)&d.status, 8));
+  HIPCHK(hipMemsetAsync(d.cand_count, 0, nseg * 4, c->stream));
+  HIPCHK(hipMemsetAsync(d.sel_ws, 0, nseg * SEL_WS * 4, c->stream));
+  HIPCHK(hipMemsetAsync(d.pool_count, 0, (size_t)ns * 4, c->stream));
+  HIPCHK(hipMemsetAsync(d.status, 0, 8, c->stream));
+  P->cs_slots_cap = ns; P->cs_cand_cap = nc;
+  return 0;
+}
+
+// postprocess scales of a decode call -> Plan::img_out_dev; the H2D copy is skipped when they equal what the device table already holds
+// (every step of a steady query stream).  Otherwise img_out_host is rewritten: wait only for the previous H2D copy of it, not for the stream
+static int upload_img_out(sylph_ctx* c, Plan* P, const int* oh, const int* ow) {
+  std::vector<ImageOut> io((size_t)P->B);
+  for (int b = 0; b < P->B; ++b) {
+    const int H = oh ? oh[b] : P->img_h[b], W = ow ? ow[b] : P->img_w[b];
+    // detector_postprocess: python-double ratios cast to the fp32 tensor dtype
+    io[b].sx = (float)((double)W / (double)P->img_w[b]);
+    io[b].sy = (float)((double)H / (double)P->img_h[b]);
+    io[b].out_w = (float)W;
+    io[b].out_h = (float)H;
+  }
+  if (!P->img_out_ev || P->img_out_last.size() != io.size() || memcmp(P->img_out_last.data(), io.data(), io.size() * sizeof(ImageOut)) != 0) {
+    if (P->img_out_ev) HIPCHK(hipEventSynchronize(P->img_out_ev));
+    else HIPCHK(hipEventCreateWithFlags(&P->img_out_ev, hipEventDisableTiming));
+    memcpy(P->img_out_host, io.data(), io.size() * sizeof(ImageOut));
+    HIPCHK(hipMemcpyAsync(P->img_out_dev, P->img_out_host, sizeof(ImageOut) * P->B, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(P->img_out_ev, c->stream));
+    P->img_out_last = io;
+  }
+  return 0;
+}
+
 }  // namespace sylph_host
 
 extern "C" {
@@ -582,7 +707,7 @@ int sylph_import_head(sylph_ctx* c, int N, int level, const float* logits, const
   BUILD(build_head(c, P), P);
   HeadOut o;
   o.src = HeadOut::imported;
-  if (P->logits && N == prev.ncls) { o.ncls = N; o.logits_ld = prev.logits_ld; }  // level by level into the buffer as the last head laid it out
+  if (P->logits && N == prev.ncls && prev.src != HeadOut::codesets) { o.ncls = N; o.logits_ld = prev.logits_ld; }  // level by level into the buffer as the last head laid it out
   else RET(ensure_logits(c, P, N, false, &o));
   const int hw = P->hl[level] * P->wl[level];
   for (int b = 0; b < P->B; ++b) {
@@ -714,9 +839,19 @@ int sylph_export_head(sylph_ctx* c, int level, float* logits, float* reg, float*
   }
   const HeadOut& o = P->out;
   const int hw = P->hl[level] * P->wl[level];
+  int sumN = 0;  // code sets: logits (B, sum N_g, h, w), set after set
+  if (o.src == HeadOut::codesets)
+    for (int n : P->cs_n) sumN += n;
   for (int b = 0; b < P->B; ++b) {
     const int row0 = b * P->Ltot + P->off[level];
-    if (logits)
+    if (logits && o.src == HeadOut::codesets) {
+      size_t ch = 0;
+      for (size_t g = 0; g < P->cs_n.size(); ++g) {
+        KCHK(launch_export_nchw_f32(P->logits, logits + ((size_t)b * sumN + ch) * hw, P->cs_n[g], hw, row0, o.logits_ld, P->cs_col0[g], c->stream),
+             "export logits");
+        ch += (size_t)P->cs_n[g];
+      }
+    } else if (logits)
       KCHK(launch_export_nchw_f32(P->logits, logits + (size_t)b * o.ncls * hw, o.ncls, hw, row0, o.logits_ld, 0, c->stream), "export logits");
     if (reg) KCHK(launch_export_nchw_f32(P->pred, reg + (size_t)b * 4 * hw, 4, hw, row0, 8, 0, c->stream), "export reg");
     if (ctr) KCHK(launch_export_nchw_f32(P->pred, ctr + (size_t)b * hw, 1, hw, row0, 8, 4, c->stream), "export ctr");
@@ -730,28 +865,12 @@ int sylph_decode_nms(sylph_ctx* c, const int* oh, const int* ow, int max_out, fl
   Plan* P = c->cur;
   if (!P || P->out.src == HeadOut::none) return fail("sylph_fcos_head must be called first");
   if (max_out <= 0) return fail("max_out must be positive");
+  if (P->out.src == HeadOut::codesets)  // (its G * B result slots would overrun the caller's B-sized buffers)
+    return fail("the last head call was sylph_fcos_head_codesets (" + std::to_string(P->out.nsets) + " code sets): decode it with sylph_decode_nms_codesets");
   const HeadOut o = P->out;
   OwnerScope own(c, P);
   RET(ensure_decode(c, P, o.ncls));
-  // postprocess scales of this call; the H2D copy is skipped when they equal what the device table already holds (every step of a
-  // steady query stream).  Otherwise img_out_host is rewritten: wait only for the previous H2D copy of it, not for the stream
-  std::vector<ImageOut> io((size_t)P->B);
-  for (int b = 0; b < P->B; ++b) {
-    const int H = oh ? oh[b] : P->img_h[b], W = ow ? ow[b] : P->img_w[b];
-    // detector_postprocess: python-double ratios cast to the fp32 tensor dtype
-    io[b].sx = (float)((double)W / (double)P->img_w[b]);
-    io[b].sy = (float)((double)H / (double)P->img_h[b]);
-    io[b].out_w = (float)W;
-    io[b].out_h = (float)H;
-  }
-  if (!P->img_out_ev || P->img_out_last.size() != io.size() || memcmp(P->img_out_last.data(), io.data(), io.size() * sizeof(ImageOut)) != 0) {
-    if (P->img_out_ev) HIPCHK(hipEventSynchronize(P->img_out_ev));
-    else HIPCHK(hipEventCreateWithFlags(&P->img_out_ev, hipEventDisableTiming));
-    memcpy(P->img_out_host, io.data(), io.size() * sizeof(ImageOut));
-    HIPCHK(hipMemcpyAsync(P->img_out_dev, P->img_out_host, sizeof(ImageOut) * P->B, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(P->img_out_ev, c->stream));
-    P->img_out_last = io;
-  }
+  RET(upload_img_out(c, P, oh, ow));
   const DecodeCfg d = decode_cfg(c, P, o, max_out);
   const int L = c->cfg.nlevels;
   // the three states of HeadOut::cand: clear stale counters in front of a scan of every image, or keep the candidates that are there
@@ -762,6 +881,98 @@ int sylph_decode_nms(sylph_ctx* c, const int* oh, const int* ow, int max_out, fl
   KCHK(launch_decode(d, o.src == HeadOut::episodes ? P->dsegs_ep : P->dsegs, P->B * L, P->hl[0] * P->wl[0], P->B, nwb, P->logits, P->pred, 8,
                      P->dbuf, P->img_out_dev, boxes, scores, classes, levels, locations, cand, counts, status, o.cand == HeadOut::cand_all, c->stream),
        "decode_nms");
+  return 0;
+}
+
+/* see include/sylph_hip.h */
+int sylph_fcos_head_codesets(sylph_ctx* c, int G, const float* cls_conv, const float* cls_bias, const int* n_classes) {
+  Plan* P = c->cur;
+  if (!P) return fail("no current batch");
+  if (c->cfg.cg_code_ksize != 1)
+    return fail("sylph_fcos_head_codesets runs 1x1 class codes only (CODE_GENERATOR.CLS_LAYER kernel size " + std::to_string(c->cfg.cg_code_ksize) +
+                " is not supported here; use sylph_fcos_head per code set)");
+  if (G <= 0) return fail("no code sets (G <= 0)");
+  if (!cls_conv) return fail("cls_conv is NULL");
+  if (!n_classes) return fail("n_classes is NULL");
+  int maxN = 0;
+  long sumN = 0;
+  for (int g = 0; g < G; ++g) {
+    if (n_classes[g] <= 0) return fail("class_code is empty (code set " + std::to_string(g) + ")");
+    if (n_classes[g] > maxN) maxN = n_classes[g];
+    sumN += n_classes[g];
+  }
+  if (sumN + 128L * G > (1L << 20)) return fail("the code sets hold " + std::to_string(sumN) + " classes: too many for one logits row");
+  OwnerScope own(c, P);
+  P->out = HeadOut();
+  BUILD(build_head(c, P), P);
+  HeadOut o;
+  o.src = HeadOut::codesets;
+  o.has_bias = c->cfg.cond_use_bias && cls_bias;
+  o.nsets = G;
+  o.ncls = maxN;  // candidate capacity per (slot, level): that of the widest set
+  RET(cs_tables(c, P, G, n_classes));
+  o.logits_ld = P->cs_ld;
+  const size_t rows = (size_t)P->B * P->Ltot;
+  if (P->cs_ld > P->logits_cap_ld) {  // all sets' logits stay resident until the decode
+    if (P->logits) c->dfree(P->logits);
+    P->logits = nullptr; P->logits_cap_ld = 0;
+    RET(c->dalloc((void**)&P->logits, rows * P->cs_ld * sizeof(float)));
+    P->logits_cap_ld = P->cs_ld;
+  }
+  // one launch packs every set's codes and biases (in front of the towers, as in sylph_fcos_head)
+  KCHK(launch_pack_codes_episodes(c->dt, cls_conv, P->cs_src_row, P->cs_rows, 256, P->cs_code_w, o.has_bias ? cls_bias : nullptr, P->cs_bias,
+                                  P->cs_bias + P->cs_rows_cap, c->stream), "pack_codes (code sets)");
+  RET(run_ops(c, P->head_ops, "fcos_head"));  // towers, box heads, cls GroupNorm statistics: once, whatever G is
+  const Plan* PP = P;
+  const int ld = P->cs_ld;
+  // the sets of up to 32 classes: GN_SETS_MAX_BLOCKS blocks of 32 packed rows per pass over the un-normalised tower output
+  for (int b0 = 0; b0 < P->cs_hot_blocks; b0 += GN_SETS_MAX_BLOCKS) {
+    const int nb = P->cs_hot_blocks - b0 < GN_SETS_MAX_BLOCKS ? P->cs_hot_blocks - b0 : GN_SETS_MAX_BLOCKS;
+    const int width = P->cs_hot_width - 32 * b0 < 32 * nb ? P->cs_hot_width - 32 * b0 : 32 * nb;
+    KCHK(timed_op(c, "gn_logits_sets_kernel", 2.0 * (double)P->head_mtiles32 * 128.0 * width * 256.0, c->stream, [=](hipStream_t st) {
+           return launch_gn_logits_sets(PP->cls_feat, 256, PP->cls_coef, (const char*)PP->cs_code_w + (size_t)32 * b0 * 256 * 2, PP->cs_bias + 32 * b0, nb,
+                                        PP->logits + 32 * b0, ld, width, PP->head_segs, PP->head_tiles32, PP->head_mtiles32, st);
+         }), "gn_logits_sets");
+  }
+  // every other set: the conv_igemm launch sylph_fcos_head gives its N, on the tower output normalised in place ONCE, after the
+  // kernel above has read the un-normalised one
+  bool applied = false;
+  for (int g = 0; g < G; ++g) {
+    const int N = n_classes[g];
+    if (set_is_hot(c, P, N)) continue;
+    const HeadKind k = head_kind(c, P, N, false);
+    if (k == HeadKind::igemm_after_apply && !applied) { RET(apply_cls_gn(c, P)); applied = true; }
+    const size_t r0 = (size_t)P->cs_col0[g];
+    const CondEp v = {(const char*)P->cs_code_w + r0 * 256 * c->esz(), o.has_bias ? P->cs_bias + r0 : nullptr, nullptr, N,
+                      P->head_tiles32, P->head_mtiles32, P->head_tiles, P->head_mtiles, (double)rows, P->logits + r0};
+    RET(launch_cond(c, P, o, k, v, false));
+  }
+  o.cand = HeadOut::cand_none;
+  P->out = o;
+  return 0;
+}
+
+/* see include/sylph_hip.h */
+int sylph_decode_nms_codesets(sylph_ctx* c, int G, const int* oh, const int* ow, int max_out, float* boxes, float* scores, int* classes,
+                              int* levels, float* locations, int* cand, int* counts, int* status) {
+  Plan* P = c->cur;
+  if (!P || P->out.src == HeadOut::none) return fail("sylph_fcos_head_codesets must be called first");
+  if (P->out.src != HeadOut::codesets)
+    return fail("the last head call was not sylph_fcos_head_codesets: decode it with sylph_decode_nms");
+  if (max_out <= 0) return fail("max_out must be positive");
+  const HeadOut o = P->out;
+  if (G != o.nsets)
+    return fail("sylph_decode_nms_codesets: G = " + std::to_string(G) + ", but the last sylph_fcos_head_codesets call ran " + std::to_string(o.nsets) +
+                " code sets");
+  OwnerScope own(c, P);
+  RET(ensure_decode_sets(c, P, G, o.ncls));
+  RET(upload_img_out(c, P, oh, ow));
+  DecodeCfg d = decode_cfg(c, P, o, max_out);
+  d.cand_cap = P->cs_cand_cap;
+  const int L = c->cfg.nlevels, slots = G * P->B;
+  KCHK(launch_decode(d, P->dsegs_cs, slots * L, P->hl[0] * P->wl[0], slots, 0, P->logits, P->pred, 8, P->dbuf_cs, P->img_out_dev, boxes, scores,
+                     classes, levels, locations, cand, counts, status, false, c->stream),
+       "decode_nms_codesets");
   return 0;
 }
 

@@ -256,7 +256,7 @@ struct SupportPass {
 // where it writes missing logits) sets Plan::out to HeadOut() first and commits the whole record in ONE assignment as its last action: a
 // failure in between leaves src none, answered with "sylph_fcos_head must be called first".  Nothing assigns single fields of Plan::out.
 struct HeadOut {
-  enum Src { none, cond, episodes, pretrained, imported } src = none;  // sylph_fcos_head | _episodes | _pretrained | sylph_import_head
+  enum Src { none, cond, episodes, pretrained, imported, codesets } src = none;  // sylph_fcos_head | _episodes | _pretrained | sylph_import_head | sylph_fcos_head_codesets
   // Whose candidates logits_scan_kernel has already left in the decode buffers:
   //   cand_none     nobody's: the decode scans every image, after clearing the counters if Plan::cand_dirty says that an earlier fused
   //                 scan's candidates are still counted (a decode that ran its own scan leaves them zero: nms_kernel)
@@ -268,7 +268,8 @@ struct HeadOut {
   enum Cand { cand_none, cand_all, cand_scanned } cand = cand_none;
   bool has_bias = false;        // the class-conditional conv adds biases
   bool logits_missing = false;  // the logits columns of the scanned images were never written: sylph_export_head runs the unfused conv first
-  int ncls = 0, logits_ld = 0;  // classes (of the widest episode) and row pitch of Plan::logits
+  int ncls = 0, logits_ld = 0;  // classes (of the widest episode / code set) and row pitch of Plan::logits
+  int nsets = 0;                // codesets: G, the sets whose logits columns Plan::logits holds side by side (Plan::cs_col0)
 };
 
 struct Plan {
@@ -360,6 +361,23 @@ struct Plan {
   int* ep_seg_row0 = nullptr;         // [B * levels]: first packed row of the segment's episode
   int2* ep_tiles_dev = nullptr;       // the tiles of the head's two tile tables regrouped episode by episode
   DecodeSeg* dsegs_ep = nullptr;      // the decode's segment table with DecodeSeg::ncls set per image
+  // Code-sets head (sylph_fcos_head_codesets): every image is scored against G code sets; the logits of set g are columns
+  // [cs_col0[g], cs_col0[g] + cs_n[g]) of Plan::logits, and packed code row r produces column r.  The sets that take the fused
+  // GroupNorm + conv kernel (bf16, cls GroupNorm deferred, N <= 32: gn_logits_sets_kernel) come first, each at a multiple of 4 (the
+  // decode scan reads 16 bytes at a time), in cs_hot_blocks blocks of 32 rows; every other set follows at a multiple of 32 with the
+  // padded width conv_igemm gives it in sylph_fcos_head.  Read only while out.src says that the head outputs are such a head's.
+  std::vector<int> cs_n, cs_col0;
+  int cs_hot_blocks = 0, cs_hot_width = 0, cs_ld = 0;
+  int cs_rows = 0, cs_rows_cap = 0;   // packed rows of all sets; capacity of cs_code_w / cs_bias / cs_src_row
+  void* cs_code_w = nullptr;          // [cs_rows][256] compute dtype
+  float* cs_bias = nullptr;           // [2][cs_rows_cap]: zero-padded biases | the copy launch_pack_codes_episodes leaves for a scan (unread)
+  int* cs_src_row = nullptr;          // [cs_rows]: row of the caller's (sum N, 256) table, -1 for a padding row
+  DecodeSeg* dsegs_cs = nullptr;      // [G][B][levels]: DecodeSeg::ncls, cls0 and slot per set
+  int dsegs_cs_cap = 0;
+  // decode buffers of the code-sets decode: G * B slots, candidate buffers of cs_cand_cap per (slot, level); the plan's own (dbuf) stay
+  // those of the B-slot decodes, so neither kind of step reallocates when the two alternate
+  DecodeBuffers dbuf_cs{};
+  int cs_slots_cap = 0, cs_cand_cap = 0;
   float* bias_pad = nullptr;  // fp32 class biases of the last sylph_fcos_head: [0, cap) zero-padded to the packed code rows; [cap, 2 cap) the
                               // same with -inf from class N on (logits_scan_kernel: padded classes never pass the threshold)
   int bias_pad_cap = 0;

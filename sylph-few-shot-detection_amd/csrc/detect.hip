@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void decode_scan_kernel(const DecodeCfg cfg, c
       loc_u[u] = r_begin + r;
       c_u[u] = e < total ? g * W : N;  // N: nothing of this slot is a class
       if (e < total) {
-        const float* src = logits + ((size_t)sg.row0 + loc_u[u]) * cfg.logits_ld + g * W;
+        const float* src = logits + ((size_t)sg.row0 + loc_u[u]) * cfg.logits_ld + sg.cls0 + g * W;
         // the location's centerness / IoU logits ride along (a cache hit for all but the first group of a location): a
         // dependent load after the threshold test would stall every round on HBM latency
         const float* prow = pred + ((size_t)sg.row0 + loc_u[u]) * pred_ld;
@@ -334,8 +334,8 @@ __global__ __launch_bounds__(1024) void decode_partition_kernel(const DecodeCfg 
   __shared__ unsigned sh_bin, sh_need;
   __shared__ unsigned long long pool_stage[2048], tie_stage[1024];
   __shared__ unsigned pool_n, pool_base, tie_n, tie_base;
-  StagedAppend<2048> pool{pool_stage, &pool_n, &pool_base, &buf.pool_count[sg.image],
-                          buf.pool_key + (size_t)sg.image * cfg.pool_cap, (unsigned)cfg.pool_cap};
+  StagedAppend<2048> pool{pool_stage, &pool_n, &pool_base, &buf.pool_count[sg.slot],
+                          buf.pool_key + (size_t)sg.slot * cfg.pool_cap, (unsigned)cfg.pool_cap};
   StagedAppend<1024> ties{tie_stage, &tie_n, &tie_base, &state[0], buf.sel_tie + (size_t)seg * SEL_TIE, (unsigned)SEL_TIE};
   pool.init();
   ties.init();
@@ -402,8 +402,8 @@ __global__ __launch_bounds__(1024) void decode_finish_kernel(const DecodeCfg cfg
   __shared__ unsigned sh_remain;
   __shared__ unsigned long long pool_stage[2048];
   __shared__ unsigned pool_n, pool_base;
-  StagedAppend<2048> pool{pool_stage, &pool_n, &pool_base, &buf.pool_count[sg.image],
-                          buf.pool_key + (size_t)sg.image * cfg.pool_cap, (unsigned)cfg.pool_cap};
+  StagedAppend<2048> pool{pool_stage, &pool_n, &pool_base, &buf.pool_count[sg.slot],
+                          buf.pool_key + (size_t)sg.slot * cfg.pool_cap, (unsigned)cfg.pool_cap};
   pool.init();
   __syncthreads();
   if (n_b <= (unsigned)SEL_TIE) {
@@ -742,7 +742,7 @@ __global__ __launch_bounds__(1024) void nms_kernel(const DecodeCfg cfg, const De
   if (n > (unsigned)cfg.pool_cap) n = cfg.pool_cap;
   const int nw = (int)((n + 63) / 64);
   const size_t base = (size_t)img * cfg.pool_cap;
-  const ImageOut io = img_out[img];
+  const ImageOut io = img_out[segs[(size_t)img * cfg.nlevels].image];  // img: the block's output slot
   const int K = cfg.post_nms_topk;
   const float thr = cfg.nms_thresh;
   const bool nms_on = thr > 0.f;

@@ -110,6 +110,98 @@ __global__ __launch_bounds__(256) void gn_logits_kernel(const bf16_t* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The same pass for SEVERAL code sets over the same images (sylph_fcos_head_codesets; the loop it stands for: one query pass per
+// support seed, meta_fcos_runner.py:451-672, or one per tenant of a served frame).  Everything in front of the class-conditional conv is
+// class-agnostic (fcos.py:582-667, head_utils.py:60-81), so a 32-row group of the tower output is read from HBM and normalised ONCE
+// and multiplied by NB blocks of 32 code rows held in registers: NB MFMAs per k-step into NB accumulators.  Operand load,
+// fma -> bf16 -> ReLU rounding point, K order and mfma_f32_32x32x16_bf16 are gn_logits_kernel's, and an MFMA output element depends on
+// its own code row and activation row only -- not on the column it sits in -- so a class's logits are bit for bit those of the
+// one-set kernel wherever its row lies in the packed table; a set may straddle two blocks.
+// w: [32 NB][256] bf16 (zero rows where no class sits), bias: as many fp32 (zeros without a bias); column n of the launch is packed
+// row n, written at out[row][n] for n < width (a multiple of 4).  The NB x 64 registers of code fragments, 64 of raw x and NB x 16
+// accumulators fit the 512-register file of one wave per SIMD (NB = 4: no scratch in the compiler's resource report).
+template <int NB>
+__global__ __launch_bounds__(256) void gn_logits_sets_kernel(const bf16_t* __restrict__ x, int ld, const float2* __restrict__ coef,
+                                                             const bf16_t* __restrict__ w, const float* __restrict__ bias,
+                                                             float* __restrict__ out, int out_ld, int width,
+                                                             const SegDesc* __restrict__ segs, const int2* __restrict__ tiles, int n_tiles) {
+  __shared__ __attribute__((aligned(16))) float cf[4][512];  // per wave: (a0, a1, b0, b1) per channel pair of its current segment
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
+
+  bf16x8 Wf[NB][16];  // lane (n = 32 b + l31, k half lh): loaded once, the code blocks never change within a launch
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) Wf[b][ks] = *reinterpret_cast<const bf16x8*>(w + (size_t)(32 * b + l31) * 256 + ks * 16 + lh * 8);
+
+  int cur_seg = -1;
+  const int n_groups = n_tiles * 4, stride = gridDim.x * 4;
+  for (int g = blockIdx.x * 4 + wave; g < n_groups; g += stride) {
+    const int2 tl = tiles[g >> 2];
+    const int seg = tl.x, r0 = tl.y + (g & 3) * 32;
+    const SegDesc& sd = segs[seg];
+    const int nrows = sd.out_H * sd.out_W;
+    if (r0 >= nrows) continue;  // wave-uniform
+    if (seg != cur_seg) {       // wave-private coefficient table, carried from one row group to the next
+      cur_seg = seg;
+      const float2* cp = coef + (size_t)seg * 256;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int pr = lane + 64 * i;  // channel pair
+        const float2 c0 = cp[2 * pr], c1 = cp[2 * pr + 1];
+        *reinterpret_cast<float4*>(&cf[wave][4 * pr]) = make_float4(c0.x, c1.x, c0.y, c1.y);
+      }
+    }
+    const int row = r0 + l31;
+    const bool valid = row < nrows;
+    const size_t grow = (size_t)(sd.out_row0 + (valid ? row : nrows - 1));
+    const bf16_t* xp = x + grow * ld + lh * 8;
+    u32x4 xv[16];
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) xv[ks] = *reinterpret_cast<const u32x4*>(xp + ks * 16);
+    f32x16 acc[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) {
+      const float* cq = &cf[wave][(ks * 16 + lh * 8) * 2];  // 4 channel pairs x (a0, a1, b0, b1)
+      u32x4 yv;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float4 c4 = *reinterpret_cast<const float4*>(cq + 4 * e);
+        const f32x2 xf = {__uint_as_float(xv[ks][e] << 16), __uint_as_float(xv[ks][e] & 0xffff0000u)};
+        const f32x2 av = {c4.x, c4.y}, bv = {c4.z, c4.w};
+        const f32x2 r = __builtin_elementwise_fma(xf, av, bv);
+        bf16x2 pk;
+        pk[0] = (bf16_t)r[0];
+        pk[1] = (bf16_t)r[1];
+        const s16x2 z = {0, 0};
+        yv[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pk), z));  // ReLU on the bf16 pair
+      }
+#pragma unroll
+      for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[b][ks], __builtin_bit_cast(bf16x8, yv), acc[b], 0, 0, 0);
+    }
+    if (valid) {
+      float* op = out + grow * out_ld + 4 * lh;
+      const float* bp = bias + 4 * lh;
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int n = 32 * b + 8 * q;  // D^T: register 4q + e of a lane is column 32 b + 8 q + 4 lh + e of row l31
+          if (n + 4 * lh < width) {
+            const float4 b4 = *reinterpret_cast<const float4*>(bp + n);  // (L2 hits: the biases are not worth 16 NB registers)
+            *reinterpret_cast<float4*>(op + n) =
+                make_float4(acc[b][4 * q] + b4.x, acc[b][4 * q + 1] + b4.y, acc[b][4 * q + 2] + b4.z, acc[b][4 * q + 3] + b4.w);
+          }
+        }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Last GroupNorm + ReLU of the bbox tower fused into the 3x3 prediction convs (bbox_pred 4 + ctrness 1 [+ iou 1] channels).
 // A 3x3 conv with a handful of output channels is linear in its taps:
 //     pred[r][n] = sum_tap ( xn[r + shift(tap)] . W[tap][n] ),     xn = relu(GN(x)),  zero outside the map,
@@ -450,6 +542,27 @@ int launch_gn_logits(const void* x, int ld, const float2* coef, const void* w, c
   const int grid = want < HEAD_STREAM_MAX_BLOCKS ? want : HEAD_STREAM_MAX_BLOCKS;
   hipLaunchKernelGGL(gn_logits_kernel<false>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, N, nullptr, out,
                      out_ld, segs, tiles, n_tiles);
+  return (int)hipGetLastError();
+}
+
+// w: [32 * nblocks][256] bf16, bias: as many fp32 (never null: zeros without a bias), nblocks in 1 .. 4; out: fp32 [rows][out_ld], columns
+// [0, width) written, width a multiple of 4 in (32 (nblocks - 1), 32 nblocks], out_ld a multiple of 4 >= width
+int launch_gn_logits_sets(const void* x, int ld, const float2* coef, const void* w, const float* bias, int nblocks, float* out, int out_ld,
+                          int width, const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s) {
+  if (nblocks < 1 || nblocks > GN_SETS_MAX_BLOCKS || !bias || width <= 32 * (nblocks - 1) || width > 32 * nblocks || (width & 3) != 0 ||
+      out_ld < width || (out_ld & 3) != 0 || n_tiles <= 0)
+    return -1;
+  const int grid = n_tiles < HEAD_STREAM_MAX_BLOCKS ? n_tiles : HEAD_STREAM_MAX_BLOCKS;  // one block = one 128-row tile per sweep
+#define SYLPH_SETS_LAUNCH(NB)                                                                                                            \
+  hipLaunchKernelGGL(gn_logits_sets_kernel<NB>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, out, \
+                     out_ld, width, segs, tiles, n_tiles)
+  switch (nblocks) {
+    case 1: SYLPH_SETS_LAUNCH(1); break;
+    case 2: SYLPH_SETS_LAUNCH(2); break;
+    case 3: SYLPH_SETS_LAUNCH(3); break;
+    default: SYLPH_SETS_LAUNCH(4); break;
+  }
+#undef SYLPH_SETS_LAUNCH
   return (int)hipGetLastError();
 }
 

@@ -28,6 +28,9 @@ struct DecodeSeg {
   int image;       // batch index
   unsigned loc_base;  // sum_{l'<l} nloc_l'; global candidate ordinal = (loc_base + loc) * N + cls
   int ncls;        // 0: N = DecodeCfg::num_classes; mixed-episode head: N of the image's episode, negated where the fused scan has left its candidates
+  int cls0;        // first logits column of the segment's classes (a multiple of 4; 0 except in a code-sets table)
+  int slot;        // output slot: pool, sorted candidates and detections are per slot.  = image, except in a code-sets table, where the
+                   // slot of (set g, image i) is g * B + i and `image` keeps indexing the image-size table
 };
 
 struct DecodeCfg {
@@ -95,6 +98,10 @@ int launch_gn_cond3x3(const void* x, int ld, const float2* coef, const void* w, 
                       const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s);
 int launch_gn_logits_episodes(const void* x, int ld, const float2* coef, const void* w, const float* bias, const int* seg_row0, float* out,
                               int out_ld, const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s);
+// several code sets over the same images: nblocks <= GN_SETS_MAX_BLOCKS blocks of 32 packed code rows per pass over the tower output
+constexpr int GN_SETS_MAX_BLOCKS = 4;
+int launch_gn_logits_sets(const void* x, int ld, const float2* coef, const void* w, const float* bias, int nblocks, float* out, int out_ld,
+                          int width, const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s);  // head_fused.hip (bf16)
 int launch_gn_pred_taps(const void* x, int ld, const float2* coef, const void* w_taps, int cp, const float* bias, int relu_nch, int mul_nch,
                         float* planes_ws, size_t plane_rows, float* out, int out_ld, const SegDesc* segs, const int2* tiles, int n_tiles,
                         hipStream_t s);  // head_fused.hip: last bbox-tower GroupNorm + 3x3 prediction convs (bf16)
@@ -165,6 +172,7 @@ int launch_conv_group(DType dt, const GroupConvArgs& a, hipStream_t s);
 int launch_logits_scan(const void* x, int ld, const float2* coef, const void* w, void* wf_ws, const float* bias_scan,
                        const SegDesc* segs, const int2* tiles, int n_tiles, const float* pred, int pred_ld, const DecodeCfg& cfg,
                        const DecodeBuffers& buf, int nseg, bool clear_counts, hipStream_t s);
+// B: output slots (images; sets x images for a code-sets table), nseg = B * levels segments, slot-major
 int launch_decode(const DecodeCfg& cfg, const DecodeSeg* segs_dev, int nseg, int max_nloc, int B, int nw_bound,
                   const float* logits, const float* pred, int pred_ld, const DecodeBuffers& buf,
                   const ImageOut* img_out_dev, float* out_boxes, float* out_scores, int* out_classes,

@@ -57,6 +57,7 @@ PROTOTYPES = {
     "sylph_export_pyramid": (c_int, [c_void_p, c_int, c_void_p]),
     "sylph_fcos_head": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "sylph_fcos_head_episodes": (c_int, [c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "sylph_fcos_head_codesets": (c_int, [c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int)]),
     "sylph_fcos_head_pretrained": (c_int, [c_void_p, POINTER(c_int)]),
     "sylph_export_head": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylph_import_head": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -64,6 +65,8 @@ PROTOTYPES = {
     "sylph_roi_align_rois": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p]),
     "sylph_decode_nms": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylph_decode_nms_codesets": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylph_codegen": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sylph_codegen_classes": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "sylph_codegen_rois": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_int, POINTER(c_int), c_void_p]),

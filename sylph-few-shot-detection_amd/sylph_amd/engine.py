@@ -202,6 +202,42 @@ def config_from_cfg(cfg) -> SylphConfig:
     return sc
 
 
+def code_set_offsets(n_classes: Sequence[int]) -> List[int]:
+    """First row of every code set in the (sum N, 256) table of `Engine.head_code_sets` -- and first channel of its logits in what
+    `export_head` returns afterwards -- followed by sum N: [0, N_0, N_0 + N_1, ..., sum N]."""
+    off = [0]
+    for g, n in enumerate(n_classes):
+        if int(n) < 1:
+            raise ValueError(f"code set {g} is empty (N_g = {int(n)}): every set needs at least one class")
+        off.append(off[-1] + int(n))
+    return off
+
+
+def check_code_sets(codes, code_ksize: int = 1) -> List[int]:
+    """Validate the `[(cls_conv, cls_bias), ...]` argument of `Engine.head_code_sets` (no GPU needed) -> classes per set."""
+    if code_ksize != 1:
+        raise NotImplementedError(f"head_code_sets runs 1x1 class codes only: CODE_GENERATOR.CLS_LAYER kernel size {code_ksize} is not "
+                                  "supported here (call head once per code set)")
+    codes = list(codes)
+    if len(codes) == 0:
+        raise ValueError("head_code_sets needs at least one code set (G = 0)")
+    n = []
+    for g, (w, b) in enumerate(codes):
+        if w.dim() != 4:
+            raise ValueError(f"code set {g}: Weight has dimension: {w.dim()}")
+        if w.size(2) != 1 or w.size(3) != 1:
+            raise ValueError(f"code set {g}: class code of spatial size {w.size(2)}x{w.size(3)}: cls_conv must be (N, 256 k, 1, 1)")
+        if w.size(1) < 256 or w.size(1) % 256 != 0:
+            raise ValueError(f"code set {g}: weight has wrong shape, {tuple(w.shape)}: 256 channels (or a multiple, ROIEncoder) expected")
+        if b is not None and b.numel() != w.size(0):
+            raise ValueError(f"code set {g}: {b.numel()} biases for {w.size(0)} classes")
+        n.append(int(w.size(0)))
+    code_set_offsets(n)  # (an empty set)
+    if len({b is None for _, b in codes}) != 1:
+        raise ValueError("cls_bias must be given for every code set or for none")
+    return n
+
+
 class Engine:
     """One HIP context: weights + per-batch-shape workspaces, all on ``device``."""
 
@@ -442,6 +478,73 @@ class Engine:
         W, Bv, n = self._ep_codes
         self._ncls = max(n)
         check(self.L.sylph_fcos_head_episodes(self._ctx, len(n), _ptr(W), _ptr(Bv), _iarr(n), _iarr(image_episode)), "fcos_head_episodes")
+
+    def head_code_sets(self, codes):
+        """The head for a batch whose every image is scored against several code sets (sylph_fcos_head_codesets): `codes` is a list of
+        (cls_conv (N_g, 256 k, 1, 1), cls_bias (N_g) or None).  The towers and box heads run once; `decode_code_sets` then returns for
+        (set g, image i) what `head(*codes[g])` + `decode()` give image i on the same batch, classes numbered within set g."""
+        self._stream()
+        codes = [(w, b) for w, b in codes]
+        check_code_sets(codes, self.code_ksize)
+        if self.owd:  # the codes are not read (one all-ones class per set, see head)
+            if getattr(self, "_owd_codes", None) is None:
+                self._owd_codes = (torch.zeros(1, 256, device=self.device), torch.full((1,), 40.0, device=self.device))
+            w1, b1 = self._owd_codes
+            key, folded = ("owd", len(codes)), [(w1, b1)] * len(codes)
+        else:
+            for w, _ in codes:
+                if w.size(1) != 256 and not self.is_roi_encoder:
+                    raise ValueError(f"weight has wrong shape, {tuple(w.shape)}: feature.size(1) != weight.size(1) (256 channels expected)")
+            key = (tuple((id(w), w._version, id(b), None if b is None else b._version) for w, b in codes),
+                   tuple(self.cond_scales), self._cond_scales_loaded, self._lib_writes)
+            folded = None
+        # the packed (sum N, 256) table is kept like head's single code set: no cast / concat kernels in a steady serving loop
+        if getattr(self, "_cs_codes_key", None) != key:
+            if folded is None:
+                folded = [self._fold_codes(w, b) for w, b in codes]
+            W = torch.cat([w.reshape(w.size(0), -1) for w, _ in folded]).contiguous()
+            Bv = torch.cat([b for _, b in folded]).contiguous() if folded[0][1] is not None else None
+            self._cs_codes = (W, Bv, [int(w.size(0)) for w, _ in folded])
+            self._cs_codes_src = codes  # keeps the ids alive
+            self._cs_codes_key = key
+        W, Bv, n = self._cs_codes
+        self._ncls = sum(n)
+        self._cs_n = list(n)
+        check(self.L.sylph_fcos_head_codesets(self._ctx, len(n), _ptr(W), _ptr(Bv), _iarr(n)), "fcos_head_codesets")
+
+    def decode_code_sets(self, out_sizes: Optional[List[Tuple[int, int]]] = None, max_out: Optional[int] = None):
+        """After `head_code_sets`: -> [g][i] dicts with the fields of `decode` (sylph_decode_nms_codesets).  Raises on a status bit as
+        `decode` does.  One device->host copy of the G * B counts."""
+        self._stream()
+        B = self._batch[0]
+        G = len(getattr(self, "_cs_n", None) or [0])
+        S = G * B
+        if max_out is None:
+            max_out = self.default_max_out()
+        dev = self.device
+        boxes = torch.empty(S, max_out, 4, device=dev)
+        scores = torch.empty(S, max_out, device=dev)
+        ints = torch.empty(3, S, max_out, device=dev, dtype=torch.int32)
+        locs = torch.empty(S, max_out, 2, device=dev)
+        counts = torch.empty(S + 1, device=dev, dtype=torch.int32)  # [S] = status word
+        oh = _iarr([s[0] for s in out_sizes]) if out_sizes is not None else None
+        ow = _iarr([s[1] for s in out_sizes]) if out_sizes is not None else None
+        check(self.L.sylph_decode_nms_codesets(self._ctx, G, oh, ow, max_out, _ptr(boxes), _ptr(scores), _ptr(ints[0]), _ptr(ints[1]),
+                                               _ptr(locs), _ptr(ints[2]), _ptr(counts), c_void_p(counts.data_ptr() + 4 * S)),
+              "decode_nms_codesets")
+        # pinned staging for the counts: the per-engine ring of decode_launch (a fresh pinned allocation per step costs milliseconds)
+        slot = self.__dict__.setdefault("_count_ring", {}).setdefault(("code sets", S), {"bufs": [], "next": 0})
+        if len(slot["bufs"]) < 8:
+            slot["bufs"].append(torch.empty(S + 1, dtype=torch.int32, pin_memory=True))
+            host_counts = slot["bufs"][-1]
+        else:
+            host_counts = slot["bufs"][slot["next"] % 8]
+            slot["next"] += 1
+        host_counts.copy_(counts, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        flat = self.decode_fetch((S, boxes, scores, ints, None, locs, None, host_counts, done, torch.cuda.current_stream(dev)))
+        return [flat[g * B:(g + 1) * B] for g in range(G)]
 
     def head_pretrained(self) -> int:
         """forward_base_train (fcos.py:543-578): towers + the checkpoint's own cls_logits conv (1x1 or 3x3) -> number of classes."""

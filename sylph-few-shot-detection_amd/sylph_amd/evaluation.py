@@ -326,6 +326,41 @@ def inference_on_dataset_with_class_codes(model, data_loader, evaluator, class_c
     return results if results is not None else {}
 
 
+def inference_on_dataset_with_code_sets(model, data_loader, evaluators, class_code_sets):
+    """Loop B once for SEVERAL code sets: one pass over the query loader, model(inputs, class_code_sets=..., run_type=
+    "meta_learn_test_instance") per batch (the backbone and towers run once, the class-conditional conv and decode per set); evaluator g
+    sees what inference_on_dataset_with_class_codes would have shown it with class_code_sets[g] -> [evaluator_g.evaluate() for g].
+    The reference runs the query set once per support seed (meta_fcos_runner.py:451-672 over meta_learn_evaluation.py:367-470)."""
+    devices = get_world_size()
+    class_code_sets = list(class_code_sets)
+    if len(class_code_sets) == 0:
+        raise ValueError("class_code_sets is empty")
+    evaluators = [e if e is not None else _NoOpEvaluator() for e in (evaluators if evaluators is not None else [None] * len(class_code_sets))]
+    if len(evaluators) != len(class_code_sets):
+        raise ValueError(f"{len(evaluators)} evaluators for {len(class_code_sets)} code sets: one evaluator per set")
+    total = len(data_loader)
+    logger.info(f"Start inference with {len(class_code_sets)} sets of predicted class codes on {total} images")
+    for e in evaluators:
+        e.reset()
+    num_warmup = min(5, max(total - 1, 0))
+    start_time, compute = time.perf_counter(), 0.0
+    with ExitStack() as stack:
+        if isinstance(model, nn.Module):
+            stack.enter_context(inference_context(model))
+        stack.enter_context(torch.no_grad())
+        for idx, inputs in enumerate(data_loader):
+            if idx == num_warmup:
+                start_time, compute = time.perf_counter(), 0.0
+            t0 = time.perf_counter()
+            outputs = model(inputs, class_code_sets=class_code_sets, run_type="meta_learn_test_instance")
+            compute += time.perf_counter() - t0
+            for e, out in zip(evaluators, outputs):
+                e.process(inputs, out)
+    _log_totals("query", "img", time.perf_counter() - start_time, compute, total - num_warmup, devices)
+    results = [e.evaluate() for e in evaluators]
+    return [r if r is not None else {} for r in results]
+
+
 DET_ROW = 8  # image id | x0 | y0 | x1 | y1 | score | contiguous class id | valid
 
 

@@ -121,6 +121,11 @@ class MetaFCOS(HipComponent):
         self.engine.head_episodes(codes, image_episode)
         return self.engine.decode(out_sizes)
 
+    def forward_code_sets(self, codes, out_sizes):
+        """Every image against several code sets in one step (Engine.head_code_sets) -> [set][image] detections."""
+        self.engine.head_code_sets(codes)
+        return self.engine.decode_code_sets(out_sizes)
+
     def forward_pretrained(self, out_sizes):
         """support_set_per_class_code = None (fcos.py:543-578): the checkpoint's own cls_logits conv, any kernel size the library
         packed (1x1 / 3x3)."""
@@ -216,6 +221,21 @@ def build_code_generator(cfg, feature_channels, feature_levels, strides):
     return CODE_GENERATOR_REGISTRY.get(name)(cfg, feature_channels, feature_levels, strides)
 
 
+def check_class_code_args(class_code, class_code_sets):
+    """`class_code` and `class_code_sets` of MetaOneStageDetector.forward exclude each other; the sets are a non-empty list of dicts."""
+    if class_code_sets is None:
+        return None
+    if class_code is not None:
+        raise ValueError("class_code and class_code_sets were both given: pass the code dict of ONE step as class_code, or the dicts of "
+                         "several code sets over the same images as class_code_sets")
+    if not isinstance(class_code_sets, (list, tuple)) or len(class_code_sets) == 0:
+        raise ValueError("class_code_sets must be a non-empty list of class-code dicts")
+    for g, d in enumerate(class_code_sets):
+        if not isinstance(d, dict) or "cls_conv" not in d:
+            raise ValueError(f"class_code_sets[{g}] is not a class-code dict (no cls_conv)")
+    return list(class_code_sets)
+
+
 def group_episodes(class_code, num_inputs: int):
     """A list / tuple of class-code dicts, one per input -> (the distinct dicts in order of first appearance, episode index per input).
     Entries that are the SAME OBJECT form one episode: equal contents in two dicts are two episodes (nothing is compared)."""
@@ -243,6 +263,8 @@ class MetaOneStageDetector(nn.Module):
       "meta_learn_test_instance"            -> forward_instances (class_code None: evaluation with the pretrained cls_logits)
                                                class_code a list / tuple of dicts, one per input: images of different episodes
                                                in one step (group_episodes; pred_classes index the image's own dict)
+                                               class_code_sets = [d_0, ..., d_{G-1}]: every image against G code sets in one step
+                                               -> a list over sets of what class_code=d_g returns (forward_instances_code_sets)
     Training is out of scope: calling the model in training mode raises NotImplementedError."""
 
     def __init__(self, cfg, dtype: Optional[str] = None, device_index: Optional[int] = None):
@@ -292,9 +314,14 @@ class MetaOneStageDetector(nn.Module):
         from .checkpoint import load_checkpoint_file
         return self.load_state_dict(load_checkpoint_file(path))
 
-    def forward(self, batched_inputs, class_code=None, run_type=None):
+    def forward(self, batched_inputs, class_code=None, run_type=None, class_code_sets=None):
         if self.training:
             raise NotImplementedError("training is out of scope of the MI355X inference path; call model.eval()")
+        sets = check_class_code_args(class_code, class_code_sets)
+        if sets is not None:
+            if run_type != "meta_learn_test_instance":
+                raise NotImplementedError(f"class_code_sets belongs to run_type 'meta_learn_test_instance', not {run_type!r}")
+            return self.forward_instances_code_sets(batched_inputs, sets)
         if run_type is None:
             # MetaProposalNetwork.forward (meta_one_stage_detector.py:120-141): a non-episodic model is a plain base detector
             if not self.episodic_learning:
@@ -427,6 +454,18 @@ class MetaOneStageDetector(nn.Module):
         """meta_one_stage_detector.py:261-296 -> [{"instances": Instances}] at input["height"/"width"] scale."""
         assert self.episodic_learning
         return self._detect(batched_inputs, class_codes)
+
+    def forward_instances_code_sets(self, batched_inputs: List[Dict[str, Any]], class_code_sets: List[Dict[str, torch.Tensor]]):
+        """The query batch against G code sets at ONE backbone / tower pass (sylph_fcos_head_codesets): the G query passes of the
+        TEST.REPEAT_TEST protocol (meta_fcos_runner.py:451-672) or G tenants of one frame -> [forward_instances(batch, d_g) for d_g]."""
+        assert self.episodic_learning
+        assert not self.training, "Not for training"
+        codes = [(d["cls_conv"], d.get("cls_bias")) for d in class_code_sets]
+        for w, _ in codes:
+            assert w.dim() == 4, f"Weight has dimension: {w.dim()}"
+            assert w.size(1) == 256
+        out_sizes = self._run_backbone(batched_inputs)
+        return [self._to_results(d, out_sizes) for d in self.proposal_generator.forward_code_sets(codes, out_sizes)]
 
     def _detect(self, batched_inputs: List[Dict[str, Any]], class_codes):
         assert not self.training, "Not for training"

@@ -13,7 +13,7 @@ import torch
 from . import config as _config
 from . import distributed as D
 from .evaluation import (format_class_codes_shared, inference_normalization, inference_on_dataset_with_class_codes,
-                         inference_on_support_set_dataset, inference_on_support_set_dataset_base)
+                         inference_on_dataset_with_code_sets, inference_on_support_set_dataset, inference_on_support_set_dataset_base)
 from .modeling import build_model as _build_model
 
 logger = logging.getLogger(__name__)
@@ -174,36 +174,42 @@ class MetaFCOSRunner:
             return len(ds)
         return fallback
 
+    def _episode_codes(self, cfg, model, support_loader, base_support_loader=None, output_folder: Optional[str] = None,
+                       num_classes: Optional[int] = None):
+        """The support half of ONE (dataset, seed) of meta_fcos_runner.py:497-560: support codes -> gather -> (base-class reduce +
+        replace) -> normalise -> the formatted class codes the query loop takes."""
+        sub = inference_on_support_set_dataset(model, support_loader, output_dir=output_folder)
+        n_items = self._global_len(support_loader, num_classes)
+        codes = self._gather_class_code(sub, capacity=D.shard_capacity(n_items) if n_items else None)
+        if base_support_loader is not None:
+            base_sub = inference_on_support_set_dataset_base(model, base_support_loader)
+            # the base path delivers at most one accumulated row per class and rank
+            n_base = num_classes if num_classes else self._global_len(base_support_loader)
+            base = self._gather_class_code(base_sub, reduce=True, engine=getattr(model, "engine", None), capacity=n_base)
+            by_cid = {int(c["support_set_target"]): c for c in base}
+            codes = [dict(c, class_code=by_cid[int(c["support_set_target"])]["class_code"])
+                     if int(c["support_set_target"]) in by_cid else c for c in codes]  # replace_class_code
+        if str(cfg.MODEL.META_LEARN.CODE_GENERATOR.NAME) != "ROIEncoder":
+            codes = inference_normalization(model, codes)  # ROIEncoder codes need none (and the reference call raises)
+        if num_classes is not None:
+            assert len(codes) == num_classes, \
+                f"Got {len(codes)} class codes for prediction, but expect to be {num_classes}."
+        return format_class_codes_shared(codes, device=model.device)
+
     def _episode(self, cfg, model, support_loader, query_loader, evaluator=None, base_support_loader=None,
                  output_folder: Optional[str] = None, num_classes: Optional[int] = None, eval_with_pretrained_code: bool = False):
         """ONE (dataset, seed) of meta_fcos_runner.py:497-560: support codes -> gather -> (base-class reduce + replace) ->
         normalise -> format -> query loop.  Returns (evaluator results, formatted class codes)."""
         class_codes = None
         if not eval_with_pretrained_code:
-            sub = inference_on_support_set_dataset(model, support_loader, output_dir=output_folder)
-            n_items = self._global_len(support_loader, num_classes)
-            codes = self._gather_class_code(sub, capacity=D.shard_capacity(n_items) if n_items else None)
-            if base_support_loader is not None:
-                base_sub = inference_on_support_set_dataset_base(model, base_support_loader)
-                # the base path delivers at most one accumulated row per class and rank
-                n_base = num_classes if num_classes else self._global_len(base_support_loader)
-                base = self._gather_class_code(base_sub, reduce=True, engine=getattr(model, "engine", None), capacity=n_base)
-                by_cid = {int(c["support_set_target"]): c for c in base}
-                codes = [dict(c, class_code=by_cid[int(c["support_set_target"])]["class_code"])
-                         if int(c["support_set_target"]) in by_cid else c for c in codes]  # replace_class_code
-            if str(cfg.MODEL.META_LEARN.CODE_GENERATOR.NAME) != "ROIEncoder":
-                codes = inference_normalization(model, codes)  # ROIEncoder codes need none (and the reference call raises)
-            if num_classes is not None:
-                assert len(codes) == num_classes, \
-                    f"Got {len(codes)} class codes for prediction, but expect to be {num_classes}."
-            class_codes = format_class_codes_shared(codes, device=model.device)
+            class_codes = self._episode_codes(cfg, model, support_loader, base_support_loader, output_folder, num_classes)
         res = inference_on_dataset_with_class_codes(model, query_loader, evaluator, class_codes,
                                                     eval_with_pretrained_code=eval_with_pretrained_code)
         return res, class_codes
 
     def _do_test_meta_learning(self, cfg, model, support_loader=None, query_loader=None, evaluator=None, base_support_loader=None,
                                output_folder: Optional[str] = None, num_classes: Optional[int] = None, train_iter=None,
-                               model_tag: str = "default", dataset_names: Optional[List[str]] = None):
+                               model_tag: str = "default", dataset_names: Optional[List[str]] = None, fuse_repeats: bool = False):
         """meta_fcos_runner.py:451-672.
 
         * With explicit loaders (support_loader + query_loader): ONE dataset / seed; returns (results, class_codes) -- the form
@@ -212,7 +218,11 @@ class MetaFCOSRunner:
           DATASETS.TEST (or `dataset_names`): loaders from the build_* methods (seeded support sets, :497-503),
           EVAL_WITH_PRETRAINED_CODE on "base" datasets (:483-486), USE_ALL_GTS_IN_BASE_CLASSES (:507-518), then
           results[f"seed{s}"][dataset] per run, results[model_tag][dataset] = the mean over seeds of every "bbox" metric
-          (:589-603) plus AP / APr / APc / APf "_avg" and "_std" over the seeds (:604-620); returns the results dict."""
+          (:589-603) plus AP / APr / APc / APf "_avg" and "_std" over the seeds (:604-620); returns the results dict.
+        * fuse_repeats=True with REPEAT_TEST > 1: every seed's class codes are built first and the query set of a dataset runs ONCE
+          against all of them (inference_on_dataset_with_code_sets: one backbone / tower pass per query batch, one evaluator per
+          seed); the results dict is the one of the loop above.  EVAL_WITH_PRETRAINED_CODE datasets and multi-rank runs keep one query
+          pass per seed."""
         if support_loader is not None or query_loader is not None:
             return self._episode(cfg, model, support_loader, query_loader, evaluator, base_support_loader, output_folder, num_classes)
         names = list(dataset_names if dataset_names is not None else cfg.DATASETS.TEST)
@@ -223,24 +233,55 @@ class MetaFCOSRunner:
         results = OrderedDict()
         results[model_tag] = OrderedDict()
         main = D.get_rank() == 0
+
+        def is_pretrained(name):
+            return "base" in name and bool(cfg.MODEL.META_LEARN.EVAL_WITH_PRETRAINED_CODE)
+
+        def folder_of(name, seed):
+            if output_folder or cfg.get("OUTPUT_DIR", None):
+                return os.path.join(output_folder or cfg.OUTPUT_DIR, "inference", model_tag,
+                                    str(train_iter) if train_iter is not None else "final", name, str(seed))
+            return None
+
+        def support_loaders(name, seed):
+            sup = self.build_episodic_learning_detection_test_support_set_loader(cfg, name, seed)
+            base = None
+            if bool(cfg.MODEL.META_LEARN.USE_ALL_GTS_IN_BASE_CLASSES):
+                base = self.build_episodic_learning_detection_test_support_set_base_loader(cfg, name)
+            return sup, base
+
+        fused = {}  # (seed, dataset) -> evaluator results of the one fused query pass of that dataset
+        if fuse_repeats and repeat > 1:
+            if D.get_world_size() > 1:
+                logger.info("fuse_repeats: a multi-rank run keeps one query pass per seed (every pass ends in its evaluator's own gather)")
+            else:
+                for name in names:
+                    if is_pretrained(name):
+                        continue  # no class codes to vary: the unfused loop below
+                    sets, evs = [], []
+                    for seed in range(repeat):
+                        sup, base = support_loaders(name, seed)
+                        sets.append(self._episode_codes(cfg, model, sup, base, folder_of(name, seed), self._global_len(sup)))
+                        evs.append(self.get_evaluator(cfg, name, output_folder=folder_of(name, seed)))
+                    qry = self.build_episodic_learning_detection_test_query_loader(cfg, name)
+                    for seed, per in enumerate(inference_on_dataset_with_code_sets(model, qry, evs, sets)):
+                        fused[(seed, name)] = per
         for seed in range(repeat):
             logger.info(f"{seed} out of {repeat} tests.")
             results[f"seed{seed}"] = OrderedDict()
             for name in names:
-                pretrained = "base" in name and bool(cfg.MODEL.META_LEARN.EVAL_WITH_PRETRAINED_CODE)
-                folder = None
-                if output_folder or cfg.get("OUTPUT_DIR", None):
-                    folder = os.path.join(output_folder or cfg.OUTPUT_DIR, "inference", model_tag,
-                                          str(train_iter) if train_iter is not None else "final", name, str(seed))
-                sup = base = None
-                if not pretrained:
-                    sup = self.build_episodic_learning_detection_test_support_set_loader(cfg, name, seed)
-                    if bool(cfg.MODEL.META_LEARN.USE_ALL_GTS_IN_BASE_CLASSES):
-                        base = self.build_episodic_learning_detection_test_support_set_base_loader(cfg, name)
-                qry = self.build_episodic_learning_detection_test_query_loader(cfg, name)
-                ev = self.get_evaluator(cfg, name, output_folder=folder)
-                n_cls = self._global_len(sup) if sup is not None else None
-                per, _ = self._episode(cfg, model, sup, qry, ev, base, folder, n_cls, eval_with_pretrained_code=pretrained)
+                pretrained = is_pretrained(name)
+                if (seed, name) in fused:
+                    per = fused[(seed, name)]
+                else:
+                    folder = folder_of(name, seed)
+                    sup = base = None
+                    if not pretrained:
+                        sup, base = support_loaders(name, seed)
+                    qry = self.build_episodic_learning_detection_test_query_loader(cfg, name)
+                    ev = self.get_evaluator(cfg, name, output_folder=folder)
+                    n_cls = self._global_len(sup) if sup is not None else None
+                    per, _ = self._episode(cfg, model, sup, qry, ev, base, folder, n_cls, eval_with_pretrained_code=pretrained)
                 if not main:
                     continue
                 results[f"seed{seed}"][name] = per
