@@ -63,7 +63,6 @@ Plan* get_plan(sylph_ctx* c, int B, int H, int W) {
   level_dims(c->cfg, H, W, p->hl, p->wl, p->off, &p->Ltot);
   p->img_h.assign(B, H);
   p->img_w.assign(B, W);
-  memset(&p->dbuf, 0, sizeof(p->dbuf));
   Plan* raw = p.get();
   c->plans[key] = std::move(p);
   return raw;

@@ -224,55 +224,78 @@ static std::vector<DecodeSeg> decode_segs(const sylph_ctx* c, const Plan* P, con
 
 static int build_decode(sylph_ctx* c, Plan* P) {
   if (P->decode_built) return 0;
-  const int L = c->cfg.nlevels, B = P->B, nseg = B * L;
+  const int L = c->cfg.nlevels, B = P->B;
   const std::vector<DecodeSeg> ds = decode_segs(c, P, nullptr);
   RET(upload(c, (void**)&P->dsegs, ds.data(), ds.size() * sizeof(DecodeSeg)));
   int pool = 64;
   while (pool < L * c->cfg.pre_nms_topk) pool <<= 1;
   if (pool > 8192) return fail("levels * PRE_NMS_TOPK exceeds the 8192-entry on-chip sort capacity");
-  P->pool_cap = pool;
-  DecodeBuffers& d = P->dbuf;  // (cand_key, cand_idx: ensure_decode)
-  RET(c->dalloc((void**)&d.cand_count, (size_t)nseg * 4));
-  RET(c->dalloc((void**)&d.sel_ws, (size_t)nseg * SEL_WS * 4));
-  RET(c->dalloc((void**)&d.sel_tie, (size_t)nseg * SEL_TIE * 8));
-  RET(c->dalloc((void**)&d.pool_key, (size_t)B * pool * 8));
-  RET(c->dalloc((void**)&d.pool_count, (size_t)B * 4));
-  RET(c->dalloc((void**)&d.s_box, (size_t)B * pool * 16));
-  RET(c->dalloc((void**)&d.s_score, (size_t)B * pool * 4));
-  RET(c->dalloc((void**)&d.s_cls, (size_t)B * pool * 4));
-  RET(c->dalloc((void**)&d.s_level, (size_t)B * pool * 4));
-  RET(c->dalloc((void**)&d.s_loc, (size_t)B * pool * 8));
-  RET(c->dalloc((void**)&d.s_ord, (size_t)B * pool * 4));
-  RET(c->dalloc((void**)&d.status, 8));
-  // zero once: every decode leaves these zero again (nms_kernel)
-  HIPCHK(hipMemsetAsync(d.cand_count, 0, (size_t)nseg * 4, c->stream));
-  HIPCHK(hipMemsetAsync(d.sel_ws, 0, (size_t)nseg * SEL_WS * 4, c->stream));
-  HIPCHK(hipMemsetAsync(d.pool_count, 0, (size_t)B * 4, c->stream));
-  HIPCHK(hipMemsetAsync(d.status, 0, 8, c->stream));
+  P->pool_cap = pool;  // (the decode buffers themselves: ensure_decode_slots)
   RET(c->dalloc((void**)&P->img_out_dev, sizeof(ImageOut) * B));
   HIPCHK(hipHostMalloc((void**)&P->img_out_host, sizeof(ImageOut) * B));
   P->decode_built = true;
   return 0;
 }
 
-// the decode buffers of the plan, with candidate buffers for ncls classes (more than the last call's: they grow)
-static int ensure_decode(sylph_ctx* c, Plan* P, int ncls) {
-  BUILD(build_decode(c, P), P);
-  if (want_cand_cap(c, P, ncls) <= P->cand_cap) return 0;
-  const size_t bytes = (size_t)P->B * c->cfg.nlevels * want_cand_cap(c, P, ncls) * 4;
-  c->dfree(P->dbuf.cand_key); c->dfree(P->dbuf.cand_idx);
-  P->dbuf.cand_key = nullptr; P->dbuf.cand_idx = nullptr; P->cand_cap = 0;
-  RET(c->dalloc((void**)&P->dbuf.cand_key, bytes));
-  RET(c->dalloc((void**)&P->dbuf.cand_idx, bytes));
-  P->cand_cap = want_cand_cap(c, P, ncls);
+// If need > *cap: release *ptr and allocate need * bytes_per_unit bytes.  Freed first, and *ptr null and *cap 0 across the allocation: a
+// failure leaves no capacity that lies.
+template <class T>
+static int grow_dev(sylph_ctx* c, T** ptr, int* cap, int need, size_t bytes_per_unit) {
+  if (need <= *cap) return 0;
+  c->dfree(*ptr);
+  *ptr = nullptr; *cap = 0;
+  RET(c->dalloc((void**)ptr, (size_t)need * bytes_per_unit));
+  *cap = need;
   return 0;
 }
 
-static DecodeCfg decode_cfg(const sylph_ctx* c, const Plan* P, const HeadOut& o, int max_out) {
+// Decode buffers S for `slots` output slots (B: sylph_decode_nms on Plan::dec; G * B: sylph_decode_nms_codesets on Plan::dec_cs) with
+// candidate buffers for ncls classes per (slot, level).  Two tiers: the per-slot members are allocated, and zeroed once (every decode
+// leaves them zero again: nms_kernel), when `slots` grows; cand_key / cand_idx are reallocated alone when the candidate capacity grows.
+// Growth must never discard candidates that a fused scan has left for the decode.  It does not: the slots of Plan::dec never grow after
+// the first call (B belongs to the plan), launch_cond grows the candidate buffers BEFORE it launches the scan, and the decode that
+// follows asks for the same ncls (HeadOut::ncls); no head leaves candidates in Plan::dec_cs.
+static int ensure_decode_slots(sylph_ctx* c, Plan* P, DecodeSlots& S, int slots, int ncls) {
+  BUILD(build_decode(c, P), P);
+  const size_t L = c->cfg.nlevels, pool = P->pool_cap;
+  DecodeBuffers& d = S.buf;
+  if (slots > S.slots_cap) {
+    const struct { void** p; size_t per_slot; bool zero; } per[] = {
+        {(void**)&d.cand_count, L * 4, true},   {(void**)&d.sel_ws, L * SEL_WS * 4, true}, {(void**)&d.sel_tie, L * SEL_TIE * 8, false},
+        {(void**)&d.pool_key, pool * 8, false}, {(void**)&d.pool_count, 4, true},          {(void**)&d.s_box, pool * 16, false},
+        {(void**)&d.s_score, pool * 4, false},  {(void**)&d.s_cls, pool * 4, false},       {(void**)&d.s_level, pool * 4, false},
+        {(void**)&d.s_loc, pool * 8, false},    {(void**)&d.s_ord, pool * 4, false}};
+    for (const auto& m : per) { c->dfree(*m.p); *m.p = nullptr; }
+    c->dfree(d.cand_key); c->dfree(d.cand_idx);
+    d.cand_key = nullptr; d.cand_idx = nullptr;
+    S.slots_cap = 0; S.cand_cap = 0;
+    for (const auto& m : per) {
+      RET(c->dalloc(m.p, (size_t)slots * m.per_slot));
+      if (m.zero) HIPCHK(hipMemsetAsync(*m.p, 0, (size_t)slots * m.per_slot, c->stream));
+    }
+    if (!d.status) {
+      RET(c->dalloc((void**)&d.status, 8));
+      HIPCHK(hipMemsetAsync(d.status, 0, 8, c->stream));
+    }
+    S.slots_cap = slots;
+  }
+  const int cap = want_cand_cap(c, P, ncls);
+  if (cap > S.cand_cap) {
+    const size_t bytes = (size_t)S.slots_cap * L * cap * 4;
+    c->dfree(d.cand_key); c->dfree(d.cand_idx);
+    d.cand_key = nullptr; d.cand_idx = nullptr; S.cand_cap = 0;
+    RET(c->dalloc((void**)&d.cand_key, bytes));
+    RET(c->dalloc((void**)&d.cand_idx, bytes));
+    S.cand_cap = cap;
+  }
+  return 0;
+}
+
+static DecodeCfg decode_cfg(const sylph_ctx* c, const Plan* P, const DecodeSlots& S, const HeadOut& o, int max_out) {
   DecodeCfg d;
   d.num_classes = o.ncls; d.logits_ld = o.logits_ld; d.pre_nms_thresh = c->cfg.pre_nms_thresh;
   d.pre_nms_topk = c->cfg.pre_nms_topk; d.nms_thresh = c->cfg.nms_thresh; d.post_nms_topk = c->cfg.post_nms_topk;
-  d.thresh_with_ctr = c->cfg.thresh_with_ctr; d.quality_mode = c->cfg.quality_mode; d.cand_cap = P->cand_cap;
+  d.thresh_with_ctr = c->cfg.thresh_with_ctr; d.quality_mode = c->cfg.quality_mode; d.cand_cap = S.cand_cap;
   d.pool_cap = P->pool_cap; d.nlevels = c->cfg.nlevels; d.max_out = max_out;
   return d;
 }
@@ -298,42 +321,40 @@ static HeadKind head_kind(const sylph_ctx* c, const Plan* P, int N, bool allow_s
   return N <= 32 ? HeadKind::gn_logits : HeadKind::igemm_after_apply;
 }
 
-// logits / packed-code buffers of the current batch for N classes (grown on demand; the previous buffers are released) -> o->ncls, o->logits_ld
-// codes1x1 = false: the logits alone (3x3 codes have a table of their own)
-static int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow, HeadOut* o, bool codes1x1 = true) {
+// the three buffers of pc for `rows` packed rows of row_bytes bytes (src_row only where the caller packs through such a table)
+static int ensure_codes(sylph_ctx* c, PackedCodes& pc, int rows, size_t row_bytes, bool with_src_row) {
+  if (rows > pc.cap) {
+    int cw = pc.cap, cb = pc.cap, cs = pc.cap;
+    pc.cap = 0;  // (one capacity for the three: it holds only once all of them have grown)
+    RET(grow_dev(c, &pc.w, &cw, rows, row_bytes));
+    RET(grow_dev(c, &pc.bias, &cb, rows, 2 * sizeof(float)));
+    if (with_src_row) RET(grow_dev(c, &pc.src_row, &cs, rows, sizeof(int)));
+    pc.cap = rows;
+  }
+  pc.rows = rows;
+  return 0;
+}
+
+// pc for the packed-row -> source-row table of a mixed or code-sets head, uploaded
+static int upload_codes(sylph_ctx* c, PackedCodes& pc, const std::vector<int>& src_row) {
+  HIPCHK(hipStreamSynchronize(c->stream));  // the previous step may still be reading the tables (this one, and those the caller uploads next)
+  RET(ensure_codes(c, pc, (int)src_row.size(), 256 * c->esz(), true));
+  HIPCHK(hipMemcpy(pc.src_row, src_row.data(), src_row.size() * sizeof(int), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// logits of the current batch for N classes and the fused scan's workspace for as many (grown on demand; the previous buffers are
+// released) -> o->ncls, o->logits_ld
+static int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow, HeadOut* o) {
   const size_t rows = (size_t)P->B * P->Ltot;
   const int Npad = cond_pad(N).Npad;
-  if (Npad > P->logits_cap_ld) {
-    if (P->logits) c->dfree(P->logits);
-    P->logits = nullptr; P->logits_cap_ld = 0;
-    RET(c->dalloc((void**)&P->logits, rows * Npad * sizeof(float)));
-    P->logits_cap_ld = Npad;
-  }
-  if (codes1x1 && Npad > P->code_w_cap) {
-    if (P->code_w) c->dfree(P->code_w);
-    P->code_w = nullptr; P->code_w_cap = 0;
-    RET(c->dalloc(&P->code_w, (size_t)Npad * 256 * c->esz()));
-    if (P->code_wf) c->dfree(P->code_wf);
-    P->code_wf = nullptr;
-    RET(c->dalloc(&P->code_wf, (size_t)Npad * 256 * c->esz()));
-    P->code_w_cap = Npad;
-  }
+  RET(grow_dev(c, &P->logits, &P->logits_cap_ld, Npad, rows * sizeof(float)));
+  RET(grow_dev(c, &P->code_wf, &P->code_wf_cap, Npad, 256 * c->esz()));
   // row pitch of the logits: the padded class count, except for <= 8 classes on the fused GroupNorm + class-conditional conv path
   // (gn_logits_kernel stores any multiple of 4 columns): 8 floats per location instead of 32 -- the conv writes and the scan reads
   // a quarter of the bytes (a 5-way episode: 46 MB instead of 183 MB per 64 images)
   o->logits_ld = allow_narrow && N <= 8 && head_kind(c, P, N, false) == HeadKind::gn_logits ? 8 : Npad;
   o->ncls = N;
-  return 0;
-}
-
-// the biases of a uniform head, zero-padded to Npad packed code rows (device copy: the caller's buffer need not outlive the call), and
-// behind them the copy with -inf in the padding rows that the fused scan reads
-static int ensure_bias_pad(sylph_ctx* c, Plan* P, int Npad) {
-  if (Npad <= P->bias_pad_cap) return 0;
-  if (P->bias_pad) c->dfree(P->bias_pad);
-  P->bias_pad = nullptr; P->bias_pad_cap = 0;
-  RET(c->dalloc((void**)&P->bias_pad, (size_t)2 * Npad * sizeof(float)));
-  P->bias_pad_cap = Npad;
   return 0;
 }
 
@@ -358,15 +379,15 @@ static HeadKind head_kind3x3(const sylph_ctx* c, const Plan* P, int N) {
 
 // the conv launch of the generic route for o.ncls classes, built once per (N, bias) on the plan's current buffers
 static int cond3x3_conv_ops(sylph_ctx* c, Plan* P, const HeadOut& o, const std::vector<OpFn>** ops_out) {
-  if (P->cond3_for[0] != P->code_w3 || P->cond3_for[1] != P->logits || P->cond3_for[2] != P->bias_pad) {
+  if (P->cond3_for[0] != P->codes3.w || P->cond3_for[1] != P->logits || P->cond3_for[2] != P->codes3.bias) {
     P->cond3_ops.clear();
-    P->cond3_for[0] = P->code_w3; P->cond3_for[1] = P->logits; P->cond3_for[2] = P->bias_pad;
+    P->cond3_for[0] = P->codes3.w; P->cond3_for[1] = P->logits; P->cond3_for[2] = P->codes3.bias;
   }
   const std::pair<int, int> key(o.ncls, o.has_bias ? 1 : 0);
   auto it = P->cond3_ops.find(key);
   if (it == P->cond3_ops.end()) {
     ConvLayer L;
-    L.w = P->code_w3; L.shift = o.has_bias ? P->bias_pad : nullptr;
+    L.w = P->codes3.w; L.shift = o.has_bias ? P->codes3.bias : nullptr;
     L.Cin = 256; L.Cout = o.ncls; L.Cout_pad = cond_pad(o.ncls).Npad; L.KH = 3; L.KW = 3;
     ConvOpts op; op.pad = 1; op.segs_per_image = c->cfg.nlevels; op.out_f32 = true;
     std::vector<OpFn> ops;
@@ -382,27 +403,21 @@ static int fcos_head_3x3(sylph_ctx* c, Plan* P, const float* cls_conv, const flo
   HeadOut o;
   o.src = HeadOut::cond;
   o.has_bias = c->cfg.cond_use_bias && cls_bias;
-  RET(ensure_logits(c, P, N, false, &o, false));
+  RET(ensure_logits(c, P, N, false, &o));
   const HeadKind k = head_kind3x3(c, P, N);
   const int Npad = cond_pad(N).Npad;
   if (k == HeadKind::gn_cond3x3 && N <= 8) o.logits_ld = 8;  // as gn_logits: the fused kernel stores any multiple of 4 columns
-  if (Npad > P->code_w3_cap) {
-    if (P->code_w3) c->dfree(P->code_w3);
-    P->code_w3 = nullptr; P->code_w3_cap = 0;
-    RET(c->dalloc(&P->code_w3, (size_t)Npad * 9 * 256 * c->esz()));
-    P->code_w3_cap = Npad;
-  }
-  RET(ensure_bias_pad(c, P, Npad));
+  PackedCodes& pc = P->codes3;
+  RET(ensure_codes(c, pc, Npad, 9 * 256 * c->esz(), false));
   // one launch in front of the towers, as for the 1x1 codes
-  KCHK(launch_pack_codes3x3(c->dt, cls_conv, N, 256, Npad, P->code_w3, o.has_bias ? cls_bias : nullptr, P->bias_pad, P->bias_pad + P->bias_pad_cap,
-                            c->stream), "pack_codes3x3");
+  KCHK(launch_pack_codes3x3(c->dt, cls_conv, N, 256, Npad, pc.w, o.has_bias ? cls_bias : nullptr, pc.bias, pc.bias + pc.cap, c->stream), "pack_codes3x3");
   RET(run_ops(c, P->head_ops, "fcos_head"));
   if (k == HeadKind::gn_cond3x3) {
     const Plan* PP = P;
-    const float* bias = o.has_bias ? P->bias_pad : nullptr;
+    const float* bias = o.has_bias ? pc.bias : nullptr;
     const int ld = o.logits_ld;
     KCHK(timed_op(c, "gn_cond3x3_kernel", 2.0 * (double)P->B * P->Ltot * N * 2304.0, c->stream, [=](hipStream_t st) {
-           return launch_gn_cond3x3(PP->cls_feat, 256, PP->cls_coef, PP->code_w3, bias, N, PP->logits, ld, PP->head_segs, PP->head_tiles32,
+           return launch_gn_cond3x3(PP->cls_feat, 256, PP->cls_coef, PP->codes3.w, bias, N, PP->logits, ld, PP->head_segs, PP->head_tiles32,
                                     PP->head_mtiles32, st);
          }), "gn_cond3x3");
   } else {
@@ -424,8 +439,9 @@ static int fcos_head_3x3(sylph_ctx* c, Plan* P, const float* cls_conv, const flo
 static int ep_tables(sylph_ctx* c, Plan* P, int E, const int* n_classes, const int* image_episode) {
   const int L = c->cfg.nlevels, B = P->B, nseg = B * L;
   std::vector<int> en(n_classes, n_classes + E), ei(image_episode, image_episode + B);
-  if (P->dsegs_ep && en == P->ep_n && ei == P->ep_image) return 0;
-  P->ep_n.clear(); P->ep_image.clear();  // (a failure below leaves no key that would match half-written tables)
+  Plan::Episodes& T = P->ep;
+  if (T.dsegs && en == T.n && ei == T.image) return 0;
+  T.n.clear(); T.image.clear();  // (a failure below leaves no key that would match half-written tables)
   std::vector<int> row0(E), src_row;
   int src = 0;
   for (int e = 0; e < E; ++e) {
@@ -434,7 +450,6 @@ static int ep_tables(sylph_ctx* c, Plan* P, int E, const int* n_classes, const i
     for (int r = 0; r < npad; ++r) src_row.push_back(r < N ? src + r : -1);
     src += N;
   }
-  const int rows = (int)src_row.size();
   std::vector<std::vector<int>> members(E);
   for (int b = 0; b < B; ++b) members[ei[b]].push_back(b);
   std::vector<int2> tiles, t32(E), tBM(E);
@@ -456,24 +471,15 @@ static int ep_tables(sylph_ctx* c, Plan* P, int E, const int* n_classes, const i
     img_ncls[b] = head_kind(c, P, N) == HeadKind::scan ? -N : N;  // negative: the fused scan leaves this image's candidates
   }
   const std::vector<DecodeSeg> ds = decode_segs(c, P, img_ncls.data());
-  HIPCHK(hipStreamSynchronize(c->stream));  // the previous step may still be reading the tables
-  if (rows > P->ep_rows_cap) {
-    c->dfree(P->ep_code_w); c->dfree(P->ep_bias); c->dfree(P->ep_src_row);
-    P->ep_code_w = nullptr; P->ep_bias = nullptr; P->ep_src_row = nullptr; P->ep_rows_cap = 0;
-    RET(c->dalloc(&P->ep_code_w, (size_t)rows * 256 * c->esz()));
-    RET(c->dalloc((void**)&P->ep_bias, (size_t)2 * rows * sizeof(float)));
-    RET(c->dalloc((void**)&P->ep_src_row, (size_t)rows * sizeof(int)));
-    P->ep_rows_cap = rows;
-  }
-  if (!P->ep_seg_row0) RET(c->dalloc((void**)&P->ep_seg_row0, (size_t)nseg * sizeof(int)));
-  if (!P->ep_tiles_dev) RET(c->dalloc((void**)&P->ep_tiles_dev, tiles.size() * sizeof(int2)));
-  if (!P->dsegs_ep) RET(c->dalloc((void**)&P->dsegs_ep, (size_t)nseg * sizeof(DecodeSeg)));
-  HIPCHK(hipMemcpy(P->ep_src_row, src_row.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(P->ep_seg_row0, seg_row0.data(), (size_t)nseg * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(P->ep_tiles_dev, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(P->dsegs_ep, ds.data(), ds.size() * sizeof(DecodeSeg), hipMemcpyHostToDevice));
-  P->ep_rows = rows; P->ep_row0 = row0; P->ep_tiles32 = t32; P->ep_tilesBM = tBM;
-  P->ep_n = en; P->ep_image = ei;
+  RET(upload_codes(c, T.codes, src_row));
+  if (!T.seg_row0) RET(c->dalloc((void**)&T.seg_row0, (size_t)nseg * sizeof(int)));
+  if (!T.tiles_dev) RET(c->dalloc((void**)&T.tiles_dev, tiles.size() * sizeof(int2)));
+  if (!T.dsegs) RET(c->dalloc((void**)&T.dsegs, (size_t)nseg * sizeof(DecodeSeg)));
+  HIPCHK(hipMemcpy(T.seg_row0, seg_row0.data(), (size_t)nseg * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(T.tiles_dev, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(T.dsegs, ds.data(), ds.size() * sizeof(DecodeSeg), hipMemcpyHostToDevice));
+  T.row0 = row0; T.tiles32 = t32; T.tilesBM = tBM;
+  T.n = en; T.image = ei;
   return 0;
 }
 
@@ -487,18 +493,24 @@ struct CondEp {
   float* out = nullptr;  // conv_igemm only: where column 0 of the launch goes (nullptr: Plan::logits; a code set: its first column)
 };
 
-// episode e of the head that o describes, to be run by kernel k; the uniform head is ONE episode over the plan's whole tile tables
+// launch e of the head that o describes, to be run by kernel k: episode e of a mixed head over its tile sub-lists, set e of a code-sets
+// head into its own columns, or (e = 0) the uniform head; the last two cover the plan's whole tile tables
 static CondEp cond_ep(const sylph_ctx* c, const Plan* P, const HeadOut& o, int e, HeadKind k) {
-  if (o.src != HeadOut::episodes)
-    return {P->code_w, o.has_bias ? P->bias_pad : nullptr, P->bias_pad + P->bias_pad_cap, o.ncls,
-            P->head_tiles32, P->head_mtiles32, P->head_tiles, P->head_mtiles, (double)P->B * P->Ltot};
-  const size_t r0 = (size_t)P->ep_row0[e];
-  const int2 a = P->ep_tiles32[e], b = P->ep_tilesBM[e];
-  int n_img = 0;
-  for (int v : P->ep_image) n_img += v == e;
-  const bool fused = k == HeadKind::gn_logits || k == HeadKind::scan;  // (their FLOPs count whole 128-row tiles)
-  return {(const char*)P->ep_code_w + r0 * 256 * c->esz(), o.has_bias ? P->ep_bias + r0 : nullptr, P->ep_bias + P->ep_rows_cap + r0, P->ep_n[e],
-          P->ep_tiles_dev + a.x, a.y, P->ep_tiles_dev + b.x, b.y, fused ? a.y * 128.0 : (double)n_img * P->Ltot};
+  const bool eps = o.src == HeadOut::episodes, sets = o.src == HeadOut::codesets;
+  const PackedCodes& pc = eps ? P->ep.codes : sets ? P->cs.codes : P->codes;
+  const size_t r0 = eps ? P->ep.row0[e] : sets ? P->cs.col0[e] : 0;
+  const int N = eps ? P->ep.n[e] : sets ? P->cs.n[e] : o.ncls;
+  CondEp v = {(const char*)pc.w + r0 * 256 * c->esz(), o.has_bias ? pc.bias + r0 : nullptr, pc.bias + pc.cap + r0, N,
+              P->head_tiles32, P->head_mtiles32, P->head_tiles, P->head_mtiles, (double)P->B * P->Ltot, sets ? P->logits + r0 : nullptr};
+  if (eps) {
+    const int2 a = P->ep.tiles32[e], b = P->ep.tilesBM[e];
+    int n_img = 0;
+    for (int i : P->ep.image) n_img += i == e;
+    const bool fused = k == HeadKind::gn_logits || k == HeadKind::scan;  // (their FLOPs count whole 128-row tiles)
+    v.t32 = P->ep.tiles_dev + a.x; v.n32 = a.y; v.tBM = P->ep.tiles_dev + b.x; v.nBM = b.y;
+    v.rows = fused ? a.y * 128.0 : (double)n_img * P->Ltot;
+  }
+  return v;
 }
 
 // one launch of kind k into the logits (pitch o.logits_ld) or, scan, into the decode buffers; clear_counts: the first scan of a head
@@ -513,8 +525,8 @@ static int launch_cond(sylph_ctx* c, Plan* P, const HeadOut& o, HeadKind k, cons
     return 0;
   }
   if (k == HeadKind::scan) {
-    RET(ensure_decode(c, P, o.ncls));
-    DecodeCfg d = decode_cfg(c, P, o, 0);
+    RET(ensure_decode_slots(c, P, P->dec, P->B, o.ncls));  // (in front of the scan: see there)
+    DecodeCfg d = decode_cfg(c, P, P->dec, o, 0);
     d.num_classes = N;
     const int nseg = P->B * c->cfg.nlevels;
     // the counters hold this scan's candidates from here on (set before the launch: a failed one may have counted too): whatever fills
@@ -523,7 +535,7 @@ static int launch_cond(sylph_ctx* c, Plan* P, const HeadOut& o, HeadKind k, cons
     P->cand_dirty = true;
     KCHK(timed_op(c, "logits_scan_kernel", flops, c->stream, [=](hipStream_t st) {
            return launch_logits_scan(PP->cls_feat, 256, PP->cls_coef, v.wt, PP->code_wf, v.bias_scan, PP->head_segs, v.t32, v.n32, PP->pred, 8, d,
-                                     PP->dbuf, nseg, clear_counts, st);
+                                     PP->dec.buf, nseg, clear_counts, st);
          }), "logits_scan");
     return 0;
   }
@@ -545,24 +557,38 @@ static int launch_cond(sylph_ctx* c, Plan* P, const HeadOut& o, HeadKind k, cons
   return 0;
 }
 
-// The class-conditional convs of the head that o describes, one launch per episode with the kernel head_kind picks for its N (the uniform
-// head is the one-episode case) -> *scanned: some episode left candidates instead of logits.  missing_only: only the episodes whose
-// logits a scan left out, with the unfused kernel (sylph_export_head).  The last cls GroupNorm is applied in place, ONCE, and only after
-// every kernel that reads the un-normalised tower output (gn_logits, scan) has been launched: the conv_igemm episodes come last.
-static int run_cond(sylph_ctx* c, Plan* P, const HeadOut& o, bool missing_only, bool* scanned) {
-  const int E = o.src == HeadOut::episodes ? (int)P->ep_n.size() : 1;
+// The launches of the uniform head (one) or of a mixed head (one per episode that has images), each with the kernel head_kind picks for its
+// N.  missing_only: only the episodes whose logits a scan left out, with the unfused kernel (sylph_export_head).
+struct CondLaunch { HeadKind k; CondEp v; };
+static std::vector<CondLaunch> cond_launches(const sylph_ctx* c, const Plan* P, const HeadOut& o, bool missing_only) {
+  std::vector<CondLaunch> list;
+  const int E = o.src == HeadOut::episodes ? (int)P->ep.n.size() : 1;
+  for (int e = 0; e < E; ++e) {
+    const int N = o.src == HeadOut::episodes ? P->ep.n[e] : o.ncls;
+    if (missing_only && head_kind(c, P, N) != HeadKind::scan) continue;
+    const HeadKind k = head_kind(c, P, N, !missing_only);
+    const CondEp v = cond_ep(c, P, o, e, k);
+    if (v.n32 != 0) list.push_back({k, v});  // (0: an episode no image uses)
+  }
+  return list;
+}
+
+// Runs the class-conditional convs `list` of the head that o describes -> *scanned: some launch left candidates instead of logits.  The
+// last cls GroupNorm is applied in place, ONCE, and only after every kernel that reads the un-normalised tower output (gn_logits, scan; the
+// caller's gn_logits_sets launches) has been launched: the conv_igemm launches that need it come last, in list order.  record_apply: the
+// apply gets a profile record of its own (the code-sets head's does).
+static int run_cond(sylph_ctx* c, Plan* P, const HeadOut& o, const std::vector<CondLaunch>& list, bool record_apply, bool* scanned) {
   bool applied = false, any_scan = false;
   for (int pass = 0; pass < 2; ++pass)
-    for (int e = 0; e < E; ++e) {
-      const int N = o.src == HeadOut::episodes ? P->ep_n[e] : o.ncls;
-      if (missing_only && head_kind(c, P, N) != HeadKind::scan) continue;
-      const HeadKind k = head_kind(c, P, N, !missing_only);
-      if ((k == HeadKind::igemm_after_apply) != (pass == 1)) continue;
-      const CondEp v = cond_ep(c, P, o, e, k);
-      if (v.n32 == 0) continue;  // an episode no image uses
-      if (pass == 1 && !applied) { KCHK(P->cls_apply(c->stream), "gn_apply (cls tower, last layer)"); applied = true; }
-      RET(launch_cond(c, P, o, k, v, !any_scan));
-      any_scan = any_scan || k == HeadKind::scan;
+    for (const CondLaunch& l : list) {
+      if ((l.k == HeadKind::igemm_after_apply) != (pass == 1)) continue;
+      if (pass == 1 && !applied) {
+        if (record_apply) RET(apply_cls_gn(c, P));
+        else KCHK(P->cls_apply(c->stream), "gn_apply (cls tower, last layer)");
+        applied = true;
+      }
+      RET(launch_cond(c, P, o, l.k, l.v, !any_scan));
+      any_scan = any_scan || l.k == HeadKind::scan;
     }
   if (scanned) *scanned = any_scan;
   return 0;
@@ -575,13 +601,14 @@ static int run_cond(sylph_ctx* c, Plan* P, const HeadOut& o, bool missing_only, 
 // fused conv + score scan is not used per set: its detections equal the logits route's (tests/test_head_sweeps_gpu.py).
 static bool set_is_hot(const sylph_ctx* c, const Plan* P, int N) { return head_kind(c, P, N, false) == HeadKind::gn_logits; }
 
-// Host and device tables of a code-sets head: column layout (Plan::cs_col0), packed-row -> source-row table, the decode's segment table
+// Host and device tables of a code-sets head: column layout (Plan::cs.col0), packed-row -> source-row table, the decode's segment table
 // of G * B slots.  Rebuilt only when n_classes differs from the previous call's on this plan.
 static int cs_tables(sylph_ctx* c, Plan* P, int G, const int* n_classes) {
   const int L = c->cfg.nlevels, B = P->B;
   std::vector<int> n(n_classes, n_classes + G);
-  if (P->dsegs_cs && n == P->cs_n) return 0;
-  P->cs_n.clear();  // (a failure below leaves no key that would match half-written tables)
+  Plan::CodeSets& T = P->cs;
+  if (T.dsegs && n == T.n) return 0;
+  T.n.clear();  // (a failure below leaves no key that would match half-written tables)
   std::vector<int> col0(G, 0), src0(G, 0);
   int col = 0, src = 0;
   for (int g = 0; g < G; ++g) { src0[g] = src; src += n[g]; }
@@ -610,61 +637,11 @@ static int cs_tables(sylph_ctx* c, Plan* P, int G, const int* n_classes) {
       d.ncls = n[g]; d.cls0 = col0[g]; d.slot = g * B + d.image;
       ds.push_back(d);
     }
-  HIPCHK(hipStreamSynchronize(c->stream));  // the previous step may still be reading the tables
-  if (rows > P->cs_rows_cap) {
-    c->dfree(P->cs_code_w); c->dfree(P->cs_bias); c->dfree(P->cs_src_row);
-    P->cs_code_w = nullptr; P->cs_bias = nullptr; P->cs_src_row = nullptr; P->cs_rows_cap = 0;
-    RET(c->dalloc(&P->cs_code_w, (size_t)rows * 256 * c->esz()));
-    RET(c->dalloc((void**)&P->cs_bias, (size_t)2 * rows * sizeof(float)));
-    RET(c->dalloc((void**)&P->cs_src_row, (size_t)rows * sizeof(int)));
-    P->cs_rows_cap = rows;
-  }
-  if (G * B * L > P->dsegs_cs_cap) {
-    c->dfree(P->dsegs_cs);
-    P->dsegs_cs = nullptr; P->dsegs_cs_cap = 0;
-    RET(c->dalloc((void**)&P->dsegs_cs, ds.size() * sizeof(DecodeSeg)));
-    P->dsegs_cs_cap = G * B * L;
-  }
-  HIPCHK(hipMemcpy(P->cs_src_row, src_row.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(P->dsegs_cs, ds.data(), ds.size() * sizeof(DecodeSeg), hipMemcpyHostToDevice));
-  P->cs_col0 = col0; P->cs_hot_blocks = hot_blocks; P->cs_hot_width = hot_width; P->cs_ld = ld; P->cs_rows = rows;
-  P->cs_n = n;
-  return 0;
-}
-
-// the decode buffers of G * B slots with candidate buffers for ncls classes per (slot, level): they grow, and are zeroed when they do
-// (every decode leaves them zero again: nms_kernel)
-static int ensure_decode_sets(sylph_ctx* c, Plan* P, int G, int ncls) {
-  BUILD(build_decode(c, P), P);
-  const int L = c->cfg.nlevels, slots = G * P->B, cap = want_cand_cap(c, P, ncls);
-  DecodeBuffers& d = P->dbuf_cs;
-  if (slots <= P->cs_slots_cap && cap <= P->cs_cand_cap) return 0;
-  const int ns = slots > P->cs_slots_cap ? slots : P->cs_slots_cap, nc = cap > P->cs_cand_cap ? cap : P->cs_cand_cap;
-  void* old[] = {d.cand_key, d.cand_idx, d.cand_count, d.sel_ws, d.sel_tie, d.pool_key, d.pool_count, d.s_box, d.s_score, d.s_cls, d.s_level,
-                 d.s_loc, d.s_ord, d.status};
-  for (void* p : old) c->dfree(p);
-  d = DecodeBuffers{};
-  P->cs_slots_cap = 0; P->cs_cand_cap = 0;
-  const size_t nseg = (size_t)ns * L, pool = (size_t)P->pool_cap;
-  RET(c->dalloc((void**)&d.cand_key, nseg * nc * 4));
-  RET(c->dalloc((void**)&d.cand_idx, nseg * nc * 4));
-  RET(c->dalloc((void**)&d.cand_count, nseg * 4));
-  RET(c->dalloc((void**)&d.sel_ws, nseg * SEL_WS * 4));
-  RET(c->dalloc((void**)&d.sel_tie, nseg * SEL_TIE * 8));
-  RET(c->dalloc((void**)&d.pool_key, ns * pool * 8));
-  RET(c->dalloc((void**)&d.pool_count, (size_t)ns * 4));
-  RET(c->dalloc((void**)&d.s_box, ns * pool * 16));
-  RET(c->dalloc((void**)&d.s_score, ns * pool * 4));
-  RET(c->dalloc((void**)&d.s_cls, ns * pool * 4));
-  RET(c->dalloc((void**)&d.s_level, ns * pool * 4));
-  RET(c->dalloc((void**)&d.s_loc, ns * pool * 8));
-  RET(c->dalloc((void**)&d.s_ord, ns * pool * 4));
-  RET(c->dalloc((void**)&d.status, 8));
-  HIPCHK(hipMemsetAsync(d.cand_count, 0, nseg * 4, c->stream));
-  HIPCHK(hipMemsetAsync(d.sel_ws, 0, nseg * SEL_WS * 4, c->stream));
-  HIPCHK(hipMemsetAsync(d.pool_count, 0, (size_t)ns * 4, c->stream));
-  HIPCHK(hipMemsetAsync(d.status, 0, 8, c->stream));
-  P->cs_slots_cap = ns; P->cs_cand_cap = nc;
+  RET(upload_codes(c, T.codes, src_row));
+  RET(grow_dev(c, &T.dsegs, &T.dsegs_cap, G * B * L, sizeof(DecodeSeg)));
+  HIPCHK(hipMemcpy(T.dsegs, ds.data(), ds.size() * sizeof(DecodeSeg), hipMemcpyHostToDevice));
+  T.col0 = col0; T.hot_blocks = hot_blocks; T.hot_width = hot_width; T.ld = ld;
+  T.n = n;
   return 0;
 }
 
@@ -734,17 +711,16 @@ int sylph_fcos_head(sylph_ctx* c, const float* cls_conv, const float* cls_bias, 
   o.src = HeadOut::cond;
   o.has_bias = c->cfg.cond_use_bias && cls_bias;
   RET(ensure_logits(c, P, N, true, &o));
-  const int Npad = cond_pad(N).Npad;
-  // the biases, zero-padded to the packed code rows (device copy: the caller's buffer need not outlive this call)
-  RET(ensure_bias_pad(c, P, Npad));
-  // one launch: packed codes + zero-padded biases + the -inf padded copy the fused scan reads
+  PackedCodes& pc = P->codes;
+  RET(ensure_codes(c, pc, cond_pad(N).Npad, 256 * c->esz(), false));
+  // one launch: packed codes + biases zero-padded to the packed code rows (device copy: the caller's buffer need not outlive this call) +
+  // the -inf padded copy the fused scan reads
   // (in FRONT of the towers: it depends on the caller's codes only, and at small batches the main stream waits for the bbox tower on the
   // side stream at the end of the head ops anyway -- behind them it was 5 us of the step's serial tail)
-  KCHK(launch_pack_codes(c->dt, cls_conv, N, 256, Npad, P->code_w, o.has_bias ? cls_bias : nullptr, P->bias_pad, P->bias_pad + P->bias_pad_cap, c->stream),
-       "pack_codes");
+  KCHK(launch_pack_codes(c->dt, cls_conv, N, 256, pc.rows, pc.w, o.has_bias ? cls_bias : nullptr, pc.bias, pc.bias + pc.cap, c->stream), "pack_codes");
   RET(run_ops(c, P->head_ops, "fcos_head"));
   bool scanned = false;
-  RET(run_cond(c, P, o, false, &scanned));
+  RET(run_cond(c, P, o, cond_launches(c, P, o, false), false, &scanned));
   o.logits_missing = scanned;
   o.cand = scanned ? HeadOut::cand_all : HeadOut::cand_none;
   P->out = o;
@@ -777,21 +753,22 @@ int sylph_fcos_head_episodes(sylph_ctx* c, int E, const float* cls_conv, const f
   RET(ensure_logits(c, P, maxN, true, &o));  // row pitch, candidate capacity and export width: those of the widest episode
   RET(ep_tables(c, P, E, n_classes, image_episode));
   // one launch packs every episode's codes and biases (in front of the towers, as in sylph_fcos_head)
-  KCHK(launch_pack_codes_episodes(c->dt, cls_conv, P->ep_src_row, P->ep_rows, 256, P->ep_code_w, o.has_bias ? cls_bias : nullptr, P->ep_bias,
-                                  P->ep_bias + P->ep_rows_cap, c->stream), "pack_codes_episodes");
+  const PackedCodes& pc = P->ep.codes;
+  KCHK(launch_pack_codes_episodes(c->dt, cls_conv, pc.src_row, pc.rows, 256, pc.w, o.has_bias ? cls_bias : nullptr, pc.bias, pc.bias + pc.cap, c->stream),
+       "pack_codes_episodes");
   RET(run_ops(c, P->head_ops, "fcos_head"));
   bool scanned = false;
   if (head_kind(c, P, maxN) == HeadKind::gn_logits) {
     // every episode takes gn_logits: ONE launch for the whole batch, whatever E is (head_fused.hip)
     const Plan* PP = P;
-    const float* bias = o.has_bias ? P->ep_bias : nullptr;
+    const float* bias = o.has_bias ? pc.bias : nullptr;
     const int ld = o.logits_ld;
     KCHK(timed_op(c, "gn_logits_episodes_kernel", 2.0 * (double)P->B * P->Ltot * maxN * 256.0, c->stream, [=](hipStream_t st) {
-           return launch_gn_logits_episodes(PP->cls_feat, 256, PP->cls_coef, PP->ep_code_w, bias, PP->ep_seg_row0, PP->logits, ld,
+           return launch_gn_logits_episodes(PP->cls_feat, 256, PP->cls_coef, PP->ep.codes.w, bias, PP->ep.seg_row0, PP->logits, ld,
                                             PP->head_segs, PP->head_tiles32, PP->head_mtiles32, st);
          }), "gn_logits_episodes");
   } else {
-    RET(run_cond(c, P, o, false, &scanned));
+    RET(run_cond(c, P, o, cond_launches(c, P, o, false), false, &scanned));
   }
   o.logits_missing = scanned;
   o.cand = scanned ? HeadOut::cand_scanned : HeadOut::cand_none;
@@ -833,7 +810,7 @@ int sylph_export_head(sylph_ctx* c, int level, float* logits, float* reg, float*
     OwnerScope own(c, P);
     HeadOut o = P->out;
     P->out = HeadOut();
-    RET(run_cond(c, P, o, true, nullptr));
+    RET(run_cond(c, P, o, cond_launches(c, P, o, true), false, nullptr));
     o.logits_missing = false;
     P->out = o;
   }
@@ -841,15 +818,15 @@ int sylph_export_head(sylph_ctx* c, int level, float* logits, float* reg, float*
   const int hw = P->hl[level] * P->wl[level];
   int sumN = 0;  // code sets: logits (B, sum N_g, h, w), set after set
   if (o.src == HeadOut::codesets)
-    for (int n : P->cs_n) sumN += n;
+    for (int n : P->cs.n) sumN += n;
   for (int b = 0; b < P->B; ++b) {
     const int row0 = b * P->Ltot + P->off[level];
     if (logits && o.src == HeadOut::codesets) {
       size_t ch = 0;
-      for (size_t g = 0; g < P->cs_n.size(); ++g) {
-        KCHK(launch_export_nchw_f32(P->logits, logits + ((size_t)b * sumN + ch) * hw, P->cs_n[g], hw, row0, o.logits_ld, P->cs_col0[g], c->stream),
+      for (size_t g = 0; g < P->cs.n.size(); ++g) {
+        KCHK(launch_export_nchw_f32(P->logits, logits + ((size_t)b * sumN + ch) * hw, P->cs.n[g], hw, row0, o.logits_ld, P->cs.col0[g], c->stream),
              "export logits");
-        ch += (size_t)P->cs_n[g];
+        ch += (size_t)P->cs.n[g];
       }
     } else if (logits)
       KCHK(launch_export_nchw_f32(P->logits, logits + (size_t)b * o.ncls * hw, o.ncls, hw, row0, o.logits_ld, 0, c->stream), "export logits");
@@ -869,17 +846,17 @@ int sylph_decode_nms(sylph_ctx* c, const int* oh, const int* ow, int max_out, fl
     return fail("the last head call was sylph_fcos_head_codesets (" + std::to_string(P->out.nsets) + " code sets): decode it with sylph_decode_nms_codesets");
   const HeadOut o = P->out;
   OwnerScope own(c, P);
-  RET(ensure_decode(c, P, o.ncls));
+  RET(ensure_decode_slots(c, P, P->dec, P->B, o.ncls));
   RET(upload_img_out(c, P, oh, ow));
-  const DecodeCfg d = decode_cfg(c, P, o, max_out);
+  const DecodeCfg d = decode_cfg(c, P, P->dec, o, max_out);
   const int L = c->cfg.nlevels;
   // the three states of HeadOut::cand: clear stale counters in front of a scan of every image, or keep the candidates that are there
-  if (o.cand == HeadOut::cand_none && P->cand_dirty) HIPCHK(hipMemsetAsync(P->dbuf.cand_count, 0, (size_t)P->B * L * 4, c->stream));
+  if (o.cand == HeadOut::cand_none && P->cand_dirty) HIPCHK(hipMemsetAsync(P->dec.buf.cand_count, 0, (size_t)P->B * L * 4, c->stream));
   P->cand_dirty = o.cand != HeadOut::cand_none;
   int nwb = (L * c->cfg.pre_nms_topk + 63) / 64;
   if (nwb > P->pool_cap / 64) nwb = P->pool_cap / 64;
-  KCHK(launch_decode(d, o.src == HeadOut::episodes ? P->dsegs_ep : P->dsegs, P->B * L, P->hl[0] * P->wl[0], P->B, nwb, P->logits, P->pred, 8,
-                     P->dbuf, P->img_out_dev, boxes, scores, classes, levels, locations, cand, counts, status, o.cand == HeadOut::cand_all, c->stream),
+  KCHK(launch_decode(d, o.src == HeadOut::episodes ? P->ep.dsegs : P->dsegs, P->B * L, P->hl[0] * P->wl[0], P->B, nwb, P->logits, P->pred, 8,
+                     P->dec.buf, P->img_out_dev, boxes, scores, classes, levels, locations, cand, counts, status, o.cand == HeadOut::cand_all, c->stream),
        "decode_nms");
   return 0;
 }
@@ -911,42 +888,34 @@ int sylph_fcos_head_codesets(sylph_ctx* c, int G, const float* cls_conv, const f
   o.nsets = G;
   o.ncls = maxN;  // candidate capacity per (slot, level): that of the widest set
   RET(cs_tables(c, P, G, n_classes));
-  o.logits_ld = P->cs_ld;
-  const size_t rows = (size_t)P->B * P->Ltot;
-  if (P->cs_ld > P->logits_cap_ld) {  // all sets' logits stay resident until the decode
-    if (P->logits) c->dfree(P->logits);
-    P->logits = nullptr; P->logits_cap_ld = 0;
-    RET(c->dalloc((void**)&P->logits, rows * P->cs_ld * sizeof(float)));
-    P->logits_cap_ld = P->cs_ld;
-  }
+  const Plan::CodeSets& T = P->cs;
+  const PackedCodes& pc = T.codes;
+  o.logits_ld = T.ld;
+  RET(grow_dev(c, &P->logits, &P->logits_cap_ld, T.ld, (size_t)P->B * P->Ltot * sizeof(float)));  // all sets' logits stay resident until the decode
   // one launch packs every set's codes and biases (in front of the towers, as in sylph_fcos_head)
-  KCHK(launch_pack_codes_episodes(c->dt, cls_conv, P->cs_src_row, P->cs_rows, 256, P->cs_code_w, o.has_bias ? cls_bias : nullptr, P->cs_bias,
-                                  P->cs_bias + P->cs_rows_cap, c->stream), "pack_codes (code sets)");
+  KCHK(launch_pack_codes_episodes(c->dt, cls_conv, pc.src_row, pc.rows, 256, pc.w, o.has_bias ? cls_bias : nullptr, pc.bias, pc.bias + pc.cap, c->stream),
+       "pack_codes (code sets)");
   RET(run_ops(c, P->head_ops, "fcos_head"));  // towers, box heads, cls GroupNorm statistics: once, whatever G is
   const Plan* PP = P;
-  const int ld = P->cs_ld;
+  const int ld = T.ld;
   // the sets of up to 32 classes: GN_SETS_MAX_BLOCKS blocks of 32 packed rows per pass over the un-normalised tower output
-  for (int b0 = 0; b0 < P->cs_hot_blocks; b0 += GN_SETS_MAX_BLOCKS) {
-    const int nb = P->cs_hot_blocks - b0 < GN_SETS_MAX_BLOCKS ? P->cs_hot_blocks - b0 : GN_SETS_MAX_BLOCKS;
-    const int width = P->cs_hot_width - 32 * b0 < 32 * nb ? P->cs_hot_width - 32 * b0 : 32 * nb;
+  for (int b0 = 0; b0 < T.hot_blocks; b0 += GN_SETS_MAX_BLOCKS) {
+    const int nb = T.hot_blocks - b0 < GN_SETS_MAX_BLOCKS ? T.hot_blocks - b0 : GN_SETS_MAX_BLOCKS;
+    const int width = T.hot_width - 32 * b0 < 32 * nb ? T.hot_width - 32 * b0 : 32 * nb;
     KCHK(timed_op(c, "gn_logits_sets_kernel", 2.0 * (double)P->head_mtiles32 * 128.0 * width * 256.0, c->stream, [=](hipStream_t st) {
-           return launch_gn_logits_sets(PP->cls_feat, 256, PP->cls_coef, (const char*)PP->cs_code_w + (size_t)32 * b0 * 256 * 2, PP->cs_bias + 32 * b0, nb,
+           return launch_gn_logits_sets(PP->cls_feat, 256, PP->cls_coef, (const char*)pc.w + (size_t)32 * b0 * 256 * 2, pc.bias + 32 * b0, nb,
                                         PP->logits + 32 * b0, ld, width, PP->head_segs, PP->head_tiles32, PP->head_mtiles32, st);
          }), "gn_logits_sets");
   }
-  // every other set: the conv_igemm launch sylph_fcos_head gives its N, on the tower output normalised in place ONCE, after the
-  // kernel above has read the un-normalised one
-  bool applied = false;
-  for (int g = 0; g < G; ++g) {
-    const int N = n_classes[g];
-    if (set_is_hot(c, P, N)) continue;
-    const HeadKind k = head_kind(c, P, N, false);
-    if (k == HeadKind::igemm_after_apply && !applied) { RET(apply_cls_gn(c, P)); applied = true; }
-    const size_t r0 = (size_t)P->cs_col0[g];
-    const CondEp v = {(const char*)P->cs_code_w + r0 * 256 * c->esz(), o.has_bias ? P->cs_bias + r0 : nullptr, nullptr, N,
-                      P->head_tiles32, P->head_mtiles32, P->head_tiles, P->head_mtiles, (double)rows, P->logits + r0};
-    RET(launch_cond(c, P, o, k, v, false));
-  }
+  // every other set, in order g: the conv_igemm launch sylph_fcos_head gives its N, on the tower output normalised in place ONCE, after
+  // the kernel above has read the un-normalised one (run_cond)
+  std::vector<CondLaunch> cold;
+  for (int g = 0; g < G; ++g)
+    if (!set_is_hot(c, P, n_classes[g])) {
+      const HeadKind k = head_kind(c, P, n_classes[g], false);
+      cold.push_back({k, cond_ep(c, P, o, g, k)});
+    }
+  RET(run_cond(c, P, o, cold, true, nullptr));
   o.cand = HeadOut::cand_none;
   P->out = o;
   return 0;
@@ -965,12 +934,11 @@ int sylph_decode_nms_codesets(sylph_ctx* c, int G, const int* oh, const int* ow,
     return fail("sylph_decode_nms_codesets: G = " + std::to_string(G) + ", but the last sylph_fcos_head_codesets call ran " + std::to_string(o.nsets) +
                 " code sets");
   OwnerScope own(c, P);
-  RET(ensure_decode_sets(c, P, G, o.ncls));
-  RET(upload_img_out(c, P, oh, ow));
-  DecodeCfg d = decode_cfg(c, P, o, max_out);
-  d.cand_cap = P->cs_cand_cap;
   const int L = c->cfg.nlevels, slots = G * P->B;
-  KCHK(launch_decode(d, P->dsegs_cs, slots * L, P->hl[0] * P->wl[0], slots, 0, P->logits, P->pred, 8, P->dbuf_cs, P->img_out_dev, boxes, scores,
+  RET(ensure_decode_slots(c, P, P->dec_cs, slots, o.ncls));
+  RET(upload_img_out(c, P, oh, ow));
+  const DecodeCfg d = decode_cfg(c, P, P->dec_cs, o, max_out);
+  KCHK(launch_decode(d, P->cs.dsegs, slots * L, P->hl[0] * P->wl[0], slots, 0, P->logits, P->pred, 8, P->dec_cs.buf, P->img_out_dev, boxes, scores,
                      classes, levels, locations, cand, counts, status, false, c->stream),
        "decode_nms_codesets");
   return 0;

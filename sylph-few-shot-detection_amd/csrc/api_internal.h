@@ -261,7 +261,7 @@ struct HeadOut {
   //   cand_none     nobody's: the decode scans every image, after clearing the counters if Plan::cand_dirty says that an earlier fused
   //                 scan's candidates are still counted (a decode that ran its own scan leaves them zero: nms_kernel)
   //   cand_all      every image's (many-way sylph_fcos_head; the scan launch clears the counters itself): the decode skips its scan
-  //   cand_scanned  those of the images whose episode takes the fused scan (mixed head; DecodeSeg::ncls < 0 in Plan::dsegs_ep):
+  //   cand_scanned  those of the images whose episode takes the fused scan (mixed head; DecodeSeg::ncls < 0 in Plan::ep.dsegs):
   //                 decode_scan_kernel skips these images
   // In the last two nms_kernel keeps the counters, so a repeated decode finds the candidates again and the counters stay dirty.  A steady
   // stream of steps of one kind never clears in the decode (no extra launch).
@@ -269,7 +269,25 @@ struct HeadOut {
   bool has_bias = false;        // the class-conditional conv adds biases
   bool logits_missing = false;  // the logits columns of the scanned images were never written: sylph_export_head runs the unfused conv first
   int ncls = 0, logits_ld = 0;  // classes (of the widest episode / code set) and row pitch of Plan::logits
-  int nsets = 0;                // codesets: G, the sets whose logits columns Plan::logits holds side by side (Plan::cs_col0)
+  int nsets = 0;                // codesets: G, the sets whose logits columns Plan::logits holds side by side (Plan::cs.col0)
+};
+
+// The packed class codes of one head call and their biases, in device buffers that grow with the request (api_head.hip: ensure_codes,
+// upload_codes).  The uniform head, the episodes of a mixed head and the sets of a code-sets head each own one and read it the same way
+// (cond_ep): codes and biases of a launch start at its first packed row.
+struct PackedCodes {
+  void* w = nullptr;       // [rows][row bytes]: [256] in the compute dtype; the 3x3 codes [3][3][256] (pack_conv's layout)
+  float* bias = nullptr;   // [2][cap]: zero-padded biases | at bias + cap the same with -inf in the padding rows (logits_scan_kernel)
+  int* src_row = nullptr;  // [rows]: row of the caller's (sum N, 256) table, -1 for a padding row (launch_pack_codes_episodes);
+                           // nullptr: one N-way table, padded by launch_pack_codes / launch_pack_codes3x3
+  int rows = 0, cap = 0;   // packed rows of the last call; capacity of the three buffers
+};
+
+// The decode buffers of `slots_cap` output slots with candidate buffers of `cand_cap` entries per (slot, level) (api_head.hip:
+// ensure_decode_slots)
+struct DecodeSlots {
+  DecodeBuffers buf{};
+  int slots_cap = 0, cand_cap = 0;
 };
 
 struct Plan {
@@ -323,15 +341,14 @@ struct Plan {
   float* logits = nullptr;  // [rows][out.logits_ld], capacity [rows][logits_cap_ld]
   int logits_cap_ld = 0;
   HeadOut out;              // what the last head entry left in logits / pred / the decode buffers
-  void* code_w = nullptr;   // packed class codes [Npad][256]
-  void* code_wf = nullptr;  // the same in MFMA fragment order (logits_scan_kernel), same capacity
-  int code_w_cap = 0;
-  // 3x3 class codes (cg_code_ksize 3): packed [Npad][3][3][256] (pack_conv's layout) and, per (N, bias or not), the conv launch add_conv
+  PackedCodes codes;        // the last sylph_fcos_head's 1x1 codes [Npad][256] and biases (Npad: cond_pad)
+  void* code_wf = nullptr;  // workspace of logits_scan_kernel: the codes of one scan in MFMA fragment order; grows with the logits' class count
+  int code_wf_cap = 0;
+  // 3x3 class codes (cg_code_ksize 3): packed [Npad][3][3][256] with their biases and, per (N, bias or not), the conv launch add_conv
   // built on them -- valid while the buffers it captured are the plan's (cond3_for)
-  void* code_w3 = nullptr;
-  int code_w3_cap = 0;
+  PackedCodes codes3;
   std::map<std::pair<int, int>, std::vector<OpFn>> cond3_ops;
-  const void* cond3_for[3] = {nullptr, nullptr, nullptr};  // code_w3, logits, bias_pad the ops read
+  const void* cond3_for[3] = {nullptr, nullptr, nullptr};  // codes3.w, logits, codes3.bias the ops read
   const SegDesc* head_segs = nullptr;
   const int2 *head_tiles = nullptr, *head_tiles32 = nullptr;
   int head_mtiles = 0, head_BM = 128, head_mtiles32 = 0;
@@ -340,47 +357,40 @@ struct Plan {
   float2* gn_stats = nullptr;
   // decode
   DecodeSeg* dsegs = nullptr;
-  DecodeBuffers dbuf;
-  bool cand_dirty = false;  // the candidate counters of dbuf are not zero: a fused scan filled them (a fact about the buffers: it survives heads)
+  // B slots (sylph_decode_nms) and G * B slots (sylph_decode_nms_codesets): two instances, so neither kind of step reallocates when the
+  // two alternate
+  DecodeSlots dec, dec_cs;
+  bool cand_dirty = false;  // the candidate counters of dec are not zero: a fused scan filled them (a fact about the buffers: it survives heads)
   bool decode_built = false;
   std::vector<OpFn> cls_logits_ops;  // the checkpoint's cls_logits conv on this plan's cls tower output (sylph_fcos_head_pretrained)
   const float* cls_logits_dst = nullptr;  // the logits buffer those ops were built for
-  int cand_cap = 0, pool_cap = 0;
+  int pool_cap = 0;
   bool stem_takes_raw = false;  // this plan's first backbone op is the fused stem + pool kernel (bf16): it can read raw images
   bool raw_input = false;     // the batch came in through sylph_preprocess and its normalisation is fused into the stem kernel
                               // (launch_stem_pool_raw reads the caller's images through img_desc_dev): x0 has NOT been written
-  // Mixed-episode head (sylph_fcos_head_episodes): image i was run with the codes of episode ep_image[i].  The tables below are read only
+  // Mixed-episode head (sylph_fcos_head_episodes): image i was run with the codes of episode ep.image[i].  The tables are read only
   // while out.src says that the plan's head outputs are such a head's.
-  std::vector<int> ep_n, ep_image;    // classes per episode, episode per image: what the device tables below were built for
-  std::vector<int> ep_row0;           // per episode: its first row in the packed code / bias tables (rows padded per episode as in sylph_fcos_head)
-  std::vector<int2> ep_tiles32, ep_tilesBM;  // per episode: {first, count} of its tiles in ep_tiles_dev (128-row tiles | head_BM-row tiles)
-  int ep_rows = 0, ep_rows_cap = 0;   // packed rows of all episodes; capacity of ep_code_w / ep_bias / ep_src_row
-  void* ep_code_w = nullptr;          // [ep_rows][256] compute dtype
-  float* ep_bias = nullptr;           // [2][ep_rows_cap]: zero-padded biases | the same with -inf in the padding rows (logits_scan_kernel)
-  int* ep_src_row = nullptr;          // [ep_rows]: row of the caller's (sum N, 256) table, -1 for a padding row
-  int* ep_seg_row0 = nullptr;         // [B * levels]: first packed row of the segment's episode
-  int2* ep_tiles_dev = nullptr;       // the tiles of the head's two tile tables regrouped episode by episode
-  DecodeSeg* dsegs_ep = nullptr;      // the decode's segment table with DecodeSeg::ncls set per image
+  struct Episodes {
+    PackedCodes codes;                   // every episode's rows, padded per episode as in sylph_fcos_head
+    std::vector<int> n, image;           // classes per episode, episode per image: what the device tables below were built for
+    std::vector<int> row0;               // per episode: its first row in `codes`
+    std::vector<int2> tiles32, tilesBM;  // per episode: {first, count} of its tiles in tiles_dev (128-row tiles | head_BM-row tiles)
+    int* seg_row0 = nullptr;             // [B * levels]: first packed row of the segment's episode
+    int2* tiles_dev = nullptr;           // the tiles of the head's two tile tables regrouped episode by episode
+    DecodeSeg* dsegs = nullptr;          // the decode's segment table with DecodeSeg::ncls set per image
+  } ep;
   // Code-sets head (sylph_fcos_head_codesets): every image is scored against G code sets; the logits of set g are columns
-  // [cs_col0[g], cs_col0[g] + cs_n[g]) of Plan::logits, and packed code row r produces column r.  The sets that take the fused
+  // [cs.col0[g], cs.col0[g] + cs.n[g]) of Plan::logits, and packed code row r produces column r.  The sets that take the fused
   // GroupNorm + conv kernel (bf16, cls GroupNorm deferred, N <= 32: gn_logits_sets_kernel) come first, each at a multiple of 4 (the
-  // decode scan reads 16 bytes at a time), in cs_hot_blocks blocks of 32 rows; every other set follows at a multiple of 32 with the
+  // decode scan reads 16 bytes at a time), in cs.hot_blocks blocks of 32 rows; every other set follows at a multiple of 32 with the
   // padded width conv_igemm gives it in sylph_fcos_head.  Read only while out.src says that the head outputs are such a head's.
-  std::vector<int> cs_n, cs_col0;
-  int cs_hot_blocks = 0, cs_hot_width = 0, cs_ld = 0;
-  int cs_rows = 0, cs_rows_cap = 0;   // packed rows of all sets; capacity of cs_code_w / cs_bias / cs_src_row
-  void* cs_code_w = nullptr;          // [cs_rows][256] compute dtype
-  float* cs_bias = nullptr;           // [2][cs_rows_cap]: zero-padded biases | the copy launch_pack_codes_episodes leaves for a scan (unread)
-  int* cs_src_row = nullptr;          // [cs_rows]: row of the caller's (sum N, 256) table, -1 for a padding row
-  DecodeSeg* dsegs_cs = nullptr;      // [G][B][levels]: DecodeSeg::ncls, cls0 and slot per set
-  int dsegs_cs_cap = 0;
-  // decode buffers of the code-sets decode: G * B slots, candidate buffers of cs_cand_cap per (slot, level); the plan's own (dbuf) stay
-  // those of the B-slot decodes, so neither kind of step reallocates when the two alternate
-  DecodeBuffers dbuf_cs{};
-  int cs_slots_cap = 0, cs_cand_cap = 0;
-  float* bias_pad = nullptr;  // fp32 class biases of the last sylph_fcos_head: [0, cap) zero-padded to the packed code rows; [cap, 2 cap) the
-                              // same with -inf from class N on (logits_scan_kernel: padded classes never pass the threshold)
-  int bias_pad_cap = 0;
+  struct CodeSets {
+    PackedCodes codes;  // every set's rows (the copy of the biases for a scan is written and never read)
+    std::vector<int> n, col0;
+    int hot_blocks = 0, hot_width = 0, ld = 0;
+    DecodeSeg* dsegs = nullptr;  // [G][B][levels]: DecodeSeg::ncls, cls0 and slot per set
+    int dsegs_cap = 0;
+  } cs;
   ImageOut* img_out_dev = nullptr;
   ImageOut* img_out_host = nullptr;
   std::vector<ImageOut> img_out_last;  // what img_out_dev holds (the H2D copy is skipped when a call's scales equal it)

@@ -21,7 +21,7 @@
 //   sylph/modeling/meta_fcos/fcos_outputs.py:1010-1028 select_over_all_levels (ml_nms, kthvalue keep)
 //   sylph/modeling/meta_arch/meta_one_stage_detector.py:288-296 detector_postprocess
 //   sylph/modeling/meta_fcos/fcos.py:270-282 compute_locations
-#include "gfx950.h"
+#include "gn_stream.h"
 #include "kernels.h"
 
 namespace sylph {
@@ -495,25 +495,14 @@ __global__ __launch_bounds__(256, 2) void logits_scan_kernel(const bf16_t* __res
   for (int q = 0; q < 4; ++q) bnext[q] = *reinterpret_cast<const float4*>(bias_scan + 8 * q + 4 * lh);
   const int n_groups = n_tiles * 4, stride = gridDim.x * 4;
   for (int g = blockIdx.x * 4 + wave; g < n_groups; g += stride) {
-    const int2 tl = tiles[g >> 2];
-    const int seg = tl.x, r0 = tl.y + (g & 3) * 32;
-    const SegDesc& sd = segs[seg];
-    const int nrows = sd.out_H * sd.out_W;
-    if (r0 >= nrows) continue;  // wave-uniform
-    if (seg != cur_seg) {
+    const RowGroup rg = row_group(segs, tiles, g);
+    if (rg.empty()) continue;
+    if (rg.seg != cur_seg) {
       flush();
-      cur_seg = seg;
-      const float2* cp = coef + (size_t)seg * 256;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int pr = lane + 64 * i;  // channel pair
-        const float2 c0 = cp[2 * pr], c1 = cp[2 * pr + 1];
-        *reinterpret_cast<float4*>(&cf[wave][4 * pr]) = make_float4(c0.x, c1.x, c0.y, c1.y);
-      }
+      cur_seg = rg.seg;
+      gn_load_coef(cf[wave], coef, rg.seg, lane);
     }
-    const int row = r0 + l31;
-    const bool valid = row < nrows;
-    const size_t grow = (size_t)(sd.out_row0 + (valid ? row : nrows - 1));
+    const size_t grow = rg.grow(l31);
     const bf16_t* xp = x + grow * ld + lh * 8;
     u32x4 yv[16];  // relu(GN(x)) of (row l31, channels 16 ks + 8 lh ..) as bf16: the B operand of every class tile
 #pragma unroll
@@ -521,23 +510,9 @@ __global__ __launch_bounds__(256, 2) void logits_scan_kernel(const bf16_t* __res
     // quality (centerness / IoU) of the lane's row, computed once per row group; rows past the segment never hit
     const float q_row = quality_from(cfg.quality_mode != 1 ? pred[grow * pred_ld + 4] : 0.f,
                                      cfg.quality_mode != 0 ? pred[grow * pred_ld + 5] : 0.f, cfg.quality_mode);
-    const float x_min_row = valid ? x_min : INFINITY;
+    const float x_min_row = rg.valid(l31) ? x_min : INFINITY;
 #pragma unroll
-    for (int ks = 0; ks < 16; ++ks) {
-      const float* cq = &cf[wave][(ks * 16 + lh * 8) * 2];  // 4 channel pairs x (a0, a1, b0, b1)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float4 c4 = *reinterpret_cast<const float4*>(cq + 4 * e);
-        const f32x2 xf = {__uint_as_float(yv[ks][e] << 16), __uint_as_float(yv[ks][e] & 0xffff0000u)};
-        const f32x2 av = {c4.x, c4.y}, bv = {c4.z, c4.w};
-        const f32x2 r = __builtin_elementwise_fma(xf, av, bv);
-        bf16x2 pk;
-        pk[0] = (bf16_t)r[0];
-        pk[1] = (bf16_t)r[1];
-        const s16x2 z = {0, 0};
-        yv[ks][e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pk), z));  // ReLU on the bf16 pair
-      }
-    }
+    for (int ks = 0; ks < 16; ++ks) yv[ks] = gn_relu_x8(yv[ks], cf[wave], ks, lh);  // in place: the raw rows are not needed again
     for (int ct = 0; ct < n_ct; ++ct) {
       f32x16 acc;
 #pragma unroll
@@ -593,7 +568,7 @@ __global__ __launch_bounds__(256, 2) void logits_scan_kernel(const bf16_t* __res
         if (pass) {
           const unsigned pos = cn + (unsigned)__popcll(m & below);
           c_key[wave][pos] = __float_as_uint(sc);
-          c_idx[wave][pos] = (unsigned)((r0 + rl) * N + cls);
+          c_idx[wave][pos] = (unsigned)((rg.r0 + rl) * N + cls);
         }
         cn += cnt;
       }
@@ -610,8 +585,7 @@ int launch_logits_scan(const void* x, int ld, const float2* coef, const void* w,
   const int n_frag = ((cfg.num_classes + 31) / 32) * 16;
   hipLaunchKernelGGL(pack_code_fragments_kernel, dim3((n_frag * 64 + 255) / 256), dim3(256), 0, s, (const bf16_t*)w, (bf16_t*)wf_ws,
                      n_frag);
-  const int grid = n_tiles < HEAD_STREAM_MAX_BLOCKS ? n_tiles : HEAD_STREAM_MAX_BLOCKS;
-  hipLaunchKernelGGL(logits_scan_kernel, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)wf_ws, bias_scan,
+  hipLaunchKernelGGL(logits_scan_kernel, dim3(head_stream_grid(n_tiles)), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)wf_ws, bias_scan,
                      segs, tiles, n_tiles, pred, pred_ld, cfg, buf);
   return (int)hipGetLastError();
 }

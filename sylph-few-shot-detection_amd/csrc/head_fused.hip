@@ -8,14 +8,16 @@
 // every wave streams 32-row groups straight from HBM into MFMA A-fragment registers (lane = (row, k half): 16 bytes per
 // k-step, a row's 512 bytes over 16 k-steps), applies the same fused multiply-add + ReLU + bf16 rounding as the apply kernel
 // (bit-identical operand values), and multiplies by the 32 x 256 code matrix held in registers.  No LDS for data, no barriers:
-// the pass is HBM-bound (one read of the tower output, one write of the fp32 logits).
+// the pass is HBM-bound (one read of the tower output, one write of the fp32 logits).  The row-group walk, the coefficient table and the
+// normalisation are gn_stream.h's, shared with every kernel below that says its operand values are this kernel's, and with
+// logits_scan_kernel (detect.hip).
 //
 // EPISODES (sylph_fcos_head_episodes; the loop the batch stands for: meta_learn_evaluation.py:421-426): the images of the batch belong
 // to different episodes.  w / bias hold every episode's block of 32 rows (zero rows and zero biases above its N), seg_row0[segment] is
 // the first row of the block of the segment's image: tile -> segment -> image -> episode -> code rows.  A wave reloads its B fragments
 // and biases only when the block of its next tile differs from the one it holds; everything else -- operand values, K order, rounding
 // points -- is the uniform kernel's, so an image's logits do not depend on which episodes its neighbours belong to.
-#include "gfx950.h"
+#include "gn_stream.h"
 #include "kernels.h"
 
 namespace sylph {
@@ -51,28 +53,18 @@ __global__ __launch_bounds__(256) void gn_logits_kernel(const bf16_t* __restrict
   const int n_groups = EPISODES ? min(n_tiles, ((int)blockIdx.x + 1) * chunk) * 4 : n_tiles * 4;
   const int stride = EPISODES ? 4 : gridDim.x * 4;
   for (int g = blockIdx.x * chunk * 4 + wave; g < n_groups; g += stride) {
-    const int2 tl = tiles[g >> 2];
-    const int seg = tl.x, r0 = tl.y + (g & 3) * 32;
-    const SegDesc& sd = segs[seg];
-    const int nrows = sd.out_H * sd.out_W;
-    if (r0 >= nrows) continue;  // wave-uniform
-    if (seg != cur_seg) {       // wave-private coefficient table (same-wave LDS traffic is ordered: no barrier)
-      cur_seg = seg;
+    const RowGroup rg = row_group(segs, tiles, g);
+    if (rg.empty()) continue;
+    if (rg.seg != cur_seg) {          // wave-private coefficient table
+      cur_seg = rg.seg;
       if constexpr (EPISODES) {
-        const int row0 = seg_row0[seg];  // wave-uniform
+        const int row0 = seg_row0[rg.seg];  // wave-uniform
         if (row0 != cur_row0) { cur_row0 = row0; load_codes(row0); }
       }
-      const float2* cp = coef + (size_t)seg * 256;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int pr = lane + 64 * i;  // channel pair
-        const float2 c0 = cp[2 * pr], c1 = cp[2 * pr + 1];
-        *reinterpret_cast<float4*>(&cf[wave][4 * pr]) = make_float4(c0.x, c1.x, c0.y, c1.y);
-      }
+      gn_load_coef(cf[wave], coef, rg.seg, lane);
     }
-    const int row = r0 + l31;
-    const bool valid = row < nrows;
-    const size_t grow = (size_t)(sd.out_row0 + (valid ? row : nrows - 1));
+    const bool valid = rg.valid(l31);
+    const size_t grow = rg.grow(l31);
     const bf16_t* xp = x + grow * ld + lh * 8;
     u32x4 xv[16];
 #pragma unroll
@@ -81,23 +73,8 @@ __global__ __launch_bounds__(256) void gn_logits_kernel(const bf16_t* __restrict
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-    for (int ks = 0; ks < 16; ++ks) {
-      const float* cq = &cf[wave][(ks * 16 + lh * 8) * 2];  // 4 channel pairs x (a0, a1, b0, b1)
-      u32x4 yv;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float4 c4 = *reinterpret_cast<const float4*>(cq + 4 * e);
-        const f32x2 xf = {__uint_as_float(xv[ks][e] << 16), __uint_as_float(xv[ks][e] & 0xffff0000u)};
-        const f32x2 av = {c4.x, c4.y}, bv = {c4.z, c4.w};
-        const f32x2 r = __builtin_elementwise_fma(xf, av, bv);
-        bf16x2 pk;
-        pk[0] = (bf16_t)r[0];
-        pk[1] = (bf16_t)r[1];
-        const s16x2 z = {0, 0};
-        yv[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pk), z));  // ReLU on the bf16 pair
-      }
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[ks], __builtin_bit_cast(bf16x8, yv), acc, 0, 0, 0);
-    }
+    for (int ks = 0; ks < 16; ++ks)
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[ks], __builtin_bit_cast(bf16x8, gn_relu_x8(xv[ks], cf[wave], ks, lh)), acc, 0, 0, 0);
     if (valid) {
       float* op = out + grow * out_ld + 4 * lh;
 #pragma unroll
@@ -137,24 +114,14 @@ __global__ __launch_bounds__(256) void gn_logits_sets_kernel(const bf16_t* __res
   int cur_seg = -1;
   const int n_groups = n_tiles * 4, stride = gridDim.x * 4;
   for (int g = blockIdx.x * 4 + wave; g < n_groups; g += stride) {
-    const int2 tl = tiles[g >> 2];
-    const int seg = tl.x, r0 = tl.y + (g & 3) * 32;
-    const SegDesc& sd = segs[seg];
-    const int nrows = sd.out_H * sd.out_W;
-    if (r0 >= nrows) continue;  // wave-uniform
-    if (seg != cur_seg) {       // wave-private coefficient table, carried from one row group to the next
-      cur_seg = seg;
-      const float2* cp = coef + (size_t)seg * 256;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int pr = lane + 64 * i;  // channel pair
-        const float2 c0 = cp[2 * pr], c1 = cp[2 * pr + 1];
-        *reinterpret_cast<float4*>(&cf[wave][4 * pr]) = make_float4(c0.x, c1.x, c0.y, c1.y);
-      }
+    const RowGroup rg = row_group(segs, tiles, g);
+    if (rg.empty()) continue;
+    if (rg.seg != cur_seg) {          // wave-private coefficient table, carried from one row group to the next
+      cur_seg = rg.seg;
+      gn_load_coef(cf[wave], coef, rg.seg, lane);
     }
-    const int row = r0 + l31;
-    const bool valid = row < nrows;
-    const size_t grow = (size_t)(sd.out_row0 + (valid ? row : nrows - 1));
+    const bool valid = rg.valid(l31);
+    const size_t grow = rg.grow(l31);
     const bf16_t* xp = x + grow * ld + lh * 8;
     u32x4 xv[16];
 #pragma unroll
@@ -166,22 +133,9 @@ __global__ __launch_bounds__(256) void gn_logits_sets_kernel(const bf16_t* __res
       for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) {
-      const float* cq = &cf[wave][(ks * 16 + lh * 8) * 2];  // 4 channel pairs x (a0, a1, b0, b1)
-      u32x4 yv;
+      const bf16x8 yv = __builtin_bit_cast(bf16x8, gn_relu_x8(xv[ks], cf[wave], ks, lh));
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float4 c4 = *reinterpret_cast<const float4*>(cq + 4 * e);
-        const f32x2 xf = {__uint_as_float(xv[ks][e] << 16), __uint_as_float(xv[ks][e] & 0xffff0000u)};
-        const f32x2 av = {c4.x, c4.y}, bv = {c4.z, c4.w};
-        const f32x2 r = __builtin_elementwise_fma(xf, av, bv);
-        bf16x2 pk;
-        pk[0] = (bf16_t)r[0];
-        pk[1] = (bf16_t)r[1];
-        const s16x2 z = {0, 0};
-        yv[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pk), z));  // ReLU on the bf16 pair
-      }
-#pragma unroll
-      for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[b][ks], __builtin_bit_cast(bf16x8, yv), acc[b], 0, 0, 0);
+      for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[b][ks], yv, acc[b], 0, 0, 0);
     }
     if (valid) {
       float* op = out + grow * out_ld + 4 * lh;
@@ -225,25 +179,13 @@ __global__ __launch_bounds__(256) void gn_taps_kernel(const bf16_t* __restrict__
   int cur_seg = -1;
   const int n_groups = n_tiles * 4, stride = gridDim.x * 4;
   for (int g = blockIdx.x * 4 + wave; g < n_groups; g += stride) {
-    const int2 tl = tiles[g >> 2];
-    const int seg = tl.x, r0 = tl.y + (g & 3) * 32;
-    const SegDesc& sd = segs[seg];
-    const int nrows = sd.out_H * sd.out_W;
-    if (r0 >= nrows) continue;
-    if (seg != cur_seg) {
-      cur_seg = seg;
-      const float2* cp = coef + (size_t)seg * 256;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int pr = lane + 64 * i;
-        const float2 c0 = cp[2 * pr], c1 = cp[2 * pr + 1];
-        *reinterpret_cast<float4*>(&cf[wave][4 * pr]) = make_float4(c0.x, c1.x, c0.y, c1.y);
-      }
+    const RowGroup rg = row_group(segs, tiles, g);
+    if (rg.empty()) continue;
+    if (rg.seg != cur_seg) {
+      cur_seg = rg.seg;
+      gn_load_coef(cf[wave], coef, rg.seg, lane);
     }
-    const int row = r0 + l31;
-    const bool valid = row < nrows;
-    const size_t grow = (size_t)(sd.out_row0 + (valid ? row : nrows - 1));
-    const bf16_t* xp = x + grow * ld + lh * 8;
+    const bf16_t* xp = x + rg.grow(l31) * ld + lh * 8;
     u32x4 xv[16];
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) xv[ks] = *reinterpret_cast<const u32x4*>(xp + ks * 16);
@@ -254,22 +196,9 @@ __global__ __launch_bounds__(256) void gn_taps_kernel(const bf16_t* __restrict__
       for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) {
-      const float* cq = &cf[wave][(ks * 16 + lh * 8) * 2];
-      u32x4 yv;
+      const bf16x8 yv = __builtin_bit_cast(bf16x8, gn_relu_x8(xv[ks], cf[wave], ks, lh));
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float4 c4 = *reinterpret_cast<const float4*>(cq + 4 * e);
-        const f32x2 xf = {__uint_as_float(xv[ks][e] << 16), __uint_as_float(xv[ks][e] & 0xffff0000u)};
-        const f32x2 av = {c4.x, c4.y}, bv = {c4.z, c4.w};
-        const f32x2 r = __builtin_elementwise_fma(xf, av, bv);
-        bf16x2 pk;
-        pk[0] = (bf16_t)r[0];
-        pk[1] = (bf16_t)r[1];
-        const s16x2 z = {0, 0};
-        yv[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pk), z));
-      }
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[t][ks], __builtin_bit_cast(bf16x8, yv), acc[t], 0, 0, 0);
+      for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[t][ks], yv, acc[t], 0, 0, 0);
     }
     // column j = kh * sw + kw * cp + n (sw = slice width, a multiple of 4): columns [kh sw, (kh + 1) sw) of a row are its record in
     // plane kh, so that pass 2 reads near-contiguous sw-float records per kernel row.  The 32 rows of the group are contiguous in
@@ -282,8 +211,8 @@ __global__ __launch_bounds__(256) void gn_taps_kernel(const bf16_t* __restrict__
       for (int q = 0; q < 4; ++q)
         *reinterpret_cast<float4*>(st + l31 * TR_PITCH + t * 32 + 8 * q + 4 * lh) =
             make_float4(acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]);
-    const int vrows = min(32, nrows - r0), q4 = sw >> 2;
-    const size_t grow0 = (size_t)sd.out_row0 + r0;
+    const int vrows = min(32, rg.nrows - rg.r0), q4 = sw >> 2;
+    const size_t grow0 = (size_t)rg.sd->out_row0 + rg.r0;
     for (int kh = 0; kh < 3; ++kh) {
       float* dst = out + ((size_t)kh * plane_rows + grow0) * sw;
       for (int i = lane; i < vrows * q4; i += 64) {
@@ -371,8 +300,7 @@ int launch_gn_pred_taps(const void* x, int ld, const float2* coef, const void* w
                         hipStream_t s) {
   const int sw = (3 * cp + 3) & ~3;
   if (cp < 1 || 3 * sw > 64 || n_tiles <= 0) return -1;
-  const int grid = n_tiles < HEAD_STREAM_MAX_BLOCKS ? n_tiles : HEAD_STREAM_MAX_BLOCKS;
-  hipLaunchKernelGGL(gn_taps_kernel<2>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w_taps, planes_ws, sw, plane_rows,
+  hipLaunchKernelGGL(gn_taps_kernel<2>, dim3(head_stream_grid(n_tiles)), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w_taps, planes_ws, sw, plane_rows,
                      segs, tiles, n_tiles);
   hipLaunchKernelGGL(tap_gather_kernel, dim3(n_tiles), dim3(128), 0, s, planes_ws, sw, plane_rows, cp, bias, relu_nch, mul_nch, out, out_ld, segs,
                      tiles);
@@ -464,15 +392,7 @@ __global__ __launch_bounds__(192) void gn_cond3x3_kernel(const bf16_t* __restric
     for (int it = 0; it < 17; ++it) {
       u32x4 yv;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const f32x2 xf = {__uint_as_float(xv[it][e] << 16), __uint_as_float(xv[it][e] & 0xffff0000u)};
-        const f32x2 r = __builtin_elementwise_fma(xf, ca[e], cb[e]);
-        bf16x2 pk;
-        pk[0] = (bf16_t)r[0];
-        pk[1] = (bf16_t)r[1];
-        const s16x2 z = {0, 0};
-        yv[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pk), z));  // ReLU on the bf16 pair
-      }
+      for (int e = 0; e < 4; ++e) yv[e] = gn_relu_pair(xv[it][e], ca[e], cb[e]);
       *reinterpret_cast<u32x4*>(&strip[ky][(2 * it + lh) * C3_PITCH + l31 * 16]) = yv;
     }
     const int gn = next_group(g);
@@ -527,8 +447,7 @@ __global__ __launch_bounds__(192) void gn_cond3x3_kernel(const bf16_t* __restric
 int launch_gn_cond3x3(const void* x, int ld, const float2* coef, const void* w, const float* bias, int N, float* out, int out_ld,
                       const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s) {
   if (N > 32 || out_ld < N || (out_ld & 3) != 0 || n_tiles <= 0) return -1;
-  const int grid = n_tiles < HEAD_STREAM_MAX_BLOCKS ? n_tiles : HEAD_STREAM_MAX_BLOCKS;  // one block = one 128-row tile per sweep
-  hipLaunchKernelGGL(gn_cond3x3_kernel, dim3(grid), dim3(192), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, N, out, out_ld, segs,
+  hipLaunchKernelGGL(gn_cond3x3_kernel, dim3(head_stream_grid(n_tiles)), dim3(192), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, N, out, out_ld, segs,
                      tiles, n_tiles);
   return (int)hipGetLastError();
 }
@@ -538,9 +457,7 @@ int launch_gn_cond3x3(const void* x, int ld, const float2* coef, const void* w, 
 int launch_gn_logits(const void* x, int ld, const float2* coef, const void* w, const float* bias, int N, float* out, int out_ld,
                      const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s) {
   if (N > 32 || out_ld < N || (out_ld & 3) != 0 || n_tiles <= 0) return -1;
-  const int want = n_tiles;  // one block = 4 row groups = one 128-row tile per sweep
-  const int grid = want < HEAD_STREAM_MAX_BLOCKS ? want : HEAD_STREAM_MAX_BLOCKS;
-  hipLaunchKernelGGL(gn_logits_kernel<false>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, N, nullptr, out,
+  hipLaunchKernelGGL(gn_logits_kernel<false>, dim3(head_stream_grid(n_tiles)), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, N, nullptr, out,
                      out_ld, segs, tiles, n_tiles);
   return (int)hipGetLastError();
 }
@@ -552,7 +469,7 @@ int launch_gn_logits_sets(const void* x, int ld, const float2* coef, const void*
   if (nblocks < 1 || nblocks > GN_SETS_MAX_BLOCKS || !bias || width <= 32 * (nblocks - 1) || width > 32 * nblocks || (width & 3) != 0 ||
       out_ld < width || (out_ld & 3) != 0 || n_tiles <= 0)
     return -1;
-  const int grid = n_tiles < HEAD_STREAM_MAX_BLOCKS ? n_tiles : HEAD_STREAM_MAX_BLOCKS;  // one block = one 128-row tile per sweep
+  const int grid = head_stream_grid(n_tiles);
 #define SYLPH_SETS_LAUNCH(NB)                                                                                                            \
   hipLaunchKernelGGL(gn_logits_sets_kernel<NB>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, out, \
                      out_ld, width, segs, tiles, n_tiles)
@@ -570,8 +487,7 @@ int launch_gn_logits_sets(const void* x, int ld, const float2* coef, const void*
 int launch_gn_logits_episodes(const void* x, int ld, const float2* coef, const void* w, const float* bias, const int* seg_row0, float* out,
                               int out_ld, const SegDesc* segs, const int2* tiles, int n_tiles, hipStream_t s) {
   if (!seg_row0 || (out_ld & 3) != 0 || out_ld <= 0 || n_tiles <= 0) return -1;
-  const int grid = n_tiles < HEAD_STREAM_MAX_BLOCKS ? n_tiles : HEAD_STREAM_MAX_BLOCKS;
-  hipLaunchKernelGGL(gn_logits_kernel<true>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, 32, seg_row0, out,
+  hipLaunchKernelGGL(gn_logits_kernel<true>, dim3(head_stream_grid(n_tiles)), dim3(256), 0, s, (const bf16_t*)x, ld, coef, (const bf16_t*)w, bias, 32, seg_row0, out,
                      out_ld, segs, tiles, n_tiles);
   return (int)hipGetLastError();
 }

@@ -11,10 +11,11 @@ struct ResizeDesc { const unsigned char* src; int h, w, new_h, new_w; int hb_off
 
 constexpr int GN_ROWS_PER_CHUNK = 256;
 // Block cap of the head's persistent streaming kernels -- gn_logits_kernel<false / true> and gn_taps_kernel (head_fused.hip),
-// logits_scan_kernel (detect.hip): each launches min(n_tiles, HEAD_STREAM_MAX_BLOCKS) blocks over the 128-row tile table, so above the
+// logits_scan_kernel (detect.hip): each launches head_stream_grid(n_tiles) = min(n_tiles, HEAD_STREAM_MAX_BLOCKS) blocks over the 128-row tile table, so above the
 // cap a wave takes several row groups and carries its coefficient table, code fragments and candidate list from one to the next.
 // tests/test_head_sweeps_gpu.py pins that regime at small shapes and restates the value: change both together.
 constexpr int HEAD_STREAM_MAX_BLOCKS = 2048;
+inline int head_stream_grid(int n_tiles) { return n_tiles < HEAD_STREAM_MAX_BLOCKS ? n_tiles : HEAD_STREAM_MAX_BLOCKS; }  // one block = one 128-row tile per sweep
 // a GroupNorm sample (= conv segment) whose statistics were left by the conv epilogue as per-M-tile partials
 struct GnSeg { int row0, nrows, tile0, ntiles; };
 

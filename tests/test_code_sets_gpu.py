@@ -10,7 +10,7 @@ Codes: `synthetic_codes(n, seed, scale)` as listed in tests/test_mixed_episodes_
 the uniform runs return, so none can pass vacuously: every (image, set) has a detection, the two 5-way sets give different detections,
 a 20- or 32-way set detects a class >= 8 (beyond the 8-float narrow logits pitch).  A decode that reports a status bit raises.
 
-Column layout (csrc/api_internal.h Plan::cs_col0): the sets of up to 32 classes (bf16, cls GroupNorm) sit side by side, each at the
+Column layout (csrc/api_internal.h Plan::cs.col0): the sets of up to 32 classes (bf16, cls GroupNorm) sit side by side, each at the
 next multiple of 4, in blocks of 32 packed code rows, four blocks per launch of gn_logits_sets_kernel.  `_starts` restates that rule
 for the premises "a set straddles a block boundary" / "a set ends at a block boundary"."""
 import ctypes
@@ -473,3 +473,72 @@ def test_runner_fuse_repeats(model, tmp_path):
         assert [x[0] for x in a] == [x[0] for x in b] == list(range(NQ))
         for x, y in zip(a, b):
             assert all(torch.equal(p, q) for p, q in zip(x[1:], y[1:])), f"seed {s}, image {x[0]}"
+
+
+# ------------------------------------------------------------------------------------------------ 11: the grow paths
+def _grow_steps():
+    """The sequence of test_buffers_grow_in_place_and_settle: (name, step), step(eng) -> the detections as a list of per-image lists"""
+    c = {k: _code(k) for k in ("n5", "n5b", "n20", "n60")}
+
+    def head(k):
+        def run(eng):
+            eng.head(c[k]["cls_conv"], c[k]["cls_bias"])
+            return [eng.decode()]
+        return run
+
+    def sets(*ks):
+        def run(eng):
+            eng.head_code_sets(_pairs([c[k] for k in ks]))
+            return eng.decode_code_sets()
+        return run
+
+    def episodes(eng):
+        eng.head_episodes(_pairs([c["n5"], c["n60"]]), [0, 1])
+        return [eng.decode()]
+
+    return [("1 head(n5)", head("n5")), ("2 sets[n5]", sets("n5")), ("3 sets[n5, n20, n5b]", sets("n5", "n20", "n5b")),
+            ("4 sets[n20, n60]", sets("n20", "n60")), ("5 episodes[n5, n60]", episodes), ("6 head(n60)", head("n60")),
+            ("7 sets[n5]", sets("n5")), ("8 head(n5)", head("n5"))]
+
+
+def _same_step(got, want, what):
+    assert len(got) == len(want), what
+    for g, (a, b) in enumerate(zip(got, want)):
+        assert len(a) == len(b), what
+        for i, (x, y) in enumerate(zip(a, b)):
+            _same(x, y, f"{what}: slot {g}, image {i}")
+
+
+def test_buffers_grow_in_place_and_settle():
+    """One bf16 engine, two images, every head in turn with growing and shrinking requests: the packed code / bias tables, the logits,
+    the decode slots and the candidate buffers of the B-slot and the G * B-slot decodes grow step by step, a 60-way fused scan leaves
+    candidates between two of the growths, and smaller requests reuse what is there.  Every step returns what a fresh engine that runs
+    only that step returns; a second pass over the sequence returns the same and allocates nothing."""
+    B = 2
+    feats = _pyramid(B, SMALL)
+    steps = _grow_steps()
+    want = {}
+    for name, step in steps:
+        fresh = _new("bf16", feats, SMALL)
+        want[name] = step(fresh)
+        fresh.close()
+        assert all(d["scores"].numel() > 0 for slot in want[name] for d in slot), f"{name}: an image has no detection on a fresh engine"
+    _same_step(want["8 head(n5)"], want["1 head(n5)"], "fresh engines: step 8 against step 1")
+    eng = _new("bf16", feats, SMALL)
+    bytes_after = []
+    for rep in range(2):
+        got = {}
+        for name, step in steps:
+            before = eng.device_bytes()
+            got[name] = step(eng)
+            grew = eng.device_bytes() - before
+            print(f"pass {rep}, step {name}: device bytes {before} {grew:+d}")
+            _same_step(got[name], want[name], f"pass {rep}, step {name}")
+            if rep == 0 and name[0] in "346":
+                assert grew > 0, f"step {name} allocated nothing: the sequence exercises no growth there"
+            if rep == 1:
+                assert grew == 0, f"second pass, step {name}: {grew} bytes allocated in the steady state"
+        _same_step(got["8 head(n5)"], got["1 head(n5)"], f"pass {rep}: step 8 against step 1")
+        bytes_after.append(eng.device_bytes())
+    assert bytes_after[1] == bytes_after[0], bytes_after
+    eng.close()
