@@ -229,12 +229,14 @@ int sylph_codegen_classes(sylph_ctx* ctx, const float* boxes_dev, int shots, flo
  * ROIEncoder.forward (roi_encoder.py:146-204) gives for a support set of seg_len[j] shots whose shot i is the feature pyramid of the
  * segment's i-th ROI's image with that ROI's box.  The backbone has run once per image, not once per instance; segments never see
  * each other (shot softmax, compute_code, token mean and the length-1 attention stay inside a segment) and a segment may be longer
- * than 64 shots.  roi_image and seg_len are HOST arrays; their device copies are kept per (batch shape, R) and uploaded again only
- * when the values change.  Afterwards sylph_codegen_weight_norm gives n_seg values and the support taps R rows (per-shot stages;
- * SYLPH_SUP_CONTEXT stays per image: B rows) or n_seg rows (class tokens). */
+ * than 64 shots.  roi_image and seg_len are HOST arrays; their device copies are kept per (batch shape, R), shared with a
+ * sylph_codegen[_classes] call where R = B, and uploaded again only when the values change.  Afterwards
+ * sylph_codegen_weight_norm gives n_seg values and the support taps R rows (per-shot stages; SYLPH_SUP_CONTEXT stays per image:
+ * B rows) or n_seg rows (class tokens). */
 int sylph_codegen_rois(sylph_ctx* ctx, int R, const float* boxes_dev, const int* roi_image, int n_seg, const int* seg_len,
                        float* codes_out_dev);
-/* How many sylph_codegen_rois calls on this context had to upload their ROI tables (a repeated list uploads none). */
+/* How many sylph_codegen / sylph_codegen_classes / sylph_codegen_rois calls on this context had to upload their ROI tables (a repeated
+ * list, or the same shots on the same batch shape, uploads none). */
 int sylph_roi_table_uploads(sylph_ctx* ctx, int64_t* n_out);
 /* With cg_has_scale: the "cls_weight_norm" outputs of the last sylph_codegen[_classes | _rois] call (one fp32 per class / segment), the factor
  * forward_normalize_code multiplies into the L2-normalised code (code_generator.py:838-840,987-993) -> pass them to

@@ -32,14 +32,12 @@ static std::vector<LevelDesc> level_table(sylph_ctx* c, Plan* P) {
 }
 
 // the first op of a support pass: ROIAlign of the call's boxes into Q->roi
-static int add_roi_align(Plan* P, SupportPass* Q, DType dt, int L) {
+static void add_roi_align(Plan* P, SupportPass* Q, DType dt, int L) {
   const void* F = P->F;
   const LevelDesc* lvd = P->lv_dev;
   void* roi = Q->roi;
   const int S = Q->S;
-  if (Q->rois) Q->ops.push_back([=](hipStream_t s) { return launch_roi_align_rois(dt, F, 256, lvd, L, Q->cur_boxes, Q->roi_image_dev, S, 7, roi, s); });
-  else Q->ops.push_back([=](hipStream_t s) { return launch_roi_align(dt, F, 256, lvd, L, Q->cur_boxes, S, 7, roi, s); });
-  return 0;
+  Q->ops.push_back([=](hipStream_t s) { return launch_roi_align(dt, F, 256, lvd, L, Q->cur_boxes, Q->roi_image_dev, S, 7, roi, s); });
 }
 
 // add_conv_gn of a support layer (7x7 maps, applied in place) with its taps: the stored pre-GroupNorm output, the statistics of the
@@ -66,9 +64,9 @@ static int ensure_level_table(sylph_ctx* c, Plan* P) {
   return upload(c, (void**)&P->lv_dev, lv.data(), lv.size() * sizeof(LevelDesc));
 }
 
-// Q: the pass to build -- the plan's own (row s = image s, S = B) or a ROI-list pass (row r = ROI r, S = R).  The two differ in the
-// ROIAlign launch (which image a row reads) and in the tail (equal classes of cur_shots rows | the segment table); the convolutions
-// between them run on image_segs(S, 7, 7, 7, 7) either way, so their routes follow the row count.
+// Q: the pass to build, for S = R rows (row r = ROI r of the call's list).  ROIAlign reads the call's image table (which image a row
+// samples), the tail its segment table (which consecutive rows make a code); the convolutions between them run on
+// image_segs(S, 7, 7, 7, 7), so their routes follow the row count.
 int build_support(sylph_ctx* c, Plan* P, SupportPass* Q) {
   if (Q->built) return 0;
   if (!c->has_codegen) return fail("code generator weights were not loaded");
@@ -86,7 +84,7 @@ int build_support(sylph_ctx* c, Plan* P, SupportPass* Q) {
   auto& ops = Q->ops;
   const DType dt = c->dt;
   SupportPass* QQ = Q;
-  RET(add_roi_align(P, Q, dt, L));
+  add_roi_align(P, Q, dt, L);
   tap_at(Q, SYLPH_SUP_ROI, 0, Q->roi, false, S, npos);
   const void* in = Q->roi;
   void* out = Q->cgA;
@@ -114,16 +112,10 @@ int build_support(sylph_ctx* c, Plan* P, SupportPass* Q) {
     const float *co = Q->cg_conv_out, *bo = Q->cg_bias_out;
     const int l2 = c->cfg.cg_bias_l2_norm, ib = c->cg_ib, iw = c->cg_iw, is = c->cg_is, ks = c->cfg.cg_code_ksize;
     float* wn = Q->cg_wnorm;
-    if (Q->rois)
-      ops.push_back([=](hipStream_t s) {
-        return launch_codegen_tail_segs(co, 256, bo, naux > 0 ? naux : 1, ib, iw, is, QQ->seg_dev, QQ->n_seg, QQ->max_len, npos, 256, ks, l2,
-                                        QQ->cur_code_out, wn, s);
-      });
-    else
-      ops.push_back([=](hipStream_t s) {
-        const int shots = QQ->cur_shots > 0 ? QQ->cur_shots : S;
-        return launch_codegen_tail(co, 256, bo, naux > 0 ? naux : 1, ib, iw, is, S / shots, shots, npos, 256, ks, l2, QQ->cur_code_out, wn, s);
-      });
+    ops.push_back([=](hipStream_t s) {
+      return launch_codegen_tail(co, 256, bo, naux > 0 ? naux : 1, ib, iw, is, QQ->seg_dev, QQ->n_seg, QQ->max_len, npos, 256, ks, l2,
+                                 QQ->cur_code_out, wn, s);
+    });
   }
   Q->built = true;
   return 0;
@@ -134,10 +126,10 @@ int build_support_roienc(sylph_ctx* c, Plan* P, SupportPass* Q) {
   if (!c->has_roienc) return fail("ROIEncoder weights were not loaded");
   RET(ensure_pyramid(c, P));
   const size_t e = c->esz();
-  // S support images = one or several classes of P->cur_shots images each (sylph_codegen_classes).  Everything up to the encoder
-  // is per image; the reference's encoder attends over the CLASS axis of a (classes, shots, C) tensor (roi_encoder.py:184-186)
-  // and always sees one class per call at inference, i.e. a length-1 sequence: here too a class never sees another one.
-  // A ROI-list pass has two row counts: S = R ROIs for everything per shot, B images for the context, which is a function of the
+  // S ROIs = the shots of one or several classes (the segments of the list).  Everything up to the encoder is per shot; the
+  // reference's encoder attends over the CLASS axis of a (classes, shots, C) tensor (roi_encoder.py:184-186) and always sees one
+  // class per call at inference, i.e. a length-1 sequence: here too a class never sees another one.
+  // The pass has two row counts: S = R ROIs for everything per shot, B images for the context, which is a function of the
   // image alone (utils.py:143-165) and is computed once per image; the MS-CAM gate of ROI r reads the context of image roi_image[r].
   const int S = Q->S, B = P->B, L = c->cfg.nlevels, npos = 49;
   RET(ensure_level_table(c, P));
@@ -159,7 +151,7 @@ int build_support_roienc(sylph_ctx* c, Plan* P, SupportPass* Q) {
   const int xbf = dt == DT_BF16 ? 1 : 0;
   SupportPass* QQ = Q;
   auto& R = c->re;
-  RET(add_roi_align(P, Q, dt, L));
+  add_roi_align(P, Q, dt, L);
   {
     const void* F = P->F;
     const LevelDesc* lvd = P->lv_dev;
@@ -175,8 +167,7 @@ int build_support_roienc(sylph_ctx* c, Plan* P, SupportPass* Q) {
     const float* ctx = Q->re_ctx;
     void* x = Q->cgA;
     const MsCamWeights w = R.cam;
-    if (Q->rois) ops.push_back([=](hipStream_t s) { return launch_mscam_rois(dt, ctx, QQ->roi_image_dev, x, S, w, s); });
-    else ops.push_back([=](hipStream_t s) { return launch_mscam(dt, ctx, x, S, w, s); });
+    ops.push_back([=](hipStream_t s) { return launch_mscam(dt, ctx, QQ->roi_image_dev, x, S, w, s); });
   }
   RET(tap_copy(c, Q, ops, SYLPH_SUP_MSCAM, 0, Q->cgA, false, S, npos));
   void* cur = Q->cgA;
@@ -220,8 +211,7 @@ int build_support_roienc(sylph_ctx* c, Plan* P, SupportPass* Q) {
   {
     float* cls = Q->re_cls;
     float* x = tok;
-    if (Q->rois) ops.push_back([=](hipStream_t s) { return launch_mean_tokens_segs(x, QQ->seg_dev, QQ->n_seg, cls, s); });
-    else ops.push_back([=](hipStream_t s) { return launch_mean_tokens(x, S / QQ->cur_shots, QQ->cur_shots, cls, s); });
+    ops.push_back([=](hipStream_t s) { return launch_mean_tokens(x, QQ->seg_dev, QQ->n_seg, cls, s); });
     const float prior = -logf((1.f - 0.01f) / 0.01f);  // ROIEncoder hard-codes prior_prob = 0.01 (roi_encoder.py:139-140), whatever MODEL.FCOS.PRIOR_PROB says
     for (int head = 0; head < 2; ++head) {
       const std::vector<sylph_ctx::Lin>& fcs = head == 0 ? R.wh : R.bh;
@@ -258,12 +248,14 @@ static int check_rois(const Plan* P, int R, const float* boxes, const int* roi_i
   return 0;
 }
 
-// Host tables of a ROI-list call -> device, like the mixed-episode head's tables (api_head.hip ep_tables): uploaded when they differ
-// from what the pass holds, so a loop that repeats its list uploads nothing.
+// Host tables of a support call -> device, like the mixed-episode head's tables (api_head.hip ep_tables): uploaded when they differ
+// from what the pass holds, so a loop that repeats its list (or its shots on its batch shape) neither uploads nor synchronises.
 static int roi_tables(sylph_ctx* c, SupportPass* Q, const int* roi_image, int n_seg, const int* seg_len) {
-  std::vector<int> ri(roi_image, roi_image + Q->S), sl(seg_len, seg_len + n_seg);
-  if (Q->roi_image_dev && ri == Q->roi_image && sl == Q->seg_len) return 0;
+  if (Q->roi_image_dev && (int)Q->seg_len.size() == n_seg && std::equal(Q->roi_image.begin(), Q->roi_image.end(), roi_image) &&
+      std::equal(Q->seg_len.begin(), Q->seg_len.end(), seg_len))
+    return 0;
   Q->roi_image.clear(); Q->seg_len.clear();  // (a failure below leaves no key that would match half-written tables)
+  std::vector<int> ri(roi_image, roi_image + Q->S), sl(seg_len, seg_len + n_seg);
   std::vector<int2> sg;
   int r0 = 0, mx = 0;
   for (int j = 0; j < n_seg; ++j) {
@@ -281,13 +273,53 @@ static int roi_tables(sylph_ctx* c, SupportPass* Q, const int* roi_image, int n_
   return 0;
 }
 
-// scratch context of the stand-alone ROIAlign entries: its allocations are freed on return
-struct RoiScratch {
-  sylph_ctx tmp;
-  hipStream_t s;
-  explicit RoiScratch(sylph_ctx* c) : s(c->stream) { tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros; }
-  ~RoiScratch() { (void)hipStreamSynchronize(s); for (void* p : tmp.allocs) (void)hipFree(p); }
-};
+// One support call, its arguments checked: the plan's pass for R rows (built on first use), the call's tables, the launches.
+static int run_support(sylph_ctx* c, Plan* P, int R, const float* boxes, const int* roi_image, int n_seg, const int* seg_len, float* codes_out,
+                       const char* what) {
+  HIPCHK(hipSetDevice(c->device));
+  OwnerScope own(c, P);
+  auto& slot = P->sup[R];
+  if (!slot) { slot.reset(new SupportPass()); slot->S = R; }
+  SupportPass* Q = slot.get();
+  if (c->cfg.cg_type == 1) BUILD(build_support_roienc(c, P, Q), P);
+  else BUILD(build_support(c, P, Q), P);
+  RET(roi_tables(c, Q, roi_image, n_seg, seg_len));
+  Q->cur_boxes = boxes;
+  Q->cur_code_out = codes_out;
+  Q->n_seg = n_seg;
+  P->sup_last = Q;
+  return run_ops(c, Q->ops, what);
+}
+
+// the stand-alone ROIAlign entries: R checked rows on a scratch context whose allocations are freed on return
+static int roi_align_alone(sylph_ctx* c, Plan* P, int R, const float* boxes, const int* roi_image, float* out, const char* what) {
+  struct Scratch {
+    sylph_ctx tmp;
+    hipStream_t s;
+    explicit Scratch(sylph_ctx* c) : s(c->stream) { tmp.device = c->device; tmp.dt = c->dt; tmp.stream = c->stream; tmp.zeros = c->zeros; }
+    ~Scratch() { (void)hipStreamSynchronize(s); for (void* p : tmp.allocs) (void)hipFree(p); }
+  };
+  HIPCHK(hipSetDevice(c->device));
+  const std::vector<LevelDesc> lv = level_table(c, P);
+  Scratch sc(c);
+  LevelDesc* lvd = nullptr;
+  int* rid = nullptr;
+  void* roi = nullptr;
+  RET(upload(&sc.tmp, (void**)&lvd, lv.data(), lv.size() * sizeof(LevelDesc)));
+  RET(upload(&sc.tmp, (void**)&rid, roi_image, (size_t)R * sizeof(int)));
+  RET(sc.tmp.dalloc(&roi, (size_t)R * 49 * 256 * c->esz()));
+  KCHK(launch_roi_align(c->dt, P->F, 256, lvd, c->cfg.nlevels, boxes, rid, R, 7, roi, c->stream), what);
+  for (int r = 0; r < R; ++r)
+    KCHK(launch_export_nchw(c->dt, roi, out + (size_t)r * 256 * 49, 256, 49, r * 49, 256, c->stream), "export roi");
+  return 0;
+}
+
+// roi_image of the one-box-per-image form: row r is image r
+static std::vector<int> identity_images(int B) {
+  std::vector<int> v(B);
+  for (int b = 0; b < B; ++b) v[b] = b;
+  return v;
+}
 
 }  // namespace sylph_host
 
@@ -297,38 +329,14 @@ int sylph_roi_align(sylph_ctx* c, const float* boxes, float* out) {
   Plan* P = c->cur;
   if (!P || !P->F) return fail("no current batch");
   if (!boxes || !out) return fail("NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  const int S = P->B, L = c->cfg.nlevels;
-  const std::vector<LevelDesc> lv = level_table(c, P);
-  RoiScratch sc(c);
-  LevelDesc* lvd = nullptr;
-  void* roi = nullptr;
-  RET(upload(&sc.tmp, (void**)&lvd, lv.data(), lv.size() * sizeof(LevelDesc)));
-  RET(sc.tmp.dalloc(&roi, (size_t)S * 49 * 256 * c->esz()));
-  KCHK(launch_roi_align(c->dt, P->F, 256, lvd, L, boxes, S, 7, roi, c->stream), "roi_align");
-  for (int s = 0; s < S; ++s)
-    KCHK(launch_export_nchw(c->dt, roi, out + (size_t)s * 256 * 49, 256, 49, s * 49, 256, c->stream), "export roi");
-  return 0;
+  return roi_align_alone(c, P, P->B, boxes, identity_images(P->B).data(), out, "roi_align");
 }
 
 int sylph_roi_align_rois(sylph_ctx* c, int R, const float* boxes, const int* roi_image, float* out) {
   Plan* P = c->cur;
   RET(check_rois(P, R, boxes, roi_image));
   if (!out) return fail("NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  const int L = c->cfg.nlevels;
-  const std::vector<LevelDesc> lv = level_table(c, P);
-  RoiScratch sc(c);
-  LevelDesc* lvd = nullptr;
-  int* rid = nullptr;
-  void* roi = nullptr;
-  RET(upload(&sc.tmp, (void**)&lvd, lv.data(), lv.size() * sizeof(LevelDesc)));
-  RET(upload(&sc.tmp, (void**)&rid, roi_image, (size_t)R * sizeof(int)));
-  RET(sc.tmp.dalloc(&roi, (size_t)R * 49 * 256 * c->esz()));
-  KCHK(launch_roi_align_rois(c->dt, P->F, 256, lvd, L, boxes, rid, R, 7, roi, c->stream), "roi_align_rois");
-  for (int r = 0; r < R; ++r)
-    KCHK(launch_export_nchw(c->dt, roi, out + (size_t)r * 256 * 49, 256, 49, r * 49, 256, c->stream), "export roi");
-  return 0;
+  return roi_align_alone(c, P, R, boxes, roi_image, out, "roi_align_rois");
 }
 
 static int support_tap(sylph_ctx* c, int stage, int index, const SupportPass::SupTap** t, int* n) {
@@ -386,23 +394,16 @@ int sylph_export_support(sylph_ctx* c, int stage, int index, float* out) {
   return 0;
 }
 
+// The one-box-per-image form: the ROI list with roi_image[r] = r in B / shots segments of `shots` rows each.
 int sylph_codegen_classes(sylph_ctx* c, const float* boxes, int shots, float* codes_out) {
   Plan* P = c->cur;
   if (!P) return fail("no current batch");
   if (!boxes || !codes_out) return fail("NULL argument");
   if (shots < 1 || P->B % shots != 0) return fail("pooled_features.shape[0] " + std::to_string(P->B) + " Vs batch_size * num_shots: the batch is not a whole number of classes");
+  // a policy of this entry, not a limit of the kernels behind it (a segment of sylph_codegen_rois may be longer)
   if (shots > 64) return fail("codegen: " + std::to_string(shots) + " shots per class in one call; the shot reduction handles at most 64 (chunk the class and reduce the chunk codes, sylph_reduce_codes)");
-  OwnerScope own(c, P);
-  SupportPass* Q = &P->sup;
-  Q->S = P->B;
-  if (c->cfg.cg_type == 1) BUILD(build_support_roienc(c, P, Q), P);
-  else BUILD(build_support(c, P, Q), P);
-  Q->cur_boxes = boxes;
-  Q->cur_code_out = codes_out;
-  Q->cur_shots = shots;
-  Q->n_seg = P->B / shots;
-  P->sup_last = Q;
-  return run_ops(c, Q->ops, "codegen");
+  const std::vector<int> roi_image = identity_images(P->B), seg_len(P->B / shots, shots);
+  return run_support(c, P, P->B, boxes, roi_image.data(), (int)seg_len.size(), seg_len.data(), codes_out, "codegen");
 }
 
 int sylph_codegen_rois(sylph_ctx* c, int R, const float* boxes, const int* roi_image, int n_seg, const int* seg_len, float* codes_out) {
@@ -417,19 +418,7 @@ int sylph_codegen_rois(sylph_ctx* c, int R, const float* boxes, const int* roi_i
   }
   if (total != R) return fail("ROI list: the segment lengths sum to " + std::to_string(total) + ", not to R = " + std::to_string(R));
   if (R > 65535) return fail("ROI list: R = " + std::to_string(R) + " ROIs in one call; at most 65535");
-  HIPCHK(hipSetDevice(c->device));
-  OwnerScope own(c, P);
-  auto& slot = P->sup_rois[R];
-  if (!slot) { slot.reset(new SupportPass()); slot->S = R; slot->rois = true; }
-  SupportPass* Q = slot.get();
-  if (c->cfg.cg_type == 1) BUILD(build_support_roienc(c, P, Q), P);
-  else BUILD(build_support(c, P, Q), P);
-  RET(roi_tables(c, Q, roi_image, n_seg, seg_len));
-  Q->cur_boxes = boxes;
-  Q->cur_code_out = codes_out;
-  Q->n_seg = n_seg;
-  P->sup_last = Q;
-  return run_ops(c, Q->ops, "codegen_rois");
+  return run_support(c, P, R, boxes, roi_image, n_seg, seg_len, codes_out, "codegen_rois");
 }
 
 int sylph_roi_table_uploads(sylph_ctx* c, int64_t* n) {

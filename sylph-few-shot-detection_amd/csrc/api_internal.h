@@ -200,7 +200,7 @@ struct sylph_ctx {
   // plans are evicted least-recently-used first once their count or their bytes exceed the budget, so a stream of
   // distinct padded shapes (real COCO / LVIS episodes) cannot grow HBM without bound.
   Plan* alloc_owner = nullptr;
-  int64_t roi_table_uploads = 0;  // sylph_codegen_rois calls that had to upload their ROI tables (sylph_roi_table_uploads)
+  int64_t roi_table_uploads = 0;  // support calls that had to upload their ROI tables (sylph_roi_table_uploads)
   bool debug_taps = false;  // sylph_set_debug_taps: tower layers keep their outputs in separate buffers (parity tests)
   uint64_t use_clock = 0;
   size_t max_plans = 32;
@@ -219,12 +219,11 @@ struct sylph_ctx {
   size_t esz() const { return dt == DT_BF16 ? 2 : 4; }
 };
 
-// One support pass of a plan: the workspaces, launches and parity taps of the code generator for S rows (ROIs) of 49 positions.
-// The plan's own pass (Plan::sup) has row s = image s with its one box; a ROI-list pass (Plan::sup_rois[R]) has row r =
-// (roi_image[r], boxes[r]) and reduces ragged segments of consecutive rows, one code per segment.
+// One support pass of a plan (Plan::sup[R]): the workspaces, launches and parity taps of the code generator for S = R rows of 49
+// positions.  Row r is the ROI (roi_image[r], boxes[r]) of the call's list; segments of consecutive rows are reduced to one code
+// each.  One box per image (sylph_codegen, sylph_codegen_classes) is the list with roi_image[r] = r and equal segments.
 struct SupportPass {
-  int S = 0;           // rows: support images (one box each) or ROIs
-  bool rois = false;   // a ROI-list pass
+  int S = 0;           // rows: ROIs
   bool built = false;
   std::vector<OpFn> ops;
   void *roi = nullptr, *cgA = nullptr, *cgB = nullptr;
@@ -242,10 +241,9 @@ struct SupportPass {
   std::map<std::pair<int, int>, SupTap> taps;
   // the current call (read by the ops at launch time)
   const float* cur_boxes = nullptr;
-  int cur_shots = 0;  // support images per class of the current sylph_codegen[_classes] call (S = classes x shots)
-  int n_seg = 0;      // codes of the current call: classes, or segments of the ROI list
+  int n_seg = 0;      // codes of the current call: the segments of its ROI list
   float* cur_code_out = nullptr;
-  // ROI-list pass: the caller's host tables as last uploaded (an unchanged list uploads nothing) and their device copies
+  // the call's host tables as last uploaded (an unchanged list uploads nothing) and their device copies
   std::vector<int> roi_image, seg_len;
   int max_len = 0;             // longest segment of seg_len
   int* roi_image_dev = nullptr;  // [S]
@@ -397,9 +395,8 @@ struct Plan {
   hipEvent_t img_out_ev = nullptr;  // recorded after the H2D copy of img_out_host (guards its reuse without a stream sync)
   // support
   LevelDesc* lv_dev = nullptr;  // per (image, level) of the batch: B x nlevels entries, shared by every support pass of the plan
-  SupportPass sup;              // sylph_codegen / sylph_codegen_classes: one box per image, S = B rows
-  // sylph_codegen_rois: one pass per ROI count R (workspaces and conv routes follow R as they follow B above)
-  std::map<int, std::unique_ptr<SupportPass>> sup_rois;
+  // one support pass per row count R (workspaces and conv routes follow R as they follow B above); sylph_codegen[_classes] use R = B
+  std::map<int, std::unique_ptr<SupportPass>> sup;
   SupportPass* sup_last = nullptr;  // the pass of the last code-generator call on this plan (taps, cls_weight_norm)
 };
 

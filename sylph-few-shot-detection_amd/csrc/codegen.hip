@@ -34,10 +34,9 @@ __device__ __forceinline__ float bilinear_at(const T* __restrict__ feat, int ld,
   return w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
 }
 
-// grid (out*out, S), block C threads (channel per thread: channel-contiguous gathers)
-// ROIS: row s is the ROI (roi_image[s], boxes[s]) of a ROI list instead of the one box of image s; everything after the choice of the
-// image's level table is the same code, so row s equals the plain kernel's on a batch whose image s is image roi_image[s].
-template <typename T, bool ROIS>
+// grid (out*out, R), block C threads (channel per thread: channel-contiguous gathers); row s is the ROI (roi_image[s], boxes[s]): box
+// s on the pyramid of image roi_image[s] of the batch
+template <typename T>
 __global__ void roi_align_kernel(const T* __restrict__ feats, int ld, const LevelDesc* __restrict__ lv, int nlevels,
                                  const float* __restrict__ boxes, const int* __restrict__ roi_image, int out_size, int C,
                                  T* __restrict__ out) {
@@ -53,7 +52,7 @@ __global__ void roi_align_kernel(const T* __restrict__ feats, int ld, const Leve
     l = fminf(fmaxf(l, min_level), min_level + (float)(nlevels - 1));
     lvl = (int)(l - min_level);
   }
-  const LevelDesc d = lv[(ROIS ? roi_image[s] : s) * nlevels + lvl];
+  const LevelDesc d = lv[roi_image[s] * nlevels + lvl];
   const float x1 = bx1 * d.scale - 0.5f, y1 = by1 * d.scale - 0.5f;
   const float x2 = bx2 * d.scale - 0.5f, y2 = by2 * d.scale - 0.5f;
   const float rw = x2 - x1, rh = y2 - y1;
@@ -73,45 +72,69 @@ __global__ void roi_align_kernel(const T* __restrict__ feats, int ld, const Leve
   }
 }
 
-int launch_roi_align(DType dt, const void* feats, int ld, const LevelDesc* lv_dev, int nlevels,
-                     const float* boxes_dev, int S, int out_size, void* out, hipStream_t s) {
-  const int C = 256;
-  dim3 grid(out_size * out_size, S), block(256);
-  if (dt == DT_BF16)
-    hipLaunchKernelGGL((roi_align_kernel<bf16_t, false>), grid, block, 0, s, (const bf16_t*)feats, ld, lv_dev, nlevels,
-                       boxes_dev, nullptr, out_size, C, (bf16_t*)out);
-  else
-    hipLaunchKernelGGL((roi_align_kernel<float, false>), grid, block, 0, s, (const float*)feats, ld, lv_dev, nlevels, boxes_dev,
-                       nullptr, out_size, C, (float*)out);
-  return (int)hipGetLastError();
-}
-
 // R ROIs (roi_image_dev[r], boxes_dev[r]) over a batch whose level table lv_dev has an entry per (image, level); the caller has
 // checked roi_image against the batch size
-int launch_roi_align_rois(DType dt, const void* feats, int ld, const LevelDesc* lv_dev, int nlevels, const float* boxes_dev,
-                          const int* roi_image_dev, int R, int out_size, void* out, hipStream_t s) {
+int launch_roi_align(DType dt, const void* feats, int ld, const LevelDesc* lv_dev, int nlevels, const float* boxes_dev,
+                     const int* roi_image_dev, int R, int out_size, void* out, hipStream_t s) {
   const int C = 256;
   if (R < 1 || R > 65535 || !roi_image_dev) return -1;
   dim3 grid(out_size * out_size, R), block(256);
   if (dt == DT_BF16)
-    hipLaunchKernelGGL((roi_align_kernel<bf16_t, true>), grid, block, 0, s, (const bf16_t*)feats, ld, lv_dev, nlevels,
-                       boxes_dev, roi_image_dev, out_size, C, (bf16_t*)out);
+    hipLaunchKernelGGL(roi_align_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)feats, ld, lv_dev, nlevels, boxes_dev, roi_image_dev,
+                       out_size, C, (bf16_t*)out);
   else
-    hipLaunchKernelGGL((roi_align_kernel<float, true>), grid, block, 0, s, (const float*)feats, ld, lv_dev, nlevels, boxes_dev,
-                       roi_image_dev, out_size, C, (float*)out);
+    hipLaunchKernelGGL(roi_align_kernel<float>, grid, block, 0, s, (const float*)feats, ld, lv_dev, nlevels, boxes_dev, roi_image_dev,
+                       out_size, C, (float*)out);
   return (int)hipGetLastError();
 }
 
-// The S shots of one class (conv_out / aux_out at its first row) combined with the shot weights wsh[S] (LDS, complete): code_out[0, C k^2)
-// by all threads, the bias and class-scale heads by the first wave.  Shared by the equal-classes and the ragged-segments kernel: a
-// class's arithmetic is the same whichever way its rows were found.
+// conv_out [R*npos][conv_ld] fp32, aux_out [R*npos][aux_ld] fp32 (channel ib: bias head, iw: shot-weight head, is: class-scale head;
+// -1 = absent) -> code_out[n_seg][C * ksize^2 + 1] (+ wnorm_out[n_seg] with a scale head).  One block per segment of the ROI list:
+// block j reduces the seg[j].y shots that start at row seg[j].x (x 49 positions) into code_out[j], the shots accumulated in segment
+// order; a segment's arithmetic does not depend on how many segments share the list or where its rows start.
+// code_generator.py:766-829: per shot the heads are global-average-pooled, the shots are combined with uniform weights 1/S or, with a
+// WEIGHT_LAYER, with softmax(pooled shot-weight logits) over the shots of the class.  The shot weights live in dynamic LDS (one float
+// per shot of the longest segment) and the softmax runs strided over one wave: lane l owns shots l, l + 64, ... and sums their
+// exponentials in that order before the wave reduction (one term per lane up to 64 shots).
 // ksize 3 (CLS_LAYER kernel size 3): F.adaptive_avg_pool2d(., (3, 3)) of the 7 x 7 map instead of the global mean -- bin i of an axis is
 // [floor(7 i / 3), ceil(7 (i + 1) / 3)) = [0,3), [2,5), [4,7): nine positions per bin, neighbours overlap in one row / column -- into
 // code_out[(c * 3 + ky) * 3 + kx], torch's (c, ky, kx) order; every value of a shot gets the shot's one weight (compute_code,
 // code_generator.py:778-829).  The bias, shot-weight and class-scale heads stay globally pooled.
-__device__ __forceinline__ void codegen_tail_shots(const float* __restrict__ conv_out, int conv_ld, const float* __restrict__ aux_out,
-                                                   int aux_ld, int ib, int is, int S, int npos, int C, int ksize, int bias_l2_norm,
-                                                   const float* wsh, float* __restrict__ code_out, float* __restrict__ wnorm_out) {
+__global__ __launch_bounds__(256) void codegen_tail_kernel(const float* __restrict__ conv_out, int conv_ld,
+                                                           const float* __restrict__ aux_out, int aux_ld, int ib, int iw, int is,
+                                                           const int2* __restrict__ seg, int npos, int C, int ksize, int bias_l2_norm,
+                                                           float* __restrict__ code_out, float* __restrict__ wnorm_out) {
+  extern __shared__ float wsh[];  // per-shot weights: max(64, longest segment) floats
+  const int S = seg[blockIdx.x].y;
+  conv_out += (size_t)seg[blockIdx.x].x * npos * conv_ld;
+  aux_out += (size_t)seg[blockIdx.x].x * npos * aux_ld;
+  code_out += (size_t)blockIdx.x * (C * ksize * ksize + 1);
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    if (iw >= 0) {  // softmax over the shots of the pooled logits (torch.nn.Softmax(dim=1), fp32)
+      float mx = -INFINITY;
+      for (int i = lane; i < S; i += 64) {
+        float sum = 0.f;
+        for (int p = 0; p < npos; ++p) sum += aux_out[((size_t)i * npos + p) * aux_ld + iw];
+        const float lg = sum / (float)npos;
+        wsh[i] = lg;
+        mx = fmaxf(mx, lg);
+      }
+      for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+      float den = 0.f;
+      for (int i = lane; i < S; i += 64) {
+        const float e = expf(wsh[i] - mx);
+        wsh[i] = e;
+        den += e;
+      }
+      for (int o = 32; o > 0; o >>= 1) den += __shfl_xor(den, o);
+      for (int i = lane; i < S; i += 64) wsh[i] = wsh[i] / den;
+    } else {
+      for (int i = lane; i < S; i += 64) wsh[i] = 1.0f / (float)S;
+    }
+  }
+  __syncthreads();
+  // code_out[0, C k^2) by all threads
   if (ksize == 3) {
     for (int i = threadIdx.x; i < C * 9; i += blockDim.x) {  // npos == 49
       const int c = i / 9, t = i - c * 9, ky = t / 3, kx = t - ky * 3;
@@ -165,99 +188,13 @@ __device__ __forceinline__ void codegen_tail_shots(const float* __restrict__ con
   }
 }
 
-// conv_out [ncls*S*npos][conv_ld] fp32, aux_out [ncls*S*npos][aux_ld] fp32 (channel ib: bias head, iw: shot-weight head, is: class-scale
-// head; -1 = absent) -> code_out[ncls][C * ksize^2 + 1] (+ wnorm_out[ncls] with a scale head); one block per class (its S consecutive support
-// images: the arithmetic of a class does not depend on how many classes share the batch).
-// code_generator.py:766-829: per shot the heads are global-average-pooled, the shots are combined with uniform weights 1/S or, with a
-// WEIGHT_LAYER, with softmax(pooled shot-weight logits) over the shots of the class.
-__global__ __launch_bounds__(256) void codegen_tail_kernel(const float* __restrict__ conv_out, int conv_ld,
-                                                           const float* __restrict__ aux_out, int aux_ld, int ib, int iw, int is, int S,
-                                                           int npos, int C, int ksize, int bias_l2_norm, float* __restrict__ code_out,
-                                                           float* __restrict__ wnorm_out) {
-  conv_out += (size_t)blockIdx.x * S * npos * conv_ld;
-  aux_out += (size_t)blockIdx.x * S * npos * aux_ld;
-  code_out += (size_t)blockIdx.x * (C * ksize * ksize + 1);
-  __shared__ float wsh[64];  // per-shot weights (S <= 64)
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    if (iw >= 0) {  // softmax over the shots of the pooled logits (torch.nn.Softmax(dim=1), fp32)
-      float lg = -INFINITY;
-      if (lane < S) {
-        float sum = 0.f;
-        for (int p = 0; p < npos; ++p) sum += aux_out[((size_t)lane * npos + p) * aux_ld + iw];
-        lg = sum / (float)npos;
-      }
-      float mx = lg;
-      for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-      const float e = lane < S ? expf(lg - mx) : 0.f;
-      float den = e;
-      for (int o = 32; o > 0; o >>= 1) den += __shfl_xor(den, o);
-      wsh[lane] = e / den;
-    } else {
-      wsh[lane] = 1.0f / (float)S;
-    }
-  }
-  __syncthreads();
-  codegen_tail_shots(conv_out, conv_ld, aux_out, aux_ld, ib, is, S, npos, C, ksize, bias_l2_norm, wsh, code_out, wnorm_out);
-}
+constexpr int TAIL_MAX_LEN = 16384;  // 64 KiB of shot weights in LDS
 
-int launch_codegen_tail(const float* conv_out, int conv_ld, const float* aux_out, int aux_ld, int ib, int iw, int is, int ncls, int S, int npos,
-                        int C, int ksize, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s) {
-  if (npos > 64 || ncls < 1 || S > 64 || (ksize != 1 && !(ksize == 3 && npos == 49))) return -1;
-  hipLaunchKernelGGL(codegen_tail_kernel, dim3(ncls), dim3(256), 0, s, conv_out, conv_ld, aux_out, aux_ld, ib, iw, is, S, npos, C, ksize,
-                     bias_l2_norm, code_out, is >= 0 ? wnorm_out : nullptr);
-  return (int)hipGetLastError();
-}
-
-// The same reduction over ragged segments of a ROI list: block j reduces the seg[j].y shots that start at row seg[j].x (x 49
-// positions) into code_out[j].  Per shot the arithmetic is codegen_tail_kernel's and the shots are accumulated in segment order; the
-// shot weights live in dynamic LDS (one float per shot of the longest segment) and the softmax runs strided over one wave: lane l
-// owns shots l, l + 64, ... and sums their exponentials in that order before the wave reduction, which for n <= 64 is one term per
-// lane, i.e. the plain kernel's reduction bit for bit.
-__global__ __launch_bounds__(256) void codegen_tail_segs_kernel(const float* __restrict__ conv_out, int conv_ld,
-                                                                const float* __restrict__ aux_out, int aux_ld, int ib, int iw, int is,
-                                                                const int2* __restrict__ seg, int npos, int C, int ksize, int bias_l2_norm,
-                                                                float* __restrict__ code_out, float* __restrict__ wnorm_out) {
-  extern __shared__ float wsh[];  // per-shot weights: max(64, longest segment) floats
-  const int S = seg[blockIdx.x].y;
-  conv_out += (size_t)seg[blockIdx.x].x * npos * conv_ld;
-  aux_out += (size_t)seg[blockIdx.x].x * npos * aux_ld;
-  code_out += (size_t)blockIdx.x * (C * ksize * ksize + 1);
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    if (iw >= 0) {  // softmax over the shots of the pooled logits (torch.nn.Softmax(dim=1), fp32)
-      float mx = -INFINITY;
-      for (int i = lane; i < S; i += 64) {
-        float sum = 0.f;
-        for (int p = 0; p < npos; ++p) sum += aux_out[((size_t)i * npos + p) * aux_ld + iw];
-        const float lg = sum / (float)npos;
-        wsh[i] = lg;
-        mx = fmaxf(mx, lg);
-      }
-      for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-      float den = 0.f;
-      for (int i = lane; i < S; i += 64) {
-        const float e = expf(wsh[i] - mx);
-        wsh[i] = e;
-        den += e;
-      }
-      for (int o = 32; o > 0; o >>= 1) den += __shfl_xor(den, o);
-      for (int i = lane; i < S; i += 64) wsh[i] = wsh[i] / den;
-    } else {
-      for (int i = lane; i < S; i += 64) wsh[i] = 1.0f / (float)S;
-    }
-  }
-  __syncthreads();
-  codegen_tail_shots(conv_out, conv_ld, aux_out, aux_ld, ib, is, S, npos, C, ksize, bias_l2_norm, wsh, code_out, wnorm_out);
-}
-
-constexpr int TAIL_SEGS_MAX_LEN = 16384;  // 64 KiB of shot weights in LDS
-
-int launch_codegen_tail_segs(const float* conv_out, int conv_ld, const float* aux_out, int aux_ld, int ib, int iw, int is, const int2* seg_dev,
-                             int n_seg, int max_len, int npos, int C, int ksize, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s) {
-  if (npos > 64 || n_seg < 1 || max_len < 1 || max_len > TAIL_SEGS_MAX_LEN || (ksize != 1 && !(ksize == 3 && npos == 49))) return -1;
+int launch_codegen_tail(const float* conv_out, int conv_ld, const float* aux_out, int aux_ld, int ib, int iw, int is, const int2* seg_dev,
+                        int n_seg, int max_len, int npos, int C, int ksize, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s) {
+  if (npos > 64 || n_seg < 1 || max_len < 1 || max_len > TAIL_MAX_LEN || (ksize != 1 && !(ksize == 3 && npos == 49))) return -1;
   const size_t lds = (size_t)(max_len > 64 ? max_len : 64) * sizeof(float);
-  hipLaunchKernelGGL(codegen_tail_segs_kernel, dim3(n_seg), dim3(256), lds, s, conv_out, conv_ld, aux_out, aux_ld, ib, iw, is, seg_dev, npos, C,
+  hipLaunchKernelGGL(codegen_tail_kernel, dim3(n_seg), dim3(256), lds, s, conv_out, conv_ld, aux_out, aux_ld, ib, iw, is, seg_dev, npos, C,
                      ksize, bias_l2_norm, code_out, is >= 0 ? wnorm_out : nullptr);
   return (int)hipGetLastError();
 }

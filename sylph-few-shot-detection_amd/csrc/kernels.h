@@ -181,15 +181,12 @@ int launch_decode(const DecodeCfg& cfg, const DecodeSeg* segs_dev, int nseg, int
 
 // codegen.hip
 struct LevelDesc { int row0; int H, W; float scale; };  // per (image, level): rows of the feature pyramid
+// row r: box r on image roi_image_dev[r] of the batch (lv_dev: an entry per (image, level))
 int launch_roi_align(DType dt, const void* feats, int ld, const LevelDesc* lv_dev, int nlevels, const float* boxes_dev,
-                     int S, int out_size, void* out, hipStream_t s);
-int launch_roi_align_rois(DType dt, const void* feats, int ld, const LevelDesc* lv_dev, int nlevels, const float* boxes_dev,
-                          const int* roi_image_dev, int R, int out_size, void* out, hipStream_t s);  // row r: box r on image roi_image[r]
-int launch_codegen_tail(const float* conv_out, int conv_ld, const float* aux_out, int aux_ld, int ib, int iw, int is, int ncls, int S, int npos,
-                        int C, int ksize, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s);
-// ragged segments of a ROI list: seg_dev[j] = {first row, rows}; max_len = the longest segment (sizes the LDS weight table)
-int launch_codegen_tail_segs(const float* conv_out, int conv_ld, const float* aux_out, int aux_ld, int ib, int iw, int is, const int2* seg_dev,
-                             int n_seg, int max_len, int npos, int C, int ksize, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s);
+                     const int* roi_image_dev, int R, int out_size, void* out, hipStream_t s);
+// one code per segment of the ROI list: seg_dev[j] = {first row, rows}; max_len = the longest segment (sizes the LDS weight table)
+int launch_codegen_tail(const float* conv_out, int conv_ld, const float* aux_out, int aux_ld, int ib, int iw, int is, const int2* seg_dev,
+                        int n_seg, int max_len, int npos, int C, int ksize, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s);
 int launch_normalize_codes(float* codes, int ncodes, int C, int ksize, const float* gn_gamma, const float* gn_beta, int post_norm,
                            int l2_norm, float conv_scale, float bias_scale, float bias_prior, const float* weight_norm,
                            hipStream_t s);
@@ -202,12 +199,10 @@ struct MsCamWeights {  // fp32 device pointers: conv1x1 256->64, GN(32,64), conv
 };
 int launch_adaptive_context(DType dt, const void* feats, int ld, const LevelDesc* lv_dev, int nlevels, int S,
                             int out_size, float* ctx, hipStream_t s);
-int launch_mscam(DType dt, const float* ctx, void* x, int S, const MsCamWeights& w, hipStream_t s);
-int launch_mscam_rois(DType dt, const float* ctx, const int* ctx_row_dev, void* x, int R, const MsCamWeights& w, hipStream_t s);
+int launch_mscam(DType dt, const float* ctx, const int* ctx_row_dev, void* x, int R, const MsCamWeights& w, hipStream_t s);
 int launch_linear(int x_is_bf16, const void* x, int ldx, int S, const float* W, const float* b, int K, int O, float* y,
                   int ldy, int relu, float add, hipStream_t s);
 int launch_add_layernorm(float* x, const float* r, int S, const float* gamma, const float* beta, hipStream_t s);
-int launch_mean_tokens(const float* x, int n_classes, int S, float* out, hipStream_t s);
-int launch_mean_tokens_segs(const float* x, const int2* seg_dev, int n_seg, float* out, hipStream_t s);
+int launch_mean_tokens(const float* x, const int2* seg_dev, int n_seg, float* out, hipStream_t s);
 
 }  // namespace sylph

@@ -60,8 +60,8 @@ __device__ __forceinline__ float gn8_lane(float v, float gamma, float beta) {  /
   return d * (1.0f / sqrtf(q * 0.125f + 1e-5f)) * gamma + beta;
 }
 
-// ROIS: shot s is a ROI of image ctx_row[s] and reads that image's context (the context is per image, the gated map per ROI)
-template <typename T, bool ROIS>
+// shot s is a ROI of image ctx_row[s] and reads that image's context (the context is per image, the gated map per ROI)
+template <typename T>
 __global__ __launch_bounds__(256) void mscam_kernel(const float* __restrict__ ctx_g, const int* __restrict__ ctx_row, T* __restrict__ x,
                                                     const MsCamWeights w) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void mscam_kernel(const float* __restrict__ ct
   float* vec = l2 + MP * MC;       // [256] scratch
   float* stat = vec + MC;          // [64]
   const int s = blockIdx.x, t = threadIdx.x;
-  const float* cg = ctx_g + (size_t)(ROIS ? ctx_row[s] : s) * MP * MC;
+  const float* cg = ctx_g + (size_t)ctx_row[s] * MP * MC;
   for (int i = t; i < MP * MC; i += 256) ctx[i] = cg[i];
   __syncthreads();
   // global descriptor: mean over positions
@@ -182,31 +182,18 @@ __global__ __launch_bounds__(256) void mscam_kernel(const float* __restrict__ ct
 
 constexpr size_t MSCAM_LDS = (size_t)(MP * MC * 2 + MP * MI + MC + 64) * sizeof(float);
 
-int launch_mscam(DType dt, const float* ctx, void* x, int S, const MsCamWeights& w, hipStream_t s) {
-  const size_t lds = MSCAM_LDS;
-  static PerDeviceOnce once;
-  if (!once.run(current_device(), [&] {
-        return hipFuncSetAttribute((const void*)mscam_kernel<bf16_t, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-               hipFuncSetAttribute((const void*)mscam_kernel<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-      }))
-    return -7;
-  if (dt == DT_BF16) hipLaunchKernelGGL((mscam_kernel<bf16_t, false>), dim3(S), dim3(256), lds, s, ctx, nullptr, (bf16_t*)x, w);
-  else hipLaunchKernelGGL((mscam_kernel<float, false>), dim3(S), dim3(256), lds, s, ctx, nullptr, (float*)x, w);
-  return (int)hipGetLastError();
-}
-
 // x holds R ROI maps; ROI r is gated by the context of image ctx_row_dev[r] (ctx: one 7x7 map per image of the batch)
-int launch_mscam_rois(DType dt, const float* ctx, const int* ctx_row_dev, void* x, int R, const MsCamWeights& w, hipStream_t s) {
+int launch_mscam(DType dt, const float* ctx, const int* ctx_row_dev, void* x, int R, const MsCamWeights& w, hipStream_t s) {
   const size_t lds = MSCAM_LDS;
   if (R < 1 || !ctx_row_dev) return -1;
   static PerDeviceOnce once;
   if (!once.run(current_device(), [&] {
-        return hipFuncSetAttribute((const void*)mscam_kernel<bf16_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-               hipFuncSetAttribute((const void*)mscam_kernel<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+        return hipFuncSetAttribute((const void*)mscam_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
+               hipFuncSetAttribute((const void*)mscam_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
       }))
     return -7;
-  if (dt == DT_BF16) hipLaunchKernelGGL((mscam_kernel<bf16_t, true>), dim3(R), dim3(256), lds, s, ctx, ctx_row_dev, (bf16_t*)x, w);
-  else hipLaunchKernelGGL((mscam_kernel<float, true>), dim3(R), dim3(256), lds, s, ctx, ctx_row_dev, (float*)x, w);
+  if (dt == DT_BF16) hipLaunchKernelGGL(mscam_kernel<bf16_t>, dim3(R), dim3(256), lds, s, ctx, ctx_row_dev, (bf16_t*)x, w);
+  else hipLaunchKernelGGL(mscam_kernel<float>, dim3(R), dim3(256), lds, s, ctx, ctx_row_dev, (float*)x, w);
   return (int)hipGetLastError();
 }
 
@@ -285,22 +272,9 @@ int launch_add_layernorm(float* x, const float* r, int S, const float* gamma, co
   return (int)hipGetLastError();
 }
 
-// ---- out[:] = mean_s x[s][:] (E = 256) --------------------------------------------------------------
-// one block per class: the S tokens of class c are rows [c S, (c + 1) S)
-__global__ void mean_tokens_kernel(const float* __restrict__ x, int S, float* __restrict__ out) {
-  const int t = threadIdx.x, c = blockIdx.x;
-  float a = 0.f;
-  for (int s = 0; s < S; ++s) a += x[((size_t)c * S + s) * 256 + t];
-  out[(size_t)c * 256 + t] = a / (float)S;
-}
-
-int launch_mean_tokens(const float* x, int n_classes, int S, float* out, hipStream_t s) {
-  hipLaunchKernelGGL(mean_tokens_kernel, dim3(n_classes), dim3(256), 0, s, x, S, out);
-  return (int)hipGetLastError();
-}
-
-// ragged classes of a ROI list: block j averages the seg[j].y tokens that start at row seg[j].x, in row order
-__global__ void mean_tokens_segs_kernel(const float* __restrict__ x, const int2* __restrict__ seg, float* __restrict__ out) {
+// ---- out[j][:] = mean of the tokens of segment j (E = 256) -------------------------------------------
+// one block per segment of the ROI list: block j averages the seg[j].y tokens that start at row seg[j].x, in row order
+__global__ void mean_tokens_kernel(const float* __restrict__ x, const int2* __restrict__ seg, float* __restrict__ out) {
   const int t = threadIdx.x, c = blockIdx.x;
   const int r0 = seg[c].x, S = seg[c].y;
   float a = 0.f;
@@ -308,9 +282,9 @@ __global__ void mean_tokens_segs_kernel(const float* __restrict__ x, const int2*
   out[(size_t)c * 256 + t] = a / (float)S;
 }
 
-int launch_mean_tokens_segs(const float* x, const int2* seg_dev, int n_seg, float* out, hipStream_t s) {
+int launch_mean_tokens(const float* x, const int2* seg_dev, int n_seg, float* out, hipStream_t s) {
   if (n_seg < 1) return -1;
-  hipLaunchKernelGGL(mean_tokens_segs_kernel, dim3(n_seg), dim3(256), 0, s, x, seg_dev, out);
+  hipLaunchKernelGGL(mean_tokens_kernel, dim3(n_seg), dim3(256), 0, s, x, seg_dev, out);
   return (int)hipGetLastError();
 }
 

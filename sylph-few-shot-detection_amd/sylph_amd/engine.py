@@ -266,6 +266,7 @@ class Engine:
         # MODEL.PROPOSAL_GENERATOR.OWD (fcos_outputs.py:913-916): class probabilities are replaced by ONE all-ones class
         self.owd = bool(cfg.MODEL.PROPOSAL_GENERATOR.get("OWD", False)) if cfg is not None else False
         self._batch = None  # (B, H, W, [(h,w)...])
+        self._sup_rows = None  # boxes of the last codegen* call: the rows of export_support's per-shot stages
         self._ncls = 0
         self._keep = []  # tensors that must outlive queued kernels
         self._lib_writes = 0  # in-place writes into caller tensors through raw pointers (part of the class-code cache key)
@@ -683,42 +684,47 @@ class Engine:
         return [dict(zip(keys, vals)) for vals in zip(*cols)]
 
     # ---- support path -------------------------------------------------------------------------------
-    def codegen(self, boxes: torch.Tensor) -> torch.Tensor:
-        self._stream()
-        B = self._batch[0]
+    def _image_boxes(self, boxes: torch.Tensor) -> torch.Tensor:
+        """One box per image of the current batch -> (B, 4) fp32 on the device; the message is the reference's."""
         bx = boxes.to(self.device, torch.float32).reshape(-1, 4).contiguous()
+        B = self._batch[0]
         assert bx.shape[0] == B, f"pooled_features.shape[0] {bx.shape[0]} Vs batch_size * num_shots {B}"
+        return bx
+
+    def _run_codegen(self, what: str, bx: torch.Tensor, n_codes: Optional[int], *args) -> torch.Tensor:
+        """The common end of the three codegen* methods, their arguments checked: sylph_<what>(ctx, *args, out) on the device boxes bx, which
+        stay alive while the library reads them -> n_codes rows of code_len floats (None: one bare row)."""
+        self._stream()
+        out = torch.empty(*(() if n_codes is None else (n_codes,)), self.code_len, device=self.device)
+        self._keep_boxes = bx
+        check(getattr(self.L, "sylph_" + what)(self._ctx, *args, _ptr(out)), what)
+        self._sup_rows = bx.shape[0]
+        return out
+
+    def codegen(self, boxes: torch.Tensor) -> torch.Tensor:
+        bx = self._image_boxes(boxes)
+        B = bx.shape[0]
         if B > 64:
             raise ValueError(f"{B} support images of one class in one call: the code generator's shot reduction handles at most 64 "
                              "(split the class into chunks and reduce them, as the base-class path does)")
-        out = torch.empty(self.code_len, device=self.device)
-        self._keep_boxes = bx
-        check(self.L.sylph_codegen(self._ctx, _ptr(bx), _ptr(out)), "codegen")
-        self._sup_rows = None
-        return out
+        return self._run_codegen("codegen", bx, None, _ptr(bx))
 
     def codegen_classes(self, boxes: torch.Tensor, shots: int) -> torch.Tensor:
         """Several classes in ONE batch: the current batch holds n_classes * shots support images (class k = images
         [k * shots, (k + 1) * shots)), boxes (n_classes * shots, 4) -> (n_classes, 256 k^2 + 1) un-normalised codes (k = code_ksize)."""
-        self._stream()
-        B = self._batch[0]
-        bx = boxes.to(self.device, torch.float32).reshape(-1, 4).contiguous()
-        assert bx.shape[0] == B and B % shots == 0, f"pooled_features.shape[0] {bx.shape[0]} Vs batch_size * num_shots {B}"
+        bx = self._image_boxes(boxes)
+        B = bx.shape[0]
+        assert B % shots == 0, f"pooled_features.shape[0] {B} Vs batch_size * num_shots {B}"
         if shots > 64:
             raise ValueError(f"{shots} shots per class in one call: the code generator's shot reduction handles at most 64 (split the "
                              "class into chunks and reduce them, as the base-class path does)")
-        out = torch.empty(B // shots, self.code_len, device=self.device)
-        self._keep_boxes = bx
-        check(self.L.sylph_codegen_classes(self._ctx, _ptr(bx), int(shots), _ptr(out)), "codegen_classes")
-        self._sup_rows = None
-        return out
+        return self._run_codegen("codegen_classes", bx, B // shots, _ptr(bx), int(shots))
 
     def codegen_rois(self, boxes: torch.Tensor, roi_image, seg_len) -> torch.Tensor:
         """Class codes from a ROI list over the current batch (sylph_codegen_rois): ROI r is boxes[r] on image roi_image[r], any
         number per image in any order; the ROIs are cut into consecutive segments of seg_len[j] >= 1 shots and row j of the
         (n_seg, 256 k^2 + 1) result is the un-normalised code of segment j, as `codegen` gives it for a batch holding the segment's images
         once per ROI.  No cap on a segment's length."""
-        self._stream()
         bx, ri = self._check_rois(boxes, roi_image)
         if seg_len is None:
             raise ValueError("seg_len must be given")
@@ -730,14 +736,10 @@ class Engine:
                 raise ValueError(f"seg_len[{j}] = {n}: a segment needs at least one ROI")
         if sum(sl) != len(ri):
             raise ValueError(f"the segment lengths sum to {sum(sl)}, not to R = {len(ri)}")
-        out = torch.empty(len(sl), self.code_len, device=self.device)
-        self._keep_boxes = bx
-        check(self.L.sylph_codegen_rois(self._ctx, len(ri), _ptr(bx), _iarr(ri), len(sl), _iarr(sl), _ptr(out)), "codegen_rois")
-        self._sup_rows = len(ri)
-        return out
+        return self._run_codegen("codegen_rois", bx, len(sl), len(ri), _ptr(bx), _iarr(ri), len(sl), _iarr(sl))
 
     def roi_table_uploads(self) -> int:
-        """How many codegen_rois calls of this engine uploaded their ROI tables (a repeated identical list uploads none)."""
+        """How many codegen* calls of this engine uploaded their ROI tables (a repeated identical list uploads none)."""
         n = c_int64(0)
         check(self.L.sylph_roi_table_uploads(self._ctx, ctypes.byref(n)), "roi_table_uploads")
         return n.value
@@ -853,9 +855,7 @@ class Engine:
         check(self.L.sylph_support_tap_numel(self._ctx, st, int(index), ctypes.byref(n)), "support_tap_numel")
         out = torch.empty(n.value, device=self.device)
         check(self.L.sylph_export_support(self._ctx, st, int(index), _ptr(out)), "export_support")
-        B = self._batch[0]
-        if stage != "context":  # after codegen_rois the per-shot stages have one row per ROI; the context stays per image
-            B = getattr(self, "_sup_rows", None) or B
+        B = self._batch[0] if stage == "context" else self._sup_rows  # per-shot stages: one row per box; the context stays per image
         if stage == "gn_coef":
             return out.view(B, 256, 2)
         if stage in ("tokens", "cls_tokens"):

@@ -139,6 +139,16 @@ def _split_code(code: torch.Tensor, k: int = 1, bias_shape=(1, 1, 1, 1)) -> Dict
     return {"cls_conv": code[:n].reshape(1, 256, k, k), "cls_bias": code[n:n + 1].reshape(*bias_shape)}
 
 
+def _code_dicts(engine, codes: torch.Tensor, k: int = 1, bias_shape=(1, 1, 1, 1), has_scale: bool = False) -> List[Dict[str, torch.Tensor]]:
+    """The rows of the codegen* call that `engine` has just made -> one code dict per row; with a SCALE_LAYER each gets the call's
+    "cls_weight_norm" (code_generator.py:987-999)."""
+    outs = [_split_code(c, k, bias_shape) for c in codes]
+    if has_scale:
+        for o, w in zip(outs, engine.codegen_weight_norm(len(outs))):
+            o["cls_weight_norm"] = w.reshape(1, 1, 1, 1)
+    return outs
+
+
 @CODE_GENERATOR_REGISTRY.register()
 class CodeGenerator(HipComponent):
     """CodeGeneratorHead: forward_roi_align on the current support pyramid (code_generator.py:924-1002) and, with cls_norm=True,
@@ -154,33 +164,20 @@ class CodeGenerator(HipComponent):
     def __call__(self, boxes: Optional[torch.Tensor] = None, cls_norm: bool = False, class_codes=None, weight_norm=None):
         if cls_norm:
             return self.engine.normalize_codes(class_codes, weight_norm)
-        out = _split_code(self.engine.codegen(boxes), self.engine.code_ksize)  # (1, 256, k, k) with CLS_LAYER kernel size k
-        if self.has_scale:  # code_generator.py:987-999
-            out["cls_weight_norm"] = self.engine.codegen_weight_norm(1).reshape(1, 1, 1, 1)
-        return out
+        return self._dicts(self.engine.codegen(boxes)[None])[0]  # cls_conv (1, 256, k, k) with CLS_LAYER kernel size k
 
     def forward_classes(self, boxes: torch.Tensor, shots: int):
         """Several classes of `shots` support boxes each in the current batch -> one code dict per class (the launches are
         shared, the per-class arithmetic is that of __call__)."""
-        codes = self.engine.codegen_classes(boxes, shots)
-        outs = [_split_code(c, self.engine.code_ksize) for c in codes]
-        if self.has_scale:
-            wn = self.engine.codegen_weight_norm(len(outs))
-            for o, w in zip(outs, wn):
-                o["cls_weight_norm"] = w.reshape(1, 1, 1, 1)
-        return outs
-
+        return self._dicts(self.engine.codegen_classes(boxes, shots))
 
     def forward_rois(self, boxes: torch.Tensor, roi_image, seg_len):
         """Classes from a ROI list over the current batch (Engine.codegen_rois): segment j of seg_len[j] (image, box) pairs -> one
         code dict per segment, in forward_classes' shapes.  A segment's arithmetic is that of __call__ on its shots."""
-        codes = self.engine.codegen_rois(boxes, roi_image, seg_len)
-        outs = [_split_code(c, self.engine.code_ksize) for c in codes]
-        if self.has_scale:
-            wn = self.engine.codegen_weight_norm(len(outs))
-            for o, w in zip(outs, wn):
-                o["cls_weight_norm"] = w.reshape(1, 1, 1, 1)
-        return outs
+        return self._dicts(self.engine.codegen_rois(boxes, roi_image, seg_len))
+
+    def _dicts(self, codes: torch.Tensor):
+        return _code_dicts(self.engine, codes, self.engine.code_ksize, has_scale=self.has_scale)
 
 
 @CODE_GENERATOR_REGISTRY.register()
@@ -194,25 +191,24 @@ class ROIEncoder(HipComponent):
         self.eval_shot = int(cfg.MODEL.META_LEARN.EVAL_SHOT)
 
     def __call__(self, boxes: torch.Tensor):  # no cls_norm / class_codes keywords, like the reference
-        code = self.engine.codegen(boxes)
-        return {"cls_conv": code[:256].reshape(1, 256, 1, 1), "cls_bias": code[256:257].reshape(1)}
+        return self._dicts(self.engine.codegen(boxes)[None])[0]
 
     def forward_classes(self, boxes: torch.Tensor, shots: int):
         """Several classes of EVAL_SHOT support boxes each in the current batch -> one code dict per class.  The launches are shared;
         a class's tokens never meet another class's (the reference's encoder sees one class per call at inference: a length-1
         sequence on its attention axis, roi_encoder.py:184-186), so the codes are those of __call__ per class."""
         assert shots == self.eval_shot, f"{shots} support images per class, EVAL_SHOT is {self.eval_shot}"
-        codes = self.engine.codegen_classes(boxes, shots)
-        return [{"cls_conv": c[:256].reshape(1, 256, 1, 1), "cls_bias": c[256:257].reshape(1)} for c in codes]
-
+        return self._dicts(self.engine.codegen_classes(boxes, shots))
 
     def forward_rois(self, boxes: torch.Tensor, roi_image, seg_len):
         """Classes from a ROI list over the current batch: every segment holds EVAL_SHOT (image, box) pairs -> one code dict per
         segment.  As in forward_classes a segment's tokens never meet another segment's."""
         for j, n in enumerate(seg_len):
             assert int(n) == self.eval_shot, f"segment {j} has {int(n)} ROIs, EVAL_SHOT is {self.eval_shot}"
-        codes = self.engine.codegen_rois(boxes, roi_image, seg_len)
-        return [{"cls_conv": c[:256].reshape(1, 256, 1, 1), "cls_bias": c[256:257].reshape(1)} for c in codes]
+        return self._dicts(self.engine.codegen_rois(boxes, roi_image, seg_len))
+
+    def _dicts(self, codes: torch.Tensor):
+        return _code_dicts(self.engine, codes, bias_shape=(1,))
 
 
 def build_code_generator(cfg, feature_channels, feature_levels, strides):

@@ -328,8 +328,8 @@ def test_support_codes_match_reference_golden(g10, g3, tag, dtype):
 @pytest.mark.parametrize("dtype", ["f32", "f32s", "bf16"])
 @pytest.mark.parametrize("tag", ["sup", "ws"])
 def test_roi_list_codes_equal_class_codes(tag, dtype):
-    """the contract between the two callers of codegen_tail_shots at k = 3: a ROI list is bit-identical to codegen_classes on the batch
-    that repeats each image per instance"""
+    """codegen_tail_kernel at k = 3, through both entry points: a ROI list is bit-identical to codegen_classes on the batch that repeats
+    each image per instance"""
     from test_support_bf16_pinned_gpu import _box_sets, _pyramid as _sup_pyramid
     from test_support_rois_gpu import H as SH, W as SW, _dup, _roi_images
     B, Rn, shots = 4, 12, 3
@@ -576,7 +576,7 @@ def test_predictor_loads_3x3_codes(model3, full_sd, tmp_path):
 
 def test_1x1_paths_equal_the_parent(golden_dir):
     """k = 1 behaves bit for bit as before: the head outputs and detections on g1 (bf16, gn_logits_kernel) and the support codes on g3
-    (codegen_tail_kernel, codegen_tail_segs_kernel, normalize_codes_kernel; bf16 and fp32) are torch.equal to what the library of the
+    (codegen_tail_kernel, normalize_codes_kernel; bf16 and fp32) are torch.equal to what the library of the
     commit before cg_code_ksize produced on an MI355X (g11_parent_1x1.npz, tests/golden/gen_parent_1x1_golden.py)"""
     want = np.load(os.path.join(golden_dir, "g11_parent_1x1.npz"))
     got = R.outputs_1x1(golden_dir)

@@ -4,6 +4,7 @@ The definition under test: segment j of a ROI list is ONE reference call on a su
 segment's i-th ROI's image with that ROI's box.  Hence the two comparisons every test here is made of:
   * the DUPLICATE BATCH: import_pyramid([f[roi_image] for f in feats]) holds image roi_image[r] as its image r, so the existing
     one-box-per-image entry points run the same kernels at the same launch sizes on identical operands: torch.equal, no tolerance.
+  * the PARENT'S BITS for the one-box-per-image entry points, which run the same pass with roi_image[r] = r (g12_parent_support.npz).
   * the per-segment restatements: tests/bf16_ulps.py codegen_tail_f64 on the exported per-ROI maps (its own fp32 summation bound), the
     mean of the exported tokens (1e-4 of max(1, max |want|), assert_f32), a lone Engine.codegen call per segment (the same 1e-4: a
     small lone call may take another conv route, so no bit claim) and the fp32 oracle through tests/support_rois_ref.py (1e-3, the
@@ -11,6 +12,7 @@ segment's i-th ROI's image with that ROI's box.  Hence the two comparisons every
 Pyramids go in through Engine.import_pyramid at 64 x 96 as in tests/test_support_bf16_pinned_gpu.py, whose helpers and route names
 are used here; R = 60 and R = 183 sit on the two sides of its conv_hpipe threshold (183: the odd pad patch, 64 x 128 cls-conv tiles)."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -270,6 +272,32 @@ def test_call_sequences_on_one_batch():
     eng.codegen_rois(bx, ri[::-1], sl[::-1])
     assert eng.roi_table_uploads() == n0 + 2
     assert torch.equal(steps["rois50"](eng), alone["rois50"]) and eng.roi_table_uploads() == n0 + 3
+    # R = B: a scattered ROI list of 4 rows shares its pass and its tables with codegen and codegen_classes(., 2); a stale image or
+    # segment table of the call before would show in the next one
+    lists[4] = (_box_sets(4, H, W, seed=404)[0], [2, 0, 3, 0], [1, 3])
+    steps["rois4"] = lambda e: e.codegen_rois(*lists[4]).clone()
+    e = _full_engine()
+    e.import_pyramid(feats, (H, W))
+    alone["rois4"] = steps["rois4"](e)
+    assert not torch.equal(alone["rois4"][:1], alone["codegen"].reshape(1, -1))
+    for name in ("rois4", "codegen", "rois4", "classes", "rois4", "classes", "codegen", "rois4"):
+        assert torch.equal(steps[name](eng), alone[name]), f"{name} in the R = B sequence differs from the call alone"
+
+
+# ------------------------------------------------------------------------------------------------ 5b. the parent's bits
+def test_class_form_equals_the_parent(golden_dir):
+    """codegen, codegen_classes and roi_align run as ROI lists (roi_image[r] = r, equal segments) and give bit for bit what their own
+    kernels gave on an MI355X with the library of the commit before (g12_parent_support.npz,
+    tests/golden/gen_parent_support_golden.py): codes, cls_weight_norm, the ROIEncoder's class tokens, the pooled edge boxes."""
+    from support_parent_ref import outputs_support
+    want = np.load(os.path.join(golden_dir, "g12_parent_support.npz"))
+    got = outputs_support()
+    assert sorted(got) == sorted(want.files)
+    for k in want.files:
+        assert got[k].shape == want[k].shape and np.array_equal(got[k], want[k]), f"{k} differs from the parent's"
+    for k in want.files:
+        if k.endswith("_codes"):
+            assert float(np.abs(want[k]).max()) > 0, f"{k}: the stored codes are all zero"
 
 
 # ------------------------------------------------------------------------------------------------ 6. errors
