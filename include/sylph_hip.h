@@ -358,6 +358,12 @@ int sylph_bottleneck(sylph_ctx* ctx, const float* x_nchw_dev, int B, int Cin, in
 int sylph_bottleneck_even(sylph_ctx* ctx, const float* x_nchw_dev, int B, int Cin, int H, int W, int mid, int cout,
                           const float* const* w_host, const float* const* scale_host, const float* const* shift_host,
                           float* y_nchw_dev);
+/* Kernel parity entry: the res3 block-pair launch of sylph_backbone_fpn (SYLPH_BLOCK_PAIR) alone, bf16 contexts only.  Device inputs t2
+ * (B,128,H,W) and x (B,512,H,W); host weights w3 (512,128), w1 (128,512) with their FrozenBN scale / shift.  Device outputs
+ * y = relu(bn3(w3 t2) + x) (B,512,H,W) and t1 = relu(bn1(w1 y)) (B,128,H,W): conv3 + residual of one identity block and conv1 of the next. */
+int sylph_res3_pair(sylph_ctx* ctx, const float* t2_nchw_dev, const float* x_nchw_dev, int B, int H, int W, const float* w3_host,
+                    const float* s3_host, const float* b3_host, const float* w1_host, const float* s1_host, const float* b1_host,
+                    float* y_nchw_dev, float* t1_nchw_dev);
 
 /* Kernel parity entry: one FPN lateral as sylph_backbone_fpn launches it (detectron2 FPN.forward: lateral 1x1 conv + bias, plus
  * the nearest-2x upsampled level above, fused as a residual; call site meta_one_stage_detector.py:181,273).  x (B,C,H,W) fp32 NCHW

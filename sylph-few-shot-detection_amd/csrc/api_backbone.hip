@@ -139,8 +139,30 @@ int add_conv3x3_c64(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, in
   return add_conv3x3(c, ops, L, pick_conv3_route(c, L, B, H, W, 1), B, H, W, 1, x, res, y, relu);
 }
 
-// How one bottleneck block is built (BlockRoute).  Hin x Win is X's map; with BK_IN_COMPACT `stride` is already 1.
-BlockRoute pick_block_route(const sylph_ctx* c, const sylph_ctx::Block& blk, int B, int Cin, int Hin, int Win, int stride, int mid, int cout, int flags) {
+// The size test of the pair route is the one pick_conv_route applies to the conv3 layer for conv_spw (spw_r1, api_conv.hip): at least 512
+// M tiles of 128 rows counted over the whole launch, ceil(B * H * W / 128) -- two per CU of a 256-CU part.  So with the default knob the
+// pair kernel takes exactly the launches whose conv3 would have taken conv_spw, and a smaller launch keeps conv_igemm for both layers.
+static const long PAIR_MIN_MTILES128 = 512;
+
+// conv3 + residual of `blk` and conv1 of `next` as one launch (conv_spw_pair.hip): bf16, both identity blocks 512 -> 128 -> 512 with a dense
+// conv2, stride 1, FrozenBN on both layers, an image within 32-bit byte offsets
+static bool block_pair_ok(const sylph_ctx* c, const sylph_ctx::Block& blk, const sylph_ctx::Block& next, int B, int Cin, int Hin, int Win, int stride,
+                          int mid, int cout) {
+  const int on = knob::block_pair();
+  if (!on || c->dt != DT_BF16 || blk.basic || next.basic || blk.has_sc || next.has_sc || blk.c2.groups != 1 || next.c2.groups != 1) return false;
+  if (Cin != 512 || cout != 512 || mid != 128 || stride != 1) return false;
+  const ConvLayer &c3 = blk.c3, &c1 = next.c1;
+  if (c3.Cin != 128 || c3.Cout != 512 || c3.Cout_pad != 512 || c3.KH != 1 || c3.KW != 1 || !c3.scale || !c3.shift) return false;
+  if (c1.Cin != 512 || c1.Cout != 128 || c1.Cout_pad != 128 || c1.KH != 1 || c1.KW != 1 || !c1.scale || !c1.shift) return false;
+  const long hw = (long)Hin * Win;
+  if (hw * 1024 >= (1L << 32) || (long)B * hw >= (1L << 31)) return false;
+  return on == 2 || ((long)B * hw + 127) / 128 >= PAIR_MIN_MTILES128;
+}
+
+// How one bottleneck block is built (BlockRoute).  Hin x Win is X's map; with BK_IN_COMPACT `stride` is already 1.  next: the block after
+// this one in its stage (nullptr: none, or not of interest).
+BlockRoute pick_block_route(const sylph_ctx* c, const sylph_ctx::Block& blk, int B, int Cin, int Hin, int Win, int stride, int mid, int cout, int flags,
+                            const sylph_ctx::Block* next) {
   BlockRoute r;
   r.chunk = B;
   r.s1 = c->cfg.stride_in_1x1 ? stride : 1; r.s3 = c->cfg.stride_in_1x1 ? 1 : stride;
@@ -157,6 +179,17 @@ BlockRoute pick_block_route(const sylph_ctx* c, const sylph_ctx::Block& blk, int
   r.tail_ok = fuse_id && (Hin & 1) == 0 && (Win & 1) == 0;
   if ((flags & BK_EVEN_OUT) && !r.tail_ok) {
     r.refuse = "the stride-2-output bottleneck is the fused bf16 identity block (C 256, mid 64) on a map of even height and width";
+    return r;
+  }
+  r.pair_ok = next && block_pair_ok(c, blk, *next, B, Cin, Hin, Win, stride, mid, cout);
+  r.pair_out = (flags & BK_PAIR_OUT) != 0;
+  r.pair_in = (flags & BK_PAIR_IN) != 0;
+  if (r.pair_out && !r.pair_ok) {
+    r.refuse = "the block pair launch is conv3 + residual of a bf16 identity block 512 -> 128 -> 512 followed by another such block";
+    return r;
+  }
+  if (r.pair_in && (c->dt != DT_BF16 || blk.has_sc || Cin != 512 || mid != 128 || stride != 1 || !dense2)) {
+    r.refuse = "internal: BK_PAIR_IN on a block whose conv1 the pair launch cannot have computed";
     return r;
   }
   if (!dense2) {
@@ -199,12 +232,32 @@ BlockRoute pick_block_route(const sylph_ctx* c, const sylph_ctx::Block& blk, int
   return r;
 }
 
+// The res3 block-pair launch (conv_spw_pair.hip) appended to `ops`: y = relu(bn3(c3 t2) + x) and t1 = relu(bn1(c1_next y)) on dense
+// tensors t2 [B][HW][128], x / y [B][HW][512], t1 [B][HW][128]; uploads the tile table (res3_pair_tiles.h) and, while profiling, pushes the
+// route record "spw_pair 64x512+128".  Shared by add_bottleneck (BK_PAIR_OUT) and the parity entry sylph_res3_pair.
+int add_res3_pair(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& c3, const ConvLayer& c1_next, int B, int HW, const void* t2, const void* x, void* y,
+                  void* t1) {
+  const std::vector<PairTile> pt = pair_tiles(B, HW);
+  void* ptd = nullptr;
+  RET(upload(c, &ptd, pt.data(), pt.size() * sizeof(PairTile)));
+  PairArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.t2 = t2; pa.x = x; pa.y = y; pa.t1 = t1;
+  pa.w3 = (const __bf16*)c3.w; pa.w1 = (const __bf16*)c1_next.w;
+  pa.s3 = c3.scale; pa.b3 = c3.shift; pa.s1 = c1_next.scale; pa.b1 = c1_next.shift;
+  pa.tiles = (const PairTile*)ptd; pa.n_tiles = (int)pt.size();
+  const double fl = 2.0 * (double)B * HW * (512.0 * 128 + 128.0 * 512);
+  ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_spw_kernel_pair", fl, s, [=](hipStream_t st) { return launch_conv_spw_pair(pa, st); }); });
+  if (c->prof) c->route_recs.push_back("spw_pair " + std::to_string(PAIR_TILE_ROWS) + "x512+128");
+  return 0;
+}
+
 // One ResNet bottleneck block (detectron2 BottleneckBlock: 1x1 -> 3x3 -> 1x1, FrozenBN folded, residual / projection shortcut)
 // appended to `ops` as pick_block_route says: X [B][Hin*Win][Cin] -> Y [B][Ho*Wo][cout].  t1 / t2 / sc are scratch activations of the stage.
 // Shared by build_backbone and the single-block parity entry sylph_bottleneck, so both run the same kernels.
 int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win,
-                          int stride, int mid, int cout, void* Y, const BkScratch& scr, int flags) {
-  const BlockRoute r = pick_block_route(c, blk, B, Cin, Hin, Win, stride, mid, cout, flags);
+                          int stride, int mid, int cout, void* Y, const BkScratch& scr, int flags, const sylph_ctx::Block* next) {
+  const BlockRoute r = pick_block_route(c, blk, B, Cin, Hin, Win, stride, mid, cout, flags, next);
   if (!r.refuse.empty()) return fail(r.refuse);
   const DType dt = c->dt;
   const int H1 = r.H1, W1 = r.W1, Ho = r.Ho, Wo = r.Wo;
@@ -246,8 +299,10 @@ int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block&
   }
   // the producer already dropped the rows a stride-2 1x1 skips: stride is 1 here, the routes are chosen for the strided layer
   const int route_stride = (flags & BK_IN_COMPACT) ? 2 : 0;
-  ConvOpts o1; o1.stride = r.s1; o1.relu_nch = 1 << 30; o1.route_stride = route_stride;
-  RET(add_conv(c, ops, blk.c1, X, Cin, t1, mid, image_segs(B, Hin, Win, H1, W1), o1));
+  if (!r.pair_in) {  // (else the pair launch of the block before left conv1's output in t1)
+    ConvOpts o1; o1.stride = r.s1; o1.relu_nch = 1 << 30; o1.route_stride = route_stride;
+    RET(add_conv(c, ops, blk.c1, X, Cin, t1, mid, image_segs(B, Hin, Win, H1, W1), o1));
+  }
   switch (r.conv2) {
     case Conv2Form::grouped: {
       GroupConvArgs ga;
@@ -265,6 +320,7 @@ int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block&
       RET(add_conv3x3(c, ops, blk.c2, Conv3Route{}, B, H1, W1, r.s3, t1, nullptr, t2, 1));
       break;
   }
+  if (r.pair_out) return add_res3_pair(c, ops, blk.c3, next->c1, B, Ho * Wo, t2, X, Y, t1);
   if (r.fused_sc) {
     // conv3 + projection shortcut as ONE pointwise GEMM over K = [t2 | X(strided)]: the shortcut
     // tensor is never written to / re-read from HBM
@@ -389,6 +445,7 @@ int build_backbone(sylph_ctx* c, Plan* P) {
     auto& blocks = c->stages[si];
     void* Y = nullptr;
     BkScratch scr{t1, t2, sc, &P->bk_trash};
+    bool pair_in = false;  // the block before computed this block's conv1
     for (size_t bi = 0; bi < blocks.size(); ++bi) {
       const int stride = bi == 0 ? first_stride : 1;
       Y = (Y == Ya) ? Yb : Ya;
@@ -396,9 +453,14 @@ int build_backbone(sylph_ctx* c, Plan* P) {
       const bool even_tail = knob::bk_strided_tail() && !basic && bi > 0 && bi + 1 == blocks.size() && !fpn_input && si + 1 < 4 && c->cfg.stride_in_1x1 &&
                              !c->stages[si + 1].empty() && !c->stages[si + 1][0].basic &&
                              pick_block_route(c, blocks[bi], B, Cin, Hin, Win, stride, mid, cout, 0).tail_ok;
+      // res3 identity blocks (SYLPH_BLOCK_PAIR): block bi's conv3 launch also computes block bi + 1's conv1, which is then not built
+      const sylph_ctx::Block* nextb = !basic && bi + 1 < blocks.size() ? &blocks[bi + 1] : nullptr;
+      const bool pair_out = nextb && pick_block_route(c, blocks[bi], B, Cin, Hin, Win, stride, mid, cout, 0, nextb).pair_ok;
       if (basic) RET(add_basic_block(c, ops, blocks[bi], B, X, Cin, Hin, Win, stride, cout, Y, scr));
       else RET(add_bottleneck(c, ops, blocks[bi], B, X, Cin, Hin, Win, stride, mid, cout, Y, scr,
-                              even_tail ? BK_EVEN_OUT : (bi == 0 && in_compact) ? BK_IN_COMPACT : 0));
+                              (even_tail ? BK_EVEN_OUT : (bi == 0 && in_compact) ? BK_IN_COMPACT : 0) | (pair_out ? BK_PAIR_OUT : 0) | (pair_in ? BK_PAIR_IN : 0),
+                              nextb));
+      pair_in = pair_out;
       if (bi == 0) in_compact = false;
       if (even_tail) {  // the dense output exists on demand only (sylph_export_stage)
         P->tail_even = true; P->tail_x = X;

@@ -18,6 +18,7 @@
 #include "../../include/sylph_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "res3_pair_tiles.h"
 
 using namespace sylph;
 namespace sylph_host {
@@ -82,6 +83,8 @@ SYLPH_KNOB_LIVE(conv_rw64, "SYLPH_CONV_RW64", 1)             // 0 off, 1 launche
                                                              // (= per build: one process can build both)
 SYLPH_KNOB_ONCE(fuse_bottleneck, "SYLPH_FUSE_BOTTLENECK", 1)  // 0: the res2 blocks as conv chains
 SYLPH_KNOB_ONCE(bk_strided_tail, "SYLPH_BK_STRIDED_TAIL", 1)  // 0: the last res2 block computes every position
+SYLPH_KNOB_ONCE(block_pair, "SYLPH_BLOCK_PAIR", 1)           // res3 identity blocks: conv3 + residual and the next block's conv1 in one launch
+                                                             // (conv_spw_pair.hip): 0 off, 1 launches whose conv3 would take conv_spw (512 M tiles of 128 rows), 2 any launch
 SYLPH_KNOB_ONCE(stem_kernel, "SYLPH_STEM_KERNEL", 1)         // 0: the stem through conv_igemm
 SYLPH_KNOB_ONCE(fuse_stem_pool, "SYLPH_FUSE_STEM_POOL", 1)   // 0: stem_conv + maxpool as two launches
 // streams and fusions of the FPN / head
@@ -478,6 +481,10 @@ struct BlockRoute {
   bool fused_sc = false;  // chain: conv3 and the projection shortcut are one GEMM
   bool tail_ok = false;   // the block can take BK_EVEN_OUT: a fused identity block on a map of even height and width
   int s1 = 1, s3 = 1, H1 = 0, W1 = 0, Ho = 0, Wo = 0;  // strides of conv1 / conv2, conv1's output map, the block's output map
+  // chain form, bf16, both blocks identity blocks 512 -> 128 -> 512 at stride 1 (R-50 / R-101 res3 blocks 1 .. n - 1):
+  bool pair_ok = false;   // this block and `next` can run as a pair: conv3 + residual of this one also leaves next's conv1 output in t1
+  bool pair_out = false;  // BK_PAIR_OUT was asked and granted: conv3 is the pair launch (conv_spw_pair.hip)
+  bool pair_in = false;   // BK_PAIR_IN: conv1 is not built, t1 holds its output already
 };
 
 // The stem + max-pool launches of build_backbone (pick_stem_route): stem_pool_kernel | stem_conv_kernel + maxpool | add_conv's stem loader + maxpool
@@ -489,7 +496,10 @@ struct BkScratch { void *t1, *t2, *sc; void** trash; };
 //                  res2 alone (bottleneck.hip, EVEN); anything else is refused
 //   BK_IN_COMPACT  X is the compact output of such a block and Hin x Win its size: the (first, stride-2, stride-in-1x1) block is
 //                  passed stride 1 and runs the strided block's launches on the rows it would have picked
-enum { BK_EVEN_OUT = 1, BK_IN_COMPACT = 2 };
+//   BK_PAIR_OUT    conv3 + residual of this block and conv1 of `next` as one launch that leaves next's conv1 output in scr.t1 (the stage's
+//                  t1 is free by then: this block's conv2 has read it); refused unless BlockRoute::pair_ok
+//   BK_PAIR_IN     the block before was built with BK_PAIR_OUT: scr.t1 holds this block's conv1 output, the block starts at conv2
+enum { BK_EVEN_OUT = 1, BK_IN_COMPACT = 2, BK_PAIR_OUT = 4, BK_PAIR_IN = 8 };
 
 namespace sylph_host {
 std::shared_ptr<PilCoeffs> pil_bilinear_coeffs(int in_size, int out_size);
@@ -545,9 +555,13 @@ std::vector<SegDesc> image_segs(int B, int Hin, int Win, int Hout, int Wout, int
 int ensure_pyramid(sylph_ctx* c, Plan* P);
 // the block-level pickers: pure (no allocation, no upload, no HIP call)
 Conv3Route pick_conv3_route(const sylph_ctx* c, const ConvLayer& L, int B, int H, int W, int stride);
-BlockRoute pick_block_route(const sylph_ctx* c, const sylph_ctx::Block& blk, int B, int Cin, int Hin, int Win, int stride, int mid, int cout, int flags);
+BlockRoute pick_block_route(const sylph_ctx* c, const sylph_ctx::Block& blk, int B, int Cin, int Hin, int Win, int stride, int mid, int cout, int flags,
+                            const sylph_ctx::Block* next = nullptr);
 StemRoute pick_stem_route(const sylph_ctx* c);
-int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win, int stride, int mid, int cout, void* Y, const BkScratch& scr, int flags = 0);
+int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win, int stride, int mid, int cout, void* Y, const BkScratch& scr, int flags = 0,
+                   const sylph_ctx::Block* next = nullptr);
+// the pair launch alone (add_bottleneck with BK_PAIR_OUT; the parity entry sylph_res3_pair): dense t2 [B][HW][128], x / y [B][HW][512], t1 [B][HW][128]
+int add_res3_pair(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& c3, const ConvLayer& c1_next, int B, int HW, const void* t2, const void* x, void* y, void* t1);
 int add_conv3x3_c64(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, int B, int H, int W, const void* x, const void* res, void* y, int relu);
 int add_basic_block(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win, int stride, int cout, void* Y, const BkScratch& scr);
 int build_backbone(sylph_ctx* c, Plan* P);

@@ -178,6 +178,42 @@ int sylph_bottleneck_even(sylph_ctx* c, const float* x, int B, int Cin, int H, i
   return bottleneck_entry(c, x, B, Cin, H, W, 1, mid, cout, 1, w_host, scale_host, shift_host, y, true);
 }
 
+// The res3 block-pair launch alone (conv_spw_pair.hip): t2 (B, 128, H, W), x (B, 512, H, W) ->
+// y = relu(bn3(w3 t2) + x) (B, 512, H, W) and t1 = relu(bn1(w1 y)) (B, 128, H, W); w3 (512, 128), w1 (128, 512)
+int sylph_res3_pair(sylph_ctx* c, const float* t2, const float* x, int B, int H, int W, const float* w3_host, const float* s3_host,
+                    const float* b3_host, const float* w1_host, const float* s1_host, const float* b1_host, float* y, float* t1) {
+  HIPCHK(hipSetDevice(c->device));
+  if (c->dt != DT_BF16) return fail("sylph_res3_pair: the pair kernel is bf16");
+  if (B < 1 || H < 1 || W < 1 || (long)H * W * 1024 >= (1L << 32) || (long)B * H * W >= (1L << 31)) return fail("sylph_res3_pair: bad shape");
+  if (!t2 || !x || !w3_host || !s3_host || !b3_host || !w1_host || !s1_host || !b1_host || !y || !t1) return fail("sylph_res3_pair: null argument");
+  Scratch tmp(c, Records::to_caller);
+  HostTensor h3, h1;
+  h3.shape = {512, 128, 1, 1}; h3.data.assign(w3_host, w3_host + (size_t)512 * 128);
+  h1.shape = {128, 512, 1, 1}; h1.data.assign(w1_host, w1_host + (size_t)128 * 512);
+  ConvLayer L3, L1;
+  RET(pack_conv(&tmp, {&h3}, &L3));
+  RET(pack_conv(&tmp, {&h1}, &L1));
+  if (L3.Cout_pad != 512 || L1.Cout_pad != 128) return fail("internal: sylph_res3_pair weight padding");
+  RET(upload_vec(&tmp, &L3.scale, std::vector<float>(s3_host, s3_host + 512), 512));
+  RET(upload_vec(&tmp, &L3.shift, std::vector<float>(b3_host, b3_host + 512), 512));
+  RET(upload_vec(&tmp, &L1.scale, std::vector<float>(s1_host, s1_host + 128), 128));
+  RET(upload_vec(&tmp, &L1.shift, std::vector<float>(b1_host, b1_host + 128), 128));
+  const size_t hw = (size_t)H * W, e = tmp.esz();
+  void *t2d, *xd, *yd, *t1d;
+  RET(tmp.dalloc(&t2d, B * hw * 128 * e));
+  RET(tmp.dalloc(&xd, B * hw * 512 * e));
+  RET(tmp.dalloc(&yd, B * hw * 512 * e));
+  RET(tmp.dalloc(&t1d, B * hw * 128 * e));
+  RET(import_nchw(&tmp, t2, t2d, B, 128, (int)hw));
+  RET(import_nchw(&tmp, x, xd, B, 512, (int)hw));
+  std::vector<OpFn> ops;
+  RET(add_res3_pair(&tmp, ops, L3, L1, B, (int)hw, t2d, xd, yd, t1d));
+  RET(run_ops(c, ops, "res3_pair"));
+  tmp.hand_records();
+  RET(export_nchw(&tmp, yd, y, B, 512, (int)hw));
+  return export_nchw(&tmp, t1d, t1, B, 128, (int)hw);
+}
+
 int sylph_bottleneck_grouped(sylph_ctx* c, const float* x, int B, int Cin, int H, int W, int stride, int mid, int cout, int groups,
                              const float* const* w_host, const float* const* scale_host, const float* const* shift_host, float* y) {
   if (groups < 1 || mid % groups != 0) return fail("sylph_bottleneck_grouped: mid must be a multiple of groups");

@@ -103,6 +103,18 @@ struct ConvRw64Args {
   int relu;
 };
 
+// conv_spw_pair.hip: conv3 + residual of a res3 identity block and conv1 of the next block in one launch (bf16).  Dense tensors
+// t2 [pos][128], x and y [pos][512], t1 [pos][128]; w3 [512][128], w1 [128][512] (the conv_igemm layouts); FrozenBN scale / shift fp32
+struct PairTile;  // res3_pair_tiles.h
+struct PairArgs {
+  const void *t2, *x;
+  void *y, *t1;
+  const __bf16 *w3, *w1;
+  const float *s3, *b3, *s1, *b1;
+  const PairTile* tiles;
+  int n_tiles;
+};
+
 template <typename T> struct Cvt;
 template <> struct Cvt<float> {
   static __device__ __forceinline__ float to_f(float v) { return v; }
@@ -196,6 +208,8 @@ int launch_pw_pack_weights(const void* w_igemm, void* w_pw, int Cout, int K, int
 // (stage-image weights for BN = 256, table, one PwDesc per 128-row M tile), four MFMA waves + four streaming waves per CU
 bool conv_spw_ok(DType dt, bool out_f32, const ConvArgs& a);
 int launch_conv_spw(const ConvArgs& a, hipStream_t s);
+// conv_spw_pair.hip: y = relu(bn3(w3 t2) + x) and t1 = relu(bn1(w1 y)) of a res3 block pair, one persistent block per CU
+int launch_conv_spw_pair(const PairArgs& a, hipStream_t s);
 int launch_pw_pack_table(const float* scale, const float* shift, float* out, int Cout, int BN, hipStream_t s);
 
 }  // namespace sylph

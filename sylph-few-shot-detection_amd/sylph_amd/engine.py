@@ -892,6 +892,19 @@ class Engine:
               "bottleneck_even")
         return y
 
+    def res3_pair(self, t2, x, w3, s3, b3, w1, s1, b1):
+        """The res3 block-pair launch alone (bf16): y = relu(bn3(w3 t2) + x) (B, 512, H, W) and t1 = relu(bn1(w1 y)) (B, 128, H, W) from
+        t2 (B, 128, H, W), x (B, 512, H, W), w3 (512, 128[, 1, 1]), w1 (128, 512[, 1, 1]) and their FrozenBN scale / shift."""
+        self._stream()
+        t2 = t2.to(self.device, torch.float32).contiguous()
+        x = x.to(self.device, torch.float32).contiguous()
+        B, _, H, W = x.shape
+        host = [t.detach().cpu().float().contiguous() for t in (w3, s3, b3, w1, s1, b1)]
+        y = torch.empty(B, 512, H, W, device=self.device)
+        t1 = torch.empty(B, 128, H, W, device=self.device)
+        check(self.L.sylph_res3_pair(self._ctx, _ptr(t2), _ptr(x), B, H, W, *[_ptr(t) for t in host], _ptr(y), _ptr(t1)), "res3_pair")
+        return y, t1
+
     def bottleneck_grouped(self, x, ws, scales, shifts, stride=1, groups=32):
         """One ResNeXt bottleneck block (conv2 grouped, weight (mid, mid / groups, 3, 3)) through the backbone's own launches."""
         self._stream()
