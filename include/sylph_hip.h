@@ -81,6 +81,9 @@ typedef struct sylph_config {
   int num_groups;          /* MODEL.RESNETS.NUM_GROUPS: groups of every bottleneck's 3x3 conv2 (1 = ResNet, > 1 = ResNeXt) */
   int width_per_group;     /* MODEL.RESNETS.WIDTH_PER_GROUP: conv2 channels per group in res2 (doubling per stage); the bottleneck width of
                               stage s (0 = res2) is num_groups * width_per_group << s (detectron2 build_resnet_backbone) */
+  int mobilenet;           /* MODEL.MOBILENET: the bottom-up path is AdelaiDet's MobileNetV2 (adet/modeling/backbone/mobilenet.py, width 1.0,
+                              FrozenBN): keys backbone.bottom_up.features.{0..17}.*, res2..res5 = the outputs of features 3 / 6 / 13 / 17
+                              with 24 / 32 / 96 / 320 channels; the FPN laterals read 32 / 96 / 320 channels.  MODEL.RESNETS.* is not read. */
   int cg_code_ksize;       /* CODE_GENERATOR.CLS_LAYER[2]: spatial size k of a class code, 1 or 3 (GlobalAdaptiveAvgPool2d(k_s = k),
                               code_generator.py:519-540).  A code row is 256 k^2 + 1 floats: cls_conv.reshape(-1) in (c, ky, kx) order,
                               then the bias; the query head runs it as a k x k conv with padding k / 2 (fcos.py:499-510,
@@ -305,6 +308,7 @@ int sylph_stem_maxpool(sylph_ctx* ctx, const float* x_nchw_dev, int B, int H, in
  * its own buffer (same kernels and launches, other destination) instead of the two ping-pong buffers.
  * sylph_export_stage: output of ResNet stage `stage` (2..5 = res2..res5) of the last sylph_backbone_fpn as
  * (B, C << (stage - 2), h, w) fp32 NCHW, C = 256 (64 for the BasicBlock depths 18 / 34) (detectron2 ResNet.forward outputs; call site meta_one_stage_detector.py:181,273).
+ * MobileNetV2 (cfg.mobilenet): 24 / 32 / 96 / 320 channels at strides 4 / 8 / 16 / 32.
  * res2 of a bf16 R-50 / R-101 step with STRIDE_IN_1X1 exists only at the even rows and columns res3 reads (SYLPH_BK_STRIDED_TAIL, default
  * on): for stage 2 the tap then runs the dense launch of res2's last block from that block's input, which the step leaves intact, into a
  * buffer of its own (allocated on the first such call) and exports that -- the same values, the dense shape.  It changes nothing a later
@@ -393,6 +397,25 @@ int sylph_basic_block(sylph_ctx* ctx, const float* x_nchw_dev, int B, int Cin, i
 int sylph_bottleneck_grouped(sylph_ctx* ctx, const float* x_nchw_dev, int B, int Cin, int H, int W, int stride, int mid, int cout,
                              int groups, const float* const* w_host, const float* const* scale_host, const float* const* shift_host,
                              float* y_nchw_dev);
+
+/* Kernel parity entry: ONE depthwise 3x3 conv (pad 1, stride 1 or 2, groups = C) as a MobileNetV2 block launches it (conv_dw.hip):
+ * y = relu6(scale * dwconv(clamp(x, 0, 6)) + shift), fp32 arithmetic in every mode.  The clamp of the INPUT is the ReLU6 of the layer
+ * in front, whose launch stores its result without it.  x (B,C,H,W), y (B,C,Ho,Wo) fp32 NCHW device; w_host (C,1,3,3); scale / shift host (C).
+ * C a multiple of 8. */
+int sylph_dwconv3x3(sylph_ctx* ctx, const float* x_nchw_dev, int B, int C, int H, int W, int stride, const float* w_host,
+                    const float* scale_host, const float* shift_host, float* y_nchw_dev);
+/* The channel count a MobileNetV2 tensor of C channels is computed with: C rounded up to the K slice of the implicit-GEMM kernels
+ * (64 in SYLPH_BF16, 32 in the fp32 modes).  The pad channels are exactly zero in every tensor. */
+int sylph_mbv2_padded_channels(sylph_ctx* ctx, int C);
+/* Kernel parity entry: ONE MobileNetV2 InvertedResidual block (AdelaiDet mobilenet.py; call site meta_one_stage_detector.py:181,273)
+ * through the launches sylph_backbone_fpn makes for it: t = 6: 1x1 expand Cin -> 6 Cin + FrozenBN + ReLU6, depthwise 3x3 (stride) +
+ * FrozenBN + ReLU6, 1x1 project -> Cout + FrozenBN, + x when stride == 1 and Cin == Cout, nothing after the add; t = 1: no expand.
+ * w_host / scale_host / shift_host[3] = expand (t Cin, Cin, 1, 1) or NULL (t = 1), depthwise (t Cin, 1, 3, 3), project (Cout, t Cin, 1, 1).
+ * x (B,Cin,H,W) fp32 NCHW device; y (B,y_channels,Ho,Wo) with y_channels = Cout, or sylph_mbv2_padded_channels(Cout) to see the pad
+ * channels too. */
+int sylph_mbv2_block(sylph_ctx* ctx, const float* x_nchw_dev, int B, int Cin, int H, int W, int t, int Cout, int stride,
+                     const float* const* w_host, const float* const* scale_host, const float* const* shift_host, int y_channels,
+                     float* y_nchw_dev);
 
 /* Bytes of device memory currently held by the context (weights + workspace). */
 int64_t sylph_device_bytes(sylph_ctx* ctx);

@@ -371,12 +371,154 @@ StemRoute pick_stem_route(const sylph_ctx* c) {
   return knob::fuse_stem_pool() ? StemRoute::fused_pool : StemRoute::stem_conv;
 }
 
-int build_backbone(sylph_ctx* c, Plan* P) {
-  if (P->backbone_built) return 0;
-  if (!c->has_backbone) return fail("backbone weights were not loaded");
+// One depthwise 3x3 conv (pad 1) + FrozenBN + ReLU6 on the ReLU6 of its input (conv_dw.hip) appended to `ops`: channels [0, C) of
+// x [B][H * W][ld] -> y [B][Ho * Wo][ld]
+int add_dwconv3x3(sylph_ctx* c, std::vector<OpFn>& ops, const float* w, const float* scale, const float* shift, int B, int C, int ld, int H, int W,
+                  int stride, const void* x, void* y) {
+  if (C < 8 || (C & 7) || ld < C || (ld & 7) || (stride != 1 && stride != 2)) return fail("internal: dwconv3x3 needs C % 8 == 0, ld % 8 == 0 and stride 1 or 2");
+  DwConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.y = y; a.w = w; a.scale = scale; a.shift = shift;
+  a.B = B; a.C = C; a.ld = ld; a.H = H; a.W = W; a.Ho = (H - 1) / stride + 1; a.Wo = (W - 1) / stride + 1; a.stride = stride;
+  const double fl = 2.0 * (double)B * a.Ho * a.Wo * C * 9.0;
+  const DType dt = c->dt;
+  ops.push_back([=](hipStream_t s) { return timed_op(c, "dwconv3x3_kernel", fl, s, [=](hipStream_t st) { return launch_dwconv3x3(dt, a, st); }); });
+  return 0;
+}
+
+// One MobileNetV2 InvertedResidual block (AdelaiDet mobilenet.py) as a chain of launches:
+//   h1 = bn(expand 1x1 (x))                      add_conv, NO activation: the depthwise kernel clamps on load (t == 1: no expand, h1 = x --
+//                                                x is then the ReLU6 output of features.0, which the clamp leaves as it is)
+//   h2 = relu6(bn(dw 3x3 (relu6(h1))))           conv_dw.hip
+//   y  = bn(project 1x1 (h2)) [+ x]              add_conv with the residual input; nothing after the add
+// The three bf16 rounding points are h1, h2 and y.
+static Mbv2Args mbv2_args(const sylph_ctx::MbBlock& blk, int B, const void* X, int Hin, int Win, void* Y) {
+  Mbv2Args a;
+  memset(&a, 0, sizeof(a));
+  a.x = X; a.y = Y;
+  a.w1 = blk.t != 1 ? blk.fw1 : nullptr; a.w2 = blk.fw2;
+  a.s1 = blk.exp.scale; a.b1 = blk.exp.shift; a.wd = blk.dw_w; a.sd = blk.dw_scale; a.bd = blk.dw_shift; a.s2 = blk.proj.scale; a.b2 = blk.proj.shift;
+  a.B = B; a.H = Hin; a.W = Win; a.Ho = (Hin - 1) / blk.stride + 1; a.Wo = (Win - 1) / blk.stride + 1; a.stride = blk.stride;
+  a.cin_p = blk.cin_p; a.cin_ld = blk.cin_ld; a.hid_p = blk.hid_p; a.cout_p = blk.cout_p; a.cout_ld = blk.cout_ld; a.residual = blk.residual();
+  return a;
+}
+
+// Which launches run one InvertedResidual block.  fp32 and f32s always take the chain.  bf16: SYLPH_MBV2_FUSED 0 = chain, 2 = the
+// one-launch kernel wherever it can run, 1 = the block shapes (cin, t, cout, stride) at which it beat the chain in the per-block
+// measurement (profiles/mobilenet_layers.txt); every other shape takes the chain.
+Mbv2Route pick_mbv2_route(const sylph_ctx* c, const sylph_ctx::MbBlock& blk, int B, int Hin, int Win) {
+  const int k = knob::mbv2_fused();
+  if (c->dt != DT_BF16 || k <= 0 || !blk.fw2 || (blk.t != 1 && !blk.fw1)) return Mbv2Route::chain;
+  if (!conv_mbv2_can_run(mbv2_args(blk, B, blk.fw2, Hin, Win, blk.fw2))) return Mbv2Route::chain;  // (the tensors' addresses play no part)
+  if (k >= 2) return Mbv2Route::fused;
+  // B = 16 at the 800 x 1344 map sizes, kernel time chain / fused: features.1 0.83 / 0.75 ms, features.3 0.87 / 0.57 ms, features.5-6
+  // 0.21 / 0.16 ms; (64, 6, 64, 1) ties (0.10 / 0.10) and every other shape loses (stride 2: 0.79 / 1.64 ms at features.2)
+  static const int pays[][4] = {{32, 1, 16, 1}, {24, 6, 24, 1}, {32, 6, 32, 1}};
+  for (auto& s : pays)
+    if (s[0] == blk.cin && s[1] == blk.t && s[2] == blk.cout && s[3] == blk.stride) return Mbv2Route::fused;
+  return Mbv2Route::chain;
+}
+
+int add_mbv2_block(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::MbBlock& blk, int B, const void* X, int Hin, int Win, void* Y, void* h1, void* h2) {
+  const int Ho = (Hin - 1) / blk.stride + 1, Wo = (Win - 1) / blk.stride + 1;
+  if (pick_mbv2_route(c, blk, B, Hin, Win) == Mbv2Route::fused) {
+    const Mbv2Args a = mbv2_args(blk, B, X, Hin, Win, Y);
+    const double fl = 2.0 * ((double)B * Hin * Win * (blk.t != 1 ? (double)blk.cin * blk.cin * blk.t : 0.0) + (double)B * Ho * Wo * blk.cin * blk.t * (9.0 + blk.cout));
+    ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_mbv2_kernel", fl, s, [=](hipStream_t st) { return launch_conv_mbv2(a, st); }); });
+    return 0;
+  }
+  // conv_igemm addresses its operands with 31-bit element offsets: a batch whose largest tensor of this block passes that is built as
+  // several chains over runs of images, all through the same h1 / h2 (the launches of one op list run in order)
+  const size_t per_img = std::max((size_t)Hin * Win * std::max(blk.cin_ld, blk.t != 1 ? blk.hid_ld : 0), (size_t)Ho * Wo * std::max(blk.hid_ld, blk.cout_ld));
+  const int chunk = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, (size_t)0x7fffffff / per_img));
+  if (chunk < B) {
+    const size_t e = c->esz();
+    for (int b0 = 0; b0 < B; b0 += chunk)
+      RET(add_mbv2_block(c, ops, blk, std::min(chunk, B - b0), (const char*)X + (size_t)b0 * Hin * Win * blk.cin_ld * e, Hin, Win,
+                         (char*)Y + (size_t)b0 * Ho * Wo * blk.cout_ld * e, h1, h2));
+    return 0;
+  }
+  const void* dw_in = X;
+  if (blk.t != 1) {
+    RET(add_conv(c, ops, blk.exp, X, blk.cin_ld, h1, blk.hid_ld, image_segs(B, Hin, Win, Hin, Win), ConvOpts()));
+    dw_in = h1;
+  }
+  // (t == 1: hidden = input, read at the input's pitch and written at the same one: cin_ld == hid_ld)
+  RET(add_dwconv3x3(c, ops, blk.dw_w, blk.dw_scale, blk.dw_shift, B, blk.hid_p, blk.hid_ld, Hin, Win, blk.stride, dw_in, h2));
+  ConvOpts o3;
+  if (blk.residual()) { o3.res = X; o3.res_ld = blk.cin_ld; o3.res_mode = 1; }
+  return add_conv(c, ops, blk.proj, h2, blk.hid_ld, Y, blk.cout_ld, image_segs(B, Ho, Wo, Ho, Wo), o3);
+}
+
+// What a bottom-up path hands to the FPN: res2..res5 as dense images [B][h * w][ld], c logical channels
+struct Trunk {
+  const void* out[4] = {nullptr, nullptr, nullptr, nullptr};
+  int h[4] = {0, 0, 0, 0}, w[4] = {0, 0, 0, 0}, c[4] = {0, 0, 0, 0}, ld[4] = {0, 0, 0, 0};
+};
+
+// MobileNetV2 bottom-up (cfg.mobilenet): features.0 on the normalised batch, then the 17 blocks.  res2..res5 (features 3 / 6 / 13 / 17) get
+// buffers of their own (the parity taps and the laterals read them after the step); every other block output goes to two ping-pong buffers.
+static int build_mbv2_trunk(sylph_ctx* c, Plan* P, Trunk* T) {
   const int B = P->B, H = P->H, W = P->W;
   const size_t e = c->esz();
-  RET(ensure_pyramid(c, P));
+  if (c->mb_blocks.size() != 17 || !c->mb_stem_w) return fail("internal: MobileNetV2 weights");
+  RET(c->dalloc(&P->x0, (size_t)B * H * W * 4 * e));
+  RET(c->dalloc((void**)&P->img_desc_dev, sizeof(ImageDesc) * B));
+  HIPCHK(hipHostMalloc((void**)&P->img_desc_host, sizeof(ImageDesc) * B));
+  auto& ops = P->backbone_ops;
+  int Hin = (H - 1) / 2 + 1, Win = (W - 1) / 2 + 1;
+  // sizes of the shared buffers: the largest block output that is not a stage output, the largest expand / depthwise outputs
+  size_t n_y = 0, n_h1 = 0, n_h2 = 0;
+  {
+    int h = Hin, w = Win;
+    for (size_t i = 0; i < c->mb_blocks.size(); ++i) {
+      const auto& blk = c->mb_blocks[i];
+      const int ho = (h - 1) / blk.stride + 1, wo = (w - 1) / blk.stride + 1;
+      if (blk.t != 1) n_h1 = std::max(n_h1, (size_t)B * h * w * blk.hid_ld);
+      n_h2 = std::max(n_h2, (size_t)B * ho * wo * blk.hid_ld);
+      n_y = std::max(n_y, (size_t)B * ho * wo * blk.cout_ld);
+      h = ho; w = wo;
+    }
+  }
+  const int c0 = c->mb_blocks[0].cin_p, ld0 = c->mb_blocks[0].cin_ld;
+  void *s0, *Ya, *Yb, *h1, *h2;
+  RET(c->dalloc(&s0, (size_t)B * Hin * Win * ld0 * e));
+  RET(c->dalloc(&Ya, n_y * e));
+  RET(c->dalloc(&Yb, n_y * e));
+  RET(c->dalloc(&h1, n_h1 * e));
+  RET(c->dalloc(&h2, n_h2 * e));
+  {
+    MbStemArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.x = P->x0; sa.y = s0; sa.w = c->mb_stem_w; sa.scale = c->mb_stem_scale; sa.shift = c->mb_stem_shift;
+    sa.B = B; sa.C = c0; sa.ld = ld0; sa.H = H; sa.W = W; sa.Ho = Hin; sa.Wo = Win;
+    const double fl = 2.0 * (double)B * Hin * Win * 32.0 * 27.0;
+    const DType dt = c->dt;
+    ops.push_back([=](hipStream_t s) { return timed_op(c, "mbv2_stem_kernel", fl, s, [=](hipStream_t st) { return launch_mbv2_stem(dt, sa, st); }); });
+  }
+  P->stem_takes_raw = false;  // sylph_preprocess writes x0
+  const void* X = s0;
+  void* Y = nullptr;
+  for (size_t i = 0; i < c->mb_blocks.size(); ++i) {
+    const auto& blk = c->mb_blocks[i];
+    const int Ho = (Hin - 1) / blk.stride + 1, Wo = (Win - 1) / blk.stride + 1;
+    const int si = i == 2 ? 0 : i == 5 ? 1 : i == 12 ? 2 : i == 16 ? 3 : -1;  // features 3 / 6 / 13 / 17
+    void* dst;
+    if (si >= 0) RET(c->dalloc(&dst, (size_t)B * Ho * Wo * blk.cout_ld * e));
+    else dst = Y = (Y == Ya) ? Yb : Ya;
+    RET(add_mbv2_block(c, ops, blk, B, X, Hin, Win, dst, h1, h2));
+    X = dst; Hin = Ho; Win = Wo;
+    if (si >= 0) { T->out[si] = dst; T->h[si] = Ho; T->w[si] = Wo; T->c[si] = blk.cout; T->ld[si] = blk.cout_ld; }
+  }
+  for (int si = 0; si < 4; ++si) {
+    P->stage_out[si] = T->out[si]; P->stage_h[si] = T->h[si]; P->stage_w[si] = T->w[si]; P->stage_c[si] = T->c[si]; P->stage_ld[si] = T->ld[si];
+  }
+  return 0;
+}
+
+static int build_resnet_trunk(sylph_ctx* c, Plan* P, Trunk* T) {
+  const int B = P->B, H = P->H, W = P->W;
+  const size_t e = c->esz();
   RET(c->dalloc(&P->x0, (size_t)B * H * W * 4 * e));
   const int H2 = (H - 1) / 2 + 1, W2 = (W - 1) / 2 + 1;
   const int H4 = (H2 - 1) / 2 + 1, W4 = (W2 - 1) / 2 + 1;
@@ -475,6 +617,23 @@ int build_backbone(sylph_ctx* c, Plan* P) {
     if (in_compact) continue;  // (P->stage_h / _w / _c hold the dense shape; P->stage_out[si] stays empty)
     P->stage_out[si] = X; P->stage_h[si] = Hin; P->stage_w[si] = Win; P->stage_c[si] = cout;
   }
+  for (int si = 0; si < 4; ++si) { T->out[si] = stage_out[si]; T->h[si] = stage_h[si]; T->w[si] = stage_w[si]; T->c[si] = T->ld[si] = stage_c[si]; }
+  return 0;
+}
+
+int build_backbone(sylph_ctx* c, Plan* P) {
+  if (P->backbone_built) return 0;
+  if (!c->has_backbone) return fail("backbone weights were not loaded");
+  const int B = P->B;
+  const size_t e = c->esz();
+  RET(ensure_pyramid(c, P));
+  Trunk T;
+  if (c->cfg.mobilenet) RET(build_mbv2_trunk(c, P, &T));
+  else RET(build_resnet_trunk(c, P, &T));
+  auto& ops = P->backbone_ops;
+  const DType dt = c->dt;
+  const void* const* stage_out = T.out;
+  const int *stage_h = T.h, *stage_w = T.w, *stage_ld = T.ld;
   // FPN (res3..res5 -> p3..p5), top-down with nearest 2x upsample fused as a residual, then P6/P7
   // Small batches: after lateral5 the FPN is two independent chains of small launches -- {output5, P6, relu, P7} and {lateral4, output4,
   // lateral3, output3} -- so the first one runs on the context's side stream between a fork and a join (as the bbox tower does,
@@ -485,7 +644,7 @@ int build_backbone(sylph_ctx* c, Plan* P) {
   std::vector<OpFn> side_ops;
   void* lat[3] = {nullptr, nullptr, nullptr};
   for (int k = 2; k >= 0; --k) {
-    const int si = k + 1, h = stage_h[si], w = stage_w[si], cin = stage_c[si];
+    const int si = k + 1, h = stage_h[si], w = stage_w[si], cin = stage_ld[si];
     if (h != P->hl[k] || w != P->wl[k]) return fail("internal: level geometry mismatch");
     RET(c->dalloc(&lat[k], (size_t)B * h * w * 256 * e));
     ConvOpts ol;

@@ -164,6 +164,7 @@ void sylph_config_default(sylph_config* cfg) {
   cfg->tower_deformable = 0;
   cfg->num_groups = 1; cfg->width_per_group = 64;
   cfg->cg_code_ksize = 1;
+  cfg->mobilenet = 0;
 }
 
 const char* sylph_last_error(void) { return g_err.c_str(); }
@@ -219,11 +220,12 @@ int sylph_set_config(sylph_ctx* c, const sylph_config* cfg) {
   if (c->finalized) return fail("sylph_set_config must precede sylph_finalize_weights");
   if (cfg->nlevels != 5) return fail("only the 5-level FCOS pyramid (p3..p7) is supported");
   const bool basic = cfg->resnet_depth == 18 || cfg->resnet_depth == 34;  // BasicBlock ResNets (stage widths 64 << s)
-  if (!basic && cfg->resnet_depth != 50 && cfg->resnet_depth != 101 && cfg->resnet_depth != 152)
+  const bool mb = cfg->mobilenet != 0;  // MobileNetV2 bottom-up: MODEL.RESNETS.* is not read
+  if (!mb && !basic && cfg->resnet_depth != 50 && cfg->resnet_depth != 101 && cfg->resnet_depth != 152)
     return fail("MODEL.RESNETS.DEPTH must be 18, 34, 50, 101 or 152");
-  if (basic && (cfg->num_groups != 1 || cfg->width_per_group != 64))
+  if (!mb && basic && (cfg->num_groups != 1 || cfg->width_per_group != 64))
     return fail("MODEL.RESNETS.DEPTH 18 / 34 (BasicBlock) needs NUM_GROUPS 1 and WIDTH_PER_GROUP 64");
-  if (cfg->num_groups != 1 || cfg->width_per_group != 64) {  // ResNeXt: what conv_group.hip covers (sylph_amd/engine.py config_from_cfg)
+  if (!mb && (cfg->num_groups != 1 || cfg->width_per_group != 64)) {  // ResNeXt: what conv_group.hip covers (sylph_amd/engine.py config_from_cfg)
     bool ok = cfg->num_groups >= 1 && cfg->width_per_group >= 1 && (cfg->num_groups * cfg->width_per_group) % 64 == 0;
     for (int s = 0; s < 4 && ok; ++s) {
       const int w = cfg->width_per_group << s;

@@ -87,6 +87,8 @@ SYLPH_KNOB_ONCE(block_pair, "SYLPH_BLOCK_PAIR", 1)           // res3 identity bl
                                                              // (conv_spw_pair.hip): 0 off, 1 launches whose conv3 would take conv_spw (512 M tiles of 128 rows), 2 any launch
 SYLPH_KNOB_ONCE(stem_kernel, "SYLPH_STEM_KERNEL", 1)         // 0: the stem through conv_igemm
 SYLPH_KNOB_ONCE(fuse_stem_pool, "SYLPH_FUSE_STEM_POOL", 1)   // 0: stem_conv + maxpool as two launches
+SYLPH_KNOB_LIVE(mbv2_fused, "SYLPH_MBV2_FUSED", 1)           // MobileNetV2 blocks as one conv_mbv2 launch, bf16: 0 off, 1 the block shapes where it beats
+                                                             // the three-launch chain (pick_mbv2_route), 2 wherever it can run; per pick (= per build)
 // streams and fusions of the FPN / head
 SYLPH_KNOB_ONCE(head_streams, "SYLPH_HEAD_STREAMS", 1)       // 0 one stream, 1 two for small batches (FPN top and bbox tower on the side stream), 2 always two
 SYLPH_KNOB_ONCE(gn_fuse, "SYLPH_GN_FUSE", 1)                 // 0: every tower GroupNorm as its own apply pass
@@ -152,6 +154,20 @@ struct sylph_ctx {
     bool basic = false;  // detectron2 BasicBlock (R-18 / R-34): c1, c2 are 3x3 convs, no c3, a shortcut only where the width changes
   };
   std::vector<std::vector<Block>> stages;  // res2..res5
+  // MobileNetV2 bottom-up (cfg.mobilenet; api_weights.hip make_mbv2_block): one InvertedResidual block.  Every channel count is computed
+  // padded to mbv2_pad() channels -- zero weights, scales and shifts, so pad channels are exactly zero in every tensor -- in rows of
+  // mbv2_ld() elements.
+  struct MbBlock {
+    int cin = 0, t = 1, cout = 0, stride = 1;  // logical: hidden = t * cin; the input is added when stride == 1 && cin == cout
+    int cin_p = 0, hid_p = 0, cout_p = 0;      // channels as computed (mbv2_pad)
+    int cin_ld = 0, hid_ld = 0, cout_ld = 0;   // row pitch of the input, the two hidden tensors and the output (mbv2_ld)
+    ConvLayer exp, proj;                       // 1x1 expand (t != 1) and 1x1 linear projection, FrozenBN folded
+    float *dw_w = nullptr, *dw_scale = nullptr, *dw_shift = nullptr;  // depthwise 3x3: fp32 [3][3][hid_p] (bf16 mode: bf16-rounded values), [hid_p]
+    bf16_t *fw1 = nullptr, *fw2 = nullptr;     // bf16 mode, for conv_mbv2.hip: expand [hid_p][cin_p] (t != 1) and projection [cout_p][hid_p], row-major
+    bool residual() const { return stride == 1 && cin == cout; }
+  };
+  std::vector<MbBlock> mb_blocks;              // features.1 .. features.17
+  float *mb_stem_w = nullptr, *mb_stem_scale = nullptr, *mb_stem_shift = nullptr;  // features.0: fp32 [3][3][4][32], [32]
   ConvLayer fpn_lat[3], fpn_out[3], p6, p7;  // index 0..2 = stage 3..5
   std::vector<ConvLayer> cls_tower, box_tower, share_tower;  // share_tower: MODEL.FCOS.NUM_SHARE_CONVS layers in front of both
   std::vector<GNLayer> share_gn;
@@ -317,6 +333,7 @@ struct Plan {
   void* tail_dense = nullptr;
   std::vector<OpFn> tail_dense_ops;
   int stage_h[4] = {0, 0, 0, 0}, stage_w[4] = {0, 0, 0, 0}, stage_c[4] = {0, 0, 0, 0};
+  int stage_ld[4] = {0, 0, 0, 0};  // row pitch of stage_out where it is not stage_c (MobileNetV2: padded channels); 0 = stage_c
   std::vector<const void*> tap_out[2];      // [cls | bbox][layer]: conv output [rows][256] (pre-GroupNorm when tap_coef is set)
   std::vector<const float2*> tap_coef[2];   // [cls | bbox][layer]: (a, b) per (segment, channel), nullptr if applied in place
   std::vector<OpFn> backbone_ops, head_ops;
@@ -487,6 +504,10 @@ struct BlockRoute {
   bool pair_in = false;   // BK_PAIR_IN: conv1 is not built, t1 holds its output already
 };
 
+// How add_mbv2_block builds one InvertedResidual block (pick_mbv2_route): chain = expand (add_conv) -> dwconv3x3 -> project (add_conv);
+// fused = ONE conv_mbv2 launch, bf16
+enum class Mbv2Route { chain, fused };
+
 // The stem + max-pool launches of build_backbone (pick_stem_route): stem_pool_kernel | stem_conv_kernel + maxpool | add_conv's stem loader + maxpool
 enum class StemRoute { fused_pool, stem_conv, igemm };
 
@@ -530,6 +551,10 @@ int make_c3sc(sylph_ctx* c, const HostTensor& w3, const float* s3, const float* 
 int make_gn(sylph_ctx* c, const std::string& name, GNLayer* G);
 int upload_f32(sylph_ctx* c, const float** dev, const HostTensor* t, const std::string& what, size_t expect = 0);
 int make_lin(sylph_ctx* c, const std::string& name, sylph_ctx::Lin* L);
+// a MobileNetV2 block from host tensors: w / scale / shift [3] = expand (nullptr for t == 1), depthwise (hid, 1, 3, 3), project
+int make_mbv2_block(sylph_ctx* c, int cin, int t, int cout, int stride, const HostTensor* const* w, const float* const* scale, const float* const* shift,
+                    sylph_ctx::MbBlock* blk);
+int make_dw_table(sylph_ctx* c, const HostTensor& w, int C, int Cp, const float* scale, const float* shift, float** w_dev, float** scale_dev, float** shift_dev);
 int make_ln(sylph_ctx* c, const std::string& name, GNLayer* G);
 bool has_prefix(sylph_ctx* c, const std::string& p);
 // api_conv.hip
@@ -564,6 +589,19 @@ int add_bottleneck(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block&
 int add_res3_pair(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& c3, const ConvLayer& c1_next, int B, int HW, const void* t2, const void* x, void* y, void* t1);
 int add_conv3x3_c64(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, int B, int H, int W, const void* x, const void* res, void* y, int relu);
 int add_basic_block(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::Block& blk, int B, const void* X, int Cin, int Hin, int Win, int stride, int cout, void* Y, const BkScratch& scr);
+// MobileNetV2 (cfg.mobilenet): channels as stored -- C rounded up to the K slice of the implicit-GEMM kernels (64 bf16, 32 fp32 modes)
+inline int mbv2_pad(const sylph_ctx* c, int C) { const int q = c->dt == DT_BF16 ? 64 : 32; return (C + q - 1) / q * q; }
+// ... and the row pitch of such a tensor: the Cout_pad pack_conv gives a layer of mbv2_pad(C) outputs.  conv_igemm launches Cout_pad / BN
+// N tiles and its bf16 epilogue stores whole tiles whenever Cout % BN == 0, so a conv output needs rows of Cout_pad elements; the
+// channels between mbv2_pad(C) and the pitch are never read.
+inline int mbv2_ld(const sylph_ctx* c, int C) { const int p = mbv2_pad(c, C), q = p >= 128 ? 128 : (p > 32 ? 64 : 32); return (p + q - 1) / q * q; }
+// One InvertedResidual block appended to `ops`: X [B][Hin * Win][cin_ld] -> Y [B][Ho * Wo][cout_ld]; h1 (the expand output, B * Hin * Win *
+// hid_ld elements; unused when t == 1) and h2 (the depthwise output, B * Ho * Wo * hid_ld) are scratch.  Shared by build_backbone and
+// the parity entry sylph_mbv2_block.
+Mbv2Route pick_mbv2_route(const sylph_ctx* c, const sylph_ctx::MbBlock& blk, int B, int Hin, int Win);
+int add_mbv2_block(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::MbBlock& blk, int B, const void* X, int Hin, int Win, void* Y, void* h1, void* h2);
+int add_dwconv3x3(sylph_ctx* c, std::vector<OpFn>& ops, const float* w, const float* scale, const float* shift, int B, int C, int ld, int H, int W,
+                  int stride, const void* x, void* y);
 int build_backbone(sylph_ctx* c, Plan* P);
 // api_head.hip
 std::vector<SegDesc> pyramid_segs(sylph_ctx* c, Plan* P);

@@ -96,6 +96,10 @@ int sylph_export_stage(sylph_ctx* c, int stage, float* out) {
     RET(run_ops(c, P->tail_dense_ops, "res2 tap"));
     src = P->tail_dense;
   }
+  if (const int ld = P->stage_ld[si]; ld && ld != C) {  // (MobileNetV2: rows of ld stored channels, the first C are the stage's)
+    for (int b = 0; b < P->B; ++b) KCHK(launch_export_nchw(c->dt, src, out + (size_t)b * C * hw, C, hw, b * hw, ld, c->stream), "export stage");
+    return 0;
+  }
   return export_nchw(c, src, out, P->B, C, hw, "export stage");
 }
 
@@ -308,6 +312,69 @@ int sylph_basic_block(sylph_ctx* c, const float* x, int B, int Cin, int H, int W
   RET(run_ops(c, ops, "basic_block"));
   tmp.hand_records();
   return export_nchw(&tmp, yout, y, B, cout, Ho * Wo);
+}
+
+int sylph_mbv2_padded_channels(sylph_ctx* c, int C) { return mbv2_pad(c, C); }
+
+int sylph_dwconv3x3(sylph_ctx* c, const float* x, int B, int C, int H, int W, int stride, const float* w_host, const float* scale_host,
+                    const float* shift_host, float* y) {
+  HIPCHK(hipSetDevice(c->device));
+  if (B < 1 || C < 8 || (C & 7) || H < 1 || W < 1 || (stride != 1 && stride != 2) || !x || !w_host || !scale_host || !shift_host || !y)
+    return fail("sylph_dwconv3x3: bad arguments (C a multiple of 8, stride 1 or 2)");
+  Scratch tmp(c, Records::to_caller);
+  HostTensor hw;
+  hw.shape = {C, 1, 3, 3};
+  hw.data.assign(w_host, w_host + (size_t)C * 9);
+  float *wd, *sd, *hd;
+  RET(make_dw_table(&tmp, hw, C, C, scale_host, shift_host, &wd, &sd, &hd));
+  const size_t e = tmp.esz();
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  void *xin, *yout;
+  RET(tmp.dalloc(&xin, (size_t)B * H * W * C * e));
+  RET(tmp.dalloc(&yout, (size_t)B * Ho * Wo * C * e));
+  RET(import_nchw(&tmp, x, xin, B, C, H * W));
+  std::vector<OpFn> ops;
+  RET(add_dwconv3x3(&tmp, ops, wd, sd, hd, B, C, C, H, W, stride, xin, yout));
+  RET(run_ops(c, ops, "dwconv3x3"));
+  tmp.hand_records();
+  return export_nchw(&tmp, yout, y, B, C, Ho * Wo);
+}
+
+int sylph_mbv2_block(sylph_ctx* c, const float* x, int B, int Cin, int H, int W, int t, int Cout, int stride, const float* const* w_host,
+                     const float* const* scale_host, const float* const* shift_host, int y_channels, float* y) {
+  HIPCHK(hipSetDevice(c->device));
+  if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || (t != 1 && t != 6) || (stride != 1 && stride != 2) || !x || !y || !w_host || !scale_host || !shift_host)
+    return fail("sylph_mbv2_block: bad arguments (t 1 or 6, stride 1 or 2)");
+  if ((t != 1) != (w_host[0] != nullptr) || !w_host[1] || !w_host[2]) return fail("sylph_mbv2_block: an expand conv exactly when t != 1");
+  for (int i = t != 1 ? 0 : 1; i < 3; ++i)
+    if (!scale_host[i] || !shift_host[i]) return fail("sylph_mbv2_block: a FrozenBN scale and shift for every conv of the block");
+  const int hid = Cin * t;
+  Scratch tmp(c, Records::to_caller);
+  HostTensor hw[3];
+  const HostTensor* hp[3] = {nullptr, &hw[1], &hw[2]};
+  if (t != 1) { hw[0].shape = {hid, Cin, 1, 1}; hw[0].data.assign(w_host[0], w_host[0] + (size_t)hid * Cin); hp[0] = &hw[0]; }
+  hw[1].shape = {hid, 1, 3, 3}; hw[1].data.assign(w_host[1], w_host[1] + (size_t)hid * 9);
+  hw[2].shape = {Cout, hid, 1, 1}; hw[2].data.assign(w_host[2], w_host[2] + (size_t)Cout * hid);
+  sylph_ctx::MbBlock blk;
+  RET(make_mbv2_block(&tmp, Cin, t, Cout, stride, hp, scale_host, shift_host, &blk));
+  if (y_channels != Cout && y_channels != blk.cout_p) return fail("sylph_mbv2_block: y_channels must be Cout or its padded count");
+  const size_t e = tmp.esz();
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  const size_t n_x = (size_t)B * H * W * blk.cin_ld * e;
+  void *xin, *yout, *h1, *h2;
+  RET(tmp.dalloc(&xin, n_x));
+  RET(tmp.dalloc(&yout, (size_t)B * Ho * Wo * blk.cout_ld * e));
+  RET(tmp.dalloc(&h1, (size_t)B * H * W * blk.hid_ld * e));
+  RET(tmp.dalloc(&h2, (size_t)B * Ho * Wo * blk.hid_ld * e));
+  HIPCHK(hipMemsetAsync(xin, 0, n_x, c->stream));  // the pad channels of the input are zero, as every producer leaves them
+  for (int b = 0; b < B; ++b) KCHK(launch_import_nchw(c->dt, x + (size_t)b * Cin * H * W, xin, Cin, H * W, b * H * W, blk.cin_ld, c->stream), "import");
+  std::vector<OpFn> ops;
+  RET(add_mbv2_block(&tmp, ops, blk, B, xin, H, W, yout, h1, h2));
+  RET(run_ops(c, ops, "mbv2_block"));
+  tmp.hand_records();
+  for (int b = 0; b < B; ++b)
+    KCHK(launch_export_nchw(c->dt, yout, y + (size_t)b * y_channels * Ho * Wo, y_channels, Ho * Wo, b * Ho * Wo, blk.cout_ld, c->stream), "export");
+  return 0;
 }
 
 int sylph_fpn_lateral(sylph_ctx* c, const float* x, int B, int C, int H, int W, const float* w_host, const float* bias_host, const float* top,

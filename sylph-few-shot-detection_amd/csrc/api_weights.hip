@@ -213,6 +213,146 @@ int make_ln(sylph_ctx* c, const std::string& name, GNLayer* G) {
   return 0;
 }
 
+// ---- MobileNetV2 (cfg.mobilenet) ----------------------------------------------------------------------------------------------------
+static std::string shape_str(const HostTensor& t) {
+  std::string got;
+  for (size_t i = 0; i < t.shape.size(); ++i) got += (i ? ", " : "") + std::to_string(t.shape[i]);
+  return "(" + got + ")";
+}
+
+// a dense 1x1 conv (cout, cin, 1, 1) stored as (cout_p, cin_p): zero rows / columns, zero scale and shift on the pad channels
+static int make_padded_1x1(sylph_ctx* c, const HostTensor& w, int cout, int cin, int cout_p, int cin_p, const float* scale, const float* shift, ConvLayer* L) {
+  HostTensor hp;
+  hp.shape = {cout_p, cin_p, 1, 1};
+  hp.data.assign((size_t)cout_p * cin_p, 0.f);
+  for (int n = 0; n < cout; ++n)
+    for (int k = 0; k < cin; ++k) hp.data[(size_t)n * cin_p + k] = w.data[(size_t)n * cin + k];
+  RET(pack_conv(c, {&hp}, L));
+  if (scale) RET(upload_vec(c, &L->scale, std::vector<float>(scale, scale + cout), L->Cout_pad));  // (nullptr: a bias conv, as make_conv_bias packs it)
+  RET(upload_vec(c, &L->shift, std::vector<float>(shift, shift + cout), L->Cout_pad));
+  return 0;
+}
+
+// depthwise weights (C, 1, 3, 3) -> fp32 [3][3][Cp] (bf16 mode: the values a bf16 weight holds), scale / shift [Cp], zeros on the pad channels
+int make_dw_table(sylph_ctx* c, const HostTensor& w, int C, int Cp, const float* scale, const float* shift, float** w_dev, float** scale_dev, float** shift_dev) {
+  std::vector<float> t((size_t)9 * Cp, 0.f);
+  for (int ch = 0; ch < C; ++ch)
+    for (int tap = 0; tap < 9; ++tap) {
+      float v = w.data[(size_t)ch * 9 + tap];
+      if (c->dt == DT_BF16) {
+        const uint32_t u = (uint32_t)f2bf_host(v) << 16;
+        memcpy(&v, &u, 4);
+      }
+      t[(size_t)tap * Cp + ch] = v;
+    }
+  RET(upload(c, (void**)w_dev, t.data(), t.size() * 4));
+  RET(upload_vec(c, scale_dev, std::vector<float>(scale, scale + C), Cp));
+  RET(upload_vec(c, shift_dev, std::vector<float>(shift, shift + C), Cp));
+  return 0;
+}
+
+int make_mbv2_block(sylph_ctx* c, int cin, int t, int cout, int stride, const HostTensor* const* w, const float* const* scale, const float* const* shift,
+                    sylph_ctx::MbBlock* blk) {
+  const int hid = cin * t;
+  blk->cin = cin; blk->t = t; blk->cout = cout; blk->stride = stride;
+  blk->cin_p = mbv2_pad(c, cin); blk->hid_p = mbv2_pad(c, hid); blk->cout_p = mbv2_pad(c, cout);
+  blk->cin_ld = mbv2_ld(c, cin); blk->hid_ld = mbv2_ld(c, hid); blk->cout_ld = mbv2_ld(c, cout);
+  if (t != 1) RET(make_padded_1x1(c, *w[0], hid, cin, blk->hid_p, blk->cin_p, scale[0], shift[0], &blk->exp));
+  RET(make_dw_table(c, *w[1], hid, blk->hid_p, scale[1], shift[1], &blk->dw_w, &blk->dw_scale, &blk->dw_shift));
+  RET(make_padded_1x1(c, *w[2], cout, hid, blk->cout_p, blk->hid_p, scale[2], shift[2], &blk->proj));
+  if ((t != 1 && blk->exp.Cout_pad != blk->hid_ld) || blk->proj.Cout_pad != blk->cout_ld) return fail("internal: MobileNetV2 row pitch");
+  if (c->dt == DT_BF16) {  // the same two matrices row-major in bf16, zero on the pad channels, for the one-launch block (conv_mbv2.hip)
+    auto pack = [&](const HostTensor& src, int rows, int cols, int rows_p, int cols_p, bf16_t** dev) {
+      std::vector<uint16_t> m((size_t)rows_p * cols_p, 0);
+      for (int n = 0; n < rows; ++n)
+        for (int k = 0; k < cols; ++k) m[(size_t)n * cols_p + k] = f2bf_host(src.data[(size_t)n * cols + k]);
+      return upload(c, (void**)dev, m.data(), m.size() * 2);
+    };
+    if (t != 1) RET(pack(*w[0], hid, cin, blk->hid_p, blk->cin_p, &blk->fw1));
+    RET(pack(*w[2], cout, hid, blk->cout_p, blk->hid_p, &blk->fw2));
+  }
+  return 0;
+}
+
+// conv `wkey`.weight of shape (cout, cin_w, k, k) + torch-style FrozenBN `bnkey`.{weight, bias, running_mean, running_var} (eps 1e-5)
+static int mbv2_conv_bn(sylph_ctx* c, const std::string& wkey, const std::string& bnkey, int cout, int cin_w, int k, const HostTensor** w,
+                        std::vector<float>* sc, std::vector<float>* sh) {
+  const std::string need = "(" + std::to_string(cout) + ", " + std::to_string(cin_w) + ", " + std::to_string(k) + ", " + std::to_string(k) + ")";
+  *w = find_w(c, wkey + ".weight");
+  if (!*w) return fail("missing weights for " + wkey + ".weight: MODEL.MOBILENET needs " + need);
+  if ((*w)->shape != std::vector<int64_t>{cout, cin_w, k, k}) return fail(wkey + ".weight: shape " + shape_str(**w) + " where MODEL.MOBILENET needs " + need);
+  const HostTensor *g = find_w(c, bnkey + ".weight"), *b = find_w(c, bnkey + ".bias");
+  const HostTensor *rm = find_w(c, bnkey + ".running_mean"), *rv = find_w(c, bnkey + ".running_var");
+  if (!g || !b || !rm || !rv) return fail("missing weights for " + bnkey);
+  if ((int)g->data.size() != cout || (int)b->data.size() != cout || (int)rm->data.size() != cout || (int)rv->data.size() != cout)
+    return fail(bnkey + ": FrozenBN tensors must have " + std::to_string(cout) + " elements");
+  sc->resize(cout); sh->resize(cout);
+  for (int i = 0; i < cout; ++i) {
+    const float s = g->data[i] * (1.0f / sqrtf(rv->data[i] + 1e-5f));
+    (*sc)[i] = s;
+    (*sh)[i] = b->data[i] - rm->data[i] * s;
+  }
+  return 0;
+}
+
+// AdelaiDet MobileNetV2 (tonylins layout, width 1.0): features.0 = conv 3x3 s2 + BN + ReLU6, features.1..17 = InvertedResidual blocks of
+// the (t, c, n, s) table; FPN laterals on res3 / res4 / res5 = features 6 / 13 / 17 (32 / 96 / 320 channels)
+static int finalize_mbv2(sylph_ctx* c) {
+  const std::string f = "backbone.bottom_up.features.";
+  {
+    const HostTensor* w;
+    std::vector<float> sc, sh;
+    RET(mbv2_conv_bn(c, f + "0.0", f + "0.1", 32, 3, 3, &w, &sc, &sh));
+    std::vector<float> t((size_t)9 * 4 * 32, 0.f);
+    for (int n = 0; n < 32; ++n)
+      for (int ch = 0; ch < 3; ++ch)
+        for (int tap = 0; tap < 9; ++tap) {
+          float v = w->data[((size_t)n * 3 + ch) * 9 + tap];
+          if (c->dt == DT_BF16) {
+            const uint32_t u = (uint32_t)f2bf_host(v) << 16;
+            memcpy(&v, &u, 4);
+          }
+          t[((size_t)tap * 4 + ch) * 32 + n] = v;
+        }
+    RET(upload(c, (void**)&c->mb_stem_w, t.data(), t.size() * 4));
+    RET(upload_vec(c, &c->mb_stem_scale, sc, 32));
+    RET(upload_vec(c, &c->mb_stem_shift, sh, 32));
+  }
+  const int table[7][4] = {{1, 16, 1, 1}, {6, 24, 2, 2}, {6, 32, 3, 2}, {6, 64, 4, 2}, {6, 96, 3, 1}, {6, 160, 3, 2}, {6, 320, 1, 1}};
+  int cin = 32, fi = 1;
+  c->mb_blocks.clear();
+  for (auto& row : table)
+    for (int i = 0; i < row[2]; ++i, ++fi) {
+      const int t = row[0], cout = row[1], stride = i == 0 ? row[3] : 1, hid = cin * t;
+      const std::string q = f + std::to_string(fi) + ".conv.";
+      const HostTensor* w[3] = {nullptr, nullptr, nullptr};
+      std::vector<float> sc[3], sh[3];
+      const int j = t == 1 ? 0 : 3;  // nn.Sequential index of the depthwise conv
+      if (t != 1) RET(mbv2_conv_bn(c, q + "0", q + "1", hid, cin, 1, &w[0], &sc[0], &sh[0]));
+      RET(mbv2_conv_bn(c, q + std::to_string(j), q + std::to_string(j + 1), hid, 1, 3, &w[1], &sc[1], &sh[1]));
+      RET(mbv2_conv_bn(c, q + std::to_string(j + 3), q + std::to_string(j + 4), cout, hid, 1, &w[2], &sc[2], &sh[2]));
+      const float* scp[3] = {sc[0].data(), sc[1].data(), sc[2].data()};
+      const float* shp[3] = {sh[0].data(), sh[1].data(), sh[2].data()};
+      c->mb_blocks.emplace_back();
+      RET(make_mbv2_block(c, cin, t, cout, stride, w, scp, shp, &c->mb_blocks.back()));
+      cin = cout;
+    }
+  const int lat_c[3] = {32, 96, 320};
+  for (int k = 0; k < 3; ++k) {
+    const std::string name = "backbone.fpn_lateral" + std::to_string(k + 3);
+    const HostTensor *lw = find_w(c, name + ".weight"), *lb = find_w(c, name + ".bias");
+    if (!lw || !lb) return fail("missing weights for " + name);
+    if (lw->shape != std::vector<int64_t>{256, lat_c[k], 1, 1} || lb->data.size() != 256)
+      return fail(name + ".weight: shape " + shape_str(*lw) + " where MODEL.MOBILENET needs (256, " + std::to_string(lat_c[k]) + ", 1, 1)");
+    RET(make_padded_1x1(c, *lw, 256, lat_c[k], 256, mbv2_pad(c, lat_c[k]), nullptr, lb->data.data(), &c->fpn_lat[k]));
+    RET(make_conv_bias(c, {"backbone.fpn_output" + std::to_string(k + 3)}, &c->fpn_out[k]));
+  }
+  RET(make_conv_bias(c, {"backbone.top_block.p6"}, &c->p6));
+  RET(make_conv_bias(c, {"backbone.top_block.p7"}, &c->p7));
+  c->has_backbone = true;
+  return 0;
+}
+
 bool has_prefix(sylph_ctx* c, const std::string& p) {
   auto it = c->host_w.lower_bound(p);
   return it != c->host_w.end() && it->first.compare(0, p.size(), p) == 0;
@@ -236,7 +376,13 @@ int sylph_finalize_weights(sylph_ctx* c) {
   if (c->finalized) return fail("weights already finalized");
   HIPCHK(hipSetDevice(c->device));
   const std::string bu = "backbone.bottom_up";
-  if (has_prefix(c, bu + ".stem")) {
+  if (c->cfg.mobilenet) {
+    if (has_prefix(c, bu + ".stem") || has_prefix(c, bu + ".res"))
+      return fail("MODEL.MOBILENET: the checkpoint holds ResNet keys (" + bu + ".stem / .res*) where " + bu + ".features.* are needed");
+    if (has_prefix(c, bu + ".features.")) RET(finalize_mbv2(c));
+  } else if (has_prefix(c, bu + ".features.")) {
+    return fail("the checkpoint holds MobileNetV2 keys (" + bu + ".features.*): set MODEL.MOBILENET True");
+  } else if (has_prefix(c, bu + ".stem")) {
     const HostTensor* w = find_w(c, bu + ".stem.conv1.weight");
     const HostTensor *g = find_w(c, bu + ".stem.conv1.norm.weight"), *b = find_w(c, bu + ".stem.conv1.norm.bias");
     const HostTensor *rm = find_w(c, bu + ".stem.conv1.norm.running_mean"),

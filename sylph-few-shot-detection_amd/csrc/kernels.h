@@ -165,6 +165,40 @@ size_t conv_group_packed_bytes(DType dt, int C, int cpg);
 void conv_group_pack(DType dt, const float* w, int C, int cpg, void* out);
 int launch_conv_group(DType dt, const GroupConvArgs& a, hipStream_t s);
 
+// conv_dw.hip: the direct convs of the MobileNetV2 bottom-up path, fp32 arithmetic in every storage mode.
+// Depthwise 3x3 (pad 1, stride 1 / 2) on dense images x [B][H * W][ld] -> y [B][Ho * Wo][ld], the first C channels of every row:
+// y = relu6(scale * conv(clamp(x, 0, 6)) + shift); w fp32 [3][3][C], scale / shift fp32 [C]; C and ld multiples of 8, ld >= C.
+struct DwConvArgs {
+  const void* x;
+  void* y;
+  const float *w, *scale, *shift;
+  int B, C, ld, H, W, Ho, Wo, stride;
+};
+int launch_dwconv3x3(DType dt, const DwConvArgs& a, hipStream_t s);
+// features.0: 3x3 stride-2 pad-1 conv 3 -> 32 + FrozenBN + ReLU6 on the normalised batch x [B][H][W][4] -> y [B][Ho * Wo][ld], the first C
+// channels of every row, C >= 32 (channels >= 32: zeros); C and ld multiples of 8; w fp32 [3][3][4][32] (input channel 3 zero), scale / shift fp32 [32]
+struct MbStemArgs {
+  const void* x;
+  void* y;
+  const float *w, *scale, *shift;
+  int B, C, ld, H, W, Ho, Wo;
+};
+int launch_mbv2_stem(DType dt, const MbStemArgs& a, hipStream_t s);
+
+// conv_mbv2.hip: one whole InvertedResidual block per launch, bf16 only; the hidden tensor stays in LDS.
+// x [B][H * W][cin_ld] -> y [B][Ho * Wo][cout_ld], the first cin_p / cout_p channels of every row.  w1 bf16 [hid_p][cin_p] (nullptr: t == 1,
+// hidden = input, hid_p == cin_p), w2 bf16 [cout_p][hid_p], wd fp32 [3][3][hid_p]; s* / b* the folded FrozenBN scale / shift of the three
+// layers.  cin_p and hid_p multiples of 32, cout_p 64 / 128 / 192 / 320; residual: y += x (stride 1, cin_p == cout_p).
+struct Mbv2Args {
+  const void* x;
+  void* y;
+  const bf16_t *w1, *w2;
+  const float *s1, *b1, *wd, *sd, *bd, *s2, *b2;
+  int B, H, W, Ho, Wo, stride, cin_p, cin_ld, hid_p, cout_p, cout_ld, residual;
+};
+bool conv_mbv2_can_run(const Mbv2Args& a);
+int launch_conv_mbv2(const Mbv2Args& a, hipStream_t s);
+
 // detect.hip
 // many-way class-conditional conv fused with the scan (detect.hip); x: raw cls-tower output, coef: its GroupNorm (a, b) per
 // (segment, channel), w: packed codes [>= 32 * ceil(N/32)][256] bf16, wf_ws: as many bytes of workspace (the codes in MFMA

@@ -32,7 +32,7 @@ class SylphConfig(Structure):
         ("head_num_fc", c_int), ("head_fc_dim", c_int), ("cg_meta_bias", c_int), ("cg_has_weight", c_int), ("cg_has_scale", c_int),
         ("num_share_convs", c_int), ("tower_norm", c_int), ("cg_tower_gn_mask", c_int), ("cg_tower_relu_mask", c_int),
         ("tower_deformable", c_int), ("num_groups", c_int), ("width_per_group", c_int),
-        ("cg_code_ksize", c_int),
+        ("mobilenet", c_int), ("cg_code_ksize", c_int),
     ]
 
 
@@ -98,6 +98,9 @@ PROTOTYPES = {
                                                                             c_void_p]),
     "sylph_conv3x3_c64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "sylph_basic_block": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
+    "sylph_dwconv3x3": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylph_mbv2_padded_channels": (c_int, [c_void_p, c_int]),
+    "sylph_mbv2_block": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p]),
     "sylph_device_bytes": (c_int64, [c_void_p]),
     "sylph_profile_enable": (c_int, [c_void_p, c_int]),
     "sylph_bench_conv": (c_int, [c_void_p] + [c_int] * 12 + [POINTER(c_float), POINTER(ctypes.c_double)]),

@@ -21,6 +21,23 @@ def _iarr(v: Sequence[int]):
     return (c_int * len(v))(*[int(x) for x in v])
 
 
+def _check_resnet_keys(sc, r, basic):
+    """The MODEL.RESNETS keys of a detectron2 ResNet bottom-up that change the graph and are not implemented (MobileNetV2 reads none)."""
+    if any(bool(v) for v in r.get("DEFORM_ON_PER_STAGE", [False] * 4)):
+        raise NotImplementedError("MODEL.RESNETS.DEFORM_ON_PER_STAGE: deformable bottleneck convs are not supported")
+    if int(r.get("RES5_DILATION", 1)) != 1:
+        raise NotImplementedError("MODEL.RESNETS.RES5_DILATION != 1 is not supported")
+    res2_out = int(r.get("RES2_OUT_CHANNELS", 256))
+    if basic and res2_out != 64:
+        raise NotImplementedError(f"MODEL.RESNETS.RES2_OUT_CHANNELS {res2_out}: DEPTH {sc.resnet_depth} (BasicBlock) needs RES2_OUT_CHANNELS 64")
+    if not basic and res2_out == 64:
+        raise NotImplementedError(f"MODEL.RESNETS.RES2_OUT_CHANNELS 64 belongs to DEPTH 18 / 34 (BasicBlock); DEPTH {sc.resnet_depth} needs 256")
+    if res2_out != (64 if basic else 256) or int(r.get("STEM_OUT_CHANNELS", 64)) != 64:
+        raise NotImplementedError("MODEL.RESNETS.RES2_OUT_CHANNELS / STEM_OUT_CHANNELS: only 256 (64 for DEPTH 18 / 34) / 64 are supported")
+    if str(r.get("NORM", "FrozenBN")) != "FrozenBN":
+        raise NotImplementedError(f"MODEL.RESNETS.NORM {r.NORM!r}: only FrozenBN (inference) is supported")
+
+
 def config_from_cfg(cfg) -> SylphConfig:
     """Map the yacs node (sylph_amd.config / the reference's keys) onto the C config struct."""
     L = _lib.lib()
@@ -30,6 +47,15 @@ def config_from_cfg(cfg) -> SylphConfig:
         return sc
     m = cfg.MODEL
     f = m.FCOS
+    # adet's build_fcos_resnet_fpn_backbone picks the bottom-up path in this order: BACKBONE.ANTI_ALIAS (low-pass-filtered ResNet),
+    # RESNETS.DEFORM_INTERVAL > 1 (interval-deformable ResNet), MODEL.MOBILENET (MobileNetV2), else detectron2's ResNet.  The first two
+    # are not implemented and win over MOBILENET there, so they refuse here whatever MOBILENET says.
+    bb = m.get("BACKBONE", None)
+    if bb is not None and bool(bb.get("ANTI_ALIAS", False)):
+        raise NotImplementedError("MODEL.BACKBONE.ANTI_ALIAS: the anti-aliased (low-pass-filtered) ResNet is not supported")
+    if int(m.RESNETS.get("DEFORM_INTERVAL", 1)) > 1:
+        raise NotImplementedError("MODEL.RESNETS.DEFORM_INTERVAL > 1: the interval-deformable ResNet is not supported")
+    sc.mobilenet = int(bool(m.get("MOBILENET", False)))  # MobileNetV2 bottom-up (csrc/conv_dw.hip): MODEL.RESNETS.* is not read
     sc.resnet_depth = int(m.RESNETS.DEPTH)
     sc.stride_in_1x1 = int(bool(m.RESNETS.get("STRIDE_IN_1X1", True)))
     sc.num_cls_convs = int(f.NUM_CLS_CONVS)
@@ -45,9 +71,11 @@ def config_from_cfg(cfg) -> SylphConfig:
     # R-18 / R-34 (detectron2 BasicBlock, csrc/conv_rw64.hip): stage widths 64 << s, i.e. RES2_OUT_CHANNELS 64; STRIDE_IN_1X1 is ignored
     # (the stride sits on conv1).  detectron2's own assertions for these depths: no groups, no deformable stages, no res5 dilation
     basic = sc.resnet_depth in (18, 34)
-    if sc.resnet_depth not in (18, 34, 50, 101, 152):
+    if sc.mobilenet:
+        sc.resnet_depth, ng, wpg = 50, 1, 64  # (not read: the C side sees the defaults)
+    elif sc.resnet_depth not in (18, 34, 50, 101, 152):
         raise NotImplementedError(f"MODEL.RESNETS.DEPTH {sc.resnet_depth}: 18, 34 (BasicBlock) and 50, 101, 152 (bottleneck) are supported")
-    if ng != 1 or wpg != 64:
+    if not sc.mobilenet and (ng != 1 or wpg != 64):
         if sc.resnet_depth not in (50, 101, 152):
             raise NotImplementedError(f"MODEL.RESNETS.DEPTH {sc.resnet_depth}: ResNeXt needs DEPTH 50, 101 or 152")
         widths = [wpg << s for s in range(4)]
@@ -56,19 +84,8 @@ def config_from_cfg(cfg) -> SylphConfig:
                 f"MODEL.RESNETS.NUM_GROUPS {ng} / WIDTH_PER_GROUP {wpg}: the grouped conv needs a per-group width WIDTH_PER_GROUP << s "
                 f"that is a power of two in [4, 64] at every stage (here {widths}) and NUM_GROUPS * WIDTH_PER_GROUP a multiple of 64")
     sc.num_groups, sc.width_per_group = ng, wpg
-    if any(bool(v) for v in r.get("DEFORM_ON_PER_STAGE", [False] * 4)):
-        raise NotImplementedError("MODEL.RESNETS.DEFORM_ON_PER_STAGE: deformable bottleneck convs are not supported")
-    if int(r.get("RES5_DILATION", 1)) != 1:
-        raise NotImplementedError("MODEL.RESNETS.RES5_DILATION != 1 is not supported")
-    res2_out = int(r.get("RES2_OUT_CHANNELS", 256))
-    if basic and res2_out != 64:
-        raise NotImplementedError(f"MODEL.RESNETS.RES2_OUT_CHANNELS {res2_out}: DEPTH {sc.resnet_depth} (BasicBlock) needs RES2_OUT_CHANNELS 64")
-    if not basic and res2_out == 64:
-        raise NotImplementedError(f"MODEL.RESNETS.RES2_OUT_CHANNELS 64 belongs to DEPTH 18 / 34 (BasicBlock); DEPTH {sc.resnet_depth} needs 256")
-    if res2_out != (64 if basic else 256) or int(r.get("STEM_OUT_CHANNELS", 64)) != 64:
-        raise NotImplementedError("MODEL.RESNETS.RES2_OUT_CHANNELS / STEM_OUT_CHANNELS: only 256 (64 for DEPTH 18 / 34) / 64 are supported")
-    if str(r.get("NORM", "FrozenBN")) != "FrozenBN":
-        raise NotImplementedError(f"MODEL.RESNETS.NORM {r.NORM!r}: only FrozenBN (inference) is supported")
+    if not sc.mobilenet:
+        _check_resnet_keys(sc, r, basic)
     fpn = m.get("FPN", None)
     if fpn is not None:
         if str(fpn.get("FUSE_TYPE", "sum")) != "sum":
@@ -110,8 +127,6 @@ def config_from_cfg(cfg) -> SylphConfig:
     else:
         raise NotImplementedError(f"MODEL.FCOS.BOX_QUALITY {bq}")
     sc.prior_prob = float(f.PRIOR_PROB)
-    if int(m.RESNETS.get("RES5_DILATION", 1)) != 1:
-        raise NotImplementedError("MODEL.RESNETS.RES5_DILATION != 1 is not supported")
     if not bool(m.META_LEARN.EPISODIC_LEARNING):
         # plain base detector (meta_one_stage_detector.py:52-58: no code generator is built): the head runs the checkpoint's
         # own 1x1 cls_logits through the class-conditional conv, always with its bias
@@ -121,8 +136,6 @@ def config_from_cfg(cfg) -> SylphConfig:
         return sc
     cg = m.META_LEARN.CODE_GENERATOR
     # knobs that change the reference arithmetic and are not implemented must fail loudly, not be ignored
-    if int(m.RESNETS.get("RES5_DILATION", 1)) != 1:
-        raise NotImplementedError("MODEL.RESNETS.RES5_DILATION != 1 is not supported")
     if bool(cg.ROI_BOX.get("FPN_MULTILEVEL_FEATURE", False)):
         # the reference cannot run it either: CodeGeneratorHead builds detectron2's ROIPooler (one output tensor), code_generator.py:943
         # then iterates over its batch dimension and GroupNorm fails on the unbatched slices
@@ -822,13 +835,15 @@ class Engine:
         check(self.L.sylph_set_debug_taps(self._ctx, int(on)), "set_debug_taps")
 
     def export_stage(self, stage: int) -> torch.Tensor:
-        """res<stage> output of the last backbone pass, (B, C, h, w) fp32 NCHW; C = 256 << (stage - 2), 64 << (stage - 2) for R-18 / R-34."""
+        """res<stage> output of the last backbone pass, (B, C, h, w) fp32 NCHW; C = 256 << (stage - 2), 64 << (stage - 2) for R-18 / R-34,
+        24 / 32 / 96 / 320 for MobileNetV2."""
         self._stream()
         B, H, W, _ = self._batch
         h, w = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         for _ in range(stage - 1):
             h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-        out = torch.empty(B, (64 if self.sc.resnet_depth in (18, 34) else 256) << (stage - 2), h, w, device=self.device)
+        ch = (24, 32, 96, 320)[stage - 2] if self.sc.mobilenet else (64 if self.sc.resnet_depth in (18, 34) else 256) << (stage - 2)
+        out = torch.empty(B, ch, h, w, device=self.device)
         check(self.L.sylph_export_stage(self._ctx, stage, _ptr(out)), "export_stage")
         return out
 
@@ -961,6 +976,39 @@ class Engine:
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
         y = torch.empty(B, cout, Ho, Wo, device=self.device)
         check(self.L.sylph_basic_block(self._ctx, _ptr(x), B, Cin, H, W, stride, cout, arrs[0], arrs[1], arrs[2], _ptr(y)), "basic_block")
+        return y
+
+    def dwconv3x3(self, x, w, scale, shift, stride=1):
+        """One depthwise 3x3 conv (pad 1) as a MobileNetV2 block launches it (conv_dw.hip): relu6(scale * conv(clamp(x, 0, 6)) + shift);
+        w (C, 1, 3, 3), C a multiple of 8."""
+        self._stream()
+        x = x.to(self.device, torch.float32).contiguous()
+        B, C, H, W = x.shape
+        assert tuple(w.shape) == (C, 1, 3, 3)
+        wh, sc, sh = [t.detach().cpu().float().contiguous() for t in (w, scale, shift)]
+        y = torch.empty(B, C, (H - 1) // stride + 1, (W - 1) // stride + 1, device=self.device)
+        check(self.L.sylph_dwconv3x3(self._ctx, _ptr(x), B, C, H, W, stride, _ptr(wh), _ptr(sc), _ptr(sh), _ptr(y)), "dwconv3x3")
+        return y
+
+    def mbv2_padded_channels(self, c: int) -> int:
+        """Channels a MobileNetV2 tensor of c channels is stored with (zero pad channels)."""
+        return int(self.L.sylph_mbv2_padded_channels(self._ctx, int(c)))
+
+    def mbv2_block(self, x, ws, scales, shifts, stride=1, padded=False):
+        """One MobileNetV2 InvertedResidual block through the backbone's own launches.  ws / scales / shifts: expand (6 Cin, Cin, 1, 1) or
+        None (t = 1), depthwise (t Cin, 1, 3, 3), project (Cout, t Cin, 1, 1) with their folded FrozenBN scale / shift; the input is added
+        when stride == 1 and Cin == Cout.  padded: return the stored pad channels (all zero) too."""
+        self._stream()
+        x = x.to(self.device, torch.float32).contiguous()
+        B, Cin, H, W = x.shape
+        t = 1 if ws[0] is None else 6
+        cout = ws[2].shape[0]
+        assert ws[1].shape[0] == t * Cin and tuple(ws[2].shape[:2]) == (cout, t * Cin)
+        keep = [[None if v is None else v.detach().cpu().float().contiguous() for v in lst] for lst in (ws, scales, shifts)]
+        arrs = [(c_void_p * 3)(*[None if v is None else v.data_ptr() for v in lst]) for lst in keep]
+        cy = self.mbv2_padded_channels(cout) if padded else cout
+        y = torch.empty(B, cy, (H - 1) // stride + 1, (W - 1) // stride + 1, device=self.device)
+        check(self.L.sylph_mbv2_block(self._ctx, _ptr(x), B, Cin, H, W, t, cout, stride, arrs[0], arrs[1], arrs[2], cy, _ptr(y)), "mbv2_block")
         return y
 
     def fpn_lateral(self, x, w, bias, top=None):

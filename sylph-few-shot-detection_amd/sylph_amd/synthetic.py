@@ -115,6 +115,60 @@ def _basic_backbone_state_dict(seed: int, depth: int) -> Dict[str, torch.Tensor]
     return sd
 
 
+MOBILENET_V2_TABLE = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1))  # (t, c, n, s)
+
+
+def mobilenet_v2_blocks() -> List[Tuple[int, int, int, int]]:
+    """(cin, t, cout, stride) of features.1 .. features.17 (width 1.0; the stride sits on the first block of a group)."""
+    out, cin = [], 32
+    for t, c, n, s in MOBILENET_V2_TABLE:
+        for i in range(n):
+            out.append((cin, t, c, s if i == 0 else 1))
+            cin = c
+    return out
+
+
+def mobilenet_backbone_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """AdelaiDet's MobileNetV2 bottom-up (adet/modeling/backbone/mobilenet.py, the tonylins layout with FrozenBatchNorm2d) + the FPN on
+    res3 / res4 / res5 = features 6 / 13 / 17 (32 / 96 / 320 channels).  Keys: backbone.bottom_up.features.0.{0.weight, 1.*} (conv 3x3 s2
+    3 -> 32, BN), features.{1..17}.conv.{i}: t = 1: 0 depthwise, 1 BN, 3 project, 4 BN; t = 6: 0 expand, 1 BN, 3 depthwise, 4 BN, 6 project,
+    7 BN.  A generator of its own: no key of the ResNet dicts changes.
+    The gains put real work on both clamps of every ReLU6: pre-activations with a standard deviation of 3 to 6 around +1 (a few per
+    cent above 6, a third below 0), projections small enough that 17 blocks with up to three residual adds in a row stay O(1)."""
+    g = torch.Generator().manual_seed(seed + 104729)
+    sd = {}
+    p = "backbone.bottom_up.features"
+
+    def bn(prefix, c, bias0):
+        sd[prefix + ".weight"] = torch.rand(c, generator=g) * 0.5 + 0.75
+        sd[prefix + ".bias"] = torch.randn(c, generator=g) * 0.3 + bias0
+        sd[prefix + ".running_mean"] = torch.randn(c, generator=g) * 0.1
+        sd[prefix + ".running_var"] = torch.rand(c, generator=g) * 0.5 + 0.75
+
+    # inputs are O(100) (0..255 minus the mean, rms ~75): pre-activation std ~3
+    sd[f"{p}.0.0.weight"] = torch.randn(32, 3, 3, 3, generator=g) * (3.0 / (75.0 * math.sqrt(27.0)))
+    bn(f"{p}.0.1", 32, 1.0)
+    for fi, (cin, t, cout, stride) in enumerate(mobilenet_v2_blocks(), start=1):
+        q, hid, j = f"{p}.{fi}.conv", cin * t, 0
+        if t != 1:
+            sd[f"{q}.0.weight"] = torch.randn(hid, cin, 1, 1, generator=g) * (4.0 / math.sqrt(cin))  # block inputs have rms 0.6 .. 1.5
+            bn(f"{q}.1", hid, 1.0)
+            j = 3
+        sd[f"{q}.{j}.weight"] = torch.randn(hid, 1, 3, 3, generator=g) * (1.2 / 3.0)  # inputs in [0, 6], rms ~2.3
+        bn(f"{q}.{j + 1}", hid, 0.5)
+        sd[f"{q}.{j + 3}.weight"] = torch.randn(cout, hid, 1, 1, generator=g) * (0.35 / math.sqrt(hid))
+        bn(f"{q}.{j + 4}", cout, 0.0)
+    for stage, c in ((3, 32), (4, 96), (5, 320)):
+        sd[f"backbone.fpn_lateral{stage}.weight"] = _conv(g, 256, c, 1, std=math.sqrt(1.0 / c))
+        sd[f"backbone.fpn_lateral{stage}.bias"] = torch.randn(256, generator=g) * 0.1
+        sd[f"backbone.fpn_output{stage}.weight"] = _conv(g, 256, 256, 3, std=math.sqrt(1.0 / 2304))
+        sd[f"backbone.fpn_output{stage}.bias"] = torch.randn(256, generator=g) * 0.1
+    for n in ("p6", "p7"):
+        sd[f"backbone.top_block.{n}.weight"] = _conv(g, 256, 256, 3, std=math.sqrt(1.0 / 2304))
+        sd[f"backbone.top_block.{n}.bias"] = torch.randn(256, generator=g) * 0.1
+    return sd
+
+
 def head_state_dict(seed: int = 1, num_classes: int = 60, c: int = 256, num_convs: int = 4,
                     levels: int = 5, num_share_convs: int = 0, norm: str = "GN", num_cls_convs: int = None,
                     num_box_convs: int = None, deformable: bool = False) -> Dict[str, torch.Tensor]:
@@ -204,10 +258,11 @@ def codegen_state_dict(seed: int = 2, c: int = 256, out_c: int = 256, tower_laye
     return sd
 
 
-def synthetic_state_dict(seed: int = 0, depth: int = 50, num_classes: int = 60) -> Dict[str, torch.Tensor]:
+def synthetic_state_dict(seed: int = 0, depth: int = 50, num_classes: int = 60, mobilenet: bool = False) -> Dict[str, torch.Tensor]:
+    """mobilenet (MODEL.MOBILENET): the MobileNetV2 bottom-up instead of the ResNet of `depth`; head and code generator are the same."""
     sd = {"pixel_mean": torch.tensor([103.530, 116.280, 123.675]).view(3, 1, 1),
           "pixel_std": torch.tensor([1.0, 1.0, 1.0]).view(3, 1, 1)}
-    sd.update(backbone_state_dict(seed, depth))
+    sd.update(mobilenet_backbone_state_dict(seed) if mobilenet else backbone_state_dict(seed, depth))
     sd.update(head_state_dict(seed + 1, num_classes))
     sd.update(codegen_state_dict(seed + 2))
     return sd
