@@ -126,6 +126,16 @@ int sylph_preprocess(sylph_ctx* ctx, int B, const float* const* images_dev, cons
  * targets.  Pillow's fixed-point two-pass resampling is reproduced bit for bit.  Makes the padded batch current. */
 int sylph_preprocess_u8(sylph_ctx* ctx, int B, const unsigned char* const* images_dev, const int* heights, const int* widths,
                         const int* new_heights, const int* new_widths, int rgb_input, int* padded_h, int* padded_w);
+/* The same pipeline for VIEWS of device-resident sources (test-time augmentation, tiled inference): image b of the batch is built from
+ * the (src_h[b], src_w[b], 3) uint8 HWC image at src_dev[b] as Image.fromarray(src).crop((x0, y0, x0 + cw, y0 + ch))
+ * .resize((new_w, new_h), BILINEAR), then ImageOps.mirror of that result when flip[b] != 0 (detectron2's transform list puts the flip
+ * behind the resize), then BGR swap, normalisation and padding -- bit for bit what sylph_preprocess_u8 writes for a host-made copy of the
+ * view.  Crop-then-resize: a pixel outside the crop never contributes (this is not Pillow's resize(box=...)).  Several views may name
+ * the same source pointer: the source is uploaded once, whatever the number of views.  All arrays are host arrays of B entries.  A crop
+ * that leaves its source, or a non-positive size, fails with a message and launches nothing.  Makes the padded batch current. */
+int sylph_preprocess_views(sylph_ctx* ctx, int B, const unsigned char* const* src_dev, const int* src_h, const int* src_w,
+                           const int* crop_x0, const int* crop_y0, const int* crop_w, const int* crop_h, const int* new_h, const int* new_w,
+                           const int* flip, int rgb_input, int* padded_h, int* padded_w);
 /* Boundary/test entry: the normalised, padded network input of the current batch as (B,3,H,W) fp32 NCHW. */
 int sylph_export_input(sylph_ctx* ctx, float* out_nchw_dev);
 
@@ -208,6 +218,26 @@ int sylph_decode_nms(sylph_ctx* ctx, const int* out_heights, const int* out_widt
 int sylph_decode_nms_codesets(sylph_ctx* ctx, int G, const int* out_heights, const int* out_widths, int max_out, float* boxes_dev,
                               float* scores_dev, int* classes_dev, int* levels_dev, float* locations_dev, int* cand_dev,
                               int* counts_dev, int* status_dev);
+
+/* Merge of the detections of several views of the same source (sylph_preprocess_views): one class-wise NMS over their union, in the
+ * coordinates of the source.  The per-view decode is sylph_decode_nms with out_heights / out_widths = the view's CROP size: its boxes are
+ * in crop pixels, clipped to the crop, in the mirrored crop for a flipped view.  Decode writes [B][max_out] rows, so the views of several
+ * steps land in consecutive slices of one [n_views][max_in] buffer set (boxes_dev [.][4], scores_dev, classes_dev; counts_dev[n_views]).
+ * Host arrays of n_views entries: view_src (in [0, n_src)), view_x0 / view_y0 (crop origin), view_w (crop width), view_flip.  Per source:
+ *   1  back to source coordinates: flipped (x1, x2) <- (w - x2, w - x1); then x += x0, y += y0; plain fp32 in that order, no clip
+ *   2  pool: the rows of its views in ascending view index, rows in order (the views of a source need not be adjacent)
+ *   3  stable sort by score, descending: a tie goes to the lower view index, then to the lower row
+ *   4  greedy class-aware NMS with MODEL.FCOS.NMS_TH: inter / (area_i + area_j - inter) > thr suppresses, equal classes only; thr <= 0: off
+ *   5  keep: the first POST_NMS_TOPK_TEST kept boxes and every later kept box whose score equals the K-th; K <= 0 keeps all
+ * Outputs, row-major [n_src][max_out]: boxes, scores, classes, and out_view_dev / out_row_dev: the input row each output came from;
+ * out_counts_dev[n_src]; status_dev[1]: bit1 (value 2) = a source was truncated at max_out.  A source whose views could hold more than
+ * MERGE_POOL_CAP = 4096 rows together (max_in x its views) fails by name before any launch.  Needs no current batch; nothing is kept
+ * between calls.  The rows are taken as decode left them, clipped to the crop: rows that a crop border cut can overlap more than they did
+ * under the view's own NMS. */
+int sylph_merge_views(sylph_ctx* ctx, int n_src, int n_views, const int* view_src, const float* view_x0, const float* view_y0,
+                      const float* view_w, const int* view_flip, int max_in, const float* boxes_dev, const float* scores_dev,
+                      const int* classes_dev, const int* counts_dev, int max_out, float* out_boxes_dev, float* out_scores_dev,
+                      int* out_classes_dev, int* out_view_dev, int* out_row_dev, int* out_counts_dev, int* status_dev);
 
 /* CodeGenerator.forward / CodeGeneratorHead.forward_roi_align, eval branch
  * (sylph/modeling/code_generator/code_generator.py:924-1002): the current batch is the S support

@@ -805,6 +805,95 @@ int sylph_preprocess_u8(sylph_ctx* c, int B, const unsigned char* const* images,
   return 0;
 }
 
+/* see include/sylph_hip.h */
+int sylph_preprocess_views(sylph_ctx* c, int B, const unsigned char* const* src, const int* shs, const int* sws, const int* cx0, const int* cy0,
+                           const int* cws, const int* chs, const int* nhs, const int* nws, const int* flip, int rgb_input, int* ph, int* pw) {
+  if (!c->finalized) return fail("weights not finalized");
+  if (B <= 0) return fail("empty batch");
+  if (!src || !shs || !sws || !cx0 || !cy0 || !cws || !chs || !nhs || !nws || !flip) return fail("sylph_preprocess_views: NULL argument");
+  int mh = 0, mw = 0;
+  for (int b = 0; b < B; ++b) {
+    if (!src[b]) return fail("sylph_preprocess_views: view " + std::to_string(b) + " has no source");
+    if (shs[b] <= 0 || sws[b] <= 0 || cws[b] <= 0 || chs[b] <= 0 || nhs[b] <= 0 || nws[b] <= 0)
+      return fail("sylph_preprocess_views: view " + std::to_string(b) + " has a non-positive size");
+    if (cx0[b] < 0 || cy0[b] < 0 || cws[b] > sws[b] - cx0[b] || chs[b] > shs[b] - cy0[b])
+      return fail("sylph_preprocess_views: view " + std::to_string(b) + ": crop (" + std::to_string(cx0[b]) + ", " + std::to_string(cy0[b]) + ") + " +
+                  std::to_string(cws[b]) + " x " + std::to_string(chs[b]) + " leaves its " + std::to_string(sws[b]) + " x " + std::to_string(shs[b]) +
+                  " source");
+    mh = nhs[b] > mh ? nhs[b] : mh; mw = nws[b] > mw ? nws[b] : mw;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  const int d = c->cfg.size_divisibility;
+  if (d > 1) { mh = (mh + d - 1) / d * d; mw = (mw + d - 1) / d * d; }
+  Plan* P = get_plan(c, B, mh, mw);
+  OwnerScope own(c, P);
+  BUILD(build_backbone(c, P), P);
+  // resampling tables (cached per (in, out) size pair); the views of one step mostly share a few: each distinct table is laid out once
+  std::vector<std::shared_ptr<PilCoeffs>> hc((size_t)B), vc((size_t)B);
+  std::map<const PilCoeffs*, size_t> tab_off;
+  std::vector<const PilCoeffs*> order;
+  size_t nint = 0;
+  for (int b = 0; b < B; ++b) {
+    for (int pass = 0; pass < 2; ++pass) {
+      const std::pair<int, int> key = pass == 0 ? std::make_pair(cws[b], nws[b]) : std::make_pair(chs[b], nhs[b]);
+      auto it = c->pil_cache.find(key);
+      if (it == c->pil_cache.end()) {
+        if (c->pil_cache.size() > 256) { c->pil_cache.clear(); }  // (hc / vc keep this call's tables alive)
+        it = c->pil_cache.emplace(key, pil_bilinear_coeffs(key.first, key.second)).first;
+      }
+      (pass == 0 ? hc : vc)[b] = it->second;
+      if (tab_off.emplace(it->second.get(), nint).second) {
+        order.push_back(it->second.get());
+        nint += it->second->bounds.size() + it->second->kk.size();
+      }
+    }
+  }
+  if (nint > (size_t)INT32_MAX) return fail("sylph_preprocess_views: resampling tables too large");
+  if (P->img_desc_ev) HIPCHK(hipEventSynchronize(P->img_desc_ev));
+  else HIPCHK(hipEventCreateWithFlags(&P->img_desc_ev, hipEventDisableTiming));
+  const size_t need = sizeof(ViewDesc) * B + nint * sizeof(int);
+  if (need > P->rz_tab_cap) {
+    if (P->rz_host) (void)hipHostFree(P->rz_host);
+    if (P->rz_desc_dev) c->dfree(P->rz_desc_dev);
+    P->rz_host = nullptr; P->rz_desc_dev = nullptr; P->rz_tab_cap = 0;
+    const size_t cap = need + need / 2;
+    HIPCHK(hipHostMalloc((void**)&P->rz_host, cap));
+    RET(c->dalloc((void**)&P->rz_desc_dev, cap));
+    P->rz_tab_cap = cap;
+  }
+  ViewDesc* dh = reinterpret_cast<ViewDesc*>(P->rz_host);
+  int* th = reinterpret_cast<int*>(P->rz_host + sizeof(ViewDesc) * B);
+  for (const PilCoeffs* pc : order) {
+    const size_t off = tab_off[pc];
+    memcpy(th + off, pc->bounds.data(), pc->bounds.size() * sizeof(int));
+    memcpy(th + off + pc->bounds.size(), pc->kk.data(), pc->kk.size() * sizeof(int));
+  }
+  for (int b = 0; b < B; ++b) {
+    ViewDesc& r = dh[b];
+    r.src = src[b]; r.pitch = sws[b]; r.x0 = cx0[b]; r.y0 = cy0[b]; r.new_h = nhs[b]; r.new_w = nws[b]; r.flip = flip[b] ? 1 : 0;
+    r.ksh = hc[b]->ksize; r.ksv = vc[b]->ksize;
+    r.hb_off = (int)tab_off[hc[b].get()]; r.hk_off = r.hb_off + (int)hc[b]->bounds.size();
+    r.vb_off = (int)tab_off[vc[b].get()]; r.vk_off = r.vb_off + (int)vc[b]->bounds.size();
+    P->img_h[b] = nhs[b]; P->img_w[b] = nws[b];
+  }
+  HIPCHK(hipMemcpyAsync(P->rz_desc_dev, P->rz_host, need, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipEventRecord(P->img_desc_ev, c->stream));
+  const ViewDesc* desc_dev = reinterpret_cast<const ViewDesc*>(P->rz_desc_dev);
+  const int* tab_dev = reinterpret_cast<const int*>(reinterpret_cast<const char*>(P->rz_desc_dev) + sizeof(ViewDesc) * B);
+  P->raw_input = false;  // this pipeline writes the normalised batch itself
+  void* x0 = P->x0;
+  const DType dt = c->dt;
+  const float* mean = c->cfg.pixel_mean;
+  const float* stdv = c->cfg.pixel_std;
+  KCHK(timed_op(c, "view_preprocess_kernel", 0.0, c->stream, [=](hipStream_t st) {
+         return launch_view_preprocess(dt, desc_dev, tab_dev, x0, B, mh, mw, mean, stdv, rgb_input, st);
+       }), "view_preprocess");
+  c->cur = P;
+  if (ph) *ph = mh;
+  if (pw) *pw = mw;
+  return 0;
+}
+
 int sylph_export_input(sylph_ctx* c, float* out) {
   Plan* P = c->cur;
   if (!P || !P->x0) return fail("sylph_preprocess must be called first");

@@ -205,6 +205,7 @@ void sylph_ctx_destroy(sylph_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
+  if (c->merge_ev) (void)hipEventDestroy(c->merge_ev);
   for (auto& kv : c->plans) free_plan(c, kv.second.get());
   c->plans.clear();
   for (void* p : c->allocs) (void)hipFree(p);

@@ -944,4 +944,67 @@ int sylph_decode_nms_codesets(sylph_ctx* c, int G, const int* oh, const int* ow,
   return 0;
 }
 
+/* see include/sylph_hip.h */
+int sylph_merge_views(sylph_ctx* c, int n_src, int n_views, const int* view_src, const float* view_x0, const float* view_y0, const float* view_w,
+                      const int* view_flip, int max_in, const float* boxes, const float* scores, const int* classes, const int* counts, int max_out,
+                      float* out_boxes, float* out_scores, int* out_classes, int* out_view, int* out_row, int* out_counts, int* status) {
+  if (n_src <= 0) return fail("sylph_merge_views: no sources (n_src <= 0)");
+  if (n_views <= 0) return fail("sylph_merge_views: no views (n_views <= 0)");
+  if (max_in <= 0 || max_out <= 0) return fail("sylph_merge_views: max_in and max_out must be positive");
+  if (!view_src || !view_x0 || !view_y0 || !view_w || !view_flip) return fail("sylph_merge_views: a view table is NULL");
+  if (!boxes || !scores || !classes || !counts || !out_boxes || !out_scores || !out_classes || !out_view || !out_row || !out_counts || !status)
+    return fail("sylph_merge_views: a device buffer is NULL");
+  if ((long)n_views * max_in >= (1L << 31)) return fail("sylph_merge_views: n_views * max_in does not fit a row index");
+  std::vector<int> per_src((size_t)n_src, 0);
+  for (int v = 0; v < n_views; ++v) {
+    if (view_src[v] < 0 || view_src[v] >= n_src)
+      return fail("sylph_merge_views: view_src[" + std::to_string(v) + "] = " + std::to_string(view_src[v]) + " is outside the " + std::to_string(n_src) + " sources");
+    ++per_src[view_src[v]];
+  }
+  int max_views = 0;
+  for (int s = 0; s < n_src; ++s) {
+    if ((long)per_src[s] * max_in > MERGE_POOL_CAP)
+      return fail("sylph_merge_views: source " + std::to_string(s) + " has " + std::to_string(per_src[s]) + " views of up to " + std::to_string(max_in) +
+                  " rows: above the pool capacity MERGE_POOL_CAP = " + std::to_string(MERGE_POOL_CAP) + " rows per source");
+    max_views = per_src[s] > max_views ? per_src[s] : max_views;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  // tables: src_off [n_src + 1] | src_views [n_views] (the views of every source, ascending) | MergeView [n_views]
+  const size_t ints = (size_t)n_src + 1 + n_views, need = ints * sizeof(int) + (size_t)n_views * sizeof(MergeView);
+  if (c->merge_ev) HIPCHK(hipEventSynchronize(c->merge_ev));
+  else HIPCHK(hipEventCreateWithFlags(&c->merge_ev, hipEventDisableTiming));
+  if (need > c->merge_tab_cap) {
+    if (c->merge_tab) c->dfree(c->merge_tab);
+    c->merge_tab = nullptr; c->merge_tab_cap = 0;
+    Plan* owner = c->alloc_owner;
+    c->alloc_owner = nullptr;  // the context's, not a plan's
+    const int r = c->dalloc(&c->merge_tab, need * 2);
+    c->alloc_owner = owner;
+    RET(r);
+    c->merge_tab_cap = need * 2;
+  }
+  c->merge_host.resize(need);
+  int* off = reinterpret_cast<int*>(c->merge_host.data());
+  int* list = off + n_src + 1;
+  MergeView* mv = reinterpret_cast<MergeView*>(c->merge_host.data() + ints * sizeof(int));
+  off[0] = 0;
+  for (int s = 0; s < n_src; ++s) off[s + 1] = off[s] + per_src[s];
+  std::vector<int> fill(off, off + n_src);
+  for (int v = 0; v < n_views; ++v) {
+    list[fill[view_src[v]]++] = v;
+    mv[v] = MergeView{view_src[v], view_x0[v], view_y0[v], view_w[v], view_flip[v] ? 1 : 0};
+  }
+  HIPCHK(hipMemcpyAsync(c->merge_tab, c->merge_host.data(), need, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipEventRecord(c->merge_ev, c->stream));
+  const int* off_dev = reinterpret_cast<const int*>(c->merge_tab);
+  const MergeView* mv_dev = reinterpret_cast<const MergeView*>(reinterpret_cast<const char*>(c->merge_tab) + ints * sizeof(int));
+  const float thr = c->cfg.nms_thresh;
+  const int K = c->cfg.post_nms_topk, pool_max = max_views * max_in;
+  KCHK(timed_op(c, "merge_views_kernel", 0.0, c->stream, [=](hipStream_t st) {
+         return launch_merge_views(n_src, off_dev, off_dev + n_src + 1, mv_dev, max_views, pool_max, max_in, boxes, scores, classes, counts, thr, K,
+                                   max_out, out_boxes, out_scores, out_classes, out_view, out_row, out_counts, status, st);
+       }), "merge_views");
+  return 0;
+}
+
 }  // extern "C"

@@ -203,6 +203,11 @@ struct sylph_ctx {
   std::map<const void*, std::pair<void*, float*>> pw_weights;  // conv_pw.hip stage-image copies of 1x1 weights + scale/shift tables, keyed by the igemm-layout pointer
   void* pw_trash = nullptr;                 // conv_pw.hip trash slots (4 KiB)
   Plan* cur = nullptr;
+  // sylph_merge_views: the call's view tables (scratch: rewritten by every call; the event guards the host copy's reuse)
+  void* merge_tab = nullptr;
+  size_t merge_tab_cap = 0;
+  std::vector<char> merge_host;
+  hipEvent_t merge_ev = nullptr;
   void* zeros = nullptr;  // 256 B of zeros (conv out-of-image taps)
   // small batches: the two FCOS towers of a head pass run on two streams (fork / join events around the bbox tower, api_head.hip)
   hipStream_t side_stream = nullptr;

@@ -109,6 +109,58 @@ int launch_resize_preprocess(DType dt, const ResizeDesc* descs_dev, const int* t
   return (int)hipGetLastError();
 }
 
+// Sibling of resize_preprocess_kernel for VIEWS of device-resident sources (sylph_preprocess_views): image b of the batch is the crop
+// (x0, y0) + (cw, ch) of its source, resized with the (cw -> new_w) / (ch -> new_h) tables -- a pixel outside the crop never contributes:
+// the tables know the crop only -- and mirrored AFTER the resize (detectron2 puts the flip behind the resize in its transform list):
+// output column x of a flipped view takes the table entry of column new_w - 1 - x.  The arithmetic per output pixel is the kernel's
+// above, so a view equals what sylph_preprocess_u8 writes for a host-made copy of it, bit for bit.
+template <typename T>
+__global__ void view_preprocess_kernel(const ViewDesc* descs, const int* __restrict__ tab, T* out, int H, int W, float m0, float m1,
+                                       float m2, float is0, float is1, float is2, int rgb_input) {
+  const int b = blockIdx.z, y = blockIdx.y;
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  if (x >= W) return;
+  const ViewDesc d = descs[b];
+  float v0 = 0.f, v1 = 0.f, v2 = 0.f;
+  if (y < d.new_h && x < d.new_w) {
+    const int xs = d.flip ? d.new_w - 1 - x : x;
+    const int xmin = tab[d.hb_off + 2 * xs], xn = tab[d.hb_off + 2 * xs + 1];
+    const int ymin = tab[d.vb_off + 2 * y], yn = tab[d.vb_off + 2 * y + 1];
+    const int* kh = tab + d.hk_off + xs * d.ksh;
+    const int* kv = tab + d.vk_off + y * d.ksv;
+    int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+    for (int j = 0; j < yn; ++j) {
+      const unsigned char* row = d.src + ((size_t)(d.y0 + ymin + j) * d.pitch + d.x0 + xmin) * 3;
+      int h0 = 1 << 21, h1 = 1 << 21, h2 = 1 << 21;
+      for (int i = 0; i < xn; ++i) {
+        const int k = kh[i];
+        h0 += row[3 * i] * k; h1 += row[3 * i + 1] * k; h2 += row[3 * i + 2] * k;
+      }
+      const int w = kv[j];
+      a0 += clip8(h0) * w; a1 += clip8(h1) * w; a2 += clip8(h2) * w;
+    }
+    int c0 = clip8(a0), c1 = clip8(a1), c2 = clip8(a2);
+    if (rgb_input) { const int t = c0; c0 = c2; c2 = t; }
+    v0 = ((float)c0 - m0) * is0;
+    v1 = ((float)c1 - m1) * is1;
+    v2 = ((float)c2 - m2) * is2;
+  }
+  T* o = out + (((size_t)b * H + y) * W + x) * 4;
+  o[0] = Cvt<T>::from_f(v0); o[1] = Cvt<T>::from_f(v1); o[2] = Cvt<T>::from_f(v2); o[3] = Cvt<T>::from_f(0.f);
+}
+
+int launch_view_preprocess(DType dt, const ViewDesc* descs_dev, const int* tab_dev, void* out, int B, int H, int W,
+                           const float* mean, const float* stdv, int rgb_input, hipStream_t s) {
+  dim3 grid((W + 127) / 128, H, B), block(128);
+  if (dt == DT_BF16)
+    hipLaunchKernelGGL(view_preprocess_kernel<bf16_t>, grid, block, 0, s, descs_dev, tab_dev, (bf16_t*)out, H, W, mean[0], mean[1],
+                       mean[2], 1.f / stdv[0], 1.f / stdv[1], 1.f / stdv[2], rgb_input);
+  else
+    hipLaunchKernelGGL(view_preprocess_kernel<float>, grid, block, 0, s, descs_dev, tab_dev, (float*)out, H, W, mean[0], mean[1],
+                       mean[2], 1.f / stdv[0], 1.f / stdv[1], 1.f / stdv[2], rgb_input);
+  return (int)hipGetLastError();
+}
+
 // [B][H][W][4] compute dtype -> (B,3,H,W) fp32 NCHW (test boundary: the preprocessed network input)
 template <typename T>
 __global__ void export_input_kernel(const T* __restrict__ x, float* __restrict__ out, int H, int W) {

@@ -8,6 +8,13 @@ struct ImageDesc { const float* ptr; int h, w; };   // one (3,h,w) fp32 plane-ma
 struct RowSeg { int row0, nrows; };                 // a run of rows (one GroupNorm sample)
 // one uint8 HWC image of the fused resize input pipeline: source, target size, offsets of its tables in the int table buffer
 struct ResizeDesc { const unsigned char* src; int h, w, new_h, new_w; int hb_off, hk_off, vb_off, vk_off, ksh, ksv; };
+// one VIEW of a device-resident uint8 HWC source (sylph_preprocess_views): the crop (x0, y0) + (cw, ch) of a source whose rows are
+// `pitch` pixels apart, resized to new_h x new_w with the tables of (cw -> new_w) / (ch -> new_h), mirrored afterwards when flip != 0
+struct ViewDesc { const unsigned char* src; int pitch, x0, y0, new_h, new_w, flip; int hb_off, hk_off, vb_off, vk_off, ksh, ksv; };
+// one view of sylph_merge_views: its source, the crop origin and width in source pixels, mirrored or not
+struct MergeView { int src; float x0, y0, w; int flip; };
+// rows one source's views may hold together (max_in x its views): keys, boxes, classes and kept positions of the whole pool live in LDS
+constexpr int MERGE_POOL_CAP = 4096;
 
 constexpr int GN_ROWS_PER_CHUNK = 256;
 // Block cap of the head's persistent streaming kernels -- gn_logits_kernel<false / true> and gn_taps_kernel (head_fused.hip),
@@ -83,7 +90,15 @@ int launch_preprocess(DType dt, const ImageDesc* imgs_dev, void* out, int B, int
                       const float* stdv, hipStream_t s);
 int launch_resize_preprocess(DType dt, const ResizeDesc* descs_dev, const int* tab_dev, void* out, int B, int H, int W,
                              const float* mean, const float* stdv, int rgb_input, hipStream_t s);
+int launch_view_preprocess(DType dt, const ViewDesc* descs_dev, const int* tab_dev, void* out, int B, int H, int W,
+                           const float* mean, const float* stdv, int rgb_input, hipStream_t s);
 int launch_export_input(DType dt, const void* x, float* out, int B, int H, int W, hipStream_t s);
+// merge_views.hip: one block per source; src_off [n_src + 1] / src_views: the views of every source in ascending order; pool_max: the
+// largest max_in x views of a source (<= MERGE_POOL_CAP); status (one int) is cleared here and receives 2 when a source was truncated
+int launch_merge_views(int n_src, const int* src_off, const int* src_views, const MergeView* views, int max_views_per_src, int pool_max,
+                       int max_in, const float* boxes, const float* scores, const int* classes, const int* counts, float nms_thresh,
+                       int post_nms_topk, int max_out, float* out_boxes, float* out_scores, int* out_classes, int* out_view, int* out_row,
+                       int* out_counts, int* status, hipStream_t s);
 int launch_maxpool(DType dt, const void* in, void* out, int B, int H, int W, int C, int Ho, int Wo, hipStream_t s);
 int launch_groupnorm(DType dt, void* x, const RowSeg* segs_dev, int nseg, int max_rows, int ld, const float* gamma,
                      const float* beta, float eps, int relu, float* partial, float2* stats, hipStream_t s);

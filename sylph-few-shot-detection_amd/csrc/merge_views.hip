@@ -1,0 +1,241 @@
+// Merge of the detections of several VIEWS of one source image (test-time augmentation, tiled inference): gfx950.
+// Every view was decoded on its own (sylph_decode_nms with the view's crop size as output size), so its boxes are in crop pixels, in the
+// mirrored crop for a flipped view.  One 1024-thread block per source:
+//   1  pool: the rows of the source's views in ascending view index, rows in order; key = (ordered score bits << 32) | ~(view * max_in + row)
+//   2  bitonic sort of the keys in LDS, descending: by score, ties to the lower view, then to the lower row (the keys are unique)
+//   3  boxes back to source coordinates, in sorted order, into LDS: flipped (x1, x2) <- (w - x2, w - x1); then x += x0, y += y0 -- plain
+//      fp32 operations in that order, no clip (this file is built without FMA contraction, like detect.hip)
+//   4  the walk of nms_kernel (detect.hip) over the sorted pool in chunks of 64 boxes: ballots against the boxes kept in earlier chunks,
+//      a 64 x 64 bit matrix inside the chunk, a serial resolve in wave 0; same overlap arithmetic, same post-NMS keep rule
+//   5  emit: box, score, class and the (view, row) the detection came from
+// Nothing is kept between calls and no atomic touches global memory.
+#include "common.h"
+#include "kernels.h"
+
+namespace sylph {
+
+// float bits -> unsigned that orders like the float (-0 as +0)
+__device__ __forceinline__ unsigned merge_score_key(float s) {
+  const unsigned u = __float_as_uint(s);
+  if ((u << 1) == 0u) return 0x80000000u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// IoU > thr for two boxes of the same class: the arithmetic of nms_overlap (detect.hip)
+__device__ __forceinline__ bool merge_overlap(float x1, float y1, float x2, float y2, float iarea, float4 b, float thr) {
+  const float xx1 = fmaxf(x1, b.x), yy1 = fmaxf(y1, b.y);
+  const float xx2 = fminf(x2, b.z), yy2 = fminf(y2, b.w);
+  const float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
+  const float inter = w * h;
+  const float jarea = (b.z - b.x) * (b.w - b.y);
+  return inter / (iarea + jarea - inter) > thr;
+}
+
+__device__ __forceinline__ unsigned long long merge_shfl_u64(unsigned long long v, int src) {
+  const unsigned lo = __shfl((unsigned)(v & 0xffffffffull), src);
+  const unsigned hi = __shfl((unsigned)(v >> 32), src);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// dynamic LDS: keys [pool_p2] u64 | boxes [pool_p2] float4 | classes [pool_p2] int | view prefix [max_views + 1] int | kept [pool_p2] u16
+__global__ __launch_bounds__(1024) void merge_views_kernel(const int* __restrict__ src_off, const int* __restrict__ src_views,
+                                                           const MergeView* __restrict__ views, int pool_p2, int max_views, int max_in,
+                                                           const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                           const int* __restrict__ classes, const int* __restrict__ counts, float thr, int K,
+                                                           int max_out, float* out_boxes, float* out_scores, int* out_classes, int* out_view,
+                                                           int* out_row, int* out_counts, int* status) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char merge_lds[];
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(merge_lds);
+  float4* s_box = reinterpret_cast<float4*>(merge_lds + (size_t)8 * pool_p2);
+  int* s_cls = reinterpret_cast<int*>(merge_lds + (size_t)24 * pool_p2);
+  int* s_pref = s_cls + pool_p2;
+  unsigned short* kept_pos = reinterpret_cast<unsigned short*>(s_pref + max_views + 1);
+  __shared__ unsigned long long s_part[16];
+  __shared__ unsigned s_d[64][2];
+  __shared__ float4 s_box4[64];
+  __shared__ int s_cls4[64];
+  __shared__ int s_kept_total, s_stop;
+  const int src = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int v0 = src_off[src], nv = min(src_off[src + 1] - v0, max_views);
+  // 1: rows per view (a count outside [0, max_in] is clamped), their prefix, the keys
+  for (int i = t; i < nv; i += 1024) {
+    const int cn = counts[src_views[v0 + i]];
+    s_pref[i + 1] = cn < 0 ? 0 : (cn > max_in ? max_in : cn);
+  }
+  if (t == 0) s_pref[0] = 0;
+  __syncthreads();
+  if (t == 0)
+    for (int i = 0; i < nv; ++i) s_pref[i + 1] += s_pref[i];
+  __syncthreads();
+  const unsigned n = min((unsigned)s_pref[nv], (unsigned)pool_p2);  // (the host has checked nv * max_in <= pool_p2)
+  unsigned P = 64;
+  while (P < n) P <<= 1;
+  for (unsigned i = t; i < P; i += 1024) {
+    unsigned long long key = 0ull;  // below every real key
+    if (i < n) {
+      int lo = 0, hi = nv - 1;  // the view whose rows hold pool position i: last k with s_pref[k] <= i
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((unsigned)s_pref[mid] <= i) lo = mid; else hi = mid - 1;
+      }
+      const unsigned g = (unsigned)src_views[v0 + lo] * (unsigned)max_in + (i - (unsigned)s_pref[lo]);
+      key = ((unsigned long long)merge_score_key(scores[g]) << 32) | (unsigned long long)(~g);
+    }
+    keys[i] = key;
+  }
+  __syncthreads();
+  // 2: bitonic network over P >= 64 keys (P a power of two; the pool itself is any size: the padding keys sort to the end)
+  for (unsigned size = 2; size <= P; size <<= 1) {
+    for (unsigned stride = size >> 1; stride > 0; stride >>= 1) {
+      for (unsigned u = t; u < (P >> 1); u += 1024) {
+        const unsigned lo = ((u / stride) * (stride << 1)) + (u % stride);
+        const unsigned hi = lo + stride;
+        const bool desc = ((lo & size) == 0);
+        const unsigned long long a = keys[lo], b = keys[hi];
+        if ((a < b) == desc) { keys[lo] = b; keys[hi] = a; }
+      }
+      __syncthreads();
+    }
+  }
+  // 3: boxes in source coordinates, classes, in sorted order
+  for (unsigned i = t; i < n; i += 1024) {
+    const unsigned g = ~(unsigned)(keys[i] & 0xffffffffull);
+    const MergeView mv = views[g / (unsigned)max_in];
+    const float4 b = *reinterpret_cast<const float4*>(boxes + (size_t)g * 4);
+    float x1 = b.x, x2 = b.z;
+    if (mv.flip) { x1 = mv.w - b.z; x2 = mv.w - b.x; }
+    s_box[i] = make_float4(x1 + mv.x0, b.y + mv.y0, x2 + mv.x0, b.w + mv.y0);
+    s_cls[i] = classes[g];
+  }
+  if (t == 0) { s_kept_total = 0; s_stop = 0; }
+  __syncthreads();
+  // 4 + 5: the chunk walk of nms_kernel
+  const int nw = (int)((n + 63) / 64);
+  const bool nms_on = thr > 0.f;
+  int kept_total = 0, nout = 0;  // wave 0 keeps the running state; kept_total is mirrored in LDS for the other waves
+  float kth = 0.f;
+  bool have_kth = false, truncated = false;
+  for (int c = 0; c < nw; ++c) {
+    const unsigned b0 = c * 64;
+    if (wave == 0) {
+      const unsigned bi = b0 + lane;
+      if (bi < n) {
+        s_box4[lane] = s_box[bi];
+        s_cls4[lane] = s_cls[bi];
+      } else {
+        s_box4[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+        s_cls4[lane] = -1 - lane;  // matches nothing
+      }
+      s_d[lane][0] = 0u; s_d[lane][1] = 0u;
+    }
+    __syncthreads();
+    const int ktot = s_kept_total;
+    const float4 mb = s_box4[lane];
+    const int mc = s_cls4[lane];
+    bool sup = false;
+    if (nms_on) {
+      for (int k = wave; k < ktot; k += 16) {
+        const int kp = kept_pos[k];
+        if (s_cls[kp] != mc) continue;
+        const float4 kb = s_box[kp];
+        const float karea = (kb.z - kb.x) * (kb.w - kb.y);
+        sup = sup || merge_overlap(kb.x, kb.y, kb.z, kb.w, karea, mb, thr);
+      }
+      const int i = t >> 4, jq = t & 15;
+      const float4 ib = s_box4[i];
+      const int ic = s_cls4[i];
+      const float iarea = (ib.z - ib.x) * (ib.w - ib.y);
+      unsigned bits = 0u;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int j = 4 * jq + e;
+        if (j > i && s_cls4[j] == ic && merge_overlap(ib.x, ib.y, ib.z, ib.w, iarea, s_box4[j], thr)) bits |= 1u << (j & 31);
+      }
+      if (bits) atomicOr(&s_d[i][jq >> 3], bits);
+    }
+    const unsigned long long part = __ballot(sup);
+    if (lane == 0) s_part[wave] = part;
+    __syncthreads();
+    if (wave == 0) {
+      const unsigned bi = b0 + lane;
+      const bool valid = bi < n;
+      unsigned long long cur = 0ull;
+#pragma unroll
+      for (int w = 0; w < 16; ++w) cur |= s_part[w];
+      if (n - b0 < 64u) cur |= ~0ull << (n - b0);
+      const unsigned long long d = ((unsigned long long)s_d[lane][1] << 32) | (unsigned long long)s_d[lane][0];
+      unsigned long long keptmask = 0ull;
+      for (int b = 0; b < 64; ++b) {
+        const unsigned long long db = merge_shfl_u64(d, b);
+        if (!((cur >> b) & 1ull)) {
+          keptmask |= 1ull << b;
+          cur |= db;
+        }
+      }
+      const int nk = __popcll(keptmask);
+      const bool is_kept = (keptmask >> lane) & 1ull;
+      const int rank = kept_total + __popcll(keptmask & ((1ull << lane) - 1ull));
+      if (is_kept) kept_pos[rank] = (unsigned short)bi;
+      const unsigned g = valid ? ~(unsigned)(keys[bi] & 0xffffffffull) : 0u;
+      const float score = valid ? scores[g] : 0.f;
+      if (K > 0 && !have_kth && kept_total + nk >= K) {
+        const unsigned long long sel = __ballot(is_kept && rank == K - 1);
+        const int srcl = __ffsll((long long)sel) - 1;
+        kth = __shfl(score, srcl);
+        have_kth = true;
+      }
+      const bool emit = is_kept && (K <= 0 || rank < K || score >= kth);
+      const unsigned long long em = __ballot(emit);
+      const int slot = nout + __popcll(em & ((1ull << lane) - 1ull));
+      if (emit) {
+        if (slot < max_out) {
+          const size_t o = (size_t)src * max_out + slot;
+          out_boxes[o * 4 + 0] = mb.x; out_boxes[o * 4 + 1] = mb.y; out_boxes[o * 4 + 2] = mb.z; out_boxes[o * 4 + 3] = mb.w;
+          out_scores[o] = score;
+          out_classes[o] = mc;
+          out_view[o] = (int)(g / (unsigned)max_in);
+          out_row[o] = (int)(g % (unsigned)max_in);
+        } else {
+          truncated = true;
+        }
+      }
+      nout += __popcll(em);
+      kept_total += nk;
+      bool stop = false;
+      if (K > 0 && kept_total >= K && c + 1 < nw) {  // nothing below the K-th kept score can be emitted any more
+        const float next_score = scores[~(unsigned)(keys[b0 + 64] & 0xffffffffull)];
+        stop = next_score < kth;
+      }
+      if (lane == 0) { s_kept_total = kept_total; s_stop = stop ? 1 : 0; }
+    }
+    __syncthreads();
+    if (s_stop) break;
+  }
+  if (wave == 0) {
+    if (__any(truncated) && lane == 0) *status = 2;  // (every truncated source stores the same word: no atomic)
+    if (lane == 0) out_counts[src] = nout < max_out ? nout : max_out;
+  }
+}
+
+int launch_merge_views(int n_src, const int* src_off, const int* src_views, const MergeView* views, int max_views_per_src, int pool_max,
+                       int max_in, const float* boxes, const float* scores, const int* classes, const int* counts, float nms_thresh,
+                       int post_nms_topk, int max_out, float* out_boxes, float* out_scores, int* out_classes, int* out_view, int* out_row,
+                       int* out_counts, int* status, hipStream_t s) {
+  if (n_src <= 0 || pool_max < 0 || pool_max > MERGE_POOL_CAP || max_in <= 0 || max_out <= 0 || max_views_per_src < 0) return (int)hipErrorInvalidValue;
+  int p2 = 64;
+  while (p2 < pool_max) p2 <<= 1;
+  // keys 8 + boxes 16 + classes 4 + kept 2 bytes per pool slot, the view prefix in between (4-byte aligned: the kept positions are u16)
+  const size_t lds = (size_t)30 * p2 + (size_t)4 * (max_views_per_src + 1);
+  constexpr int LDS_MAX = 30 * MERGE_POOL_CAP + 4 * (MERGE_POOL_CAP + 1);  // 139 268 B of the CU's 160 KiB
+  static PerDeviceOnce once;
+  if (!once.run(current_device(), [] {
+        return hipFuncSetAttribute((const void*)merge_views_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX) == hipSuccess;
+      }))
+    return -7;
+  if (hipMemsetAsync(status, 0, sizeof(int), s) != hipSuccess) return -8;
+  hipLaunchKernelGGL(merge_views_kernel, dim3(n_src), dim3(1024), lds, s, src_off, src_views, views, p2, max_views_per_src, max_in, boxes, scores,
+                     classes, counts, nms_thresh, post_nms_topk, max_out, out_boxes, out_scores, out_classes, out_view, out_row, out_counts, status);
+  return (int)hipGetLastError();
+}
+
+}  // namespace sylph

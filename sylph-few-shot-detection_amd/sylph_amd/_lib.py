@@ -50,6 +50,7 @@ PROTOTYPES = {
                                  POINTER(c_int), POINTER(c_int)]),
     "sylph_preprocess_u8": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                     POINTER(c_int), c_int, POINTER(c_int), POINTER(c_int)]),
+    "sylph_preprocess_views": (c_int, [c_void_p, c_int, POINTER(c_void_p)] + [POINTER(c_int)] * 9 + [c_int, POINTER(c_int), POINTER(c_int)]),
     "sylph_export_input": (c_int, [c_void_p, c_void_p]),
     "sylph_backbone_fpn": (c_int, [c_void_p]),
     "sylph_import_pyramid": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int),
@@ -67,6 +68,8 @@ PROTOTYPES = {
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylph_decode_nms_codesets": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylph_merge_views": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_int),
+                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 7),
     "sylph_codegen": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sylph_codegen_classes": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "sylph_codegen_rois": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_int, POINTER(c_int), c_void_p]),

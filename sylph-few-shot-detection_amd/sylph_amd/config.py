@@ -235,7 +235,10 @@ DEFAULTS = {
                  "NOVEL_CLASSES_SPLIT": "", "NUMS_CLASSES": [0]},
     "DATALOADER": {"NUM_WORKERS": 4, "ASPECT_RATIO_GROUPING": True},
     "SOLVER": {"IMS_PER_BATCH": 16, "MAX_ITER": 40000},
-    "TEST": {"EVAL_PERIOD": 0, "REPEAT_TEST": 1, "DETECTIONS_PER_IMAGE": 100},
+    "TEST": {"EVAL_PERIOD": 0, "REPEAT_TEST": 1, "DETECTIONS_PER_IMAGE": 100,
+             # detectron2's test-time augmentation keys with its defaults: multi-scale + horizontal flip views of every query image,
+             # merged on the device (sylph_amd.views.tta_views, MetaOneStageDetector.forward_instances_views)
+             "AUG": {"ENABLED": False, "MIN_SIZES": (400, 500, 600, 700, 800, 900, 1000, 1100, 1200), "MAX_SIZE": 4000, "FLIP": True}},
 }
 
 

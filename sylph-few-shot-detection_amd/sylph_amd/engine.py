@@ -357,6 +357,30 @@ class Engine:
         self._batch = (B, ph.value, pw.value, [(int(s[0]), int(s[1])) for s in new_sizes])
         return ph.value, pw.value
 
+    def preprocess_views(self, sources: List[torch.Tensor], views: List[Dict], rgb_input: bool = False) -> Tuple[int, int]:
+        """The input pipeline for VIEWS of resident sources (sylph_preprocess_views): `sources` are (h, w, 3) uint8 HWC images (device,
+        or pinned host: each is copied once, however many views name it), `views` dicts {"source": index into sources, "crop": (x0, y0,
+        cw, ch), "size": (new_h, new_w), "flip": bool} (sylph_amd.views).  Image b of the batch is crop -> PIL-exact BILINEAR resize ->
+        mirror when flipped -> BGR -> normalise -> pad: what preprocess_u8 writes for a host-made copy of the view, in one kernel."""
+        self._stream()
+        srcs = [im.to(self.device, non_blocking=True).contiguous() for im in sources]
+        for im in srcs:
+            assert im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3, "uint8 HWC images expected"
+        B = len(views)
+        vs = [srcs[int(v["source"])] for v in views]
+        ptrs = (c_void_p * B)(*[im.data_ptr() for im in vs])
+        crops = [[int(t) for t in v["crop"]] for v in views]
+        sizes = [(int(v["size"][0]), int(v["size"][1])) for v in views]
+        ph, pw = c_int(0), c_int(0)
+        check(self.L.sylph_preprocess_views(self._ctx, B, ptrs, _iarr([im.shape[0] for im in vs]), _iarr([im.shape[1] for im in vs]),
+                                            _iarr([c[0] for c in crops]), _iarr([c[1] for c in crops]), _iarr([c[2] for c in crops]),
+                                            _iarr([c[3] for c in crops]), _iarr([s[0] for s in sizes]), _iarr([s[1] for s in sizes]),
+                                            _iarr([1 if v.get("flip", False) else 0 for v in views]), int(rgb_input),
+                                            ctypes.byref(ph), ctypes.byref(pw)), "preprocess_views")
+        self._keep = srcs
+        self._batch = (B, ph.value, pw.value, sizes)
+        return ph.value, pw.value
+
     def export_input(self) -> torch.Tensor:
         self._stream()
         B, H, W, _ = self._batch
@@ -695,6 +719,81 @@ class Engine:
         cols = [[nar(r, 0, 0, n) for r, n in zip(t.unbind(0), cnt)] for t in (boxes, scores, classes, levels, locs, cand)]
         keys = ("pred_boxes", "scores", "pred_classes", "fpn_levels", "locations", "cand_index")
         return [dict(zip(keys, vals)) for vals in zip(*cols)]
+
+    # ---- views: per-view rows of several steps, merged per source ------------------------------------------
+    def new_view_rows(self, n_views: int, max_in: Optional[int] = None) -> Dict:
+        """Row buffers [n_views][max_in] for the detections of n_views views: every step's `decode_rows` fills the slice of its views."""
+        if max_in is None:
+            max_in = self.default_max_out()
+        dev = self.device
+        ints = torch.empty(3, n_views, max_in, device=dev, dtype=torch.int32)  # classes | levels | candidate ordinals
+        meta = torch.zeros(2 * n_views, device=dev, dtype=torch.int32)         # counts [n_views] | status word of every decode
+        return {"n_views": n_views, "max_in": int(max_in), "boxes": torch.empty(n_views, max_in, 4, device=dev),
+                "scores": torch.empty(n_views, max_in, device=dev), "classes": ints[0], "levels": ints[1], "cand": ints[2],
+                "locations": torch.empty(n_views, max_in, 2, device=dev), "meta": meta, "counts": meta[:n_views], "steps": 0}
+
+    def decode_rows(self, rows: Dict, row0: int, out_sizes: Optional[List[Tuple[int, int]]] = None):
+        """decode + NMS of the current batch into rows [row0, row0 + B) of `rows` (decode writes [B][max_out] rows, so the steps of a
+        view list land in consecutive slices).  Nothing is read back: `merge_views` fetches every step's status with the counts."""
+        self._stream()
+        B, n, m = self._batch[0], rows["n_views"], rows["max_in"]
+        if row0 < 0 or row0 + B > n:
+            raise ValueError(f"rows [{row0}, {row0 + B}) are outside the {n} view rows")
+        oh = _iarr([s[0] for s in out_sizes]) if out_sizes is not None else None
+        ow = _iarr([s[1] for s in out_sizes]) if out_sizes is not None else None
+        sl = lambda t: c_void_p(t[row0:].data_ptr())
+        check(self.L.sylph_decode_nms(self._ctx, oh, ow, m, sl(rows["boxes"]), sl(rows["scores"]), sl(rows["classes"]), sl(rows["levels"]),
+                                      sl(rows["locations"]), sl(rows["cand"]), sl(rows["counts"]),
+                                      c_void_p(rows["meta"].data_ptr() + 4 * (n + rows["steps"]))), "decode_nms")
+        rows["steps"] += 1
+
+    def merge_views(self, view_table: List[Dict], rows: Dict, max_out: Optional[int] = None, n_src: Optional[int] = None):
+        """One class-wise NMS over the views of every source (sylph_merge_views).  view_table[v] = {"source", "crop", "flip"} describes
+        view v, whose detections are rows["boxes" | "scores" | "classes"][v, :rows["counts"][v]] ([n_views][max_in]; classes int32), in
+        crop pixels.  -> per source a dict of pred_boxes (source pixels), scores, pred_classes, view_index, view_row (the input row of
+        each output).  One device->host copy: the merged counts with the status words of the merge and of every decode_rows step."""
+        self._stream()
+        nv = len(view_table)
+        boxes, scores, classes, counts = rows["boxes"], rows["scores"], rows["classes"], rows["counts"]
+        max_in = int(scores.shape[1])
+        if scores.shape[0] != nv or counts.numel() != nv:
+            raise ValueError(f"the view table has {nv} views, the row buffers {scores.shape[0]}")
+        assert boxes.dtype == torch.float32 and scores.dtype == torch.float32 and classes.dtype == torch.int32 and counts.dtype == torch.int32
+        assert boxes.is_contiguous() and scores.is_contiguous() and classes.is_contiguous() and counts.is_contiguous()
+        src = [int(v["source"]) for v in view_table]
+        if n_src is None:
+            n_src = max(src) + 1
+        if max_out is None:
+            max_out = self.default_max_out()
+        dev = self.device
+        farr = lambda v: (ctypes.c_float * len(v))(*[float(x) for x in v])
+        ob = torch.empty(n_src, max_out, 4, device=dev)
+        osc = torch.empty(n_src, max_out, device=dev)
+        oi = torch.empty(3, n_src, max_out, device=dev, dtype=torch.int32)  # classes | view | row
+        steps = int(rows.get("steps", 0))
+        tail = torch.empty(n_src + 1 + steps, device=dev, dtype=torch.int32)  # merged counts | merge status | decode status words
+        check(self.L.sylph_merge_views(self._ctx, n_src, nv, _iarr(src), farr([v["crop"][0] for v in view_table]),
+                                       farr([v["crop"][1] for v in view_table]), farr([v["crop"][2] for v in view_table]),
+                                       _iarr([1 if v.get("flip", False) else 0 for v in view_table]), max_in, _ptr(boxes), _ptr(scores),
+                                       _ptr(classes), _ptr(counts), max_out, _ptr(ob), _ptr(osc), _ptr(oi[0]), _ptr(oi[1]), _ptr(oi[2]),
+                                       _ptr(tail), c_void_p(tail.data_ptr() + 4 * n_src)), "merge_views")
+        if steps:
+            tail[n_src + 1:].copy_(rows["meta"][nv:nv + steps])
+        cnt = tail.tolist()  # the only sync
+        for st in cnt[n_src + 1:]:
+            if st & 1:
+                raise RuntimeError("sylph decode: per-level candidate capacity exceeded (raise cand_cap)")
+            if st & 2:
+                raise RuntimeError("sylph decode: more tied detections than max_out")
+        if cnt[n_src] & 2:
+            raise RuntimeError("sylph merge_views: more detections of a source than max_out")
+        wide = oi.long()
+        out = []
+        for s_ in range(n_src):
+            k = cnt[s_]
+            out.append({"pred_boxes": ob[s_, :k], "scores": osc[s_, :k], "pred_classes": wide[0, s_, :k], "view_index": wide[1, s_, :k],
+                        "view_row": wide[2, s_, :k]})
+        return out
 
     # ---- support path -------------------------------------------------------------------------------
     def _image_boxes(self, boxes: torch.Tensor) -> torch.Tensor:
@@ -1039,7 +1138,7 @@ class Engine:
     def profile_read(self) -> Dict[str, float]:
         """Summed conv-kernel time (HIP events on the launch stream), algorithmic FLOPs, launches -- and the same per kernel
         (`kernels`: name -> {ms, flops, launches})."""
-        mx = 32
+        mx = 64  # distinct kernel names of a step; the list is in order of first launch, so a short buffer would drop the last stages
         names = ctypes.create_string_buffer(mx * 64)
         ms, fl, ln, n = (ctypes.c_double * mx)(), (ctypes.c_double * mx)(), (c_int64 * mx)(), c_int(0)
         check(self.L.sylph_profile_read_kernels(self._ctx, mx, names, ms, fl, ln, ctypes.byref(n)), "profile_read_kernels")

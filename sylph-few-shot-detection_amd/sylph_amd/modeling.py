@@ -19,6 +19,7 @@ from torch import nn
 
 from .engine import Engine
 from .structures import Boxes, Instances
+from .views import DEFAULT_MAX_BATCH, check_views, make_view, plan_view_steps, tta_views, view_out_size
 
 logger = logging.getLogger(__name__)
 
@@ -261,6 +262,9 @@ class MetaOneStageDetector(nn.Module):
                                                in one step (group_episodes; pred_classes index the image's own dict)
                                                class_code_sets = [d_0, ..., d_{G-1}]: every image against G code sets in one step
                                                -> a list over sets of what class_code=d_g returns (forward_instances_code_sets)
+                                               inputs carrying "views" next to "image_u8", or cfg.TEST.AUG.ENABLED: every input is
+                                               run on a list of views (crop, size, flip) and the views' detections are merged on the
+                                               device (forward_instances_views)
     Training is out of scope: calling the model in training mode raises NotImplementedError."""
 
     def __init__(self, cfg, dtype: Optional[str] = None, device_index: Optional[int] = None):
@@ -314,6 +318,12 @@ class MetaOneStageDetector(nn.Module):
         if self.training:
             raise NotImplementedError("training is out of scope of the MI355X inference path; call model.eval()")
         sets = check_class_code_args(class_code, class_code_sets)
+        views = self._input_views(batched_inputs) if run_type == "meta_learn_test_instance" else None
+        if views is not None:
+            if sets is not None:
+                raise NotImplementedError("class_code_sets together with query views (inputs carrying \"views\", or TEST.AUG.ENABLED) is not "
+                                          "supported: run the view list once per code set with class_code")
+            return self.forward_instances_views(batched_inputs, class_code, views)
         if sets is not None:
             if run_type != "meta_learn_test_instance":
                 raise NotImplementedError(f"class_code_sets belongs to run_type 'meta_learn_test_instance', not {run_type!r}")
@@ -477,18 +487,7 @@ class MetaOneStageDetector(nn.Module):
             return self._to_results(self.proposal_generator.forward_episodes(codes, image_episode, out_sizes), out_sizes)
         pretrained = class_codes is None
         if class_codes is None:
-            # MetaFCOSHead.forward with support_set_per_class_code=None -> forward_base_train (fcos.py:543-578):
-            # logits = self.cls_logits(cls_tower), the pretrained base-class classifier.  A 1x1 cls_logits conv (the
-            # CLS_LOGITS_KERNEL_SIZE of the Meta-FCOS recipes) is exactly the class-conditional conv with fixed codes.
-            pre = getattr(self, "_pretrained_cls_logits", None)
-            if pre is None:
-                raise ValueError("class_code is None and the checkpoint has no proposal_generator.fcos_head.cls_logits weights")
-            if pre[0].dim() != 4 or tuple(pre[0].shape[2:]) not in ((1, 1), (3, 3)):
-                raise NotImplementedError(f"pretrained cls_logits with kernel {tuple(pre[0].shape[2:])}: only 1x1 and 3x3 "
-                                          "(MODEL.FCOS.CLS_LOGITS_KERNEL_SIZE) are supported")
-            if self.episodic_learning and not bool(self.cfg.MODEL.META_LEARN.CODE_GENERATOR.USE_BIAS):
-                raise NotImplementedError("pretrained cls_logits needs the bias path of the class-conditional conv (USE_BIAS)")
-            class_codes = {"cls_conv": pre[0].to(self.device), "cls_bias": pre[1].to(self.device)}
+            class_codes = self._pretrained_class_codes()
         w, b = class_codes["cls_conv"], class_codes.get("cls_bias")
         assert w.dim() == 4, f"Weight has dimension: {w.dim()}"
         assert w.size(1) == 256
@@ -500,6 +499,114 @@ class MetaOneStageDetector(nn.Module):
         else:
             dets = self.proposal_generator(w, b, out_sizes, raw=True) if pretrained else self.proposal_generator(w, b, out_sizes)
         return self._to_results(dets, out_sizes)
+
+    def _pretrained_class_codes(self) -> Dict[str, torch.Tensor]:
+        """class_code None: the checkpoint's own classifier as a code dict"""
+        # MetaFCOSHead.forward with support_set_per_class_code=None -> forward_base_train (fcos.py:543-578):
+        # logits = self.cls_logits(cls_tower), the pretrained base-class classifier.  A 1x1 cls_logits conv (the
+        # CLS_LOGITS_KERNEL_SIZE of the Meta-FCOS recipes) is exactly the class-conditional conv with fixed codes.
+        pre = getattr(self, "_pretrained_cls_logits", None)
+        if pre is None:
+            raise ValueError("class_code is None and the checkpoint has no proposal_generator.fcos_head.cls_logits weights")
+        if pre[0].dim() != 4 or tuple(pre[0].shape[2:]) not in ((1, 1), (3, 3)):
+            raise NotImplementedError(f"pretrained cls_logits with kernel {tuple(pre[0].shape[2:])}: only 1x1 and 3x3 "
+                                      "(MODEL.FCOS.CLS_LOGITS_KERNEL_SIZE) are supported")
+        if self.episodic_learning and not bool(self.cfg.MODEL.META_LEARN.CODE_GENERATOR.USE_BIAS):
+            raise NotImplementedError("pretrained cls_logits needs the bias path of the class-conditional conv (USE_BIAS)")
+        return {"cls_conv": pre[0].to(self.device), "cls_bias": pre[1].to(self.device)}
+
+    # ---- query views: test-time augmentation and tiled images ----------------------------------------------
+    view_max_batch = DEFAULT_MAX_BATCH  # views per step (plan_view_steps)
+
+    def _input_views(self, batched_inputs: List[Dict[str, Any]]):
+        """The view list of every input, or None when the batch has none: no input carries "views" and TEST.AUG.ENABLED is off.
+        An input's own "views" win; with TEST.AUG.ENABLED the others get detectron2's DatasetMapperTTA list (tta_views); without it an
+        input that has no views next to inputs that have some is one full-frame view at its "resize_hw"."""
+        cfg = getattr(self, "cfg", None)
+        aug = cfg.get("TEST", {}).get("AUG", {}) if hasattr(cfg, "get") else {}
+        enabled = bool(aug.get("ENABLED", False))
+        if not enabled and not any("views" in x for x in batched_inputs):
+            return None
+        out = []
+        for i, x in enumerate(batched_inputs):
+            if "image_u8" not in x:
+                why = "TEST.AUG.ENABLED" if enabled and "views" not in x else "an input with \"views\""
+                raise ValueError(f"input {i}: {why} needs the original uint8 image as \"image_u8\" (the views are cut from it on the device); "
+                                 "a float \"image\" has already been resized")
+            h, w = int(x["image_u8"].shape[0]), int(x["image_u8"].shape[1])
+            if "views" in x:
+                out.append(check_views(x["views"], h, w, f"input {i}: views"))
+            elif enabled:
+                out.append(tta_views(h, w, [int(s) for s in aug.MIN_SIZES], int(aug.MAX_SIZE), bool(aug.FLIP)))
+            else:
+                out.append([make_view((0, 0, w, h), x["resize_hw"])])
+        return out
+
+    def forward_instances_views(self, batched_inputs: List[Dict[str, Any]], class_codes, per_input_views):
+        """Every input on its views, merged per input: the views of the whole batch are planned into steps by resize target
+        (plan_view_steps); a step is preprocess_views (cut from the sources, which are uploaded once) -> backbone -> head -> decode at
+        the crop size into its slice of one row buffer; then ONE merge launch (class-wise NMS over the views of a source, in source
+        pixels) and one read-back.  class_codes: a dict (every view), a per-input list (all views of an input take its episode) or
+        None (the pretrained classifier).  -> [{"instances": Instances}] at the source's size, or at "height" / "width" when they differ
+        (rescaled and clipped as detector_postprocess does) with pred_boxes, scores, pred_classes and the provenance view_index (into the
+        input's own view list) / view_row."""
+        assert not self.training, "Not for training"
+        eng = self.engine
+        run_head = self._view_head(class_codes, len(batched_inputs))
+        table = [dict(v, source=i, view=k) for i, vs in enumerate(per_input_views) for k, v in enumerate(vs)]
+        steps = plan_view_steps(table, int(self.view_max_batch), int(getattr(self.backbone, "size_divisibility", 32)))
+        table = [table[i] for st in steps for i in st]  # view index = row of the buffer: step after step
+        sources = [x["image_u8"].to(self.device, non_blocking=True).contiguous() for x in batched_inputs]
+        rgb = str(batched_inputs[0].get("input_format", "BGR")) == "RGB"
+        rows = eng.new_view_rows(len(table))
+        row0 = 0
+        for st in steps:
+            vs = table[row0:row0 + len(st)]
+            eng.preprocess_views(sources, vs, rgb_input=rgb)
+            eng.backbone()
+            run_head([v["source"] for v in vs])
+            eng.decode_rows(rows, row0, [view_out_size(v) for v in vs])
+            row0 += len(st)
+        results = []
+        own_index = torch.tensor([v["view"] for v in table], device=self.device)  # row of the buffer -> index in the input's own view list
+        for x, src, d in zip(batched_inputs, sources, eng.merge_views(table, rows, n_src=len(batched_inputs))):
+            h, w = int(src.shape[0]), int(src.shape[1])
+            H, W = int(x.get("height", h)), int(x.get("width", w))
+            boxes, scores, classes = d["pred_boxes"], d["scores"], d["pred_classes"]
+            view_index, view_row = own_index[d["view_index"]], d["view_row"]
+            if (H, W) != (h, w):  # detector_postprocess: scale, clip, drop what became empty
+                boxes = boxes * boxes.new_tensor([W / w, H / h, W / w, H / h])
+                boxes = torch.minimum(boxes.clamp(min=0), boxes.new_tensor([W, H, W, H]))
+                keep = ((boxes[:, 2] - boxes[:, 0]) > 0) & ((boxes[:, 3] - boxes[:, 1]) > 0)
+                boxes, scores, classes, view_index, view_row = boxes[keep], scores[keep], classes[keep], view_index[keep], view_row[keep]
+            r = Instances((H, W))
+            r.pred_boxes = Boxes(boxes)
+            r.scores = scores
+            r.pred_classes = classes
+            r.view_index = view_index  # which of the input's views each detection came from, and its row in that view's decode
+            r.view_row = view_row
+            results.append({"instances": r})
+        return results
+
+    def _view_head(self, class_codes, num_inputs: int):
+        """-> run(view_sources): the head on the current batch of views, view b belonging to input view_sources[b]"""
+        eng = self.engine
+        if isinstance(class_codes, (list, tuple)):
+            dicts, input_episode = group_episodes(class_codes, num_inputs)
+            codes = [(d["cls_conv"], d.get("cls_bias")) for d in dicts]
+            for w, _ in codes:
+                assert w.dim() == 4, f"Weight has dimension: {w.dim()}"
+                assert w.size(1) == 256
+            return lambda view_sources: eng.head_episodes(codes, [input_episode[s] for s in view_sources])
+        pretrained = class_codes is None
+        if pretrained:
+            class_codes = self._pretrained_class_codes()
+        w, b = class_codes["cls_conv"], class_codes.get("cls_bias")
+        assert w.dim() == 4, f"Weight has dimension: {w.dim()}"
+        assert w.size(1) == 256
+        if pretrained and tuple(w.shape[2:]) == (3, 3):
+            return lambda view_sources: eng.head_pretrained()
+        return lambda view_sources: eng.head(w, b, raw=pretrained)
 
     def _run_backbone(self, batched_inputs: List[Dict[str, Any]]):
         """preprocess + backbone of the query batch -> the (height, width) each image's detections are scaled to"""

@@ -13,19 +13,9 @@ import torch
 
 from .evaluation import format_class_codes_shared
 from .runner import create_cfg, create_runner
+from .views import resize_shortest_edge_shape, tile_views  # noqa: F401  (resize_shortest_edge_shape: part of this module's surface)
 
 logger = logging.getLogger(__name__)
-
-
-def resize_shortest_edge_shape(h: int, w: int, size: int, max_size: int) -> Tuple[int, int]:
-    """detectron2 ResizeShortestEdge.get_output_shape (sylph/predictor.py:117-120 builds it with
-    [MIN_SIZE_TEST, MIN_SIZE_TEST], MAX_SIZE_TEST)."""
-    scale = size * 1.0 / min(h, w)
-    newh, neww = (size, scale * w) if h < w else (scale * h, size)
-    if max(newh, neww) > max_size:
-        s = max_size * 1.0 / max(newh, neww)
-        newh, neww = newh * s, neww * s
-    return int(newh + 0.5), int(neww + 0.5)
 
 
 def resize_image(img: np.ndarray, new_h: int, new_w: int) -> np.ndarray:
@@ -45,7 +35,12 @@ def resize_image(img: np.ndarray, new_h: int, new_w: int) -> np.ndarray:
 class SylphPredictor:
     def __init__(self, config_file: str, weight_path: str, class_code_path: str,
                  runner_name: str = "sylph.runner.MetaFCOSRunner", test_dataset_names: Dict = None,
-                 dtype: Optional[str] = None, fused_preprocess: bool = True):
+                 dtype: Optional[str] = None, fused_preprocess: bool = True, tiles: Optional[Tuple[int, int]] = None,
+                 tile_overlap: float = 0.2):
+        """tiles = (tile_h, tile_w): large images are run as a grid of overlapping crops of that size plus the full frame, each resized
+        by the MIN_SIZE_TEST / MAX_SIZE_TEST rule, and the detections are merged on the device in the coordinates of the image
+        (sylph_amd.views.tile_views).  cfg.TEST.AUG.ENABLED gives multi-scale / flip test-time augmentation the same way.  Both need
+        the fused uint8 input path."""
         logger.info("SylphPredictor initializing...")
         runner = create_runner(runner_name)
         self.cfg = create_cfg(runner.get_default_cfg(), config_file, None).clone()
@@ -70,6 +65,10 @@ class SylphPredictor:
         self.min_size = int(self.cfg.INPUT.MIN_SIZE_TEST)
         self.max_size = int(self.cfg.INPUT.MAX_SIZE_TEST)
         self.fused_preprocess = fused_preprocess
+        self.tiles = (int(tiles[0]), int(tiles[1])) if tiles is not None else None
+        self.tile_overlap = float(tile_overlap)
+        if self.tiles is not None and not fused_preprocess:
+            raise ValueError("tiles needs fused_preprocess=True: the tiles are cut from the uint8 original on the device")
         self._pinned = {}  # (h, w) -> pinned uint8 staging buffer for the asynchronous H2D copy
         self.input_format = self.cfg.INPUT.FORMAT
         assert self.input_format in ["RGB", "BGR"], self.input_format
@@ -110,7 +109,12 @@ class SylphPredictor:
                     self._pinned.clear()
                 buf = self._pinned[(height, width)] = torch.empty(height, width, 3, dtype=torch.uint8, pin_memory=True)
             buf.copy_(torch.from_numpy(np.ascontiguousarray(original_image)))
-            return {"image_u8": buf, "resize_hw": (nh, nw), "input_format": self.input_format, "height": height, "width": width}
+            inputs = {"image_u8": buf, "resize_hw": (nh, nw), "input_format": self.input_format, "height": height, "width": width}
+            if self.tiles is not None:
+                inputs["views"] = tile_views(height, width, self.tiles, self.tile_overlap, self.min_size, self.max_size)
+            return inputs
+        if self.tiles is not None:
+            raise ValueError(f"tiles needs a uint8 image, got {original_image.dtype}")
         if self.input_format == "RGB":
             original_image = original_image[:, :, ::-1]
         image = resize_image(np.ascontiguousarray(original_image), nh, nw)

@@ -230,6 +230,11 @@ class MetaFCOSRunner:
         max_iter = cfg.get("SOLVER", {}).get("MAX_ITER", None) if hasattr(cfg, "get") else None
         is_final = train_iter is None or (max_iter is not None and train_iter == max_iter - 1)
         repeat = int(cfg.TEST.REPEAT_TEST) if is_final and "TEST" in cfg and "REPEAT_TEST" in cfg.TEST else 1
+        if is_final and "TEST" in cfg and bool(cfg.TEST.get("AUG", {}).get("ENABLED", False)):
+            # meta_fcos_runner.py:633-651 wraps the model in GeneralizedRCNNWithTTA here, which a MetaOneStageDetector cannot go through.
+            # This model runs the views itself (forward_instances_views reads cfg.TEST.AUG): the ordinary query loop below IS the
+            # test-time-augmented evaluation; the query loader must hand out the uint8 originals ("image_u8")
+            logger.info("Running inference with test-time augmentation ...")
         results = OrderedDict()
         results[model_tag] = OrderedDict()
         main = D.get_rank() == 0
