@@ -419,6 +419,16 @@ Mbv2Route pick_mbv2_route(const sylph_ctx* c, const sylph_ctx::MbBlock& blk, int
   return Mbv2Route::chain;
 }
 
+// Images per run of the chain.  conv_igemm addresses its operands with 31-bit element offsets: a batch whose largest tensor of this block
+// passes that is built as several chains over runs of `*run` images and a shorter last one.  One image that passes it alone is refused.
+int mbv2_chain_run(const sylph_ctx::MbBlock& blk, int B, int Hin, int Win, int* run) {
+  const int Ho = (Hin - 1) / blk.stride + 1, Wo = (Win - 1) / blk.stride + 1;
+  const size_t per_img = std::max((size_t)Hin * Win * std::max(blk.cin_ld, blk.t != 1 ? blk.hid_ld : 0), (size_t)Ho * Wo * std::max(blk.hid_ld, blk.cout_ld));
+  if (per_img > (size_t)0x7fffffff) return fail("image too large for the MobileNetV2 chain: " + std::to_string(per_img) + " elements per image");
+  *run = (int)std::min<size_t>((size_t)B, (size_t)0x7fffffff / per_img);
+  return 0;
+}
+
 int add_mbv2_block(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::MbBlock& blk, int B, const void* X, int Hin, int Win, void* Y, void* h1, void* h2) {
   const int Ho = (Hin - 1) / blk.stride + 1, Wo = (Win - 1) / blk.stride + 1;
   if (pick_mbv2_route(c, blk, B, Hin, Win) == Mbv2Route::fused) {
@@ -427,10 +437,9 @@ int add_mbv2_block(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::MbBloc
     ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_mbv2_kernel", fl, s, [=](hipStream_t st) { return launch_conv_mbv2(a, st); }); });
     return 0;
   }
-  // conv_igemm addresses its operands with 31-bit element offsets: a batch whose largest tensor of this block passes that is built as
-  // several chains over runs of images, all through the same h1 / h2 (the launches of one op list run in order)
-  const size_t per_img = std::max((size_t)Hin * Win * std::max(blk.cin_ld, blk.t != 1 ? blk.hid_ld : 0), (size_t)Ho * Wo * std::max(blk.hid_ld, blk.cout_ld));
-  const int chunk = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, (size_t)0x7fffffff / per_img));
+  // the runs all go through the same h1 / h2 (the launches of one op list run in order)
+  int chunk = 0;
+  RET(mbv2_chain_run(blk, B, Hin, Win, &chunk));
   if (chunk < B) {
     const size_t e = c->esz();
     for (int b0 = 0; b0 < B; b0 += chunk)

@@ -604,6 +604,9 @@ inline int mbv2_ld(const sylph_ctx* c, int C) { const int p = mbv2_pad(c, C), q 
 // hid_ld elements; unused when t == 1) and h2 (the depthwise output, B * Ho * Wo * hid_ld) are scratch.  Shared by build_backbone and
 // the parity entry sylph_mbv2_block.
 Mbv2Route pick_mbv2_route(const sylph_ctx* c, const sylph_ctx::MbBlock& blk, int B, int Hin, int Win);
+// images per run when add_mbv2_block builds the chain (B unless a tensor of the block would pass 2^31 - 1 elements); fails by name for an
+// image that is too large alone
+int mbv2_chain_run(const sylph_ctx::MbBlock& blk, int B, int Hin, int Win, int* run);
 int add_mbv2_block(sylph_ctx* c, std::vector<OpFn>& ops, const sylph_ctx::MbBlock& blk, int B, const void* X, int Hin, int Win, void* Y, void* h1, void* h2);
 int add_dwconv3x3(sylph_ctx* c, std::vector<OpFn>& ops, const float* w, const float* scale, const float* shift, int B, int C, int ld, int H, int W,
                   int stride, const void* x, void* y);

@@ -358,6 +358,10 @@ int sylph_mbv2_block(sylph_ctx* c, const float* x, int B, int Cin, int H, int W,
   sylph_ctx::MbBlock blk;
   RET(make_mbv2_block(&tmp, Cin, t, Cout, stride, hp, scale_host, shift_host, &blk));
   if (y_channels != Cout && y_channels != blk.cout_p) return fail("sylph_mbv2_block: y_channels must be Cout or its padded count");
+  if (pick_mbv2_route(&tmp, blk, B, H, W) == Mbv2Route::chain) {  // an image the chain refuses: before the buffers are allocated
+    int run = 0;
+    RET(mbv2_chain_run(blk, B, H, W, &run));
+  }
   const size_t e = tmp.esz();
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   const size_t n_x = (size_t)B * H * W * blk.cin_ld * e;
