@@ -219,6 +219,39 @@ int sylph_decode_nms_codesets(sylph_ctx* ctx, int G, const int* out_heights, con
                               float* scores_dev, int* classes_dev, int* levels_dev, float* locations_dev, int* cand_dev,
                               int* counts_dev, int* status_dev);
 
+/* Query records: score new class codes on stored tower outputs.
+ * Everything MetaFCOSHead.forward computes in front of the class-conditional conv is class-agnostic (fcos.py:582-667: the towers, bbox_pred,
+ * ctrness, iou_overlap; the codes enter in CondConvBasic alone).  The reference's evaluation runs the same query set once per support seed and
+ * per shot setting (meta_learn_evaluation.py:367-470 per pass, meta_fcos_runner.py:451-672 over TEST.REPEAT_TEST and the shot settings) and
+ * pays the whole network every time.  A record keeps what one pass left, so that codes which arrive later are scored without the backbone and
+ * the towers: any head entry followed by its decode on a loaded record gives, bit for bit, what it gives on the fresh batch.
+ *
+ * sylph_fcos_towers: the class-agnostic part of MetaFCOSHead.forward (fcos.py:582-667 up to the cls_logits call) on the current fresh
+ * batch, with no class codes.  It leaves no logits: a decode or a head export after it fails as before any head call. */
+typedef struct sylph_record sylph_record;
+int sylph_fcos_towers(sylph_ctx* ctx);
+/* Snapshot of what the towers left for the current fresh batch: the cls tower output, where its last GroupNorm is deferred (bf16 with
+ * FCOS.NORM "GN") un-normalised together with that GroupNorm's coefficient and partial-statistics tables, otherwise normalised; the box /
+ * centerness / IoU predictions; B, the padded H and W and the per-image sizes.  Valid after sylph_fcos_towers or after any head entry of
+ * the batch -- except one that has applied the deferred GroupNorm in place (a bf16 head of more than 32 classes with the fused scan
+ * switched off, the pretrained head, a logits export after a fused scan): the call then fails and names the remedy, sylph_fcos_towers
+ * again.  The record is immutable, owned by the caller, allocated by the context (counted in sylph_device_bytes) and independent of the
+ * plan cache.  On an allocation failure the error names the bytes asked for and nothing stays allocated. */
+int sylph_record_store(sylph_ctx* ctx, sylph_record** out);
+/* Make the record the current batch (the query loop of meta_learn_evaluation.py:421-426 from its stored tower outputs).  sylph_fcos_head,
+ * sylph_fcos_head_episodes, sylph_fcos_head_codesets, sylph_fcos_head_pretrained, sylph_decode_nms, sylph_decode_nms_codesets and
+ * sylph_export_head then work as on the fresh batch but launch no tower: the bf16 streaming kernels (up to 32 classes, the code-sets and
+ * mixed-episode kernels, the fused scan) read the record in place; the other routes copy it into the plan's buffers first.
+ * sylph_preprocess*, sylph_import_pyramid and sylph_import_head make a fresh batch current again.  The entries that need the pyramid
+ * (sylph_backbone_fpn, sylph_export_pyramid, sylph_codegen*, sylph_roi_align*, the backbone and tower taps) and sylph_fcos_towers fail and
+ * name the record.  A record made under another dtype, or under a sylph_config with another tower norm, level count, strides or code kernel size, is refused. */
+int sylph_record_load(sylph_ctx* ctx, const sylph_record* rec);
+/* Batch size, padded size and device bytes of a record; NULL skips. */
+int sylph_record_info(const sylph_record* rec, int* B, int* padded_h, int* padded_w, int64_t* bytes);
+/* Release a record, with the context that stored it (the stream is drained first).  If it is the current batch, no batch is current
+ * afterwards.  sylph_ctx_destroy releases the records that are still alive. */
+void sylph_record_destroy(sylph_ctx* ctx, sylph_record* rec);
+
 /* Merge of the detections of several views of the same source (sylph_preprocess_views): one class-wise NMS over their union, in the
  * coordinates of the source.  The per-view decode is sylph_decode_nms with out_heights / out_widths = the view's CROP size: its boxes are
  * in crop pixels, clipped to the crop, in the mirrored crop for a flipped view.  Decode writes [B][max_out] rows, so the views of several

@@ -741,6 +741,7 @@ int sylph_preprocess(sylph_ctx* c, int B, const float* const* images, const int*
   if (!P->raw_input)
     KCHK(launch_preprocess(c->dt, P->img_desc_dev, P->x0, B, mh, mw, c->cfg.pixel_mean, c->cfg.pixel_std, c->stream),
          "preprocess");
+  begin_fresh_batch(c, P);
   c->cur = P;
   if (ph) *ph = mh;
   if (pw) *pw = mw;
@@ -808,6 +809,7 @@ int sylph_preprocess_u8(sylph_ctx* c, int B, const unsigned char* const* images,
   P->raw_input = false;  // this pipeline writes the normalised batch itself
   KCHK(launch_resize_preprocess(c->dt, P->rz_desc_dev, tab_dev, P->x0, B, mh, mw, c->cfg.pixel_mean, c->cfg.pixel_std, rgb_input,
                                 c->stream), "resize_preprocess");
+  begin_fresh_batch(c, P);
   c->cur = P;
   if (ph) *ph = mh;
   if (pw) *pw = mw;
@@ -897,6 +899,7 @@ int sylph_preprocess_views(sylph_ctx* c, int B, const unsigned char* const* src,
   KCHK(timed_op(c, "view_preprocess_kernel", 0.0, c->stream, [=](hipStream_t st) {
          return launch_view_preprocess(dt, desc_dev, tab_dev, x0, B, mh, mw, mean, stdv, rgb_input, st);
        }), "view_preprocess");
+  begin_fresh_batch(c, P);
   c->cur = P;
   if (ph) *ph = mh;
   if (pw) *pw = mw;
@@ -904,6 +907,7 @@ int sylph_preprocess_views(sylph_ctx* c, int B, const unsigned char* const* src,
 }
 
 int sylph_export_input(sylph_ctx* c, float* out) {
+  RET(refuse_on_record(c, "sylph_export_input"));
   Plan* P = c->cur;
   if (!P || !P->x0) return fail("sylph_preprocess must be called first");
   if (P->raw_input)  // the normalisation is fused into the stem kernel: x0 has not been written for this batch (raw_input stays set)
@@ -913,6 +917,7 @@ int sylph_export_input(sylph_ctx* c, float* out) {
 }
 
 int sylph_backbone_fpn(sylph_ctx* c) {
+  RET(refuse_on_record(c, "sylph_backbone_fpn"));
   if (!c->cur || !c->cur->backbone_built) return fail("sylph_preprocess must be called first");
   return run_ops(c, c->cur->backbone_ops, "backbone_fpn");
 }
@@ -931,11 +936,13 @@ int sylph_import_pyramid(sylph_ctx* c, int B, int H, int W, const int* hs, const
                               c->stream),
            "import_pyramid");
   }
+  begin_fresh_batch(c, P);
   c->cur = P;
   return 0;
 }
 
 int sylph_export_pyramid(sylph_ctx* c, int level, float* out) {
+  RET(refuse_on_record(c, "sylph_export_pyramid"));
   Plan* P = c->cur;
   if (!P || !P->F) return fail("no current batch");
   if (level < 0 || level >= c->cfg.nlevels) return fail("bad level");

@@ -326,6 +326,7 @@ static std::vector<int> identity_images(int B) {
 extern "C" {
 
 int sylph_roi_align(sylph_ctx* c, const float* boxes, float* out) {
+  RET(refuse_on_record(c, "sylph_roi_align"));
   Plan* P = c->cur;
   if (!P || !P->F) return fail("no current batch");
   if (!boxes || !out) return fail("NULL argument");
@@ -333,6 +334,7 @@ int sylph_roi_align(sylph_ctx* c, const float* boxes, float* out) {
 }
 
 int sylph_roi_align_rois(sylph_ctx* c, int R, const float* boxes, const int* roi_image, float* out) {
+  RET(refuse_on_record(c, "sylph_roi_align_rois"));
   Plan* P = c->cur;
   RET(check_rois(P, R, boxes, roi_image));
   if (!out) return fail("NULL argument");
@@ -396,6 +398,7 @@ int sylph_export_support(sylph_ctx* c, int stage, int index, float* out) {
 
 // The one-box-per-image form: the ROI list with roi_image[r] = r in B / shots segments of `shots` rows each.
 int sylph_codegen_classes(sylph_ctx* c, const float* boxes, int shots, float* codes_out) {
+  RET(refuse_on_record(c, "sylph_codegen_classes"));
   Plan* P = c->cur;
   if (!P) return fail("no current batch");
   if (!boxes || !codes_out) return fail("NULL argument");
@@ -407,6 +410,7 @@ int sylph_codegen_classes(sylph_ctx* c, const float* boxes, int shots, float* co
 }
 
 int sylph_codegen_rois(sylph_ctx* c, int R, const float* boxes, const int* roi_image, int n_seg, const int* seg_len, float* codes_out) {
+  RET(refuse_on_record(c, "sylph_codegen_rois"));
   Plan* P = c->cur;
   RET(check_rois(P, R, boxes, roi_image));
   if (!seg_len || !codes_out) return fail("NULL argument");
@@ -437,6 +441,7 @@ int sylph_codegen_weight_norm(sylph_ctx* c, float* out) {
 }
 
 int sylph_codegen(sylph_ctx* c, const float* boxes, float* code_out) {
+  RET(refuse_on_record(c, "sylph_codegen"));
   if (!c->cur) return fail("no current batch");
   return sylph_codegen_classes(c, boxes, c->cur->B, code_out);
 }

@@ -471,18 +471,19 @@ int add_conv(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const voi
 // it (+ ReLU) to its input halo in LDS (ConvOpts::gn_coef).
 int add_conv_gn(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, int in_ld, void* out,
                        const std::vector<SegDesc>& segs, ConvOpts o, const GNLayer& G, int relu, const float2** coef_out,
-                       OpFn* apply_out) {
+                       OpFn* apply_out, GnDeferred* deferred_out) {
   o.want_gn = 1;
   Geom g;
   RET(add_conv(c, ops, L, in, in_ld, out, L.Cout, segs, o, &g));
-  return add_gn_from_partials(c, ops, out, L.Cout, segs, g, G, relu, coef_out, apply_out);
+  return add_gn_from_partials(c, ops, out, L.Cout, segs, g, G, relu, coef_out, apply_out, nullptr, deferred_out);
 }
 
 // the GroupNorm of a conv whose epilogue left per-M-tile partials in g.gn_partial (conv_igemm / conv_hpipe / conv_deform): finalize +
 // in-place apply, or (coef_out) the (a, b) table for the next consumer and optionally (apply_out) the stand-alone apply
-// (stats_out: where the finalize leaves (mean, rstd) per (segment, group) -- the parity taps of the support path)
+// (stats_out: where the finalize leaves (mean, rstd) per (segment, group) -- the parity taps of the support path; deferred_out, with
+// coef_out: the table and the partials with their sizes, all that a later stand-alone apply or a streaming consumer reads of this layer)
 int add_gn_from_partials(sylph_ctx* c, std::vector<OpFn>& ops, void* out, int ld, const std::vector<SegDesc>& segs, const Geom& g, const GNLayer& G, int relu,
-                         const float2** coef_out, OpFn* apply_out, const float2** stats_out) {
+                         const float2** coef_out, OpFn* apply_out, const float2** stats_out, GnDeferred* deferred_out) {
   const int ngroups = ld / 8;
   const float* partial = g.gn_partial;
   std::vector<GnSeg> gs;
@@ -505,6 +506,8 @@ int add_gn_from_partials(sylph_ctx* c, std::vector<OpFn>& ops, void* out, int ld
     RET(c->dalloc((void**)&coef, (size_t)nseg * ld * sizeof(float2)));
     ops.push_back([=](hipStream_t s) { return launch_gn_finalize_coef(ngroups, gsd, nseg, partial, stats_ws, ga, be, 1e-5f, coef, s); });
     *coef_out = coef;
+    if (deferred_out)  // (the partials' size: add_conv / add_conv_deform allocate n_mtiles + 1 tiles)
+      *deferred_out = GnDeferred{coef, (size_t)nseg * ld * sizeof(float2), partial, (size_t)(g.n_mtiles + 1) * ngroups * 3 * sizeof(float)};
     if (apply_out)  // the stand-alone apply of the same layer, for a consumer that cannot take the coefficients
       *apply_out = [=](hipStream_t s) {
         return launch_gn_apply_partials(dt, out, ld, ngroups, gsd, nseg, max_rows, partial, stats_ws, ga, be, 1e-5f, relu, s);
@@ -521,7 +524,8 @@ int add_gn_from_partials(sylph_ctx* c, std::vector<OpFn>& ops, void* out, int ld
 // pixels must not be rounded to bf16) through add_conv, then conv_deform.hip with bias (+ ReLU) and, when G is given, the GroupNorm
 // partials of its epilogue followed by the same GroupNorm handling as add_conv_gn.  `in` is the layer input after its GroupNorm + ReLU.
 int add_conv_deform(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& off, const ConvLayer& L, const void* in, void* out,
-                    const std::vector<SegDesc>& segs, int segs_per_image, const GNLayer* G, int relu, const float2** coef_out, OpFn* apply_out) {
+                    const std::vector<SegDesc>& segs, int segs_per_image, const GNLayer* G, int relu, const float2** coef_out, OpFn* apply_out,
+                    GnDeferred* deferred_out) {
   if (off.Cout != 27 || off.Cin != 256 || off.KH != 3 || L.Cin != 256 || L.Cout != 256 || L.KH != 3 || L.KW != 3)
     return fail("internal: deformable tower layer shapes");
   long rows = 0;
@@ -543,7 +547,7 @@ int add_conv_deform(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& off, 
   const DType dt = c->dt;
   ops.push_back([=](hipStream_t s) { return timed_op(c, "conv_deform_kernel", flops, s, [=](hipStream_t st) { return launch_conv_deform(dt, a, st); }); });
   if (!G) return 0;
-  return add_gn_from_partials(c, ops, out, 256, segs, g, *G, relu, coef_out, apply_out);
+  return add_gn_from_partials(c, ops, out, 256, segs, g, *G, relu, coef_out, apply_out, nullptr, deferred_out);
 }
 
 std::vector<SegDesc> image_segs(int B, int Hin, int Win, int Hout, int Wout, int resH, int resW) {

@@ -208,6 +208,7 @@ void sylph_ctx_destroy(sylph_ctx* c) {
   if (c->merge_ev) (void)hipEventDestroy(c->merge_ev);
   for (auto& kv : c->plans) free_plan(c, kv.second.get());
   c->plans.clear();
+  for (sylph_record* r : c->records) delete r;  // (their device bytes are among c->allocs)
   for (void* p : c->allocs) (void)hipFree(p);
   delete c;
 }

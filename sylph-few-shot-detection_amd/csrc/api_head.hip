@@ -99,10 +99,11 @@ int build_head(sylph_ctx* c, Plan* P) {
       const bool feeds_deform = doff && i + 2 == convs.size();
       const bool defer = (fuse && !is_last && !feeds_deform) || (is_last && defer_last);
       OpFn apply;
+      GnDeferred* keep = (is_last && defer_last && which == 0) ? &P->cls_gn : nullptr;  // (what a query record stores of this layer)
       if (doff && is_last)
-        RET(add_conv_deform(c, ops, *doff, convs[i], in, out, segs, c->cfg.nlevels, &gns[i], 1, defer ? &coef : nullptr, defer_last ? &apply : nullptr));
+        RET(add_conv_deform(c, ops, *doff, convs[i], in, out, segs, c->cfg.nlevels, &gns[i], 1, defer ? &coef : nullptr, defer_last ? &apply : nullptr, keep));
       else
-        RET(add_conv_gn(c, ops, convs[i], in, 256, out, segs, o, gns[i], 1, defer ? &coef : nullptr, (is_last && defer_last) ? &apply : nullptr));
+        RET(add_conv_gn(c, ops, convs[i], in, 256, out, segs, o, gns[i], 1, defer ? &coef : nullptr, (is_last && defer_last) ? &apply : nullptr, keep));
       if (is_last && defer_last) { *coef_last = coef; *apply_last = apply; }
       coef_prev = coef;
       if (which < 2) { P->tap_out[which].push_back(out); P->tap_coef[which].push_back(coef); }
@@ -117,7 +118,7 @@ int build_head(sylph_ctx* c, Plan* P) {
   const float2* box_coef = nullptr;
   OpFn box_apply;
   // the cls tower's last GroupNorm is left to sylph_fcos_head (fused into the class-conditional conv when N <= 32)
-  P->cls_coef = nullptr; P->cls_apply = nullptr;
+  P->cls_coef = nullptr; P->cls_apply = nullptr; P->cls_gn = GnDeferred();
   const bool defer = knob::fuse_gn_logits() && c->dt == DT_BF16 && tower_gn;
   OpFn cls_apply;
   if (!c->share_tower.empty()) {
@@ -361,7 +362,53 @@ static int ensure_logits(sylph_ctx* c, Plan* P, int N, bool allow_narrow, HeadOu
 // the deferred last cls GroupNorm, applied in place, with a profile record of its own
 static int apply_cls_gn(sylph_ctx* c, Plan* P) {
   const Plan* PP = P;
+  P->cls_applied = true;
   KCHK(timed_op(c, "gn_apply_partials_kernel", 0.0, c->stream, [=](hipStream_t st) { return PP->cls_apply(st); }), "gn_apply (cls tower, last layer)");
+  return 0;
+}
+
+// ---- the towers' outputs of the current batch: a fresh batch's in the plan's buffers, or a query record's ------------------------------
+
+void begin_fresh_batch(sylph_ctx* c, Plan* P) {
+  // the plan that scored the record may hold logits of it and sources that point into it: nothing of that describes a later batch
+  if (c->rec && c->cur) c->cur->out = HeadOut();
+  c->rec = nullptr;
+  P->towers_fresh = false;
+}
+
+int refuse_on_record(const sylph_ctx* c, const char* entry) {
+  if (!c->rec) return 0;
+  return fail(std::string(entry) + ": the current batch is a query record (sylph_record_load), which holds the towers' outputs and no pyramid; "
+              "make a fresh batch current first");
+}
+
+// The record's tower outputs, copied into the plan's own buffers: for the routes that normalise cls_feat in place or run conv launches built
+// on the plan's pointers (fp32 storage, FCOS.NORM "none", igemm_after_apply, 3x3 codes, the pretrained head, the logits export after a
+// scan).  With the partials the deferred apply reads, so that it runs exactly as on the fresh batch.  pred is never copied: nothing writes it.
+static int restore_record(sylph_ctx* c, Plan* P) {
+  const sylph_record* R = c->rec;
+  HIPCHK(hipMemcpyAsync(P->cls_feat, R->feat, R->feat_bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (R->coef) {
+    HIPCHK(hipMemcpyAsync(const_cast<float2*>(P->cls_gn.coef), R->coef, R->coef_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(const_cast<float*>(P->cls_gn.partial), R->partial, R->partial_bytes, hipMemcpyDeviceToDevice, c->stream));
+  }
+  P->src.feat = P->cls_feat; P->src.coef = P->cls_coef; P->src.pred = R->pred;
+  return 0;
+}
+
+// What every head entry does where the class-agnostic part of the step belongs.  A fresh batch: the head ops (towers, box heads, cls
+// GroupNorm statistics).  A query record: no launch at all when every kernel of the call streams its operands through pointers
+// (`streaming`: gn_logits, the sets and episodes kernels, the fused scan) -- they read the record in place -- and restore_record otherwise.
+static int run_towers(sylph_ctx* c, Plan* P, bool streaming) {
+  if (c->rec) {
+    if (!streaming) return restore_record(c, P);
+    P->src.feat = c->rec->feat; P->src.coef = c->rec->coef; P->src.pred = c->rec->pred;
+    return 0;
+  }
+  P->towers_fresh = false;
+  RET(run_ops(c, P->head_ops, "fcos_head"));
+  P->towers_fresh = true; P->cls_applied = false;
+  P->src.feat = P->cls_feat; P->src.coef = P->cls_coef; P->src.pred = P->pred;
   return 0;
 }
 
@@ -411,13 +458,13 @@ static int fcos_head_3x3(sylph_ctx* c, Plan* P, const float* cls_conv, const flo
   RET(ensure_codes(c, pc, Npad, 9 * 256 * c->esz(), false));
   // one launch in front of the towers, as for the 1x1 codes
   KCHK(launch_pack_codes3x3(c->dt, cls_conv, N, 256, Npad, pc.w, o.has_bias ? cls_bias : nullptr, pc.bias, pc.bias + pc.cap, c->stream), "pack_codes3x3");
-  RET(run_ops(c, P->head_ops, "fcos_head"));
+  RET(run_towers(c, P, false));
   if (k == HeadKind::gn_cond3x3) {
     const Plan* PP = P;
     const float* bias = o.has_bias ? pc.bias : nullptr;
     const int ld = o.logits_ld;
     KCHK(timed_op(c, "gn_cond3x3_kernel", 2.0 * (double)P->B * P->Ltot * N * 2304.0, c->stream, [=](hipStream_t st) {
-           return launch_gn_cond3x3(PP->cls_feat, 256, PP->cls_coef, PP->codes3.w, bias, N, PP->logits, ld, PP->head_segs, PP->head_tiles32,
+           return launch_gn_cond3x3(PP->src.feat, 256, PP->src.coef, PP->codes3.w, bias, N, PP->logits, ld, PP->head_segs, PP->head_tiles32,
                                     PP->head_mtiles32, st);
          }), "gn_cond3x3");
   } else {
@@ -520,7 +567,7 @@ static int launch_cond(sylph_ctx* c, Plan* P, const HeadOut& o, HeadKind k, cons
   const double flops = 2.0 * v.rows * N * 256.0;
   if (k == HeadKind::gn_logits) {
     KCHK(timed_op(c, "gn_logits_kernel", flops, c->stream, [=](hipStream_t st) {
-           return launch_gn_logits(PP->cls_feat, 256, PP->cls_coef, v.wt, v.bias, N, PP->logits, ld, PP->head_segs, v.t32, v.n32, st);
+           return launch_gn_logits(PP->src.feat, 256, PP->src.coef, v.wt, v.bias, N, PP->logits, ld, PP->head_segs, v.t32, v.n32, st);
          }), "gn_logits");
     return 0;
   }
@@ -534,7 +581,7 @@ static int launch_cond(sylph_ctx* c, Plan* P, const HeadOut& o, HeadKind k, cons
     // them (sylph_decode_nms clears a dirty table in front of a plain scan)
     P->cand_dirty = true;
     KCHK(timed_op(c, "logits_scan_kernel", flops, c->stream, [=](hipStream_t st) {
-           return launch_logits_scan(PP->cls_feat, 256, PP->cls_coef, v.wt, PP->code_wf, v.bias_scan, PP->head_segs, v.t32, v.n32, PP->pred, 8, d,
+           return launch_logits_scan(PP->src.feat, 256, PP->src.coef, v.wt, PP->code_wf, v.bias_scan, PP->head_segs, v.t32, v.n32, PP->src.pred, 8, d,
                                      PP->dec.buf, nseg, clear_counts, st);
          }), "logits_scan");
     return 0;
@@ -573,6 +620,13 @@ static std::vector<CondLaunch> cond_launches(const sylph_ctx* c, const Plan* P, 
   return list;
 }
 
+// does every launch of `list` read the tower output through pointers, un-normalised (run_towers)?
+static bool all_streaming(const std::vector<CondLaunch>& list) {
+  for (const CondLaunch& l : list)
+    if (l.k != HeadKind::gn_logits && l.k != HeadKind::scan) return false;
+  return true;
+}
+
 // Runs the class-conditional convs `list` of the head that o describes -> *scanned: some launch left candidates instead of logits.  The
 // last cls GroupNorm is applied in place, ONCE, and only after every kernel that reads the un-normalised tower output (gn_logits, scan; the
 // caller's gn_logits_sets launches) has been launched: the conv_igemm launches that need it come last, in list order.  record_apply: the
@@ -584,7 +638,7 @@ static int run_cond(sylph_ctx* c, Plan* P, const HeadOut& o, const std::vector<C
       if ((l.k == HeadKind::igemm_after_apply) != (pass == 1)) continue;
       if (pass == 1 && !applied) {
         if (record_apply) RET(apply_cls_gn(c, P));
-        else KCHK(P->cls_apply(c->stream), "gn_apply (cls tower, last layer)");
+        else { P->cls_applied = true; KCHK(P->cls_apply(c->stream), "gn_apply (cls tower, last layer)"); }
         applied = true;
       }
       RET(launch_cond(c, P, o, l.k, l.v, !any_scan));
@@ -679,9 +733,11 @@ int sylph_import_head(sylph_ctx* c, int N, int level, const float* logits, const
   if (N <= 0) return fail("class_code is empty");
   if (level < 0 || level >= c->cfg.nlevels) return fail("bad level");
   OwnerScope own(c, P);
+  begin_fresh_batch(c, P);  // (pred is the caller's from here on: no longer what the towers left)
   const HeadOut prev = P->out;
   P->out = HeadOut();
   BUILD(build_head(c, P), P);
+  P->src.feat = P->cls_feat; P->src.coef = P->cls_coef; P->src.pred = P->pred;
   HeadOut o;
   o.src = HeadOut::imported;
   if (P->logits && N == prev.ncls && prev.src != HeadOut::codesets) { o.ncls = N; o.logits_ld = prev.logits_ld; }  // level by level into the buffer as the last head laid it out
@@ -718,9 +774,10 @@ int sylph_fcos_head(sylph_ctx* c, const float* cls_conv, const float* cls_bias, 
   // (in FRONT of the towers: it depends on the caller's codes only, and at small batches the main stream waits for the bbox tower on the
   // side stream at the end of the head ops anyway -- behind them it was 5 us of the step's serial tail)
   KCHK(launch_pack_codes(c->dt, cls_conv, N, 256, pc.rows, pc.w, o.has_bias ? cls_bias : nullptr, pc.bias, pc.bias + pc.cap, c->stream), "pack_codes");
-  RET(run_ops(c, P->head_ops, "fcos_head"));
+  const std::vector<CondLaunch> list = cond_launches(c, P, o, false);
+  RET(run_towers(c, P, all_streaming(list)));
   bool scanned = false;
-  RET(run_cond(c, P, o, cond_launches(c, P, o, false), false, &scanned));
+  RET(run_cond(c, P, o, list, false, &scanned));
   o.logits_missing = scanned;
   o.cand = scanned ? HeadOut::cand_all : HeadOut::cand_none;
   P->out = o;
@@ -756,19 +813,21 @@ int sylph_fcos_head_episodes(sylph_ctx* c, int E, const float* cls_conv, const f
   const PackedCodes& pc = P->ep.codes;
   KCHK(launch_pack_codes_episodes(c->dt, cls_conv, pc.src_row, pc.rows, 256, pc.w, o.has_bias ? cls_bias : nullptr, pc.bias, pc.bias + pc.cap, c->stream),
        "pack_codes_episodes");
-  RET(run_ops(c, P->head_ops, "fcos_head"));
+  const bool one_launch = head_kind(c, P, maxN) == HeadKind::gn_logits;
+  const std::vector<CondLaunch> list = one_launch ? std::vector<CondLaunch>() : cond_launches(c, P, o, false);
+  RET(run_towers(c, P, all_streaming(list)));
   bool scanned = false;
-  if (head_kind(c, P, maxN) == HeadKind::gn_logits) {
+  if (one_launch) {
     // every episode takes gn_logits: ONE launch for the whole batch, whatever E is (head_fused.hip)
     const Plan* PP = P;
     const float* bias = o.has_bias ? pc.bias : nullptr;
     const int ld = o.logits_ld;
     KCHK(timed_op(c, "gn_logits_episodes_kernel", 2.0 * (double)P->B * P->Ltot * maxN * 256.0, c->stream, [=](hipStream_t st) {
-           return launch_gn_logits_episodes(PP->cls_feat, 256, PP->cls_coef, PP->ep.codes.w, bias, PP->ep.seg_row0, PP->logits, ld,
+           return launch_gn_logits_episodes(PP->src.feat, 256, PP->src.coef, PP->ep.codes.w, bias, PP->ep.seg_row0, PP->logits, ld,
                                             PP->head_segs, PP->head_tiles32, PP->head_mtiles32, st);
          }), "gn_logits_episodes");
   } else {
-    RET(run_cond(c, P, o, cond_launches(c, P, o, false), false, &scanned));
+    RET(run_cond(c, P, o, list, false, &scanned));
   }
   o.logits_missing = scanned;
   o.cand = scanned ? HeadOut::cand_scanned : HeadOut::cand_none;
@@ -794,7 +853,7 @@ int sylph_fcos_head_pretrained(sylph_ctx* c, int* num_classes) {
     RET(add_conv(c, P->cls_logits_ops, c->cls_logits, P->cls_feat, 256, P->logits, o.logits_ld, pyramid_segs(c, P), op));
     P->cls_logits_dst = P->logits;
   }
-  RET(run_ops(c, P->head_ops, "fcos_head"));
+  RET(run_towers(c, P, false));
   if (P->cls_coef) RET(apply_cls_gn(c, P));
   RET(run_ops(c, P->cls_logits_ops, "cls_logits"));
   if (num_classes) *num_classes = N;
@@ -810,6 +869,7 @@ int sylph_export_head(sylph_ctx* c, int level, float* logits, float* reg, float*
     OwnerScope own(c, P);
     HeadOut o = P->out;
     P->out = HeadOut();
+    if (c->rec) RET(restore_record(c, P));  // (the unfused conv normalises in place: on the plan's copy, never in the record)
     RET(run_cond(c, P, o, cond_launches(c, P, o, true), false, nullptr));
     o.logits_missing = false;
     P->out = o;
@@ -830,9 +890,9 @@ int sylph_export_head(sylph_ctx* c, int level, float* logits, float* reg, float*
       }
     } else if (logits)
       KCHK(launch_export_nchw_f32(P->logits, logits + (size_t)b * o.ncls * hw, o.ncls, hw, row0, o.logits_ld, 0, c->stream), "export logits");
-    if (reg) KCHK(launch_export_nchw_f32(P->pred, reg + (size_t)b * 4 * hw, 4, hw, row0, 8, 0, c->stream), "export reg");
-    if (ctr) KCHK(launch_export_nchw_f32(P->pred, ctr + (size_t)b * hw, 1, hw, row0, 8, 4, c->stream), "export ctr");
-    if (iou) KCHK(launch_export_nchw_f32(P->pred, iou + (size_t)b * hw, 1, hw, row0, 8, 5, c->stream), "export iou");
+    if (reg) KCHK(launch_export_nchw_f32(P->src.pred, reg + (size_t)b * 4 * hw, 4, hw, row0, 8, 0, c->stream), "export reg");
+    if (ctr) KCHK(launch_export_nchw_f32(P->src.pred, ctr + (size_t)b * hw, 1, hw, row0, 8, 4, c->stream), "export ctr");
+    if (iou) KCHK(launch_export_nchw_f32(P->src.pred, iou + (size_t)b * hw, 1, hw, row0, 8, 5, c->stream), "export iou");
   }
   return 0;
 }
@@ -855,7 +915,7 @@ int sylph_decode_nms(sylph_ctx* c, const int* oh, const int* ow, int max_out, fl
   P->cand_dirty = o.cand != HeadOut::cand_none;
   int nwb = (L * c->cfg.pre_nms_topk + 63) / 64;
   if (nwb > P->pool_cap / 64) nwb = P->pool_cap / 64;
-  KCHK(launch_decode(d, o.src == HeadOut::episodes ? P->ep.dsegs : P->dsegs, P->B * L, P->hl[0] * P->wl[0], P->B, nwb, P->logits, P->pred, 8,
+  KCHK(launch_decode(d, o.src == HeadOut::episodes ? P->ep.dsegs : P->dsegs, P->B * L, P->hl[0] * P->wl[0], P->B, nwb, P->logits, P->src.pred, 8,
                      P->dec.buf, P->img_out_dev, boxes, scores, classes, levels, locations, cand, counts, status, o.cand == HeadOut::cand_all, c->stream),
        "decode_nms");
   return 0;
@@ -895,7 +955,13 @@ int sylph_fcos_head_codesets(sylph_ctx* c, int G, const float* cls_conv, const f
   // one launch packs every set's codes and biases (in front of the towers, as in sylph_fcos_head)
   KCHK(launch_pack_codes_episodes(c->dt, cls_conv, pc.src_row, pc.rows, 256, pc.w, o.has_bias ? cls_bias : nullptr, pc.bias, pc.bias + pc.cap, c->stream),
        "pack_codes (code sets)");
-  RET(run_ops(c, P->head_ops, "fcos_head"));  // towers, box heads, cls GroupNorm statistics: once, whatever G is
+  std::vector<CondLaunch> cold;  // every set that does not take gn_logits_sets_kernel, in order g
+  for (int g = 0; g < G; ++g)
+    if (!set_is_hot(c, P, n_classes[g])) {
+      const HeadKind k = head_kind(c, P, n_classes[g], false);
+      cold.push_back({k, cond_ep(c, P, o, g, k)});
+    }
+  RET(run_towers(c, P, cold.empty()));  // towers, box heads, cls GroupNorm statistics: once, whatever G is
   const Plan* PP = P;
   const int ld = T.ld;
   // the sets of up to 32 classes: GN_SETS_MAX_BLOCKS blocks of 32 packed rows per pass over the un-normalised tower output
@@ -903,18 +969,12 @@ int sylph_fcos_head_codesets(sylph_ctx* c, int G, const float* cls_conv, const f
     const int nb = T.hot_blocks - b0 < GN_SETS_MAX_BLOCKS ? T.hot_blocks - b0 : GN_SETS_MAX_BLOCKS;
     const int width = T.hot_width - 32 * b0 < 32 * nb ? T.hot_width - 32 * b0 : 32 * nb;
     KCHK(timed_op(c, "gn_logits_sets_kernel", 2.0 * (double)P->head_mtiles32 * 128.0 * width * 256.0, c->stream, [=](hipStream_t st) {
-           return launch_gn_logits_sets(PP->cls_feat, 256, PP->cls_coef, (const char*)pc.w + (size_t)32 * b0 * 256 * 2, pc.bias + 32 * b0, nb,
+           return launch_gn_logits_sets(PP->src.feat, 256, PP->src.coef, (const char*)pc.w + (size_t)32 * b0 * 256 * 2, pc.bias + 32 * b0, nb,
                                         PP->logits + 32 * b0, ld, width, PP->head_segs, PP->head_tiles32, PP->head_mtiles32, st);
          }), "gn_logits_sets");
   }
   // every other set, in order g: the conv_igemm launch sylph_fcos_head gives its N, on the tower output normalised in place ONCE, after
   // the kernel above has read the un-normalised one (run_cond)
-  std::vector<CondLaunch> cold;
-  for (int g = 0; g < G; ++g)
-    if (!set_is_hot(c, P, n_classes[g])) {
-      const HeadKind k = head_kind(c, P, n_classes[g], false);
-      cold.push_back({k, cond_ep(c, P, o, g, k)});
-    }
   RET(run_cond(c, P, o, cold, true, nullptr));
   o.cand = HeadOut::cand_none;
   P->out = o;
@@ -938,10 +998,133 @@ int sylph_decode_nms_codesets(sylph_ctx* c, int G, const int* oh, const int* ow,
   RET(ensure_decode_slots(c, P, P->dec_cs, slots, o.ncls));
   RET(upload_img_out(c, P, oh, ow));
   const DecodeCfg d = decode_cfg(c, P, P->dec_cs, o, max_out);
-  KCHK(launch_decode(d, P->cs.dsegs, slots * L, P->hl[0] * P->wl[0], slots, 0, P->logits, P->pred, 8, P->dec_cs.buf, P->img_out_dev, boxes, scores,
+  KCHK(launch_decode(d, P->cs.dsegs, slots * L, P->hl[0] * P->wl[0], slots, 0, P->logits, P->src.pred, 8, P->dec_cs.buf, P->img_out_dev, boxes, scores,
                      classes, levels, locations, cand, counts, status, false, c->stream),
        "decode_nms_codesets");
   return 0;
+}
+
+/* see include/sylph_hip.h */
+int sylph_fcos_towers(sylph_ctx* c) {
+  Plan* P = c->cur;
+  if (!P) return fail("no current batch");
+  RET(refuse_on_record(c, "sylph_fcos_towers"));
+  OwnerScope own(c, P);
+  P->out = HeadOut();  // no logits: a decode or an export answers "sylph_fcos_head must be called first"
+  BUILD(build_head(c, P), P);
+  return run_towers(c, P, true);
+}
+
+/* see include/sylph_hip.h */
+int sylph_record_store(sylph_ctx* c, sylph_record** out) {
+  if (!out) return fail("sylph_record_store: out is NULL");
+  *out = nullptr;
+  Plan* P = c->cur;
+  if (!P) return fail("no current batch");
+  if (c->rec) return fail("sylph_record_store: the current batch is a query record already");
+  if (!P->head_built || !P->towers_fresh)
+    return fail("sylph_record_store: the towers have not run on the current batch (call sylph_fcos_towers or a head entry first)");
+  if (P->cls_coef && P->cls_applied)
+    return fail("sylph_record_store: an earlier head call on this batch applied the cls tower's last GroupNorm in place (igemm_after_apply, the "
+                "pretrained head, or a logits export after a fused scan): the tower output is no longer the one the streaming kernels read; "
+                "run sylph_fcos_towers again first");
+  if (P->cls_coef && (!P->cls_gn.coef || !P->cls_gn.partial)) return fail("internal: deferred cls GroupNorm without its tables");
+  HIPCHK(hipSetDevice(c->device));
+  std::unique_ptr<sylph_record> R(new sylph_record());
+  const size_t rows = (size_t)P->B * P->Ltot;
+  auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
+  R->feat_bytes = rows * 256 * c->esz();
+  R->pred_bytes = rows * 8 * sizeof(float);
+  R->coef_bytes = P->cls_coef ? P->cls_gn.coef_bytes : 0;
+  R->partial_bytes = P->cls_coef ? P->cls_gn.partial_bytes : 0;
+  const size_t total = pad(R->feat_bytes) + pad(R->pred_bytes) + pad(R->coef_bytes) + pad(R->partial_bytes);
+  {
+    Plan* owner = c->alloc_owner;
+    c->alloc_owner = nullptr;  // the context's, not a plan's: eviction never frees a record
+    const int r = c->dalloc(&R->base, total);
+    c->alloc_owner = owner;
+    if (r != 0) return fail("sylph_record_store: cannot allocate the record's " + std::to_string(total) + " bytes (" + sylph_last_error() + ")");
+  }
+  char* p = (char*)R->base;
+  R->feat = p; p += pad(R->feat_bytes);
+  R->pred = (const float*)p; p += pad(R->pred_bytes);
+  if (P->cls_coef) {
+    R->coef = (const float2*)p; p += pad(R->coef_bytes);
+    R->partial = (const float*)p;
+  }
+  hipError_t e = hipMemcpyAsync(R->base, P->cls_feat, R->feat_bytes, hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync((void*)R->pred, P->pred, R->pred_bytes, hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess && R->coef) e = hipMemcpyAsync((void*)R->coef, P->cls_gn.coef, R->coef_bytes, hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess && R->coef) e = hipMemcpyAsync((void*)R->partial, P->cls_gn.partial, R->partial_bytes, hipMemcpyDeviceToDevice, c->stream);
+  if (e != hipSuccess) {
+    c->dfree(R->base);
+    return fail(std::string("sylph_record_store: copy failed: ") + hipGetErrorString(e));
+  }
+  R->owner = c; R->device = c->device; R->dt = c->dt;
+  R->tower_norm = c->cfg.tower_norm; R->nlevels = c->cfg.nlevels; R->code_ksize = c->cfg.cg_code_ksize;
+  for (int l = 0; l < 8; ++l) R->strides[l] = c->cfg.strides[l];
+  R->B = P->B; R->H = P->H; R->W = P->W;
+  R->img_h = P->img_h; R->img_w = P->img_w;
+  R->bytes = (int64_t)total;
+  c->records.push_back(R.get());
+  *out = R.release();
+  return 0;
+}
+
+/* see include/sylph_hip.h */
+int sylph_record_load(sylph_ctx* c, const sylph_record* R) {
+  if (!R) return fail("sylph_record_load: the record is NULL");
+  if (!c->finalized) return fail("weights not finalized");
+  static const char* const dt_name[] = {"f32", "bf16", "f32s"};
+  auto dtn = [&](DType d) { return d == DT_BF16 ? dt_name[1] : (d == DT_F32S ? dt_name[2] : dt_name[0]); };
+  if (R->device != c->device) return fail("sylph_record_load: the record lives on device " + std::to_string(R->device) + ", the context on " + std::to_string(c->device));
+  if (R->dt != c->dt)
+    return fail(std::string("sylph_record_load: the record was made under dtype ") + dtn(R->dt) + ", the context runs " + dtn(c->dt));
+  bool same = R->tower_norm == c->cfg.tower_norm && R->nlevels == c->cfg.nlevels && R->code_ksize == c->cfg.cg_code_ksize;
+  for (int l = 0; l < 8 && same; ++l) same = R->strides[l] == c->cfg.strides[l];
+  if (!same)
+    return fail("sylph_record_load: the record was made under another sylph_config (tower norm " + std::to_string(R->tower_norm) + ", " +
+                std::to_string(R->nlevels) + " levels, first stride " + std::to_string(R->strides[0]) + ", code kernel size " + std::to_string(R->code_ksize) +
+                "; the context: " + std::to_string(c->cfg.tower_norm) + ", " + std::to_string(c->cfg.nlevels) + ", " + std::to_string(c->cfg.strides[0]) + ", " +
+                std::to_string(c->cfg.cg_code_ksize) + ")");
+  HIPCHK(hipSetDevice(c->device));
+  Plan* P = get_plan(c, R->B, R->H, R->W);
+  OwnerScope own(c, P);
+  BUILD(build_head(c, P), P);
+  if ((size_t)P->B * P->Ltot * 256 * c->esz() != R->feat_bytes || (R->coef != nullptr) != (P->cls_coef != nullptr) ||
+      (R->coef && (R->coef_bytes != P->cls_gn.coef_bytes || R->partial_bytes != P->cls_gn.partial_bytes)))
+    return fail("sylph_record_load: the record's tower layout is not this context's (the deferred cls GroupNorm or the tile geometry differ)");
+  begin_fresh_batch(c, P);  // (leaves an earlier record; P's own towers' outputs may be overwritten by a restore from here on)
+  P->out = HeadOut();
+  P->img_h = R->img_h; P->img_w = R->img_w;
+  c->cur = P;
+  c->rec = R;
+  return 0;
+}
+
+/* see include/sylph_hip.h */
+int sylph_record_info(const sylph_record* R, int* B, int* H, int* W, int64_t* bytes) {
+  if (!R) return fail("sylph_record_info: the record is NULL");
+  if (B) *B = R->B;
+  if (H) *H = R->H;
+  if (W) *W = R->W;
+  if (bytes) *bytes = R->bytes;
+  return 0;
+}
+
+/* see include/sylph_hip.h */
+void sylph_record_destroy(sylph_ctx* c, sylph_record* R) {
+  if (!c || !R) return;
+  if (c->rec == R) {  // the plan that was scoring it keeps nothing that points into it
+    if (c->cur) c->cur->out = HeadOut();
+    c->rec = nullptr;
+    c->cur = nullptr;
+  }
+  for (size_t i = 0; i < c->records.size(); ++i)
+    if (c->records[i] == R) { c->records[i] = c->records.back(); c->records.pop_back(); break; }
+  (void)hipSetDevice(c->device);
+  c->dfree(R->base);  // drains the stream first
+  delete R;
 }
 
 /* see include/sylph_hip.h */

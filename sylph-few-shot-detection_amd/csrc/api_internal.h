@@ -127,6 +127,40 @@ struct GNLayer {
 
 struct Plan;
 
+// A query record (sylph_record_store): what the towers left for one batch, in ONE device allocation of the context that made it -- not a
+// plan's, so plan eviction does not touch it.  Nothing that scores a record writes into it.
+struct sylph_record {
+  sylph_ctx* owner = nullptr;
+  int device = 0;
+  DType dt = DT_BF16;
+  int tower_norm = 0, nlevels = 0, strides[8] = {0}, code_ksize = 1;  // the sylph_config fields a record's layout and meaning depend on
+  int B = 0, H = 0, W = 0;
+  std::vector<int> img_h, img_w;
+  void* base = nullptr;              // the allocation: feat | pred | coef | partial, each at a multiple of 256 bytes
+  const void* feat = nullptr;        // cls tower output [B * Ltot][256]: un-normalised where the last GroupNorm is deferred (coef != nullptr)
+  const float* pred = nullptr;       // [B * Ltot][8]
+  const float2* coef = nullptr;      // deferred GroupNorm: (a, b) per (segment, channel) -- what the streaming kernels read
+  const float* partial = nullptr;    // ... and the conv epilogue's per-tile partials, which the stand-alone apply reads
+  size_t feat_bytes = 0, pred_bytes = 0, coef_bytes = 0, partial_bytes = 0;
+  int64_t bytes = 0;
+};
+
+// where the class-conditional kernels and the decode read the towers' outputs of the current batch: the plan's own buffers, or a query
+// record's in place (api_head.hip: run_towers)
+struct TowerSrc {
+  const void* feat = nullptr;
+  const float2* coef = nullptr;
+  const float* pred = nullptr;
+};
+
+// the deferred last GroupNorm of a tower, as add_gn_from_partials leaves it: the coefficient table and the per-tile partials behind it
+struct GnDeferred {
+  const float2* coef = nullptr;
+  size_t coef_bytes = 0;
+  const float* partial = nullptr;
+  size_t partial_bytes = 0;
+};
+
 // Pillow's precompute_coeffs + normalize_coeffs_8bpc for the BILINEAR filter (libImaging/Resample.c), in double like the
 // original: per output index the first input index, the tap count and `ksize` 22-bit fixed-point weights.
 struct PilCoeffs {
@@ -203,6 +237,10 @@ struct sylph_ctx {
   std::map<const void*, std::pair<void*, float*>> pw_weights;  // conv_pw.hip stage-image copies of 1x1 weights + scale/shift tables, keyed by the igemm-layout pointer
   void* pw_trash = nullptr;                 // conv_pw.hip trash slots (4 KiB)
   Plan* cur = nullptr;
+  // Query records: `rec` is the record that is the current batch (nullptr: a fresh batch; then cur is the plan that scores it), `records`
+  // every live record this context allocated
+  const sylph_record* rec = nullptr;
+  std::vector<sylph_record*> records;
   // sylph_merge_views: the call's view tables (scratch: rewritten by every call; the event guards the host copy's reuse)
   void* merge_tab = nullptr;
   size_t merge_tab_cap = 0;
@@ -360,6 +398,11 @@ struct Plan {
   // class-conditional conv (N <= 32: head_fused.hip) or runs cls_apply first
   const float2* cls_coef = nullptr;
   std::function<int(hipStream_t)> cls_apply;
+  GnDeferred cls_gn;        // cls_coef with its size and the partials cls_apply reads (a query record keeps both)
+  // State of the towers' outputs in this plan's buffers, for sylph_record_store: the head ops ran on the current fresh batch and nothing
+  // has overwritten cls_feat / pred since; the deferred last cls GroupNorm has been applied in place since they ran
+  bool towers_fresh = false, cls_applied = false;
+  TowerSrc src;             // set by every head entry (run_towers): read by its launches, by sylph_export_head and by the decodes
   float* pred = nullptr;    // [rows][8]
   float* logits = nullptr;  // [rows][out.logits_ld], capacity [rows][logits_cap_ld]
   int logits_cap_ld = 0;
@@ -574,12 +617,12 @@ ConvRoute pick_conv_route(const sylph_ctx* c, const ConvLayer& L, int in_ld, con
 std::string conv_route_name(const ConvRoute& r);  // "igemm_splitk 64x64 nbuf2 ks8", "hpipe 256x256", "pw 128x256", ...
 void adopt_records(sylph_ctx* c, sylph_ctx* tmp);  // parity entries: move a scratch context's profile + route records to the caller's
 int add_conv(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, int in_ld, void* out, int out_ld, const std::vector<SegDesc>& segs, const ConvOpts& o, Geom* geom_out = nullptr);
-int add_conv_gn(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, int in_ld, void* out, const std::vector<SegDesc>& segs, ConvOpts o, const GNLayer& G, int relu, const float2** coef_out = nullptr, OpFn* apply_out = nullptr);
+int add_conv_gn(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& L, const void* in, int in_ld, void* out, const std::vector<SegDesc>& segs, ConvOpts o, const GNLayer& G, int relu, const float2** coef_out = nullptr, OpFn* apply_out = nullptr, GnDeferred* deferred_out = nullptr);
 int add_gn_from_partials(sylph_ctx* c, std::vector<OpFn>& ops, void* out, int ld, const std::vector<SegDesc>& segs, const Geom& g, const GNLayer& G, int relu,
-                         const float2** coef_out, OpFn* apply_out, const float2** stats_out = nullptr);
+                         const float2** coef_out, OpFn* apply_out, const float2** stats_out = nullptr, GnDeferred* deferred_out = nullptr);
 int add_conv_deform(sylph_ctx* c, std::vector<OpFn>& ops, const ConvLayer& off, const ConvLayer& L, const void* in, void* out,
                     const std::vector<SegDesc>& segs, int segs_per_image, const GNLayer* G, int relu, const float2** coef_out = nullptr,
-                    OpFn* apply_out = nullptr);
+                    OpFn* apply_out = nullptr, GnDeferred* deferred_out = nullptr);
 std::vector<SegDesc> image_segs(int B, int Hin, int Win, int Hout, int Wout, int resH = 0, int resW = 0);
 // api_backbone.hip
 int ensure_pyramid(sylph_ctx* c, Plan* P);
@@ -616,6 +659,11 @@ std::vector<SegDesc> pyramid_segs(sylph_ctx* c, Plan* P);
 int add_gn(sylph_ctx* c, Plan* P, std::vector<OpFn>& ops, void* x, const RowSeg* segs_dev, int nseg, int max_rows, const GNLayer& G, int relu);
 int ensure_gn_ws(sylph_ctx* c, Plan* P, int nseg, int max_rows);
 int build_head(sylph_ctx* c, Plan* P);
+// A fresh batch becomes current on plan P (sylph_preprocess*, sylph_import_pyramid, sylph_import_head): a loaded query record is left, and
+// whatever the towers left in P's buffers belongs to an earlier batch
+void begin_fresh_batch(sylph_ctx* c, Plan* P);
+// fails, naming `entry`, when the current batch is a query record (the entries that need the pyramid or the backbone's tensors)
+int refuse_on_record(const sylph_ctx* c, const char* entry);
 // api_codegen.hip
 int build_support(sylph_ctx* c, Plan* P, SupportPass* Q);
 int build_support_roienc(sylph_ctx* c, Plan* P, SupportPass* Q);

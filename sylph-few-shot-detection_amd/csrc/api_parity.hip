@@ -76,6 +76,7 @@ int sylph_set_debug_taps(sylph_ctx* c, int on) {
 }
 
 int sylph_export_stage(sylph_ctx* c, int stage, float* out) {
+  RET(refuse_on_record(c, "sylph_export_stage"));
   Plan* P = c->cur;
   if (!P || !P->backbone_built) return fail("no backbone pass on the current batch");
   const bool on_demand = stage == 2 && P->tail_even;
@@ -104,6 +105,7 @@ int sylph_export_stage(sylph_ctx* c, int stage, float* out) {
 }
 
 int sylph_export_tower(sylph_ctx* c, int tower, int layer, int level, float* y, float* coef) {
+  RET(refuse_on_record(c, "sylph_export_tower"));
   Plan* P = c->cur;
   if (!P || !P->head_built) return fail("no head pass on the current batch");
   if (tower < 0 || tower > 1 || layer < 0 || layer >= (int)P->tap_out[tower].size()) return fail("bad tower / layer");

@@ -62,6 +62,11 @@ PROTOTYPES = {
     "sylph_fcos_head_pretrained": (c_int, [c_void_p, POINTER(c_int)]),
     "sylph_export_head": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylph_import_head": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylph_fcos_towers": (c_int, [c_void_p]),
+    "sylph_record_store": (c_int, [c_void_p, POINTER(c_void_p)]),
+    "sylph_record_load": (c_int, [c_void_p, c_void_p]),
+    "sylph_record_info": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int64)]),
+    "sylph_record_destroy": (None, [c_void_p, c_void_p]),
     "sylph_roi_align": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sylph_roi_align_rois": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p]),
     "sylph_decode_nms": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,

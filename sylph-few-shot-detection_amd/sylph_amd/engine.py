@@ -251,6 +251,35 @@ def check_code_sets(codes, code_ksize: int = 1) -> List[int]:
     return n
 
 
+class QueryRecord:
+    """What the towers left for one batch (sylph_record_store): an immutable device snapshot that any head entry can score, any number of
+    times, without the backbone and the towers (Engine.load_record).  Owned by the caller; `close()` gives its bytes back."""
+
+    def __init__(self, engine: "Engine", handle: c_void_p, sizes: List[Tuple[int, int]]):
+        self._engine = engine
+        self._h = handle
+        B, H, W, n = c_int(0), c_int(0), c_int(0), c_int64(0)
+        check(engine.L.sylph_record_info(handle, ctypes.byref(B), ctypes.byref(H), ctypes.byref(W), ctypes.byref(n)), "record_info")
+        self.batch = (B.value, H.value, W.value, list(sizes))  # (B, padded H, padded W, [(h, w) per image]), as Engine._batch
+        self.nbytes = int(n.value)
+
+    @property
+    def closed(self) -> bool:
+        return self._h is None
+
+    def close(self):
+        if self._h is not None:
+            eng, h = self._engine, self._h
+            self._h = None
+            if eng._ctx:  # (a closed engine has released its records already)
+                eng.L.sylph_record_destroy(eng._ctx, h)
+                if eng._record is self:
+                    eng._record = None
+                    eng._batch = None
+            if self in eng._records:
+                eng._records.remove(self)
+
+
 class Engine:
     """One HIP context: weights + per-batch-shape workspaces, all on ``device``."""
 
@@ -283,9 +312,13 @@ class Engine:
         self._ncls = 0
         self._keep = []  # tensors that must outlive queued kernels
         self._lib_writes = 0  # in-place writes into caller tensors through raw pointers (part of the class-code cache key)
+        self._records = []  # live QueryRecords of this engine
+        self._record = None  # the one that is the current batch (load_record), None on a fresh batch
 
     def close(self):
         if self._ctx:
+            for rec in list(getattr(self, "_records", [])):
+                rec.close()
             self.L.sylph_ctx_destroy(self._ctx)
             self._ctx = c_void_p(0)
 
@@ -338,6 +371,7 @@ class Engine:
         check(self.L.sylph_preprocess(self._ctx, B, ptrs, hs, ws, ctypes.byref(ph), ctypes.byref(pw)), "preprocess")
         self._keep = imgs
         self._batch = (B, ph.value, pw.value, [(int(im.shape[1]), int(im.shape[2])) for im in imgs])
+        self._record = None
         return ph.value, pw.value
 
     def preprocess_u8(self, images: List[torch.Tensor], new_sizes: List[Tuple[int, int]], rgb_input: bool = False) -> Tuple[int, int]:
@@ -355,6 +389,7 @@ class Engine:
                                          ctypes.byref(ph), ctypes.byref(pw)), "preprocess_u8")
         self._keep = imgs
         self._batch = (B, ph.value, pw.value, [(int(s[0]), int(s[1])) for s in new_sizes])
+        self._record = None
         return ph.value, pw.value
 
     def preprocess_views(self, sources: List[torch.Tensor], views: List[Dict], rgb_input: bool = False) -> Tuple[int, int]:
@@ -379,6 +414,7 @@ class Engine:
                                             ctypes.byref(ph), ctypes.byref(pw)), "preprocess_views")
         self._keep = srcs
         self._batch = (B, ph.value, pw.value, sizes)
+        self._record = None
         return ph.value, pw.value
 
     def export_input(self) -> torch.Tensor:
@@ -407,6 +443,7 @@ class Engine:
                                           _iarr([s[1] for s in sizes]), ptrs), "import_pyramid")
         self._keep = lv
         self._batch = (B, H, W, list(sizes))
+        self._record = None
 
     def export_pyramid(self) -> List[torch.Tensor]:
         self._stream()
@@ -417,6 +454,38 @@ class Engine:
             check(self.L.sylph_export_pyramid(self._ctx, l, _ptr(t)), "export_pyramid")
             out.append(t)
         return out
+
+    # ---- query records: the towers once, class codes any number of times ------------------------------------------
+    def towers(self):
+        """The class-agnostic part of the head (towers, box / centerness / IoU predictions, cls GroupNorm statistics) on the current fresh
+        batch, with no class codes: what `store_record` snapshots.  Leaves nothing to decode."""
+        self._stream()
+        check(self.L.sylph_fcos_towers(self._ctx), "fcos_towers")
+        self._ncls = 0
+
+    def store_record(self) -> QueryRecord:
+        """Snapshot of what the towers left for the current fresh batch (after `towers()` or any head call on it)."""
+        self._stream()
+        if getattr(self, "_batch", None) is None:
+            raise RuntimeError("store_record: no current batch")
+        h = c_void_p(0)
+        check(self.L.sylph_record_store(self._ctx, ctypes.byref(h)), "record_store")
+        rec = QueryRecord(self, h, self._batch[3])
+        self._records.append(rec)
+        return rec
+
+    def load_record(self, rec: QueryRecord):
+        """Make `rec` the current batch: head*, decode* and export_head then work as on the fresh batch, without running the towers."""
+        if not isinstance(rec, QueryRecord):
+            raise TypeError(f"load_record: a QueryRecord is expected, not {type(rec).__name__}")
+        if rec.closed:
+            raise RuntimeError("load_record: the query record is closed")
+        self._stream()
+        check(self.L.sylph_record_load(self._ctx, rec._h), "record_load")
+        self._batch = rec.batch
+        self._record = rec
+        self._keep = []
+        self._ncls = 0
 
     def _fold_codes(self, cls_conv: torch.Tensor, cls_bias: Optional[torch.Tensor], raw: bool = False):
         """One episode's class codes -> ((N, 256) fp32, (N,) fp32 or None) on the device, the CondConvBlock of a ROIEncoder model folded in."""
@@ -617,6 +686,7 @@ class Engine:
             check(self.L.sylph_import_head(self._ctx, N, l, _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _ptr(ts[3])), "import_head")
         self._keep_head = keep
         self._ncls = N
+        self._record = None
 
     def roi_align(self, boxes: torch.Tensor) -> torch.Tensor:
         """Test boundary: ROIPooler(7x7, ROIAlignV2) of one box per image of the current batch -> (S,256,7,7)."""

@@ -292,10 +292,73 @@ class _NoOpEvaluator:
         return {}
 
 
+def _evaluator_inputs(inputs):
+    """what evaluator.process is shown for a query batch: the batch itself, or the stored metadata of a record-input (cache_query_dataset)"""
+    if isinstance(inputs, (list, tuple)) and len(inputs) == 1 and isinstance(inputs[0], dict) and "record" in inputs[0]:
+        return inputs[0]["inputs"]
+    return inputs
+
+
+def release_query_records(records):
+    """close every QueryRecord of a cache_query_dataset list (their device bytes go back to the engine)"""
+    for item in records:
+        for x in item:
+            if isinstance(x, dict) and hasattr(x.get("record"), "close"):
+                x["record"].close()
+
+
+def cache_query_dataset(model, data_loader, max_bytes=None) -> List[Any]:
+    """ONE network pass over a query loader, no class codes: model(inputs, run_type="meta_learn_cache_query") per batch -> the list of
+    what it returned, in loader order: per batch a list of one record-input ({"record": QueryRecord, "inputs": metadata per image}; no
+    image tensors are kept).  inference_on_dataset_with_class_codes and inference_on_dataset_with_code_sets take the list in place of the
+    loader, any number of times: every seed or shot setting of the reference's protocol (meta_fcos_runner.py:451-672 over
+    meta_learn_evaluation.py:367-470) is then scored without the backbone and the towers.
+    max_bytes: device bytes the records may hold (default: half of the free device memory at the call).  MemoryError, naming the bytes
+    needed and allowed, BEFORE the store that would pass it: as soon as the first record shows that the whole loader would (its bytes x
+    the loader's length), or when the records so far plus one more batch at the bytes per image seen so far would.  Nothing stays allocated
+    then.  release_query_records(list) gives the bytes back when the list is no longer needed."""
+    if max_bytes is None and torch.cuda.is_available():
+        max_bytes = int(torch.cuda.mem_get_info()[0]) // 2
+    try:
+        total = len(data_loader)
+    except TypeError:
+        total = None
+    records: List[Any] = []
+    used, images = 0, 0
+
+    def refuse(needed: int, why: str):
+        release_query_records(records)
+        raise MemoryError(f"cache_query_dataset: {why} needs {needed} bytes of query records, {max_bytes} are allowed (max_bytes); "
+                          "nothing is kept")
+
+    with ExitStack() as stack:
+        if isinstance(model, nn.Module):
+            stack.enter_context(inference_context(model))
+        stack.enter_context(torch.no_grad())
+        for idx, inputs in enumerate(data_loader):
+            if max_bytes is not None and images:
+                nxt = used + (used * len(inputs) + images - 1) // images
+                if nxt > max_bytes:
+                    refuse(nxt, f"batch {idx} on top of the {len(records)} stored")
+            out = model(inputs, run_type="meta_learn_cache_query")
+            records.append(out)
+            used += int(out[0]["record"].nbytes)
+            images += len(inputs)
+            if max_bytes is not None:
+                if idx == 0 and total is not None and used * total > max_bytes:
+                    refuse(used * total, f"the whole loader ({total} batches of about {used} bytes each)")
+                if used > max_bytes:
+                    refuse(used, f"batch {idx}")
+    logger.info(f"Cached {images} query images as {len(records)} records, {used} device bytes")
+    return records
+
+
 def inference_on_dataset_with_class_codes(model, data_loader, evaluator, class_codes, cls_reweight=False,
                                           eval_with_pretrained_code=False):
     """Loop B (meta_learn_evaluation.py:367-470): model(inputs, class_code=..., run_type=
-    "meta_learn_test_instance") per query batch, evaluator.process(inputs, outputs), evaluator.evaluate()."""
+    "meta_learn_test_instance") per query batch, evaluator.process(inputs, outputs), evaluator.evaluate().
+    data_loader may be the list cache_query_dataset returned: the model then scores the stored records, and evaluator.process receives
+    the stored metadata of each batch as `inputs`."""
     devices = get_world_size()
     if eval_with_pretrained_code:
         assert class_codes is None  # meta_learn_evaluation.py:376-378: the model's own cls_logits are the codes
@@ -320,7 +383,7 @@ def inference_on_dataset_with_class_codes(model, data_loader, evaluator, class_c
             outputs = model(inputs, class_code=class_codes, run_type="meta_learn_test_instance")
             # forward_instances ends on the count read-back: the device work of this batch is complete
             compute += time.perf_counter() - t0
-            evaluator.process(inputs, outputs)
+            evaluator.process(_evaluator_inputs(inputs), outputs)
     _log_totals("query", "img", time.perf_counter() - start_time, compute, total - num_warmup, devices)
     results = evaluator.evaluate()
     return results if results is not None else {}
@@ -330,7 +393,8 @@ def inference_on_dataset_with_code_sets(model, data_loader, evaluators, class_co
     """Loop B once for SEVERAL code sets: one pass over the query loader, model(inputs, class_code_sets=..., run_type=
     "meta_learn_test_instance") per batch (the backbone and towers run once, the class-conditional conv and decode per set); evaluator g
     sees what inference_on_dataset_with_class_codes would have shown it with class_code_sets[g] -> [evaluator_g.evaluate() for g].
-    The reference runs the query set once per support seed (meta_fcos_runner.py:451-672 over meta_learn_evaluation.py:367-470)."""
+    The reference runs the query set once per support seed (meta_fcos_runner.py:451-672 over meta_learn_evaluation.py:367-470).
+    data_loader may be the list cache_query_dataset returned (see inference_on_dataset_with_class_codes)."""
     devices = get_world_size()
     class_code_sets = list(class_code_sets)
     if len(class_code_sets) == 0:
@@ -355,7 +419,7 @@ def inference_on_dataset_with_code_sets(model, data_loader, evaluators, class_co
             outputs = model(inputs, class_code_sets=class_code_sets, run_type="meta_learn_test_instance")
             compute += time.perf_counter() - t0
             for e, out in zip(evaluators, outputs):
-                e.process(inputs, out)
+                e.process(_evaluator_inputs(inputs), out)
     _log_totals("query", "img", time.perf_counter() - start_time, compute, total - num_warmup, devices)
     results = [e.evaluate() for e in evaluators]
     return [r if r is not None else {} for r in results]

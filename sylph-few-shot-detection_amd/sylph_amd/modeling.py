@@ -17,7 +17,7 @@ from typing import Any, Dict, List, Optional
 import torch
 from torch import nn
 
-from .engine import Engine
+from .engine import Engine, QueryRecord
 from .structures import Boxes, Instances
 from .views import DEFAULT_MAX_BATCH, check_views, make_view, plan_view_steps, tta_views, view_out_size
 
@@ -250,6 +250,23 @@ def group_episodes(class_code, num_inputs: int):
     return dicts, image_episode
 
 
+RECORD_META_KEYS = ("image_id", "file_name", "height", "width")
+
+
+def record_input(batched_inputs):
+    """The record-input of a model call, or None: `batched_inputs` is then a list of ONE dict {"record": QueryRecord, "inputs": [metadata
+    per image]} that stands for the whole batch it was made from (run_type "meta_learn_cache_query")."""
+    if not isinstance(batched_inputs, (list, tuple)) or not any(isinstance(x, dict) and "record" in x for x in batched_inputs):
+        return None
+    if len(batched_inputs) != 1:
+        raise ValueError(f"a record input stands for a whole batch: pass a list of exactly one record input, not {len(batched_inputs)} inputs "
+                         "(records are not merged, and not mixed with images)")
+    x = batched_inputs[0]
+    if not isinstance(x["record"], QueryRecord) or len(x.get("inputs", ())) != x["record"].batch[0]:
+        raise ValueError("a record input is {'record': QueryRecord, 'inputs': [metadata of each of its images]}")
+    return x
+
+
 @META_ARCH_REGISTRY.register()
 class MetaOneStageDetector(nn.Module):
     """Four inference forward types (meta_one_stage_detector.py:415-455):
@@ -265,6 +282,11 @@ class MetaOneStageDetector(nn.Module):
                                                inputs carrying "views" next to "image_u8", or cfg.TEST.AUG.ENABLED: every input is
                                                run on a list of views (crop, size, flip) and the views' detections are merged on the
                                                device (forward_instances_views)
+                                               batched_inputs a list of one record-input (below): the same results from the
+                                               record's stored tower outputs, without the backbone and the towers
+      "meta_learn_cache_query"              -> forward_cache_query: one network pass, no class codes -> [record-input]: a QueryRecord of
+                                               the batch with each input's metadata and no image tensors (not in the reference, whose
+                                               evaluation pays the whole network per seed and shot setting, meta_fcos_runner.py:451-672)
     Training is out of scope: calling the model in training mode raises NotImplementedError."""
 
     def __init__(self, cfg, dtype: Optional[str] = None, device_index: Optional[int] = None):
@@ -318,7 +340,14 @@ class MetaOneStageDetector(nn.Module):
         if self.training:
             raise NotImplementedError("training is out of scope of the MI355X inference path; call model.eval()")
         sets = check_class_code_args(class_code, class_code_sets)
-        views = self._input_views(batched_inputs) if run_type == "meta_learn_test_instance" else None
+        rec = record_input(batched_inputs) if run_type != "meta_learn_normalize_code" else None
+        if rec is not None or run_type == "meta_learn_cache_query":
+            self._refuse_views_with_records(batched_inputs if rec is None else rec["inputs"])
+            if rec is not None and run_type != "meta_learn_test_instance":
+                raise ValueError(f"a query record is scored with run_type 'meta_learn_test_instance', not {run_type!r}")
+            if run_type == "meta_learn_cache_query":
+                return self.forward_cache_query(batched_inputs)
+        views = self._input_views(batched_inputs) if run_type == "meta_learn_test_instance" and rec is None else None
         if views is not None:
             if sets is not None:
                 raise NotImplementedError("class_code_sets together with query views (inputs carrying \"views\", or TEST.AUG.ENABLED) is not "
@@ -478,7 +507,8 @@ class MetaOneStageDetector(nn.Module):
         if isinstance(class_codes, (list, tuple)):
             # one class-code dict per input: the images of several episodes share one step (sylph_fcos_head_episodes); pred_classes
             # index the image's own dict
-            dicts, image_episode = group_episodes(class_codes, len(batched_inputs))
+            rec = record_input(batched_inputs)
+            dicts, image_episode = group_episodes(class_codes, len(batched_inputs) if rec is None else len(rec["inputs"]))
             codes = [(d["cls_conv"], d.get("cls_bias")) for d in dicts]
             for w, _ in codes:
                 assert w.dim() == 4, f"Weight has dimension: {w.dim()}"
@@ -608,8 +638,39 @@ class MetaOneStageDetector(nn.Module):
             return lambda view_sources: eng.head_pretrained()
         return lambda view_sources: eng.head(w, b, raw=pretrained)
 
-    def _run_backbone(self, batched_inputs: List[Dict[str, Any]]):
-        """preprocess + backbone of the query batch -> the (height, width) each image's detections are scaled to"""
+    def _refuse_views_with_records(self, inputs):
+        cfg = getattr(self, "cfg", None)
+        aug = cfg.get("TEST", {}).get("AUG", {}) if hasattr(cfg, "get") else {}
+        if bool(aug.get("ENABLED", False)):
+            raise NotImplementedError("query records with TEST.AUG.ENABLED are not supported: a record holds one batch as the network saw it, "
+                                      "not the views of its inputs")
+        if any("views" in x for x in inputs):
+            raise NotImplementedError("query records of inputs that carry \"views\" are not supported: a record holds one batch as the network "
+                                      "saw it, not the views of its inputs")
+
+    def forward_cache_query(self, batched_inputs: List[Dict[str, Any]]):
+        """One network pass over the query batch with no class codes -> [{"record": QueryRecord, "inputs": [...]}]: what the towers left
+        (Engine.store_record) and, per input, image_id / file_name / height / width and the size the network saw ("net_height",
+        "net_width") -- no image tensors.  Passed back as batched_inputs of a "meta_learn_test_instance" call, with class_code or
+        class_code_sets, it gives what that call gives on `batched_inputs`.  The caller owns the record (close() releases its bytes)."""
+        assert not self.training, "Not for training"
+        out_sizes, net_sizes = self._run_backbone(batched_inputs, with_net_sizes=True)
+        self.engine.towers()
+        rec = self.engine.store_record()
+        metas = []
+        for x, (oh, ow), (nh, nw) in zip(batched_inputs, out_sizes, net_sizes):
+            m = {k: x[k] for k in RECORD_META_KEYS if k in x}
+            m.update(height=oh, width=ow, net_height=nh, net_width=nw)
+            metas.append(m)
+        return [{"record": rec, "inputs": metas}]
+
+    def _run_backbone(self, batched_inputs: List[Dict[str, Any]], with_net_sizes: bool = False):
+        """preprocess + backbone of the query batch -> the (height, width) each image's detections are scaled to.  A record-input: no
+        network at all, its record becomes the current batch and the sizes are the stored ones."""
+        rec = record_input(batched_inputs)
+        if rec is not None:
+            self.engine.load_record(rec["record"])
+            return [(int(m["height"]), int(m["width"])) for m in rec["inputs"]]
         if all("image_u8" in x for x in batched_inputs):
             # fused input pipeline (SURVEY.md 8f-3): the original uint8 HWC image + its ResizeShortestEdge target; resize,
             # BGR conversion, normalisation and padding run in one HIP kernel (sylph_preprocess_u8)
@@ -617,7 +678,8 @@ class MetaOneStageDetector(nn.Module):
                                   rgb_input=str(batched_inputs[0].get("input_format", "BGR")) == "RGB")
         else:
             sizes = self.backbone(images=[x["image"] for x in batched_inputs])
-        return [(int(x.get("height", s[0])), int(x.get("width", s[1]))) for x, s in zip(batched_inputs, sizes)]
+        out = [(int(x.get("height", s[0])), int(x.get("width", s[1]))) for x, s in zip(batched_inputs, sizes)]
+        return (out, [(int(s[0]), int(s[1])) for s in sizes]) if with_net_sizes else out
 
     @staticmethod
     def _to_results(dets, out_sizes):

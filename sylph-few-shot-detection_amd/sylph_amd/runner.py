@@ -12,8 +12,9 @@ import torch
 
 from . import config as _config
 from . import distributed as D
-from .evaluation import (format_class_codes_shared, inference_normalization, inference_on_dataset_with_class_codes,
-                         inference_on_dataset_with_code_sets, inference_on_support_set_dataset, inference_on_support_set_dataset_base)
+from .evaluation import (cache_query_dataset, format_class_codes_shared, inference_normalization, inference_on_dataset_with_class_codes,
+                         inference_on_dataset_with_code_sets, inference_on_support_set_dataset, inference_on_support_set_dataset_base,
+                         release_query_records)
 from .modeling import build_model as _build_model
 
 logger = logging.getLogger(__name__)
@@ -209,7 +210,8 @@ class MetaFCOSRunner:
 
     def _do_test_meta_learning(self, cfg, model, support_loader=None, query_loader=None, evaluator=None, base_support_loader=None,
                                output_folder: Optional[str] = None, num_classes: Optional[int] = None, train_iter=None,
-                               model_tag: str = "default", dataset_names: Optional[List[str]] = None, fuse_repeats: bool = False):
+                               model_tag: str = "default", dataset_names: Optional[List[str]] = None, fuse_repeats: bool = False,
+                               cache_queries: bool = False, cache_max_bytes: Optional[int] = None):
         """meta_fcos_runner.py:451-672.
 
         * With explicit loaders (support_loader + query_loader): ONE dataset / seed; returns (results, class_codes) -- the form
@@ -222,7 +224,11 @@ class MetaFCOSRunner:
         * fuse_repeats=True with REPEAT_TEST > 1: every seed's class codes are built first and the query set of a dataset runs ONCE
           against all of them (inference_on_dataset_with_code_sets: one backbone / tower pass per query batch, one evaluator per
           seed); the results dict is the one of the loop above.  EVAL_WITH_PRETRAINED_CODE datasets and multi-rank runs keep one query
-          pass per seed."""
+          pass per seed.
+        * cache_queries=True: ONE network pass per dataset's query set, kept as query records (evaluation.cache_query_dataset, at most
+          cache_max_bytes of device memory; default: half of what is free); every seed is then scored from the records -- class-conditional
+          conv and decode only.  A dataset whose records would not fit (estimated from its first record) keeps the plain loop, with a
+          logged reason.  The results dict is the one of the loop above."""
         if support_loader is not None or query_loader is not None:
             return self._episode(cfg, model, support_loader, query_loader, evaluator, base_support_loader, output_folder, num_classes)
         names = list(dataset_names if dataset_names is not None else cfg.DATASETS.TEST)
@@ -271,6 +277,15 @@ class MetaFCOSRunner:
                     qry = self.build_episodic_learning_detection_test_query_loader(cfg, name)
                     for seed, per in enumerate(inference_on_dataset_with_code_sets(model, qry, evs, sets)):
                         fused[(seed, name)] = per
+        cached = {}  # dataset -> its query records, in loader order
+        if cache_queries:
+            for name in names:
+                if any((seed, name) not in fused for seed in range(repeat)):
+                    try:
+                        cached[name] = cache_query_dataset(model, self.build_episodic_learning_detection_test_query_loader(cfg, name),
+                                                           max_bytes=cache_max_bytes)
+                    except MemoryError as e:
+                        logger.info(f"cache_queries: {name} keeps one network pass per seed ({e})")
         for seed in range(repeat):
             logger.info(f"{seed} out of {repeat} tests.")
             results[f"seed{seed}"] = OrderedDict()
@@ -283,7 +298,7 @@ class MetaFCOSRunner:
                     sup = base = None
                     if not pretrained:
                         sup, base = support_loaders(name, seed)
-                    qry = self.build_episodic_learning_detection_test_query_loader(cfg, name)
+                    qry = cached[name] if name in cached else self.build_episodic_learning_detection_test_query_loader(cfg, name)
                     ev = self.get_evaluator(cfg, name, output_folder=folder)
                     n_cls = self._global_len(sup) if sup is not None else None
                     per, _ = self._episode(cfg, model, sup, qry, ev, base, folder, n_cls, eval_with_pretrained_code=pretrained)
@@ -307,6 +322,8 @@ class MetaFCOSRunner:
                         if hist:
                             results[model_tag][name]["bbox"][f"{k}_avg"] = float(np.array(hist).mean())
                             results[model_tag][name]["bbox"][f"{k}_std"] = float(np.array(hist).std())
+        for recs in cached.values():
+            release_query_records(recs)
         return results
 
     def do_test(self, cfg, model, train_iter=None, support_loader=None, query_loader=None, evaluator=None):
