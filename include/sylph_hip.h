@@ -272,6 +272,40 @@ int sylph_merge_views(sylph_ctx* ctx, int n_src, int n_views, const int* view_sr
                       const int* classes_dev, const int* counts_dev, int max_out, float* out_boxes_dev, float* out_scores_dev,
                       int* out_classes_dev, int* out_view_dev, int* out_row_dev, int* out_counts_dev, int* status_dev);
 
+/* COCO bbox evaluation on detection rows, device side: what evaluator.evaluate() (sylph/evaluation/meta_learn_evaluation.py:465) hands to
+ * pycocotools -- pycocotools/cocoeval.py evaluateImg (sylph_coco_match) and accumulate (sylph_coco_accumulate), useCats = 1 -- in float64, in the
+ * operation order that tests/cocoeval_ref.py restates.  Pair p = image index * n_cat + category index, both in ascending id order.
+ * sylph_coco_match: det_rows_dev (n_det, 8) fp32 rows (image id | x0 | y0 | x1 | y1 | score | class | valid) ALREADY ordered by (pair, score
+ * descending, arrival); det_off_dev [n_pairs + 1] the rows of every pair.  Ground truth ordered by (pair, file order): gt_box_dev (G, 4) XYWH
+ * f64, gt_area_dev (the annotation's area), gt_crowd_dev, gt_off_dev [n_pairs + 1]; max_gt = the most boxes any pair holds.  iou_thr_dev
+ * [n_thr] and area_rng_dev [n_area][2] f64 as the host computed them.  Per pair the first max_det rows are matched greedily; per row
+ * matched_dev / ignored_dev receive one bit per (area a, threshold t) at bit a * n_thr + t (later rows of a pair are left alone);
+ * npig_dev [n_cat][n_area] is cleared and receives the non-ignored ground-truth count.  IoU = i / u with iw = min(dx + dw, gx + gw) - max(dx, gx),
+ * 0 when iw or ih <= 0, u = crowd ? dw * dh : dw * dh + gw * gh - i.  A pair of up to sylph_coco_match_tile_gt(max_det) boxes keeps its IoU
+ * tile on chip: SYLPH_COCO_MATCH_TILE_GT = 128 for max_det <= 131, fewer beyond (the tile is max_det x boxes float64 in 144 KiB of LDS: 55
+ * boxes at max_det 300, 13 at 1024).  A larger pair recomputes the same expression per visit -- identical results -- and keeps its flags in
+ * gt_scratch_dev: 64 bytes per ground-truth box (64 * G bytes for the G rows of gt_box_dev), any contents; it may be NULL only when
+ * max_gt <= sylph_coco_match_tile_gt(max_det), and the call fails by name otherwise.  n_area <= 4, n_area * n_thr <= 40, max_det <= 1024.
+ * n_det is the row count of det_rows_dev / matched_dev / ignored_dev; det_off_dev lives on the device and is not read by the host, so
+ * det_off_dev[n_pairs] <= n_det and ascending offsets are the caller's contract (as gt_off_dev's are against gt_box_dev).
+ * sylph_coco_accumulate: rows ordered by (category, score descending, image, rank) -- score_dev, rank_dev (rank inside the pair), the two masks --
+ * with cat_off_dev [n_cat + 1]; per (category, area, maxDet) the tp / fp cumulative sums over rows of rank < maxDet, recall, the
+ * right-to-left precision maximum and the rec_thr_dev [n_rec] look-ups (first index with recall >= threshold) ->
+ * precision_dev [T][R][K][A][M], recall_dev [T][K][A][M], scores_dev [T][R][K][A][M] f64, -1 where npig = 0.  A category's segment is scanned in
+ * chunks of SYLPH_COCO_ACC_CHUNK = 1024 rows and may be arbitrarily long.  n_thr <= 10, n_rec <= 128.  Neither call needs a current batch. */
+#define SYLPH_COCO_MATCH_TILE_GT 128 /* ground-truth boxes of one pair whose IoU tile stays on chip, for max_det <= 131 */
+#define SYLPH_COCO_ACC_CHUNK 1024    /* rows of a category's segment per scan step of sylph_coco_accumulate */
+/* the bound that holds for this max_det (<= SYLPH_COCO_MATCH_TILE_GT; -1 for a max_det outside 1 .. 1024): no context, no device */
+int sylph_coco_match_tile_gt(int max_det);
+int sylph_coco_match(sylph_ctx* ctx, int n_det, const float* det_rows_dev, int n_pairs, int n_cat, const int* det_off_dev,
+                     const double* gt_box_dev, const double* gt_area_dev, const int* gt_crowd_dev, const int* gt_off_dev, int max_gt, int n_thr,
+                     const double* iou_thr_dev, int n_area, const double* area_rng_dev, int max_det, unsigned char* gt_scratch_dev,
+                     unsigned long long* matched_dev, unsigned long long* ignored_dev, int* npig_dev);
+int sylph_coco_accumulate(sylph_ctx* ctx, int n_det, const float* score_dev, const int* rank_dev, const unsigned long long* matched_dev,
+                          const unsigned long long* ignored_dev, int n_cat, const int* cat_off_dev, const int* npig_dev, int n_thr, int n_rec,
+                          const double* rec_thr_dev, int n_area, int n_maxdet, const int* max_dets_dev, double* precision_dev,
+                          double* recall_dev, double* scores_dev);
+
 /* CodeGenerator.forward / CodeGeneratorHead.forward_roi_align, eval branch
  * (sylph/modeling/code_generator/code_generator.py:924-1002): the current batch is the S support
  * images of ONE class; boxes_dev (S,4) fp32 XYXY (one gt box per image).  code_out_dev: 256 k^2 + 1 fp32 (k = cg_code_ksize;

@@ -99,6 +99,30 @@ int launch_merge_views(int n_src, const int* src_off, const int* src_views, cons
                        int max_in, const float* boxes, const float* scores, const int* classes, const int* counts, float nms_thresh,
                        int post_nms_topk, int max_out, float* out_boxes, float* out_scores, int* out_classes, int* out_view, int* out_row,
                        int* out_counts, int* status, hipStream_t s);
+// coco_eval.hip: COCO bbox matching and accumulation (include/sylph_hip.h: sylph_coco_match / sylph_coco_accumulate)
+// ground-truth boxes of one (image, category) pair whose D x G float64 IoU tile (D <= max_det) is kept in LDS; a pair with more recomputes
+// every IoU where the walk visits it and keeps its matched flags in the caller's scratch.  The bound holds up to max_det = 131; a larger
+// max_det shrinks it so that the block's LDS (32 B per detection slot + (8 max_det + 64) B per box) stays within COCO_MATCH_LDS_BYTES:
+// coco_match_tile_gt(max_det) is THE bound -- launch, host checks and sylph_coco_match_tile_gt all call it.
+// tests/test_coco_eval_gpu.py crosses both the constant and a shrunken bound.
+constexpr int COCO_MATCH_TILE_GT = 128;
+constexpr int COCO_MATCH_LDS_BYTES = 144 * 1024;  // of the CU's 160 KiB
+inline int coco_match_tile_gt(int max_det) {
+  const long fit = ((long)COCO_MATCH_LDS_BYTES - 32L * max_det) / (8L * max_det + 64);
+  return fit < COCO_MATCH_TILE_GT ? (int)fit : COCO_MATCH_TILE_GT;
+}
+constexpr int COCO_MATCH_MAX_DETS = 1024;  // maxDets[-1]: the detection boxes of a pair live in LDS
+constexpr int COCO_MATCH_LANES = 40;       // (area range, IoU threshold) combinations: one lane and one mask bit each
+// rows of a category's segment one block scans per step of coco_accumulate_kernel; longer segments carry their counts from chunk to chunk
+constexpr int COCO_ACC_CHUNK = 1024;
+constexpr int COCO_MAX_THRESHOLDS = 10;
+constexpr int COCO_MAX_REC_THRESHOLDS = 128;
+int launch_coco_match(int n_pairs, int K, const float* det, const int* det_off, const double* gt_box, const double* gt_area, const int* gt_crowd,
+                      const int* gt_off, int max_gt, const double* iou_thr, int T, const double* area_rng, int A, int max_det,
+                      unsigned char* gt_scratch, unsigned long long* matched, unsigned long long* ignored, int* npig, hipStream_t s);
+int launch_coco_accumulate(const float* score, const int* rank, const unsigned long long* matched, const unsigned long long* ignored, int K,
+                           const int* cat_off, const int* npig, int T, int R, const double* rec_thr, int A, int M, const int* max_dets,
+                           double* precision, double* recall, double* scores, hipStream_t s);
 int launch_maxpool(DType dt, const void* in, void* out, int B, int H, int W, int C, int Ho, int Wo, hipStream_t s);
 int launch_groupnorm(DType dt, void* x, const RowSeg* segs_dev, int nseg, int max_rows, int ld, const float* gamma,
                      const float* beta, float eps, int relu, float* partial, float2* stats, hipStream_t s);

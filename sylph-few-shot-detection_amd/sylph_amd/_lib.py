@@ -17,6 +17,9 @@ LIB_PATH = os.environ.get("SYLPH_LIB_PATH") or os.path.join(os.path.dirname(_HER
 SYLPH_F32 = 0
 SYLPH_BF16 = 1
 SYLPH_F32S = 2
+# bounds of the COCO evaluation kernels (include/sylph_hip.h, csrc/kernels.h)
+COCO_MATCH_TILE_GT = 128  # ground-truth boxes of one (image, category) pair whose IoU tile stays in LDS (maxDets[-1] <= 131; sylph_coco_match_tile_gt)
+COCO_ACC_CHUNK = 1024  # rows of a category's segment per scan step
 
 
 class SylphConfig(Structure):
@@ -75,6 +78,11 @@ PROTOTYPES = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylph_merge_views": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_int),
                                   c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 7),
+    "sylph_coco_match_tile_gt": (c_int, [c_int]),
+    "sylph_coco_match": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p, c_int, c_void_p, c_int] +
+                         [c_void_p] * 4),
+    "sylph_coco_accumulate": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int] +
+                              [c_void_p] * 4),
     "sylph_codegen": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sylph_codegen_classes": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "sylph_codegen_rois": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_int, POINTER(c_int), c_void_p]),

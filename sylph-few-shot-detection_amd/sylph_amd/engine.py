@@ -958,6 +958,47 @@ class Engine:
                                         int(divide_by_acc)), "reduce_codes")
         return out
 
+    # ---- COCO bbox evaluation (sylph_amd.coco_eval.DeviceCOCOEvaluator) ----------------------------------
+    def coco_match(self, det_rows: torch.Tensor, det_off: torch.Tensor, gt: Dict[str, torch.Tensor], n_cat: int, iou_thr: torch.Tensor,
+                   area_rng: torch.Tensor, max_det: int):
+        """sylph_coco_match: det_rows (n, 8) fp32 ordered by (pair, score descending), det_off [pairs + 1] int32; gt: the device table
+        {"box" (G, 4) f64 XYWH, "area" f64, "crowd" int32, "off" [pairs + 1] int32, "max_per_pair" int} ordered by (pair, file order)
+        -> (matched, ignored) int64 [n] (bit a * T + t), npig int32 [n_cat, areas].  Nothing is read back."""
+        self._stream()
+        n, n_pairs = det_rows.shape[0], det_off.numel() - 1
+        assert det_rows.is_cuda and det_rows.dtype == torch.float32 and det_rows.is_contiguous() and (n == 0 or det_rows.shape[1] == 8)
+        assert det_off.dtype == torch.int32 and gt["off"].dtype == torch.int32 and gt["off"].numel() == n_pairs + 1
+        assert iou_thr.dtype == torch.float64 and area_rng.dtype == torch.float64 and area_rng.is_contiguous()
+        matched = torch.zeros(n, dtype=torch.int64, device=self.device)
+        ignored = torch.zeros(n, dtype=torch.int64, device=self.device)
+        npig = torch.empty(n_cat, area_rng.shape[0], dtype=torch.int32, device=self.device)
+        max_gt = int(gt["max_per_pair"])
+        scratch = None
+        tile_gt = self.L.sylph_coco_match_tile_gt(int(max_det))  # COCO_MATCH_TILE_GT, fewer for maxDets[-1] > 131; -1: the entry refuses max_det
+        if tile_gt < 0 or max_gt > tile_gt:
+            scratch = torch.empty(gt["box"].shape[0] * 64, dtype=torch.uint8, device=self.device)
+        check(self.L.sylph_coco_match(self._ctx, n, _ptr(det_rows), n_pairs, n_cat, _ptr(det_off), _ptr(gt["box"]), _ptr(gt["area"]),
+                                      _ptr(gt["crowd"]), _ptr(gt["off"]), max_gt, iou_thr.numel(), _ptr(iou_thr), area_rng.shape[0],
+                                      _ptr(area_rng), int(max_det), _ptr(scratch), _ptr(matched), _ptr(ignored), _ptr(npig)), "coco_match")
+        return matched, ignored, npig
+
+    def coco_accumulate(self, score: torch.Tensor, rank: torch.Tensor, matched: torch.Tensor, ignored: torch.Tensor, cat_off: torch.Tensor,
+                        npig: torch.Tensor, n_thr: int, rec_thr: torch.Tensor, max_dets: torch.Tensor):
+        """sylph_coco_accumulate on rows ordered by (category, score descending, image, rank) -> precision [T, R, K, A, M], recall [T, K, A, M],
+        scores [T, R, K, A, M] float64 on the device."""
+        self._stream()
+        n, K, A, M, R = score.numel(), cat_off.numel() - 1, npig.shape[1], max_dets.numel(), rec_thr.numel()
+        assert score.dtype == torch.float32 and rank.dtype == torch.int32 and matched.dtype == torch.int64 and ignored.dtype == torch.int64
+        assert cat_off.dtype == torch.int32 and npig.dtype == torch.int32 and max_dets.dtype == torch.int32 and rec_thr.dtype == torch.float64
+        assert all(t.is_cuda and t.is_contiguous() for t in (score, rank, matched, ignored, cat_off, npig, max_dets, rec_thr))
+        precision = torch.empty(n_thr, R, K, A, M, dtype=torch.float64, device=self.device)
+        recall = torch.empty(n_thr, K, A, M, dtype=torch.float64, device=self.device)
+        scores = torch.empty(n_thr, R, K, A, M, dtype=torch.float64, device=self.device)
+        check(self.L.sylph_coco_accumulate(self._ctx, n, _ptr(score), _ptr(rank), _ptr(matched), _ptr(ignored), K, _ptr(cat_off), _ptr(npig),
+                                           int(n_thr), R, _ptr(rec_thr), A, M, _ptr(max_dets), _ptr(precision), _ptr(recall), _ptr(scores)),
+              "coco_accumulate")
+        return precision, recall, scores
+
     # ---- primitive entries (kernel parity tests) ------------------------------------------------------
     def conv2d(self, x, w, scale=None, shift=None, stride=1, pad=0, relu=False, residual=None):
         self._stream()

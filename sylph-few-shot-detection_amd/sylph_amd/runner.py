@@ -161,7 +161,8 @@ class MetaFCOSRunner:
         raise NotImplementedError("override build_episodic_learning_detection_test_query_loader")
 
     def get_evaluator(self, cfg, dataset_name: str, output_folder: Optional[str] = None):
-        """COCO / LVIS evaluators are out of scope; None = the no-op evaluator of inference_on_dataset_with_class_codes."""
+        """None = the no-op evaluator of inference_on_dataset_with_class_codes.  Dataset registration is out of scope, so no ground truth is
+        known here; an override returns sylph_amd.coco_eval.DeviceCOCOEvaluator(gt json, ...) for COCO bbox AP."""
         return None
 
     @staticmethod
