@@ -306,6 +306,37 @@ int sylph_coco_accumulate(sylph_ctx* ctx, int n_det, const float* score_dev, con
                           const double* rec_thr_dev, int n_area, int n_maxdet, const int* max_dets_dev, double* precision_dev,
                           double* recall_dev, double* scores_dev);
 
+/* LVIS (federated) bbox evaluation on detection rows, device side: what FewshotLVISEvaluator (sylph/evaluation/lvis_evaluation.py:246-250,
+ * _evaluate_predictions_on_lvis_with_per_category: LVISResults + LVISEval.run()) hands to lvis-api -- lvis/eval.py evaluate_img (sylph_lvis_match)
+ * and accumulate (sylph_coco_accumulate with n_maxdet = 1 and max_dets = [max_dets_per_image]: arithmetically the same) -- in float64, in
+ * the operation order that tests/lviseval_ref.py restates.  The per-image budget (LVISResults.limit_dets_per_image), the federated filter
+ * (LVISEval._prepare) and the pair list are the caller's (sylph_amd/lvis_eval.py, torch on the device).
+ * sylph_lvis_match runs over a COMPACTED list of the (image, category) pairs that exist (detections or ground truth), never over a table
+ * of images x categories.  max_pairs is a host-known upper bound of the pair count (it sizes the grid and the four per-pair arrays);
+ * n_pairs_dev is the live count, one int on the device, which the host does not read: surplus waves return.  Per pair p < *n_pairs_dev:
+ * pair_cat_dev[p] the category index (for npig), pair_flags_dev[p] bit 0 = the category is not exhaustively annotated in this image,
+ * det_off_dev [max_pairs + 1] / gt_off_dev [max_pairs + 1] its rows of det_rows_dev (ordered by (pair, score descending, arrival); layout as
+ * for sylph_coco_match) and of the ground truth (gt_box_dev (G, 4) XYWH f64, gt_area_dev, gt_ignore_dev, ordered by (pair, file order)).
+ * A box is ignored in an area range when its ignore flag is set or its area is outside; detections walk the non-ignored boxes first, a
+ * matched box is never matched again (no crowd boxes), and an unmatched detection is ignored when its own area w * h is outside the range or
+ * the pair's flag bit 0 is set.  There is no cut inside a pair: a pair may hold up to max_det (= max_dets_per_image) detections,
+ * max_det <= SYLPH_LVIS_MATCH_MAX_DETS = 1024; max_gt = the most boxes any pair holds.  matched_dev / ignored_dev / npig_dev as for
+ * sylph_coco_match.  One wave per pair, four waves per block, each with an LDS slice of SYLPH_LVIS_MATCH_SLICE_BYTES = 36 KiB: a pair of D
+ * detections and G boxes keeps its IoU tile and state rows there when 32 D + G (8 D + 64) <= 36864 -- sylph_lvis_match_fits(D, G), decided
+ * per pair from its own counts: D = 300 fits 11 boxes, D = 64 fits 60, D = 1 fits 511 -- and otherwise recomputes the IoU per visit
+ * (identical results) with its state rows in gt_scratch_dev: 64 bytes per ground-truth box, any contents; it may be NULL only when
+ * sylph_lvis_match_fits(max_det, max_gt), and the call fails by name otherwise.  n_area <= 4, n_area * n_thr <= 40. */
+#define SYLPH_LVIS_MATCH_SLICE_BYTES 36864 /* LDS of one wave = one pair: 32 B per detection, 8 B per IoU, 64 B per ground-truth box */
+#define SYLPH_LVIS_MATCH_MAX_DETS 1024     /* detections of one pair, i.e. max_dets_per_image */
+/* 1: a pair of n_det detections and n_gt boxes keeps its IoU tile on chip, 0: it needs the scratch; -1 for negative counts or
+ * n_det > SYLPH_LVIS_MATCH_MAX_DETS.  No context, no device */
+int sylph_lvis_match_fits(int n_det, int n_gt);
+int sylph_lvis_match(sylph_ctx* ctx, int n_det, const float* det_rows_dev, int max_pairs, const int* n_pairs_dev, int n_cat,
+                     const int* pair_cat_dev, const int* pair_flags_dev, const int* det_off_dev, const double* gt_box_dev,
+                     const double* gt_area_dev, const int* gt_ignore_dev, const int* gt_off_dev, int max_gt, int n_thr,
+                     const double* iou_thr_dev, int n_area, const double* area_rng_dev, int max_det, unsigned char* gt_scratch_dev,
+                     unsigned long long* matched_dev, unsigned long long* ignored_dev, int* npig_dev);
+
 /* CodeGenerator.forward / CodeGeneratorHead.forward_roi_align, eval branch
  * (sylph/modeling/code_generator/code_generator.py:924-1002): the current batch is the S support
  * images of ONE class; boxes_dev (S,4) fp32 XYXY (one gt box per image).  code_out_dev: 256 k^2 + 1 fp32 (k = cg_code_ksize;

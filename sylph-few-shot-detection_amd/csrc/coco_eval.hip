@@ -16,20 +16,11 @@
 //   the later chunks' maximum as carry, and at every row where the recall steps the recall thresholds it is the first to reach.
 #include "common.h"
 #include "kernels.h"
+#include "eval_iou.h"
 
 namespace sylph {
 
 typedef unsigned long long u64;
-
-__device__ __forceinline__ double coco_iou(double dx, double dy, double dw, double dh, const double* __restrict__ g, int crowd) {
-  const double gx = g[0], gy = g[1], gw = g[2], gh = g[3];
-  const double iw = fmin(dx + dw, gx + gw) - fmax(dx, gx);
-  const double ih = fmin(dy + dh, gy + gh) - fmax(dy, gy);
-  if (iw <= 0.0 || ih <= 0.0) return 0.0;
-  const double i = iw * ih;
-  const double u = crowd ? dw * dh : dw * dh + gw * gh - i;
-  return i / u;
-}
 
 // dynamic LDS: detection boxes [max_det][4] f64 | IoU tile [max_det][tile_g] f64 | state rows [tile_g][64] bytes
 __global__ __launch_bounds__(64) void coco_match_kernel(const float* __restrict__ det, const int* __restrict__ det_off,

@@ -123,6 +123,22 @@ int launch_coco_match(int n_pairs, int K, const float* det, const int* det_off, 
 int launch_coco_accumulate(const float* score, const int* rank, const unsigned long long* matched, const unsigned long long* ignored, int K,
                            const int* cat_off, const int* npig, int T, int R, const double* rec_thr, int A, int M, const int* max_dets,
                            double* precision, double* recall, double* scores, hipStream_t s);
+// lvis_eval.hip: LVIS (federated) bbox matching over a compacted list of the (image, category) pairs that exist (include/sylph_hip.h:
+// sylph_lvis_match); the accumulation is coco_accumulate_kernel with one unbounded maxDet.  One wave per pair, LVIS_MATCH_WAVES waves per
+// block, each wave with an LDS slice of LVIS_MATCH_SLICE_BYTES = 36 KiB of its own (4 x 36 KiB = 144 KiB of the CU's 160 KiB).  A pair of D
+// detections and G boxes keeps its D x G float64 IoU tile and its G 64-byte state rows in the slice when
+// 32 D + G (8 D + 64) <= LVIS_MATCH_SLICE_BYTES (D = 300: 11 boxes, D = 64: 60, D = 1: 511); any other pair recomputes the IoU at every
+// visit and keeps its state rows in the caller's scratch.  lvis_match_fits is THE rule: kernel, host check and sylph_lvis_match_fits call it.
+constexpr int LVIS_MATCH_WAVES = 4;
+constexpr int LVIS_MATCH_SLICE_BYTES = 36 * 1024;
+constexpr int LVIS_MATCH_MAX_DETS = 1024;  // detections of one pair (<= max_dets_per_image): their boxes live in the wave's slice, 32 B each
+__host__ __device__ inline bool lvis_match_fits(int n_det, int n_gt) {
+  return 32L * n_det + (long)n_gt * (8L * n_det + 64) <= (long)LVIS_MATCH_SLICE_BYTES;
+}
+int launch_lvis_match(int max_pairs, const int* n_pairs, int K, const float* det, const int* det_off, const int* pair_cat, const int* pair_flags,
+                      const double* gt_box, const double* gt_area, const int* gt_ignore, const int* gt_off, const double* iou_thr, int T,
+                      const double* area_rng, int A, int max_det, unsigned char* gt_scratch, unsigned long long* matched,
+                      unsigned long long* ignored, int* npig, hipStream_t s);
 int launch_maxpool(DType dt, const void* in, void* out, int B, int H, int W, int C, int Ho, int Wo, hipStream_t s);
 int launch_groupnorm(DType dt, void* x, const RowSeg* segs_dev, int nseg, int max_rows, int ld, const float* gamma,
                      const float* beta, float eps, int relu, float* partial, float2* stats, hipStream_t s);

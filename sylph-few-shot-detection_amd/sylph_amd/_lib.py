@@ -20,6 +20,9 @@ SYLPH_F32S = 2
 # bounds of the COCO evaluation kernels (include/sylph_hip.h, csrc/kernels.h)
 COCO_MATCH_TILE_GT = 128  # ground-truth boxes of one (image, category) pair whose IoU tile stays in LDS (maxDets[-1] <= 131; sylph_coco_match_tile_gt)
 COCO_ACC_CHUNK = 1024  # rows of a category's segment per scan step
+# bounds of the LVIS match kernel (include/sylph_hip.h, csrc/kernels.h)
+LVIS_MATCH_SLICE_BYTES = 36 * 1024  # LDS of one wave = one pair: 32 D + G (8 D + 64) bytes fit, or the pair recomputes (sylph_lvis_match_fits)
+LVIS_MATCH_MAX_DETS = 1024  # detections of one pair, i.e. max_dets_per_image
 
 
 class SylphConfig(Structure):
@@ -83,6 +86,9 @@ PROTOTYPES = {
                          [c_void_p] * 4),
     "sylph_coco_accumulate": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int] +
                               [c_void_p] * 4),
+    "sylph_lvis_match_fits": (c_int, [c_int, c_int]),
+    "sylph_lvis_match": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_int, c_void_p, c_int, c_void_p,
+                                                                                                      c_int] + [c_void_p] * 4),
     "sylph_codegen": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sylph_codegen_classes": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "sylph_codegen_rois": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_int, POINTER(c_int), c_void_p]),

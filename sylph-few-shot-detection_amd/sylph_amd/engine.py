@@ -982,6 +982,32 @@ class Engine:
                                       _ptr(area_rng), int(max_det), _ptr(scratch), _ptr(matched), _ptr(ignored), _ptr(npig)), "coco_match")
         return matched, ignored, npig
 
+    def lvis_match(self, det_rows: torch.Tensor, pairs: Dict[str, torch.Tensor], gt: Dict[str, torch.Tensor], n_cat: int, iou_thr: torch.Tensor,
+                   area_rng: torch.Tensor, max_det: int):
+        """sylph_lvis_match: det_rows (n, 8) fp32 ordered by (pair, score descending, arrival); pairs: the compacted pair list
+        {"n" int32 [1] the live count (stays on the device), "cat", "flags" int32 [P], "det_off", "gt_off" int32 [P + 1]}, P a host-known upper
+        bound; gt: {"box" (G, 4) f64 XYWH, "area" f64, "ignore" int32, "max_per_pair" int} ordered by (pair, file order); max_det: the most
+        detections a pair can hold (max_dets_per_image) -> (matched, ignored) int64 [n], npig int32 [n_cat, areas].  Nothing is read back."""
+        self._stream()
+        n, P = det_rows.shape[0], pairs["cat"].numel()
+        assert det_rows.is_cuda and det_rows.dtype == torch.float32 and det_rows.is_contiguous() and (n == 0 or det_rows.shape[1] == 8)
+        assert all(pairs[k].dtype == torch.int32 and pairs[k].is_cuda and pairs[k].is_contiguous() for k in ("n", "cat", "flags", "det_off", "gt_off"))
+        assert P > 0 and pairs["flags"].numel() == P and pairs["det_off"].numel() == P + 1 and pairs["gt_off"].numel() == P + 1
+        assert gt["ignore"].dtype == torch.int32 and gt["box"].dtype == torch.float64 and gt["area"].dtype == torch.float64
+        assert iou_thr.dtype == torch.float64 and area_rng.dtype == torch.float64 and area_rng.is_contiguous()
+        matched = torch.zeros(n, dtype=torch.int64, device=self.device)
+        ignored = torch.zeros(n, dtype=torch.int64, device=self.device)
+        npig = torch.empty(n_cat, area_rng.shape[0], dtype=torch.int32, device=self.device)
+        max_gt = int(gt["max_per_pair"])
+        scratch = None
+        if self.L.sylph_lvis_match_fits(int(max_det), max_gt) != 1:  # some pair may need it (0), or the entry refuses max_det by name (-1)
+            scratch = torch.empty(max(gt["box"].shape[0], 1) * 64, dtype=torch.uint8, device=self.device)
+        check(self.L.sylph_lvis_match(self._ctx, n, _ptr(det_rows), P, _ptr(pairs["n"]), n_cat, _ptr(pairs["cat"]), _ptr(pairs["flags"]),
+                                      _ptr(pairs["det_off"]), _ptr(gt["box"]), _ptr(gt["area"]), _ptr(gt["ignore"]), _ptr(pairs["gt_off"]), max_gt,
+                                      iou_thr.numel(), _ptr(iou_thr), area_rng.shape[0], _ptr(area_rng), int(max_det), _ptr(scratch),
+                                      _ptr(matched), _ptr(ignored), _ptr(npig)), "lvis_match")
+        return matched, ignored, npig
+
     def coco_accumulate(self, score: torch.Tensor, rank: torch.Tensor, matched: torch.Tensor, ignored: torch.Tensor, cat_off: torch.Tensor,
                         npig: torch.Tensor, n_thr: int, rec_thr: torch.Tensor, max_dets: torch.Tensor):
         """sylph_coco_accumulate on rows ordered by (category, score descending, image, rank) -> precision [T, R, K, A, M], recall [T, K, A, M],

@@ -162,7 +162,9 @@ class MetaFCOSRunner:
 
     def get_evaluator(self, cfg, dataset_name: str, output_folder: Optional[str] = None):
         """None = the no-op evaluator of inference_on_dataset_with_class_codes.  Dataset registration is out of scope, so no ground truth is
-        known here; an override returns sylph_amd.coco_eval.DeviceCOCOEvaluator(gt json, ...) for COCO bbox AP."""
+        known here; an override returns sylph_amd.coco_eval.DeviceCOCOEvaluator(gt json, ...) for COCO bbox AP, or, for an LVIS dataset (the
+        reference's FewshotLVISEvaluator), sylph_amd.lvis_eval.DeviceLVISEvaluator(gt json, contiguous_to_dataset_id=..., category_ids=...)
+        for the federated LVIS bbox AP with APr / APc / APf."""
         return None
 
     @staticmethod
