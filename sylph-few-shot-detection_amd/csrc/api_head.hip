@@ -450,8 +450,15 @@ static int fcos_head_3x3(sylph_ctx* c, Plan* P, const float* cls_conv, const flo
   HeadOut o;
   o.src = HeadOut::cond;
   o.has_bias = c->cfg.cond_use_bias && cls_bias;
-  RET(ensure_logits(c, P, N, false, &o));
   const HeadKind k = head_kind3x3(c, P, N);
+  // Deformable towers promise the default route's detections bit for bit from every entry (tests/test_head_variants_gpu.py).  The fused
+  // kernel cannot give them: it adds nine per-tap fp32 accumulators in a fixed order, conv_igemm runs one accumulator over K = 2 304, and
+  // a score comes out one fp32 ulp apart (3.6e-7 measured).  Refused before anything is launched, not run as a near miss.
+  if (k == HeadKind::gn_cond3x3 && c->cfg.tower_deformable)
+    return fail("SYLPH_GN_COND3X3=1 with MODEL.FCOS.USE_DEFORMABLE: gn_cond3x3_kernel sums its nine taps in another order than the default route "
+                "(GroupNorm apply + conv_igemm) and its scores differ from that route's in the last fp32 bit; the fused 3x3 route is not offered "
+                "for deformable towers (unset SYLPH_GN_COND3X3)");
+  RET(ensure_logits(c, P, N, false, &o));
   const int Npad = cond_pad(N).Npad;
   if (k == HeadKind::gn_cond3x3 && N <= 8) o.logits_ld = 8;  // as gn_logits: the fused kernel stores any multiple of 4 columns
   PackedCodes& pc = P->codes3;

@@ -4,6 +4,7 @@ Tensors are torch CUDA(ROCm) tensors used purely as device-memory owners: every 
 call through the C ABI (include/sylph_hip.h) into hand-written HIP kernels.
 """
 import ctypes
+import os
 from ctypes import c_int, c_int64, c_void_p
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -15,6 +16,14 @@ from ._lib import SylphConfig, check
 
 def _ptr(t: Optional[torch.Tensor]):
     return c_void_p(t.data_ptr()) if t is not None else c_void_p(0)
+
+
+def _env_int(name: str, default: int) -> int:
+    """an integer SYLPH_* environment override as the library reads it (knob_env): `default` when unset or not a number"""
+    try:
+        return int(os.environ.get(name, default))
+    except ValueError:
+        return default
 
 
 def _iarr(v: Sequence[int]):
@@ -193,6 +202,12 @@ def config_from_cfg(cfg) -> SylphConfig:
     if len(cl) != 3 or cl[0] not in ("", "none") or cl[1] != "" or int(cl[2]) not in (1, 3):
         raise NotImplementedError(f"CODE_GENERATOR.CLS_LAYER {cl} (only ['', '', 1] and ['', '', 3]: no norm, no activation, a 1x1 or 3x3 class code)")
     sc.cg_code_ksize = int(cl[2])
+    if sc.cg_code_ksize == 3 and sc.tower_deformable and sc.tower_norm == 0 and _env_int("SYLPH_GN_COND3X3", 0):
+        # gn_cond3x3_kernel adds nine per-tap accumulators, the default route (GroupNorm apply + conv_igemm) one: scores one fp32 ulp
+        # apart, where deformable towers promise the default route's detections bit for bit.  sylph_fcos_head refuses it per call too
+        # (the variable is read at every head call)
+        raise NotImplementedError("SYLPH_GN_COND3X3=1 with MODEL.FCOS.USE_DEFORMABLE: the fused 3x3 class-code route is not offered for "
+                                  "deformable towers (its scores differ from the default route's in the last fp32 bit); unset SYLPH_GN_COND3X3")
     bl = list(cg.BIAS_LAYER)
     sc.cg_has_bias = int(len(bl) != 0)
     if len(bl) and (len(bl) != 3 or bl[0] not in ("", "none") or bl[1] != "" or int(bl[2]) != 1):

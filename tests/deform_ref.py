@@ -13,7 +13,9 @@ Three forms:
   * deform_conv_grid_sample: F.grid_sample(bilinear, zeros, align_corners=True) on normalised coordinates;
   * deform_conv_bf16: rounds where csrc/conv_deform.hip rounds -- bf16 input, fp32 offsets, the fp32 blend
     (((v00 w00 + v01 w01) + v10 w10) + v11 w11) * mask, the A operand rounded to bf16 -- then an fp32-exact product sum.
-deform_fcos_head mirrors oracle.head.fcos_head with the deformable last tower layer.
+deform_fcos_head mirrors oracle.head.fcos_head with the deformable last tower layer, for every tower variant the head builder accepts:
+a shared tower in front (never deformable), towers of depth 0 (no layer at all) and 1 (the deformable layer reads the tower input),
+unequal depths, MODEL.FCOS.NORM "none", 3x3 class codes, and maps under 2 x 2 (deform_conv_any: the loop form there).
 """
 import math
 from typing import Dict, List, Optional
@@ -133,9 +135,19 @@ def deform_conv_bf16(x_bf: torch.Tensor, om: torch.Tensor, w: torch.Tensor, b: t
     return deform_conv_from_samples(A, _bf16(w), b.float())
 
 
+def deform_conv_any(x: torch.Tensor, om: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
+    """deform_conv_grid_sample, and deform_conv_loop on maps under 2 x 2 (a 1-row or 1-column map has no normalised coordinate)."""
+    if min(x.shape[-2:]) < 2:
+        return deform_conv_loop(x, om, w, b)
+    return deform_conv_grid_sample(x, om, w, b)
+
+
 def deform_tower(x: torch.Tensor, sd: Dict[str, torch.Tensor], prefix: str, num_convs: int = 4, norm: str = "GN",
-                 deform=deform_conv_grid_sample) -> torch.Tensor:
-    """oracle.head.tower for layers 0 .. n-2, then the DFConv2d layer (+ GroupNorm) + ReLU."""
+                 deform=deform_conv_any) -> torch.Tensor:
+    """oracle.head.tower for layers 0 .. n-2, then the DFConv2d layer (+ GroupNorm) + ReLU.  num_convs 1: the deformable layer reads the
+    tower input itself; num_convs 0: no tower (fcos.py:72-122 builds an empty nn.Sequential) and no deformable layer."""
+    if num_convs == 0:
+        return x
     step = 2 if norm in ("none", "", None) else 3
     x = plain_tower(x, sd, prefix, num_convs - 1, norm)
     k = step * (num_convs - 1)
@@ -149,20 +161,30 @@ def deform_tower(x: torch.Tensor, sd: Dict[str, torch.Tensor], prefix: str, num_
 def deform_fcos_head(features: List[torch.Tensor], sd: Dict[str, torch.Tensor], class_codes: Dict[str, torch.Tensor],
                      num_cls_convs: int = 4, num_box_convs: int = 4, use_scale: bool = True, use_bias: bool = True,
                      cond_block: bool = False, prefix: str = HEAD_PREFIX, cond_scales: Optional[List[float]] = None,
-                     norm: str = "GN", dtype=torch.float64):
-    """oracle.head.fcos_head (episodic branch, fcos.py:582-667) with MODEL.FCOS.USE_DEFORMABLE towers; computed in `dtype`."""
+                     norm: str = "GN", dtype=torch.float64, num_share_convs: int = 0, deformable: bool = True,
+                     deform=deform_conv_any):
+    """oracle.head.fcos_head (episodic branch, fcos.py:582-667) with MODEL.FCOS.USE_DEFORMABLE towers; computed in `dtype`.
+    num_share_convs: the shared tower in front of both towers, never deformable (fcos.py:388-397, 626).  Class codes (N, 256, k, k) run
+    with padding k // 2 (fcos.py:499-510).  deformable False: plain towers, i.e. oracle.head.fcos_head in `dtype`.  deform: the form of
+    the deformable conv (deform_conv_any, or deform_conv_loop / deform_conv_grid_sample on every level)."""
     sdd = {k: v.to(dtype) for k, v in sd.items()}
     w = class_codes["cls_conv"].to(dtype)
     b = class_codes["cls_bias"].to(dtype) if class_codes.get("cls_bias") is not None else None
+
+    def one_tower(x, name, n):
+        if deformable:
+            return deform_tower(x, sdd, f"{prefix}.{name}", n, norm, deform)
+        return plain_tower(x, sdd, f"{prefix}.{name}", n, norm)
+
     logits, regs, ctrs, ious = [], [], [], []
     for level, feat in enumerate(features):
-        feat = feat.to(dtype)
-        cls_t = deform_tower(feat, sdd, f"{prefix}.cls_tower", num_cls_convs, norm)
-        box_t = deform_tower(feat, sdd, f"{prefix}.bbox_tower", num_box_convs, norm)
+        feat = plain_tower(feat.to(dtype), sdd, f"{prefix}.share_tower", num_share_convs, norm)
+        cls_t = one_tower(feat, "cls_tower", num_cls_convs)
+        box_t = one_tower(feat, "bbox_tower", num_box_convs)
         if cond_block:
             logit = cond_conv_block(cls_t, w, b, scales=cond_scales)
         else:
-            logit = cond_conv_basic(cls_t, w, b, padding=0, use_bias=use_bias)
+            logit = cond_conv_basic(cls_t, w, b, padding=w.shape[-1] // 2, use_bias=use_bias)
         reg = F.conv2d(box_t, sdd[f"{prefix}.bbox_pred.weight"], sdd[f"{prefix}.bbox_pred.bias"], padding=1)
         if use_scale:
             reg = reg * sdd[f"{prefix}.scales.{level}.scale"]
