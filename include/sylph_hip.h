@@ -366,6 +366,28 @@ int sylph_codegen_classes(sylph_ctx* ctx, const float* boxes_dev, int shots, flo
  * B rows) or n_seg rows (class tokens). */
 int sylph_codegen_rois(sylph_ctx* ctx, int R, const float* boxes_dev, const int* roi_image, int n_seg, const int* seg_len,
                        float* codes_out_dev);
+/* Shot bank: the support path cut at its per-shot stage, so that the class codes of any draw of shots from a pool of instances cost
+ * a gather and a combination, not a network pass (the reference runs CodeGeneratorHead.forward_roi_align / ROIEncoder.forward on the
+ * support images of every seed and shot count again, meta_fcos_runner.py:497-560 over meta_learn_evaluation.py:256-365).
+ * sylph_shot_row_floats: floats of one bank row under the context's config -- 256 k^2 + 4 (k = cg_code_ksize; 256 + 4 with cg_type 1). */
+int sylph_shot_row_floats(sylph_ctx* ctx, int* n_out);
+/* The support pass of sylph_codegen_rois up to the last stage that looks at one shot alone: rows_out_dev (R, row) fp32, row r for ROI
+ * (roi_image[r], boxes_dev[r]) of the current batch.  CodeGenerator (code_generator.py:954-967 and utils.py:51-67, the per-shot half of
+ * forward_roi_align :924-1002): [0, 256 k^2) the pooled cls_conv map in (c, ky, kx) order (global mean, or the (3, 3) adaptive
+ * average), then the pooled bias term (BIAS_L2_NORM applied), the pooled shot-weight logit, the pooled class-scale term (0 for a head
+ * the config lacks) and one 0 pad.  ROIEncoder (roi_encoder.py:146-186): the shot's token after the last encoder layer, four 0 pads.
+ * The pass, its checks and its image table are those of sylph_codegen_rois (a call with the same list uploads no image table
+ * again); fails on a loaded query record.  Rows are valid under the weights, dtype and generator config that made them. */
+int sylph_codegen_shots(sylph_ctx* ctx, int R, const float* boxes_dev, const int* roi_image, float* rows_out_dev);
+/* The class codes of segments drawn from a bank rows_dev (n_rows, row) of such rows: idx[M] (host, each in [0, n_rows), repeats
+ * allowed) is cut into n_seg consecutive segments of seg_len[j] in [1, 16384] indices (host, sum = M); row j of codes_out_dev
+ * (n_seg, 256 k^2 + 1) is, bit for bit, what sylph_codegen_rois gives for a segment holding those shots in that order: the shot
+ * softmax or 1 / S and compute_code (code_generator.py:766-829), resp. the token mean and the two head FC stacks with the prior
+ * (roi_encoder.py:184-204).  weight_norm_out_dev (may be NULL): n_seg cls_weight_norm values when the generator has a scale head
+ * (code_generator.py:987-993), as sylph_normalize_codes takes them.  Needs no current batch and works on a loaded query record; every
+ * failure names the offending position. */
+int sylph_shot_combine(sylph_ctx* ctx, const float* rows_dev, int n_rows, int M, const int* idx, int n_seg, const int* seg_len,
+                       float* codes_out_dev, float* weight_norm_out_dev);
 /* How many sylph_codegen / sylph_codegen_classes / sylph_codegen_rois calls on this context had to upload their ROI tables (a repeated
  * list, or the same shots on the same batch shape, uploads none). */
 int sylph_roi_table_uploads(sylph_ctx* ctx, int64_t* n_out);

@@ -108,6 +108,7 @@ int build_support(sylph_ctx* c, Plan* P, SupportPass* Q) {
   if (naux > 0) RET(add_conv(c, ops, c->cg_bias, in, 256, Q->cg_bias_out, naux, segs, oc));
   tap_at(Q, SYLPH_SUP_CONV_OUT, 0, Q->cg_conv_out, true, S, npos);
   if (naux > 0) tap_at(Q, SYLPH_SUP_CONV_OUT, 1, Q->cg_bias_out, true, S, npos, naux, naux);
+  Q->n_shot_ops = ops.size();  // what follows looks at segments
   {
     const float *co = Q->cg_conv_out, *bo = Q->cg_bias_out;
     const int l2 = c->cfg.cg_bias_l2_norm, ib = c->cg_ib, iw = c->cg_iw, is = c->cg_is, ks = c->cfg.cg_code_ksize;
@@ -118,6 +119,31 @@ int build_support(sylph_ctx* c, Plan* P, SupportPass* Q) {
     });
   }
   Q->built = true;
+  return 0;
+}
+
+// The ROIEncoder's two head FC stacks on n class tokens cls[n][256] -> codes_out (n, 257): class k -> row k, the weight head at
+// column 0, the bias head (+ prior) at column 256.  h: [2][h_rows][hdim] hidden activations, n <= h_rows.  Shared by the support
+// pass and sylph_shot_combine.
+static int launch_roienc_heads(const sylph_ctx* c, const float* cls, int n, float* h, int h_rows, int hdim, float* codes_out, hipStream_t s) {
+  const float prior = -logf((1.f - 0.01f) / 0.01f);  // ROIEncoder hard-codes prior_prob = 0.01 (roi_encoder.py:139-140), whatever MODEL.FCOS.PRIOR_PROB says
+  for (int head = 0; head < 2; ++head) {
+    const std::vector<sylph_ctx::Lin>& fcs = head == 0 ? c->re.wh : c->re.bh;
+    const float* in = cls;
+    float* h0 = h + (size_t)head * h_rows * hdim;
+    for (size_t k = 0; k < fcs.size(); ++k) {
+      const sylph_ctx::Lin& f = fcs[k];
+      const bool last = k + 1 == fcs.size();
+      int r;
+      if (last) {
+        r = launch_linear(0, in, f.K, n, f.W, f.b, f.K, f.O, codes_out + (head == 0 ? 0 : 256), 257, 0, head == 1 ? prior : 0.f, s);
+      } else {
+        r = launch_linear(0, in, f.K, n, f.W, f.b, f.K, f.O, h0, f.O, 1, 0.f, s);
+        in = h0;
+      }
+      if (r != 0) return r;
+    }
+  }
   return 0;
 }
 
@@ -208,30 +234,14 @@ int build_support_roienc(sylph_ctx* c, Plan* P, SupportPass* Q) {
     RET(tap_copy(c, Q, ops, SYLPH_SUP_TOKENS, ++layer, tok, true, S, 1));
   }
   tap_at(Q, SYLPH_SUP_CLS_TOKENS, 0, Q->re_cls, true, 0, 1);
+  Q->n_shot_ops = ops.size();  // what follows looks at segments
+  Q->shot_tok = tok;
   {
     float* cls = Q->re_cls;
     float* x = tok;
     ops.push_back([=](hipStream_t s) { return launch_mean_tokens(x, QQ->seg_dev, QQ->n_seg, cls, s); });
-    const float prior = -logf((1.f - 0.01f) / 0.01f);  // ROIEncoder hard-codes prior_prob = 0.01 (roi_encoder.py:139-140), whatever MODEL.FCOS.PRIOR_PROB says
-    for (int head = 0; head < 2; ++head) {
-      const std::vector<sylph_ctx::Lin>& fcs = head == 0 ? R.wh : R.bh;
-      const float* in = cls;
-      float* h0 = Q->re_h + (size_t)head * S * hdim;
-      for (size_t k = 0; k < fcs.size(); ++k) {
-        const sylph_ctx::Lin f = fcs[k];
-        const bool last = k + 1 == fcs.size();
-        const float add = (last && head == 1) ? prior : 0.f;
-        const int off = head == 0 ? 0 : 256;
-        if (last) {
-          ops.push_back([=](hipStream_t s) {  // class k -> row k of the (classes, 257) output
-            return launch_linear(0, in, f.K, QQ->n_seg, f.W, f.b, f.K, f.O, QQ->cur_code_out + off, 257, 0, add, s);
-          });
-        } else {
-          ops.push_back([=](hipStream_t s) { return launch_linear(0, in, f.K, QQ->n_seg, f.W, f.b, f.K, f.O, h0, f.O, 1, 0.f, s); });
-          in = h0;
-        }
-      }
-    }
+    float* h = Q->re_h;
+    ops.push_back([=](hipStream_t s) { return launch_roienc_heads(c, cls, QQ->n_seg, h, S, hdim, QQ->cur_code_out, s); });
   }
   Q->built = true;
   return 0;
@@ -250,9 +260,21 @@ static int check_rois(const Plan* P, int R, const float* boxes, const int* roi_i
 
 // Host tables of a support call -> device, like the mixed-episode head's tables (api_head.hip ep_tables): uploaded when they differ
 // from what the pass holds, so a loop that repeats its list (or its shots on its batch shape) neither uploads nor synchronises.
+// seg_len == nullptr (sylph_codegen_shots, which stops in front of the segments): the image table alone; the segment table of the pass
+// stays what it is, so a sylph_codegen_rois call that follows with the same list and the segments of the call before uploads nothing.
 static int roi_tables(sylph_ctx* c, SupportPass* Q, const int* roi_image, int n_seg, const int* seg_len) {
-  if (Q->roi_image_dev && (int)Q->seg_len.size() == n_seg && std::equal(Q->roi_image.begin(), Q->roi_image.end(), roi_image) &&
-      std::equal(Q->seg_len.begin(), Q->seg_len.end(), seg_len))
+  const bool same_images = Q->roi_image_dev && (int)Q->roi_image.size() == Q->S && std::equal(Q->roi_image.begin(), Q->roi_image.end(), roi_image);
+  if (!seg_len) {
+    if (same_images) return 0;
+    Q->roi_image.clear();  // (a failure below leaves no key that would match a half-written table)
+    HIPCHK(hipStreamSynchronize(c->stream));  // the previous call may still be reading the table
+    if (!Q->roi_image_dev) RET(c->dalloc((void**)&Q->roi_image_dev, (size_t)Q->S * sizeof(int)));
+    HIPCHK(hipMemcpy(Q->roi_image_dev, roi_image, (size_t)Q->S * sizeof(int), hipMemcpyHostToDevice));
+    Q->roi_image.assign(roi_image, roi_image + Q->S);
+    ++c->roi_table_uploads;
+    return 0;
+  }
+  if (same_images && Q->seg_dev && (int)Q->seg_len.size() == n_seg && std::equal(Q->seg_len.begin(), Q->seg_len.end(), seg_len))
     return 0;
   Q->roi_image.clear(); Q->seg_len.clear();  // (a failure below leaves no key that would match half-written tables)
   std::vector<int> ri(roi_image, roi_image + Q->S), sl(seg_len, seg_len + n_seg);
@@ -289,6 +311,41 @@ static int run_support(sylph_ctx* c, Plan* P, int R, const float* boxes, const i
   Q->n_seg = n_seg;
   P->sup_last = Q;
   return run_ops(c, Q->ops, what);
+}
+
+// floats of one shot-bank row under the context's config: the code values of one shot, then bias term | logit | scale term | pad
+// (CodeGenerator), or the shot's token and four pad floats (ROIEncoder)
+static int shot_row_floats(const sylph_ctx* c) {
+  const int k = c->cfg.cg_type == 1 ? 1 : c->cfg.cg_code_ksize;
+  return 256 * k * k + 4;
+}
+
+// The per-shot part of one support call, its arguments checked: the ops of the plan's pass for R rows in front of its first
+// segment-wise op, then the rows.
+static int run_shots(sylph_ctx* c, Plan* P, int R, const float* boxes, const int* roi_image, float* rows_out) {
+  HIPCHK(hipSetDevice(c->device));
+  OwnerScope own(c, P);
+  auto& slot = P->sup[R];
+  if (!slot) { slot.reset(new SupportPass()); slot->S = R; }
+  SupportPass* Q = slot.get();
+  if (c->cfg.cg_type == 1) BUILD(build_support_roienc(c, P, Q), P);
+  else BUILD(build_support(c, P, Q), P);
+  RET(roi_tables(c, Q, roi_image, 0, nullptr));
+  Q->cur_boxes = boxes;
+  P->sup_last = Q;
+  std::vector<OpFn> ops(Q->ops.begin(), Q->ops.begin() + Q->n_shot_ops);
+  const int row = shot_row_floats(c);
+  if (c->cfg.cg_type == 1) {
+    const float* tok = Q->shot_tok;
+    ops.push_back([=](hipStream_t s) { return launch_shot_token_rows(tok, R, rows_out, row, s); });
+  } else {
+    const float *co = Q->cg_conv_out, *bo = Q->cg_bias_out;
+    const int naux = c->cg_naux, l2 = c->cfg.cg_bias_l2_norm, ib = c->cg_ib, iw = c->cg_iw, is = c->cg_is, ks = c->cfg.cg_code_ksize;
+    ops.push_back([=](hipStream_t s) {
+      return launch_shot_pool(co, 256, bo, naux > 0 ? naux : 1, ib, iw, is, R, 49, 256, ks, l2, rows_out, row, s);
+    });
+  }
+  return run_ops(c, ops, "codegen_shots");
 }
 
 // the stand-alone ROIAlign entries: R checked rows on a scratch context whose allocations are freed on return
@@ -423,6 +480,90 @@ int sylph_codegen_rois(sylph_ctx* c, int R, const float* boxes, const int* roi_i
   if (total != R) return fail("ROI list: the segment lengths sum to " + std::to_string(total) + ", not to R = " + std::to_string(R));
   if (R > 65535) return fail("ROI list: R = " + std::to_string(R) + " ROIs in one call; at most 65535");
   return run_support(c, P, R, boxes, roi_image, n_seg, seg_len, codes_out, "codegen_rois");
+}
+
+/* see include/sylph_hip.h */
+int sylph_shot_row_floats(sylph_ctx* c, int* n) {
+  if (!n) return fail("NULL argument");
+  if (c->cfg.cg_type != 1 && c->cfg.cg_code_ksize != 1 && c->cfg.cg_code_ksize != 3)
+    return fail("sylph_shot_row_floats: cg_code_ksize " + std::to_string(c->cfg.cg_code_ksize) + " (1 or 3)");
+  *n = shot_row_floats(c);
+  return 0;
+}
+
+int sylph_codegen_shots(sylph_ctx* c, int R, const float* boxes, const int* roi_image, float* rows_out) {
+  RET(refuse_on_record(c, "sylph_codegen_shots"));
+  Plan* P = c->cur;
+  RET(check_rois(P, R, boxes, roi_image));
+  if (!rows_out) return fail("NULL argument");
+  if (R > 65535) return fail("ROI list: R = " + std::to_string(R) + " ROIs in one call; at most 65535");
+  return run_shots(c, P, R, boxes, roi_image, rows_out);
+}
+
+int sylph_shot_combine(sylph_ctx* c, const float* rows, int n_rows, int M, const int* idx, int n_seg, const int* seg_len, float* codes_out,
+                       float* weight_norm_out) {
+  const bool roienc = c->cfg.cg_type == 1;
+  if (roienc ? !c->has_roienc : !c->has_codegen) return fail(roienc ? "ROIEncoder weights were not loaded" : "code generator weights were not loaded");
+  if (!rows || !idx || !seg_len || !codes_out) return fail("NULL argument");
+  if (n_rows < 1) return fail("shot bank: n_rows = " + std::to_string(n_rows) + " (the bank is empty)");
+  if (M < 1) return fail("shot bank: M = " + std::to_string(M) + " (at least one index is needed)");
+  if (n_seg < 1) return fail("shot bank: n_seg = " + std::to_string(n_seg) + " (at least one segment is needed)");
+  for (int i = 0; i < M; ++i)
+    if (idx[i] < 0 || idx[i] >= n_rows)
+      return fail("shot bank: idx[" + std::to_string(i) + "] = " + std::to_string(idx[i]) + " is outside the bank of " + std::to_string(n_rows) + " rows");
+  long total = 0;
+  int max_len = 0;
+  for (int j = 0; j < n_seg; ++j) {
+    if (seg_len[j] < 1) return fail("shot bank: seg_len[" + std::to_string(j) + "] = " + std::to_string(seg_len[j]) + " (a segment needs at least one shot)");
+    if (seg_len[j] > TAIL_MAX_LEN)
+      return fail("shot bank: seg_len[" + std::to_string(j) + "] = " + std::to_string(seg_len[j]) + " shots in one segment; at most " + std::to_string(TAIL_MAX_LEN));
+    total += seg_len[j];
+    max_len = seg_len[j] > max_len ? seg_len[j] : max_len;
+  }
+  if (total != M) return fail("shot bank: the segment lengths sum to " + std::to_string(total) + ", not to M = " + std::to_string(M));
+  HIPCHK(hipSetDevice(c->device));
+  // tables: idx [M] | {first index, shots} [n_seg], 8-byte aligned
+  const size_t seg_off = ((size_t)M + 1) / 2 * 2, ints = seg_off + 2 * (size_t)n_seg, need = ints * sizeof(int);
+  if (c->shot_ev) HIPCHK(hipEventSynchronize(c->shot_ev));
+  else HIPCHK(hipEventCreateWithFlags(&c->shot_ev, hipEventDisableTiming));
+  Plan* owner = c->alloc_owner;
+  c->alloc_owner = nullptr;  // the context's, not a plan's
+  struct Restore { sylph_ctx* c; Plan* p; ~Restore() { c->alloc_owner = p; } } restore{c, owner};
+  if (need > c->shot_tab_cap) {
+    if (c->shot_tab) c->dfree(c->shot_tab);
+    c->shot_tab = nullptr; c->shot_tab_cap = 0;
+    RET(c->dalloc(&c->shot_tab, need * 2));
+    c->shot_tab_cap = need * 2;
+  }
+  const int hdim = c->cfg.head_fc_dim > 256 ? c->cfg.head_fc_dim : 256;
+  if (roienc && n_seg > c->shot_seg_cap) {
+    if (c->shot_cls) c->dfree(c->shot_cls);
+    if (c->shot_h) c->dfree(c->shot_h);
+    c->shot_cls = c->shot_h = nullptr; c->shot_seg_cap = 0;
+    RET(c->dalloc((void**)&c->shot_cls, (size_t)n_seg * 2 * 256 * sizeof(float)));
+    RET(c->dalloc((void**)&c->shot_h, (size_t)2 * n_seg * 2 * hdim * sizeof(float)));
+    c->shot_seg_cap = n_seg * 2;
+  }
+  c->shot_host.assign(ints, 0);
+  std::copy(idx, idx + M, c->shot_host.begin());
+  for (int j = 0, i0 = 0; j < n_seg; i0 += seg_len[j], ++j) {
+    c->shot_host[seg_off + 2 * j] = i0;
+    c->shot_host[seg_off + 2 * j + 1] = seg_len[j];
+  }
+  HIPCHK(hipMemcpyAsync(c->shot_tab, c->shot_host.data(), need, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipEventRecord(c->shot_ev, c->stream));
+  const int* idx_dev = reinterpret_cast<const int*>(c->shot_tab);
+  const int2* seg_dev = reinterpret_cast<const int2*>(idx_dev + seg_off);
+  const int row = shot_row_floats(c);
+  if (roienc) {
+    KCHK(launch_shot_mean_tokens(rows, row, idx_dev, seg_dev, n_seg, c->shot_cls, c->stream), "shot_combine (token mean)");
+    KCHK(launch_roienc_heads(c, c->shot_cls, n_seg, c->shot_h, c->shot_seg_cap, hdim, codes_out, c->stream), "shot_combine (heads)");
+    return 0;
+  }
+  KCHK(launch_shot_combine(rows, row, idx_dev, seg_dev, n_seg, max_len, row - 4, c->cg_ib >= 0, c->cg_iw >= 0, c->cg_is >= 0, codes_out,
+                           weight_norm_out, c->stream),
+       "shot_combine");
+  return 0;
 }
 
 int sylph_roi_table_uploads(sylph_ctx* c, int64_t* n) {

@@ -206,6 +206,7 @@ void sylph_ctx_destroy(sylph_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
   if (c->merge_ev) (void)hipEventDestroy(c->merge_ev);
+  if (c->shot_ev) (void)hipEventDestroy(c->shot_ev);
   for (auto& kv : c->plans) free_plan(c, kv.second.get());
   c->plans.clear();
   for (sylph_record* r : c->records) delete r;  // (their device bytes are among c->allocs)

@@ -246,6 +246,14 @@ struct sylph_ctx {
   size_t merge_tab_cap = 0;
   std::vector<char> merge_host;
   hipEvent_t merge_ev = nullptr;
+  // sylph_shot_combine: the call's index list and segment table (scratch like the merge tables: rewritten by every call, the event guards
+  // the host copy's reuse) and, for the ROIEncoder, the class tokens and head activations of its segments
+  void* shot_tab = nullptr;
+  size_t shot_tab_cap = 0;
+  std::vector<int> shot_host;
+  hipEvent_t shot_ev = nullptr;
+  float *shot_cls = nullptr, *shot_h = nullptr;
+  int shot_seg_cap = 0;
   void* zeros = nullptr;  // 256 B of zeros (conv out-of-image taps)
   // small batches: the two FCOS towers of a head pass run on two streams (fork / join events around the bbox tower, api_head.hip)
   hipStream_t side_stream = nullptr;
@@ -301,6 +309,10 @@ struct SupportPass {
     const float *gamma = nullptr, *beta = nullptr;
   };
   std::map<std::pair<int, int>, SupTap> taps;
+  // sylph_codegen_shots: ops[0, n_shot_ops) are the per-shot stages (everything in front of the tail resp. the token mean);
+  // shot_tok: the ROIEncoder's tokens after the last encoder layer, [S][256]
+  size_t n_shot_ops = 0;
+  const float* shot_tok = nullptr;
   // the current call (read by the ops at launch time)
   const float* cur_boxes = nullptr;
   int n_seg = 0;      // codes of the current call: the segments of its ROI list

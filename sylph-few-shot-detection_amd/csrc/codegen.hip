@@ -188,8 +188,6 @@ __global__ __launch_bounds__(256) void codegen_tail_kernel(const float* __restri
   }
 }
 
-constexpr int TAIL_MAX_LEN = 16384;  // 64 KiB of shot weights in LDS
-
 int launch_codegen_tail(const float* conv_out, int conv_ld, const float* aux_out, int aux_ld, int ib, int iw, int is, const int2* seg_dev,
                         int n_seg, int max_len, int npos, int C, int ksize, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s) {
   if (npos > 64 || n_seg < 1 || max_len < 1 || max_len > TAIL_MAX_LEN || (ksize != 1 && !(ksize == 3 && npos == 49))) return -1;

@@ -273,6 +273,7 @@ struct LevelDesc { int row0; int H, W; float scale; };  // per (image, level): r
 // row r: box r on image roi_image_dev[r] of the batch (lv_dev: an entry per (image, level))
 int launch_roi_align(DType dt, const void* feats, int ld, const LevelDesc* lv_dev, int nlevels, const float* boxes_dev,
                      const int* roi_image_dev, int R, int out_size, void* out, hipStream_t s);
+constexpr int TAIL_MAX_LEN = 16384;  // longest segment of a tail / shot-combine launch: 64 KiB of shot weights in LDS
 // one code per segment of the ROI list: seg_dev[j] = {first row, rows}; max_len = the longest segment (sizes the LDS weight table)
 int launch_codegen_tail(const float* conv_out, int conv_ld, const float* aux_out, int aux_ld, int ib, int iw, int is, const int2* seg_dev,
                         int n_seg, int max_len, int npos, int C, int ksize, int bias_l2_norm, float* code_out, float* wnorm_out, hipStream_t s);
@@ -293,5 +294,14 @@ int launch_linear(int x_is_bf16, const void* x, int ldx, int S, const float* W, 
                   int ldy, int relu, float add, hipStream_t s);
 int launch_add_layernorm(float* x, const float* r, int S, const float* gamma, const float* beta, hipStream_t s);
 int launch_mean_tokens(const float* x, const int2* seg_dev, int n_seg, float* out, hipStream_t s);
+
+// shot_bank.hip: the per-shot rows of the support path ([R][row_ld] fp32, row_ld >= C k^2 + 4 resp. 256) and the code of any gathered
+// list of them: segment j = rows idx_dev[seg_dev[j].x + i], i < seg_dev[j].y; n = C k^2 code values per row
+int launch_shot_pool(const float* conv_out, int conv_ld, const float* aux_out, int aux_ld, int ib, int iw, int is, int R, int npos, int C,
+                     int ksize, int bias_l2_norm, float* rows, int row_ld, hipStream_t s);
+int launch_shot_token_rows(const float* tok, int R, float* rows, int row_ld, hipStream_t s);
+int launch_shot_combine(const float* rows, int row_ld, const int* idx_dev, const int2* seg_dev, int n_seg, int max_len, int n, int has_b,
+                        int has_w, int has_s, float* code_out, float* wnorm_out, hipStream_t s);
+int launch_shot_mean_tokens(const float* rows, int row_ld, const int* idx_dev, const int2* seg_dev, int n_seg, float* out, hipStream_t s);
 
 }  // namespace sylph

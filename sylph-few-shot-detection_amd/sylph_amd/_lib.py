@@ -92,6 +92,9 @@ PROTOTYPES = {
     "sylph_codegen": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sylph_codegen_classes": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "sylph_codegen_rois": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_int, POINTER(c_int), c_void_p]),
+    "sylph_shot_row_floats": (c_int, [c_void_p, POINTER(c_int)]),
+    "sylph_codegen_shots": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p]),
+    "sylph_shot_combine": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int), c_void_p, c_void_p]),
     "sylph_roi_table_uploads": (c_int, [c_void_p, POINTER(c_int64)]),
     "sylph_codegen_weight_norm": (c_int, [c_void_p, c_void_p]),
     "sylph_normalize_codes": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

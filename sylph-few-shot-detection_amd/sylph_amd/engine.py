@@ -6,7 +6,7 @@ call through the C ABI (include/sylph_hip.h) into hand-written HIP kernels.
 import ctypes
 import os
 from ctypes import c_int, c_int64, c_void_p
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -934,6 +934,60 @@ class Engine:
         if sum(sl) != len(ri):
             raise ValueError(f"the segment lengths sum to {sum(sl)}, not to R = {len(ri)}")
         return self._run_codegen("codegen_rois", bx, len(sl), len(ri), _ptr(bx), _iarr(ri), len(sl), _iarr(sl))
+
+    # ---- shot bank (sylph_amd.shots.ShotBank) ----
+    @property
+    def shot_row_floats(self) -> int:
+        """Floats of one shot-bank row under this engine's config (sylph_shot_row_floats)."""
+        n = c_int(0)
+        check(self.L.sylph_shot_row_floats(self._ctx, ctypes.byref(n)), "shot_row_floats")
+        return n.value
+
+    def shot_key(self) -> Dict[str, Any]:
+        """What a bank's rows depend on besides the weights: generator type, code kernel size, dtype, row width."""
+        return {"generator": "ROIEncoder" if self.is_roi_encoder else "CodeGenerator", "code_ksize": self.code_ksize,
+                "dtype": "f32" if self.dtype == "fp32" else self.dtype, "row_floats": self.shot_row_floats}
+
+    def codegen_shots(self, boxes: torch.Tensor, roi_image) -> torch.Tensor:
+        """The per-shot rows of the ROI list over the current batch (sylph_codegen_shots) -> (R, shot_row_floats) fp32: everything
+        codegen_rois computes from one ROI alone.  combine_shots turns any list of such rows into class codes."""
+        bx, ri = self._check_rois(boxes, roi_image)
+        self._stream()
+        out = torch.empty(len(ri), self.shot_row_floats, device=self.device)
+        self._keep_boxes = bx
+        check(self.L.sylph_codegen_shots(self._ctx, len(ri), _ptr(bx), _iarr(ri), _ptr(out)), "codegen_shots")
+        self._sup_rows = len(ri)
+        return out
+
+    def combine_shots(self, rows: torch.Tensor, idx, seg_len) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """Class codes of segments drawn from bank rows (sylph_shot_combine): idx (M) row numbers, repeats allowed, cut into consecutive
+        segments of seg_len[j] >= 1 -> ((n_seg, 256 k^2 + 1) un-normalised codes, (n_seg,) cls_weight_norm or None without a
+        SCALE_LAYER): bit for bit what codegen_rois gives for segments holding those shots in that order.  Needs no current batch."""
+        if rows is None or idx is None or seg_len is None:
+            raise ValueError("rows, idx and seg_len must be given")
+        if not (torch.is_tensor(rows) and rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2 and rows.is_contiguous()):
+            raise ValueError("rows must be a contiguous 2-d fp32 tensor on the device")
+        if rows.shape[1] != self.shot_row_floats:
+            raise ValueError(f"bank rows of {rows.shape[1]} floats on an engine whose shot rows are {self.shot_row_floats} floats wide "
+                             f"({'ROIEncoder' if self.is_roi_encoder else 'CodeGenerator'}, code kernel size {self.code_ksize})")
+        ix = [int(i) for i in (idx.tolist() if torch.is_tensor(idx) or hasattr(idx, "tolist") else idx)]
+        sl = [int(n) for n in (seg_len.tolist() if torch.is_tensor(seg_len) or hasattr(seg_len, "tolist") else seg_len)]
+        if len(sl) < 1:
+            raise ValueError("the draw has no segment (n_seg < 1)")
+        for i, v in enumerate(ix):
+            if v < 0 or v >= rows.shape[0]:
+                raise ValueError(f"idx[{i}] = {v} is outside the bank of {rows.shape[0]} rows")
+        for j, n in enumerate(sl):
+            if n < 1:
+                raise ValueError(f"seg_len[{j}] = {n}: a segment needs at least one shot")
+        if sum(sl) != len(ix):
+            raise ValueError(f"the segment lengths sum to {sum(sl)}, not to M = {len(ix)}")
+        self._stream()
+        codes = torch.empty(len(sl), self.code_len, device=self.device)
+        wn = torch.empty(len(sl), device=self.device) if (not self.is_roi_encoder and int(self.sc.cg_has_scale)) else None
+        check(self.L.sylph_shot_combine(self._ctx, _ptr(rows), rows.shape[0], len(ix), _iarr(ix), len(sl), _iarr(sl), _ptr(codes), _ptr(wn)),
+              "shot_combine")
+        return codes, wn
 
     def roi_table_uploads(self) -> int:
         """How many codegen* calls of this engine uploaded their ROI tables (a repeated identical list uploads none)."""

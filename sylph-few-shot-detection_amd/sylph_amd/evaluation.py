@@ -281,6 +281,61 @@ def inference_on_annotated_images(model, data_loader, chunk: int = 10, class_nam
     return results
 
 
+def build_shot_bank(model, data_loader, chunk: int = 10):
+    """A ShotBank of every annotated instance of a loader, at one backbone pass per image.  The loader is
+    inference_on_annotated_images': each item a list of annotated records, run as ONE batch (model.forward_shot_rows).  A row is
+    remembered with its class id, its image id (the record's "image_id", else the running image count) and its annotation index
+    within the record.  `chunk` is inference_on_annotated_images' argument, accepted so that the two take the same call; a bank
+    row is per instance and does not depend on it (segments are cut at the draw)."""
+    from .shots import ShotBank
+    if int(chunk) < 1:
+        raise ValueError(f"chunk must be at least 1, got {chunk}")
+    engine = model.engine
+    bank = ShotBank(engine.shot_key(), device=engine.device)
+    seen = 0
+    with ExitStack() as stack:
+        if isinstance(model, nn.Module):
+            stack.enter_context(inference_context(model))
+        stack.enter_context(torch.no_grad())
+        for records in data_loader:
+            rows, image_index, ann_index, class_ids = model.forward_shot_rows(records)
+            if rows is not None:
+                ids = [int(rec.get("image_id", seen + b)) for b, rec in enumerate(records)]
+                bank.append(rows, class_ids, [ids[b] for b in image_index], ann_index)
+            seen += len(records)
+    bank.tensor()
+    logger.info(f"Banked {len(bank)} support instances of {len(bank.classes())} classes from {seen} images, {bank.nbytes} device bytes")
+    return bank
+
+
+def class_codes_from_bank(model, bank, idx, seg_len, class_ids, class_names=None, normalize: bool = True) -> List[Dict[str, Any]]:
+    """The class codes of one draw from a ShotBank (bank.draw), with no support pass: segment j -- the rows idx[...] of seg_len[j]
+    shots -- is class class_ids[j].  Returns inference_on_annotated_images' records ({"support_set_target", "class_name",
+    "class_code": {"cls_conv" (1, 256, k, k), "cls_bias" (1, 1, 1, 1)[, "cls_weight_norm" (1, 1, 1, 1)]}}, host tensors; no
+    "acc_weight": a draw's code is whole, nothing is left to accumulate) in the order of the segments; the codes are bit for bit those of model.forward_class_codes_rois on segments holding
+    the same instances in the same order (Engine.combine_shots).  normalize: the records then go through inference_normalization
+    (sylph_normalize_codes with cls_weight_norm) like the runner's; the ROIEncoder's codes need none."""
+    engine = model.engine
+    bank.check_key(engine)
+    if len(class_ids) != len(seg_len):
+        raise ValueError(f"{len(class_ids)} class ids for {len(seg_len)} segments")
+    with torch.no_grad():
+        codes, wn = engine.combine_shots(bank.tensor(), idx, seg_len)
+    codes = codes.cpu()  # the only read-back of the draw
+    wn = wn.cpu() if wn is not None else None
+    k, n = engine.code_ksize, 256 * engine.code_ksize ** 2
+    results = []
+    for j, cid in enumerate(class_ids):
+        cc = {"cls_conv": codes[j, :n].reshape(1, 256, k, k).clone(), "cls_bias": codes[j, n:n + 1].reshape(1, 1, 1, 1).clone()}
+        if wn is not None:
+            cc["cls_weight_norm"] = wn[j:j + 1].reshape(1, 1, 1, 1).clone()
+        name = str(cid) if class_names is None else str(class_names[cid])
+        results.append({"support_set_target": int(cid), "class_name": name, "class_code": cc})
+    if normalize and not engine.is_roi_encoder:
+        results = inference_normalization(model, results)
+    return results
+
+
 class _NoOpEvaluator:
     def reset(self):
         pass

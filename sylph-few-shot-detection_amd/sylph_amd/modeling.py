@@ -446,6 +446,31 @@ class MetaOneStageDetector(nn.Module):
         self.backbone(images=[rec["image"] for rec in records])
         return self.code_generator.forward_rois(torch.cat(boxes, dim=0), roi_image, seg_len)
 
+    def forward_shot_rows(self, records: List[Dict[str, Any]]):
+        """Shot-bank rows of annotated images at ONE backbone pass per image: every annotated instance of `records` (dicts with "image"
+        and "instances" carrying gt_boxes / gt_classes), in record order, then box order -> (rows (R, shot_row_floats) on the device,
+        image_index [R], ann_index [R], class_ids [R]); (None, [], [], []) when no record carries a box.  Row r is everything
+        forward_class_codes_rois computes from instance r alone (Engine.codegen_shots); Engine.combine_shots makes the code of any
+        list of such rows.  Nothing is drawn at random."""
+        assert not self.training, "Not for training"
+        assert self.episodic_learning and self.code_generator is not None
+        boxes, image_index, ann_index, class_ids = [], [], [], []
+        for b, rec in enumerate(records):
+            inst = rec.get("instances")
+            if inst is None or len(inst.gt_boxes.tensor) == 0:
+                continue
+            gt = inst.gt_boxes.tensor.detach().float().cpu().reshape(-1, 4)
+            cls = torch.as_tensor(inst.gt_classes).reshape(-1).tolist()
+            assert len(cls) == gt.shape[0], f"record {b}: {len(cls)} classes for {gt.shape[0]} boxes"
+            boxes.append(gt)
+            image_index += [b] * len(cls)
+            ann_index += list(range(len(cls)))
+            class_ids += [int(c) for c in cls]
+        if not boxes:
+            return None, [], [], []
+        self.backbone(images=[rec["image"] for rec in records])
+        return self.engine.codegen_shots(torch.cat(boxes, dim=0), image_index), image_index, ann_index, class_ids
+
     def normalize_class_code(self, codes: List[Dict]):
         """code_generator.py:877-897 via meta_one_stage_detector.py:256-259 (mutates the list)."""
         assert self.episodic_learning

@@ -12,7 +12,7 @@ import torch
 
 from . import config as _config
 from . import distributed as D
-from .evaluation import (cache_query_dataset, format_class_codes_shared, inference_normalization, inference_on_dataset_with_class_codes,
+from .evaluation import (cache_query_dataset, class_codes_from_bank, format_class_codes_shared, inference_normalization, inference_on_dataset_with_class_codes,
                          inference_on_dataset_with_code_sets, inference_on_support_set_dataset, inference_on_support_set_dataset_base,
                          release_query_records)
 from .modeling import build_model as _build_model
@@ -214,7 +214,7 @@ class MetaFCOSRunner:
     def _do_test_meta_learning(self, cfg, model, support_loader=None, query_loader=None, evaluator=None, base_support_loader=None,
                                output_folder: Optional[str] = None, num_classes: Optional[int] = None, train_iter=None,
                                model_tag: str = "default", dataset_names: Optional[List[str]] = None, fuse_repeats: bool = False,
-                               cache_queries: bool = False, cache_max_bytes: Optional[int] = None):
+                               cache_queries: bool = False, cache_max_bytes: Optional[int] = None, shot_bank=None, bank_draws=None):
         """meta_fcos_runner.py:451-672.
 
         * With explicit loaders (support_loader + query_loader): ONE dataset / seed; returns (results, class_codes) -- the form
@@ -231,7 +231,13 @@ class MetaFCOSRunner:
         * cache_queries=True: ONE network pass per dataset's query set, kept as query records (evaluation.cache_query_dataset, at most
           cache_max_bytes of device memory; default: half of what is free); every seed is then scored from the records -- class-conditional
           conv and decode only.  A dataset whose records would not fit (estimated from its first record) keeps the plain loop, with a
-          logged reason.  The results dict is the one of the loop above."""
+          logged reason.  The results dict is the one of the loop above.
+        * shot_bank=ShotBank with bank_draws=[(shots, seed), ...]: no support pass at all -- every draw's class codes come from the bank
+          (evaluation.class_codes_from_bank on shot_bank.draw(shots, seed)); the query side runs as above, on query_loader, or on the
+          datasets' loaders, or (cache_queries) on their records.  Returns results[f"shots{K}_seed{s}"][dataset] (dataset "query" for an
+          explicit query_loader).  One rank only."""
+        if shot_bank is not None or bank_draws is not None:
+            return self._bank_sweep(cfg, model, shot_bank, bank_draws, query_loader, evaluator, dataset_names, cache_queries, cache_max_bytes)
         if support_loader is not None or query_loader is not None:
             return self._episode(cfg, model, support_loader, query_loader, evaluator, base_support_loader, output_folder, num_classes)
         names = list(dataset_names if dataset_names is not None else cfg.DATASETS.TEST)
@@ -327,6 +333,48 @@ class MetaFCOSRunner:
                             results[model_tag][name]["bbox"][f"{k}_std"] = float(np.array(hist).std())
         for recs in cached.values():
             release_query_records(recs)
+        return results
+
+    def _bank_sweep(self, cfg, model, shot_bank, bank_draws, query_loader=None, evaluator=None, dataset_names=None,
+                    cache_queries: bool = False, cache_max_bytes: Optional[int] = None):
+        """_do_test_meta_learning with a shot bank: one query evaluation per (shots, seed) draw, class codes from the bank."""
+        world = D.get_world_size()
+        if world > 1:
+            raise NotImplementedError(f"shot_bank: a bank's rows live on one device and its draws are not gathered across ranks; world size is "
+                                      f"{world}, run the sweep on one rank")
+        if shot_bank is None or not bank_draws:
+            raise ValueError("shot_bank and bank_draws go together: a ShotBank and a non-empty list of (shots, seed) draws")
+        if query_loader is not None:
+            datasets = [("query", query_loader, evaluator)]
+        else:
+            names = list(dataset_names if dataset_names is not None else cfg.DATASETS.TEST)
+            assert len(names)
+            datasets = [(name, None, None) for name in names]
+        results = OrderedDict()
+        cached = {}
+        try:
+            for shots, seed in bank_draws:
+                idx, seg_len, class_ids = shot_bank.draw(int(shots), int(seed))
+                codes = class_codes_from_bank(model, shot_bank, idx, seg_len, class_ids)
+                class_codes = format_class_codes_shared(codes, device=model.device)
+                tag = f"shots{int(shots)}_seed{int(seed)}"
+                results[tag] = OrderedDict()
+                for name, loader, ev in datasets:
+                    if loader is None:
+                        ev = self.get_evaluator(cfg, name)
+                        if name not in cached and cache_queries:
+                            try:
+                                cached[name] = cache_query_dataset(model, self.build_episodic_learning_detection_test_query_loader(cfg, name),
+                                                                   max_bytes=cache_max_bytes)
+                            except MemoryError as e:
+                                cached[name] = None
+                                logger.info(f"cache_queries: {name} keeps one network pass per draw ({e})")
+                        loader = cached.get(name) or self.build_episodic_learning_detection_test_query_loader(cfg, name)
+                    results[tag][name] = inference_on_dataset_with_class_codes(model, loader, ev, class_codes)
+        finally:
+            for recs in cached.values():
+                if recs:
+                    release_query_records(recs)
         return results
 
     def do_test(self, cfg, model, train_iter=None, support_loader=None, query_loader=None, evaluator=None):
