@@ -271,6 +271,23 @@ int sylph_merge_views(sylph_ctx* ctx, int n_src, int n_views, const int* view_sr
                       const float* view_w, const int* view_flip, int max_in, const float* boxes_dev, const float* scores_dev,
                       const int* classes_dev, const int* counts_dev, int max_out, float* out_boxes_dev, float* out_scores_dev,
                       int* out_classes_dev, int* out_view_dev, int* out_row_dev, int* out_counts_dev, int* status_dev);
+/* The same merge for sources of any size: inputs, outputs and the rules 1 - 5 are those written above sylph_merge_views, and on every
+ * input that both entries accept the result is the same bit for bit.  The pool lives in the caller's workspace_dev (16-byte aligned, any
+ * contents, nothing is kept in it between calls) of at least sylph_merge_views_large_bytes(n_src, n_views, max_in) bytes: about 33 bytes
+ * per row of the [n_views][max_in] buffers rounded up to a power of two; the function returns -1 and sets sylph_last_error() for a
+ * non-positive argument or n_views * max_in >= 2^31.  topk is rule 5's K: above 0 that many, 0 keeps every kept box, -1 takes
+ * POST_NMS_TOPK_TEST.  A source whose views could hold more than MERGE_LARGE_POOL_CAP = 1048576 rows together (max_in x its views), a NULL
+ * workspace and a workspace smaller than the bytes function says fail by name before any launch.  status_dev[0] is cleared by the call;
+ * bit1 (value 2) = a source was truncated at max_out, whose first max_out rows in order are then written.  The call runs on the context's
+ * stream and reads nothing back; like sylph_merge_views its only wait is for the previous merge call's upload of the view tables to have
+ * left the host copy, never for a kernel.  It needs no current batch and works while a query record is loaded.
+ * Class ids are any int32, compared for equality only; a count outside [0, max_in] is clamped. */
+int64_t sylph_merge_views_large_bytes(int n_src, int n_views, int max_in);
+int sylph_merge_views_large(sylph_ctx* ctx, int n_src, int n_views, const int* view_src, const float* view_x0, const float* view_y0,
+                            const float* view_w, const int* view_flip, int max_in, const float* boxes_dev, const float* scores_dev,
+                            const int* classes_dev, const int* counts_dev, int topk, int max_out, float* out_boxes_dev,
+                            float* out_scores_dev, int* out_classes_dev, int* out_view_dev, int* out_row_dev, int* out_counts_dev,
+                            int* status_dev, void* workspace_dev, int64_t workspace_bytes);
 
 /* COCO bbox evaluation on detection rows, device side: what evaluator.evaluate() (sylph/evaluation/meta_learn_evaluation.py:465) hands to
  * pycocotools -- pycocotools/cocoeval.py evaluateImg (sylph_coco_match) and accumulate (sylph_coco_accumulate), useCats = 1 -- in float64, in the

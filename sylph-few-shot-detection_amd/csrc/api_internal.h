@@ -241,7 +241,7 @@ struct sylph_ctx {
   // every live record this context allocated
   const sylph_record* rec = nullptr;
   std::vector<sylph_record*> records;
-  // sylph_merge_views: the call's view tables (scratch: rewritten by every call; the event guards the host copy's reuse)
+  // sylph_merge_views, sylph_merge_views_large: the call's view tables (scratch: rewritten by every call; the event guards the host copy's reuse)
   void* merge_tab = nullptr;
   size_t merge_tab_cap = 0;
   std::vector<char> merge_host;

@@ -99,6 +99,34 @@ int launch_merge_views(int n_src, const int* src_off, const int* src_views, cons
                        int max_in, const float* boxes, const float* scores, const int* classes, const int* counts, float nms_thresh,
                        int post_nms_topk, int max_out, float* out_boxes, float* out_scores, int* out_classes, int* out_view, int* out_row,
                        int* out_counts, int* status, hipStream_t s);
+// merge_views_large.hip: the same merge with the pool in a caller's workspace (sylph_merge_views_large).  Rows one source's views may hold
+// together.  It bounds the workspace, not the time: a one-class source with K = 0 is one serial, roughly quadratic walk of
+// pool / MERGE_LARGE_CHUNK chunks (DESIGN: 6.1 s at 262 144 rows, about 100 s at the cap by extrapolation, not measured).
+constexpr int MERGE_LARGE_POOL_CAP = 1048576;
+constexpr int MERGE_LARGE_SORT_TILE = 2048;  // keys one block sorts in LDS; the sorted length is a power of two of at least one tile
+constexpr int MERGE_LARGE_CHUNK = 64;        // boxes per step of a segment's walk, as in merge_views_kernel
+constexpr int MERGE_LARGE_KEPT_LDS = 2048;   // kept boxes of a segment that stay in LDS; later ones spill to the workspace
+// merge_large_layout(...) is THE workspace layout -- launch, the host check, sylph_merge_views_large_bytes all call it.  bytes = -1: refused
+// (a non-positive argument, or n_views * max_in does not fit a row index).  Every part starts 16-byte aligned.
+struct MergeLargeLayout { long long bytes, rows, P, keys_off, kbox_off, kept_off, bounds_off; };
+inline MergeLargeLayout merge_large_layout(int n_src, int n_views, int max_in) {
+  MergeLargeLayout L = {-1, 0, 0, 0, 0, 0, 0};
+  if (n_src <= 0 || n_views <= 0 || max_in <= 0 || (long long)n_views * max_in >= (1LL << 31)) return L;
+  L.rows = (long long)n_views * max_in;
+  L.P = MERGE_LARGE_SORT_TILE;
+  while (L.P < L.rows) L.P <<= 1;
+  const auto up16 = [](long long v) { return (v + 15) / 16 * 16; };
+  L.keys_off = 0;                                  // P 128-bit keys
+  L.kbox_off = L.keys_off + 16 * L.P;              // rows float4: the kept boxes a segment spills
+  L.kept_off = L.kbox_off + 16 * L.rows;           // rows bytes: kept or not, per sorted position
+  L.bounds_off = L.kept_off + up16(L.rows);        // n_src x (begin, end) of every source's kept run
+  L.bytes = L.bounds_off + up16(8LL * n_src);
+  return L;
+}
+// status (one int) is cleared here and receives 2 when a source was truncated; K <= 0 keeps every kept box
+int launch_merge_views_large(int n_src, int n_views, const MergeView* views, int max_in, const float* boxes, const float* scores,
+                             const int* classes, const int* counts, float nms_thresh, int K, int max_out, float* out_boxes, float* out_scores,
+                             int* out_classes, int* out_view, int* out_row, int* out_counts, int* status, void* workspace, hipStream_t s);
 // coco_eval.hip: COCO bbox matching and accumulation (include/sylph_hip.h: sylph_coco_match / sylph_coco_accumulate)
 // ground-truth boxes of one (image, category) pair whose D x G float64 IoU tile (D <= max_det) is kept in LDS; a pair with more recomputes
 // every IoU where the walk visits it and keeps its matched flags in the caller's scratch.  The bound holds up to max_det = 131; a larger

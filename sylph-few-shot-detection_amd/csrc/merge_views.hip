@@ -11,31 +11,9 @@
 // Nothing is kept between calls and no atomic touches global memory.
 #include "common.h"
 #include "kernels.h"
+#include "merge_math.h"
 
 namespace sylph {
-
-// float bits -> unsigned that orders like the float (-0 as +0)
-__device__ __forceinline__ unsigned merge_score_key(float s) {
-  const unsigned u = __float_as_uint(s);
-  if ((u << 1) == 0u) return 0x80000000u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// IoU > thr for two boxes of the same class: the arithmetic of nms_overlap (detect.hip)
-__device__ __forceinline__ bool merge_overlap(float x1, float y1, float x2, float y2, float iarea, float4 b, float thr) {
-  const float xx1 = fmaxf(x1, b.x), yy1 = fmaxf(y1, b.y);
-  const float xx2 = fminf(x2, b.z), yy2 = fminf(y2, b.w);
-  const float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
-  const float inter = w * h;
-  const float jarea = (b.z - b.x) * (b.w - b.y);
-  return inter / (iarea + jarea - inter) > thr;
-}
-
-__device__ __forceinline__ unsigned long long merge_shfl_u64(unsigned long long v, int src) {
-  const unsigned lo = __shfl((unsigned)(v & 0xffffffffull), src);
-  const unsigned hi = __shfl((unsigned)(v >> 32), src);
-  return ((unsigned long long)hi << 32) | lo;
-}
 
 // dynamic LDS: keys [pool_p2] u64 | boxes [pool_p2] float4 | classes [pool_p2] int | view prefix [max_views + 1] int | kept [pool_p2] u16
 __global__ __launch_bounds__(1024) void merge_views_kernel(const int* __restrict__ src_off, const int* __restrict__ src_views,
@@ -100,11 +78,7 @@ __global__ __launch_bounds__(1024) void merge_views_kernel(const int* __restrict
   // 3: boxes in source coordinates, classes, in sorted order
   for (unsigned i = t; i < n; i += 1024) {
     const unsigned g = ~(unsigned)(keys[i] & 0xffffffffull);
-    const MergeView mv = views[g / (unsigned)max_in];
-    const float4 b = *reinterpret_cast<const float4*>(boxes + (size_t)g * 4);
-    float x1 = b.x, x2 = b.z;
-    if (mv.flip) { x1 = mv.w - b.z; x2 = mv.w - b.x; }
-    s_box[i] = make_float4(x1 + mv.x0, b.y + mv.y0, x2 + mv.x0, b.w + mv.y0);
+    s_box[i] = merge_source_box(boxes, views, g, (unsigned)max_in);
     s_cls[i] = classes[g];
   }
   if (t == 0) { s_kept_total = 0; s_stop = 0; }

@@ -1,0 +1,323 @@
+// Merge of the detections of several views of one source with no LDS-sized pool limit: gfx950.  The rules and the result are those of
+// merge_views_kernel (merge_views.hip; include/sylph_hip.h above sylph_merge_views), bit for bit; the pool lives in a caller's workspace
+// and class-aware NMS runs per (source, class) segment.  The launches of one call, all on one stream, no atomics, nothing kept:
+//   1  keys: every row g = view * max_in + row of the [n_views][max_in] buffers becomes a 128-bit key
+//        hi = source << 32 | class bits,  lo = ~(ordered score bits) << 32 | g      (rows beyond a view's count and the padding: all ones)
+//   2  bitonic sort, ascending, over P = the power of two >= n_views * max_in (at least one tile): MERGE_LARGE_SORT_TILE keys per block
+//      in LDS for the strides below a tile, one compare-exchange per thread in global memory for the strides above.  The keys are
+//      unique, so the order is (source, class, score descending, view, row) whatever the network does
+//   3  NMS: the block of 64 sorted positions walks every segment that STARTS among them (most blocks find none and leave), in chunks of
+//      MERGE_LARGE_CHUNK = 64 boxes as step 4 of merge_views_kernel: ballots against the boxes kept in earlier chunks, a 64 x 64 bit
+//      matrix inside the chunk, a serial resolve in wave 0.  The first MERGE_LARGE_KEPT_LDS kept boxes of a segment stay in LDS, later
+//      ones spill to the workspace at (segment start + rank): a segment keeps at most as many boxes as it holds.  The waves take the
+//      kept boxes in groups of 64 and skip the division for a box that meets none of the chunk's.  With K > 0 a segment stops once it
+//      has kept K boxes and the scores have fallen below its K-th: rule 5 cannot emit what lies behind
+//   4  keys again: hi = source for a kept row, all ones for the others; the same sort -> per source its kept rows in rule-3 order
+//   5  the bounds of every source's run, then emit: with the rows in score order rule 5 keeps a PREFIX (rank < K or score >= the K-th),
+//      so every thread decides from its own row and its neighbour's; the thread of the last emitted row writes the count
+#include "common.h"
+#include "kernels.h"
+#include "merge_math.h"
+
+namespace sylph {
+
+namespace {
+
+constexpr unsigned long long KEY_NONE = ~0ull;
+constexpr int TILE = MERGE_LARGE_SORT_TILE, CHUNK = MERGE_LARGE_CHUNK, KEPT_LDS = MERGE_LARGE_KEPT_LDS;
+static_assert(CHUNK == 64 && KEPT_LDS % 64 == 0, "one chunk is one wave's ballot; the kept boxes are compared in groups of 64");
+static_assert(TILE == 2048, "the tile sort gives each of its 1024 threads one pair");
+
+__device__ __forceinline__ bool key_less(ulonglong2 a, ulonglong2 b) { return a.x < b.x || (a.x == b.x && a.y < b.y); }
+
+// 1: a count outside [0, max_in] is clamped, as merge_views_kernel does
+__global__ __launch_bounds__(256) void merge_large_keys_kernel(ulonglong2* __restrict__ keys, unsigned P, unsigned n_rows, int max_in,
+                                                               const MergeView* __restrict__ views, const float* __restrict__ scores,
+                                                               const int* __restrict__ classes, const int* __restrict__ counts) {
+  const unsigned g = blockIdx.x * 256u + threadIdx.x;
+  if (g >= P) return;
+  ulonglong2 key = make_ulonglong2(KEY_NONE, KEY_NONE);
+  if (g < n_rows) {
+    const unsigned v = g / (unsigned)max_in, r = g % (unsigned)max_in;
+    const int cn = counts[v];
+    const unsigned rows = cn < 0 ? 0u : (cn > max_in ? (unsigned)max_in : (unsigned)cn);
+    if (r < rows) {
+      key.x = ((unsigned long long)(unsigned)views[v].src << 32) | (unsigned long long)(unsigned)classes[g];
+      key.y = ((unsigned long long)(~merge_score_key(scores[g])) << 32) | (unsigned long long)g;
+    }
+  }
+  keys[g] = key;
+}
+
+// 2: the steps of the bitonic network whose stride is below a tile, for the sizes size_first ... size_last (powers of two; a size above
+// the tile starts at stride TILE / 2: its larger strides were merge_large_sort_step_kernel's)
+__global__ __launch_bounds__(1024) void merge_large_sort_tile_kernel(ulonglong2* __restrict__ keys, unsigned size_first, unsigned size_last) {
+  __shared__ unsigned long long s_hi[TILE], s_lo[TILE];
+  const unsigned t = threadIdx.x, base = blockIdx.x * (unsigned)TILE;
+  for (unsigned i = t; i < (unsigned)TILE; i += 1024) {
+    const ulonglong2 k = keys[base + i];
+    s_hi[i] = k.x; s_lo[i] = k.y;
+  }
+  __syncthreads();
+  for (unsigned size = size_first; size <= size_last && size != 0; size <<= 1) {
+    unsigned stride = size >> 1;
+    if (stride > (unsigned)TILE / 2) stride = TILE / 2;
+    for (; stride > 0; stride >>= 1) {
+      const unsigned lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), hi = lo + stride;
+      const bool asc = ((base + lo) & size) == 0;
+      const ulonglong2 a = make_ulonglong2(s_hi[lo], s_lo[lo]), b = make_ulonglong2(s_hi[hi], s_lo[hi]);
+      if (key_less(b, a) == asc) {
+        s_hi[lo] = b.x; s_lo[lo] = b.y;
+        s_hi[hi] = a.x; s_lo[hi] = a.y;
+      }
+      __syncthreads();
+    }
+  }
+  for (unsigned i = t; i < (unsigned)TILE; i += 1024) keys[base + i] = make_ulonglong2(s_hi[i], s_lo[i]);
+}
+
+// 2: one step of a stride of at least a tile: P / 2 threads, one pair each
+__global__ __launch_bounds__(256) void merge_large_sort_step_kernel(ulonglong2* __restrict__ keys, unsigned P, unsigned size, unsigned stride) {
+  const unsigned u = blockIdx.x * 256u + threadIdx.x;
+  if (u >= (P >> 1)) return;
+  const unsigned lo = ((u & ~(stride - 1)) << 1) | (u & (stride - 1)), hi = lo + stride;
+  const bool asc = (lo & size) == 0;
+  const ulonglong2 a = keys[lo], b = keys[hi];
+  if (key_less(b, a) == asc) { keys[lo] = b; keys[hi] = a; }
+}
+
+// 3: see the head of the file.  kept [n_rows] (cleared before): set for every sorted position whose row is kept.  K > 0: a segment
+// that has kept K boxes stops at the first chunk that begins below its K-th kept score -- the source's K-th kept score is no lower,
+// so rule 5 emits none of the rows behind (the early stop of merge_views_kernel, per segment); they stay unkept
+__global__ __launch_bounds__(1024) void merge_large_nms_kernel(const ulonglong2* __restrict__ keys, unsigned P, const MergeView* __restrict__ views,
+                                                               int max_in, const float* __restrict__ boxes, float thr, int K, float4* kbox,
+                                                               unsigned char* __restrict__ kept) {
+  __shared__ float4 s_kept[KEPT_LDS];
+  __shared__ float4 s_stage[16][64];  // per wave: the group of spilled kept boxes it is comparing against
+  __shared__ unsigned long long s_part[16];
+  __shared__ unsigned s_d[64][2];
+  __shared__ float4 s_box4[64];
+  __shared__ unsigned long long s_starts, s_valid;
+  __shared__ int s_kept_total, s_last;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const unsigned p0 = blockIdx.x * 64u;
+  if (wave == 0) {
+    const unsigned p = p0 + lane;  // (P is a multiple of 64)
+    const unsigned long long hi = keys[p].x;
+    const bool start = hi != KEY_NONE && (p == 0 || keys[p - 1].x != hi);
+    const unsigned long long m = __ballot(start);
+    if (lane == 0) s_starts = m;
+  }
+  __syncthreads();
+  unsigned long long starts = s_starts;
+  while (starts) {
+    const unsigned seg0 = p0 + (unsigned)(__ffsll((long long)starts) - 1);
+    starts &= starts - 1;
+    const unsigned long long seg_hi = keys[seg0].x;
+    int kept_total = 0;  // wave 0 keeps the running state; mirrored in LDS for the other waves
+    unsigned ord = 0u, kth_ord = 0u;  // ~(ordered score bits) of the lane's row and of the segment's K-th kept row: ascending = score descending
+    bool have_kth = false;
+    if (t == 0) s_kept_total = 0;
+    for (unsigned c = 0;; ++c) {
+      const unsigned long long pos = (unsigned long long)seg0 + 64ull * c + (unsigned)lane;
+      if (wave == 0) {
+        bool valid = false;
+        float4 bx = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (pos < P) {
+          const ulonglong2 k = keys[pos];
+          if (k.x == seg_hi) {  // (the segment is a run of the sorted keys: the valid lanes of a chunk are its first ones)
+            valid = true;
+            ord = (unsigned)(k.y >> 32);
+            const unsigned g = (unsigned)(k.y & 0xffffffffull);
+            bx = merge_source_box(boxes, views, g, (unsigned)max_in);
+          }
+        }
+        s_box4[lane] = bx;
+        s_d[lane][0] = 0u; s_d[lane][1] = 0u;
+        const unsigned long long vm = __ballot(valid);
+        if (lane == 0) s_valid = vm;
+      }
+      __syncthreads();
+      const int ktot = s_kept_total;
+      const unsigned long long vmask = s_valid;
+      const float4 mb = s_box4[lane];
+      bool sup = false;
+      // the kept boxes in groups of 64, a group per wave: a spilled group comes in with one coalesced load and is then read like the LDS
+      // list, one box for all lanes.  A box that no lane's box intersects is done after the intersection (inter = 0 never suppresses:
+      // thr > 0), so the division runs only for the few kept boxes near the chunk's
+      for (int base = wave * 64; base < ktot; base += 16 * 64) {
+        const int cnt = ktot - base < 64 ? ktot - base : 64;
+        const float4* grp = s_kept + base;  // (KEPT_LDS is a multiple of 64: a group is on one side)
+        if (base >= KEPT_LDS) {
+          if (lane < cnt) s_stage[wave][lane] = kbox[(size_t)seg0 + base + lane];
+          grp = s_stage[wave];
+        }
+        float4 next = grp[0];
+        for (int j = 0; j < cnt; ++j) {
+          const float4 kb = next;
+          if (j + 1 < cnt) next = grp[j + 1];  // (in flight under this box's test)
+          const float iw = fmaxf(0.f, fminf(kb.z, mb.z) - fmaxf(kb.x, mb.x)), ih = fmaxf(0.f, fminf(kb.w, mb.w) - fmaxf(kb.y, mb.y));
+          if (__any(iw * ih > 0.f)) {
+            const float karea = (kb.z - kb.x) * (kb.w - kb.y);
+            sup = sup || merge_overlap(kb.x, kb.y, kb.z, kb.w, karea, mb, thr);
+          }
+        }
+      }
+      {
+        const int i = t >> 4, jq = t & 15;
+        const float4 ib = s_box4[i];
+        const float iarea = (ib.z - ib.x) * (ib.w - ib.y);
+        unsigned bits = 0u;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int j = 4 * jq + e;
+          if (j > i && merge_overlap(ib.x, ib.y, ib.z, ib.w, iarea, s_box4[j], thr)) bits |= 1u << (j & 31);
+        }
+        if (bits) atomicOr(&s_d[i][jq >> 3], bits);
+      }
+      const unsigned long long part = __ballot(sup);
+      if (lane == 0) s_part[wave] = part;
+      __syncthreads();
+      if (wave == 0) {
+        unsigned long long cur = ~vmask;  // the lanes past the segment's end are never kept
+#pragma unroll
+        for (int w = 0; w < 16; ++w) cur |= s_part[w];
+        const unsigned long long d = ((unsigned long long)s_d[lane][1] << 32) | (unsigned long long)s_d[lane][0];
+        unsigned long long keptmask = 0ull;
+        for (int b = 0; b < 64; ++b) {
+          const unsigned long long db = merge_shfl_u64(d, b);
+          if (!((cur >> b) & 1ull)) {
+            keptmask |= 1ull << b;
+            cur |= db;
+          }
+        }
+        const bool is_kept = (keptmask >> lane) & 1ull;
+        const int rank = kept_total + __popcll(keptmask & ((1ull << lane) - 1ull));
+        if (is_kept) {
+          if (rank < KEPT_LDS) s_kept[rank] = mb;
+          else kbox[(size_t)seg0 + rank] = mb;
+        }
+        if (is_kept) kept[pos] = 1;
+        if (K > 0 && !have_kth && kept_total + __popcll(keptmask) >= K) {
+          const unsigned long long sel = __ballot(is_kept && rank == K - 1);
+          kth_ord = __shfl(ord, __ffsll((long long)sel) - 1);
+          have_kth = true;
+        }
+        kept_total += __popcll(keptmask);
+        bool last = vmask != ~0ull;
+        if (!last && have_kth && lane == 0) {  // does the next chunk begin below the K-th kept score?
+          const unsigned long long np = (unsigned long long)seg0 + 64ull * (c + 1);
+          if (np < P) {
+            const ulonglong2 nk = keys[np];
+            last = nk.x == seg_hi && (unsigned)(nk.y >> 32) > kth_ord;
+          }
+        }
+        if (lane == 0) { s_kept_total = kept_total; s_last = last ? 1 : 0; }
+      }
+      __syncthreads();
+      if (s_last) break;
+    }
+  }
+}
+
+// 4: the keys of the second sort.  nms_on == 0: every row is kept (thr <= 0), the NMS kernel did not run
+__global__ __launch_bounds__(256) void merge_large_rekey_kernel(ulonglong2* __restrict__ keys, unsigned P, const unsigned char* __restrict__ kept,
+                                                                int nms_on) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= P) return;
+  ulonglong2 k = keys[i];
+  if (k.x == KEY_NONE) return;
+  if (!nms_on || kept[i]) k.x >>= 32;
+  else k = make_ulonglong2(KEY_NONE, KEY_NONE);
+  keys[i] = k;
+}
+
+// 5: bounds [n_src][2] (cleared before: a source without a kept row keeps 0, 0): the run of every source in the sorted keys
+__global__ __launch_bounds__(256) void merge_large_bounds_kernel(const ulonglong2* __restrict__ keys, unsigned P, unsigned* __restrict__ bounds) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= P) return;
+  const unsigned long long hi = keys[i].x;
+  if (hi == KEY_NONE) return;
+  if (i == 0 || keys[i - 1].x != hi) bounds[2 * hi] = i;
+  if (i + 1 == P || keys[i + 1].x != hi) bounds[2 * hi + 1] = i + 1;
+}
+
+// 5: thread j of source blockIdx.x / blocks_per_src looks at the source's j-th kept row, j <= max_out (row max_out only tells that the source is truncated)
+__global__ __launch_bounds__(256) void merge_large_emit_kernel(const ulonglong2* __restrict__ keys, const unsigned* __restrict__ bounds,
+                                                               const MergeView* __restrict__ views, int max_in, const float* __restrict__ boxes,
+                                                               const float* __restrict__ scores, const int* __restrict__ classes, int K,
+                                                               int max_out, int blocks_per_src, float* out_boxes, float* out_scores, int* out_classes, int* out_view,
+                                                               int* out_row, int* out_counts, int* status) {
+  const int src = blockIdx.x / blocks_per_src;
+  const unsigned j = (blockIdx.x % blocks_per_src) * 256u + threadIdx.x;
+  const unsigned beg = bounds[2 * src], n = bounds[2 * src + 1] - beg;
+  if (n == 0) {
+    if (j == 0) out_counts[src] = 0;
+    return;
+  }
+  if (j >= n || j > (unsigned)max_out) return;
+  const unsigned g = (unsigned)(keys[beg + j].y & 0xffffffffull);
+  const float score = scores[g];
+  const bool cut = K > 0 && n > (unsigned)K;
+  const float kth = cut ? scores[(unsigned)(keys[beg + K - 1].y & 0xffffffffull)] : 0.f;
+  if (cut && j >= (unsigned)K && !(score >= kth)) return;
+  bool next = j + 1 < n;  // is the row behind this one emitted too?
+  if (next && cut && j + 1 >= (unsigned)K) next = scores[(unsigned)(keys[beg + j + 1].y & 0xffffffffull)] >= kth;
+  if (j == (unsigned)max_out) {  // (every truncated source stores the same word: no atomic)
+    *status = 2;
+    out_counts[src] = max_out;
+    return;
+  }
+  const float4 b = merge_source_box(boxes, views, g, (unsigned)max_in);
+  const size_t o = (size_t)src * max_out + j;
+  out_boxes[o * 4 + 0] = b.x; out_boxes[o * 4 + 1] = b.y; out_boxes[o * 4 + 2] = b.z; out_boxes[o * 4 + 3] = b.w;
+  out_scores[o] = score;
+  out_classes[o] = classes[g];
+  out_view[o] = (int)(g / (unsigned)max_in);
+  out_row[o] = (int)(g % (unsigned)max_in);
+  if (!next) out_counts[src] = (int)j + 1;
+}
+
+void sort_keys(ulonglong2* keys, unsigned P, hipStream_t s) {
+  const unsigned tiles = P / TILE, steps = (P / 2 + 255) / 256;
+  hipLaunchKernelGGL(merge_large_sort_tile_kernel, dim3(tiles), dim3(1024), 0, s, keys, 2u, (unsigned)TILE);
+  for (unsigned long long size = 2ull * TILE; size <= P; size <<= 1) {
+    for (unsigned stride = (unsigned)(size >> 1); stride >= (unsigned)TILE; stride >>= 1)
+      hipLaunchKernelGGL(merge_large_sort_step_kernel, dim3(steps), dim3(256), 0, s, keys, P, (unsigned)size, stride);
+    hipLaunchKernelGGL(merge_large_sort_tile_kernel, dim3(tiles), dim3(1024), 0, s, keys, (unsigned)size, (unsigned)size);
+  }
+}
+
+}  // namespace
+
+int launch_merge_views_large(int n_src, int n_views, const MergeView* views, int max_in, const float* boxes, const float* scores,
+                             const int* classes, const int* counts, float nms_thresh, int K, int max_out, float* out_boxes, float* out_scores,
+                             int* out_classes, int* out_view, int* out_row, int* out_counts, int* status, void* workspace, hipStream_t s) {
+  const MergeLargeLayout L = merge_large_layout(n_src, n_views, max_in);
+  if (L.bytes < 0 || max_out <= 0 || !workspace) return (int)hipErrorInvalidValue;
+  char* ws = static_cast<char*>(workspace);
+  ulonglong2* keys = reinterpret_cast<ulonglong2*>(ws + L.keys_off);
+  float4* kbox = reinterpret_cast<float4*>(ws + L.kbox_off);
+  unsigned char* kept = reinterpret_cast<unsigned char*>(ws + L.kept_off);
+  unsigned* bounds = reinterpret_cast<unsigned*>(ws + L.bounds_off);
+  const unsigned P = (unsigned)L.P, n_rows = (unsigned)L.rows, flat = (P + 255) / 256;
+  const int nms_on = nms_thresh > 0.f ? 1 : 0;
+  if (hipMemsetAsync(status, 0, sizeof(int), s) != hipSuccess) return -8;
+  if (hipMemsetAsync(bounds, 0, (size_t)2 * n_src * sizeof(unsigned), s) != hipSuccess) return -8;
+  hipLaunchKernelGGL(merge_large_keys_kernel, dim3(flat), dim3(256), 0, s, keys, P, n_rows, max_in, views, scores, classes, counts);
+  if (nms_on) {
+    sort_keys(keys, P, s);
+    if (hipMemsetAsync(kept, 0, (size_t)n_rows, s) != hipSuccess) return -8;
+    hipLaunchKernelGGL(merge_large_nms_kernel, dim3(P / 64), dim3(1024), 0, s, keys, P, views, max_in, boxes, nms_thresh, K, kbox, kept);
+  }
+  hipLaunchKernelGGL(merge_large_rekey_kernel, dim3(flat), dim3(256), 0, s, keys, P, kept, nms_on);
+  sort_keys(keys, P, s);
+  hipLaunchKernelGGL(merge_large_bounds_kernel, dim3(flat), dim3(256), 0, s, keys, P, bounds);
+  const int bps = max_out / 256 + 1;  // max_out + 1 threads per source
+  if ((long long)bps * n_src > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(merge_large_emit_kernel, dim3((unsigned)bps * n_src), dim3(256), 0, s, keys, bounds, views, max_in, boxes, scores,
+                     classes, K, max_out, bps, out_boxes, out_scores, out_classes, out_view, out_row, out_counts, status);
+  return (int)hipGetLastError();
+}
+
+}  // namespace sylph

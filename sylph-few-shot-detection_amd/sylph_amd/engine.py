@@ -329,6 +329,7 @@ class Engine:
         self._lib_writes = 0  # in-place writes into caller tensors through raw pointers (part of the class-code cache key)
         self._records = []  # live QueryRecords of this engine
         self._record = None  # the one that is the current batch (load_record), None on a fresh batch
+        self._merge_ws = None  # merge_views_large's workspace: grows on demand, contents are scratch
 
     def close(self):
         if self._ctx:
@@ -837,6 +838,16 @@ class Engine:
         view v, whose detections are rows["boxes" | "scores" | "classes"][v, :rows["counts"][v]] ([n_views][max_in]; classes int32), in
         crop pixels.  -> per source a dict of pred_boxes (source pixels), scores, pred_classes, view_index, view_row (the input row of
         each output).  One device->host copy: the merged counts with the status words of the merge and of every decode_rows step."""
+        return self._merge_views(view_table, rows, max_out, n_src, None, large=False)
+
+    def merge_views_large(self, view_table: List[Dict], rows: Dict, max_out: Optional[int] = None, n_src: Optional[int] = None,
+                          topk: Optional[int] = None):
+        """`merge_views` for sources of any size (sylph_merge_views_large: up to MERGE_LARGE_POOL_CAP rows per source, the pool in a
+        workspace this engine owns and grows on demand): the same result, the same read-back, the same errors.  topk is rule 5's K for
+        this call: a count, 0 = every kept box, None = POST_NMS_TOPK_TEST."""
+        return self._merge_views(view_table, rows, max_out, n_src, -1 if topk is None else int(topk), large=True)
+
+    def _merge_views(self, view_table, rows, max_out, n_src, topk, large: bool):
         self._stream()
         nv = len(view_table)
         boxes, scores, classes, counts = rows["boxes"], rows["scores"], rows["classes"], rows["counts"]
@@ -857,11 +868,19 @@ class Engine:
         oi = torch.empty(3, n_src, max_out, device=dev, dtype=torch.int32)  # classes | view | row
         steps = int(rows.get("steps", 0))
         tail = torch.empty(n_src + 1 + steps, device=dev, dtype=torch.int32)  # merged counts | merge status | decode status words
-        check(self.L.sylph_merge_views(self._ctx, n_src, nv, _iarr(src), farr([v["crop"][0] for v in view_table]),
-                                       farr([v["crop"][1] for v in view_table]), farr([v["crop"][2] for v in view_table]),
-                                       _iarr([1 if v.get("flip", False) else 0 for v in view_table]), max_in, _ptr(boxes), _ptr(scores),
-                                       _ptr(classes), _ptr(counts), max_out, _ptr(ob), _ptr(osc), _ptr(oi[0]), _ptr(oi[1]), _ptr(oi[2]),
-                                       _ptr(tail), c_void_p(tail.data_ptr() + 4 * n_src)), "merge_views")
+        tables = (n_src, nv, _iarr(src), farr([v["crop"][0] for v in view_table]), farr([v["crop"][1] for v in view_table]),
+                  farr([v["crop"][2] for v in view_table]), _iarr([1 if v.get("flip", False) else 0 for v in view_table]), max_in,
+                  _ptr(boxes), _ptr(scores), _ptr(classes), _ptr(counts))
+        outs = (max_out, _ptr(ob), _ptr(osc), _ptr(oi[0]), _ptr(oi[1]), _ptr(oi[2]), _ptr(tail), c_void_p(tail.data_ptr() + 4 * n_src))
+        if large:
+            need = int(self.L.sylph_merge_views_large_bytes(n_src, nv, max_in))
+            ws = self._merge_ws
+            if need > 0 and (ws is None or ws.numel() < need):  # (a refused size: the entry names the reason)
+                ws = self._merge_ws = torch.empty(need, device=dev, dtype=torch.uint8)
+            check(self.L.sylph_merge_views_large(self._ctx, *tables, topk, *outs, _ptr(ws) if ws is not None else None,
+                                                 ws.numel() if ws is not None else 0), "merge_views_large")
+        else:
+            check(self.L.sylph_merge_views(self._ctx, *tables, *outs), "merge_views")
         if steps:
             tail[n_src + 1:].copy_(rows["meta"][nv:nv + steps])
         cnt = tail.tolist()  # the only sync

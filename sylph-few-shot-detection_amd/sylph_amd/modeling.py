@@ -19,7 +19,7 @@ from torch import nn
 
 from .engine import Engine, QueryRecord
 from .structures import Boxes, Instances
-from .views import DEFAULT_MAX_BATCH, check_views, make_view, plan_view_steps, tta_views, view_out_size
+from .views import DEFAULT_MAX_BATCH, check_views, make_view, merge_route, plan_view_steps, tta_views, view_out_size
 
 logger = logging.getLogger(__name__)
 
@@ -348,6 +348,10 @@ class MetaOneStageDetector(nn.Module):
             if run_type == "meta_learn_cache_query":
                 return self.forward_cache_query(batched_inputs)
         views = self._input_views(batched_inputs) if run_type == "meta_learn_test_instance" and rec is None else None
+        if views is None and run_type == "meta_learn_test_instance" and rec is None and \
+                any(isinstance(x, dict) and x.get("max_detections") is not None for x in batched_inputs):
+            raise ValueError("\"max_detections\" is the keep count of the merge of an input's views: it needs \"views\" on the inputs or "
+                             "TEST.AUG.ENABLED (without views POST_NMS_TOPK_TEST decides)")
         if views is not None:
             if sets is not None:
                 raise NotImplementedError("class_code_sets together with query views (inputs carrying \"views\", or TEST.AUG.ENABLED) is not "
@@ -600,13 +604,15 @@ class MetaOneStageDetector(nn.Module):
     def forward_instances_views(self, batched_inputs: List[Dict[str, Any]], class_codes, per_input_views):
         """Every input on its views, merged per input: the views of the whole batch are planned into steps by resize target
         (plan_view_steps); a step is preprocess_views (cut from the sources, which are uploaded once) -> backbone -> head -> decode at
-        the crop size into its slice of one row buffer; then ONE merge launch (class-wise NMS over the views of a source, in source
-        pixels) and one read-back.  class_codes: a dict (every view), a per-input list (all views of an input take its episode) or
-        None (the pretrained classifier).  -> [{"instances": Instances}] at the source's size, or at "height" / "width" when they differ
+        the crop size into its slice of one row buffer; then ONE merge call (class-wise NMS over the views of a source, in source
+        pixels; views.merge_route picks the one-block merge or, for a source of more than 4 096 rows or a "max_detections" = K on the
+        inputs, the workspace merge with K as rule 5's count and 2 K output rows) and one read-back.  class_codes: a dict (every
+        view), a per-input list (all views of an input take its episode) or None (the pretrained classifier).  -> [{"instances": Instances}] at the source's size, or at "height" / "width" when they differ
         (rescaled and clipped as detector_postprocess does) with pred_boxes, scores, pred_classes and the provenance view_index (into the
         input's own view list) / view_row."""
         assert not self.training, "Not for training"
         eng = self.engine
+        topk = self._max_detections(batched_inputs)
         run_head = self._view_head(class_codes, len(batched_inputs))
         table = [dict(v, source=i, view=k) for i, vs in enumerate(per_input_views) for k, v in enumerate(vs)]
         steps = plan_view_steps(table, int(self.view_max_batch), int(getattr(self.backbone, "size_divisibility", 32)))
@@ -624,7 +630,12 @@ class MetaOneStageDetector(nn.Module):
             row0 += len(st)
         results = []
         own_index = torch.tensor([v["view"] for v in table], device=self.device)  # row of the buffer -> index in the input's own view list
-        for x, src, d in zip(batched_inputs, sources, eng.merge_views(table, rows, n_src=len(batched_inputs))):
+        per_source = [len(vs) for vs in per_input_views]
+        if merge_route(per_source, rows["max_in"], topk) == "block":
+            merged = eng.merge_views(table, rows, n_src=len(batched_inputs))
+        else:  # a K of the inputs' own replaces the config's for the merged result only: every view was decoded under the config
+            merged = eng.merge_views_large(table, rows, max_out=None if topk is None else 2 * topk, n_src=len(batched_inputs), topk=topk)
+        for x, src, d in zip(batched_inputs, sources, merged):
             h, w = int(src.shape[0]), int(src.shape[1])
             H, W = int(x.get("height", h)), int(x.get("width", w))
             boxes, scores, classes = d["pred_boxes"], d["scores"], d["pred_classes"]
@@ -642,6 +653,17 @@ class MetaOneStageDetector(nn.Module):
             r.view_row = view_row
             results.append({"instances": r})
         return results
+
+    @staticmethod
+    def _max_detections(batched_inputs: List[Dict[str, Any]]) -> Optional[int]:
+        """The "max_detections" of a batch with views: rule 5's K of the merge, None when no input carries one.  One merge call has one K."""
+        ks = {int(x["max_detections"]) if x.get("max_detections") is not None else None for x in batched_inputs}
+        if len(ks) > 1:
+            raise ValueError(f"the inputs of one batch disagree on \"max_detections\": {sorted(ks, key=lambda k: (k is not None, k))}")
+        k = ks.pop()
+        if k is not None and k <= 0:
+            raise ValueError(f"\"max_detections\" must be a positive count, got {k}")
+        return k
 
     def _view_head(self, class_codes, num_inputs: int):
         """-> run(view_sources): the head on the current batch of views, view b belonging to input view_sources[b]"""

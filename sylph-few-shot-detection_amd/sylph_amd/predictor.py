@@ -36,11 +36,13 @@ class SylphPredictor:
     def __init__(self, config_file: str, weight_path: str, class_code_path: str,
                  runner_name: str = "sylph.runner.MetaFCOSRunner", test_dataset_names: Dict = None,
                  dtype: Optional[str] = None, fused_preprocess: bool = True, tiles: Optional[Tuple[int, int]] = None,
-                 tile_overlap: float = 0.2):
+                 tile_overlap: float = 0.2, max_detections: Optional[int] = None):
         """tiles = (tile_h, tile_w): large images are run as a grid of overlapping crops of that size plus the full frame, each resized
         by the MIN_SIZE_TEST / MAX_SIZE_TEST rule, and the detections are merged on the device in the coordinates of the image
         (sylph_amd.views.tile_views).  cfg.TEST.AUG.ENABLED gives multi-scale / flip test-time augmentation the same way.  Both need
-        the fused uint8 input path."""
+        the fused uint8 input path.  max_detections = K (with tiles or cfg.TEST.AUG.ENABLED, i.e. wherever views are merged): the merged
+        result of an image keeps its K best boxes (and the ties of the K-th) instead of POST_NMS_TOPK_TEST, which stays the bound of
+        every single view.  Without views there is no merge and the argument is refused."""
         logger.info("SylphPredictor initializing...")
         runner = create_runner(runner_name)
         self.cfg = create_cfg(runner.get_default_cfg(), config_file, None).clone()
@@ -67,6 +69,10 @@ class SylphPredictor:
         self.fused_preprocess = fused_preprocess
         self.tiles = (int(tiles[0]), int(tiles[1])) if tiles is not None else None
         self.tile_overlap = float(tile_overlap)
+        self.max_detections = int(max_detections) if max_detections is not None else None
+        aug = self.cfg.get("TEST", {}).get("AUG", {})
+        if self.max_detections is not None and (self.max_detections <= 0 or (self.tiles is None and not bool(aug.get("ENABLED", False)))):
+            raise ValueError("max_detections is a positive count for the merged result of an image's views: it needs tiles or TEST.AUG.ENABLED")
         if self.tiles is not None and not fused_preprocess:
             raise ValueError("tiles needs fused_preprocess=True: the tiles are cut from the uint8 original on the device")
         self._pinned = {}  # (h, w) -> pinned uint8 staging buffer for the asynchronous H2D copy
@@ -112,6 +118,8 @@ class SylphPredictor:
             inputs = {"image_u8": buf, "resize_hw": (nh, nw), "input_format": self.input_format, "height": height, "width": width}
             if self.tiles is not None:
                 inputs["views"] = tile_views(height, width, self.tiles, self.tile_overlap, self.min_size, self.max_size)
+            if self.max_detections is not None:  # (tiles, or the model's TEST.AUG views)
+                inputs["max_detections"] = self.max_detections
             return inputs
         if self.tiles is not None:
             raise ValueError(f"tiles needs a uint8 image, got {original_image.dtype}")

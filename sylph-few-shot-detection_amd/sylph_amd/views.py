@@ -3,12 +3,14 @@
 A view is a dict {"crop": (x0, y0, cw, ch), "size": (new_h, new_w), "flip": bool} of one source image: the crop, resized to `size`
 (PIL BILINEAR), mirrored afterwards when `flip`.  Engine.preprocess_views cuts the views of a step out of sources resident on the
 device (a "source" key names the source of each view there), the per-view decode runs with the crop size as output size, and
-Engine.merge_views pools the views of a source under one class-wise NMS, in the coordinates of the source.  Nothing here touches
-the GPU."""
+Engine.merge_views (Engine.merge_views_large for a source of more than MERGE_POOL_CAP rows: merge_route) pools the views of a source
+under one class-wise NMS, in the coordinates of the source.  Nothing here touches the GPU."""
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 DEFAULT_MAX_BATCH = 192  # views per step: the batch the benchmark runs at
+# rows of one source (max_in x its views) that Engine.merge_views pools on chip (csrc/kernels.h); Engine.merge_views_large goes beyond
+MERGE_POOL_CAP = 4096
 
 
 def resize_shortest_edge_shape(h: int, w: int, size: int, max_size: int) -> Tuple[int, int]:
@@ -110,3 +112,12 @@ def plan_view_steps(views: Sequence[Dict], max_batch: int = DEFAULT_MAX_BATCH, d
 def view_out_size(view: Dict) -> Tuple[int, int]:
     """(height, width) the per-view decode scales its boxes to: the crop's own pixels."""
     return int(view["crop"][3]), int(view["crop"][2])
+
+
+def merge_route(views_per_source: Sequence[int], max_in: int, topk: Optional[int]) -> str:
+    """Which merge a view table takes: "block" -- Engine.merge_views, one block per source with its pool on chip -- when every source's
+    views hold at most MERGE_POOL_CAP rows together (views x max_in) and rule 5's K is the config's (topk None); "large" --
+    Engine.merge_views_large -- otherwise."""
+    if topk is None and all(int(n) * int(max_in) <= MERGE_POOL_CAP for n in views_per_source):
+        return "block"
+    return "large"
