@@ -266,7 +266,8 @@ void sylph_record_destroy(sylph_ctx* ctx, sylph_record* rec);
  * out_counts_dev[n_src]; status_dev[1]: bit1 (value 2) = a source was truncated at max_out.  A source whose views could hold more than
  * MERGE_POOL_CAP = 4096 rows together (max_in x its views) fails by name before any launch.  Needs no current batch; nothing is kept
  * between calls.  The rows are taken as decode left them, clipped to the crop: rows that a crop border cut can overlap more than they did
- * under the view's own NMS. */
+ * under the view's own NMS, and the fragments of one object that several tiles cut share too little to suppress each other:
+ * sylph_stitch_views (below) joins them. */
 int sylph_merge_views(sylph_ctx* ctx, int n_src, int n_views, const int* view_src, const float* view_x0, const float* view_y0,
                       const float* view_w, const int* view_flip, int max_in, const float* boxes_dev, const float* scores_dev,
                       const int* classes_dev, const int* counts_dev, int max_out, float* out_boxes_dev, float* out_scores_dev,
@@ -288,6 +289,40 @@ int sylph_merge_views_large(sylph_ctx* ctx, int n_src, int n_views, const int* v
                             const int* classes_dev, const int* counts_dev, int topk, int max_out, float* out_boxes_dev,
                             float* out_scores_dev, int* out_classes_dev, int* out_view_dev, int* out_row_dev, int* out_counts_dev,
                             int* status_dev, void* workspace_dev, int64_t workspace_bytes);
+
+/* The merge that stitches what tile borders cut: an object that a crop border cuts comes back as a clipped fragment from every tile that
+ * sees part of it, and rule 4 keeps them all.  Inputs and outputs are those of sylph_merge_views_large plus the host arrays view_h
+ * [n_views] (crop heights), src_w / src_h [n_src] (source sizes), stitch_thr in (0, 1], border_px >= 0 and one more output,
+ * out_stitched_dev [n_src][max_out] int32.  Rules 1, 2, 3 and 5 are those written above sylph_merge_views; plain fp32 in the order written:
+ *   0  the cut flag of a row, after rule 1, box (x1, y1, x2, y2) in source pixels, crop L = x0, T = y0, R = x0 + w, B = y0 + h: cut iff
+ *      (L > 0 and x1 <= L + border_px) or (R < src_w and x2 >= R - border_px) or (T > 0 and y1 <= T + border_px) or
+ *      (B < src_h and y2 >= B - border_px).  A crop border that is the source's own never cuts: a full-frame view has no cut row
+ *   M  the pair test, equal classes, i before j in rule-3 order, inter as in rule 4, areas (x2 - x1) * (y2 - y1): if i or j is cut,
+ *      inter / fminf(area_i, area_j) > stitch_thr (intersection over the smaller box; 0 / 0 is NaN: false); otherwise rule 4's test
+ *      with NMS_TH, and NMS_TH <= 0 means that such pairs never match
+ *   4a walk the rows in rule-3 order: row j is kept unless an earlier kept row matches it; its keeper is the FIRST kept row i, in keep
+ *      order, with M(i, j); matching always uses the keeper's ORIGINAL box.  Every kept row i carries a union box U_i, at first its own
+ *      box; a cut pair grows it, U_i <- the component-wise hull (fminf / fmaxf) of U_i and box j, and adds 1 to stitched_i; an uncut
+ *      pair only suppresses
+ *   4b drop only, nothing grows: walk the kept rows in order; a kept row k that is cut is dropped if an earlier surviving row i of its
+ *      class has inter(U_i, box_k) / area(box_k) > stitch_thr, U_i as 4a left it; the first such i gets stitched_i += 1; what k had
+ *      absorbed itself is not passed on
+ *   5  on the survivors with their own scores.  An output row carries U as its box, the survivor's score, class, view and row, and
+ *      out_stitched = 1 + its count
+ * With no cut row in the pool every output equals sylph_merge_views_large's bit for bit and out_stitched is 1 everywhere.  The hull does
+ * not depend on an order, so the bits are reproducible.  Fragments match on their original boxes: two fragments that no row bridges
+ * are joined only while the object is narrower than about 3 x the overlap strip (at stitch_thr 0.5); larger objects rely on a full-frame
+ * view.  workspace_dev: at least sylph_stitch_views_bytes(n_src, n_views, max_in) bytes, never fewer than the large merge's (about 77
+ * bytes per row); -1 as sylph_merge_views_large_bytes.  Refused by name before any launch: stitch_thr outside (0, 1] or NaN, border_px
+ * < 0 or NaN, a non-positive source or crop size, a crop that leaves its source, a NULL or short workspace, and what
+ * sylph_merge_views_large refuses.  Stream, waits, status_dev, topk, class ids and counts: as sylph_merge_views_large. */
+int64_t sylph_stitch_views_bytes(int n_src, int n_views, int max_in);
+int sylph_stitch_views(sylph_ctx* ctx, int n_src, int n_views, const int* view_src, const float* view_x0, const float* view_y0,
+                       const float* view_w, const float* view_h, const int* view_flip, const float* src_w, const float* src_h, int max_in,
+                       const float* boxes_dev, const float* scores_dev, const int* classes_dev, const int* counts_dev, float stitch_thr,
+                       float border_px, int topk, int max_out, float* out_boxes_dev, float* out_scores_dev, int* out_classes_dev,
+                       int* out_view_dev, int* out_row_dev, int* out_stitched_dev, int* out_counts_dev, int* status_dev,
+                       void* workspace_dev, int64_t workspace_bytes);
 
 /* COCO bbox evaluation on detection rows, device side: what evaluator.evaluate() (sylph/evaluation/meta_learn_evaluation.py:465) hands to
  * pycocotools -- pycocotools/cocoeval.py evaluateImg (sylph_coco_match) and accumulate (sylph_coco_accumulate), useCats = 1 -- in float64, in the

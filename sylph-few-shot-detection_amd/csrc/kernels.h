@@ -127,6 +127,35 @@ inline MergeLargeLayout merge_large_layout(int n_src, int n_views, int max_in) {
 int launch_merge_views_large(int n_src, int n_views, const MergeView* views, int max_in, const float* boxes, const float* scores,
                              const int* classes, const int* counts, float nms_thresh, int K, int max_out, float* out_boxes, float* out_scores,
                              int* out_classes, int* out_view, int* out_row, int* out_counts, int* status, void* workspace, hipStream_t s);
+// merge_views_large.hip: the merge that stitches what tile borders cut (sylph_stitch_views): the keys and sorts of the large merge, a
+// segment walk that absorbs cut fragments into their keeper's union box (rule 4a), a second walk over the kept rows (rule 4b).
+// StitchView: what rule 0 needs beyond MergeView -- the crop's height and the source's size
+struct StitchView { float h, src_w, src_h; };
+// stitch_layout(...) is THE workspace layout of sylph_stitch_views, refused like merge_large_layout.  Never below the large merge's
+struct StitchLayout { long long bytes, rows, P, keys_off, kbox_off, ubox_off, meta_off, row_off, outu_off, outc_off, bounds_off; };
+inline StitchLayout stitch_layout(int n_src, int n_views, int max_in) {
+  StitchLayout L = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const MergeLargeLayout M = merge_large_layout(n_src, n_views, max_in);
+  if (M.bytes < 0) return L;
+  L.rows = M.rows;
+  L.P = M.P;
+  const auto up16 = [](long long v) { return (v + 15) / 16 * 16; };
+  L.keys_off = 0;                                  // P 128-bit keys
+  L.kbox_off = L.keys_off + 16 * L.P;              // rows float4: the kept boxes a segment spills
+  L.ubox_off = L.kbox_off + 16 * L.rows;           // rows float4: their union boxes
+  L.meta_off = L.ubox_off + 16 * L.rows;           // rows words: their cut bit, dropped bit and count
+  L.row_off = L.meta_off + up16(4 * L.rows);       // rows words: the input row of each
+  L.outu_off = L.row_off + up16(4 * L.rows);       // rows float4: per INPUT row, the union box of a survivor
+  L.outc_off = L.outu_off + 16 * L.rows;           // rows ints: per input row, 0 or 1 + what the survivor absorbed
+  L.bounds_off = L.outc_off + up16(4 * L.rows);    // n_src x (begin, end) of every source's run of survivors
+  L.bytes = L.bounds_off + up16(8LL * n_src);
+  return L;
+}
+// status as launch_merge_views_large; sviews [n_views]; stitch_thr in (0, 1], border_px >= 0 (the host has checked)
+int launch_stitch_views(int n_src, int n_views, const MergeView* views, const StitchView* sviews, int max_in, const float* boxes,
+                        const float* scores, const int* classes, const int* counts, float nms_thresh, float stitch_thr, float border_px, int K,
+                        int max_out, float* out_boxes, float* out_scores, int* out_classes, int* out_view, int* out_row, int* out_stitched,
+                        int* out_counts, int* status, void* workspace, hipStream_t s);
 // coco_eval.hip: COCO bbox matching and accumulation (include/sylph_hip.h: sylph_coco_match / sylph_coco_accumulate)
 // ground-truth boxes of one (image, category) pair whose D x G float64 IoU tile (D <= max_det) is kept in LDS; a pair with more recomputes
 // every IoU where the walk visits it and keeps its matched flags in the caller's scratch.  The bound holds up to max_det = 131; a larger

@@ -1,5 +1,6 @@
-// The arithmetic both view merges share (merge_views.hip, merge_views_large.hip): the order key of a score, rule 1's way back to source
-// coordinates and the overlap test of rule 4 (include/sylph_hip.h, sylph_merge_views).  Both files are built without FMA contraction.
+// The arithmetic the view merges share (merge_views.hip, merge_views_large.hip): the order key of a score, rule 1's way back to source
+// coordinates, the overlap test of rule 4 (include/sylph_hip.h, sylph_merge_views) and the tests of the stitching merge
+// (sylph_stitch_views).  Both files are built without FMA contraction.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -31,6 +32,32 @@ __device__ __forceinline__ bool merge_overlap(float x1, float y1, float x2, floa
   const float inter = w * h;
   const float jarea = (b.z - b.x) * (b.w - b.y);
   return inter / (iarea + jarea - inter) > thr;
+}
+
+// The stitching merge (include/sylph_hip.h, sylph_stitch_views).  Rule 0: does a border of its crop that lies inside the source cut the
+// box (source coordinates)?  The crop's sides are x0, y0, x0 + w, y0 + h in fp32
+__device__ __forceinline__ bool stitch_cut(float4 b, MergeView mv, StitchView sv, float border) {
+  const float L = mv.x0, T = mv.y0, R = mv.x0 + mv.w, B = mv.y0 + sv.h;
+  return (L > 0.f && b.x <= L + border) || (R < sv.src_w && b.z >= R - border) || (T > 0.f && b.y <= T + border) ||
+         (B < sv.src_h && b.w >= B - border);
+}
+
+// rule 4a's pair test M(i, j) for two boxes of one class: a pair with a cut box matches on intersection over the smaller box (0 / 0 is
+// NaN: no match), any other pair on merge_overlap, which nms_thr <= 0 switches off
+__device__ __forceinline__ bool stitch_match(float4 a, float4 b, bool cut_pair, float nms_thr, float stitch_thr) {
+  const float aarea = (a.z - a.x) * (a.w - a.y);
+  if (!cut_pair) return nms_thr > 0.f && merge_overlap(a.x, a.y, a.z, a.w, aarea, b, nms_thr);
+  const float w = fmaxf(0.f, fminf(a.z, b.z) - fmaxf(a.x, b.x)), h = fmaxf(0.f, fminf(a.w, b.w) - fmaxf(a.y, b.y));
+  const float inter = w * h;
+  const float barea = (b.z - b.x) * (b.w - b.y);
+  return inter / fminf(aarea, barea) > stitch_thr;
+}
+
+// rule 4b's test: does the union box u hold more than stitch_thr of box b?
+__device__ __forceinline__ bool stitch_covered(float4 u, float4 b, float stitch_thr) {
+  const float w = fmaxf(0.f, fminf(u.z, b.z) - fmaxf(u.x, b.x)), h = fmaxf(0.f, fminf(u.w, b.w) - fmaxf(u.y, b.y));
+  const float inter = w * h;
+  return inter / ((b.z - b.x) * (b.w - b.y)) > stitch_thr;
 }
 
 __device__ __forceinline__ unsigned long long merge_shfl_u64(unsigned long long v, int src) {

@@ -288,7 +288,374 @@ void sort_keys(ulonglong2* keys, unsigned P, hipStream_t s) {
   }
 }
 
+// ---- the stitching merge (sylph_stitch_views): launches 1 and 2 as above, then
+//   3s  stitch_walk_kernel: per (source, class) segment, rule 4a as launch 3 walks it -- but a row remembers the LOWEST-ranked kept box
+//       that matches it (its keeper), every kept box carries a cut bit, a union box U and a count next to its own box (in LDS up to
+//       MERGE_LARGE_KEPT_LDS, spilled beyond), and there is no early stop: a row behind the K-th kept score can still grow an emitted box.
+//       Then rule 4b over the segment's kept boxes, 64 ranks a step, against the frozen U of the earlier survivors; then every survivor
+//       leaves U and 1 + its count at its INPUT row
+//   4s  stitch_rekey_kernel: a row with a count survives; the same sort; launch 5's bounds; stitch_emit_kernel: launch 5's emit with U as the box
+// The hull is a min / max, the counts are integers: no order of arrival can change a bit.
+
+constexpr unsigned META_CUT = 0x80000000u, META_DROPPED = 0x40000000u, META_COUNT = 0x3fffffffu;
+constexpr int NO_KEEPER = 0x7fffffff;
+// dynamic LDS of stitch_walk_kernel: kept boxes | their U | the waves' staged groups (boxes) | meta | input rows | staged meta
+constexpr size_t STITCH_LDS = (size_t)KEPT_LDS * (16 + 16 + 4 + 4) + (size_t)16 * 64 * (16 + 4);
+
+struct StitchKept {  // the per-kept arrays of the segment at seg0: rank < KEPT_LDS in LDS, later ranks in the workspace at seg0 + rank
+  float4 *s_box, *s_u, *g_box, *g_u;
+  unsigned *s_meta, *s_row, *g_meta, *g_row;
+  size_t seg0;
+  __device__ __forceinline__ float4& box(int r) const { return r < KEPT_LDS ? s_box[r] : g_box[seg0 + r]; }
+  __device__ __forceinline__ float4& u(int r) const { return r < KEPT_LDS ? s_u[r] : g_u[seg0 + r]; }
+  __device__ __forceinline__ unsigned& meta(int r) const { return r < KEPT_LDS ? s_meta[r] : g_meta[seg0 + r]; }
+  __device__ __forceinline__ unsigned& row(int r) const { return r < KEPT_LDS ? s_row[r] : g_row[seg0 + r]; }
+};
+
+// wave 0: every lane with `on` adds one to the count of kept box r and, with `hull`, its box b to that box's U.  Lanes that name the same
+// r are folded in the wave first (min / max, a popcount), so one lane updates r once
+__device__ __forceinline__ void stitch_absorb(const StitchKept& k, int lane, bool on, int r, bool hull, float4 b) {
+  const float inf = __builtin_inff();
+  unsigned long long pend = __ballot(on);
+  while (pend) {
+    const int lead = __ffsll((long long)pend) - 1;
+    const int r0 = __shfl(r, lead);
+    const bool mine = on && r == r0;
+    const unsigned long long m = __ballot(mine);
+    pend &= ~m;
+    if (hull) {
+      float x1 = mine ? b.x : inf, y1 = mine ? b.y : inf, x2 = mine ? b.z : -inf, y2 = mine ? b.w : -inf;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        x1 = fminf(x1, __shfl_xor(x1, o)); y1 = fminf(y1, __shfl_xor(y1, o));
+        x2 = fmaxf(x2, __shfl_xor(x2, o)); y2 = fmaxf(y2, __shfl_xor(y2, o));
+      }
+      if (lane == lead) {
+        const float4 u = k.u(r0);
+        k.u(r0) = make_float4(fminf(u.x, x1), fminf(u.y, y1), fmaxf(u.z, x2), fmaxf(u.w, y2));
+      }
+    }
+    if (lane == lead) k.meta(r0) += (unsigned)__popcll(m);
+    __threadfence_block();  // (a spilled box may be updated again, by another lane)
+  }
+}
+
+__global__ __launch_bounds__(1024) void stitch_walk_kernel(const ulonglong2* __restrict__ keys, unsigned P, const MergeView* __restrict__ views,
+                                                           const StitchView* __restrict__ sviews, int max_in, const float* __restrict__ boxes,
+                                                           float thr, float sthr, float border, float4* kbox, float4* ubox, unsigned* kmeta,
+                                                           unsigned* krow, float4* __restrict__ out_u, int* __restrict__ out_cnt) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char stitch_lds[];
+  float4* s_kept = reinterpret_cast<float4*>(stitch_lds);
+  float4* s_u = s_kept + KEPT_LDS;
+  float4* s_stage = s_u + KEPT_LDS;  // [16][64], per wave: the group of spilled kept boxes (4b: of their U) it is comparing against
+  unsigned* s_meta = reinterpret_cast<unsigned*>(s_stage + 16 * 64);
+  unsigned* s_row = s_meta + KEPT_LDS;
+  unsigned* s_stagem = s_row + KEPT_LDS;  // [16][64]
+  __shared__ int s_best[16][64];
+  __shared__ unsigned s_d[64][2];
+  __shared__ float4 s_box4[64], s_u4[64];
+  __shared__ unsigned long long s_starts, s_valid, s_cutm;
+  __shared__ int s_kept_total, s_last, s_any_cut;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const unsigned p0 = blockIdx.x * 64u;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  if (wave == 0) {
+    const unsigned p = p0 + lane;  // (P is a multiple of 64)
+    const unsigned long long hi = keys[p].x;
+    const bool start = hi != KEY_NONE && (p == 0 || keys[p - 1].x != hi);
+    const unsigned long long m = __ballot(start);
+    if (lane == 0) s_starts = m;
+  }
+  __syncthreads();
+  unsigned long long starts = s_starts;
+  while (starts) {
+    const unsigned seg0 = p0 + (unsigned)(__ffsll((long long)starts) - 1);
+    starts &= starts - 1;
+    const unsigned long long seg_hi = keys[seg0].x;
+    const StitchKept kl = {s_kept, s_u, kbox, ubox, s_meta, s_row, kmeta, krow, (size_t)seg0};
+    int kept_total = 0;  // wave 0 keeps the running state; mirrored in LDS for the other waves
+    bool any_cut = false;
+    if (t == 0) s_kept_total = 0;
+    // rule 4a
+    for (unsigned c = 0;; ++c) {
+      const unsigned long long pos = (unsigned long long)seg0 + 64ull * c + (unsigned)lane;
+      unsigned g = 0u;
+      if (wave == 0) {
+        bool valid = false, cut = false;
+        float4 bx = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (pos < P) {
+          const ulonglong2 k = keys[pos];
+          if (k.x == seg_hi) {  // (the segment is a run of the sorted keys: the valid lanes of a chunk are its first ones)
+            valid = true;
+            g = (unsigned)(k.y & 0xffffffffull);
+            bx = merge_source_box(boxes, views, g, (unsigned)max_in);
+            const unsigned v = g / (unsigned)max_in;
+            cut = stitch_cut(bx, views[v], sviews[v], border);
+          }
+        }
+        s_box4[lane] = bx;
+        s_d[lane][0] = 0u; s_d[lane][1] = 0u;
+        const unsigned long long vm = __ballot(valid), cm = __ballot(cut);
+        if (lane == 0) { s_valid = vm; s_cutm = cm; }
+      }
+      __syncthreads();
+      const int ktot = s_kept_total;
+      const unsigned long long vmask = s_valid, cutm = s_cutm;
+      const float4 mb = s_box4[lane];
+      const bool mcut = (cutm >> lane) & 1ull;
+      int best = NO_KEEPER;  // the lowest rank this wave's groups hold of a kept box that matches the lane's (ranks ascend along the loop)
+      for (int base = wave * 64; base < ktot; base += 16 * 64) {
+        const int cnt = ktot - base < 64 ? ktot - base : 64;
+        const float4* grp = s_kept + base;  // (KEPT_LDS is a multiple of 64: a group is on one side)
+        const unsigned* gm = s_meta + base;
+        if (base >= KEPT_LDS) {
+          if (lane < cnt) {
+            s_stage[wave * 64 + lane] = kbox[(size_t)seg0 + base + lane];
+            s_stagem[wave * 64 + lane] = kmeta[(size_t)seg0 + base + lane];
+          }
+          grp = s_stage + wave * 64;
+          gm = s_stagem + wave * 64;
+        }
+        for (int j = 0; j < cnt; ++j) {
+          const float4 kb = grp[j];
+          const float iw = fmaxf(0.f, fminf(kb.z, mb.z) - fmaxf(kb.x, mb.x)), ih = fmaxf(0.f, fminf(kb.w, mb.w) - fmaxf(kb.y, mb.y));
+          if (__any(iw * ih > 0.f)) {  // (no intersection matches under neither test)
+            const bool pair_cut = mcut || (gm[j] & META_CUT);
+            if (best == NO_KEEPER && stitch_match(kb, mb, pair_cut, thr, sthr)) best = base + j;
+          }
+        }
+      }
+      {
+        const int i = t >> 4, jq = t & 15;
+        const float4 ib = s_box4[i];
+        const bool icut = (cutm >> i) & 1ull;
+        unsigned bits = 0u;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int j = 4 * jq + e;
+          if (j > i && stitch_match(ib, s_box4[j], icut || ((cutm >> j) & 1ull), thr, sthr)) bits |= 1u << (j & 31);
+        }
+        if (bits) atomicOr(&s_d[i][jq >> 3], bits);
+      }
+      s_best[wave][lane] = best;
+      __syncthreads();
+      if (wave == 0) {
+        int ext = NO_KEEPER;  // the keeper among the boxes kept in earlier chunks: they all rank below this chunk's
+#pragma unroll
+        for (int w = 0; w < 16; ++w) ext = min(ext, s_best[w][lane]);
+        unsigned long long cur = ~vmask | __ballot(ext != NO_KEEPER);  // the lanes past the segment's end are never kept
+        const unsigned long long d = ((unsigned long long)s_d[lane][1] << 32) | (unsigned long long)s_d[lane][0];
+        unsigned long long keptmask = 0ull;
+        int ink = -1;  // the first box kept in this chunk that matches the lane's
+        for (int b = 0; b < 64; ++b) {
+          const unsigned long long db = merge_shfl_u64(d, b);
+          if (!((cur >> b) & 1ull)) {
+            keptmask |= 1ull << b;
+            cur |= db;
+            if (ink < 0 && ((db >> lane) & 1ull)) ink = b;
+          }
+        }
+        const bool valid = (vmask >> lane) & 1ull, is_kept = (keptmask >> lane) & 1ull;
+        const int rank = kept_total + __popcll(keptmask & below);
+        if (is_kept) {
+          kl.box(rank) = mb;
+          kl.u(rank) = mb;
+          kl.meta(rank) = mcut ? META_CUT : 0u;
+          kl.row(rank) = g;
+        }
+        __threadfence_block();
+        const bool absorbed = valid && !is_kept;
+        int keeper = 0;
+        bool kcut = false;
+        if (absorbed) {
+          if (ext != NO_KEEPER) {
+            keeper = ext;
+            kcut = kl.meta(ext) & META_CUT;
+          } else {  // (ink >= 0: an absorbed row without a keeper before the chunk has one inside)
+            keeper = kept_total + __popcll(keptmask & ((1ull << ink) - 1ull));
+            kcut = (cutm >> ink) & 1ull;
+          }
+        }
+        stitch_absorb(kl, lane, absorbed && (mcut || kcut), keeper, true, mb);  // an uncut pair only suppresses
+        any_cut = any_cut || (keptmask & cutm) != 0ull;
+        kept_total += __popcll(keptmask);
+        if (lane == 0) { s_kept_total = kept_total; s_last = vmask != ~0ull ? 1 : 0; s_any_cut = any_cut ? 1 : 0; }
+      }
+      __syncthreads();
+      if (s_last) break;
+    }
+    // rule 4b: only a cut kept box can be dropped
+    const int ktotal = s_kept_total;
+    if (s_any_cut) {
+      for (int k0 = 0; k0 < ktotal; k0 += 64) {
+        if (wave == 0) {
+          const bool valid = k0 + lane < ktotal;
+          const unsigned meta = valid ? kl.meta(k0 + lane) : 0u;
+          s_box4[lane] = valid ? kl.box(k0 + lane) : make_float4(0.f, 0.f, 0.f, 0.f);
+          s_u4[lane] = valid ? kl.u(k0 + lane) : make_float4(0.f, 0.f, 0.f, 0.f);
+          s_d[lane][0] = 0u; s_d[lane][1] = 0u;
+          const unsigned long long cm = __ballot((meta & META_CUT) != 0u);
+          if (lane == 0) s_cutm = cm;
+        }
+        __syncthreads();
+        const unsigned long long cutm = s_cutm;
+        if (cutm == 0ull) {  // (uniform) nothing to drop here, and the boxes stay what they are for the later chunks
+          __syncthreads();
+          continue;
+        }
+        const float4 mb = s_box4[lane];
+        const bool mcut = (cutm >> lane) & 1ull;
+        int best = NO_KEEPER;
+        for (int base = wave * 64; base < k0; base += 16 * 64) {  // (k0 is a multiple of 64: full groups)
+          const float4* grp = s_u + base;
+          const unsigned* gm = s_meta + base;
+          if (base >= KEPT_LDS) {
+            s_stage[wave * 64 + lane] = ubox[(size_t)seg0 + base + lane];
+            s_stagem[wave * 64 + lane] = kmeta[(size_t)seg0 + base + lane];
+            grp = s_stage + wave * 64;
+            gm = s_stagem + wave * 64;
+          }
+          for (int j = 0; j < 64; ++j) {
+            const float4 ub = grp[j];
+            const float iw = fmaxf(0.f, fminf(ub.z, mb.z) - fmaxf(ub.x, mb.x)), ih = fmaxf(0.f, fminf(ub.w, mb.w) - fmaxf(ub.y, mb.y));
+            if (__any(iw * ih > 0.f)) {
+              if (best == NO_KEEPER && mcut && !(gm[j] & META_DROPPED) && stitch_covered(ub, mb, sthr)) best = base + j;
+            }
+          }
+        }
+        {
+          const int i = t >> 4, jq = t & 15;
+          const float4 iu = s_u4[i];
+          unsigned bits = 0u;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int j = 4 * jq + e;
+            if (j > i && ((cutm >> j) & 1ull) && stitch_covered(iu, s_box4[j], sthr)) bits |= 1u << (j & 31);
+          }
+          if (bits) atomicOr(&s_d[i][jq >> 3], bits);
+        }
+        s_best[wave][lane] = best;
+        __syncthreads();
+        if (wave == 0) {
+          int ext = NO_KEEPER;
+#pragma unroll
+          for (int w = 0; w < 16; ++w) ext = min(ext, s_best[w][lane]);
+          unsigned long long cur = __ballot(ext != NO_KEEPER);  // dropped
+          const unsigned long long d = ((unsigned long long)s_d[lane][1] << 32) | (unsigned long long)s_d[lane][0];
+          int ink = -1;  // the first survivor of this chunk whose U holds the lane's box
+          for (int b = 0; b < 64; ++b) {
+            const unsigned long long db = merge_shfl_u64(d, b);
+            if (!((cur >> b) & 1ull)) {
+              cur |= db;
+              if (ink < 0 && ((db >> lane) & 1ull)) ink = b;
+            }
+          }
+          const bool dropped = (cur >> lane) & 1ull;  // (a lane past the end has no cut bit: never dropped)
+          if (dropped) kl.meta(k0 + lane) |= META_DROPPED;
+          __threadfence_block();
+          stitch_absorb(kl, lane, dropped, ext != NO_KEEPER ? ext : k0 + ink, false, mb);
+        }
+        __syncthreads();
+      }
+    }
+    for (int r = t; r < ktotal; r += 1024) {
+      const unsigned meta = kl.meta(r);
+      if (meta & META_DROPPED) continue;
+      const unsigned g = kl.row(r);
+      out_u[g] = kl.u(r);
+      out_cnt[g] = 1 + (int)(meta & META_COUNT);
+    }
+    __syncthreads();
+  }
+}
+
+// 4s: the keys of the second sort.  cnt [n_rows] per input row: 0 or 1 + what the survivor absorbed
+__global__ __launch_bounds__(256) void stitch_rekey_kernel(ulonglong2* __restrict__ keys, unsigned P, const int* __restrict__ cnt) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= P) return;
+  ulonglong2 k = keys[i];
+  if (k.x == KEY_NONE) return;
+  if (cnt[(unsigned)(k.y & 0xffffffffull)] != 0) k.x >>= 32;
+  else k = make_ulonglong2(KEY_NONE, KEY_NONE);
+  keys[i] = k;
+}
+
+// merge_large_emit_kernel over the survivors: the same prefix rule on their own scores; the box is U, out_stitched the count
+__global__ __launch_bounds__(256) void stitch_emit_kernel(const ulonglong2* __restrict__ keys, const unsigned* __restrict__ bounds, int max_in,
+                                                          const float4* __restrict__ ubox, const int* __restrict__ cnt,
+                                                          const float* __restrict__ scores, const int* __restrict__ classes, int K, int max_out,
+                                                          int blocks_per_src, float* out_boxes, float* out_scores, int* out_classes, int* out_view,
+                                                          int* out_row, int* out_stitched, int* out_counts, int* status) {
+  const int src = blockIdx.x / blocks_per_src;
+  const unsigned j = (blockIdx.x % blocks_per_src) * 256u + threadIdx.x;
+  const unsigned beg = bounds[2 * src], n = bounds[2 * src + 1] - beg;
+  if (n == 0) {
+    if (j == 0) out_counts[src] = 0;
+    return;
+  }
+  if (j >= n || j > (unsigned)max_out) return;
+  const unsigned g = (unsigned)(keys[beg + j].y & 0xffffffffull);
+  const float score = scores[g];
+  const bool cut = K > 0 && n > (unsigned)K;
+  const float kth = cut ? scores[(unsigned)(keys[beg + K - 1].y & 0xffffffffull)] : 0.f;
+  if (cut && j >= (unsigned)K && !(score >= kth)) return;
+  bool next = j + 1 < n;  // is the row behind this one emitted too?
+  if (next && cut && j + 1 >= (unsigned)K) next = scores[(unsigned)(keys[beg + j + 1].y & 0xffffffffull)] >= kth;
+  if (j == (unsigned)max_out) {  // (every truncated source stores the same word: no atomic)
+    *status = 2;
+    out_counts[src] = max_out;
+    return;
+  }
+  const float4 b = ubox[g];
+  const size_t o = (size_t)src * max_out + j;
+  out_boxes[o * 4 + 0] = b.x; out_boxes[o * 4 + 1] = b.y; out_boxes[o * 4 + 2] = b.z; out_boxes[o * 4 + 3] = b.w;
+  out_scores[o] = score;
+  out_classes[o] = classes[g];
+  out_view[o] = (int)(g / (unsigned)max_in);
+  out_row[o] = (int)(g % (unsigned)max_in);
+  out_stitched[o] = cnt[g];
+  if (!next) out_counts[src] = (int)j + 1;
+}
+
 }  // namespace
+
+int launch_stitch_views(int n_src, int n_views, const MergeView* views, const StitchView* sviews, int max_in, const float* boxes,
+                        const float* scores, const int* classes, const int* counts, float nms_thresh, float stitch_thr, float border_px, int K,
+                        int max_out, float* out_boxes, float* out_scores, int* out_classes, int* out_view, int* out_row, int* out_stitched,
+                        int* out_counts, int* status, void* workspace, hipStream_t s) {
+  const StitchLayout L = stitch_layout(n_src, n_views, max_in);
+  if (L.bytes < 0 || max_out <= 0 || !workspace) return (int)hipErrorInvalidValue;
+  static PerDeviceOnce once;
+  if (!once.run(current_device(), [] {
+        return hipFuncSetAttribute((const void*)stitch_walk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STITCH_LDS) == hipSuccess;
+      }))
+    return -7;
+  char* ws = static_cast<char*>(workspace);
+  ulonglong2* keys = reinterpret_cast<ulonglong2*>(ws + L.keys_off);
+  float4* kbox = reinterpret_cast<float4*>(ws + L.kbox_off);
+  float4* ubox = reinterpret_cast<float4*>(ws + L.ubox_off);
+  unsigned* kmeta = reinterpret_cast<unsigned*>(ws + L.meta_off);
+  unsigned* krow = reinterpret_cast<unsigned*>(ws + L.row_off);
+  float4* out_u = reinterpret_cast<float4*>(ws + L.outu_off);
+  int* out_cnt = reinterpret_cast<int*>(ws + L.outc_off);
+  unsigned* bounds = reinterpret_cast<unsigned*>(ws + L.bounds_off);
+  const unsigned P = (unsigned)L.P, n_rows = (unsigned)L.rows, flat = (P + 255) / 256;
+  if (hipMemsetAsync(status, 0, sizeof(int), s) != hipSuccess) return -8;
+  if (hipMemsetAsync(bounds, 0, (size_t)2 * n_src * sizeof(unsigned), s) != hipSuccess) return -8;
+  if (hipMemsetAsync(out_cnt, 0, (size_t)n_rows * sizeof(int), s) != hipSuccess) return -8;
+  hipLaunchKernelGGL(merge_large_keys_kernel, dim3(flat), dim3(256), 0, s, keys, P, n_rows, max_in, views, scores, classes, counts);
+  sort_keys(keys, P, s);  // (also with NMS off: a cut pair matches whatever NMS_TH is)
+  hipLaunchKernelGGL(stitch_walk_kernel, dim3(P / 64), dim3(1024), STITCH_LDS, s, keys, P, views, sviews, max_in, boxes, nms_thresh, stitch_thr,
+                     border_px, kbox, ubox, kmeta, krow, out_u, out_cnt);
+  hipLaunchKernelGGL(stitch_rekey_kernel, dim3(flat), dim3(256), 0, s, keys, P, out_cnt);
+  sort_keys(keys, P, s);
+  hipLaunchKernelGGL(merge_large_bounds_kernel, dim3(flat), dim3(256), 0, s, keys, P, bounds);
+  const int bps = max_out / 256 + 1;  // max_out + 1 threads per source
+  if ((long long)bps * n_src > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(stitch_emit_kernel, dim3((unsigned)bps * n_src), dim3(256), 0, s, keys, bounds, max_in, out_u, out_cnt, scores, classes, K,
+                     max_out, bps, out_boxes, out_scores, out_classes, out_view, out_row, out_stitched, out_counts, status);
+  return (int)hipGetLastError();
+}
 
 int launch_merge_views_large(int n_src, int n_views, const MergeView* views, int max_in, const float* boxes, const float* scores,
                              const int* classes, const int* counts, float nms_thresh, int K, int max_out, float* out_boxes, float* out_scores,

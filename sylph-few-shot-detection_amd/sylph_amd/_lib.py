@@ -84,6 +84,10 @@ PROTOTYPES = {
     "sylph_merge_views_large_bytes": (c_int64, [c_int, c_int, c_int]),
     "sylph_merge_views_large": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_int),
                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 8 + [c_int64]),
+    "sylph_stitch_views_bytes": (c_int64, [c_int, c_int, c_int]),
+    "sylph_stitch_views": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_float),
+                                   POINTER(c_int), POINTER(c_float), POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                   c_float, c_int, c_int] + [c_void_p] * 9 + [c_int64]),
     "sylph_coco_match_tile_gt": (c_int, [c_int]),
     "sylph_coco_match": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p, c_int, c_void_p, c_int] +
                          [c_void_p] * 4),

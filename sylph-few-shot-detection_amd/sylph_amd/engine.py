@@ -847,7 +847,17 @@ class Engine:
         this call: a count, 0 = every kept box, None = POST_NMS_TOPK_TEST."""
         return self._merge_views(view_table, rows, max_out, n_src, -1 if topk is None else int(topk), large=True)
 
-    def _merge_views(self, view_table, rows, max_out, n_src, topk, large: bool):
+    def stitch_views(self, view_table: List[Dict], rows: Dict, source_sizes: Sequence[Tuple[int, int]], stitch_thr: float = 0.5,
+                     border_px: float = 2.0, max_out: Optional[int] = None, n_src: Optional[int] = None, topk: Optional[int] = None):
+        """`merge_views_large` that also stitches what tile borders cut (sylph_stitch_views; the rules stand in include/sylph_hip.h): a row
+        within border_px of a crop border that lies inside its source is cut; a cut row joins the first kept box of its class that shares
+        more than stitch_thr of the smaller of the two, whose box grows to their hull.  source_sizes[s] = (height, width) of source s.
+        -> merge_views_large's dicts plus "stitched": the rows each output stands for, itself included.  The workspace is the
+        engine's own, as for the large merge."""
+        return self._merge_views(view_table, rows, max_out, n_src, -1 if topk is None else int(topk), large=True,
+                                 stitch=(list(source_sizes), float(stitch_thr), float(border_px)))
+
+    def _merge_views(self, view_table, rows, max_out, n_src, topk, large: bool, stitch=None):
         self._stream()
         nv = len(view_table)
         boxes, scores, classes, counts = rows["boxes"], rows["scores"], rows["classes"], rows["counts"]
@@ -872,7 +882,20 @@ class Engine:
                   farr([v["crop"][2] for v in view_table]), _iarr([1 if v.get("flip", False) else 0 for v in view_table]), max_in,
                   _ptr(boxes), _ptr(scores), _ptr(classes), _ptr(counts))
         outs = (max_out, _ptr(ob), _ptr(osc), _ptr(oi[0]), _ptr(oi[1]), _ptr(oi[2]), _ptr(tail), c_void_p(tail.data_ptr() + 4 * n_src))
-        if large:
+        if stitch is not None:
+            sizes, sthr, border = stitch
+            if len(sizes) != n_src:
+                raise ValueError(f"stitch_views: {len(sizes)} source sizes for {n_src} sources")
+            ost = torch.empty(n_src, max_out, device=dev, dtype=torch.int32)
+            need = int(self.L.sylph_stitch_views_bytes(n_src, nv, max_in))
+            ws = self._merge_ws
+            if need > 0 and (ws is None or ws.numel() < need):  # (a refused size: the entry names the reason)
+                ws = self._merge_ws = torch.empty(need, device=dev, dtype=torch.uint8)
+            t = tables
+            check(self.L.sylph_stitch_views(self._ctx, *t[:6], farr([v["crop"][3] for v in view_table]), t[6], farr([hw[1] for hw in sizes]),
+                                            farr([hw[0] for hw in sizes]), *t[7:], sthr, border, topk, *outs[:6], _ptr(ost), *outs[6:],
+                                            _ptr(ws) if ws is not None else None, ws.numel() if ws is not None else 0), "stitch_views")
+        elif large:
             need = int(self.L.sylph_merge_views_large_bytes(n_src, nv, max_in))
             ws = self._merge_ws
             if need > 0 and (ws is None or ws.numel() < need):  # (a refused size: the entry names the reason)
@@ -897,6 +920,8 @@ class Engine:
             k = cnt[s_]
             out.append({"pred_boxes": ob[s_, :k], "scores": osc[s_, :k], "pred_classes": wide[0, s_, :k], "view_index": wide[1, s_, :k],
                         "view_row": wide[2, s_, :k]})
+            if stitch is not None:
+                out[-1]["stitched"] = ost[s_, :k].long()
         return out
 
     # ---- support path -------------------------------------------------------------------------------

@@ -12,14 +12,15 @@ components the meta-architecture builds, binds to its HIP context and calls wher
 another implementation registered under another name plugs in the same way.
 """
 import logging
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 from torch import nn
 
 from .engine import Engine, QueryRecord
 from .structures import Boxes, Instances
-from .views import DEFAULT_MAX_BATCH, check_views, make_view, merge_route, plan_view_steps, tta_views, view_out_size
+from .views import (DEFAULT_MAX_BATCH, check_views, make_view, plan_view_steps, stitch_params, tta_views, view_merge_route,
+                    view_out_size)
 
 logger = logging.getLogger(__name__)
 
@@ -352,6 +353,9 @@ class MetaOneStageDetector(nn.Module):
                 any(isinstance(x, dict) and x.get("max_detections") is not None for x in batched_inputs):
             raise ValueError("\"max_detections\" is the keep count of the merge of an input's views: it needs \"views\" on the inputs or "
                              "TEST.AUG.ENABLED (without views POST_NMS_TOPK_TEST decides)")
+        if views is None and run_type == "meta_learn_test_instance" and rec is None and \
+                any(isinstance(x, dict) and stitch_params(x.get("stitch")) is not None for x in batched_inputs):
+            raise ValueError("\"stitch\" joins what the borders of an input's views cut: it needs \"views\" on the inputs or TEST.AUG.ENABLED")
         if views is not None:
             if sets is not None:
                 raise NotImplementedError("class_code_sets together with query views (inputs carrying \"views\", or TEST.AUG.ENABLED) is not "
@@ -606,13 +610,15 @@ class MetaOneStageDetector(nn.Module):
         (plan_view_steps); a step is preprocess_views (cut from the sources, which are uploaded once) -> backbone -> head -> decode at
         the crop size into its slice of one row buffer; then ONE merge call (class-wise NMS over the views of a source, in source
         pixels; views.merge_route picks the one-block merge or, for a source of more than 4 096 rows or a "max_detections" = K on the
-        inputs, the workspace merge with K as rule 5's count and 2 K output rows) and one read-back.  class_codes: a dict (every
+        inputs, the workspace merge with K as rule 5's count and 2 K output rows; with "stitch" on the inputs, Engine.stitch_views, which
+        also joins what tile borders cut and adds the field `stitched`) and one read-back.  class_codes: a dict (every
         view), a per-input list (all views of an input take its episode) or None (the pretrained classifier).  -> [{"instances": Instances}] at the source's size, or at "height" / "width" when they differ
         (rescaled and clipped as detector_postprocess does) with pred_boxes, scores, pred_classes and the provenance view_index (into the
         input's own view list) / view_row."""
         assert not self.training, "Not for training"
         eng = self.engine
         topk = self._max_detections(batched_inputs)
+        stitch = self._stitch(batched_inputs)
         run_head = self._view_head(class_codes, len(batched_inputs))
         table = [dict(v, source=i, view=k) for i, vs in enumerate(per_input_views) for k, v in enumerate(vs)]
         steps = plan_view_steps(table, int(self.view_max_batch), int(getattr(self.backbone, "size_divisibility", 32)))
@@ -631,8 +637,12 @@ class MetaOneStageDetector(nn.Module):
         results = []
         own_index = torch.tensor([v["view"] for v in table], device=self.device)  # row of the buffer -> index in the input's own view list
         per_source = [len(vs) for vs in per_input_views]
-        if merge_route(per_source, rows["max_in"], topk) == "block":
+        route = view_merge_route(per_source, rows["max_in"], topk, stitch)
+        if route == "block":
             merged = eng.merge_views(table, rows, n_src=len(batched_inputs))
+        elif route == "stitch":
+            merged = eng.stitch_views(table, rows, [(int(s.shape[0]), int(s.shape[1])) for s in sources], stitch[0], stitch[1],
+                                      max_out=None if topk is None else 2 * topk, n_src=len(batched_inputs), topk=topk)
         else:  # a K of the inputs' own replaces the config's for the merged result only: every view was decoded under the config
             merged = eng.merge_views_large(table, rows, max_out=None if topk is None else 2 * topk, n_src=len(batched_inputs), topk=topk)
         for x, src, d in zip(batched_inputs, sources, merged):
@@ -640,19 +650,31 @@ class MetaOneStageDetector(nn.Module):
             H, W = int(x.get("height", h)), int(x.get("width", w))
             boxes, scores, classes = d["pred_boxes"], d["scores"], d["pred_classes"]
             view_index, view_row = own_index[d["view_index"]], d["view_row"]
+            stitched = d.get("stitched")
             if (H, W) != (h, w):  # detector_postprocess: scale, clip, drop what became empty
                 boxes = boxes * boxes.new_tensor([W / w, H / h, W / w, H / h])
                 boxes = torch.minimum(boxes.clamp(min=0), boxes.new_tensor([W, H, W, H]))
                 keep = ((boxes[:, 2] - boxes[:, 0]) > 0) & ((boxes[:, 3] - boxes[:, 1]) > 0)
                 boxes, scores, classes, view_index, view_row = boxes[keep], scores[keep], classes[keep], view_index[keep], view_row[keep]
+                stitched = stitched[keep] if stitched is not None else None
             r = Instances((H, W))
             r.pred_boxes = Boxes(boxes)
             r.scores = scores
             r.pred_classes = classes
             r.view_index = view_index  # which of the input's views each detection came from, and its row in that view's decode
             r.view_row = view_row
+            if stitched is not None:
+                r.stitched = stitched  # the rows this detection stands for, itself included (1: nothing was joined to it)
             results.append({"instances": r})
         return results
+
+    @staticmethod
+    def _stitch(batched_inputs: List[Dict[str, Any]]) -> Optional[Tuple[float, float]]:
+        """The "stitch" of a batch with views -> (stitch_thr, border_px), None when no input asks for it.  One merge call has one pair."""
+        ps = {stitch_params(x.get("stitch")) for x in batched_inputs}
+        if len(ps) > 1:
+            raise ValueError(f"the inputs of one batch disagree on \"stitch\": {sorted(ps, key=lambda p: (p is not None, p))}")
+        return ps.pop()
 
     @staticmethod
     def _max_detections(batched_inputs: List[Dict[str, Any]]) -> Optional[int]:

@@ -13,7 +13,7 @@ import torch
 
 from .evaluation import format_class_codes_shared
 from .runner import create_cfg, create_runner
-from .views import resize_shortest_edge_shape, tile_views  # noqa: F401  (resize_shortest_edge_shape: part of this module's surface)
+from .views import resize_shortest_edge_shape, stitch_params, tile_views  # noqa: F401  (resize_shortest_edge_shape: part of this module's surface)
 
 logger = logging.getLogger(__name__)
 
@@ -36,13 +36,17 @@ class SylphPredictor:
     def __init__(self, config_file: str, weight_path: str, class_code_path: str,
                  runner_name: str = "sylph.runner.MetaFCOSRunner", test_dataset_names: Dict = None,
                  dtype: Optional[str] = None, fused_preprocess: bool = True, tiles: Optional[Tuple[int, int]] = None,
-                 tile_overlap: float = 0.2, max_detections: Optional[int] = None):
+                 tile_overlap: float = 0.2, max_detections: Optional[int] = None, stitch: bool = False, stitch_thr: float = 0.5,
+                 stitch_border: float = 2.0):
         """tiles = (tile_h, tile_w): large images are run as a grid of overlapping crops of that size plus the full frame, each resized
         by the MIN_SIZE_TEST / MAX_SIZE_TEST rule, and the detections are merged on the device in the coordinates of the image
         (sylph_amd.views.tile_views).  cfg.TEST.AUG.ENABLED gives multi-scale / flip test-time augmentation the same way.  Both need
         the fused uint8 input path.  max_detections = K (with tiles or cfg.TEST.AUG.ENABLED, i.e. wherever views are merged): the merged
         result of an image keeps its K best boxes (and the ties of the K-th) instead of POST_NMS_TOPK_TEST, which stays the bound of
-        every single view.  Without views there is no merge and the argument is refused."""
+        every single view.  Without views there is no merge and the argument is refused.  stitch=True (with tiles or TEST.AUG.ENABLED):
+        an object that tile borders cut comes back once, with its whole box, instead of one clipped piece per tile: a box within
+        stitch_border pixels of an inner tile border is joined to the first kept box of its class that shares more than stitch_thr of
+        the smaller of the two (sylph_stitch_views); the outputs gain `stitched`, the rows each one stands for."""
         logger.info("SylphPredictor initializing...")
         runner = create_runner(runner_name)
         self.cfg = create_cfg(runner.get_default_cfg(), config_file, None).clone()
@@ -73,6 +77,11 @@ class SylphPredictor:
         aug = self.cfg.get("TEST", {}).get("AUG", {})
         if self.max_detections is not None and (self.max_detections <= 0 or (self.tiles is None and not bool(aug.get("ENABLED", False)))):
             raise ValueError("max_detections is a positive count for the merged result of an image's views: it needs tiles or TEST.AUG.ENABLED")
+        self.stitch = {"thr": float(stitch_thr), "border": float(stitch_border)} if stitch else None
+        if self.stitch is not None:
+            if self.tiles is None and not bool(aug.get("ENABLED", False)):
+                raise ValueError("stitch joins what the borders of an image's views cut: it needs tiles or TEST.AUG.ENABLED")
+            stitch_params(self.stitch)  # (refuses a threshold outside (0, 1] and a negative border by name)
         if self.tiles is not None and not fused_preprocess:
             raise ValueError("tiles needs fused_preprocess=True: the tiles are cut from the uint8 original on the device")
         self._pinned = {}  # (h, w) -> pinned uint8 staging buffer for the asynchronous H2D copy
@@ -120,6 +129,8 @@ class SylphPredictor:
                 inputs["views"] = tile_views(height, width, self.tiles, self.tile_overlap, self.min_size, self.max_size)
             if self.max_detections is not None:  # (tiles, or the model's TEST.AUG views)
                 inputs["max_detections"] = self.max_detections
+            if getattr(self, "stitch", None) is not None:
+                inputs["stitch"] = dict(self.stitch)
             return inputs
         if self.tiles is not None:
             raise ValueError(f"tiles needs a uint8 image, got {original_image.dtype}")

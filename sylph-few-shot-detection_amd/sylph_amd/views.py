@@ -121,3 +121,54 @@ def merge_route(views_per_source: Sequence[int], max_in: int, topk: Optional[int
     if topk is None and all(int(n) * int(max_in) <= MERGE_POOL_CAP for n in views_per_source):
         return "block"
     return "large"
+
+
+DEFAULT_STITCH_THR = 0.5    # share of the smaller box that a cut fragment and its keeper must have in common
+DEFAULT_STITCH_BORDER = 2.0  # pixels from an inner crop border within which a box counts as cut
+
+
+def stitch_params(stitch) -> Optional[Tuple[float, float]]:
+    """An input's "stitch" value -> (stitch_thr, border_px), None when stitching is off: True takes the defaults, a dict may carry "thr"
+    and "border".  A threshold outside (0, 1], a negative border or an unknown key raises ValueError by name."""
+    if stitch is None or stitch is False:
+        return None
+    if stitch is True:
+        return DEFAULT_STITCH_THR, DEFAULT_STITCH_BORDER
+    if not isinstance(stitch, dict) or set(stitch) - {"thr", "border"}:
+        raise ValueError(f"\"stitch\" must be True or a dict with \"thr\" and / or \"border\", got {stitch!r}")
+    thr, border = float(stitch.get("thr", DEFAULT_STITCH_THR)), float(stitch.get("border", DEFAULT_STITCH_BORDER))
+    if not 0.0 < thr <= 1.0:
+        raise ValueError(f"\"stitch\": thr {thr} is outside (0, 1]")
+    if not border >= 0.0:
+        raise ValueError(f"\"stitch\": border {border} must be at least 0")
+    return thr, border
+
+
+def view_merge_route(views_per_source: Sequence[int], max_in: int, topk: Optional[int], stitch: Optional[Tuple[float, float]]) -> str:
+    """merge_route with stitching: "stitch" -- Engine.stitch_views -- whenever the call asks for it (stitch_params gave a pair), whatever
+    its size; otherwise merge_route's answer, unchanged."""
+    if stitch is not None:
+        return "stitch"
+    return merge_route(views_per_source, max_in, topk)
+
+
+def cut_flags(view: Dict, source_hw: Sequence[int], boxes_src, border_px: float):
+    """Rule 0 of sylph_stitch_views in float32 on the host: boxes_src (N, 4) in SOURCE pixels (after the view's flip and offset) -> (N,)
+    bool, True where a border of the view's crop that lies inside the (height, width) source cuts the box: the box comes within
+    border_px of it.  A crop border that is the source's own never cuts."""
+    import numpy as np
+    f = np.float32
+    b = np.asarray(boxes_src, dtype=f).reshape(-1, 4)
+    x0, y0, cw, ch = (f(t) for t in view["crop"])
+    sh, sw, bp = f(source_hw[0]), f(source_hw[1]), f(border_px)
+    left, top, right, bottom = x0, y0, f(x0 + cw), f(y0 + ch)
+    cut = np.zeros(len(b), dtype=bool)
+    if left > 0:
+        cut |= b[:, 0] <= f(left + bp)
+    if right < sw:
+        cut |= b[:, 2] >= f(right - bp)
+    if top > 0:
+        cut |= b[:, 1] <= f(top + bp)
+    if bottom < sh:
+        cut |= b[:, 3] >= f(bottom - bp)
+    return cut
