@@ -330,6 +330,8 @@ class Engine:
         self._records = []  # live QueryRecords of this engine
         self._record = None  # the one that is the current batch (load_record), None on a fresh batch
         self._merge_ws = None  # merge_views_large's workspace: grows on demand, contents are scratch
+        self._counts_free = {}  # length -> pinned count buffers no handle owns (_counts_acquire)
+        self._counts_out = set()  # ids of the pinned count buffers that unfetched decode handles own
 
     def close(self):
         if self._ctx:
@@ -655,14 +657,7 @@ class Engine:
         check(self.L.sylph_decode_nms_codesets(self._ctx, G, oh, ow, max_out, _ptr(boxes), _ptr(scores), _ptr(ints[0]), _ptr(ints[1]),
                                                _ptr(locs), _ptr(ints[2]), _ptr(counts), c_void_p(counts.data_ptr() + 4 * S)),
               "decode_nms_codesets")
-        # pinned staging for the counts: the per-engine ring of decode_launch (a fresh pinned allocation per step costs milliseconds)
-        slot = self.__dict__.setdefault("_count_ring", {}).setdefault(("code sets", S), {"bufs": [], "next": 0})
-        if len(slot["bufs"]) < 8:
-            slot["bufs"].append(torch.empty(S + 1, dtype=torch.int32, pin_memory=True))
-            host_counts = slot["bufs"][-1]
-        else:
-            host_counts = slot["bufs"][slot["next"] % 8]
-            slot["next"] += 1
+        host_counts = self._counts_acquire(S + 1)  # pinned staging for the counts, as in decode_launch
         host_counts.copy_(counts, non_blocking=True)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(dev))
@@ -752,7 +747,18 @@ class Engine:
 
     def decode_launch(self, out_sizes: Optional[List[Tuple[int, int]]] = None, max_out: Optional[int] = None):
         """Enqueue decode + NMS on the current stream and return a handle WITHOUT synchronising: the caller can
-        launch the next batch (another Engine on another stream) before `decode_fetch` reads the counts back."""
+        launch the next batch (another Engine on another stream) before `decode_fetch` reads the counts back.
+
+        The in-flight contract (tests/test_steps_in_flight_gpu.py):
+          * any number of handles may be outstanding, and they may be fetched in any order, each once; a handle carries its own counts
+            and its own status word, so `decode_fetch` raises for the step that overflowed and for no other;
+          * every entry runs on torch's current stream.  While handles are outstanding the engine stays on one stream, or the caller
+            orders the streams itself (`new.wait_stream(old)`) before it switches; `decode_fetch` may run on any stream (it makes
+            the current stream wait for the handle's);
+          * the caller keeps the tensors it passed in (images, class codes) alive until the step that reads them has been fetched:
+            the library reads device images through the caller's pointers when the step runs, not when it is enqueued.  Writing
+            into them in place is fine when the write is ordered on the engine's stream (a `copy_` there is seen by the steps
+            enqueued after it and by none before it)."""
         self._stream()
         B = self._batch[0]
         if max_out is None:
@@ -769,25 +775,33 @@ class Engine:
         check(self.L.sylph_decode_nms(self._ctx, oh, ow, max_out, _ptr(boxes), _ptr(scores), _ptr(classes),
                                       _ptr(levels), _ptr(locs), _ptr(cand), _ptr(counts),
                                       c_void_p(counts.data_ptr() + 4 * B)), "decode_nms")
-        # pinned staging for the counts: a small per-engine ring (a fresh pinned allocation per step costs milliseconds
-        # of host time, which is the whole step at batch 1)
-        ring = self.__dict__.setdefault("_count_ring", {})
-        slot = ring.setdefault(B, {"bufs": [], "next": 0})
-        if len(slot["bufs"]) < 8:
-            slot["bufs"].append(torch.empty(B + 1, dtype=torch.int32, pin_memory=True))
-            host_counts = slot["bufs"][-1]
-        else:
-            host_counts = slot["bufs"][slot["next"] % 8]
-            slot["next"] += 1
+        host_counts = self._counts_acquire(B + 1)  # pinned staging for the counts: this handle's until decode_fetch has read it
         host_counts.copy_(counts, non_blocking=True)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(dev))
         return (B, boxes, scores, ints, None, locs, None, host_counts, done, torch.cuda.current_stream(dev))
 
+    def _counts_acquire(self, n: int) -> torch.Tensor:
+        """A pinned (n,) int32 staging buffer for one decode's counts and status word.  It belongs to the handle that carries it from
+        the launch until decode_fetch has read it, however many decodes are launched in between; fetched buffers are reused, and a new
+        one is allocated only when none of that length is free (a fresh pinned allocation costs milliseconds of host time, which is the
+        whole step at batch 1): a serving loop with k steps in flight allocates k buffers and then none."""
+        free = self._counts_free.setdefault(n, [])
+        buf = free.pop() if free else torch.empty(n, dtype=torch.int32, pin_memory=True)
+        self._counts_out.add(id(buf))
+        return buf
+
+    def _counts_release(self, buf: torch.Tensor):
+        self._counts_out.discard(id(buf))
+        self._counts_free.setdefault(buf.numel(), []).append(buf)
+
     def decode_fetch(self, handle):
         B, boxes, scores, ints, _, locs, _, host_counts, done, stream = handle
+        if id(host_counts) not in self._counts_out:
+            raise RuntimeError("sylph decode_fetch: this handle has been fetched already (or belongs to another Engine)")
         done.synchronize()
         cnt = host_counts.tolist()
+        self._counts_release(host_counts)  # read: the buffer is free for the next launch, whatever the status word says
         status = cnt[B]
         if status & 1:
             raise RuntimeError("sylph decode: per-level candidate capacity exceeded (raise cand_cap)")
