@@ -246,6 +246,35 @@ int sylph_record_store(sylph_ctx* ctx, sylph_record** out);
  * (sylph_backbone_fpn, sylph_export_pyramid, sylph_codegen*, sylph_roi_align*, the backbone and tower taps) and sylph_fcos_towers fail and
  * name the record.  A record made under another dtype, or under a sylph_config with another tower norm, level count, strides or code kernel size, is refused. */
 int sylph_record_load(sylph_ctx* ctx, const sylph_record* rec);
+
+/* Fine-tuning the class-conditional layer on the current batch's stored tower outputs: the TFA protocol the reference compares against
+ * (configs/COCO-Detection/TFA/FCOS_finetune.yaml, the Meta-FCOS-pretrain-tfa-finetune yamls of each dataset: FREEZE_CLS_TOWER,
+ * FREEZE_BBOX_TOWER / FREEZE_BBOX_BRANCH, MODEL.TFA.*), where only the last classifier layer -- CondConvBasic's codes, or the base
+ * detector's cls_logits -- is trained on the K shots.  The three entries act on the current batch, a fresh one after sylph_fcos_towers (or
+ * a head entry) or a loaded query record, bf16 with the deferred last GroupNorm and 1x1 codes; fp32 / f32s contexts, FCOS.NORM "none",
+ * 3x3 codes and the ROIEncoder are refused by name.  None of them changes anything a later sylph_fcos_head* / sylph_decode_nms* on the
+ * same batch or record reads.
+ *
+ * sylph_fcos_targets: FCOSOutputs.compute_targets_for_locations + get_sample_region (fcos_outputs.py:193-349), labels only.  n_gt boxes
+ * (x0, y0, x1, y1) in network-input pixels with their class index and image index, sorted by image, all device arrays; sizes_of_interest:
+ * host, nlevels - 1 values (MODEL.FCOS.SIZES_OF_INTEREST); center_sample / pos_radius: MODEL.FCOS.CENTER_SAMPLE / POS_RADIUS.
+ * labels_out_dev: one int32 per row of the tower output (B * rows-per-image, the row order of the logits): the class index of the
+ * smallest-area box that claims the location (the lowest index among equal areas), -1 for background; every location of the padded map
+ * gets a label, as in the reference.  num_pos_out_dev: one int32, the number of rows with a label >= 0 (fcos_outputs.py:646). */
+int sylph_fcos_targets(sylph_ctx* ctx, int n_gt, const float* boxes_dev, const int* gt_class_dev, const int* gt_image_dev,
+                       const float* sizes_of_interest, int n_soi, int center_sample, float pos_radius, int* labels_out_dev,
+                       int* num_pos_out_dev);
+/* Bytes of workspace sylph_cls_grad needs for the current batch (the per-unit partial sums of one class block; N does not change it). */
+int sylph_cls_grad_bytes(sylph_ctx* ctx, int N, int64_t* bytes_out);
+/* Loss and gradient of the classification loss of FCOSOutputs.fcos_losses (fcos_outputs.py:640-660: sigmoid_focal_loss_jit(logits, one-hot,
+ * alpha, gamma, reduction "sum"), NOT yet divided by num_pos_avg -- the caller normalises) with respect to the class codes, through
+ * CondConvBasic (head_utils.py:60-81): logits = cls_tower . bf16(cls_conv)^T + cls_bias on the operand values sylph_fcos_head serves.
+ * cls_conv_dev (N, 256) fp32 and cls_bias_dev (N) fp32 or NULL: device; class n of this call is label class_offset + n, so that a large
+ * class set may be passed in pieces (the loss is separable per class).  Any N: one pass over the tower output per 32 classes.
+ * loss_out_dev: one float, the sum over rows and the N classes; grad_w_out_dev (N, 256), grad_b_out_dev (N) or NULL.  The same inputs
+ * give the same bits on every call. */
+int sylph_cls_grad(sylph_ctx* ctx, const int* labels_dev, const float* cls_conv_dev, const float* cls_bias_dev, int N, int class_offset,
+                   float alpha, float gamma, void* workspace_dev, float* loss_out_dev, float* grad_w_out_dev, float* grad_b_out_dev);
 /* Batch size, padded size and device bytes of a record; NULL skips. */
 int sylph_record_info(const sylph_record* rec, int* B, int* padded_h, int* padded_w, int64_t* bytes);
 /* Release a record, with the context that stored it (the stream is drained first).  If it is the current batch, no batch is current

@@ -254,6 +254,9 @@ struct sylph_ctx {
   hipEvent_t shot_ev = nullptr;
   float *shot_cls = nullptr, *shot_h = nullptr;
   int shot_seg_cap = 0;
+  // sylph_cls_grad: the packed codes [32][256] and biases [32] of the class block in flight (stream order serialises the blocks of a call)
+  void* ft_codes = nullptr;
+  float* ft_bias = nullptr;
   void* zeros = nullptr;  // 256 B of zeros (conv out-of-image taps)
   // small batches: the two FCOS towers of a head pass run on two streams (fork / join events around the bbox tower, api_head.hip)
   hipStream_t side_stream = nullptr;

@@ -218,6 +218,18 @@ int launch_gn_logits_sets(const void* x, int ld, const float2* coef, const void*
 int launch_gn_pred_taps(const void* x, int ld, const float2* coef, const void* w_taps, int cp, const float* bias, int relu_nch, int mul_nch,
                         float* planes_ws, size_t plane_rows, float* out, int out_ld, const SegDesc* segs, const int2* tiles, int n_tiles,
                         hipStream_t s);  // head_fused.hip: last bbox-tower GroupNorm + 3x3 prediction convs (bf16)
+// finetune.hip: FCOS classification targets, and loss + gradient of the focal loss with respect to one block of <= 32 class codes (bf16)
+struct FcosTargetCfg { int strides[8]; float lo[8], hi[8]; int center_sample; float radius; };  // lo / hi: the level's range of the largest regression target
+int launch_fcos_targets(const SegDesc* segs, int nseg, int nlevels, int max_rows, const FcosTargetCfg& cfg, int n_gt, const float* boxes,
+                        const int* gt_class, const int* gt_image, int* labels, int* num_pos, hipStream_t s);
+constexpr int CLS_GRAD_UNIT_GROUPS = 16;  // 32-row groups behind one partial: fixed by the tile table, so the sums do not depend on the grid
+constexpr int CLS_GRAD_PARTIAL = 8256;    // floats per partial: [256][32] dW^T | [32] db | loss, rounded up to 128 bytes
+constexpr int CLS_GRAD_MAX_BLOCKS = 1024;  // one block of four waves per CU and a few to spare; SYLPH_CLS_GRAD_BLOCKS overrides it
+int cls_grad_units(int n_tiles);
+size_t cls_grad_ws_floats(int n_tiles);
+int launch_cls_grad(const void* x, int ld, const float2* coef, const void* w, const float* bias, int nb, int n0, const int* labels, float alpha,
+                    float gamma, float* ws, float* loss, int accumulate, float* grad_w, float* grad_b, const SegDesc* segs, const int2* tiles,
+                    int n_tiles, hipStream_t s);
 int launch_stem_pool(const void* x, const void* wp, const float* scale, const float* shift, void* out, void* trash, int B, int H, int W,
                      int H2, int W2, int H4, int W4, hipStream_t s);
 constexpr int STEM_RAW_MAX_BATCH = 512;  // the image table of launch_stem_pool_raw lives in LDS

@@ -73,6 +73,9 @@ PROTOTYPES = {
     "sylph_record_load": (c_int, [c_void_p, c_void_p]),
     "sylph_record_info": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int64)]),
     "sylph_record_destroy": (None, [c_void_p, c_void_p]),
+    "sylph_fcos_targets": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_int, c_float, c_void_p, c_void_p]),
+    "sylph_cls_grad_bytes": (c_int, [c_void_p, c_int, POINTER(c_int64)]),
+    "sylph_cls_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylph_roi_align": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sylph_roi_align_rois": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p]),
     "sylph_decode_nms": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,

@@ -330,6 +330,13 @@ class Engine:
         self._records = []  # live QueryRecords of this engine
         self._record = None  # the one that is the current batch (load_record), None on a fresh batch
         self._merge_ws = None  # merge_views_large's workspace: grows on demand, contents are scratch
+        self._ft_ws = None  # cls_grad's workspace (the per-unit partial sums): grows on demand, contents are scratch
+        # what the training-side entries (fcos_targets, cls_grad) read from MODEL.FCOS: focal loss and target assignment
+        f = cfg.MODEL.FCOS if cfg is not None else {}
+        self.fcos_train = {"alpha": float(f.get("LOSS_ALPHA", 0.25)), "gamma": float(f.get("LOSS_GAMMA", 2.0)),
+                           "sizes_of_interest": [float(v) for v in f.get("SIZES_OF_INTEREST", [64, 128, 256, 512])],
+                           "center_sample": bool(f.get("CENTER_SAMPLE", True)), "pos_radius": float(f.get("POS_RADIUS", 1.5)),
+                           "prior_prob": float(f.get("PRIOR_PROB", 0.01))}
         self._counts_free = {}  # length -> pinned count buffers no handle owns (_counts_acquire)
         self._counts_out = set()  # ids of the pinned count buffers that unfetched decode handles own
 
@@ -504,6 +511,77 @@ class Engine:
         self._record = rec
         self._keep = []
         self._ncls = 0
+
+    # ---- fine-tuning the class codes on the current batch's tower outputs (sylph_amd.finetune) ---------------------------------
+    def batch_rows(self) -> int:
+        """Rows of the current batch's tower output: B x the locations of the padded pyramid."""
+        if getattr(self, "_batch", None) is None:
+            raise RuntimeError("no current batch")
+        B, H, W, _ = self._batch
+        return B * sum(h * w for h, w in self.level_shapes(H, W))
+
+    def fcos_targets(self, boxes: torch.Tensor, classes: torch.Tensor, image_index: torch.Tensor):
+        """FCOS classification targets of the current batch (a fresh batch after `towers()`, or a loaded record): `boxes` (n, 4) in
+        network-input pixels, `classes` (n,), `image_index` (n,) sorted.  Returns (labels, num_pos): int32 device tensors, one label per
+        row of the tower output (-1: background) and the count of positives; nothing is read back.  (The arguments are validated on
+        the host: device tensors are copied back for that.)"""
+        self._stream()
+        bx = torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 4)
+        cl = torch.as_tensor(classes).reshape(-1)
+        im = torch.as_tensor(image_index).reshape(-1)
+        n = bx.shape[0]
+        if cl.numel() != n or im.numel() != n:
+            raise ValueError(f"fcos_targets: {n} boxes, {cl.numel()} classes and {im.numel()} image indices")
+        rows = self.batch_rows()
+        B = self._batch[0]
+        iml = im.tolist()
+        if any(a > b for a, b in zip(iml, iml[1:])):
+            raise ValueError("fcos_targets: gt_image is not sorted (image_index must not decrease)")
+        if n and (iml[0] < 0 or iml[-1] >= B):
+            raise ValueError(f"fcos_targets: image_index outside the batch of {B} images")
+        if n and int(cl.min()) < 0:
+            raise ValueError("fcos_targets: a class index is negative")
+        fc = self.fcos_train
+        bx = bx.to(self.device).contiguous()
+        cl = cl.to(self.device, torch.int32).contiguous()
+        im = im.to(self.device, torch.int32).contiguous()
+        labels = torch.empty(rows, device=self.device, dtype=torch.int32)
+        num_pos = torch.empty(1, device=self.device, dtype=torch.int32)
+        soi = (ctypes.c_float * len(fc["sizes_of_interest"]))(*fc["sizes_of_interest"])
+        check(self.L.sylph_fcos_targets(self._ctx, n, _ptr(bx), _ptr(cl), _ptr(im), soi, len(fc["sizes_of_interest"]),
+                                        int(fc["center_sample"]), float(fc["pos_radius"]), _ptr(labels), _ptr(num_pos)), "fcos_targets")
+        return labels, num_pos
+
+    def cls_grad(self, labels: torch.Tensor, cls_conv: torch.Tensor, cls_bias: Optional[torch.Tensor], class_offset: int = 0,
+                 check_labels: bool = True):
+        """Sum of the sigmoid focal loss over the current batch's locations and the N classes of `cls_conv` (N, 256[, 1, 1]), and its
+        gradient: (loss_sum (1,), grad_w (N, 256), grad_b (N,) or None), fp32 device tensors, not divided by the number of positives.
+        Class n is label class_offset + n.  check_labels reads the largest label back (one sync) and refuses a label >= N by name; a
+        loop that has validated its annotations passes False."""
+        self._stream()
+        if not torch.is_tensor(labels) or labels.dtype != torch.int32 or labels.device != self.device or labels.numel() != self.batch_rows():
+            raise ValueError(f"cls_grad: labels must be the int32 device tensor of {self.batch_rows()} rows fcos_targets returns for this batch")
+        w = cls_conv.to(self.device, torch.float32).reshape(cls_conv.shape[0], -1).contiguous()
+        if w.shape[1] != 256:
+            raise ValueError(f"cls_grad: 3x3 class codes are not supported: cls_conv must be (N, 256) or (N, 256, 1, 1), not {tuple(cls_conv.shape)}")
+        N = w.shape[0]
+        b = cls_bias.to(self.device, torch.float32).reshape(-1).contiguous() if cls_bias is not None else None
+        if b is not None and b.numel() != N:
+            raise ValueError(f"cls_grad: {b.numel()} biases for {N} classes")
+        if check_labels and class_offset == 0 and labels.numel() and int(labels.max()) >= N:
+            raise ValueError(f"cls_grad: a label >= N (largest label {int(labels.max())}, {N} classes)")
+        need = c_int64(0)
+        check(self.L.sylph_cls_grad_bytes(self._ctx, N, ctypes.byref(need)), "cls_grad_bytes")
+        if self._ft_ws is None or self._ft_ws.numel() < need.value:
+            self._ft_ws = torch.empty(need.value, device=self.device, dtype=torch.uint8)
+        loss = torch.empty(1, device=self.device, dtype=torch.float32)
+        gw = torch.empty(N, 256, device=self.device, dtype=torch.float32)
+        gb = torch.empty(N, device=self.device, dtype=torch.float32) if b is not None else None
+        fc = self.fcos_train
+        check(self.L.sylph_cls_grad(self._ctx, _ptr(labels), _ptr(w), _ptr(b), N, int(class_offset), float(fc["alpha"]), float(fc["gamma"]),
+                                    _ptr(self._ft_ws), _ptr(loss), _ptr(gw), _ptr(gb)), "cls_grad")
+        self._keep_ft = (w, b)
+        return loss, gw, gb
 
     def _fold_codes(self, cls_conv: torch.Tensor, cls_bias: Optional[torch.Tensor], raw: bool = False):
         """One episode's class codes -> ((N, 256) fp32, (N,) fp32 or None) on the device, the CondConvBlock of a ROIEncoder model folded in."""

@@ -288,7 +288,8 @@ class MetaOneStageDetector(nn.Module):
       "meta_learn_cache_query"              -> forward_cache_query: one network pass, no class codes -> [record-input]: a QueryRecord of
                                                the batch with each input's metadata and no image tensors (not in the reference, whose
                                                evaluation pays the whole network per seed and shot setting, meta_fcos_runner.py:451-672)
-    Training is out of scope: calling the model in training mode raises NotImplementedError."""
+    Training the network is out of scope: calling the model in training mode raises NotImplementedError.  What is trained here is the
+    class-conditional layer alone, on stored tower outputs: `finetune_class_codes` (the TFA baseline; sylph_amd.finetune)."""
 
     def __init__(self, cfg, dtype: Optional[str] = None, device_index: Optional[int] = None):
         super().__init__()
@@ -732,6 +733,61 @@ class MetaOneStageDetector(nn.Module):
             m.update(height=oh, width=ow, net_height=nh, net_width=nw)
             metas.append(m)
         return [{"record": rec, "inputs": metas}]
+
+    # ---- fine-tuning the class codes on annotated images (the TFA baseline; sylph_amd.finetune) --------------------------------------
+    @staticmethod
+    def _record_annotations(rec_input) -> Dict[str, torch.Tensor]:
+        """boxes / classes / image_index of one record-input whose per-image metadata carries "instances".  gt_boxes live in the frame
+        instances.image_size names; they are scaled to the size the network saw (net_height, net_width)."""
+        boxes, classes, index = [], [], []
+        for i, m in enumerate(rec_input["inputs"]):
+            inst = m.get("instances")
+            if inst is None:
+                raise ValueError(f"finetune_class_codes: input {i} of a record carries no \"instances\"")
+            bx = inst.gt_boxes.tensor.detach().float().cpu().reshape(-1, 4)
+            ih, iw = inst.image_size
+            nh, nw = int(m.get("net_height", ih)), int(m.get("net_width", iw))
+            if (nh, nw) != (int(ih), int(iw)):
+                bx = bx * torch.tensor([nw / iw, nh / ih, nw / iw, nh / ih])
+            boxes.append(bx)
+            classes.append(inst.gt_classes.detach().cpu().reshape(-1).long())
+            index.append(torch.full((bx.shape[0],), i, dtype=torch.long))
+        return {"boxes": torch.cat(boxes), "classes": torch.cat(classes), "image_index": torch.cat(index)}
+
+    def finetune_class_codes(self, batched_inputs, class_code=None, *, batch_size: Optional[int] = None, **kw):
+        """Refine `class_code` on annotated images (sylph_amd.finetune.finetune_class_codes; kw: iters, lr, momentum, weight_decay,
+        records_per_step, trainable, lr_steps, lr_gamma, seed).  `batched_inputs`: dicts with "image" (or "image_u8" + "resize_hw") and
+        "instances" -- one network pass per `batch_size` of them makes the records, which are released at the end -- or record-inputs
+        of "meta_learn_cache_query" whose per-image metadata was given "instances".  `class_code`: the dict of "meta_learn_test_support" +
+        "meta_learn_normalize_code", or None for the checkpoint's own cls_logits rows (a base detector).  Returns (class codes for
+        "meta_learn_test_instance", the loss of every step as one device tensor)."""
+        from .finetune import finetune_class_codes
+        assert not self.training, "call model.eval(): only the class codes are trained, by their own optimiser"
+        if class_code is None:
+            class_code = self._pretrained_class_codes()
+        inputs = list(batched_inputs)
+        is_rec = [isinstance(x, dict) and "record" in x for x in inputs]
+        if any(is_rec) and not all(is_rec):
+            raise ValueError("finetune_class_codes: records are not mixed with images")
+        own = []
+        try:
+            if not any(is_rec):
+                bs = int(batch_size) if batch_size else max(len(inputs), 1)
+                rec_inputs = []
+                for i in range(0, len(inputs), bs):
+                    chunk = inputs[i:i + bs]
+                    r = self.forward_cache_query(chunk)[0]
+                    own.append(r["record"])
+                    for m, x in zip(r["inputs"], chunk):
+                        m["instances"] = x["instances"]
+                    rec_inputs.append(r)
+            else:
+                rec_inputs = inputs
+            return finetune_class_codes(self, [r["record"] for r in rec_inputs], [self._record_annotations(r) for r in rec_inputs],
+                                        class_code, **kw)
+        finally:
+            for r in own:
+                r.close()
 
     def _run_backbone(self, batched_inputs: List[Dict[str, Any]], with_net_sizes: bool = False):
         """preprocess + backbone of the query batch -> the (height, width) each image's detections are scaled to.  A record-input: no

@@ -200,13 +200,45 @@ class MetaFCOSRunner:
                 f"Got {len(codes)} class codes for prediction, but expect to be {num_classes}."
         return format_class_codes_shared(codes, device=model.device)
 
+    @staticmethod
+    def _finetune_codes(model, support_loader, class_codes, finetune: Dict[str, Any]):
+        """The TFA step of one (dataset, seed): `class_codes` (None: the checkpoint's own cls_logits rows) refined on that seed's support
+        images, every support record's boxes labelled with its item's support_set_target (the row of its code).  finetune: the keyword
+        arguments of MetaOneStageDetector.finetune_class_codes (iters, lr, ..., batch_size: support images per network pass, default 16)."""
+        if D.get_world_size() > 1:
+            raise NotImplementedError(f"finetune: a rank sees its own shard of the support set and gradients are not reduced across ranks; "
+                                      f"world size is {D.get_world_size()}")
+        if support_loader is None:
+            raise ValueError("finetune needs the support images: pass support_loader (or override the support-set loader builder)")
+        kw = dict(finetune)
+        kw.setdefault("batch_size", 16)
+        batch = []
+        for item in support_loader:
+            for x in item:
+                c = int(x["support_set_target"])
+                for rec in x["support_set"]:
+                    src = rec["instances"]
+                    inst = type(src)(src.image_size)
+                    inst.gt_boxes = src.gt_boxes
+                    inst.gt_classes = torch.full((len(src.gt_boxes),), c, dtype=torch.long)
+                    batch.append(dict({k: v for k, v in rec.items() if k != "instances"}, instances=inst))
+        codes, losses = model.finetune_class_codes(batch, class_codes, **kw)
+        ls = losses.cpu()
+        logger.info(f"finetune: {ls.numel()} steps on {len(batch)} support images, loss {float(ls[0]):.4f} -> {float(ls[-1]):.4f}")
+        return codes
+
     def _episode(self, cfg, model, support_loader, query_loader, evaluator=None, base_support_loader=None,
-                 output_folder: Optional[str] = None, num_classes: Optional[int] = None, eval_with_pretrained_code: bool = False):
+                 output_folder: Optional[str] = None, num_classes: Optional[int] = None, eval_with_pretrained_code: bool = False,
+                 finetune: Optional[Dict[str, Any]] = None):
         """ONE (dataset, seed) of meta_fcos_runner.py:497-560: support codes -> gather -> (base-class reduce + replace) ->
-        normalise -> format -> query loop.  Returns (evaluator results, formatted class codes)."""
+        normalise -> format -> [finetune: the codes refined on the support images] -> query loop.  Returns (evaluator results,
+        formatted class codes)."""
         class_codes = None
         if not eval_with_pretrained_code:
             class_codes = self._episode_codes(cfg, model, support_loader, base_support_loader, output_folder, num_classes)
+        if finetune is not None:
+            class_codes = self._finetune_codes(model, support_loader, class_codes, finetune)
+            eval_with_pretrained_code = False  # the refined rows are passed as class codes, also where they started as cls_logits
         res = inference_on_dataset_with_class_codes(model, query_loader, evaluator, class_codes,
                                                     eval_with_pretrained_code=eval_with_pretrained_code)
         return res, class_codes
@@ -214,7 +246,8 @@ class MetaFCOSRunner:
     def _do_test_meta_learning(self, cfg, model, support_loader=None, query_loader=None, evaluator=None, base_support_loader=None,
                                output_folder: Optional[str] = None, num_classes: Optional[int] = None, train_iter=None,
                                model_tag: str = "default", dataset_names: Optional[List[str]] = None, fuse_repeats: bool = False,
-                               cache_queries: bool = False, cache_max_bytes: Optional[int] = None, shot_bank=None, bank_draws=None):
+                               cache_queries: bool = False, cache_max_bytes: Optional[int] = None, shot_bank=None, bank_draws=None,
+                               finetune: Optional[Dict[str, Any]] = None):
         """meta_fcos_runner.py:451-672.
 
         * With explicit loaders (support_loader + query_loader): ONE dataset / seed; returns (results, class_codes) -- the form
@@ -235,11 +268,22 @@ class MetaFCOSRunner:
         * shot_bank=ShotBank with bank_draws=[(shots, seed), ...]: no support pass at all -- every draw's class codes come from the bank
           (evaluation.class_codes_from_bank on shot_bank.draw(shots, seed)); the query side runs as above, on query_loader, or on the
           datasets' loaders, or (cache_queries) on their records.  Returns results[f"shots{K}_seed{s}"][dataset] (dataset "query" for an
-          explicit query_loader).  One rank only."""
+          explicit query_loader).  One rank only.
+        * finetune=dict(iters=..., lr=..., ...): the TFA baseline -- every seed's class codes (on an EVAL_WITH_PRETRAINED_CODE dataset the
+          checkpoint's cls_logits rows) are refined on that seed's support images before its query loop (_finetune_codes;
+          sylph_amd.finetune).  One rank only; not together with fuse_repeats or a shot bank."""
+        if finetune is not None:
+            if D.get_world_size() > 1:
+                raise NotImplementedError(f"finetune: a rank sees its own shard of the support set and gradients are not reduced across ranks; "
+                                          f"world size is {D.get_world_size()}")
+            if shot_bank is not None or bank_draws is not None or fuse_repeats:
+                raise NotImplementedError("finetune together with fuse_repeats or a shot bank is not supported: the codes of every seed are "
+                                          "refined on that seed's support images, one query pass per seed")
         if shot_bank is not None or bank_draws is not None:
             return self._bank_sweep(cfg, model, shot_bank, bank_draws, query_loader, evaluator, dataset_names, cache_queries, cache_max_bytes)
         if support_loader is not None or query_loader is not None:
-            return self._episode(cfg, model, support_loader, query_loader, evaluator, base_support_loader, output_folder, num_classes)
+            return self._episode(cfg, model, support_loader, query_loader, evaluator, base_support_loader, output_folder, num_classes,
+                                 finetune=finetune)
         names = list(dataset_names if dataset_names is not None else cfg.DATASETS.TEST)
         assert len(names)
         max_iter = cfg.get("SOLVER", {}).get("MAX_ITER", None) if hasattr(cfg, "get") else None
@@ -305,12 +349,12 @@ class MetaFCOSRunner:
                 else:
                     folder = folder_of(name, seed)
                     sup = base = None
-                    if not pretrained:
+                    if not pretrained or finetune is not None:
                         sup, base = support_loaders(name, seed)
                     qry = cached[name] if name in cached else self.build_episodic_learning_detection_test_query_loader(cfg, name)
                     ev = self.get_evaluator(cfg, name, output_folder=folder)
                     n_cls = self._global_len(sup) if sup is not None else None
-                    per, _ = self._episode(cfg, model, sup, qry, ev, base, folder, n_cls, eval_with_pretrained_code=pretrained)
+                    per, _ = self._episode(cfg, model, sup, qry, ev, base, folder, n_cls, eval_with_pretrained_code=pretrained, finetune=finetune)
                 if not main:
                     continue
                 results[f"seed{seed}"][name] = per
