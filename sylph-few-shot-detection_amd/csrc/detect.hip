@@ -13,7 +13,8 @@
 //   sort    : per image bitonic sort (descending) in LDS, then box decode of the sorted candidates
 //   nms     : one block per image walks 64-box chunks of the sorted pool: suppression by the boxes kept so far (same class &&
 //             IoU > thr) computed for the visited chunks only, stops once post_nms_topk (+ score ties) are kept, applies
-//             rescale/clip/non-empty filter, writes the outputs.
+//             rescale/clip/non-empty filter, writes the outputs.  The walk itself is block_walk (nms_walk.h), which the view
+//             merges run too; this file supplies the pool's buffers and the emit.
 //
 // Reference arithmetic followed (paths relative to /root/reference):
 //   sylph/modeling/meta_fcos/fcos_outputs.py:904-1008 forward_for_single_feature_map
@@ -23,6 +24,7 @@
 //   sylph/modeling/meta_fcos/fcos.py:270-282 compute_locations
 #include "gn_stream.h"
 #include "kernels.h"
+#include "nms_walk.h"
 
 namespace sylph {
 
@@ -675,24 +677,39 @@ __global__ __launch_bounds__(1024) void decode_sort_kernel(const DecodeCfg cfg, 
   }
 }
 
-__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int src) {
-  const unsigned lo = __shfl((unsigned)(v & 0xffffffffull), src);
-  const unsigned hi = __shfl((unsigned)(v >> 32), src);
-  return ((unsigned long long)hi << 32) | lo;
-}
+// what block_walk (nms_walk.h) asks of the decode pool: positions of image `base / pool_cap` in the sorted-pool buffers; a kept box is rescaled
+// to the output size, clipped, dropped when empty, and written with its level, location and candidate
+struct DecodeWalkSrc {
+  const DecodeBuffers& buf;
+  size_t base;
+  ImageOut io;
+  float *out_boxes, *out_scores;
+  int *out_classes, *out_levels;
+  float* out_locations;
+  int* out_cand;
+  __device__ __forceinline__ float4 box(unsigned p) const { return *reinterpret_cast<const float4*>(buf.s_box + (base + p) * 4); }
+  __device__ __forceinline__ int cls(unsigned p) const { return buf.s_cls[base + p]; }
+  __device__ __forceinline__ float score(unsigned p) const { return buf.s_score[base + p]; }
+  __device__ __forceinline__ bool shape(float4& b) const {
+    b.x *= io.sx; b.y *= io.sy;
+    b.z *= io.sx; b.w *= io.sy;
+    b.x = fminf(fmaxf(b.x, 0.f), io.out_w); b.y = fminf(fmaxf(b.y, 0.f), io.out_h);
+    b.z = fminf(fmaxf(b.z, 0.f), io.out_w); b.w = fminf(fmaxf(b.w, 0.f), io.out_h);
+    return (b.z - b.x) > 0.f && (b.w - b.y) > 0.f;
+  }
+  __device__ __forceinline__ void write(size_t o, unsigned p, float4 b, float score, int cls) const {
+    out_boxes[o * 4 + 0] = b.x; out_boxes[o * 4 + 1] = b.y; out_boxes[o * 4 + 2] = b.z; out_boxes[o * 4 + 3] = b.w;
+    out_scores[o] = score;
+    out_classes[o] = cls;
+    out_levels[o] = buf.s_level[base + p];
+    out_locations[o * 2 + 0] = buf.s_loc[(base + p) * 2 + 0];
+    out_locations[o * 2 + 1] = buf.s_loc[(base + p) * 2 + 1];
+    out_cand[o] = (int)buf.s_ord[base + p];
+  }
+};
 
-// IoU > thr for two boxes of the same class: torchvision's nms arithmetic (inter / (area_i + area_j - inter), no +1)
-__device__ __forceinline__ bool nms_overlap(float x1, float y1, float x2, float y2, float iarea, float4 b, float thr) {
-  const float xx1 = fmaxf(x1, b.x), yy1 = fmaxf(y1, b.y);
-  const float xx2 = fminf(x2, b.z), yy2 = fminf(y2, b.w);
-  const float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
-  const float inter = w * h;
-  const float jarea = (b.z - b.x) * (b.w - b.y);
-  return inter / (iarea + jarea - inter) > thr;
-}
-
-// Class-aware greedy NMS + post-NMS keep + postprocess, one 1024-thread block per image, walking the score-sorted pool in chunks of
-// 64 boxes.  Per chunk:
+// Class-aware greedy NMS + post-NMS keep + postprocess, one 1024-thread block per image: block_walk (nms_walk.h) over the score-sorted
+// pool in chunks of 64 boxes.  Per chunk:
 //   1  suppression by the boxes kept in EARLIER chunks: thread (box b = t & 63, slice t >> 6) tests box b against every 16th kept
 //      box (class first; the kept box is one broadcast 16-byte load per wave), the 16 per-wave ballots are OR-ed through LDS;
 //   2  the 64 x 64 suppression bits inside the chunk (four pairs per thread);
@@ -701,138 +718,20 @@ __device__ __forceinline__ bool nms_overlap(float x1, float y1, float x2, float 
 //      writes the outputs; the walk stops as soon as the next chunk's best score is below the K-th kept score.
 // Only the chunks the walk visits cost anything (typically 3-10 of up to 79), and there is no B x pool x pool / 64 suppression
 // matrix in HBM: rounds 1-3 built that matrix for ALL chunk pairs in a separate launch (0.19 ms at the headline shape, 0.5 GB).
+// The overlap arithmetic (merge_math.h) is torchvision's nms: inter / (area_i + area_j - inter) > thr, no +1.
 __global__ __launch_bounds__(1024) void nms_kernel(const DecodeCfg cfg, const DecodeSeg* __restrict__ segs, const DecodeBuffers buf,
                                                    const ImageOut* __restrict__ img_out,
                                                    float* out_boxes, float* out_scores, int* out_classes, int* out_levels,
                                                    float* out_locations, int* out_cand, int* out_counts, int* status_out, int clear_cands) {
   extern __shared__ unsigned short kept_pos[];  // [pool_cap]: pool positions of the boxes kept so far
-  __shared__ unsigned long long s_part[16];
-  __shared__ unsigned s_d[64][2];                // suppression bits inside the chunk: word i = boxes of the chunk suppressed by box i
-  __shared__ float4 s_box4[64];
-  __shared__ int s_cls4[64];
-  __shared__ int s_kept_total, s_stop;
-  const int img = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  __shared__ BlockWalkLds s_walk;
+  const int img = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;  // img: the block's output slot
   unsigned n = buf.pool_count[img];
   if (n > (unsigned)cfg.pool_cap) n = cfg.pool_cap;
-  const int nw = (int)((n + 63) / 64);
-  const size_t base = (size_t)img * cfg.pool_cap;
-  const ImageOut io = img_out[segs[(size_t)img * cfg.nlevels].image];  // img: the block's output slot
-  const int K = cfg.post_nms_topk;
-  const float thr = cfg.nms_thresh;
-  const bool nms_on = thr > 0.f;
-  int kept_total = 0, nout = 0;  // wave 0 keeps the running state; kept_total is mirrored in LDS for the other waves
-  float kth = -1.f;
-  bool truncated = false;
-  if (t == 0) { s_kept_total = 0; s_stop = 0; }
-  __syncthreads();
-  for (int c = 0; c < nw; ++c) {
-    const unsigned b0 = c * 64;
-    // the chunk's boxes -> LDS (wave 0), suppression words cleared
-    if (wave == 0) {
-      const unsigned bi = b0 + lane;
-      if (bi < n) {
-        s_box4[lane] = *reinterpret_cast<const float4*>(buf.s_box + (base + bi) * 4);
-        s_cls4[lane] = buf.s_cls[base + bi];
-      } else {
-        s_box4[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
-        s_cls4[lane] = -1 - lane;  // matches nothing
-      }
-      s_d[lane][0] = 0u; s_d[lane][1] = 0u;
-    }
-    __syncthreads();
-    const int ktot = s_kept_total;
-    const float4 mb = s_box4[lane];
-    const int mc = s_cls4[lane];
-    bool sup = false;
-    if (nms_on) {
-      // 1: against the kept boxes of earlier chunks (kept box = the earlier, higher-scored one: "i" of the pair)
-      for (int k = wave; k < ktot; k += 16) {
-        const size_t kp = base + kept_pos[k];
-        if (buf.s_cls[kp] != mc) continue;
-        const float4 kb = *reinterpret_cast<const float4*>(buf.s_box + kp * 4);
-        const float karea = (kb.z - kb.x) * (kb.w - kb.y);
-        sup = sup || nms_overlap(kb.x, kb.y, kb.z, kb.w, karea, mb, thr);
-      }
-      // 2: inside the chunk: thread -> box i = t >> 4 against boxes j = 4 (t & 15) .. + 3, j > i
-      const int i = t >> 4, jq = t & 15;
-      const float4 ib = s_box4[i];
-      const int ic = s_cls4[i];
-      const float iarea = (ib.z - ib.x) * (ib.w - ib.y);
-      unsigned bits = 0u;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int j = 4 * jq + e;
-        if (j > i && s_cls4[j] == ic && nms_overlap(ib.x, ib.y, ib.z, ib.w, iarea, s_box4[j], thr)) bits |= 1u << (j & 31);
-      }
-      if (bits) atomicOr(&s_d[i][jq >> 3], bits);
-    }
-    const unsigned long long part = __ballot(sup);
-    if (lane == 0) s_part[wave] = part;
-    __syncthreads();
-    if (wave == 0) {
-      // 3: serial resolve + emit (the arithmetic and order of the former nms_reduce_kernel)
-      const unsigned bi = b0 + lane;
-      const bool valid = bi < n;
-      unsigned long long cur = 0ull;
-#pragma unroll
-      for (int w = 0; w < 16; ++w) cur |= s_part[w];
-      if (n - b0 < 64u) cur |= ~0ull << (n - b0);
-      const unsigned long long d = ((unsigned long long)s_d[lane][1] << 32) | (unsigned long long)s_d[lane][0];
-      unsigned long long keptmask = 0ull;
-      for (int b = 0; b < 64; ++b) {
-        const unsigned long long db = shfl_u64(d, b);
-        if (!((cur >> b) & 1ull)) {
-          keptmask |= 1ull << b;
-          cur |= db;
-        }
-      }
-      const int nk = __popcll(keptmask);
-      const bool is_kept = (keptmask >> lane) & 1ull;
-      const int rank = kept_total + __popcll(keptmask & ((1ull << lane) - 1ull));
-      if (is_kept) kept_pos[rank] = (unsigned short)bi;
-      const float score = valid ? buf.s_score[base + bi] : 0.f;
-      if (K > 0 && kth < 0.f && kept_total + nk >= K) {
-        const unsigned long long sel = __ballot(is_kept && rank == K - 1);
-        const int src = __ffsll((long long)sel) - 1;
-        kth = __shfl(score, src);
-      }
-      bool emit = is_kept && (K <= 0 || rank < K || score >= kth);
-      float bx1 = 0.f, by1 = 0.f, bx2 = 0.f, by2 = 0.f;
-      if (emit) {
-        bx1 = mb.x * io.sx; by1 = mb.y * io.sy;
-        bx2 = mb.z * io.sx; by2 = mb.w * io.sy;
-        bx1 = fminf(fmaxf(bx1, 0.f), io.out_w); by1 = fminf(fmaxf(by1, 0.f), io.out_h);
-        bx2 = fminf(fmaxf(bx2, 0.f), io.out_w); by2 = fminf(fmaxf(by2, 0.f), io.out_h);
-        emit = (bx2 - bx1) > 0.f && (by2 - by1) > 0.f;
-      }
-      const unsigned long long em = __ballot(emit);
-      const int slot = nout + __popcll(em & ((1ull << lane) - 1ull));
-      if (emit) {
-        if (slot < cfg.max_out) {
-          const size_t o = (size_t)img * cfg.max_out + slot;
-          out_boxes[o * 4 + 0] = bx1; out_boxes[o * 4 + 1] = by1; out_boxes[o * 4 + 2] = bx2; out_boxes[o * 4 + 3] = by2;
-          out_scores[o] = score;
-          out_classes[o] = mc;
-          out_levels[o] = buf.s_level[base + bi];
-          out_locations[o * 2 + 0] = buf.s_loc[(base + bi) * 2 + 0];
-          out_locations[o * 2 + 1] = buf.s_loc[(base + bi) * 2 + 1];
-          out_cand[o] = (int)buf.s_ord[base + bi];
-        } else {
-          truncated = true;
-        }
-      }
-      nout += __popcll(em);
-      kept_total += nk;
-      bool stop = false;
-      if (K > 0 && kept_total >= K && c + 1 < nw) {
-        const float next_score = buf.s_score[base + b0 + 64];
-        stop = next_score < kth;
-      }
-      if (lane == 0) { s_kept_total = kept_total; s_stop = stop ? 1 : 0; }
-    }
-    __syncthreads();
-    if (s_stop) break;
-  }
+  const DecodeWalkSrc src = {buf, (size_t)img * cfg.pool_cap, img_out[segs[(size_t)img * cfg.nlevels].image],
+                             out_boxes, out_scores, out_classes, out_levels, out_locations, out_cand};
+  bool truncated;
+  const int nout = block_walk(s_walk, kept_pos, n, cfg.nms_thresh, cfg.post_nms_topk, cfg.max_out, src, &truncated);
   if (wave == 0) {
     if (__any(truncated) && lane == 0) atomicOr(buf.status, 2);
     if (lane == 0) out_counts[img] = nout < cfg.max_out ? nout : cfg.max_out;

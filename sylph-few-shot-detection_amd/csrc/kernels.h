@@ -104,13 +104,14 @@ int launch_merge_views(int n_src, const int* src_off, const int* src_views, cons
 // pool / MERGE_LARGE_CHUNK chunks (DESIGN: 6.1 s at 262 144 rows, about 100 s at the cap by extrapolation, not measured).
 constexpr int MERGE_LARGE_POOL_CAP = 1048576;
 constexpr int MERGE_LARGE_SORT_TILE = 2048;  // keys one block sorts in LDS; the sorted length is a power of two of at least one tile
-constexpr int MERGE_LARGE_CHUNK = 64;        // boxes per step of a segment's walk, as in merge_views_kernel
+constexpr int MERGE_LARGE_CHUNK = 64;        // boxes per step of a segment's walk: the chunk of nms_walk.h
 constexpr int MERGE_LARGE_KEPT_LDS = 2048;   // kept boxes of a segment that stay in LDS; later ones spill to the workspace
-// merge_large_layout(...) is THE workspace layout -- launch, the host check, sylph_merge_views_large_bytes all call it.  bytes = -1: refused
-// (a non-positive argument, or n_views * max_in does not fit a row index).  Every part starts 16-byte aligned.
-struct MergeLargeLayout { long long bytes, rows, P, keys_off, kbox_off, kept_off, bounds_off; };
-inline MergeLargeLayout merge_large_layout(int n_src, int n_views, int max_in) {
-  MergeLargeLayout L = {-1, 0, 0, 0, 0, 0, 0};
+// merge_large_layout(...) is THE workspace layout -- launch, the host check, sylph_merge_views_large_bytes all call it -- and with `stitch`
+// that of sylph_stitch_views, which is never below the large merge's.  bytes = -1: refused (a non-positive argument, or n_views * max_in
+// does not fit a row index).  Every part starts 16-byte aligned; an offset of the other layout is 0
+struct MergeLargeLayout { long long bytes, rows, P, keys_off, kbox_off, kept_off, ubox_off, meta_off, row_off, outu_off, outc_off, bounds_off; };
+inline MergeLargeLayout merge_large_layout(int n_src, int n_views, int max_in, bool stitch = false) {
+  MergeLargeLayout L = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (n_src <= 0 || n_views <= 0 || max_in <= 0 || (long long)n_views * max_in >= (1LL << 31)) return L;
   L.rows = (long long)n_views * max_in;
   L.P = MERGE_LARGE_SORT_TILE;
@@ -118,8 +119,19 @@ inline MergeLargeLayout merge_large_layout(int n_src, int n_views, int max_in) {
   const auto up16 = [](long long v) { return (v + 15) / 16 * 16; };
   L.keys_off = 0;                                  // P 128-bit keys
   L.kbox_off = L.keys_off + 16 * L.P;              // rows float4: the kept boxes a segment spills
-  L.kept_off = L.kbox_off + 16 * L.rows;           // rows bytes: kept or not, per sorted position
-  L.bounds_off = L.kept_off + up16(L.rows);        // n_src x (begin, end) of every source's kept run
+  long long end = L.kbox_off + 16 * L.rows;
+  if (!stitch) {
+    L.kept_off = end;                              // rows bytes: kept or not, per sorted position
+    end = L.kept_off + up16(L.rows);
+  } else {
+    L.ubox_off = end;                              // rows float4: the kept boxes' union boxes
+    L.meta_off = L.ubox_off + 16 * L.rows;         // rows words: their cut bit, dropped bit and count
+    L.row_off = L.meta_off + up16(4 * L.rows);     // rows words: the input row of each
+    L.outu_off = L.row_off + up16(4 * L.rows);     // rows float4: per INPUT row, the union box of a survivor
+    L.outc_off = L.outu_off + 16 * L.rows;         // rows ints: per input row, 0 or 1 + what the survivor absorbed
+    end = L.outc_off + up16(4 * L.rows);
+  }
+  L.bounds_off = end;                              // n_src x (begin, end) of every source's run of kept rows / survivors
   L.bytes = L.bounds_off + up16(8LL * n_src);
   return L;
 }
@@ -131,26 +143,7 @@ int launch_merge_views_large(int n_src, int n_views, const MergeView* views, int
 // segment walk that absorbs cut fragments into their keeper's union box (rule 4a), a second walk over the kept rows (rule 4b).
 // StitchView: what rule 0 needs beyond MergeView -- the crop's height and the source's size
 struct StitchView { float h, src_w, src_h; };
-// stitch_layout(...) is THE workspace layout of sylph_stitch_views, refused like merge_large_layout.  Never below the large merge's
-struct StitchLayout { long long bytes, rows, P, keys_off, kbox_off, ubox_off, meta_off, row_off, outu_off, outc_off, bounds_off; };
-inline StitchLayout stitch_layout(int n_src, int n_views, int max_in) {
-  StitchLayout L = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const MergeLargeLayout M = merge_large_layout(n_src, n_views, max_in);
-  if (M.bytes < 0) return L;
-  L.rows = M.rows;
-  L.P = M.P;
-  const auto up16 = [](long long v) { return (v + 15) / 16 * 16; };
-  L.keys_off = 0;                                  // P 128-bit keys
-  L.kbox_off = L.keys_off + 16 * L.P;              // rows float4: the kept boxes a segment spills
-  L.ubox_off = L.kbox_off + 16 * L.rows;           // rows float4: their union boxes
-  L.meta_off = L.ubox_off + 16 * L.rows;           // rows words: their cut bit, dropped bit and count
-  L.row_off = L.meta_off + up16(4 * L.rows);       // rows words: the input row of each
-  L.outu_off = L.row_off + up16(4 * L.rows);       // rows float4: per INPUT row, the union box of a survivor
-  L.outc_off = L.outu_off + 16 * L.rows;           // rows ints: per input row, 0 or 1 + what the survivor absorbed
-  L.bounds_off = L.outc_off + up16(4 * L.rows);    // n_src x (begin, end) of every source's run of survivors
-  L.bytes = L.bounds_off + up16(8LL * n_src);
-  return L;
-}
+inline MergeLargeLayout stitch_layout(int n_src, int n_views, int max_in) { return merge_large_layout(n_src, n_views, max_in, true); }
 // status as launch_merge_views_large; sviews [n_views]; stitch_thr in (0, 1], border_px >= 0 (the host has checked)
 int launch_stitch_views(int n_src, int n_views, const MergeView* views, const StitchView* sviews, int max_in, const float* boxes,
                         const float* scores, const int* classes, const int* counts, float nms_thresh, float stitch_thr, float border_px, int K,

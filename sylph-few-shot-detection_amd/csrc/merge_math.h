@@ -1,6 +1,6 @@
-// The arithmetic the view merges share (merge_views.hip, merge_views_large.hip): the order key of a score, rule 1's way back to source
-// coordinates, the overlap test of rule 4 (include/sylph_hip.h, sylph_merge_views) and the tests of the stitching merge
-// (sylph_stitch_views).  Both files are built without FMA contraction.
+// The arithmetic decode NMS and the view merges share (detect.hip, merge_views.hip, merge_views_large.hip, through nms_walk.h): the order
+// key of a score, rule 1's way back to source coordinates, the overlap test of NMS and of rule 4 (include/sylph_hip.h, sylph_merge_views),
+// the 64-bit shuffle and the tests of the stitching merge (sylph_stitch_views).  All three files are built without FMA contraction.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -24,7 +24,7 @@ __device__ __forceinline__ float4 merge_source_box(const float* __restrict__ box
   return make_float4(x1 + mv.x0, b.y + mv.y0, x2 + mv.x0, b.w + mv.y0);
 }
 
-// IoU > thr for two boxes of the same class: the arithmetic of nms_overlap (detect.hip)
+// IoU > thr for two boxes of the same class: torchvision's nms arithmetic (inter / (area_i + area_j - inter), no +1)
 __device__ __forceinline__ bool merge_overlap(float x1, float y1, float x2, float y2, float iarea, float4 b, float thr) {
   const float xx1 = fmaxf(x1, b.x), yy1 = fmaxf(y1, b.y);
   const float xx2 = fminf(x2, b.z), yy2 = fminf(y2, b.w);

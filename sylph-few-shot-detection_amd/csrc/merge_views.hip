@@ -5,15 +5,40 @@
 //   2  bitonic sort of the keys in LDS, descending: by score, ties to the lower view, then to the lower row (the keys are unique)
 //   3  boxes back to source coordinates, in sorted order, into LDS: flipped (x1, x2) <- (w - x2, w - x1); then x += x0, y += y0 -- plain
 //      fp32 operations in that order, no clip (this file is built without FMA contraction, like detect.hip)
-//   4  the walk of nms_kernel (detect.hip) over the sorted pool in chunks of 64 boxes: ballots against the boxes kept in earlier chunks,
-//      a 64 x 64 bit matrix inside the chunk, a serial resolve in wave 0; same overlap arithmetic, same post-NMS keep rule
+//   4  block_walk (nms_walk.h), the function nms_kernel (detect.hip) runs, over the sorted pool in chunks of 64 boxes: ballots against the
+//      boxes kept in earlier chunks, a 64 x 64 bit matrix inside the chunk, a serial resolve in wave 0; same overlap arithmetic, same
+//      post-NMS keep rule
 //   5  emit: box, score, class and the (view, row) the detection came from
 // Nothing is kept between calls and no atomic touches global memory.
 #include "common.h"
 #include "kernels.h"
-#include "merge_math.h"
+#include "nms_walk.h"
 
 namespace sylph {
+
+// what block_walk (nms_walk.h) asks of the pool in LDS: sorted position p holds row ~(low word of keys[p]); the box goes out as it is
+struct MergeWalkSrc {
+  const unsigned long long* keys;
+  const float4* s_box;
+  const int* s_cls;
+  const float* scores;
+  int max_in;
+  float *out_boxes, *out_scores;
+  int *out_classes, *out_view, *out_row;
+  __device__ __forceinline__ unsigned row(unsigned p) const { return ~(unsigned)(keys[p] & 0xffffffffull); }
+  __device__ __forceinline__ float4 box(unsigned p) const { return s_box[p]; }
+  __device__ __forceinline__ int cls(unsigned p) const { return s_cls[p]; }
+  __device__ __forceinline__ float score(unsigned p) const { return scores[row(p)]; }
+  __device__ __forceinline__ bool shape(float4&) const { return true; }
+  __device__ __forceinline__ void write(size_t o, unsigned p, float4 b, float score, int cls) const {
+    const unsigned g = row(p);
+    out_boxes[o * 4 + 0] = b.x; out_boxes[o * 4 + 1] = b.y; out_boxes[o * 4 + 2] = b.z; out_boxes[o * 4 + 3] = b.w;
+    out_scores[o] = score;
+    out_classes[o] = cls;
+    out_view[o] = (int)(g / (unsigned)max_in);
+    out_row[o] = (int)(g % (unsigned)max_in);
+  }
+};
 
 // dynamic LDS: keys [pool_p2] u64 | boxes [pool_p2] float4 | classes [pool_p2] int | view prefix [max_views + 1] int | kept [pool_p2] u16
 __global__ __launch_bounds__(1024) void merge_views_kernel(const int* __restrict__ src_off, const int* __restrict__ src_views,
@@ -28,11 +53,7 @@ __global__ __launch_bounds__(1024) void merge_views_kernel(const int* __restrict
   int* s_cls = reinterpret_cast<int*>(merge_lds + (size_t)24 * pool_p2);
   int* s_pref = s_cls + pool_p2;
   unsigned short* kept_pos = reinterpret_cast<unsigned short*>(s_pref + max_views + 1);
-  __shared__ unsigned long long s_part[16];
-  __shared__ unsigned s_d[64][2];
-  __shared__ float4 s_box4[64];
-  __shared__ int s_cls4[64];
-  __shared__ int s_kept_total, s_stop;
+  __shared__ BlockWalkLds s_walk;
   const int src = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int v0 = src_off[src], nv = min(src_off[src + 1] - v0, max_views);
   // 1: rows per view (a count outside [0, max_in] is clamped), their prefix, the keys
@@ -81,110 +102,10 @@ __global__ __launch_bounds__(1024) void merge_views_kernel(const int* __restrict
     s_box[i] = merge_source_box(boxes, views, g, (unsigned)max_in);
     s_cls[i] = classes[g];
   }
-  if (t == 0) { s_kept_total = 0; s_stop = 0; }
-  __syncthreads();
-  // 4 + 5: the chunk walk of nms_kernel
-  const int nw = (int)((n + 63) / 64);
-  const bool nms_on = thr > 0.f;
-  int kept_total = 0, nout = 0;  // wave 0 keeps the running state; kept_total is mirrored in LDS for the other waves
-  float kth = 0.f;
-  bool have_kth = false, truncated = false;
-  for (int c = 0; c < nw; ++c) {
-    const unsigned b0 = c * 64;
-    if (wave == 0) {
-      const unsigned bi = b0 + lane;
-      if (bi < n) {
-        s_box4[lane] = s_box[bi];
-        s_cls4[lane] = s_cls[bi];
-      } else {
-        s_box4[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
-        s_cls4[lane] = -1 - lane;  // matches nothing
-      }
-      s_d[lane][0] = 0u; s_d[lane][1] = 0u;
-    }
-    __syncthreads();
-    const int ktot = s_kept_total;
-    const float4 mb = s_box4[lane];
-    const int mc = s_cls4[lane];
-    bool sup = false;
-    if (nms_on) {
-      for (int k = wave; k < ktot; k += 16) {
-        const int kp = kept_pos[k];
-        if (s_cls[kp] != mc) continue;
-        const float4 kb = s_box[kp];
-        const float karea = (kb.z - kb.x) * (kb.w - kb.y);
-        sup = sup || merge_overlap(kb.x, kb.y, kb.z, kb.w, karea, mb, thr);
-      }
-      const int i = t >> 4, jq = t & 15;
-      const float4 ib = s_box4[i];
-      const int ic = s_cls4[i];
-      const float iarea = (ib.z - ib.x) * (ib.w - ib.y);
-      unsigned bits = 0u;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int j = 4 * jq + e;
-        if (j > i && s_cls4[j] == ic && merge_overlap(ib.x, ib.y, ib.z, ib.w, iarea, s_box4[j], thr)) bits |= 1u << (j & 31);
-      }
-      if (bits) atomicOr(&s_d[i][jq >> 3], bits);
-    }
-    const unsigned long long part = __ballot(sup);
-    if (lane == 0) s_part[wave] = part;
-    __syncthreads();
-    if (wave == 0) {
-      const unsigned bi = b0 + lane;
-      const bool valid = bi < n;
-      unsigned long long cur = 0ull;
-#pragma unroll
-      for (int w = 0; w < 16; ++w) cur |= s_part[w];
-      if (n - b0 < 64u) cur |= ~0ull << (n - b0);
-      const unsigned long long d = ((unsigned long long)s_d[lane][1] << 32) | (unsigned long long)s_d[lane][0];
-      unsigned long long keptmask = 0ull;
-      for (int b = 0; b < 64; ++b) {
-        const unsigned long long db = merge_shfl_u64(d, b);
-        if (!((cur >> b) & 1ull)) {
-          keptmask |= 1ull << b;
-          cur |= db;
-        }
-      }
-      const int nk = __popcll(keptmask);
-      const bool is_kept = (keptmask >> lane) & 1ull;
-      const int rank = kept_total + __popcll(keptmask & ((1ull << lane) - 1ull));
-      if (is_kept) kept_pos[rank] = (unsigned short)bi;
-      const unsigned g = valid ? ~(unsigned)(keys[bi] & 0xffffffffull) : 0u;
-      const float score = valid ? scores[g] : 0.f;
-      if (K > 0 && !have_kth && kept_total + nk >= K) {
-        const unsigned long long sel = __ballot(is_kept && rank == K - 1);
-        const int srcl = __ffsll((long long)sel) - 1;
-        kth = __shfl(score, srcl);
-        have_kth = true;
-      }
-      const bool emit = is_kept && (K <= 0 || rank < K || score >= kth);
-      const unsigned long long em = __ballot(emit);
-      const int slot = nout + __popcll(em & ((1ull << lane) - 1ull));
-      if (emit) {
-        if (slot < max_out) {
-          const size_t o = (size_t)src * max_out + slot;
-          out_boxes[o * 4 + 0] = mb.x; out_boxes[o * 4 + 1] = mb.y; out_boxes[o * 4 + 2] = mb.z; out_boxes[o * 4 + 3] = mb.w;
-          out_scores[o] = score;
-          out_classes[o] = mc;
-          out_view[o] = (int)(g / (unsigned)max_in);
-          out_row[o] = (int)(g % (unsigned)max_in);
-        } else {
-          truncated = true;
-        }
-      }
-      nout += __popcll(em);
-      kept_total += nk;
-      bool stop = false;
-      if (K > 0 && kept_total >= K && c + 1 < nw) {  // nothing below the K-th kept score can be emitted any more
-        const float next_score = scores[~(unsigned)(keys[b0 + 64] & 0xffffffffull)];
-        stop = next_score < kth;
-      }
-      if (lane == 0) { s_kept_total = kept_total; s_stop = stop ? 1 : 0; }
-    }
-    __syncthreads();
-    if (s_stop) break;
-  }
+  // 4 + 5 (the walk's first barrier ends step 3)
+  const MergeWalkSrc wsrc = {keys, s_box, s_cls, scores, max_in, out_boxes, out_scores, out_classes, out_view, out_row};
+  bool truncated;
+  const int nout = block_walk(s_walk, kept_pos, n, thr, K, max_out, wsrc, &truncated);
   if (wave == 0) {
     if (__any(truncated) && lane == 0) *status = 2;  // (every truncated source stores the same word: no atomic)
     if (lane == 0) out_counts[src] = nout < max_out ? nout : max_out;

@@ -7,8 +7,9 @@
 //      in LDS for the strides below a tile, one compare-exchange per thread in global memory for the strides above.  The keys are
 //      unique, so the order is (source, class, score descending, view, row) whatever the network does
 //   3  NMS: the block of 64 sorted positions walks every segment that STARTS among them (most blocks find none and leave), in chunks of
-//      MERGE_LARGE_CHUNK = 64 boxes as step 4 of merge_views_kernel: ballots against the boxes kept in earlier chunks, a 64 x 64 bit
-//      matrix inside the chunk, a serial resolve in wave 0.  The first MERGE_LARGE_KEPT_LDS kept boxes of a segment stay in LDS, later
+//      MERGE_LARGE_CHUNK = 64 boxes with the pieces of nms_walk.h that step 4 of merge_views_kernel is made of: ballots against the boxes
+//      kept in earlier chunks (walk_kept_groups), a 64 x 64 bit matrix inside the chunk (walk_fill_matrix, on IoU alone: a segment is one
+//      class), a serial resolve in wave 0 (walk_resolve).  The first MERGE_LARGE_KEPT_LDS kept boxes of a segment stay in LDS, later
 //      ones spill to the workspace at (segment start + rank): a segment keeps at most as many boxes as it holds.  The waves take the
 //      kept boxes in groups of 64 and skip the division for a box that meets none of the chunk's.  With K > 0 a segment stops once it
 //      has kept K boxes and the scores have fallen below its K-th: rule 5 cannot emit what lies behind
@@ -17,13 +18,12 @@
 //      so every thread decides from its own row and its neighbour's; the thread of the last emitted row writes the count
 #include "common.h"
 #include "kernels.h"
-#include "merge_math.h"
+#include "nms_walk.h"
 
 namespace sylph {
 
 namespace {
 
-constexpr unsigned long long KEY_NONE = ~0ull;
 constexpr int TILE = MERGE_LARGE_SORT_TILE, CHUNK = MERGE_LARGE_CHUNK, KEPT_LDS = MERGE_LARGE_KEPT_LDS;
 static_assert(CHUNK == 64 && KEPT_LDS % 64 == 0, "one chunk is one wave's ballot; the kept boxes are compared in groups of 64");
 static_assert(TILE == 2048, "the tile sort gives each of its 1024 threads one pair");
@@ -101,15 +101,7 @@ __global__ __launch_bounds__(1024) void merge_large_nms_kernel(const ulonglong2*
   __shared__ int s_kept_total, s_last;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const unsigned p0 = blockIdx.x * 64u;
-  if (wave == 0) {
-    const unsigned p = p0 + lane;  // (P is a multiple of 64)
-    const unsigned long long hi = keys[p].x;
-    const bool start = hi != KEY_NONE && (p == 0 || keys[p - 1].x != hi);
-    const unsigned long long m = __ballot(start);
-    if (lane == 0) s_starts = m;
-  }
-  __syncthreads();
-  unsigned long long starts = s_starts;
+  unsigned long long starts = segment_starts(keys, p0, &s_starts);
   while (starts) {
     const unsigned seg0 = p0 + (unsigned)(__ffsll((long long)starts) - 1);
     starts &= starts - 1;
@@ -121,59 +113,25 @@ __global__ __launch_bounds__(1024) void merge_large_nms_kernel(const ulonglong2*
     for (unsigned c = 0;; ++c) {
       const unsigned long long pos = (unsigned long long)seg0 + 64ull * c + (unsigned)lane;
       if (wave == 0) {
-        bool valid = false;
-        float4 bx = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (pos < P) {
-          const ulonglong2 k = keys[pos];
-          if (k.x == seg_hi) {  // (the segment is a run of the sorted keys: the valid lanes of a chunk are its first ones)
-            valid = true;
-            ord = (unsigned)(k.y >> 32);
-            const unsigned g = (unsigned)(k.y & 0xffffffffull);
-            bx = merge_source_box(boxes, views, g, (unsigned)max_in);
-          }
-        }
-        s_box4[lane] = bx;
-        s_d[lane][0] = 0u; s_d[lane][1] = 0u;
-        const unsigned long long vm = __ballot(valid);
-        if (lane == 0) s_valid = vm;
+        unsigned long long lo;
+        float4 bx;
+        segment_chunk_load(keys, P, pos, seg_hi, boxes, views, max_in, lane, s_box4, s_d, &s_valid, &lo, &bx);
+        ord = (unsigned)(lo >> 32);
       }
       __syncthreads();
       const int ktot = s_kept_total;
       const unsigned long long vmask = s_valid;
       const float4 mb = s_box4[lane];
       bool sup = false;
-      // the kept boxes in groups of 64, a group per wave: a spilled group comes in with one coalesced load and is then read like the LDS
-      // list, one box for all lanes.  A box that no lane's box intersects is done after the intersection (inter = 0 never suppresses:
-      // thr > 0), so the division runs only for the few kept boxes near the chunk's
-      for (int base = wave * 64; base < ktot; base += 16 * 64) {
-        const int cnt = ktot - base < 64 ? ktot - base : 64;
-        const float4* grp = s_kept + base;  // (KEPT_LDS is a multiple of 64: a group is on one side)
-        if (base >= KEPT_LDS) {
-          if (lane < cnt) s_stage[wave][lane] = kbox[(size_t)seg0 + base + lane];
-          grp = s_stage[wave];
-        }
-        float4 next = grp[0];
-        for (int j = 0; j < cnt; ++j) {
-          const float4 kb = next;
-          if (j + 1 < cnt) next = grp[j + 1];  // (in flight under this box's test)
-          const float iw = fmaxf(0.f, fminf(kb.z, mb.z) - fmaxf(kb.x, mb.x)), ih = fmaxf(0.f, fminf(kb.w, mb.w) - fmaxf(kb.y, mb.y));
-          if (__any(iw * ih > 0.f)) {
-            const float karea = (kb.z - kb.x) * (kb.w - kb.y);
-            sup = sup || merge_overlap(kb.x, kb.y, kb.z, kb.w, karea, mb, thr);
-          }
-        }
-      }
+      walk_kept_groups<true, false>(ktot, lane, wave, mb, s_kept, kbox + seg0, &s_stage[0][0], nullptr, nullptr, nullptr,
+                                    [&](int, float4 kb, unsigned) {
+                                      const float karea = (kb.z - kb.x) * (kb.w - kb.y);
+                                      sup = sup || merge_overlap(kb.x, kb.y, kb.z, kb.w, karea, mb, thr);
+                                    });
       {
-        const int i = t >> 4, jq = t & 15;
-        const float4 ib = s_box4[i];
+        const float4 ib = s_box4[t >> 4];
         const float iarea = (ib.z - ib.x) * (ib.w - ib.y);
-        unsigned bits = 0u;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int j = 4 * jq + e;
-          if (j > i && merge_overlap(ib.x, ib.y, ib.z, ib.w, iarea, s_box4[j], thr)) bits |= 1u << (j & 31);
-        }
-        if (bits) atomicOr(&s_d[i][jq >> 3], bits);
+        walk_fill_matrix(s_d, t, [&](int, int j) { return merge_overlap(ib.x, ib.y, ib.z, ib.w, iarea, s_box4[j], thr); });
       }
       const unsigned long long part = __ballot(sup);
       if (lane == 0) s_part[wave] = part;
@@ -182,15 +140,7 @@ __global__ __launch_bounds__(1024) void merge_large_nms_kernel(const ulonglong2*
         unsigned long long cur = ~vmask;  // the lanes past the segment's end are never kept
 #pragma unroll
         for (int w = 0; w < 16; ++w) cur |= s_part[w];
-        const unsigned long long d = ((unsigned long long)s_d[lane][1] << 32) | (unsigned long long)s_d[lane][0];
-        unsigned long long keptmask = 0ull;
-        for (int b = 0; b < 64; ++b) {
-          const unsigned long long db = merge_shfl_u64(d, b);
-          if (!((cur >> b) & 1ull)) {
-            keptmask |= 1ull << b;
-            cur |= db;
-          }
-        }
+        const unsigned long long keptmask = walk_resolve<false>(cur, s_d, lane, nullptr);
         const bool is_kept = (keptmask >> lane) & 1ull;
         const int rank = kept_total + __popcll(keptmask & ((1ull << lane) - 1ull));
         if (is_kept) {
@@ -198,11 +148,7 @@ __global__ __launch_bounds__(1024) void merge_large_nms_kernel(const ulonglong2*
           else kbox[(size_t)seg0 + rank] = mb;
         }
         if (is_kept) kept[pos] = 1;
-        if (K > 0 && !have_kth && kept_total + __popcll(keptmask) >= K) {
-          const unsigned long long sel = __ballot(is_kept && rank == K - 1);
-          kth_ord = __shfl(ord, __ffsll((long long)sel) - 1);
-          have_kth = true;
-        }
+        walk_select_kth(K, kept_total, keptmask, is_kept, rank, ord, &kth_ord, &have_kth);
         kept_total += __popcll(keptmask);
         bool last = vmask != ~0ull;
         if (!last && have_kth && lane == 0) {  // does the next chunk begin below the K-th kept score?
@@ -220,14 +166,18 @@ __global__ __launch_bounds__(1024) void merge_large_nms_kernel(const ulonglong2*
   }
 }
 
-// 4: the keys of the second sort.  nms_on == 0: every row is kept (thr <= 0), the NMS kernel did not run
+// 4: the keys of the second sort: hi = source for a row that stays.  The large merge: sorted position i stays when kept[i] is set, or
+// nms_on == 0 (thr <= 0: every row stays, the NMS kernel did not run).  STITCH: a row stays when cnt [n_rows], indexed by INPUT row, holds
+// its 1 + what the survivor absorbed and not 0
+template <bool STITCH>
 __global__ __launch_bounds__(256) void merge_large_rekey_kernel(ulonglong2* __restrict__ keys, unsigned P, const unsigned char* __restrict__ kept,
-                                                                int nms_on) {
+                                                                int nms_on, const int* __restrict__ cnt) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   if (i >= P) return;
   ulonglong2 k = keys[i];
   if (k.x == KEY_NONE) return;
-  if (!nms_on || kept[i]) k.x >>= 32;
+  // (the test stays inside the if: held in a bool first, hipcc of ROCm 7 emitted a kept row's k.y as all ones on the nms_on path)
+  if (STITCH ? cnt[(unsigned)(k.y & 0xffffffffull)] != 0 : (!nms_on || kept[i])) k.x >>= 32;
   else k = make_ulonglong2(KEY_NONE, KEY_NONE);
   keys[i] = k;
 }
@@ -242,12 +192,16 @@ __global__ __launch_bounds__(256) void merge_large_bounds_kernel(const ulonglong
   if (i + 1 == P || keys[i + 1].x != hi) bounds[2 * hi + 1] = i + 1;
 }
 
-// 5: thread j of source blockIdx.x / blocks_per_src looks at the source's j-th kept row, j <= max_out (row max_out only tells that the source is truncated)
+// 5: thread j of source blockIdx.x / blocks_per_src looks at the source's j-th kept row, j <= max_out (row max_out only tells that the source is truncated).
+// STITCH: the rows are the survivors, the same prefix rule on their own scores; the box is the union box ubox [n_rows] of the input row,
+// out_stitched its count cnt [n_rows] (neither is touched otherwise)
+template <bool STITCH>
 __global__ __launch_bounds__(256) void merge_large_emit_kernel(const ulonglong2* __restrict__ keys, const unsigned* __restrict__ bounds,
                                                                const MergeView* __restrict__ views, int max_in, const float* __restrict__ boxes,
+                                                               const float4* __restrict__ ubox, const int* __restrict__ cnt,
                                                                const float* __restrict__ scores, const int* __restrict__ classes, int K,
                                                                int max_out, int blocks_per_src, float* out_boxes, float* out_scores, int* out_classes, int* out_view,
-                                                               int* out_row, int* out_counts, int* status) {
+                                                               int* out_row, int* out_stitched, int* out_counts, int* status) {
   const int src = blockIdx.x / blocks_per_src;
   const unsigned j = (blockIdx.x % blocks_per_src) * 256u + threadIdx.x;
   const unsigned beg = bounds[2 * src], n = bounds[2 * src + 1] - beg;
@@ -268,13 +222,14 @@ __global__ __launch_bounds__(256) void merge_large_emit_kernel(const ulonglong2*
     out_counts[src] = max_out;
     return;
   }
-  const float4 b = merge_source_box(boxes, views, g, (unsigned)max_in);
+  const float4 b = STITCH ? ubox[g] : merge_source_box(boxes, views, g, (unsigned)max_in);
   const size_t o = (size_t)src * max_out + j;
   out_boxes[o * 4 + 0] = b.x; out_boxes[o * 4 + 1] = b.y; out_boxes[o * 4 + 2] = b.z; out_boxes[o * 4 + 3] = b.w;
   out_scores[o] = score;
   out_classes[o] = classes[g];
   out_view[o] = (int)(g / (unsigned)max_in);
   out_row[o] = (int)(g % (unsigned)max_in);
+  if (STITCH) out_stitched[o] = cnt[g];
   if (!next) out_counts[src] = (int)j + 1;
 }
 
@@ -294,7 +249,10 @@ void sort_keys(ulonglong2* keys, unsigned P, hipStream_t s) {
 //       MERGE_LARGE_KEPT_LDS, spilled beyond), and there is no early stop: a row behind the K-th kept score can still grow an emitted box.
 //       Then rule 4b over the segment's kept boxes, 64 ranks a step, against the frozen U of the earlier survivors; then every survivor
 //       leaves U and 1 + its count at its INPUT row
-//   4s  stitch_rekey_kernel: a row with a count survives; the same sort; launch 5's bounds; stitch_emit_kernel: launch 5's emit with U as the box
+//   4s  launches 4 and 5 in their STITCH instantiation: a row with a count survives; the same sort and bounds; the emit with U as the box
+// Both rules run on the walk's pieces of nms_walk.h: the segment prologue and chunk load of launch 3, walk_kept_groups with a meta word per
+// kept box and a body that records the lowest matching rank, walk_fill_matrix on stitch_match (4a) or stitch_covered (4b), and the
+// walk_resolve that also names the first kept box of the chunk holding the lane's bit.
 // The hull is a min / max, the counts are integers: no order of arrival can change a bit.
 
 constexpr unsigned META_CUT = 0x80000000u, META_DROPPED = 0x40000000u, META_COUNT = 0x3fffffffu;
@@ -359,15 +317,7 @@ __global__ __launch_bounds__(1024) void stitch_walk_kernel(const ulonglong2* __r
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const unsigned p0 = blockIdx.x * 64u;
   const unsigned long long below = (1ull << lane) - 1ull;
-  if (wave == 0) {
-    const unsigned p = p0 + lane;  // (P is a multiple of 64)
-    const unsigned long long hi = keys[p].x;
-    const bool start = hi != KEY_NONE && (p == 0 || keys[p - 1].x != hi);
-    const unsigned long long m = __ballot(start);
-    if (lane == 0) s_starts = m;
-  }
-  __syncthreads();
-  unsigned long long starts = s_starts;
+  unsigned long long starts = segment_starts(keys, p0, &s_starts);
   while (starts) {
     const unsigned seg0 = p0 + (unsigned)(__ffsll((long long)starts) - 1);
     starts &= starts - 1;
@@ -381,22 +331,16 @@ __global__ __launch_bounds__(1024) void stitch_walk_kernel(const ulonglong2* __r
       const unsigned long long pos = (unsigned long long)seg0 + 64ull * c + (unsigned)lane;
       unsigned g = 0u;
       if (wave == 0) {
-        bool valid = false, cut = false;
-        float4 bx = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (pos < P) {
-          const ulonglong2 k = keys[pos];
-          if (k.x == seg_hi) {  // (the segment is a run of the sorted keys: the valid lanes of a chunk are its first ones)
-            valid = true;
-            g = (unsigned)(k.y & 0xffffffffull);
-            bx = merge_source_box(boxes, views, g, (unsigned)max_in);
-            const unsigned v = g / (unsigned)max_in;
-            cut = stitch_cut(bx, views[v], sviews[v], border);
-          }
+        unsigned long long lo;
+        float4 bx;
+        bool cut = false;
+        if (segment_chunk_load(keys, P, pos, seg_hi, boxes, views, max_in, lane, s_box4, s_d, &s_valid, &lo, &bx)) {
+          g = (unsigned)(lo & 0xffffffffull);
+          const unsigned v = g / (unsigned)max_in;
+          cut = stitch_cut(bx, views[v], sviews[v], border);
         }
-        s_box4[lane] = bx;
-        s_d[lane][0] = 0u; s_d[lane][1] = 0u;
-        const unsigned long long vm = __ballot(valid), cm = __ballot(cut);
-        if (lane == 0) { s_valid = vm; s_cutm = cm; }
+        const unsigned long long cm = __ballot(cut);
+        if (lane == 0) s_cutm = cm;
       }
       __syncthreads();
       const int ktot = s_kept_total;
@@ -404,38 +348,15 @@ __global__ __launch_bounds__(1024) void stitch_walk_kernel(const ulonglong2* __r
       const float4 mb = s_box4[lane];
       const bool mcut = (cutm >> lane) & 1ull;
       int best = NO_KEEPER;  // the lowest rank this wave's groups hold of a kept box that matches the lane's (ranks ascend along the loop)
-      for (int base = wave * 64; base < ktot; base += 16 * 64) {
-        const int cnt = ktot - base < 64 ? ktot - base : 64;
-        const float4* grp = s_kept + base;  // (KEPT_LDS is a multiple of 64: a group is on one side)
-        const unsigned* gm = s_meta + base;
-        if (base >= KEPT_LDS) {
-          if (lane < cnt) {
-            s_stage[wave * 64 + lane] = kbox[(size_t)seg0 + base + lane];
-            s_stagem[wave * 64 + lane] = kmeta[(size_t)seg0 + base + lane];
-          }
-          grp = s_stage + wave * 64;
-          gm = s_stagem + wave * 64;
-        }
-        for (int j = 0; j < cnt; ++j) {
-          const float4 kb = grp[j];
-          const float iw = fmaxf(0.f, fminf(kb.z, mb.z) - fmaxf(kb.x, mb.x)), ih = fmaxf(0.f, fminf(kb.w, mb.w) - fmaxf(kb.y, mb.y));
-          if (__any(iw * ih > 0.f)) {  // (no intersection matches under neither test)
-            const bool pair_cut = mcut || (gm[j] & META_CUT);
-            if (best == NO_KEEPER && stitch_match(kb, mb, pair_cut, thr, sthr)) best = base + j;
-          }
-        }
-      }
+      walk_kept_groups<false, true>(ktot, lane, wave, mb, s_kept, kbox + seg0, s_stage, s_meta, kmeta + seg0, s_stagem,
+                                    [&](int r, float4 kb, unsigned meta) {
+                                      const bool pair_cut = mcut || (meta & META_CUT);
+                                      if (best == NO_KEEPER && stitch_match(kb, mb, pair_cut, thr, sthr)) best = r;
+                                    });
       {
-        const int i = t >> 4, jq = t & 15;
-        const float4 ib = s_box4[i];
-        const bool icut = (cutm >> i) & 1ull;
-        unsigned bits = 0u;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int j = 4 * jq + e;
-          if (j > i && stitch_match(ib, s_box4[j], icut || ((cutm >> j) & 1ull), thr, sthr)) bits |= 1u << (j & 31);
-        }
-        if (bits) atomicOr(&s_d[i][jq >> 3], bits);
+        const float4 ib = s_box4[t >> 4];
+        const bool icut = (cutm >> (t >> 4)) & 1ull;
+        walk_fill_matrix(s_d, t, [&](int, int j) { return stitch_match(ib, s_box4[j], icut || ((cutm >> j) & 1ull), thr, sthr); });
       }
       s_best[wave][lane] = best;
       __syncthreads();
@@ -443,18 +364,9 @@ __global__ __launch_bounds__(1024) void stitch_walk_kernel(const ulonglong2* __r
         int ext = NO_KEEPER;  // the keeper among the boxes kept in earlier chunks: they all rank below this chunk's
 #pragma unroll
         for (int w = 0; w < 16; ++w) ext = min(ext, s_best[w][lane]);
-        unsigned long long cur = ~vmask | __ballot(ext != NO_KEEPER);  // the lanes past the segment's end are never kept
-        const unsigned long long d = ((unsigned long long)s_d[lane][1] << 32) | (unsigned long long)s_d[lane][0];
-        unsigned long long keptmask = 0ull;
-        int ink = -1;  // the first box kept in this chunk that matches the lane's
-        for (int b = 0; b < 64; ++b) {
-          const unsigned long long db = merge_shfl_u64(d, b);
-          if (!((cur >> b) & 1ull)) {
-            keptmask |= 1ull << b;
-            cur |= db;
-            if (ink < 0 && ((db >> lane) & 1ull)) ink = b;
-          }
-        }
+        const unsigned long long cur = ~vmask | __ballot(ext != NO_KEEPER);  // the lanes past the segment's end are never kept
+        int ink;  // the first box kept in this chunk that matches the lane's
+        const unsigned long long keptmask = walk_resolve<true>(cur, s_d, lane, &ink);
         const bool valid = (vmask >> lane) & 1ull, is_kept = (keptmask >> lane) & 1ull;
         const int rank = kept_total + __popcll(keptmask & below);
         if (is_kept) {
@@ -506,33 +418,14 @@ __global__ __launch_bounds__(1024) void stitch_walk_kernel(const ulonglong2* __r
         const float4 mb = s_box4[lane];
         const bool mcut = (cutm >> lane) & 1ull;
         int best = NO_KEEPER;
-        for (int base = wave * 64; base < k0; base += 16 * 64) {  // (k0 is a multiple of 64: full groups)
-          const float4* grp = s_u + base;
-          const unsigned* gm = s_meta + base;
-          if (base >= KEPT_LDS) {
-            s_stage[wave * 64 + lane] = ubox[(size_t)seg0 + base + lane];
-            s_stagem[wave * 64 + lane] = kmeta[(size_t)seg0 + base + lane];
-            grp = s_stage + wave * 64;
-            gm = s_stagem + wave * 64;
-          }
-          for (int j = 0; j < 64; ++j) {
-            const float4 ub = grp[j];
-            const float iw = fmaxf(0.f, fminf(ub.z, mb.z) - fmaxf(ub.x, mb.x)), ih = fmaxf(0.f, fminf(ub.w, mb.w) - fmaxf(ub.y, mb.y));
-            if (__any(iw * ih > 0.f)) {
-              if (best == NO_KEEPER && mcut && !(gm[j] & META_DROPPED) && stitch_covered(ub, mb, sthr)) best = base + j;
-            }
-          }
-        }
+        // against the frozen U of the earlier chunks' ranks (k0 is a multiple of 64: full groups)
+        walk_kept_groups<false, true>(k0, lane, wave, mb, s_u, ubox + seg0, s_stage, s_meta, kmeta + seg0, s_stagem,
+                                      [&](int r, float4 ub, unsigned meta) {
+                                        if (best == NO_KEEPER && mcut && !(meta & META_DROPPED) && stitch_covered(ub, mb, sthr)) best = r;
+                                      });
         {
-          const int i = t >> 4, jq = t & 15;
-          const float4 iu = s_u4[i];
-          unsigned bits = 0u;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int j = 4 * jq + e;
-            if (j > i && ((cutm >> j) & 1ull) && stitch_covered(iu, s_box4[j], sthr)) bits |= 1u << (j & 31);
-          }
-          if (bits) atomicOr(&s_d[i][jq >> 3], bits);
+          const float4 iu = s_u4[t >> 4];
+          walk_fill_matrix(s_d, t, [&](int, int j) { return ((cutm >> j) & 1ull) && stitch_covered(iu, s_box4[j], sthr); });
         }
         s_best[wave][lane] = best;
         __syncthreads();
@@ -540,17 +433,9 @@ __global__ __launch_bounds__(1024) void stitch_walk_kernel(const ulonglong2* __r
           int ext = NO_KEEPER;
 #pragma unroll
           for (int w = 0; w < 16; ++w) ext = min(ext, s_best[w][lane]);
-          unsigned long long cur = __ballot(ext != NO_KEEPER);  // dropped
-          const unsigned long long d = ((unsigned long long)s_d[lane][1] << 32) | (unsigned long long)s_d[lane][0];
-          int ink = -1;  // the first survivor of this chunk whose U holds the lane's box
-          for (int b = 0; b < 64; ++b) {
-            const unsigned long long db = merge_shfl_u64(d, b);
-            if (!((cur >> b) & 1ull)) {
-              cur |= db;
-              if (ink < 0 && ((db >> lane) & 1ull)) ink = b;
-            }
-          }
-          const bool dropped = (cur >> lane) & 1ull;  // (a lane past the end has no cut bit: never dropped)
+          int ink;  // the first survivor of this chunk whose U holds the lane's box
+          const unsigned long long alive = walk_resolve<true>(__ballot(ext != NO_KEEPER), s_d, lane, &ink);
+          const bool dropped = !((alive >> lane) & 1ull);  // (a lane past the end has no cut bit: never dropped)
           if (dropped) kl.meta(k0 + lane) |= META_DROPPED;
           __threadfence_block();
           stitch_absorb(kl, lane, dropped, ext != NO_KEEPER ? ext : k0 + ink, false, mb);
@@ -569,52 +454,36 @@ __global__ __launch_bounds__(1024) void stitch_walk_kernel(const ulonglong2* __r
   }
 }
 
-// 4s: the keys of the second sort.  cnt [n_rows] per input row: 0 or 1 + what the survivor absorbed
-__global__ __launch_bounds__(256) void stitch_rekey_kernel(ulonglong2* __restrict__ keys, unsigned P, const int* __restrict__ cnt) {
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= P) return;
-  ulonglong2 k = keys[i];
-  if (k.x == KEY_NONE) return;
-  if (cnt[(unsigned)(k.y & 0xffffffffull)] != 0) k.x >>= 32;
-  else k = make_ulonglong2(KEY_NONE, KEY_NONE);
-  keys[i] = k;
+// the head both launches share: status and bounds cleared (and `clear`, when given), the keys, the first sort when asked for
+int large_head(const MergeLargeLayout& L, char* ws, int n_src, const MergeView* views, int max_in, const float* scores, const int* classes,
+               const int* counts, int* status, void* clear, size_t clear_bytes, bool sort, hipStream_t s) {
+  ulonglong2* keys = reinterpret_cast<ulonglong2*>(ws + L.keys_off);
+  const unsigned P = (unsigned)L.P;
+  if (hipMemsetAsync(status, 0, sizeof(int), s) != hipSuccess) return -8;
+  if (hipMemsetAsync(ws + L.bounds_off, 0, (size_t)2 * n_src * sizeof(unsigned), s) != hipSuccess) return -8;
+  if (clear && hipMemsetAsync(clear, 0, clear_bytes, s) != hipSuccess) return -8;
+  hipLaunchKernelGGL(merge_large_keys_kernel, dim3((P + 255) / 256), dim3(256), 0, s, keys, P, (unsigned)L.rows, max_in, views, scores, classes, counts);
+  if (sort) sort_keys(keys, P, s);
+  return 0;
 }
 
-// merge_large_emit_kernel over the survivors: the same prefix rule on their own scores; the box is U, out_stitched the count
-__global__ __launch_bounds__(256) void stitch_emit_kernel(const ulonglong2* __restrict__ keys, const unsigned* __restrict__ bounds, int max_in,
-                                                          const float4* __restrict__ ubox, const int* __restrict__ cnt,
-                                                          const float* __restrict__ scores, const int* __restrict__ classes, int K, int max_out,
-                                                          int blocks_per_src, float* out_boxes, float* out_scores, int* out_classes, int* out_view,
-                                                          int* out_row, int* out_stitched, int* out_counts, int* status) {
-  const int src = blockIdx.x / blocks_per_src;
-  const unsigned j = (blockIdx.x % blocks_per_src) * 256u + threadIdx.x;
-  const unsigned beg = bounds[2 * src], n = bounds[2 * src + 1] - beg;
-  if (n == 0) {
-    if (j == 0) out_counts[src] = 0;
-    return;
-  }
-  if (j >= n || j > (unsigned)max_out) return;
-  const unsigned g = (unsigned)(keys[beg + j].y & 0xffffffffull);
-  const float score = scores[g];
-  const bool cut = K > 0 && n > (unsigned)K;
-  const float kth = cut ? scores[(unsigned)(keys[beg + K - 1].y & 0xffffffffull)] : 0.f;
-  if (cut && j >= (unsigned)K && !(score >= kth)) return;
-  bool next = j + 1 < n;  // is the row behind this one emitted too?
-  if (next && cut && j + 1 >= (unsigned)K) next = scores[(unsigned)(keys[beg + j + 1].y & 0xffffffffull)] >= kth;
-  if (j == (unsigned)max_out) {  // (every truncated source stores the same word: no atomic)
-    *status = 2;
-    out_counts[src] = max_out;
-    return;
-  }
-  const float4 b = ubox[g];
-  const size_t o = (size_t)src * max_out + j;
-  out_boxes[o * 4 + 0] = b.x; out_boxes[o * 4 + 1] = b.y; out_boxes[o * 4 + 2] = b.z; out_boxes[o * 4 + 3] = b.w;
-  out_scores[o] = score;
-  out_classes[o] = classes[g];
-  out_view[o] = (int)(g / (unsigned)max_in);
-  out_row[o] = (int)(g % (unsigned)max_in);
-  out_stitched[o] = cnt[g];
-  if (!next) out_counts[src] = (int)j + 1;
+// the tail both launches share: the second keys (kept / nms_on of the large merge, or the stitching merge's cnt), their sort, the bounds
+// and the emit (ubox and out_stitched: the stitching merge's)
+template <bool STITCH>
+int large_tail(const MergeLargeLayout& L, char* ws, int n_src, const MergeView* views, int max_in, const float* boxes, const float* scores,
+               const int* classes, const unsigned char* kept, int nms_on, const float4* ubox, const int* cnt, int K, int max_out, float* out_boxes,
+               float* out_scores, int* out_classes, int* out_view, int* out_row, int* out_stitched, int* out_counts, int* status, hipStream_t s) {
+  ulonglong2* keys = reinterpret_cast<ulonglong2*>(ws + L.keys_off);
+  unsigned* bounds = reinterpret_cast<unsigned*>(ws + L.bounds_off);
+  const unsigned P = (unsigned)L.P, flat = (P + 255) / 256;
+  hipLaunchKernelGGL(merge_large_rekey_kernel<STITCH>, dim3(flat), dim3(256), 0, s, keys, P, kept, nms_on, cnt);
+  sort_keys(keys, P, s);
+  hipLaunchKernelGGL(merge_large_bounds_kernel, dim3(flat), dim3(256), 0, s, keys, P, bounds);
+  const int bps = max_out / 256 + 1;  // max_out + 1 threads per source
+  if ((long long)bps * n_src > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(merge_large_emit_kernel<STITCH>, dim3((unsigned)bps * n_src), dim3(256), 0, s, keys, bounds, views, max_in, boxes, ubox, cnt,
+                     scores, classes, K, max_out, bps, out_boxes, out_scores, out_classes, out_view, out_row, out_stitched, out_counts, status);
+  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -623,7 +492,7 @@ int launch_stitch_views(int n_src, int n_views, const MergeView* views, const St
                         const float* scores, const int* classes, const int* counts, float nms_thresh, float stitch_thr, float border_px, int K,
                         int max_out, float* out_boxes, float* out_scores, int* out_classes, int* out_view, int* out_row, int* out_stitched,
                         int* out_counts, int* status, void* workspace, hipStream_t s) {
-  const StitchLayout L = stitch_layout(n_src, n_views, max_in);
+  const MergeLargeLayout L = stitch_layout(n_src, n_views, max_in);
   if (L.bytes < 0 || max_out <= 0 || !workspace) return (int)hipErrorInvalidValue;
   static PerDeviceOnce once;
   if (!once.run(current_device(), [] {
@@ -632,29 +501,15 @@ int launch_stitch_views(int n_src, int n_views, const MergeView* views, const St
     return -7;
   char* ws = static_cast<char*>(workspace);
   ulonglong2* keys = reinterpret_cast<ulonglong2*>(ws + L.keys_off);
-  float4* kbox = reinterpret_cast<float4*>(ws + L.kbox_off);
-  float4* ubox = reinterpret_cast<float4*>(ws + L.ubox_off);
-  unsigned* kmeta = reinterpret_cast<unsigned*>(ws + L.meta_off);
-  unsigned* krow = reinterpret_cast<unsigned*>(ws + L.row_off);
   float4* out_u = reinterpret_cast<float4*>(ws + L.outu_off);
   int* out_cnt = reinterpret_cast<int*>(ws + L.outc_off);
-  unsigned* bounds = reinterpret_cast<unsigned*>(ws + L.bounds_off);
-  const unsigned P = (unsigned)L.P, n_rows = (unsigned)L.rows, flat = (P + 255) / 256;
-  if (hipMemsetAsync(status, 0, sizeof(int), s) != hipSuccess) return -8;
-  if (hipMemsetAsync(bounds, 0, (size_t)2 * n_src * sizeof(unsigned), s) != hipSuccess) return -8;
-  if (hipMemsetAsync(out_cnt, 0, (size_t)n_rows * sizeof(int), s) != hipSuccess) return -8;
-  hipLaunchKernelGGL(merge_large_keys_kernel, dim3(flat), dim3(256), 0, s, keys, P, n_rows, max_in, views, scores, classes, counts);
-  sort_keys(keys, P, s);  // (also with NMS off: a cut pair matches whatever NMS_TH is)
-  hipLaunchKernelGGL(stitch_walk_kernel, dim3(P / 64), dim3(1024), STITCH_LDS, s, keys, P, views, sviews, max_in, boxes, nms_thresh, stitch_thr,
-                     border_px, kbox, ubox, kmeta, krow, out_u, out_cnt);
-  hipLaunchKernelGGL(stitch_rekey_kernel, dim3(flat), dim3(256), 0, s, keys, P, out_cnt);
-  sort_keys(keys, P, s);
-  hipLaunchKernelGGL(merge_large_bounds_kernel, dim3(flat), dim3(256), 0, s, keys, P, bounds);
-  const int bps = max_out / 256 + 1;  // max_out + 1 threads per source
-  if ((long long)bps * n_src > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(stitch_emit_kernel, dim3((unsigned)bps * n_src), dim3(256), 0, s, keys, bounds, max_in, out_u, out_cnt, scores, classes, K,
-                     max_out, bps, out_boxes, out_scores, out_classes, out_view, out_row, out_stitched, out_counts, status);
-  return (int)hipGetLastError();
+  // (the first sort also with NMS off: a cut pair matches whatever NMS_TH is)
+  if (const int r = large_head(L, ws, n_src, views, max_in, scores, classes, counts, status, out_cnt, (size_t)L.rows * sizeof(int), true, s)) return r;
+  hipLaunchKernelGGL(stitch_walk_kernel, dim3((unsigned)L.P / 64), dim3(1024), STITCH_LDS, s, keys, (unsigned)L.P, views, sviews, max_in, boxes,
+                     nms_thresh, stitch_thr, border_px, reinterpret_cast<float4*>(ws + L.kbox_off), reinterpret_cast<float4*>(ws + L.ubox_off),
+                     reinterpret_cast<unsigned*>(ws + L.meta_off), reinterpret_cast<unsigned*>(ws + L.row_off), out_u, out_cnt);
+  return large_tail<true>(L, ws, n_src, views, max_in, boxes, scores, classes, nullptr, 0, out_u, out_cnt, K, max_out, out_boxes, out_scores,
+                          out_classes, out_view, out_row, out_stitched, out_counts, status, s);
 }
 
 int launch_merge_views_large(int n_src, int n_views, const MergeView* views, int max_in, const float* boxes, const float* scores,
@@ -664,27 +519,16 @@ int launch_merge_views_large(int n_src, int n_views, const MergeView* views, int
   if (L.bytes < 0 || max_out <= 0 || !workspace) return (int)hipErrorInvalidValue;
   char* ws = static_cast<char*>(workspace);
   ulonglong2* keys = reinterpret_cast<ulonglong2*>(ws + L.keys_off);
-  float4* kbox = reinterpret_cast<float4*>(ws + L.kbox_off);
   unsigned char* kept = reinterpret_cast<unsigned char*>(ws + L.kept_off);
-  unsigned* bounds = reinterpret_cast<unsigned*>(ws + L.bounds_off);
-  const unsigned P = (unsigned)L.P, n_rows = (unsigned)L.rows, flat = (P + 255) / 256;
   const int nms_on = nms_thresh > 0.f ? 1 : 0;
-  if (hipMemsetAsync(status, 0, sizeof(int), s) != hipSuccess) return -8;
-  if (hipMemsetAsync(bounds, 0, (size_t)2 * n_src * sizeof(unsigned), s) != hipSuccess) return -8;
-  hipLaunchKernelGGL(merge_large_keys_kernel, dim3(flat), dim3(256), 0, s, keys, P, n_rows, max_in, views, scores, classes, counts);
+  if (const int r = large_head(L, ws, n_src, views, max_in, scores, classes, counts, status, nullptr, 0, nms_on != 0, s)) return r;
   if (nms_on) {
-    sort_keys(keys, P, s);
-    if (hipMemsetAsync(kept, 0, (size_t)n_rows, s) != hipSuccess) return -8;
-    hipLaunchKernelGGL(merge_large_nms_kernel, dim3(P / 64), dim3(1024), 0, s, keys, P, views, max_in, boxes, nms_thresh, K, kbox, kept);
+    if (hipMemsetAsync(kept, 0, (size_t)L.rows, s) != hipSuccess) return -8;
+    hipLaunchKernelGGL(merge_large_nms_kernel, dim3((unsigned)L.P / 64), dim3(1024), 0, s, keys, (unsigned)L.P, views, max_in, boxes, nms_thresh, K,
+                       reinterpret_cast<float4*>(ws + L.kbox_off), kept);
   }
-  hipLaunchKernelGGL(merge_large_rekey_kernel, dim3(flat), dim3(256), 0, s, keys, P, kept, nms_on);
-  sort_keys(keys, P, s);
-  hipLaunchKernelGGL(merge_large_bounds_kernel, dim3(flat), dim3(256), 0, s, keys, P, bounds);
-  const int bps = max_out / 256 + 1;  // max_out + 1 threads per source
-  if ((long long)bps * n_src > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(merge_large_emit_kernel, dim3((unsigned)bps * n_src), dim3(256), 0, s, keys, bounds, views, max_in, boxes, scores,
-                     classes, K, max_out, bps, out_boxes, out_scores, out_classes, out_view, out_row, out_counts, status);
-  return (int)hipGetLastError();
+  return large_tail<false>(L, ws, n_src, views, max_in, boxes, scores, classes, kept, nms_on, nullptr, nullptr, K, max_out, out_boxes, out_scores,
+                           out_classes, out_view, out_row, nullptr, out_counts, status, s);
 }
 
 }  // namespace sylph
