@@ -247,10 +247,11 @@ int sylph_record_store(sylph_ctx* ctx, sylph_record** out);
  * name the record.  A record made under another dtype, or under a sylph_config with another tower norm, level count, strides or code kernel size, is refused. */
 int sylph_record_load(sylph_ctx* ctx, const sylph_record* rec);
 
-/* Fine-tuning the class-conditional layer on the current batch's stored tower outputs: the TFA protocol the reference compares against
- * (configs/COCO-Detection/TFA/FCOS_finetune.yaml, the Meta-FCOS-pretrain-tfa-finetune yamls of each dataset: FREEZE_CLS_TOWER,
- * FREEZE_BBOX_TOWER / FREEZE_BBOX_BRANCH, MODEL.TFA.*), where only the last classifier layer -- CondConvBasic's codes, or the base
- * detector's cls_logits -- is trained on the K shots.  The three entries act on the current batch, a fresh one after sylph_fcos_towers (or
+/* Fine-tuning the class-conditional layer on the current batch's stored tower outputs: the classifier half of the TFA protocol the
+ * reference compares against (MODEL.TFA.*, FREEZE_CLS_TOWER, FREEZE_BBOX_TOWER), where the last classifier layer -- CondConvBasic's
+ * codes, or the base detector's cls_logits -- is trained on the K shots.  configs/COCO-Detection/TFA/FCOS_finetune.yaml and the
+ * "-simplified" yamls train the classifier only (FREEZE_BBOX_BRANCH); the Meta-FCOS-pretrain-tfa-finetune yamls of each dataset also train
+ * the box branch: sylph_box_samples / sylph_box_grad / sylph_set_box_branch below.  The three entries act on the current batch, a fresh one after sylph_fcos_towers (or
  * a head entry) or a loaded query record, bf16 with the deferred last GroupNorm and 1x1 codes; fp32 / f32s contexts, FCOS.NORM "none",
  * 3x3 codes and the ROIEncoder are refused by name.  None of them changes anything a later sylph_fcos_head* / sylph_decode_nms* on the
  * same batch or record reads.
@@ -275,6 +276,51 @@ int sylph_cls_grad_bytes(sylph_ctx* ctx, int N, int64_t* bytes_out);
  * give the same bits on every call. */
 int sylph_cls_grad(sylph_ctx* ctx, const int* labels_dev, const float* cls_conv_dev, const float* cls_bias_dev, int N, int class_offset,
                    float alpha, float gamma, void* workspace_dev, float* loss_out_dev, float* grad_w_out_dev, float* grad_b_out_dev);
+/* Fine-tuning the box branch -- bbox_pred (4) + ctrness (1) + iou_overlap (1), one 3x3 conv on the frozen bbox tower, and the per-level
+ * Scales -- on the K shots: what _freeze_detector_head (meta_one_stage_detector.py:141-155) leaves trainable under the
+ * Meta-FCOS-pretrain-tfa-finetune yamls (FREEZE_BBOX_TOWER on, FREEZE_BBOX_BRANCH off), trained by loss_fcos_loc / loss_fcos_ctr /
+ * loss_fcos_iou (fcos_outputs.py:86-91, 675-741).  bf16 with FCOS.NORM "GN" / "NaiveGN" (the bbox tower's last GroupNorm is deferred);
+ * fp32 / f32s contexts, FCOS.NORM "none" and the ROIEncoder are refused by name.  LOC_LOSS_TYPE is "giou".
+ *
+ * sylph_box_samples: the box-sample bank of the current FRESH batch (after sylph_fcos_towers or a head entry; a loaded record is refused by
+ * name: it holds no bbox tower).  The first nine arguments and the assignment rule are sylph_fcos_targets'.  For every positive location,
+ * in ascending row order (the order does not depend on the grid: a scan, no atomics), sample p is
+ *   info_out_dev[p]     int32 (row, level, index of the claiming box, its class)
+ *   targets_out_dev[p]  fp32 (l, t, r, b) / stride, plain fp32 as compute_targets_for_locations + fcos_outputs.py:185-189
+ *   patches_out_dev[p]  bf16 [3][3][256]: bf16(relu(fma(x, a, b))) of the bbox tower's last layer at the nine neighbours (ky, kx), from the
+ *                       deferred GroupNorm's coefficient table -- the operand values of the served prediction conv; zeros outside the map
+ * count_out_dev[0] is the number of positives, also when it exceeds max_samples; then status_dev[0] = 1 (else 0) and nothing is written
+ * past the capacity.  Nothing a later head / decode on the batch reads is changed. */
+int sylph_box_samples(sylph_ctx* ctx, int n_gt, const float* boxes_dev, const int* gt_class_dev, const int* gt_image_dev,
+                      const float* sizes_of_interest, int n_soi, int center_sample, float pos_radius, int max_samples, void* patches_out_dev,
+                      float* targets_out_dev, int* info_out_dev, int* count_out_dev, int* status_dev);
+/* Bytes of workspace sylph_box_grad needs for a bank of n samples (0 for n = 0). */
+int sylph_box_grad_bytes(sylph_ctx* ctx, int n, int64_t* bytes_out);
+/* Loss and gradient of the box losses of FCOSOutputs.fcos_losses (fcos_outputs.py:675-741) over a bank of n samples, with respect to the
+ * box branch: w_dev (Cout, 256, 3, 3) fp32 in torch order, b_dev (Cout), scales_dev (levels), all device.  Needs no current batch.
+ *   z = patch . bf16(w)^T + b (fp32 accumulation); reg = relu(scale_level z[0:4]); ious, gious: iou_loss.py:26-65; centerness targets:
+ *   fcos_outputs.py:52-60; quality: 1 = BOX_QUALITY ["ctrness"], 2 = ["iou"], 3 = both; iou_mask: MODEL.FCOS.IOU_MASK (IoU targets
+ *   below 0.3 become 0).  All targets are constants; the gradient passes the ReLU (zero where scale z <= 0) and reaches the scales.
+ * sums_out_dev[4], UN-normalised: sum weight (1 - giou) (weight = the centerness target with "ctrness", else 1), the centerness BCE sum,
+ * the IoU-quality BCE sum, sum of the centerness targets: the caller divides as fcos_outputs.py:698-738 (loc by max(sums[3], 1e-6) or by
+ * num_pos, the other two by num_pos).  Channel 4 receives a gradient only with "ctrness", channel 5 only with "iou" (the reference
+ * detaches the other loss).  grad_w_out_dev (Cout, 256, 3, 3), grad_b_out_dev (Cout), grad_scales_out_dev (levels): of the un-normalised
+ * sum of the losses that are on.  z_out_dev / g_out_dev: NULL, or (n, Cout) pre-activations / d loss / d z.  n = 0 gives zeros.
+ * No atomics: fixed units of 32 samples summed in a fixed order, the same bits on every call and grid. */
+int sylph_box_grad(sylph_ctx* ctx, int n, const void* patches_dev, const float* targets_dev, const int* info_dev, const float* w_dev,
+                   const float* b_dev, const float* scales_dev, int quality, int iou_mask, void* workspace_dev, float* sums_out_dev,
+                   float* grad_w_out_dev, float* grad_b_out_dev, float* grad_scales_out_dev, float* z_out_dev, float* g_out_dev);
+/* The box branch the context runs: Cout (5 or 6), the level count and the branch stamp (0: the finalized tensors); NULL skips. */
+int sylph_box_branch_shape(sylph_ctx* ctx, int* cout, int* nlevels, uint64_t* stamp);
+/* Host copies of the box branch: w_host (Cout, 256, 3, 3) bbox_pred | ctrness | iou_overlap stacked, b_host (Cout), scales_host (levels). */
+int sylph_get_box_branch(sylph_ctx* ctx, float* w_host, float* b_host, float* scales_host);
+/* Install another box branch: the prediction conv's packed weights, its tap table, biases and the level scales are re-packed as
+ * sylph_finalize_weights packs them, and every cached plan is dropped (their segment tables carry the old scales): no batch is current
+ * afterwards, and from the next batch on every tower / head step is bit-identical to a context finalized with these tensors.  Three NULLs
+ * restore the finalized tensors.  The context carries a branch stamp: 0 for the finalized tensors, a fresh value per set, 0 again after a
+ * restore; a query record keeps the stamp it was stored under and sylph_record_load refuses a record with another stamp, naming the
+ * remedy (its stored predictions come from another branch). */
+int sylph_set_box_branch(sylph_ctx* ctx, const float* w_host, const float* b_host, const float* scales_host);
 /* Batch size, padded size and device bytes of a record; NULL skips. */
 int sylph_record_info(const sylph_record* rec, int* B, int* padded_h, int* padded_w, int64_t* bytes);
 /* Release a record, with the context that stored it (the stream is drained first).  If it is the current batch, no batch is current

@@ -113,3 +113,201 @@ int sylph_cls_grad(sylph_ctx* c, const int* labels_dev, const float* cls_conv_de
   }
   return 0;
 }
+
+// ---- the box branch: sample bank, loss + gradient, install (box_finetune.hip) ------------------------------------------------------------
+
+namespace {
+
+// what every box-branch entry refuses, by name
+int box_mode(sylph_ctx* c, const std::string& w) {
+  if (c->dt != DT_BF16)
+    return fail(w + ": the box branch is fine-tuned in the bf16 mode only (this context: " + (c->dt == DT_F32S ? "f32s" : "fp32") +
+                " storage; there is no fp32 / f32s sample or gradient kernel)");
+  if (c->cfg.tower_norm != 0)
+    return fail(w + ": MODEL.FCOS.NORM \"none\" is not supported (the samples are cut from the bbox tower output with its deferred GroupNorm)");
+  if (c->cfg.cg_type == 1) return fail(w + ": the ROIEncoder is not supported");
+  return 0;
+}
+
+int grow_ints(sylph_ctx* c, int** p, size_t* cap, size_t need) {
+  if (need <= *cap) return 0;
+  c->dfree(*p);
+  *p = nullptr; *cap = 0;
+  Plan* owner = c->alloc_owner;
+  c->alloc_owner = nullptr;  // the context's: plan eviction must not free it
+  const int r = c->dalloc((void**)p, need * sizeof(int));
+  c->alloc_owner = owner;
+  RET(r);
+  *cap = need;
+  return 0;
+}
+
+// pred, pred_taps and the biases re-packed from (Cout, 256, 3, 3) / (Cout) into the buffers the cached launches captured, as
+// sylph_finalize_weights packs them (api_weights.hip: pack_conv, the tap table)
+int install_box_branch(sylph_ctx* c, const std::vector<float>& w, const std::vector<float>& b, const std::vector<float>& scales) {
+  const int cp = c->pred.Cout, sw = (3 * cp + 3) & ~3;
+  std::vector<uint16_t> pk((size_t)c->pred.Cout_pad * 2304, 0), tw((size_t)64 * 256, 0);
+  for (int n = 0; n < cp; ++n)
+    for (int ci = 0; ci < 256; ++ci)
+      for (int tap = 0; tap < 9; ++tap) {
+        const uint16_t v = f2bf_host(w[((size_t)n * 256 + ci) * 9 + tap]);
+        pk[(size_t)n * 2304 + (size_t)tap * 256 + ci] = v;
+        tw[(size_t)((tap / 3) * sw + (tap % 3) * cp + n) * 256 + ci] = v;
+      }
+  std::vector<float> sh(b);
+  sh.resize((size_t)c->pred.Cout_pad, 0.f);
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));  // a queued step may still read the tables
+  if (c->side_stream) HIPCHK(hipStreamSynchronize(c->side_stream));
+  HIPCHK(hipMemcpy(c->pred.w, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(c->pred.shift, sh.data(), sh.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(c->pred_taps, tw.data(), tw.size() * 2, hipMemcpyHostToDevice));
+  c->level_scales = scales;
+  c->box_w = w; c->box_b = b;
+  // re-packed copies of pred's weights (a prediction conv that went through add_conv) and every cached plan: their segment tables carry
+  // SegDesc::mul = the old scales.  The next batch builds its plan again, exactly as a context finalized with these tensors does.
+  auto hp = c->hp_weights.find(c->pred.w);
+  if (hp != c->hp_weights.end()) { c->dfree(hp->second); c->hp_weights.erase(hp); }
+  auto pw = c->pw_weights.find(c->pred.w);
+  if (pw != c->pw_weights.end()) { c->dfree(pw->second.first); c->dfree(pw->second.second); c->pw_weights.erase(pw); }
+  while (!c->plans.empty()) {
+    free_plan(c, c->plans.begin()->second.get());
+    c->plans.erase(c->plans.begin());
+  }
+  c->cur = nullptr;
+  c->rec = nullptr;
+  return 0;
+}
+
+}  // namespace
+
+/* see include/sylph_hip.h */
+int sylph_box_samples(sylph_ctx* c, int n_gt, const float* boxes_dev, const int* gt_class_dev, const int* gt_image_dev,
+                      const float* sizes_of_interest, int n_soi, int center_sample, float pos_radius, int max_samples, void* patches_out_dev,
+                      float* targets_out_dev, int* info_out_dev, int* count_out_dev, int* status_dev) {
+  const std::string w = "sylph_box_samples";
+  Plan* P = c->cur;
+  if (!P) return fail(w + ": no current batch");
+  RET(box_mode(c, w));
+  if (c->rec)
+    return fail(w + ": the current batch is a query record (sylph_record_load): a record holds the cls tower's output and the predictions, no "
+                "bbox tower; collect the samples on the fresh batch, after sylph_fcos_towers or a head entry");
+  if (!P->head_built || !P->towers_fresh)
+    return fail(w + ": the towers have not run on the current batch (call sylph_fcos_towers or a head entry first)");
+  const float2* coef = P->tap_coef[1].empty() ? nullptr : P->tap_coef[1].back();
+  if (!coef || !c->pred_taps)
+    return fail(w + ": the bbox tower's last GroupNorm is not deferred in this build (SYLPH_FUSE_GN_LOGITS=0, or a prediction conv the fused "
+                "pass does not take)");
+  if (n_gt < 0) return fail(w + ": n_gt is negative");
+  if (n_gt > 0 && (!boxes_dev || !gt_class_dev || !gt_image_dev)) return fail(w + ": a ground-truth array is NULL");
+  if (max_samples < 0) return fail(w + ": max_samples is negative");
+  if (!count_out_dev || !status_dev || (max_samples > 0 && (!patches_out_dev || !targets_out_dev || !info_out_dev))) return fail(w + ": an output is NULL");
+  const int L = c->cfg.nlevels;
+  if (!sizes_of_interest || n_soi != L - 1)
+    return fail(w + ": sizes_of_interest must hold " + std::to_string(L - 1) + " values (one less than the levels), got " + std::to_string(n_soi));
+  if (!(pos_radius > 0.f) && center_sample) return fail(w + ": pos_radius must be positive");
+  FcosTargetCfg t;
+  memset(&t, 0, sizeof(t));
+  for (int l = 0; l < L; ++l) {
+    t.strides[l] = c->cfg.strides[l];
+    t.lo[l] = l == 0 ? -1.f : sizes_of_interest[l - 1];
+    t.hi[l] = l < n_soi ? sizes_of_interest[l] : 100000000.f;
+  }
+  t.center_sample = center_sample ? 1 : 0;
+  t.radius = pos_radius;
+  HIPCHK(hipSetDevice(c->device));
+  const int max_rows = P->hl[0] * P->wl[0], nseg = P->B * L;
+  RET(grow_ints(c, &c->bx_assign, &c->bx_assign_cap, (size_t)P->B * P->Ltot));
+  RET(grow_ints(c, &c->bx_blk, &c->bx_blk_cap, (size_t)nseg * box_samples_gx(max_rows)));
+  const void* x = P->tap_out[1].back();
+  const Plan* PP = P;
+  KCHK(timed_op(c, "box_samples", 0.0, c->stream,
+                [=](hipStream_t st) {
+                  return launch_box_samples(x, coef, PP->head_segs, nseg, L, max_rows, PP->Ltot, t, n_gt, boxes_dev, gt_class_dev, gt_image_dev,
+                                            c->bx_assign, c->bx_blk, max_samples, patches_out_dev, targets_out_dev, info_out_dev, count_out_dev,
+                                            status_dev, st);
+                }),
+       "box_samples");
+  return 0;
+}
+
+/* see include/sylph_hip.h */
+int sylph_box_grad_bytes(sylph_ctx* c, int n, int64_t* bytes_out) {
+  RET(box_mode(c, "sylph_box_grad_bytes"));
+  if (n < 0) return fail("sylph_box_grad_bytes: n is negative");
+  if (!bytes_out) return fail("sylph_box_grad_bytes: bytes_out is NULL");
+  *bytes_out = (int64_t)(box_grad_ws_floats(n) * sizeof(float));
+  return 0;
+}
+
+/* see include/sylph_hip.h */
+int sylph_box_grad(sylph_ctx* c, int n, const void* patches_dev, const float* targets_dev, const int* info_dev, const float* w_dev,
+                   const float* b_dev, const float* scales_dev, int quality, int iou_mask, void* workspace_dev, float* sums_out_dev,
+                   float* grad_w_out_dev, float* grad_b_out_dev, float* grad_scales_out_dev, float* z_out_dev, float* g_out_dev) {
+  const std::string w = "sylph_box_grad";
+  RET(box_mode(c, w));
+  if (!c->finalized || !c->has_head) return fail(w + ": FCOS head weights were not loaded");
+  const int cout = c->pred.Cout;
+  if (c->pred.KH != 3 || c->pred.Cin != 256 || cout < 5 || cout > 6)
+    return fail(w + ": the box branch must be a 3x3 conv of 256 -> 5 or 6 channels (bbox_pred + ctrness [+ iou_overlap]); this context has " +
+                std::to_string(cout));
+  if (n < 0) return fail(w + ": n is negative");
+  if (quality < 1 || quality > 3) return fail(w + ": quality must be 1 (ctrness), 2 (iou) or 3 (both), got " + std::to_string(quality));
+  if ((quality & 2) && cout < 6) return fail(w + ": BOX_QUALITY names \"iou\" but the context has no iou_overlap channel");
+  if (n > 0 && (!patches_dev || !targets_dev || !info_dev || !workspace_dev)) return fail(w + ": a required pointer is NULL");
+  if (!w_dev || !b_dev || !scales_dev || !sums_out_dev || !grad_w_out_dev || !grad_b_out_dev || !grad_scales_out_dev)
+    return fail(w + ": a required pointer is NULL");
+  HIPCHK(hipSetDevice(c->device));
+  const int L = c->cfg.nlevels;
+  const double fl = 2.0 * (double)n * 2304.0 * cout * 2.0;
+  KCHK(timed_op(c, "box_grad_kernel", fl, c->stream,
+                [=](hipStream_t st) {
+                  return launch_box_grad(n, patches_dev, targets_dev, info_dev, w_dev, b_dev, scales_dev, cout, L, quality, iou_mask ? 1 : 0,
+                                         (float*)workspace_dev, sums_out_dev, grad_w_out_dev, grad_b_out_dev, grad_scales_out_dev, z_out_dev,
+                                         g_out_dev, st);
+                }),
+       "box_grad");
+  return 0;
+}
+
+/* see include/sylph_hip.h */
+int sylph_box_branch_shape(sylph_ctx* c, int* cout, int* nlevels, uint64_t* stamp) {
+  if (!c->finalized || !c->has_head || c->box_w.empty()) return fail("sylph_box_branch_shape: no 3x3 box branch is loaded");
+  if (cout) *cout = c->pred.Cout;
+  if (nlevels) *nlevels = c->cfg.nlevels;
+  if (stamp) *stamp = c->box_stamp;
+  return 0;
+}
+
+/* see include/sylph_hip.h */
+int sylph_get_box_branch(sylph_ctx* c, float* w_host, float* b_host, float* scales_host) {
+  if (!c->finalized || !c->has_head || c->box_w.empty()) return fail("sylph_get_box_branch: no 3x3 box branch is loaded");
+  if (w_host) memcpy(w_host, c->box_w.data(), c->box_w.size() * sizeof(float));
+  if (b_host) memcpy(b_host, c->box_b.data(), c->box_b.size() * sizeof(float));
+  if (scales_host) memcpy(scales_host, c->level_scales.data(), c->level_scales.size() * sizeof(float));
+  return 0;
+}
+
+/* see include/sylph_hip.h */
+int sylph_set_box_branch(sylph_ctx* c, const float* w_host, const float* b_host, const float* scales_host) {
+  const std::string w = "sylph_set_box_branch";
+  if (!c->finalized || !c->has_head || c->box_w.empty()) return fail(w + ": no 3x3 box branch is loaded");
+  RET(box_mode(c, w));
+  if (!c->pred_taps) return fail(w + ": this context has no fused prediction pass (pred_taps): the box branch cannot be replaced");
+  const bool none = !w_host && !b_host && !scales_host;
+  if (!none && (!w_host || !b_host || !scales_host)) return fail(w + ": pass the three tensors, or three NULLs to restore the finalized ones");
+  if (none) {
+    if (c->box_stamp == 0) return 0;
+    RET(install_box_branch(c, c->box_w0, c->box_b0, c->box_s0));
+    c->box_stamp = 0;
+    return 0;
+  }
+  const size_t L = (size_t)c->cfg.nlevels;
+  std::vector<float> sc(scales_host, scales_host + L);
+  if (!c->cfg.use_scale)
+    for (float v : sc)
+      if (v != 1.f) return fail(w + ": MODEL.FCOS.USE_SCALE is off: every scale must be 1");
+  RET(install_box_branch(c, std::vector<float>(w_host, w_host + c->box_w0.size()), std::vector<float>(b_host, b_host + c->box_b0.size()), sc));
+  c->box_stamp = ++c->box_stamp_next;
+  return 0;
+}

@@ -1071,6 +1071,7 @@ int sylph_record_store(sylph_ctx* c, sylph_record** out) {
   R->tower_norm = c->cfg.tower_norm; R->nlevels = c->cfg.nlevels; R->code_ksize = c->cfg.cg_code_ksize;
   for (int l = 0; l < 8; ++l) R->strides[l] = c->cfg.strides[l];
   R->B = P->B; R->H = P->H; R->W = P->W;
+  R->box_stamp = c->box_stamp;
   R->img_h = P->img_h; R->img_w = P->img_w;
   R->bytes = (int64_t)total;
   c->records.push_back(R.get());
@@ -1094,6 +1095,10 @@ int sylph_record_load(sylph_ctx* c, const sylph_record* R) {
                 std::to_string(R->nlevels) + " levels, first stride " + std::to_string(R->strides[0]) + ", code kernel size " + std::to_string(R->code_ksize) +
                 "; the context: " + std::to_string(c->cfg.tower_norm) + ", " + std::to_string(c->cfg.nlevels) + ", " + std::to_string(c->cfg.strides[0]) + ", " +
                 std::to_string(c->cfg.cg_code_ksize) + ")");
+  if (R->box_stamp != c->box_stamp)
+    return fail("sylph_record_load: the record's box / centerness / IoU predictions come from another box branch (stored under branch stamp " +
+                std::to_string(R->box_stamp) + ", the context now runs " + std::to_string(c->box_stamp) +
+                "; 0 = the finalized tensors): restore that branch (sylph_set_box_branch; three NULLs for the finalized one) or store the record again");
   HIPCHK(hipSetDevice(c->device));
   Plan* P = get_plan(c, R->B, R->H, R->W);
   OwnerScope own(c, P);

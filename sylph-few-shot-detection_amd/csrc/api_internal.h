@@ -135,6 +135,7 @@ struct sylph_record {
   DType dt = DT_BF16;
   int tower_norm = 0, nlevels = 0, strides[8] = {0}, code_ksize = 1;  // the sylph_config fields a record's layout and meaning depend on
   int B = 0, H = 0, W = 0;
+  uint64_t box_stamp = 0;            // sylph_ctx::box_stamp when the record was stored: its pred rows come from that box branch
   std::vector<int> img_h, img_w;
   void* base = nullptr;              // the allocation: feat | pred | coef | partial, each at a multiple of 256 bytes
   const void* feat = nullptr;        // cls tower output [B * Ltot][256]: un-normalised where the last GroupNorm is deferred (coef != nullptr)
@@ -257,6 +258,14 @@ struct sylph_ctx {
   // sylph_cls_grad: the packed codes [32][256] and biases [32] of the class block in flight (stream order serialises the blocks of a call)
   void* ft_codes = nullptr;
   float* ft_bias = nullptr;
+  // sylph_box_samples: the claiming box per row and the positives per 256-row block of the call in flight (scratch; grown on demand)
+  int *bx_assign = nullptr, *bx_blk = nullptr;
+  size_t bx_assign_cap = 0, bx_blk_cap = 0;
+  // sylph_set_box_branch: 0 while pred / pred_taps / level_scales are the finalized tensors, else the value of the set that installed
+  // them (box_stamp_next counts up); a query record keeps the stamp it was stored under
+  uint64_t box_stamp = 0, box_stamp_next = 0;
+  // the box branch as installed (box_w (Cout, 256, 3, 3) in torch order, box_b (Cout), level_scales) and as finalized (box_w0, box_b0, box_s0)
+  std::vector<float> box_w, box_b, box_w0, box_b0, box_s0;
   void* zeros = nullptr;  // 256 B of zeros (conv out-of-image taps)
   // small batches: the two FCOS towers of a head pass run on two streams (fork / join events around the bbox tower, api_head.hip)
   hipStream_t side_stream = nullptr;

@@ -564,6 +564,17 @@ int sylph_finalize_weights(sylph_ctx* c) {
         if (!s) return fail("missing " + hp + ".scales." + std::to_string(l) + ".scale");
         c->level_scales[l] = s->data[0];
       }
+    // the box branch as finalized, in torch order: what sylph_get_box_branch returns and a reset of sylph_set_box_branch restores
+    c->box_w0.clear(); c->box_b0.clear();
+    if (c->pred.KH == 3 && c->pred.KW == 3 && c->pred.Cin == 256)
+      for (const char* nm : {".bbox_pred", ".ctrness", ".iou_overlap"}) {
+        const HostTensor *w = find_w(c, hp + nm + ".weight"), *b = find_w(c, hp + nm + ".bias");
+        c->box_w0.insert(c->box_w0.end(), w->data.begin(), w->data.end());
+        c->box_b0.insert(c->box_b0.end(), b->data.begin(), b->data.end());
+      }
+    c->box_s0 = c->level_scales;
+    c->box_w = c->box_w0; c->box_b = c->box_b0;
+    c->box_stamp = 0;
     c->has_head = true;
   }
   const std::string cp = "code_generator.code_generator_head";

@@ -35,12 +35,11 @@
 //   0.30 ms of gn_logits_kernel on the same record; the loop is VALU-bound (focal loss, GroupNorm, AGPR copies), not HBM-bound.
 #include <stdlib.h>
 
+#include "fcos_assign.h"
 #include "gn_stream.h"
 #include "kernels.h"
 
 namespace sylph {
-
-constexpr float FCOS_INF = 100000000.f;  // fcos_outputs.py:27
 
 // segs: the head's (image, level) segments, image-major; gt_*: the boxes of the whole batch; lo / hi of a level from sizes_of_interest:
 // [-1, s0], [s0, s1], .., [s_last, INF]
@@ -51,35 +50,13 @@ __global__ __launch_bounds__(256) void fcos_targets_kernel(const SegDesc* __rest
   const int seg = blockIdx.y, b = seg / nlevels, lv = seg - b * nlevels;
   const SegDesc& sd = segs[seg];
   const int W = sd.out_W, n = sd.out_H * W, stride = cfg.strides[lv];
-  const float lo = cfg.lo[lv], hi = cfg.hi[lv];
-  const float st = (float)((double)stride * (double)cfg.radius);  // `strides[level] * radius`: a Python float, cast by the tensor op
-  // "no gt" of get_sample_region: the centre-x of the image's FIRST box is 0 (fcos_outputs.py:227)
-  int first = 0;
-  while (first < n_gt && gt_image[first] != b) ++first;
-  const bool region_empty = cfg.center_sample && first < n_gt && (boxes[4 * first] + boxes[4 * first + 2]) * 0.5f == 0.f;
+  const FcosSegCtx sc = fcos_seg_ctx(cfg, b, lv, n_gt, boxes, gt_image);
   int pos = 0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     const int yi = i / W, xi = i - yi * W;
     const float x = (float)(xi * stride + stride / 2), y = (float)(yi * stride + stride / 2);
-    float best = FCOS_INF;
-    int lab = -1;
-    for (int k = first; k < n_gt; ++k) {
-      if (gt_image[k] != b) continue;
-      const float x0 = boxes[4 * k], y0 = boxes[4 * k + 1], x1 = boxes[4 * k + 2], y1 = boxes[4 * k + 3];
-      const float l = x - x0, t = y - y0, r = x1 - x, bt = y1 - y;
-      bool inside;
-      if (cfg.center_sample) {
-        const float cx = (x0 + x1) * 0.5f, cy = (y0 + y1) * 0.5f;
-        const float xmin = cx - st, ymin = cy - st, xmax = cx + st, ymax = cy + st;
-        const float c0 = xmin > x0 ? xmin : x0, c1 = ymin > y0 ? ymin : y0, c2 = xmax > x1 ? x1 : xmax, c3 = ymax > y1 ? y1 : ymax;
-        inside = !region_empty && fminf(fminf(x - c0, y - c1), fminf(c2 - x, c3 - y)) > 0.f;
-      } else {
-        inside = fminf(fminf(l, t), fminf(r, bt)) > 0.f;
-      }
-      const float m = fmaxf(fmaxf(l, t), fmaxf(r, bt));
-      const float area = (x1 - x0) * (y1 - y0);
-      if (inside && m >= lo && m <= hi && area < best) { best = area; lab = gt_class[k]; }  // smallest area, lowest index among equals
-    }
+    const int k = fcos_assign(cfg, sc, b, n_gt, boxes, gt_image, x, y);
+    const int lab = k >= 0 ? gt_class[k] : -1;
     labels[sd.out_row0 + i] = lab;
     pos += lab >= 0;
   }

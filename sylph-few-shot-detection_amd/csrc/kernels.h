@@ -223,6 +223,23 @@ size_t cls_grad_ws_floats(int n_tiles);
 int launch_cls_grad(const void* x, int ld, const float2* coef, const void* w, const float* bias, int nb, int n0, const int* labels, float alpha,
                     float gamma, float* ws, float* loss, int accumulate, float* grad_w, float* grad_b, const SegDesc* segs, const int2* tiles,
                     int n_tiles, hipStream_t s);
+// box_finetune.hip: the box-sample bank of a fresh batch (positives in row order: info, targets, normalised 3x3 patches of the bbox tower),
+// and loss + gradient of the box / centerness / IoU losses with respect to the box branch (bf16)
+inline int box_samples_gx(int max_rows) { return (max_rows + 255) / 256; }  // 256-row blocks per segment: assign [rows], blk [nseg * gx] ints
+int launch_box_samples(const void* x, const float2* coef, const SegDesc* segs, int nseg, int nlevels, int max_rows, int rows_per_image,
+                       const FcosTargetCfg& cfg, int n_gt, const float* boxes, const int* gt_class, const int* gt_image, int* assign, int* blk,
+                       int max_samples, void* patches, float* targets, int* info, int* count, int* status, hipStream_t s);
+constexpr int BOX_GRAD_UNIT = 32;          // samples behind one partial: fixed by n, so the sums do not depend on the grid
+constexpr int BOX_GRAD_DB = 6 * 2304;      // a partial: [6][2304] dW | [6] db | [8] d scales | [4] sums, rounded up to 128 bytes
+constexpr int BOX_GRAD_DS = BOX_GRAD_DB + 8;
+constexpr int BOX_GRAD_SUMS = BOX_GRAD_DS + 8;
+constexpr int BOX_GRAD_PARTIAL = BOX_GRAD_SUMS + 16;
+constexpr int BOX_GRAD_MAX_BLOCKS = 1024;  // SYLPH_BOX_GRAD_BLOCKS overrides it
+int box_grad_units(int n);
+size_t box_grad_ws_floats(int n);
+int launch_box_grad(int n, const void* patches, const float* targets, const int* info, const float* w, const float* bias, const float* scales,
+                    int cout, int nlevels, int quality, int iou_mask, float* ws, float* sums, float* grad_w, float* grad_b, float* grad_scales,
+                    float* z_out, float* g_out, hipStream_t s);
 int launch_stem_pool(const void* x, const void* wp, const float* scale, const float* shift, void* out, void* trash, int B, int H, int W,
                      int H2, int W2, int H4, int W4, hipStream_t s);
 constexpr int STEM_RAW_MAX_BATCH = 512;  // the image table of launch_stem_pool_raw lives in LDS

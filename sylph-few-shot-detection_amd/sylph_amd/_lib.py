@@ -76,6 +76,12 @@ PROTOTYPES = {
     "sylph_fcos_targets": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_int, c_float, c_void_p, c_void_p]),
     "sylph_cls_grad_bytes": (c_int, [c_void_p, c_int, POINTER(c_int64)]),
     "sylph_cls_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylph_box_samples": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_int, c_float, c_int] + [c_void_p] * 5),
+    "sylph_box_grad_bytes": (c_int, [c_void_p, c_int, POINTER(c_int64)]),
+    "sylph_box_grad": (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 7),
+    "sylph_box_branch_shape": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(ctypes.c_uint64)]),
+    "sylph_get_box_branch": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
+    "sylph_set_box_branch": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
     "sylph_roi_align": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sylph_roi_align_rois": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p]),
     "sylph_decode_nms": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,

@@ -295,6 +295,36 @@ class QueryRecord:
                 eng._records.remove(self)
 
 
+class BoxSamples:
+    """A box-sample bank (Engine.box_samples): what the trainable box branch reads of the positive locations of one or more batches.
+    patches (n, 3, 3, 256) bf16: the normalised bbox tower output at the nine taps; targets (n, 4) fp32: (l, t, r, b) / stride;
+    info (n, 4) int32: (row, level, box index, class).  Device tensors; `count` is the number of positives found (above n only after an
+    overflow of the capacity)."""
+
+    def __init__(self, patches: torch.Tensor, targets: torch.Tensor, info: torch.Tensor, count: Optional[int] = None, overflow: bool = False):
+        self.patches, self.targets, self.info = patches, targets, info
+        self.n = int(info.shape[0])
+        self.count = self.n if count is None else int(count)
+        self.overflow = bool(overflow)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.patches, self.targets, self.info))
+
+    @staticmethod
+    def cat(banks: Sequence["BoxSamples"]) -> "BoxSamples":
+        """the banks of several batches as one, in the order given (rows and box indices stay those of their own batch)"""
+        banks = list(banks)
+        if not banks:
+            raise ValueError("BoxSamples.cat: no banks")
+        return BoxSamples(torch.cat([b.patches for b in banks]).contiguous(), torch.cat([b.targets for b in banks]).contiguous(),
+                          torch.cat([b.info for b in banks]).contiguous())
+
+    def select(self, index: torch.Tensor) -> "BoxSamples":
+        """the samples `index` (a device index tensor) as a bank of their own"""
+        return BoxSamples(self.patches[index].contiguous(), self.targets[index].contiguous(), self.info[index].contiguous())
+
+
 class Engine:
     """One HIP context: weights + per-batch-shape workspaces, all on ``device``."""
 
@@ -331,12 +361,16 @@ class Engine:
         self._record = None  # the one that is the current batch (load_record), None on a fresh batch
         self._merge_ws = None  # merge_views_large's workspace: grows on demand, contents are scratch
         self._ft_ws = None  # cls_grad's workspace (the per-unit partial sums): grows on demand, contents are scratch
+        self._box_ws = None  # box_grad's workspace, likewise
         # what the training-side entries (fcos_targets, cls_grad) read from MODEL.FCOS: focal loss and target assignment
         f = cfg.MODEL.FCOS if cfg is not None else {}
         self.fcos_train = {"alpha": float(f.get("LOSS_ALPHA", 0.25)), "gamma": float(f.get("LOSS_GAMMA", 2.0)),
                            "sizes_of_interest": [float(v) for v in f.get("SIZES_OF_INTEREST", [64, 128, 256, 512])],
                            "center_sample": bool(f.get("CENTER_SAMPLE", True)), "pos_radius": float(f.get("POS_RADIUS", 1.5)),
-                           "prior_prob": float(f.get("PRIOR_PROB", 0.01))}
+                           "prior_prob": float(f.get("PRIOR_PROB", 0.01)),
+                           # ... and the box losses (box_samples, box_grad)
+                           "box_quality": [str(v) for v in f.get("BOX_QUALITY", ["ctrness"])], "iou_mask": bool(f.get("IOU_MASK", False)),
+                           "loc_loss_type": str(f.get("LOC_LOSS_TYPE", "giou"))}
         self._counts_free = {}  # length -> pinned count buffers no handle owns (_counts_acquire)
         self._counts_out = set()  # ids of the pinned count buffers that unfetched decode handles own
 
@@ -582,6 +616,147 @@ class Engine:
                                     _ptr(self._ft_ws), _ptr(loss), _ptr(gw), _ptr(gb)), "cls_grad")
         self._keep_ft = (w, b)
         return loss, gw, gb
+
+    # ---- fine-tuning the box branch on a bank of positive samples (sylph_amd.finetune.finetune_box_branch) ----------------------
+    def _box_refuse(self, who: str):
+        from . import distributed as D
+        if D.get_world_size() > 1:
+            raise NotImplementedError(f"{who}: gradients are not reduced across ranks; world size is {D.get_world_size()}")
+        fc = self.fcos_train
+        if fc["loc_loss_type"] != "giou":
+            raise NotImplementedError(f"{who}: MODEL.FCOS.LOC_LOSS_TYPE \"{fc['loc_loss_type']}\" is not supported (the gradient kernel implements \"giou\")")
+
+    def box_samples(self, boxes: torch.Tensor, classes: torch.Tensor, image_index: torch.Tensor, max_samples: Optional[int] = None,
+                    out=None, allow_overflow: bool = False) -> "BoxSamples":
+        """The box-sample bank of the current FRESH batch (after `towers()` or a head call): one sample per positive location of
+        `fcos_targets`' assignment, in ascending row order.  Arguments as `fcos_targets`.  max_samples: the capacity (default: a bound that
+        cannot overflow: 9 per box and level under centre sampling with POS_RADIUS <= 1.5, else every row); a count above it raises unless
+        allow_overflow (then `.overflow` is set and `.count` is the true count).  out: (patches, targets, info) tensors of at least
+        max_samples rows to write into.  Reads the count back (one sync)."""
+        self._stream()
+        self._box_refuse("box_samples")
+        bx = torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 4)
+        cl = torch.as_tensor(classes).reshape(-1)
+        im = torch.as_tensor(image_index).reshape(-1)
+        n = bx.shape[0]
+        if cl.numel() != n or im.numel() != n:
+            raise ValueError(f"box_samples: {n} boxes, {cl.numel()} classes and {im.numel()} image indices")
+        if getattr(self, "_batch", None) is None:
+            raise RuntimeError("box_samples: no current batch")
+        rows, B = self.batch_rows(), self._batch[0]
+        iml = im.tolist()
+        if any(a > b for a, b in zip(iml, iml[1:])):
+            raise ValueError("box_samples: gt_image is not sorted (image_index must not decrease)")
+        if n and (iml[0] < 0 or iml[-1] >= B):
+            raise ValueError(f"box_samples: image_index outside the batch of {B} images")
+        fc = self.fcos_train
+        if max_samples is None:
+            cap = rows if not (fc["center_sample"] and fc["pos_radius"] <= 1.5) else min(rows, 9 * self.nlevels * n)
+        else:
+            cap = int(max_samples)
+            if cap < 0:
+                raise ValueError("box_samples: max_samples is negative")
+        bx = bx.to(self.device).contiguous()
+        cl = cl.to(self.device, torch.int32).contiguous()
+        im = im.to(self.device, torch.int32).contiguous()
+        if out is None:
+            patches = torch.empty(cap, 3, 3, 256, device=self.device, dtype=torch.bfloat16)
+            targets = torch.empty(cap, 4, device=self.device, dtype=torch.float32)
+            info = torch.empty(cap, 4, device=self.device, dtype=torch.int32)
+        else:
+            patches, targets, info = out
+            if (patches.dtype != torch.bfloat16 or targets.dtype != torch.float32 or info.dtype != torch.int32 or
+                    patches.numel() < cap * 2304 or targets.numel() < cap * 4 or info.numel() < cap * 4 or
+                    not (patches.is_contiguous() and targets.is_contiguous() and info.is_contiguous())):
+                raise ValueError(f"box_samples: out must be contiguous (patches bf16, targets fp32, info int32) device tensors of at least {cap} rows")
+        cs = torch.empty(2, device=self.device, dtype=torch.int32)  # count | status
+        soi = (ctypes.c_float * len(fc["sizes_of_interest"]))(*fc["sizes_of_interest"])
+        check(self.L.sylph_box_samples(self._ctx, n, _ptr(bx), _ptr(cl), _ptr(im), soi, len(fc["sizes_of_interest"]), int(fc["center_sample"]),
+                                       float(fc["pos_radius"]), cap, _ptr(patches), _ptr(targets), _ptr(info), _ptr(cs), _ptr(cs[1:])), "box_samples")
+        count, status = (int(v) for v in cs.tolist())
+        if status and not allow_overflow:
+            raise RuntimeError(f"box_samples: {count} positive locations exceed max_samples = {cap}")
+        k = min(count, cap)
+        return BoxSamples(patches[:k], targets[:k], info[:k], count=count, overflow=bool(status))
+
+    def box_grad(self, samples: "BoxSamples", w: torch.Tensor, b: torch.Tensor, scales: torch.Tensor, debug: bool = False,
+                 quality=None, iou_mask: Optional[bool] = None):
+        """Un-normalised box losses over the bank and their gradient with respect to the box branch: w (Cout, 256, 3, 3), b (Cout,),
+        scales (levels,).  -> dict: sums (4,) = [sum weight (1 - giou), centerness BCE sum, IoU BCE sum, sum of centerness targets],
+        grad_w, grad_b, grad_scales; with debug also z and g, the (n, Cout) pre-activations and d loss / d z.  quality / iou_mask
+        default to MODEL.FCOS.BOX_QUALITY / IOU_MASK.  Nothing is read back."""
+        self._stream()
+        self._box_refuse("box_grad")
+        if not isinstance(samples, BoxSamples):
+            raise TypeError(f"box_grad: a BoxSamples bank is expected, not {type(samples).__name__}")
+        cout, L = self.box_branch_shape()[:2]
+        w = torch.as_tensor(w).to(self.device, torch.float32).contiguous()
+        b = torch.as_tensor(b).to(self.device, torch.float32).reshape(-1).contiguous()
+        s = torch.as_tensor(scales).to(self.device, torch.float32).reshape(-1).contiguous()
+        if tuple(w.shape) != (cout, 256, 3, 3) or b.numel() != cout or s.numel() != L:
+            raise ValueError(f"box_grad: the box branch is w ({cout}, 256, 3, 3), b ({cout},), scales ({L},); got {tuple(w.shape)}, "
+                             f"{tuple(b.shape)}, {tuple(s.shape)}")
+        q = sorted(self.fcos_train["box_quality"] if quality is None else quality)
+        if q not in (["ctrness"], ["iou"], ["ctrness", "iou"]):
+            raise NotImplementedError(f"box_grad: MODEL.FCOS.BOX_QUALITY {q}")
+        qbits = (1 if "ctrness" in q else 0) | (2 if "iou" in q else 0)
+        mask = self.fcos_train["iou_mask"] if iou_mask is None else bool(iou_mask)
+        n = samples.n
+        need = c_int64(0)
+        check(self.L.sylph_box_grad_bytes(self._ctx, n, ctypes.byref(need)), "box_grad_bytes")
+        if self._box_ws is None or self._box_ws.numel() < need.value:
+            self._box_ws = torch.empty(max(need.value, 4), device=self.device, dtype=torch.uint8)
+        out = {"sums": torch.empty(4, device=self.device), "grad_w": torch.empty_like(w), "grad_b": torch.empty_like(b),
+               "grad_scales": torch.empty_like(s)}
+        if debug:
+            out["z"] = torch.empty(n, cout, device=self.device)
+            out["g"] = torch.empty(n, cout, device=self.device)
+        check(self.L.sylph_box_grad(self._ctx, n, _ptr(samples.patches), _ptr(samples.targets), _ptr(samples.info), _ptr(w), _ptr(b), _ptr(s),
+                                    qbits, int(mask), _ptr(self._box_ws), _ptr(out["sums"]), _ptr(out["grad_w"]), _ptr(out["grad_b"]),
+                                    _ptr(out["grad_scales"]), _ptr(out.get("z")), _ptr(out.get("g"))), "box_grad")
+        self._keep_box = (w, b, s, samples)
+        return out
+
+    def box_branch_shape(self):
+        """(Cout, levels, stamp) of the box branch the context runs; stamp 0: the checkpoint's tensors"""
+        co, lv, st = c_int(0), c_int(0), ctypes.c_uint64(0)
+        check(self.L.sylph_box_branch_shape(self._ctx, ctypes.byref(co), ctypes.byref(lv), ctypes.byref(st)), "box_branch_shape")
+        return co.value, lv.value, st.value
+
+    def box_branch(self):
+        """The box branch the context runs, as the state dict names it (CPU fp32): bbox_pred.weight|bias, ctrness.weight|bias,
+        iou_overlap.weight|bias (a 6-channel branch), scales.{l}.scale"""
+        from .finetune import split_box_branch
+        cout, L, _ = self.box_branch_shape()
+        w, b, s = torch.empty(cout, 256, 3, 3), torch.empty(cout), torch.empty(L)
+        fp = lambda t: ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_float))
+        check(self.L.sylph_get_box_branch(self._ctx, fp(w), fp(b), fp(s)), "get_box_branch")
+        return split_box_branch(w, b, s)
+
+    def set_box_branch(self, branch):
+        """Install `branch` (the dict `box_branch()` returns, or None for the checkpoint's): from the next batch on every step is
+        bit-identical to an engine loaded with a state dict carrying it.  No batch is current afterwards; query records stored under
+        another branch are refused by `load_record` until that branch is back."""
+        self._stream()
+        if branch is None:
+            check(self.L.sylph_set_box_branch(self._ctx, None, None, None), "set_box_branch")
+        else:
+            from .finetune import stack_box_branch
+            cout, L, _ = self.box_branch_shape()
+            w, b, s = (t.detach().to("cpu", torch.float32).contiguous() for t in stack_box_branch(branch))
+            if tuple(w.shape) != (cout, 256, 3, 3) or b.numel() != cout or s.numel() != L:
+                raise ValueError(f"set_box_branch: the box branch is w ({cout}, 256, 3, 3), b ({cout},), scales ({L},); got {tuple(w.shape)}, "
+                                 f"{tuple(b.shape)}, {tuple(s.shape)}")
+            fp = lambda t: ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_float))
+            check(self.L.sylph_set_box_branch(self._ctx, fp(w), fp(b), fp(s)), "set_box_branch")
+        self._batch = None
+        self._record = None
+        self._sup_rows = None
+        self._keep = []
+        self._ncls = 0
+
+    def reset_box_branch(self):
+        self.set_box_branch(None)
 
     def _fold_codes(self, cls_conv: torch.Tensor, cls_bias: Optional[torch.Tensor], raw: bool = False):
         """One episode's class codes -> ((N, 256) fp32, (N,) fp32 or None) on the device, the CondConvBlock of a ROIEncoder model folded in."""

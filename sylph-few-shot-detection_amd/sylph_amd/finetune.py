@@ -1,7 +1,11 @@
-"""TFA-style fine-tuning of class codes on query records: the baseline the reference compares Sylph against
-(configs/COCO-Detection/TFA/FCOS_finetune.yaml: FREEZE_CLS_TOWER, FREEZE_BBOX_TOWER, MODEL.TFA.*), which trains only the last classifier
-layer on the K shots.  A record keeps the cls tower's output, so one gradient step is one streaming pass over it per 32 classes
-(csrc/finetune.hip) -- no backbone, no towers, no autograd graph.  The optimiser acts on 257 N floats and stays in torch.
+"""TFA-style fine-tuning on the K shots: the baseline the reference compares Sylph against (MODEL.TFA.*, FREEZE_CLS_TOWER,
+FREEZE_BBOX_TOWER).  configs/COCO-Detection/TFA/FCOS_finetune.yaml and the "-simplified" yamls train only the last classifier layer
+(FREEZE_BBOX_BRANCH); the Meta-FCOS-pretrain-tfa-finetune yamls also train the box branch.
+
+Class codes (finetune_class_codes): a record keeps the cls tower's output, so one gradient step is one streaming pass over it per 32
+classes (csrc/finetune.hip) -- no backbone, no towers, no autograd graph.  The optimiser acts on 257 N floats and stays in torch.
+The box branch (finetune_box_branch, below): bbox_pred / ctrness / iou_overlap and the level scales on a box-sample bank -- the 3x3x256
+patches of the frozen bbox tower at the positive locations, cut out once per batch -- one launch per step (csrc/box_finetune.hip).
 
     codes, losses = finetune_class_codes(engine, records, annotations, class_codes, iters=200, lr=0.02)
     model(record_inputs, class_code=codes, run_type="meta_learn_test_instance")
@@ -139,3 +143,111 @@ def finetune_class_codes(engine_or_model, records, annotations, class_codes: Dic
     if opt.b is not None:
         out["cls_bias"] = opt.b.reshape(b_in.shape).to(b_in.dtype)
     return out, losses
+
+
+# ---- the box branch (the Meta-FCOS-pretrain-tfa-finetune yamls: FREEZE_BBOX_TOWER on, FREEZE_BBOX_BRANCH off) --------------------------
+BOX_BRANCH_PARTS = ("bbox_pred", "ctrness", "iou_overlap")
+
+
+def stack_box_branch(branch: Dict[str, torch.Tensor]):
+    """{"bbox_pred.weight|bias", "ctrness.*"[, "iou_overlap.*"], "scales.{l}.scale"} -> (w (Cout, 256, 3, 3), b (Cout,), scales (levels,))"""
+    parts = [p for p in BOX_BRANCH_PARTS if f"{p}.weight" in branch]
+    if parts[:2] != ["bbox_pred", "ctrness"]:
+        raise ValueError(f"box branch: bbox_pred and ctrness are required, got {sorted(branch)}")
+    w = torch.cat([branch[f"{p}.weight"].float() for p in parts])
+    b = torch.cat([branch[f"{p}.bias"].float().reshape(-1) for p in parts])
+    L = 0
+    while f"scales.{L}.scale" in branch:
+        L += 1
+    s = torch.stack([branch[f"scales.{l}.scale"].float().reshape(()) for l in range(L)]) if L else torch.zeros(0)
+    return w, b, s
+
+
+def split_box_branch(w: torch.Tensor, b: torch.Tensor, scales: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """the inverse of stack_box_branch (Cout 5: no iou_overlap)"""
+    out, n0 = {}, 0
+    for p, co in zip(BOX_BRANCH_PARTS, (4, 1, 1)):
+        if n0 >= w.shape[0]:
+            break
+        out[f"{p}.weight"] = w[n0:n0 + co].clone()
+        out[f"{p}.bias"] = b[n0:n0 + co].clone()
+        n0 += co
+    for l in range(scales.numel()):
+        out[f"scales.{l}.scale"] = scales[l].reshape(1).clone()
+    return out
+
+
+def box_loss_norms(sums: torch.Tensor, n: int, quality: Sequence[str]):
+    """fcos_outputs.py:698-738 on one rank: (the divisor of loss_fcos_loc, num_pos_avg) as 0-d device tensors.  loc is divided by
+    max(sum of centerness targets, 1e-6) when "ctrness" weights it, by num_pos_avg = max(n, 1) under ["iou"] alone."""
+    npos = torch.tensor(float(max(int(n), 1)), device=sums.device)
+    return (sums[3].clamp(min=1e-6) if "ctrness" in quality else npos), npos
+
+
+class BranchOptimizer:
+    """fp32 masters of the box branch under torch.optim.SGD + MultiStepLR, as CodeOptimizer keeps the codes.  `step` takes box_grad's
+    un-normalised gradients and the two divisors.  Parts that receive no gradient -- the quality channel BOX_QUALITY does not name, the
+    scales without USE_SCALE -- keep their bits: neither weight decay nor momentum moves them."""
+
+    def __init__(self, w: torch.Tensor, b: torch.Tensor, scales: torch.Tensor, quality: Sequence[str], *, lr: float, momentum: float = 0.9,
+                 weight_decay: float = 1e-4, lr_steps: Sequence[int] = (), lr_gamma: float = 0.1, train_scales: bool = True):
+        self.w, self.b, self.s = (t.detach().to(torch.float32).clone() for t in (w, b, scales))
+        cout = self.w.shape[0]
+        frozen = torch.zeros(cout, dtype=torch.bool)
+        if "ctrness" not in quality:
+            frozen[4] = True
+        if cout > 5 and "iou" not in quality:
+            frozen[5] = True
+        self.frozen = frozen.to(self.w.device) if bool(frozen.any()) else None
+        self.train_scales = bool(train_scales)
+        self.w0, self.b0, self.s0 = self.w.clone(), self.b.clone(), self.s.clone()
+        self.opt = torch.optim.SGD([self.w, self.b, self.s], lr=lr, momentum=momentum, weight_decay=weight_decay)
+        self.sched = torch.optim.lr_scheduler.MultiStepLR(self.opt, milestones=sorted(int(v) for v in lr_steps), gamma=lr_gamma)
+
+    @property
+    def lr(self) -> float:
+        return self.opt.param_groups[0]["lr"]
+
+    def step(self, grad_w: torch.Tensor, grad_b: torch.Tensor, grad_scales: torch.Tensor, loc_norm: torch.Tensor, num_pos: torch.Tensor):
+        div = torch.cat([loc_norm.reshape(1).expand(4), num_pos.reshape(1).expand(self.w.shape[0] - 4)])
+        self.w.grad = grad_w / div.reshape(-1, 1, 1, 1)
+        self.b.grad = grad_b / div
+        self.s.grad = grad_scales / loc_norm
+        self.opt.step()
+        self.sched.step()
+        if self.frozen is not None:
+            self.w[self.frozen] = self.w0[self.frozen]
+            self.b[self.frozen] = self.b0[self.frozen]
+        if not self.train_scales:
+            self.s.copy_(self.s0)
+
+
+def finetune_box_branch(engine_or_model, samples, branch: Dict[str, torch.Tensor], *, iters: int, lr: float, momentum: float = 0.9,
+                        weight_decay: float = 1e-4, lr_steps: Sequence[int] = (), lr_gamma: float = 0.1,
+                        samples_per_step: Optional[int] = None, seed: int = 0):
+    """Train `branch` (Engine.box_branch()'s dict) on the box-sample bank `samples` (Engine.box_samples, BoxSamples.cat): per step one
+    box_grad launch over the bank -- or over the next `samples_per_step` of a stream of seeded permutations -- the gradients divided as
+    fcos_outputs.py:698-738 divides the losses, one SGD step.  BOX_QUALITY / IOU_MASK come from cfg.MODEL.FCOS.  Returns (branch, losses):
+    the trained dict (not installed: Engine.set_box_branch does that) and the normalised (loc, ctr, iou) losses of every step as one
+    (iters, 3) device tensor."""
+    from . import distributed as D
+    if D.get_world_size() > 1:
+        raise NotImplementedError(f"finetune_box_branch: gradients are not reduced across ranks; world size is {D.get_world_size()}")
+    eng = getattr(engine_or_model, "engine", engine_or_model)
+    quality = sorted(eng.fcos_train["box_quality"])
+    w, b, s = (t.to(eng.device) for t in stack_box_branch(branch))
+    opt = BranchOptimizer(w, b, s, quality, lr=lr, momentum=momentum, weight_decay=weight_decay, lr_steps=lr_steps, lr_gamma=lr_gamma,
+                          train_scales=bool(eng.sc.use_scale))
+    n = samples.n
+    if samples_per_step is None or int(samples_per_step) >= n:
+        plan = None
+    else:
+        plan = step_records(n, int(samples_per_step), int(iters), seed)
+    losses = torch.zeros(int(iters), 3, device=eng.device)
+    for it in range(int(iters)):
+        bank = samples if plan is None else samples.select(torch.tensor(plan[it], device=eng.device))
+        out = eng.box_grad(bank, opt.w, opt.b, opt.s)
+        loc_norm, npos = box_loss_norms(out["sums"], bank.n, quality)
+        losses[it] = out["sums"][:3] / torch.stack([loc_norm, npos, npos])
+        opt.step(out["grad_w"], out["grad_b"], out["grad_scales"], loc_norm, npos)
+    return {k: v.cpu() for k, v in split_box_branch(opt.w, opt.b, opt.s).items()}, losses

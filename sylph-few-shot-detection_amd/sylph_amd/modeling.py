@@ -789,6 +789,38 @@ class MetaOneStageDetector(nn.Module):
             for r in own:
                 r.close()
 
+    # ---- fine-tuning the box branch on annotated images (the tfa-finetune yamls; sylph_amd.finetune.finetune_box_branch) ---------------
+    def box_samples_of(self, batched_inputs, *, batch_size: Optional[int] = 16):
+        """The box-sample bank of annotated images (dicts with "image" or "image_u8" + "resize_hw", and "instances"): one network pass
+        per `batch_size` of them, the samples of every pass collected while its bbox tower output is fresh."""
+        from .engine import BoxSamples
+        assert not self.training, "call model.eval(): only the box branch is trained, by its own optimiser"
+        inputs = list(batched_inputs)
+        if any(isinstance(x, dict) and "record" in x for x in inputs):
+            raise ValueError("finetune_box_branch: a query record holds no bbox tower; pass the annotated images themselves")
+        bs = int(batch_size) if batch_size else max(len(inputs), 1)
+        banks = []
+        for i in range(0, len(inputs), bs):
+            chunk = inputs[i:i + bs]
+            out_sizes, net_sizes = self._run_backbone(chunk, with_net_sizes=True)
+            self.engine.towers()
+            metas = [dict(instances=x["instances"], net_height=nh, net_width=nw) for x, (nh, nw) in zip(chunk, net_sizes)]
+            ann = self._record_annotations({"inputs": metas})
+            banks.append(self.engine.box_samples(ann["boxes"], ann["classes"], ann["image_index"]))
+        return BoxSamples.cat(banks)
+
+    def finetune_box_branch(self, batched_inputs, *, batch_size: Optional[int] = 16, **kw):
+        """Train the box branch (bbox_pred, ctrness, iou_overlap, the level scales) on annotated images: the samples are collected by
+        `box_samples_of`, then sylph_amd.finetune.finetune_box_branch runs from the branch the engine runs now (kw: iters, lr, momentum,
+        weight_decay, lr_steps, lr_gamma, samples_per_step, seed).  Returns (branch, losses); `set_box_branch` installs the branch."""
+        from .finetune import finetune_box_branch
+        samples = self.box_samples_of(batched_inputs, batch_size=batch_size)
+        return finetune_box_branch(self.engine, samples, self.engine.box_branch(), **kw)
+
+    def set_box_branch(self, branch):
+        """Install a box branch for every later pass (None: the checkpoint's).  Query records made under another branch are refused."""
+        self.engine.set_box_branch(branch)
+
     def _run_backbone(self, batched_inputs: List[Dict[str, Any]], with_net_sizes: bool = False):
         """preprocess + backbone of the query batch -> the (height, width) each image's detections are scaled to.  A record-input: no
         network at all, its record becomes the current batch and the sizes are the stored ones."""

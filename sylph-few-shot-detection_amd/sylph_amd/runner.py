@@ -201,17 +201,8 @@ class MetaFCOSRunner:
         return format_class_codes_shared(codes, device=model.device)
 
     @staticmethod
-    def _finetune_codes(model, support_loader, class_codes, finetune: Dict[str, Any]):
-        """The TFA step of one (dataset, seed): `class_codes` (None: the checkpoint's own cls_logits rows) refined on that seed's support
-        images, every support record's boxes labelled with its item's support_set_target (the row of its code).  finetune: the keyword
-        arguments of MetaOneStageDetector.finetune_class_codes (iters, lr, ..., batch_size: support images per network pass, default 16)."""
-        if D.get_world_size() > 1:
-            raise NotImplementedError(f"finetune: a rank sees its own shard of the support set and gradients are not reduced across ranks; "
-                                      f"world size is {D.get_world_size()}")
-        if support_loader is None:
-            raise ValueError("finetune needs the support images: pass support_loader (or override the support-set loader builder)")
-        kw = dict(finetune)
-        kw.setdefault("batch_size", 16)
+    def _support_batch(support_loader):
+        """every support record of the loader as an annotated image: its boxes labelled with its item's support_set_target"""
         batch = []
         for item in support_loader:
             for x in item:
@@ -222,6 +213,34 @@ class MetaFCOSRunner:
                     inst.gt_boxes = src.gt_boxes
                     inst.gt_classes = torch.full((len(src.gt_boxes),), c, dtype=torch.long)
                     batch.append(dict({k: v for k, v in rec.items() if k != "instances"}, instances=inst))
+        return batch
+
+    @staticmethod
+    def _finetune_box_branch(model, support_loader, box_branch: Dict[str, Any]):
+        """The box half of the tfa-finetune recipe for one (dataset, seed): the box branch trained on that seed's support images
+        (MetaOneStageDetector.finetune_box_branch; box_branch: its keyword arguments).  Returns the branch; the caller installs it."""
+        kw = dict(box_branch)
+        kw.setdefault("batch_size", 16)
+        batch = MetaFCOSRunner._support_batch(support_loader)
+        branch, losses = model.finetune_box_branch(batch, **kw)
+        ls = losses.cpu()
+        logger.info(f"finetune box branch: {ls.shape[0]} steps on {len(batch)} support images, (loc, ctr, iou) "
+                    f"{[round(float(v), 4) for v in ls[0]]} -> {[round(float(v), 4) for v in ls[-1]]}")
+        return branch
+
+    @staticmethod
+    def _finetune_codes(model, support_loader, class_codes, finetune: Dict[str, Any]):
+        """The TFA step of one (dataset, seed): `class_codes` (None: the checkpoint's own cls_logits rows) refined on that seed's support
+        images, every support record's boxes labelled with its item's support_set_target (the row of its code).  finetune: the keyword
+        arguments of MetaOneStageDetector.finetune_class_codes (iters, lr, ..., batch_size: support images per network pass, default 16)."""
+        if D.get_world_size() > 1:
+            raise NotImplementedError(f"finetune: a rank sees its own shard of the support set and gradients are not reduced across ranks; "
+                                      f"world size is {D.get_world_size()}")
+        if support_loader is None:
+            raise ValueError("finetune needs the support images: pass support_loader (or override the support-set loader builder)")
+        kw = {k: v for k, v in finetune.items() if k != "box_branch"}
+        kw.setdefault("batch_size", 16)
+        batch = MetaFCOSRunner._support_batch(support_loader)
         codes, losses = model.finetune_class_codes(batch, class_codes, **kw)
         ls = losses.cpu()
         logger.info(f"finetune: {ls.numel()} steps on {len(batch)} support images, loss {float(ls[0]):.4f} -> {float(ls[-1]):.4f}")
@@ -236,11 +255,21 @@ class MetaFCOSRunner:
         class_codes = None
         if not eval_with_pretrained_code:
             class_codes = self._episode_codes(cfg, model, support_loader, base_support_loader, output_folder, num_classes)
-        if finetune is not None:
-            class_codes = self._finetune_codes(model, support_loader, class_codes, finetune)
-            eval_with_pretrained_code = False  # the refined rows are passed as class codes, also where they started as cls_logits
-        res = inference_on_dataset_with_class_codes(model, query_loader, evaluator, class_codes,
-                                                    eval_with_pretrained_code=eval_with_pretrained_code)
+        installed = False
+        try:
+            if finetune is not None:
+                class_codes = self._finetune_codes(model, support_loader, class_codes, finetune)
+                eval_with_pretrained_code = False  # the refined rows are passed as class codes, also where they started as cls_logits
+                if finetune.get("box_branch") is not None:
+                    # the box branch trained on the same support images and installed for this seed's query loop only
+                    branch = self._finetune_box_branch(model, support_loader, finetune["box_branch"])
+                    model.set_box_branch(branch)
+                    installed = True
+            res = inference_on_dataset_with_class_codes(model, query_loader, evaluator, class_codes,
+                                                        eval_with_pretrained_code=eval_with_pretrained_code)
+        finally:
+            if installed:
+                model.set_box_branch(None)
         return res, class_codes
 
     def _do_test_meta_learning(self, cfg, model, support_loader=None, query_loader=None, evaluator=None, base_support_loader=None,
@@ -271,7 +300,10 @@ class MetaFCOSRunner:
           explicit query_loader).  One rank only.
         * finetune=dict(iters=..., lr=..., ...): the TFA baseline -- every seed's class codes (on an EVAL_WITH_PRETRAINED_CODE dataset the
           checkpoint's cls_logits rows) are refined on that seed's support images before its query loop (_finetune_codes;
-          sylph_amd.finetune).  One rank only; not together with fuse_repeats or a shot bank."""
+          sylph_amd.finetune).  One rank only; not together with fuse_repeats or a shot bank.
+          finetune=dict(..., box_branch=dict(iters=..., lr=..., ...)) also trains the box branch on the same support images (the
+          Meta-FCOS-pretrain-tfa-finetune yamls leave FREEZE_BBOX_BRANCH off) and installs it for that seed's query loop, restoring
+          the checkpoint's in a `finally`; not together with cache_queries, fuse_repeats or a shot bank."""
         if finetune is not None:
             if D.get_world_size() > 1:
                 raise NotImplementedError(f"finetune: a rank sees its own shard of the support set and gradients are not reduced across ranks; "
@@ -279,6 +311,11 @@ class MetaFCOSRunner:
             if shot_bank is not None or bank_draws is not None or fuse_repeats:
                 raise NotImplementedError("finetune together with fuse_repeats or a shot bank is not supported: the codes of every seed are "
                                           "refined on that seed's support images, one query pass per seed")
+            if finetune.get("box_branch") is not None:
+                for on, what in ((cache_queries, "cache_queries"), (fuse_repeats, "fuse_repeats"), (shot_bank is not None or bank_draws is not None, "a shot bank")):
+                    if on:
+                        raise NotImplementedError(f"finetune box_branch together with {what} is not supported: the query records / fused passes "
+                                                  f"were made under another box branch than the one each seed trains")
         if shot_bank is not None or bank_draws is not None:
             return self._bank_sweep(cfg, model, shot_bank, bank_draws, query_loader, evaluator, dataset_names, cache_queries, cache_max_bytes)
         if support_loader is not None or query_loader is not None:
