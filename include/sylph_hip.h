@@ -321,6 +321,59 @@ int sylph_get_box_branch(sylph_ctx* ctx, float* w_host, float* b_host, float* sc
  * restore; a query record keeps the stamp it was stored under and sylph_record_load refuses a record with another stamp, naming the
  * remedy (its stored predictions come from another branch). */
 int sylph_set_box_branch(sylph_ctx* ctx, const float* w_host, const float* b_host, const float* scales_host);
+
+/* Meta-training of the code generator on a frozen detector: the second stage of the paper, the recipes
+ * configs/LVISv1-Detection/Meta-FCOS/Meta-FCOS-finetune-{once,2,sylph-fa}.yaml and configs/COCO-Detection/Meta-FCOS/Meta-FCOS-finetune-lvis.yaml
+ * (BACKBONE.FREEZE, FREEZE_CLS_TOWER, FREEZE_BBOX_BRANCH on, CODE_GENERATOR.FREEZE off).  With a frozen backbone the 7x7x256 ROI maps of
+ * the support instances are constants (sylph_roi_rows), with frozen towers the query side of an episode is a query record, and
+ * sylph_cls_grad gives d loss / d (code, bias); the entries below are the generator's training-mode forward and its backward.
+ * bf16 contexts only.  Refused by name, before any launch: fp32 / f32s contexts, the ROIEncoder, 3x3 codes, WEIGHT_LAYER / SCALE_LAYER
+ * heads, BIAS_L2_NORM, META_BIAS, a TOWER_LAYERS entry other than ["GN", "ReLU"], idx out of range, seg_len that does not sum to M. */
+/* The ROIPooler call of sylph_roi_align_rois (code_generator.py:341-348,928-930) written straight to the caller's (R, 49, 256) bf16
+ * position-major device buffer: one launch, no per-ROI export, no temporary allocation; the values are exactly those of
+ * sylph_roi_align_rois.  boxes_dev (R, 4) device, roi_image (R) host.  This is the ROI bank: it depends on the backbone only. */
+int sylph_roi_rows(sylph_ctx* ctx, int R, const float* boxes_dev, const int* roi_image, void* rows_out_dev);
+/* The generator's trainable tensors under the context's config as (state-dict key, offset, element count) triples in ONE flat fp32
+ * vector: code_generator.code_generator_head.support_set_shared_tower.{3 i, 3 i + 1}.{weight, bias}, .support_set_cls_conv.0.*,
+ * .support_set_cls_bias.0.* (BIAS_LAYER), .post_norm.* (POST_NORM "GN"), .conv_scale.scale (USE_WEIGHT_SCALE with POST_NORM or CONV_L2_NORM),
+ * .bias_scale.scale (BIAS_LAYER) -- code_generator.py:341-402,648-688.  init_norm.* is never used by the forward and is not in the vector.
+ * keys_out: max_entries x 128 bytes (NUL-terminated), or the three arrays NULL to ask for *n_out and *total_out (floats) alone. */
+int sylph_codegen_param_layout(sylph_ctx* ctx, int max_entries, char* keys_out, int64_t* offset_out, int64_t* numel_out, int* n_out,
+                               int64_t* total_out);
+/* Host copy of the FINALIZED generator in that layout / install another one (NULL: restore the finalized one).  Install re-packs the
+ * support convolutions, GroupNorm tables and tail constants as sylph_finalize_weights packs them, in place: cached support passes read the
+ * new tensors from their next call on, and from then every sylph_codegen* / sylph_normalize_codes result is bit-identical to a context
+ * finalized with those tensors.  Plans, the current batch and query records are not touched.  The context carries a generator stamp
+ * (sylph_codegen_stamp): 0 for the finalized generator, a fresh value per set, 0 again after a restore; shot-bank rows are a function of
+ * the generator, so a caller keeps the stamp with a bank (modelled on sylph_set_box_branch). */
+int sylph_get_code_generator(sylph_ctx* ctx, float* flat_host);
+int sylph_set_code_generator(sylph_ctx* ctx, const float* flat_host);
+int sylph_codegen_stamp(sylph_ctx* ctx, uint64_t* stamp);
+/* Workspace bytes of one training step on M shots in n_seg classes. */
+int sylph_codegen_train_bytes(sylph_ctx* ctx, int M, int n_seg, int64_t* bytes_out);
+/* What the binding and the tests need to know of a step's shape: the units of CGT_UNIT_SHOTS = 4 whole shots the weight gradient's row
+ * reduction is cut into, its reduce passes (fan-in 8, the final one included), the floats of debug_out.  NULL skips. */
+int sylph_codegen_train_shape(sylph_ctx* ctx, int M, int n_seg, int* units_out, int* passes_out, int64_t* debug_floats_out);
+/* CodeGeneratorHead.forward_roi_align, training branch (code_generator.py:924-1002 with :766-875), on rows_dev (n_rows, 49, 256) bf16:
+ * idx (host, M) selects bank rows, repeats allowed; the M shots are cut into n_seg consecutive segments of seg_len (host) shots.
+ *   per tower layer i: y_i = conv3x3_pad1(x_i, bf16(W_i)) + b_i; x_{i+1} = bf16(relu(GroupNorm32(y_i)))  (statistics per shot, fp32, eps 1e-5)
+ *   c[s] = mean_49(conv3x3_pad1(x_L, bf16(W_cls))) + b_cls, computed as Xsum[s] . bf16(W_cls)^T / 49 with Xsum the box sums of x_L (the
+ *   pool commutes with the conv); rb[s] likewise (0 without BIAS_LAYER); code_raw[j], bias_raw[j] = the shot means of segment j
+ *   code[j] = conv_scale * l2_normalize(GroupNorm32(code_raw[j]));  bias[j] = bias_scale * bias_raw[j] - log((1 - PRIOR_PROB) / PRIOR_PROB)
+ * params_dev: the caller's fp32 master copy in the layout above.  codes_out_dev (n_seg, 257): code ++ bias, what sylph_fcos_head and
+ * sylph_cls_grad take.  Saved activations stay in workspace_dev (sylph_codegen_train_bytes).  Needs no current batch. */
+int sylph_codegen_train_forward(sylph_ctx* ctx, const float* params_dev, const void* rows_dev, int n_rows, int M, const int* idx, int n_seg,
+                                const int* seg_len, void* workspace_dev, float* codes_out_dev);
+/* The backward of the preceding forward (the same workspace, params, rows, n_rows, M, n_seg): grad_codes_dev (n_seg, 257) =
+ * d loss / d codes_out -> grad_out_dev, flat in the layout above; a tensor that receives no gradient holds exact zeros.  Every rounding of
+ * the forward is treated as the identity; d y_i is rounded to bf16 where it enters the data- and weight-gradient MFMAs, all else is fp32.
+ * No atomics: the weight gradient's rows are summed per unit and the units in a fixed order, the same bits on every call and on every grid
+ * (SYLPH_CODEGEN_TRAIN_BLOCKS caps the blocks).  debug_out_dev: NULL, or sylph_codegen_train_shape's floats: every stage in fp32 --
+ *   per layer i: y_i (M 49, 256) | (mean, rstd) (M, 32, 2) | x_{i+1} as stored; Xsum (M, 2304) | c (M, 256) | rb (M) | code_raw (n_seg, 256) |
+ *   bias_raw (n_seg) | d code_raw | d bias_raw | d c (M, 256) | d rb (M) | with a tower: d Xsum (M, 2304) | d x_L | for i = L - 1 .. 0:
+ *   d y_i | d x_i (i >= 1). */
+int sylph_codegen_train_backward(sylph_ctx* ctx, const float* params_dev, const void* rows_dev, int n_rows, int M, int n_seg,
+                                 void* workspace_dev, const float* grad_codes_dev, float* grad_out_dev, float* debug_out_dev);
 /* Batch size, padded size and device bytes of a record; NULL skips. */
 int sylph_record_info(const sylph_record* rec, int* B, int* padded_h, int* padded_w, int64_t* bytes);
 /* Release a record, with the context that stored it (the stream is drained first).  If it is the current batch, no batch is current

@@ -398,6 +398,33 @@ int sylph_roi_align_rois(sylph_ctx* c, int R, const float* boxes, const int* roi
   return roi_align_alone(c, P, R, boxes, roi_image, out, "roi_align_rois");
 }
 
+/* see include/sylph_hip.h */
+int sylph_roi_rows(sylph_ctx* c, int R, const float* boxes_dev, const int* roi_image, void* rows_out_dev) {
+  RET(refuse_on_record(c, "sylph_roi_rows"));
+  if (c->dt != DT_BF16)
+    return fail(std::string("sylph_roi_rows: the ROI bank is bf16 (this context: ") + (c->dt == DT_F32S ? "f32s" : "fp32") + " storage)");
+  Plan* P = c->cur;
+  RET(check_rois(P, R, boxes_dev, roi_image));
+  if (!rows_out_dev) return fail("NULL argument");
+  if (R > 65535) return fail("ROI list: R = " + std::to_string(R) + " ROIs in one call; at most 65535");
+  HIPCHK(hipSetDevice(c->device));
+  {
+    OwnerScope own(c, P);
+    RET(ensure_level_table(c, P));
+  }
+  if ((size_t)R > c->roi_rows_cap) {  // the call's image table: the context's, grown on demand
+    OwnerScope ctx_owned(c, nullptr);
+    if (c->roi_rows_img) c->dfree(c->roi_rows_img);
+    c->roi_rows_img = nullptr; c->roi_rows_cap = 0;
+    RET(c->dalloc((void**)&c->roi_rows_img, (size_t)R * 2 * sizeof(int)));
+    c->roi_rows_cap = (size_t)R * 2;
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));  // the previous call may still be reading the table
+  HIPCHK(hipMemcpy(c->roi_rows_img, roi_image, (size_t)R * sizeof(int), hipMemcpyHostToDevice));
+  KCHK(launch_roi_align(c->dt, P->F, 256, P->lv_dev, c->cfg.nlevels, boxes_dev, c->roi_rows_img, R, 7, rows_out_dev, c->stream), "roi_rows");
+  return 0;
+}
+
 static int support_tap(sylph_ctx* c, int stage, int index, const SupportPass::SupTap** t, int* n) {
   Plan* P = c->cur;
   const SupportPass* Q = P ? P->sup_last : nullptr;

@@ -266,6 +266,16 @@ struct sylph_ctx {
   uint64_t box_stamp = 0, box_stamp_next = 0;
   // the box branch as installed (box_w (Cout, 256, 3, 3) in torch order, box_b (Cout), level_scales) and as finalized (box_w0, box_b0, box_s0)
   std::vector<float> box_w, box_b, box_w0, box_b0, box_s0;
+  // sylph_codegen_train_forward: the workspace and the episode sizes of the last forward (what a backward must be given again)
+  void* cgt_ws = nullptr;
+  int cgt_M = 0, cgt_nseg = 0, cgt_rows = 0;
+  // sylph_set_code_generator: 0 while the support path runs the finalized generator, else the value of the set that installed the current
+  // one (cg_stamp_next counts up); cg_flat / cg_flat0: the generator as installed / as finalized, in the flat layout of
+  // sylph_codegen_param_layout (empty: the config is not trainable or no generator was loaded)
+  uint64_t cg_stamp = 0, cg_stamp_next = 0;
+  std::vector<float> cg_flat, cg_flat0;
+  int* roi_rows_img = nullptr;  // sylph_roi_rows: the image table of the call in flight (grown on demand)
+  size_t roi_rows_cap = 0;
   void* zeros = nullptr;  // 256 B of zeros (conv out-of-image taps)
   // small batches: the two FCOS towers of a head pass run on two streams (fork / join events around the bbox tower, api_head.hip)
   hipStream_t side_stream = nullptr;
@@ -621,6 +631,7 @@ int pack_conv_grouped(sylph_ctx* c, const HostTensor& w, const std::string& key,
 int make_conv_bias(sylph_ctx* c, const std::vector<std::string>& names, ConvLayer* L);
 int make_c3sc(sylph_ctx* c, const HostTensor& w3, const float* s3, const float* h3, const HostTensor& ws, const float* ss, const float* hs, ConvLayer* L);
 int make_gn(sylph_ctx* c, const std::string& name, GNLayer* G);
+void capture_code_generator(sylph_ctx* c);  // api_codegen_train.hip
 int upload_f32(sylph_ctx* c, const float** dev, const HostTensor* t, const std::string& what, size_t expect = 0);
 int make_lin(sylph_ctx* c, const std::string& name, sylph_ctx::Lin* L);
 // a MobileNetV2 block from host tensors: w / scale / shift [3] = expand (nullptr for t == 1), depthwise (hid, 1, 3, 3), project

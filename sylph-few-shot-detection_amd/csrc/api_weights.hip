@@ -620,6 +620,7 @@ int sylph_finalize_weights(sylph_ctx* c) {
       c->cg_bias_prior = bv->data[0];
     }
     c->has_codegen = true;
+    capture_code_generator(c);
   }
   if (c->cfg.cg_type == 1 && has_prefix(c, "code_generator.box_pooler")) {
     const std::string rp = "code_generator";

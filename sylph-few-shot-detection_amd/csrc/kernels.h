@@ -383,4 +383,26 @@ int launch_shot_combine(const float* rows, int row_ld, const int* idx_dev, const
                         int has_w, int has_s, float* code_out, float* wnorm_out, hipStream_t s);
 int launch_shot_mean_tokens(const float* rows, int row_ld, const int* idx_dev, const int2* seg_dev, int n_seg, float* out, hipStream_t s);
 
+// codegen_train.hip: training-mode forward of the CodeGenerator on a bank of ROI rows and its backward down to every parameter
+constexpr int CGT_MAX_TOWER = 30;    // TOWER_LAYERS entries
+constexpr int CGT_UNIT_SHOTS = 4;    // shots behind one weight-gradient partial: fixed by M, so the sums do not depend on the grid
+constexpr int CGT_FANIN = 8;         // partials added per reduce pass
+constexpr int CGT_MAX_BLOCKS = 4096; // SYLPH_CODEGEN_TRAIN_BLOCKS overrides it
+struct CgtCfg { int L, has_bias, post_norm, l2_norm, has_conv_scale; float prior; };
+// offsets (floats) of the trainable tensors in the flat parameter / gradient vector; -1: the config has no such tensor
+struct CgtParams { long tw[CGT_MAX_TOWER], tb[CGT_MAX_TOWER], tg[CGT_MAX_TOWER], tbe[CGT_MAX_TOWER], cw, cb, bw, bb, pg, pb, cs, bs, total; };
+// offsets (bytes) of the workspace's parts
+struct CgtWs {
+  size_t idx, seg, wf[CGT_MAX_TOWER], wd[CGT_MAX_TOWER], wh, wht, wb, y[CGT_MAX_TOWER], st[CGT_MAX_TOWER], x[CGT_MAX_TOWER], xsum, c, rb, code_raw,
+      bias_raw, dcode_raw, dbias_raw, tpg, tpb, tpcs, tpbs, dc, drb, dxsum, dxa, dya, gsg, gsb, gsd, part, total;
+  int units, passes;
+};
+void cgt_param_layout(const CgtCfg& cfg, CgtParams* p);
+void cgt_workspace(const CgtCfg& cfg, int M, int n_seg, CgtWs* w);
+size_t cgt_debug_floats(const CgtCfg& cfg, int M, int n_seg);
+// rows: the bank, (n_rows, 49, 256) bf16; ws: cgt_workspace bytes whose idx (M ints) and seg (n_seg int2 {first shot, shots}) are filled
+int launch_cgt_forward(const CgtCfg& cfg, const float* params, const void* rows, int M, int n_seg, char* ws, float* codes_out, hipStream_t s);
+int launch_cgt_backward(const CgtCfg& cfg, const float* params, const void* rows, int M, int n_seg, char* ws, const float* grad_codes,
+                        float* grad_out, float* debug_out, hipStream_t s);
+
 }  // namespace sylph

@@ -82,6 +82,15 @@ PROTOTYPES = {
     "sylph_box_branch_shape": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(ctypes.c_uint64)]),
     "sylph_get_box_branch": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
     "sylph_set_box_branch": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
+    "sylph_roi_rows": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p]),
+    "sylph_codegen_param_layout": (c_int, [c_void_p, c_int, ctypes.c_char_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int), POINTER(c_int64)]),
+    "sylph_get_code_generator": (c_int, [c_void_p, POINTER(c_float)]),
+    "sylph_set_code_generator": (c_int, [c_void_p, POINTER(c_float)]),
+    "sylph_codegen_stamp": (c_int, [c_void_p, POINTER(ctypes.c_uint64)]),
+    "sylph_codegen_train_bytes": (c_int, [c_void_p, c_int, c_int, POINTER(c_int64)]),
+    "sylph_codegen_train_shape": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int64)]),
+    "sylph_codegen_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int), c_void_p, c_void_p]),
+    "sylph_codegen_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylph_roi_align": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sylph_roi_align_rois": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p]),
     "sylph_decode_nms": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,

@@ -1300,6 +1300,142 @@ class Engine:
               "shot_combine")
         return codes, wn
 
+    # ---- meta-training of the code generator (sylph_amd/metatrain.py) ------------------------------------------------------------------
+
+    def roi_rows(self, boxes: torch.Tensor, roi_image) -> torch.Tensor:
+        """The ROI bank rows of a ROI list over the current batch (sylph_roi_rows) -> (R, 49, 256) bf16, position-major: the values of
+        roi_align_rois, written in one launch.  They depend on the backbone alone."""
+        bx, ri = self._check_rois(boxes, roi_image)
+        self._stream()
+        out = torch.empty(len(ri), 49, 256, device=self.device, dtype=torch.bfloat16)
+        self._keep_boxes = bx
+        check(self.L.sylph_roi_rows(self._ctx, len(ri), _ptr(bx), _iarr(ri), _ptr(out)), "roi_rows")
+        return out
+
+    def codegen_params(self) -> List[Tuple[str, int, int]]:
+        """(state-dict key, offset, element count) of the generator's trainable tensors in the flat fp32 vector (sylph_codegen_param_layout)."""
+        n, total = c_int(0), c_int64(0)
+        check(self.L.sylph_codegen_param_layout(self._ctx, 0, None, None, None, ctypes.byref(n), ctypes.byref(total)), "codegen_param_layout")
+        keys = ctypes.create_string_buffer(128 * n.value)
+        off, cnt = (c_int64 * n.value)(), (c_int64 * n.value)()
+        check(self.L.sylph_codegen_param_layout(self._ctx, n.value, keys, off, cnt, ctypes.byref(n), ctypes.byref(total)), "codegen_param_layout")
+        return [(keys.raw[128 * i:128 * (i + 1)].split(b"\0", 1)[0].decode(), int(off[i]), int(cnt[i])) for i in range(n.value)]
+
+    @staticmethod
+    def codegen_param_shape(key: str, numel: int) -> Tuple[int, ...]:
+        """torch shape of a layout entry"""
+        if key.endswith(".weight") and numel % 2304 == 0:
+            return (numel // 2304, 256, 3, 3)
+        return (numel,)
+
+    def codegen_flat_size(self) -> int:
+        lay = self.codegen_params()
+        return lay[-1][1] + lay[-1][2]
+
+    def code_generator(self) -> torch.Tensor:
+        """The checkpoint's generator as the flat fp32 vector of codegen_params() (CPU)."""
+        flat = torch.empty(self.codegen_flat_size(), dtype=torch.float32)
+        check(self.L.sylph_get_code_generator(self._ctx, ctypes.cast(flat.data_ptr(), ctypes.POINTER(ctypes.c_float))), "get_code_generator")
+        return flat
+
+    def codegen_stamp(self) -> int:
+        """0 while the support path runs the checkpoint's generator, else the stamp of the set_code_generator that installed the current one"""
+        st = ctypes.c_uint64(0)
+        check(self.L.sylph_codegen_stamp(self._ctx, ctypes.byref(st)), "codegen_stamp")
+        return st.value
+
+    def set_code_generator(self, flat):
+        """Install a generator (the flat vector of codegen_params(), or a dict of its state-dict entries; None: the checkpoint's).  From the
+        next support pass on every codegen* / normalize_codes result is bit-identical to an engine loaded with a state dict carrying these
+        tensors.  The current batch and query records stay as they are; shot banks built under another generator are refused."""
+        self._stream()
+        if flat is None:
+            check(self.L.sylph_set_code_generator(self._ctx, None), "set_code_generator")
+            return
+        if isinstance(flat, dict):
+            vec = self.code_generator()
+            for k, o, n in self.codegen_params():
+                if k in flat:
+                    vec[o:o + n] = flat[k].detach().to("cpu", torch.float32).reshape(-1)
+            flat = vec
+        flat = torch.as_tensor(flat).detach().to("cpu", torch.float32).reshape(-1).contiguous()
+        if flat.numel() != self.codegen_flat_size():
+            raise ValueError(f"set_code_generator: the flat vector holds {self.codegen_flat_size()} floats under this config, got {flat.numel()}")
+        check(self.L.sylph_set_code_generator(self._ctx, ctypes.cast(flat.data_ptr(), ctypes.POINTER(ctypes.c_float))), "set_code_generator")
+
+    def codegen_train_shape(self, M: int, n_seg: int) -> Dict[str, int]:
+        """units / passes of the weight gradient's reduction and the floats of the debug export for a step of M shots in n_seg classes"""
+        u, p, d = c_int(0), c_int(0), c_int64(0)
+        check(self.L.sylph_codegen_train_shape(self._ctx, int(M), int(n_seg), ctypes.byref(u), ctypes.byref(p), ctypes.byref(d)), "codegen_train_shape")
+        return {"units": u.value, "passes": p.value, "debug_floats": d.value}
+
+    def codegen_train_forward(self, params: torch.Tensor, rows: torch.Tensor, idx, seg_len) -> torch.Tensor:
+        """Training-mode forward of the generator (sylph_codegen_train_forward): params the flat fp32 device vector, rows the (n_rows, 49,
+        256) bf16 ROI bank, idx (M) bank rows cut into consecutive segments of seg_len shots -> (n_seg, 257) normalised code ++ processed
+        bias.  The saved activations stay in a workspace of the engine until the backward.  Needs no current batch."""
+        if not (torch.is_tensor(params) and params.is_cuda and params.dtype == torch.float32 and params.is_contiguous()):
+            raise ValueError("codegen_train_forward: params must be a contiguous fp32 tensor on the device")
+        if not (torch.is_tensor(rows) and rows.is_cuda and rows.dtype == torch.bfloat16 and rows.is_contiguous() and tuple(rows.shape[1:]) == (49, 256)):
+            raise ValueError("codegen_train_forward: rows must be a contiguous (n_rows, 49, 256) bf16 tensor on the device")
+        ix = [int(i) for i in (idx.tolist() if hasattr(idx, "tolist") else idx)]
+        sl = [int(n) for n in (seg_len.tolist() if hasattr(seg_len, "tolist") else seg_len)]
+        self._stream()
+        need = c_int64(0)
+        check(self.L.sylph_codegen_train_bytes(self._ctx, len(ix), len(sl), ctypes.byref(need)), "codegen_train_bytes")
+        if params.numel() != self.codegen_flat_size():
+            raise ValueError(f"codegen_train_forward: params holds {params.numel()} floats, the layout {self.codegen_flat_size()}")
+        if getattr(self, "_cgt_ws", None) is None or self._cgt_ws.numel() < need.value:
+            self._cgt_ws = torch.empty(need.value, device=self.device, dtype=torch.uint8)
+        codes = torch.empty(len(sl), 257, device=self.device)
+        check(self.L.sylph_codegen_train_forward(self._ctx, _ptr(params), _ptr(rows), rows.shape[0], len(ix), _iarr(ix), len(sl), _iarr(sl),
+                                                 _ptr(self._cgt_ws), _ptr(codes)), "codegen_train_forward")
+        self._cgt_last = (params, rows, len(ix), len(sl))
+        return codes
+
+    def codegen_train_backward(self, grad_codes: torch.Tensor, debug: bool = False):
+        """Backward of the preceding codegen_train_forward: grad_codes (n_seg, 257) = d loss / d codes -> the flat gradient (device, the
+        layout of codegen_params()); with debug -> (grad, stages), stages a dict of every exported stage in fp32 (see include/sylph_hip.h)."""
+        last = getattr(self, "_cgt_last", None)
+        if last is None:
+            raise ValueError("codegen_train_backward: no codegen_train_forward precedes it")
+        params, rows, M, n_seg = last
+        g = torch.as_tensor(grad_codes).to(self.device, torch.float32).contiguous()
+        if tuple(g.shape) != (n_seg, 257):
+            raise ValueError(f"codegen_train_backward: grad_codes must be ({n_seg}, 257), got {tuple(g.shape)}")
+        self._stream()
+        grad = torch.empty_like(params)
+        dbg = torch.empty(self.codegen_train_shape(M, n_seg)["debug_floats"], device=self.device) if debug else None
+        check(self.L.sylph_codegen_train_backward(self._ctx, _ptr(params), _ptr(rows), rows.shape[0], M, n_seg, _ptr(self._cgt_ws), _ptr(g),
+                                                  _ptr(grad), _ptr(dbg)), "codegen_train_backward")
+        self._keep_cgt = g
+        if not debug:
+            return grad
+        L, R = int(self.sc.cg_tower_layers), M * 49
+        st, o = {}, 0
+
+        def take(name, *shape):
+            nonlocal o
+            n = 1
+            for s in shape:
+                n *= s
+            st[name] = dbg[o:o + n].view(*shape)
+            o += n
+        for i in range(L):
+            take(f"y{i}", R, 256)
+            take(f"stats{i}", M, 32, 2)
+            take(f"x{i + 1}", R, 256)
+        take("xsum", M, 2304); take("c", M, 256); take("rb", M); take("code_raw", n_seg, 256); take("bias_raw", n_seg)
+        take("d_code_raw", n_seg, 256); take("d_bias_raw", n_seg); take("d_c", M, 256); take("d_rb", M)
+        if L:
+            take("d_xsum", M, 2304)
+            take(f"d_x{L}", R, 256)
+            for i in range(L - 1, -1, -1):
+                take(f"d_y{i}", R, 256)
+                if i >= 1:
+                    take(f"d_x{i}", R, 256)
+        assert o == dbg.numel()
+        return grad, st
+
     def roi_table_uploads(self) -> int:
         """How many codegen* calls of this engine uploaded their ROI tables (a repeated identical list uploads none)."""
         n = c_int64(0)

@@ -292,6 +292,7 @@ def build_shot_bank(model, data_loader, chunk: int = 10):
         raise ValueError(f"chunk must be at least 1, got {chunk}")
     engine = model.engine
     bank = ShotBank(engine.shot_key(), device=engine.device)
+    bank.stamp = engine.codegen_stamp()
     seen = 0
     with ExitStack() as stack:
         if isinstance(model, nn.Module):
@@ -308,6 +309,28 @@ def build_shot_bank(model, data_loader, chunk: int = 10):
     return bank
 
 
+def build_roi_bank(model, data_loader):
+    """A RoiBank (sylph_amd.metatrain) of every annotated instance of a loader, at one backbone pass per image: the 7x7x256 ROI maps the
+    code generator's training forward starts from.  The loader is build_shot_bank's: each item a list of annotated records, run as ONE
+    batch (model.forward_roi_rows).  The rows depend on the backbone alone, not on the generator."""
+    from .metatrain import RoiBank
+    engine = model.engine
+    bank = RoiBank(device=engine.device)
+    seen = 0
+    with ExitStack() as stack:
+        if isinstance(model, nn.Module):
+            stack.enter_context(inference_context(model))
+        stack.enter_context(torch.no_grad())
+        for records in data_loader:
+            rows, class_ids = model.forward_roi_rows(records)
+            if rows is not None:
+                bank.append(rows, class_ids)
+            seen += len(records)
+    bank.tensor()
+    logger.info(f"Banked {len(bank)} ROI maps of {len(bank.classes())} classes from {seen} images, {bank.nbytes} device bytes")
+    return bank
+
+
 def class_codes_from_bank(model, bank, idx, seg_len, class_ids, class_names=None, normalize: bool = True) -> List[Dict[str, Any]]:
     """The class codes of one draw from a ShotBank (bank.draw), with no support pass: segment j -- the rows idx[...] of seg_len[j]
     shots -- is class class_ids[j].  Returns inference_on_annotated_images' records ({"support_set_target", "class_name",
@@ -317,6 +340,7 @@ def class_codes_from_bank(model, bank, idx, seg_len, class_ids, class_names=None
     (sylph_normalize_codes with cls_weight_norm) like the runner's; the ROIEncoder's codes need none."""
     engine = model.engine
     bank.check_key(engine)
+    bank.check_stamp(engine)
     if len(class_ids) != len(seg_len):
         raise ValueError(f"{len(class_ids)} class ids for {len(seg_len)} segments")
     with torch.no_grad():

@@ -480,6 +480,38 @@ class MetaOneStageDetector(nn.Module):
         self.backbone(images=[rec["image"] for rec in records])
         return self.engine.codegen_shots(torch.cat(boxes, dim=0), image_index), image_index, ann_index, class_ids
 
+    def forward_roi_rows(self, records: List[Dict[str, Any]]):
+        """ROI-bank rows of annotated images at ONE backbone pass per image: every annotated instance of `records`, in record order, then
+        box order -> (rows (R, 49, 256) bf16 on the device, class_ids [R]); (None, []) when no record carries a box (Engine.roi_rows)."""
+        assert not self.training, "Not for training"
+        boxes, image_index, class_ids = [], [], []
+        for b, rec in enumerate(records):
+            inst = rec.get("instances")
+            if inst is None or len(inst.gt_boxes.tensor) == 0:
+                continue
+            gt = inst.gt_boxes.tensor.detach().float().cpu().reshape(-1, 4)
+            cls = torch.as_tensor(inst.gt_classes).reshape(-1).tolist()
+            assert len(cls) == gt.shape[0], f"record {b}: {len(cls)} classes for {gt.shape[0]} boxes"
+            boxes.append(gt)
+            image_index += [b] * len(cls)
+            class_ids += [int(c) for c in cls]
+        if not boxes:
+            return None, []
+        self.backbone(images=[rec["image"] for rec in records])
+        return self.engine.roi_rows(torch.cat(boxes, dim=0), image_index), class_ids
+
+    def train_code_generator(self, bank, records, annotations, **kw):
+        """Meta-train the code generator on the frozen detector (sylph_amd.metatrain.train_code_generator; kw: iters, classes_per_step,
+        shots, records_per_step, lr, clip_norm, momentum, weight_decay, lr_steps, lr_gamma, trainable, seed).  Returns (state_dict,
+        losses); set_code_generator installs the state dict."""
+        from .metatrain import train_code_generator
+        return train_code_generator(self, bank, records, annotations, **kw)
+
+    def set_code_generator(self, state):
+        """Install a trained generator (train_code_generator's state dict, a flat vector, or None for the checkpoint's) into the serving
+        path (Engine.set_code_generator): shot banks built under another generator are refused from then on."""
+        self.engine.set_code_generator(state)
+
     def normalize_class_code(self, codes: List[Dict]):
         """code_generator.py:877-897 via meta_one_stage_detector.py:256-259 (mutates the list)."""
         assert self.episodic_learning

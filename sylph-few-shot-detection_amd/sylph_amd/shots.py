@@ -32,6 +32,7 @@ class ShotBank:
         self.image_ids: List[int] = []
         self.ann_ids: List[int] = []
         self._parts: List[torch.Tensor] = []  # appended chunks not yet concatenated into rows
+        self.stamp = 0  # Engine.codegen_stamp() when the rows were made: 0 = the checkpoint's generator (build_shot_bank sets it)
 
     def __len__(self) -> int:
         return len(self.class_ids)
@@ -101,8 +102,17 @@ class ShotBank:
                 raise ValueError(f"shot bank: made with {f} = {self.key[f]!r}, the engine has {f} = {theirs[f]!r}; its rows are valid only "
                                  "under the weights, dtype and generator config that made them")
 
+    def check_stamp(self, engine) -> None:
+        """refuse a bank whose rows were made by another generator than the one `engine` runs now (Engine.set_code_generator)"""
+        now = int(engine.codegen_stamp())
+        if int(self.stamp) != now:
+            raise ValueError(f"shot bank: its rows were made under generator stamp {int(self.stamp)}, the engine now runs stamp {now} "
+                             "(set_code_generator installed another generator since): build the bank again under the current generator, or "
+                             "restore the one it was made under (set_code_generator(None) for stamp 0)")
+
     def save(self, path: str) -> None:
-        torch.save({"key": dict(self.key), "rows": self.tensor().cpu(), "class_ids": list(self.class_ids), "image_ids": list(self.image_ids),
+        torch.save({"key": dict(self.key), **({"stamp": int(self.stamp)} if int(self.stamp) else {}),  # (a bank of the checkpoint's generator saves what it always saved)
+                    "rows": self.tensor().cpu(), "class_ids": list(self.class_ids), "image_ids": list(self.image_ids),
                     "ann_ids": list(self.ann_ids)}, path)
 
     @classmethod
@@ -110,6 +120,7 @@ class ShotBank:
         """The saved bank, on `device` (default: the engine's, else the CPU).  With an engine the key is checked (check_key)."""
         d = torch.load(path, map_location="cpu")
         bank = cls(d["key"], device=device if device is not None else (engine.device if engine is not None else None))
+        bank.stamp = int(d.get("stamp", 0))
         if engine is not None:
             bank.check_key(engine)
         if len(d["class_ids"]):
