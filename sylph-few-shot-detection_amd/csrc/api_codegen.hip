@@ -553,13 +553,10 @@ int sylph_shot_combine(sylph_ctx* c, const float* rows, int n_rows, int M, const
   const size_t seg_off = ((size_t)M + 1) / 2 * 2, ints = seg_off + 2 * (size_t)n_seg, need = ints * sizeof(int);
   if (c->shot_ev) HIPCHK(hipEventSynchronize(c->shot_ev));
   else HIPCHK(hipEventCreateWithFlags(&c->shot_ev, hipEventDisableTiming));
-  Plan* owner = c->alloc_owner;
-  c->alloc_owner = nullptr;  // the context's, not a plan's
-  struct Restore { sylph_ctx* c; Plan* p; ~Restore() { c->alloc_owner = p; } } restore{c, owner};
   if (need > c->shot_tab_cap) {
     if (c->shot_tab) c->dfree(c->shot_tab);
     c->shot_tab = nullptr; c->shot_tab_cap = 0;
-    RET(c->dalloc(&c->shot_tab, need * 2));
+    RET(ctx_alloc(c, &c->shot_tab, need * 2));
     c->shot_tab_cap = need * 2;
   }
   const int hdim = c->cfg.head_fc_dim > 256 ? c->cfg.head_fc_dim : 256;
@@ -567,8 +564,8 @@ int sylph_shot_combine(sylph_ctx* c, const float* rows, int n_rows, int M, const
     if (c->shot_cls) c->dfree(c->shot_cls);
     if (c->shot_h) c->dfree(c->shot_h);
     c->shot_cls = c->shot_h = nullptr; c->shot_seg_cap = 0;
-    RET(c->dalloc((void**)&c->shot_cls, (size_t)n_seg * 2 * 256 * sizeof(float)));
-    RET(c->dalloc((void**)&c->shot_h, (size_t)2 * n_seg * 2 * hdim * sizeof(float)));
+    RET(ctx_alloc(c, (void**)&c->shot_cls, (size_t)n_seg * 2 * 256 * sizeof(float)));
+    RET(ctx_alloc(c, (void**)&c->shot_h, (size_t)2 * n_seg * 2 * hdim * sizeof(float)));
     c->shot_seg_cap = n_seg * 2;
   }
   c->shot_host.assign(ints, 0);

@@ -118,10 +118,7 @@ int install_code_generator(sylph_ctx* c, const CgtCfg& g, const std::vector<floa
   if (c->side_stream) HIPCHK(hipStreamSynchronize(c->side_stream));
   auto put_conv = [&](ConvLayer& L, long wo, long bo, int cout) -> int {
     if (L.KH != 3 || L.KW != 3 || L.Cin != 256 || L.Cout != cout || !L.w || !L.shift) return fail("sylph_set_code_generator: internal: unexpected support conv");
-    std::vector<uint16_t> pk((size_t)L.Cout_pad * 2304, 0);
-    for (int n = 0; n < cout; ++n)
-      for (int ci = 0; ci < 256; ++ci)
-        for (int tap = 0; tap < 9; ++tap) pk[(size_t)n * 2304 + (size_t)tap * 256 + ci] = f2bf_host(flat[(size_t)wo + ((size_t)n * 256 + ci) * 9 + tap]);
+    const std::vector<uint16_t> pk = pack_conv3x3_bf16(flat.data() + wo, cout, L.Cout_pad);
     std::vector<float> sh((size_t)L.Cout_pad, 0.f);
     std::copy(flat.begin() + bo, flat.begin() + bo + cout, sh.begin());
     HIPCHK(hipMemcpy(L.w, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));

@@ -34,6 +34,27 @@ int finetune_src(sylph_ctx* c, const char* who, Plan** P_out, TowerSrc* src) {
   return 0;
 }
 
+// the ground truth and the assignment rule of sylph_fcos_targets / sylph_box_samples checked, under the entry's name, and the kernels'
+// FcosTargetCfg filled
+int fcos_target_cfg(sylph_ctx* c, const std::string& w, int n_gt, const float* boxes_dev, const int* gt_class_dev, const int* gt_image_dev,
+                    const float* sizes_of_interest, int n_soi, int center_sample, float pos_radius, FcosTargetCfg* t) {
+  if (n_gt < 0) return fail(w + ": n_gt is negative");
+  if (n_gt > 0 && (!boxes_dev || !gt_class_dev || !gt_image_dev)) return fail(w + ": a ground-truth array is NULL");
+  const int L = c->cfg.nlevels;
+  if (!sizes_of_interest || n_soi != L - 1)
+    return fail(w + ": sizes_of_interest must hold " + std::to_string(L - 1) + " values (one less than the levels), got " + std::to_string(n_soi));
+  if (!(pos_radius > 0.f) && center_sample) return fail(w + ": pos_radius must be positive");
+  memset(t, 0, sizeof(*t));
+  for (int l = 0; l < L; ++l) {  // fcos_outputs.py:150-160: [-1, s0], [s0, s1], .., [s_last, INF]
+    t->strides[l] = c->cfg.strides[l];
+    t->lo[l] = l == 0 ? -1.f : sizes_of_interest[l - 1];
+    t->hi[l] = l < n_soi ? sizes_of_interest[l] : 100000000.f;
+  }
+  t->center_sample = center_sample ? 1 : 0;
+  t->radius = pos_radius;
+  return 0;
+}
+
 }  // namespace
 
 /* see include/sylph_hip.h */
@@ -43,22 +64,10 @@ int sylph_fcos_targets(sylph_ctx* c, int n_gt, const float* boxes_dev, const int
   Plan* P = nullptr;
   TowerSrc src;
   RET(finetune_src(c, "sylph_fcos_targets", &P, &src));
-  if (n_gt < 0) return fail("sylph_fcos_targets: n_gt is negative");
-  if (n_gt > 0 && (!boxes_dev || !gt_class_dev || !gt_image_dev)) return fail("sylph_fcos_targets: a ground-truth array is NULL");
   if (!labels_out_dev || !num_pos_out_dev) return fail("sylph_fcos_targets: an output is NULL");
-  const int L = c->cfg.nlevels;
-  if (!sizes_of_interest || n_soi != L - 1)
-    return fail("sylph_fcos_targets: sizes_of_interest must hold " + std::to_string(L - 1) + " values (one less than the levels), got " + std::to_string(n_soi));
-  if (!(pos_radius > 0.f) && center_sample) return fail("sylph_fcos_targets: pos_radius must be positive");
   FcosTargetCfg t;
-  memset(&t, 0, sizeof(t));
-  for (int l = 0; l < L; ++l) {  // fcos_outputs.py:150-160: [-1, s0], [s0, s1], .., [s_last, INF]
-    t.strides[l] = c->cfg.strides[l];
-    t.lo[l] = l == 0 ? -1.f : sizes_of_interest[l - 1];
-    t.hi[l] = l < n_soi ? sizes_of_interest[l] : 100000000.f;
-  }
-  t.center_sample = center_sample ? 1 : 0;
-  t.radius = pos_radius;
+  RET(fcos_target_cfg(c, "sylph_fcos_targets", n_gt, boxes_dev, gt_class_dev, gt_image_dev, sizes_of_interest, n_soi, center_sample, pos_radius, &t));
+  const int L = c->cfg.nlevels;
   HIPCHK(hipSetDevice(c->device));
   KCHK(launch_fcos_targets(P->head_segs, P->B * L, L, P->hl[0] * P->wl[0], t, n_gt, boxes_dev, gt_class_dev, gt_image_dev, labels_out_dev,
                            num_pos_out_dev, c->stream),
@@ -89,12 +98,8 @@ int sylph_cls_grad(sylph_ctx* c, const int* labels_dev, const float* cls_conv_de
   if (!(gamma >= 0.f)) return fail("sylph_cls_grad: gamma must not be negative");
   HIPCHK(hipSetDevice(c->device));
   if (!c->ft_codes) {
-    Plan* owner = c->alloc_owner;
-    c->alloc_owner = nullptr;  // the context's: plan eviction must not free it
-    int r = c->dalloc(&c->ft_codes, 32 * 256 * sizeof(bf16_t));
-    if (r == 0) r = c->dalloc((void**)&c->ft_bias, 32 * sizeof(float));
-    c->alloc_owner = owner;
-    RET(r);
+    RET(ctx_alloc(c, &c->ft_codes, 32 * 256 * sizeof(bf16_t)));
+    RET(ctx_alloc(c, (void**)&c->ft_bias, 32 * sizeof(float)));
   }
   const Plan* PP = P;
   for (int n0 = 0; n0 < N; n0 += 32) {
@@ -133,11 +138,7 @@ int grow_ints(sylph_ctx* c, int** p, size_t* cap, size_t need) {
   if (need <= *cap) return 0;
   c->dfree(*p);
   *p = nullptr; *cap = 0;
-  Plan* owner = c->alloc_owner;
-  c->alloc_owner = nullptr;  // the context's: plan eviction must not free it
-  const int r = c->dalloc((void**)p, need * sizeof(int));
-  c->alloc_owner = owner;
-  RET(r);
+  RET(ctx_alloc(c, (void**)p, need * sizeof(int)));
   *cap = need;
   return 0;
 }
@@ -145,15 +146,7 @@ int grow_ints(sylph_ctx* c, int** p, size_t* cap, size_t need) {
 // pred, pred_taps and the biases re-packed from (Cout, 256, 3, 3) / (Cout) into the buffers the cached launches captured, as
 // sylph_finalize_weights packs them (api_weights.hip: pack_conv, the tap table)
 int install_box_branch(sylph_ctx* c, const std::vector<float>& w, const std::vector<float>& b, const std::vector<float>& scales) {
-  const int cp = c->pred.Cout, sw = (3 * cp + 3) & ~3;
-  std::vector<uint16_t> pk((size_t)c->pred.Cout_pad * 2304, 0), tw((size_t)64 * 256, 0);
-  for (int n = 0; n < cp; ++n)
-    for (int ci = 0; ci < 256; ++ci)
-      for (int tap = 0; tap < 9; ++tap) {
-        const uint16_t v = f2bf_host(w[((size_t)n * 256 + ci) * 9 + tap]);
-        pk[(size_t)n * 2304 + (size_t)tap * 256 + ci] = v;
-        tw[(size_t)((tap / 3) * sw + (tap % 3) * cp + n) * 256 + ci] = v;
-      }
+  const std::vector<uint16_t> pk = pack_conv3x3_bf16(w.data(), c->pred.Cout, c->pred.Cout_pad), tw = pack_pred_taps(w.data(), c->pred.Cout);
   std::vector<float> sh(b);
   sh.resize((size_t)c->pred.Cout_pad, 0.f);
   HIPCHK(hipSetDevice(c->device));
@@ -198,23 +191,11 @@ int sylph_box_samples(sylph_ctx* c, int n_gt, const float* boxes_dev, const int*
   if (!coef || !c->pred_taps)
     return fail(w + ": the bbox tower's last GroupNorm is not deferred in this build (SYLPH_FUSE_GN_LOGITS=0, or a prediction conv the fused "
                 "pass does not take)");
-  if (n_gt < 0) return fail(w + ": n_gt is negative");
-  if (n_gt > 0 && (!boxes_dev || !gt_class_dev || !gt_image_dev)) return fail(w + ": a ground-truth array is NULL");
   if (max_samples < 0) return fail(w + ": max_samples is negative");
   if (!count_out_dev || !status_dev || (max_samples > 0 && (!patches_out_dev || !targets_out_dev || !info_out_dev))) return fail(w + ": an output is NULL");
-  const int L = c->cfg.nlevels;
-  if (!sizes_of_interest || n_soi != L - 1)
-    return fail(w + ": sizes_of_interest must hold " + std::to_string(L - 1) + " values (one less than the levels), got " + std::to_string(n_soi));
-  if (!(pos_radius > 0.f) && center_sample) return fail(w + ": pos_radius must be positive");
   FcosTargetCfg t;
-  memset(&t, 0, sizeof(t));
-  for (int l = 0; l < L; ++l) {
-    t.strides[l] = c->cfg.strides[l];
-    t.lo[l] = l == 0 ? -1.f : sizes_of_interest[l - 1];
-    t.hi[l] = l < n_soi ? sizes_of_interest[l] : 100000000.f;
-  }
-  t.center_sample = center_sample ? 1 : 0;
-  t.radius = pos_radius;
+  RET(fcos_target_cfg(c, w, n_gt, boxes_dev, gt_class_dev, gt_image_dev, sizes_of_interest, n_soi, center_sample, pos_radius, &t));
+  const int L = c->cfg.nlevels;
   HIPCHK(hipSetDevice(c->device));
   const int max_rows = P->hl[0] * P->wl[0], nseg = P->B * L;
   RET(grow_ints(c, &c->bx_assign, &c->bx_assign_cap, (size_t)P->B * P->Ltot));

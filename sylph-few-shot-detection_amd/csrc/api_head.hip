@@ -1045,13 +1045,8 @@ int sylph_record_store(sylph_ctx* c, sylph_record** out) {
   R->coef_bytes = P->cls_coef ? P->cls_gn.coef_bytes : 0;
   R->partial_bytes = P->cls_coef ? P->cls_gn.partial_bytes : 0;
   const size_t total = pad(R->feat_bytes) + pad(R->pred_bytes) + pad(R->coef_bytes) + pad(R->partial_bytes);
-  {
-    Plan* owner = c->alloc_owner;
-    c->alloc_owner = nullptr;  // the context's, not a plan's: eviction never frees a record
-    const int r = c->dalloc(&R->base, total);
-    c->alloc_owner = owner;
-    if (r != 0) return fail("sylph_record_store: cannot allocate the record's " + std::to_string(total) + " bytes (" + sylph_last_error() + ")");
-  }
+  if (ctx_alloc(c, &R->base, total) != 0)  // eviction never frees a record
+    return fail("sylph_record_store: cannot allocate the record's " + std::to_string(total) + " bytes (" + sylph_last_error() + ")");
   char* p = (char*)R->base;
   R->feat = p; p += pad(R->feat_bytes);
   R->pred = (const float*)p; p += pad(R->pred_bytes);

@@ -508,6 +508,11 @@ struct OwnerScope {
   OwnerScope(sylph_ctx* c_, Plan* P) : c(c_), prev(c_->alloc_owner) { c->alloc_owner = P; }
   ~OwnerScope() { c->alloc_owner = prev; }
 };
+// an allocation the context owns whichever plan is being built: plan eviction never frees it
+inline int ctx_alloc(sylph_ctx* c, void** p, size_t n) {
+  OwnerScope own(c, nullptr);
+  return c->dalloc(p, n);
+}
 
 struct Geom {
   const SegDesc* segs;
@@ -624,6 +629,10 @@ OpFn on_side_stream(sylph_ctx* c, const OpFn& op);  // `op`, launched on the sid
 // api_weights.hip
 const HostTensor* find_w(sylph_ctx* c, const std::string& k);
 int pack_conv(sylph_ctx* c, const std::vector<const HostTensor*>& ws, ConvLayer* L);
+// a 256-input 3x3 conv in torch order, w (cout, 256, 3, 3): pack_conv's bf16 operand [cout_pad][tap][ci] (the rows past cout zero) ...
+std::vector<uint16_t> pack_conv3x3_bf16(const float* w, int cout, int cout_pad);
+// ... and the tap table of the fused GroupNorm + prediction pass, [64][256] bf16: row kh * sw + kw * cout + n, sw = roundup4(3 cout)
+std::vector<uint16_t> pack_pred_taps(const float* w, int cout);
 int upload_vec(sylph_ctx* c, float** dev, const std::vector<float>& v, int pad_to);
 int make_conv_bn(sylph_ctx* c, const std::string& name, ConvLayer* L);
 int pack_conv_grouped(sylph_ctx* c, const HostTensor& w, const std::string& key, int C, int groups, const float* scale, const float* shift,

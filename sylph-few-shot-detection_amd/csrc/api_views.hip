@@ -67,11 +67,7 @@ static int merge_upload_tables(sylph_ctx* c, int n_src, int n_views, const int* 
   if (need > c->merge_tab_cap) {
     if (c->merge_tab) c->dfree(c->merge_tab);
     c->merge_tab = nullptr; c->merge_tab_cap = 0;
-    Plan* owner = c->alloc_owner;
-    c->alloc_owner = nullptr;  // the context's, not a plan's
-    const int r = c->dalloc(&c->merge_tab, need * 2);
-    c->alloc_owner = owner;
-    RET(r);
+    RET(ctx_alloc(c, &c->merge_tab, need * 2));
     c->merge_tab_cap = need * 2;
   }
   c->merge_host.resize(need);

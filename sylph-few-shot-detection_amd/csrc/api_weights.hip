@@ -61,6 +61,23 @@ int pack_conv(sylph_ctx* c, const std::vector<const HostTensor*>& ws, ConvLayer*
   return 0;
 }
 
+std::vector<uint16_t> pack_conv3x3_bf16(const float* w, int cout, int cout_pad) {
+  std::vector<uint16_t> pk((size_t)cout_pad * 2304, 0);
+  for (int n = 0; n < cout; ++n)
+    for (int tap = 0; tap < 9; ++tap)
+      for (int ci = 0; ci < 256; ++ci) pk[(size_t)n * 2304 + (size_t)tap * 256 + ci] = f2bf_host(w[w3x3_torch(n, tap, ci)]);
+  return pk;
+}
+
+std::vector<uint16_t> pack_pred_taps(const float* w, int cout) {
+  const int sw = (3 * cout + 3) & ~3;
+  std::vector<uint16_t> tw((size_t)64 * 256, 0);
+  for (int n = 0; n < cout; ++n)
+    for (int tap = 0; tap < 9; ++tap)
+      for (int ci = 0; ci < 256; ++ci) tw[(size_t)((tap / 3) * sw + (tap % 3) * cout + n) * 256 + ci] = f2bf_host(w[w3x3_torch(n, tap, ci)]);
+  return tw;
+}
+
 int upload_vec(sylph_ctx* c, float** dev, const std::vector<float>& v, int pad_to) {
   std::vector<float> t(v);
   t.resize((size_t)pad_to, 0.f);
@@ -539,22 +556,18 @@ int sylph_finalize_weights(sylph_ctx* c) {
         c->has_cls_logits = true;
       }
     }
-    c->pred_taps = nullptr;
-    if (c->dt == DT_BF16 && c->pred.KH == 3 && c->pred.KW == 3 && c->pred.Cin == 256 && 3 * ((3 * c->pred.Cout + 3) & ~3) <= 64) {
-      // the same weights stacked for the fused GroupNorm + prediction pass: row kh * sw + kw * Cout + n, sw = roundup4(3 * Cout)
-      const int cp = c->pred.Cout, sw = (3 * cp + 3) & ~3;
-      std::vector<uint16_t> tw((size_t)64 * 256, 0);
-      int n0 = 0;
+    // the box branch as finalized, stacked in torch order: what sylph_get_box_branch returns and a reset of sylph_set_box_branch restores
+    c->box_w0.clear(); c->box_b0.clear();
+    if (c->pred.KH == 3 && c->pred.KW == 3 && c->pred.Cin == 256)
       for (const char* nm : {".bbox_pred", ".ctrness", ".iou_overlap"}) {
-        const HostTensor* w = find_w(c, hp + nm + ".weight");
-        if (!w) continue;
-        const int co = (int)w->shape[0];
-        for (int n = 0; n < co; ++n)
-          for (int ci = 0; ci < 256; ++ci)
-            for (int tap = 0; tap < 9; ++tap)
-              tw[(size_t)((tap / 3) * sw + (tap % 3) * cp + n0 + n) * 256 + ci] = f2bf_host(w->data[((size_t)n * 256 + ci) * 9 + tap]);
-        n0 += co;
+        const HostTensor *w = find_w(c, hp + nm + ".weight"), *b = find_w(c, hp + nm + ".bias");
+        c->box_w0.insert(c->box_w0.end(), w->data.begin(), w->data.end());
+        c->box_b0.insert(c->box_b0.end(), b->data.begin(), b->data.end());
       }
+    c->pred_taps = nullptr;
+    if (c->dt == DT_BF16 && !c->box_w0.empty() && 3 * ((3 * c->pred.Cout + 3) & ~3) <= 64) {
+      // the same weights as the tap table of the fused GroupNorm + prediction pass
+      const std::vector<uint16_t> tw = pack_pred_taps(c->box_w0.data(), c->pred.Cout);
       RET(upload(c, &c->pred_taps, tw.data(), tw.size() * 2));
     }
     c->level_scales.assign(c->cfg.nlevels, 1.f);
@@ -563,14 +576,6 @@ int sylph_finalize_weights(sylph_ctx* c) {
         const HostTensor* s = find_w(c, hp + ".scales." + std::to_string(l) + ".scale");
         if (!s) return fail("missing " + hp + ".scales." + std::to_string(l) + ".scale");
         c->level_scales[l] = s->data[0];
-      }
-    // the box branch as finalized, in torch order: what sylph_get_box_branch returns and a reset of sylph_set_box_branch restores
-    c->box_w0.clear(); c->box_b0.clear();
-    if (c->pred.KH == 3 && c->pred.KW == 3 && c->pred.Cin == 256)
-      for (const char* nm : {".bbox_pred", ".ctrness", ".iou_overlap"}) {
-        const HostTensor *w = find_w(c, hp + nm + ".weight"), *b = find_w(c, hp + nm + ".bias");
-        c->box_w0.insert(c->box_w0.end(), w->data.begin(), w->data.end());
-        c->box_b0.insert(c->box_b0.end(), b->data.begin(), b->data.end());
       }
     c->box_s0 = c->level_scales;
     c->box_w = c->box_w0; c->box_b = c->box_b0;

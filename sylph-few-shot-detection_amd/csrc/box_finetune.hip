@@ -22,8 +22,8 @@
 //               g[n] = d loss / d z[n]; channel 4 only with "ctrness", channel 5 only with "iou" (the reference detaches the other)
 //   backward  thread t owns the channel pairs t + 384 j, j < 3: dW[n][k] += g[s][n] x[s][k] over the unit's samples in ascending s
 //             (fmaf), 36 accumulators; db, d scales and the four sums by single threads in the same order
-// The unit's partial (BOX_GRAD_PARTIAL floats) goes to the workspace; box_sum_kernel adds partials in chunks of 64 consecutive units,
-// box_reduce_kernel the last <= 64 in order and writes torch's (Cout, 256, 3, 3) layout: no atomics, the same bits on every grid.
+// The unit's partial (BOX_GRAD_PARTIAL floats) goes to the workspace; the ordered tree of partial_sum.h (fan-in 64) adds the partials and
+// its sink here, BoxGradSink, writes torch's (Cout, 256, 3, 3) layout: no atomics, the same bits on every grid.
 // The products run on the VALU: Cout is 5 or 6, so an MFMA tile would be 10 / 16 zeros, and the whole bank (a few thousand rows of
 // 4.6 KB) is read twice per step, from L2 / MALL the second time.
 #include <stdlib.h>
@@ -31,6 +31,7 @@
 #include "fcos_assign.h"
 #include "gn_stream.h"
 #include "kernels.h"
+#include "partial_sum.h"
 
 namespace sylph {
 
@@ -220,8 +221,8 @@ __global__ __launch_bounds__(384) void box_grad_kernel(int n, const bf16_t* __re
     const int c = i / BG_PAIRS, pr = i - c * BG_PAIRS, tap = pr >> 7, ci = (pr & 127) * 2;
     bf16x2 q = {(bf16_t)0.f, (bf16_t)0.f};
     if (c < cout) {
-      q[0] = (bf16_t)w[((size_t)c * 256 + ci) * 9 + tap];
-      q[1] = (bf16_t)w[((size_t)c * 256 + ci + 1) * 9 + tap];
+      q[0] = (bf16_t)w[w3x3_torch(c, tap, ci)];
+      q[1] = (bf16_t)w[w3x3_torch(c, tap, ci + 1)];
     }
     wl[c][pr] = __builtin_bit_cast(unsigned, q);
   }
@@ -318,65 +319,42 @@ __global__ __launch_bounds__(384) void box_grad_kernel(int n, const bf16_t* __re
   }
 }
 
-// out[c][i] = sum of in[64 c + k][i], k = 0 .. 63 (those below n_in), in that order
-__global__ __launch_bounds__(256) void box_sum_kernel(const float* __restrict__ in, int n_in, float* __restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
-  if (i >= BOX_GRAD_PARTIAL) return;
-  const int k1 = min(n_in, 64 * (c + 1));
-  float s = 0.f;
-  for (int k = 64 * c; k < k1; ++k) s += in[(size_t)k * BOX_GRAD_PARTIAL + i];
-  out[(size_t)c * BOX_GRAD_PARTIAL + i] = s;
-}
-
-// the last n_in <= 64 partials summed in order -> grad_w (cout, 256, 3, 3), grad_b (cout), grad_scales (nlevels), sums (4); n_in = 0: zeros
-__global__ __launch_bounds__(256) void box_reduce_kernel(const float* __restrict__ in, int n_in, int cout, int nlevels, float* __restrict__ grad_w,
-                                                         float* __restrict__ grad_b, float* __restrict__ grad_scales, float* __restrict__ sums) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= BOX_GRAD_SUMS + 4) return;
-  float s = 0.f;
-  for (int k = 0; k < n_in; ++k) s += in[(size_t)k * BOX_GRAD_PARTIAL + i];
-  if (i < 6 * BG_K) {
-    const int c = i / BG_K, k = i - c * BG_K, tap = k >> 8, ci = k & 255;
-    if (c < cout) grad_w[((size_t)c * 256 + ci) * 9 + tap] = s;
-  } else if (i >= BOX_GRAD_DB && i < BOX_GRAD_DB + 6) {
-    if (i - BOX_GRAD_DB < cout) grad_b[i - BOX_GRAD_DB] = s;
-  } else if (i >= BOX_GRAD_DS && i < BOX_GRAD_DS + 8) {
-    if (i - BOX_GRAD_DS < nlevels) grad_scales[i - BOX_GRAD_DS] = s;
-  } else if (i >= BOX_GRAD_SUMS) {
-    sums[i - BOX_GRAD_SUMS] = s;
+// the sink of the tree's final kernel: element i of the summed partial -> grad_w (cout, 256, 3, 3), grad_b (cout), grad_scales (nlevels),
+// sums (4).  An empty bank (no partial) sums to zeros
+struct BoxGradSink {
+  int cout, nlevels;
+  float *grad_w, *grad_b, *grad_scales, *sums;
+  __device__ void operator()(int i, float s) const {
+    if (i < 6 * BG_K) {
+      const int c = i / BG_K, k = i - c * BG_K, tap = k >> 8, ci = k & 255;
+      if (c < cout) grad_w[w3x3_torch(c, tap, ci)] = s;
+    } else if (i >= BOX_GRAD_DB && i < BOX_GRAD_DB + 6) {
+      if (i - BOX_GRAD_DB < cout) grad_b[i - BOX_GRAD_DB] = s;
+    } else if (i >= BOX_GRAD_DS && i < BOX_GRAD_DS + 8) {
+      if (i - BOX_GRAD_DS < nlevels) grad_scales[i - BOX_GRAD_DS] = s;
+    } else if (i >= BOX_GRAD_SUMS) {
+      sums[i - BOX_GRAD_SUMS] = s;
+    }
   }
-}
+};
 
 int box_grad_units(int n) { return (n + BOX_GRAD_UNIT - 1) / BOX_GRAD_UNIT; }
 
-size_t box_grad_ws_floats(int n) {
-  size_t u = (size_t)box_grad_units(n), tot = u;
-  while (u > 64) { u = (u + 63) / 64; tot += u; }
-  return tot * BOX_GRAD_PARTIAL;
-}
+size_t box_grad_ws_floats(int n) { return partial_tree(box_grad_units(n), BOX_GRAD_FANIN).planes * BOX_GRAD_PARTIAL; }
 
 int launch_box_grad(int n, const void* patches, const float* targets, const int* info, const float* w, const float* bias, const float* scales,
                     int cout, int nlevels, int quality, int iou_mask, float* ws, float* sums, float* grad_w, float* grad_b, float* grad_scales,
                     float* z_out, float* g_out, hipStream_t s) {
   if (n < 0 || cout < 5 || cout > 6 || nlevels < 1 || nlevels > 8 || (n > 0 && !ws)) return -1;
-  int u = box_grad_units(n);
-  float* in = ws;
+  const int u = box_grad_units(n);
   if (u > 0) {
     // SYLPH_BOX_GRAD_BLOCKS: another block cap (tests: a block then takes several units; the results must keep their bits)
-    const char* e = getenv("SYLPH_BOX_GRAD_BLOCKS");
-    const int cap = e && atoi(e) > 0 ? atoi(e) : BOX_GRAD_MAX_BLOCKS;
+    const int cap = block_cap("SYLPH_BOX_GRAD_BLOCKS", BOX_GRAD_MAX_BLOCKS);
     hipLaunchKernelGGL(box_grad_kernel, dim3(u < cap ? u : cap), dim3(384), 0, s, n, (const bf16_t*)patches, targets, info, w, bias, scales, cout,
                        nlevels, quality, iou_mask, ws, z_out, g_out);
-    while (u > 64) {
-      const int m = (u + 63) / 64;
-      float* out = in + (size_t)u * BOX_GRAD_PARTIAL;
-      hipLaunchKernelGGL(box_sum_kernel, dim3((BOX_GRAD_PARTIAL + 255) / 256, m), dim3(256), 0, s, in, u, out);
-      in = out;
-      u = m;
-    }
   }
-  hipLaunchKernelGGL(box_reduce_kernel, dim3((BOX_GRAD_SUMS + 4 + 255) / 256), dim3(256), 0, s, in, u, cout, nlevels, grad_w, grad_b, grad_scales,
-                     sums);
+  partial_final(partial_sum_passes(ws, u, BOX_GRAD_PARTIAL, BOX_GRAD_FANIN, s), BOX_GRAD_PARTIAL, BOX_GRAD_SUMS + 4,
+                BoxGradSink{cout, nlevels, grad_w, grad_b, grad_scales, sums}, s);
   return (int)hipGetLastError();
 }
 

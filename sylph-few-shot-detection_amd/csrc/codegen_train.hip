@@ -21,8 +21,8 @@
 //           cgt_conv_kernel      d x_i = conv(bf16(d y_i), flipped transposed weights), layers 1 and up
 //           cgt_wgrad_kernel     d W_i[co][tap][ci] = sum_rows bf16(d y_i)[row][co] x_i[row + tap][ci] on the MFMAs: the rows are cut into UNITS
 //                                of CGT_UNIT_SHOTS whole shots, a function of M alone; a block stages 32 rows of both operands transposed
-//                                in LDS per K step and writes the unit's partial; cgt_sum_kernel adds CGT_FANIN consecutive partials per
-//                                pass, cgt_wgrad_final_kernel the last ones in order into torch's (co, ci, ky, kx) layout
+//                                in LDS per K step and writes the unit's partial; the ordered tree of partial_sum.h (fan-in CGT_FANIN) adds
+//                                the partials and its sink here, CgtWgradSink, writes torch's (co, ci, ky, kx) layout
 // No atomics anywhere: the same inputs give the same bits on every call and on every grid (SYLPH_CODEGEN_TRAIN_BLOCKS caps the blocks).
 // Rounding points: conv weights and d y_i to bf16 at the operand, x_{i+1} stored in bf16; everything else fp32.  The gradient treats
 // every rounding as the identity.
@@ -30,6 +30,7 @@
 
 #include "gfx950.h"
 #include "kernels.h"
+#include "partial_sum.h"
 
 namespace sylph {
 
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(256) void cgt_pack_kernel(const float* __restrict__
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= cout * K9) return;
   const int co = i / K9, k = i - co * K9, tap = k >> 8, ci = k & 255;
-  const bf16_t v = (bf16_t)w[((size_t)co * C + ci) * 9 + tap];
+  const bf16_t v = (bf16_t)w[w3x3_torch(co, tap, ci)];
   wf[i] = v;
   if (wd) wd[(size_t)ci * K9 + (8 - tap) * C + co] = v;
   if (wt) wt[(size_t)k * cout + co] = v;
@@ -311,7 +312,7 @@ __global__ __launch_bounds__(256) void cgt_head_wgrad_kernel(const float* __rest
   const int co = i / K9, k = i - co * K9, tap = k >> 8, ci = k & 255;
   float a = 0.f;
   for (int s = 0; s < M; ++s) a = fmaf(dc[(size_t)s * cout + co], xsum[(size_t)s * K9 + k], a);
-  grad[((size_t)co * C + ci) * 9 + tap] = a / 49.f;
+  grad[w3x3_torch(co, tap, ci)] = a / 49.f;
 }
 
 // d Xsum[s][k] = (sum_co dc[s][co] bf16(W_cls)[co][k] + drb[s] bf16(W_bias)[k]) / 49; grid (9, M)
@@ -441,37 +442,25 @@ __global__ __launch_bounds__(256) void cgt_wgrad_kernel(const float* __restrict_
   }
 }
 
-// out[c][i] = sum of in[CGT_FANIN c + k][i], k = 0 .. CGT_FANIN - 1 (those below n_in), in that order
-__global__ __launch_bounds__(256) void cgt_sum_kernel(const float* __restrict__ in, int n_in, float* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, plane = (size_t)C * K9;
-  const int c = blockIdx.y, k1 = min(n_in, CGT_FANIN * (c + 1));
-  float s = 0.f;
-  for (int k = CGT_FANIN * c; k < k1; ++k) s += in[(size_t)k * plane + i];
-  out[(size_t)c * plane + i] = s;
-}
-
-// the last n_in <= CGT_FANIN partials [co][tap][ci] summed in order -> grad (co, ci, ky, kx)
-__global__ __launch_bounds__(256) void cgt_wgrad_final_kernel(const float* __restrict__ in, int n_in, float* __restrict__ grad) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const int co = i / K9, k = i - co * K9, tap = k >> 8, ci = k & 255;
-  float s = 0.f;
-  for (int q = 0; q < n_in; ++q) s += in[(size_t)q * C * K9 + i];
-  grad[((size_t)co * C + ci) * 9 + tap] = s;
-}
+// the sink of the tree's final kernel: element i of the summed partial [co][tap][ci] -> grad (co, ci, ky, kx)
+struct CgtWgradSink {
+  float* grad;
+  __device__ void operator()(int i, float s) const {
+    const int co = i / K9, k = i - co * K9, tap = k >> 8, ci = k & 255;
+    grad[w3x3_torch(co, tap, ci)] = s;
+  }
+};
 
 __global__ __launch_bounds__(256) void cgt_bf16_to_f32_kernel(const bf16_t* __restrict__ in, size_t n, float* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) out[i] = (float)in[i];
 }
 
-int block_cap() {
-  const char* e = getenv("SYLPH_CODEGEN_TRAIN_BLOCKS");
-  return e && atoi(e) > 0 ? atoi(e) : CGT_MAX_BLOCKS;
-}
+int cgt_block_cap() { return block_cap("SYLPH_CODEGEN_TRAIN_BLOCKS", CGT_MAX_BLOCKS); }
 
 template <typename TIn>
 void conv(const TIn* in, const int* shot_map, const bf16_t* wp, const float* bias, float* out, int rows, hipStream_t s) {
-  const int tiles = (rows + 31) / 32, cap = block_cap();
+  const int tiles = (rows + 31) / 32, cap = cgt_block_cap();
   hipLaunchKernelGGL(cgt_conv_kernel<TIn>, dim3(tiles < cap ? tiles : cap), dim3(256), 0, s, in, shot_map, wp, bias, out, rows);
 }
 
@@ -538,14 +527,9 @@ void cgt_workspace(const CgtCfg& cfg, int M, int n_seg, CgtWs* w) {
   w->gsb = take((size_t)M * C * 4);
   w->gsd = take((size_t)M * C * 4);
   w->units = (M + CGT_UNIT_SHOTS - 1) / CGT_UNIT_SHOTS;
-  w->passes = 1;  // the final one
-  size_t planes = 0;
-  if (cfg.L) {
-    int u = w->units;
-    planes = (size_t)u;
-    while (u > CGT_FANIN) { u = (u + CGT_FANIN - 1) / CGT_FANIN; planes += (size_t)u; ++w->passes; }
-  }
-  w->part = take(planes * C * K9 * 4);
+  const PartialTree tree = partial_tree(cfg.L ? w->units : 0, CGT_FANIN);  // without a tower no weight gradient goes through the tree
+  w->passes = tree.passes;
+  w->part = take(tree.planes * C * K9 * 4);
   w->total = o;
 }
 
@@ -660,7 +644,7 @@ int launch_cgt_backward(const CgtCfg& cfg, const float* params, const void* rows
     hipLaunchKernelGGL(cgt_scatter_kernel, dim3(M), dim3(256), 0, s, F(W.dxsum), dxa);
     put(F(W.dxsum), (size_t)M * K9);
     put(dxa, R * C);
-    const int cap = block_cap();
+    const int cap = cgt_block_cap();
     for (int i = L - 1; i >= 0; --i) {
       hipLaunchKernelGGL(cgt_gn_bwd_kernel, dim3(M), dim3(256), 0, s, dxa, H(W.x[i]), F(W.y[i]), reinterpret_cast<const float2*>(ws + W.st[i]),
                          params + P.tg[i], dya, F(W.gsg), F(W.gsb), F(W.gsd));
@@ -668,18 +652,10 @@ int launch_cgt_backward(const CgtCfg& cfg, const float* params, const void* rows
       colsum(F(W.gsb), M, C, C, grad_out + P.tbe[i], s);
       colsum(F(W.gsd), M, C, C, grad_out + P.tb[i], s);
       put(dya, R * C);
-      int u = W.units;
+      const int u = W.units;
       const bf16_t* xin = i > 0 ? H(W.x[i - 1]) : static_cast<const bf16_t*>(rows);
       hipLaunchKernelGGL(cgt_wgrad_kernel, dim3(36, u < cap ? u : cap), dim3(256), 0, s, dya, xin, i > 0 ? (const int*)nullptr : idx, M, u, part);
-      float* in = part;
-      while (u > CGT_FANIN) {
-        const int m = (u + CGT_FANIN - 1) / CGT_FANIN;
-        float* out = in + (size_t)u * C * K9;
-        hipLaunchKernelGGL(cgt_sum_kernel, dim3(C * K9 / 256, m), dim3(256), 0, s, in, u, out);
-        in = out;
-        u = m;
-      }
-      hipLaunchKernelGGL(cgt_wgrad_final_kernel, dim3(C * K9 / 256), dim3(256), 0, s, in, u, grad_out + P.tw[i]);
+      partial_final(partial_sum_passes(part, u, C * K9, CGT_FANIN, s), C * K9, C * K9, CgtWgradSink{grad_out + P.tw[i]}, s);
       if (i > 0) {
         conv<float>(dya, nullptr, H(W.wd[i]), nullptr, dxa, (int)R, s);
         put(dxa, R * C);

@@ -127,6 +127,10 @@ template <> struct Cvt<bf16_t> {
 
 __device__ __forceinline__ float bf16_bits_to_f(uint32_t hi16) { return __uint_as_float(hi16 << 16); }
 
+// a 256-input 3x3 conv: torch holds it as (co, ci, ky, kx), the kernels as [co][tap][ci] = co * 2304 + tap * 256 + ci, tap = 3 ky + kx.
+// The torch offset of the kernels' (co, tap, ci)
+__host__ __device__ inline size_t w3x3_torch(int co, int tap, int ci) { return ((size_t)co * 256 + ci) * 9 + tap; }
+
 // load 8 consecutive elements of T as floats (16-byte aligned for bf16, 32-byte span for f32)
 template <typename T> __device__ __forceinline__ void load8(const T* p, float (&v)[8]);
 template <> __device__ __forceinline__ void load8<float>(const float* p, float (&v)[8]) {

@@ -24,9 +24,8 @@
 //   clamped and computed (g = 0), never masked.  Same-wave LDS traffic is ordered: no barrier in the loop.
 //   No atomics.  The row groups are cut into UNITS of CLS_GRAD_UNIT_GROUPS consecutive groups -- a function of the tile table alone, not of
 //   the grid -- and a wave keeps the 8 x 16 accumulator registers of dW^T, db and the loss over one unit, then writes the unit's partial
-//   ([256][32] dW^T | [32] db | loss, CLS_GRAD_PARTIAL floats).  cls_grad_sum_kernel adds partials in chunks of 64 consecutive units,
-//   cls_grad_reduce_kernel adds the last <= 64 in order and writes the N x 256 layout: the same inputs give the same bits whatever grid
-//   runs them.
+//   ([256][32] dW^T | [32] db | loss, CLS_GRAD_PARTIAL floats).  The ordered tree of partial_sum.h (fan-in 64) adds the partials; its
+//   sink here, ClsGradSink, writes the N x 256 layout: the same inputs give the same bits whatever grid runs them.
 //   Compiler's resource report (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): cls_grad_kernel 256 VGPRs + 170 AGPRs, 0 bytes
 //   of scratch, 22 SGPRs spilled to VGPR lanes, 90 624 bytes of LDS, occupancy 1 wave per SIMD (one block per CU).  The AGPRs are spill
 //   space: hipcc computes the dW^T tiles in VGPRs and copies them to AGPRs and back (~650 v_accvgpr moves in the kernel, most of them in
@@ -38,6 +37,7 @@
 #include "fcos_assign.h"
 #include "gn_stream.h"
 #include "kernels.h"
+#include "partial_sum.h"
 
 namespace sylph {
 
@@ -218,64 +218,41 @@ __global__ __launch_bounds__(256) void cls_grad_kernel(const bf16_t* __restrict_
   }
 }
 
-// out[c][i] = sum of in[64 c + k][i], k = 0 .. 63 (those below n_in), in that order
-__global__ __launch_bounds__(256) void cls_grad_sum_kernel(const float* __restrict__ in, int n_in, float* __restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
-  if (i >= CLS_GRAD_PARTIAL) return;
-  const int k1 = min(n_in, 64 * (c + 1));
-  float s = 0.f;
-  for (int k = 64 * c; k < k1; ++k) s += in[(size_t)k * CLS_GRAD_PARTIAL + i];
-  out[(size_t)c * CLS_GRAD_PARTIAL + i] = s;
-}
-
-// the last n_in <= 64 partials summed in order -> grad_w[nb][256], grad_b[nb] (nullptr: none), loss (accumulate: added to what the
-// earlier class blocks of the call left there)
-__global__ __launch_bounds__(256) void cls_grad_reduce_kernel(const float* __restrict__ in, int n_in, int nb, float* __restrict__ grad_w,
-                                                              float* __restrict__ grad_b, float* __restrict__ loss, int accumulate) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 8225) return;
-  float s = 0.f;
-  for (int k = 0; k < n_in; ++k) s += in[(size_t)k * CLS_GRAD_PARTIAL + i];
-  if (i < 8192) {
-    const int c = i >> 5, n = i & 31;
-    if (n < nb) grad_w[n * 256 + c] = s;
-  } else if (i < 8224) {
-    if (grad_b && i - 8192 < nb) grad_b[i - 8192] = s;
-  } else {
-    *loss = accumulate ? *loss + s : s;
+// the sink of the tree's final kernel: element i of the summed partial -> grad_w[nb][256], grad_b[nb] (nullptr: none), loss (accumulate:
+// added to what the earlier class blocks of the call left there)
+struct ClsGradSink {
+  int nb;
+  float *grad_w, *grad_b, *loss;
+  int accumulate;
+  __device__ void operator()(int i, float s) const {
+    if (i < 8192) {
+      const int c = i >> 5, n = i & 31;
+      if (n < nb) grad_w[n * 256 + c] = s;
+    } else if (i < 8224) {
+      if (grad_b && i - 8192 < nb) grad_b[i - 8192] = s;
+    } else {
+      *loss = accumulate ? *loss + s : s;
+    }
   }
-}
+};
 
 int cls_grad_units(int n_tiles) { return (n_tiles * 4 + CLS_GRAD_UNIT_GROUPS - 1) / CLS_GRAD_UNIT_GROUPS; }
 
 // floats of workspace for one class block: the units' partials and every level of their sums
-size_t cls_grad_ws_floats(int n_tiles) {
-  size_t n = (size_t)cls_grad_units(n_tiles), tot = n;
-  while (n > 64) { n = (n + 63) / 64; tot += n; }
-  return tot * CLS_GRAD_PARTIAL;
-}
+size_t cls_grad_ws_floats(int n_tiles) { return partial_tree(cls_grad_units(n_tiles), CLS_GRAD_FANIN).planes * CLS_GRAD_PARTIAL; }
 
 // w: [32][256] bf16 (rows >= nb zero), bias: [32] fp32; ws: cls_grad_ws_floats(n_tiles) floats; grad_w: [nb][256], grad_b: [nb] or nullptr
 int launch_cls_grad(const void* x, int ld, const float2* coef, const void* w, const float* bias, int nb, int n0, const int* labels, float alpha,
                     float gamma, float* ws, float* loss, int accumulate, float* grad_w, float* grad_b, const SegDesc* segs, const int2* tiles,
                     int n_tiles, hipStream_t s) {
   if (nb < 1 || nb > 32 || n_tiles <= 0 || !bias || !ws) return -1;
-  int n = cls_grad_units(n_tiles);
-  const int blocks = (n + 3) / 4;
+  const int n = cls_grad_units(n_tiles), blocks = (n + 3) / 4;
   // SYLPH_CLS_GRAD_BLOCKS: another block cap (tests: a wave then takes several units; the results must keep their bits)
-  const char* e = getenv("SYLPH_CLS_GRAD_BLOCKS");
-  const int cap = e && atoi(e) > 0 ? atoi(e) : CLS_GRAD_MAX_BLOCKS;
+  const int cap = block_cap("SYLPH_CLS_GRAD_BLOCKS", CLS_GRAD_MAX_BLOCKS);
   hipLaunchKernelGGL(cls_grad_kernel, dim3(blocks < cap ? blocks : cap), dim3(256), 0, s, (const bf16_t*)x, ld, coef,
                      (const bf16_t*)w, bias, nb, n0, labels, alpha, gamma, ws, segs, tiles, n_tiles);
-  float* in = ws;
-  while (n > 64) {
-    const int m = (n + 63) / 64;
-    float* out = in + (size_t)n * CLS_GRAD_PARTIAL;
-    hipLaunchKernelGGL(cls_grad_sum_kernel, dim3((CLS_GRAD_PARTIAL + 255) / 256, m), dim3(256), 0, s, in, n, out);
-    in = out;
-    n = m;
-  }
-  hipLaunchKernelGGL(cls_grad_reduce_kernel, dim3((8225 + 255) / 256), dim3(256), 0, s, in, n, nb, grad_w, grad_b, loss, accumulate);
+  partial_final(partial_sum_passes(ws, n, CLS_GRAD_PARTIAL, CLS_GRAD_FANIN, s), CLS_GRAD_PARTIAL, 8225,
+                ClsGradSink{nb, grad_w, grad_b, loss, accumulate}, s);
   return (int)hipGetLastError();
 }
 

@@ -217,6 +217,7 @@ int launch_fcos_targets(const SegDesc* segs, int nseg, int nlevels, int max_rows
                         const int* gt_class, const int* gt_image, int* labels, int* num_pos, hipStream_t s);
 constexpr int CLS_GRAD_UNIT_GROUPS = 16;  // 32-row groups behind one partial: fixed by the tile table, so the sums do not depend on the grid
 constexpr int CLS_GRAD_PARTIAL = 8256;    // floats per partial: [256][32] dW^T | [32] db | loss, rounded up to 128 bytes
+constexpr int CLS_GRAD_FANIN = 64;        // partials added per reduce pass (partial_sum.h)
 constexpr int CLS_GRAD_MAX_BLOCKS = 1024;  // one block of four waves per CU and a few to spare; SYLPH_CLS_GRAD_BLOCKS overrides it
 int cls_grad_units(int n_tiles);
 size_t cls_grad_ws_floats(int n_tiles);
@@ -234,6 +235,7 @@ constexpr int BOX_GRAD_DB = 6 * 2304;      // a partial: [6][2304] dW | [6] db |
 constexpr int BOX_GRAD_DS = BOX_GRAD_DB + 8;
 constexpr int BOX_GRAD_SUMS = BOX_GRAD_DS + 8;
 constexpr int BOX_GRAD_PARTIAL = BOX_GRAD_SUMS + 16;
+constexpr int BOX_GRAD_FANIN = 64;         // partials added per reduce pass (partial_sum.h)
 constexpr int BOX_GRAD_MAX_BLOCKS = 1024;  // SYLPH_BOX_GRAD_BLOCKS overrides it
 int box_grad_units(int n);
 size_t box_grad_ws_floats(int n);

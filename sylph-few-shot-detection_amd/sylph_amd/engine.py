@@ -362,6 +362,7 @@ class Engine:
         self._merge_ws = None  # merge_views_large's workspace: grows on demand, contents are scratch
         self._ft_ws = None  # cls_grad's workspace (the per-unit partial sums): grows on demand, contents are scratch
         self._box_ws = None  # box_grad's workspace, likewise
+        self._cgt_ws = None  # the generator's training workspace: the saved activations of a forward until its backward, then scratch
         # what the training-side entries (fcos_targets, cls_grad) read from MODEL.FCOS: focal loss and target assignment
         f = cfg.MODEL.FCOS if cfg is not None else {}
         self.fcos_train = {"alpha": float(f.get("LOSS_ALPHA", 0.25)), "gamma": float(f.get("LOSS_GAMMA", 2.0)),
@@ -554,31 +555,43 @@ class Engine:
         B, H, W, _ = self._batch
         return B * sum(h * w for h, w in self.level_shapes(H, W))
 
+    def _check_gt(self, who: str, boxes, classes, image_index):
+        """The ground truth of the current batch validated on the host, under the entry's name: one class and one image per box,
+        image_index sorted and inside the batch -> (boxes (n, 4) fp32, classes (n,) int32, image_index (n,) int32) on the device."""
+        bx = torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 4)
+        cl = torch.as_tensor(classes).reshape(-1)
+        im = torch.as_tensor(image_index).reshape(-1)
+        n = bx.shape[0]
+        if cl.numel() != n or im.numel() != n:
+            raise ValueError(f"{who}: {n} boxes, {cl.numel()} classes and {im.numel()} image indices")
+        B = self._batch[0]
+        iml = im.tolist()
+        if any(a > b for a, b in zip(iml, iml[1:])):
+            raise ValueError(f"{who}: gt_image is not sorted (image_index must not decrease)")
+        if n and (iml[0] < 0 or iml[-1] >= B):
+            raise ValueError(f"{who}: image_index outside the batch of {B} images")
+        return bx.to(self.device).contiguous(), cl.to(self.device, torch.int32).contiguous(), im.to(self.device, torch.int32).contiguous()
+
+    def _grow_ws(self, attr: str, need: int) -> torch.Tensor:
+        """The engine's scratch workspace `attr` with room for `need` bytes: it grows on demand and is never empty."""
+        ws = getattr(self, attr)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(max(need, 4), device=self.device, dtype=torch.uint8)
+            setattr(self, attr, ws)
+        return ws
+
     def fcos_targets(self, boxes: torch.Tensor, classes: torch.Tensor, image_index: torch.Tensor):
         """FCOS classification targets of the current batch (a fresh batch after `towers()`, or a loaded record): `boxes` (n, 4) in
         network-input pixels, `classes` (n,), `image_index` (n,) sorted.  Returns (labels, num_pos): int32 device tensors, one label per
         row of the tower output (-1: background) and the count of positives; nothing is read back.  (The arguments are validated on
         the host: device tensors are copied back for that.)"""
         self._stream()
-        bx = torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 4)
-        cl = torch.as_tensor(classes).reshape(-1)
-        im = torch.as_tensor(image_index).reshape(-1)
-        n = bx.shape[0]
-        if cl.numel() != n or im.numel() != n:
-            raise ValueError(f"fcos_targets: {n} boxes, {cl.numel()} classes and {im.numel()} image indices")
         rows = self.batch_rows()
-        B = self._batch[0]
-        iml = im.tolist()
-        if any(a > b for a, b in zip(iml, iml[1:])):
-            raise ValueError("fcos_targets: gt_image is not sorted (image_index must not decrease)")
-        if n and (iml[0] < 0 or iml[-1] >= B):
-            raise ValueError(f"fcos_targets: image_index outside the batch of {B} images")
-        if n and int(cl.min()) < 0:
+        bx, cl, im = self._check_gt("fcos_targets", boxes, classes, image_index)
+        n = bx.shape[0]
+        if n and int(torch.as_tensor(classes).min()) < 0:
             raise ValueError("fcos_targets: a class index is negative")
         fc = self.fcos_train
-        bx = bx.to(self.device).contiguous()
-        cl = cl.to(self.device, torch.int32).contiguous()
-        im = im.to(self.device, torch.int32).contiguous()
         labels = torch.empty(rows, device=self.device, dtype=torch.int32)
         num_pos = torch.empty(1, device=self.device, dtype=torch.int32)
         soi = (ctypes.c_float * len(fc["sizes_of_interest"]))(*fc["sizes_of_interest"])
@@ -606,22 +619,20 @@ class Engine:
             raise ValueError(f"cls_grad: a label >= N (largest label {int(labels.max())}, {N} classes)")
         need = c_int64(0)
         check(self.L.sylph_cls_grad_bytes(self._ctx, N, ctypes.byref(need)), "cls_grad_bytes")
-        if self._ft_ws is None or self._ft_ws.numel() < need.value:
-            self._ft_ws = torch.empty(need.value, device=self.device, dtype=torch.uint8)
+        ws = self._grow_ws("_ft_ws", need.value)
         loss = torch.empty(1, device=self.device, dtype=torch.float32)
         gw = torch.empty(N, 256, device=self.device, dtype=torch.float32)
         gb = torch.empty(N, device=self.device, dtype=torch.float32) if b is not None else None
         fc = self.fcos_train
         check(self.L.sylph_cls_grad(self._ctx, _ptr(labels), _ptr(w), _ptr(b), N, int(class_offset), float(fc["alpha"]), float(fc["gamma"]),
-                                    _ptr(self._ft_ws), _ptr(loss), _ptr(gw), _ptr(gb)), "cls_grad")
+                                    _ptr(ws), _ptr(loss), _ptr(gw), _ptr(gb)), "cls_grad")
         self._keep_ft = (w, b)
         return loss, gw, gb
 
     # ---- fine-tuning the box branch on a bank of positive samples (sylph_amd.finetune.finetune_box_branch) ----------------------
     def _box_refuse(self, who: str):
-        from . import distributed as D
-        if D.get_world_size() > 1:
-            raise NotImplementedError(f"{who}: gradients are not reduced across ranks; world size is {D.get_world_size()}")
+        from .finetune import _single_rank
+        _single_rank(who)
         fc = self.fcos_train
         if fc["loc_loss_type"] != "giou":
             raise NotImplementedError(f"{who}: MODEL.FCOS.LOC_LOSS_TYPE \"{fc['loc_loss_type']}\" is not supported (the gradient kernel implements \"giou\")")
@@ -635,20 +646,11 @@ class Engine:
         max_samples rows to write into.  Reads the count back (one sync)."""
         self._stream()
         self._box_refuse("box_samples")
-        bx = torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 4)
-        cl = torch.as_tensor(classes).reshape(-1)
-        im = torch.as_tensor(image_index).reshape(-1)
-        n = bx.shape[0]
-        if cl.numel() != n or im.numel() != n:
-            raise ValueError(f"box_samples: {n} boxes, {cl.numel()} classes and {im.numel()} image indices")
         if getattr(self, "_batch", None) is None:
             raise RuntimeError("box_samples: no current batch")
-        rows, B = self.batch_rows(), self._batch[0]
-        iml = im.tolist()
-        if any(a > b for a, b in zip(iml, iml[1:])):
-            raise ValueError("box_samples: gt_image is not sorted (image_index must not decrease)")
-        if n and (iml[0] < 0 or iml[-1] >= B):
-            raise ValueError(f"box_samples: image_index outside the batch of {B} images")
+        rows = self.batch_rows()
+        bx, cl, im = self._check_gt("box_samples", boxes, classes, image_index)
+        n = bx.shape[0]
         fc = self.fcos_train
         if max_samples is None:
             cap = rows if not (fc["center_sample"] and fc["pos_radius"] <= 1.5) else min(rows, 9 * self.nlevels * n)
@@ -656,9 +658,6 @@ class Engine:
             cap = int(max_samples)
             if cap < 0:
                 raise ValueError("box_samples: max_samples is negative")
-        bx = bx.to(self.device).contiguous()
-        cl = cl.to(self.device, torch.int32).contiguous()
-        im = im.to(self.device, torch.int32).contiguous()
         if out is None:
             patches = torch.empty(cap, 3, 3, 256, device=self.device, dtype=torch.bfloat16)
             targets = torch.empty(cap, 4, device=self.device, dtype=torch.float32)
@@ -704,15 +703,14 @@ class Engine:
         n = samples.n
         need = c_int64(0)
         check(self.L.sylph_box_grad_bytes(self._ctx, n, ctypes.byref(need)), "box_grad_bytes")
-        if self._box_ws is None or self._box_ws.numel() < need.value:
-            self._box_ws = torch.empty(max(need.value, 4), device=self.device, dtype=torch.uint8)
+        ws = self._grow_ws("_box_ws", need.value)
         out = {"sums": torch.empty(4, device=self.device), "grad_w": torch.empty_like(w), "grad_b": torch.empty_like(b),
                "grad_scales": torch.empty_like(s)}
         if debug:
             out["z"] = torch.empty(n, cout, device=self.device)
             out["g"] = torch.empty(n, cout, device=self.device)
         check(self.L.sylph_box_grad(self._ctx, n, _ptr(samples.patches), _ptr(samples.targets), _ptr(samples.info), _ptr(w), _ptr(b), _ptr(s),
-                                    qbits, int(mask), _ptr(self._box_ws), _ptr(out["sums"]), _ptr(out["grad_w"]), _ptr(out["grad_b"]),
+                                    qbits, int(mask), _ptr(ws), _ptr(out["sums"]), _ptr(out["grad_w"]), _ptr(out["grad_b"]),
                                     _ptr(out["grad_scales"]), _ptr(out.get("z")), _ptr(out.get("g"))), "box_grad")
         self._keep_box = (w, b, s, samples)
         return out
@@ -1384,11 +1382,10 @@ class Engine:
         check(self.L.sylph_codegen_train_bytes(self._ctx, len(ix), len(sl), ctypes.byref(need)), "codegen_train_bytes")
         if params.numel() != self.codegen_flat_size():
             raise ValueError(f"codegen_train_forward: params holds {params.numel()} floats, the layout {self.codegen_flat_size()}")
-        if getattr(self, "_cgt_ws", None) is None or self._cgt_ws.numel() < need.value:
-            self._cgt_ws = torch.empty(need.value, device=self.device, dtype=torch.uint8)
+        ws = self._grow_ws("_cgt_ws", need.value)
         codes = torch.empty(len(sl), 257, device=self.device)
         check(self.L.sylph_codegen_train_forward(self._ctx, _ptr(params), _ptr(rows), rows.shape[0], len(ix), _iarr(ix), len(sl), _iarr(sl),
-                                                 _ptr(self._cgt_ws), _ptr(codes)), "codegen_train_forward")
+                                                 _ptr(ws), _ptr(codes)), "codegen_train_forward")
         self._cgt_last = (params, rows, len(ix), len(sl))
         return codes
 

@@ -40,11 +40,46 @@ def step_records(n_records: int, records_per_step: Optional[int], iters: int, se
     return [stream[i * r:(i + 1) * r] for i in range(iters)]
 
 
-class CodeOptimizer:
-    """fp32 master copies of the codes under torch.optim.SGD + MultiStepLR.  `step` takes the gradient SUMS of the step's records and the
-    number of positive locations, divides by max(num_pos, 1) (fcos_outputs.py:651, one rank) and steps.  Rows whose `trainable` entry is
-    False keep their bits: neither the gradient nor weight decay nor momentum moves them (TFA's USE_PRETRAINED_BASE_CLS_LOGITS keeps
-    the base classes fixed this way)."""
+def _single_rank(who: str):
+    """every training entry here steps on one rank's gradients: refused by name under a larger world"""
+    from . import distributed as D
+    if D.get_world_size() > 1:
+        raise NotImplementedError(f"{who}: gradients are not reduced across ranks; world size is {D.get_world_size()}")
+
+
+class MasterSGD:
+    """torch.optim.SGD + MultiStepLR over fp32 master tensors: the shell of CodeOptimizer, BranchOptimizer and GeneratorOptimizer, which
+    add how kernel outputs become `.grad`.  `_freeze(master, frozen)` saves the master as it stands; after every step its elements
+    under the bool mask `frozen` (broadcast against it) get the saved bits back, so neither the gradient nor weight decay nor momentum
+    moves them."""
+
+    def _init_sgd(self, masters, *, lr: float, momentum: float, weight_decay: float, lr_steps: Sequence[int], lr_gamma: float):
+        self._masters = list(masters)
+        self._frozen = []
+        self.opt = torch.optim.SGD(self._masters, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        self.sched = torch.optim.lr_scheduler.MultiStepLR(self.opt, milestones=sorted(int(s) for s in lr_steps), gamma=lr_gamma)
+
+    @property
+    def lr(self) -> float:
+        return self.opt.param_groups[0]["lr"]
+
+    def _freeze(self, master: torch.Tensor, frozen: torch.Tensor):
+        self._frozen.append((master, master.clone(), frozen.to(master.device)))
+
+    def _sgd_step(self, *grads: torch.Tensor):
+        """one gradient per master, in their order: step, schedule, put the frozen elements back"""
+        for p, g in zip(self._masters, grads):
+            p.grad = g
+        self.opt.step()
+        self.sched.step()
+        for p, p0, frozen in self._frozen:
+            p.copy_(torch.where(frozen, p0, p))
+
+
+class CodeOptimizer(MasterSGD):
+    """fp32 master copies of the codes.  `step` takes the gradient SUMS of the step's records and the number of positive locations,
+    divides by max(num_pos, 1) (fcos_outputs.py:651, one rank) and steps.  Rows whose `trainable` entry is False keep their bits (TFA's
+    USE_PRETRAINED_BASE_CLS_LOGITS keeps the base classes fixed this way)."""
 
     def __init__(self, cls_conv: torch.Tensor, cls_bias: Optional[torch.Tensor], *, lr: float, momentum: float = 0.9, weight_decay: float = 1e-4,
                  trainable=None, lr_steps: Sequence[int] = (), lr_gamma: float = 0.1):
@@ -55,34 +90,20 @@ class CodeOptimizer:
         self.b = cls_bias.detach().to(self.w.device, torch.float32).reshape(-1).clone() if cls_bias is not None else None
         if self.b is not None and self.b.numel() != n:
             raise ValueError(f"finetune_class_codes: {self.b.numel()} biases for {n} classes")
-        self.frozen = None
+        self._init_sgd([self.w] + ([self.b] if self.b is not None else []), lr=lr, momentum=momentum, weight_decay=weight_decay,
+                       lr_steps=lr_steps, lr_gamma=lr_gamma)
         if trainable is not None:
             m = torch.as_tensor(trainable, dtype=torch.bool).reshape(-1)
             if m.numel() != n:
                 raise ValueError(f"finetune_class_codes: trainable has {m.numel()} entries for {n} classes")
             if not bool(m.all()):
-                self.frozen = (~m).to(self.w.device)
-                self.w0 = self.w.clone()
-                self.b0 = self.b.clone() if self.b is not None else None
-        params = [self.w] + ([self.b] if self.b is not None else [])
-        self.opt = torch.optim.SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
-        self.sched = torch.optim.lr_scheduler.MultiStepLR(self.opt, milestones=sorted(int(s) for s in lr_steps), gamma=lr_gamma)
-
-    @property
-    def lr(self) -> float:
-        return self.opt.param_groups[0]["lr"]
+                self._freeze(self.w, ~m.reshape(n, 1))
+                if self.b is not None:
+                    self._freeze(self.b, ~m)
 
     def step(self, grad_w_sum: torch.Tensor, grad_b_sum: Optional[torch.Tensor], num_pos: torch.Tensor):
         norm = num_pos.reshape(()).clamp(min=1).to(torch.float32)
-        self.w.grad = grad_w_sum / norm
-        if self.b is not None:
-            self.b.grad = grad_b_sum / norm
-        self.opt.step()
-        self.sched.step()
-        if self.frozen is not None:
-            self.w[self.frozen] = self.w0[self.frozen]
-            if self.b is not None:
-                self.b[self.frozen] = self.b0[self.frozen]
+        self._sgd_step(grad_w_sum / norm, *([grad_b_sum / norm] if self.b is not None else []))
         return norm
 
 
@@ -109,9 +130,7 @@ def finetune_class_codes(engine_or_model, records, annotations, class_codes: Dic
     load_record + cls_grad for each record of the step, gradients summed, divided by max(sum num_pos, 1), one SGD step.  Focal alpha /
     gamma and the target assignment come from cfg.MODEL.FCOS.  Returns (codes, losses): the dict "meta_learn_test_instance" takes, and
     the normalised loss of every step as one device tensor (read it back once, at the end)."""
-    from . import distributed as D
-    if D.get_world_size() > 1:
-        raise NotImplementedError(f"finetune_class_codes: gradients are not reduced across ranks; world size is {D.get_world_size()}")
+    _single_rank("finetune_class_codes")
     eng = getattr(engine_or_model, "engine", engine_or_model)
     w_in, b_in = class_codes["cls_conv"], class_codes.get("cls_bias")
     opt = CodeOptimizer(w_in.to(eng.device), b_in, lr=lr, momentum=momentum, weight_decay=weight_decay, trainable=trainable, lr_steps=lr_steps,
@@ -184,42 +203,30 @@ def box_loss_norms(sums: torch.Tensor, n: int, quality: Sequence[str]):
     return (sums[3].clamp(min=1e-6) if "ctrness" in quality else npos), npos
 
 
-class BranchOptimizer:
-    """fp32 masters of the box branch under torch.optim.SGD + MultiStepLR, as CodeOptimizer keeps the codes.  `step` takes box_grad's
-    un-normalised gradients and the two divisors.  Parts that receive no gradient -- the quality channel BOX_QUALITY does not name, the
-    scales without USE_SCALE -- keep their bits: neither weight decay nor momentum moves them."""
+class BranchOptimizer(MasterSGD):
+    """fp32 masters of the box branch, as CodeOptimizer keeps the codes.  `step` takes box_grad's un-normalised gradients and the two
+    divisors.  Parts that receive no gradient -- the quality channel BOX_QUALITY does not name, the scales without USE_SCALE -- keep
+    their bits."""
 
     def __init__(self, w: torch.Tensor, b: torch.Tensor, scales: torch.Tensor, quality: Sequence[str], *, lr: float, momentum: float = 0.9,
                  weight_decay: float = 1e-4, lr_steps: Sequence[int] = (), lr_gamma: float = 0.1, train_scales: bool = True):
         self.w, self.b, self.s = (t.detach().to(torch.float32).clone() for t in (w, b, scales))
+        self._init_sgd([self.w, self.b, self.s], lr=lr, momentum=momentum, weight_decay=weight_decay, lr_steps=lr_steps, lr_gamma=lr_gamma)
         cout = self.w.shape[0]
         frozen = torch.zeros(cout, dtype=torch.bool)
         if "ctrness" not in quality:
             frozen[4] = True
         if cout > 5 and "iou" not in quality:
             frozen[5] = True
-        self.frozen = frozen.to(self.w.device) if bool(frozen.any()) else None
-        self.train_scales = bool(train_scales)
-        self.w0, self.b0, self.s0 = self.w.clone(), self.b.clone(), self.s.clone()
-        self.opt = torch.optim.SGD([self.w, self.b, self.s], lr=lr, momentum=momentum, weight_decay=weight_decay)
-        self.sched = torch.optim.lr_scheduler.MultiStepLR(self.opt, milestones=sorted(int(v) for v in lr_steps), gamma=lr_gamma)
-
-    @property
-    def lr(self) -> float:
-        return self.opt.param_groups[0]["lr"]
+        if bool(frozen.any()):
+            self._freeze(self.w, frozen.reshape(cout, 1, 1, 1))
+            self._freeze(self.b, frozen)
+        if not train_scales:
+            self._freeze(self.s, torch.ones(1, dtype=torch.bool))
 
     def step(self, grad_w: torch.Tensor, grad_b: torch.Tensor, grad_scales: torch.Tensor, loc_norm: torch.Tensor, num_pos: torch.Tensor):
         div = torch.cat([loc_norm.reshape(1).expand(4), num_pos.reshape(1).expand(self.w.shape[0] - 4)])
-        self.w.grad = grad_w / div.reshape(-1, 1, 1, 1)
-        self.b.grad = grad_b / div
-        self.s.grad = grad_scales / loc_norm
-        self.opt.step()
-        self.sched.step()
-        if self.frozen is not None:
-            self.w[self.frozen] = self.w0[self.frozen]
-            self.b[self.frozen] = self.b0[self.frozen]
-        if not self.train_scales:
-            self.s.copy_(self.s0)
+        self._sgd_step(grad_w / div.reshape(-1, 1, 1, 1), grad_b / div, grad_scales / loc_norm)
 
 
 def finetune_box_branch(engine_or_model, samples, branch: Dict[str, torch.Tensor], *, iters: int, lr: float, momentum: float = 0.9,
@@ -230,9 +237,7 @@ def finetune_box_branch(engine_or_model, samples, branch: Dict[str, torch.Tensor
     fcos_outputs.py:698-738 divides the losses, one SGD step.  BOX_QUALITY / IOU_MASK come from cfg.MODEL.FCOS.  Returns (branch, losses):
     the trained dict (not installed: Engine.set_box_branch does that) and the normalised (loc, ctr, iou) losses of every step as one
     (iters, 3) device tensor."""
-    from . import distributed as D
-    if D.get_world_size() > 1:
-        raise NotImplementedError(f"finetune_box_branch: gradients are not reduced across ranks; world size is {D.get_world_size()}")
+    _single_rank("finetune_box_branch")
     eng = getattr(engine_or_model, "engine", engine_or_model)
     quality = sorted(eng.fcos_train["box_quality"])
     w, b, s = (t.to(eng.device) for t in stack_box_branch(branch))

@@ -16,7 +16,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .finetune import step_records
+from .finetune import MasterSGD, _single_rank, step_records
 
 
 def _ints(v) -> List[int]:
@@ -116,11 +116,10 @@ def clip_scale(total_norm: torch.Tensor, clip_norm: Optional[float]) -> torch.Te
     return (float(clip_norm) / (total_norm + 1e-6)).clamp(max=1.0)
 
 
-class GeneratorOptimizer:
-    """The generator's fp32 master copy as ONE flat device vector under torch.optim.SGD (momentum, weight decay) + MultiStepLR, with
-    gradient clipping by total norm (the recipes set SOLVER.CLIP_GRADIENTS norm 1.0).  `layout` is Engine.codegen_params().  `trainable`:
-    key prefixes; tensors no prefix matches are frozen and keep their bits -- neither the gradient nor weight decay nor momentum moves
-    them, and they do not count in the clipped norm."""
+class GeneratorOptimizer(MasterSGD):
+    """The generator's fp32 master copy as ONE flat device vector, with gradient clipping by total norm (the recipes set
+    SOLVER.CLIP_GRADIENTS norm 1.0).  `layout` is Engine.codegen_params().  `trainable`: key prefixes; tensors no prefix matches are
+    frozen and keep their bits, and they do not count in the clipped norm."""
 
     def __init__(self, flat: torch.Tensor, layout: Sequence[Tuple[str, int, int]], *, lr: float = 5e-4, momentum: float = 0.9,
                  weight_decay: float = 1e-4, lr_steps: Sequence[int] = (), lr_gamma: float = 0.1, clip_norm: Optional[float] = 1.0,
@@ -132,6 +131,7 @@ class GeneratorOptimizer:
         self.layout = [(k, int(o), int(n)) for k, o, n in layout]
         self.clip_norm = clip_norm
         self.mask = None
+        self._init_sgd([self.p], lr=lr, momentum=momentum, weight_decay=weight_decay, lr_steps=lr_steps, lr_gamma=lr_gamma)
         if trainable is not None:
             pre = tuple(trainable)
             m = torch.zeros(total, dtype=torch.bool)
@@ -145,13 +145,7 @@ class GeneratorOptimizer:
                 raise ValueError(f"GeneratorOptimizer: trainable prefix {sorted(set(pre) - hit)} matches no tensor of the layout")
             if not bool(m.all()):
                 self.mask = m.to(self.p.device)
-                self.p0 = self.p.clone()
-        self.opt = torch.optim.SGD([self.p], lr=lr, momentum=momentum, weight_decay=weight_decay)
-        self.sched = torch.optim.lr_scheduler.MultiStepLR(self.opt, milestones=sorted(int(s) for s in lr_steps), gamma=lr_gamma)
-
-    @property
-    def lr(self) -> float:
-        return self.opt.param_groups[0]["lr"]
+                self._freeze(self.p, ~m)
 
     def step(self, grad_sum: torch.Tensor, num_pos: torch.Tensor):
         """grad_sum: the flat gradient of the un-normalised loss sum; divided by max(num_pos, 1) (fcos_outputs.py:651, one rank), clipped, stepped"""
@@ -159,12 +153,7 @@ class GeneratorOptimizer:
         g = grad_sum / norm
         if self.mask is not None:
             g = torch.where(self.mask, g, torch.zeros_like(g))
-        g = g * clip_scale(g.norm(), self.clip_norm)
-        self.p.grad = g
-        self.opt.step()
-        self.sched.step()
-        if self.mask is not None:
-            self.p.copy_(torch.where(self.mask, self.p, self.p0))
+        self._sgd_step(g * clip_scale(g.norm(), self.clip_norm))
         return norm
 
     def state_dict(self, engine=None) -> Dict[str, torch.Tensor]:
@@ -201,9 +190,7 @@ def train_code_generator(engine_or_model, bank: RoiBank, records, annotations, *
     codegen_train_backward; one clipped SGD step.  Starts from the engine's finalized generator (or `init`, a flat vector).  Returns
     (state_dict, losses): the trained tensors under their checkpoint keys (not installed: Engine.set_code_generator does that) and the
     normalised loss of every step as one device tensor."""
-    from . import distributed as D
-    if D.get_world_size() > 1:
-        raise NotImplementedError(f"train_code_generator: gradients are not reduced across ranks; world size is {D.get_world_size()}")
+    _single_rank("train_code_generator")
     _refuse(getattr(engine_or_model, "cfg", None))
     eng = getattr(engine_or_model, "engine", engine_or_model)
     if len(annotations) != len(records):

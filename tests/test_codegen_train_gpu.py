@@ -344,6 +344,41 @@ def test_same_bits_twice_and_on_any_grid(eng2, monkeypatch):
     assert float(out[0][1].abs().max()) > 0
 
 
+def test_third_level_of_the_reduction_tree(monkeypatch):
+    """A depth-1 generator, M = 257 shots over a 12-row bank (repeated indices) in 4 segments: 65 units of 4 shots, so the ordered tree of
+    csrc/partial_sum.h takes three passes at fan-in 8 (65 -> 9 -> 2 -> the final kernel).  The last unit holds ONE shot, the last chunk of
+    the first pass ONE partial, and the second pass reads at the second level's offset.  d W of the tower layer against the float64 sum
+    of the kernel's own exported d y (rounded to bf16, as the kernel rounds it) and x, within _chk's worst-case fp32 bound of R49 + 8
+    roundings -- the bound d W has in _stage_check -- and the whole flat gradient bit-equal under block caps unset, 1 and 3.
+    The class-code and box-branch gradients run the same tree from the same header (fan-in 64): their third level would need more than
+    4096 units, so this test is what pins the level-offset arithmetic for them too."""
+    eng = _engine(1)
+    try:
+        M, seg_len = 257, [64, 64, 64, 65]
+        idx = [(7 * i) % 12 for i in range(M)]
+        shp = eng.codegen_train_shape(M, len(seg_len))
+        assert shp["units"] == 65 and shp["passes"] == 3
+        rows = _bank(12, seed=257).cuda()
+        dev = _params(eng)[0].cuda()
+        lay = eng.codegen_params()
+        G = torch.randn(len(seg_len), 257, generator=torch.Generator().manual_seed(8)).cuda()
+        monkeypatch.delenv("SYLPH_CODEGEN_TRAIN_BLOCKS", raising=False)
+        eng.codegen_train_forward(dev, rows, idx, seg_len)
+        grad, st = eng.codegen_train_backward(G, debug=True)
+        grad = grad.clone()
+        # d W[co][(ci, ky, kx)] = sum over rows of bf16(d y)[row][co] x[row + tap][ci]: one float64 product over the M * 49 rows
+        dyr = R.rbf(_maps(st["d_y0"])).reshape(M, 256, 49).permute(1, 0, 2).reshape(256, M * 49)
+        xu = F.unfold(_maps(rows.cpu()[torch.tensor(idx)]), 3, padding=1).permute(1, 0, 2).reshape(2304, M * 49)
+        got = _unflat(grad.cpu(), lay)[f"{P}.support_set_shared_tower.0.weight"]
+        _chk("d W0", got, dyr @ xu.t(), dyr.abs() @ xu.abs().t(), M * 49 + 8)
+        for cap in ("1", "3"):
+            monkeypatch.setenv("SYLPH_CODEGEN_TRAIN_BLOCKS", cap)
+            eng.codegen_train_forward(dev, rows, idx, seg_len)
+            assert torch.equal(eng.codegen_train_backward(G), grad), f"block cap {cap}: other bits"
+    finally:
+        eng.close()
+
+
 # ------------------------------------------------------------------------------------------------ refusals (host checks, before any launch)
 def test_refusals_by_name(eng2):
     flat, _ = _params(eng2)
